@@ -12,6 +12,14 @@ true architecture (no checkpoints in this environment), fresh N(0,1) latents per
 Prints ONE JSON line on rank 0.  Multi-GPU: the population shards across ranks (weak
 scaling, 64 candidates per GPU) and the only collective is one RCCL all-gather of the
 [P/N, n_obj] fitness rows per step.
+
+A plain run sets up, warms up, times K steps and prints the headline line (metric, value,
+unit, higher_is_better, dtype, ms_per_step); nothing in it is instrumented.  `--full` adds
+what takes runs or passes of its own: the per-kernel roofline (profiled warm-up, dominant
+kernel instrumented in the timed region, one single-stream instrumented pass after it), the
+CPU baseline, the biggan512 / gpt2 legs and the GLASS_BENCH_DETAIL dump.
+`--dump-outputs DIR` writes the fitness rows F of the last timed step to DIR/fitness.npy
+(float32 [P * N, n_obj]); the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -126,6 +134,18 @@ def family_table(iso, step_ms, traffic_rows, top=12):
                 time_weighted_frac_mfma=round(sum(r["frac_mfma"] * r["ms"] for r in rows) / covered, 4) if covered else None,
                 note="one single-stream pass with every launch instrumented (after the timed region); traffic_ratio = stored PMC bytes "
                      "per launch / algorithmic bytes per launch (kernel average over its layers)")
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, **arrays):
+    """--dump-outputs: each array as <path>/<name>.npy in float32 (float64 stays float64), 64 MB at most in all."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_LIMIT_BYTES, "outputs exceed the 64 MB dump limit"
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def cpu_baseline(sd, cfg, target, pop=BATCH, budget_s=150.0, threads=(8, 16, 32, 64, 128)):
@@ -269,6 +289,8 @@ def bench_gpt2(args):
     assert F.shape == (P,) and np.isfinite(F).all()
     assert clock["tok_fail"] == 0, "clip.tokenize refused a decoded text: the timed steps skipped the text tower"
     assert np.abs(F).max() > 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fitness=F)
     dec_ms = clock["dec_gpu_ms"]
     # decode = weight streaming: every fp32 weight of the 12 blocks + the tied lm_head is read once per step
     n_w = 12 * (768 * 2304 + 768 * 768 + 2 * 768 * 3072) + 50257 * 768
@@ -312,7 +334,7 @@ def run_legs(args):
     for name, extra in (("biggan512", ["--warmup", "2", "--no-cpu-baseline"]), ("gpt2", ["--warmup", "1"])):
         t0 = time.time()
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(args.leg_steps), "--no-legs"] + extra,
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(args.leg_steps), "--full", "--no-legs"] + extra,
                                capture_output=True, text=True, timeout=240, env=child_env)
             line = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
             if r.returncode != 0 or not line:
@@ -341,12 +363,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="ffhq", help="model size key (tests/models.py naming); ffhq = the headline")
     ap.add_argument("--pop", type=int, default=POP)
+    ap.add_argument("--full", action="store_true", help="also measure the roofline / per-kernel table, the CPU baseline and the "
+                                                         "biggan512 / gpt2 legs (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's fitness rows to DIR/fitness.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-pop", type=int, default=BATCH, help="candidates in the CPU baseline sample (multiple of 4; 64 = the whole headline population, ~4 min)")
     ap.add_argument("--cpu-baseline-budget", type=float, default=150.0, help="seconds the CPU baseline's sweep + fresh calls may spend (a P = 64 sweep needs ~1500)")
     ap.add_argument("--cpu-baseline-threads", type=int, default=0, help="torch intra-op threads of the CPU baseline (0 = sweep 8/16/32/64/128 and report the best)")
     ap.add_argument("--chunk", type=int, default=0)
-    ap.add_argument("--no-legs", action="store_true", help="headline only: skip the biggan512 / gpt2 legs attached to the default line")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the biggan512 / gpt2 legs attached to the line")
     ap.add_argument("--leg-steps", type=int, default=5)
     args = ap.parse_args()
 
@@ -453,27 +478,33 @@ def main():
     # stream mode of the timed region: 2 = CLIP's image tower on a second stream next to the discriminator (the engine's default),
     # 1 = chunk pipelining (GLASS_OVERLAP=1), 0 = one stream.  Every fully instrumented pass runs on ONE stream.
     mode = 1 if os.environ.get("GLASS_OVERLAP") else (0 if os.environ.get("GLASS_NO_CLIP_OVERLAP") else 2)
-    eng.set_overlap(0)
-    eng.set_profiling(True)
-    warm = {}
-    for s in range(max(args.warmup, 1)):
-        ev.evaluate_local(population(1000 * rank + s, P), generation=s)
-        warm = {}
-        for r in eng.profile():
-            kern = kernel_family(r["name"])
-            a = warm.setdefault(kern, 0.0)
-            warm[kern] = a + r["total_ms"]
-    full_prof = {r["name"]: dict(launches=r["launches"], total_ms=r["total_ms"], flops=r["flops"], bytes=r["bytes"])
-                 for r in eng.profile()}
-    dominant = max(warm.items(), key=lambda kv: kv[1])[0]
-    if os.environ.get("GLASS_BENCH_NOPROF"):
-        eng.set_profiling(False)
-    elif not os.environ.get("GLASS_BENCH_FULLPROF"):
-        eng.set_profile_filter(dominant)
     prof = {}
-    eng.set_overlap(mode)
-    ev.evaluate_local(population(1000 * rank + 99, P), generation=99)     # (one un-timed pass in the timed region's stream mode)
-    eng.profile()
+    if args.full:
+        eng.set_overlap(0)
+        eng.set_profiling(True)
+        warm = {}
+        for s in range(max(args.warmup, 1)):
+            ev.evaluate_local(population(1000 * rank + s, P), generation=s)
+            warm = {}
+            for r in eng.profile():
+                kern = kernel_family(r["name"])
+                a = warm.setdefault(kern, 0.0)
+                warm[kern] = a + r["total_ms"]
+        full_prof = {r["name"]: dict(launches=r["launches"], total_ms=r["total_ms"], flops=r["flops"], bytes=r["bytes"])
+                     for r in eng.profile()}
+        dominant = max(warm.items(), key=lambda kv: kv[1])[0]
+        if os.environ.get("GLASS_BENCH_NOPROF"):
+            eng.set_profiling(False)
+        elif not os.environ.get("GLASS_BENCH_FULLPROF"):
+            eng.set_profile_filter(dominant)
+        eng.set_overlap(mode)
+        ev.evaluate_local(population(1000 * rank + 99, P), generation=99)     # (one un-timed pass in the timed region's stream mode)
+        eng.profile()
+    else:
+        # plain run: the warm-up passes already run in the timed region's stream mode, and no launch is instrumented
+        eng.set_overlap(mode)
+        for s in range(max(args.warmup, 1)):
+            ev.evaluate_local(population(1000 * rank + s, P), generation=s)
     # the K fresh populations are drawn BEFORE the clock starts: drawing synthetic latents (numpy RandomState, ~1-2 ms of host time per
     # 64 x 512 population) is input synthesis, not the hot path — the timed region starts with its inputs ready in host memory and
     # still carries every H2D copy of them (the boundary takes host buffers, include/glass.h)
@@ -484,26 +515,28 @@ def main():
     for s in range(args.steps):
         F_all = ev.evaluate_local(pops[s], generation=100 + s)
         gpu_ms += eng.last_gpu_ms()         # hipEvent pair around the whole pass on the engine's main stream (engine.cpp run_pass)
-        for r in eng.profile():
-            a = prof.setdefault(r["name"], dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
-            for k in a:
-                a[k] += r[k]
+        if args.full:
+            for r in eng.profile():
+                a = prof.setdefault(r["name"], dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
+                for k in a:
+                    a[k] += r[k]
     sync()
     dt = time.perf_counter() - t0
-    eng.set_profiling(False)
-    # one extra pass OUTSIDE the timed region, single stream + every launch instrumented: clean per-kernel
-    # durations (in the timed region kernels of the two streams co-run and stretch each other)
-    eng.set_overlap(0)
-    eng.set_profile_filter("")
-    eng.set_profiling(True)
-    ev.evaluate_local(population(1000 * rank + 500, P), generation=500)
-    iso = {}
-    for r in eng.profile():
-        kk = r["name"].split("@")[1] if "@" in r["name"] else r["name"]
-        a3 = iso.setdefault(kk, dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
-        for k3 in a3:
-            a3[k3] += r[k3]
-    eng.set_profiling(False)
+    if args.full:
+        eng.set_profiling(False)
+        # one extra pass OUTSIDE the timed region, single stream + every launch instrumented: clean per-kernel
+        # durations (in the timed region kernels of the two streams co-run and stretch each other)
+        eng.set_overlap(0)
+        eng.set_profile_filter("")
+        eng.set_profiling(True)
+        ev.evaluate_local(population(1000 * rank + 500, P), generation=500)
+        iso = {}
+        for r in eng.profile():
+            kk = r["name"].split("@")[1] if "@" in r["name"] else r["name"]
+            a3 = iso.setdefault(kk, dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
+            for k3 in a3:
+                a3[k3] += r[k3]
+        eng.set_profiling(False)
     if dist is not None:
         tt = torch.tensor([dt], device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -511,72 +544,73 @@ def main():
     assert F_all.shape == (P * world, n_obj) and np.isfinite(F_all).all()
 
     if rank == 0:
-        # dominant kernel = the SOURCE kernel (all its template instances) with the largest share of device time
-        iso_fam = {}
-        for k3, v3 in iso.items():
-            a4 = iso_fam.setdefault(k3.split("<")[0], dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
-            for k4 in a4:
-                a4[k4] += v3[k4]
-        by_kernel = {}
-        for name, a in prof.items():
-            kern = kernel_family(name)
-            b = by_kernel.setdefault(kern, dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
-            for k in b:
-                b[k] += a[k]
-        if not by_kernel:
-            by_kernel = {"(profiling off)": dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0)}
-        kern, a = max(by_kernel.items(), key=lambda kv: kv[1]["total_ms"])
-        secs = a["total_ms"] * 1e-3
-        tf = a["flops"] / secs / 1e12 if secs > 0 else 0.0          # algorithmic FLOP of its launches / their duration
-        gbs = a["bytes"] / secs / 1e9 if secs > 0 else 0.0          # algorithmic bytes (in + out maps + weights)
-        warm_total = sum(warm.values())
-        total_ms = sum(v["total_ms"] for v in full_prof.values())
-        total_flops = sum(v["flops"] for v in full_prof.values())
-        # the roof that binds = the one the kernel sits closer to (the same kernel runs
-        # MFMA-bound mid-resolution layers and HBM-bound 512^2/1024^2 layers)
-        frac_mfma, frac_hbm = tf / MFMA_PEAK_TFLOPS, gbs / HBM_PEAK_GBS
-        # `traffic`: NOT measured in this run — the counters need their own rocprofv3 --pmc passes (tools/measure_traffic.sh: one
-        # FETCH_SIZE and one WRITE_SIZE pass of this same command, every launch at the full population); the stored table is
-        # profiles/traffic_latest.json and the line says so
-        traffic, traffic_src = None, None
-        tname = "traffic_latest_biggan512.json" if biggan else "traffic_latest.json"
-        tpath = os.path.join(ROOT, "profiles", tname)
-        traffic_rows = json.load(open(tpath)).get("per_kernel", {}) if os.path.exists(tpath) else {}
-        if traffic_rows:
-            row = match_family(kern, traffic_rows)
-            if row:
-                traffic = row["bytes_per_launch"]
-                traffic_src = ("stored rocprofv3 --pmc passes (FETCH_SIZE x 2 + WRITE_SIZE, tools/measure_traffic.sh -> profiles/%s), "
-                               "average over this kernel's %d launches at P = %d; not collected by this run" % (tname, row["launches"], P))
-        if frac_hbm > frac_mfma:
-            roofline = dict(bound="hbm", achieved=gbs, peak=HBM_PEAK_GBS, unit="GB/s", frac=frac_hbm)
-        else:
-            roofline = dict(bound="mfma", achieved=tf, peak=MFMA_PEAK_TFLOPS, unit="TFLOP/s", frac=frac_mfma)
-        alg_bpl = a["bytes"] / max(a["launches"], 1)
-        roofline.update(kernel=kern, launches=a["launches"], avg_ms=a["total_ms"] / max(a["launches"], 1), traffic=traffic,
-                        traffic_source=traffic_src, traffic_ratio=(traffic / alg_bpl if traffic and alg_bpl else None),
-                        algorithmic_tflops=tf, algorithmic_gbs=gbs, frac_of_mfma_peak=frac_mfma, frac_of_hbm_peak=frac_hbm,
-                        algorithmic_bytes_per_launch=a["bytes"] / max(a["launches"], 1),
-                        algorithmic_flop_per_launch=a["flops"] / max(a["launches"], 1),
-                        share_of_gpu_time=warm.get(kern, 0.0) / warm_total if warm_total else None,
-                        instances=sorted(k for k in iso if k.split("<")[0] == kern),
-                        isolated=(dict(avg_ms=iso_fam[kern]["total_ms"] / max(iso_fam[kern]["launches"], 1),
-                                       algorithmic_tflops=iso_fam[kern]["flops"] / (iso_fam[kern]["total_ms"] * 1e-3) / 1e12,
-                                       algorithmic_gbs=iso_fam[kern]["bytes"] / (iso_fam[kern]["total_ms"] * 1e-3) / 1e9,
-                                       note="same kernel, one extra single-stream pass after the timed region")
-                                  if kern in iso_fam and iso_fam[kern]["total_ms"] > 0 else None),
-                        concurrency={0: "single stream",
-                                     1: "two HIP streams (GLASS_OVERLAP=1): durations include co-running kernels",
-                                     2: "G and D on one stream; CLIP's image tower on a second stream next to D (G launches never "
-                                        "have a co-runner, D launches may; `isolated` = one-stream pass)"}[mode],
-                        # whole pass: algorithmic FLOP of one population (the reference's op count: every launch's tag) over the
-                        # TIMED region's ms_per_step (driver-comparable) — and over the instrumented one-stream pass for reference
-                        whole_pass_tflops=total_flops / (dt / args.steps) / 1e12,
-                        whole_pass_frac_of_mfma_peak=total_flops / (dt / args.steps) / 1e12 / MFMA_PEAK_TFLOPS,
-                        whole_pass_algorithmic_gflop_per_candidate=total_flops / P / 1e9,
-                        families=family_table(iso, dt / args.steps * 1e3, traffic_rows),
-                        instrumented_pass_ms=total_ms,
-                        instrumented_pass_frac_of_mfma_peak=(total_flops / (total_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS) if total_ms else None)
+        if args.full:
+            # dominant kernel = the SOURCE kernel (all its template instances) with the largest share of device time
+            iso_fam = {}
+            for k3, v3 in iso.items():
+                a4 = iso_fam.setdefault(k3.split("<")[0], dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
+                for k4 in a4:
+                    a4[k4] += v3[k4]
+            by_kernel = {}
+            for name, a in prof.items():
+                kern = kernel_family(name)
+                b = by_kernel.setdefault(kern, dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
+                for k in b:
+                    b[k] += a[k]
+            if not by_kernel:
+                by_kernel = {"(profiling off)": dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0)}
+            kern, a = max(by_kernel.items(), key=lambda kv: kv[1]["total_ms"])
+            secs = a["total_ms"] * 1e-3
+            tf = a["flops"] / secs / 1e12 if secs > 0 else 0.0          # algorithmic FLOP of its launches / their duration
+            gbs = a["bytes"] / secs / 1e9 if secs > 0 else 0.0          # algorithmic bytes (in + out maps + weights)
+            warm_total = sum(warm.values())
+            total_ms = sum(v["total_ms"] for v in full_prof.values())
+            total_flops = sum(v["flops"] for v in full_prof.values())
+            # the roof that binds = the one the kernel sits closer to (the same kernel runs
+            # MFMA-bound mid-resolution layers and HBM-bound 512^2/1024^2 layers)
+            frac_mfma, frac_hbm = tf / MFMA_PEAK_TFLOPS, gbs / HBM_PEAK_GBS
+            # `traffic`: NOT measured in this run — the counters need their own rocprofv3 --pmc passes (tools/measure_traffic.sh: one
+            # FETCH_SIZE and one WRITE_SIZE pass of this same command, every launch at the full population); the stored table is
+            # profiles/traffic_latest.json and the line says so
+            traffic, traffic_src = None, None
+            tname = "traffic_latest_biggan512.json" if biggan else "traffic_latest.json"
+            tpath = os.path.join(ROOT, "profiles", tname)
+            traffic_rows = json.load(open(tpath)).get("per_kernel", {}) if os.path.exists(tpath) else {}
+            if traffic_rows:
+                row = match_family(kern, traffic_rows)
+                if row:
+                    traffic = row["bytes_per_launch"]
+                    traffic_src = ("stored rocprofv3 --pmc passes (FETCH_SIZE x 2 + WRITE_SIZE, tools/measure_traffic.sh -> profiles/%s), "
+                                   "average over this kernel's %d launches at P = %d; not collected by this run" % (tname, row["launches"], P))
+            if frac_hbm > frac_mfma:
+                roofline = dict(bound="hbm", achieved=gbs, peak=HBM_PEAK_GBS, unit="GB/s", frac=frac_hbm)
+            else:
+                roofline = dict(bound="mfma", achieved=tf, peak=MFMA_PEAK_TFLOPS, unit="TFLOP/s", frac=frac_mfma)
+            alg_bpl = a["bytes"] / max(a["launches"], 1)
+            roofline.update(kernel=kern, launches=a["launches"], avg_ms=a["total_ms"] / max(a["launches"], 1), traffic=traffic,
+                            traffic_source=traffic_src, traffic_ratio=(traffic / alg_bpl if traffic and alg_bpl else None),
+                            algorithmic_tflops=tf, algorithmic_gbs=gbs, frac_of_mfma_peak=frac_mfma, frac_of_hbm_peak=frac_hbm,
+                            algorithmic_bytes_per_launch=a["bytes"] / max(a["launches"], 1),
+                            algorithmic_flop_per_launch=a["flops"] / max(a["launches"], 1),
+                            share_of_gpu_time=warm.get(kern, 0.0) / warm_total if warm_total else None,
+                            instances=sorted(k for k in iso if k.split("<")[0] == kern),
+                            isolated=(dict(avg_ms=iso_fam[kern]["total_ms"] / max(iso_fam[kern]["launches"], 1),
+                                           algorithmic_tflops=iso_fam[kern]["flops"] / (iso_fam[kern]["total_ms"] * 1e-3) / 1e12,
+                                           algorithmic_gbs=iso_fam[kern]["bytes"] / (iso_fam[kern]["total_ms"] * 1e-3) / 1e9,
+                                           note="same kernel, one extra single-stream pass after the timed region")
+                                      if kern in iso_fam and iso_fam[kern]["total_ms"] > 0 else None),
+                            concurrency={0: "single stream",
+                                         1: "two HIP streams (GLASS_OVERLAP=1): durations include co-running kernels",
+                                         2: "G and D on one stream; CLIP's image tower on a second stream next to D (G launches never "
+                                            "have a co-runner, D launches may; `isolated` = one-stream pass)"}[mode],
+                            # whole pass: algorithmic FLOP of one population (the reference's op count: every launch's tag) over the
+                            # TIMED region's ms_per_step (driver-comparable) — and over the instrumented one-stream pass for reference
+                            whole_pass_tflops=total_flops / (dt / args.steps) / 1e12,
+                            whole_pass_frac_of_mfma_peak=total_flops / (dt / args.steps) / 1e12 / MFMA_PEAK_TFLOPS,
+                            whole_pass_algorithmic_gflop_per_candidate=total_flops / P / 1e9,
+                            families=family_table(iso, dt / args.steps * 1e3, traffic_rows),
+                            instrumented_pass_ms=total_ms,
+                            instrumented_pass_frac_of_mfma_peak=(total_flops / (total_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS) if total_ms else None)
         if biggan:
             metric = "candidate latents scored/sec (GAN→CLIP fitness), DeepMindBigGAN512 pop=%d" % P
             workload = ("DeepMindBigGAN512: BigGAN-deep 512px G + CLIP ViT-B/32, pop=%d per GPU, batch_size=%d, n_obj=1" % (P, BATCH))
@@ -589,28 +623,31 @@ def main():
                    scaling="weak", vs_baseline=None, dtype="f16", data="synthetic",
                    config=dict(workload=workload, pop_per_gpu=P, global_pop=P * world, batch_size=BATCH, parallelism="population-shard x%d" % world,
                                device="%(name)s, %(cus)d CUs" % device_info(local_rank), hbm_gib=round(device_info(local_rank)["hbm_bytes"] / 2 ** 30)),
-                   roofline=roofline,
                    # device time of the timed region = sum over its steps of the hipEvent interval around each pass (H2D of the latents
                    # ... D2H of F): checkable against `ms_per_step` even when an smi sampler misses the ~1 s window
                    gpu_active_s=gpu_ms * 1e-3, gpu_active_frac_of_timed_region=gpu_ms * 1e-3 / dt)
-        if world == 1 and not args.no_cpu_baseline and not biggan:
-            out["cpu_baseline"] = cpu_baseline(sd, cfg, target, pop=max(BATCH, args.cpu_baseline_pop // BATCH * BATCH), budget_s=args.cpu_baseline_budget,
-                                               threads=((args.cpu_baseline_threads,) if args.cpu_baseline_threads else (8, 16, 32, 64, 128)))
-        if world == 1 and args.config == "ffhq" and not args.no_legs and dist is None:
-            # the other single-GPU configs of BASELINE.json (configs[2] DeepMindBigGAN512, configs[4] GPT2) as short legs of the
-            # same driver-run line, each with its own roofline; the headline engine is closed first
-            eng.close()
-            out["legs"] = run_legs(args)
-        if os.environ.get("GLASS_BENCH_DETAIL"):
-            with open(os.environ["GLASS_BENCH_DETAIL"], "w") as f:
-                wk = {}
-                for name, a2 in full_prof.items():
-                    kk = name.split("@")[1] if "@" in name else name
-                    b2 = wk.setdefault(kk, dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
-                    for k2 in b2:
-                        b2[k2] += a2[k2]
-                json.dump(dict(per_tag=full_prof, per_kernel=wk, seconds=dt / args.steps, note="per_tag/per_kernel: ONE fully "
-                               "instrumented warm-up pass; timed region instruments only the dominant kernel"), f, indent=1)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, fitness=F_all)
+        if args.full:
+            out["roofline"] = roofline
+            if world == 1 and not args.no_cpu_baseline and not biggan:
+                out["cpu_baseline"] = cpu_baseline(sd, cfg, target, pop=max(BATCH, args.cpu_baseline_pop // BATCH * BATCH), budget_s=args.cpu_baseline_budget,
+                                                   threads=((args.cpu_baseline_threads,) if args.cpu_baseline_threads else (8, 16, 32, 64, 128)))
+            if world == 1 and args.config == "ffhq" and not args.no_legs and dist is None:
+                # the other single-GPU configs of BASELINE.json (configs[2] DeepMindBigGAN512, configs[4] GPT2) as short legs of the
+                # same driver-run line, each with its own roofline; the headline engine is closed first
+                eng.close()
+                out["legs"] = run_legs(args)
+            if os.environ.get("GLASS_BENCH_DETAIL"):
+                with open(os.environ["GLASS_BENCH_DETAIL"], "w") as f:
+                    wk = {}
+                    for name, a2 in full_prof.items():
+                        kk = name.split("@")[1] if "@" in name else name
+                        b2 = wk.setdefault(kk, dict(launches=0, total_ms=0.0, flops=0.0, bytes=0.0))
+                        for k2 in b2:
+                            b2[k2] += a2[k2]
+                    json.dump(dict(per_tag=full_prof, per_kernel=wk, seconds=dt / args.steps, note="per_tag/per_kernel: ONE fully "
+                                   "instrumented warm-up pass; timed region instruments only the dominant kernel"), f, indent=1)
         if json_fd is not None:
             os.write(json_fd, (json.dumps(out) + "\n").encode())
         else:

@@ -138,10 +138,9 @@ def test_oracle_reproduces_reference_text_tower_full_size():
 
 
 def test_clip_tokenizer_reproduces_text_fixture_tokens():
-    """Own BPE (clip_glass_amd/tokenizer.py) on the fixture's eight texts == the ids the reference tokenizer wrote into it."""
-    bpe = "/root/reference/assets/bpe_simple_vocab_16e6.txt.gz"
-    if not os.path.exists(bpe):
-        pytest.skip("reference BPE asset not present")
+    """Own BPE (clip_glass_amd/tokenizer.py) on the fixture's eight texts == the ids the reference tokenizer wrote into it; merge
+    table: the reference's, cut down to what the tests' texts reach (clip_bpe_subset.txt.gz, same ranks and ids)."""
+    bpe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clip_bpe_subset.txt.gz")
     from clip_glass_amd.tokenizer import ClipTokenizer
     g = _load("clip_text_full.npz")
     ids = ClipTokenizer(bpe).tokenize([str(t) for t in g["texts"]])

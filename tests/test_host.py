@@ -397,10 +397,10 @@ def test_generation_problem_two_process_gloo():
 
 
 def test_clip_tokenizer_matches_reference_known_answers():
-    """Own BPE implementation vs the reference tokenizer (needs the reference's merges asset)."""
-    bpe = "/root/reference/assets/bpe_simple_vocab_16e6.txt.gz"
-    if not os.path.exists(bpe):
-        pytest.skip("reference BPE asset not present")
+    """Own BPE implementation vs the reference tokenizer's ids (tests/golden/clip_bpe_texts.npz), on the reference's merge table
+    cut down to what these texts reach (tests/golden/clip_bpe_subset.txt.gz, same ranks and ids; tests/golden/make_bpe_fixture.py)."""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    bpe = os.path.join(golden, "clip_bpe_subset.txt.gz")
     from clip_glass_amd.tokenizer import ClipTokenizer
     tok = ClipTokenizer(bpe)
     ids = tok.tokenize(["a wolf at night with the moon in the background"])
@@ -415,6 +415,8 @@ def test_clip_tokenizer_matches_reference_known_answers():
     texts = ["A photo of  a CAT!!", "it's 42 degrees & sunny -- don't you think?", "naïve café façade", "x" * 10,
              "the quick brown fox jumps over the lazy dog, twice.", "&amp; html &lt;escapes&gt;"]
     mine = tok.tokenize(texts)
+    g = np.load(os.path.join(golden, "clip_bpe_texts.npz"))
+    np.testing.assert_array_equal(mine, g["tokens"][[list(g["texts"]).index(t) for t in texts]])
     if ref_tok is not None:
         np.testing.assert_array_equal(mine, ref_tok(texts).numpy())
     with pytest.raises(RuntimeError, match="too long"):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of environment knobs on ONE box: tools/ab_bench.sh <out_dir> "<name>:<ENV=1 ENV2=..>" ...   (name "base": no knobs)
-# Each variant: python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-legs, JSON line + per-layer table under <out_dir>/.
+# Each variant: python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-legs, JSON line + per-layer table under <out_dir>/.
 # Knobs only exist in the developer build (`make -C clip_glass_amd/csrc AB=1` -> tools/lib/libglass_ab.so): every variant that names a
 # knob runs on it (GLASS_LIB), "base" runs on the release library — so a knob run also A/Bs the two builds against each other.
 out=$1; shift
@@ -15,7 +15,7 @@ for spec in "$@"; do
     [ -f "$ablib" ] || { echo "  $ablib missing: make -C clip_glass_amd/csrc AB=1" | tee -a "$out/summary.txt"; continue; }
     envs="GLASS_LIB=$ablib $envs"
   fi
-  env $envs GLASS_BENCH_DETAIL="$out/detail_$name.json" timeout 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-legs > "$out/bench_$name.json" 2> "$out/bench_$name.err"
+  env $envs GLASS_BENCH_DETAIL="$out/detail_$name.json" timeout 600 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-legs > "$out/bench_$name.json" 2> "$out/bench_$name.err"
   python - "$out/bench_$name.json" <<'PY' | tee -a "$out/summary.txt"
 import json, sys
 try:

@@ -14,7 +14,7 @@ mkdir -p $OUT
 # dispatches are then its P = 64 launches only
 # (GLASS_NO_CLIP_OVERLAP is read by bench.py, which calls glass_engine_set_overlap(0): the release library itself reads no environment)
 export GLASS_NO_CLIP_OVERLAP=1 GLASS_BENCH_NOPROF=1 GLASS_BENCH_UNIFORM_POP=1
-ARGS="--config $CFG --steps 1 --warmup 1 --no-cpu-baseline --no-legs"
+ARGS="--full --config $CFG --steps 1 --warmup 1 --no-cpu-baseline --no-legs"
 timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT -o fetch -- python bench.py $ARGS > /dev/null 2> $OUT/fetch.err
 timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT -o write -- python bench.py $ARGS > /dev/null 2> $OUT/write.err
 python tools/traffic_table.py $OUT/fetch_counter_collection.csv $OUT/write_counter_collection.csv > $OUT/traffic.json
