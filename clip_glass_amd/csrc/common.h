@@ -33,6 +33,18 @@ __device__ __forceinline__ f16x mfma32(h8 a, h8 b, f16x c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ int mfma32_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+// Philox4x32-10 (counter c, key {k0, k1}) in place — the noise planes (kernels_misc.hip) and the GPT-2 sampler (gpt2.hip);
+// numpy mirror: synth.philox4x32
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint64_t p0 = (uint64_t)c[0] * 0xD2511F53ull, p1 = (uint64_t)c[2] * 0xCD9E8D57ull;
+        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
 
 // ---- toRGB applied to a wave's output tile while it is still in registers (conv_stream / conv_tiled / conv_glds) -------------
 // The activated fp16 quads a lane holds after the epilogue math (lane (px, kh): channels j*32 + 8g + 4kh + q of pixel px) are a

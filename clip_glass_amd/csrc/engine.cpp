@@ -1697,12 +1697,13 @@ static void gpt2_work_free(glass_engine* e) {
     auto& w = e->gwork;
     if (w.exec) hipGraphExecDestroy(w.exec);
     if (w.graph) hipGraphDestroy(w.graph);
-    hipFree(w.d_tok); hipFree(w.d_gen); hipFree(w.d_state); hipFree(w.x); hipFree(w.ln); hipFree(w.qkv); hipFree(w.att); hipFree(w.hid);
+    hipFree(w.d_tok); hipFree(w.d_gen); hipFree(w.d_state); hipFree(w.d_samp); hipFree(w.x); hipFree(w.ln); hipFree(w.qkv); hipFree(w.att); hipFree(w.hid);
     hipFree(w.last); hipFree(w.logits); hipFree(w.kc); hipFree(w.vc); hipFree(w.part); hipFree(w.stats); hipFree(w.pairs); hipFree(w.pst);
     w = glass_engine::Gpt2Work();
 }
 
-static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length, int32_t* out_tokens);
+static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length, int32_t* out_tokens,
+                             const int32_t* samp);
 
 // Sequences are independent, and the single-token step kernels hold at most 64 rows: a longer population is decoded in row groups of
 // 64, each through exactly the launches a 64-row call makes — a row's tokens do not depend on how many rows the call (or a shard) holds.
@@ -1712,7 +1713,7 @@ extern "C" int glass_engine_gpt2_decode(glass_engine* e, const int32_t* context,
     float total_ms = 0.f;
     for (int g0 = 0; g0 < P; g0 += 64) {
         const int rc = gpt2_decode_group(e, context + (size_t)g0 * nctx, std::min(64, P - g0), nctx, length,
-                                         out_tokens + (size_t)g0 * (nctx + length));
+                                         out_tokens + (size_t)g0 * (nctx + length), nullptr);
         if (rc) return rc;
         total_ms += e->gwork.last_ms;
     }
@@ -1721,7 +1722,40 @@ extern "C" int glass_engine_gpt2_decode(glass_engine* e, const int32_t* context,
     return GLASS_OK;
 }
 
-static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length, int32_t* out_tokens) {
+// Stochastic decode: the same row groups, each group's first global row in the sampler's words — a row's draws depend on its global index,
+// the step, (seed, generation, purpose) and its own logits only.
+extern "C" int glass_engine_gpt2_sample(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length, float temperature,
+                                        int32_t top_k, uint64_t seed, int32_t generation, int32_t first_row, int32_t purpose,
+                                        int32_t* out_tokens) {
+    REQUIRE(e && context && out_tokens && P > 0 && nctx > 0 && length > 0, GLASS_ERR_ARG, "bad argument");
+    REQUIRE(temperature > 0.f && temperature < INFINITY, GLASS_ERR_ARG, "temperature must be a finite value > 0");
+    REQUIRE(top_k >= 0 && top_k <= GPT2_SAMPLE_TOPK_MAX, GLASS_ERR_ARG, "top_k must lie in [0, 256]");
+    REQUIRE(first_row >= 0 && (long long)first_row + P <= 0x7fffffffLL, GLASS_ERR_ARG, "first_row out of range");
+    REQUIRE(e->g_wte == nullptr || gpt2_sample_supported(e->g_vocab), GLASS_ERR_ARG, "vocabulary too large for the sampler (> 131072)");
+    float total_ms = 0.f;
+    for (int g0 = 0; g0 < P; g0 += 64) {
+        int32_t samp[GPT2_SP_WORDS];
+        samp[GPT2_SP_SEED_LO] = (int32_t)(uint32_t)(seed & 0xFFFFFFFFu);
+        samp[GPT2_SP_SEED_HI] = (int32_t)(uint32_t)(seed >> 32);
+        samp[GPT2_SP_GEN] = generation;
+        samp[GPT2_SP_ROW0] = first_row + g0;
+        samp[GPT2_SP_PURPOSE] = purpose;
+        memcpy(&samp[GPT2_SP_TEMP], &temperature, sizeof(float));
+        samp[GPT2_SP_TOPK] = top_k;
+        samp[GPT2_SP_STEP] = 0;
+        const int rc = gpt2_decode_group(e, context + (size_t)g0 * nctx, std::min(64, P - g0), nctx, length,
+                                         out_tokens + (size_t)g0 * (nctx + length), samp);
+        if (rc) return rc;
+        total_ms += e->gwork.last_ms;
+    }
+    e->gwork.last_ms = total_ms;
+    e->last_ms = total_ms;
+    return GLASS_OK;
+}
+
+// samp: the sampler's GPT2_SP_* words (host), nullptr = greedy
+static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length, int32_t* out_tokens,
+                             const int32_t* samp) {
     REQUIRE(e && context && out_tokens && P > 0 && nctx > 0 && length > 0, GLASS_ERR_ARG, "bad argument");
     REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
     REQUIRE(e->g_wte != nullptr, GLASS_ERR_STATE, "GPT-2 weights were not loaded (gpt2.transformer.*)");
@@ -1745,6 +1779,7 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
         hipError_t err = hipMalloc(&w.d_tok, rows * sizeof(int));
         if (err == hipSuccess) err = hipMalloc(&w.d_gen, (size_t)P * length * sizeof(int));
         if (err == hipSuccess) err = hipMalloc(&w.d_state, 3 * sizeof(int));      // {past length, step index, ticket counter of the fused step tail}
+        if (err == hipSuccess) err = hipMalloc(&w.d_samp, GPT2_SP_WORDS * sizeof(int));
         if (err == hipSuccess) err = hipMalloc(&w.x, rows * D * sizeof(float));
         if (err == hipSuccess) err = hipMalloc(&w.ln, rows * D * sizeof(float));
         if (err == hipSuccess) err = hipMalloc(&w.qkv, rows * 3 * D * sizeof(float));
@@ -1764,6 +1799,13 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
             return GLASS_ERR_NOMEM;
         }
         w.P = P; w.nctx = nctx; w.length = length;
+    }
+    // the captured step graph belongs to the mode it was recorded in: greedy never replays a sampling step, nor the reverse
+    const int sample = samp ? 1 : 0;
+    if (w.sample != sample) {
+        if (w.exec) { hipGraphExecDestroy(w.exec); w.exec = nullptr; }
+        if (w.graph) { hipGraphDestroy(w.graph); w.graph = nullptr; }
+        w.sample = sample;
     }
     // one transformer pass over `nd` new positions per sequence; step_state != nullptr: single-token step whose past length /
     // step index are read from device memory (the form that is captured into a hipGraph and replayed)
@@ -1821,16 +1863,25 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
                 launch_gpt2_finalize(S > 1 ? w.part : nullptr, S, b.b_pr, w.x, P, D, w.stats, st);      // residual + next LayerNorm's statistics
             }
             if (tail_fused) {
-                step_refused |= !launch_gpt2_head_tail(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.pairs, w.d_gen, w.d_state, e->g_wte, e->g_wpe,
-                                                       w.x, w.stats, st);
+                if (samp)       // the sampling twin: logits written too, the sampler from the pairs, the same embed / advance tail
+                    step_refused |= !launch_gpt2_head_sample(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.logits, w.pairs, w.d_samp,
+                                                             w.d_gen, w.d_state, true, e->g_wte, e->g_wpe, w.x, w.stats, st);
+                else
+                    step_refused |= !launch_gpt2_head_tail(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.pairs, w.d_gen, w.d_state, e->g_wte,
+                                                           e->g_wpe, w.x, w.stats, st);
                 return;
             }
-            if (no_head || !launch_gpt2_head(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, nullptr, w.pairs, w.d_gen, w.d_state, st)) {
+            const bool head = !no_head && (samp ? launch_gpt2_head_sample(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.logits, w.pairs,
+                                                                          w.d_samp, w.d_gen, w.d_state, false, nullptr, nullptr, nullptr, nullptr, st)
+                                                : launch_gpt2_head(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, nullptr, w.pairs, w.d_gen,
+                                                                   w.d_state, st));
+            if (!head) {
                 // ln_f fused; the real vocabulary (1571 column blocks) is never split, a small one may be
                 const int S = launch_gemm_f32_step(w.x, e->g_wte, nullptr, w.logits, P, V, D, D, V, 0, st, w.part, w.part_elems, w.stats, e->g_lnf_g, e->g_lnf_b);
                 step_refused |= S == 0;
                 if (S > 1) launch_gpt2_reduce(w.part, S, nullptr, w.logits, P, V, V, 0, st);
-                launch_argmax(w.logits, P, V, w.d_gen, st, w.d_state, w.stats + 2 * P);
+                if (samp) launch_gpt2_sample(w.logits, P, V, w.d_samp, w.d_gen, w.d_state, st);
+                else launch_argmax(w.logits, P, V, w.d_gen, st, w.d_state, w.stats + 2 * P);
             }
             launch_gpt2_advance(w.d_state, st);
             return;
@@ -1850,7 +1901,8 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
         // ln_f on the last position of each sequence, tied lm_head, greedy pick -> d_gen[step][P]
         launch_layernorm(w.x + (size_t)(nd - 1) * D, (long long)nd * D, P, D, e->g_lnf_g, e->g_lnf_b, nullptr, w.last, st);
         launch_gemm_f32(w.last, e->g_wte, nullptr, w.logits, P, V, D, D, V, 0, st, w.part, w.part_elems);
-        launch_argmax(w.logits, P, V, w.d_gen, st, w.d_state, w.stats + 2 * P);
+        if (samp) launch_gpt2_sample(w.logits, P, V, w.d_samp, w.d_gen, w.d_state, st);
+        else launch_argmax(w.logits, P, V, w.d_gen, st, w.d_state, w.stats + 2 * P);
         launch_gpt2_advance(w.d_state, st);
     };
     std::vector<int32_t> gen((size_t)P * length);
@@ -1858,6 +1910,7 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
     hipMemcpyAsync(w.d_tok, context, rows * sizeof(int), hipMemcpyHostToDevice, st);
     const int state0[3] = {0, 0, 0}, state1[3] = {nctx, 1, 0};
     hipMemcpyAsync(w.d_state, state0, sizeof state0, hipMemcpyHostToDevice, st);
+    if (samp) hipMemcpyAsync(w.d_samp, samp, GPT2_SP_WORDS * sizeof(int), hipMemcpyHostToDevice, st);
     pass(nctx, 0, nullptr);                                 // prefill = step 0 (writes d_gen[0 .. P))
     hipMemcpyAsync(w.d_state, state1, sizeof state1, hipMemcpyHostToDevice, st);
     if (tail_fused && length > 1) launch_gpt2_embed_step(w.d_gen, w.d_state, P, e->g_wte, e->g_wpe, D, w.x, st, w.stats);   // step 1's embedding (later ones: the step tail)

@@ -138,7 +138,8 @@ struct glass_engine {
     // decode workspace, kept between calls (one geometry at a time): buffers + the captured single-token step
     struct Gpt2Work {
         int P = 0, nctx = 0, length = 0;
-        int *d_tok = nullptr, *d_gen = nullptr, *d_state = nullptr;
+        int *d_tok = nullptr, *d_gen = nullptr, *d_state = nullptr, *d_samp = nullptr;   // d_samp: the sampler's per-call words (GPT2_SP_*)
+        int sample = 0;           // mode the captured step graph was recorded in: 0 greedy, 1 stochastic
         float *x = nullptr, *ln = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *last = nullptr, *logits = nullptr,
               *kc = nullptr, *vc = nullptr, *part = nullptr, *stats = nullptr, *pairs = nullptr, *pst = nullptr;   // stats: [P][2] LayerNorm {mean, rstd} of the fused step
         size_t part_elems = 0;

@@ -662,36 +662,13 @@ __global__ __launch_bounds__(256) void argmax_pairs_kernel(const float* pv, cons
     }
     if (threadIdx.x == 0) out[(step_dev ? (long long)step_dev[1] * gridDim.x : 0) + blockIdx.x] = bi[0];
 }
-// stage 2 + the NEXT step's first kernel + the state update in one launch (round 4: a launch is ~4 us of dispatch whatever it does): the
-// row's token goes to gen[step][row], its embedding at position past + 1 and the first layer's LayerNorm statistics are left exactly as
-// gpt2_embed_step_kernel would leave them at the top of the next step (same arithmetic), and the LAST workgroup to get here advances
-// {past, step} — every workgroup has read the state before it takes its ticket.  state[2] is the ticket counter (zero between launches).
-__global__ __launch_bounds__(256) void gpt2_pick_embed_kernel(const float* pv, const int* pi, int NB, int* gen, int* state, int P, const float* wte,
-                                                              const float* wpe, int D, float* x, float* stats) {
-    __shared__ float bv[256];
-    __shared__ int bi[256];
-    __shared__ float red[4];
-    const int row = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int past = state[0], step = state[1];
-    float best = -INFINITY;
-    int idx = 0x7fffffff;
-    for (int i = t; i < NB; i += 256) {
-        const float v = pv[(long long)row * NB + i];
-        const int j = pi[(long long)row * NB + i];
-        if (v > best || (v == best && j < idx)) { best = v; idx = j; }
-    }
-    bv[t] = best;
-    bi[t] = idx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) {
-            const float v2 = bv[t + o];
-            const int i2 = bi[t + o];
-            if (v2 > bv[t] || (v2 == bv[t] && i2 < bi[t])) { bv[t] = v2; bi[t] = i2; }
-        }
-        __syncthreads();
-    }
-    const int tok = bi[0];
+// the fused step tail behind the pick (gpt2_pick_embed_kernel, gpt2_sample_kernel<.., true>): the row's token goes to gen[step][row], its
+// embedding at position past + 1 and the first layer's LayerNorm statistics are left exactly as gpt2_embed_step_kernel would leave them at
+// the top of the next step (same arithmetic), and the LAST workgroup to get here advances {past, step} — every workgroup has read the state
+// before it takes its ticket.  state[2] is the ticket counter (zero between launches).  red: 4 floats of LDS.
+__device__ __forceinline__ void gpt2_step_tail(int tok, int row, int past, int step, int* gen, int* state, int P, const float* wte,
+                                               const float* wpe, int D, float* x, float* stats, float* red) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (t == 0) gen[(long long)step * P + row] = tok;
     const float* te = wte + (long long)tok * D;
     const float* pe = wpe + (long long)(past + 1) * D;
@@ -719,6 +696,35 @@ __global__ __launch_bounds__(256) void gpt2_pick_embed_kernel(const float* pv, c
         if (atomicAdd(&state[2], 1) == (int)gridDim.x - 1) { state[0] = past + 1; state[1] = step + 1; state[2] = 0; }
     }
 }
+// stage 2 + the NEXT step's first kernel + the state update in one launch (round 4: a launch is ~4 us of dispatch whatever it does):
+// the arg-max of the pairs, then gpt2_step_tail.
+__global__ __launch_bounds__(256) void gpt2_pick_embed_kernel(const float* pv, const int* pi, int NB, int* gen, int* state, int P, const float* wte,
+                                                              const float* wpe, int D, float* x, float* stats) {
+    __shared__ float bv[256];
+    __shared__ int bi[256];
+    __shared__ float red[4];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const int past = state[0], step = state[1];
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int i = t; i < NB; i += 256) {
+        const float v = pv[(long long)row * NB + i];
+        const int j = pi[(long long)row * NB + i];
+        if (v > best || (v == best && j < idx)) { best = v; idx = j; }
+    }
+    bv[t] = best;
+    bi[t] = idx;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            const float v2 = bv[t + o];
+            const int i2 = bi[t + o];
+            if (v2 > bv[t] || (v2 == bv[t] && i2 < bi[t])) { bv[t] = v2; bi[t] = i2; }
+        }
+        __syncthreads();
+    }
+    gpt2_step_tail(bi[0], row, past, step, gen, state, P, wte, wpe, D, x, stats, red);
+}
 bool gpt2_head_supported(int M, int N, int K, int lda) { return M <= 64 && K % GS_KC == 0 && lda % 4 == 0 && N >= 4096; }
 // the vocabulary projection + the fused pick / embed / advance tail (D <= 1024); false: shape not covered, nothing launched
 bool launch_gpt2_head_tail(const float* A, const float* W, int M, int N, int K, int lda, const float* stats_in, const float* lng, const float* lnb,
@@ -738,6 +744,224 @@ bool launch_gpt2_head(const float* A, const float* W, int M, int N, int K, int l
     int* pi = (int*)(pairs + (size_t)M * NB);
     hipLaunchKernelGGL(gpt2_head_kernel, dim3((NB + HD_NW - 1) / HD_NW), dim3(64 * HD_NW), 0, st, A, W, M, N, K, lda, stats, lng, lnb, logits, pairs, pi, NB);
     hipLaunchKernelGGL(argmax_pairs_kernel, dim3(M), dim3(256), 0, st, pairs, pi, NB, out, step_dev);
+    return true;
+}
+
+// ---- stochastic pick (gpt2/sample.py:21-36 with sample=True; models.py:45-60 with config.stochastic) --------------------------------------
+// The rule, per row r at step s (numpy mirror: synth.gpt2_sample_uniform + tests/test_gpt2_sampling.py):
+//   l' = l / T (a true fp32 division, as the reference divides by the Python float); m = the k-th largest l' counting repeats; the kept
+//   set is every index with l' >= m (more than k on ties at m, as top_k_logits); k == 0 or k >= V keeps everything; p_i = exp(l'_i - max l')
+//   over the kept set (1 where l'_i == max, which also covers an all -inf row); u = (x + 0.5) 2^-32 with x the first word of
+//   Philox4x32-10 at counter (first_row + r, s, generation, purpose) under key (seed_lo, seed_hi ^ GPT2_SAMPLE_TAG); the token is the first
+//   kept index, in vocabulary order, whose running sum of p exceeds u * sum(p) — the last kept index if rounding leaves none.
+// One workgroup per row.  The k-th value is found without sorting the row: the 32-column block maxima (the head kernel's `pairs`, or a
+// pass over the row) hold >= k distinct elements at or above their own k-th largest value t, so m >= t and every kept element lies in a
+// block whose maximum is >= t.  A radix select over the block maxima gives t, the candidate blocks (max >= t, in vocabulary order) are
+// listed in LDS, and a second radix select over their elements gives m — for k = 40 on GPT-2 logits about 40 blocks (1.3 K values).  Ties
+// only lengthen the list (at worst every block: the whole row, still exact).  Sums run in tiles of 256 elements in vocabulary order, a
+// fixed-order scan per tile: the total and the crossing point come from the same arithmetic, and nothing depends on other rows.
+// Per-call values live in device memory (sp[GPT2_SP_*], loaded before the steps), so one captured step graph serves every row group.
+#define GS_NBMAX 4096                       // block maxima in LDS: V <= 131072
+#define GPT2_SAMPLE_TAG 0x47505432u         // "GPT2", XOR-ed into the key's high word: disjoint from the noise planes' stream
+__device__ __forceinline__ uint32_t gs_key(float v) {               // order-preserving float -> uint32 (both zeros -> +0)
+    const uint32_t u = __float_as_uint(v == 0.f ? 0.f : v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float gs_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+__device__ __forceinline__ int gs_wave_incl_scan(int v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int w = __shfl_up(v, o);
+        if (lane >= o) v += w;
+    }
+    return v;
+}
+__device__ __forceinline__ float gs_wave_incl_scanf(float v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float w = __shfl_up(v, o);
+        if (lane >= o) v += w;
+    }
+    return v;
+}
+// key of the k-th largest (1 <= k <= number of valid items) of n items; key_of(i, &key) -> item i exists.  256 threads; 8-bit digits,
+// four passes of an LDS histogram, wave 0 finds the digit (bins from the top, four per lane, one wave scan).
+template <class F>
+__device__ uint32_t gs_radix_select(int n, int k, F key_of, int* hist, int* sh) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    uint32_t prefix = 0, mask = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hist[t] = 0;
+        __syncthreads();
+        for (int i = t; i < n; i += 256) {
+            uint32_t key;
+            if (key_of(i, key) && (key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1);
+        }
+        __syncthreads();
+        if (wave == 0) {
+            int c[4], s = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { c[j] = hist[255 - 4 * lane - j]; s += c[j]; }
+            const int incl = gs_wave_incl_scan(s, lane), excl = incl - s;
+            if (excl < k && k <= incl) {
+                int cum = excl, bin = 0, kk = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (kk == 0 && cum + c[j] >= k) { bin = 255 - 4 * lane - j; kk = k - cum; }
+                    cum += c[j];
+                }
+                sh[0] = bin; sh[1] = kk;
+            }
+        }
+        __syncthreads();
+        prefix |= (uint32_t)sh[0] << shift;
+        mask |= 0xFFu << shift;
+        k = sh[1];
+        __syncthreads();
+    }
+    return prefix;
+}
+// PAIRS: block maxima from the head kernel's pairs (pv[row][NB]); otherwise from a pass over the row.  TAIL: gpt2_step_tail behind the pick
+// (the fused step); otherwise the token goes to out[(state ? state[1] : 0) * rows + row].  The counter's step is state[1], or sp[GPT2_SP_STEP]
+// without a state (the diagnostic op).
+template <bool PAIRS, bool TAIL>
+__global__ __launch_bounds__(256) void gpt2_sample_kernel(const float* logits, const float* pv, int NB, int V, const int* sp, int* out, int* state,
+                                                          const float* wte, const float* wpe, int D, float* x, float* stats) {
+    __shared__ float bm[GS_NBMAX];            // block maxima of l'
+    __shared__ int cand[GS_NBMAX];            // candidate blocks, ascending
+    __shared__ int hist[256];
+    __shared__ int sh[4];
+    __shared__ float redf[4];
+    __shared__ int redi[4];
+    const int row = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const float T = __int_as_float(sp[GPT2_SP_TEMP]);
+    const int k = sp[GPT2_SP_TOPK];
+    const int past = state ? state[0] : 0, step = state ? state[1] : sp[GPT2_SP_STEP];
+    const float* lr = logits + (long long)row * V;
+    // 1. block maxima (max of the raw logits, then / T: the division is monotone) and the row maximum
+    if (PAIRS) {
+        for (int j = t; j < NB; j += 256) bm[j] = pv[(long long)row * NB + j] / T;
+    } else {
+        for (int j0 = 0; j0 < NB; j0 += 8) {      // half a wave per block, coalesced
+            const int j = j0 + 2 * wave + (lane >> 5), n = j * 32 + (lane & 31);
+            float v = (j < NB && n < V) ? lr[n] : -INFINITY;
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+            if (j < NB && (lane & 31) == 0) bm[j] = v / T;
+        }
+    }
+    __syncthreads();
+    float mx = -INFINITY;
+    for (int j = t; j < NB; j += 256) mx = fmaxf(mx, bm[j]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if (lane == 0) redf[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
+    // 2. candidate blocks: maximum >= t, the k-th largest block maximum (every block when k > NB or the row is kept whole)
+    const bool keep_all = k <= 0 || k >= V;
+    float tb = -INFINITY;
+    if (!keep_all && k <= NB)
+        tb = gs_unkey(gs_radix_select(NB, k, [&](int i, uint32_t& key) { key = gs_key(bm[i]); return true; }, hist, sh));
+    int C = 0;
+    for (int j0 = 0; j0 < NB; j0 += 256) {
+        const int j = j0 + t;
+        const bool f = j < NB && bm[j] >= tb;
+        const unsigned long long b = __ballot(f);
+        const int before = __popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) redi[wave] = __popcll(b);
+        __syncthreads();
+        int off = C;
+        for (int w = 0; w < wave; ++w) off += redi[w];
+        if (f) cand[off + before] = j;
+        C += (redi[0] + redi[1]) + (redi[2] + redi[3]);
+        __syncthreads();
+    }
+    const int n = C * 32;
+    auto col = [&](int i) { return cand[i >> 5] * 32 + (i & 31); };
+    // 3. m, the k-th largest l' among the candidates' elements
+    float m = -INFINITY;
+    if (!keep_all)
+        m = gs_unkey(gs_radix_select(n, k, [&](int i, uint32_t& key) {
+            const int c = col(i);
+            if (c >= V) return false;
+            key = gs_key(lr[c] / T);
+            return true;
+        }, hist, sh));
+    // 4. running sums in tiles of 256 (vocabulary order): tile(i0) -> this thread's inclusive running sum; `carry` = the sum before the tile
+    float carry = 0.f;
+    auto tile = [&](int i0, bool& kept, int& c) {
+        const int i = i0 + t;
+        c = i < n ? col(i) : V;
+        float p = 0.f;
+        kept = false;
+        if (c < V) {
+            const float l = lr[c] / T;
+            kept = l >= m;
+            if (kept) p = l == mx ? 1.f : expf(l - mx);
+        }
+        const float incl = gs_wave_incl_scanf(p, lane);
+        if (lane == 63) redf[wave] = incl;
+        __syncthreads();
+        float off = carry;
+        for (int w = 0; w < wave; ++w) off += redf[w];
+        const float run = off + incl;
+        carry += ((redf[0] + redf[1]) + redf[2]) + redf[3];
+        __syncthreads();
+        return run;
+    };
+    for (int i0 = 0; i0 < n; i0 += 256) { bool kept; int c; (void)tile(i0, kept, c); }
+    const float total = carry;
+    uint32_t ctr[4] = {(uint32_t)(sp[GPT2_SP_ROW0] + row), (uint32_t)step, (uint32_t)sp[GPT2_SP_GEN], (uint32_t)sp[GPT2_SP_PURPOSE]};
+    philox4x32_10(ctr, (uint32_t)sp[GPT2_SP_SEED_LO], (uint32_t)sp[GPT2_SP_SEED_HI] ^ GPT2_SAMPLE_TAG);
+    const double target = ((double)ctr[0] + 0.5) * 0x1p-32 * (double)total;
+    // 5. the first kept index whose running sum exceeds the target (same tiles, same arithmetic); else the last kept index
+    carry = 0.f;
+    int tok = -1, last = -1;
+    for (int i0 = 0; i0 < n && tok < 0; i0 += 256) {
+        bool kept; int c;
+        const float run = tile(i0, kept, c);
+        if (kept) last = c;                   // (ascending within a thread)
+        const unsigned long long hit = __ballot(kept && (double)run > target);
+        if (lane == 0) redi[wave] = hit ? i0 + 64 * wave + __ffsll((long long)hit) - 1 : 0x7fffffff;
+        __syncthreads();
+        const int first = min(min(redi[0], redi[1]), min(redi[2], redi[3]));
+        if (first != 0x7fffffff) tok = col(first);
+        __syncthreads();
+    }
+    if (tok < 0) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o));
+        if (lane == 0) redi[wave] = last;
+        __syncthreads();
+        tok = max(max(redi[0], redi[1]), max(redi[2], redi[3]));
+        tok = max(tok, 0);                    // (an empty kept set needs NaN logits: never an index outside the table)
+    }
+    if (TAIL) {
+        gpt2_step_tail(tok, row, past, step, out, state, gridDim.x, wte, wpe, D, x, stats, redf);
+    } else if (t == 0) {
+        out[(state ? (long long)step * gridDim.x : 0) + row] = tok;
+    }
+}
+bool gpt2_sample_supported(int V) { return V > 0 && V <= 32 * GS_NBMAX; }
+// generic form: sampler over full logits rows [rows][V]
+void launch_gpt2_sample(const float* logits, int rows, int V, const int* sp, int* out, int* state, hipStream_t st) {
+    hipLaunchKernelGGL((gpt2_sample_kernel<false, false>), dim3(rows), dim3(256), 0, st, logits, (const float*)nullptr, (V + 31) / 32, V, sp, out,
+                       state, (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, (float*)nullptr);
+}
+// the vocabulary projection writing its logits as well as its pairs, then the sampler from the pairs; tail: + the fused pick / embed /
+// advance tail of launch_gpt2_head_tail (wte / wpe / x / stats_out; D <= 1024), else the token goes to gen[step][row].  false: not covered.
+bool launch_gpt2_head_sample(const float* A, const float* W, int M, int N, int K, int lda, const float* stats_in, const float* lng, const float* lnb,
+                             float* logits, float* pairs, const int* sp, int* gen, int* state, bool tail, const float* wte, const float* wpe, float* x,
+                             float* stats_out, hipStream_t st) {
+    if (!gpt2_head_supported(M, N, K, lda) || !pairs || !logits || !gpt2_sample_supported(N) || (tail && K > 1024)) return false;
+    const int NB = (N + 31) / 32;
+    int* pi = (int*)(pairs + (size_t)M * NB);
+    hipLaunchKernelGGL(gpt2_head_kernel, dim3((NB + HD_NW - 1) / HD_NW), dim3(64 * HD_NW), 0, st, A, W, M, N, K, lda, stats_in, lng, lnb, logits, pairs, pi, NB);
+    if (tail)
+        hipLaunchKernelGGL((gpt2_sample_kernel<true, true>), dim3(M), dim3(256), 0, st, logits, pairs, NB, N, sp, gen, state, wte, wpe, K, x, stats_out);
+    else
+        hipLaunchKernelGGL((gpt2_sample_kernel<true, false>), dim3(M), dim3(256), 0, st, logits, pairs, NB, N, sp, gen, state, wte, wpe, K, x, stats_out);
     return true;
 }
 

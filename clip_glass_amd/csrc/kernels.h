@@ -163,5 +163,16 @@ bool gemm_f32_rowblk_supported(int M, int N, int K, int lda, bool ln_fused, bool
 bool launch_gemm_f32_rowblk(const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int lda, int ldo, int mode,
                             hipStream_t st, const float* pst_in, int np_in, const float* lng, const float* lnb, float* pst_out);
 void launch_gpt2_advance(int* state, hipStream_t st);
+// stochastic pick (top-k temperature sampling, gpt2.hip): the per-call values are int32 words in device memory, sp[GPT2_SP_WORDS]
+// (temperature as its float bits; STEP is read only without a device step state — the diagnostic op)
+enum { GPT2_SP_SEED_LO, GPT2_SP_SEED_HI, GPT2_SP_GEN, GPT2_SP_ROW0, GPT2_SP_PURPOSE, GPT2_SP_TEMP, GPT2_SP_TOPK, GPT2_SP_STEP, GPT2_SP_WORDS };
+#define GPT2_SAMPLE_TOPK_MAX 256
+bool gpt2_sample_supported(int V);
+// logits [rows][V] -> out[(state ? state[1] : 0) * rows + row]
+void launch_gpt2_sample(const float* logits, int rows, int V, const int* sp, int* out, int* state, hipStream_t st);
+// vocabulary projection (logits + pairs written) + sampler from the pairs; tail: launch_gpt2_head_tail's pick / embed / advance tail
+bool launch_gpt2_head_sample(const float* A, const float* W, int M, int N, int K, int lda, const float* stats_in, const float* lng, const float* lnb,
+                             float* logits, float* pairs, const int* sp, int* gen, int* state, bool tail, const float* wte, const float* wpe, float* x,
+                             float* stats_out, hipStream_t st);
 // NCHW fp32 image [n][3][S][S] -> CLIP patch matrix [n*G*G][3*ps*ps] fp16
 void launch_image_patches(const float* img, int n, int S, int ps, half_t* patches, hipStream_t st);

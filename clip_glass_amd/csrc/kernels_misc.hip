@@ -326,17 +326,7 @@ void launch_modulate_weights(const half_t* w, long long elems, int Cin, int Cout
                        ds_stride, wm);
 }
 
-// ---- noise planes: Philox4x32-10 + Box-Muller (numpy mirror: clip_glass_amd/synth.py) --
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint64_t p0 = (uint64_t)c[0] * 0xD2511F53ull, p1 = (uint64_t)c[2] * 0xCD9E8D57ull;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
+// ---- noise planes: Philox4x32-10 (common.h) + Box-Muller (numpy mirror: clip_glass_amd/synth.py) --
 __global__ void noise_kernel(float* out, int hw, uint32_t layer, uint32_t mb0, uint32_t generation, uint32_t k0,
                              uint32_t k1) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;

@@ -378,6 +378,35 @@ extern "C" int glass_op_noise(int32_t device, int32_t n_mb, int32_t hw, uint32_t
     return GLASS_OK;
 }
 
+extern "C" int glass_op_gpt2_sample(int32_t device, int32_t rows, int32_t V, const float* logits, float temperature, int32_t top_k,
+                                    uint64_t seed, int32_t generation, int32_t first_row, int32_t step, int32_t purpose, int32_t* out) {
+    OPREQ(logits && out && rows > 0 && V > 0, "bad argument");
+    OPREQ(temperature > 0.f && temperature < INFINITY, "temperature must be a finite value > 0");
+    OPREQ(top_k >= 0 && top_k <= GPT2_SAMPLE_TOPK_MAX, "top_k must lie in [0, 256]");
+    OPREQ(gpt2_sample_supported(V), "vocabulary too large for the sampler (> 131072)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* d = dv.up32(logits, (size_t)rows * V);
+    int* sp = dv.alloc<int>(GPT2_SP_WORDS);
+    int* o = dv.alloc<int>(rows);
+    OPREQ(d && sp && o, "hipMalloc failed");
+    int32_t h[GPT2_SP_WORDS];
+    h[GPT2_SP_SEED_LO] = (int32_t)(uint32_t)(seed & 0xFFFFFFFFu);
+    h[GPT2_SP_SEED_HI] = (int32_t)(uint32_t)(seed >> 32);
+    h[GPT2_SP_GEN] = generation;
+    h[GPT2_SP_ROW0] = first_row;
+    h[GPT2_SP_PURPOSE] = purpose;
+    memcpy(&h[GPT2_SP_TEMP], &temperature, sizeof(float));
+    h[GPT2_SP_TOPK] = top_k;
+    h[GPT2_SP_STEP] = step;
+    GLASS_HIP(hipMemcpy(sp, h, sizeof h, hipMemcpyHostToDevice));
+    launch_gpt2_sample(d, rows, V, sp, o, nullptr, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, o, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
 __global__ void mfma_probe_kernel(const half_t* a, const half_t* b, float* d) {
     const int lane = threadIdx.x;
     const int r = lane & 31, kh = lane >> 5;

@@ -66,6 +66,9 @@ def load_library(path=None):
     lib.glass_engine_encode_text.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, fp]
     lib.glass_engine_encode_image.argtypes = [C.c_void_p, fp, C.c_int32, fp]
     lib.glass_engine_gpt2_decode.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    if hasattr(lib, "glass_engine_gpt2_sample"):        # (absent from older A/B builds loaded through GLASS_LIB)
+        lib.glass_engine_gpt2_sample.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                                 C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
     lib.glass_engine_evaluate.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GlassNoise), fp]
     lib.glass_engine_generate.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GlassNoise), fp]
     lib.glass_engine_last_details.argtypes = [C.c_void_p, C.c_int32, fp, fp, fp]
@@ -195,6 +198,18 @@ class Engine:
         ip = C.POINTER(C.c_int32)
         _check(self.lib, self.lib.glass_engine_gpt2_decode(self._h, c.ctypes.data_as(ip), c.shape[0], c.shape[1], length,
                                                             out.ctypes.data_as(ip)))
+        return out
+
+    def gpt2_sample(self, context, length, temperature=0.7, top_k=40, seed=0, generation=0, first_row=0, purpose=0):
+        """gpt2/sample.py:21-36 with sample=True: int tokens [P, n] -> [P, n + length], top-k temperature sampling on the device.
+        Draws are a function of (seed, generation, purpose, first_row + row, step) and the row's logits (include/glass.h); purpose
+        separates the fitness evaluation (GPT2_SAMPLE_EVALUATE) from the save callback (GPT2_SAMPLE_SAVE) of one generation."""
+        c = np.ascontiguousarray(context, dtype=np.int32)
+        out = np.empty((c.shape[0], c.shape[1] + length), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        _check(self.lib, self.lib.glass_engine_gpt2_sample(self._h, c.ctypes.data_as(ip), c.shape[0], c.shape[1], length, float(temperature),
+                                                            int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation), int(first_row),
+                                                            int(purpose), out.ctypes.data_as(ip)))
         return out
 
     # --- the pass ------------------------------------------------------------

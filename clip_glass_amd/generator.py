@@ -172,8 +172,10 @@ class Generator:
     # --- the hot path: generate + clip_similarity + discriminate in ONE device pass -------------
     def evaluate(self, ls, noise=None, first_minibatch=0):
         if self.config.task == "img2txt":           # problem.py:19-20,27 with the GPT2 config
-            texts = self.model.generate(*ls())
+            # (config.stochastic: each generation draws fresh texts; greedy decoding ignores the generation)
+            texts = self.model.generate(*ls(), generation=self.generation, purpose=synth.GPT2_SAMPLE_EVALUATE)
             self.last_texts = texts
+            self.generation += 1
             return -self.clip_similarity_texts(texts)[:, None]
         z = ls.population()
         if self.sharder is not None:        # one process per GPU: this rank scores its shard, ONE all-gather of the rows
@@ -189,8 +191,8 @@ class Generator:
 
     def generate(self, ls, minibatch=None, noise=None):
         """generator.py:29-34 — images [P,3,R,R] float32 after config.norm (biggan_norm); texts for img2txt."""
-        if self.config.task == "img2txt":
-            return self.model.generate(*ls())
+        if self.config.task == "img2txt":        # deterministic per generation, never the draw evaluate() used
+            return self.model.generate(*ls(), generation=self.generation, purpose=synth.GPT2_SAMPLE_SAVE)
         z = ls.population()
         bs = self.config.batch_size
         P = z.shape[0]

@@ -159,10 +159,19 @@ class GPT2:
     def has_discriminator(self):
         return False
 
-    def decode_tokens(self, z):
-        """models.py:45-60: context = z ++ init_tokens, 30 greedy steps."""
+    def decode_tokens(self, z, generation=0, purpose=synth.GPT2_SAMPLE_EVALUATE):
+        """models.py:45-60: context = z ++ init_tokens, 30 steps — greedy, or with config.stochastic top-k temperature sampling
+        (sample.py:21-36 with sample=True: the reference's hard-coded temperature 0.7 / top_k 40 unless the config sets
+        `temperature` / `top_k`; seed config.sample_seed, else config.seed, else 0).  generation / purpose select the draw."""
         z = np.asarray(z, dtype=np.int64)
         ctx = np.concatenate([z, np.tile(self.init_tokens, (z.shape[0], 1))], axis=1)
+        if getattr(self.config, "stochastic", False):
+            seed = getattr(self.config, "sample_seed", None)
+            if seed is None:
+                seed = getattr(self.config, "seed", None) or 0
+            return self.engine.gpt2_sample(ctx, self.config.max_tokens_len, temperature=getattr(self.config, "temperature", 0.7),
+                                           top_k=getattr(self.config, "top_k", 40), seed=int(seed), generation=int(generation),
+                                           first_row=0, purpose=purpose)
         return self.engine.gpt2_decode(ctx, self.config.max_tokens_len)
 
     def parse_out(self, out):
@@ -178,7 +187,7 @@ class GPT2:
             texts.append(self.enc.decode(text)[:self.config.max_text_len])
         return texts
 
-    def generate(self, z, minibatch=None):
+    def generate(self, z, minibatch=None, generation=0, purpose=synth.GPT2_SAMPLE_EVALUATE):
         if self.enc is None:
             raise RuntimeError("GPT-2 BPE assets not found (config.encoder / config.vocab)")
-        return self.parse_out(self.decode_tokens(z))
+        return self.parse_out(self.decode_tokens(z, generation, purpose))

@@ -255,6 +255,20 @@ def noise(n_mb, hw, layer, mb0, generation, seed, device=0):
     return out
 
 
+def gpt2_sample(logits, temperature, top_k, seed, generation, first_row, step, purpose=0, device=0):
+    """The GPT-2 stochastic pick on logits [rows, V] float32 (gpt2.hip, generic path) -> int32 tokens [rows]."""
+    lib = load_library()
+    lg = _f32(logits)
+    rows, V = lg.shape
+    out = np.empty(rows, dtype=np.int32)
+    ip = C.POINTER(C.c_int32)
+    lib.glass_op_gpt2_sample.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_int32, C.c_uint64,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip]
+    _check(lib, lib.glass_op_gpt2_sample(device, rows, V, _fp(lg), float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                         int(generation), int(first_row), int(step), int(purpose), out.ctypes.data_as(ip)))
+    return out
+
+
 def mfma_probe(a, b, device=0):
     lib = load_library()
     a, b = _f32(a), _f32(b)

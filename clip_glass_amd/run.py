@@ -32,6 +32,8 @@ def build_parser():
     p.add_argument("--clip-weights", type=str, default=None, help="ViT-B-32.pt, or synthetic:<seed>")
     p.add_argument("--bpe-path", type=str, default=None)
     p.add_argument("--pop-size", type=int, default=None)
+    p.add_argument("--stochastic", action="store_true", default=None,
+                   help="GPT2 config: top-k temperature sampling instead of greedy decoding (the config table's `stochastic`)")
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--dist", action="store_true",
                    help="multi-GPU: run under `torchrun --nproc-per-node N -m clip_glass_amd.run --dist ...` (one process per GPU, "
@@ -44,7 +46,7 @@ def main(argv=None, extra_config=None):
     config = build_parser().parse_args(argv)
     over = {k: v for k, v in vars(config).items() if v is not None}
     vars(config).update(get_config(config.config))                             # run.py:25
-    for k in ("weights", "clip_weights", "bpe_path", "pop_size"):
+    for k in ("weights", "clip_weights", "bpe_path", "pop_size", "stochastic"):
         if k in over:
             setattr(config, k, over[k])
     if extra_config:

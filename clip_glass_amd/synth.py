@@ -250,6 +250,19 @@ def noise_plane(seed, generation, minibatch, layer, h, w):
     return out.reshape(-1)[:n].reshape(h, w)
 
 
+# GPT-2 stochastic decode (csrc/gpt2.hip, gpt2_sample_kernel): one uniform per (global row, step, generation, purpose) — the first
+# Philox word under the seed with this tag XOR-ed into the key's high word, so the draws never share a stream with the noise planes.
+GPT2_SAMPLE_TAG = 0x47505432
+GPT2_SAMPLE_EVALUATE, GPT2_SAMPLE_SAVE = 0, 1          # purpose words: fitness evaluation / save callback
+
+
+def gpt2_sample_uniform(seed, generation, row, step, purpose=GPT2_SAMPLE_EVALUATE):
+    """u in (0, 1), float64, broadcast over the array arguments — the device's draw for that counter."""
+    x = philox4x32(row, step, np.asarray(generation, np.int64).astype(np.uint32), purpose, np.uint32(seed & 0xFFFFFFFF),
+                   np.uint32(((seed >> 32) & 0xFFFFFFFF) ^ GPT2_SAMPLE_TAG))[0]
+    return (x.astype(np.float64) + 0.5) * 2.0 ** -32
+
+
 def g_noise_planes(seed, generation, minibatch, channels=FFHQ_CHANNELS):
     """The 1+2*(n-1) noise planes of one G call (one minibatch), execution order."""
     convs, _ = g_layers(channels)

@@ -118,6 +118,17 @@ int glass_engine_encode_image(glass_engine* e, const float* images, int32_t n, f
 int glass_engine_gpt2_decode(glass_engine* e, const int32_t* context, int32_t P, int32_t n_ctx_tok, int32_t length,
                              int32_t* out_tokens);
 
+/* GPT-2 stochastic decode (config GPT2 with stochastic = True: models.py:45-60, gpt2/sample.py:10-36 with sample=True), same
+ * context / output layout as glass_engine_gpt2_decode.  Each step divides the logits by `temperature` (> 0), keeps the entries at or
+ * above the top_k-th largest (ties included; top_k in [0, 256], 0 or >= vocabulary keeps all), and draws the next token from their
+ * softmax with a uniform from Philox4x32-10 at counter (first_row + row, step, generation, purpose) under `seed` (with a fixed tag in
+ * the key's high word, disjoint from the noise planes' stream).  first_row: global index of context row 0, so a population decoded
+ * in slices gives the same tokens as one call.  purpose: separates draws of the same generation (0: fitness evaluation, 1: the
+ * save callback).  Deterministic for equal arguments.  Vocabulary <= 131072. */
+int glass_engine_gpt2_sample(glass_engine* e, const int32_t* context, int32_t P, int32_t n_ctx_tok, int32_t length,
+                             float temperature, int32_t top_k, uint64_t seed, int32_t generation, int32_t first_row,
+                             int32_t purpose, int32_t* out_tokens);
+
 /* THE HOT PATH — replaces GenerationProblem._evaluate (problem.py:14-29).
  * latents: host float32 [P, latent_size] row-major (latent.py:37-38);
  * generation: index folded into the device noise stream (noise_mode 1);

@@ -82,6 +82,11 @@ int glass_op_attention(int32_t device, int32_t n_img, int32_t L, int32_t heads, 
                        float* out);
 int glass_op_noise(int32_t device, int32_t n_mb, int32_t hw, uint32_t layer, uint32_t mb0, uint32_t generation,
                    uint64_t seed, float* out);
+/* The GPT-2 stochastic pick (gpt2.hip, gpt2_sample_kernel, the engine's generic path) on caller logits [rows, V] float32: top-k
+ * temperature sampling as glass_engine_gpt2_sample draws it at step `step` for global rows first_row .. first_row + rows - 1
+ * (temperature > 0, top_k in [0, 256], 0 = keep all; V <= 131072); out: int32 [rows]. */
+int glass_op_gpt2_sample(int32_t device, int32_t rows, int32_t V, const float* logits, float temperature, int32_t top_k,
+                         uint64_t seed, int32_t generation, int32_t first_row, int32_t step, int32_t purpose, int32_t* out);
 /* raw MFMA layout probe: D = A[32x16] * B[16x32] through the fragment mapping of common.h */
 int glass_op_mfma_probe(int32_t device, const float* a /*[32,16]*/, const float* b /*[16,32]*/, float* d /*[32,32]*/);
 
