@@ -8,15 +8,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-// A/B knobs (environment variables that switch a dispatcher to an older kernel or change a tile rule) exist in the developer
-// build only: `make AB=1` (-DGLASS_AB_KNOBS -> tools/lib/libglass_ab.so, driven by tools/ab_bench.sh through GLASS_LIB).  In the
-// release library every knob reads as "not set" and the branch it guards folds away — the product has ONE code path per layer.
-#ifdef GLASS_AB_KNOBS
-inline const char* glass_knob(const char* name) { return getenv(name); }
-#else
-inline const char* glass_knob(const char*) { return nullptr; }
-#endif
-
 typedef _Float16 half_t;
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -240,8 +231,7 @@ struct ConvParams {
                             // steps and every line crossed the fabric twice (PMC traffic 1.59 x the algorithmic bytes: the r256 layer ran at 5.6 TB/s)
     int x_planar8;         // the input map is chunk-planar
     int y_planar8;         // the output map is written chunk-planar
-    int no_tstore;          // experiment knob: 1 = scattered 8-byte stores (no LDS-transposed epilogue)
-    int row_walk;           // conv_stream A/B knob: row-major walk of the persistent workgroups (round 2) instead of down the columns
+    int row_walk;           // conv_stream: row-major walk of the persistent workgroups (the fromRGB form) instead of down the columns
     half_t* y;              // output [B][Ho][Wo][Cout] fp16 (or)
     float* y32;             // output fp32, same layout
 };

@@ -94,32 +94,8 @@ struct D0Params {
     half_t* y;            // [B][R/2][R/2][64], or chunk-planar [B][8][R/2][R/2][8] (common.h x_planar8: the consumer is conv_wreg)
     int B, R;
     int y_planar8;
-#if defined(GLASS_AB_KNOBS) || defined(GLASS_DEV_TRACE)      // developer builds only (make AB=1 / TRACE=1): the release struct carries none of these
-    unsigned long long* trace;   // GLASS_D0_TRACE: phase timestamps of workgroup 0
-    int skew;             // GLASS_D0_SKEW: start delay (units of ~1000 clocks) of the second half of the grid
-    int ablate;           // GLASS_D0_ABLATE: timing experiments that switch phases off — 1 image loads, 2 P1 (fromRGB MFMA + lrelu + patch writes),
-                          // 4 P2 (skip-input FIR), 8 conv0 MFMAs, 16 conv0 epilogue + horizontal FIR, 32 P4 (vertical FIR), 64 conv1 + skip MFMAs,
-                          // 128 output stores.  WRONG RESULTS.
-#endif
 };
-#if defined(D0_ABLATE_CT)       // compile-time bits (tools/build_ablations.sh): a run-time bit costs branches and lets nothing be deleted (DESIGN "Round 6")
-#define D0_ABL(bit) (((D0_ABLATE_CT) & (bit)) != 0)
-#elif defined(GLASS_AB_KNOBS)
-#define D0_ABL(bit) (p.ablate & (bit))
-#else
-#define D0_ABL(bit) false
-#endif
-// phases: 0 top, 1 after B0, 2 patch written, 3 after B1, 4 P2 done, 5 conv0 MFMAs done, 6 ring written, 7 after B2, 8 P4 done, 9 after B3,
-// 10 conv1 MFMAs done, 11 stores issued
-#ifdef GLASS_DEV_TRACE
-#define D0TRACE(ph)                                                                                          \
-    if (TR && blockIdx.x == 0 && (threadIdx.x & 63) == 0 && n_item < 96)                                      \
-        p.trace[(n_item * 16 + (ph)) * 4 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memtime()
-#else
-#define D0TRACE(ph) (void)n_item
-#endif
 
-template <bool TR>
 __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_x, int tiles_y, int n_steps, int per_block) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* Cb0 = (float*)(smem + OFF_C);
@@ -217,7 +193,6 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
     // when the operand is built)
     float yv[3][3];
     auto load_image = [&](const Item& c) {
-        if (D0_ABL(1)) return;
         const int t = opaque(threadIdx.x);
         const int y0 = 4 * c.k + 1, x0 = XW * c.tx - 3;
         const long long hw = (long long)R * R;
@@ -233,15 +208,12 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
         }
     };
 
-    int n_item = 0;
     auto step = [&](const Item& c, const Item& nx) {
         const int b = c.b, tx = c.tx, k = c.k;
         const int y0 = 4 * k + 1, x0 = XW * tx - 3;
-        D0TRACE(0);
         __syncthreads();       // B0: every wave is done with the previous item's operand image / patch / XS
-        D0TRACE(1);
         // ---- P1: fromRGB of this wave's patch blocks -> F: one MFMA per 32 pixels, lrelu in packed fp16, four 8-byte stores per lane -------
-        if (!D0_ABL(2)) {
+        {
             const int t = opaque(threadIdx.x), lr1 = t & 31, kh1 = (t >> 5) & 1, wv = uni(t >> 6);
             f16x zacc;
 #pragma unroll
@@ -282,15 +254,13 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
                 }
             }
         }
-        D0TRACE(2);
         __syncthreads();       // B1: patch complete
-        D0TRACE(3);
         const int tm = opaque(threadIdx.x), lr = tm & 31, kh = (tm >> 5) & 1, lane = tm & 63, wave = uni(tm >> 6);
         // ---- P2: skip-branch input: FIR 4x4 (pad 1) + ::2 of the fromRGB map, output row 2k + 1 + r (one row ahead of P5).  The wave's 32
         // pixels x 2 chunks are dealt (pixel = lane / 2, chunk = nh * 2 + lane % 2): a stride-2 pixel walk touches every other 64-byte
         // window, so sixteen consecutive lanes must bring two chunks each to cover all sixteen 16-byte bank groups (the image goes
         // through LDS to the skip MFMAs anyway, so this phase's lane mapping is free) ----
-        if (!D0_ABL(4)) {
+        {
             const int r = wave >> 1, nh = wave & 1, ch = nh * 2 + (lane & 1), lrx = lane >> 1;
             h8 hr[4];
             const int fc0 = min(2 * lrx + 2, FC - 4);                                  // (lanes past the tile's 29 columns: any columns that exist)
@@ -311,7 +281,6 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
             const int xslot = uni((2 * k + 1 + r + 3) % 3);                             // ring slot of output row o: o mod 3 (k >= -1)
             *(h8*)(smem + OFF_XS + xslot * 2048 + swz(lrx, ch)) = fir4(hr[0], hr[1], hr[2], hr[3]);
         }
-        D0TRACE(4);
         // ---- P3: conv0 of new h row 8k + 2 + wave -> row image -> horizontal FIR -> ring -------------------------------------------------
         {
             const int yh = 4 * k + 2 + wave;                                           // uniform per wave
@@ -345,11 +314,10 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
 #pragma unroll
                         for (int blk = 0; blk < 2; ++blk) d[kk * 2 + blk] = *(const h8*)(smem + fb[kx][kk] + ky * (FP * 64) + blk * 2048);
                 };
-                if (!D0_ABL(8)) rd4(0, xq[0]);
+                rd4(0, xq[0]);
                 __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int tap = 0; tap < 9; ++tap) {
-                    if (D0_ABL(8)) break;
                     if (tap + 1 < 9) rd4(tap + 1, xq[(tap + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -359,7 +327,6 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 __builtin_amdgcn_s_setprio(0);
-                D0TRACE(5);
                 // bias + lrelu * sqrt2 exactly as conv_stream<fromrgb> formed h: fp32 sum -> fp16 -> max(v k1, v k2) in packed fp16
                 // (r05: moving the sqrt2 gain into conv1's weight fragments saves 16 of the step's ~880 VALU instructions, changes no
                 // timing — the kernel is not bound by VALU issue, DESIGN section 5 — and re-rounds the weights: D error 5.4e-4 -> 8.1e-4; not kept)
@@ -381,12 +348,8 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
                         }
                     }
                 };
-                if (D0_ABL(16)) {
-                    if (acc[0][0] == 12345.678f) p.y[0] = (half_t)1.f;
-                } else {
                 if (edge) epi0(true);
                 else epi0(false);
-                D0TRACE(12);
                 __builtin_amdgcn_wave_barrier();
                 h8 v[7];
 #pragma unroll
@@ -395,25 +358,20 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
                     v[q] = *(const h8*)(smem + OFF_RT + wave * ROWB + vrot(colq, cgl ^ ((colq >> 2) & 3)));
                     if (q >= 4 && jj == 15) v[q] = zero;                               // window columns 64 .. 66 do not exist
                 }
-                if (TR) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-                D0TRACE(13);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     if (4 * jj + i <= XW) *(h8*)(ring + hw4[i]) = fir4(v[i], v[i + 1], v[i + 2], v[i + 3]);
                 __builtin_amdgcn_wave_barrier();
-                }
             }
         }
-        D0TRACE(6);
         load_image(nx);        // the next item's image values travel during P4 / P5 (issued here, not before conv0: twelve fewer live
                                // registers in the step's tightest loop)
-        if (c.prime) { ++n_item; return; }
+        if (c.prime) return;
         __syncthreads();       // B2: ring complete; every wave is done reading F
-        D0TRACE(7);
         // ---- P4: vertical FIR over the ring -> operand image A (rows 0 .. 4 = blurred rows 4k .. 4k + 4) -----------------------------------
         {
             const int t = opaque(threadIdx.x);
-            if (t < 240 && !D0_ABL(32)) {                                           // ring slots 0 .. 59 (even columns 0 .. 58 | 30 unused | odd columns 1 .. 57)
+            if (t < 240) {                                           // ring slots 0 .. 59 (even columns 0 .. 58 | 30 unused | odd columns 1 .. 57)
                 const int base = uni((4 * k + RING) & (RING - 1));                      // ring slot of window row 0 (h row 4k - 2)
                 h8 v[8];
 #pragma unroll
@@ -422,9 +380,7 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
                 for (int j = 0; j < AR; ++j) *(h8*)(smem + j * ROWB + p4off) = fir4(v[j], v[j + 1], v[j + 2], v[j + 3]);
             }
         }
-        D0TRACE(8);
         __syncthreads();       // B3: operand image complete
-        D0TRACE(9);
         // ---- P5: stride-2 conv + skip, wave = (output row 2k + r, n half nh) ----------------------------------------------------------------
         {
             const int r = wave >> 1, nh = wave & 1;
@@ -442,11 +398,11 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) d[kk] = *(const h8*)(smem + sb[kx][kk] + ky * ROWB);
             };
-            if (!D0_ABL(64)) { rd2(0, xq[0]); rd2(1, xq[1]); }
+            rd2(0, xq[0]);
+            rd2(1, xq[1]);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
-                if (D0_ABL(64)) break;
                 if (tap + 2 < 9) rd2(tap + 2, xq[(tap + 2) % 3]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -454,7 +410,6 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
                 __builtin_amdgcn_sched_barrier(0);
             }
             __builtin_amdgcn_s_setprio(0);
-            D0TRACE(10);
             // lrelu; its sqrt2 gain cancels against the merge's 1/sqrt2.  As f4 arithmetic: v_pk_mul_f32 + v_max_f32 (24 instructions; the
             // scalar fmaxf form compiled to 48: a canonicalising v_max per operand)
 #pragma unroll
@@ -467,7 +422,7 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
             const int xslot = uni((2 * k + r) % 3);
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
-                if (!D0_ABL(64)) acc = mfma32(Wsf[kk], *(const h8*)(smem + OFF_XS + xslot * 2048 + swz(lr, kk * 2 + kh)), acc);
+                acc = mfma32(Wsf[kk], *(const h8*)(smem + OFF_XS + xslot * 2048 + swz(lr, kk * 2 + kh)), acc);
             const int orow = 2 * k + r;
             if (p.y_planar8) {
                 // chunk-planar output (four planes of 8 channels per n half): lane (px, kh) holds channels 4kh .. 4kh + 3 of planes g = 0 .. 3 —
@@ -488,7 +443,7 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
                         hi[e] = sw[1];
                     }
                     const u4x d = {lo[0], lo[1], hi[0], hi[1]};
-                    if (on && (!D0_ABL(128) || d[0] == 777u)) *(u4x*)(ypx + 2 * pr * plane) = d;
+                    if (on) *(u4x*)(ypx + 2 * pr * plane) = d;
                 }
             } else {
             // transposition through the wave's row image (32 px x 64 B), then 16-byte stores in row order
@@ -505,24 +460,14 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
             for (int u = 0; u < 2; ++u) {
                 const int v = lane + 64 * u, pix = v >> 2, chv = v & 3;
                 const h8 d = *(const h8*)(smem + OFF_RT + wave * ROWB + swz(pix, chv));
-                if (pix < TW && TW * tx + pix < Ro && orow < Ro && (!D0_ABL(128) || d[0] == (half_t)777.f)) *(h8*)(yrow + pix * 64 + chv * 8) = d;
+                if (pix < TW && TW * tx + pix < Ro && orow < Ro) *(h8*)(yrow + pix * 64 + chv * 8) = d;
             }
             __builtin_amdgcn_wave_barrier();
             }
-            D0TRACE(11);
         }
-        ++n_item;
     };
 
     __syncthreads();           // constants staged
-#ifdef GLASS_AB_KNOBS
-    if (p.skew > 0 && blockIdx.x >= (gridDim.x >> 1)) {
-        // the two workgroups of a CU start together and run identical phases: in lock-step their MFMA phases meet on the same matrix pipe
-        // and their VALU phases on the same issue port; the second half of the grid (the second workgroup of every CU under round-robin
-        // placement) starts half a step late
-        for (int i = 0; i < p.skew; ++i) __builtin_amdgcn_s_sleep(16);     // 16 x 64 clocks
-    }
-#endif
     Item cur = next_item();
     load_image(cur);
     for (;;) {
@@ -535,8 +480,7 @@ __global__ __launch_bounds__(NTHR, 2) void dblock0_kernel(D0Params p, int tiles_
 }
 
 bool dblock0_supported(int R, int Cin, int Cout) {
-    static const bool off = glass_knob("GLASS_NO_D0_FUSE") != nullptr;   // A/B knob: conv_stream<fromrgb> + conv_down instead
-    return !off && glass_lds_fits(LDS_BYTES) && R % 4 == 0 && R >= 16 && Cin == 32 && Cout == 64 && 3LL * R * R < (1LL << 31);
+    return glass_lds_fits(LDS_BYTES) && R % 4 == 0 && R >= 16 && Cin == 32 && Cout == 64 && 3LL * R * R < (1LL << 31);
 }
 
 // Returns the kernel symbol, or nullptr when the block does not qualify (caller runs the two-kernel form).
@@ -546,57 +490,14 @@ const char* launch_dblock0(const float* rgb_y, const float* rgb_w, const float* 
     D0Params p;
     p.rgb_y = rgb_y; p.rgb_w = rgb_w; p.rgb_b = rgb_b; p.w0 = w0; p.b0 = b0; p.w1 = w1; p.ws = ws; p.b1 = b1; p.y = y; p.B = B; p.R = R;
     p.y_planar8 = y_planar8;
-#if defined(GLASS_AB_KNOBS) || defined(GLASS_DEV_TRACE)
-    p.trace = nullptr;
-    static const int ablate = glass_knob("GLASS_D0_ABLATE") ? atoi(glass_knob("GLASS_D0_ABLATE")) : 0;
-    p.ablate = ablate;
-    static const int skew = glass_knob("GLASS_D0_SKEW") ? atoi(glass_knob("GLASS_D0_SKEW")) : 0;
-    p.skew = skew;
-#endif
     const int Ro = R / 2, tiles_x = (Ro + TW - 1) / TW, tiles_y = R / 4;
     const long long n_steps = (long long)B * tiles_x * tiles_y;
     if (n_steps >= (1LL << 30)) return nullptr;
     static DevOnce once;
-    once.run([&] { (void)hipFuncSetAttribute((const void*)dblock0_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); });
-    int slots = 2 * glass_cu_count();             // two 256-thread workgroups per CU (79 KB of LDS each)
-    int lds_bytes = LDS_BYTES;
-#ifdef GLASS_AB_KNOBS
-    // developer build: ONE workgroup per CU (LDS request raised so that a second one cannot be placed) — does a workgroup's step get
-    // shorter when it has the CU to itself (the pipes are contended) or not (each workgroup is latency-bound and co-residency is free)?
-    static const bool one_wg = glass_knob("GLASS_D0_ONE_WG") != nullptr;
-    if (one_wg) {
-        slots = glass_cu_count();
-        lds_bytes = 120 * 1024;
-        static DevOnce once1;
-        once1.run([&] { (void)hipFuncSetAttribute((const void*)dblock0_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024); });
-    }
-#endif
+    once.run([&] { (void)hipFuncSetAttribute((const void*)dblock0_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); });
+    const int slots = 2 * glass_cu_count();       // two 256-thread workgroups per CU (79 KB of LDS each)
     const int per_block = (int)((n_steps + slots - 1) / slots);
     const int grid = (int)((n_steps + per_block - 1) / per_block);
-#ifdef GLASS_DEV_TRACE      // dev build (make TRACE=1): traced instance, stamps of workgroup 0 to a file; synchronises, single engine only
-    if (const char* tp = getenv("GLASS_D0_TRACE")) {
-        constexpr int NTR = 96 * 16 * 4;
-        (void)hipMalloc(&p.trace, NTR * sizeof(unsigned long long));
-        (void)hipMemset(p.trace, 0, NTR * sizeof(unsigned long long));
-        (void)hipFuncSetAttribute((const void*)dblock0_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        hipLaunchKernelGGL(dblock0_kernel<true>, dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, (int)n_steps, per_block);
-        static unsigned long long hb[NTR];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(hb, p.trace, sizeof hb, hipMemcpyDeviceToHost);
-        (void)hipFree(p.trace);
-        if (FILE* f = fopen(tp, "a")) {
-            fprintf(f, "# dblock0_kernel<trace> B=%d R=%d per_block=%d: item phase t[wave0..3]\n", B, R, per_block);
-            for (int i = 0; i < 96; ++i)
-                for (int ph = 0; ph < 16; ++ph) {
-                    fprintf(f, "%d %d", i, ph);
-                    for (int w = 0; w < 4; ++w) fprintf(f, " %llu", hb[(i * 16 + ph) * 4 + w] ? hb[(i * 16 + ph) * 4 + w] - hb[0] : 0ULL);
-                    fprintf(f, "\n");
-                }
-            fclose(f);
-        }
-        return "dblock0_kernel<trace>";
-    }
-#endif
-    hipLaunchKernelGGL(dblock0_kernel<false>, dim3(grid), dim3(NTHR), lds_bytes, st, p, tiles_x, tiles_y, (int)n_steps, per_block);
+    hipLaunchKernelGGL(dblock0_kernel, dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, (int)n_steps, per_block);
     return "dblock0_kernel";
 }

@@ -72,14 +72,8 @@ struct DownParams {
     const float* b1;    // [64]
     half_t* y;          // [B][R/2][R/2][64]
     int B, R;
-    int row_walk;       // A/B knob (GLASS_ROW_WALK): round 2's row-major tile walk
-    unsigned long long* trace;   // phase timestamps of workgroup 0 (GLASS_DOWN_TRACE; nullable)
 };
-#define TRACE(ph)                                                                                                  \
-    if (TR && p.trace && blockIdx.x == 0 && (threadIdx.x & 63) == 0 && it - first < 64)                             \
-        p.trace[((it - first) * 8 + (ph)) * 4 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memtime()
 
-template <bool TR>      // TR: phase-timestamp build (dev tool); the production instance carries no trace code at all
 __global__ __launch_bounds__(256, 2) void conv_down_kernel(DownParams p, int tiles_x, int tiles_y, int n_tiles, int per_block) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Vs = smem;
@@ -102,8 +96,8 @@ __global__ __launch_bounds__(256, 2) void conv_down_kernel(DownParams p, int til
         // (PMC: 7.66 GB fetched for 4.8 GB of input).
         nx_b = uni(first / tpi);
         const int trem = first - nx_b * tpi;
-        if (p.row_walk) { nx_ty = uni(trem / tiles_x); nx_tx = uni(trem - nx_ty * tiles_x); }
-        else { nx_tx = uni(trem / tiles_y); nx_ty = uni(trem - nx_tx * tiles_y); }
+        nx_tx = uni(trem / tiles_y);
+        nx_ty = uni(trem - nx_tx * tiles_y);
     }
     // The 18 loads of a refill are NOT issued as one burst: a burst keeps the CU's address unit busy for ~2000 cycles with every
     // wave of the workgroup stalled at issue.  They go out in three groups of six, threaded between the rows of the
@@ -118,8 +112,7 @@ __global__ __launch_bounds__(256, 2) void conv_down_kernel(DownParams p, int til
         is_rs = R * CIN;
         if (nx_it + 1 < last) {        // advance the walk (uniform); past the end it stays on the last tile
             ++nx_it;
-            if (p.row_walk) { if (++nx_tx == tiles_x) { nx_tx = 0; if (++nx_ty == tiles_y) { nx_ty = 0; ++nx_b; } } }
-            else if (++nx_ty == tiles_y) { nx_ty = 0; if (++nx_tx == tiles_x) { nx_tx = 0; ++nx_b; } }
+            if (++nx_ty == tiles_y) { nx_ty = 0; if (++nx_tx == tiles_x) { nx_tx = 0; ++nx_b; } }
         } else {
             nx_it = last;
         }
@@ -174,9 +167,7 @@ __global__ __launch_bounds__(256, 2) void conv_down_kernel(DownParams p, int til
     auto step = [&](int it, RSet& Rg) {
         const int b = Rg.b, ty0 = Rg.ty0, tx0 = Rg.tx0, valid = Rg.valid;
         const int oy = 2 * ty0 - 2, ox = 2 * tx0 - 2;
-        TRACE(0);
         __syncthreads();       // B0: every wave is done with the operand image (MFMA reads, own output transposition) of the previous tile
-        TRACE(1);
         // ---- vertical FIR on this thread's window column -> LDS; edge vector parked raw -----------------------------
         {
             const int t = opaque(threadIdx.x), cg = t & 3, cs = t >> 2;
@@ -195,12 +186,9 @@ __global__ __launch_bounds__(256, 2) void conv_down_kernel(DownParams p, int til
             if (t < 144) *(h8*)(smem + OFF_EM + t * 16) = fir4(Rg.e[0], Rg.e[1], Rg.e[2], Rg.e[3]);   // [row][edge column][cg]
         }
         const h8 xs0 = Rg.s[0], xs1 = Rg.s[1];     // this tile's skip fragments (the set is refilled next)
-        TRACE(2);
         issue_begin(Rg);       // refill, first third (two tiles of window loads stay in flight)
         issue_rows(Rg, 0);
-        TRACE(3);
         __syncthreads();       // B1: vertical-pass image complete
-        TRACE(4);
         // ---- horizontal FIR: each wave owns whole rows and rewrites them in place as the operand image ------------------
         {
             const int t = opaque(threadIdx.x), lane = t & 63, wave = uni(t >> 6);
@@ -239,9 +227,7 @@ __global__ __launch_bounds__(256, 2) void conv_down_kernel(DownParams p, int til
             issue_rest(Rg);                          // refill, last third
             if (wave == 0) hrow(8);
         }
-        TRACE(5);
         __syncthreads();       // B2: operand image complete
-        TRACE(6);
         // ---- MFMA: 9 taps x 2 k16 steps x 2 n blocks; wave = output row ty0 + wave -------------------------------------------
         const int tm = opaque(threadIdx.x), lr = tm & 31, kh = (tm >> 5) & 1, wave = uni(tm >> 6);
         f16x acc[2];
@@ -264,7 +250,6 @@ __global__ __launch_bounds__(256, 2) void conv_down_kernel(DownParams p, int til
                     }
                     if (kk && kx == 2) __builtin_amdgcn_sched_barrier(0);   // one tap ROW's fragments live at a time (the window sets own the registers)
                 }
-        TRACE(7);
         // ---- activation in the accumulators, then the skip branch on top -------------------------------------------------------
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -320,8 +305,7 @@ __global__ __launch_bounds__(256, 2) void conv_down_kernel(DownParams p, int til
 }
 
 bool conv_down_supported(int R, int Cin, int Cout) {
-    static const bool off = glass_knob("GLASS_NO_DOWN") != nullptr;   // A/B knob
-    return !off && glass_lds_fits(LDS_BYTES) && R % 64 == 0 && R >= 64 && Cin == CIN && Cout == NT && (long long)R * R * Cin < (1LL << 31);
+    return glass_lds_fits(LDS_BYTES) && R % 64 == 0 && R >= 64 && Cin == CIN && Cout == NT && (long long)R * R * Cin < (1LL << 31);
 }
 
 // Returns the kernel symbol, or nullptr when the block does not qualify (caller runs the separate passes).
@@ -330,45 +314,14 @@ const char* launch_conv_down(const half_t* h, const half_t* xs, const half_t* w1
     if (!conv_down_supported(R, Cin, Cout)) return nullptr;
     DownParams p;
     p.h = h; p.xs = xs; p.w1 = w1; p.ws = ws; p.b1 = b1; p.y = y; p.B = B; p.R = R;
-    p.trace = nullptr;
-    static const bool row_walk = glass_knob("GLASS_ROW_WALK") != nullptr;
-    p.row_walk = row_walk ? 1 : 0;
-    const char* trace_path = nullptr;
-#ifdef GLASS_DEV_TRACE      // dev build (make TRACE=1): per-phase shader-clock timestamps of workgroup 0; synchronises, single engine only
-    trace_path = getenv("GLASS_DOWN_TRACE");
-#endif
-    if (trace_path) (void)hipMalloc(&p.trace, 64 * 8 * 4 * sizeof(unsigned long long));
-    if (p.trace) (void)hipMemsetAsync(p.trace, 0, 64 * 8 * 4 * sizeof(unsigned long long), st);
     const int Ro = R / 2, tiles_x = Ro / 32, tiles_y = Ro / TH;
     const long long tiles = (long long)B * tiles_x * tiles_y;
     if (tiles >= (1LL << 30)) return nullptr;
     static DevOnce once;
-    once.run([&] {
-        (void)hipFuncSetAttribute((const void*)conv_down_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_down_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    });
+    once.run([&] { (void)hipFuncSetAttribute((const void*)conv_down_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); });
     const int slots = glass_cu_count() * 2;
     const int per_block = (int)((tiles + slots - 1) / slots);
     const int grid = (int)((tiles + per_block - 1) / per_block);
-    if (p.trace) hipLaunchKernelGGL(conv_down_kernel<true>, dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, (int)tiles, per_block);
-    else hipLaunchKernelGGL(conv_down_kernel<false>, dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, (int)tiles, per_block);
-    if (p.trace) {
-        static unsigned long long hbuf[64 * 8 * 4];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(hbuf, p.trace, sizeof hbuf, hipMemcpyDeviceToHost);
-        (void)hipFree(p.trace);
-        if (FILE* f = fopen(trace_path, "w")) {
-            fprintf(f, "# tile phase: t[wave0..3] (shader clocks, relative to the first stamp); phases: 0 enter, 1 after B0, 2 after vertical pass, "
-                       "3 after refill issue, 4 after B1, 5 after horizontal pass, 6 after B2, 7 after main MFMAs; per_block=%d\n", per_block);
-            const unsigned long long t0 = hbuf[0];
-            for (int i = 0; i < 64 && i < per_block; ++i)
-                for (int ph = 0; ph < 8; ++ph) {
-                    fprintf(f, "%d %d", i, ph);
-                    for (int w = 0; w < 4; ++w) fprintf(f, " %llu", hbuf[(i * 8 + ph) * 4 + w] ? hbuf[(i * 8 + ph) * 4 + w] - t0 : 0ULL);
-                    fprintf(f, "\n");
-                }
-            fclose(f);
-        }
-    }
+    hipLaunchKernelGGL(conv_down_kernel, dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, (int)tiles, per_block);
     return "conv_down_kernel";
 }

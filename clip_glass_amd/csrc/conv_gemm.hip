@@ -94,9 +94,8 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(ConvParams p, const fl
 
 // cap_a / cap_c: scratch capacity PER CANDIDATE (halfs of A, floats of C); the buffers hold p.B candidates
 const char* launch_conv_gemm(const ConvParams& p, half_t* ws_a, long long cap_a, float* ws_c, long long cap_c, hipStream_t st) {
-    static const bool off = glass_knob("GLASS_NO_CONV_GEMM") != nullptr;   // A/B knob: these layers stay on conv_direct
     if (p.x_planar8 || p.y_planar8 || p.x_planar32) return nullptr;   // chunk-planar maps (common.h): not implemented here
-    if (off || !ws_a || !ws_c || p.y32 || !p.y || p.w_bstride != 0 || p.rgb_y || p.trgb_yout || p.skip_x) return nullptr;
+    if (!ws_a || !ws_c || p.y32 || !p.y || p.w_bstride != 0 || p.rgb_y || p.trgb_yout || p.skip_x) return nullptr;
     if (p.pre_shift && !p.sn) return nullptr;
     if (p.xs_out || p.post_scale16) return nullptr;   // by-products / output transforms this path does not implement: refuse, never ignore
     if ((p.KS != 1 && p.KS != 3) || p.Cin % 64 != 0 || p.Neff % 64 != 0 || (p.Cout & 3) || (p.res_cs & 3)) return nullptr;
@@ -113,8 +112,7 @@ const char* launch_conv_gemm(const ConvParams& p, half_t* ws_a, long long cap_a,
     if (p.dry_run) return direct_y ? "gemm_tiled_kernel" : "conv_gemm(im2col+gemm_tiled+finish)";
     // no activation-side transform of the input (the D blocks' convolutions): the GEMM's loader walks the map itself (GemmParams::g_*,
     // gemm_tiled_kernel<.., gather>) — the patch matrix, a 9x copy of the map written to HBM and read back, is never materialised (round 6)
-    static const bool no_gather = glass_knob("GLASS_CONV_GEMM_NO_GATHER") != nullptr;   // A/B knob
-    bool gather = !no_gather && !direct_a && !p.sn && !p.pre_shift && !p.in_up && p.Cin % 64 == 0;
+    bool gather = !direct_a && !p.sn && !p.pre_shift && !p.in_up && p.Cin % 64 == 0;
     GemmParams g;
     memset(&g, 0, sizeof g);
     auto set_gather = [&](bool on) {
@@ -137,9 +135,8 @@ const char* launch_conv_gemm(const ConvParams& p, half_t* ws_a, long long cap_a,
     // split-K (round 3): a 4 x 4 / 8 x 8 grid per candidate is 16 / 64 rows — at 64 candidates the product has 64 / 256 tiles walking
     // 72 K steps each.  S slices (a function of the per-candidate geometry only, like every choice here) of raw sums, added in a fixed
     // order by the finishing pass; the scratch holds them while S x grid x Neff fits its per-candidate capacity.
-    static const bool no_split = glass_knob("GLASS_CONV_GEMM_NO_SPLIT") != nullptr;   // A/B knob
     int S = 1;
-    if (!no_split && p.KS == 3) {
+    if (p.KS == 3) {
         const int px = p.Hc * p.Wc;
         S = px <= 16 ? 4 : (px <= 64 ? 2 : 1);
         while (S > 1 && (K % (64LL * S) != 0 || (long long)S * px * p.Neff > cap_c)) S >>= 1;

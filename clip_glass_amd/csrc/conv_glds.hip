@@ -720,7 +720,6 @@ static const char* launch_glds_inst(const ConvParams& p, hipStream_t st, const c
     const int PT = p.B * tiles_x * tiles_y;
     const int NTn = p.Neff / NT;
     const int PT8 = (PT + 7) / 8 * 8;
-    static const bool no_persist = glass_knob("GLASS_NO_GLDS_PERSIST") != nullptr;   // A/B knob: one work item per workgroup
     const int n_cu = glass_cu_count() - glass_cu_count() % 8;       // a workgroup keeps its XCD (id % 8) across items
     static DevOnce once_p;
     once_p.run([&] {
@@ -734,7 +733,7 @@ static const char* launch_glds_inst(const ConvParams& p, hipStream_t st, const c
     // (>= 2 work items per CU at the NOMINAL population, common.h: this branch also decides whether the blur-down by-product exists,
     // so it must be a function of the layer geometry only)
     const long long work_nominal = (long long)GLASS_NOMINAL_POP * tiles_x * tiles_y * NTn;
-    if (TW == 32 && !no_persist && (p.Cin & 63) == 0 && work_nominal >= 2 * n_cu) {   // ring parity needs an even chunk count
+    if (TW == 32 && (p.Cin & 63) == 0 && work_nominal >= 2 * n_cu) {   // ring parity needs an even chunk count
         // (reported under the symbol that runs, so that the per-kernel profile lines up with rocprofv3's kernel names)
         const bool xs = p.xs_out && !TRGB, sty = p.sn16 != nullptr;
         const char* pname = xs ? (sty ? "conv_gldsp_kernel<false,true,true>" : "conv_gldsp_kernel<false,true,false>")
@@ -754,13 +753,12 @@ static const char* launch_glds_inst(const ConvParams& p, hipStream_t st, const c
     return name;
 }
 
-const char* launch_conv_glds(const ConvParams& p0, hipStream_t st, bool force) {
+const char* launch_conv_glds(const ConvParams& p0, hipStream_t st) {
     ConvParams p = p0;
     if (const char* k = launch_conv_wreg(p, st)) return k;     // 64 -> 64 channels: the weights-in-registers form (conv_wreg.hip)
     if (p.x_planar8 || p.y_planar8 || p.x_planar32) return nullptr;   // chunk-planar maps (common.h): not implemented here
-    static const bool on = glass_knob("GLASS_NO_GLDS") == nullptr;   // A/B knob: GLASS_NO_GLDS=1 falls back to conv_tiled
     if (!glass_lds_fits(Geo<32>::LDS_BYTES) || !glass_lds_fits(Geo<16>::LDS_BYTES)) return nullptr;
-    if ((!on && !force) || p.up || (p.xs_out && (p.sn || p.trgb_yout || p.Wc % 32 != 0)) || p.y32 || !p.y || p.KS != 3 || p.stride != 1 || p.pad != 1) return nullptr;
+    if (p.up || (p.xs_out && (p.sn || p.trgb_yout || p.Wc % 32 != 0)) || p.y32 || !p.y || p.KS != 3 || p.stride != 1 || p.pad != 1) return nullptr;
     if ((p.sn && !p.sn16) || p.pre_shift || p.in_up || p.Cin > 1024 || (p.x_bstride == 0 && p.B > 1)) return nullptr;
     if (p.Cin % 32 != 0 || p.Cin < 128 || p.Neff % NT != 0 || (p.Cout & 7) || p.Hc % 16 != 0) return nullptr;
     if ((long long)p.H * p.W * p.Cin >= (1LL << 31)) return nullptr;

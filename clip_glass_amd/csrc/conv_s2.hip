@@ -28,12 +28,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-// dev tool (GLASS_S2_TRACE=path): shader-clock stamps of the first stages of ONE workgroup in the middle of the grid (TR instance only)
-__device__ unsigned long long* g_s2_trace = nullptr;
-#define S2TRACE(ph) \
-    if (TR && blockIdx.x == gridDim.x / 2 + 3 && (threadIdx.x & 63) == 0 && gst < 96) \
-        g_s2_trace[(gst * 8 + (ph)) * 8 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memtime()
-
 namespace {
 constexpr int NT = 128, NTHR = 512, TH = 8;
 constexpr int PXR = 65;                                  // input pixels per patch row
@@ -62,7 +56,6 @@ __device__ __forceinline__ int opq(int v) { asm volatile("" : "+v"(v)); return v
 #define S2_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 }  // namespace
 
-template <bool TR, bool IL>
 __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, int tiles_x, int tiles_y, int PT) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -194,7 +187,6 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
     issue_odd(cs, 0);
     issue_even(cs, 0);
     issue_w(cs, 0, 1, 1);
-    int gst = 0;                                // (trace only) stages run so far
     int slot = 0;                               // weight slot of the stage about to run (stage g lives in slot g % 3)
     const int wr = wave & 3, wn = wave >> 2;
     for (;;) {
@@ -219,7 +211,6 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
             const int nc = last_c ? 0 : c + 1;
 #pragma unroll
             for (int f = 0; f < 4; ++f) {
-                S2TRACE(0);
                 // s_waitcnt vmcnt(N), N = DMA instructions this wave issued AFTER the last operand of this stage (the counter retires in order):
                 if (f == 0) {                      // even(c) [na_e], W(g + 1) [3] behind odd(c) / W(g)
                     if (na_e == 5) S2_WAIT(8); else S2_WAIT(7);
@@ -230,9 +221,7 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
                 } else {                           // W(g + 1) [3] behind the skip weights
                     if (more) S2_WAIT(3); else S2_WAIT(0);
                 }
-                S2TRACE(1);
                 __builtin_amdgcn_s_barrier();      // this stage's operands are visible to every wave; whatever stage g - 1 read is free
-                S2TRACE(2);
                 const int slot2 = slot == 0 ? 2 : slot - 1;          // (g + 2) % 3
                 // the i-th DMA instruction of this stage (the order fixes the vmcnt counts above):
                 //   f = 0: skip operand(c) [2], W(g + 2) [3]        f = 1: odd(c + 1) [<= 5], skip weights [1]
@@ -251,11 +240,6 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
                         else if (i < 8 && more) w_piece(nsrc, nc, 1, slot2, i - 5);
                     }
                 };
-                if (!IL) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) piece(i);
-                }
-                S2TRACE(3);
                 // ---- MFMAs ---------------------------------------------------------------------------------------------------------
                 const int tm = opq(threadIdx.x), lr = tm & 31, kh = (tm >> 5) & 1;
                 const char* Ws = smem + OFF_W + slot * W_SLOT;
@@ -283,10 +267,9 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
                                 const int P = prow * PXR + q;
                                 xf[i] = *(const h8*)(As + P * 64 + ((lc ^ ((P >> 2) & 3)) << 4));
                             }
-                            if (IL) {               // one DMA instruction per block of 4 MFMAs: its issue cost hides under the MFMAs in flight
-                                piece(tx * 2 + kk);
-                                if (tx == 2 && kk == 1) { piece(6); piece(7); }
-                            }
+                            // one DMA instruction per block of 4 MFMAs: its issue cost hides under the MFMAs in flight
+                            piece(tx * 2 + kk);
+                            if (tx == 2 && kk == 1) { piece(6); piece(7); }
 #pragma unroll
                             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -310,10 +293,8 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
                             const int P = (wr * 2 + i) * 32 + lr;
                             xf[i] = *(const h8*)(Xs + P * 64 + ((lc ^ ((P >> 2) & 3)) << 4));
                         }
-                        if (IL) {
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) piece(kk * 4 + i);
-                        }
+                        for (int i = 0; i < 4; ++i) piece(kk * 4 + i);
 #pragma unroll
                         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -321,8 +302,6 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
                     }
                 }
                 __builtin_amdgcn_s_setprio(0);
-                S2TRACE(4);
-                if (TR) ++gst;
                 slot = slot == 2 ? 0 : slot + 1;
             }
         }
@@ -334,7 +313,6 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
             const int t = opq(threadIdx.x), lane = t & 63, lr = lane & 31, kh = lane >> 5;
             const float* Cc = (const float*)(smem + OFF_C) + n0;
             __builtin_amdgcn_s_barrier();          // every wave is done with the skip operand buffer (its LDS reads have returned)
-            if (TR) { --gst; S2TRACE(5); }
             char* Os = smem + OFF_XS + wave * 2048;
             const ActK ak = act_consts(p.act, p.out_scale);
             const int oyb = ty0 + wr * 2;
@@ -368,7 +346,6 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
                 }
             }
         }
-        if (TR) { S2TRACE(6); ++gst; }
         if (!has_next) break;
         id = nid;
         cur = nxt;
@@ -376,7 +353,7 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
     }
 }
 
-// Tried and dropped (round 3, same-box A/B on the four D layers; tools/trace_s2.py stamps): a two-stage version — skip + ky 1 /
+// Tried and dropped (round 3, same-box A/B on the four D layers; phase-trace stamps): a two-stage version — skip + ky 1 /
 // ky 0 + ky 2, weights double-buffered as 32 + 48 KB, the skip operand loaded straight into registers, fragment reads software-pipelined
 // one MFMA block ahead — was 3-6 % SLOWER (3.09 vs 2.92 ms): half the barriers, but one stage of DMA lead instead of two, and the waits
 // at the stage tops grew by what the barriers saved.  Bunching a stage's DMA instructions at its front is worse again (+4 %): eight waves'
@@ -386,9 +363,8 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
 // what this tile shape gives; a bigger tile does not fit 160 KB of LDS / 256 registers.
 
 const char* launch_conv_s2(const ConvParams& p, hipStream_t st, bool force) {
-    static const bool off = glass_knob("GLASS_NO_S2DMA") != nullptr;      // A/B knob: the register-staged conv_tiled<3,2,4,128,skip> instead
     if (p.x_planar8 || p.y_planar8) return nullptr;   // chunk-planar maps (common.h): not implemented here
-    if ((off && !force) || !p.skip_x || !p.skip_w || p.KS != 3 || p.stride != 2 || p.pad != 0 || p.up || p.y32 || !p.y) return nullptr;
+    if (!p.skip_x || !p.skip_w || p.KS != 3 || p.stride != 2 || p.pad != 0 || p.up || p.y32 || !p.y) return nullptr;
     if (p.res || p.dscale || p.noise || p.shift || p.sn || p.pre_shift || p.in_up || p.xs_out || p.trgb_yout || p.post_scale16 || p.rgb_y) return nullptr;
     if (p.Neff != p.Cout || p.Neff % NT != 0 || p.Neff > MAX_N || p.Cin % 32 != 0 || p.Hc % TH != 0 || p.Wc % 32 != 0) return nullptr;
     if (p.H != 2 * p.Hc + 1 || p.W != 2 * p.Wc + 1 || p.Ho != p.Hc || p.Wo != p.Wc || p.w_bstride != 0) return nullptr;
@@ -407,42 +383,8 @@ const char* launch_conv_s2(const ConvParams& p, hipStream_t st, bool force) {
     if (p.dry_run) return "conv_s2_kernel";
     static DevOnce once;
     once.run([&] {
-        (void)hipFuncSetAttribute((const void*)conv_s2_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-#ifdef GLASS_DEV_TRACE
-        (void)hipFuncSetAttribute((const void*)conv_s2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-#endif
-        (void)hipFuncSetAttribute((const void*)conv_s2_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)conv_s2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     });
-#ifdef GLASS_DEV_TRACE      // dev build (make TRACE=1): traced instance, stamps to a file; synchronises, single engine only
-    if (const char* tp = getenv("GLASS_S2_TRACE")) {          // dev tool: traced instance, stamps to a file
-        unsigned long long* dtr = nullptr;
-        constexpr int NTR = 96 * 8 * 8;
-        (void)hipMalloc(&dtr, NTR * sizeof(unsigned long long));
-        (void)hipMemset(dtr, 0, NTR * sizeof(unsigned long long));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_s2_trace), &dtr, sizeof dtr);
-        hipLaunchKernelGGL((conv_s2_kernel<true, true>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT);
-        static unsigned long long hb[NTR];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(hb, dtr, sizeof hb, hipMemcpyDeviceToHost);
-        (void)hipFree(dtr);
-        if (FILE* f = fopen(tp, "a")) {
-            fprintf(f, "# conv_s2_kernel<trace> Cin=%d Cout=%d Hc=%d B=%d: stage phase t[wave0..7]; phases 0 top, 1 operands landed, 2 after barrier, 3 DMAs issued, 4 MFMAs done, 5 epilogue barrier, 6 epilogue done\n", p.Cin, p.Cout, p.Hc, p.B);
-            for (int i = 0; i < 96; ++i)
-                for (int ph = 0; ph < 7; ++ph) {
-                    fprintf(f, "%d %d", i, ph);
-                    for (int w = 0; w < 8; ++w) fprintf(f, " %llu", hb[(i * 8 + ph) * 8 + w] ? hb[(i * 8 + ph) * 8 + w] - hb[0] : 0ULL);
-                    fprintf(f, "\n");
-                }
-            fclose(f);
-        }
-        return "conv_s2_kernel<trace>";
-    }
-#endif
-    static const bool no_il = glass_knob("GLASS_S2_NO_IL") != nullptr;     // A/B knob: every DMA of a stage issued before its MFMAs
-    if (no_il) {
-        hipLaunchKernelGGL((conv_s2_kernel<false, false>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT);
-        return "conv_s2_kernel<noil>";
-    }
-    hipLaunchKernelGGL((conv_s2_kernel<false, true>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT);
+    hipLaunchKernelGGL(conv_s2_kernel, dim3(grid), dim3(NTHR), LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT);
     return "conv_s2_kernel";
 }

@@ -34,13 +34,6 @@ __device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); retur
 __device__ __forceinline__ int swa(int pr, int pc, int chunk) { return ((pr * PP + pc) << 6) + ((chunk ^ ((pc >> 2) & 3)) << 4); }
 }  // namespace
 
-// dev tool (GLASS_STREAM_TRACE=path): phase timestamps (shader clocks) of workgroup 0, first 64 tiles; the production
-// instance (TR = false) carries no trace code
-__device__ unsigned long long* g_stream_trace = nullptr;
-#define STRACE(ph) \
-    if (TR && blockIdx.x == 0 && (threadIdx.x & 63) == 0 && id - first < 64) \
-        g_stream_trace[((id - first) * 8 + (ph)) * 4 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memtime()
-
 // FRGB: the input map is produced on the fly from the skip image y (D's fromRGB, stylegan2/models.py:1125-1143: biggan
 // denorm(norm(y)) -> 1x1 conv 3 -> 32 + bias + lrelu*sqrt2), 12 bytes per pixel read instead of 64; the tile's interior
 // of that map can be written out (p.rgb_x_out) and / or its FIR (pad 1) + ::2 (p.rgb_xs_out) for the D block's skip path.
@@ -54,6 +47,8 @@ __device__ unsigned long long* g_stream_trace = nullptr;
 // image row, 4-6 / 12-14 for the second: lane half kh then owns image row kh), so the product matches the fp32 pass's to ~1e-7.
 template <bool FRGB, bool TRGB, bool TR = false>
 __global__ __launch_bounds__(256, 3) void conv_stream_kernel(ConvParams p, int tiles_x, int tiles_y, int PT, int per_block) {
+    // TR (the removed phase-trace instance) stays in the parameter list: bench.py reads this kernel's labels by template-argument position
+    static_assert(!TR, "placeholder of a removed experiment");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ws = smem;
     char* As = smem + W_BYTES;
@@ -195,9 +190,7 @@ __global__ __launch_bounds__(256, 3) void conv_stream_kernel(ConvParams p, int t
     auto step = [&](int id, const Cur& cc, const Cur& lc, RSet& R) {
         const bool valid = id < last;
         const int b = cc.b, ty0 = cc.ty * TH, tx0 = cc.tx * 32;
-        STRACE(0);
         __syncthreads();                           // every wave is done reading As / Ws of the previous tile
-        STRACE(1);
         if (wb != b && (TRGB || wb < 0 || p.w_bstride != 0 || p.dscale || p.shift || p.sn16)) {
             const half_t* wsrc = p.w + (long long)b * p.w_bstride;   // [9][32][32]
             for (int u = t; u < 9 * 32 * 4; u += 256)
@@ -301,11 +294,8 @@ __global__ __launch_bounds__(256, 3) void conv_stream_kernel(ConvParams p, int t
                 for (int ch = 0; ch < 3; ++ch) Ys[ch * 85 + r * 17 + col] = ok ? R.ys[ch] : 0.f;
             }
         }
-        STRACE(2);
         __syncthreads();
-        STRACE(3);
         const float nz0 = p.noise ? p.noise_strength * R.nz[0] : 0.f, nz1 = p.noise ? p.noise_strength * R.nz[1] : 0.f;
-        STRACE(4);
 
         f16x acc[2];
 #pragma unroll
@@ -332,8 +322,6 @@ __global__ __launch_bounds__(256, 3) void conv_stream_kernel(ConvParams p, int t
                 }
             }
         __builtin_amdgcn_s_setprio(0);
-
-        STRACE(5);
         if (FRGB && p.rgb_xs_out && valid) {
             // the D block's skip branch wants FIR 4x4 (pad 1) + ::2 of the fromRGB map (modules.py:1238-1254 via 1587-1601): the
             // 8 x 32 tile (+ halo, zeros outside the image) sits in LDS, so its 4 x 16 down-sampled pixels are 16 reads + 5
@@ -351,7 +339,6 @@ __global__ __launch_bounds__(256, 3) void conv_stream_kernel(ConvParams p, int t
             const h8 o = (hr[0] + hr[3]) * (half_t)0.125f + (hr[1] + hr[2]) * (half_t)0.375f;
             *(h8*)(p.rgb_xs_out + (((long long)b * (p.H >> 1) + (ty0 >> 1) + ly) * (p.W >> 1) + (tx0 >> 1) + lx) * 32 + part * 8) = o;
         }
-        STRACE(6);
         // ---- epilogue: lane = pixel lr of tile row (wave*2 + i); quads of 4 consecutive channels.  fp32 up to the activation
         // input (acc * demod + noise + bias), then packed fp16: act 0 / 1 / 2 = max(v * k1, v * k2) with (k1, k2) =
         // (s, s) / (sqrt2 s, 0.2 sqrt2 s) / (s, 0) -------------------------------------------------------------------------------
@@ -457,11 +444,10 @@ static int stream_slots() {
 }
 
 bool conv_stream_applies(const ConvParams& p) {
-    static const bool off = glass_knob("GLASS_NO_STREAM") != nullptr;   // experiment knob
     const bool trgb = p.trgb_yout != nullptr;
     if (!glass_lds_fits(LDS_BYTES)) return false;
     if (p.x_planar8 || p.y_planar8 || p.x_planar32) return false;   // chunk-planar maps (common.h): not implemented here
-    if (off || p.up || p.xs_out || p.y32 || (!p.y && !trgb) || p.KS != 3 || p.stride != 1 || p.pad != 1 || (p.sn && !p.sn16)) return false;
+    if (p.up || p.xs_out || p.y32 || (!p.y && !trgb) || p.KS != 3 || p.stride != 1 || p.pad != 1 || (p.sn && !p.sn16)) return false;
     const bool frgb = p.rgb_y != nullptr;
     if (frgb && (!p.rgb_w || !p.rgb_b || (!p.rgb_x_out && !p.rgb_xs_out) || p.sn || trgb)) return false;
     if (trgb && (!p.trgb_w || !p.trgb_b || !p.trgb_sn || !p.trgb_smax || p.Ho != p.Hc || p.Wo != p.Wc)) return false;
@@ -478,10 +464,9 @@ bool conv_stream_applies(const ConvParams& p) {
 const char* launch_conv_stream(const ConvParams& p0, hipStream_t st) {
     if (!conv_stream_applies(p0)) return nullptr;
     ConvParams p = p0;
-    static const bool row_walk = glass_knob("GLASS_ROW_WALK") != nullptr;      // A/B knob: round 2's row-major tile walk
     // measured (same box, column vs row walk): <torgb> 1821 vs 1844 us, conv_down 1762 vs 1823 us, <fromrgb> 2593 vs 2530 us — the
     // planar fp32 image the fromRGB form reads is friendlier to the row-major walk
-    p.row_walk = (row_walk || p.rgb_y) ? 1 : 0;
+    p.row_walk = p.rgb_y ? 1 : 0;
     const bool trgb = p.trgb_yout != nullptr, frgb = p.rgb_y != nullptr;
     const int tiles_x = p.Wc / 32, tiles_y = p.Hc / TH;
     const int PT = p.B * tiles_x * tiles_y;
@@ -489,36 +474,6 @@ const char* launch_conv_stream(const ConvParams& p0, hipStream_t st) {
     const int per_block = (PT + slots - 1) / slots;
     const int grid = (PT + per_block - 1) / per_block;
     const char* name = frgb ? "conv_stream_kernel<fromrgb>" : trgb ? "conv_stream_kernel<torgb>" : "conv_stream_kernel";
-#ifdef GLASS_DEV_TRACE      // dev build (make TRACE=1): traced instance, one launch, timestamps to a file; synchronises, single engine only
-    if (const char* trace_path = getenv("GLASS_STREAM_TRACE")) {       // dev tool: traced instance, one launch, timestamps to a file
-        unsigned long long* dtr = nullptr;
-        (void)hipMalloc(&dtr, 64 * 8 * 4 * sizeof(unsigned long long));
-        (void)hipMemset(dtr, 0, 64 * 8 * 4 * sizeof(unsigned long long));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stream_trace), &dtr, sizeof dtr);
-        (void)hipFuncSetAttribute((const void*)conv_stream_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_stream_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_stream_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (frgb) hipLaunchKernelGGL((conv_stream_kernel<true, false, true>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);
-        else if (trgb) hipLaunchKernelGGL((conv_stream_kernel<false, true, true>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);
-        else hipLaunchKernelGGL((conv_stream_kernel<false, false, true>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);
-        static unsigned long long hb[64 * 8 * 4];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(hb, dtr, sizeof hb, hipMemcpyDeviceToHost);
-        (void)hipFree(dtr);
-        if (FILE* f = fopen(trace_path, "a")) {
-            fprintf(f, "# %s: tile phase t[wave0..3]; phases 0 enter, 1 after sync, 2 patch staged, 3 after sync, 4 refill issued, "
-                       "5 MFMAs done, 6 skip by-product done, (next 0) epilogue done; per_block=%d\n", name, per_block);
-            for (int i = 0; i < 64 && i < per_block; ++i)
-                for (int ph = 0; ph < 7; ++ph) {
-                    fprintf(f, "%d %d", i, ph);
-                    for (int w = 0; w < 4; ++w) fprintf(f, " %llu", hb[(i * 8 + ph) * 4 + w] - hb[0]);
-                    fprintf(f, "\n");
-                }
-            fclose(f);
-        }
-        return name;
-    }
-#endif
     if (frgb) hipLaunchKernelGGL((conv_stream_kernel<true, false, false>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);
     else if (trgb) hipLaunchKernelGGL((conv_stream_kernel<false, true, false>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);
     else hipLaunchKernelGGL((conv_stream_kernel<false, false, false>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);

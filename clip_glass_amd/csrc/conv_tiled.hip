@@ -32,15 +32,7 @@ __device__ __forceinline__ int tl_row(int r) { return (r & ~7) | ((r & 7) >> 1) 
 // the 64 banks exactly (4 LDS cycles instead of 8)
 __device__ __forceinline__ int tl_col(int ci) { return ci ^ (((ci >> 2) ^ (ci >> 1)) & 1); }
 
-// dev tool (GLASS_TILED_TRACE=path): shader-clock stamps of the K stages of ONE workgroup in the middle of the grid (TR instance only)
-__device__ unsigned long long* g_tiled_trace = nullptr;
-#define TTRACE(ph) \
-    if (TR && blockIdx.x == gridDim.x / 2 && (threadIdx.x & 63) == 0 && s < 64) \
-        g_tiled_trace[(s * 8 + (ph)) * 4 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memtime()
-
-// PERSIST: the block walks several work items and prefetches the first stage of the next tile during
-// the last MFMA block + store epilogue of the current one (memory-bound small-K layers); otherwise
-// one work item per block (MFMA-bound layers: fewer live registers).
+// One work item (pixel tile, n tile) per block.
 // TRGB (fast path, TH = 8, one n tile = all output channels): toRGB + skip-image sum of the block (stylegan2/models.py:852-870,
 // 1004-1013) applied to the finished tile while it is in registers (common.h: 2 MFMAs per 32 channels per tile row) — the
 // separate toRGB pass would re-read the whole map.
@@ -49,11 +41,13 @@ __device__ unsigned long long* g_tiled_trace = nullptr;
 // XS (3x3 stride 1, TH = 8, one n tile): ConvParams::xs_out — the blur-down of the input map from the patch already in LDS.
 // SPL: the four waves form a 2 x 2 grid (row pair x n half) instead of 4 x 1: each weight fragment a wave reads feeds two tile rows
 // (stride-2 convs, TH = 4: 8 fragment reads per 8 MFMAs instead of 10).
-// B2: the weight slices alternate between TWO register sets and are requested two stages ahead (costs NB * 4 VGPRs).
 // DEEP: the next chunk's patch is requested as soon as this chunk's patch is in LDS (three stages ahead instead of one).
+// PERSIST, B2 and TR (removed experiments: persistent blocks, two weight register sets, phase trace) stay in the parameter list because
+// bench.py reads this kernel's labels by template-argument position.
 template <int KS, int S, int TH, int NT, bool PERSIST = false, bool TRGB = false, bool SKIP = false, bool XS = false, bool SPL = false, bool B2 = false,
           bool DEEP = false, bool TR = false>
 __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void conv_tiled_kernel(ConvParams p, int NTn, int tiles_x, int tiles_y, int PT) {
+    static_assert(!PERSIST && !B2 && !TR, "placeholders of removed experiments");
     constexpr int RW = SPL ? TH / 2 : TH / 4;  // tile rows per wave
     constexpr int NJ = SPL ? NT / 64 : NT / 32; // 32-wide n tiles per wave
     constexpr int PH = (TH - 1) * S + KS;      // patch rows
@@ -79,8 +73,8 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
     const int PT8 = (PT + 7) & ~7;
     const int n_work = PT8 * NTn;              // work items = (pixel tile, n tile)
 
-    // ---- persistent block: work items id, id + gridDim.x, ...  An item decodes to (pixel tile, n tile)
-    // such that the n-tiles of one pixel tile sit on one XCD (id % 8) and share its L2. -------------
+    // ---- work items: an item decodes to (pixel tile, n tile) such that the n-tiles of one pixel tile sit on one XCD (id % 8) and
+    // share its L2 -------------
     struct Tile { int b, ty0, tx0, n0; bool valid; };
     auto decode = [&](int id) {
         Tile w;
@@ -96,7 +90,7 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
         return w;
     };
 
-    // staging state of the tile being LOADED (may be one tile ahead of the tile being computed).
+    // staging state of the tile being LOADED.
     // Loads are UNCONDITIONAL (vectors outside the image / past the patch read a valid address) and masked when they are
     // written to LDS, on border tiles only; the per-vector LDS offsets are computed once per tile; every option of the input
     // transform is tested on the (uniform) launch parameters, not on per-thread pointers — round 2's instruction diet: the
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
     };
     static_assert(PH * PW * ROWB + 64 < 65536, "LDS offsets are packed in 16 bits");
 
-    h8 ra[NA], rb[NB], rb2[B2 ? NB : 1];   // B2: two weight-stage register sets, stage s is stored from set s & 1
+    h8 ra[NA], rb[NB];
     h8 sh;   // style of this thread's 8 channels of the current chunk (fp16: packed multiply at staging)
     int ld_c0 = 0;   // chunk offset of the patch held in ra (pre-activation shift is fetched at store time)
 #pragma unroll
@@ -198,28 +192,18 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
     if (id >= n_work) return;
     // per-channel epilogue constants of this block's n tile (demod scale, bias, shift) are parked in LDS by the epilogue
     // prologue: one batched round trip instead of one per accumulator quad
-    const bool fast = TRGB || SKIP || (!PERSIST && !p.up && (p.Cout & 7) == 0 && !p.no_tstore);
+    const bool fast = TRGB || SKIP || (!p.up && (p.Cout & 7) == 0);
     float* Cc = (float*)(smem + CC_OFF);   // [3][NT]
     char* Tt = smem + CC_OFF + 3 * NT * 4;  // TRGB: this sample's weight tables [2][16][NT] fp16
     // DEEP prefetch (round 3): every register-staged kernel ran at ~3.3 us per K stage whatever its MFMA count (24 - 36 per
     // wave = 0.3 - 0.5 us) — one stage of prefetch distance means every stage waits out a loaded L2 / HBM round trip.  The patch
     // of the NEXT chunk is now requested right after this chunk's patch has gone to LDS (three stages ahead instead of one: its
-    // registers are free from then on), and the weight slices alternate between two register sets, requested two stages ahead.
-    constexpr bool deep = DEEP && !PERSIST;
+    // registers are free from then on).
     aim(cur);
     load_a(0);
     load_b(rb, 0, 0);
-    if constexpr (B2) {
-        if (deep && n_stages > 1) load_b(rb2, KS > 1 ? 0 : 32, KS > 1 ? 1 : 0);
-    }
 
-    for (;;) {
-        // next valid work item of this block (uniform across the block)
-        int nid = id + gridDim.x;
-        Tile nxt = decode(nid);
-        while (nid < n_work && !nxt.valid) { nid += gridDim.x; nxt = decode(nid); }
-        const bool has_next = PERSIST && nid < n_work;
-
+    {
         f16x acc[RW][NJ];
 #pragma unroll
         for (int i = 0; i < RW; ++i)
@@ -229,20 +213,11 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
                 for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
 
         int c = 0, ty = 0;
-        auto stage = [&](int s, h8 (&RBc)[NB], h8 (&RBo)[NB]) {   // RBc: the set this stage stores from; RBo: the other one
-            TTRACE(0);
-            __syncthreads();  // previous stage's (or previous tile's) fragment reads are done
-            TTRACE(1);
-            if (TR) {                         // traced instance only: split "operands landed" from "operands written to LDS"
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                TTRACE(6);
-            }
+        auto stage = [&](int s) {
+            __syncthreads();  // previous stage's fragment reads are done
             if (ty == 0) store_a();
-            store_b(RBc);
-            if (TR) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            TTRACE(2);
+            store_b(rb);
             __syncthreads();
-            TTRACE(3);
             if (XS && ty == 0) {
                 // the 8 x 32 tile of this 32-channel chunk (+ halo, zeros outside the image) sits in LDS: its 4 x 16 down-sampled
                 // pixels are 16 reads + 5 packed-fp16 FIRs per thread, and the separate blur-down pass (a full read of the map) goes
@@ -272,25 +247,13 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
             }
             int nc = c, nty = ty + 1;
             if (nty == KS) { nty = 0; nc = c + 1; }
-            if (deep) {
+            if (DEEP) {
                 if (ty == 0 && c + 1 < n_chunks) load_a((c + 1) * 32);          // this chunk's patch is in LDS: its registers carry the next one
-                if (B2) {
-                    if (s + 2 < n_stages) {                                      // the set just stored takes stage s + 2
-                        const int t2 = ty + 2;
-                        load_b(RBc, (c + t2 / KS) * 32, t2 % KS);
-                    }
-                } else if (s + 1 < n_stages) {
-                    load_b(RBo, nc * 32, nty);
-                }
+                if (s + 1 < n_stages) load_b(rb, nc * 32, nty);
             } else if (s + 1 < n_stages) {  // prefetch the next stage while this one computes
                 if (nty == 0) load_a(nc * 32);
-                load_b(RBo, nc * 32, nty);
-            } else if (has_next) {   // last stage: prefetch stage 0 of the NEXT tile; it stays in flight
-                aim(nxt);            // through this tile's MFMA block and store epilogue
-                load_a(0);
-                load_b(RBo, 0, 0);
+                load_b(rb, nc * 32, nty);
             }
-            TTRACE(4);
             // ---- MFMA block: KS taps x 2 k16 steps x RW x NJ --------------------------------
 #pragma unroll
             for (int tx = 0; tx < KS; ++tx) {
@@ -310,18 +273,10 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
                     }
                 }
             }
-            TTRACE(5);
             c = nc;
             ty = nty;
         };
-        if constexpr (B2) {
-            for (int s = 0; s < n_stages; s += 2) {
-                stage(s, rb, rb2);
-                if (s + 1 < n_stages) stage(s + 1, rb2, rb);
-            }
-        } else {
-            for (int s = 0; s < n_stages; ++s) stage(s, rb, rb);          // (single weight set)
-        }
+        for (int s = 0; s < n_stages; ++s) stage(s);
 
         const int b = cur.b;
         if (SKIP) {
@@ -505,7 +460,7 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
             }
             }
         } else {
-            // generic path (folded up-conv with depth-to-space, odd channel counts, persistent variant)
+            // generic path (folded up-conv with depth-to-space, odd channel counts)
             static_assert(!SPL || SKIP, "the 2 x 2 wave grid exists for the fast-path stride-2 instances only");
 #pragma unroll
             for (int i = 0; i < RW; ++i) {
@@ -569,9 +524,6 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
                 }
             }
         }
-        if (!has_next) break;
-        id = nid;
-        cur = nxt;
     }
 }
 
@@ -592,35 +544,16 @@ static const char* launch_inst(const ConvParams& p, hipStream_t st, const char* 
     const int PT = p.B * tiles_x * tiles_y;
     const int NTn = p.Neff / NT;
     const int PT8 = (PT + 7) / 8 * 8;
-    // persistent grid: as many workgroups as are resident at once (256 CUs x blocks/CU), a multiple of 8
-    // so a block keeps its XCD; each block walks its work items with cross-tile prefetch
-    int resident = 1 << 30;
-    if (PERSIST) {
-        static int per_cu_cache = 0;           // occupancy is a property of the kernel + architecture; the CU count is per device
-        if (!per_cu_cache) {
-            int per_cu = 1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv_tiled_kernel<KS, S, TH, NT, PERSIST, TRGB, SKIP, XS, SPL, B2, DEEP, TR>, 256, LDS);
-            per_cu_cache = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-        }
-        resident = glass_cu_count() * per_cu_cache;
-        resident -= resident % 8;
-    }
-    const int n_work = PT8 * NTn;
-    const int grid = n_work < resident ? n_work : resident;
+    const int grid = PT8 * NTn;                // one work item per workgroup
     if (p.dry_run) return name;
     hipLaunchKernelGGL((conv_tiled_kernel<KS, S, TH, NT, PERSIST, TRGB, SKIP, XS, SPL, B2, DEEP, TR>), dim3(grid), dim3(256), LDS, st, p, NTn, tiles_x, tiles_y, PT);
     return name;
 }
 
-const char* launch_conv_tiled(const ConvParams& p0, hipStream_t st) {
-    ConvParams p = p0;
+const char* launch_conv_tiled(const ConvParams& p, hipStream_t st) {
     if (p.x_planar8 || p.y_planar8 || p.x_planar32) return nullptr;   // chunk-planar maps (common.h): not implemented here
-    static const bool no_ts = glass_knob("GLASS_NO_TSTORE") != nullptr;   // experiment knob
-    if (no_ts) p.no_tstore = 1;
-    // A/B knob GLASS_DEEP: 0 = round 2's one-stage prefetch distance, 1 = patch three stages ahead, 2 = + two weight register sets (stride 2)
-    static const int deep_on = glass_knob("GLASS_DEEP") ? atoi(glass_knob("GLASS_DEEP")) : 1;
     if (p.rgb_tanh_out) {   // planar tanh(channels 0..2) from the accumulators: the one-n-tile 3x3 instance's fast path only
-        if (p.y32 || p.trgb_yout || p.xs_out || p.up || p.KS != 3 || p.stride != 1 || p.pad != 1 || p.no_tstore || p.Neff != 32 || p.Cout != 32 ||
+        if (p.y32 || p.trgb_yout || p.xs_out || p.up || p.KS != 3 || p.stride != 1 || p.pad != 1 || p.Neff != 32 || p.Cout != 32 ||
             p.Hc % 8 != 0 || p.Wc % 32 != 0 || p.Cin % 32 != 0 || (p.sn && !p.sn16) || (p.pre_shift && !p.pre_shift16) || p.res || p.noise ||
             (p.x_bstride == 0 && p.B > 1) || (long long)p.H * p.W * p.Cin >= (1LL << 31))
             return nullptr;
@@ -628,20 +561,18 @@ const char* launch_conv_tiled(const ConvParams& p0, hipStream_t st) {
     }
     if (p.y32 || !p.y) return nullptr;
     if (p.trgb_yout) {   // fused toRGB: only where one workgroup holds every output channel of its pixels
-        if (!p.trgb_tab || !p.trgb_b || p.up || p.KS != 3 || p.stride != 1 || p.pad != 1 || p.no_tstore || p.Neff != 64 || p.Cout != 64 ||
+        if (!p.trgb_tab || !p.trgb_b || p.up || p.KS != 3 || p.stride != 1 || p.pad != 1 || p.Neff != 64 || p.Cout != 64 ||
             p.Hc % 8 != 0 || p.Wc % 32 != 0 || p.Cin % 32 != 0 || (p.sn && !p.sn16) || (p.pre_shift && !p.pre_shift16) ||
             (p.x_bstride == 0 && p.B > 1) || (long long)p.H * p.W * p.Cin >= (1LL << 31))
             return nullptr;
-        if (deep_on) return launch_inst<3, 1, 8, 64, false, true, false, false, false, false, true>(p, st, "conv_tiled_kernel<3,1,8,64,torgb,deep>");
-        return launch_inst<3, 1, 8, 64, false, true>(p, st, "conv_tiled_kernel<3,1,8,64,torgb>");
+        return launch_inst<3, 1, 8, 64, false, true, false, false, false, false, true>(p, st, "conv_tiled_kernel<3,1,8,64,torgb,deep>");
     }
     if (p.xs_out) {   // blur-down of the input as a by-product: un-transformed input, every chunk staged exactly once per pixel tile
-        if (p.KS != 3 || p.stride != 1 || p.pad != 1 || p.sn || p.pre_shift || p.in_up || p.up || p.Neff != 64 || p.Cout != 64 || p.no_tstore ||
+        if (p.KS != 3 || p.stride != 1 || p.pad != 1 || p.sn || p.pre_shift || p.in_up || p.up || p.Neff != 64 || p.Cout != 64 ||
             p.Hc % 8 != 0 || p.Wc % 32 != 0 || p.Cin % 32 != 0 || p.trgb_yout || (p.x_bstride == 0 && p.B > 1) ||
             (long long)p.H * p.W * p.Cin >= (1LL << 31))
             return nullptr;
-        if (deep_on) return launch_inst<3, 1, 8, 64, false, false, false, true, false, false, true>(p, st, "conv_tiled_kernel<3,1,8,64,xs,deep>");
-        return launch_inst<3, 1, 8, 64, false, false, false, true>(p, st, "conv_tiled_kernel<3,1,8,64,xs>");
+        return launch_inst<3, 1, 8, 64, false, false, false, true, false, false, true>(p, st, "conv_tiled_kernel<3,1,8,64,xs,deep>");
     }
     if ((p.sn && !p.sn16) || (p.pre_shift && !p.pre_shift16)) return nullptr;   // fp16 tables not provided: direct path
     if (p.x_bstride == 0 && p.B > 1) return nullptr;  // broadcast input (4x4 const): direct path
@@ -649,61 +580,18 @@ const char* launch_conv_tiled(const ConvParams& p0, hipStream_t st) {
     if ((long long)p.H * p.W * p.Cin >= (1LL << 31)) return nullptr;
     const int KS = p.KS, S = p.stride;
     if (KS == 3 && S == 1 && p.pad == 1) {
-        static const int th4 = glass_knob("GLASS_TH4") ? atoi(glass_knob("GLASS_TH4")) : 0;   // experiment knob
-        static const bool nt64 = glass_knob("GLASS_NT64") != nullptr;   // experiment knob
-        if (!nt64 && p.Neff % 128 == 0 && p.Hc % 8 == 0) return launch_inst<3, 1, 8, 128>(p, st, "conv_tiled_kernel<3,1,8,128>");
-        if ((th4 & 2) && p.Neff % 64 == 0 && p.Hc % 4 == 0) return launch_inst<3, 1, 4, 64>(p, st, "conv_tiled_kernel<3,1,4,64>");
-        static const bool persist = glass_knob("GLASS_PERSIST") != nullptr;   // measured slower (more live registers -> lower occupancy): off
-        if (persist && p.Neff % 64 == 0 && p.Hc % 8 == 0) return launch_inst<3, 1, 8, 64, true>(p, st, "conv_tiled_kernel<3,1,8,64,persist>");
+        if (p.Neff % 128 == 0 && p.Hc % 8 == 0) return launch_inst<3, 1, 8, 128>(p, st, "conv_tiled_kernel<3,1,8,128>");
         if (p.Neff % 64 == 0 && p.Hc % 8 == 0) return launch_inst<3, 1, 8, 64>(p, st, "conv_tiled_kernel<3,1,8,64>");
-        // memory-bound, tiny K: small tiles = more workgroups per CU = more bytes in flight
-        if ((th4 & 1) && p.Neff % 32 == 0 && p.Hc % 4 == 0) return launch_inst<3, 1, 4, 32>(p, st, "conv_tiled_kernel<3,1,4,32>");
-        if (persist && p.Neff % 32 == 0 && p.Hc % 8 == 0) return launch_inst<3, 1, 8, 32, true>(p, st, "conv_tiled_kernel<3,1,8,32,persist>");
         if (p.Neff % 32 == 0 && p.Hc % 8 == 0) return launch_inst<3, 1, 8, 32>(p, st, "conv_tiled_kernel<3,1,8,32>");
         return nullptr;
     }
     if (p.skip_x) {   // skip branch as extra K stages: stride-2 fast path without demodulation / noise / shift / residual
         if (KS != 3 || S != 2 || p.pad != 0 || !p.skip_w || p.res || p.dscale || p.noise || p.shift || p.sn || p.pre_shift || p.up ||
-            (p.Cout & 7) || p.no_tstore || p.Hc % 4 != 0)
+            (p.Cout & 7) || p.Hc % 4 != 0)
             return nullptr;
-#ifdef GLASS_DEV_TRACE
-        static const bool tiled_trace = getenv("GLASS_TILED_TRACE") != nullptr;
-#else
-        constexpr bool tiled_trace = false;
-#endif
-        if (!tiled_trace)
-            if (const char* k = launch_conv_s2(p, st)) return k;        // LDS-DMA ring kernel where its geometry applies
-        static const bool spl = glass_knob("GLASS_NO_S2_SPLIT") == nullptr;  // 2 x 2 wave grid (A/B knob: GLASS_NO_S2_SPLIT=1 -> 4 x 1; measured -4.4 % on the four stride-2 layers)
-        if (spl && deep_on == 2 && p.Neff % 128 == 0) return launch_inst<3, 2, 4, 128, false, false, true, false, true, true, true>(p, st, "conv_tiled_kernel<3,2,4,128,skip,spl,b2,deep>");
-#ifdef GLASS_DEV_TRACE      // dev build (make TRACE=1): traced instance, stamps of one mid-grid workgroup to a file; synchronises, single engine only
-        if (const char* tp = getenv("GLASS_TILED_TRACE")) {      // dev tool: traced instance, stamps of one mid-grid workgroup to a file
-            if (spl && p.Neff % 128 == 0 && !p.dry_run) {
-                unsigned long long* dtr = nullptr;
-                (void)hipMalloc(&dtr, 64 * 8 * 4 * sizeof(unsigned long long));
-                (void)hipMemset(dtr, 0, 64 * 8 * 4 * sizeof(unsigned long long));
-                (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tiled_trace), &dtr, sizeof dtr);
-                const char* nm = launch_inst<3, 2, 4, 128, false, false, true, false, true, false, true, true>(p, st, "conv_tiled_kernel<3,2,4,128,skip,spl,deep,trace>");
-                static unsigned long long hb[64 * 8 * 4];
-                (void)hipStreamSynchronize(st);
-                (void)hipMemcpy(hb, dtr, sizeof hb, hipMemcpyDeviceToHost);
-                (void)hipFree(dtr);
-                if (FILE* f = fopen(tp, "a")) {
-                    fprintf(f, "# %s Cin=%d Cout=%d Hc=%d: stage phase t[wave0..3]; phases 0 top, 1 after barrier, 2 operands stored, 3 after barrier, 4 loads issued, 5 MFMAs done, 6 operands landed (between 1 and 2)\n", nm, p.Cin, p.Cout, p.Hc);
-                    for (int i = 0; i < 64; ++i)
-                        for (int ph = 0; ph < 7; ++ph) {
-                            fprintf(f, "%d %d", i, ph);
-                            for (int w = 0; w < 4; ++w) fprintf(f, " %llu", hb[(i * 8 + ph) * 4 + w] ? hb[(i * 8 + ph) * 4 + w] - hb[0] : 0ULL);
-                            fprintf(f, "\n");
-                        }
-                    fclose(f);
-                }
-                return nm;
-            }
-        }
-#endif
-        if (spl && deep_on && p.Neff % 128 == 0) return launch_inst<3, 2, 4, 128, false, false, true, false, true, false, true>(p, st, "conv_tiled_kernel<3,2,4,128,skip,spl,deep>");
-        if (spl && p.Neff % 128 == 0) return launch_inst<3, 2, 4, 128, false, false, true, false, true>(p, st, "conv_tiled_kernel<3,2,4,128,skip,spl>");
-        if (p.Neff % 128 == 0) return launch_inst<3, 2, 4, 128, false, false, true>(p, st, "conv_tiled_kernel<3,2,4,128,skip>");
+        if (const char* k = launch_conv_s2(p, st)) return k;        // LDS-DMA ring kernel where its geometry applies
+        // 2 x 2 wave grid (SPL; 4 x 1 measured -4.4 % on the four stride-2 layers)
+        if (p.Neff % 128 == 0) return launch_inst<3, 2, 4, 128, false, false, true, false, true, false, true>(p, st, "conv_tiled_kernel<3,2,4,128,skip,spl,deep>");
         if (p.Neff % 64 == 0) return launch_inst<3, 2, 4, 64, false, false, true>(p, st, "conv_tiled_kernel<3,2,4,64,skip>");
         return nullptr;
     }

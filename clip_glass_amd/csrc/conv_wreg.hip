@@ -94,20 +94,10 @@ __device__ __forceinline__ void swap32(h8& a, h8& b) {
 #define WG_LDS_RD(dst, vaddr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(vaddr), "n"(imm))
 #define WG_WAIT_LGKM6(a, b, c, d, e, f) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f)::"memory")
 #define WG_WAIT_LGKM4(a, b, c, d) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory")
-// developer builds only: timing experiments that switch parts of a tile off — 1 the whole epilogue, 2 its global
-// stores, 4 the K loop's MFMAs, 8 the patch fragment reads, 32 the ring's requests, 64 the epilogue's lane swaps, 128 its arithmetic (WRONG RESULTS)
-// (a RUN-TIME bit costs a branch per MFMA group and distorts what it measures: the bits are a COMPILE-time constant, -DWG_ABLATE_CT=<bits>,
-// one library per experiment — tools/build_ablations.sh)
-#define WG_ABL_ARG
-#ifdef WG_ABLATE_CT
-#define WG_ABL(bit) (((WG_ABLATE_CT) & (bit)) != 0)
-#else
-#define WG_ABL(bit) false
-#endif
 }  // namespace
 
 template <bool TRGB, bool XS>
-__global__ __launch_bounds__(256, 1) void conv_wreg_kernel(ConvParams p, int tiles_x, int tiles_y, int PT, int per_wg WG_ABL_ARG) {
+__global__ __launch_bounds__(256, 1) void conv_wreg_kernel(ConvParams p, int tiles_x, int tiles_y, int PT, int per_wg) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tpi = tiles_x * tiles_y;
@@ -319,8 +309,8 @@ __global__ __launch_bounds__(256, 1) void conv_wreg_kernel(ConvParams p, int til
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
                         for (int i = 0; i < RW; ++i)
-                            if (!WG_ABL(4)) acc[i][j] = mfma32(wreg[c][ty * 3 + tx][j], xf[qs][i + ty], acc[i][j]);
-                    if (ty == 0 && tx == 0 && !WG_ABL(32)) {      // the ring: tile id + 2, one chunk per chunk; tile id + 1's operands ahead of the first
+                            acc[i][j] = mfma32(wreg[c][ty * 3 + tx][j], xf[qs][i + ty], acc[i][j]);
+                    if (ty == 0 && tx == 0) {      // the ring: tile id + 2, one chunk per chunk; tile id + 1's operands ahead of the first
                         __builtin_amdgcn_sched_barrier(0);
                         if (c == 0) issue_operands(nxt, es_nxt);
                         issue_chunk(slot_req, c);
@@ -334,10 +324,7 @@ __global__ __launch_bounds__(256, 1) void conv_wreg_kernel(ConvParams p, int til
                 }
                 if (q + 2 < 3 * NCH) {         // column q + 2 of this tile, into the registers this column just released
 #pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) {
-                        if (!WG_ABL(8)) WG_LDS_RD(xf[qs][rr], xbase, ((q + 2) / 3) * A_BYTES + rr * ROWB + ((q + 2) % 3) * 16);
-                        else xf[qs][rr] = h8{0, 0, 0, 0, 0, 0, 0, 0};
-                    }
+                    for (int rr = 0; rr < 4; ++rr) WG_LDS_RD(xf[qs][rr], xbase, ((q + 2) / 3) * A_BYTES + rr * ROWB + ((q + 2) % 3) * 16);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -384,7 +371,6 @@ __global__ __launch_bounds__(256, 1) void conv_wreg_kernel(ConvParams p, int til
             constexpr bool PLAIN = decltype(plain_tag)::value;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                if (WG_ABL(1)) { if (acc[0][j][0] == 12345.678f) p.y[0] = (half_t)1.f; continue; }
                 f4 bias4[4];
                 if (PLAIN) {
 #pragma unroll
@@ -404,7 +390,7 @@ __global__ __launch_bounds__(256, 1) void conv_wreg_kernel(ConvParams p, int til
 #pragma unroll
                     for (int i = 0; i < RW; ++i) {
                         const f4 a = {acc[i][j][g * 4], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]};
-                        f4 v = WG_ABL(128) ? a : act_apply(PLAIN ? a + bq + nzr[i] : a * dq + bq + nzr[i], ak);      // (a * 1 + b == a + b: the same bits)
+                        f4 v = act_apply(PLAIN ? a + bq + nzr[i] : a * dq + bq + nzr[i], ak);      // (a * 1 + b == a + b: the same bits)
                         h4 out;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) out[q] = (half_t)v[q];
@@ -429,9 +415,9 @@ __global__ __launch_bounds__(256, 1) void conv_wreg_kernel(ConvParams p, int til
 #pragma unroll
                     for (int gp = 0; gp < 2; ++gp) {
                         h4 lo = va[i][2 * gp], hi = va[i][2 * gp + 1];
-                        if (!WG_ABL(64)) swap32(lo, hi);
+                        swap32(lo, hi);
                         const h8 ov = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                        if (!WG_ABL(2) || ov[0] == (half_t)123.f) *(h8*)(yrow + i * yrow_pitch + (j * 32 + 16 * gp) * 2 + yoff) = ov;
+                        *(h8*)(yrow + i * yrow_pitch + (j * 32 + 16 * gp) * 2 + yoff) = ov;
                     }
             }
         };
@@ -466,8 +452,7 @@ __global__ __launch_bounds__(256, 1) void conv_wreg_kernel(ConvParams p, int til
 
 // would a plain 3x3 layer of this geometry run here?  (the producers of its input ask before they write the chunk-planar layout)
 bool conv_wreg_supported(int Cin, int Cout, int H, int W) {
-    static const bool off = glass_knob("GLASS_NO_WREG") != nullptr;       // A/B knob (developer build): conv_wres / conv_tiled<3,1,8,64> instead
-    if (off || Cin != 64 || Cout != NT || H % TH != 0 || W % TW != 0 || (long long)H * W * Cin >= (1LL << 31)) return false;
+    if (Cin != 64 || Cout != NT || H % TH != 0 || W % TW != 0 || (long long)H * W * Cin >= (1LL << 31)) return false;
     if (!glass_lds_fits(LDS_BYTES)) return false;
     // worth a persistent workgroup per CU only with several tiles each — judged at the nominal population (common.h), so that a layer runs on
     // the same kernel whatever the size of this launch
@@ -498,9 +483,8 @@ const char* launch_conv_wreg(const ConvParams& p, hipStream_t st) {
     // contiguous tile ranges: the tiles of a candidate split over whole workgroups where they can (per-sample weights load once per range)
     const int per_wg = (PT + n_cu - 1) / n_cu;
     const int grid = (PT + per_wg - 1) / per_wg;
-#define WG_ABL_PASS
-    if (p.trgb_yout) hipLaunchKernelGGL((conv_wreg_kernel<true, false>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg WG_ABL_PASS);
-    else if (p.xs_out) hipLaunchKernelGGL((conv_wreg_kernel<false, true>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg WG_ABL_PASS);
-    else hipLaunchKernelGGL((conv_wreg_kernel<false, false>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg WG_ABL_PASS);
+    if (p.trgb_yout) hipLaunchKernelGGL((conv_wreg_kernel<true, false>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg);
+    else if (p.xs_out) hipLaunchKernelGGL((conv_wreg_kernel<false, true>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg);
+    else hipLaunchKernelGGL((conv_wreg_kernel<false, false>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg);
     return name;
 }

@@ -155,13 +155,13 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
         return GLASS_ERR_ARG;
     }
     e->chunk = chunk;
-    // Stream mode: glass_engine_set_overlap() is the only control in the release library (glass_knob() reads nothing there; the two
-    // variables below exist in the developer build, and bench.py translates them into set_overlap() calls for the measure_* scripts).
+    // Stream mode: glass_engine_set_overlap() is the only control (bench.py translates GLASS_OVERLAP / GLASS_NO_CLIP_OVERLAP into
+    // set_overlap() calls for the measure_* scripts).
     // Chunk pipelining (mode 1) stretches every co-running kernel ~2x, which makes per-kernel profiles meaningless: opt-in.
-    e->overlap = glass_knob("GLASS_OVERLAP") != nullptr;
+    e->overlap = false;
     // default (mode 2): CLIP's image tower (short, latency-bound launches) on the second stream next to the discriminator, which only
     // shares the finished image with it
-    e->clip_overlap = glass_knob("GLASS_NO_CLIP_OVERLAP") == nullptr;
+    e->clip_overlap = true;
     hipError_t err = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
     if (err == hipSuccess) {
         // the second stream carries CLIP's ~75 short dependent launches beside the discriminator's chip-filling kernels: at the highest
@@ -174,7 +174,6 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     if (err == hipSuccess) err = hipEventCreate(&e->ev0);
     if (err == hipSuccess) err = hipEventCreate(&e->ev1);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&e->ev_noise, hipEventDisableTiming);
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&e->ev_rgb, hipEventDisableTiming);
     if (err != hipSuccess) {
         delete e;
         glass_set_error(std::string("stream/event creation failed: ") + hipGetErrorString(err));
@@ -207,7 +206,6 @@ extern "C" void glass_engine_destroy(glass_engine* e) {
     if (e->ev0) hipEventDestroy(e->ev0);
     if (e->ev1) hipEventDestroy(e->ev1);
     if (e->ev_noise) hipEventDestroy(e->ev_noise);
-    if (e->ev_rgb) hipEventDestroy(e->ev_rgb);
     if (e->stream) hipStreamDestroy(e->stream);
     if (e->stream_d) hipStreamDestroy(e->stream_d);
     delete e;
@@ -582,7 +580,7 @@ static int alloc_buffers(glass_engine* e) {
             if ((rc = dev_alloc(e, &e->ws_a2, (size_t)(e->cap_a * P)))) return rc;
             if ((rc = dev_alloc(e, &e->ws_c2, (size_t)(e->cap_c * P)))) return rc;
         }
-    } else if (e->cfg.generator == GLASS_GEN_BIGGAN_DEEP && !glass_knob("GLASS_BG_NO_CONV_GEMM")) {
+    } else if (e->cfg.generator == GLASS_GEN_BIGGAN_DEEP) {
         // BigGAN-deep's 4 x 4 .. 16 x 16 layers (3 x 3 on ch * 4 = 512 channels, 1 x 1 up to ch * 16 outputs) on the same path (round 3:
         // they ran on conv_direct at 64 - 220 TFLOP/s); the walk over the population is chunked, so the scratch holds one chunk
         const int cmax = 4 * e->cfg.bg_ch;
@@ -598,8 +596,9 @@ static int alloc_buffers(glass_engine* e) {
         const bool fused_ok = g.up && g.cin % 32 == 0 && g.cout % 32 == 0 && g.res_in >= 16;
         const bool tiled_ok = !g.up && g.cin % 32 == 0 && g.cout % 32 == 0 && g.res_in % 32 == 0;
         g.welems = 9LL * g.cin * g.cout;
-        static const long long premod_kb = glass_knob("GLASS_PREMOD_MAX_KB") ? atoll(glass_knob("GLASS_PREMOD_MAX_KB")) : 500;   // A/B knob (round 3: the 256 -> 128 up-conv, 590 KB per sample, runs 4 % faster on the shared-weight image grid, and its consumer 5 % faster on the pre-styled output; 1200 was round 2's value)
-        g.premod = (fused_ok || tiled_ok) && g.welems * 2 <= (premod_kb << 10) && !glass_knob("GLASS_NO_PREMOD");
+        // at most 500 KB per sample (round 3: the 256 -> 128 up-conv, 590 KB per sample, runs 4 % faster on the shared-weight image grid,
+        // and its consumer 5 % faster on the pre-styled output; 1200 was round 2's value)
+        g.premod = (fused_ok || tiled_ok) && g.welems * 2 <= (500LL << 10);
         if (g.premod && (rc = dev_alloc(e, &g.wm, (size_t)P * g.welems))) return rc;
     }
     if (c.noise_mode != 0) {
@@ -769,22 +768,9 @@ extern "C" int glass_engine_set_target(glass_engine* e, const float* feat, int32
 void collect_profile(glass_engine* e) {
     std::map<std::string, glass_prof_row> rows;
     std::vector<std::string> order;
-#ifdef GLASS_AB_KNOBS
-    // developer build: GLASS_TIMELINE=<file> appends "start end name" (ms from the pass's first event) of every instrumented launch —
-    // where the second stream's launches sit beside the main stream's (tools/layer_ab.py --mode 2)
-    FILE* tl = getenv("GLASS_TIMELINE") ? fopen(getenv("GLASS_TIMELINE"), "a") : nullptr;
-    if (tl) fprintf(tl, "# pass\n");
-#endif
     for (auto& pe : e->prof_events) {
         float ms = 0.f;
         hipEventElapsedTime(&ms, pe.e0, pe.e1);
-#ifdef GLASS_AB_KNOBS
-        if (tl) {
-            float t0 = 0.f;
-            hipEventElapsedTime(&t0, e->ev0, pe.e0);
-            fprintf(tl, "%9.3f %9.3f %s\n", t0, t0 + ms, pe.name.c_str());
-        }
-#endif
         auto it = rows.find(pe.name);
         if (it == rows.end()) {
             glass_prof_row r;
@@ -798,9 +784,6 @@ void collect_profile(glass_engine* e) {
         it->second.flops += pe.flops;
         it->second.bytes += pe.bytes;
     }
-#ifdef GLASS_AB_KNOBS
-    if (tl) fclose(tl);
-#endif
     e->prof_rows.clear();
     for (auto& n : order) e->prof_rows.push_back(rows[n]);
     e->prof_events.clear();
@@ -889,8 +872,7 @@ static void run_styles(glass_engine* e, int P) {
     const int L = c.latent_size;
     {
         Prof pr(e, "mapping", 2.0 * P * L * L * c.mapping_layers, 4.0 * L * L * c.mapping_layers);
-        static const bool no_fused = glass_knob("GLASS_NO_MAP_FUSE") != nullptr;   // A/B knob
-        if (no_fused || c.mapping_layers < 1 ||
+        if (c.mapping_layers < 1 ||
             !launch_mapping_fused(e->d_z, e->d_w0, P, L, 1e-8f, e->map_wt.data(), e->map_b.data(), c.mapping_layers, e->cur)) {
             launch_pixelnorm(e->d_z, e->d_w0, P, L, 1e-8f, e->cur);
             float *a = e->d_w0, *b = e->d_w1;
@@ -939,26 +921,10 @@ static void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, con
     char tag[48];
     int gi = b_lo == 0 ? 0 : 1 + 2 * (b_lo - 1);
     int yi = 0;
-    static const bool no_trgb_fuse = glass_knob("GLASS_NO_TRGB_FUSE") != nullptr;   // experiment knobs
-    static const bool no_trgb_mid = glass_knob("GLASS_NO_TRGB_MID") != nullptr;
-    static const bool no_pre_style = glass_knob("GLASS_NO_PRE_STYLE") != nullptr;
-    static const bool no_planar = glass_knob("GLASS_NO_PLANAR") != nullptr;      // A/B knob: conv_wreg's input stays pixel-major
-    // A block's SEPARATE toRGB pass (blocks wider than 128 channels) is a bandwidth-bound read of the map the next block's
-    // up-conv reads too; in the two-stream mode it runs on the second stream next to that (issue-bound) up-conv.  The main
-    // stream joins before the next block's last conv: that launch overwrites the map toRGB reads and consumes its skip image.
-    // Measured (round 3): 33.77 vs 33.74 ms per population — no gain, co-running kernels share the CUs they would have had
-    // anyway (the late-CLIP variant, GLASS_CLIP_LATE, loses 0.3 ms).  Opt-in knob only.
-    static const bool rgb_side_on = glass_knob("GLASS_TRGB_SIDE") != nullptr;
-    const bool rgb_side = e->clip_overlap && e->cur == e->stream && rgb_side_on;
-    bool rgb_pending = false;
     for (int b = b_lo; b < b_hi; ++b) {
         const int nl = b == 0 ? 1 : 2;
         bool rgb_done = false, pre_styled = false, x_planar = false;
         for (int l = 0; l < nl; ++l, ++gi) {
-            if (rgb_pending && l == nl - 1) {
-                hipStreamWaitEvent(e->stream, e->ev_rgb, 0);
-                rgb_pending = false;
-            }
             const GConv& g = e->gconv[gi];
             ConvParams p = conv_defaults();
             p.x = x;
@@ -999,7 +965,7 @@ static void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, con
             // runs and that conv modulates on the activation side) its style is applied once, to the up-conv's output
             if (pre_styled) { p.sn = nullptr; p.sn16 = nullptr; pre_styled = false; }
             if (x_planar) { p.x_planar8 = 1; x_planar = false; }     // (a launcher that does not read the layout refuses the layer: run_conv reports it)
-            if (g.up && l == 0 && nl == 2 && !no_pre_style && !e->gconv[gi + 1].premod && !e->gconv[gi + 1].up) {
+            if (g.up && l == 0 && nl == 2 && !e->gconv[gi + 1].premod && !e->gconv[gi + 1].up) {
                 ConvParams dq = p;
                 dq.dry_run = 1;
                 dq.y = pp[0];
@@ -1014,7 +980,7 @@ static void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, con
             p.y = out;
             // upconv -> conv_wreg link: that kernel reads its input one 32-channel chunk at a time, so the up-conv writes the map
             // chunk-planar for it (common.h x_planar8) — where the up-conv instance that can runs and the conv has no activation-side style
-            if (g.up && l == 0 && nl == 2 && !no_planar && !e->gconv[gi + 1].up && (pre_styled || e->gconv[gi + 1].premod) &&
+            if (g.up && l == 0 && nl == 2 && !e->gconv[gi + 1].up && (pre_styled || e->gconv[gi + 1].premod) &&
                 conv_wreg_supported(e->gconv[gi + 1].cin, e->gconv[gi + 1].cout, g.res_out, g.res_out)) {
                 ConvParams dq = p;
                 dq.dry_run = 1;
@@ -1025,7 +991,7 @@ static void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, con
             const double bytes = 2.0 * B * ((double)g.res_in * g.res_in * g.cin + (double)g.res_out * g.res_out * g.cout) +
                                  2.0 * 9 * g.cin * p.Neff;
             snprintf(tag, sizeof tag, "G.%s.r%d.%dx%d", g.up ? "upconv" : "conv", g.res_out, g.cin, g.cout);
-            if (l == nl - 1 && !g.up && !no_trgb_fuse) {
+            if (l == nl - 1 && !g.up) {
                 // toRGB of the block fused into its last conv (common.h).  The network's LAST conv feeds toRGB only:
                 // conv_stream<torgb> writes just the skip image and the 64-byte-per-pixel feature map never goes to HBM;
                 // the mid-resolution blocks still store their map (the next block reads it) but toRGB no longer re-reads it.
@@ -1048,7 +1014,7 @@ static void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, con
                         x = nullptr;   // not produced
                     }
                 }
-                if (!rgb_done && !no_trgb_mid && r.cin <= 128) {
+                if (!rgb_done && r.cin <= 128) {
                     q.y = out;
                     q.trgb_tab = e->d_trgb_tab + (size_t)c0 * 32 * 128;
                     q.dry_run = 1;
@@ -1069,7 +1035,7 @@ static void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, con
                     }
                 }
             }
-            if (l == nl - 1 && !g.up && !no_trgb_fuse && !rgb_done && !no_trgb_mid && e->d_trgb_part) {
+            if (l == nl - 1 && !g.up && !rgb_done && e->d_trgb_part) {
                 // blocks wider than 128 channels (several 128-wide n tiles per pixel): every n tile's conv epilogue writes the toRGB partial sum of
                 // its channels, a 3-value-per-pixel pass adds them (+ bias + the upsampled previous image) — the separate toRGB pass read the
                 // whole feature map again (0.19 + 0.09 + 0.03 ms at r128 / r64 / r32)
@@ -1107,30 +1073,16 @@ static void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, con
         const GRgb& r = e->grgb[b];
         if (!rgb_done) {
             snprintf(tag, sizeof tag, "G.torgb.r%d", r.res);
-            const bool side = rgb_side && b + 1 < b_hi;       // (the last block's image is consumed right away)
-            if (side) {
-                hipEventRecord(e->ev_rgb, e->stream);
-                hipStreamWaitEvent(e->stream_d, e->ev_rgb, 0);
-                e->cur = e->stream_d;
-            }
-            {
             Prof pr(e, tag, 2.0 * B * (double)r.res * r.res * 3 * r.cin,
                     B * ((double)r.res * r.res * (2.0 * r.cin + 12.0 + (b ? 3.0 : 0.0))));
             if (!launch_torgb(x, B, r.res, r.res, r.cin, r.w, r.bias, e->d_s + (size_t)c0 * e->S_total + r.style_off,
                               e->S_total, e->d_smax + (size_t)c0 * e->n_style + r.style_idx, e->n_style, yprev, yb[yi], e->cur) &&
                 e->launch_error.empty())
                 e->launch_error = std::string("toRGB width not instantiated: ") + tag;
-            }
-            if (side) {
-                hipEventRecord(e->ev_rgb, e->stream_d);
-                e->cur = e->stream;
-                rgb_pending = true;
-            }
         }
         yprev = yb[yi];
         yi ^= 1;
     }
-    if (rgb_pending) hipStreamWaitEvent(e->stream, e->ev_rgb, 0);
     *x_out = x;
     *y_out = yprev;
 }
@@ -1146,7 +1098,6 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
                             const float* rgb_y = nullptr) {
     char tag[64];
     half_t *Hb = bufs[0], *HB = bufs[1], *XS = bufs[2], *S = bufs[3], *O = bufs[4];
-    static const bool no_planar = glass_knob("GLASS_NO_PLANAR") != nullptr;      // A/B knob: conv_wreg's input stays pixel-major
     bool x_planar = false;       // X is chunk-planar (common.h x_planar8): written so by the fused first block for conv_wreg
     for (int i = i_lo; i < i_hi; ++i) {
         const DBlock& d = e->dblk[i];
@@ -1163,8 +1114,7 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
             const double px = (double)B * r * r, px2 = (double)B * r2 * r2;
             Prof pr(e, tag, 2.0 * px * (9.0 * d.cin * d.cin + 3.0 * d.cin) + 2.0 * px2 * 10.0 * d.cin * d.cout, px * 12.0 + px2 * 2.0 * d.cout);
             // the next block's first conv on conv_wreg (with the blur-down by-product: nothing else reads this map): chunk-planar output
-            static const bool no_xs_fuse = glass_knob("GLASS_NO_XS_FUSE") != nullptr;
-            const bool planar = !no_planar && !no_xs_fuse && i + 1 < i_hi && e->dblk[i + 1].cin == d.cout && conv_wreg_supported(d.cout, d.cout, r2, r2);
+            const bool planar = i + 1 < i_hi && e->dblk[i + 1].cin == d.cout && conv_wreg_supported(d.cout, d.cout, r2, r2);
             const char* k = launch_dblock0(rgb_y, e->d_frgb_w, e->d_frgb_b, d.w0, d.b0, d.w1, d.wskip, d.b1, O, B, r, d.cin, d.cout, e->cur, planar);
             if (k) {
                 x_planar = planar;
@@ -1177,7 +1127,6 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
         }
         const bool fuse_down = conv_down_supported(r, d.cin, d.cout);   // blur + skip + stride-2 conv + merge as one kernel
         if (i == 0 && rgb_y) {
-            static const bool no_fuse = glass_knob("GLASS_NO_FRGB_FUSE") != nullptr;   // A/B knob
             ConvParams q = p;
             q.rgb_y = rgb_y; q.rgb_w = e->d_frgb_w; q.rgb_b = e->d_frgb_b;
             q.rgb_x_out = fuse_down ? nullptr : X;       // the fused second half reads the down-sampled skip input only
@@ -1185,7 +1134,7 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
             snprintf(tag, sizeof tag, "D.fromrgb+conv0.r%d.%dx%d", r, d.cin, d.cin);
             const double px = (double)B * r * r;
             Prof pr(e, tag, 2.0 * px * (9.0 * d.cin * d.cin + 3.0 * d.cin), px * (12.0 + 2.0 * d.cin + (fuse_down ? 0.5 : 2.0) * d.cin));
-            const char* k = no_fuse ? nullptr : launch_conv_stream(q, e->cur);
+            const char* k = launch_conv_stream(q, e->cur);
             if (k) {
                 fused_rgb = true;
                 have_xs = fuse_down;
@@ -1198,10 +1147,9 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
         if (i == 0 && rgb_y && !fused_rgb) run_fromrgb(e, B, rgb_y, X);
         snprintf(tag, sizeof tag, "D.conv0.r%d.%dx%d", r, d.cin, d.cin);
         if (!fused_rgb) {
-            static const bool no_xs = glass_knob("GLASS_NO_XS_FUSE") != nullptr;   // A/B knob
             ConvParams qx = p;
             qx.xs_out = XS; qx.dry_run = 1;
-            if (!no_xs && !have_xs && (launch_conv_glds(qx, e->cur) || launch_conv_tiled(qx, e->cur))) {   // the skip branch's blur-down rides in the first conv
+            if (!have_xs &&(launch_conv_glds(qx, e->cur) || launch_conv_tiled(qx, e->cur))) {   // the skip branch's blur-down rides in the first conv
                 qx.dry_run = 0;
                 p = qx;
                 have_xs = true;
@@ -1234,11 +1182,9 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
         // blur -> conv_s2 link: that kernel stages its input one 32-channel chunk per K step, so (where it runs) the blur writes 32-channel planes
         bool hb_planar = false;
         {
-            static const bool no_planar = glass_knob("GLASS_NO_PLANAR") != nullptr;      // A/B knob
-            static const bool no_skip_fuse0 = glass_knob("GLASS_NO_SKIP_FUSE") != nullptr;
             ConvParams qp = q;
             qp.skip_x = XS; qp.skip_w = d.wskip; qp.x_planar32 = 1; qp.dry_run = 1;
-            hb_planar = !no_planar && !no_skip_fuse0 && blur_pad2_planar32_ok(d.cin) && launch_conv_s2(qp, e->cur) != nullptr;
+            hb_planar = blur_pad2_planar32_ok(d.cin) && launch_conv_s2(qp, e->cur) != nullptr;
         }
         {
             snprintf(tag, sizeof tag, "D.blur.r%d", r);
@@ -1248,11 +1194,10 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
         snprintf(tag, sizeof tag, "D.conv1.r%d.%dx%d", r2, d.cin, d.cout);
         const double f1 = 2.0 * B * (double)r2 * r2 * 9 * d.cin * d.cout, fs = 2.0 * B * (double)r2 * r2 * d.cin * d.cout;
         {   // skip branch as extra K stages of the stride-2 conv (conv_tiled<3,2,4,N,skip>) where that kernel applies
-            static const bool no_skip_fuse = glass_knob("GLASS_NO_SKIP_FUSE") != nullptr;   // A/B knob
             ConvParams qs = q;
             qs.skip_x = XS; qs.skip_w = d.wskip; qs.dry_run = 1;
             qs.x_planar32 = hb_planar;
-            if (!no_skip_fuse && (hb_planar ? launch_conv_s2(qs, e->cur) : launch_conv_tiled(qs, e->cur))) {
+            if (hb_planar ? launch_conv_s2(qs, e->cur) : launch_conv_tiled(qs, e->cur)) {
                 qs.dry_run = 0;
                 Prof pr(e, tag, f1 + fs, 2.0 * B * ((double)(r + 1) * (r + 1) * d.cin + (double)r2 * r2 * (d.cin + d.cout)));
                 const char* k = hb_planar ? launch_conv_s2(qs, e->cur) : launch_conv_tiled(qs, e->cur);
@@ -1302,9 +1247,8 @@ static void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch)
     g.out32 = e->d_dh; g.ldo = CL; g.cand_rows = 1;
     // M = P rows, K = 16 CL = 8192: the 128 x 64 tiles are 8 workgroups walking 128 K steps each (97 us for 0.5 GFLOP).  Split K into 16
     // slices (blockIdx.z) with raw partial sums, finished in a fixed order with bias + activation: 128+ workgroups, 8 steps each.
-    static const bool no_d0_split = glass_knob("GLASS_NO_DENSE0_SPLIT") != nullptr;   // A/B knob
     const int S0 = 16;
-    if (!no_d0_split && e->d_dh_part && g.K % (S0 * 64) == 0 && P <= e->cfg.max_pop) {
+    if (e->d_dh_part && g.K % (S0 * 64) == 0 && P <= e->cfg.max_pop) {
         GemmParams q = g;
         q.ld = g.K; q.K = g.K / S0; q.batch = S0; q.a_bs = q.K; q.w_bs = q.K; q.o_bs = (long long)P * CL;
         q.bias = nullptr; q.mode = 3; q.out32 = e->d_dh_part;
@@ -1436,8 +1380,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
     }
     // device-generated noise planes depend on nothing but (seed, generation, minibatch, layer): their 17 short launches run on the
     // second stream next to the mapping network / style / demodulation chain instead of ahead of it
-    static const bool no_noise_ov = glass_knob("GLASS_NO_NOISE_OVERLAP") != nullptr;      // A/B knob, read once
-    const bool noise_ov = e->clip_overlap && c.noise_mode == 1 && !no_noise_ov;
+    const bool noise_ov = e->clip_overlap && c.noise_mode == 1;
     int rc;
     if (noise_ov) {
         e->cur = e->stream_d;
@@ -1484,7 +1427,6 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
     }
     const bool overlap = e->overlap && out_F;
     const bool clip_ov = e->clip_overlap && !overlap && out_F && want_d;
-    static const bool clip_late = glass_knob("GLASS_CLIP_LATE") != nullptr;      // A/B knob
     hipStream_t sd = overlap ? e->stream_d : e->stream;
     for (int c0 = 0, k = 0; c0 < P; c0 += e->chunk, ++k) {
         const int B = std::min(e->chunk, P - c0);
@@ -1514,15 +1456,13 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
                 launch_resize_patches(y, B, e->R, c.clip_res, ps, e->d_patches + (size_t)c0 * G * G * 3 * ps * ps,
                                       e->cur);
             }
-            if (clip_ov && !clip_late && c0 + e->chunk >= P) {   // last chunk's patches are in place: CLIP starts now
+            if (clip_ov && c0 + e->chunk >= P) {   // last chunk's patches are in place: CLIP starts now
                 // its first layers on the MAIN stream (alone on the chip), the rest on the second stream beside the discriminator
-                static const int serial_layers = glass_knob("GLASS_CLIP_SERIAL") ? atoi(glass_knob("GLASS_CLIP_SERIAL")) : GLASS_CLIP_SERIAL_LAYERS;
-                if (serial_layers >= 0) run_clip(e, P, 0, serial_layers);      // (0: the patch embedding alone; -1: nothing)
+                run_clip(e, P, 0, GLASS_CLIP_SERIAL_LAYERS);
                 GLASS_HIP(hipEventRecord(e->ev_g[0], e->stream));
                 GLASS_HIP(hipStreamWaitEvent(e->stream_d, e->ev_g[0], 0));
                 e->cur = e->stream_d;
-                if (serial_layers >= 0) run_clip_rest(e, P, serial_layers);
-                else run_clip(e, P, 0, 1 << 20);
+                run_clip_rest(e, P, GLASS_CLIP_SERIAL_LAYERS);
                 GLASS_HIP(hipEventRecord(e->ev_d[0], e->stream_d));
                 e->cur = e->stream;
             }
@@ -1538,14 +1478,6 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
             }
             if (overlap) GLASS_HIP(hipEventRecord(e->ev_d[k], sd));
         }
-    }
-    if (clip_ov && clip_late) {   // CLIP's short launches next to the LOW-resolution discriminator (equally short launches) instead of
-        GLASS_HIP(hipEventRecord(e->ev_g[0], e->stream));          // next to its chip-filling high-resolution kernels
-        GLASS_HIP(hipStreamWaitEvent(e->stream_d, e->ev_g[0], 0));
-        e->cur = e->stream_d;
-        run_clip(e, P, 0, 1 << 20);
-        GLASS_HIP(hipEventRecord(e->ev_d[0], e->stream_d));
-        e->cur = e->stream;
     }
     // ---- phase C: low-resolution discriminator + head (second stream) || CLIP (main stream) ------
     if (want_d) {
@@ -1809,27 +1741,22 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
     }
     // one transformer pass over `nd` new positions per sequence; step_state != nullptr: single-token step whose past length /
     // step index are read from device memory (the form that is captured into a hipGraph and replayed)
-    // single-token steps, fused form (round 3; A/B knob GLASS_GPT2_NO_FUSE): LayerNorm applied on the activation operand of the next
+    // single-token steps, fused form (round 3): LayerNorm applied on the activation operand of the next
     // product from row statistics, products with complete outputs (no split-K reduce launch) except the MLP's second one, whose
     // split-K slices of the residual products finished together with the residual add and the next statistics: 9 launches per layer
     // instead of 11 (complete-output products — 72 / 24 / 96 workgroups walking three chunks each — were 21 us against 9 + 4: dropped)
-    static const bool no_fuse = glass_knob("GLASS_GPT2_NO_FUSE") != nullptr;
     // (the launcher's own shape conditions, asked through the launcher's predicate: a product it refuses returns 0 slices and nothing written)
-    const bool fuse_ok = !no_fuse && gemm_f32_step_supported(P, D, D, true) && gemm_f32_step_supported(P, 4 * D, 4 * D, false);
+    const bool fuse_ok = gemm_f32_step_supported(P, D, D, true) && gemm_f32_step_supported(P, 4 * D, 4 * D, false);
     bool step_refused = false;
-    static const bool no_attn_step = glass_knob("GLASS_GPT2_NO_ATTN_STEP") != nullptr;   // A/B knob
     // fused step tail (round 4): the pick also writes the NEXT step's embedding + first LayerNorm statistics and advances the state — a step
-    // starts at layer 0's qkv product; the first step's embedding is one eager launch after the prefill.  A/B knob: GLASS_GPT2_NO_TAIL.
-    static const bool no_head = glass_knob("GLASS_GPT2_NO_HEAD") != nullptr;   // A/B knob: generic product + two-stage arg-max
-    static const bool no_tail = glass_knob("GLASS_GPT2_NO_TAIL") != nullptr;
-    const bool tail_fused = fuse_ok && !no_head && !no_tail && D <= 1024 && gpt2_head_supported(P, V, D, D);
+    // starts at layer 0's qkv product; the first step's embedding is one eager launch after the prefill.
+    const bool tail_fused = fuse_ok && D <= 1024 && gpt2_head_supported(P, V, D, D);
     auto pass = [&](int nd, int past, const int* step_state) {
         const int M = P * nd;
         // round 4 (gpt2.hip): the attention output product and the MLP's first product in the complete-output form — no slices, so no
         // gpt2_finalize / splitk_reduce launch behind them: 6 launches per layer instead of 8.  (The qkv product and the MLP's second one
-        // stay split: complete, they were 12-14 us against 9.5 and 34 against 12 + 5.)  A/B knob: GLASS_GPT2_NO_ROWBLK.
-        static const bool no_rowblk = glass_knob("GLASS_GPT2_NO_ROWBLK") != nullptr;
-        const bool rowblk = step_state && fuse_ok && !no_rowblk && D % 32 == 0 && D / 32 <= 24 &&
+        // stay split: complete, they were 12-14 us against 9.5 and 34 against 12 + 5.)
+        const bool rowblk = step_state && fuse_ok && D % 32 == 0 && D / 32 <= 24 &&
                             gemm_f32_rowblk_supported(P, D, D, D, false, true) && gemm_f32_rowblk_supported(P, 4 * D, D, D, true, false);
         if (step_state) { if (!tail_fused) launch_gpt2_embed_step(w.d_gen, step_state, P, e->g_wte, e->g_wpe, D, w.x, st, fuse_ok ? w.stats : nullptr); }
         else launch_gpt2_embed(w.d_tok, e->g_wte, e->g_wpe, M, nd, past, D, w.x, st);
@@ -1840,7 +1767,7 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
                 float* vcl = w.vc + (size_t)l * P * Tmax * D;
                 int S = launch_gemm_f32_step(w.x, b.w_qkv, b.b_qkv, w.qkv, P, 3 * D, D, D, 3 * D, 0, st, w.part, w.part_elems, w.stats, b.ln1_g, b.ln1_b);
                 step_refused |= S == 0;
-                if (Tmax <= 64 && !no_attn_step) {      // one wave per (sequence, head); it sums the product's slices itself
+                if (Tmax <= 64) {      // one wave per (sequence, head); it sums the product's slices itself
                     launch_gpt2_attention_step(w.qkv, S > 1 ? w.part : nullptr, S, b.b_qkv, kcl, vcl, P, Tmax, heads, w.att, st, step_state);
                 } else {
                     if (S > 1) launch_gpt2_reduce(w.part, S, b.b_qkv, w.qkv, P, 3 * D, 3 * D, 0, st);
@@ -1871,10 +1798,10 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
                                                            e->g_wpe, w.x, w.stats, st);
                 return;
             }
-            const bool head = !no_head && (samp ? launch_gpt2_head_sample(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.logits, w.pairs,
-                                                                          w.d_samp, w.d_gen, w.d_state, false, nullptr, nullptr, nullptr, nullptr, st)
-                                                : launch_gpt2_head(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, nullptr, w.pairs, w.d_gen,
-                                                                   w.d_state, st));
+            const bool head = samp ? launch_gpt2_head_sample(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.logits, w.pairs,
+                                                             w.d_samp, w.d_gen, w.d_state, false, nullptr, nullptr, nullptr, nullptr, st)
+                                   : launch_gpt2_head(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, nullptr, w.pairs, w.d_gen,
+                                                      w.d_state, st);
             if (!head) {
                 // ln_f fused; the real vocabulary (1571 column blocks) is never split, a small one may be
                 const int S = launch_gemm_f32_step(w.x, e->g_wte, nullptr, w.logits, P, V, D, D, V, 0, st, w.part, w.part_elems, w.stats, e->g_lnf_g, e->g_lnf_b);
@@ -1918,8 +1845,7 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
     if (length > 1) {
         // the 29 single-token steps are the same ~190 launches each: capture one step once, replay it (launch latency, not work,
         // is what the un-graphed loop spent its time on)
-        static const bool no_graph = glass_knob("GLASS_GPT2_NO_GRAPH") != nullptr;   // A/B knob
-        if (!w.exec && !no_graph) {
+        if (!w.exec) {
             err = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
             if (err == hipSuccess) {
                 pass(1, 0, w.d_state);

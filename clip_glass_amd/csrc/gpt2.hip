@@ -209,12 +209,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* part, i
 #define GS_KC 64
 // Weight fragments of the single-token steps.  Non-temporal loads (MI355X_MICROARCH.md price list, row nt-weights: for weights that ONE CU
 // reads once) were measured here and LOSE (r05, same box: decode 27.7 -> 32.1 ms per population): the two row-block waves of a workgroup
-// read the same fragments, and the second one finds them in the L1 only with the default policy.  -DGLASS_GPT2_NT rebuilds the experiment.
-#ifdef GLASS_GPT2_NT
-#define GS_WLOAD(p) __builtin_nontemporal_load((const f4*)(p))
-#else
+// read the same fragments, and the second one finds them in the L1 only with the default policy.
 #define GS_WLOAD(p) (*(const f4*)(p))
-#endif
 // LNX: the activation operand is LayerNorm(A) (model.py:15-28), applied to the fragments in registers: (a - mean[m]) * rstd[m] * g[k] + b[k] with
 // the row statistics from gpt2_finalize_kernel (same arithmetic as layernorm_kernel) and g / b of the workgroup's K slice parked in LDS —
 // the separate LayerNorm launch and its [M][D] round trip are gone.
@@ -980,10 +976,9 @@ int launch_gemm_f32_step(const float* A, const float* W, const float* bias, floa
     // {1, 2, 4, 6} take the one with the most workgroups that still fit the chip in ONE round (nb * S <= CUs: 288 workgroups on 256 CUs
     // ran the MLP products at 14 us against 9.7 us for the 216 of the qkv product), fewest slices among equals; a product too small to
     // fill the CUs either way takes the most slices its scratch allows.
-    static const bool old_rule = glass_knob("GLASS_GPT2_OLD_SPLIT") != nullptr;     // A/B knob
     const int C = K / GS_KC, n_cu = glass_cu_count();
     int S = 0, NK = 1;
-    if (!old_rule && nb < 1024) {
+    if (nb < 1024) {
         static const int nks[] = {6, 4, 2, 1};          // (8 parts = 1024 threads = a 128-VGPR budget: spills)
         int best_wg = -1;
         for (int nk : nks) {
@@ -996,7 +991,7 @@ int launch_gemm_f32_step(const float* A, const float* W, const float* bias, floa
             if (S == 0 || score > best_wg) { best_wg = score; S = sl; NK = nk; }
         }
     }
-    if (S == 0) {      // the vocabulary projection (never split globally), shapes the rule above does not cover, and the A/B knob
+    if (S == 0) {      // the vocabulary projection (never split globally) and shapes the rule above does not cover
         S = 1; NK = 1;
         static const int cand[] = {1, 2, 3, 4, 6, 8, 12, 16};
         for (int c : cand) {
@@ -1021,8 +1016,7 @@ void launch_gpt2_reduce(const float* part, int S, const float* bias, float* out,
 // `part`: scratch for split-K partial sums (nullable = never split); sized by the caller for GPT2_SPLITK_MAX slices of M x N.
 void launch_gemm_f32(const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int lda, int ldo,
                      int mode, hipStream_t st, float* part, size_t part_elems, bool prefill) {
-    static const bool no_stream = glass_knob("GLASS_GPT2_NO_STREAM") != nullptr;      // A/B knob: round 2's gemm_f32_kernel<64,64> for the steps
-    if (!prefill && M <= 64 && K % GS_KC == 0 && lda % 4 == 0 && !no_stream) {
+    if (!prefill && M <= 64 && K % GS_KC == 0 && lda % 4 == 0) {
         // a workgroup per 32 weight rows; global K split S (small: the partial sums are traffic) x NK K parts inside the workgroup so
         // that a wave's share is one or two 64-deep chunks; the vocabulary projection (1571 workgroups) is not split globally
         const int nb = (N + 31) / 32;
@@ -1057,17 +1051,12 @@ void launch_gemm_f32(const float* A, const float* W, const float* bias, float* o
             hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long long)M * N + 255) / 256)), dim3(256), 0, st, part, S, bias, out,
                                M, N, ldo, mode);
     } else {
-        // prefill: 64 x 64 tiles for every product.  Measured per shape over the whole decode (M = 64 x 23 rows, GLASS_GPT2_TILE): 128 x 128
+        // prefill: 64 x 64 tiles for every product.  Measured per shape over the whole decode (M = 64 x 23 rows): 128 x 128
         // everywhere 30.4 ms, 128 x 64 28.3, the shape whose grid quantises best on the CUs 28.2, 64 x 64 27.8 — a 64 x 64 workgroup is 17 KB
         // of LDS and 32 VGPRs, so a CU holds many of them and their barriers / LDS round trips overlap; the larger tiles run one
         // workgroup (one wave per SIMD) per CU.  Every shape adds an element's k terms in the same order: the choice never changes a value.
-        static const int shapes[3][2] = {{128, 128}, {128, 64}, {64, 64}};
-        static const int force = glass_knob("GLASS_GPT2_TILE") ? atoi(glass_knob("GLASS_GPT2_TILE")) : -1;   // A/B knob
-        const int best = (force >= 0 && force < 3) ? force : 2;
-        const dim3 g((M + shapes[best][0] - 1) / shapes[best][0], (N + shapes[best][1] - 1) / shapes[best][1], 1);
-        if (best == 0) hipLaunchKernelGGL((gemm_f32_kernel<128, 128>), g, dim3(256), 0, st, A, W, bias, out, M, N, K, lda, ldo, mode, part);
-        else if (best == 1) hipLaunchKernelGGL((gemm_f32_kernel<128, 64>), g, dim3(256), 0, st, A, W, bias, out, M, N, K, lda, ldo, mode, part);
-        else hipLaunchKernelGGL((gemm_f32_kernel<64, 64>), g, dim3(256), 0, st, A, W, bias, out, M, N, K, lda, ldo, mode, part);
+        const dim3 g((M + 63) / 64, (N + 63) / 64, 1);
+        hipLaunchKernelGGL((gemm_f32_kernel<64, 64>), g, dim3(256), 0, st, A, W, bias, out, M, N, K, lda, ldo, mode, part);
     }
 }
 

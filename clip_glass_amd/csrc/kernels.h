@@ -14,7 +14,7 @@ const char* launch_conv_stream(const ConvParams& p, hipStream_t st);
 const char* launch_conv_gemm(const ConvParams& p, half_t* ws_a, long long cap_a, float* ws_c, long long cap_c, hipStream_t st);
 bool conv_stream_applies(const ConvParams& p);   // trgb_yout set: the fused conv + toRGB form
 // LDS-DMA staged 3x3 conv for the MFMA-bound mid-resolution layers (conv_glds.hip); nullptr when unsupported / disabled
-const char* launch_conv_glds(const ConvParams& p, hipStream_t st, bool force = false);
+const char* launch_conv_glds(const ConvParams& p, hipStream_t st);
 // conv_wreg.hip: 3x3 stride-1 conv 64 -> 64 channels with the WHOLE weight tensor in registers, one wave per SIMD, the patches on a three-tile
 // LDS-DMA ring (tried first by launch_conv_glds); reads pixel-major or chunk-planar input; nullptr: the layer does not qualify
 const char* launch_conv_wreg(const ConvParams& p, hipStream_t st);

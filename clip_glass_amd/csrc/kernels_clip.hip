@@ -308,13 +308,12 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const half_t* qkv, 
 void launch_attention(const half_t* qkv, int n_img, int L, int heads, int hd, int causal, half_t* out,
                       hipStream_t st) {
     (void)hd;  // 64 (asserted by the engine)
-    static const bool no_mfma = glass_knob("GLASS_NO_ATTN_MFMA") != nullptr;   // A/B knob
-    if (L <= 64 && !no_mfma) {
+    if (L <= 64) {
         const int n_pairs = n_img * heads;
         hipLaunchKernelGGL(attention_mfma_kernel<2>, dim3((n_pairs + 1) / 2), dim3(256), 0, st, qkv, L, heads, n_pairs, causal, out);
         return;
     }
-    if (L <= 96 && !no_mfma) {          // the text tower's context (77)
+    if (L <= 96) {          // the text tower's context (77)
         const int n_pairs = n_img * heads;
         hipLaunchKernelGGL(attention_mfma_kernel<3>, dim3(n_pairs), dim3(256), 0, st, qkv, L, heads, n_pairs, causal, out);
         return;

@@ -847,8 +847,7 @@ __global__ __launch_bounds__(1024) void mbstd_vec_kernel(const half_t* x, int hw
 void launch_mbstd(const half_t* x, int B, int hw, int C, int Cpad, int batch_size, int group, float eps,
                   half_t* out, hipStream_t st) {
     const int nsub = batch_size / group;
-    static const bool scalar = glass_knob("GLASS_MBSTD_SCALAR") != nullptr;      // A/B knob
-    if ((C & 7) == 0 && (Cpad & 7) == 0 && group <= 8 && !scalar) {
+    if ((C & 7) == 0 && (Cpad & 7) == 0 && group <= 8) {
         hipLaunchKernelGGL(mbstd_vec_kernel, dim3((B / batch_size) * nsub), dim3(1024), 0, st, x, hw, C, Cpad, batch_size, group, eps, out);
         return;
     }

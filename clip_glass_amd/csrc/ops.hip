@@ -155,7 +155,7 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     } else if (d->impl == 5) {
         if (p.skip_x) {
             if (!launch_conv_s2(p, 0, true)) { glass_set_error("LDS-DMA stride-2 conv: unsupported shape"); return GLASS_ERR_ARG; }
-        } else if (!launch_conv_glds(p, 0, true)) { glass_set_error("LDS-DMA conv: unsupported shape"); return GLASS_ERR_ARG; }
+        } else if (!launch_conv_glds(p, 0)) { glass_set_error("LDS-DMA conv: unsupported shape"); return GLASS_ERR_ARG; }
     } else if (!(d->up && launch_upconv_fused(p, 0)) && !launch_conv_stream(p, 0) && !launch_conv_tiled(p, 0) && !launch_conv_direct(p, 0)) {
         glass_set_error("no kernel accepts this convolution");
         return GLASS_ERR_ARG;
