@@ -94,6 +94,31 @@ std::vector<float> transposed(const float* W, int N, int K, float coef) {
 // ------------------------------------------------------------------------------------
 // create / destroy / load
 // ------------------------------------------------------------------------------------
+// The one rule for the CLIP image tower's geometry (host only: no device is touched).  Every kernel of the tower is written in
+// terms of the token count, the width and the patch size; what is fixed is the head dimension (the attention kernels are built for
+// 64) and the GEMMs' 64-wide N tiles.  The patch-embedding GEMM's K = 3 patch^2 is padded to the K step by the engine.
+extern "C" int glass_clip_geometry_supported(int32_t width, int32_t layers, int32_t heads, int32_t patch, int32_t res, int32_t embed) {
+    char msg[256];
+#define GEOM_REQ(cond, ...)                       \
+    if (!(cond)) {                                \
+        snprintf(msg, sizeof msg, __VA_ARGS__);   \
+        glass_set_error(msg);                     \
+        return GLASS_ERR_ARG;                     \
+    }
+    GEOM_REQ(width > 0 && layers > 0 && heads > 0 && patch > 0 && res > 0 && embed > 0,
+             "unsupported CLIP geometry: width, layers, heads, patch, resolution and embed must be positive");
+    GEOM_REQ(width % heads == 0 && width / heads == 64,
+             "unsupported CLIP geometry: head dim must be 64 (width %d / heads %d)", width, heads);
+    GEOM_REQ(res % patch == 0, "unsupported CLIP geometry: resolution %d is not a multiple of patch %d", res, patch);
+    GEOM_REQ(patch <= 64 && res / patch <= 63,
+             "unsupported CLIP geometry: patch %d / grid %d out of range (patch <= 64, at most 63 x 63 patches)", patch, res / patch);
+    GEOM_REQ(layers <= 64 && width <= 4096 && embed <= 4096, "unsupported CLIP geometry: layers %d / width %d / embed %d out of range",
+             layers, width, embed);
+#undef GEOM_REQ
+    return GLASS_OK;
+}
+static int clip_patch_k(const glass_config& c) { return (3 * c.clip_patch * c.clip_patch + 63) / 64 * 64; }   // patch rows padded to gemm_tiled's K step
+
 extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) {
     REQUIRE(cfg && out, GLASS_ERR_ARG, "null argument");
     REQUIRE(cfg->n_blocks >= 0 && cfg->n_blocks <= GLASS_MAX_BLOCKS, GLASS_ERR_ARG, "n_blocks out of range");
@@ -110,10 +135,9 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
         REQUIRE(cfg->mbstd_group >= 2 && cfg->mbstd_group <= 8 && cfg->batch_size % cfg->mbstd_group == 0, GLASS_ERR_ARG,
                 "batch_size must be a multiple of mbstd_group (modules.py:716)");
     }
-    REQUIRE(cfg->clip_width > 0 && cfg->clip_width % 16 == 0 && cfg->clip_heads > 0 &&
-                cfg->clip_width / cfg->clip_heads == 64 && cfg->clip_patch > 0 &&
-                cfg->clip_res % cfg->clip_patch == 0 && (3 * cfg->clip_patch * cfg->clip_patch) % 16 == 0,
-            GLASS_ERR_ARG, "unsupported CLIP geometry (head dim must be 64)");
+    if (int grc = glass_clip_geometry_supported(cfg->clip_width, cfg->clip_layers, cfg->clip_heads, cfg->clip_patch, cfg->clip_res,
+                                                cfg->clip_embed))
+        return grc;
     REQUIRE(cfg->noise_mode >= 0 && cfg->noise_mode <= 2, GLASS_ERR_ARG, "noise_mode must be 0,1,2");
     int bg_res = 0;
     if (cfg->generator == GLASS_GEN_BIGGAN_DEEP) {
@@ -506,7 +530,14 @@ static int finalize_clip(glass_engine* e) {
     REQUIRE(numel(conv1) == (size_t)W * 3 * ps * ps && numel(cls) == (size_t)W && numel(pos) == (size_t)T * W &&
                 numel(proj) == (size_t)W * E,
             GLASS_ERR_ARG, "bad CLIP visual shapes");
-    int rc = upload(e, &e->c_patch_w, to_half(conv1->data.data(), numel(conv1)));
+    const int K = 3 * ps * ps, Kp = clip_patch_k(c);
+    std::vector<_Float16> pw = to_half(conv1->data.data(), numel(conv1));
+    if (Kp != K) {      // [W][Kp] with zero columns (patch 14: 588 -> 640)
+        std::vector<_Float16> padded((size_t)W * Kp, (_Float16)0.f);
+        for (int n = 0; n < W; ++n) std::copy(pw.begin() + (size_t)n * K, pw.begin() + (size_t)(n + 1) * K, padded.begin() + (size_t)n * Kp);
+        pw.swap(padded);
+    }
+    int rc = upload(e, &e->c_patch_w, pw);
     if (rc) return rc;
     if ((rc = upload(e, &e->c_cls, cls->data))) return rc;
     if ((rc = upload(e, &e->c_pos, pos->data))) return rc;
@@ -641,7 +672,9 @@ static int alloc_buffers(glass_engine* e) {
     }
     if ((rc = dev_alloc(e, &e->d_img, (size_t)CH * 3 * e->R * e->R))) return rc;
     const int W = c.clip_width, ps = c.clip_patch, G = c.clip_res / ps, T = G * G + 1;
-    if ((rc = dev_alloc(e, &e->d_patches, (size_t)P * G * G * 3 * ps * ps))) return rc;
+    const size_t Kp = (size_t)clip_patch_k(c);
+    if ((rc = dev_alloc(e, &e->d_patches, (size_t)P * G * G * Kp))) return rc;
+    if (Kp != (size_t)3 * ps * ps) GLASS_HIP(hipMemset(e->d_patches, 0, (size_t)P * G * G * Kp * sizeof(half_t)));   // the row tails stay zero: no kernel writes them
     if ((rc = dev_alloc(e, &e->d_pe, (size_t)P * G * G * W))) return rc;
     if ((rc = dev_alloc(e, &e->d_x, (size_t)P * T * W))) return rc;
     if ((rc = dev_alloc(e, &e->d_ln16, (size_t)P * T * W))) return rc;
@@ -1285,7 +1318,7 @@ void run_clip(glass_engine* e, int P, int l0, int l1) {
     GemmParams g;
     if (l0 == 0) {
         memset(&g, 0, sizeof g);
-        g.a = e->d_patches; g.w = e->c_patch_w; g.M = P * G * G; g.N = W; g.K = 3 * ps * ps; g.mode = 3; g.out32 = e->d_pe; g.ldo = W; g.cand_rows = G * G;
+        g.a = e->d_patches; g.w = e->c_patch_w; g.M = P * G * G; g.N = W; g.K = clip_patch_k(c); g.mode = 3; g.out32 = e->d_pe; g.ldo = W; g.cand_rows = G * G;
         run_gemm(e, g, "clip.patch_embed");
         Prof pr(e, "clip.embed_lnpre", 0, 8.0 * M * W);
         launch_embed_lnpre(e->d_pe, e->c_cls, e->c_pos, e->c_lnpre_g, e->c_lnpre_b, P, T, W, e->d_x, e->cur);
@@ -1361,7 +1394,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
             }
             if (out_F) {
                 Prof pr(e, "clip.resize", 0, B * (16.0 * c.clip_res * c.clip_res * 3 + 2.0 * 3 * c.clip_res * c.clip_res));
-                launch_resize_patches(y, B, e->R, c.clip_res, ps, e->d_patches + (size_t)c0 * G * G * 3 * ps * ps, e->cur);
+                launch_resize_patches(y, B, e->R, c.clip_res, ps, clip_patch_k(c), e->d_patches + (size_t)c0 * G * G * clip_patch_k(c), e->cur);
             }
         }
         if (out_F) {
@@ -1453,7 +1486,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
             e->cur = sd;
             {
                 Prof pr(e, "clip.resize", 0, B * (16.0 * c.clip_res * c.clip_res * 3 + 2.0 * 3 * c.clip_res * c.clip_res));
-                launch_resize_patches(y, B, e->R, c.clip_res, ps, e->d_patches + (size_t)c0 * G * G * 3 * ps * ps,
+                launch_resize_patches(y, B, e->R, c.clip_res, ps, clip_patch_k(c), e->d_patches + (size_t)c0 * G * G * clip_patch_k(c),
                                       e->cur);
             }
             if (clip_ov && c0 + e->chunk >= P) {   // last chunk's patches are in place: CLIP starts now
@@ -1609,7 +1642,7 @@ extern "C" int glass_engine_encode_image(glass_engine* e, const float* images, i
     GLASS_HIP(hipMalloc(&d_img, elems * sizeof(float)));
     hipError_t err = hipMemcpyAsync(d_img, images, elems * sizeof(float), hipMemcpyHostToDevice, e->stream);
     e->cur = e->stream;
-    launch_image_patches(d_img, n, c.clip_res, c.clip_patch, e->d_patches, e->stream);
+    launch_image_patches(d_img, n, c.clip_res, c.clip_patch, clip_patch_k(c), e->d_patches, e->stream);
     run_clip(e, n, 0, 1 << 20);
     if (err == hipSuccess)
         err = hipMemcpyAsync(out_feat, e->d_feat, (size_t)n * c.clip_embed * sizeof(float), hipMemcpyDeviceToHost, e->stream);

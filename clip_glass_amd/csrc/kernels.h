@@ -77,7 +77,7 @@ bool launch_torgb(const half_t* x, int B, int H, int W, int C, const float* wrgb
 // img = clip((y+1)/2, 0, 1)
 void launch_finalize_image(const float* y, float* img, long long n, hipStream_t st);
 // bilinear (align_corners=False) resize of clip((y+1)/2,0,1) into the patch matrix [B*G*G][3*ps*ps] fp16
-void launch_resize_patches(const float* y, int B, int R, int clip_res, int ps, half_t* patches,
+void launch_resize_patches(const float* y, int B, int R, int clip_res, int ps, int ld, half_t* patches,
                            hipStream_t st);
 void launch_fromrgb(const float* y, int B, int R, int Cout, const float* w, const float* bias,
                     half_t* out, hipStream_t st);
@@ -175,4 +175,4 @@ bool launch_gpt2_head_sample(const float* A, const float* W, int M, int N, int K
                              float* logits, float* pairs, const int* sp, int* gen, int* state, bool tail, const float* wte, const float* wpe, float* x,
                              float* stats_out, hipStream_t st);
 // NCHW fp32 image [n][3][S][S] -> CLIP patch matrix [n*G*G][3*ps*ps] fp16
-void launch_image_patches(const float* img, int n, int S, int ps, half_t* patches, hipStream_t st);
+void launch_image_patches(const float* img, int n, int S, int ps, int ld, half_t* patches, hipStream_t st);

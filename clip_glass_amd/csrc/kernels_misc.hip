@@ -572,8 +572,9 @@ void launch_finalize_image(const float* y, float* img, long long n, hipStream_t 
 
 // ---- kornia.resize(x,(224,224)) (generator.py:45) on biggan_norm(y), written straight
 // into the patch-embedding GEMM operand: row = b*G*G + gy*G + gx, col = c*ps*ps + iy*ps + ix
-// (conv1.weight.reshape(width, -1) order, clip/model.py:206,219).
-__global__ void resize_patches_kernel(const float* y, int B, int R, int S, int ps, half_t* patches) {
+// (conv1.weight.reshape(width, -1) order, clip/model.py:206,219).  ld = elements per row (>= 3 ps ps: the engine pads its rows to the
+// GEMM's K step and keeps the tail zero).
+__global__ void resize_patches_kernel(const float* y, int B, int R, int S, int ps, int ld, half_t* patches) {
     const int G = S / ps;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // over b, c, Y, X
     const int X = (int)(idx % S);
@@ -594,13 +595,13 @@ __global__ void resize_patches_kernel(const float* y, int B, int R, int S, int p
     const float v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
     const int gy = Y / ps, iy = Y - gy * ps, gx = X / ps, ix = X - gx * ps;
     const long long row = ((long long)b * G + gy) * G + gx;
-    patches[row * (3LL * ps * ps) + ((long long)c * ps + iy) * ps + ix] = (half_t)v;
+    patches[row * ld + ((long long)c * ps + iy) * ps + ix] = (half_t)v;
 }
-void launch_resize_patches(const float* y, int B, int R, int clip_res, int ps, half_t* patches, hipStream_t st) {
+void launch_resize_patches(const float* y, int B, int R, int clip_res, int ps, int ld, half_t* patches, hipStream_t st) {
     const long long n = 3LL * clip_res * clip_res;  // per image
     const long long total = n * B;
     hipLaunchKernelGGL(resize_patches_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, y, B, R,
-                       clip_res, ps, patches);
+                       clip_res, ps, ld, patches);
 }
 
 // ---- D fromRGB: biggan_denorm (utils.py:19-21) + 1x1 conv 3->C + bias + lrelu*sqrt2

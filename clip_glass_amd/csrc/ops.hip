@@ -332,7 +332,7 @@ extern "C" int glass_op_resize(int32_t device, int32_t B, int32_t R, int32_t S, 
     float* dy = dv.up32(y, (size_t)B * 3 * R * R);
     const size_t n = (size_t)B * 3 * S * S;
     half_t* dp = dv.alloc<half_t>(n);
-    launch_resize_patches(dy, B, R, S, ps, dp, 0);
+    launch_resize_patches(dy, B, R, S, ps, 3 * ps * ps, dp, 0);
     int rc = finish();
     if (rc) return rc;
     return down16(patches, dp, n);
@@ -353,7 +353,7 @@ extern "C" int glass_op_layernorm(int32_t device, int32_t M, int32_t D, const fl
 
 extern "C" int glass_op_attention(int32_t device, int32_t n_img, int32_t L, int32_t heads, int32_t causal,
                                   const float* qkv, float* out) {
-    OPREQ(qkv && out && L <= 128, "bad argument");
+    OPREQ(qkv && out && n_img > 0 && heads > 0 && L >= 1 && L <= 4096, "bad argument (1 <= L <= 4096)");
     GLASS_HIP(hipSetDevice(device));
     Dev dv;
     const int D = heads * 64;

@@ -58,6 +58,8 @@ def load_library(path=None):
     lib.glass_last_error.restype = C.c_char_p
     lib.glass_version.restype = C.c_char_p
     lib.glass_engine_create.argtypes = [C.POINTER(GlassConfig), C.POINTER(C.c_void_p)]
+    if hasattr(lib, "glass_clip_geometry_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
+        lib.glass_clip_geometry_supported.argtypes = [C.c_int32] * 6
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -96,6 +98,14 @@ def _f32(a):
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def clip_geometry_supported(geometry):
+    """(ok, message) for a CLIP image tower (width, layers, heads, patch, input_res, embed): the library's own rule, the one
+    glass_engine_create applies.  Host only: needs the built library, not a GPU."""
+    lib = load_library()
+    rc = lib.glass_clip_geometry_supported(*[int(v) for v in geometry])
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
 
 
 def device_info(device=0):

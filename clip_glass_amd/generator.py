@@ -10,10 +10,49 @@ import os
 import numpy as np
 
 from . import synth
-from .engine import Engine
+from .engine import Engine, clip_geometry_supported
 from .utils import save_grid, save_image
 
 CLIP_VIT_B32 = (768, 12, 12, 32, 224, 512)
+# Named image towers: (width, layers, heads, patch, input_res, embed) as clip/model.py:363-399 derives them from the released
+# checkpoints, and the text tower that goes with each (the embed dim is shared).  The engine runs any ViT with head dim 64
+# (glass_clip_geometry_supported); these are the ones `config.clip_model` / `--clip-model` can name.
+CLIP_MODELS = {
+    "ViT-B/32": CLIP_VIT_B32,
+    "ViT-B/16": (768, 12, 12, 16, 224, 512),
+    "ViT-L/14": (1024, 24, 16, 14, 224, 768),
+    "ViT-L/14@336": (1024, 24, 16, 14, 336, 768),
+}
+CLIP_TEXT_MODELS = {
+    "ViT-B/32": dict(width=512, layers=12),
+    "ViT-B/16": dict(width=512, layers=12),
+    "ViT-L/14": dict(width=768, layers=12),
+    "ViT-L/14@336": dict(width=768, layers=12),
+}
+DEFAULT_CLIP_MODEL = "ViT-B/32"
+
+
+def clip_model_geometry(name):
+    """Geometry of a named image tower; ValueError lists the names when it is not one of them."""
+    if name not in CLIP_MODELS:
+        raise ValueError("unknown CLIP model %r: expected one of %s" % (name, ", ".join(sorted(CLIP_MODELS))))
+    return CLIP_MODELS[name]
+
+
+def clip_model_name(geometry):
+    """Name of the tower with this geometry, or None."""
+    geometry = tuple(int(v) for v in geometry)
+    for name, g in CLIP_MODELS.items():
+        if g == geometry:
+            return name
+    return None
+
+
+def check_clip_geometry(geometry):
+    """Raise ValueError with the library's message when the engine cannot run this image tower — before any engine is built."""
+    ok, msg = clip_geometry_supported(geometry)
+    if not ok:
+        raise ValueError("CLIP image tower %s: %s" % (tuple(int(v) for v in geometry), msg))
 
 
 def clip_geometry_from_state(state):
@@ -44,15 +83,19 @@ def _load_clip_state(config, with_text):
     if w is None:
         # the reference always loads the pretrained ViT-B/32 (clip/clip.py:29-33); a silent random-weight CLIP would run a
         # whole search against meaningless fitness values
-        raise RuntimeError("config.clip_weights is not set: pass the CLIP ViT-B/32 checkpoint (--clip-weights PATH), or "
+        raise RuntimeError("config.clip_weights is not set: pass a CLIP ViT checkpoint (--clip-weights PATH), or "
                            "'synthetic:<seed>' explicitly for tests / benchmarks")
     w = str(w)
     if w.startswith("synthetic"):
         seed = int(w.split(":")[1]) if ":" in w else 0
-        geom = tuple(getattr(config, "clip_geometry", CLIP_VIT_B32))
+        # an explicit clip_geometry wins; otherwise the named model (default ViT-B/32) gives both towers' geometry
+        model = getattr(config, "clip_model", None) or DEFAULT_CLIP_MODEL
+        geom = getattr(config, "clip_geometry", None)
+        named = geom is None
+        geom = tuple(clip_model_geometry(model) if named else geom)
         state = synth.make_state(synth.clip_visual_spec(geom[0], geom[1], geom[3], geom[4], geom[5]), seed)
         if with_text:
-            tg = getattr(config, "clip_text_geometry", dict(width=512, layers=12))
+            tg = getattr(config, "clip_text_geometry", None) or (CLIP_TEXT_MODELS[model] if named else dict(width=512, layers=12))
             state.update(synth.make_state(synth.clip_text_spec(width=tg["width"], layers=tg["layers"],
                                                                vocab=tg.get("vocab", 49408), out_dim=geom[5]), seed))
         return state, geom
@@ -62,7 +105,12 @@ def _load_clip_state(config, with_text):
     except RuntimeError:
         sd = torch.load(w, map_location="cpu")
     state = clip_state_from_checkpoint(sd, with_text)
-    return state, clip_geometry_from_state(state)
+    geom = clip_geometry_from_state(state)
+    model = getattr(config, "clip_model", None)
+    if model is not None and clip_model_geometry(model) != geom:      # the checkpoint decides; a name that disagrees is a mistake
+        raise ValueError("clip_model %r is %s, but the checkpoint %s holds %s %s"
+                         % (model, clip_model_geometry(model), w, clip_model_name(geom) or "an unnamed tower", geom))
+    return state, geom
 
 
 def clip_preprocess(path_or_image, n_px=224):
@@ -115,6 +163,8 @@ class Generator:
         self.sharder = None
         if config.task == "img2txt":                                        # generator.py:25-27, 52-59
             clip_state, geom = _load_clip_state(config, True)
+            check_clip_geometry(geom)
+            self.clip_geometry = tuple(int(v) for v in geom)
             self.engine = Engine([], latent_size=4, mapping_layers=0, batch_size=1, use_discriminator=False, n_obj=1,
                                  max_pop=pop, clip=geom, noise_mode=0, device=device)
             self.engine.load_state(self.model.state)
@@ -130,6 +180,8 @@ class Generator:
             return
         need_text = getattr(config, "target_features", None) is None
         clip_state, geom = _load_clip_state(config, need_text)
+        check_clip_geometry(geom)        # an unsupported checkpoint fails here, not in generation 1
+        self.clip_geometry = tuple(int(v) for v in geom)
         pop = (pop + config.batch_size - 1) // config.batch_size * config.batch_size
         if hasattr(self.model, "geometry"):     # BigGAN-deep (models.py:64-86)
             self.engine = Engine([], batch_size=config.batch_size, max_pop=pop, chunk=getattr(config, "chunk", 0),

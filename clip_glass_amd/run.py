@@ -14,6 +14,7 @@ import pickle
 import numpy as np
 
 from .config import get_config
+from .generator import CLIP_MODELS
 from .operators import get_operators
 from .problem import GenerationProblem
 from . import search
@@ -29,7 +30,11 @@ def build_parser():
     p.add_argument("--target", type=str, default="a wolf at night with the moon in the background")
     # additions (no checkpoints / vocab in this environment)
     p.add_argument("--weights", type=str, default=None, help="directory with G.pth/D.pth, or synthetic:<seed>")
-    p.add_argument("--clip-weights", type=str, default=None, help="ViT-B-32.pt, or synthetic:<seed>")
+    p.add_argument("--clip-weights", type=str, default=None,
+                   help="a CLIP ViT checkpoint (ViT-B-32.pt, ViT-B-16.pt, ViT-L-14.pt, ...: the geometry is read from it), or synthetic:<seed>")
+    p.add_argument("--clip-model", type=str, default=None, choices=sorted(CLIP_MODELS),
+                   help="CLIP image tower: selects the geometry of synthetic weights (default ViT-B/32); with a checkpoint it must "
+                        "agree with what the checkpoint holds")
     p.add_argument("--bpe-path", type=str, default=None)
     p.add_argument("--pop-size", type=int, default=None)
     p.add_argument("--stochastic", action="store_true", default=None,
@@ -46,7 +51,7 @@ def main(argv=None, extra_config=None):
     config = build_parser().parse_args(argv)
     over = {k: v for k, v in vars(config).items() if v is not None}
     vars(config).update(get_config(config.config))                             # run.py:25
-    for k in ("weights", "clip_weights", "bpe_path", "pop_size", "stochastic"):
+    for k in ("weights", "clip_weights", "clip_model", "bpe_path", "pop_size", "stochastic"):
         if k in over:
             setattr(config, k, over[k])
     if extra_config:

@@ -54,7 +54,7 @@ typedef struct glass_config {
     int32_t n_obj;                /* problem_args["n_obj"] (problem.py:21) */
     int32_t max_pop;              /* capacity in candidates (rows of x) */
     int32_t chunk;                /* candidates resident per pass at high resolution (multiple of batch_size; 0 = auto) */
-    int32_t clip_width, clip_layers, clip_heads, clip_patch, clip_res, clip_embed; /* 768,12,12,32,224,512 */
+    int32_t clip_width, clip_layers, clip_heads, clip_patch, clip_res, clip_embed; /* 768,12,12,32,224,512 (ViT-B/32); see glass_clip_geometry_supported */
     int32_t noise_mode;           /* 0 none, 1 device Philox N(0,1) planes, 2 caller-provided planes */
     uint64_t noise_seed;
     /* --- BigGAN-deep generator (configs DeepMindBigGAN256/512, config.py:31-74; models.py:64-86 calls
@@ -84,6 +84,13 @@ typedef struct glass_noise {
 
 const char* glass_last_error(void);
 const char* glass_version(void);
+
+/* Which CLIP image towers the engine runs (host only: callable without a GPU).  Any ViT whose head dimension
+ * (width / heads) is 64 and whose input resolution is a multiple of its patch size: ViT-B/32, ViT-B/16,
+ * ViT-L/14, ViT-L/14@336 among them.  Returns GLASS_OK, or GLASS_ERR_ARG with the reason in
+ * glass_last_error().  glass_engine_create applies the same rule. */
+int glass_clip_geometry_supported(int32_t width, int32_t layers, int32_t heads, int32_t patch, int32_t res,
+                                  int32_t embed);
 
 int glass_engine_create(const glass_config* cfg, glass_engine** out);
 void glass_engine_destroy(glass_engine* e);
