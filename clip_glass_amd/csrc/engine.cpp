@@ -1726,6 +1726,9 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
     REQUIRE(e->g_wte != nullptr, GLASS_ERR_STATE, "GPT-2 weights were not loaded (gpt2.transformer.*)");
     const int D = e->g_dim, V = e->g_vocab, heads = D / 64, Tmax = nctx + length;
     REQUIRE(Tmax <= e->g_npos && Tmax <= 256, GLASS_ERR_ARG, "sequence longer than the position table / 256");
+    // the prefill attention holds a sequence's keys, values and its whole score matrix in LDS: 4 * (n^2 + 196 n) bytes of the 160 KB
+    REQUIRE(gpt2_attention_lds_bytes(nctx, nctx) <= GPT2_ATTENTION_LDS_MAX, GLASS_ERR_ARG,
+            "context longer than 126 tokens (the prefill attention keeps 4 * (n^2 + 196 n) bytes per sequence in 160 KB of LDS)");
     for (long long i = 0; i < (long long)P * nctx; ++i)
         REQUIRE(context[i] >= 0 && context[i] < V, GLASS_ERR_ARG, "token id out of range");
     GLASS_HIP(hipSetDevice(e->cfg.device));

@@ -1123,12 +1123,15 @@ __global__ __launch_bounds__(256) void gpt2_attention_kernel(const float* qkv, f
         out[((long long)seq * nd + i) * D + h * hd + d] = a;
     }
 }
+// LDS of one launch: q [nd][65], k / v [ns][65], scores [nd][ns + 1].  A workgroup has 160 KB: a prefill (nd == ns) fits up to 126
+// positions, a single-token step (nd == 1) any history the engine accepts (ns <= 256: 134 KB).
+size_t gpt2_attention_lds_bytes(int nd, int ns) { return ((size_t)nd * 65 + (size_t)2 * ns * 65 + (size_t)nd * (ns + 1)) * sizeof(float); }
 void launch_gpt2_attention(const float* qkv, float* kc, float* vc, int P, int nd, int past, int Tmax, int heads,
                            float* out, hipStream_t st, const int* past_dev) {
     const int ns = past_dev ? Tmax : past + nd;      // graph replay: LDS sized for the longest history
-    const size_t lds = (size_t)(nd * 65 + 2 * ns * 65 + nd * (ns + 1)) * sizeof(float);
+    const size_t lds = gpt2_attention_lds_bytes(nd, ns);
     static DevOnce once;
-    once.run([&] { (void)hipFuncSetAttribute((const void*)gpt2_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+    once.run([&] { (void)hipFuncSetAttribute((const void*)gpt2_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GPT2_ATTENTION_LDS_MAX); });
     hipLaunchKernelGGL(gpt2_attention_kernel, dim3(P * heads), dim3(256), lds, st, qkv, kc, vc, nd, past, Tmax, heads, out, past_dev);
 }
 
@@ -1136,7 +1139,8 @@ void launch_gpt2_attention(const float* qkv, float* kc, float* vc, int P, int nd
 // summed here (part / S / bias as in splitk_reduce_kernel; part == nullptr: qkv holds finished values) — the general kernel above spent
 // 10 us on five barriers and scalar cache loads, plus 4.6 us for the reduce launch in front of it.  Lane = feature d for q / k / v and
 // the output, lane = key position j for the scores (each lane reads one 256-byte key row); q and the probabilities cross lanes through
-// LDS; the value rows are read coalesced.  Sum orders as in gpt2_attention_kernel.
+// LDS; the value rows are read coalesced.  Sum orders as in gpt2_attention_kernel in the source; the outputs are bitwise equal to that
+// kernel's only without a history (past = 0) and differ by ~3e-8 of max|v| with one (tests/test_gpu_gpt2_ops.py logs it per case).
 __global__ __launch_bounds__(256) void gpt2_attention_step_kernel(const float* qkv, const float* part, int S, const float* bias, float* kc, float* vc,
                                                                   int P, int Tmax, int heads, float* out, const int* past_dev) {
     __shared__ __attribute__((aligned(16))) float qs[4][64], ks[4][64], ps[4][64], hs[4][64];

@@ -150,6 +150,8 @@ bool launch_gpt2_head(const float* A, const float* W, int M, int N, int K, int l
                       float* logits, float* pairs, int* out, const int* step_dev, hipStream_t st);
 void launch_gpt2_reduce(const float* part, int S, const float* bias, float* out, int M, int N, int ldo, int mode, hipStream_t st);
 void launch_gpt2_finalize(const float* part, int S, const float* bias, float* x, int M, int D, float* stats, hipStream_t st);
+#define GPT2_ATTENTION_LDS_MAX (160 * 1024)
+size_t gpt2_attention_lds_bytes(int nd, int ns);      // dynamic LDS of one launch_gpt2_attention (ns = history + new positions)
 // past_dev / step_dev: device-resident step state {past length, step index} for the captured single-token step
 void launch_gpt2_attention(const float* qkv, float* kc, float* vc, int P, int nd, int past, int Tmax, int heads,
                            float* out, hipStream_t st, const int* past_dev = nullptr);

@@ -407,6 +407,179 @@ extern "C" int glass_op_gpt2_sample(int32_t device, int32_t rows, int32_t V, con
     return GLASS_OK;
 }
 
+// ---- GPT-2 trunk kernels (gpt2.hip), launched exactly as gpt2_decode_group (engine.cpp) launches them ---------------------------------
+extern "C" int glass_op_gpt2_gemm(int32_t device, int32_t form, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t mode, int32_t width,
+                                  const float* a, const float* w, const float* bias, const float* lng, const float* lnb, const float* pst_in,
+                                  int32_t np_in, float* out, float* stats_out, float* pst_out, int32_t* splits) {
+    OPREQ(a && w && out && splits, "null argument");
+    OPREQ(form >= 0 && form <= 3 && mode >= 0 && mode <= 2, "form must lie in [0, 3], mode in [0, 2]");
+    OPREQ(M > 0 && N > 0 && K > 0 && K % 4 == 0 && lda >= K && lda % 4 == 0 && width > 0, "bad shape (K, lda multiples of 4, lda >= K)");
+    OPREQ((lng == nullptr) == (lnb == nullptr), "LayerNorm gain and bias come together");
+    OPREQ(!lng || form >= 2, "LayerNorm is fused on the operand of forms 2 and 3 only");
+    OPREQ(!lng || mode != 2, "the residual products have no fused LayerNorm");
+    const bool ln = lng != nullptr;
+    if (form == 2) {
+        OPREQ(gemm_f32_step_supported(M, K, lda, ln), "launch_gemm_f32_step does not take this shape (M <= 64, K % 64 == 0, K <= 1024 with LayerNorm)");
+        OPREQ(!ln || (lda == K && stats_out), "fused LayerNorm: gpt2_finalize_kernel makes the statistics of dense rows (lda == K), returned in stats_out");
+        OPREQ(mode != 2 || (N <= 1024 && stats_out), "a residual product is finished by gpt2_finalize_kernel: N <= 1024, statistics returned in stats_out");
+    }
+    if (form == 3) {
+        OPREQ(gemm_f32_rowblk_supported(M, N, K, lda, ln, pst_out != nullptr),
+              "launch_gemm_f32_rowblk does not take this shape (M <= 64, N % 32 == 0, K % 768 == 0, K <= 1024 with LayerNorm, N <= 768 with statistics)");
+        OPREQ(ln == (pst_in != nullptr), "fused LayerNorm consumes the row partials pst_in [M, np_in, 2]");
+        OPREQ(!ln || (np_in >= 1 && np_in <= 24 && K % np_in == 0), "np_in must divide K and lie in [1, 24]");
+    }
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t part_elems = (size_t)16 * M * 4 * width;                      // the engine's split-K scratch for a model of this width
+    float* da = dv.up32(a, (size_t)M * lda); float* dw = dv.up32(w, (size_t)N * K); float* db = dv.up32(bias, N);
+    float* dg = dv.up32(lng, K); float* dlb = dv.up32(lnb, K);
+    // the output is followed by guard rows up to the kernels' 64-row granularity: a store of a clamped row (m >= M) lands there and is reported
+    const size_t rows_alloc = (size_t)(M + 63) / 64 * 64, n_guard = (rows_alloc - M) * N;
+    float* dout = dv.alloc<float>(rows_alloc * N);
+    float* part = dv.alloc<float>(part_elems);
+    float* dstats = dv.alloc<float>((size_t)M * 2);
+    float* dpi = ln && form == 3 ? dv.up32(pst_in, (size_t)M * np_in * 2) : nullptr;
+    float* dpo = pst_out ? dv.alloc<float>((size_t)M * (N / 32 + 1) * 2) : nullptr;
+    OPREQ(da && dw && dout && part && dstats && (!bias || db) && (!ln || (dg && dlb)) && (!pst_out || dpo), "hipMalloc failed");
+    GLASS_HIP(hipMemset(dout, 0xff, rows_alloc * N * sizeof(float)));      // NaN: an element nobody stores shows
+    if (mode == 2) GLASS_HIP(hipMemcpy(dout, out, (size_t)M * N * sizeof(float), hipMemcpyHostToDevice));
+    int S = 1;
+    if (form == 0 || form == 1) {
+        launch_gemm_f32(da, dw, db, dout, M, N, K, lda, N, mode, 0, part, part_elems, form == 0);
+    } else if (form == 2) {
+        if (ln) launch_gpt2_finalize(nullptr, 0, nullptr, da, M, K, dstats, 0);
+        S = launch_gemm_f32_step(da, dw, db, dout, M, N, K, lda, N, mode, 0, part, part_elems, ln ? dstats : nullptr, dg, dlb);
+        OPREQ(S > 0, "launch_gemm_f32_step refused the shape");
+        if (mode == 2) launch_gpt2_finalize(S > 1 ? part : nullptr, S, db, dout, M, N, dstats, 0);
+        else if (S > 1) launch_gpt2_reduce(part, S, db, dout, M, N, N, mode, 0);
+    } else {
+        OPREQ(launch_gemm_f32_rowblk(da, dw, db, dout, M, N, K, lda, N, mode, 0, dpi, np_in, dg, dlb, dpo), "launch_gemm_f32_rowblk refused the shape");
+    }
+    int rc = finish();
+    if (rc) return rc;
+    *splits = S;
+    GLASS_HIP(hipMemcpy(out, dout, (size_t)M * N * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> guard(n_guard);
+    GLASS_HIP(hipMemcpy(guard.data(), dout + (size_t)M * N, n_guard * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n_guard; ++i)
+        if (guard[i] != 0xffffffffu) {
+            glass_set_error("gpt2_gemm: the product stored to row " + std::to_string(M + i / N) + " >= M");
+            return GLASS_ERR_STATE;
+        }
+    if (stats_out && form == 2 && (ln || mode == 2)) GLASS_HIP(hipMemcpy(stats_out, dstats, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (pst_out && form == 3) GLASS_HIP(hipMemcpy(pst_out, dpo, (size_t)M * (N / 32) * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_gpt2_attention(int32_t device, int32_t form, int32_t P, int32_t nd, int32_t past, int32_t Tmax, int32_t heads, int32_t S,
+                                       const float* qkv, const float* bias, float* kc, float* vc, float* out) {
+    OPREQ(qkv && kc && vc && out, "null argument");
+    OPREQ(form >= 0 && form <= 2, "form must lie in [0, 2]");
+    OPREQ(P > 0 && heads > 0 && nd > 0 && past >= 0 && past + nd <= Tmax, "bad shape (past + nd <= Tmax)");
+    const int D = heads * 64;
+    if (form == 2) {
+        OPREQ(nd == 1 && Tmax <= 64, "gpt2_attention_step_kernel: one new position, Tmax <= 64");
+        OPREQ(S >= 0 && S <= 16, "S must lie in [0, 16] (0: finished qkv values)");
+    } else {
+        OPREQ(S == 0 && !bias, "the general kernel takes finished qkv values");
+        const int ns = form == 1 ? Tmax : past + nd;      // launch_gpt2_attention's own size
+        OPREQ(gpt2_attention_lds_bytes(nd, ns) <= GPT2_ATTENTION_LDS_MAX,
+              "gpt2_attention_kernel: nd * 65 + 2 * ns * 65 + nd * (ns + 1) floats exceed 160 KB of LDS");
+    }
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t nq = (size_t)(form == 2 && S > 0 ? S : 1) * P * nd * 3 * D, nc = (size_t)P * Tmax * D, no = (size_t)P * nd * D;
+    float* dq = dv.up32(qkv, nq); float* db = dv.up32(bias, 3 * D);
+    float* dk = dv.up32(kc, nc); float* dvc = dv.up32(vc, nc);
+    float* dout = dv.alloc<float>(no);
+    int* dpast = dv.alloc<int>(3);
+    OPREQ(dq && dk && dvc && dout && dpast && (!bias || db), "hipMalloc failed");
+    const int state[3] = {past, 1, 0};
+    GLASS_HIP(hipMemcpy(dpast, state, sizeof state, hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemset(dout, 0xff, no * sizeof(float)));
+    if (form == 2) launch_gpt2_attention_step(dq, S > 0 ? dq : nullptr, S > 0 ? S : 1, db, dk, dvc, P, Tmax, heads, dout, 0, dpast);
+    else launch_gpt2_attention(dq, dk, dvc, P, nd, form == 1 ? 0 : past, Tmax, heads, dout, 0, form == 1 ? dpast : nullptr);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, dout, no * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(kc, dk, nc * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(vc, dvc, nc * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_gpt2_head(int32_t device, int32_t M, int32_t V, int32_t K, int32_t tail, const float* x, const float* wte, const float* lng,
+                                  const float* lnb, const float* wpe, int32_t npos, int32_t past, int32_t step, float* logits, float* pair_val,
+                                  int32_t* pair_idx, int32_t* token, float* stats, float* x_next, float* stats_next, int32_t* state) {
+    OPREQ(x && wte && lng && lnb && token && stats, "null argument");
+    OPREQ(M > 0 && K > 0 && K <= 1024 && gpt2_head_supported(M, V, K, K), "gpt2_head_kernel: M <= 64, K % 64 == 0, K <= 1024, V >= 4096");
+    if (tail) OPREQ(wpe && x_next && stats_next && state && past >= 0 && past + 1 < npos && step >= 0, "tail: wpe [npos, K], past + 1 < npos, step >= 0");
+    else OPREQ(logits && pair_val && pair_idx, "null argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const int NB = (V + 31) / 32;
+    float* dx = dv.up32(x, (size_t)M * K); float* dw = dv.up32(wte, (size_t)V * K); float* dg = dv.up32(lng, K); float* db = dv.up32(lnb, K);
+    float* dstats = dv.alloc<float>((size_t)M * 2);
+    float* pairs = dv.alloc<float>((size_t)2 * M * NB);
+    OPREQ(dx && dw && dg && db && dstats && pairs, "hipMalloc failed");
+    launch_gpt2_finalize(nullptr, 0, nullptr, dx, M, K, dstats, 0);            // the statistics the last layer's finalize leaves
+    if (!tail) {
+        float* dl = dv.alloc<float>((size_t)M * V);
+        int* dtok = dv.alloc<int>(M);
+        OPREQ(dl && dtok, "hipMalloc failed");
+        GLASS_HIP(hipMemset(dl, 0xff, (size_t)M * V * sizeof(float)));
+        GLASS_HIP(hipMemset(pairs, 0xff, (size_t)2 * M * NB * sizeof(float)));
+        OPREQ(launch_gpt2_head(dx, dw, M, V, K, K, dstats, dg, db, dl, pairs, dtok, nullptr, 0), "launch_gpt2_head refused the shape");
+        int rc = finish();
+        if (rc) return rc;
+        GLASS_HIP(hipMemcpy(stats, dstats, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost));
+        GLASS_HIP(hipMemcpy(logits, dl, (size_t)M * V * sizeof(float), hipMemcpyDeviceToHost));
+        GLASS_HIP(hipMemcpy(pair_val, pairs, (size_t)M * NB * sizeof(float), hipMemcpyDeviceToHost));
+        GLASS_HIP(hipMemcpy(pair_idx, pairs + (size_t)M * NB, (size_t)M * NB * sizeof(int), hipMemcpyDeviceToHost));
+        GLASS_HIP(hipMemcpy(token, dtok, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+        return GLASS_OK;
+    }
+    float* dpe = dv.up32(wpe, (size_t)npos * K);
+    int* dgen = dv.alloc<int>((size_t)(step + 1) * M);
+    int* dstate = dv.alloc<int>(3);
+    OPREQ(dpe && dgen && dstate, "hipMalloc failed");
+    const int st0[3] = {past, step, 0};
+    GLASS_HIP(hipMemcpy(dstate, st0, sizeof st0, hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemcpy(stats, dstats, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    // as the engine: the residual stream and its statistics are the head's operands AND the buffers the tail leaves the next step's in
+    OPREQ(launch_gpt2_head_tail(dx, dw, M, V, K, K, dstats, dg, db, pairs, dgen, dstate, dw, dpe, dx, dstats, 0), "launch_gpt2_head_tail refused the shape");
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(token, dgen + (size_t)step * M, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(x_next, dx, (size_t)M * K * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(stats_next, dstats, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(state, dstate, 3 * sizeof(int), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_gpt2_embed_step(int32_t device, int32_t M, int32_t V, int32_t K, const int32_t* token, const float* wte, const float* wpe,
+                                        int32_t npos, int32_t past, int32_t step, float* x, float* stats) {
+    OPREQ(token && wte && wpe && x && stats, "null argument");
+    OPREQ(M > 0 && V > 0 && K > 0 && K <= 1024 && past >= 0 && past < npos && step >= 1, "bad argument (K <= 1024 with statistics, past < npos, step >= 1)");
+    for (int i = 0; i < M; ++i) OPREQ(token[i] >= 0 && token[i] < V, "token id out of range");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dw = dv.up32(wte, (size_t)V * K); float* dpe = dv.up32(wpe, (size_t)npos * K);
+    float* dx = dv.alloc<float>((size_t)M * K); float* ds = dv.alloc<float>((size_t)M * 2);
+    int* dgen = dv.alloc<int>((size_t)step * M);
+    int* dstate = dv.alloc<int>(3);
+    OPREQ(dw && dpe && dx && ds && dgen && dstate, "hipMalloc failed");
+    const int st0[3] = {past, step, 0};
+    GLASS_HIP(hipMemcpy(dstate, st0, sizeof st0, hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemcpy(dgen + (size_t)(step - 1) * M, token, (size_t)M * sizeof(int), hipMemcpyHostToDevice));
+    launch_gpt2_embed_step(dgen, dstate, M, dw, dpe, K, dx, 0, ds);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(x, dx, (size_t)M * K * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(stats, ds, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
 __global__ void mfma_probe_kernel(const half_t* a, const half_t* b, float* d) {
     const int lane = threadIdx.x;
     const int r = lane & 31, kh = lane >> 5;

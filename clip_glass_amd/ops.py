@@ -269,6 +269,117 @@ def gpt2_sample(logits, temperature, top_k, seed, generation, first_row, step, p
     return out
 
 
+GPT2_GEMM_FORMS = {"prefill": 0, "decode": 1, "step": 2, "rowblk": 3}
+
+
+def gpt2_gemm(a, w, bias=None, mode=0, form="step", res=None, ln=None, pst_in=None, want_pst=False, width=None, device=0):
+    """A GPT-2 trunk product (gpt2.hip) launched as the engine launches it: out = a[M, :K] @ w[N, K]^T (+ bias), mode 0 plain / 1 GELU-tanh /
+    2 `res` + (in place on the device).  `a` may be a view with a row stride > K.  form: "prefill" / "decode" (launch_gemm_f32), "step"
+    (launch_gemm_f32_step + its finishing launch), "rowblk" (launch_gemm_f32_rowblk).  ln = (gain, bias): LayerNorm fused on the operand
+    from the device's own row statistics ("step": gpt2_finalize_kernel; "rowblk": pst_in, the partials an earlier rowblk call returned).
+    Returns a dict: out [M, N], S (the global K split), stats [M, 2] (step form: the fused LayerNorm's, or those a residual product
+    leaves), pst [M, N/32, 2] (rowblk with want_pst)."""
+    lib = load_library()
+    a = np.asarray(a, dtype=np.float32)
+    assert a.ndim == 2 and a.strides[1] == 4 and a.strides[0] % 4 == 0
+    M, K = a.shape
+    lda = a.strides[0] // 4 if M > 1 else K
+    abuf = np.zeros((M, lda), dtype=np.float32)
+    abuf[:, :K] = a
+    if lda > K:                                     # what lies between the rows is not the product's business
+        abuf[:, K:] = np.nan
+    w = _f32(w)
+    N = w.shape[0]
+    assert w.shape == (N, K)
+    f = GPT2_GEMM_FORMS[form]
+    out = np.empty((M, N), dtype=np.float32)
+    if mode == 2:
+        out[...] = res
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    bias_a, bias_p = _opt(bias)
+    g_a, g_p = _opt(None if ln is None else ln[0])
+    b_a, b_p = _opt(None if ln is None else ln[1])
+    pi_a, pi_p = _opt(pst_in)
+    np_in = 0 if pst_in is None else int(pi_a.shape[1])
+    stats = np.full((M, 2), np.nan, dtype=np.float32)
+    pst = np.full((M, max(N // 32, 1), 2), np.nan, dtype=np.float32) if want_pst else None
+    S = C.c_int32(0)
+    lib.glass_op_gpt2_gemm.argtypes = [C.c_int32] * 8 + [fp] * 6 + [C.c_int32, fp, fp, fp, ip]
+    _check(lib, lib.glass_op_gpt2_gemm(device, f, M, N, K, lda, int(mode), int(width or min(N, K)), _fp(abuf), _fp(w), bias_p, g_p, b_p, pi_p,
+                                       np_in, _fp(out), _fp(stats), None if pst is None else _fp(pst), C.byref(S)))
+    return dict(out=out, S=int(S.value), stats=stats, pst=pst)
+
+
+def gpt2_attention(qkv, kc, vc, past, heads, form="general", bias=None, device=0):
+    """One GPT-2 attention launch (gpt2.hip) over caches kc / vc [P, Tmax, D].  form "general": gpt2_attention_kernel with the host's
+    past; "general_dev": the same kernel with `past` in device memory (the graph-replay form); "step": gpt2_attention_step_kernel.
+    qkv: [P * nd, 3 D] finished values, or for "step" [S, P, 3 D] split-K slices (summed by the kernel, + bias [3 D]).
+    Returns (out [P * nd, D], kc, vc) — the caches after the call."""
+    lib = load_library()
+    kc, vc = np.array(kc, dtype=np.float32, order="C"), np.array(vc, dtype=np.float32, order="C")
+    P, Tmax, D = kc.shape
+    assert vc.shape == kc.shape and D == heads * 64
+    qkv = _f32(qkv)
+    f = {"general": 0, "general_dev": 1, "step": 2}[form]
+    if qkv.ndim == 3:
+        S, nd = qkv.shape[0], 1
+        assert f == 2 and qkv.shape[1:] == (P, 3 * D)
+    else:
+        S, nd = 0, qkv.shape[0] // P
+        assert qkv.shape == (P * nd, 3 * D)
+    out = np.empty((P * nd, D), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    bias_a, bias_p = _opt(bias)
+    lib.glass_op_gpt2_attention.argtypes = [C.c_int32] * 8 + [fp] * 5
+    _check(lib, lib.glass_op_gpt2_attention(device, f, P, nd, int(past), Tmax, heads, S, _fp(qkv), bias_p, _fp(kc), _fp(vc), _fp(out)))
+    return out, kc, vc
+
+
+def gpt2_head(x, wte, lng, lnb, tail=False, wpe=None, past=0, step=0, device=0):
+    """The vocabulary head of a single-token step (gpt2.hip): row statistics by gpt2_finalize_kernel, then launch_gpt2_head (tail=False:
+    returns logits [M, V], pair_val / pair_idx [M, ceil(V/32)], token [M], stats [M, 2]) or launch_gpt2_head_tail at the state
+    {past, step, 0} (tail=True: token, stats, x_next [M, K], stats_next [M, 2], state [3])."""
+    lib = load_library()
+    x, wte, lng, lnb = _f32(x), _f32(wte), _f32(lng), _f32(lnb)
+    M, K = x.shape
+    V = wte.shape[0]
+    NB = (V + 31) // 32
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    token = np.full(M, -1, dtype=np.int32)
+    stats = np.full((M, 2), np.nan, dtype=np.float32)
+    lib.glass_op_gpt2_head.argtypes = [C.c_int32] * 5 + [fp] * 5 + [C.c_int32] * 3 + [fp, fp, ip, ip, fp, fp, fp, ip]
+    if not tail:
+        logits = np.empty((M, V), dtype=np.float32)
+        pv = np.empty((M, NB), dtype=np.float32)
+        pi = np.empty((M, NB), dtype=np.int32)
+        _check(lib, lib.glass_op_gpt2_head(device, M, V, K, 0, _fp(x), _fp(wte), _fp(lng), _fp(lnb), None, 0, 0, 0, _fp(logits), _fp(pv),
+                                           pi.ctypes.data_as(ip), token.ctypes.data_as(ip), _fp(stats), None, None, None))
+        return dict(logits=logits, pair_val=pv, pair_idx=pi, token=token, stats=stats)
+    wpe = _f32(wpe)
+    x_next = np.full((M, K), np.nan, dtype=np.float32)
+    stats_next = np.full((M, 2), np.nan, dtype=np.float32)
+    state = np.full(3, -1, dtype=np.int32)
+    _check(lib, lib.glass_op_gpt2_head(device, M, V, K, 1, _fp(x), _fp(wte), _fp(lng), _fp(lnb), _fp(wpe), wpe.shape[0], int(past), int(step),
+                                       None, None, None, token.ctypes.data_as(ip), _fp(stats), _fp(x_next), _fp(stats_next),
+                                       state.ctypes.data_as(ip)))
+    return dict(token=token, stats=stats, x_next=x_next, stats_next=stats_next, state=state)
+
+
+def gpt2_embed_step(token, wte, wpe, past, step, device=0):
+    """launch_gpt2_embed_step with statistics at the state {past, step}: (x [M, K] = wte[token] + wpe[past], stats [M, 2])."""
+    lib = load_library()
+    wte, wpe = _f32(wte), _f32(wpe)
+    tok = np.ascontiguousarray(token, dtype=np.int32)
+    M, (V, K) = tok.shape[0], wte.shape
+    x = np.full((M, K), np.nan, dtype=np.float32)
+    stats = np.full((M, 2), np.nan, dtype=np.float32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    lib.glass_op_gpt2_embed_step.argtypes = [C.c_int32] * 4 + [ip, fp, fp] + [C.c_int32] * 3 + [fp, fp]
+    _check(lib, lib.glass_op_gpt2_embed_step(device, M, V, K, tok.ctypes.data_as(ip), _fp(wte), _fp(wpe), wpe.shape[0], int(past), int(step),
+                                             _fp(x), _fp(stats)))
+    return x, stats
+
+
 def mfma_probe(a, b, device=0):
     lib = load_library()
     a, b = _f32(a), _f32(b)

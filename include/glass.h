@@ -121,7 +121,10 @@ int glass_engine_encode_image(glass_engine* e, const float* images, int32_t n, f
 /* GPT-2 greedy decode (config GPT2 / img2txt: models.py:45-62, gpt2/sample.py:21-36 with sample=False).
  * Needs the "gpt2.transformer.*" tensors (reference GPT2LMHeadModel keys after gpt2/utils.py load_weight).
  * context: host int32 [P, n_ctx_tok] (latent tokens ++ init_text tokens); out: host int32
- * [P, n_ctx_tok + length] = context ++ `length` greedily decoded tokens.  All arithmetic is fp32. */
+ * [P, n_ctx_tok + length] = context ++ `length` greedily decoded tokens.  All arithmetic is fp32.
+ * Limits (GLASS_ERR_ARG otherwise): n_ctx_tok + length <= min(256, the position table); n_ctx_tok <= 126 — the prefill attention keeps
+ * one sequence's keys, values and score matrix in LDS, 4 * (n^2 + 196 n) bytes of the 160 KB a workgroup has.  The same limits hold
+ * for glass_engine_gpt2_sample. */
 int glass_engine_gpt2_decode(glass_engine* e, const int32_t* context, int32_t P, int32_t n_ctx_tok, int32_t length,
                              int32_t* out_tokens);
 

@@ -87,6 +87,39 @@ int glass_op_noise(int32_t device, int32_t n_mb, int32_t hw, uint32_t layer, uin
  * (temperature > 0, top_k in [0, 256], 0 = keep all; V <= 131072); out: int32 [rows]. */
 int glass_op_gpt2_sample(int32_t device, int32_t rows, int32_t V, const float* logits, float temperature, int32_t top_k,
                          uint64_t seed, int32_t generation, int32_t first_row, int32_t step, int32_t purpose, int32_t* out);
+/* The GPT-2 trunk's fp32 kernels (gpt2.hip), each launched as gpt2_decode_group (engine.cpp) launches it.  A shape a launcher does not
+ * take is an error (glass_last_error names the condition), never a different kernel.
+ *
+ * glass_op_gpt2_gemm: out[M,N] = A[M,K] (row stride lda >= K) @ W[N,K]^T (+ bias[N], nullable); mode 0 plain, 1 GELU-tanh, 2 out += (out
+ * holds the residual on entry).  form 0: launch_gemm_f32(prefill = true); 1: launch_gemm_f32(prefill = false); 2: launch_gemm_f32_step,
+ * finished by launch_gpt2_reduce (modes 0 / 1) or launch_gpt2_finalize (mode 2; N <= 1024); 3: launch_gemm_f32_rowblk.  The split-K scratch
+ * holds 16 * M * 4 * width floats, as the engine sizes it for a model of that width.  lng / lnb [K] (forms 2 / 3, modes 0 / 1): the operand
+ * is LayerNorm(A) with the row statistics of the device's own producers — form 2: gpt2_finalize_kernel over A (lda == K), returned in
+ * stats_out [M,2] = {mean, rstd}; form 3: the (mean, M2) partials pst_in [M, np_in, 2] an earlier form-3 call returned.  stats_out
+ * also receives the statistics a form-2 residual product leaves for the next LayerNorm; pst_out [M, N/32, 2] (form 3, nullable) the row
+ * partials of the epilogue.  *splits: the global K split the launcher chose (1 for forms 0, 1 and 3).  The device output is followed
+ * by guard rows up to the next multiple of 64: a store to a row >= M is an error (GLASS_ERR_STATE). */
+int glass_op_gpt2_gemm(int32_t device, int32_t form, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t mode, int32_t width,
+                       const float* a, const float* w, const float* bias, const float* lng, const float* lnb, const float* pst_in,
+                       int32_t np_in, float* out, float* stats_out, float* pst_out, int32_t* splits);
+/* One attention launch over caller caches kc / vc [P, Tmax, D = 64 * heads] (in and out: the call appends rows past .. past + nd - 1).
+ * form 0: launch_gpt2_attention with the host's `past`; 1: the same kernel reading `past` from device memory (LDS sized for Tmax);
+ * 2: launch_gpt2_attention_step (nd == 1, Tmax <= 64).  qkv: [P * nd, 3 D] finished values (S == 0), or for form 2 with S in [1, 16] the
+ * S split-K slices [S, P, 3 D] the kernel sums itself, plus bias [3 D] (nullable).  out: [P * nd, D]. */
+int glass_op_gpt2_attention(int32_t device, int32_t form, int32_t P, int32_t nd, int32_t past, int32_t Tmax, int32_t heads, int32_t S,
+                            const float* qkv, const float* bias, float* kc, float* vc, float* out);
+/* The vocabulary head of a single-token step on x [M, K] (M <= 64, K % 64 == 0, K <= 1024, V >= 4096): launch_gpt2_finalize(part = nullptr)
+ * for the row statistics (returned in stats [M,2]), then
+ * tail == 0: launch_gpt2_head with logits -> logits [M, V], the block (max, lowest index) pairs pair_val / pair_idx [M, ceil(V/32)], token [M];
+ * tail != 0: launch_gpt2_head_tail with the state {past, step, 0} -> token [M], the next step's embedding x_next [M, K] (wte[token] +
+ *            wpe[past + 1]; wpe [npos, K]), its statistics stats_next [M, 2] and the state words state [3] afterwards. */
+int glass_op_gpt2_head(int32_t device, int32_t M, int32_t V, int32_t K, int32_t tail, const float* x, const float* wte, const float* lng,
+                       const float* lnb, const float* wpe, int32_t npos, int32_t past, int32_t step, float* logits, float* pair_val,
+                       int32_t* pair_idx, int32_t* token, float* stats, float* x_next, float* stats_next, int32_t* state);
+/* launch_gpt2_embed_step with statistics at the state {past, step}: x [M, K] = wte[token] + wpe[past], stats [M, 2] — the other producer
+ * of a step's first operand (token [M] = the previous step's picks). */
+int glass_op_gpt2_embed_step(int32_t device, int32_t M, int32_t V, int32_t K, const int32_t* token, const float* wte, const float* wpe,
+                             int32_t npos, int32_t past, int32_t step, float* x, float* stats);
 /* raw MFMA layout probe: D = A[32x16] * B[16x32] through the fragment mapping of common.h */
 int glass_op_mfma_probe(int32_t device, const float* a /*[32,16]*/, const float* b /*[16,32]*/, float* d /*[32,32]*/);
 

@@ -132,6 +132,104 @@ def test_engine_gpt2_decode_matches_oracle(geo, P, n_ctx, length):
     _assert_token_parity("decode P=%d L=%d" % (P, length), got, ora, detail["margins"].numpy() if hasattr(detail["margins"], "numpy") else detail["margins"], n_ctx)
 
 
+# Geometries that reach the branches of gpt2_decode_group the cases above do not (all n_layer = 2, weight seed 2, context seed 1).
+# id -> (n_embd, vocab, P, n_ctx, length, n_positions); the step path each one takes, from the launch conditions in engine.cpp:
+#   D64     fused + tail-fused, not rowblk; every step product unsplit but the MLP's second (S = 4); step attention, P * heads = 33 (the
+#           last workgroup has one live wave); prefill rows 33 * 23
+#   D192    fused + tail-fused; three 64-deep chunks: S = 3 with one K part per workgroup (qkv, attention output, MLP first), S = 12 (MLP second)
+#   D1024   fused + tail-fused, not rowblk (1024 % 768 != 0); gpt2_finalize_kernel with all four 256-wide column groups live; S = 4 / 8 / 4 / 16
+#   D1280   unfused step under graph replay: launch_layernorm + launch_gemm_f32(prefill = false) + general attention with the device's
+#           past + two-stage launch_argmax (greedy) / launch_gpt2_sample (sampling)
+#   P1, P63 D = 256 fused + tail-fused; one row / a partly filled second 32-row block (M = 63) in every step kernel
+#   L1+63   Tmax = 64 exactly: step attention with all 64 lanes keys at the last step; the "prefill" has nd = 1 and takes the M <= 64
+#           streaming products (launch_gemm_f32 with prefill = false)
+#   L23+41  Tmax = 64 from an ordinary prefill
+#   L23+42  Tmax = 65: the general attention kernel with `past` from device memory, LDS sized for Tmax, behind launch_gpt2_reduce
+#   L126+130 the longest accepted context (prefill attention at 162 288 of 163 840 bytes of LDS) and Tmax = 256
+GEOMETRY_CASES = {
+    "D64": (64, 4096, 33, 23, 12, 64), "D192": (192, 4096, 33, 23, 12, 64), "D1024": (1024, 8192, 33, 23, 12, 64),
+    "D1280": (1280, 8192, 33, 23, 12, 64), "P1": (256, 5000, 1, 23, 12, 64), "P63": (256, 5000, 63, 23, 12, 64),
+    "L1+63": (128, 2048, 8, 1, 63, 256), "L23+41": (128, 2048, 8, 23, 41, 256), "L23+42": (128, 2048, 8, 23, 42, 256),
+    "L126+130": (128, 2048, 8, 126, 130, 256),
+}
+NEAR_TIE_ROWS_PER = 16          # at most one row in sixteen may use the near-tie escape
+
+
+def _geometry_state(case):
+    D, V, P, n_ctx, length, npos = GEOMETRY_CASES[case]
+    sd = synth.make_state(synth.gpt2_spec(n_embd=D, n_layer=2, vocab=V, n_positions=npos), 2)
+    return sd, _ctx(1, P, n_ctx, V), length
+
+
+def _gpt2_engine(sd, P):
+    import glass_models as M
+    from clip_glass_amd.engine import Engine
+    clip = M.CONFIGS["mini"]["clip"]
+    sd = dict(sd)
+    sd.update(synth.make_state(synth.clip_visual_spec(clip[0], clip[1], clip[3], clip[4], clip[5]), 0))
+    e = Engine([], latent_size=4, mapping_layers=0, batch_size=1, use_discriminator=False, n_obj=1, max_pop=P, clip=clip, noise_mode=0)
+    e.load_state(sd)
+    e.finalize()
+    return e
+
+
+def _oracle_tokens_within_cap(case, sd, ctx, length):
+    """The oracle's tokens and margins; asserts ON THE ORACLE that the near-tie rule cannot swallow the case: the rows with any step's
+    top-2 margin below 1e-4 (the only rows the rule may ever except) number at most one in sixteen."""
+    detail = {}
+    ora = gpt2_ref.sample_sequence(_t(sd), torch.tensor(ctx), length, detail=detail).numpy()
+    mg = detail["margins"].numpy() if hasattr(detail["margins"], "numpy") else detail["margins"]
+    near = int((mg.min(axis=1) < 1e-4).sum())
+    cap = ctx.shape[0] // NEAR_TIE_ROWS_PER
+    diag("[gpt2] %s: oracle rows with a top-2 margin below 1e-4: %d/%d (cap %d)" % (case, near, ctx.shape[0], cap))
+    assert near <= cap, "%s: %d/%d oracle rows are near-ties: choose other inputs" % (case, near, ctx.shape[0])
+    return ora, mg, cap
+
+
+@pytest.mark.parametrize("case", sorted(GEOMETRY_CASES))
+def test_geometry_case_inputs_keep_the_oracle_clear_of_near_ties(case):
+    """CPU: the inputs of the engine geometry cases leave at most one oracle row in sixteen with a near-tie at any step."""
+    sd, ctx, length = _geometry_state(case)
+    _oracle_tokens_within_cap(case, sd, ctx, length)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,entry", [(c, "greedy") for c in sorted(GEOMETRY_CASES)] +
+                         [(c, "sample") for c in ("D1280", "L23+42", "L126+130")])
+def test_engine_gpt2_decode_untested_geometries(case, entry):
+    """Engine vs oracle token parity on the widths, row counts and lengths listed at GEOMETRY_CASES.  entry "sample": the stochastic
+    entry point with top_k = 1, which keeps the maximum alone and so equals the greedy decode."""
+    sd, ctx, length = _geometry_state(case)
+    n_ctx = ctx.shape[1]
+    e = _gpt2_engine(sd, ctx.shape[0])
+    got = e.gpt2_decode(ctx, length) if entry == "greedy" else e.gpt2_sample(ctx, length, temperature=0.7, top_k=1, seed=5)
+    e.close()
+    ora, mg, cap = _oracle_tokens_within_cap(case, sd, ctx, length)
+    assert got.shape == ora.shape and np.array_equal(got[:, :n_ctx], ctx)
+    excepted = _assert_token_parity("%s %s" % (case, entry), got, ora, mg, n_ctx)
+    assert len(excepted) <= cap, "%s: %d rows took the near-tie escape, cap %d" % (case, len(excepted), cap)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P,n_ctx,length", [(8, 127, 2), (5, 200, 56)])
+def test_engine_gpt2_decode_refuses_long_contexts_by_name(P, n_ctx, length):
+    """The prefill attention keeps a sequence's keys, values and score matrix in LDS (4 * (n^2 + 196 n) bytes): 126 tokens are the most
+    that fit 160 KB (the L126+130 case runs them).  A longer context is refused up front with that limit in the message (include/glass.h),
+    on both entry points, and the engine decodes normally afterwards."""
+    geo = dict(n_embd=128, n_layer=2, vocab=2048)
+    sd = synth.make_state(synth.gpt2_spec(**geo, n_positions=256), 2)
+    e = _gpt2_engine(sd, P)
+    ctx = _ctx(1, P, n_ctx, geo["vocab"])
+    with pytest.raises(RuntimeError, match="context longer than 126 tokens"):
+        e.gpt2_decode(ctx, length)
+    with pytest.raises(RuntimeError, match="context longer than 126 tokens"):
+        e.gpt2_sample(ctx, length, top_k=1)
+    got = e.gpt2_decode(ctx[:, :23], 4)
+    e.close()
+    ora = gpt2_ref.sample_sequence(_t(sd), torch.tensor(ctx[:, :23]), 4).numpy()
+    assert np.array_equal(got, ora)
+
+
 @pytest.mark.gpu
 def test_engine_gpt2_decode_rows_do_not_depend_on_the_launch():
     """A sequence's tokens are a function of its own context only: P = 72 in one call (decoded as row groups of 64 + 8) equals the
