@@ -119,6 +119,28 @@ extern "C" int glass_clip_geometry_supported(int32_t width, int32_t layers, int3
 }
 static int clip_patch_k(const glass_config& c) { return (3 * c.clip_patch * c.clip_patch + 63) / 64 * 64; }   // patch rows padded to gemm_tiled's K step
 
+// The one rule for the opt-in CLIP preprocessing (host only).  gen_res: side of the generated image, 0 for an engine without a generator
+// (only the ranges of the two fields are checked then).
+extern "C" int glass_clip_preprocess_supported(int32_t gen_res, int32_t clip_res, int32_t clip_resize, int32_t clip_normalize) {
+    if (clip_resize < 0 || clip_resize > 2) {
+        glass_set_error("clip_resize must be 0 (point-sampled bilinear: the reference), 1 (antialiased bilinear) or 2 (antialiased bicubic), got " +
+                        std::to_string(clip_resize));
+        return GLASS_ERR_ARG;
+    }
+    if (clip_normalize < 0 || clip_normalize > 1) {
+        glass_set_error("clip_normalize must be 0 (none: the reference) or 1 (CLIP mean / std), got " + std::to_string(clip_normalize));
+        return GLASS_ERR_ARG;
+    }
+    if (clip_resize == 0 || gen_res == 0) return GLASS_OK;
+    ResizeTaps t;
+    std::string why;
+    if (!build_resize_taps(gen_res, clip_res, clip_resize, t, why)) {
+        glass_set_error(why);
+        return GLASS_ERR_ARG;
+    }
+    return GLASS_OK;
+}
+
 extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) {
     REQUIRE(cfg && out, GLASS_ERR_ARG, "null argument");
     REQUIRE(cfg->n_blocks >= 0 && cfg->n_blocks <= GLASS_MAX_BLOCKS, GLASS_ERR_ARG, "n_blocks out of range");
@@ -164,13 +186,15 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     } else {
         REQUIRE(cfg->generator == GLASS_GEN_STYLEGAN2, GLASS_ERR_ARG, "unknown generator kind");
     }
+    const int gen_res = cfg->n_blocks > 0 ? 4 << (cfg->n_blocks - 1) : bg_res;
+    if (int prc = glass_clip_preprocess_supported(gen_res, cfg->clip_res, cfg->clip_resize, cfg->clip_normalize)) return prc;
     int ndev = 0;
     GLASS_HIP(hipGetDeviceCount(&ndev));
     REQUIRE(cfg->device >= 0 && cfg->device < ndev, GLASS_ERR_ARG, "no such HIP device");
     GLASS_HIP(hipSetDevice(cfg->device));
     glass_engine* e = new glass_engine();
     e->cfg = *cfg;
-    e->R = cfg->n_blocks > 0 ? 4 << (cfg->n_blocks - 1) : bg_res;
+    e->R = gen_res;
     int chunk = cfg->chunk > 0 ? cfg->chunk : std::max(cfg->batch_size, (64 / cfg->batch_size) * cfg->batch_size);   // 288 GB of HBM: one chunk of 64 candidates (36 GB of activations at 1024 px) keeps every launch large
     chunk = std::min(chunk, cfg->max_pop);
     if (chunk % cfg->batch_size != 0) {
@@ -767,6 +791,20 @@ static int finalize_gpt2(glass_engine* e) {
     return GLASS_OK;
 }
 
+// clip_resize 1 / 2: the tap table of one axis (both axes share it), built on the host in float64 and kept on the device as fp32
+static int finalize_preprocess(glass_engine* e) {
+    const glass_config& c = e->cfg;
+    if (c.clip_resize == 0 || e->R == 0) return GLASS_OK;
+    ResizeTaps t;
+    std::string why;
+    REQUIRE(build_resize_taps(e->R, c.clip_res, c.clip_resize, t, why), GLASS_ERR_ARG, why);
+    float* d_table = nullptr;
+    int rc = upload(e, &d_table, t.table);
+    if (rc) return rc;
+    e->rz.table = d_table; e->rz.n4 = (int)(t.table.size() / 4); e->rz.ts = t.ts; e->rz.lds_bytes = t.lds_bytes;
+    return GLASS_OK;
+}
+
 extern "C" int glass_engine_finalize(glass_engine* e) {
     REQUIRE(e, GLASS_ERR_ARG, "null engine");
     REQUIRE(!e->finalized, GLASS_ERR_STATE, "engine already finalized");
@@ -779,6 +817,7 @@ extern "C" int glass_engine_finalize(glass_engine* e) {
     if (e->cfg.generator == GLASS_GEN_BIGGAN_DEEP && (rc = glass_biggan_finalize(e))) return rc;
     if ((rc = finalize_gpt2(e))) return rc;
     if ((rc = finalize_clip(e))) return rc;
+    if ((rc = finalize_preprocess(e))) return rc;
     if ((rc = alloc_buffers(e))) return rc;
     e->host.clear();  // host copies no longer needed
     e->finalized = true;
@@ -1359,6 +1398,21 @@ void run_clip(glass_engine* e, int P, int l0, int l1) {
     }
 }
 
+// Generated images y [B][3][R][R] -> CLIP's patch operand.  The default (clip_resize 0, clip_normalize 0) launches resize_patches_kernel, which
+// reads four input pixels per output; the antialiased modes read the whole image.
+static double clip_resize_bytes(const glass_engine* e, int B) {
+    const glass_config& c = e->cfg;
+    const double out = 2.0 * 3 * c.clip_res * c.clip_res;
+    return B * ((c.clip_resize ? 4.0 * 3 * e->R * e->R : 16.0 * c.clip_res * c.clip_res * 3) + out);
+}
+static void run_clip_resize(glass_engine* e, const float* y, int B, half_t* patches) {
+    const glass_config& c = e->cfg;
+    if (c.clip_resize == 0 && c.clip_normalize == 0)
+        launch_resize_patches(y, B, e->R, c.clip_res, c.clip_patch, clip_patch_k(c), patches, e->cur);
+    else
+        launch_preprocess_patches(y, B, e->R, c.clip_res, c.clip_patch, clip_patch_k(c), c.clip_resize, c.clip_normalize, e->rz, patches, e->cur);
+}
+
 static int run_pass(glass_engine* e, const float* latents, int P, int generation, int first_mb,
                     const glass_noise* noise, float* out_F, float* images) {
     REQUIRE(e && latents, GLASS_ERR_ARG, "null argument");
@@ -1393,8 +1447,8 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
                                          hipMemcpyDeviceToHost, e->cur));
             }
             if (out_F) {
-                Prof pr(e, "clip.resize", 0, B * (16.0 * c.clip_res * c.clip_res * 3 + 2.0 * 3 * c.clip_res * c.clip_res));
-                launch_resize_patches(y, B, e->R, c.clip_res, ps, clip_patch_k(c), e->d_patches + (size_t)c0 * G * G * clip_patch_k(c), e->cur);
+                Prof pr(e, "clip.resize", 0, clip_resize_bytes(e, B));
+                run_clip_resize(e, y, B, e->d_patches + (size_t)c0 * G * G * clip_patch_k(c));
             }
         }
         if (out_F) {
@@ -1485,9 +1539,8 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
             }
             e->cur = sd;
             {
-                Prof pr(e, "clip.resize", 0, B * (16.0 * c.clip_res * c.clip_res * 3 + 2.0 * 3 * c.clip_res * c.clip_res));
-                launch_resize_patches(y, B, e->R, c.clip_res, ps, clip_patch_k(c), e->d_patches + (size_t)c0 * G * G * clip_patch_k(c),
-                                      e->cur);
+                Prof pr(e, "clip.resize", 0, clip_resize_bytes(e, B));
+                run_clip_resize(e, y, B, e->d_patches + (size_t)c0 * G * G * clip_patch_k(c));
             }
             if (clip_ov && c0 + e->chunk >= P) {   // last chunk's patches are in place: CLIP starts now
                 // its first layers on the MAIN stream (alone on the chip), the rest on the second stream beside the discriminator

@@ -9,6 +9,7 @@
 
 #include "../../include/glass.h"
 #include "common.h"
+#include "kernels.h"
 
 void glass_set_error(const std::string& s);
 #define GLASS_HIP(call)                                                                        \
@@ -130,6 +131,7 @@ struct glass_engine {
     float *c_cls = nullptr, *c_pos = nullptr, *c_lnpre_g = nullptr, *c_lnpre_b = nullptr;
     float *c_lnpost_g = nullptr, *c_lnpost_b = nullptr, *c_proj = nullptr;
     std::vector<ClipBlock> cblk;
+    ResizeTapsDev rz;          // clip_resize 1 / 2: the antialiased resize's tap table (finalize_preprocess)
     // GPT-2 (optional, fp32; config C5)
     struct Gpt2Block { float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *w_qkv, *b_qkv, *w_o, *b_o, *w_fc, *b_fc, *w_pr, *b_pr; };
     std::vector<Gpt2Block> gblk;

@@ -2,6 +2,9 @@
 #pragma once
 #include "common.h"
 
+#include <string>
+#include <vector>
+
 // Each launcher returns the kernel symbol it launched (for the per-kernel profile).
 const char* launch_conv_direct(const ConvParams& p, hipStream_t st);
 const char* launch_gemm_direct(const GemmParams& p, hipStream_t st);
@@ -79,6 +82,30 @@ void launch_finalize_image(const float* y, float* img, long long n, hipStream_t 
 // bilinear (align_corners=False) resize of clip((y+1)/2,0,1) into the patch matrix [B*G*G][3*ps*ps] fp16
 void launch_resize_patches(const float* y, int B, int R, int clip_res, int ps, int ld, half_t* patches,
                            hipStream_t st);
+// CLIP's own preprocessing (glass_config::clip_resize / clip_normalize): antialiased bilinear (1) / bicubic (2, then clamp to [0, 1]) resize
+// through a host-built tap table, and / or Normalize(mean, std) of clip/clip.py:73 before the fp16 store.  Same output layout as
+// launch_resize_patches, which stays the kernel of the default (0, 0).
+#define GLASS_RESIZE_MAX_TAPS 32   // taps per output pixel and axis (1024 -> 224 bicubic: 19)
+#define PREPROCESS_TY 8            // output rows per workgroup
+#define PREPROCESS_RB 8            // input rows per load batch
+#define PREPROCESS_MAX_R 1024      // one thread per four input columns
+struct ResizeTaps {                // one axis, host side
+    std::vector<int> start, count; // [S]
+    std::vector<float> taps;       // [S][GLASS_RESIZE_MAX_TAPS], zero past count
+    std::vector<float> table;      // what the kernel keeps in LDS: taps [S][ts], start [S], count [S]
+    int max_count = 0, nr = 0, ts = 0;   // nr: input rows of the tallest band, in whole pairs of load batches
+    size_t lds_bytes = 0;
+};
+struct ResizeTapsDev {
+    const float* table = nullptr;  // ResizeTaps::table on the device
+    int n4 = 0, ts = 0;            // its length in 16-byte vectors; the taps' row stride
+    size_t lds_bytes = 0;
+};
+// false: (R, S, mode) is outside what preprocess_patches_kernel takes; `why` says which limit
+bool build_resize_taps(int R, int S, int mode, ResizeTaps& t, std::string& why);
+// resize_mode 0 (with normalize 1): resize_patches_norm_kernel, `t` unused; 1 / 2: preprocess_patches_kernel
+void launch_preprocess_patches(const float* y, int B, int R, int clip_res, int ps, int ld, int resize_mode, int normalize,
+                               const ResizeTapsDev& t, half_t* patches, hipStream_t st);
 void launch_fromrgb(const float* y, int B, int R, int Cout, const float* w, const float* bias,
                     half_t* out, hipStream_t st);
 // 4x4 FIR [1,3,3,1]^2/64, zero pad 2, stride 1: [B,H,W,C] -> [B,H+1,W+1,C]

@@ -4,6 +4,9 @@
 #include "common.h"
 #include "kernels.h"
 #include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -602,6 +605,232 @@ void launch_resize_patches(const float* y, int B, int R, int clip_res, int ps, i
     const long long total = n * B;
     hipLaunchKernelGGL(resize_patches_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, y, B, R,
                        clip_res, ps, ld, patches);
+}
+
+// ---- CLIP's own preprocessing (clip/clip.py:68-74), opt-in: glass_config::clip_resize / clip_normalize -----------------
+// Normalize((0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)), clip/clip.py:73
+__device__ __forceinline__ float clip_normalize_px(float v, int c) {
+    const float mean = c == 0 ? 0.48145466f : c == 1 ? 0.4578275f : 0.40821073f;
+    const float std = c == 0 ? 0.26862954f : c == 1 ? 0.26130258f : 0.27577711f;
+    return (v - mean) / std;
+}
+// clip_resize 0 with clip_normalize 1: resize_patches_kernel's arithmetic, then Normalize before the fp16 store
+__global__ void resize_patches_norm_kernel(const float* y, int B, int R, int S, int ps, int ld, half_t* patches) {
+    const int G = S / ps;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // over b, c, Y, X
+    const int X = (int)(idx % S);
+    const int Y = (int)((idx / S) % S);
+    const int c = (int)((idx / ((long long)S * S)) % 3);
+    const int b = (int)(idx / ((long long)S * S * 3));
+    if (b >= B) return;
+    const float scale = (float)R / (float)S;
+    float sy = scale * ((float)Y + 0.5f) - 0.5f, sx = scale * ((float)X + 0.5f) - 0.5f;
+    sy = fmaxf(sy, 0.f); sx = fmaxf(sx, 0.f);
+    const int y0 = min((int)sy, R - 1), x0 = min((int)sx, R - 1);
+    const int y1 = min(y0 + 1, R - 1), x1 = min(x0 + 1, R - 1);
+    const float ly = sy - (float)y0, lx = sx - (float)x0;
+    const float* yp = y + ((long long)b * 3 + c) * R * R;
+    auto nrm = [](float v) { return fminf(fmaxf((v + 1.f) * 0.5f, 0.f), 1.f); };
+    const float v00 = nrm(yp[(long long)y0 * R + x0]), v01 = nrm(yp[(long long)y0 * R + x1]);
+    const float v10 = nrm(yp[(long long)y1 * R + x0]), v11 = nrm(yp[(long long)y1 * R + x1]);
+    const float v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+    const int gy = Y / ps, iy = Y - gy * ps, gx = X / ps, ix = X - gx * ps;
+    const long long row = ((long long)b * G + gy) * G + gx;
+    patches[row * ld + ((long long)c * ps + iy) * ps + ix] = (half_t)clip_normalize_px(v, c);
+}
+
+// The tap table of one axis of an antialiased resize R -> S, as torch's upsample_bilinear2d_aa / upsample_bicubic2d_aa build it
+// (align_corners = False): scale = R / S, m = max(scale, 1), support = r m (r = 1 triangle, 2 cubic with a = -0.5); for output i:
+// c = scale (i + 0.5), taps j in [max(int(c - support + 0.5), 0), min(int(c + support + 0.5), R)) with weight f((j - c + 0.5) / m),
+// divided by their sum.  Computed in float64, stored as fp32; both axes use the same table (the images are square).
+bool build_resize_taps(int R, int S, int mode, ResizeTaps& t, std::string& why) {
+    char msg[256];
+    if (mode != 1 && mode != 2) {
+        why = "clip_resize must be 0 (point-sampled bilinear), 1 (antialiased bilinear) or 2 (antialiased bicubic)";
+        return false;
+    }
+    if (R <= 0 || S <= 0 || R % 4 != 0 || R > PREPROCESS_MAX_R) {
+        snprintf(msg, sizeof msg, "antialiased resize %d -> %d: the image size must be a positive multiple of 4, at most %d", R, S, PREPROCESS_MAX_R);
+        why = msg;
+        return false;
+    }
+    const double scale = (double)R / (double)S, m = scale > 1.0 ? scale : 1.0, support = (mode == 2 ? 2.0 : 1.0) * m;
+    auto f = [mode](double u) {
+        u = u < 0 ? -u : u;
+        if (mode == 1) return u < 1.0 ? 1.0 - u : 0.0;
+        const double a = -0.5;
+        if (u < 1.0) return ((a + 2.0) * u - (a + 3.0)) * u * u + 1.0;
+        if (u < 2.0) return (((u - 5.0) * u + 8.0) * u - 4.0) * a;
+        return 0.0;
+    };
+    t.start.assign(S, 0);
+    t.count.assign(S, 0);
+    t.taps.assign((size_t)S * GLASS_RESIZE_MAX_TAPS, 0.f);
+    t.max_count = 0;
+    for (int i = 0; i < S; ++i) {
+        const double c = scale * (i + 0.5);
+        const int lo = std::max((int)(c - support + 0.5), 0), hi = std::min((int)(c + support + 0.5), R), n = hi - lo;
+        if (n < 1 || n > GLASS_RESIZE_MAX_TAPS) {
+            snprintf(msg, sizeof msg, "antialiased resize %d -> %d (clip_resize %d) needs %d taps per output pixel: at most %d are supported", R, S,
+                     mode, n, GLASS_RESIZE_MAX_TAPS);
+            why = msg;
+            return false;
+        }
+        double w[GLASS_RESIZE_MAX_TAPS], sum = 0.0;
+        for (int j = 0; j < n; ++j) sum += (w[j] = f((lo + j - c + 0.5) / m));
+        for (int j = 0; j < n; ++j) t.taps[(size_t)i * GLASS_RESIZE_MAX_TAPS + j] = (float)(w[j] / sum);
+        t.start[i] = lo;
+        t.count[i] = n;
+        t.max_count = std::max(t.max_count, n);
+    }
+    // input rows a band of PREPROCESS_TY output rows reads, rounded up to whole load batches
+    t.nr = 0;
+    for (int y0 = 0; y0 < S; y0 += PREPROCESS_TY) {
+        const int yl = std::min(y0 + PREPROCESS_TY, S) - 1;
+        t.nr = std::max(t.nr, t.start[yl] + t.count[yl] - t.start[y0]);
+    }
+    t.nr = (t.nr + 2 * PREPROCESS_RB - 1) / (2 * PREPROCESS_RB) * (2 * PREPROCESS_RB);
+    t.ts = t.max_count | 1;      // odd LDS row stride of the taps: neighbouring outputs' taps fall into different banks
+    // the image the kernel copies into LDS as it is: taps [S][ts], start [S], count [S] (int bits), padded to whole 16-byte vectors
+    t.table.assign(((size_t)S * t.ts + 2 * (size_t)S + 3) / 4 * 4, 0.f);
+    for (int i = 0; i < S; ++i) {
+        for (int k = 0; k < t.count[i]; ++k) t.table[(size_t)i * t.ts + k] = t.taps[(size_t)i * GLASS_RESIZE_MAX_TAPS + k];
+        memcpy(&t.table[(size_t)S * t.ts + i], &t.start[i], sizeof(int));
+        memcpy(&t.table[(size_t)S * t.ts + S + i], &t.count[i], sizeof(int));
+    }
+    t.lds_bytes = sizeof(float) * (t.table.size() + (size_t)PREPROCESS_TY * R + (size_t)t.nr * PREPROCESS_TY);
+    if (t.lds_bytes > 64 * 1024) {
+        snprintf(msg, sizeof msg, "antialiased resize %d -> %d (clip_resize %d): the kernel's tables need %zu bytes of LDS, more than 64 KB", R, S, mode,
+                 t.lds_bytes);
+        why = msg;
+        return false;
+    }
+    return true;
+}
+
+// Antialiased bilinear / bicubic resize of clip((y+1)/2, 0, 1) [B][3][R][R] into the patch matrix, optionally CLIP-normalised.  Unlike
+// resize_patches_kernel it reads EVERY input pixel, so it is an HBM stream (unconditional batched 16-byte loads, the next
+// batch issued before the current one is consumed, the tap tables in LDS).  A workgroup owns PREPROCESS_TY output rows of one (image, channel)
+// plane.  Vertical pass first, in registers: thread t holds columns 4t .. 4t+3, streams the band's input rows and accumulates all
+// PREPROCESS_TY output rows against a dense weight matrix Wt[input row][output row] (zero outside a row's support; wave-uniform broadcast
+// reads from LDS).  The band's PREPROCESS_TY x R fp32 rows then go through LDS for the horizontal pass, one thread per output pixel.
+// The halo rows two neighbouring bands share are read twice; the block index is re-dealt so that neighbours run back to back on one XCD and
+// the second read comes from its L2.
+struct PreprocessParams {
+    const float* y;
+    const float* table;    // ResizeTaps::table, n4 16-byte vectors
+    int B, R, S, ps, ld, n4, ts, clamp01, normalize;
+    half_t* patches;
+};
+__global__ __launch_bounds__(256) void preprocess_patches_kernel(PreprocessParams p) {
+    extern __shared__ __align__(16) float pp_lds[];
+    constexpr int TY = PREPROCESS_TY, RB = PREPROCESS_RB;
+    static_assert(TY == 8, "the vertical pass reads a row's weights as two 16-byte vectors");
+    const int R = p.R, S = p.S, nt = blockDim.x, tid = threadIdx.x;
+    float* tl = pp_lds;                        // [S][ts] taps
+    const int* sl = (const int*)(tl + S * p.ts);     // start [S], count [S]
+    float* tmp = pp_lds + p.n4 * 4;            // [TY][R] vertically reduced rows
+    float* Wt = tmp + TY * R;                  // [input row of the band][TY]
+    // blocks i, i + 8, i + 16 ... share an XCD: give each XCD a contiguous run of (plane, band) indices
+    const int n = gridDim.x, q = n >> 3, rem = n & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int L = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + slot;
+    const int nb = (S + TY - 1) / TY;
+    const int band = L % nb, plane = L / nb, Y0 = band * TY;
+    const int r0 = __float_as_int(p.table[S * p.ts + Y0]);
+    const float* src = p.y + (long long)plane * R * R + min(tid * 4, R - 4);
+    auto load = [&](int it, f4* v) {
+#pragma unroll
+        for (int j = 0; j < RB; ++j) v[j] = *(const f4*)(src + (long long)min(r0 + it * RB + j, R - 1) * R);
+    };
+    f4 a[RB], b[RB];
+    load(0, a);
+    for (int e0 = 0; e0 < p.n4; e0 += 4 * nt) {      // the table, four independent 16-byte loads per thread and round
+        f4 tv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) tv[u] = ((const f4*)p.table)[min(e0 + u * nt + tid, p.n4 - 1)];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (e0 + u * nt + tid < p.n4) ((f4*)pp_lds)[e0 + u * nt + tid] = tv[u];
+    }
+    __syncthreads();
+    const int Yl = min(Y0 + TY, S) - 1;
+    const int nit = (sl[Yl] + sl[S + Yl] - r0 + RB - 1) / RB;      // load batches of this band
+    const int nit2 = (nit + 1) & ~1;                               // (the loop below takes two per round; 2 RB | nr, so nit2 RB <= nr)
+    for (int e = tid; e < nit2 * RB * TY; e += nt) {
+        const int j = e / TY, Y = Y0 + (e % TY);
+        float w = 0.f;
+        if (Y < S) {
+            const int k = r0 + j - sl[Y];
+            if (k >= 0 && k < sl[S + Y]) w = tl[Y * p.ts + k];
+        }
+        Wt[e] = w;
+    }
+    __syncthreads();
+    f4 acc[TY];
+#pragma unroll
+    for (int yy = 0; yy < TY; ++yy) acc[yy] = f4{0.f, 0.f, 0.f, 0.f};
+    auto consume = [&](int it, const f4* v8) {
+#pragma unroll
+        for (int j = 0; j < RB; ++j) {
+            f4 v = (v8[j] + 1.f) * 0.5f;       // biggan_norm on load (utils.py:14-17)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = fminf(fmaxf(v[u], 0.f), 1.f);
+            const f4 w0 = *(const f4*)(Wt + (it * RB + j) * TY), w1 = *(const f4*)(Wt + (it * RB + j) * TY + 4);
+#pragma unroll
+            for (int yy = 0; yy < 4; ++yy) {
+                acc[yy] += w0[yy] * v;
+                acc[yy + 4] += w1[yy] * v;
+            }
+        }
+    };
+    // two register sets in turn, the next batch issued before the current one is consumed; every load is unconditional (row index
+    // clamped: rows past the band carry zero weights, and the last round re-reads rows it already has, which hit the cache)
+    for (int it = 0; it < nit2; it += 2) {
+        load(it + 1, b);
+        __builtin_amdgcn_sched_barrier(0);     // (the scheduler otherwise sinks the batch below the arithmetic it is meant to run under)
+        consume(it, a);
+        __builtin_amdgcn_sched_barrier(0);
+        load(it + 2, a);
+        __builtin_amdgcn_sched_barrier(0);
+        consume(it + 1, b);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (tid * 4 < R) {
+#pragma unroll
+        for (int yy = 0; yy < TY; ++yy) *(f4*)(tmp + yy * R + tid * 4) = acc[yy];
+    }
+    __syncthreads();
+    const int G = S / p.ps, c = plane % 3, img = plane / 3;
+    for (int o = tid; o < TY * S; o += nt) {
+        const int yy = o / S, X = o - yy * S, Y = Y0 + yy;
+        if (Y >= S) break;
+        const int cn = sl[S + X];
+        const float* row = tmp + yy * R + sl[X];
+        const float* t = tl + X * p.ts;
+        float s = 0.f;
+        for (int k = 0; k < cn; ++k) s += row[k] * t[k];
+        if (p.clamp01) s = fminf(fmaxf(s, 0.f), 1.f);
+        if (p.normalize) s = clip_normalize_px(s, c);
+        const int gy = Y / p.ps, iy = Y - gy * p.ps, gx = X / p.ps, ix = X - gx * p.ps;
+        const long long prow = ((long long)img * G + gy) * G + gx;
+        p.patches[prow * p.ld + ((long long)c * p.ps + iy) * p.ps + ix] = (half_t)s;
+    }
+}
+void launch_preprocess_patches(const float* y, int B, int R, int clip_res, int ps, int ld, int resize_mode, int normalize,
+                               const ResizeTapsDev& t, half_t* patches, hipStream_t st) {
+    if (resize_mode == 0) {
+        const long long total = 3LL * clip_res * clip_res * B;
+        hipLaunchKernelGGL(resize_patches_norm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, y, B, R, clip_res, ps, ld, patches);
+        return;
+    }
+    PreprocessParams p;
+    p.y = y; p.table = t.table;
+    p.B = B; p.R = R; p.S = clip_res; p.ps = ps; p.ld = ld; p.n4 = t.n4; p.ts = t.ts;
+    p.clamp01 = resize_mode == 2; p.normalize = normalize;
+    p.patches = patches;
+    const int nb = (clip_res + PREPROCESS_TY - 1) / PREPROCESS_TY;
+    const int nt = std::min(256, (R / 4 + 63) / 64 * 64);     // one thread per four columns (R <= PREPROCESS_MAX_R = 1024)
+    hipLaunchKernelGGL(preprocess_patches_kernel, dim3((unsigned)(B * 3 * nb)), dim3(nt), t.lds_bytes, st, p);
 }
 
 // ---- D fromRGB: biggan_denorm (utils.py:19-21) + 1x1 conv 3->C + bias + lrelu*sqrt2

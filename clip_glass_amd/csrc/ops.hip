@@ -338,6 +338,35 @@ extern "C" int glass_op_resize(int32_t device, int32_t B, int32_t R, int32_t S, 
     return down16(patches, dp, n);
 }
 
+extern "C" int glass_op_preprocess(int32_t device, int32_t B, int32_t R, int32_t S, int32_t ps, int32_t resize_mode, int32_t normalize,
+                                   const float* y, float* patches) {
+    OPREQ(y && patches && B > 0 && R > 0 && ps > 0 && S > 0 && S % ps == 0, "bad argument");
+    if (int rc = glass_clip_preprocess_supported(R, S, resize_mode, normalize)) return rc;
+    ResizeTaps t;
+    std::string why;
+    if (resize_mode) OPREQ(build_resize_taps(R, S, resize_mode, t, why), why);
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dy = dv.up32(y, (size_t)B * 3 * R * R);
+    const size_t n = (size_t)B * 3 * S * S;
+    half_t* dp = dv.alloc<half_t>(n);
+    OPREQ(dy && dp, "device allocation failed");
+    if (resize_mode == 0 && normalize == 0) {
+        launch_resize_patches(dy, B, R, S, ps, 3 * ps * ps, dp, 0);
+    } else {
+        ResizeTapsDev td;
+        if (resize_mode) {
+            float* dt = dv.up32(t.table.data(), t.table.size());
+            OPREQ(dt, "device allocation failed");
+            td.table = dt; td.n4 = (int)(t.table.size() / 4); td.ts = t.ts; td.lds_bytes = t.lds_bytes;
+        }
+        launch_preprocess_patches(dy, B, R, S, ps, 3 * ps * ps, resize_mode, normalize, td, dp, 0);
+    }
+    int rc = finish();
+    if (rc) return rc;
+    return down16(patches, dp, n);
+}
+
 extern "C" int glass_op_layernorm(int32_t device, int32_t M, int32_t D, const float* x, const float* g, const float* b, float* out) {
     OPREQ(x && g && b && out, "null argument");
     GLASS_HIP(hipSetDevice(device));
@@ -615,5 +644,19 @@ extern "C" int glass_host_pack_conv(const float* w, int32_t Cout, int32_t Cin, i
         glass_pack_conv(w, Cout, Cin, KS, Cin, pk);
     }
     for (size_t i = 0; i < pk.size(); ++i) out[i] = (float)pk[i];
+    return GLASS_OK;
+}
+
+extern "C" int glass_host_resize_taps(int32_t R, int32_t S, int32_t mode, int32_t* start, int32_t* count, float* taps, int32_t max) {
+    OPREQ(start && count && taps && max > 0, "bad argument");
+    ResizeTaps t;
+    std::string why;
+    OPREQ(build_resize_taps(R, S, mode, t, why), why);
+    OPREQ(t.max_count <= max, "a row needs " + std::to_string(t.max_count) + " taps, more than the caller's " + std::to_string(max));
+    for (int i = 0; i < S; ++i) {
+        start[i] = t.start[i];
+        count[i] = t.count[i];
+        for (int k = 0; k < max; ++k) taps[(size_t)i * max + k] = k < GLASS_RESIZE_MAX_TAPS ? t.taps[(size_t)i * GLASS_RESIZE_MAX_TAPS + k] : 0.f;
+    }
     return GLASS_OK;
 }

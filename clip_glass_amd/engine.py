@@ -28,7 +28,8 @@ class GlassConfig(C.Structure):
                 ("generator", C.c_int32), ("bg_ch", C.c_int32), ("bg_z_dim", C.c_int32), ("bg_num_classes", C.c_int32),
                 ("bg_n_layers", C.c_int32), ("bg_layers", (C.c_int32 * 3) * MAX_BG_LAYERS),
                 ("bg_attention_pos", C.c_int32), ("bg_n_stats", C.c_int32), ("bg_eps", C.c_float),
-                ("bg_truncation", C.c_float)]
+                ("bg_truncation", C.c_float),
+                ("clip_resize", C.c_int32), ("clip_normalize", C.c_int32)]
 
 
 class GlassNoise(C.Structure):
@@ -60,6 +61,8 @@ def load_library(path=None):
     lib.glass_engine_create.argtypes = [C.POINTER(GlassConfig), C.POINTER(C.c_void_p)]
     if hasattr(lib, "glass_clip_geometry_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
         lib.glass_clip_geometry_supported.argtypes = [C.c_int32] * 6
+    if hasattr(lib, "glass_clip_preprocess_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
+        lib.glass_clip_preprocess_supported.argtypes = [C.c_int32] * 4
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -108,6 +111,14 @@ def clip_geometry_supported(geometry):
     return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
 
 
+def clip_preprocess_supported(gen_res, clip_res, clip_resize, clip_normalize):
+    """(ok, message) for the CLIP preprocessing fields (clip_resize, clip_normalize) from a gen_res px image to clip_res: the library's
+    own rule, the one glass_engine_create applies.  Host only."""
+    lib = load_library()
+    rc = lib.glass_clip_preprocess_supported(int(gen_res), int(clip_res), int(clip_resize), int(clip_normalize))
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
 def device_info(device=0):
     lib = load_library()
     name = C.create_string_buffer(256)
@@ -122,9 +133,10 @@ class Engine:
 
     def __init__(self, channels, latent_size=512, mapping_layers=8, batch_size=4, use_discriminator=True,
                  n_obj=2, max_pop=64, chunk=0, clip=(768, 12, 12, 32, 224, 512), noise_mode=1, noise_seed=0,
-                 mbstd_group=4, device=0, biggan=None):
+                 mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0):
         """`biggan` = dict(layers=[(up, in_mult, out_mult), ...], attention_pos, ch, z_dim, num_classes, n_stats, eps,
-        truncation) selects the BigGAN-deep generator (channels must then be empty, no discriminator)."""
+        truncation) selects the BigGAN-deep generator (channels must then be empty, no discriminator).
+        clip_resize / clip_normalize: how a generated image is prepared for CLIP (include/glass.h); (0, 0) is the reference's way."""
         self.lib = load_library()
         cfg = GlassConfig()
         cfg.device = device
@@ -149,6 +161,7 @@ class Engine:
         cfg.max_pop, cfg.chunk = max_pop, chunk
         (cfg.clip_width, cfg.clip_layers, cfg.clip_heads, cfg.clip_patch, cfg.clip_res, cfg.clip_embed) = clip
         cfg.noise_mode, cfg.noise_seed = noise_mode, noise_seed
+        cfg.clip_resize, cfg.clip_normalize = int(clip_resize), int(clip_normalize)
         self.cfg = cfg
         self.channels = list(channels)
         self.res = 4 << (len(channels) - 1) if channels else 0

@@ -30,6 +30,12 @@ CLIP_TEXT_MODELS = {
     "ViT-L/14@336": dict(width=768, layers=12),
 }
 DEFAULT_CLIP_MODEL = "ViT-B/32"
+# How a generated image is prepared for CLIP, `config.clip_preprocess` / `--clip-preprocess` -> (clip_resize, clip_normalize) of
+# include/glass.h.  "reference": generator.py:45, a point-sampled bilinear resize and no normalisation — what every parity number of this
+# project is quoted for.  "antialias": the same bilinear filter widened to the down-scale, so every input pixel counts.  "clip": the transform
+# CLIP was trained with (clip/clip.py:68-74), antialiased bicubic Resize + Normalize — a deliberate departure from the reference.
+CLIP_PREPROCESS = {"reference": (0, 0), "antialias": (1, 0), "clip": (2, 1)}
+DEFAULT_CLIP_PREPROCESS = "reference"
 
 
 def clip_model_geometry(name):
@@ -46,6 +52,14 @@ def clip_model_name(geometry):
         if g == geometry:
             return name
     return None
+
+
+def clip_preprocess_fields(name):
+    """(clip_resize, clip_normalize) of a named preprocessing (None: the default); ValueError lists the names otherwise."""
+    name = DEFAULT_CLIP_PREPROCESS if name is None else name
+    if name not in CLIP_PREPROCESS:
+        raise ValueError("unknown clip_preprocess %r: expected one of %s" % (name, ", ".join(CLIP_PREPROCESS)))
+    return CLIP_PREPROCESS[name]
 
 
 def check_clip_geometry(geometry):
@@ -161,7 +175,13 @@ class Generator:
         pop = int(getattr(config, "max_pop", max(config.pop_size, config.batch_size)))
         self.generation = 0
         self.sharder = None
+        self.clip_preprocess = getattr(config, "clip_preprocess", None) or DEFAULT_CLIP_PREPROCESS
+        clip_resize, clip_normalize = clip_preprocess_fields(self.clip_preprocess)
         if config.task == "img2txt":                                        # generator.py:25-27, 52-59
+            if (clip_resize, clip_normalize) != (0, 0):
+                # no image is generated here: the target image goes through clip_preprocess() below (clip/clip.py:68-74) either way
+                raise ValueError("clip_preprocess=%r applies to generated images (txt2img); the img2txt task has none: leave it at %r"
+                                 % (self.clip_preprocess, DEFAULT_CLIP_PREPROCESS))
             clip_state, geom = _load_clip_state(config, True)
             check_clip_geometry(geom)
             self.clip_geometry = tuple(int(v) for v in geom)
@@ -185,14 +205,16 @@ class Generator:
         pop = (pop + config.batch_size - 1) // config.batch_size * config.batch_size
         if hasattr(self.model, "geometry"):     # BigGAN-deep (models.py:64-86)
             self.engine = Engine([], batch_size=config.batch_size, max_pop=pop, chunk=getattr(config, "chunk", 0),
-                                 clip=geom, device=device, biggan=self.model.geometry)
+                                 clip=geom, device=device, biggan=self.model.geometry, clip_resize=clip_resize,
+                                 clip_normalize=clip_normalize)
         else:
             self.engine = Engine(self.model.channels[::-1], latent_size=config.dim_z,
                                  mapping_layers=getattr(config, "mapping_layers", 8), batch_size=config.batch_size,
                                  use_discriminator=bool(config.use_discriminator and config.problem_args["n_obj"] == 2),
                                  n_obj=config.problem_args["n_obj"], max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  clip=geom, noise_mode=getattr(config, "noise_mode", 1),
-                                 noise_seed=getattr(config, "noise_seed", 0), device=device)
+                                 noise_seed=getattr(config, "noise_seed", 0), device=device, clip_resize=clip_resize,
+                                 clip_normalize=clip_normalize)
         self.engine.load_state(self.model.state)
         self.engine.load_state(clip_state)
         self.engine.finalize()

@@ -226,6 +226,19 @@ def resize(y, S, ps, device=0):
     return out
 
 
+def preprocess(y, S, ps, resize_mode=0, normalize=0, device=0):
+    """The engine's CLIP preprocessing (glass_config.clip_resize / clip_normalize) on images [B,3,R,R] in (-1, 1); output as `resize`."""
+    lib = load_library()
+    y = _f32(y)
+    B, _, R, _ = y.shape
+    G = S // ps
+    out = np.empty((B * G * G, 3 * ps * ps), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_preprocess.argtypes = [C.c_int32] * 7 + [fp, fp]
+    _check(lib, lib.glass_op_preprocess(device, B, R, S, ps, int(resize_mode), int(normalize), _fp(y), _fp(out)))
+    return out
+
+
 def layernorm(x, g, b, device=0):
     lib = load_library()
     x, g, b = _f32(x), _f32(g), _f32(b)
@@ -400,3 +413,18 @@ def host_pack_conv(w, up=False):
     lib.glass_host_pack_conv.argtypes = [fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]
     _check(lib, lib.glass_host_pack_conv(_fp(w), Cout, Cin, KS, int(up), _fp(out)))
     return out
+
+
+RESIZE_MAX_TAPS = 32      # GLASS_RESIZE_MAX_TAPS (csrc/kernels.h): taps per output pixel and axis
+
+
+def host_resize_taps(R, S, mode, max_taps=RESIZE_MAX_TAPS):
+    """finalize()'s tap table of one axis of the antialiased resize R -> S (mode 1 bilinear, 2 bicubic), host only:
+    (start int32 [S], count int32 [S], taps float32 [S, max_taps])."""
+    lib = load_library()
+    start, count = np.empty(S, np.int32), np.empty(S, np.int32)
+    taps = np.empty((S, max_taps), np.float32)
+    ip = C.POINTER(C.c_int32)
+    lib.glass_host_resize_taps.argtypes = [C.c_int32] * 3 + [ip, ip, C.POINTER(C.c_float), C.c_int32]
+    _check(lib, lib.glass_host_resize_taps(R, S, int(mode), start.ctypes.data_as(ip), count.ctypes.data_as(ip), _fp(taps), max_taps))
+    return start, count, taps

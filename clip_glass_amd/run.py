@@ -14,7 +14,7 @@ import pickle
 import numpy as np
 
 from .config import get_config
-from .generator import CLIP_MODELS
+from .generator import CLIP_MODELS, CLIP_PREPROCESS
 from .operators import get_operators
 from .problem import GenerationProblem
 from . import search
@@ -35,6 +35,10 @@ def build_parser():
     p.add_argument("--clip-model", type=str, default=None, choices=sorted(CLIP_MODELS),
                    help="CLIP image tower: selects the geometry of synthetic weights (default ViT-B/32); with a checkpoint it must "
                         "agree with what the checkpoint holds")
+    p.add_argument("--clip-preprocess", type=str, default=None, choices=list(CLIP_PREPROCESS),
+                   help="how a generated image is prepared for CLIP: reference (default: the reference's point-sampled bilinear resize, no "
+                        "normalisation), antialias (antialiased bilinear resize), clip (CLIP's own transform: antialiased bicubic resize + "
+                        "mean / std normalisation — departs from the reference on purpose)")
     p.add_argument("--bpe-path", type=str, default=None)
     p.add_argument("--pop-size", type=int, default=None)
     p.add_argument("--stochastic", action="store_true", default=None,
@@ -51,7 +55,7 @@ def main(argv=None, extra_config=None):
     config = build_parser().parse_args(argv)
     over = {k: v for k, v in vars(config).items() if v is not None}
     vars(config).update(get_config(config.config))                             # run.py:25
-    for k in ("weights", "clip_weights", "clip_model", "bpe_path", "pop_size", "stochastic"):
+    for k in ("weights", "clip_weights", "clip_model", "clip_preprocess", "bpe_path", "pop_size", "stochastic"):
         if k in over:
             setattr(config, k, over[k])
     if extra_config:

@@ -71,6 +71,13 @@ typedef struct glass_config {
     int32_t bg_n_stats;           /* stored truncation steps of the batch-norm statistics (51) */
     float bg_eps;                 /* batch-norm eps (1e-4) */
     float bg_truncation;          /* config.truncation (1.0): selects / blends the statistics row */
+    /* --- opt-in: score through CLIP's own image preprocessing (clip/clip.py:68-74) instead of the reference's point-sampled resize
+     * (generator.py:45).  Appended last: zero, or a caller built against the shorter struct of an older library, selects the reference's
+     * behaviour.  See glass_clip_preprocess_supported. */
+    int32_t clip_resize;          /* 0: bilinear reading 2 x 2 input pixels per output (the reference, default); 1: antialiased bilinear;
+                                     2: antialiased bicubic (a = -0.5), then clamp to [0, 1] — both as torch F.interpolate(antialias=True) */
+    int32_t clip_normalize;       /* 0: none (the reference, default); 1: (v - mean_c) / std_c with the constants of clip/clip.py:73,
+                                     after the resize (and the clamp), before the fp16 store */
 } glass_config;
 
 /* Caller-provided noise (noise_mode 2): planes[m * n_layers + l] points at a host
@@ -91,6 +98,12 @@ const char* glass_version(void);
  * glass_last_error().  glass_engine_create applies the same rule. */
 int glass_clip_geometry_supported(int32_t width, int32_t layers, int32_t heads, int32_t patch, int32_t res,
                                   int32_t embed);
+
+/* Whether the engine runs the preprocessing (clip_resize, clip_normalize) from a gen_res x gen_res generated image to clip_res (host
+ * only: callable without a GPU; gen_res 0 checks the ranges of the two fields alone).  The antialiased modes take an image side that is a
+ * multiple of 4 up to 1024 and at most 32 taps per output pixel and axis (a bicubic down-scale up to 7.5 x, a bilinear one up to 15 x).
+ * Returns GLASS_OK, or GLASS_ERR_ARG with the reason in glass_last_error().  glass_engine_create applies the same rule. */
+int glass_clip_preprocess_supported(int32_t gen_res, int32_t clip_res, int32_t clip_resize, int32_t clip_normalize);
 
 int glass_engine_create(const glass_config* cfg, glass_engine** out);
 void glass_engine_destroy(glass_engine* e);

@@ -77,6 +77,10 @@ int glass_op_mbstd(int32_t device, int32_t B, int32_t hw, int32_t C, int32_t Cpa
                    const float* x, float* out);
 int glass_op_resize(int32_t device, int32_t B, int32_t R, int32_t S, int32_t ps, const float* y /*[B,3,R,R]*/,
                     float* patches /*[B*G*G, 3*ps*ps]*/);
+/* The engine's CLIP preprocessing (glass_config::clip_resize / clip_normalize) on caller images: (0, 0) launches what glass_op_resize
+ * launches, (0, 1) the normalising instance of that kernel, resize_mode 1 / 2 preprocess_patches_kernel.  Dense output as glass_op_resize. */
+int glass_op_preprocess(int32_t device, int32_t B, int32_t R, int32_t S, int32_t ps, int32_t resize_mode, int32_t normalize,
+                        const float* y /*[B,3,R,R]*/, float* patches /*[B*G*G, 3*ps*ps]*/);
 int glass_op_layernorm(int32_t device, int32_t M, int32_t D, const float* x, const float* g, const float* b, float* out);
 int glass_op_attention(int32_t device, int32_t n_img, int32_t L, int32_t heads, int32_t causal, const float* qkv,
                        float* out);
@@ -126,6 +130,10 @@ int glass_op_mfma_probe(int32_t device, const float* a /*[32,16]*/, const float*
 /* Host-only (no GPU): the weight repacking finalize() applies, for CPU tests.
  * out: [KS*KS][Neff][Cin] float32 (values already rounded to fp16), Neff = up ? 4*Cout : Cout. */
 int glass_host_pack_conv(const float* w, int32_t Cout, int32_t Cin, int32_t KS, int32_t up, float* out);
+/* Host-only (no GPU): the tap table finalize() builds for one axis of the antialiased resize R -> S (mode 1 bilinear, 2 bicubic): output
+ * i reads inputs start[i] .. start[i] + count[i] - 1 with weights taps[i * max + k] (fp32 roundings of the float64 weights; zero past count).
+ * GLASS_ERR_ARG when (R, S, mode) is refused (glass_clip_preprocess_supported) or a row needs more than `max` taps. */
+int glass_host_resize_taps(int32_t R, int32_t S, int32_t mode, int32_t* start, int32_t* count, float* taps, int32_t max);
 
 #ifdef __cplusplus
 }
