@@ -342,9 +342,7 @@ void bg_attention(glass_engine* e, int B, const half_t* x, half_t* y) {
         Prof pr(e, "bg.attn.split_pool", 0, 2.0 * B * ((double)hw * CT + (double)hw * c8 + (double)hq * (c8 + c2)));
         launch_bg_attn_split(g.a_T, B, res, res, c8, c2, g.a_theta, g.a_phi, g.a_gT, e->cur);
     }
-    GemmParams q;
-    memset(&q, 0, sizeof q);   // logits = theta . phi^T  (fp32 out)
-    q.a = g.a_theta; q.w = g.a_phi; q.M = hw; q.N = hq; q.K = c8; q.mode = 3; q.out32 = g.a_S; q.ldo = hq;
+    GemmParams q = gemm_params(g.a_theta, g.a_phi, hw, hq, c8, nullptr, 3, nullptr, g.a_S, 0);   // logits = theta . phi^T  (fp32 out)
     q.cand_batch = 1;
     q.batch = B; q.a_bs = (long long)hw * c8; q.w_bs = (long long)hq * c8; q.o_bs = (long long)hw * hq;
     {
@@ -357,8 +355,7 @@ void bg_attention(glass_engine* e, int B, const half_t* x, half_t* y) {
         Prof pr(e, "bg.attn.softmax", 0, 6.0 * B * hw * (double)hq);
         launch_bg_softmax(g.a_S, (long long)B * hw, hq, g.a_P, e->cur);
     }
-    memset(&q, 0, sizeof q);   // attn_g = P . g^T
-    q.a = g.a_P; q.w = g.a_gT; q.M = hw; q.N = c2; q.K = hq; q.mode = 0; q.out16 = g.a_O; q.ldo = c2;
+    q = gemm_params(g.a_P, g.a_gT, hw, c2, hq, nullptr, 0, g.a_O, nullptr, 0);   // attn_g = P . g^T
     q.cand_batch = 1;
     q.batch = B; q.a_bs = (long long)hw * hq; q.w_bs = (long long)c2 * hq; q.o_bs = (long long)hw * c2;
     {

@@ -1,0 +1,336 @@
+// clip.cpp — CLIP behind the engine: the image tower of the fitness pass, the text tower (glass_engine_encode_text) and the image
+// preprocessing in front of the patch embedding.  Both towers are the same transformer blocks (run_blocks) over different buffers.
+#include <math.h>
+#include <string.h>
+
+#include "engine.h"
+
+// The one rule for the CLIP image tower's geometry (host only: no device is touched).  Every kernel of the tower is written in
+// terms of the token count, the width and the patch size; what is fixed is the head dimension (the attention kernels are built for
+// 64) and the GEMMs' 64-wide N tiles.  The patch-embedding GEMM's K = 3 patch^2 is padded to the K step by the engine.
+extern "C" int glass_clip_geometry_supported(int32_t width, int32_t layers, int32_t heads, int32_t patch, int32_t res, int32_t embed) {
+    char msg[256];
+#define GEOM_REQ(cond, ...)                       \
+    if (!(cond)) {                                \
+        snprintf(msg, sizeof msg, __VA_ARGS__);   \
+        glass_set_error(msg);                     \
+        return GLASS_ERR_ARG;                     \
+    }
+    GEOM_REQ(width > 0 && layers > 0 && heads > 0 && patch > 0 && res > 0 && embed > 0,
+             "unsupported CLIP geometry: width, layers, heads, patch, resolution and embed must be positive");
+    GEOM_REQ(width % heads == 0 && width / heads == 64,
+             "unsupported CLIP geometry: head dim must be 64 (width %d / heads %d)", width, heads);
+    GEOM_REQ(res % patch == 0, "unsupported CLIP geometry: resolution %d is not a multiple of patch %d", res, patch);
+    GEOM_REQ(patch <= 64 && res / patch <= 63,
+             "unsupported CLIP geometry: patch %d / grid %d out of range (patch <= 64, at most 63 x 63 patches)", patch, res / patch);
+    GEOM_REQ(layers <= 64 && width <= 4096 && embed <= 4096, "unsupported CLIP geometry: layers %d / width %d / embed %d out of range",
+             layers, width, embed);
+#undef GEOM_REQ
+    return GLASS_OK;
+}
+int clip_patch_k(const glass_config& c) { return (3 * c.clip_patch * c.clip_patch + 63) / 64 * 64; }   // patch rows padded to gemm_tiled's K step
+
+// The one rule for the opt-in CLIP preprocessing (host only).  gen_res: side of the generated image, 0 for an engine without a generator
+// (only the ranges of the two fields are checked then).
+extern "C" int glass_clip_preprocess_supported(int32_t gen_res, int32_t clip_res, int32_t clip_resize, int32_t clip_normalize) {
+    if (clip_resize < 0 || clip_resize > 2) {
+        glass_set_error("clip_resize must be 0 (point-sampled bilinear: the reference), 1 (antialiased bilinear) or 2 (antialiased bicubic), got " +
+                        std::to_string(clip_resize));
+        return GLASS_ERR_ARG;
+    }
+    if (clip_normalize < 0 || clip_normalize > 1) {
+        glass_set_error("clip_normalize must be 0 (none: the reference) or 1 (CLIP mean / std), got " + std::to_string(clip_normalize));
+        return GLASS_ERR_ARG;
+    }
+    if (clip_resize == 0 || gen_res == 0) return GLASS_OK;
+    ResizeTaps t;
+    std::string why;
+    if (!build_resize_taps(gen_res, clip_res, clip_resize, t, why)) {
+        glass_set_error(why);
+        return GLASS_ERR_ARG;
+    }
+    return GLASS_OK;
+}
+
+static int load_clip_blocks(glass_engine* e, const char* prefix, int layers, int W, std::vector<ClipBlock>& out) {
+    char nm[256];
+    int rc;
+    for (int i = 0; i < layers; ++i) {
+        snprintf(nm, sizeof nm, "%s%d.", prefix, i);
+        const std::string p = nm;
+        ClipBlock b;
+        GET(l1g, p + "ln_1.weight");
+        GET(l1b, p + "ln_1.bias");
+        GET(l2g, p + "ln_2.weight");
+        GET(l2b, p + "ln_2.bias");
+        GET(wq, p + "attn.in_proj_weight");
+        GET(bq, p + "attn.in_proj_bias");
+        GET(wo, p + "attn.out_proj.weight");
+        GET(bo, p + "attn.out_proj.bias");
+        GET(wf, p + "mlp.c_fc.weight");
+        GET(bf, p + "mlp.c_fc.bias");
+        GET(wp, p + "mlp.c_proj.weight");
+        GET(bp, p + "mlp.c_proj.bias");
+        REQUIRE(numel(wq) == (size_t)3 * W * W && numel(wo) == (size_t)W * W && numel(wf) == (size_t)4 * W * W &&
+                    numel(wp) == (size_t)4 * W * W,
+                GLASS_ERR_ARG, "bad CLIP block shapes: " + p);
+        if ((rc = upload(e, &b.ln1_g, l1g->data))) return rc;
+        if ((rc = upload(e, &b.ln1_b, l1b->data))) return rc;
+        if ((rc = upload(e, &b.ln2_g, l2g->data))) return rc;
+        if ((rc = upload(e, &b.ln2_b, l2b->data))) return rc;
+        if ((rc = upload(e, &b.w_qkv, to_half(wq->data.data(), numel(wq))))) return rc;
+        if ((rc = upload(e, &b.w_out, to_half(wo->data.data(), numel(wo))))) return rc;
+        if ((rc = upload(e, &b.w_fc, to_half(wf->data.data(), numel(wf))))) return rc;
+        if ((rc = upload(e, &b.w_proj, to_half(wp->data.data(), numel(wp))))) return rc;
+        if ((rc = upload(e, &b.b_qkv, bq->data))) return rc;
+        if ((rc = upload(e, &b.b_out, bo->data))) return rc;
+        if ((rc = upload(e, &b.b_fc, bf->data))) return rc;
+        if ((rc = upload(e, &b.b_proj, bp->data))) return rc;
+        out.push_back(b);
+    }
+    return GLASS_OK;
+}
+
+int finalize_clip(glass_engine* e) {
+    const glass_config& c = e->cfg;
+    const int W = c.clip_width, ps = c.clip_patch, G = c.clip_res / ps, T = G * G + 1, E = c.clip_embed;
+    const std::string v = "clip.visual.";
+    GET(conv1, v + "conv1.weight");
+    GET(cls, v + "class_embedding");
+    GET(pos, v + "positional_embedding");
+    GET(lg, v + "ln_pre.weight");
+    GET(lb, v + "ln_pre.bias");
+    GET(pg, v + "ln_post.weight");
+    GET(pb, v + "ln_post.bias");
+    GET(proj, v + "proj");
+    REQUIRE(numel(conv1) == (size_t)W * 3 * ps * ps && numel(cls) == (size_t)W && numel(pos) == (size_t)T * W &&
+                numel(proj) == (size_t)W * E,
+            GLASS_ERR_ARG, "bad CLIP visual shapes");
+    const int K = 3 * ps * ps, Kp = clip_patch_k(c);
+    std::vector<_Float16> pw = to_half(conv1->data.data(), numel(conv1));
+    if (Kp != K) {      // [W][Kp] with zero columns (patch 14: 588 -> 640)
+        std::vector<_Float16> padded((size_t)W * Kp, (_Float16)0.f);
+        for (int n = 0; n < W; ++n) std::copy(pw.begin() + (size_t)n * K, pw.begin() + (size_t)(n + 1) * K, padded.begin() + (size_t)n * Kp);
+        pw.swap(padded);
+    }
+    int rc = upload(e, &e->c_patch_w, pw);
+    if (rc) return rc;
+    if ((rc = upload(e, &e->c_cls, cls->data))) return rc;
+    if ((rc = upload(e, &e->c_pos, pos->data))) return rc;
+    if ((rc = upload(e, &e->c_lnpre_g, lg->data))) return rc;
+    if ((rc = upload(e, &e->c_lnpre_b, lb->data))) return rc;
+    if ((rc = upload(e, &e->c_lnpost_g, pg->data))) return rc;
+    if ((rc = upload(e, &e->c_lnpost_b, pb->data))) return rc;
+    if ((rc = upload(e, &e->c_proj, proj->data))) return rc;  // already [K=W][N=E]
+    int rc2 = load_clip_blocks(e, "clip.visual.transformer.resblocks.", c.clip_layers, W, e->cblk);
+    if (rc2) return rc2;
+    // ---- optional text tower (clip/model.py:277-290) ----
+    if (find(e, "clip.token_embedding.weight") != nullptr) {
+        GET(tok, "clip.token_embedding.weight");
+        GET(tpos, "clip.positional_embedding");
+        GET(fg, "clip.ln_final.weight");
+        GET(fb, "clip.ln_final.bias");
+        GET(tp, "clip.text_projection");
+        REQUIRE(tok->dims.size() == 2 && tpos->dims.size() == 2 && tpos->dims[1] == tok->dims[1], GLASS_ERR_ARG,
+                "bad CLIP text embedding shapes");
+        e->t_vocab = (int)tok->dims[0];
+        e->t_width = (int)tok->dims[1];
+        e->t_ctx = (int)tpos->dims[0];
+        REQUIRE(e->t_width % 64 == 0 && numel(tp) == (size_t)e->t_width * E, GLASS_ERR_ARG, "bad CLIP text projection shape");
+        int nl = 0;
+        char nm2[256];
+        for (;; ++nl) {
+            snprintf(nm2, sizeof nm2, "clip.transformer.resblocks.%d.ln_1.weight", nl);
+            if (!find(e, nm2)) break;
+        }
+        if ((rc = upload(e, &e->t_tok, tok->data))) return rc;
+        if ((rc = upload(e, &e->t_pos, tpos->data))) return rc;
+        if ((rc = upload(e, &e->t_lnf_g, fg->data))) return rc;
+        if ((rc = upload(e, &e->t_lnf_b, fb->data))) return rc;
+        if ((rc = upload(e, &e->t_proj, tp->data))) return rc;
+        if ((rc = load_clip_blocks(e, "clip.transformer.resblocks.", nl, e->t_width, e->tblk))) return rc;
+    }
+    return GLASS_OK;
+}
+
+// clip_resize 1 / 2: the tap table of one axis (both axes share it), built on the host in float64 and kept on the device as fp32
+int finalize_preprocess(glass_engine* e) {
+    const glass_config& c = e->cfg;
+    if (c.clip_resize == 0 || e->R == 0) return GLASS_OK;
+    ResizeTaps t;
+    std::string why;
+    REQUIRE(build_resize_taps(e->R, c.clip_res, c.clip_resize, t, why), GLASS_ERR_ARG, why);
+    float* d_table = nullptr;
+    int rc = upload(e, &d_table, t.table);
+    if (rc) return rc;
+    e->rz.table = d_table; e->rz.n4 = (int)(t.table.size() / 4); e->rz.ts = t.ts; e->rz.lds_bytes = t.lds_bytes;
+    return GLASS_OK;
+}
+
+// Transformer blocks [l0, l1) of a tower: LN -> qkv -> attention -> out (+= x) -> LN -> fc (QuickGELU) -> proj (+= x), over `seqs`
+// sequences of T rows in x [seqs * T][W].  pfx: the launches' tag prefix ("clip": tags clip.layernorm, clip.qkv, ...; the stream must be
+// e->cur then, the profiling scopes record there); nullptr: no scope and no tag_kernel entry, the profile tables are not touched.
+static void run_blocks(glass_engine* e, const std::vector<ClipBlock>& blk, int l0, int l1, float* x, half_t* ln16, half_t* qkv, half_t* att,
+                       half_t* hid, int T, int seqs, int W, int heads, int causal, hipStream_t st, const char* pfx) {
+    const int M = seqs * T;
+    char buf[48];
+    auto tag = [&](const char* op) -> const char* {
+        if (!pfx) return nullptr;
+        snprintf(buf, sizeof buf, "%s.%s", pfx, op);
+        return buf;
+    };
+    auto gemm = [&](const GemmParams& g, const char* op) {
+        if (pfx) run_gemm(e, g, tag(op));
+        else if (!launch_gemm_tiled(g, st)) launch_gemm_direct(g, st);
+    };
+    auto layernorm = [&](const float* g, const float* b) {
+        Prof pr(e, tag("layernorm"), 0, 6.0 * M * W);
+        launch_layernorm(x, W, M, W, g, b, ln16, nullptr, st);
+    };
+    for (int li = l0; li < l1; ++li) {
+        const ClipBlock& b = blk[li];
+        layernorm(b.ln1_g, b.ln1_b);
+        gemm(gemm_params(ln16, b.w_qkv, M, 3 * W, W, b.b_qkv, 0, qkv, nullptr, T), "qkv");
+        {
+            Prof pr(e, tag("attention"), 4.0 * seqs * heads * (double)T * T * 64, 8.0 * M * W);
+            launch_attention(qkv, seqs, T, heads, 64, causal, att, st);
+        }
+        gemm(gemm_params(att, b.w_out, M, W, W, b.b_out, 2, nullptr, x, T), "attn_out");
+        layernorm(b.ln2_g, b.ln2_b);
+        gemm(gemm_params(ln16, b.w_fc, M, 4 * W, W, b.b_fc, 1, hid, nullptr, T), "mlp_fc");
+        gemm(gemm_params(hid, b.w_proj, M, W, 4 * W, b.b_proj, 2, nullptr, x, T), "mlp_proj");
+    }
+}
+
+// ---- the image tower (declared in engine.h) ----
+void run_clip_embed(glass_engine* e, int P) {
+    const glass_config& c = e->cfg;
+    const int W = c.clip_width, G = c.clip_res / c.clip_patch, T = G * G + 1;
+    run_gemm(e, gemm_params(e->d_patches, e->c_patch_w, P * G * G, W, clip_patch_k(c), nullptr, 3, nullptr, e->d_pe, G * G), "clip.patch_embed");
+    Prof pr(e, "clip.embed_lnpre", 0, 8.0 * P * T * W);
+    launch_embed_lnpre(e->d_pe, e->c_cls, e->c_pos, e->c_lnpre_g, e->c_lnpre_b, P, T, W, e->d_x, e->cur);
+}
+void run_clip_layers(glass_engine* e, int P, int l0, int l1) {
+    const glass_config& c = e->cfg;
+    const int G = c.clip_res / c.clip_patch;
+    run_blocks(e, e->cblk, l0, std::min(l1, (int)e->cblk.size()), e->d_x, e->d_ln16, e->d_qkv, e->d_attn, e->d_hid, G * G + 1, P, c.clip_width, c.clip_heads, 0, e->cur, "clip");
+}
+void run_clip_head(glass_engine* e, int P) {
+    const glass_config& c = e->cfg;
+    const int W = c.clip_width, G = c.clip_res / c.clip_patch, T = G * G + 1;
+    Prof pr(e, "clip.head", 2.0 * P * W * c.clip_embed, 4.0 * W * c.clip_embed);
+    launch_layernorm(e->d_x, (long long)T * W, P, W, e->c_lnpost_g, e->c_lnpost_b, nullptr, e->d_cls, e->cur);
+    launch_dense(e->d_cls, W, P, W, e->c_proj, c.clip_embed, nullptr, e->d_feat, c.clip_embed, 0, 0, nullptr, 0,
+                 e->cur);
+    launch_cosine(e->d_feat, e->d_target, P, c.clip_embed, e->d_sim, e->cur);
+}
+void run_clip(glass_engine* e, int P) {
+    run_clip_embed(e, P);
+    run_clip_layers(e, P, 0, (int)e->cblk.size());
+    run_clip_head(e, P);
+}
+
+// Generated images y [B][3][R][R] -> CLIP's patch operand.  The default (clip_resize 0, clip_normalize 0) launches resize_patches_kernel, which
+// reads four input pixels per output; the antialiased modes read the whole image.
+double clip_resize_bytes(const glass_engine* e, int B) {
+    const glass_config& c = e->cfg;
+    const double out = 2.0 * 3 * c.clip_res * c.clip_res;
+    return B * ((c.clip_resize ? 4.0 * 3 * e->R * e->R : 16.0 * c.clip_res * c.clip_res * 3) + out);
+}
+void run_clip_resize(glass_engine* e, const float* y, int B, half_t* patches) {
+    const glass_config& c = e->cfg;
+    if (c.clip_resize == 0 && c.clip_normalize == 0)
+        launch_resize_patches(y, B, e->R, c.clip_res, c.clip_patch, clip_patch_k(c), patches, e->cur);
+    else
+        launch_preprocess_patches(y, B, e->R, c.clip_res, c.clip_patch, clip_patch_k(c), c.clip_resize, c.clip_normalize, e->rz, patches, e->cur);
+}
+
+void text_work_free(glass_engine* e) {
+    for (void* p : e->twork.owned) hipFree(p);
+    e->twork = glass_engine::TextWork();
+}
+
+// CLIP text tower: token+pos embedding -> causal transformer -> ln_final -> EOT row @ text_projection
+extern "C" int glass_engine_encode_text(glass_engine* e, const int32_t* tokens, int32_t n_texts, int32_t ctx, float* out_feat) {
+    REQUIRE(e && tokens && out_feat && n_texts > 0, GLASS_ERR_ARG, "null argument");
+    REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
+    REQUIRE(e->t_tok != nullptr, GLASS_ERR_STATE, "CLIP text tower weights were not loaded (clip.token_embedding.weight ...)");
+    REQUIRE(ctx == e->t_ctx && ctx <= 128, GLASS_ERR_ARG, "context length does not match positional_embedding");
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    const int W = e->t_width, heads = W / 64, M = n_texts * ctx, E = e->cfg.clip_embed;
+    std::vector<int> eot(n_texts);
+    for (int n = 0; n < n_texts; ++n) {       // text.argmax(dim=-1): EOT has the highest id (clip/model.py:318)
+        int best = 0;
+        for (int t = 0; t < ctx; ++t) {
+            const int v = tokens[(size_t)n * ctx + t];
+            REQUIRE(v >= 0 && v < e->t_vocab, GLASS_ERR_ARG, "token id out of range");
+            if (v > tokens[(size_t)n * ctx + best]) best = t;
+        }
+        eot[n] = best;
+    }
+    auto& tw = e->twork;
+    hipError_t err = hipSuccess;
+    if (tw.n_texts != n_texts) {          // (re)build the workspace for this batch size
+        text_work_free(e);
+        if (err == hipSuccess) err = owned_alloc(tw.owned, &tw.d_tok, (size_t)M);
+        if (err == hipSuccess) err = owned_alloc(tw.owned, &tw.d_rows, (size_t)n_texts);
+        if (err == hipSuccess) err = owned_alloc(tw.owned, &tw.x, (size_t)M * W);
+        if (err == hipSuccess) err = owned_alloc(tw.owned, &tw.cls, (size_t)n_texts * W);
+        if (err == hipSuccess) err = owned_alloc(tw.owned, &tw.feat, (size_t)n_texts * E);
+        if (err == hipSuccess) err = owned_alloc(tw.owned, &tw.ln16, (size_t)M * W);
+        if (err == hipSuccess) err = owned_alloc(tw.owned, &tw.qkv, (size_t)M * 3 * W);
+        if (err == hipSuccess) err = owned_alloc(tw.owned, &tw.att, (size_t)M * W);
+        if (err == hipSuccess) err = owned_alloc(tw.owned, &tw.hid, (size_t)M * 4 * W);
+        if (err != hipSuccess) {
+            text_work_free(e);
+            glass_set_error(std::string("encode_text: hipMalloc failed: ") + hipGetErrorString(err));
+            return GLASS_ERR_NOMEM;
+        }
+        tw.n_texts = n_texts;
+    }
+    for (int n = 0; n < n_texts; ++n) eot[n] += n * ctx;          // row of each text's EOT token in x
+    hipStream_t st = e->stream;
+    hipMemcpyAsync(tw.d_tok, tokens, (size_t)M * sizeof(int), hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(tw.d_rows, eot.data(), (size_t)n_texts * sizeof(int), hipMemcpyHostToDevice, st);
+    launch_embed_text(tw.d_tok, e->t_tok, e->t_pos, M, ctx, W, tw.x, st);
+    run_blocks(e, e->tblk, 0, (int)e->tblk.size(), tw.x, tw.ln16, tw.qkv, tw.att, tw.hid, ctx, n_texts, W, heads, 1, st, nullptr);
+    // ln_final on the EOT row of each text only (row-wise op): one launch over the gathered rows (round 4: it was one launch per text)
+    launch_layernorm_rows(tw.x, tw.d_rows, n_texts, W, e->t_lnf_g, e->t_lnf_b, tw.cls, st);
+    launch_dense(tw.cls, W, n_texts, W, e->t_proj, E, nullptr, tw.feat, E, 0, 0, nullptr, 0, st);
+    err = hipMemcpyAsync(out_feat, tw.feat, (size_t)n_texts * E * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err == hipSuccess) err = hipGetLastError();
+    if (err != hipSuccess) {
+        text_work_free(e);
+        glass_set_error(std::string("encode_text failed: ") + hipGetErrorString(err));
+        return GLASS_ERR_HIP;
+    }
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_encode_image(glass_engine* e, const float* images, int32_t n, float* out_feat) {
+    REQUIRE(e && images && out_feat && n > 0, GLASS_ERR_ARG, "null argument");
+    REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
+    REQUIRE(n <= e->cfg.max_pop, GLASS_ERR_ARG, "more images than max_pop");
+    const glass_config& c = e->cfg;
+    GLASS_HIP(hipSetDevice(c.device));
+    const size_t elems = (size_t)n * 3 * c.clip_res * c.clip_res;
+    float* d_img = nullptr;
+    GLASS_HIP(hipMalloc(&d_img, elems * sizeof(float)));
+    hipError_t err = hipMemcpyAsync(d_img, images, elems * sizeof(float), hipMemcpyHostToDevice, e->stream);
+    e->cur = e->stream;
+    launch_image_patches(d_img, n, c.clip_res, c.clip_patch, clip_patch_k(c), e->d_patches, e->stream);
+    run_clip(e, n);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(out_feat, e->d_feat, (size_t)n * c.clip_embed * sizeof(float), hipMemcpyDeviceToHost, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    if (err == hipSuccess) err = hipGetLastError();
+    hipFree(d_img);
+    e->prof_events.clear();
+    e->event_next = 0;
+    if (err != hipSuccess) {
+        glass_set_error(std::string("encode_image failed: ") + hipGetErrorString(err));
+        return GLASS_ERR_HIP;
+    }
+    return GLASS_OK;
+}

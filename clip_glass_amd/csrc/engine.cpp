@@ -3,15 +3,13 @@
 // Host-side mirror of problem.py:14-29 / generator.py:29-60 / models.py:108-129:
 //   latents -> mapping -> styles/demod -> [per chunk: synthesis -> toRGB/skip -> resize -> D] -> CLIP -> F
 // One engine per (process, GPU); one private stream; weights repacked once in finalize().
+// Here: lifecycle, weight packing, StyleGAN2 G / D and the pass.  The other networks' host code: clip.cpp, gpt2_host.cpp, biggan.cpp.
 #include "engine.h"
 
 #include <math.h>
 #include <string.h>
 
-#include <algorithm>
 #include <stdlib.h>
-
-#include "kernels.h"
 
 static thread_local std::string g_err;
 void glass_set_error(const std::string& s) { g_err = s; }
@@ -94,53 +92,6 @@ std::vector<float> transposed(const float* W, int N, int K, float coef) {
 // ------------------------------------------------------------------------------------
 // create / destroy / load
 // ------------------------------------------------------------------------------------
-// The one rule for the CLIP image tower's geometry (host only: no device is touched).  Every kernel of the tower is written in
-// terms of the token count, the width and the patch size; what is fixed is the head dimension (the attention kernels are built for
-// 64) and the GEMMs' 64-wide N tiles.  The patch-embedding GEMM's K = 3 patch^2 is padded to the K step by the engine.
-extern "C" int glass_clip_geometry_supported(int32_t width, int32_t layers, int32_t heads, int32_t patch, int32_t res, int32_t embed) {
-    char msg[256];
-#define GEOM_REQ(cond, ...)                       \
-    if (!(cond)) {                                \
-        snprintf(msg, sizeof msg, __VA_ARGS__);   \
-        glass_set_error(msg);                     \
-        return GLASS_ERR_ARG;                     \
-    }
-    GEOM_REQ(width > 0 && layers > 0 && heads > 0 && patch > 0 && res > 0 && embed > 0,
-             "unsupported CLIP geometry: width, layers, heads, patch, resolution and embed must be positive");
-    GEOM_REQ(width % heads == 0 && width / heads == 64,
-             "unsupported CLIP geometry: head dim must be 64 (width %d / heads %d)", width, heads);
-    GEOM_REQ(res % patch == 0, "unsupported CLIP geometry: resolution %d is not a multiple of patch %d", res, patch);
-    GEOM_REQ(patch <= 64 && res / patch <= 63,
-             "unsupported CLIP geometry: patch %d / grid %d out of range (patch <= 64, at most 63 x 63 patches)", patch, res / patch);
-    GEOM_REQ(layers <= 64 && width <= 4096 && embed <= 4096, "unsupported CLIP geometry: layers %d / width %d / embed %d out of range",
-             layers, width, embed);
-#undef GEOM_REQ
-    return GLASS_OK;
-}
-static int clip_patch_k(const glass_config& c) { return (3 * c.clip_patch * c.clip_patch + 63) / 64 * 64; }   // patch rows padded to gemm_tiled's K step
-
-// The one rule for the opt-in CLIP preprocessing (host only).  gen_res: side of the generated image, 0 for an engine without a generator
-// (only the ranges of the two fields are checked then).
-extern "C" int glass_clip_preprocess_supported(int32_t gen_res, int32_t clip_res, int32_t clip_resize, int32_t clip_normalize) {
-    if (clip_resize < 0 || clip_resize > 2) {
-        glass_set_error("clip_resize must be 0 (point-sampled bilinear: the reference), 1 (antialiased bilinear) or 2 (antialiased bicubic), got " +
-                        std::to_string(clip_resize));
-        return GLASS_ERR_ARG;
-    }
-    if (clip_normalize < 0 || clip_normalize > 1) {
-        glass_set_error("clip_normalize must be 0 (none: the reference) or 1 (CLIP mean / std), got " + std::to_string(clip_normalize));
-        return GLASS_ERR_ARG;
-    }
-    if (clip_resize == 0 || gen_res == 0) return GLASS_OK;
-    ResizeTaps t;
-    std::string why;
-    if (!build_resize_taps(gen_res, clip_res, clip_resize, t, why)) {
-        glass_set_error(why);
-        return GLASS_ERR_ARG;
-    }
-    return GLASS_OK;
-}
-
 extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) {
     REQUIRE(cfg && out, GLASS_ERR_ARG, "null argument");
     REQUIRE(cfg->n_blocks >= 0 && cfg->n_blocks <= GLASS_MAX_BLOCKS, GLASS_ERR_ARG, "n_blocks out of range");
@@ -231,12 +182,6 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     return GLASS_OK;
 }
 
-static void gpt2_work_free(glass_engine* e);
-static void text_work_free(glass_engine* e) {
-    auto& w = e->twork;
-    hipFree(w.d_tok); hipFree(w.d_rows); hipFree(w.x); hipFree(w.cls); hipFree(w.feat); hipFree(w.ln16); hipFree(w.qkv); hipFree(w.att); hipFree(w.hid);
-    w = glass_engine::TextWork();
-}
 extern "C" void glass_engine_destroy(glass_engine* e) {
     if (!e) return;
     hipSetDevice(e->cfg.device);
@@ -500,107 +445,6 @@ static int finalize_discriminator(glass_engine* e) {
     return upload(e, &e->d_dense1_b, B1->data);
 }
 
-static int load_clip_blocks(glass_engine* e, const char* prefix, int layers, int W, std::vector<ClipBlock>& out) {
-    char nm[256];
-    int rc;
-    for (int i = 0; i < layers; ++i) {
-        snprintf(nm, sizeof nm, "%s%d.", prefix, i);
-        const std::string p = nm;
-        ClipBlock b;
-        GET(l1g, p + "ln_1.weight");
-        GET(l1b, p + "ln_1.bias");
-        GET(l2g, p + "ln_2.weight");
-        GET(l2b, p + "ln_2.bias");
-        GET(wq, p + "attn.in_proj_weight");
-        GET(bq, p + "attn.in_proj_bias");
-        GET(wo, p + "attn.out_proj.weight");
-        GET(bo, p + "attn.out_proj.bias");
-        GET(wf, p + "mlp.c_fc.weight");
-        GET(bf, p + "mlp.c_fc.bias");
-        GET(wp, p + "mlp.c_proj.weight");
-        GET(bp, p + "mlp.c_proj.bias");
-        REQUIRE(numel(wq) == (size_t)3 * W * W && numel(wo) == (size_t)W * W && numel(wf) == (size_t)4 * W * W &&
-                    numel(wp) == (size_t)4 * W * W,
-                GLASS_ERR_ARG, "bad CLIP block shapes: " + p);
-        if ((rc = upload(e, &b.ln1_g, l1g->data))) return rc;
-        if ((rc = upload(e, &b.ln1_b, l1b->data))) return rc;
-        if ((rc = upload(e, &b.ln2_g, l2g->data))) return rc;
-        if ((rc = upload(e, &b.ln2_b, l2b->data))) return rc;
-        if ((rc = upload(e, &b.w_qkv, to_half(wq->data.data(), numel(wq))))) return rc;
-        if ((rc = upload(e, &b.w_out, to_half(wo->data.data(), numel(wo))))) return rc;
-        if ((rc = upload(e, &b.w_fc, to_half(wf->data.data(), numel(wf))))) return rc;
-        if ((rc = upload(e, &b.w_proj, to_half(wp->data.data(), numel(wp))))) return rc;
-        if ((rc = upload(e, &b.b_qkv, bq->data))) return rc;
-        if ((rc = upload(e, &b.b_out, bo->data))) return rc;
-        if ((rc = upload(e, &b.b_fc, bf->data))) return rc;
-        if ((rc = upload(e, &b.b_proj, bp->data))) return rc;
-        out.push_back(b);
-    }
-    return GLASS_OK;
-}
-
-static int finalize_clip(glass_engine* e) {
-    const glass_config& c = e->cfg;
-    const int W = c.clip_width, ps = c.clip_patch, G = c.clip_res / ps, T = G * G + 1, E = c.clip_embed;
-    const std::string v = "clip.visual.";
-    GET(conv1, v + "conv1.weight");
-    GET(cls, v + "class_embedding");
-    GET(pos, v + "positional_embedding");
-    GET(lg, v + "ln_pre.weight");
-    GET(lb, v + "ln_pre.bias");
-    GET(pg, v + "ln_post.weight");
-    GET(pb, v + "ln_post.bias");
-    GET(proj, v + "proj");
-    REQUIRE(numel(conv1) == (size_t)W * 3 * ps * ps && numel(cls) == (size_t)W && numel(pos) == (size_t)T * W &&
-                numel(proj) == (size_t)W * E,
-            GLASS_ERR_ARG, "bad CLIP visual shapes");
-    const int K = 3 * ps * ps, Kp = clip_patch_k(c);
-    std::vector<_Float16> pw = to_half(conv1->data.data(), numel(conv1));
-    if (Kp != K) {      // [W][Kp] with zero columns (patch 14: 588 -> 640)
-        std::vector<_Float16> padded((size_t)W * Kp, (_Float16)0.f);
-        for (int n = 0; n < W; ++n) std::copy(pw.begin() + (size_t)n * K, pw.begin() + (size_t)(n + 1) * K, padded.begin() + (size_t)n * Kp);
-        pw.swap(padded);
-    }
-    int rc = upload(e, &e->c_patch_w, pw);
-    if (rc) return rc;
-    if ((rc = upload(e, &e->c_cls, cls->data))) return rc;
-    if ((rc = upload(e, &e->c_pos, pos->data))) return rc;
-    if ((rc = upload(e, &e->c_lnpre_g, lg->data))) return rc;
-    if ((rc = upload(e, &e->c_lnpre_b, lb->data))) return rc;
-    if ((rc = upload(e, &e->c_lnpost_g, pg->data))) return rc;
-    if ((rc = upload(e, &e->c_lnpost_b, pb->data))) return rc;
-    if ((rc = upload(e, &e->c_proj, proj->data))) return rc;  // already [K=W][N=E]
-    int rc2 = load_clip_blocks(e, "clip.visual.transformer.resblocks.", c.clip_layers, W, e->cblk);
-    if (rc2) return rc2;
-    // ---- optional text tower (clip/model.py:277-290) ----
-    if (find(e, "clip.token_embedding.weight") != nullptr) {
-        GET(tok, "clip.token_embedding.weight");
-        GET(tpos, "clip.positional_embedding");
-        GET(fg, "clip.ln_final.weight");
-        GET(fb, "clip.ln_final.bias");
-        GET(tp, "clip.text_projection");
-        REQUIRE(tok->dims.size() == 2 && tpos->dims.size() == 2 && tpos->dims[1] == tok->dims[1], GLASS_ERR_ARG,
-                "bad CLIP text embedding shapes");
-        e->t_vocab = (int)tok->dims[0];
-        e->t_width = (int)tok->dims[1];
-        e->t_ctx = (int)tpos->dims[0];
-        REQUIRE(e->t_width % 64 == 0 && numel(tp) == (size_t)e->t_width * E, GLASS_ERR_ARG, "bad CLIP text projection shape");
-        int nl = 0;
-        char nm2[256];
-        for (;; ++nl) {
-            snprintf(nm2, sizeof nm2, "clip.transformer.resblocks.%d.ln_1.weight", nl);
-            if (!find(e, nm2)) break;
-        }
-        if ((rc = upload(e, &e->t_tok, tok->data))) return rc;
-        if ((rc = upload(e, &e->t_pos, tpos->data))) return rc;
-        if ((rc = upload(e, &e->t_lnf_g, fg->data))) return rc;
-        if ((rc = upload(e, &e->t_lnf_b, fb->data))) return rc;
-        if ((rc = upload(e, &e->t_proj, tp->data))) return rc;
-        if ((rc = load_clip_blocks(e, "clip.transformer.resblocks.", nl, e->t_width, e->tblk))) return rc;
-    }
-    return GLASS_OK;
-}
-
 static int alloc_buffers(glass_engine* e) {
     const glass_config& c = e->cfg;
     const int P = c.max_pop, L = c.latent_size, CH = e->chunk;
@@ -735,76 +579,6 @@ static int alloc_buffers(glass_engine* e) {
     return GLASS_OK;
 }
 
-// ------------------------------------------------------------------------------------
-// GPT-2 (optional): Conv1D weights are [nx][nf] (gpt2/model.py:30-43) -> transposed to [nf][nx]
-// ------------------------------------------------------------------------------------
-static int finalize_gpt2(glass_engine* e) {
-    if (!find(e, "gpt2.transformer.wte.weight")) return GLASS_OK;
-    GET(wte, "gpt2.transformer.wte.weight");
-    GET(wpe, "gpt2.transformer.wpe.weight");
-    GET(lg, "gpt2.transformer.ln_f.weight");
-    GET(lb, "gpt2.transformer.ln_f.bias");
-    REQUIRE(wte->dims.size() == 2 && wpe->dims.size() == 2 && wpe->dims[1] == wte->dims[1], GLASS_ERR_ARG, "bad GPT-2 embedding shapes");
-    e->g_vocab = (int)wte->dims[0];
-    e->g_dim = (int)wte->dims[1];
-    e->g_npos = (int)wpe->dims[0];
-    const int D = e->g_dim;
-    REQUIRE(D % 64 == 0, GLASS_ERR_ARG, "GPT-2 width must be a multiple of the 64-wide head");
-    int rc;
-    if ((rc = upload(e, &e->g_wte, wte->data))) return rc;
-    if ((rc = upload(e, &e->g_wpe, wpe->data))) return rc;
-    if ((rc = upload(e, &e->g_lnf_g, lg->data))) return rc;
-    if ((rc = upload(e, &e->g_lnf_b, lb->data))) return rc;
-    char nm[256];
-    auto tr = [](const HostTensor* w, int nx, int nf) {   // [nx][nf] -> [nf][nx]
-        std::vector<float> v((size_t)nx * nf);
-        for (int i = 0; i < nx; ++i)
-            for (int j = 0; j < nf; ++j) v[(size_t)j * nx + i] = w->data[(size_t)i * nf + j];
-        return v;
-    };
-    for (int i = 0;; ++i) {
-        snprintf(nm, sizeof nm, "gpt2.transformer.h.%d.", i);
-        const std::string p = nm;
-        if (!find(e, p + "ln_1.weight")) break;
-        glass_engine::Gpt2Block b;
-        GET(l1g, p + "ln_1.weight"); GET(l1b, p + "ln_1.bias"); GET(l2g, p + "ln_2.weight"); GET(l2b, p + "ln_2.bias");
-        GET(wa, p + "attn.c_attn.weight"); GET(ba, p + "attn.c_attn.bias");
-        GET(wo, p + "attn.c_proj.weight"); GET(bo, p + "attn.c_proj.bias");
-        GET(wf, p + "mlp.c_fc.weight"); GET(bf, p + "mlp.c_fc.bias");
-        GET(wp, p + "mlp.c_proj.weight"); GET(bp, p + "mlp.c_proj.bias");
-        REQUIRE(numel(wa) == (size_t)3 * D * D && numel(wo) == (size_t)D * D && numel(wf) == (size_t)4 * D * D &&
-                    numel(wp) == (size_t)4 * D * D, GLASS_ERR_ARG, "bad GPT-2 block shapes: " + p);
-        if ((rc = upload(e, &b.ln1_g, l1g->data))) return rc;
-        if ((rc = upload(e, &b.ln1_b, l1b->data))) return rc;
-        if ((rc = upload(e, &b.ln2_g, l2g->data))) return rc;
-        if ((rc = upload(e, &b.ln2_b, l2b->data))) return rc;
-        if ((rc = upload(e, &b.w_qkv, tr(wa, D, 3 * D)))) return rc;
-        if ((rc = upload(e, &b.b_qkv, ba->data))) return rc;
-        if ((rc = upload(e, &b.w_o, tr(wo, D, D)))) return rc;
-        if ((rc = upload(e, &b.b_o, bo->data))) return rc;
-        if ((rc = upload(e, &b.w_fc, tr(wf, D, 4 * D)))) return rc;
-        if ((rc = upload(e, &b.b_fc, bf->data))) return rc;
-        if ((rc = upload(e, &b.w_pr, tr(wp, 4 * D, D)))) return rc;
-        if ((rc = upload(e, &b.b_pr, bp->data))) return rc;
-        e->gblk.push_back(b);
-    }
-    return GLASS_OK;
-}
-
-// clip_resize 1 / 2: the tap table of one axis (both axes share it), built on the host in float64 and kept on the device as fp32
-static int finalize_preprocess(glass_engine* e) {
-    const glass_config& c = e->cfg;
-    if (c.clip_resize == 0 || e->R == 0) return GLASS_OK;
-    ResizeTaps t;
-    std::string why;
-    REQUIRE(build_resize_taps(e->R, c.clip_res, c.clip_resize, t, why), GLASS_ERR_ARG, why);
-    float* d_table = nullptr;
-    int rc = upload(e, &d_table, t.table);
-    if (rc) return rc;
-    e->rz.table = d_table; e->rz.n4 = (int)(t.table.size() / 4); e->rz.ts = t.ts; e->rz.lds_bytes = t.lds_bytes;
-    return GLASS_OK;
-}
-
 extern "C" int glass_engine_finalize(glass_engine* e) {
     REQUIRE(e, GLASS_ERR_ARG, "null engine");
     REQUIRE(!e->finalized, GLASS_ERR_STATE, "engine already finalized");
@@ -873,8 +647,7 @@ void run_conv(glass_engine* e, const ConvParams& p, const char* tag, double flop
         k = launch_conv_tiled(p, e->cur);
         if (!k && e->launch_error.empty()) e->launch_error = std::string("no kernel writes the planar tanh output of layer ") + tag;
         if (!k) k = "(refused)";
-        if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-        if (e->profiling) e->tag_kernel[tag] = k;
+        pr.ran(tag, k);
         return;
     }
     if (!k) k = launch_conv_stream(p, e->cur);
@@ -889,15 +662,13 @@ void run_conv(glass_engine* e, const ConvParams& p, const char* tag, double flop
         if (e->launch_error.empty()) e->launch_error = std::string("no kernel accepts layer ") + tag;
         k = "(refused)";
     }
-    if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-    if (e->profiling) e->tag_kernel[tag] = k;
+    pr.ran(tag, k);
 }
 void run_gemm(glass_engine* e, const GemmParams& p, const char* tag) {
     Prof pr(e, tag, 2.0 * p.M * p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N));
     const char* k = launch_gemm_tiled(p, e->cur);
     if (!k) k = launch_gemm_direct(p, e->cur);
-    if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-    if (e->profiling) e->tag_kernel[tag] = k;
+    pr.ran(tag, k);
 }
 
 ConvParams conv_defaults() {
@@ -907,6 +678,15 @@ ConvParams conv_defaults() {
     p.batch_size = 1;
     p.stride = 1;
     return p;
+}
+
+GemmParams gemm_params(const half_t* a, const half_t* w, int M, int N, int K, const float* bias, int mode, half_t* out16, float* out32,
+                       int cand_rows) {
+    GemmParams g;
+    memset(&g, 0, sizeof g);
+    g.a = a; g.w = w; g.M = M; g.N = N; g.K = K; g.bias = bias; g.mode = mode;
+    g.out16 = out16; g.out32 = out32; g.ldo = N; g.cand_rows = cand_rows;
+    return g;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1072,65 +852,42 @@ static void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, con
                 q.trgb_w = r.w; q.trgb_b = r.bias;
                 q.trgb_sn = e->d_s + (size_t)c0 * e->S_total + r.style_off; q.trgb_sn_stride = e->S_total;
                 q.trgb_smax = e->d_smax + (size_t)c0 * e->n_style + r.style_idx; q.trgb_smax_stride = e->n_style;
-                q.trgb_yprev = yprev; q.trgb_yout = yb[yi];
                 const double tflops = flops + 2.0 * B * (double)r.res * r.res * 3 * r.cin;
-                const double ybytes = B * (double)r.res * r.res * (12.0 + (b ? 3.0 : 0.0));
                 if (b == c.n_blocks - 1) {
-                    q.y = nullptr;
-                    if (conv_stream_applies(q)) {
+                    ConvParams qs = q;
+                    qs.trgb_yprev = yprev; qs.trgb_yout = yb[yi];
+                    qs.y = nullptr;
+                    if (conv_stream_applies(qs)) {
+                        const double ybytes = B * (double)r.res * r.res * (12.0 + (b ? 3.0 : 0.0));
                         Prof pr(e, tag, tflops, 2.0 * B * (double)g.res_in * g.res_in * g.cin + ybytes);
-                        const char* k = launch_conv_stream(q, e->cur);
-                        if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-                        if (e->profiling) e->tag_kernel[tag] = k;
+                        pr.ran(tag, launch_conv_stream(qs, e->cur));
                         rgb_done = true;
                         x = nullptr;   // not produced
                     }
                 }
-                if (!rgb_done && r.cin <= 128) {
-                    q.y = out;
-                    q.trgb_tab = e->d_trgb_tab + (size_t)c0 * 32 * 128;
-                    q.dry_run = 1;
-                    const char* k = launch_conv_glds(q, e->cur);
-                    if (!k) k = launch_conv_tiled(q, e->cur);
-                    if (k) {
-                        q.dry_run = 0;
-                        Prof pr(e, tag, tflops, bytes + ybytes);
-                        launch_trgb_tables(q.trgb_w, q.trgb_sn, q.trgb_sn_stride, q.trgb_smax, q.trgb_smax_stride, B, r.cin,
-                                           e->d_trgb_tab + (size_t)c0 * 32 * 128, e->cur);
-                        k = launch_conv_glds(q, e->cur);
-                        if (!k) k = launch_conv_tiled(q, e->cur);
-                        if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-                        if (e->profiling) e->tag_kernel[tag] = k;
-                        rgb_done = true;
-                        x = out;
-                        xbs = (long long)g.res_out * g.res_out * g.cout;
-                    }
-                }
-            }
-            if (l == nl - 1 && !g.up && !rgb_done && e->d_trgb_part) {
-                // blocks wider than 128 channels (several 128-wide n tiles per pixel): every n tile's conv epilogue writes the toRGB partial sum of
-                // its channels, a 3-value-per-pixel pass adds them (+ bias + the upsampled previous image) — the separate toRGB pass read the
-                // whole feature map again (0.19 + 0.09 + 0.03 ms at r128 / r64 / r32)
-                const GRgb& r = e->grgb[b];
-                if (r.cin > 128 && r.cin % 128 == 0 && r.cin <= 512) {
-                    ConvParams q = p;
-                    q.trgb_w = r.w; q.trgb_b = r.bias;
-                    q.trgb_sn = e->d_s + (size_t)c0 * e->S_total + r.style_off; q.trgb_sn_stride = e->S_total;
-                    q.trgb_smax = e->d_smax + (size_t)c0 * e->n_style + r.style_idx; q.trgb_smax_stride = e->n_style;
-                    q.trgb_tab = e->d_trgb_tab + (size_t)c0 * 32 * 512;
-                    q.trgb_part = e->d_trgb_part;
-                    q.dry_run = 1;
-                    if (launch_conv_glds(q, e->cur)) {
-                        q.dry_run = 0;
-                        const double tflops = flops + 2.0 * B * (double)r.res * r.res * 3 * r.cin;
-                        const double ybytes = B * (double)r.res * r.res * (12.0 * (1 + 2 * (r.cin / 128)) + (b ? 3.0 : 0.0));
-                        Prof pr(e, tag, tflops, bytes + ybytes);
-                        launch_trgb_tables(q.trgb_w, q.trgb_sn, q.trgb_sn_stride, q.trgb_smax, q.trgb_smax_stride, B, r.cin,
-                                           e->d_trgb_tab + (size_t)c0 * 32 * 512, e->cur);
+                // Up to 128 channels (one n tile per pixel) the conv's epilogue writes the skip image itself.  Blocks wider than that (several
+                // 128-wide n tiles per pixel): every n tile's conv epilogue writes the toRGB partial sum of its channels, a 3-value-per-pixel pass
+                // adds them (+ bias + the upsampled previous image) — the separate toRGB pass read the whole feature map again
+                // (0.19 + 0.09 + 0.03 ms at r128 / r64 / r32)
+                const bool wide = r.cin > 128;
+                if (!rgb_done && (wide ? e->d_trgb_part && r.cin % 128 == 0 && r.cin <= 512 : true)) {
+                    half_t* tab = e->d_trgb_tab + (size_t)c0 * 32 * (wide ? 512 : 128);
+                    q.trgb_tab = tab;
+                    if (wide) q.trgb_part = e->d_trgb_part;
+                    else { q.trgb_yprev = yprev; q.trgb_yout = yb[yi]; }
+                    auto launch = [&]() {
                         const char* k = launch_conv_glds(q, e->cur);
-                        launch_trgb_finish(e->d_trgb_part, r.cin / 128, B, r.res, r.bias, yprev, yb[yi], e->cur);
-                        if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-                        if (e->profiling) e->tag_kernel[tag] = k;
+                        return (k || wide) ? k : launch_conv_tiled(q, e->cur);
+                    };
+                    q.dry_run = 1;
+                    if (launch()) {
+                        q.dry_run = 0;
+                        const double ybytes = B * (double)r.res * r.res * (12.0 * (wide ? 1 + 2 * (r.cin / 128) : 1) + (b ? 3.0 : 0.0));
+                        Prof pr(e, tag, tflops, bytes + ybytes);
+                        launch_trgb_tables(q.trgb_w, q.trgb_sn, q.trgb_sn_stride, q.trgb_smax, q.trgb_smax_stride, B, r.cin, tab, e->cur);
+                        const char* k = launch();
+                        if (wide) launch_trgb_finish(e->d_trgb_part, r.cin / 128, B, r.res, r.bias, yprev, yb[yi], e->cur);
+                        pr.ran(tag, k);
                         rgb_done = true;
                         x = out;
                         xbs = (long long)g.res_out * g.res_out * g.cout;
@@ -1159,10 +916,16 @@ static void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, con
     *y_out = yprev;
 }
 
+static void run_fromrgb(glass_engine* e, int B, const float* y, half_t* X) {
+    const glass_config& c = e->cfg;
+    const int n = c.n_blocks;
+    Prof pr(e, "D.fromrgb", 2.0 * B * (double)e->R * e->R * 3 * c.channels[n - 1],
+            B * (double)e->R * e->R * (12.0 + 2.0 * c.channels[n - 1]));
+    launch_fromrgb(y, B, e->R, c.channels[n - 1], e->d_frgb_w, e->d_frgb_b, X, e->cur);
+}
+
 // Discriminator conv blocks [i_lo, i_hi) (D order: block i works at resolution R >> i).
 // bufs: six scratch feature maps; X enters in `X`; the result pointer is returned.
-static void run_fromrgb(glass_engine* e, int B, const float* y, half_t* X);
-
 // rgb_y != nullptr (only with i_lo == 0): X has NOT been produced yet — the first conv builds the fromRGB map from the
 // skip image on the fly and writes it to X as a side output (conv_stream<fromrgb>), or, where that kernel does not
 // apply, the separate fromRGB pass runs first.
@@ -1190,12 +953,11 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
             const char* k = launch_dblock0(rgb_y, e->d_frgb_w, e->d_frgb_b, d.w0, d.b0, d.w1, d.wskip, d.b1, O, B, r, d.cin, d.cout, e->cur, planar);
             if (k) {
                 x_planar = planar;
-                if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-                if (e->profiling) e->tag_kernel[tag] = k;
+                pr.ran(tag, k);
                 std::swap(X, O);
                 continue;
             }
-            pr.on = false;
+            pr.drop();
         }
         const bool fuse_down = conv_down_supported(r, d.cin, d.cout);   // blur + skip + stride-2 conv + merge as one kernel
         if (i == 0 && rgb_y) {
@@ -1210,10 +972,9 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
             if (k) {
                 fused_rgb = true;
                 have_xs = fuse_down;
-                if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-                if (e->profiling) e->tag_kernel[tag] = k;
+                pr.ran(tag, k);
             } else {
-                pr.on = false;
+                pr.drop();
             }
         }
         if (i == 0 && rgb_y && !fused_rgb) run_fromrgb(e, B, rgb_y, X);
@@ -1240,12 +1001,11 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
             Prof pr(e, tag, 2.0 * px2 * (9.0 + 1.0) * d.cin * d.cout, 2.0 * (B * (double)r * r * d.cin + px2 * (d.cin + d.cout)));
             const char* k = launch_conv_down(Hb, XS, d.w1, d.wskip, d.b1, O, B, r, d.cin, d.cout, e->cur);
             if (k) {
-                if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-                if (e->profiling) e->tag_kernel[tag] = k;
+                pr.ran(tag, k);
                 std::swap(X, O);
                 continue;
             }
-            pr.on = false;
+            pr.drop();
         }
         ConvParams q = conv_defaults();
         q.x = HB; q.x_bstride = (long long)(r + 1) * (r + 1) * d.cin; q.B = B; q.H = q.W = r + 1; q.Cin = d.cin;
@@ -1273,8 +1033,7 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
                 qs.dry_run = 0;
                 Prof pr(e, tag, f1 + fs, 2.0 * B * ((double)(r + 1) * (r + 1) * d.cin + (double)r2 * r2 * (d.cin + d.cout)));
                 const char* k = hb_planar ? launch_conv_s2(qs, e->cur) : launch_conv_tiled(qs, e->cur);
-                if (pr.on) pr.pe.name = std::string(tag) + "@" + k;
-                if (e->profiling) e->tag_kernel[tag] = k;
+                pr.ran(tag, k);
                 std::swap(X, O);
                 continue;
             }
@@ -1292,14 +1051,6 @@ static half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* 
     return X;
 }
 
-static void run_fromrgb(glass_engine* e, int B, const float* y, half_t* X) {
-    const glass_config& c = e->cfg;
-    const int n = c.n_blocks;
-    Prof pr(e, "D.fromrgb", 2.0 * B * (double)e->R * e->R * 3 * c.channels[n - 1],
-            B * (double)e->R * e->R * (12.0 + 2.0 * c.channels[n - 1]));
-    launch_fromrgb(y, B, e->R, c.channels[n - 1], e->d_frgb_w, e->d_frgb_b, X, e->cur);
-}
-
 // mbstd + final conv + dense head for the whole population: X is [P][4][4][C0]
 static void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch) {
     const glass_config& c = e->cfg;
@@ -1313,10 +1064,7 @@ static void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch)
     p.KS = 3; p.pad = 1; p.w = e->d_final_w; p.Cout = p.Neff = CL; p.Ho = p.Wo = 4; p.bias = e->d_final_b; p.act = 1;
     p.y = e->d_dfin;
     run_conv(e, p, "D.final_conv", 2.0 * P * 16 * 9.0 * (CL + 1) * CL, 2.0 * 9 * CL * (CL + 1));
-    GemmParams g;
-    memset(&g, 0, sizeof g);
-    g.a = e->d_dfin; g.w = e->d_dense0_w; g.M = P; g.N = CL; g.K = 16 * CL; g.bias = e->d_dense0_b; g.mode = 4;
-    g.out32 = e->d_dh; g.ldo = CL; g.cand_rows = 1;
+    const GemmParams g = gemm_params(e->d_dfin, e->d_dense0_w, P, CL, 16 * CL, e->d_dense0_b, 4, nullptr, e->d_dh, 1);
     // M = P rows, K = 16 CL = 8192: the 128 x 64 tiles are 8 workgroups walking 128 K steps each (97 us for 0.5 GFLOP).  Split K into 16
     // slices (blockIdx.z) with raw partial sums, finished in a fixed order with bias + activation: 128+ workgroups, 8 steps each.
     const int S0 = 16;
@@ -1331,7 +1079,7 @@ static void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch)
             if (pr.on) pr.pe.name = std::string("D.dense0+1@") + k + "+dense01_finish";
             return;
         }
-        pr.on = false;
+        pr.drop();
     }
     run_gemm(e, g, "D.dense0");
     {
@@ -1340,77 +1088,36 @@ static void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch)
     }
 }
 
-void run_clip(glass_engine* e, int P, int l0, int l1);
-// layers [l0, end) + the head WITHOUT the patch embedding (it ran with layers [0, l0) on another stream)
-static void run_clip_rest(glass_engine* e, int P, int l0) {
-    if (l0 == 0) {          // run_clip's l0 == 0 means "with the embedding": walk layer 0 through the general path's layer loop instead
-        run_clip(e, P, -1, 1 << 20);
-        return;
-    }
-    run_clip(e, P, l0, 1 << 20);
-}
-// layers [l0, l1) of the image tower; l0 == 0 also runs the patch embedding (l0 < 0: layers from 0 WITHOUT it), l1 >= the layer count also
-// the head (ln_post, projection, cosine)
-void run_clip(glass_engine* e, int P, int l0, int l1) {
+// The end of a pass for both generators, on e->cur (the main stream): CLIP unless it already ran on the second stream (clip_done; the main
+// stream waits for it), F, the copy, the wait, the launchers' verdict, the profile.  d_join: the stream the discriminator's head is on when
+// that is not the main one (stream mode 1); joined behind CLIP.
+static int finish_pass(glass_engine* e, int P, float* out_F, bool clip_done, hipStream_t d_join) {
     const glass_config& c = e->cfg;
-    const int W = c.clip_width, ps = c.clip_patch, G = c.clip_res / ps, T = G * G + 1, M = P * T;
-    GemmParams g;
-    if (l0 == 0) {
-        memset(&g, 0, sizeof g);
-        g.a = e->d_patches; g.w = e->c_patch_w; g.M = P * G * G; g.N = W; g.K = clip_patch_k(c); g.mode = 3; g.out32 = e->d_pe; g.ldo = W; g.cand_rows = G * G;
-        run_gemm(e, g, "clip.patch_embed");
-        Prof pr(e, "clip.embed_lnpre", 0, 8.0 * M * W);
-        launch_embed_lnpre(e->d_pe, e->c_cls, e->c_pos, e->c_lnpre_g, e->c_lnpre_b, P, T, W, e->d_x, e->cur);
-    }
-    for (int li = l0 < 0 ? 0 : l0; li < l1 && li < (int)e->cblk.size(); ++li) {
-        auto& b = e->cblk[li];
-        {
-            Prof pr(e, "clip.layernorm", 0, 6.0 * M * W);
-            launch_layernorm(e->d_x, W, M, W, b.ln1_g, b.ln1_b, e->d_ln16, nullptr, e->cur);
+    if (out_F) {
+        if (!clip_done) run_clip(e, P);
+        if (d_join) {   // join: D head finished
+            GLASS_HIP(hipEventRecord(e->ev_g[0], d_join));
+            GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_g[0], 0));
         }
-        memset(&g, 0, sizeof g);
-        g.a = e->d_ln16; g.w = b.w_qkv; g.M = M; g.N = 3 * W; g.K = W; g.bias = b.b_qkv; g.mode = 0; g.out16 = e->d_qkv; g.ldo = 3 * W; g.cand_rows = T;
-        run_gemm(e, g, "clip.qkv");
-        {
-            Prof pr(e, "clip.attention", 4.0 * P * c.clip_heads * (double)T * T * 64, 8.0 * M * W);
-            launch_attention(e->d_qkv, P, T, c.clip_heads, 64, 0, e->d_attn, e->cur);
-        }
-        memset(&g, 0, sizeof g);
-        g.a = e->d_attn; g.w = b.w_out; g.M = M; g.N = W; g.K = W; g.bias = b.b_out; g.mode = 2; g.out32 = e->d_x; g.ldo = W; g.cand_rows = T;
-        run_gemm(e, g, "clip.attn_out");
-        {
-            Prof pr(e, "clip.layernorm", 0, 6.0 * M * W);
-            launch_layernorm(e->d_x, W, M, W, b.ln2_g, b.ln2_b, e->d_ln16, nullptr, e->cur);
-        }
-        memset(&g, 0, sizeof g);
-        g.a = e->d_ln16; g.w = b.w_fc; g.M = M; g.N = 4 * W; g.K = W; g.bias = b.b_fc; g.mode = 1; g.out16 = e->d_hid; g.ldo = 4 * W; g.cand_rows = T;
-        run_gemm(e, g, "clip.mlp_fc");
-        memset(&g, 0, sizeof g);
-        g.a = e->d_hid; g.w = b.w_proj; g.M = M; g.N = W; g.K = 4 * W; g.bias = b.b_proj; g.mode = 2; g.out32 = e->d_x; g.ldo = W; g.cand_rows = T;
-        run_gemm(e, g, "clip.mlp_proj");
+        launch_assemble_F(e->d_sim, e->d_dis, P, c.n_obj, e->d_F, e->cur);
+        GLASS_HIP(hipMemcpyAsync(e->h_pinned, e->d_F, (size_t)P * c.n_obj * sizeof(float), hipMemcpyDeviceToHost,
+                                 e->cur));
     }
-    if (l1 >= (int)e->cblk.size()) {
-        Prof pr(e, "clip.head", 2.0 * P * W * c.clip_embed, 4.0 * W * c.clip_embed);
-        launch_layernorm(e->d_x, (long long)T * W, P, W, e->c_lnpost_g, e->c_lnpost_b, nullptr, e->d_cls, e->cur);
-        launch_dense(e->d_cls, W, P, W, e->c_proj, c.clip_embed, nullptr, e->d_feat, c.clip_embed, 0, 0, nullptr, 0,
-                     e->cur);
-        launch_cosine(e->d_feat, e->d_target, P, c.clip_embed, e->d_sim, e->cur);
+    GLASS_HIP(hipEventRecord(e->ev1, e->cur));
+    GLASS_HIP(hipStreamSynchronize(e->cur));
+    GLASS_HIP(hipGetLastError());
+    GLASS_HIP(hipEventElapsedTime(&e->last_ms, e->ev0, e->ev1));
+    if (!e->launch_error.empty()) {
+        const std::string msg = e->launch_error;
+        e->launch_error.clear();
+        if (e->profiling) collect_profile(e);
+        glass_set_error(msg);
+        return GLASS_ERR_STATE;
     }
-}
-
-// Generated images y [B][3][R][R] -> CLIP's patch operand.  The default (clip_resize 0, clip_normalize 0) launches resize_patches_kernel, which
-// reads four input pixels per output; the antialiased modes read the whole image.
-static double clip_resize_bytes(const glass_engine* e, int B) {
-    const glass_config& c = e->cfg;
-    const double out = 2.0 * 3 * c.clip_res * c.clip_res;
-    return B * ((c.clip_resize ? 4.0 * 3 * e->R * e->R : 16.0 * c.clip_res * c.clip_res * 3) + out);
-}
-static void run_clip_resize(glass_engine* e, const float* y, int B, half_t* patches) {
-    const glass_config& c = e->cfg;
-    if (c.clip_resize == 0 && c.clip_normalize == 0)
-        launch_resize_patches(y, B, e->R, c.clip_res, c.clip_patch, clip_patch_k(c), patches, e->cur);
-    else
-        launch_preprocess_patches(y, B, e->R, c.clip_res, c.clip_patch, clip_patch_k(c), c.clip_resize, c.clip_normalize, e->rz, patches, e->cur);
+    if (out_F) memcpy(out_F, e->h_pinned, (size_t)P * c.n_obj * sizeof(float));
+    e->last_P = P;
+    if (e->profiling) collect_profile(e);
+    return GLASS_OK;
 }
 
 static int run_pass(glass_engine* e, const float* latents, int P, int generation, int first_mb,
@@ -1451,19 +1158,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
                 run_clip_resize(e, y, B, e->d_patches + (size_t)c0 * G * G * clip_patch_k(c));
             }
         }
-        if (out_F) {
-            run_clip(e, P, 0, 1 << 20);
-            launch_assemble_F(e->d_sim, e->d_dis, P, c.n_obj, e->d_F, e->cur);
-            GLASS_HIP(hipMemcpyAsync(e->h_pinned, e->d_F, (size_t)P * c.n_obj * sizeof(float), hipMemcpyDeviceToHost, e->cur));
-        }
-        GLASS_HIP(hipEventRecord(e->ev1, e->cur));
-        GLASS_HIP(hipStreamSynchronize(e->cur));
-        GLASS_HIP(hipGetLastError());
-        GLASS_HIP(hipEventElapsedTime(&e->last_ms, e->ev0, e->ev1));
-        if (out_F) memcpy(out_F, e->h_pinned, (size_t)P * c.n_obj * sizeof(float));
-        e->last_P = P;
-        if (e->profiling) collect_profile(e);
-        return GLASS_OK;
+        return finish_pass(e, P, out_F, false, nullptr);
     }
     // device-generated noise planes depend on nothing but (seed, generation, minibatch, layer): their 17 short launches run on the
     // second stream next to the mapping network / style / demodulation chain instead of ahead of it
@@ -1544,11 +1239,13 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
             }
             if (clip_ov && c0 + e->chunk >= P) {   // last chunk's patches are in place: CLIP starts now
                 // its first layers on the MAIN stream (alone on the chip), the rest on the second stream beside the discriminator
-                run_clip(e, P, 0, GLASS_CLIP_SERIAL_LAYERS);
+                run_clip_embed(e, P);
+                run_clip_layers(e, P, 0, GLASS_CLIP_SERIAL_LAYERS);
                 GLASS_HIP(hipEventRecord(e->ev_g[0], e->stream));
                 GLASS_HIP(hipStreamWaitEvent(e->stream_d, e->ev_g[0], 0));
                 e->cur = e->stream_d;
-                run_clip_rest(e, P, GLASS_CLIP_SERIAL_LAYERS);
+                run_clip_layers(e, P, GLASS_CLIP_SERIAL_LAYERS, c.clip_layers);
+                run_clip_head(e, P);
                 GLASS_HIP(hipEventRecord(e->ev_d[0], e->stream_d));
                 e->cur = e->stream;
             }
@@ -1576,404 +1273,10 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
         if (overlap) {   // patches (written on the second stream) -> CLIP on the main stream
             GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_d[n_chunks - 1], 0));
         }
-        e->cur = e->stream;
         if (clip_ov) GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_d[0], 0));   // join: CLIP finished on the second stream
-        else run_clip(e, P, 0, 1 << 20);
-        if (overlap) {   // join: D head finished
-            GLASS_HIP(hipEventRecord(e->ev_g[0], sd));
-            GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_g[0], 0));
-        }
-        launch_assemble_F(e->d_sim, e->d_dis, P, c.n_obj, e->d_F, e->cur);
-        GLASS_HIP(hipMemcpyAsync(e->h_pinned, e->d_F, (size_t)P * c.n_obj * sizeof(float), hipMemcpyDeviceToHost,
-                                 e->cur));
     }
     e->cur = e->stream;
-    GLASS_HIP(hipEventRecord(e->ev1, e->cur));
-    GLASS_HIP(hipStreamSynchronize(e->cur));
-    GLASS_HIP(hipGetLastError());
-    GLASS_HIP(hipEventElapsedTime(&e->last_ms, e->ev0, e->ev1));
-    if (!e->launch_error.empty()) {
-        const std::string msg = e->launch_error;
-        e->launch_error.clear();
-        if (e->profiling) collect_profile(e);
-        glass_set_error(msg);
-        return GLASS_ERR_STATE;
-    }
-    if (out_F) memcpy(out_F, e->h_pinned, (size_t)P * c.n_obj * sizeof(float));
-    e->last_P = P;
-    if (e->profiling) collect_profile(e);
-    return GLASS_OK;
-}
-
-// CLIP text tower: token+pos embedding -> causal transformer -> ln_final -> EOT row @ text_projection
-extern "C" int glass_engine_encode_text(glass_engine* e, const int32_t* tokens, int32_t n_texts, int32_t ctx, float* out_feat) {
-    REQUIRE(e && tokens && out_feat && n_texts > 0, GLASS_ERR_ARG, "null argument");
-    REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
-    REQUIRE(e->t_tok != nullptr, GLASS_ERR_STATE, "CLIP text tower weights were not loaded (clip.token_embedding.weight ...)");
-    REQUIRE(ctx == e->t_ctx && ctx <= 128, GLASS_ERR_ARG, "context length does not match positional_embedding");
-    GLASS_HIP(hipSetDevice(e->cfg.device));
-    const int W = e->t_width, heads = W / 64, M = n_texts * ctx, E = e->cfg.clip_embed;
-    std::vector<int> eot(n_texts);
-    for (int n = 0; n < n_texts; ++n) {       // text.argmax(dim=-1): EOT has the highest id (clip/model.py:318)
-        int best = 0;
-        for (int t = 0; t < ctx; ++t) {
-            const int v = tokens[(size_t)n * ctx + t];
-            REQUIRE(v >= 0 && v < e->t_vocab, GLASS_ERR_ARG, "token id out of range");
-            if (v > tokens[(size_t)n * ctx + best]) best = t;
-        }
-        eot[n] = best;
-    }
-    auto& tw = e->twork;
-    auto cleanup = [&]() { text_work_free(e); };
-    hipError_t err = hipSuccess;
-    if (tw.n_texts != n_texts) {          // (re)build the workspace for this batch size
-        text_work_free(e);
-        err = hipMalloc(&tw.d_tok, (size_t)M * sizeof(int));
-        if (err == hipSuccess) err = hipMalloc(&tw.d_rows, (size_t)n_texts * sizeof(int));
-        if (err == hipSuccess) err = hipMalloc(&tw.x, (size_t)M * W * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&tw.cls, (size_t)n_texts * W * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&tw.feat, (size_t)n_texts * E * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&tw.ln16, (size_t)M * W * sizeof(half_t));
-        if (err == hipSuccess) err = hipMalloc(&tw.qkv, (size_t)M * 3 * W * sizeof(half_t));
-        if (err == hipSuccess) err = hipMalloc(&tw.att, (size_t)M * W * sizeof(half_t));
-        if (err == hipSuccess) err = hipMalloc(&tw.hid, (size_t)M * 4 * W * sizeof(half_t));
-        if (err != hipSuccess) {
-            cleanup();
-            glass_set_error(std::string("encode_text: hipMalloc failed: ") + hipGetErrorString(err));
-            return GLASS_ERR_NOMEM;
-        }
-        tw.n_texts = n_texts;
-    }
-    int* d_tok = tw.d_tok;
-    float *x = tw.x, *cls = tw.cls, *feat = tw.feat;
-    half_t *ln16 = tw.ln16, *qkv = tw.qkv, *att = tw.att, *hid = tw.hid;
-    for (int n = 0; n < n_texts; ++n) eot[n] += n * ctx;          // row of each text's EOT token in x
-    hipStream_t st = e->stream;
-    hipMemcpyAsync(d_tok, tokens, (size_t)M * sizeof(int), hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(tw.d_rows, eot.data(), (size_t)n_texts * sizeof(int), hipMemcpyHostToDevice, st);
-    launch_embed_text(d_tok, e->t_tok, e->t_pos, M, ctx, W, x, st);
-    GemmParams g;
-    for (auto& b : e->tblk) {
-        launch_layernorm(x, W, M, W, b.ln1_g, b.ln1_b, ln16, nullptr, st);
-        memset(&g, 0, sizeof g);
-        g.a = ln16; g.w = b.w_qkv; g.M = M; g.N = 3 * W; g.K = W; g.bias = b.b_qkv; g.mode = 0; g.out16 = qkv; g.ldo = 3 * W; g.cand_rows = ctx;
-        if (!launch_gemm_tiled(g, st)) launch_gemm_direct(g, st);
-        launch_attention(qkv, n_texts, ctx, heads, 64, 1, att, st);
-        memset(&g, 0, sizeof g);
-        g.a = att; g.w = b.w_out; g.M = M; g.N = W; g.K = W; g.bias = b.b_out; g.mode = 2; g.out32 = x; g.ldo = W; g.cand_rows = ctx;
-        if (!launch_gemm_tiled(g, st)) launch_gemm_direct(g, st);
-        launch_layernorm(x, W, M, W, b.ln2_g, b.ln2_b, ln16, nullptr, st);
-        memset(&g, 0, sizeof g);
-        g.a = ln16; g.w = b.w_fc; g.M = M; g.N = 4 * W; g.K = W; g.bias = b.b_fc; g.mode = 1; g.out16 = hid; g.ldo = 4 * W; g.cand_rows = ctx;
-        if (!launch_gemm_tiled(g, st)) launch_gemm_direct(g, st);
-        memset(&g, 0, sizeof g);
-        g.a = hid; g.w = b.w_proj; g.M = M; g.N = W; g.K = 4 * W; g.bias = b.b_proj; g.mode = 2; g.out32 = x; g.ldo = W; g.cand_rows = ctx;
-        if (!launch_gemm_tiled(g, st)) launch_gemm_direct(g, st);
-    }
-    // ln_final on the EOT row of each text only (row-wise op): one launch over the gathered rows (round 4: it was one launch per text)
-    launch_layernorm_rows(x, tw.d_rows, n_texts, W, e->t_lnf_g, e->t_lnf_b, cls, st);
-    launch_dense(cls, W, n_texts, W, e->t_proj, E, nullptr, feat, E, 0, 0, nullptr, 0, st);
-    err = hipMemcpyAsync(out_feat, feat, (size_t)n_texts * E * sizeof(float), hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) {
-        cleanup();
-        glass_set_error(std::string("encode_text failed: ") + hipGetErrorString(err));
-        return GLASS_ERR_HIP;
-    }
-    return GLASS_OK;
-}
-
-extern "C" int glass_engine_encode_image(glass_engine* e, const float* images, int32_t n, float* out_feat) {
-    REQUIRE(e && images && out_feat && n > 0, GLASS_ERR_ARG, "null argument");
-    REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
-    REQUIRE(n <= e->cfg.max_pop, GLASS_ERR_ARG, "more images than max_pop");
-    const glass_config& c = e->cfg;
-    GLASS_HIP(hipSetDevice(c.device));
-    const size_t elems = (size_t)n * 3 * c.clip_res * c.clip_res;
-    float* d_img = nullptr;
-    GLASS_HIP(hipMalloc(&d_img, elems * sizeof(float)));
-    hipError_t err = hipMemcpyAsync(d_img, images, elems * sizeof(float), hipMemcpyHostToDevice, e->stream);
-    e->cur = e->stream;
-    launch_image_patches(d_img, n, c.clip_res, c.clip_patch, clip_patch_k(c), e->d_patches, e->stream);
-    run_clip(e, n, 0, 1 << 20);
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(out_feat, e->d_feat, (size_t)n * c.clip_embed * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err == hipSuccess) err = hipGetLastError();
-    hipFree(d_img);
-    e->prof_events.clear();
-    e->event_next = 0;
-    if (err != hipSuccess) {
-        glass_set_error(std::string("encode_image failed: ") + hipGetErrorString(err));
-        return GLASS_ERR_HIP;
-    }
-    return GLASS_OK;
-}
-
-static void gpt2_work_free(glass_engine* e) {
-    auto& w = e->gwork;
-    if (w.exec) hipGraphExecDestroy(w.exec);
-    if (w.graph) hipGraphDestroy(w.graph);
-    hipFree(w.d_tok); hipFree(w.d_gen); hipFree(w.d_state); hipFree(w.d_samp); hipFree(w.x); hipFree(w.ln); hipFree(w.qkv); hipFree(w.att); hipFree(w.hid);
-    hipFree(w.last); hipFree(w.logits); hipFree(w.kc); hipFree(w.vc); hipFree(w.part); hipFree(w.stats); hipFree(w.pairs); hipFree(w.pst);
-    w = glass_engine::Gpt2Work();
-}
-
-static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length, int32_t* out_tokens,
-                             const int32_t* samp);
-
-// Sequences are independent, and the single-token step kernels hold at most 64 rows: a longer population is decoded in row groups of
-// 64, each through exactly the launches a 64-row call makes — a row's tokens do not depend on how many rows the call (or a shard) holds.
-extern "C" int glass_engine_gpt2_decode(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length,
-                                        int32_t* out_tokens) {
-    REQUIRE(e && context && out_tokens && P > 0 && nctx > 0 && length > 0, GLASS_ERR_ARG, "bad argument");
-    float total_ms = 0.f;
-    for (int g0 = 0; g0 < P; g0 += 64) {
-        const int rc = gpt2_decode_group(e, context + (size_t)g0 * nctx, std::min(64, P - g0), nctx, length,
-                                         out_tokens + (size_t)g0 * (nctx + length), nullptr);
-        if (rc) return rc;
-        total_ms += e->gwork.last_ms;
-    }
-    e->gwork.last_ms = total_ms;
-    e->last_ms = total_ms;
-    return GLASS_OK;
-}
-
-// Stochastic decode: the same row groups, each group's first global row in the sampler's words — a row's draws depend on its global index,
-// the step, (seed, generation, purpose) and its own logits only.
-extern "C" int glass_engine_gpt2_sample(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length, float temperature,
-                                        int32_t top_k, uint64_t seed, int32_t generation, int32_t first_row, int32_t purpose,
-                                        int32_t* out_tokens) {
-    REQUIRE(e && context && out_tokens && P > 0 && nctx > 0 && length > 0, GLASS_ERR_ARG, "bad argument");
-    REQUIRE(temperature > 0.f && temperature < INFINITY, GLASS_ERR_ARG, "temperature must be a finite value > 0");
-    REQUIRE(top_k >= 0 && top_k <= GPT2_SAMPLE_TOPK_MAX, GLASS_ERR_ARG, "top_k must lie in [0, 256]");
-    REQUIRE(first_row >= 0 && (long long)first_row + P <= 0x7fffffffLL, GLASS_ERR_ARG, "first_row out of range");
-    REQUIRE(e->g_wte == nullptr || gpt2_sample_supported(e->g_vocab), GLASS_ERR_ARG, "vocabulary too large for the sampler (> 131072)");
-    float total_ms = 0.f;
-    for (int g0 = 0; g0 < P; g0 += 64) {
-        int32_t samp[GPT2_SP_WORDS];
-        samp[GPT2_SP_SEED_LO] = (int32_t)(uint32_t)(seed & 0xFFFFFFFFu);
-        samp[GPT2_SP_SEED_HI] = (int32_t)(uint32_t)(seed >> 32);
-        samp[GPT2_SP_GEN] = generation;
-        samp[GPT2_SP_ROW0] = first_row + g0;
-        samp[GPT2_SP_PURPOSE] = purpose;
-        memcpy(&samp[GPT2_SP_TEMP], &temperature, sizeof(float));
-        samp[GPT2_SP_TOPK] = top_k;
-        samp[GPT2_SP_STEP] = 0;
-        const int rc = gpt2_decode_group(e, context + (size_t)g0 * nctx, std::min(64, P - g0), nctx, length,
-                                         out_tokens + (size_t)g0 * (nctx + length), samp);
-        if (rc) return rc;
-        total_ms += e->gwork.last_ms;
-    }
-    e->gwork.last_ms = total_ms;
-    e->last_ms = total_ms;
-    return GLASS_OK;
-}
-
-// samp: the sampler's GPT2_SP_* words (host), nullptr = greedy
-static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length, int32_t* out_tokens,
-                             const int32_t* samp) {
-    REQUIRE(e && context && out_tokens && P > 0 && nctx > 0 && length > 0, GLASS_ERR_ARG, "bad argument");
-    REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
-    REQUIRE(e->g_wte != nullptr, GLASS_ERR_STATE, "GPT-2 weights were not loaded (gpt2.transformer.*)");
-    const int D = e->g_dim, V = e->g_vocab, heads = D / 64, Tmax = nctx + length;
-    REQUIRE(Tmax <= e->g_npos && Tmax <= 256, GLASS_ERR_ARG, "sequence longer than the position table / 256");
-    // the prefill attention holds a sequence's keys, values and its whole score matrix in LDS: 4 * (n^2 + 196 n) bytes of the 160 KB
-    REQUIRE(gpt2_attention_lds_bytes(nctx, nctx) <= GPT2_ATTENTION_LDS_MAX, GLASS_ERR_ARG,
-            "context longer than 126 tokens (the prefill attention keeps 4 * (n^2 + 196 n) bytes per sequence in 160 KB of LDS)");
-    for (long long i = 0; i < (long long)P * nctx; ++i)
-        REQUIRE(context[i] >= 0 && context[i] < V, GLASS_ERR_ARG, "token id out of range");
-    GLASS_HIP(hipSetDevice(e->cfg.device));
-    const int nl = (int)e->gblk.size();
-    const size_t rows = (size_t)P * nctx;
-    auto& w = e->gwork;
-    hipStream_t st = e->stream;
-    auto fits = [&](const glass_engine::Gpt2Work& g) { return g.P == P && g.nctx == nctx && g.length == length; };
-    if (!fits(w)) std::swap(e->gwork, e->gwork_alt);   // second slot: a ragged population alternates between a 64-row group and its
-                                                       // remainder — each keeps its buffers and its captured step graph
-    if (!fits(w)) {      // (re)build the workspace for this geometry
-        gpt2_work_free(e);
-        // split-K scratch for the single-token steps (M = P <= 64 rows: each weight is streamed once per step, so the number
-        // of workgroups pulling on HBM is what matters), device-resident tokens and step state {past length, step index}
-        w.part_elems = (size_t)16 * P * 4 * D;
-        hipError_t err = hipMalloc(&w.d_tok, rows * sizeof(int));
-        if (err == hipSuccess) err = hipMalloc(&w.d_gen, (size_t)P * length * sizeof(int));
-        if (err == hipSuccess) err = hipMalloc(&w.d_state, 3 * sizeof(int));      // {past length, step index, ticket counter of the fused step tail}
-        if (err == hipSuccess) err = hipMalloc(&w.d_samp, GPT2_SP_WORDS * sizeof(int));
-        if (err == hipSuccess) err = hipMalloc(&w.x, rows * D * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.ln, rows * D * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.qkv, rows * 3 * D * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.att, rows * D * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.hid, rows * 4 * D * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.last, (size_t)P * D * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.logits, (size_t)P * V * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.kc, (size_t)nl * P * Tmax * D * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.vc, (size_t)nl * P * Tmax * D * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.part, w.part_elems * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.pairs, (size_t)2 * P * ((V + 31) / 32) * sizeof(float));   // (max, index) per (row, 32-column block)
-        if (err == hipSuccess) err = hipMalloc(&w.stats, (size_t)P * (2 + 2 * 32) * sizeof(float));
-        if (err == hipSuccess) err = hipMalloc(&w.pst, (size_t)P * 24 * 2 * sizeof(float));   // row partials (mean, M2) of the complete-output step products   // + the two-stage arg-max's (value, index) pairs
-        if (err != hipSuccess) {
-            gpt2_work_free(e);
-            glass_set_error(std::string("gpt2_decode: hipMalloc failed: ") + hipGetErrorString(err));
-            return GLASS_ERR_NOMEM;
-        }
-        w.P = P; w.nctx = nctx; w.length = length;
-    }
-    // the captured step graph belongs to the mode it was recorded in: greedy never replays a sampling step, nor the reverse
-    const int sample = samp ? 1 : 0;
-    if (w.sample != sample) {
-        if (w.exec) { hipGraphExecDestroy(w.exec); w.exec = nullptr; }
-        if (w.graph) { hipGraphDestroy(w.graph); w.graph = nullptr; }
-        w.sample = sample;
-    }
-    // one transformer pass over `nd` new positions per sequence; step_state != nullptr: single-token step whose past length /
-    // step index are read from device memory (the form that is captured into a hipGraph and replayed)
-    // single-token steps, fused form (round 3): LayerNorm applied on the activation operand of the next
-    // product from row statistics, products with complete outputs (no split-K reduce launch) except the MLP's second one, whose
-    // split-K slices of the residual products finished together with the residual add and the next statistics: 9 launches per layer
-    // instead of 11 (complete-output products — 72 / 24 / 96 workgroups walking three chunks each — were 21 us against 9 + 4: dropped)
-    // (the launcher's own shape conditions, asked through the launcher's predicate: a product it refuses returns 0 slices and nothing written)
-    const bool fuse_ok = gemm_f32_step_supported(P, D, D, true) && gemm_f32_step_supported(P, 4 * D, 4 * D, false);
-    bool step_refused = false;
-    // fused step tail (round 4): the pick also writes the NEXT step's embedding + first LayerNorm statistics and advances the state — a step
-    // starts at layer 0's qkv product; the first step's embedding is one eager launch after the prefill.
-    const bool tail_fused = fuse_ok && D <= 1024 && gpt2_head_supported(P, V, D, D);
-    auto pass = [&](int nd, int past, const int* step_state) {
-        const int M = P * nd;
-        // round 4 (gpt2.hip): the attention output product and the MLP's first product in the complete-output form — no slices, so no
-        // gpt2_finalize / splitk_reduce launch behind them: 6 launches per layer instead of 8.  (The qkv product and the MLP's second one
-        // stay split: complete, they were 12-14 us against 9.5 and 34 against 12 + 5.)
-        const bool rowblk = step_state && fuse_ok && D % 32 == 0 && D / 32 <= 24 &&
-                            gemm_f32_rowblk_supported(P, D, D, D, false, true) && gemm_f32_rowblk_supported(P, 4 * D, D, D, true, false);
-        if (step_state) { if (!tail_fused) launch_gpt2_embed_step(w.d_gen, step_state, P, e->g_wte, e->g_wpe, D, w.x, st, fuse_ok ? w.stats : nullptr); }
-        else launch_gpt2_embed(w.d_tok, e->g_wte, e->g_wpe, M, nd, past, D, w.x, st);
-        if (step_state && fuse_ok) {      // (the embedding kernel left the first layer's LayerNorm statistics)
-            for (int l = 0; l < nl; ++l) {
-                const auto& b = e->gblk[l];
-                float* kcl = w.kc + (size_t)l * P * Tmax * D;
-                float* vcl = w.vc + (size_t)l * P * Tmax * D;
-                int S = launch_gemm_f32_step(w.x, b.w_qkv, b.b_qkv, w.qkv, P, 3 * D, D, D, 3 * D, 0, st, w.part, w.part_elems, w.stats, b.ln1_g, b.ln1_b);
-                step_refused |= S == 0;
-                if (Tmax <= 64) {      // one wave per (sequence, head); it sums the product's slices itself
-                    launch_gpt2_attention_step(w.qkv, S > 1 ? w.part : nullptr, S, b.b_qkv, kcl, vcl, P, Tmax, heads, w.att, st, step_state);
-                } else {
-                    if (S > 1) launch_gpt2_reduce(w.part, S, b.b_qkv, w.qkv, P, 3 * D, 3 * D, 0, st);
-                    launch_gpt2_attention(w.qkv, kcl, vcl, P, 1, past, Tmax, heads, w.att, st, step_state);
-                }
-                if (rowblk) {       // x += att @ Wo + b (row partials of LayerNorm 2 in the epilogue); hid = gelu(LN2(x) @ Wfc + b)
-                    bool ok = launch_gemm_f32_rowblk(w.att, b.w_o, b.b_o, w.x, P, D, D, D, D, 2, st, nullptr, 0, nullptr, nullptr, w.pst);
-                    ok &= launch_gemm_f32_rowblk(w.x, b.w_fc, b.b_fc, w.hid, P, 4 * D, D, D, 4 * D, 1, st, w.pst, D / 32, b.ln2_g, b.ln2_b, nullptr);
-                    step_refused |= !ok;
-                } else {
-                    S = launch_gemm_f32_step(w.att, b.w_o, b.b_o, w.x, P, D, D, D, D, 2, st, w.part, w.part_elems, nullptr, nullptr, nullptr);
-                    step_refused |= S == 0;
-                    launch_gpt2_finalize(S > 1 ? w.part : nullptr, S, b.b_o, w.x, P, D, w.stats, st);       // residual + LayerNorm 2 statistics
-                    S = launch_gemm_f32_step(w.x, b.w_fc, b.b_fc, w.hid, P, 4 * D, D, D, 4 * D, 1, st, w.part, w.part_elems, w.stats, b.ln2_g, b.ln2_b);
-                    step_refused |= S == 0;
-                    if (S > 1) launch_gpt2_reduce(w.part, S, b.b_fc, w.hid, P, 4 * D, 4 * D, 1, st);
-                }
-                S = launch_gemm_f32_step(w.hid, b.w_pr, b.b_pr, w.x, P, D, 4 * D, 4 * D, D, 2, st, w.part, w.part_elems, nullptr, nullptr, nullptr);
-                step_refused |= S == 0;
-                launch_gpt2_finalize(S > 1 ? w.part : nullptr, S, b.b_pr, w.x, P, D, w.stats, st);      // residual + next LayerNorm's statistics
-            }
-            if (tail_fused) {
-                if (samp)       // the sampling twin: logits written too, the sampler from the pairs, the same embed / advance tail
-                    step_refused |= !launch_gpt2_head_sample(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.logits, w.pairs, w.d_samp,
-                                                             w.d_gen, w.d_state, true, e->g_wte, e->g_wpe, w.x, w.stats, st);
-                else
-                    step_refused |= !launch_gpt2_head_tail(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.pairs, w.d_gen, w.d_state, e->g_wte,
-                                                           e->g_wpe, w.x, w.stats, st);
-                return;
-            }
-            const bool head = samp ? launch_gpt2_head_sample(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.logits, w.pairs,
-                                                             w.d_samp, w.d_gen, w.d_state, false, nullptr, nullptr, nullptr, nullptr, st)
-                                   : launch_gpt2_head(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, nullptr, w.pairs, w.d_gen,
-                                                      w.d_state, st);
-            if (!head) {
-                // ln_f fused; the real vocabulary (1571 column blocks) is never split, a small one may be
-                const int S = launch_gemm_f32_step(w.x, e->g_wte, nullptr, w.logits, P, V, D, D, V, 0, st, w.part, w.part_elems, w.stats, e->g_lnf_g, e->g_lnf_b);
-                step_refused |= S == 0;
-                if (S > 1) launch_gpt2_reduce(w.part, S, nullptr, w.logits, P, V, V, 0, st);
-                if (samp) launch_gpt2_sample(w.logits, P, V, w.d_samp, w.d_gen, w.d_state, st);
-                else launch_argmax(w.logits, P, V, w.d_gen, st, w.d_state, w.stats + 2 * P);
-            }
-            launch_gpt2_advance(w.d_state, st);
-            return;
-        }
-        for (int l = 0; l < nl; ++l) {
-            const auto& b = e->gblk[l];
-            float* kcl = w.kc + (size_t)l * P * Tmax * D;
-            float* vcl = w.vc + (size_t)l * P * Tmax * D;
-            launch_layernorm(w.x, D, M, D, b.ln1_g, b.ln1_b, nullptr, w.ln, st);
-            launch_gemm_f32(w.ln, b.w_qkv, b.b_qkv, w.qkv, M, 3 * D, D, D, 3 * D, 0, st, w.part, w.part_elems, nd > 1);
-            launch_gpt2_attention(w.qkv, kcl, vcl, P, nd, past, Tmax, heads, w.att, st, step_state);
-            launch_gemm_f32(w.att, b.w_o, b.b_o, w.x, M, D, D, D, D, 2, st, w.part, w.part_elems, nd > 1);
-            launch_layernorm(w.x, D, M, D, b.ln2_g, b.ln2_b, nullptr, w.ln, st);
-            launch_gemm_f32(w.ln, b.w_fc, b.b_fc, w.hid, M, 4 * D, D, D, 4 * D, 1, st, w.part, w.part_elems, nd > 1);
-            launch_gemm_f32(w.hid, b.w_pr, b.b_pr, w.x, M, D, 4 * D, 4 * D, D, 2, st, w.part, w.part_elems, nd > 1);
-        }
-        // ln_f on the last position of each sequence, tied lm_head, greedy pick -> d_gen[step][P]
-        launch_layernorm(w.x + (size_t)(nd - 1) * D, (long long)nd * D, P, D, e->g_lnf_g, e->g_lnf_b, nullptr, w.last, st);
-        launch_gemm_f32(w.last, e->g_wte, nullptr, w.logits, P, V, D, D, V, 0, st, w.part, w.part_elems);
-        if (samp) launch_gpt2_sample(w.logits, P, V, w.d_samp, w.d_gen, w.d_state, st);
-        else launch_argmax(w.logits, P, V, w.d_gen, st, w.d_state, w.stats + 2 * P);
-        launch_gpt2_advance(w.d_state, st);
-    };
-    std::vector<int32_t> gen((size_t)P * length);
-    GLASS_HIP(hipEventRecord(e->ev0, st));
-    hipMemcpyAsync(w.d_tok, context, rows * sizeof(int), hipMemcpyHostToDevice, st);
-    const int state0[3] = {0, 0, 0}, state1[3] = {nctx, 1, 0};
-    hipMemcpyAsync(w.d_state, state0, sizeof state0, hipMemcpyHostToDevice, st);
-    if (samp) hipMemcpyAsync(w.d_samp, samp, GPT2_SP_WORDS * sizeof(int), hipMemcpyHostToDevice, st);
-    pass(nctx, 0, nullptr);                                 // prefill = step 0 (writes d_gen[0 .. P))
-    hipMemcpyAsync(w.d_state, state1, sizeof state1, hipMemcpyHostToDevice, st);
-    if (tail_fused && length > 1) launch_gpt2_embed_step(w.d_gen, w.d_state, P, e->g_wte, e->g_wpe, D, w.x, st, w.stats);   // step 1's embedding (later ones: the step tail)
-    hipError_t err = hipSuccess;
-    if (length > 1) {
-        // the 29 single-token steps are the same ~190 launches each: capture one step once, replay it (launch latency, not work,
-        // is what the un-graphed loop spent its time on)
-        if (!w.exec) {
-            err = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            if (err == hipSuccess) {
-                pass(1, 0, w.d_state);
-                err = hipStreamEndCapture(st, &w.graph);
-                if (err == hipSuccess) err = hipGraphInstantiate(&w.exec, w.graph, nullptr, nullptr, 0);
-            }
-            if (err != hipSuccess) {       // capture unavailable: eager steps (same kernels, same device-side state)
-                (void)hipGetLastError();
-                if (w.exec) { hipGraphExecDestroy(w.exec); w.exec = nullptr; }
-                if (w.graph) { hipGraphDestroy(w.graph); w.graph = nullptr; }
-                err = hipSuccess;
-            }
-        }
-        for (int step = 1; step < length && err == hipSuccess; ++step) {
-            if (w.exec) err = hipGraphLaunch(w.exec, st);
-            else pass(1, 0, w.d_state);
-        }
-    }
-    if (err == hipSuccess) err = hipEventRecord(e->ev1, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(gen.data(), w.d_gen, (size_t)P * length * sizeof(int), hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) {
-        gpt2_work_free(e);
-        glass_set_error(std::string("gpt2_decode failed: ") + hipGetErrorString(err));
-        return GLASS_ERR_HIP;
-    }
-    if (step_refused) {        // fuse_ok and the launcher disagreed about a shape: buffers were consumed unwritten — never a silent result
-        gpt2_work_free(e);
-        glass_set_error("gpt2_decode: a fused step product refused its shape (launch_gemm_f32_step returned 0)");
-        return GLASS_ERR_STATE;
-    }
-    (void)hipEventElapsedTime(&w.last_ms, e->ev0, e->ev1);
-    e->last_ms = w.last_ms;
-    for (int p = 0; p < P; ++p) {
-        for (int t = 0; t < nctx; ++t) out_tokens[(size_t)p * Tmax + t] = context[(size_t)p * nctx + t];
-        for (int s2 = 0; s2 < length; ++s2) out_tokens[(size_t)p * Tmax + nctx + s2] = gen[(size_t)s2 * P + p];
-    }
-    return GLASS_OK;
+    return finish_pass(e, P, out_F, clip_ov, overlap ? sd : nullptr);
 }
 
 extern "C" int glass_engine_evaluate(glass_engine* e, const float* latents, int32_t P, int32_t generation,

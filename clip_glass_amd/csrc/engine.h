@@ -148,6 +148,7 @@ struct glass_engine {
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         float last_ms = 0.f;      // device time of the last decode (hipEvents around the passes)
+        std::vector<void*> owned; // every buffer above (owned_alloc), freed by gpt2_work_free
     } gwork, gwork_alt;       // current workspace + the previous geometry's (glass_engine_gpt2_decode's row groups: 64 rows and a remainder)
     // text tower (optional)
     std::vector<ClipBlock> tblk;
@@ -157,6 +158,7 @@ struct glass_engine {
         int *d_tok = nullptr, *d_rows = nullptr;
         float *x = nullptr, *cls = nullptr, *feat = nullptr;
         half_t *ln16 = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr;
+        std::vector<void*> owned;   // every buffer above (owned_alloc), freed by text_work_free
     } twork;
     int t_width = 0, t_ctx = 0, t_vocab = 0;
     float* d_target = nullptr;
@@ -202,7 +204,7 @@ struct glass_engine {
 };
 
 // ------------------------------------------------------------------------------------
-// helpers shared by engine.cpp and biggan.cpp
+// helpers shared by the host files (engine.cpp, clip.cpp, gpt2_host.cpp, biggan.cpp)
 // ------------------------------------------------------------------------------------
 #define REQUIRE(cond, code, msg)          \
     do {                                  \
@@ -215,17 +217,23 @@ struct glass_engine {
 // ------------------------------------------------------------------------------------
 // allocation / upload helpers
 // ------------------------------------------------------------------------------------
+// hipMalloc into the list that owns the buffer: the engine's (dev_alloc), or that of a workspace which is rebuilt when its geometry
+// changes (TextWork, Gpt2Work), so that the free is a loop over the list
+template <typename T>
+inline hipError_t owned_alloc(std::vector<void*>& owned, T** p, size_t n) {
+    void* q = nullptr;
+    const hipError_t err = hipMalloc(&q, n * sizeof(T));
+    if (err != hipSuccess) return err;
+    owned.push_back(q);
+    *p = (T*)q;
+    return hipSuccess;
+}
 template <typename T>
 inline int dev_alloc(glass_engine* e, T** p, size_t n) {
-    void* q = nullptr;
-    hipError_t err = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-    if (err != hipSuccess) {
-        glass_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(err));
-        return GLASS_ERR_NOMEM;
-    }
-    e->allocs.push_back(q);
-    *p = (T*)q;
-    return GLASS_OK;
+    const hipError_t err = owned_alloc(e->allocs, p, std::max<size_t>(n, 1));
+    if (err == hipSuccess) return GLASS_OK;
+    glass_set_error(std::string("hipMalloc failed: ") + hipGetErrorString(err));
+    return GLASS_ERR_NOMEM;
 }
 template <typename T>
 inline int upload(glass_engine* e, T** p, const std::vector<T>& v) {
@@ -254,7 +262,8 @@ struct Prof {
     glass_engine* e;
     bool on;
     ProfEvent pe;
-    Prof(glass_engine* e_, const char* name, double flops, double bytes) : e(e_), on(e_->profiling) {
+    // name == nullptr: no scope (the text tower's launches are never profiled)
+    Prof(glass_engine* e_, const char* name, double flops, double bytes) : e(e_), on(name && e_->profiling) {
         if (on && !e->prof_filter.empty()) {   // only launches whose kernel symbol (as of the previous pass) matches
             auto it = e->tag_kernel.find(name);
             on = it != e->tag_kernel.end() && it->second.find(e->prof_filter) != std::string::npos;
@@ -280,13 +289,35 @@ struct Prof {
         hipEventRecord(pe.e1, e->cur);
         e->prof_events.push_back(pe);
     }
+    // the launch went to kernel `k`: the row is named tag@k, and set_profile_filter() finds the tag's kernel in the next pass
+    void ran(const char* tag, const char* k) {
+        if (on) pe.name = std::string(tag) + "@" + k;
+        if (e->profiling) e->tag_kernel[tag] = k;
+    }
+    void drop() { on = false; }   // the launcher refused: nothing ran in this scope
 };
 
 void collect_profile(glass_engine* e);
 void run_conv(glass_engine* e, const ConvParams& p, const char* tag, double flops, double bytes);
 void run_gemm(glass_engine* e, const GemmParams& p, const char* tag);
 ConvParams conv_defaults();
-void run_clip(glass_engine* e, int P, int l0, int l1);
+// out[M][N] = a[M][K] x w[N][K]^T (+ bias), written as `mode` says (common.h GemmParams: fp16 to out16 for modes 0 / 1, fp32 to out32 above)
+GemmParams gemm_params(const half_t* a, const half_t* w, int M, int N, int K, const float* bias, int mode, half_t* out16, float* out32,
+                       int cand_rows);
+
+// ---- CLIP (clip.cpp) ----
+int clip_patch_k(const glass_config& c);     // the patch-embedding GEMM's K: 3 patch^2 padded to gemm_tiled's K step
+int finalize_clip(glass_engine* e);
+int finalize_preprocess(glass_engine* e);
+void text_work_free(glass_engine* e);
+double clip_resize_bytes(const glass_engine* e, int B);
+void run_clip_resize(glass_engine* e, const float* y, int B, half_t* patches);
+// the image tower on e->cur, for the P candidates whose patch operand is in d_patches: patch embedding + ln_pre, layers [l0, l1), and the
+// head (ln_post, projection, cosine against the target); run_clip is all of it
+void run_clip_embed(glass_engine* e, int P);
+void run_clip_layers(glass_engine* e, int P, int l0, int l1);
+void run_clip_head(glass_engine* e, int P);
+void run_clip(glass_engine* e, int P);
 // Stream mode 2: the patch embedding and this many layers of CLIP's image tower run on the MAIN stream, alone on the chip, before the
 // discriminator starts; the rest of the tower runs on the second stream beside it.  Forked right behind the resize (rounds 2-5), the tower's
 // first launch raced the discriminator's first kernel — a persistent kernel that fills every CU for 3.9 ms — and lost about every other
@@ -297,6 +328,11 @@ std::vector<_Float16> to_half(const float* p, size_t n, float scale = 1.f);
 std::vector<float> scaled(const float* p, size_t n, float scale);
 std::vector<float> transposed(const float* W, int N, int K, float coef);
 
-// engine_ops.cpp helpers shared with the diagnostic op ABI
+
+// ---- GPT-2 (gpt2_host.cpp) ----
+int finalize_gpt2(glass_engine* e);
+void gpt2_work_free(glass_engine* e);     // frees e->gwork (buffers + captured step graph) and resets it
+
+// weight packing (engine.cpp), shared with the diagnostic op ABI (ops.hip)
 int glass_fold_upconv(const float* W, int cout, int cin, std::vector<_Float16>& out);  // [9][4*cout][cin]
 void glass_pack_conv(const float* W, int cout, int cin, int ks, int cin_pad, std::vector<_Float16>& out);  // [ks*ks][cout][cin_pad]

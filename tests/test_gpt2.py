@@ -133,7 +133,7 @@ def test_engine_gpt2_decode_matches_oracle(geo, P, n_ctx, length):
 
 
 # Geometries that reach the branches of gpt2_decode_group the cases above do not (all n_layer = 2, weight seed 2, context seed 1).
-# id -> (n_embd, vocab, P, n_ctx, length, n_positions); the step path each one takes, from the launch conditions in engine.cpp:
+# id -> (n_embd, vocab, P, n_ctx, length, n_positions); the step path each one takes, from the launch conditions in gpt2_host.cpp:
 #   D64     fused + tail-fused, not rowblk; every step product unsplit but the MLP's second (S = 4); step attention, P * heads = 33 (the
 #           last workgroup has one live wave); prefill rows 33 * 23
 #   D192    fused + tail-fused; three 64-deep chunks: S = 3 with one K part per workgroup (qkv, attention output, MLP first), S = 12 (MLP second)
