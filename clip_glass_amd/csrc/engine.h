@@ -204,7 +204,7 @@ struct glass_engine {
 };
 
 // ------------------------------------------------------------------------------------
-// helpers shared by the host files (engine.cpp, clip.cpp, gpt2_host.cpp, biggan.cpp)
+// helpers shared by the host files (engine.cpp, stylegan2.cpp, clip.cpp, gpt2_host.cpp, biggan.cpp)
 // ------------------------------------------------------------------------------------
 #define REQUIRE(cond, code, msg)          \
     do {                                  \
@@ -301,9 +301,28 @@ void collect_profile(glass_engine* e);
 void run_conv(glass_engine* e, const ConvParams& p, const char* tag, double flops, double bytes);
 void run_gemm(glass_engine* e, const GemmParams& p, const char* tag);
 ConvParams conv_defaults();
+// dry run: the kernel `launch` would run `p` on, or nullptr where it refuses the layer; nothing is launched
+template <typename Launcher>
+inline const char* would_run(Launcher launch, ConvParams p) {
+    p.dry_run = 1;
+    return launch(p, nullptr);
+}
 // out[M][N] = a[M][K] x w[N][K]^T (+ bias), written as `mode` says (common.h GemmParams: fp16 to out16 for modes 0 / 1, fp32 to out32 above)
 GemmParams gemm_params(const half_t* a, const half_t* w, int M, int N, int K, const float* bias, int mode, half_t* out16, float* out32,
                        int cand_rows);
+
+// ---- StyleGAN2 (stylegan2.cpp) ----
+#pragma GCC visibility push(hidden)   // called from engine.cpp only: the library's exported symbols stay what they were
+int finalize_generator(glass_engine* e);
+int finalize_discriminator(glass_engine* e);
+int upload_noise(glass_engine* e, int P, int generation, int first_mb, const glass_noise* noise);
+void run_styles(glass_engine* e, int P);
+void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, const half_t* x, long long xbs, half_t* const pp[2],
+                  const float* yprev, float* const yb[2], const half_t** x_out, const float** y_out);
+void run_fromrgb(glass_engine* e, int B, const float* y, half_t* X);
+half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* X, half_t* const bufs[5], const float* rgb_y = nullptr);
+void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch);
+#pragma GCC visibility pop
 
 // ---- CLIP (clip.cpp) ----
 int clip_patch_k(const glass_config& c);     // the patch-embedding GEMM's K: 3 patch^2 padded to gemm_tiled's K step

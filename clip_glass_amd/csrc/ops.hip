@@ -68,8 +68,7 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     OPREQ(d->out_scale > 0.f, "out_scale must be positive (the epilogues fold it into the activation constants: max(v k1, v k2))");
     GLASS_HIP(hipSetDevice(device));
     Dev dv;
-    ConvParams p;
-    memset(&p, 0, sizeof p);
+    ConvParams p = conv_defaults();
     const size_t xin = (size_t)(d->broadcast_x ? 1 : d->B) * d->H * d->W * d->Cin;
     p.x = dv.up16(d->x, xin);
     p.x_bstride = d->broadcast_x ? 0 : (long long)d->H * d->W * d->Cin;

@@ -1,0 +1,620 @@
+// stylegan2.cpp — StyleGAN2 host code: weights -> device layouts, and the launches of the mapping / style chain, the synthesis blocks
+// and the discriminator.  The pass that strings them together: engine.cpp run_pass.
+#include "engine.h"
+
+#include <math.h>
+#include <stdio.h>
+
+int finalize_generator(glass_engine* e) {
+    const glass_config& c = e->cfg;
+    const int L = c.latent_size;
+    char nm[256];
+    // mapping network (stylegan2/models.py:566-588): weight coef = lr_mul/sqrt(fan_in), bias coef = lr_mul
+    const float lr = 0.01f;
+    for (int i = 0; i < c.mapping_layers; ++i) {
+        snprintf(nm, sizeof nm, "G_mapping.main.%d.layer.weight", i);
+        GET(w, nm);
+        REQUIRE(numel(w) == (size_t)L * L, GLASS_ERR_ARG, std::string("bad shape: ") + nm);
+        snprintf(nm, sizeof nm, "G_mapping.main.%d.bias", i);
+        GET(b, nm);
+        REQUIRE(numel(b) == (size_t)L, GLASS_ERR_ARG, std::string("bad shape: ") + nm);
+        float *dw, *db;
+        int rc = upload(e, &dw, transposed(w->data.data(), L, L, lr / sqrtf((float)L)));
+        if (rc) return rc;
+        rc = upload(e, &db, scaled(b->data.data(), L, lr));
+        if (rc) return rc;
+        e->map_wt.push_back(dw);
+        e->map_b.push_back(db);
+    }
+    // layer list (stylegan2/models.py:812-896, 969-1014)
+    int style_idx = 0, soff = 0, dsoff = 0, noise_idx = 0;
+    for (int b = 0; b < c.n_blocks; ++b) {
+        const int res = 4 << b;
+        const int nl = b == 0 ? 1 : 2;
+        for (int l = 0; l < nl; ++l) {
+            GConv g;
+            g.up = (b > 0 && l == 0);
+            g.cin = (b == 0) ? c.channels[0] : (l == 0 ? c.channels[b - 1] : c.channels[b]);
+            g.cout = c.channels[b];
+            g.res_out = res;
+            g.res_in = g.up ? res / 2 : res;
+            g.style_idx = style_idx++;
+            g.style_off = soff;
+            soff += g.cin;
+            g.ds_off = dsoff;
+            dsoff += g.cout;
+            g.noise_idx = noise_idx++;
+            e->gconv.push_back(g);
+        }
+        GRgb r;
+        r.cin = c.channels[b];
+        r.res = res;
+        r.style_idx = style_idx++;
+        r.style_off = soff;
+        soff += r.cin;
+        e->grgb.push_back(r);
+    }
+    e->n_style = style_idx;
+    e->S_total = soff;
+    e->D_total = dsoff;
+    // style affines, concatenated: s = w @ (A/sqrt(L))^T + b   (modules.py:879-894, 936)
+    std::vector<float> swt((size_t)L * e->S_total), sb((size_t)e->S_total);
+    e->style_off.assign(e->n_style, 0);
+    e->style_len.assign(e->n_style, 0);
+    auto add_style = [&](const std::string& prefix, int sidx, int off, int cin) -> int {
+        GET(A, prefix + ".dense.layer.weight");
+        GET(Ab, prefix + ".dense.bias");
+        REQUIRE(numel(A) == (size_t)cin * L && numel(Ab) == (size_t)cin, GLASS_ERR_ARG, "bad style shape: " + prefix);
+        const float coef = 1.0f / sqrtf((float)L);
+        for (int i = 0; i < cin; ++i) {
+            for (int k = 0; k < L; ++k) swt[(size_t)k * e->S_total + off + i] = A->data[(size_t)i * L + k] * coef;
+            sb[off + i] = Ab->data[i];
+        }
+        e->style_off[sidx] = off;
+        e->style_len[sidx] = cin;
+        return GLASS_OK;
+    };
+    {
+        GET(cst, "G_synthesis.const");
+        const int C0 = c.channels[0];
+        REQUIRE(numel(cst) == (size_t)C0 * 16, GLASS_ERR_ARG, "bad shape: G_synthesis.const");
+        std::vector<_Float16> h((size_t)16 * C0);
+        for (int ch = 0; ch < C0; ++ch)
+            for (int p = 0; p < 16; ++p) h[(size_t)p * C0 + ch] = (_Float16)cst->data[(size_t)ch * 16 + p];
+        int rc = upload(e, &e->g_const, h);
+        if (rc) return rc;
+    }
+    int gi = 0;
+    for (int b = 0; b < c.n_blocks; ++b) {
+        const int nl = b == 0 ? 1 : 2;
+        for (int l = 0; l < nl; ++l, ++gi) {
+            GConv& g = e->gconv[gi];
+            snprintf(nm, sizeof nm, "G_synthesis.conv_blocks.%d.conv_block.%d", b, l);
+            const std::string p = nm;
+            GET(W, p + ".layer.layer.weight");
+            GET(bias, p + ".bias");
+            GET(ns, p + ".layer.weight");
+            REQUIRE(numel(W) == (size_t)g.cout * g.cin * 9 && numel(bias) == (size_t)g.cout && numel(ns) == 1,
+                    GLASS_ERR_ARG, "bad conv shape: " + p);
+            int rc = add_style(p + ".layer.layer", g.style_idx, g.style_off, g.cin);
+            if (rc) return rc;
+            std::vector<_Float16> packed;
+            if (g.up) glass_fold_upconv(W->data.data(), g.cout, g.cin, packed);
+            else glass_pack_conv(W->data.data(), g.cout, g.cin, 3, g.cin, packed);
+            rc = upload(e, &g.w, packed);
+            if (rc) return rc;
+            if (g.up) {
+                glass_pack_conv(W->data.data(), g.cout, g.cin, 3, g.cin, packed);
+                rc = upload(e, &g.w_up, packed);
+                if (rc) return rc;
+            }
+            // demod table: Wsq[i][o] = sum_taps (W*coef)^2   (modules.py:943-954, SURVEY 8a note 1)
+            std::vector<float> wsq((size_t)g.cin * g.cout);
+            const float coef2 = 1.0f / ((float)g.cin * 9.f);
+            for (int o = 0; o < g.cout; ++o)
+                for (int i = 0; i < g.cin; ++i) {
+                    const float* w = W->data.data() + ((size_t)o * g.cin + i) * 9;
+                    float s = 0.f;
+                    for (int t = 0; t < 9; ++t) s += w[t] * w[t];
+                    wsq[(size_t)i * g.cout + o] = s * coef2;
+                }
+            rc = upload(e, &g.wsq, wsq);
+            if (rc) return rc;
+            rc = upload(e, &g.bias, bias->data);
+            if (rc) return rc;
+            g.noise_strength = ns->data[0];
+        }
+        GRgb& r = e->grgb[b];
+        snprintf(nm, sizeof nm, "G_synthesis.to_data_layers.%d", b);
+        const std::string p = nm;
+        GET(W, p + ".layer.weight");
+        GET(bias, p + ".bias");
+        REQUIRE(numel(W) == (size_t)3 * r.cin && numel(bias) == 3, GLASS_ERR_ARG, "bad toRGB shape: " + p);
+        int rc = add_style(p + ".layer", r.style_idx, r.style_off, r.cin);
+        if (rc) return rc;
+        rc = upload(e, &r.w, scaled(W->data.data(), (size_t)3 * r.cin, 1.0f / sqrtf((float)r.cin)));
+        if (rc) return rc;
+        rc = upload(e, &r.bias, bias->data);
+        if (rc) return rc;
+    }
+    int rc = upload(e, &e->style_wt, swt);
+    if (rc) return rc;
+    rc = upload(e, &e->style_b, sb);
+    if (rc) return rc;
+    rc = upload(e, &e->d_style_off, e->style_off);
+    if (rc) return rc;
+    rc = upload(e, &e->d_style_len, e->style_len);
+    return rc;
+}
+
+int finalize_discriminator(glass_engine* e) {
+    const glass_config& c = e->cfg;
+    const int n = c.n_blocks;
+    char nm[256];
+    auto chD = [&](int i) { return c.channels[n - 1 - i]; };  // D order: first (full res) -> last (4x4)
+    {
+        GET(W, "D.from_data_layers.0.layer.weight");
+        GET(b, "D.from_data_layers.0.bias");
+        REQUIRE(numel(W) == (size_t)chD(0) * 3 && numel(b) == (size_t)chD(0), GLASS_ERR_ARG, "bad fromRGB shape");
+        int rc = upload(e, &e->d_frgb_w, scaled(W->data.data(), numel(W), 1.0f / sqrtf(3.f)));
+        if (rc) return rc;
+        rc = upload(e, &e->d_frgb_b, b->data);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < n - 1; ++i) {
+        DBlock d;
+        d.cin = chD(i);
+        d.cout = chD(i + 1);
+        d.res = e->R >> i;
+        snprintf(nm, sizeof nm, "D.conv_blocks.%d", i);
+        const std::string p = nm;
+        GET(W0, p + ".conv_block.0.layer.weight");
+        GET(B0, p + ".conv_block.0.bias");
+        GET(W1, p + ".conv_block.1.layer.weight");
+        GET(B1, p + ".conv_block.1.bias");
+        GET(WS, p + ".projection.weight");
+        REQUIRE(numel(W0) == (size_t)d.cin * d.cin * 9 && numel(W1) == (size_t)d.cout * d.cin * 9 &&
+                    numel(WS) == (size_t)d.cout * d.cin && numel(B0) == (size_t)d.cin && numel(B1) == (size_t)d.cout,
+                GLASS_ERR_ARG, "bad D block shape: " + p);
+        std::vector<_Float16> pk;
+        glass_pack_conv(W0->data.data(), d.cin, d.cin, 3, d.cin, pk);
+        int rc = upload(e, &d.w0, pk);
+        if (rc) return rc;
+        glass_pack_conv(W1->data.data(), d.cout, d.cin, 3, d.cin, pk);
+        rc = upload(e, &d.w1, pk);
+        if (rc) return rc;
+        glass_pack_conv(WS->data.data(), d.cout, d.cin, 1, d.cin, pk);
+        rc = upload(e, &d.wskip, pk);
+        if (rc) return rc;
+        rc = upload(e, &d.b0, B0->data);
+        if (rc) return rc;
+        rc = upload(e, &d.b1, B1->data);
+        if (rc) return rc;
+        e->dblk.push_back(d);
+    }
+    const int CL = chD(n - 1);
+    snprintf(nm, sizeof nm, "D.conv_blocks.%d.1.conv_block.0", n - 1);
+    const std::string p = nm;
+    GET(WF, p + ".layer.weight");
+    GET(BF, p + ".bias");
+    REQUIRE(numel(WF) == (size_t)CL * (CL + 1) * 9 && numel(BF) == (size_t)CL, GLASS_ERR_ARG, "bad D final conv shape");
+    e->d_final_cpad = ((CL + 1 + 15) / 16) * 16;
+    std::vector<_Float16> pk;
+    glass_pack_conv(WF->data.data(), CL, CL + 1, 3, e->d_final_cpad, pk);
+    int rc = upload(e, &e->d_final_w, pk);
+    if (rc) return rc;
+    rc = upload(e, &e->d_final_b, BF->data);
+    if (rc) return rc;
+    GET(W0, "D.dense.0.layer.weight");
+    GET(B0, "D.dense.0.bias");
+    GET(W1, "D.dense.1.layer.weight");
+    GET(B1, "D.dense.1.bias");
+    REQUIRE(numel(W0) == (size_t)CL * CL * 16 && numel(B0) == (size_t)CL && numel(W1) == (size_t)CL && numel(B1) == 1,
+            GLASS_ERR_ARG, "bad D dense shape");
+    // x.view(B,-1) flattens NCHW (models.py:1224): column c*16+p ; our activations are [p][c].
+    std::vector<_Float16> d0((size_t)CL * CL * 16);
+    const float coef0 = 1.0f / sqrtf((float)CL * 16.f);
+    for (int o = 0; o < CL; ++o)
+        for (int ch = 0; ch < CL; ++ch)
+            for (int px = 0; px < 16; ++px)
+                d0[(size_t)o * CL * 16 + (size_t)px * CL + ch] = (_Float16)(W0->data[(size_t)o * CL * 16 + ch * 16 + px] * coef0);
+    rc = upload(e, &e->d_dense0_w, d0);
+    if (rc) return rc;
+    rc = upload(e, &e->d_dense0_b, B0->data);
+    if (rc) return rc;
+    rc = upload(e, &e->d_dense1_wt, transposed(W1->data.data(), 1, CL, 1.0f / sqrtf((float)CL)));
+    if (rc) return rc;
+    return upload(e, &e->d_dense1_b, B1->data);
+}
+
+int upload_noise(glass_engine* e, int P, int generation, int first_mb, const glass_noise* noise) {
+    const glass_config& c = e->cfg;
+    const int n_mb = P / c.batch_size;
+    if (c.noise_mode == 1) {
+        for (size_t l = 0; l < e->gconv.size(); ++l) {
+            const int hw = e->gconv[l].res_out * e->gconv[l].res_out;
+            Prof pr(e, "noise", 0, (double)n_mb * hw * 4);
+            launch_noise(e->d_noise[l], n_mb, hw, (uint32_t)l, (uint32_t)first_mb, (uint32_t)generation, c.noise_seed,
+                         e->cur);
+        }
+    } else if (c.noise_mode == 2) {
+        REQUIRE(noise && noise->planes, GLASS_ERR_ARG, "noise_mode 2 requires caller-provided noise planes");
+        REQUIRE(noise->n_layers == (int)e->gconv.size() && noise->n_minibatches >= n_mb, GLASS_ERR_ARG,
+                "noise: wrong number of layers / minibatches");
+        for (int m = 0; m < n_mb; ++m)
+            for (size_t l = 0; l < e->gconv.size(); ++l) {
+                const size_t hw = (size_t)e->gconv[l].res_out * e->gconv[l].res_out;
+                const float* src = noise->planes[(size_t)m * noise->n_layers + l];
+                REQUIRE(src, GLASS_ERR_ARG, "noise: null plane");
+                GLASS_HIP(hipMemcpyAsync(e->d_noise[l] + (size_t)m * hw, src, hw * sizeof(float), hipMemcpyHostToDevice,
+                                         e->cur));
+            }
+        GLASS_HIP(hipStreamSynchronize(e->cur));  // caller's planes may be freed after return
+    }
+    return GLASS_OK;
+}
+
+void run_styles(glass_engine* e, int P) {
+    const glass_config& c = e->cfg;
+    const int L = c.latent_size;
+    {
+        Prof pr(e, "mapping", 2.0 * P * L * L * c.mapping_layers, 4.0 * L * L * c.mapping_layers);
+        if (c.mapping_layers < 1 ||
+            !launch_mapping_fused(e->d_z, e->d_w0, P, L, 1e-8f, e->map_wt.data(), e->map_b.data(), c.mapping_layers, e->cur)) {
+            launch_pixelnorm(e->d_z, e->d_w0, P, L, 1e-8f, e->cur);
+            float *a = e->d_w0, *b = e->d_w1;
+            for (int i = 0; i < c.mapping_layers; ++i) {
+                if (L % 64 == 0 && L <= 768) launch_dense_splitk(a, L, P, L, e->map_wt[i], L, e->map_b[i], b, L, 1, e->cur);
+                else launch_dense(a, L, P, L, e->map_wt[i], L, e->map_b[i], b, L, 0, 1, nullptr, 0, e->cur);
+                std::swap(a, b);
+            }
+            if (a != e->d_w0)  // result must end in d_w0
+                hipMemcpyAsync(e->d_w0, a, (size_t)P * L * sizeof(float), hipMemcpyDeviceToDevice, e->cur);
+        }
+    }
+    {
+        Prof pr(e, "styles", 2.0 * P * L * e->S_total, 4.0 * L * e->S_total);
+        launch_dense(e->d_w0, L, P, L, e->style_wt, e->S_total, e->style_b, e->d_s, e->S_total, 0, 0, nullptr, 0,
+                     e->cur);
+        launch_style_norm(e->d_s, e->S_total, P, e->n_style, e->d_style_off, e->d_style_len, e->d_smax, e->d_epsrow,
+                          1e-8f, e->cur);
+        launch_bg_to_half(e->d_s, e->d_s16, (long long)P * e->S_total, e->cur);   // fp16 table for the LDS-tiled kernels
+    }
+    {
+        Prof pr(e, "demod", 0, 0);
+        launch_dense_multi((const DenseDesc*)e->d_demod_desc, (int)e->gconv.size(), e->demod_max_n, P, 1, 2, e->cur);
+    }
+    {
+        Prof pr(e, "premod_weights", 0, 0);
+        for (auto& g : e->gconv)
+            if (g.premod)
+                launch_modulate_weights(g.up ? g.w_up : g.w, g.welems, g.cin, g.cout, e->d_s + g.style_off, e->S_total,
+                                        e->d_dscale + g.ds_off, e->D_total, P, g.wm, e->cur);
+    }
+}
+
+static ConvParams g_conv_params(glass_engine* e, const GConv& g, int c0, int B, const half_t* x, long long xbs, half_t* out) {
+    const glass_config& c = e->cfg;
+    ConvParams p = conv_defaults();
+    p.x = x; p.x_bstride = xbs; p.B = B; p.H = p.W = g.res_in; p.Cin = g.cin; p.Hc = p.Wc = g.res_in; p.KS = 3; p.pad = 1;
+    p.w = g.w; p.w_up = g.w_up; p.Cout = g.cout; p.up = g.up; p.Neff = g.up ? 4 * g.cout : g.cout; p.Ho = p.Wo = g.res_out;
+    p.sn = e->d_s + (size_t)c0 * e->S_total + g.style_off; p.sn16 = e->d_s16 + (size_t)c0 * e->S_total + g.style_off; p.sn_stride = e->S_total;
+    p.dscale = e->d_dscale + (size_t)c0 * e->D_total + g.ds_off; p.ds_stride = e->D_total;
+    if (c.noise_mode != 0) { p.noise = e->d_noise[g.noise_idx] + (size_t)(c0 / c.batch_size) * g.res_out * g.res_out; p.noise_strength = g.noise_strength; }
+    p.batch_size = c.batch_size; p.bias = g.bias; p.act = 1; p.y = out;
+    if (g.premod) {   // weights already carry style and demod of each sample
+        p.sn = nullptr; p.sn16 = nullptr; p.dscale = nullptr; p.w_bstride = g.welems;
+        if (g.up) { p.w_up = g.wm + (size_t)c0 * g.welems; p.w = nullptr; }
+        else p.w = g.wm + (size_t)c0 * g.welems;
+    }
+    return p;
+}
+
+struct GCost { char tag[48]; double flops, bytes; };
+static GCost g_conv_cost(const GConv& g, int B) {
+    GCost k;
+    k.flops = 2.0 * B * (double)g.res_in * g.res_in * 9.0 * g.cin * g.cout;  // reference count
+    k.bytes = 2.0 * B * ((double)g.res_in * g.res_in * g.cin + (double)g.res_out * g.res_out * g.cout) + 2.0 * 9 * g.cin * (g.up ? 4 * g.cout : g.cout);
+    snprintf(k.tag, sizeof k.tag, "G.%s.r%d.%dx%d", g.up ? "upconv" : "conv", g.res_out, g.cin, g.cout);
+    return k;
+}
+
+// upconv -> conv link: the up-conv's only consumer is the block's second conv.
+//   post_style: where the fused up-conv kernel runs and that conv modulates on the activation side, its style is applied once, to the
+//     up-conv's output.
+//   planar: conv_wreg reads its input one 32-channel chunk at a time, so the up-conv writes the map chunk-planar for it (common.h
+//     x_planar8) — where the up-conv instance that can runs and the conv has no activation-side style.  (A launcher that does not read the
+//     layout refuses the layer: run_conv reports it.)
+struct UpLink { bool post_style = false, planar = false; };
+static UpLink up_link(const GConv& g, const GConv& next, const ConvParams& p) {
+    UpLink k;
+    k.post_style = !next.premod && would_run(launch_upconv_fused, p);
+    if ((k.post_style || next.premod) && conv_wreg_supported(next.cin, next.cout, g.res_out, g.res_out)) {
+        ConvParams q = p;
+        q.y_planar8 = 1;
+        k.planar = would_run(launch_upconv_fused, q);
+    }
+    return k;
+}
+
+// toRGB of the block fused into its last conv (common.h).
+//   stream_only: the network's LAST conv feeds toRGB only: conv_stream<torgb> writes just the skip image and the 64-byte-per-pixel feature
+//     map never goes to HBM.
+//   epilogue: up to 128 channels (one n tile per pixel) the conv's epilogue writes the skip image itself; the block still stores its map
+//     (the next block reads it) but toRGB no longer re-reads it.
+//   partial: blocks wider than that (several 128-wide n tiles per pixel): every n tile's conv epilogue writes the toRGB partial sum of its
+//     channels, a 3-value-per-pixel pass adds them (+ bias + the upsampled previous image) — the separate toRGB pass read the whole feature
+//     map again (0.19 + 0.09 + 0.03 ms at r128 / r64 / r32).
+enum class ToRgb { separate, stream_only, epilogue, partial };
+
+static half_t* trgb_tab(glass_engine* e, int c0, ToRgb form) { return e->d_trgb_tab + (size_t)c0 * 32 * (form == ToRgb::partial ? 512 : 128); }
+static ConvParams torgb_conv_params(glass_engine* e, ConvParams q, const GRgb& r, int c0, ToRgb form, const float* yprev, float* yout) {
+    q.trgb_w = r.w; q.trgb_b = r.bias;
+    q.trgb_sn = e->d_s + (size_t)c0 * e->S_total + r.style_off; q.trgb_sn_stride = e->S_total;
+    q.trgb_smax = e->d_smax + (size_t)c0 * e->n_style + r.style_idx; q.trgb_smax_stride = e->n_style;
+    if (form == ToRgb::partial) q.trgb_part = e->d_trgb_part;
+    else { q.trgb_yprev = yprev; q.trgb_yout = yout; }
+    if (form == ToRgb::stream_only) q.y = nullptr;
+    else q.trgb_tab = trgb_tab(e, c0, form);
+    return q;
+}
+static void run_trgb_tables(glass_engine* e, const ConvParams& q, half_t* tab) {
+    launch_trgb_tables(q.trgb_w, q.trgb_sn, q.trgb_sn_stride, q.trgb_smax, q.trgb_smax_stride, q.B, q.Cout, tab, e->cur);
+}
+static const char* launch_torgb_conv(const ConvParams& q, hipStream_t st) {
+    const char* k = launch_conv_glds(q, st);
+    return (k || q.trgb_part) ? k : launch_conv_tiled(q, st);
+}
+static ToRgb choose_torgb(glass_engine* e, const ConvParams& p, const GRgb& r, int c0, bool last_block, const float* yprev, float* yout) {
+    if (last_block && conv_stream_applies(torgb_conv_params(e, p, r, c0, ToRgb::stream_only, yprev, yout))) return ToRgb::stream_only;
+    const bool wide = r.cin > 128;
+    if (wide && !(e->d_trgb_part && r.cin % 128 == 0 && r.cin <= 512)) return ToRgb::separate;
+    const ToRgb form = wide ? ToRgb::partial : ToRgb::epilogue;
+    return would_run(launch_torgb_conv, torgb_conv_params(e, p, r, c0, form, yprev, yout)) ? form : ToRgb::separate;
+}
+
+// ------------------------------------------------------------------------------------
+// Synthesis blocks [b_lo, b_hi) for candidates [c0, c0+B).  Low-resolution blocks
+// (res <= low_res) run once for the whole population (launch-/latency-bound otherwise),
+// high-resolution blocks run per chunk so the working set stays near the caches.
+//   x/xbs: input feature map (bstride 0 = the learned const); pp[2]: ping-pong outputs;
+//   yprev: skip image of the previous block (nullptr for block 0); yb[2]: skip ping-pong.
+// Returns the final feature map / skip image through the out parameters.
+// ------------------------------------------------------------------------------------
+void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, const half_t* x, long long xbs, half_t* const pp[2],
+                  const float* yprev, float* const yb[2], const half_t** x_out, const float** y_out) {
+    int yi = 0;
+    for (int b = b_lo; b < b_hi; ++b) {
+        UpLink link;
+        if (b > 0) {
+            const GConv &g = e->gconv[2 * b - 1], &next = e->gconv[2 * b];
+            half_t* out = pp[(x == pp[0]) ? 1 : 0];
+            ConvParams p = g_conv_params(e, g, c0, B, x, xbs, out);
+            link = up_link(g, next, p);
+            if (link.post_style) { p.post_scale16 = e->d_s16 + (size_t)c0 * e->S_total + next.style_off; p.post_stride = e->S_total; }
+            p.y_planar8 = link.planar;
+            const GCost k = g_conv_cost(g, B);
+            run_conv(e, p, k.tag, k.flops, k.bytes);
+            x = out;
+            xbs = (long long)g.res_out * g.res_out * g.cout;
+        }
+        const GConv& g = e->gconv[2 * b];
+        const GRgb& r = e->grgb[b];
+        half_t* out = pp[(x == pp[0]) ? 1 : 0];
+        ConvParams p = g_conv_params(e, g, c0, B, x, xbs, out);
+        if (link.post_style) { p.sn = nullptr; p.sn16 = nullptr; }
+        p.x_planar8 = link.planar;
+        const GCost k = g_conv_cost(g, B);
+        const double px = B * (double)r.res * r.res, tflops = k.flops + 2.0 * px * 3 * r.cin, yup = b ? 3.0 : 0.0;
+        const ToRgb form = choose_torgb(e, p, r, c0, b == e->cfg.n_blocks - 1, yprev, yb[yi]);
+        const ConvParams q = torgb_conv_params(e, p, r, c0, form, yprev, yb[yi]);
+        x = out;
+        xbs = (long long)g.res_out * g.res_out * g.cout;
+        switch (form) {
+        case ToRgb::stream_only: {
+            Prof pr(e, k.tag, tflops, 2.0 * B * (double)g.res_in * g.res_in * g.cin + px * (12.0 + yup));
+            pr.ran(k.tag, launch_conv_stream(q, e->cur));
+            x = nullptr;   // not produced
+            break;
+        }
+        case ToRgb::epilogue: {
+            Prof pr(e, k.tag, tflops, k.bytes + px * (12.0 + yup));
+            run_trgb_tables(e, q, trgb_tab(e, c0, form));
+            pr.ran(k.tag, launch_torgb_conv(q, e->cur));
+            break;
+        }
+        case ToRgb::partial: {
+            Prof pr(e, k.tag, tflops, k.bytes + px * (12.0 * (1 + 2 * (r.cin / 128)) + yup));
+            run_trgb_tables(e, q, trgb_tab(e, c0, form));
+            const char* kernel = launch_torgb_conv(q, e->cur);
+            launch_trgb_finish(e->d_trgb_part, r.cin / 128, B, r.res, r.bias, yprev, yb[yi], e->cur);
+            pr.ran(k.tag, kernel);
+            break;
+        }
+        case ToRgb::separate: {
+            run_conv(e, p, k.tag, k.flops, k.bytes);
+            char tag[48];
+            snprintf(tag, sizeof tag, "G.torgb.r%d", r.res);
+            Prof pr(e, tag, 2.0 * px * 3 * r.cin, px * (2.0 * r.cin + 12.0 + yup));
+            const bool ok = launch_torgb(x, B, r.res, r.res, r.cin, r.w, r.bias, q.trgb_sn, e->S_total, q.trgb_smax, e->n_style, yprev, yb[yi], e->cur);
+            if (!ok && e->launch_error.empty()) e->launch_error = std::string("toRGB width not instantiated: ") + tag;
+            break;
+        }
+        }
+        yprev = yb[yi];
+        yi ^= 1;
+    }
+    *x_out = x;
+    *y_out = yprev;
+}
+
+void run_fromrgb(glass_engine* e, int B, const float* y, half_t* X) {
+    const glass_config& c = e->cfg;
+    const int n = c.n_blocks;
+    Prof pr(e, "D.fromrgb", 2.0 * B * (double)e->R * e->R * 3 * c.channels[n - 1],
+            B * (double)e->R * e->R * (12.0 + 2.0 * c.channels[n - 1]));
+    launch_fromrgb(y, B, e->R, c.channels[n - 1], e->d_frgb_w, e->d_frgb_b, X, e->cur);
+}
+
+// the whole block from the skip image in one kernel (conv_d0.hip): neither x nor h reaches HBM.  false: the block does not qualify
+static bool run_d_block0(glass_engine* e, int B, const DBlock& d, const float* rgb_y, half_t* O, bool planar) {
+    char tag[64];
+    const int r = d.res, r2 = r / 2;
+    snprintf(tag, sizeof tag, "D.block0.r%d.%dx%dx%d", r, d.cin, d.cin, d.cout);
+    const double px = (double)B * r * r, px2 = (double)B * r2 * r2;
+    Prof pr(e, tag, 2.0 * px * (9.0 * d.cin * d.cin + 3.0 * d.cin) + 2.0 * px2 * 10.0 * d.cin * d.cout, px * 12.0 + px2 * 2.0 * d.cout);
+    const char* k = launch_dblock0(rgb_y, e->d_frgb_w, e->d_frgb_b, d.w0, d.b0, d.w1, d.wskip, d.b1, O, B, r, d.cin, d.cout, e->cur, planar);
+    if (k) pr.ran(tag, k);
+    else pr.drop();
+    return k != nullptr;
+}
+
+// First half of a block: h = conv0(x) in Hb.  Returns whether the launch also wrote XS, the blur-down of x that the skip branch reads.
+// rgb_y != nullptr: X has NOT been produced yet — the conv builds the fromRGB map from the skip image on the fly and writes it to X
+// (or, where the fused second half follows, its blur-down to XS) as a side output (conv_stream<fromrgb>), or, where that kernel does not
+// apply, the separate fromRGB pass runs first.
+static bool run_d_conv0(glass_engine* e, int B, const DBlock& d, half_t* X, bool x_planar, const float* rgb_y, half_t* Hb, half_t* XS) {
+    char tag[64];
+    const int r = d.res;
+    ConvParams p = conv_defaults();
+    p.x = X; p.x_bstride = (long long)r * r * d.cin; p.B = B; p.H = p.W = r; p.Cin = d.cin;
+    p.Hc = p.Wc = r; p.KS = 3; p.pad = 1; p.w = d.w0; p.Cout = p.Neff = d.cin; p.Ho = p.Wo = r;
+    p.bias = d.b0; p.act = 1; p.y = Hb;
+    p.x_planar8 = x_planar;
+    if (rgb_y) {
+        const bool fuse_down = conv_down_supported(r, d.cin, d.cout);
+        ConvParams q = p;
+        q.rgb_y = rgb_y; q.rgb_w = e->d_frgb_w; q.rgb_b = e->d_frgb_b;
+        q.rgb_x_out = fuse_down ? nullptr : X;       // the fused second half reads the down-sampled skip input only
+        q.rgb_xs_out = fuse_down ? XS : nullptr;
+        snprintf(tag, sizeof tag, "D.fromrgb+conv0.r%d.%dx%d", r, d.cin, d.cin);
+        const double px = (double)B * r * r;
+        Prof pr(e, tag, 2.0 * px * (9.0 * d.cin * d.cin + 3.0 * d.cin), px * (12.0 + 2.0 * d.cin + (fuse_down ? 0.5 : 2.0) * d.cin));
+        if (const char* k = launch_conv_stream(q, e->cur)) {
+            pr.ran(tag, k);
+            return fuse_down;
+        }
+        pr.drop();
+        run_fromrgb(e, B, rgb_y, X);
+    }
+    ConvParams qx = p;
+    qx.xs_out = XS;
+    const bool have_xs = would_run(launch_conv_glds, qx) || would_run(launch_conv_tiled, qx);   // the skip branch's blur-down rides in the first conv
+    snprintf(tag, sizeof tag, "D.conv0.r%d.%dx%d", r, d.cin, d.cin);
+    run_conv(e, have_xs ? qx : p, tag, 2.0 * B * (double)r * r * 9 * d.cin * d.cin, 4.0 * B * (double)r * r * d.cin + (have_xs ? 0.5 * B * (double)r * r * d.cin : 0.0));
+    if (!have_xs && x_planar && e->launch_error.empty()) e->launch_error = std::string("chunk-planar block input without the fused blur-down: ") + tag;
+    return have_xs;
+}
+
+// Second half of a block: out = (lrelu(conv1 stride 2 (blur(h)) + b1) * sqrt2 + skip(XS)) / sqrt2 in O, from h in Hb and (have_xs) XS
+static void run_d_conv1(glass_engine* e, int B, const DBlock& d, const half_t* X, bool have_xs, half_t* Hb, half_t* HB, half_t* XS, half_t* S,
+                        half_t* O) {
+    char tag[64];
+    const int r = d.res, r2 = r / 2;
+    if (!have_xs) {
+        snprintf(tag, sizeof tag, "D.blurdown.r%d", r);
+        Prof pr(e, tag, 2.0 * B * (double)r2 * r2 * d.cin * 16, 2.5 * B * (double)r * r * d.cin);
+        launch_blur_down(X, B, r, r, d.cin, XS, e->cur);
+    }
+    if (conv_down_supported(r, d.cin, d.cout)) {   // blur + skip + stride-2 conv + merge as one kernel
+        snprintf(tag, sizeof tag, "D.down.r%d.%dx%d", r2, d.cin, d.cout);
+        const double px2 = (double)B * r2 * r2;
+        Prof pr(e, tag, 2.0 * px2 * (9.0 + 1.0) * d.cin * d.cout, 2.0 * (B * (double)r * r * d.cin + px2 * (d.cin + d.cout)));
+        if (const char* k = launch_conv_down(Hb, XS, d.w1, d.wskip, d.b1, O, B, r, d.cin, d.cout, e->cur)) {
+            pr.ran(tag, k);
+            return;
+        }
+        pr.drop();
+    }
+    ConvParams q = conv_defaults();
+    q.x = HB; q.x_bstride = (long long)(r + 1) * (r + 1) * d.cin; q.B = B; q.H = q.W = r + 1; q.Cin = d.cin;
+    q.Hc = q.Wc = r2; q.KS = 3; q.stride = 2; q.pad = 0; q.w = d.w1; q.Cout = q.Neff = d.cout; q.Ho = q.Wo = r2;
+    q.bias = d.b1; q.act = 1; q.out_scale = 0.70710678118654752440f; q.y = O;
+    // skip branch as extra K stages of the stride-2 conv (conv_s2, or conv_tiled<3,2,4,N,skip>) where that kernel applies
+    ConvParams qs = q;
+    qs.skip_x = XS; qs.skip_w = d.wskip; qs.x_planar32 = 1;
+    // blur -> conv_s2 link: that kernel stages its input one 32-channel chunk per K step, so (where it runs) the blur writes 32-channel planes
+    const auto conv_s2 = +[](const ConvParams& p, hipStream_t st) { return launch_conv_s2(p, st); };
+    const bool hb_planar = blur_pad2_planar32_ok(d.cin) && would_run(conv_s2, qs);
+    qs.x_planar32 = hb_planar;
+    {
+        snprintf(tag, sizeof tag, "D.blur.r%d", r);
+        Prof pr(e, tag, 2.0 * B * (double)(r + 1) * (r + 1) * d.cin * 16, 4.0 * B * (double)r * r * d.cin);
+        launch_blur_pad2(Hb, B, r, r, d.cin, HB, e->cur, hb_planar);
+    }
+    snprintf(tag, sizeof tag, "D.conv1.r%d.%dx%d", r2, d.cin, d.cout);
+    const double f1 = 2.0 * B * (double)r2 * r2 * 9 * d.cin * d.cout, fs = 2.0 * B * (double)r2 * r2 * d.cin * d.cout;
+    const auto fused = hb_planar ? conv_s2 : launch_conv_tiled;
+    if (hb_planar || would_run(launch_conv_tiled, qs)) {
+        Prof pr(e, tag, f1 + fs, 2.0 * B * ((double)(r + 1) * (r + 1) * d.cin + (double)r2 * r2 * (d.cin + d.cout)));
+        pr.ran(tag, fused(qs, e->cur));
+        return;
+    }
+    ConvParams s = conv_defaults();
+    s.x = XS; s.x_bstride = (long long)r2 * r2 * d.cin; s.B = B; s.H = s.W = r2; s.Cin = d.cin;
+    s.Hc = s.Wc = r2; s.KS = 1; s.pad = 0; s.w = d.wskip; s.Cout = s.Neff = d.cout; s.Ho = s.Wo = r2; s.y = S;
+    char stag[64];
+    snprintf(stag, sizeof stag, "D.skip.r%d.%dx%d", r2, d.cin, d.cout);
+    run_conv(e, s, stag, fs, 2.0 * B * (double)r2 * r2 * (d.cin + d.cout));
+    q.res = S;
+    run_conv(e, q, tag, f1, 2.0 * B * ((double)(r + 1) * (r + 1) * d.cin + 2.0 * r2 * r2 * d.cout));
+}
+
+// Discriminator conv blocks [i_lo, i_hi) (D order: block i works at resolution R >> i).
+// bufs: five scratch feature maps; X enters in `X`; the result pointer is returned.
+// rgb_y != nullptr (only with i_lo == 0): X has NOT been produced yet — the first block starts from the skip image.
+half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* X, half_t* const bufs[5], const float* rgb_y) {
+    half_t *Hb = bufs[0], *HB = bufs[1], *XS = bufs[2], *S = bufs[3], *O = bufs[4];
+    bool x_planar = false;       // X is chunk-planar (common.h x_planar8): written so by the fused first block for conv_wreg
+    for (int i = i_lo; i < i_hi; ++i) {
+        const DBlock& d = e->dblk[i];
+        const float* y = i == 0 ? rgb_y : nullptr;
+        // the next block's first conv on conv_wreg (with the blur-down by-product: nothing else reads this map): chunk-planar output
+        const bool planar = y && i + 1 < i_hi && e->dblk[i + 1].cin == d.cout && conv_wreg_supported(d.cout, d.cout, d.res / 2, d.res / 2);
+        const bool whole = y && run_d_block0(e, B, d, y, O, planar);
+        if (!whole) {
+            const bool have_xs = run_d_conv0(e, B, d, X, x_planar, y, Hb, XS);
+            run_d_conv1(e, B, d, X, have_xs, Hb, HB, XS, S, O);
+        }
+        x_planar = whole && planar;
+        std::swap(X, O);
+    }
+    return X;
+}
+
+// mbstd + final conv + dense head for the whole population: X is [P][4][4][C0]
+void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch) {
+    const glass_config& c = e->cfg;
+    const int CL = c.channels[0];
+    {
+        Prof pr(e, "D.mbstd", 0, 4.0 * P * 16 * CL);
+        launch_mbstd(X, P, 16, CL, e->d_final_cpad, c.batch_size, c.mbstd_group, 1e-8f, scratch, e->cur);
+    }
+    ConvParams p = conv_defaults();
+    p.x = scratch; p.x_bstride = 16LL * e->d_final_cpad; p.B = P; p.H = p.W = 4; p.Cin = e->d_final_cpad; p.Hc = p.Wc = 4;
+    p.KS = 3; p.pad = 1; p.w = e->d_final_w; p.Cout = p.Neff = CL; p.Ho = p.Wo = 4; p.bias = e->d_final_b; p.act = 1;
+    p.y = e->d_dfin;
+    run_conv(e, p, "D.final_conv", 2.0 * P * 16 * 9.0 * (CL + 1) * CL, 2.0 * 9 * CL * (CL + 1));
+    const GemmParams g = gemm_params(e->d_dfin, e->d_dense0_w, P, CL, 16 * CL, e->d_dense0_b, 4, nullptr, e->d_dh, 1);
+    // M = P rows, K = 16 CL = 8192: the 128 x 64 tiles are 8 workgroups walking 128 K steps each (97 us for 0.5 GFLOP).  Split K into 16
+    // slices (blockIdx.z) with raw partial sums, finished in a fixed order with bias + activation: 128+ workgroups, 8 steps each.
+    const int S0 = 16;
+    if (e->d_dh_part && g.K % (S0 * 64) == 0 && P <= e->cfg.max_pop) {
+        GemmParams q = g;
+        q.ld = g.K; q.K = g.K / S0; q.batch = S0; q.a_bs = q.K; q.w_bs = q.K; q.o_bs = (long long)P * CL;
+        q.bias = nullptr; q.mode = 3; q.out32 = e->d_dh_part;
+        Prof pr(e, "D.dense0", 2.0 * P * (double)g.K * CL, 2.0 * (double)g.K * CL);
+        const char* k = launch_gemm_tiled(q, e->cur);
+        if (k) {    // finish + the second dense layer (CL -> 1) in one launch
+            launch_dense01_finish(e->d_dh_part, S0, q.o_bs, g.bias, e->d_dense1_wt, e->d_dense1_b, e->d_dis, P, CL, e->cur);
+            if (pr.on) pr.pe.name = std::string("D.dense0+1@") + k + "+dense01_finish";
+            return;
+        }
+        pr.drop();
+    }
+    run_gemm(e, g, "D.dense0");
+    {
+        Prof pr(e, "D.dense1", 2.0 * P * CL, 0);
+        launch_dense(e->d_dh, CL, P, CL, e->d_dense1_wt, 1, e->d_dense1_b, e->d_dis, 1, 0, 0, nullptr, 0, e->cur);
+    }
+}

@@ -11,6 +11,9 @@ CONFIGS = {
     "mini": dict(channels=[16, 16, 32, 32], latent=32, mapping=2, clip=(64, 2, 1, 8, 32, 32)),
     # 64 px, channel counts that reach the LDS-tiled kernels (W >= 32), resize 64 -> 32
     "mid": dict(channels=[32, 64, 64, 64, 64], latent=64, mapping=3, clip=(128, 2, 2, 8, 32, 64)),
+    # 128 px, the smallest network on which the engine's block walkers leave `mid`'s kernel forms: a 512-channel pair at 32 x 32 (toRGB
+    # partial sums, conv_gldsp), 64 -> 64 at 128 x 128 (chunk-planar up-conv output for conv_wreg) and a D without the one-kernel first block
+    "r128": dict(channels=[64, 64, 512, 512, 512, 512], latent=64, mapping=2, clip=(128, 2, 2, 8, 32, 64)),
     # the real thing: StyleGAN2 ffhq config-f 1024 px + CLIP ViT-B/32
     "ffhq": dict(channels=synth.FFHQ_CHANNELS, latent=512, mapping=8, clip=(768, 12, 12, 32, 224, 512)),
     # config.py:96-135 (StyleGAN2_church_* 256 px, StyleGAN2_car_* 512 px): config-f channel tables of the smaller networks

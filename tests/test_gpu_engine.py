@@ -235,6 +235,44 @@ def test_stream_modes_give_identical_results():
     e.close()
 
 
+def test_launch_table_is_pinned():
+    """Which kernel every layer runs on, in launch order: the profile's (row name, launches) list of one evaluate on two small networks
+    against tests/golden/launch_table.json, recorded on the MI355X from the commit BEFORE the block walkers were rewritten.  A walker that
+    falls back to a slower but correct path passes every parity test; it does not pass this one.  `mid` and `r128` (glass_models.py) are
+    the smallest networks that reach the walkers' branches; the conditions below say which.  Not reachable at 128 px or below:
+    conv_stream_kernel<torgb> (its admission wants 72 tiles per image: 256 px) and dblock0's chunk-planar output for conv_wreg (256 px)."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_table.json")) as f:
+        golden = json.load(f)
+    names = {k: [r[0] for r in rows] for k, rows in golden.items()}
+    every = names["mid"] + names["r128"]
+
+    def follows(rows, first, then):
+        return any(first in a and then in b for a, b in zip(rows, rows[1:]))
+    assert follows(names["r128"], "G.upconv.r128.64x64@upfir2_kernel", "G.conv.r128.64x64@conv_wreg_kernel")
+    assert "G.conv.r32.512x512@conv_gldsp_kernel<true,false,false>" in every            # toRGB partial sums + finish
+    assert any("torgb" in n and n.startswith("G.conv.") for n in every)                 # toRGB in the conv's epilogue
+    assert any(n.startswith("G.torgb.") for n in every)                                 # separate toRGB
+    assert any(n.endswith("@dblock0_kernel") for n in every)
+    assert "D.conv0.r32.512x512@conv_gldsp_kernel<false,true,false>" in every and "D.blurdown.r32" not in every   # blur-down by-product
+    assert any(n.startswith("D.conv1.") and n.endswith("@conv_s2_kernel") for n in every)               # fused skip
+    assert any(n.startswith("D.conv1.") and n.endswith("skip>") for n in every)
+    assert any(n.startswith("D.skip.") for n in every)                                  # separate skip + residual
+    assert "D.fromrgb" in names["r128"] and any(n.startswith("D.blurdown.") for n in every)
+    for name in ("mid", "r128"):
+        c = M.CONFIGS[name]
+        e = M.make_engine(name, M.make_state(name, 0), batch_size=4, use_discriminator=True, max_pop=4, noise_mode=1)
+        e.set_target(np.ones(c["clip"][5], np.float32))
+        e.set_profiling(True)
+        e.evaluate(synth.latents(1, 4, c["latent"]))
+        rows = [[r["name"], r["launches"]] for r in e.profile()]
+        e.close()
+        diff = [(i, a, b) for i, (a, b) in enumerate(zip(rows, golden[name])) if a != b]
+        assert not diff and len(rows) == len(golden[name]), "%s: %d rows against %d pinned, first difference %r" % (
+            name, len(rows), len(golden[name]), diff[:1])
+
+
 def test_pop512_as_eight_shards_of_64():
     """BASELINE.json configs[3] (StyleGAN2_ffhq_d pop=512, 64 per GPU x 8) exercised as offset shards on ONE GPU at the mid
     architecture: the eight 64-row shard calls reproduce the whole-population call row for row."""
