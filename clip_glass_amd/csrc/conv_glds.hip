@@ -757,6 +757,7 @@ const char* launch_conv_glds(const ConvParams& p0, hipStream_t st) {
     ConvParams p = p0;
     if (const char* k = launch_conv_wreg(p, st)) return k;     // 64 -> 64 channels: the weights-in-registers form (conv_wreg.hip)
     if (p.x_planar8 || p.y_planar8 || p.x_planar32) return nullptr;   // chunk-planar maps (common.h): not implemented here
+    if (p.post_scale16) return nullptr;   // an output transform of the fused up-conv only: refuse, never ignore
     if (!glass_lds_fits(Geo<32>::LDS_BYTES) || !glass_lds_fits(Geo<16>::LDS_BYTES)) return nullptr;
     if (p.up || (p.xs_out && (p.sn || p.trgb_yout || p.Wc % 32 != 0)) || p.y32 || !p.y || p.KS != 3 || p.stride != 1 || p.pad != 1) return nullptr;
     if ((p.sn && !p.sn16) || p.pre_shift || p.in_up || p.Cin > 1024 || (p.x_bstride == 0 && p.B > 1)) return nullptr;

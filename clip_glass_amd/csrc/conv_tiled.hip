@@ -552,6 +552,7 @@ static const char* launch_inst(const ConvParams& p, hipStream_t st, const char* 
 
 const char* launch_conv_tiled(const ConvParams& p, hipStream_t st) {
     if (p.x_planar8 || p.y_planar8 || p.x_planar32) return nullptr;   // chunk-planar maps (common.h): not implemented here
+    if (p.post_scale16) return nullptr;   // an output transform of the fused up-conv only: refuse, never ignore
     if (p.rgb_tanh_out) {   // planar tanh(channels 0..2) from the accumulators: the one-n-tile 3x3 instance's fast path only
         if (p.y32 || p.trgb_yout || p.xs_out || p.up || p.KS != 3 || p.stride != 1 || p.pad != 1 || p.Neff != 32 || p.Cout != 32 ||
             p.Hc % 8 != 0 || p.Wc % 32 != 0 || p.Cin % 32 != 0 || (p.sn && !p.sn16) || (p.pre_shift && !p.pre_shift16) || p.res || p.noise ||

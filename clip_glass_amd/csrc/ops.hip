@@ -139,6 +139,33 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     }
     p.x_planar8 = d->x_planar8;
     p.x_planar32 = d->x_planar32;
+    p.y_planar8 = d->y_planar8;
+    if (d->post_scale) {
+        p.post_scale16 = dv.up16(d->post_scale, (size_t)d->B * d->Cout); p.post_stride = d->Cout;
+        OPREQ(p.post_scale16, "device allocation failed");
+    }
+    if (d->premod) {      // per-sample pre-modulated weights, set up as stylegan2.cpp g_conv_params does for a premod layer
+        OPREQ(d->sn && d->KS == 3 && !d->broadcast_x, "premod: 3x3 with sn, not with broadcast_x");
+        OPREQ(!d->up || d->impl == 3, "premod up-conv: impl 3 only (the folded table is not modulated)");
+        const long long welems = 9LL * d->Cin * d->Cout;
+        half_t* wm = dv.alloc<half_t>((size_t)d->B * welems);
+        OPREQ(wm && p.sn && (p.dscale || !d->dscale), "device allocation failed");
+        launch_modulate_weights(d->up ? p.w_up : p.w, welems, d->Cin, d->Cout, p.sn, p.sn_stride, p.dscale, p.ds_stride, d->B, wm, 0);
+        p.sn = nullptr; p.sn16 = nullptr; p.dscale = nullptr; p.w_bstride = welems;
+        if (d->up) { p.w_up = wm; p.w = nullptr; }
+        else p.w = wm;
+    }
+    float* part = nullptr;
+    const float* part_yprev = p.trgb_yprev;
+    const int ntn = d->Cout / 128;
+    if (d->trgb_partial) {   // toRGB partial sums per 128-wide n tile, as torgb_conv_params sets ToRgb::partial up; launch_trgb_finish below
+        OPREQ(yrgb && d->impl == 5 && d->Cout % 128 == 0 && d->Ho == d->Wo, "toRGB partial sums: impl 5 with the trgb inputs, Cout % 128 == 0, Ho == Wo");
+        const size_t npart = (size_t)ntn * nrgb;
+        part = dv.alloc<float>(npart);
+        OPREQ(part, "device allocation failed");
+        GLASS_HIP(hipMemset(part, 0xFF, npart * sizeof(float)));      // NaN: a partial the conv does not write shows in the sum
+        p.trgb_part = part; p.trgb_yout = nullptr; p.trgb_yprev = nullptr;
+    }
     if (d->impl == 1) { if (!launch_conv_direct(p, 0)) { glass_set_error("direct conv: unsupported launch"); return GLASS_ERR_ARG; } }
     else if (d->impl == 3) {
         if (!launch_upconv_fused(p, 0)) { glass_set_error("fused up-conv: unsupported shape"); return GLASS_ERR_ARG; }
@@ -161,6 +188,10 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     }
     int rc = finish();
     if (rc) return rc;
+    if (part) {
+        launch_trgb_finish(part, ntn, d->B, d->Ho, p.trgb_b, part_yprev, yrgb, 0);
+        if ((rc = finish())) return rc;
+    }
     if (yrgb) {
         GLASS_HIP(hipMemcpy(d->trgb_yout, yrgb, nrgb * sizeof(float), hipMemcpyDeviceToHost));
         return p.y ? down16(d->y, y, nout) : GLASS_OK;      // (the forms that also store the feature map hand it back too)

@@ -24,7 +24,9 @@ class ConvDesc(C.Structure):
                 ("trgb_smax", C.POINTER(C.c_float)), ("trgb_yprev", C.POINTER(C.c_float)),
                 ("trgb_yout", C.POINTER(C.c_float)),
                 ("skip_x", C.POINTER(C.c_float)), ("skip_w", C.POINTER(C.c_float)), ("xs_out", C.POINTER(C.c_float)),
-                ("x_planar8", C.c_int32), ("x_planar32", C.c_int32)]
+                ("x_planar8", C.c_int32), ("x_planar32", C.c_int32),
+                ("premod", C.c_int32), ("post_scale", C.POINTER(C.c_float)), ("y_planar8", C.c_int32),
+                ("trgb_partial", C.c_int32)]
 
 
 def to_planar8(a):
@@ -56,11 +58,16 @@ def _opt(a):
 
 def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None, noise_strength=0.0,
          batch_size=1, bias=None, act=False, res=None, out_scale=1.0, impl=0, broadcast_x=False, B=None, device=0,
-         torgb=None, skip=None, xs_out=None, planar_x=False, both=False, planar32_x=False):
+         torgb=None, skip=None, xs_out=None, planar_x=False, both=False, planar32_x=False, premod=False, post_scale=None,
+         planar_y=False, trgb_partial=False):
     """x [B,H,W,Cin] NHWC; w [Cout,Cin,KS,KS] (reference layout).  Returns y [B,Ho,Wo,Cout].
     torgb = dict(w [3,Cout], b [3], sn [B,Cout], smax [B], yprev [B,3,Ho/2,Wo/2] or None) with impl=4: the fused conv + toRGB
     form of the streaming kernel — returns the skip image [B,3,Ho,Wo] instead of y.
-    planar_x: the device gets x chunk-planar (the permutation happens here; impl 5, 64 -> 64)."""
+    planar_x: the device gets x chunk-planar (the permutation happens here; impl 5, 64 -> 64).
+    The forms the StyleGAN2 host builds (csrc/stylegan2.cpp): premod — sn / dscale go into per-sample weights first
+    (modulate_weights_kernel) and the conv runs without them; post_scale [B,Cout] — the consumer's style applied to the finished
+    output (fused up-conv); planar_y — the device stores y chunk-planar (un-permuted here); trgb_partial — with torgb and impl 5: toRGB
+    partial sums per 128-wide n tile + the finishing pass."""
     lib = load_library()
     x = _f32(x); w = _f32(w)
     Bx, H, W, Cin = x.shape
@@ -83,9 +90,10 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
     d.noise_strength, d.out_scale = noise_strength, out_scale
     d.x_planar8 = int(planar_x)
     d.x_planar32 = int(planar32_x)
+    d.premod, d.y_planar8, d.trgb_partial = int(premod), int(planar_y), int(trgb_partial)
     keep = []
     d.x, d.w, d.y = _fp(x), _fp(w), _fp(y)
-    for name, val in (("sn", sn), ("dscale", dscale), ("noise", noise), ("bias", bias), ("res", res)):
+    for name, val in (("sn", sn), ("dscale", dscale), ("noise", noise), ("bias", bias), ("res", res), ("post_scale", post_scale)):
         a, p = _opt(val)
         keep.append(a)
         if p is not None:
@@ -108,6 +116,8 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
         d.trgb_yout = _fp(yrgb)
     lib.glass_op_conv.argtypes = [C.c_int32, C.POINTER(ConvDesc)]
     _check(lib, lib.glass_op_conv(device, C.byref(d)))
+    if planar_y:
+        y = from_planar8(y, B, Ho, Wo, Cout)
     if both:                  # fused toRGB forms that store the feature map too (impl 2 / 5): (skip image, feature map)
         return yrgb, y
     return yrgb if yrgb is not None else y

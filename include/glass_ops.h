@@ -47,6 +47,15 @@ typedef struct glass_conv_desc {
     int32_t x_planar8;
     /* impl 5 with the fused skip branch (conv_s2): x is handed over in 32-channel planes, [B,Cin/32,H,W,32] (the layout the pad-2 blur writes for it) */
     int32_t x_planar32;
+    /* The forms only the StyleGAN2 host builds (stylegan2.cpp g_conv_params / up_link / torgb_conv_params).  A launcher that refuses one is an error. */
+    /* 3x3, needs sn (dscale optional), not with broadcast_x: launch_modulate_weights on the packed table (w_up for an up-conv), then the
+     * launch as g_conv_params sets a premod layer up — no sn / sn16 / dscale, per-sample weights (w_bstride = 9 Cin Cout) */
+    int32_t premod;
+    const float* post_scale; /* [B,Cout] or NULL: ConvParams::post_scale16 (fp16), the consumer's style applied to the finished output */
+    int32_t y_planar8;       /* y is stored, and handed back, chunk-planar: [B,Cout/8,Ho,Wo,8] */
+    /* impl 5 with the trgb_* inputs, Cout a multiple of 128, Ho == Wo: the conv writes toRGB partial sums per 128-wide n tile
+     * (ConvParams::trgb_part, NaN-filled before the launch), launch_trgb_finish adds them into trgb_yout; y is returned too */
+    int32_t trgb_partial;
 } glass_conv_desc;
 
 int glass_op_conv(int32_t device, const glass_conv_desc* d);

@@ -9,7 +9,7 @@ import torch.nn.functional as F
 
 from clip_glass_amd import synth
 from oracle import stylegan2_ref as sg
-from util import check, diag, nchw, nhwc, style_tables
+from util import _torgb_ref, check, diag, nchw, nhwc, style_tables
 
 pytestmark = pytest.mark.gpu
 ops = None
@@ -75,6 +75,29 @@ def _modconv_case(up, impl, B=4, H=8, Cin=32, Cout=48, L=24, batch_size=2, broad
     got = ops.conv(nhwc(x), w, up=up, sn=sn, dscale=dscale, noise=noise, noise_strength=strength,
                    batch_size=batch_size, bias=bias, act=True, impl=impl, broadcast_x=broadcast, B=B)
     return got, ref
+
+
+def _oracle_conv(x, w, sn=None, dscale=None, noise=None, noise_strength=0.0, batch_size=1, bias=None, act=False, res=None, out_scale=1.0,
+                 stride=1, pad=1, **_):
+    """oracle.stylegan2_ref of one diagnostic conv launch (NHWC in and out): _conv — _mod_conv without demodulation where the launch has a
+    style, the latent being the style itself — then the epilogue as the kernels apply it (conv_direct.hip):
+    ((conv * dscale + strength * noise + bias -> lrelu * sqrt2) + res) * out_scale."""
+    xt = torch.tensor(nchw(x))
+    Cin = xt.shape[1]
+    if sn is None:
+        y = sg._conv(xt, torch.tensor(w), stride=stride, padding=pad)
+    else:
+        assert stride == 1 and pad == w.shape[2] // 2
+        eye = torch.eye(Cin) * math.sqrt(Cin)          # _dense scales by 1 / sqrt(fan_in): style = latent
+        y = sg._mod_conv(xt, torch.tensor(np.asarray(sn, dtype=np.float32)), torch.tensor(w), eye, torch.zeros(Cin), demod=False, up=False)
+    if dscale is not None:
+        y = y * torch.tensor(np.asarray(dscale, dtype=np.float32))[:, :, None, None]
+    if noise is not None:
+        y = y + noise_strength * torch.tensor(np.asarray(noise, dtype=np.float32)).repeat_interleave(batch_size, dim=0)[:, None]
+    y = sg._bias_act(y, torch.tensor(np.asarray(bias, dtype=np.float32)), act=act) if bias is not None else y
+    if res is not None:
+        y = y + torch.tensor(nchw(res))
+    return nhwc((y * out_scale).numpy())
 
 
 def test_conv_stream_matches_tiled_and_direct():
@@ -202,6 +225,8 @@ def test_conv_gemm_matches_direct(case):
     got = ops.conv(x, w, impl=6, **kw)
     ref = ops.conv(x, w, impl=1, **kw)
     check("conv_gemm %s vs direct" % case, got, ref, 2e-3)
+    if case in ("plain4", "conv8"):      # the smallest un-styled and the styled 3x3 case: also against the oracle, not only the sibling kernel
+        check("conv_gemm %s vs oracle" % case, got, _oracle_conv(x, w, **kw), 5e-3)
 
 
 def test_conv_tiled_blurdown_byproduct():
@@ -219,25 +244,6 @@ def test_conv_tiled_blurdown_byproduct():
     xp = np.pad(x.astype(np.float64), ((0, 0), (1, 1), (1, 1), (0, 0)))
     ref = sum(f[a] * f[b2] * xp[:, a:a + H:2, b2:b2 + W:2] for a in range(4) for b2 in range(4))
     check("blur-down by-product", xs, ref, 2e-3)
-
-
-def _torgb_ref(feat, wrgb, brgb, srgb, smax, yprev):
-    """float64 toRGB (stylegan2/models.py:852-870) + FIR-upsampled skip image (modules.py:580-602) of an NHWC map."""
-    B, H, W, _ = feat.shape
-    wm = wrgb[None].astype(np.float64) * (srgb.astype(np.float64) * smax[:, None])[:, None, :]    # [B,3,C]
-    ref = np.einsum("bhwc,boc->bohw", feat.astype(np.float64), wm) + brgb[None, :, None, None]
-    if yprev is not None:
-        yp = np.pad(yprev.astype(np.float64), ((0, 0), (0, 0), (1, 0), (1, 0)))       # x[m-1] with zero at m = 0
-        a, bq = yp[:, :, :-1], yp[:, :, 1:]                                          # rows m-1, m
-        rows = np.empty((B, 3, H, W // 2 + 1))
-        rows[:, :, 0::2] = 0.75 * a + 0.25 * bq
-        rows[:, :, 1::2] = 0.25 * a + 0.75 * bq
-        a, bq = rows[..., :-1], rows[..., 1:]
-        up = np.empty((B, 3, H, W))
-        up[..., 0::2] = 0.75 * a + 0.25 * bq
-        up[..., 1::2] = 0.25 * a + 0.75 * bq
-        ref = ref + up
-    return ref
 
 
 @pytest.mark.parametrize("impl,C,with_skip", [(2, 64, True), (2, 64, False), (5, 128, True), (5, 128, False)])
@@ -288,6 +294,9 @@ def test_conv_glds_matches_tiled(B, H, W, Cin, Cout):
     got_s = ops.conv(x, w, impl=5, sn=sn, **kw)
     ref_s = ops.conv(x, w, impl=1, sn=sn, **kw)
     check("conv_glds (style on weights) vs direct", got_s, ref_s, 4e-3)
+    if (B, H, W, Cin, Cout) == (2, 32, 16, 128, 384):      # the smallest case: also against the oracle, not only the sibling kernels
+        check("conv_glds vs oracle", got, _oracle_conv(x, w, **kw), 5e-3)
+        check("conv_glds (style on weights) vs oracle", got_s, _oracle_conv(x, w, sn=sn, **kw), 5e-3)
 
 
 def test_conv_glds_persistent_matches_tiled():
@@ -306,6 +315,7 @@ def test_conv_glds_persistent_matches_tiled():
     got = ops.conv(x, w, impl=5, **kw)
     ref_t = ops.conv(x, w, impl=2, **kw)
     assert np.abs(got - ref_t).max() <= 2.0 ** -8 * max(1.0, float(np.abs(ref_t).max()))
+    check("persistent conv_glds vs oracle", got, _oracle_conv(x, w, **kw), 5e-3)
     sn = rng.uniform(-1.0, 1.0, (B, Cin)).astype(np.float32)
     check("persistent conv_glds (style on weights) vs direct", ops.conv(x, w, impl=5, sn=sn, **kw), ops.conv(x, w, impl=1, sn=sn, **kw), 4e-3)
     # blur-down of the input as a by-product of the staged patches (two n tiles per pixel tile: chunk c is written by n tile c % 2)
@@ -353,6 +363,8 @@ def test_conv_wreg_matches_tiled(B, H, W):
     diag("[wreg] B%d %dx%d max|wreg-tiled| %.3e" % (B, H, W, np.abs(got - ref_t).max()))
     assert np.abs(got - ref_t).max() <= 2.0 ** -8 * max(1.0, float(np.abs(ref_t).max()))
     check("conv_wreg vs direct", got, ops.conv(x, w, impl=1, **kw), 4e-3)
+    if (B, H, W) == (1, 256, 128):      # the smallest case: also against the oracle, not only the sibling kernels
+        check("conv_wreg vs oracle", got, _oracle_conv(x, w, **kw), 5e-3)
     np.testing.assert_array_equal(got, ops.conv(x, w, impl=5, **kw))          # the ring is deterministic
     np.testing.assert_array_equal(got, ops.conv(x, w, impl=5, planar_x=True, **kw))      # chunk-planar input (common.h x_planar8): same values
     kwp = dict(bias=bias, act=True)                                          # the engine's form: no per-channel scale, no shift (the PLAIN epilogue)

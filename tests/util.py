@@ -92,3 +92,22 @@ def style_tables(latent, dense_w, dense_b, W, demod=True, eps=1e-8):
     else:
         dscale = np.repeat(smax, cout, axis=1)
     return sn.astype(np.float32), smax.astype(np.float32), dscale.astype(np.float32)
+
+
+def _torgb_ref(feat, wrgb, brgb, srgb, smax, yprev):
+    """float64 toRGB (stylegan2/models.py:852-870) + FIR-upsampled skip image (modules.py:580-602) of an NHWC map."""
+    B, H, W, _ = feat.shape
+    wm = wrgb[None].astype(np.float64) * (srgb.astype(np.float64) * smax[:, None])[:, None, :]    # [B,3,C]
+    ref = np.einsum("bhwc,boc->bohw", feat.astype(np.float64), wm) + brgb[None, :, None, None]
+    if yprev is not None:
+        yp = np.pad(yprev.astype(np.float64), ((0, 0), (0, 0), (1, 0), (1, 0)))       # x[m-1] with zero at m = 0
+        a, bq = yp[:, :, :-1], yp[:, :, 1:]                                          # rows m-1, m
+        rows = np.empty((B, 3, H, W // 2 + 1))
+        rows[:, :, 0::2] = 0.75 * a + 0.25 * bq
+        rows[:, :, 1::2] = 0.25 * a + 0.75 * bq
+        a, bq = rows[..., :-1], rows[..., 1:]
+        up = np.empty((B, 3, H, W))
+        up[..., 0::2] = 0.75 * a + 0.25 * bq
+        up[..., 1::2] = 0.25 * a + 0.75 * bq
+        ref = ref + up
+    return ref
