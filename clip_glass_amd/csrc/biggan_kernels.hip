@@ -68,8 +68,10 @@ void launch_bg_bn_tables(float* tab, int P, int C, const float* inv_std, const f
 }
 
 // ---- fp32 -> fp16 -------------------------------------------------------------------------------------
-__global__ void bg_to_half_kernel(const float* __restrict__ x, half_t* __restrict__ y, long long n4) {
+__global__ void bg_to_half_kernel(const float* __restrict__ x, half_t* __restrict__ y, long long n4, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0)                                   // the n % 4 elements past the last whole vector
+        for (long long k = n4 * 4; k < n; ++k) y[k] = (half_t)x[k];
     if (i >= n4) return;
     const f4 v = ((const f4*)x)[i];
     h4 o;
@@ -78,8 +80,9 @@ __global__ void bg_to_half_kernel(const float* __restrict__ x, half_t* __restric
     ((h4*)y)[i] = o;
 }
 void launch_bg_to_half(const float* x, half_t* y, long long n, hipStream_t st) {
+    if (n <= 0) return;
     const long long n4 = n / 4;
-    hipLaunchKernelGGL(bg_to_half_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, y, n4);
+    hipLaunchKernelGGL(bg_to_half_kernel, dim3((unsigned)std::max((n4 + 255) / 256, 1LL)), dim3(256), 0, st, x, y, n4, n);
 }
 
 // ---- SelfAttn split: T [B][H][W][c8 + c8 + c2] (theta | phi | g) ->
@@ -166,19 +169,20 @@ __global__ __launch_bounds__(256) void bg_attn_split_vec_kernel(const half_t* __
         *(h8*)(gT + (b * c2 + c0 + c) * hq + q0 + part * 8) = *(const h8*)(&Ls[c][part * 8]);
     }
 }
-void launch_bg_attn_split(const half_t* T, int B, int H, int W, int c8, int c2, half_t* theta, half_t* phi, half_t* gT,
-                          hipStream_t st) {
+const char* launch_bg_attn_split(const half_t* T, int B, int H, int W, int c8, int c2, half_t* theta, half_t* phi, half_t* gT,
+                                 hipStream_t st) {
     const int hw = H * W, hq = hw / 4;
     if (c8 % 8 == 0 && c2 % 64 == 0 && hq % 32 == 0 && W % 2 == 0) {
         const int nb_theta = (int)(((long long)hw * (c8 >> 3) + 255) / 256), nb_phi = (int)(((long long)hq * (c8 >> 3) + 255) / 256);
         const int nb_g = (hq / 32) * (c2 >> 6);
         hipLaunchKernelGGL(bg_attn_split_vec_kernel, dim3((unsigned)(nb_theta + nb_phi + nb_g), B), dim3(256), 0, st, T, H, W, c8, c2, theta, phi, gT,
                            nb_theta, nb_phi);
-        return;
+        return "bg_attn_split_vec_kernel";
     }
     const long long n = (long long)H * W * c8 + (long long)(H * W / 4) * (c8 + c2);
     hipLaunchKernelGGL(bg_attn_split_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, T, H, W, c8, c2, theta,
                        phi, gT);
+    return "bg_attn_split_kernel";
 }
 
 // ---- row softmax: S fp32 [rows][n] -> P fp16 [rows][n]; one wave per row, the row held in registers (one pass over

@@ -135,9 +135,11 @@ void launch_assemble_F(const float* sim, const float* dis, int P, int n_obj, flo
 void launch_bg_cond(const float* x, int P, int L, int zd, int nc, const float* et, float* cond, hipStream_t st);
 void launch_bg_bn_tables(float* tab, int P, int C, const float* inv_std, const float* mean, const float* prebias,
                          hipStream_t st);
+// any n: whole 4-element vectors, then the n % 4 tail elements one by one (x and y 16 / 8 byte aligned)
 void launch_bg_to_half(const float* x, half_t* y, long long n, hipStream_t st);
-void launch_bg_attn_split(const half_t* T, int B, int H, int W, int c8, int c2, half_t* theta, half_t* phi, half_t* gT,
-                          hipStream_t st);
+// returns the kernel it launched: the vector form where c8 % 8 == 0, c2 % 64 == 0, (H W / 4) % 32 == 0, else the scalar form (H, W even)
+const char* launch_bg_attn_split(const half_t* T, int B, int H, int W, int c8, int c2, half_t* theta, half_t* phi, half_t* gT,
+                                 hipStream_t st);
 void launch_bg_softmax(const float* S, long long rows, int n, half_t* Pm, hipStream_t st);
 void launch_bg_rgb_tanh(const half_t* x, int B, long long hw, int C, float* y, hipStream_t st);
 

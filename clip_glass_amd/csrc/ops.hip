@@ -66,12 +66,21 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     OPREQ(d && d->x && d->w && d->y, "null argument");
     OPREQ(d->Cin % 16 == 0, "Cin must be a multiple of 16");
     OPREQ(d->out_scale > 0.f, "out_scale must be positive (the epilogues fold it into the activation constants: max(v k1, v k2))");
+    OPREQ(!d->pre_shift || d->sn, "pre_shift needs sn (the input affine is relu(x * sn + pre_shift))");
+    OPREQ(d->in_up == 0 || (d->in_up == 1 && d->H % 2 == 0 && d->W % 2 == 0 && !d->up && !d->broadcast_x),
+          "in_up: H and W are the upsampled dims and must be even (not with up / broadcast_x)");
+    OPREQ(d->res_up == 0 || (d->res_up == 1 && d->res && d->Ho % 2 == 0 && d->Wo % 2 == 0), "res_up: needs res, Ho and Wo even");
+    OPREQ(d->res_cs == 0 || (d->res && d->res_cs >= d->Cout), "res_cs: needs res, res_cs >= Cout");
+    OPREQ(!d->rgb_tanh || d->impl == 0 || d->impl == 2, "rgb_tanh: conv_tiled only (impl 0 / 2), as run_conv dispatches it");
+    OPREQ(!d->rgb_tanh || (!d->trgb_yout && !d->xs_out), "rgb_tanh: not with the fused toRGB or the blur-down by-product");
     GLASS_HIP(hipSetDevice(device));
     Dev dv;
     ConvParams p = conv_defaults();
-    const size_t xin = (size_t)(d->broadcast_x ? 1 : d->B) * d->H * d->W * d->Cin;
+    const int Hx = d->H >> d->in_up, Wx = d->W >> d->in_up;      // the stored input map
+    const size_t xin = (size_t)(d->broadcast_x ? 1 : d->B) * Hx * Wx * d->Cin;
     p.x = dv.up16(d->x, xin);
-    p.x_bstride = d->broadcast_x ? 0 : (long long)d->H * d->W * d->Cin;
+    p.x_bstride = d->broadcast_x ? 0 : (long long)Hx * Wx * d->Cin;
+    p.in_up = d->in_up;
     p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin;
     p.KS = d->KS; p.stride = d->stride; p.pad = d->pad; p.up = d->up;
     p.Cout = d->Cout; p.Neff = d->up ? 4 * d->Cout : d->Cout;
@@ -90,16 +99,42 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
         glass_pack_conv(d->w, d->Cout, d->Cin, 3, d->Cin, pk2);
         p.w_up = dv.up16v(pk2);
     }
-    p.sn = dv.up32(d->sn, (size_t)d->B * d->Cin); p.sn_stride = d->Cin;
-    p.sn16 = dv.up16(d->sn, (size_t)d->B * d->Cin);
-    p.dscale = dv.up32(d->dscale, (size_t)d->B * d->Cout); p.ds_stride = d->Cout;
+    if (d->pre_shift) {       // one per-candidate table [A | S], fp32 and fp16, as bg_conv points sn / pre_shift / sn16 / pre_shift16 into tab / tab16
+        std::vector<float> tab((size_t)d->B * 2 * d->Cin);
+        for (int b = 0; b < d->B; ++b)
+            for (int c = 0; c < d->Cin; ++c) {
+                tab[((size_t)b * 2) * d->Cin + c] = d->sn[(size_t)b * d->Cin + c];
+                tab[((size_t)b * 2 + 1) * d->Cin + c] = d->pre_shift[(size_t)b * d->Cin + c];
+            }
+        const float* t32 = dv.up32(tab.data(), tab.size());
+        const half_t* t16 = dv.up16(tab.data(), tab.size());
+        OPREQ(t32 && t16, "device allocation failed");
+        p.sn = t32; p.pre_shift = t32 + d->Cin; p.sn16 = t16; p.pre_shift16 = t16 + d->Cin; p.sn_stride = 2 * d->Cin;
+    } else {
+        p.sn = dv.up32(d->sn, (size_t)d->B * d->Cin); p.sn_stride = d->Cin;
+        p.sn16 = dv.up16(d->sn, (size_t)d->B * d->Cin);
+    }
+    if (d->shift) {           // one table [dscale | shift], as bg_conv points dscale / shift into tab
+        std::vector<float> tab((size_t)d->B * 2 * d->Cout);
+        for (int b = 0; b < d->B; ++b)
+            for (int c = 0; c < d->Cout; ++c) {
+                tab[((size_t)b * 2) * d->Cout + c] = d->dscale ? d->dscale[(size_t)b * d->Cout + c] : 1.f;
+                tab[((size_t)b * 2 + 1) * d->Cout + c] = d->shift[(size_t)b * d->Cout + c];
+            }
+        const float* t32 = dv.up32(tab.data(), tab.size());
+        OPREQ(t32, "device allocation failed");
+        p.dscale = d->dscale ? t32 : nullptr; p.shift = t32 + d->Cout; p.ds_stride = 2 * d->Cout;
+    } else {
+        p.dscale = dv.up32(d->dscale, (size_t)d->B * d->Cout); p.ds_stride = d->Cout;
+    }
     p.batch_size = d->batch_size > 0 ? d->batch_size : 1;
     p.noise = dv.up32(d->noise, (size_t)(d->B / p.batch_size) * d->Ho * d->Wo);
     p.noise_strength = d->noise_strength;
     p.bias = dv.up32(d->bias, d->Cout);
     p.act = d->act;
     const size_t nout = (size_t)d->B * d->Ho * d->Wo * d->Cout;
-    p.res = dv.up16(d->res, nout);
+    p.res_cs = d->res_cs; p.res_up = d->res_up;
+    p.res = dv.up16(d->res, (size_t)d->B * (d->Ho >> d->res_up) * (d->Wo >> d->res_up) * (d->res_cs ? d->res_cs : d->Cout));
     p.out_scale = d->out_scale;
     half_t* y = dv.alloc<half_t>(nout);
     p.y = y;
@@ -155,6 +190,13 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
         if (d->up) { p.w_up = wm; p.w = nullptr; }
         else p.w = wm;
     }
+    float* ytanh = nullptr;
+    if (d->rgb_tanh) {
+        ytanh = dv.alloc<float>(nrgb);
+        OPREQ(ytanh, "device allocation failed");
+        GLASS_HIP(hipMemset(ytanh, 0xFF, nrgb * sizeof(float)));        // NaN: a pixel the conv does not write shows
+        p.rgb_tanh_out = ytanh;
+    }
     float* part = nullptr;
     const float* part_yprev = p.trgb_yprev;
     const int ntn = d->Cout / 128;
@@ -166,7 +208,9 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
         GLASS_HIP(hipMemset(part, 0xFF, npart * sizeof(float)));      // NaN: a partial the conv does not write shows in the sum
         p.trgb_part = part; p.trgb_yout = nullptr; p.trgb_yprev = nullptr;
     }
-    if (d->impl == 1) { if (!launch_conv_direct(p, 0)) { glass_set_error("direct conv: unsupported launch"); return GLASS_ERR_ARG; } }
+    if (ytanh) {              // run_conv: one kernel family writes this output
+        if (!launch_conv_tiled(p, 0)) { glass_set_error("tiled conv: no instance writes the planar tanh output of this shape"); return GLASS_ERR_ARG; }
+    } else if (d->impl == 1) { if (!launch_conv_direct(p, 0)) { glass_set_error("direct conv: unsupported launch"); return GLASS_ERR_ARG; } }
     else if (d->impl == 3) {
         if (!launch_upconv_fused(p, 0)) { glass_set_error("fused up-conv: unsupported shape"); return GLASS_ERR_ARG; }
     } else if (d->impl == 2) {
@@ -174,7 +218,8 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     } else if (d->impl == 4) {
         if (!launch_conv_stream(p, 0)) { glass_set_error("streaming conv: unsupported shape"); return GLASS_ERR_ARG; }
     } else if (d->impl == 6) {
-        const long long cap_a = (long long)p.Hc * p.Wc * p.KS * p.KS * p.Cin, cap_c = (long long)p.Hc * p.Wc * p.Neff;   // per candidate
+        // per candidate; room for the four split-K slices the launcher may choose, as the engine's scratch (256 * 4 * cmax floats) always has
+        const long long cap_a = (long long)p.Hc * p.Wc * p.KS * p.KS * p.Cin, cap_c = 4LL * p.Hc * p.Wc * p.Neff;
         half_t* wa = dv.alloc<half_t>((size_t)(cap_a * p.B));
         float* wc = dv.alloc<float>((size_t)(cap_c * p.B));
         if (!launch_conv_gemm(p, wa, cap_a, wc, cap_c, 0)) { glass_set_error("im2col + GEMM conv: unsupported shape"); return GLASS_ERR_ARG; }
@@ -191,6 +236,10 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     if (part) {
         launch_trgb_finish(part, ntn, d->B, d->Ho, p.trgb_b, part_yprev, yrgb, 0);
         if ((rc = finish())) return rc;
+    }
+    if (ytanh) {              // (p.y is not written)
+        GLASS_HIP(hipMemcpy(d->rgb_tanh, ytanh, nrgb * sizeof(float), hipMemcpyDeviceToHost));
+        return GLASS_OK;
     }
     if (yrgb) {
         GLASS_HIP(hipMemcpy(d->trgb_yout, yrgb, nrgb * sizeof(float), hipMemcpyDeviceToHost));
@@ -213,6 +262,34 @@ extern "C" int glass_op_gemm(int32_t device, int32_t M, int32_t N, int32_t K, co
     half_t* o16 = nullptr; float* o32 = nullptr;
     if (mode <= 1) { o16 = dv.alloc<half_t>(n); g.out16 = o16; }
     else { o32 = mode == 2 ? dv.up32(out, n) : dv.alloc<float>(n); g.out32 = o32; }
+    if (impl == 1) launch_gemm_direct(g, 0);
+    else if (impl == 2) {
+        if (!launch_gemm_tiled(g, 0)) { glass_set_error("tiled gemm: unsupported shape"); return GLASS_ERR_ARG; }
+    } else if (!launch_gemm_tiled(g, 0)) launch_gemm_direct(g, 0);
+    int rc = finish();
+    if (rc) return rc;
+    if (o16) return down16(out, o16, n);
+    GLASS_HIP(hipMemcpy(out, o32, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_gemm_batched(int32_t device, int32_t batch, int32_t M, int32_t N, int32_t K, const float* a, const float* w, int32_t mode,
+                                     int32_t cand_batch, int32_t impl, float* out) {
+    OPREQ(a && w && out && batch >= 1 && M > 0 && N > 0 && K > 0 && K % 16 == 0, "bad argument (K a multiple of 16)");
+    OPREQ(mode == 0 || mode == 3, "batched gemm: mode 0 (fp16 out) or 3 (fp32 out), the self-attention products");
+    OPREQ(impl >= 0 && impl <= 2, "impl must lie in [0, 2]");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)batch * M * N;
+    half_t* da = dv.up16(a, (size_t)batch * M * K);
+    half_t* dw = dv.up16(w, (size_t)batch * N * K);
+    half_t* o16 = mode == 0 ? dv.alloc<half_t>(n) : nullptr;
+    float* o32 = mode == 3 ? dv.alloc<float>(n) : nullptr;
+    OPREQ(da && dw && (o16 || o32), "device allocation failed");
+    GLASS_HIP(hipMemset(o16 ? (void*)o16 : (void*)o32, 0xFF, n * (o16 ? sizeof(half_t) : sizeof(float))));      // NaN: an element nobody stores shows
+    GemmParams g = gemm_params(da, dw, M, N, K, nullptr, mode, o16, o32, 0);      // as bg_attention (biggan.cpp)
+    g.cand_batch = cand_batch ? 1 : 0;
+    g.batch = batch; g.a_bs = (long long)M * K; g.w_bs = (long long)N * K; g.o_bs = (long long)M * N;
     if (impl == 1) launch_gemm_direct(g, 0);
     else if (impl == 2) {
         if (!launch_gemm_tiled(g, 0)) { glass_set_error("tiled gemm: unsupported shape"); return GLASS_ERR_ARG; }
@@ -636,6 +713,152 @@ extern "C" int glass_op_gpt2_embed_step(int32_t device, int32_t M, int32_t V, in
     if (rc) return rc;
     GLASS_HIP(hipMemcpy(x, dx, (size_t)M * K * sizeof(float), hipMemcpyDeviceToHost));
     GLASS_HIP(hipMemcpy(stats, ds, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+// ---- BigGAN-deep glue kernels (biggan_kernels.hip) and the fused last stage (bg_tail.hip), launched as biggan.cpp launches them ------------
+extern "C" int glass_op_bg_cond(int32_t device, int32_t P, int32_t L, int32_t zd, int32_t nc, const float* x, const float* et, float* cond) {
+    OPREQ(x && et && cond && P > 0 && zd > 0 && nc > 0 && L >= zd + nc, "bad argument (rows are [z (zd) | class bits (nc)], L >= zd + nc)");
+    OPREQ((size_t)(nc + 8) * sizeof(float) <= 64 * 1024, "bg_cond_kernel keeps the class probabilities in LDS: nc + 8 floats <= 64 KB");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dx = dv.up32(x, (size_t)P * L); float* de = dv.up32(et, (size_t)nc * zd);
+    float* dc = dv.alloc<float>((size_t)P * 2 * zd);
+    OPREQ(dx && de && dc, "device allocation failed");
+    GLASS_HIP(hipMemset(dc, 0xFF, (size_t)P * 2 * zd * sizeof(float)));
+    launch_bg_cond(dx, P, L, zd, nc, de, dc, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(cond, dc, (size_t)P * 2 * zd * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_bg_bn_tables(int32_t device, int32_t P, int32_t cd, int32_t C, const float* cond, const float* wt, const float* bias,
+                                     const float* inv_std, const float* mean, const float* prebias, float* tab, float* tab16) {
+    OPREQ(cond && wt && bias && inv_std && mean && prebias && tab && tab16 && P > 0 && cd > 0 && C > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)P * 2 * C;
+    float* dc = dv.up32(cond, (size_t)P * cd); float* dw = dv.up32(wt, (size_t)cd * 2 * C); float* db = dv.up32(bias, 2 * (size_t)C);
+    float* di = dv.up32(inv_std, C); float* dm = dv.up32(mean, C); float* dp = dv.up32(prebias, C);
+    float* dt = dv.alloc<float>(n);
+    half_t* dt16 = dv.alloc<half_t>(n);
+    OPREQ(dc && dw && db && di && dm && dp && dt && dt16, "device allocation failed");
+    GLASS_HIP(hipMemset(dt16, 0xFF, n * sizeof(half_t)));
+    // glass_biggan_prepare's three launches
+    launch_dense(dc, cd, P, cd, dw, 2 * C, db, dt, 2 * C, 0, 0, nullptr, 0, 0);
+    launch_bg_bn_tables(dt, P, C, di, dm, dp, 0);
+    launch_bg_to_half(dt, dt16, (long long)n, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(tab, dt, n * sizeof(float), hipMemcpyDeviceToHost));
+    return down16(tab16, dt16, n);
+}
+
+extern "C" int glass_op_bg_attn_split(int32_t device, int32_t B, int32_t H, int32_t W, int32_t c8, int32_t c2, const float* T, float* theta,
+                                      float* phi, float* gT, int32_t* vec) {
+    OPREQ(T && theta && phi && gT && vec && B > 0 && c8 > 0 && c2 > 0, "bad argument");
+    OPREQ(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "bg_attn_split: H and W must be even (2x2 max-pool)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t hw = (size_t)H * W, hq = hw / 4, CT = 2 * (size_t)c8 + c2;
+    half_t* dT = dv.up16(T, (size_t)B * hw * CT);
+    half_t* dth = dv.alloc<half_t>((size_t)B * hw * c8);
+    half_t* dph = dv.alloc<half_t>((size_t)B * hq * c8);
+    half_t* dg = dv.alloc<half_t>((size_t)B * hq * c2);
+    OPREQ(dT && dth && dph && dg, "device allocation failed");
+    GLASS_HIP(hipMemset(dth, 0xFF, (size_t)B * hw * c8 * sizeof(half_t)));      // NaN: an element nobody stores shows
+    GLASS_HIP(hipMemset(dph, 0xFF, (size_t)B * hq * c8 * sizeof(half_t)));
+    GLASS_HIP(hipMemset(dg, 0xFF, (size_t)B * hq * c2 * sizeof(half_t)));
+    const char* k = launch_bg_attn_split(dT, B, H, W, c8, c2, dth, dph, dg, 0);
+    *vec = strcmp(k, "bg_attn_split_vec_kernel") == 0;
+    int rc = finish();
+    if (rc) return rc;
+    if ((rc = down16(theta, dth, (size_t)B * hw * c8))) return rc;
+    if ((rc = down16(phi, dph, (size_t)B * hq * c8))) return rc;
+    return down16(gT, dg, (size_t)B * hq * c2);
+}
+
+extern "C" int glass_op_bg_softmax(int32_t device, int32_t rows, int32_t n, const float* S, float* out) {
+    OPREQ(S && out && rows > 0 && n > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t tot = (size_t)rows * n;
+    float* ds = dv.up32(S, tot);
+    half_t* dp = dv.alloc<half_t>(tot);
+    OPREQ(ds && dp, "device allocation failed");
+    GLASS_HIP(hipMemset(dp, 0xFF, tot * sizeof(half_t)));
+    launch_bg_softmax(ds, rows, n, dp, 0);
+    int rc = finish();
+    if (rc) return rc;
+    return down16(out, dp, tot);
+}
+
+extern "C" int glass_op_bg_rgb_tanh(int32_t device, int32_t B, int32_t hw, int32_t C, const float* x, float* y) {
+    OPREQ(x && y && B > 0 && hw > 0 && C >= 3, "bad argument (C >= 3)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    half_t* dx = dv.up16(x, (size_t)B * hw * C);
+    float* dy = dv.alloc<float>((size_t)B * 3 * hw);
+    OPREQ(dx && dy, "device allocation failed");
+    GLASS_HIP(hipMemset(dy, 0xFF, (size_t)B * 3 * hw * sizeof(float)));
+    launch_bg_rgb_tanh(dx, B, hw, C, dy, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(y, dy, (size_t)B * 3 * hw * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_bg_to_half(int32_t device, int64_t n, const float* x, float* out) {
+    OPREQ(x && out && n > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dx = dv.up32(x, (size_t)n);
+    half_t* dy = dv.alloc<half_t>((size_t)n + 4);      // four guard elements behind the output
+    OPREQ(dx && dy, "device allocation failed");
+    GLASS_HIP(hipMemset(dy, 0xFF, ((size_t)n + 4) * sizeof(half_t)));
+    launch_bg_to_half(dx, dy, n, 0);
+    int rc = finish();
+    if (rc) return rc;
+    uint16_t guard[4];
+    GLASS_HIP(hipMemcpy(guard, dy + n, sizeof guard, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) OPREQ(guard[i] == 0xFFFFu, "bg_to_half stored past element n");
+    return down16(out, dy, (size_t)n);
+}
+
+extern "C" int glass_op_bg_tail(int32_t device, int32_t B, int32_t R, int32_t mid, const float* h, const float* x0, const float* w3, const float* b3,
+                                const float* bn_a, const float* bn_s, const float* rgb_w, const float* rgb_b, float* y) {
+    OPREQ(h && x0 && w3 && b3 && bn_a && bn_s && rgb_w && rgb_b && y && B > 0 && R > 0 && mid > 0, "bad argument");
+    const int C = 128, cpad = 32;                           // the last block's width; BgState::rgb_cpad
+    OPREQ(bg_tail_supported(R, mid, C, C, 1, cpad), "bg_tail: unsupported shape (R % 32 == 0, R >= 32, mid == 32, 128 -> 128 channels of an up block)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const int R2 = R / 2;
+    std::vector<_Float16> pk((size_t)9 * cpad * C, (_Float16)0.f);      // [tap][cpad][128], rows 0..2 used (biggan.cpp pack())
+    for (int o = 0; o < 3; ++o)
+        for (int i = 0; i < C; ++i)
+            for (int t = 0; t < 9; ++t) pk[((size_t)t * cpad + o) * C + i] = (_Float16)rgb_w[((size_t)o * C + i) * 9 + t];
+    std::vector<float> tab(2 * (size_t)C), rb(cpad, 0.f);
+    for (int c = 0; c < C; ++c) { tab[c] = bn_a[c]; tab[C + c] = bn_s[c]; }
+    for (int c = 0; c < 3; ++c) rb[c] = rgb_b[c];
+    BgTailParams tp;
+    memset(&tp, 0, sizeof tp);
+    tp.h = dv.up16(h, (size_t)B * R * R * mid);
+    tp.x0 = dv.up16(x0, (size_t)B * R2 * R2 * C);
+    tp.w3 = dv.up16(w3, (size_t)C * mid);
+    tp.b3 = dv.up32(b3, C);
+    tp.tab = dv.up32(tab.data(), tab.size()); tp.bnf_off = 0; tp.ctot = C;
+    tp.rgb_w = dv.up16v(pk); tp.cpad = cpad;
+    tp.rgb_b = dv.up32(rb.data(), rb.size());
+    const size_t ny = (size_t)B * 3 * R * R;
+    float* dy = dv.alloc<float>(ny);
+    tp.y = dy; tp.B = B; tp.R = R;
+    OPREQ(tp.h && tp.x0 && tp.w3 && tp.b3 && tp.tab && tp.rgb_w && tp.rgb_b && dy, "device allocation failed");
+    GLASS_HIP(hipMemset(dy, 0xFF, ny * sizeof(float)));      // NaN: a pixel no tile writes shows
+    OPREQ(launch_bg_tail(tp, 0), "bg_tail: the launcher refused the shape");
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(y, dy, ny * sizeof(float), hipMemcpyDeviceToHost));
     return GLASS_OK;
 }
 

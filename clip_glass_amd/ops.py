@@ -26,7 +26,9 @@ class ConvDesc(C.Structure):
                 ("skip_x", C.POINTER(C.c_float)), ("skip_w", C.POINTER(C.c_float)), ("xs_out", C.POINTER(C.c_float)),
                 ("x_planar8", C.c_int32), ("x_planar32", C.c_int32),
                 ("premod", C.c_int32), ("post_scale", C.POINTER(C.c_float)), ("y_planar8", C.c_int32),
-                ("trgb_partial", C.c_int32)]
+                ("trgb_partial", C.c_int32),
+                ("pre_shift", C.POINTER(C.c_float)), ("in_up", C.c_int32), ("shift", C.POINTER(C.c_float)),
+                ("res_cs", C.c_int32), ("res_up", C.c_int32), ("rgb_tanh", C.POINTER(C.c_float))]
 
 
 def to_planar8(a):
@@ -59,7 +61,7 @@ def _opt(a):
 def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None, noise_strength=0.0,
          batch_size=1, bias=None, act=False, res=None, out_scale=1.0, impl=0, broadcast_x=False, B=None, device=0,
          torgb=None, skip=None, xs_out=None, planar_x=False, both=False, planar32_x=False, premod=False, post_scale=None,
-         planar_y=False, trgb_partial=False):
+         planar_y=False, trgb_partial=False, pre_shift=None, in_up=False, shift=None, res_cs=0, res_up=False, rgb_tanh=False):
     """x [B,H,W,Cin] NHWC; w [Cout,Cin,KS,KS] (reference layout).  Returns y [B,Ho,Wo,Cout].
     torgb = dict(w [3,Cout], b [3], sn [B,Cout], smax [B], yprev [B,3,Ho/2,Wo/2] or None) with impl=4: the fused conv + toRGB
     form of the streaming kernel — returns the skip image [B,3,Ho,Wo] instead of y.
@@ -67,10 +69,16 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
     The forms the StyleGAN2 host builds (csrc/stylegan2.cpp): premod — sn / dscale go into per-sample weights first
     (modulate_weights_kernel) and the conv runs without them; post_scale [B,Cout] — the consumer's style applied to the finished
     output (fused up-conv); planar_y — the device stores y chunk-planar (un-permuted here); trgb_partial — with torgb and impl 5: toRGB
-    partial sums per 128-wide n tile + the finishing pass."""
+    partial sums per 128-wide n tile + the finishing pass.
+    The forms the BigGAN host builds (csrc/biggan.cpp bg_conv): pre_shift [B,Cin] with sn — relu(x * sn + pre_shift) while staging, the zero
+    padding stays zero; in_up — x is [B,H/2,W/2,Cin], read through a nearest x2 upsample; shift [B,Cout] — added after the bias (act=2:
+    ReLU); res [B,Ho >> res_up,Wo >> res_up,res_cs or Cout] — the first Cout channels, nearest x2 with res_up; rgb_tanh — returns
+    tanh(channels 0..2) [B,3,Ho,Wo] from the accumulators instead of y (conv_tiled only)."""
     lib = load_library()
     x = _f32(x); w = _f32(w)
     Bx, H, W, Cin = x.shape
+    if in_up:
+        H, W = 2 * H, 2 * W
     if planar_x:
         x = to_planar8(x)
     if planar32_x:            # conv_s2's input in 32-channel planes (permuted here)
@@ -91,9 +99,11 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
     d.x_planar8 = int(planar_x)
     d.x_planar32 = int(planar32_x)
     d.premod, d.y_planar8, d.trgb_partial = int(premod), int(planar_y), int(trgb_partial)
+    d.in_up, d.res_cs, d.res_up = int(in_up), int(res_cs), int(res_up)
     keep = []
     d.x, d.w, d.y = _fp(x), _fp(w), _fp(y)
-    for name, val in (("sn", sn), ("dscale", dscale), ("noise", noise), ("bias", bias), ("res", res), ("post_scale", post_scale)):
+    for name, val in (("sn", sn), ("dscale", dscale), ("noise", noise), ("bias", bias), ("res", res), ("post_scale", post_scale),
+                      ("pre_shift", pre_shift), ("shift", shift)):
         a, p = _opt(val)
         keep.append(a)
         if p is not None:
@@ -114,8 +124,14 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
             if p is not None:
                 setattr(d, "trgb_" + name, p)
         d.trgb_yout = _fp(yrgb)
+    ytanh = None
+    if rgb_tanh:
+        ytanh = np.empty((B, 3, Ho, Wo), dtype=np.float32)
+        d.rgb_tanh = _fp(ytanh)
     lib.glass_op_conv.argtypes = [C.c_int32, C.POINTER(ConvDesc)]
     _check(lib, lib.glass_op_conv(device, C.byref(d)))
+    if rgb_tanh:
+        return ytanh
     if planar_y:
         y = from_planar8(y, B, Ho, Wo, Cout)
     if both:                  # fused toRGB forms that store the feature map too (impl 2 / 5): (skip image, feature map)
@@ -132,6 +148,21 @@ def gemm(a, w, bias=None, mode=3, impl=0, acc=None, device=0):
     b, bp = _opt(bias)
     lib.glass_op_gemm.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_float)] * 3 + [C.c_int32, C.c_int32, C.POINTER(C.c_float)]
     _check(lib, lib.glass_op_gemm(device, M, N, K, _fp(a), _fp(w), bp, mode, impl, _fp(out)))
+    return out
+
+
+def gemm_batched(a, w, mode=3, cand_batch=True, impl=0, device=0):
+    """a [batch,M,K], w [batch,N,K] -> out [batch,M,N] = a[z] @ w[z]^T, set up as the BigGAN self-attention products (csrc/biggan.cpp
+    bg_attention).  mode 3: fp32 out, 0: fp16 out.  impl 0: gemm_tiled, then gemm_direct where it refuses; 1: direct; 2: tiled."""
+    lib = load_library()
+    a = _f32(a); w = _f32(w)
+    batch, M, K = a.shape
+    N = w.shape[1]
+    assert w.shape == (batch, N, K)
+    out = np.empty((batch, M, N), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_gemm_batched.argtypes = [C.c_int32] * 5 + [fp, fp] + [C.c_int32] * 3 + [fp]
+    _check(lib, lib.glass_op_gemm_batched(device, batch, M, N, K, _fp(a), _fp(w), int(mode), int(cand_batch), int(impl), _fp(out)))
     return out
 
 
@@ -401,6 +432,105 @@ def gpt2_embed_step(token, wte, wpe, past, step, device=0):
     _check(lib, lib.glass_op_gpt2_embed_step(device, M, V, K, tok.ctypes.data_as(ip), _fp(wte), _fp(wpe), wpe.shape[0], int(past), int(step),
                                              _fp(x), _fp(stats)))
     return x, stats
+
+
+def bg_cond(x, et, zd, device=0):
+    """bg_cond_kernel: population rows x [P, zd + nc] = [z | class bits], et = E^T [nc, zd] -> cond [P, 2 zd] = [clip(z, -2, 2) | softmax @ E^T]."""
+    lib = load_library()
+    x, et = _f32(x), _f32(et)
+    P, L = x.shape
+    nc = et.shape[0]
+    assert et.shape == (nc, zd) and L >= zd + nc
+    cond = np.empty((P, 2 * zd), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_bg_cond.argtypes = [C.c_int32] * 5 + [fp] * 3
+    _check(lib, lib.glass_op_bg_cond(device, P, L, zd, nc, _fp(x), _fp(et), _fp(cond)))
+    return cond
+
+
+def bg_bn_tables(cond, wt, bias, inv_std, mean, prebias, device=0):
+    """The three launches of glass_biggan_prepare (dense + bg_bn_tables_kernel + bg_to_half_kernel): cond [P, cd], wt [cd, 2C] (gain | offset
+    columns), bias [2C], inv_std / mean / prebias [C] -> (tab [P, 2C] = [A | S] float32, tab16: its fp16 copy as float32 values)."""
+    lib = load_library()
+    cond, wt, bias, inv_std, mean, prebias = (_f32(a) for a in (cond, wt, bias, inv_std, mean, prebias))
+    P, cd = cond.shape
+    Cc = inv_std.shape[0]
+    assert wt.shape == (cd, 2 * Cc) and bias.shape == (2 * Cc,) and mean.shape == (Cc,) and prebias.shape == (Cc,)
+    tab = np.empty((P, 2 * Cc), dtype=np.float32)
+    tab16 = np.empty((P, 2 * Cc), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_bg_bn_tables.argtypes = [C.c_int32] * 4 + [fp] * 8
+    _check(lib, lib.glass_op_bg_bn_tables(device, P, cd, Cc, _fp(cond), _fp(wt), _fp(bias), _fp(inv_std), _fp(mean), _fp(prebias), _fp(tab),
+                                          _fp(tab16)))
+    return tab, tab16
+
+
+def bg_attn_split(T, c8, c2, device=0):
+    """T [B,H,W,2 c8 + c2] (theta | phi | g) -> (theta [B,HW,c8], phi [B,HW/4,c8], gT [B,c2,HW/4], kernel name): the split + 2x2
+    max-pool + transpose of the self-attention block; the name says which of the launcher's two kernels ran."""
+    lib = load_library()
+    T = _f32(T)
+    B, H, W, CT = T.shape
+    assert CT == 2 * c8 + c2
+    hw = H * W
+    theta = np.empty((B, hw, c8), dtype=np.float32)
+    phi = np.empty((B, hw // 4, c8), dtype=np.float32)
+    gT = np.empty((B, c2, hw // 4), dtype=np.float32)
+    vec = C.c_int32(-1)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_bg_attn_split.argtypes = [C.c_int32] * 6 + [fp] * 4 + [C.POINTER(C.c_int32)]
+    _check(lib, lib.glass_op_bg_attn_split(device, B, H, W, c8, c2, _fp(T), _fp(theta), _fp(phi), _fp(gT), C.byref(vec)))
+    return theta, phi, gT, "bg_attn_split_vec_kernel" if vec.value == 1 else "bg_attn_split_kernel"
+
+
+def bg_softmax(S, device=0):
+    """Row softmax S [rows, n] float32 -> [rows, n] (the kernel's fp16 values)."""
+    lib = load_library()
+    S = _f32(S)
+    rows, n = S.shape
+    out = np.empty((rows, n), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_bg_softmax.argtypes = [C.c_int32] * 3 + [fp, fp]
+    _check(lib, lib.glass_op_bg_softmax(device, rows, n, _fp(S), _fp(out)))
+    return out
+
+
+def bg_rgb_tanh(x, device=0):
+    """x [B, hw, C] (rounded to fp16) -> [B, 3, hw] = tanh of channels 0..2, planar float32."""
+    lib = load_library()
+    x = _f32(x)
+    B, hw, Cc = x.shape
+    y = np.empty((B, 3, hw), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_bg_rgb_tanh.argtypes = [C.c_int32] * 4 + [fp, fp]
+    _check(lib, lib.glass_op_bg_rgb_tanh(device, B, hw, Cc, _fp(x), _fp(y)))
+    return y
+
+
+def bg_to_half(x, device=0):
+    """bg_to_half_kernel on a flat float32 array of any length -> its fp16 values (as float32)."""
+    lib = load_library()
+    x = _f32(x).reshape(-1)
+    out = np.empty(x.shape, dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_bg_to_half.argtypes = [C.c_int32, C.c_int64, fp, fp]
+    _check(lib, lib.glass_op_bg_to_half(device, x.shape[0], _fp(x), _fp(out)))
+    return out
+
+
+def bg_tail(h, x0, w3, b3, bn_a, bn_s, rgb_w, rgb_b, device=0):
+    """BigGAN-deep's fused last stage (bg_tail.hip): h [B,R,R,mid] (= relu(bn_3(conv_2))), x0 [B,R/2,R/2,128] (the block input), w3 [128,mid],
+    b3 [128], the final bn's folded A / S [128], rgb_w [3,128,3,3], rgb_b [3] -> tanh(conv_to_rgb(relu(bn(conv_3(h) + up(x0))))) [B,3,R,R]."""
+    lib = load_library()
+    h, x0, w3, b3, bn_a, bn_s, rgb_w, rgb_b = (_f32(a) for a in (h, x0, w3, b3, bn_a, bn_s, rgb_w, rgb_b))
+    B, R, _, mid = h.shape
+    assert w3.shape[0] == 128 and w3.size == 128 * mid and rgb_w.shape == (3, 128, 3, 3) and b3.shape == bn_a.shape == bn_s.shape == (128,)
+    assert x0.shape == (B, R // 2, R // 2, 128) and rgb_b.shape == (3,)
+    y = np.empty((B, 3, R, R), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_bg_tail.argtypes = [C.c_int32] * 4 + [fp] * 9
+    _check(lib, lib.glass_op_bg_tail(device, B, R, mid, _fp(h), _fp(x0), _fp(w3), _fp(b3), _fp(bn_a), _fp(bn_s), _fp(rgb_w), _fp(rgb_b), _fp(y)))
+    return y
 
 
 def mfma_probe(a, b, device=0):

@@ -5,6 +5,10 @@
  * kernel's fp16/fp32 layouts internally), so tests/ can compare every kernel against
  * the oracle's corresponding torch op in isolation.  All return GLASS_OK or a negative
  * status (glass_last_error()).  Layouts are NHWC for activations.
+ *
+ * Families: the convolution forms of the StyleGAN2 and BigGAN hosts (glass_op_conv), the GEMMs (glass_op_gemm, glass_op_gemm_batched),
+ * the StyleGAN2 / CLIP glue kernels, the GPT-2 trunk (glass_op_gpt2_*) and the BigGAN-deep glue kernels and fused tail (glass_op_bg_*;
+ * tests/test_gpu_biggan_ops.py against the float64 restatements of tests/biggan_ops_ref.py).
  */
 #ifndef GLASS_OPS_H
 #define GLASS_OPS_H
@@ -56,12 +60,27 @@ typedef struct glass_conv_desc {
     /* impl 5 with the trgb_* inputs, Cout a multiple of 128, Ho == Wo: the conv writes toRGB partial sums per 128-wide n tile
      * (ConvParams::trgb_part, NaN-filled before the launch), launch_trgb_finish adds them into trgb_yout; y is returned too */
     int32_t trgb_partial;
+    /* The forms only the BigGAN host builds (biggan.cpp bg_conv).  A launcher that refuses one is an error. */
+    const float* pre_shift;  /* [B,Cin] or NULL, needs sn: x <- relu(x * sn + pre_shift) while staging, the zero padding stays zero.  The op uploads ONE
+                              * per-candidate table [sn | pre_shift] (row stride 2 Cin) and its fp16 copy, as bg_conv points into tab / tab16 */
+    int32_t in_up;           /* x is [B,H/2,W/2,Cin], read through a nearest x2 upsample; H, W are the upsampled dims */
+    const float* shift;      /* [B,Cout] or NULL: added after the bias (act 2 = ReLU then); uploaded as one table [dscale | shift], ds_stride 2 Cout
+                              * (the dscale columns are ones where dscale is NULL) */
+    int32_t res_cs;          /* channel stride of the residual rows (0 = Cout): the first Cout of res_cs channels are added (channel-drop skip) */
+    int32_t res_up;          /* res is [B,Ho/2,Wo/2,res_cs ? res_cs : Cout], read through a nearest x2 upsample */
+    float* rgb_tanh;         /* [B,3,Ho,Wo] or NULL: tanh of output channels 0..2 from the accumulators (ConvParams::rgb_tanh_out), y is not written.
+                              * As run_conv: conv_tiled only (impl 0 / 2); any other impl, or a refusal, is an error */
 } glass_conv_desc;
 
 int glass_op_conv(int32_t device, const glass_conv_desc* d);
 /* out[M,N] = epi(a[M,K] @ w[N,K]^T + bias); mode as GemmParams (0 plain,1 quickgelu,2 +=,3 f32,4 lrelu) */
 int glass_op_gemm(int32_t device, int32_t M, int32_t N, int32_t K, const float* a, const float* w,
                   const float* bias, int32_t mode, int32_t impl, float* out);
+/* `batch` problems out[z] = a[z] [M,K] @ w[z] [N,K]^T set up as bg_attention (biggan.cpp) sets the self-attention products up: blockIdx.z
+ * walks the problems a_bs = M K / w_bs = N K / o_bs = M N elements apart, cand_batch as given.  mode 3 (fp32 out) or 0 (fp16 out).
+ * impl 0: gemm_tiled, then gemm_direct where it refuses (as the host); 1: gemm_direct; 2: gemm_tiled (error if it refuses) */
+int glass_op_gemm_batched(int32_t device, int32_t batch, int32_t M, int32_t N, int32_t K, const float* a, const float* w, int32_t mode,
+                          int32_t cand_batch, int32_t impl, float* out);
 int glass_op_dense(int32_t device, int32_t P, int32_t K, int32_t N, const float* x, const float* wt /*[K,N]*/,
                    const float* bias, int32_t in_sq, int32_t mode, const float* eps_row, float* out);
 int glass_op_torgb(int32_t device, int32_t B, int32_t H, int32_t C, const float* x, const float* wrgb /*[3,C] scaled*/,
@@ -133,6 +152,28 @@ int glass_op_gpt2_head(int32_t device, int32_t M, int32_t V, int32_t K, int32_t 
  * of a step's first operand (token [M] = the previous step's picks). */
 int glass_op_gpt2_embed_step(int32_t device, int32_t M, int32_t V, int32_t K, const int32_t* token, const float* wte, const float* wpe,
                              int32_t npos, int32_t past, int32_t step, float* x, float* stats);
+/* The BigGAN-deep glue kernels (biggan_kernels.hip) and the fused last stage (bg_tail.hip), each launched as biggan.cpp launches it.
+ *
+ * glass_op_bg_cond: launch_bg_cond on population rows x [P,L] = [z (zd) | class bits (nc) | ...], et = E^T [nc,zd] -> cond [P, 2 zd].
+ * glass_op_bg_bn_tables: the three launches of glass_biggan_prepare — launch_dense (cond [P,cd] x wt [cd,2C] + bias [2C]),
+ *   launch_bg_bn_tables (inv_std / mean / prebias [C]) and launch_bg_to_half -> tab [P,2C] = [A | S] fp32 and tab16, its fp16 copy.
+ * glass_op_bg_attn_split: T [B,H,W,2 c8 + c2] (theta | phi | g) -> theta [B,HW,c8], phi [B,HW/4,c8], gT [B,c2,HW/4]; *vec = 1 when the
+ *   launcher took bg_attn_split_vec_kernel, 0 for bg_attn_split_kernel (H, W even).
+ * glass_op_bg_softmax: S [rows,n] fp32 -> row softmax [rows,n] (fp16 values).
+ * glass_op_bg_rgb_tanh: x [B,hw,C] (fp16) -> y [B,3,hw] = tanh of channels 0..2.
+ * glass_op_bg_to_half: x [n] -> out [n] (fp16 values), any n.
+ * glass_op_bg_tail: h [B,R,R,mid], x0 [B,R/2,R/2,128], w3 [128,mid], b3 [128], the final bn's A / S [128], rgb_w [3,128,3,3], rgb_b [3]
+ *   -> y [B,3,R,R]; refused where bg_tail_supported says no (R % 32 == 0, mid == 32).  Weights are taken as given (no coefficient). */
+int glass_op_bg_cond(int32_t device, int32_t P, int32_t L, int32_t zd, int32_t nc, const float* x, const float* et, float* cond);
+int glass_op_bg_bn_tables(int32_t device, int32_t P, int32_t cd, int32_t C, const float* cond, const float* wt, const float* bias,
+                          const float* inv_std, const float* mean, const float* prebias, float* tab, float* tab16);
+int glass_op_bg_attn_split(int32_t device, int32_t B, int32_t H, int32_t W, int32_t c8, int32_t c2, const float* T, float* theta, float* phi,
+                           float* gT, int32_t* vec);
+int glass_op_bg_softmax(int32_t device, int32_t rows, int32_t n, const float* S, float* out);
+int glass_op_bg_rgb_tanh(int32_t device, int32_t B, int32_t hw, int32_t C, const float* x, float* y);
+int glass_op_bg_to_half(int32_t device, int64_t n, const float* x, float* out);
+int glass_op_bg_tail(int32_t device, int32_t B, int32_t R, int32_t mid, const float* h, const float* x0, const float* w3, const float* b3,
+                     const float* bn_a, const float* bn_s, const float* rgb_w, const float* rgb_b, float* y);
 /* raw MFMA layout probe: D = A[32x16] * B[16x32] through the fragment mapping of common.h */
 int glass_op_mfma_probe(int32_t device, const float* a /*[32,16]*/, const float* b /*[16,32]*/, float* d /*[32,32]*/);
 

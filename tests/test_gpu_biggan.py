@@ -111,8 +111,9 @@ def test_biggan_512_full_population():
 
 
 def test_biggan_512_eight_candidates_streaming_kernels():
-    """P = 8 makes the 512^2 layers large enough (>= 4096 tiles) for conv_stream (nearest-up input addressing and the
-    fused bn shift + relu epilogue), which the two-candidate case leaves to conv_tiled."""
+    """P = 8 makes the 512^2 layers large enough (>= 4096 tiles) for conv_stream (the fused bn shift + relu epilogue of conv_2; the
+    streaming kernel refuses in_up, so conv_1's nearest-up input addressing stays on conv_tiled), which the two-candidate case leaves
+    to conv_tiled."""
     _run_case("bg512", 8, 8)
 
 
