@@ -304,7 +304,9 @@ __global__ __launch_bounds__(256, 2) void conv_down_kernel(DownParams p, int til
     }
 }
 
+// One decision point for both channel pairs: 32 -> 64 runs here, 64 -> 128 on conv_down64.hip.
 bool conv_down_supported(int R, int Cin, int Cout) {
+    if (Cin == 64) return conv_down64_supported(R, Cin, Cout);
     return glass_lds_fits(LDS_BYTES) && R % 64 == 0 && R >= 64 && Cin == CIN && Cout == NT && (long long)R * R * Cin < (1LL << 31);
 }
 
@@ -312,6 +314,7 @@ bool conv_down_supported(int R, int Cin, int Cout) {
 const char* launch_conv_down(const half_t* h, const half_t* xs, const half_t* w1, const half_t* ws, const float* b1, half_t* y,
                              int B, int R, int Cin, int Cout, hipStream_t st) {
     if (!conv_down_supported(R, Cin, Cout)) return nullptr;
+    if (Cin == 64) return launch_conv_down64(h, xs, w1, ws, b1, y, B, R, Cin, Cout, st);
     DownParams p;
     p.h = h; p.xs = xs; p.w1 = w1; p.ws = ws; p.b1 = b1; p.y = y; p.B = B; p.R = R;
     const int Ro = R / 2, tiles_x = Ro / 32, tiles_y = Ro / TH;

@@ -30,6 +30,10 @@ const char* launch_conv_s2(const ConvParams& p, hipStream_t st, bool force = fal
 const char* launch_conv_down(const half_t* h, const half_t* xs, const half_t* w1, const half_t* ws, const float* b1, half_t* y,
                              int B, int R, int Cin, int Cout, hipStream_t st);
 bool conv_down_supported(int R, int Cin, int Cout);
+// the same op at 64 -> 128 channels (conv_down64.hip: weights in registers, rolling column walk); reached through the two above
+const char* launch_conv_down64(const half_t* h, const half_t* xs, const half_t* w1, const half_t* ws, const float* b1, half_t* y,
+                               int B, int R, int Cin, int Cout, hipStream_t st);
+bool conv_down64_supported(int R, int Cin, int Cout);
 // the WHOLE full-resolution discriminator block in one kernel (conv_d0.hip): skip image -> fromRGB -> conv3x3 32 -> 32 -> FIR (pad 2) ->
 // conv3x3 stride 2 32 -> 64, + the 1x1 skip branch of FIR (pad 1)[::2] of the fromRGB map, merged; x and h never leave the CU.
 // nullptr when the block does not qualify (caller: conv_stream<fromrgb> + conv_down)

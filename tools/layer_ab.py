@@ -67,14 +67,16 @@ def main():
         for mode in (2, 0):
             print("%-60s" % ("wall ms per pass, stream mode %d (median / min of %d x %d)" % (mode, a.rounds, a.timed)) +
                   "".join("%10s" % ("%.2f/%.2f" % (float(np.median(wall[n][mode])), min(wall[n][mode]))) for n in names))
-    rows = [k for k in data[names[0]] if pat.search(k) and k != "~pass"]
+    rows = []        # every library's matching tags, in first-seen order (a build may launch a layer under another tag)
+    for n in names:
+        rows += [k for k in data[n] if pat.search(k) and k != "~pass" and k not in rows]
     print("%-60s" % ("median us per launch, %d interleaved rounds" % a.rounds) + "".join("%10s" % n[:9] for n in names))
     sums = {n: 0.0 for n in names}
     for k in rows:
         line = "%-60s" % k[:60]
         for n in names:
-            v = float(np.median(data[n].get(k, [float("nan")])))
-            sums[n] += v
+            v = float(np.median(data[n][k])) if k in data[n] else float("nan")
+            sums[n] += 0.0 if np.isnan(v) else v
             line += "%10.1f" % v
         print(line)
     print("%-60s" % "sum of the rows" + "".join("%10.1f" % sums[n] for n in names))
