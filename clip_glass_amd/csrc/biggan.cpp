@@ -285,9 +285,8 @@ struct BgConv {
     const half_t* resid = nullptr;
     int res_cs = 0, res_up = 0;
     float* rgb_tanh = nullptr;      // planar tanh(channels 0..2) instead of y (ConvParams::rgb_tanh_out)
-    bool dry = false;               // only ask whether conv_tiled takes the layer in that form
 };
-bool bg_conv(glass_engine* e, const char* tag, int c0, int B, const BgConv& q) {
+ConvParams bg_conv_params(glass_engine* e, int c0, int B, const BgConv& q) {
     BgState& g = e->bg;
     ConvParams p = conv_defaults();
     const int rin = q.res >> q.in_up;
@@ -319,15 +318,18 @@ bool bg_conv(glass_engine* e, const char* tag, int c0, int B, const BgConv& q) {
     p.res_up = q.res_up;
     p.y = q.y;
     p.rgb_tanh_out = q.rgb_tanh;
-    if (q.dry) {
-        p.dry_run = 1;
-        return launch_conv_tiled(p, e->cur) != nullptr;
-    }
+    return p;
+}
+// chosen: the kernel the caller already asked a chooser for (empty: run_conv's order)
+void bg_conv(glass_engine* e, const char* tag, int c0, int B, const BgConv& q, const ConvKernel& chosen = ConvKernel()) {
+    const int rin = q.res >> q.in_up;
     const double M = (double)B * q.res * q.res, Min = (double)B * rin * rin;
     const double rbytes = q.resid ? M * q.cout / (q.res_up ? 4 : 1) : 0.0;
-    run_conv(e, p, tag, 2.0 * M * q.cout * q.cin * q.ks * q.ks,
-             2.0 * (Min * q.cin + (q.rgb_tanh ? M * 6.0 : M * q.cout) + rbytes + (double)q.cout * q.cin * q.ks * q.ks));
-    return true;
+    const double flops = 2.0 * M * q.cout * q.cin * q.ks * q.ks;
+    const double bytes = 2.0 * (Min * q.cin + (q.rgb_tanh ? M * 6.0 : M * q.cout) + rbytes + (double)q.cout * q.cin * q.ks * q.ks);
+    const ConvParams p = bg_conv_params(e, c0, B, q);
+    if (chosen) run_chosen(e, chosen, p, tag, flops, bytes);
+    else run_conv(e, p, tag, flops, bytes);
 }
 
 void bg_attention(glass_engine* e, int B, const half_t* x, half_t* y) {
@@ -464,10 +466,8 @@ int glass_biggan_chunk(glass_engine* e, int c0, int B, float* y) {
         // P = 64) and the pass that re-read it are gone.  (Small test geometries the instance does not take keep the two-pass form.)
         BgConv qd = q;
         qd.rgb_tanh = y;
-        qd.dry = true;
-        if (bg_conv(e, "bg.final.conv_to_rgb", c0, B, qd)) {
-            qd.dry = false;
-            bg_conv(e, "bg.final.conv_to_rgb+tanh", c0, B, qd);
+        if (const ConvKernel k = choose_conv(bg_conv_params(e, c0, B, qd))) {
+            bg_conv(e, "bg.final.conv_to_rgb+tanh", c0, B, qd, k);
         } else {
             bg_conv(e, "bg.final.conv_to_rgb", c0, B, q);
             Prof pr(e, "bg.final.tanh", 0, B * (double)R * R * (2.0 * g.rgb_cpad + 12.0));

@@ -220,7 +220,6 @@ struct ConvParams {
     // top of it (no separate 1x1 pass, no fp16 round trip of its result)
     const half_t* skip_x;   // [B][Ho][Wo][Cin] (nullable)
     const half_t* skip_w;   // [Neff][Cin]
-    int dry_run;            // conv_tiled / conv_glds launchers: report the kernel that would run, launch nothing
     // chunk-planar activation maps [B][C / 8][H][W][8] (round 6): conv_wreg stages the 16-channel chunks of its input at different times,
     // and in the pixel-major layout the pieces of every 128-byte line crossed the fabric once per chunk (the first LDS-resident form of this layer, two
     // 32-channel chunks: 4.6 GB fetched per launch for 2.15 GB of input, PMC).  With 8-channel planes a line belongs to ONE chunk and a
@@ -235,6 +234,82 @@ struct ConvParams {
     half_t* y;              // output [B][Ho][Wo][Cout] fp16 (or)
     float* y32;             // output fp32, same layout
 };
+
+// What a launch asks for beyond what every conv family does (bias, act, out_scale): one bit per capability.  A family states the mask it
+// implements next to its kernel and refuses `conv_features(p) & ~mask` before it looks at the geometry — a feature is refused, never ignored.
+enum ConvFeature : uint32_t {
+    CF_UP = 1u << 0,           // up
+    CF_STYLE = 1u << 1,        // sn / sn16: activation-side style
+    CF_PRE_SHIFT = 1u << 2,    // pre_shift / pre_shift16
+    CF_IN_UP = 1u << 3,        // in_up
+    CF_DEMOD = 1u << 4,        // dscale
+    CF_SHIFT = 1u << 5,        // shift
+    CF_NOISE = 1u << 6,        // noise
+    CF_RES = 1u << 7,          // res
+    CF_RES_CS = 1u << 8,       // res_cs: the residual's rows are wider than Cout
+    CF_RES_UP = 1u << 9,       // res_up
+    CF_Y32 = 1u << 10,         // y32: fp32 output
+    CF_SAMPLE_W = 1u << 11,    // w_bstride: per-sample weights
+    CF_BCAST_X = 1u << 12,     // x_bstride == 0 with B > 1: one input map for every candidate
+    CF_FROMRGB = 1u << 13,     // rgb_y: the input map built from the skip image
+    CF_TORGB = 1u << 14,       // trgb_yout: toRGB image out
+    CF_NO_MAP = 1u << 15,      // trgb_yout without y: the feature map is not stored
+    CF_TORGB_PART = 1u << 16,  // trgb_part: toRGB partial sums per n tile
+    CF_RGB_TANH = 1u << 17,    // rgb_tanh_out: planar tanh of channels 0..2
+    CF_XS_OUT = 1u << 18,      // xs_out: blur-down of the input as a by-product
+    CF_POST_SCALE = 1u << 19,  // post_scale16
+    CF_SKIP = 1u << 20,        // skip_x: the D block's 1x1 skip branch as extra K stages
+    CF_X_PLANAR8 = 1u << 21,   // x_planar8
+    CF_Y_PLANAR8 = 1u << 22,   // y_planar8
+    CF_X_PLANAR32 = 1u << 23,  // x_planar32
+    CF_COUNT = 24
+};
+inline uint32_t conv_features(const ConvParams& p) {
+    uint32_t f = 0;
+    if (p.up) f |= CF_UP;
+    if (p.sn || p.sn16) f |= CF_STYLE;
+    if (p.pre_shift || p.pre_shift16) f |= CF_PRE_SHIFT;
+    if (p.in_up) f |= CF_IN_UP;
+    if (p.dscale) f |= CF_DEMOD;
+    if (p.shift) f |= CF_SHIFT;
+    if (p.noise) f |= CF_NOISE;
+    if (p.res) f |= CF_RES;
+    if (p.res_cs) f |= CF_RES_CS;
+    if (p.res_up) f |= CF_RES_UP;
+    if (p.y32) f |= CF_Y32;
+    if (p.w_bstride) f |= CF_SAMPLE_W;
+    if (p.x_bstride == 0 && p.B > 1) f |= CF_BCAST_X;
+    if (p.rgb_y) f |= CF_FROMRGB;
+    if (p.trgb_yout) f |= CF_TORGB;
+    if (p.trgb_yout && !p.y) f |= CF_NO_MAP;
+    if (p.trgb_part) f |= CF_TORGB_PART;
+    if (p.rgb_tanh_out) f |= CF_RGB_TANH;
+    if (p.xs_out) f |= CF_XS_OUT;
+    if (p.post_scale16) f |= CF_POST_SCALE;
+    if (p.skip_x) f |= CF_SKIP;
+    if (p.x_planar8) f |= CF_X_PLANAR8;
+    if (p.y_planar8) f |= CF_Y_PLANAR8;
+    if (p.x_planar32) f |= CF_X_PLANAR32;
+    return f;
+}
+// the name of a feature bit as a refusal message spells it (the diagnostic ops' argument names)
+inline const char* conv_feature_name(int bit) {
+    static const char* const names[CF_COUNT] = {
+        "up", "sn (activation-side style)", "pre_shift", "in_up", "dscale", "shift", "noise", "res", "res_cs", "res_up", "y32 (fp32 output)",
+        "premod (per-sample weights)", "broadcast_x", "rgb_y (fused fromRGB)", "trgb_yout (fused toRGB)", "trgb_yout without y (map not stored)",
+        "trgb_partial", "rgb_tanh", "xs_out", "post_scale", "skip_x (fused skip)", "x_planar8", "y_planar8", "x_planar32"};
+    return bit >= 0 && bit < CF_COUNT ? names[bit] : "?";
+}
+
+// A chooser's answer: the kernel instance that takes the launch (its profile name) and the function that launches it, or an empty value —
+// the family refuses; `outside` then holds the feature bits its mask lacks (0: the geometry or a combination of features it does not do).
+struct ConvKernel {
+    const char* name = nullptr;
+    void (*launch)(const ConvParams&, hipStream_t) = nullptr;
+    uint32_t outside = 0;
+    explicit operator bool() const { return launch != nullptr; }
+};
+inline ConvKernel conv_refused(uint32_t outside = 0) { ConvKernel k; k.outside = outside; return k; }
 
 struct GemmParams {
     const half_t* a;  // [M][K]

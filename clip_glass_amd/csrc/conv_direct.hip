@@ -167,30 +167,31 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvParams p) {
     }
 }
 
-const char* launch_conv_direct(const ConvParams& p, hipStream_t st) {
-    if (p.x_planar8 || p.y_planar8 || p.x_planar32) return nullptr;   // chunk-planar maps (common.h): not implemented here
-    if (p.w_bstride != 0) return nullptr;  // per-sample weights are a tiled / up-conv-only path: refuse, the caller reports it
-    if (p.post_scale16) return nullptr;    // an output transform of the fused up-conv only: refuse, never ignore
+// what conv_direct_kernel implements (style and pre_shift from the fp32 tables)
+static constexpr uint32_t DIRECT_FEATURES = CF_UP | CF_STYLE | CF_PRE_SHIFT | CF_IN_UP | CF_DEMOD | CF_SHIFT | CF_NOISE | CF_RES | CF_RES_CS |
+                                            CF_RES_UP | CF_Y32 | CF_BCAST_X;
+
+template <int NW, bool SPLITK>
+static void launch_direct(const ConvParams& p, hipStream_t st) {
     const long long M = (long long)p.B * p.Hc * p.Wc;
+    constexpr int ROWS = SPLITK ? 32 : 128;
+    hipLaunchKernelGGL((conv_direct_kernel<NW, SPLITK>), dim3((unsigned)((M + ROWS - 1) / ROWS), (p.Neff + 32 * NW - 1) / (32 * NW)), dim3(256), 0,
+                       st, p);
+}
+
+ConvKernel choose_conv_direct(const ConvParams& p) {
+    const uint32_t f = conv_features(p);
+    if (f & ~DIRECT_FEATURES) return conv_refused(f & ~DIRECT_FEATURES);
+    if (!p.y && !p.y32) return conv_refused();
+    if (((f & CF_STYLE) && !p.sn) || ((f & CF_PRE_SHIFT) && !p.pre_shift)) return conv_refused();   // fp16 tables only
     // instance choice at the NOMINAL population (common.h): the row-parallel and the split-K forms sum in different orders
     const long long Mn = (long long)GLASS_NOMINAL_POP * p.Hc * p.Wc;
-    if (p.Neff > 64 && ((Mn + 127) / 128) * ((p.Neff + 127) / 128) >= 256) {   // enough 128 x 128 blocks to fill the chip: row-parallel
-        hipLaunchKernelGGL((conv_direct_kernel<4, false>), dim3((unsigned)((M + 127) / 128), (p.Neff + 127) / 128), dim3(256), 0,
-                           st, p);
-        return "conv_direct_kernel<4,rows>";
-    }
-    const unsigned gx = (unsigned)((M + 31) / 32);
+    if (p.Neff > 64 && ((Mn + 127) / 128) * ((p.Neff + 127) / 128) >= 256)    // enough 128 x 128 blocks to fill the chip: row-parallel
+        return {"conv_direct_kernel<4,rows>", launch_direct<4, false>};
     // wide n tiles re-use the activation fragment; narrow ones give small problems more blocks
-    if (p.Neff > 64 && ((Mn + 31) / 32) * ((p.Neff + 127) / 128) >= 512) {
-        hipLaunchKernelGGL((conv_direct_kernel<4, true>), dim3(gx, (p.Neff + 127) / 128), dim3(256), 0, st, p);
-        return "conv_direct_kernel<4>";
-    }
-    if (p.Neff > 32) {
-        hipLaunchKernelGGL((conv_direct_kernel<2, true>), dim3(gx, (p.Neff + 63) / 64), dim3(256), 0, st, p);
-        return "conv_direct_kernel<2>";
-    }
-    hipLaunchKernelGGL((conv_direct_kernel<1, true>), dim3(gx, 1), dim3(256), 0, st, p);
-    return "conv_direct_kernel<1>";
+    if (p.Neff > 64 && ((Mn + 31) / 32) * ((p.Neff + 127) / 128) >= 512) return {"conv_direct_kernel<4>", launch_direct<4, true>};
+    if (p.Neff > 32) return {"conv_direct_kernel<2>", launch_direct<2, true>};
+    return {"conv_direct_kernel<1>", launch_direct<1, true>};
 }
 
 // ---------------------------------------------------------------------------------

@@ -92,15 +92,23 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(ConvParams p, const fl
     *(h4*)(p.y + oidx) = out;
 }
 
-// cap_a / cap_c: scratch capacity PER CANDIDATE (halfs of A, floats of C); the buffers hold p.B candidates
-const char* launch_conv_gemm(const ConvParams& p, half_t* ws_a, long long cap_a, float* ws_c, long long cap_c, hipStream_t st) {
-    if (p.x_planar8 || p.y_planar8 || p.x_planar32) return nullptr;   // chunk-planar maps (common.h): not implemented here
-    if (!ws_a || !ws_c || p.y32 || !p.y || p.w_bstride != 0 || p.rgb_y || p.trgb_yout || p.skip_x) return nullptr;
-    if (p.pre_shift && !p.sn) return nullptr;
-    if (p.xs_out || p.post_scale16) return nullptr;   // by-products / output transforms this path does not implement: refuse, never ignore
-    if ((p.KS != 1 && p.KS != 3) || p.Cin % 64 != 0 || p.Neff % 64 != 0 || (p.Cout & 3) || (p.res_cs & 3)) return nullptr;
+// what conv_im2col_kernel + the GEMM + conv_finish_kernel implement (style and pre_shift from the fp32 tables)
+static constexpr uint32_t GEMM_FEATURES = CF_UP | CF_STYLE | CF_PRE_SHIFT | CF_IN_UP | CF_DEMOD | CF_SHIFT | CF_NOISE | CF_RES | CF_RES_CS | CF_RES_UP | CF_BCAST_X;
+// cap_a / cap_c: scratch capacity PER CANDIDATE (halfs of A, floats of C)
+bool conv_gemm_admits(const ConvParams& p, long long cap_a, long long cap_c, uint32_t* outside) {
+    const uint32_t f = conv_features(p);
+    if (outside) *outside = f & ~GEMM_FEATURES;
+    if (f & ~GEMM_FEATURES) return false;
+    if (!p.y || ((f & (CF_STYLE | CF_PRE_SHIFT)) && !p.sn) || ((f & CF_PRE_SHIFT) && !p.pre_shift)) return false;
+    if ((p.KS != 1 && p.KS != 3) || p.Cin % 64 != 0 || p.Neff % 64 != 0 || (p.Cout & 3) || (p.res_cs & 3)) return false;
     const long long M = (long long)p.B * p.Hc * p.Wc, K = (long long)p.KS * p.KS * p.Cin;
-    if ((long long)p.Hc * p.Wc * K > cap_a || (long long)p.Hc * p.Wc * p.Neff > cap_c || M * K >= (1LL << 31)) return nullptr;
+    return (long long)p.Hc * p.Wc * K <= cap_a && (long long)p.Hc * p.Wc * p.Neff <= cap_c && M * K < (1LL << 31);
+}
+
+// the buffers hold p.B candidates
+const char* launch_conv_gemm(const ConvParams& p, half_t* ws_a, long long cap_a, float* ws_c, long long cap_c, hipStream_t st) {
+    if (!ws_a || !ws_c || !conv_gemm_admits(p, cap_a, cap_c)) return nullptr;
+    const long long M = (long long)p.B * p.Hc * p.Wc, K = (long long)p.KS * p.KS * p.Cin;
     const long long n_vec = M * K / 8, n_quad = M * p.Neff / 4;
     // a 1x1 convolution of an un-modulated, contiguous map IS its patch matrix (the D blocks' skip branches: the im2col pass was a copy);
     // with nothing to do after the product either (no demodulation / noise / bias / activation / residual / gain) the GEMM's own fp16
@@ -109,7 +117,6 @@ const char* launch_conv_gemm(const ConvParams& p, half_t* ws_a, long long cap_a,
                           p.x_bstride == (long long)p.Hc * p.Wc * p.Cin;
     const bool direct_y = direct_a && !p.up && !p.dscale && !p.noise && !p.bias && !p.shift && p.act == 0 && !p.res && p.out_scale == 1.f &&
                           p.Ho == p.Hc && p.Wo == p.Wc && p.Neff == p.Cout;
-    if (p.dry_run) return direct_y ? "gemm_tiled_kernel" : "conv_gemm(im2col+gemm_tiled+finish)";
     // no activation-side transform of the input (the D blocks' convolutions): the GEMM's loader walks the map itself (GemmParams::g_*,
     // gemm_tiled_kernel<.., gather>) — the patch matrix, a 9x copy of the map written to HBM and read back, is never materialised (round 6)
     bool gather = !direct_a && !p.sn && !p.pre_shift && !p.in_up && p.Cin % 64 == 0;

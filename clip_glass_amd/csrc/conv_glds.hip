@@ -711,68 +711,66 @@ __global__ __launch_bounds__(512, 1) void conv_gldsp_kernel(ConvParams p, int NT
 }
 
 
-template <int TW, bool TRGB = false>
-static const char* launch_glds_inst(const ConvParams& p, hipStream_t st, const char* name) {
+// what conv_glds_kernel / conv_gldsp_kernel implement (style from the fp16 table, applied to the weight fragments)
+static constexpr uint32_t GLDS_FEATURES = CF_STYLE | CF_DEMOD | CF_SHIFT | CF_NOISE | CF_RES | CF_RES_CS | CF_RES_UP | CF_SAMPLE_W | CF_TORGB |
+                                          CF_TORGB_PART | CF_XS_OUT;
+
+static int glds_cus() { return glass_cu_count() - glass_cu_count() % 8; }       // a workgroup keeps its XCD (id % 8) across items
+template <int TW, bool TRGB>
+static void launch_glds(const ConvParams& p, hipStream_t st) {
     using G = Geo<TW>;
     static DevOnce once;                       // (one per template instance)
     once.run([&] { (void)hipFuncSetAttribute((const void*)conv_glds_kernel<TW, TRGB>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES); });
-    const int tiles_x = p.Wc / TW, tiles_y = p.Hc / G::TH;
-    const int PT = p.B * tiles_x * tiles_y;
-    const int NTn = p.Neff / NT;
-    const int PT8 = (PT + 7) / 8 * 8;
-    const int n_cu = glass_cu_count() - glass_cu_count() % 8;       // a workgroup keeps its XCD (id % 8) across items
-    static DevOnce once_p;
-    once_p.run([&] {
-        (void)hipFuncSetAttribute((const void*)conv_gldsp_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<32>::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_gldsp_kernel<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<32>::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_gldsp_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<32>::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_gldsp_kernel<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<32>::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_gldsp_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<32>::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_gldsp_kernel<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo<32>::LDS_BYTES);
-    });
-    // (>= 2 work items per CU at the NOMINAL population, common.h: this branch also decides whether the blur-down by-product exists,
-    // so it must be a function of the layer geometry only)
-    const long long work_nominal = (long long)GLASS_NOMINAL_POP * tiles_x * tiles_y * NTn;
-    if (TW == 32 && (p.Cin & 63) == 0 && work_nominal >= 2 * n_cu) {   // ring parity needs an even chunk count
-        // (reported under the symbol that runs, so that the per-kernel profile lines up with rocprofv3's kernel names)
-        const bool xs = p.xs_out && !TRGB, sty = p.sn16 != nullptr;
-        const char* pname = xs ? (sty ? "conv_gldsp_kernel<false,true,true>" : "conv_gldsp_kernel<false,true,false>")
-                          : TRGB ? (sty ? "conv_gldsp_kernel<true,false,true>" : "conv_gldsp_kernel<true,false,false>")
-                                 : (sty ? "conv_gldsp_kernel<false,false,true>" : "conv_gldsp_kernel<false,false,false>");
-        if (p.dry_run) return pname;
-#define GLDSP_LAUNCH(...) hipLaunchKernelGGL((conv_gldsp_kernel<__VA_ARGS__>), dim3(n_cu), dim3(NTHR), G::LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT)
-        if (xs) { if (sty) GLDSP_LAUNCH(false, true, true); else GLDSP_LAUNCH(false, true, false); }
-        else if (sty) GLDSP_LAUNCH(TRGB, false, true);
-        else GLDSP_LAUNCH(TRGB, false, false);
-#undef GLDSP_LAUNCH
-        return pname;
-    }
-    if (p.xs_out || p.trgb_part) return nullptr;   // (the blur-down by-product and the toRGB partial sums exist in the persistent form only)
-    if (p.dry_run) return name;
-    hipLaunchKernelGGL((conv_glds_kernel<TW, TRGB>), dim3(PT8 * NTn), dim3(NTHR), G::LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT);
-    return name;
+    const int tiles_x = p.Wc / TW, tiles_y = p.Hc / G::TH, PT = p.B * tiles_x * tiles_y, NTn = p.Neff / NT;
+    hipLaunchKernelGGL((conv_glds_kernel<TW, TRGB>), dim3((PT + 7) / 8 * 8 * NTn), dim3(NTHR), G::LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT);
+}
+template <bool TRGB, bool XS, bool ST>
+static void launch_gldsp(const ConvParams& p, hipStream_t st) {
+    using G = Geo<32>;
+    static DevOnce once;
+    once.run([&] { (void)hipFuncSetAttribute((const void*)conv_gldsp_kernel<TRGB, XS, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES); });
+    const int tiles_x = p.Wc / 32, tiles_y = p.Hc / G::TH, PT = p.B * tiles_x * tiles_y, NTn = p.Neff / NT;
+    hipLaunchKernelGGL((conv_gldsp_kernel<TRGB, XS, ST>), dim3(glds_cus()), dim3(NTHR), G::LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT);
 }
 
-const char* launch_conv_glds(const ConvParams& p0, hipStream_t st) {
-    ConvParams p = p0;
-    if (const char* k = launch_conv_wreg(p, st)) return k;     // 64 -> 64 channels: the weights-in-registers form (conv_wreg.hip)
-    if (p.x_planar8 || p.y_planar8 || p.x_planar32) return nullptr;   // chunk-planar maps (common.h): not implemented here
-    if (p.post_scale16) return nullptr;   // an output transform of the fused up-conv only: refuse, never ignore
-    if (!glass_lds_fits(Geo<32>::LDS_BYTES) || !glass_lds_fits(Geo<16>::LDS_BYTES)) return nullptr;
-    if (p.up || (p.xs_out && (p.sn || p.trgb_yout || p.Wc % 32 != 0)) || p.y32 || !p.y || p.KS != 3 || p.stride != 1 || p.pad != 1) return nullptr;
-    if ((p.sn && !p.sn16) || p.pre_shift || p.in_up || p.Cin > 1024 || (p.x_bstride == 0 && p.B > 1)) return nullptr;
-    if (p.Cin % 32 != 0 || p.Cin < 128 || p.Neff % NT != 0 || (p.Cout & 7) || p.Hc % 16 != 0) return nullptr;
-    if ((long long)p.H * p.W * p.Cin >= (1LL << 31)) return nullptr;
-    if (p.trgb_part) {   // toRGB partial sums per 128-wide n tile (persistent form only: the caller falls back to the separate pass otherwise)
-        if (!p.trgb_tab || p.trgb_yout || p.trgb_yprev || p.xs_out || p.Neff != p.Cout || p.Neff % NT != 0 || p.Wc % 32 != 0) return nullptr;
-        const char* k = launch_glds_inst<32, true>(p, st, nullptr);
-        return k;
+// the persistent form where the launch has >= 2 work items per CU, else the one-item-per-workgroup form `name`
+template <int TW, bool TRGB = false>
+static ConvKernel glds_inst(const ConvParams& p, const char* name) {
+    // (>= 2 work items per CU at the NOMINAL population, common.h: this branch also decides whether the blur-down by-product exists,
+    // so it must be a function of the layer geometry only)
+    const long long work_nominal = (long long)GLASS_NOMINAL_POP * (p.Wc / TW) * (p.Hc / Geo<TW>::TH) * (p.Neff / NT);
+    if (TW == 32 && (p.Cin & 63) == 0 && work_nominal >= 2 * glds_cus()) {   // ring parity needs an even chunk count
+        // (reported under the symbol that runs, so that the per-kernel profile lines up with rocprofv3's kernel names)
+        const bool sty = p.sn16 != nullptr;
+        if (p.xs_out && !TRGB) return sty ? ConvKernel{"conv_gldsp_kernel<false,true,true>", launch_gldsp<false, true, true>}
+                                          : ConvKernel{"conv_gldsp_kernel<false,true,false>", launch_gldsp<false, true, false>};
+        if (TRGB) return sty ? ConvKernel{"conv_gldsp_kernel<true,false,true>", launch_gldsp<true, false, true>}
+                             : ConvKernel{"conv_gldsp_kernel<true,false,false>", launch_gldsp<true, false, false>};
+        return sty ? ConvKernel{"conv_gldsp_kernel<false,false,true>", launch_gldsp<false, false, true>}
+                   : ConvKernel{"conv_gldsp_kernel<false,false,false>", launch_gldsp<false, false, false>};
     }
-    if (p.trgb_yout) {   // fused toRGB: only where one workgroup holds every output channel of its pixels
-        if (!p.trgb_tab || !p.trgb_b || p.Neff != NT || p.Cout != NT || p.Wc % 32 != 0) return nullptr;
-        return launch_glds_inst<32, true>(p, st, "conv_glds_kernel<32,true>");
+    if (p.xs_out || p.trgb_part) return conv_refused();   // (the blur-down by-product and the toRGB partial sums exist in the persistent form only)
+    return {name, launch_glds<TW, TRGB>};
+}
+
+ConvKernel choose_conv_glds(const ConvParams& p) {
+    const uint32_t f = conv_features(p);
+    if (f & ~GLDS_FEATURES) return conv_refused(f & ~GLDS_FEATURES);
+    if (!glass_lds_fits(Geo<32>::LDS_BYTES) || !glass_lds_fits(Geo<16>::LDS_BYTES)) return conv_refused();
+    if (((f & CF_XS_OUT) && ((f & (CF_STYLE | CF_TORGB | CF_TORGB_PART)) || p.Wc % 32 != 0)) || !p.y || p.KS != 3 || p.stride != 1 || p.pad != 1)
+        return conv_refused();
+    if (((f & CF_STYLE) && !p.sn16) || p.Cin > 1024) return conv_refused();
+    if (p.Cin % 32 != 0 || p.Cin < 128 || p.Neff % NT != 0 || (p.Cout & 7) || p.Hc % 16 != 0) return conv_refused();
+    if ((long long)p.H * p.W * p.Cin >= (1LL << 31)) return conv_refused();
+    if (f & CF_TORGB_PART) {   // toRGB partial sums per 128-wide n tile (persistent form only: the caller falls back to the separate pass otherwise)
+        if (!p.trgb_tab || (f & CF_TORGB) || p.trgb_yprev || p.Neff != p.Cout || p.Wc % 32 != 0) return conv_refused();
+        return glds_inst<32, true>(p, nullptr);
     }
-    if (p.Wc % 32 == 0) return launch_glds_inst<32>(p, st, "conv_glds_kernel<32>");
-    if (p.Wc % 16 == 0) return launch_glds_inst<16>(p, st, "conv_glds_kernel<16>");
-    return nullptr;
+    if (f & CF_TORGB) {   // fused toRGB: only where one workgroup holds every output channel of its pixels
+        if (!p.trgb_tab || !p.trgb_b || p.Neff != NT || p.Cout != NT || p.Wc % 32 != 0) return conv_refused();
+        return glds_inst<32, true>(p, "conv_glds_kernel<32,true>");
+    }
+    if (p.Wc % 32 == 0) return glds_inst<32>(p, "conv_glds_kernel<32>");
+    if (p.Wc % 16 == 0) return glds_inst<16>(p, "conv_glds_kernel<16>");
+    return conv_refused();
 }

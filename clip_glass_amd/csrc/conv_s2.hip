@@ -362,29 +362,30 @@ __global__ __launch_bounds__(512, 1) void conv_s2_kernel(ConvParams p, int NTn, 
 // blocking: 2560 LDS cycles) for 5120 MFMA cycles per SIMD — the three pipes are within 2x of each other, so ~45 % of the MFMA rate is
 // what this tile shape gives; a bigger tile does not fit 160 KB of LDS / 256 registers.
 
-const char* launch_conv_s2(const ConvParams& p, hipStream_t st, bool force) {
-    if (p.x_planar8 || p.y_planar8) return nullptr;   // chunk-planar maps (common.h): not implemented here
-    if (!p.skip_x || !p.skip_w || p.KS != 3 || p.stride != 2 || p.pad != 0 || p.up || p.y32 || !p.y) return nullptr;
-    if (p.res || p.dscale || p.noise || p.shift || p.sn || p.pre_shift || p.in_up || p.xs_out || p.trgb_yout || p.post_scale16 || p.rgb_y) return nullptr;
-    if (p.Neff != p.Cout || p.Neff % NT != 0 || p.Neff > MAX_N || p.Cin % 32 != 0 || p.Hc % TH != 0 || p.Wc % 32 != 0) return nullptr;
-    if (p.H != 2 * p.Hc + 1 || p.W != 2 * p.Wc + 1 || p.Ho != p.Hc || p.Wo != p.Wc || p.w_bstride != 0) return nullptr;
-    if (p.x_bstride != (long long)p.H * p.W * p.Cin) return nullptr;
-    if ((long long)p.H * p.W * p.Cin >= (1LL << 31) || 9LL * p.Neff * p.Cin >= (1LL << 31) || (long long)p.Ho * p.Wo * p.Cin >= (1LL << 31)) return nullptr;
-    if (!glass_lds_fits(LDS_BYTES)) return nullptr;          // 162 880 B: conv_tiled<3,2,..,skip> where the device offers less
-    const int tiles_x = p.Wc / 32, tiles_y = p.Hc / TH;
-    const int PT = p.B * tiles_x * tiles_y;
-    const int NTn = p.Neff / NT;
-    const int n_work = ((PT + 7) & ~7) * NTn;
-    const int n_cu = glass_cu_count() - glass_cu_count() % 8;          // a workgroup keeps its XCD (id % 8) across items
+// what conv_s2_kernel implements: the stride-2 conv WITH the skip branch, from pixel-major or 32-channel-plane input
+static constexpr uint32_t S2_FEATURES = CF_SKIP | CF_X_PLANAR32;
+
+static int s2_cus() { return glass_cu_count() - glass_cu_count() % 8; }          // a workgroup keeps its XCD (id % 8) across items
+static void launch_s2(const ConvParams& p, hipStream_t st) {
+    static DevOnce once;
+    once.run([&] { (void)hipFuncSetAttribute((const void*)conv_s2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); });
+    const int tiles_x = p.Wc / 32, tiles_y = p.Hc / TH, PT = p.B * tiles_x * tiles_y, NTn = p.Neff / NT;
+    const int n_work = ((PT + 7) & ~7) * NTn, n_cu = s2_cus();
+    hipLaunchKernelGGL(conv_s2_kernel, dim3(n_work < n_cu ? n_work : n_cu), dim3(NTHR), LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT);   // (n_work is a multiple of 8)
+}
+
+// any_fill: ignore the fill threshold (the diagnostic op runs the kernel at test sizes)
+ConvKernel choose_conv_s2(const ConvParams& p, bool any_fill) {
+    const uint32_t f = conv_features(p);
+    if (f & ~S2_FEATURES) return conv_refused(f & ~S2_FEATURES);
+    if (!p.skip_x || !p.skip_w || p.KS != 3 || p.stride != 2 || p.pad != 0 || !p.y) return conv_refused();
+    if (p.Neff != p.Cout || p.Neff % NT != 0 || p.Neff > MAX_N || p.Cin % 32 != 0 || p.Hc % TH != 0 || p.Wc % 32 != 0) return conv_refused();
+    if (p.H != 2 * p.Hc + 1 || p.W != 2 * p.Wc + 1 || p.Ho != p.Hc || p.Wo != p.Wc) return conv_refused();
+    if (p.x_bstride != (long long)p.H * p.W * p.Cin) return conv_refused();
+    if ((long long)p.H * p.W * p.Cin >= (1LL << 31) || 9LL * p.Neff * p.Cin >= (1LL << 31) || (long long)p.Ho * p.Wo * p.Cin >= (1LL << 31)) return conv_refused();
+    if (!glass_lds_fits(LDS_BYTES)) return conv_refused();          // 162 880 B: conv_tiled<3,2,..,skip> where the device offers less
     // too small to fill the chip with one workgroup per CU — judged at the nominal population (common.h), so that a layer runs on the
     // same kernel whatever the size of this launch
-    if ((long long)GLASS_NOMINAL_POP * tiles_x * tiles_y * NTn < n_cu && !force) return nullptr;
-    const int grid = n_work < n_cu ? n_work : n_cu;                     // (n_work is a multiple of 8)
-    if (p.dry_run) return "conv_s2_kernel";
-    static DevOnce once;
-    once.run([&] {
-        (void)hipFuncSetAttribute((const void*)conv_s2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    });
-    hipLaunchKernelGGL(conv_s2_kernel, dim3(grid), dim3(NTHR), LDS_BYTES, st, p, NTn, tiles_x, tiles_y, PT);
-    return "conv_s2_kernel";
+    if ((long long)GLASS_NOMINAL_POP * (p.Wc / 32) * (p.Hc / TH) * (p.Neff / NT) < s2_cus() && !any_fill) return conv_refused();
+    return {"conv_s2_kernel", launch_s2};
 }

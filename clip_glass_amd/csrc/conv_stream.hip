@@ -443,40 +443,41 @@ static int stream_slots() {
     return glass_cu_count() * 3;      // 168 VGPRs, 51.5 KB of LDS: three workgroups per CU
 }
 
-bool conv_stream_applies(const ConvParams& p) {
-    const bool trgb = p.trgb_yout != nullptr;
-    if (!glass_lds_fits(LDS_BYTES)) return false;
-    if (p.x_planar8 || p.y_planar8 || p.x_planar32) return false;   // chunk-planar maps (common.h): not implemented here
-    if (p.post_scale16) return false;   // an output transform of the fused up-conv only: refuse, never ignore
-    if (p.up || p.xs_out || p.y32 || (!p.y && !trgb) || p.KS != 3 || p.stride != 1 || p.pad != 1 || (p.sn && !p.sn16)) return false;
-    const bool frgb = p.rgb_y != nullptr;
-    if (frgb && (!p.rgb_w || !p.rgb_b || (!p.rgb_x_out && !p.rgb_xs_out) || p.sn || trgb)) return false;
-    if (trgb && (!p.trgb_w || !p.trgb_b || !p.trgb_sn || !p.trgb_smax || p.Ho != p.Hc || p.Wo != p.Wc)) return false;
-    if (p.Cin != 32 || p.Neff != 32 || p.Cout != 32 || p.res || p.pre_shift || p.res_cs || p.res_up) return false;
-    if (p.in_up || (frgb && p.shift)) return false;
-    if (p.Wc % 32 != 0 || p.Hc % TH != 0 || p.W >= 256 * 32 || (!frgb && p.x_bstride == 0 && p.B > 1)) return false;
-    if ((long long)p.H * p.W * p.Cin >= (1LL << 31)) return false;
-    // streaming only pays with many tiles per workgroup — judged at the nominal population (common.h), not at this launch's B:
-    // the choice between this kernel and conv_tiled (different epilogue rounding) must not depend on chunking or sharding
-    const long long PT_nominal = (long long)GLASS_NOMINAL_POP * (p.Wc / 32) * (p.Hc / TH);
-    return PT_nominal >= (long long)stream_slots() * 6;
-}
+// what conv_stream_kernel implements; <fromrgb> builds the input map itself (it never reads x: any x_bstride), <torgb> writes the skip image
+// INSTEAD of the map
+static constexpr uint32_t STREAM_FEATURES = CF_STYLE | CF_DEMOD | CF_SHIFT | CF_NOISE | CF_SAMPLE_W | CF_BCAST_X | CF_FROMRGB | CF_TORGB | CF_NO_MAP;
 
-const char* launch_conv_stream(const ConvParams& p0, hipStream_t st) {
-    if (!conv_stream_applies(p0)) return nullptr;
+template <bool FRGB, bool TRGB>
+static void launch_stream(const ConvParams& p0, hipStream_t st) {
     ConvParams p = p0;
     // measured (same box, column vs row walk): <torgb> 1821 vs 1844 us, conv_down 1762 vs 1823 us, <fromrgb> 2593 vs 2530 us — the
     // planar fp32 image the fromRGB form reads is friendlier to the row-major walk
-    p.row_walk = p.rgb_y ? 1 : 0;
-    const bool trgb = p.trgb_yout != nullptr, frgb = p.rgb_y != nullptr;
+    p.row_walk = FRGB ? 1 : 0;
     const int tiles_x = p.Wc / 32, tiles_y = p.Hc / TH;
     const int PT = p.B * tiles_x * tiles_y;
     const int slots = stream_slots();
     const int per_block = (PT + slots - 1) / slots;
     const int grid = (PT + per_block - 1) / per_block;
-    const char* name = frgb ? "conv_stream_kernel<fromrgb>" : trgb ? "conv_stream_kernel<torgb>" : "conv_stream_kernel";
-    if (frgb) hipLaunchKernelGGL((conv_stream_kernel<true, false, false>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);
-    else if (trgb) hipLaunchKernelGGL((conv_stream_kernel<false, true, false>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);
-    else hipLaunchKernelGGL((conv_stream_kernel<false, false, false>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);
-    return name;
+    hipLaunchKernelGGL((conv_stream_kernel<FRGB, TRGB, false>), dim3(grid), dim3(256), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_block);
+}
+
+ConvKernel choose_conv_stream(const ConvParams& p) {
+    const uint32_t f = conv_features(p);
+    if (f & ~STREAM_FEATURES) return conv_refused(f & ~STREAM_FEATURES);
+    const bool trgb = f & CF_TORGB, frgb = f & CF_FROMRGB;
+    if (trgb != !p.y) return conv_refused();       // the map or the skip image, never both
+    if (!glass_lds_fits(LDS_BYTES)) return conv_refused();
+    if (p.KS != 3 || p.stride != 1 || p.pad != 1 || ((f & CF_STYLE) && !p.sn16)) return conv_refused();
+    if (frgb && (!p.rgb_w || !p.rgb_b || (!p.rgb_x_out && !p.rgb_xs_out) || (f & (CF_STYLE | CF_TORGB | CF_SHIFT)))) return conv_refused();
+    if (trgb && (!p.trgb_w || !p.trgb_b || !p.trgb_sn || !p.trgb_smax || p.Ho != p.Hc || p.Wo != p.Wc)) return conv_refused();
+    if (p.Cin != 32 || p.Neff != 32 || p.Cout != 32) return conv_refused();
+    if (p.Wc % 32 != 0 || p.Hc % TH != 0 || p.W >= 256 * 32 || (!frgb && (f & CF_BCAST_X))) return conv_refused();
+    if ((long long)p.H * p.W * p.Cin >= (1LL << 31)) return conv_refused();
+    // streaming only pays with many tiles per workgroup — judged at the nominal population (common.h), not at this launch's B:
+    // the choice between this kernel and conv_tiled (different epilogue rounding) must not depend on chunking or sharding
+    const long long PT_nominal = (long long)GLASS_NOMINAL_POP * (p.Wc / 32) * (p.Hc / TH);
+    if (PT_nominal < (long long)stream_slots() * 6) return conv_refused();
+    if (frgb) return {"conv_stream_kernel<fromrgb>", launch_stream<true, false>};
+    if (trgb) return {"conv_stream_kernel<torgb>", launch_stream<false, true>};
+    return {"conv_stream_kernel", launch_stream<false, false>};
 }

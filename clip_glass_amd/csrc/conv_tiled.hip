@@ -527,86 +527,74 @@ __global__ __launch_bounds__(256, (DEEP && NT == 64 && S == 1) ? 3 : 2) void con
     }
 }
 
-template <int KS, int S, int TH, int NT, bool PERSIST = false, bool TRGB = false, bool SKIP = false, bool XS = false, bool SPL = false, bool B2 = false, bool DEEP = false, bool TR = false>
-static const char* launch_inst(const ConvParams& p, hipStream_t st, const char* name) {
-    constexpr int PH = (TH - 1) * S + KS, PW = 31 * S + KS;
-    constexpr int A_BYTES = ((PH * PW * ROWB + 15) / 16) * 16;
-    constexpr int LDS_K = A_BYTES + KS * NT * ROWB, LDS_O = 4 * (SPL ? TH / 2 : TH / 4) * 32 * ((SPL ? NT / 64 : NT / 32) * 64 + 16);   // K-loop images | epilogue image
-    constexpr int LDS = (LDS_K > LDS_O ? LDS_K : LDS_O) + 3 * NT * 4 + (TRGB ? 64 * NT : 0);
-    if (!glass_lds_fits(LDS)) return nullptr;
-    static DevOnce once;                       // (one per template instance)
-    if (LDS > 64 * 1024)
-        once.run([&] {
-            (void)hipFuncSetAttribute((const void*)conv_tiled_kernel<KS, S, TH, NT, PERSIST, TRGB, SKIP, XS, SPL, B2, DEEP, TR>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        });
-    const int tiles_x = p.Wc / 32, tiles_y = p.Hc / TH;
-    const int PT = p.B * tiles_x * tiles_y;
-    const int NTn = p.Neff / NT;
-    const int PT8 = (PT + 7) / 8 * 8;
-    const int grid = PT8 * NTn;                // one work item per workgroup
-    if (p.dry_run) return name;
-    hipLaunchKernelGGL((conv_tiled_kernel<KS, S, TH, NT, PERSIST, TRGB, SKIP, XS, SPL, B2, DEEP, TR>), dim3(grid), dim3(256), LDS, st, p, NTn, tiles_x, tiles_y, PT);
-    return name;
-}
+// what conv_tiled_kernel implements (style and pre_shift from the fp16 tables); of the four special forms — planar tanh, toRGB in the
+// epilogue, the blur-down by-product, the fused skip branch — an instance does one
+static constexpr uint32_t TILED_FEATURES = CF_UP | CF_STYLE | CF_PRE_SHIFT | CF_IN_UP | CF_DEMOD | CF_SHIFT | CF_NOISE | CF_RES | CF_RES_CS |
+                                           CF_RES_UP | CF_SAMPLE_W | CF_TORGB | CF_RGB_TANH | CF_XS_OUT | CF_SKIP;
 
-const char* launch_conv_tiled(const ConvParams& p, hipStream_t st) {
-    if (p.x_planar8 || p.y_planar8 || p.x_planar32) return nullptr;   // chunk-planar maps (common.h): not implemented here
-    if (p.post_scale16) return nullptr;   // an output transform of the fused up-conv only: refuse, never ignore
-    if (p.rgb_tanh_out) {   // planar tanh(channels 0..2) from the accumulators: the one-n-tile 3x3 instance's fast path only
-        if (p.y32 || p.trgb_yout || p.xs_out || p.up || p.KS != 3 || p.stride != 1 || p.pad != 1 || p.Neff != 32 || p.Cout != 32 ||
-            p.Hc % 8 != 0 || p.Wc % 32 != 0 || p.Cin % 32 != 0 || (p.sn && !p.sn16) || (p.pre_shift && !p.pre_shift16) || p.res || p.noise ||
-            (p.x_bstride == 0 && p.B > 1) || (long long)p.H * p.W * p.Cin >= (1LL << 31))
-            return nullptr;
-        return launch_inst<3, 1, 8, 32>(p, st, "conv_tiled_kernel<3,1,8,32>");
+template <int KS, int S, int TH, int NT, bool TRGB = false, bool SKIP = false, bool XS = false, bool SPL = false, bool DEEP = false>
+struct TiledInst {
+    static constexpr int PH = (TH - 1) * S + KS, PW = 31 * S + KS;
+    static constexpr int A_BYTES = ((PH * PW * ROWB + 15) / 16) * 16;
+    static constexpr int LDS_K = A_BYTES + KS * NT * ROWB, LDS_O = 4 * (SPL ? TH / 2 : TH / 4) * 32 * ((SPL ? NT / 64 : NT / 32) * 64 + 16);   // K-loop images | epilogue image
+    static constexpr int LDS = (LDS_K > LDS_O ? LDS_K : LDS_O) + 3 * NT * 4 + (TRGB ? 64 * NT : 0);
+    static void launch(const ConvParams& p, hipStream_t st) {
+        static DevOnce once;                       // (one per template instance)
+        if (LDS > 64 * 1024)
+            once.run([&] {
+                (void)hipFuncSetAttribute((const void*)conv_tiled_kernel<KS, S, TH, NT, false, TRGB, SKIP, XS, SPL, false, DEEP, false>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+            });
+        const int tiles_x = p.Wc / 32, tiles_y = p.Hc / TH;
+        const int PT = p.B * tiles_x * tiles_y;
+        const int NTn = p.Neff / NT;
+        const int PT8 = (PT + 7) / 8 * 8;
+        const int grid = PT8 * NTn;                // one work item per workgroup
+        hipLaunchKernelGGL((conv_tiled_kernel<KS, S, TH, NT, false, TRGB, SKIP, XS, SPL, false, DEEP, false>), dim3(grid), dim3(256), LDS, st, p, NTn, tiles_x, tiles_y, PT);
     }
-    if (p.y32 || !p.y) return nullptr;
-    if (p.trgb_yout) {   // fused toRGB: only where one workgroup holds every output channel of its pixels
-        if (!p.trgb_tab || !p.trgb_b || p.up || p.KS != 3 || p.stride != 1 || p.pad != 1 || p.Neff != 64 || p.Cout != 64 ||
-            p.Hc % 8 != 0 || p.Wc % 32 != 0 || p.Cin % 32 != 0 || (p.sn && !p.sn16) || (p.pre_shift && !p.pre_shift16) ||
-            (p.x_bstride == 0 && p.B > 1) || (long long)p.H * p.W * p.Cin >= (1LL << 31))
-            return nullptr;
-        return launch_inst<3, 1, 8, 64, false, true, false, false, false, false, true>(p, st, "conv_tiled_kernel<3,1,8,64,torgb,deep>");
+    static ConvKernel as(const char* name) { return glass_lds_fits(LDS) ? ConvKernel{name, launch} : conv_refused(); }
+};
+
+ConvKernel choose_conv_tiled(const ConvParams& p) {
+    const uint32_t f = conv_features(p);
+    if (f & ~TILED_FEATURES) return conv_refused(f & ~TILED_FEATURES);
+    const uint32_t form = f & (CF_RGB_TANH | CF_TORGB | CF_XS_OUT | CF_SKIP);
+    if (form & (form - 1)) return conv_refused();
+    if (((f & CF_STYLE) && !p.sn16) || ((f & CF_PRE_SHIFT) && !p.pre_shift16)) return conv_refused();   // fp16 tables not provided: direct path
+    if ((long long)p.H * p.W * p.Cin >= (1LL << 31)) return conv_refused();
+    // the one-n-tile 3x3 forms: geometry they share
+    const bool one_tile_3x3 = !p.up && p.KS == 3 && p.stride == 1 && p.pad == 1 && p.Hc % 8 == 0 && p.Wc % 32 == 0 && p.Cin % 32 == 0;
+    if (f & CF_RGB_TANH) {   // planar tanh(channels 0..2) from the accumulators: the one-n-tile 3x3 instance's fast path only
+        if (!one_tile_3x3 || p.Neff != 32 || p.Cout != 32 || (f & (CF_RES | CF_NOISE))) return conv_refused();
+        return TiledInst<3, 1, 8, 32>::as("conv_tiled_kernel<3,1,8,32>");
     }
-    if (p.xs_out) {   // blur-down of the input as a by-product: un-transformed input, every chunk staged exactly once per pixel tile
-        if (p.KS != 3 || p.stride != 1 || p.pad != 1 || p.sn || p.pre_shift || p.in_up || p.up || p.Neff != 64 || p.Cout != 64 ||
-            p.Hc % 8 != 0 || p.Wc % 32 != 0 || p.Cin % 32 != 0 || p.trgb_yout || (p.x_bstride == 0 && p.B > 1) ||
-            (long long)p.H * p.W * p.Cin >= (1LL << 31))
-            return nullptr;
-        return launch_inst<3, 1, 8, 64, false, false, false, true, false, false, true>(p, st, "conv_tiled_kernel<3,1,8,64,xs,deep>");
+    if (!p.y) return conv_refused();
+    if (f & CF_TORGB) {   // fused toRGB: only where one workgroup holds every output channel of its pixels
+        if (!one_tile_3x3 || !p.trgb_tab || !p.trgb_b || p.Neff != 64 || p.Cout != 64) return conv_refused();
+        return TiledInst<3, 1, 8, 64, true, false, false, false, true>::as("conv_tiled_kernel<3,1,8,64,torgb,deep>");
     }
-    if ((p.sn && !p.sn16) || (p.pre_shift && !p.pre_shift16)) return nullptr;   // fp16 tables not provided: direct path
-    if (p.x_bstride == 0 && p.B > 1) return nullptr;  // broadcast input (4x4 const): direct path
-    if (p.Cin % 32 != 0 || p.Wc % 32 != 0 || p.Cout % 4 != 0) return nullptr;
-    if ((long long)p.H * p.W * p.Cin >= (1LL << 31)) return nullptr;
+    if (f & CF_XS_OUT) {   // blur-down of the input as a by-product: un-transformed input, every chunk staged exactly once per pixel tile
+        if (!one_tile_3x3 || (f & (CF_STYLE | CF_PRE_SHIFT | CF_IN_UP)) || p.Neff != 64 || p.Cout != 64) return conv_refused();
+        return TiledInst<3, 1, 8, 64, false, false, true, false, true>::as("conv_tiled_kernel<3,1,8,64,xs,deep>");
+    }
+    if (p.Cin % 32 != 0 || p.Wc % 32 != 0 || p.Cout % 4 != 0) return conv_refused();
     const int KS = p.KS, S = p.stride;
-    if (KS == 3 && S == 1 && p.pad == 1) {
-        if (p.Neff % 128 == 0 && p.Hc % 8 == 0) return launch_inst<3, 1, 8, 128>(p, st, "conv_tiled_kernel<3,1,8,128>");
-        if (p.Neff % 64 == 0 && p.Hc % 8 == 0) return launch_inst<3, 1, 8, 64>(p, st, "conv_tiled_kernel<3,1,8,64>");
-        if (p.Neff % 32 == 0 && p.Hc % 8 == 0) return launch_inst<3, 1, 8, 32>(p, st, "conv_tiled_kernel<3,1,8,32>");
-        return nullptr;
-    }
-    if (p.skip_x) {   // skip branch as extra K stages: stride-2 fast path without demodulation / noise / shift / residual
-        if (KS != 3 || S != 2 || p.pad != 0 || !p.skip_w || p.res || p.dscale || p.noise || p.shift || p.sn || p.pre_shift || p.up ||
+    if (f & CF_SKIP) {   // skip branch as extra K stages: stride-2 fast path without demodulation / noise / shift / residual
+        if (KS != 3 || S != 2 || p.pad != 0 || !p.skip_w || (f & (CF_RES | CF_DEMOD | CF_NOISE | CF_SHIFT | CF_STYLE | CF_PRE_SHIFT | CF_UP)) ||
             (p.Cout & 7) || p.Hc % 4 != 0)
-            return nullptr;
-        if (const char* k = launch_conv_s2(p, st)) return k;        // LDS-DMA ring kernel where its geometry applies
+            return conv_refused();
         // 2 x 2 wave grid (SPL; 4 x 1 measured -4.4 % on the four stride-2 layers)
-        if (p.Neff % 128 == 0) return launch_inst<3, 2, 4, 128, false, false, true, false, true, false, true>(p, st, "conv_tiled_kernel<3,2,4,128,skip,spl,deep>");
-        if (p.Neff % 64 == 0) return launch_inst<3, 2, 4, 64, false, false, true>(p, st, "conv_tiled_kernel<3,2,4,64,skip>");
-        return nullptr;
+        if (p.Neff % 128 == 0) return TiledInst<3, 2, 4, 128, false, true, false, true, true>::as("conv_tiled_kernel<3,2,4,128,skip,spl,deep>");
+        if (p.Neff % 64 == 0) return TiledInst<3, 2, 4, 64, false, true>::as("conv_tiled_kernel<3,2,4,64,skip>");
+        return conv_refused();
     }
-    if (KS == 3 && S == 2 && p.pad == 0) {
-        if (p.Neff % 128 == 0 && p.Hc % 4 == 0) return launch_inst<3, 2, 4, 128>(p, st, "conv_tiled_kernel<3,2,4,128>");
-        if (p.Neff % 64 == 0 && p.Hc % 4 == 0) return launch_inst<3, 2, 4, 64>(p, st, "conv_tiled_kernel<3,2,4,64>");
-        if (p.Neff % 32 == 0 && p.Hc % 4 == 0) return launch_inst<3, 2, 4, 32>(p, st, "conv_tiled_kernel<3,2,4,32>");
-        return nullptr;
-    }
-    if (KS == 1 && S == 1 && p.pad == 0) {
-        if (p.Neff % 128 == 0 && p.Hc % 8 == 0) return launch_inst<1, 1, 8, 128>(p, st, "conv_tiled_kernel<1,1,8,128>");
-        if (p.Neff % 64 == 0 && p.Hc % 8 == 0) return launch_inst<1, 1, 8, 64>(p, st, "conv_tiled_kernel<1,1,8,64>");
-        if (p.Neff % 32 == 0 && p.Hc % 8 == 0) return launch_inst<1, 1, 8, 32>(p, st, "conv_tiled_kernel<1,1,8,32>");
-        return nullptr;
-    }
-    return nullptr;
+#define TILED_PLAIN(KS_, S_, TH_)                                                                                                    \
+    return p.Neff % 128 == 0 ? TiledInst<KS_, S_, TH_, 128>::as("conv_tiled_kernel<" #KS_ "," #S_ "," #TH_ ",128>")                       \
+           : p.Neff % 64 == 0 ? TiledInst<KS_, S_, TH_, 64>::as("conv_tiled_kernel<" #KS_ "," #S_ "," #TH_ ",64>")                        \
+           : p.Neff % 32 == 0 ? TiledInst<KS_, S_, TH_, 32>::as("conv_tiled_kernel<" #KS_ "," #S_ "," #TH_ ",32>") : conv_refused()
+    if (KS == 3 && S == 1 && p.pad == 1 && p.Hc % 8 == 0) TILED_PLAIN(3, 1, 8);
+    if (KS == 3 && S == 2 && p.pad == 0 && p.Hc % 4 == 0) TILED_PLAIN(3, 2, 4);
+    if (KS == 1 && S == 1 && p.pad == 0 && p.Hc % 8 == 0) TILED_PLAIN(1, 1, 8);
+#undef TILED_PLAIN
+    return conv_refused();
 }

@@ -450,41 +450,36 @@ __global__ __launch_bounds__(256, 1) void conv_wreg_kernel(ConvParams p, int til
     WG_WAIT_VM(0);                             // the last tiles' self-prefetches
 }
 
-// would a plain 3x3 layer of this geometry run here?  (the producers of its input ask before they write the chunk-planar layout)
-bool conv_wreg_supported(int Cin, int Cout, int H, int W) {
-    if (Cin != 64 || Cout != NT || H % TH != 0 || W % TW != 0 || (long long)H * W * Cin >= (1LL << 31)) return false;
-    if (!glass_lds_fits(LDS_BYTES)) return false;
-    // worth a persistent workgroup per CU only with several tiles each — judged at the nominal population (common.h), so that a layer runs on
-    // the same kernel whatever the size of this launch
-    return (long long)GLASS_NOMINAL_POP * (W / TW) * (H / TH) >= 16LL * glass_cu_count();
-}
+// what conv_wreg_kernel implements: reads pixel-major or chunk-planar input, writes pixel-major; <true,.> toRGB in the epilogue,
+// <.,true> the blur-down by-product — one of the two
+static constexpr uint32_t WREG_FEATURES = CF_DEMOD | CF_SHIFT | CF_NOISE | CF_SAMPLE_W | CF_TORGB | CF_XS_OUT | CF_X_PLANAR8;
 
-// nullptr: the layer does not qualify (the caller goes on to conv_wres / conv_tiled)
-const char* launch_conv_wreg(const ConvParams& p, hipStream_t st) {
-    if (!conv_wreg_supported(p.Cin, p.Cout, p.Hc, p.Wc)) return nullptr;
-    if (p.Cin != 64 || p.Neff != NT || p.Cout != NT || p.up || p.y32 || !p.y || p.KS != 3 || p.stride != 1 || p.pad != 1) return nullptr;
-    if (p.sn || p.sn16 || p.pre_shift || p.in_up || p.rgb_y || p.rgb_tanh_out || p.skip_x || p.post_scale16 || p.trgb_part) return nullptr;
-    if (p.Hc % TH != 0 || p.Wc % TW != 0 || p.Hc != p.H || p.Wc != p.W || (p.x_bstride == 0 && p.B > 1)) return nullptr;
-    if (p.xs_out && p.trgb_yout) return nullptr;
-    if (p.res) return nullptr;                     // (no residual input: neither layer has one; conv_wres takes such a call)
-    if (p.y_planar8 || p.x_planar32) return nullptr;   // (reads the 8-channel-plane layout, writes pixel-major)
-    if (p.trgb_yout && (!p.trgb_tab || !p.trgb_b)) return nullptr;
+template <bool TRGB, bool XS>
+static void launch_wreg(const ConvParams& p, hipStream_t st) {
+    static DevOnce once;
+    once.run([&] { (void)hipFuncSetAttribute((const void*)conv_wreg_kernel<TRGB, XS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); });
     const int tiles_x = p.Wc / TW, tiles_y = p.Hc / TH;
     const int n_cu = glass_cu_count();
     const int PT = p.B * tiles_x * tiles_y;
-    const char* name = p.trgb_yout ? "conv_wreg_kernel<true,false>" : p.xs_out ? "conv_wreg_kernel<false,true>" : "conv_wreg_kernel<false,false>";
-    if (p.dry_run) return name;
-    static DevOnce once;
-    once.run([&] {
-        (void)hipFuncSetAttribute((const void*)conv_wreg_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_wreg_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv_wreg_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    });
     // contiguous tile ranges: the tiles of a candidate split over whole workgroups where they can (per-sample weights load once per range)
     const int per_wg = (PT + n_cu - 1) / n_cu;
     const int grid = (PT + per_wg - 1) / per_wg;
-    if (p.trgb_yout) hipLaunchKernelGGL((conv_wreg_kernel<true, false>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg);
-    else if (p.xs_out) hipLaunchKernelGGL((conv_wreg_kernel<false, true>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg);
-    else hipLaunchKernelGGL((conv_wreg_kernel<false, false>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg);
-    return name;
+    hipLaunchKernelGGL((conv_wreg_kernel<TRGB, XS>), dim3(grid), dim3(NTHR), LDS_BYTES, st, p, tiles_x, tiles_y, PT, per_wg);
+}
+
+// (the producers of a layer's input ask with the layer's own parameters, x_planar8 set, before they write the chunk-planar layout)
+ConvKernel choose_conv_wreg(const ConvParams& p) {
+    const uint32_t f = conv_features(p);
+    if (f & ~WREG_FEATURES) return conv_refused(f & ~WREG_FEATURES);
+    if ((f & CF_XS_OUT) && (f & CF_TORGB)) return conv_refused();
+    if (p.Cin != 64 || p.Neff != NT || p.Cout != NT || !p.y || p.KS != 3 || p.stride != 1 || p.pad != 1) return conv_refused();
+    if (p.Hc % TH != 0 || p.Wc % TW != 0 || p.Hc != p.H || p.Wc != p.W || (long long)p.H * p.W * p.Cin >= (1LL << 31)) return conv_refused();
+    if ((f & CF_TORGB) && (!p.trgb_tab || !p.trgb_b)) return conv_refused();
+    if (!glass_lds_fits(LDS_BYTES)) return conv_refused();
+    // worth a persistent workgroup per CU only with several tiles each — judged at the nominal population (common.h), so that a layer runs on
+    // the same kernel whatever the size of this launch
+    if ((long long)GLASS_NOMINAL_POP * (p.Wc / TW) * (p.Hc / TH) < 16LL * glass_cu_count()) return conv_refused();
+    if (f & CF_TORGB) return {"conv_wreg_kernel<true,false>", launch_wreg<true, false>};
+    if (f & CF_XS_OUT) return {"conv_wreg_kernel<false,true>", launch_wreg<false, true>};
+    return {"conv_wreg_kernel<false,false>", launch_wreg<false, false>};
 }

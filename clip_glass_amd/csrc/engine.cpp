@@ -411,33 +411,49 @@ void collect_profile(glass_engine* e) {
     e->event_next = 0;
 }
 
-void run_conv(glass_engine* e, const ConvParams& p, const char* tag, double flops, double bytes) {
-    if (!(p.out_scale > 0.f)) {   // the epilogues fold the scale into the activation constants, max(v k1, v k2) (common.h act_apply): s > 0 only
-        if (e->launch_error.empty()) e->launch_error = std::string("out_scale must be positive: ") + tag;
-        return;
-    }
+// The order in which the single-kernel conv families are asked, written once; the first that takes the layer runs it.  run_conv goes on to
+// conv_gemm (which needs the engine's scratch) and conv_direct where all of them refuse.
+ConvKernel choose_conv(const ConvParams& p) {
+    ConvKernel k;
+    if (p.up && (k = choose_conv_upfir(p))) return k;
+    if ((k = choose_conv_stream(p))) return k;
+    if ((k = choose_conv_wreg(p))) return k;
+    if ((k = choose_conv_glds(p))) return k;
+    if ((k = choose_conv_s2(p))) return k;
+    return choose_conv_tiled(p);
+}
+
+// the epilogues fold the scale into the activation constants, max(v k1, v k2) (common.h act_apply): s > 0 only
+static bool out_scale_ok(glass_engine* e, const ConvParams& p, const char* tag) {
+    if (p.out_scale > 0.f) return true;
+    if (e->launch_error.empty()) e->launch_error = std::string("out_scale must be positive: ") + tag;
+    return false;
+}
+
+// a walker asked a chooser first and kept the answer: launch that kernel
+void run_chosen(glass_engine* e, const ConvKernel& k, const ConvParams& p, const char* tag, double flops, double bytes) {
+    if (!out_scale_ok(e, p, tag)) return;
     Prof pr(e, tag, flops, bytes);
-    const char* k = p.up ? launch_upconv_fused(p, e->cur) : nullptr;
-    if (p.rgb_tanh_out) {      // (one kernel family writes this output; the caller asked conv_tiled's dry run first)
-        k = launch_conv_tiled(p, e->cur);
-        if (!k && e->launch_error.empty()) e->launch_error = std::string("no kernel writes the planar tanh output of layer ") + tag;
-        if (!k) k = "(refused)";
-        pr.ran(tag, k);
-        return;
-    }
-    if (!k) k = launch_conv_stream(p, e->cur);
-    if (!k) k = launch_conv_glds(p, e->cur);
-    if (!k) k = launch_conv_tiled(p, e->cur);
+    k.launch(p, e->cur);
+    pr.ran(tag, k.name);
+}
+
+void run_conv(glass_engine* e, const ConvParams& p, const char* tag, double flops, double bytes) {
+    if (!out_scale_ok(e, p, tag)) return;
+    Prof pr(e, tag, flops, bytes);
+    ConvKernel k = choose_conv(p);
+    const char* name = k.name;
     if (!k) {
         const bool second = e->cur == e->stream_d && e->ws_a2;
-        k = launch_conv_gemm(p, second ? e->ws_a2 : e->ws_a, e->cap_a, second ? e->ws_c2 : e->ws_c, e->cap_c, e->cur);
+        name = launch_conv_gemm(p, second ? e->ws_a2 : e->ws_a, e->cap_a, second ? e->ws_c2 : e->ws_c, e->cap_c, e->cur);
+        if (!name && (k = choose_conv_direct(p))) name = k.name;
     }
-    if (!k) k = launch_conv_direct(p, e->cur);
-    if (!k) {   // no kernel family accepts this layer: remember it, the pass returns an error instead of a wrong result
+    if (k) k.launch(p, e->cur);
+    if (!name) {   // no kernel family accepts this layer: remember it, the pass returns an error instead of a wrong result
         if (e->launch_error.empty()) e->launch_error = std::string("no kernel accepts layer ") + tag;
-        k = "(refused)";
+        name = "(refused)";
     }
-    pr.ran(tag, k);
+    pr.ran(tag, name);
 }
 void run_gemm(glass_engine* e, const GemmParams& p, const char* tag) {
     Prof pr(e, tag, 2.0 * p.M * p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N));

@@ -298,15 +298,11 @@ struct Prof {
 };
 
 void collect_profile(glass_engine* e);
+ConvKernel choose_conv(const ConvParams& p);   // the single-kernel conv families in the engine's order; empty: conv_gemm / conv_direct (run_conv)
 void run_conv(glass_engine* e, const ConvParams& p, const char* tag, double flops, double bytes);
+void run_chosen(glass_engine* e, const ConvKernel& k, const ConvParams& p, const char* tag, double flops, double bytes);   // k: a chooser's answer for p
 void run_gemm(glass_engine* e, const GemmParams& p, const char* tag);
 ConvParams conv_defaults();
-// dry run: the kernel `launch` would run `p` on, or nullptr where it refuses the layer; nothing is launched
-template <typename Launcher>
-inline const char* would_run(Launcher launch, ConvParams p) {
-    p.dry_run = 1;
-    return launch(p, nullptr);
-}
 // out[M][N] = a[M][K] x w[N][K]^T (+ bias), written as `mode` says (common.h GemmParams: fp16 to out16 for modes 0 / 1, fp32 to out32 above)
 GemmParams gemm_params(const half_t* a, const half_t* w, int M, int N, int K, const float* bias, int mode, half_t* out16, float* out32,
                        int cand_rows);

@@ -1,29 +1,31 @@
-// kernels.h — host-callable launch wrappers (one per kernel family).
+// kernels.h — host-callable choosers and launch wrappers (one per kernel family).
 #pragma once
 #include "common.h"
 
 #include <string>
 #include <vector>
 
-// Each launcher returns the kernel symbol it launched (for the per-kernel profile).
-const char* launch_conv_direct(const ConvParams& p, hipStream_t st);
-const char* launch_gemm_direct(const GemmParams& p, hipStream_t st);
-// LDS-tiled fast paths; return nullptr when the shape is not supported (caller falls back to direct).
-const char* launch_conv_tiled(const ConvParams& p, hipStream_t st);
-const char* launch_gemm_tiled(const GemmParams& p, hipStream_t st);
-// persistent streaming 3x3 conv for the 32 -> 32 channel 1024^2 layers (conv_stream.hip); nullptr when unsupported
-const char* launch_conv_stream(const ConvParams& p, hipStream_t st);
-// the low-resolution layers as im2col + gemm_tiled + finishing pass (conv_gemm.hip); ws_a / ws_c: scratch of cap_a halfs / cap_c floats PER CANDIDATE
-const char* launch_conv_gemm(const ConvParams& p, half_t* ws_a, long long cap_a, float* ws_c, long long cap_c, hipStream_t st);
-bool conv_stream_applies(const ConvParams& p);   // trgb_yout set: the fused conv + toRGB form
-// LDS-DMA staged 3x3 conv for the MFMA-bound mid-resolution layers (conv_glds.hip); nullptr when unsupported / disabled
-const char* launch_conv_glds(const ConvParams& p, hipStream_t st);
+// --- ConvParams kernel families ------------------------------------------------------------------------------------------------
+// One chooser per family: it reads the launch's features (common.h conv_features) and geometry, launches nothing, and returns the kernel
+// instance that takes the layer — its profile name and its launch function — or an empty ConvKernel.  What it returns is what runs:
+// `k.launch(p, stream)`.  The order in which the engine asks the families is choose_conv (engine.cpp).
+ConvKernel choose_conv_direct(const ConvParams& p);    // conv_direct.hip: operands straight from global memory, any shape; the last resort
+ConvKernel choose_conv_tiled(const ConvParams& p);     // conv_tiled.hip: the LDS-tiled kernel (W % 32 == 0)
+ConvKernel choose_conv_stream(const ConvParams& p);    // conv_stream.hip: persistent streaming 3x3 conv for the 32 -> 32 channel 1024^2 layers
+ConvKernel choose_conv_glds(const ConvParams& p);      // conv_glds.hip: LDS-DMA staged 3x3 conv for the MFMA-bound mid-resolution layers (Cin >= 128)
 // conv_wreg.hip: 3x3 stride-1 conv 64 -> 64 channels with the WHOLE weight tensor in registers, one wave per SIMD, the patches on a three-tile
-// LDS-DMA ring (tried first by launch_conv_glds); reads pixel-major or chunk-planar input; nullptr: the layer does not qualify
-const char* launch_conv_wreg(const ConvParams& p, hipStream_t st);
-bool conv_wreg_supported(int Cin, int Cout, int H, int W);
-// conv_s2.hip: the D blocks' stride-2 3x3 conv + fused 1x1 skip branch on an LDS-DMA ring (nullptr: not applicable -> conv_tiled)
-const char* launch_conv_s2(const ConvParams& p, hipStream_t st, bool force = false);
+// LDS-DMA ring; reads pixel-major or chunk-planar input
+ConvKernel choose_conv_wreg(const ConvParams& p);
+// conv_s2.hip: the D blocks' stride-2 3x3 conv + fused 1x1 skip branch on an LDS-DMA ring; any_fill: also where the launch does not fill the chip
+ConvKernel choose_conv_s2(const ConvParams& p, bool any_fill = false);
+ConvKernel choose_conv_upfir(const ConvParams& p);     // upfir.hip: fused transposed-conv + FIR + epilogue
+// conv_gemm.hip: the low-resolution layers as im2col + gemm_tiled + finishing pass — several launches and scratch, so admission and launch are
+// separate: ws_a / ws_c: scratch of cap_a halfs / cap_c floats PER CANDIDATE; outside: the feature bits the family lacks
+bool conv_gemm_admits(const ConvParams& p, long long cap_a, long long cap_c, uint32_t* outside = nullptr);
+const char* launch_conv_gemm(const ConvParams& p, half_t* ws_a, long long cap_a, float* ws_c, long long cap_c, hipStream_t st);   // nullptr: refused
+// GemmParams launchers return the kernel symbol they launched (for the per-kernel profile); tiled: nullptr when the shape is not supported
+const char* launch_gemm_direct(const GemmParams& p, hipStream_t st);
+const char* launch_gemm_tiled(const GemmParams& p, hipStream_t st);
 // second half of the full-resolution discriminator block in one kernel (conv_down.hip):
 //   y = (lrelu(conv3x3 stride 2 (fir_pad2(h)) + b1) * sqrt2 + conv1x1(xs)) / sqrt2, xs = fir_pad1(x)[::2] (32 -> 64 channels);
 // nullptr when the shape does not qualify (caller runs the separate passes)
@@ -40,8 +42,6 @@ bool conv_down64_supported(int R, int Cin, int Cout);
 const char* launch_dblock0(const float* rgb_y, const float* rgb_w, const float* rgb_b, const half_t* w0, const float* b0, const half_t* w1,
                            const half_t* ws, const float* b1, half_t* y, int B, int R, int Cin, int Cout, hipStream_t st, int y_planar8 = 0);
 bool dblock0_supported(int R, int Cin, int Cout);
-// fused transposed-conv + FIR + epilogue (upfir.hip); nullptr when unsupported
-const char* launch_upconv_fused(const ConvParams& p, hipStream_t st);
 
 // --- small fp32 ops (mapping network, style affines, demodulation, heads) ---------
 void launch_pixelnorm(const float* z, float* out, int P, int L, float eps, hipStream_t st);

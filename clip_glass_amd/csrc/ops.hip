@@ -71,8 +71,6 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
           "in_up: H and W are the upsampled dims and must be even (not with up / broadcast_x)");
     OPREQ(d->res_up == 0 || (d->res_up == 1 && d->res && d->Ho % 2 == 0 && d->Wo % 2 == 0), "res_up: needs res, Ho and Wo even");
     OPREQ(d->res_cs == 0 || (d->res && d->res_cs >= d->Cout), "res_cs: needs res, res_cs >= Cout");
-    OPREQ(!d->rgb_tanh || d->impl == 0 || d->impl == 2, "rgb_tanh: conv_tiled only (impl 0 / 2), as run_conv dispatches it");
-    OPREQ(!d->rgb_tanh || (!d->trgb_yout && !d->xs_out), "rgb_tanh: not with the fused toRGB or the blur-down by-product");
     GLASS_HIP(hipSetDevice(device));
     Dev dv;
     ConvParams p = conv_defaults();
@@ -140,7 +138,7 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     p.y = y;
     OPREQ(p.x && p.w && y, "device allocation failed");
     if (d->skip_x) {
-        OPREQ(d->skip_w && (d->impl == 2 || d->impl == 5), "fused skip branch: impl 2 / 5 with skip_x and skip_w");
+        OPREQ(d->skip_w, "fused skip branch: skip_x and skip_w");
         std::vector<_Float16> pks;
         glass_pack_conv(d->skip_w, d->Cout, d->Cin, 1, d->Cin, pks);
         p.skip_w = dv.up16v(pks);
@@ -149,24 +147,22 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     half_t* xs_dev = nullptr;
     const size_t nxs = (size_t)d->B * (d->H / 2) * (d->W / 2) * d->Cin;
     if (d->xs_out) {
-        OPREQ(d->impl == 2 || d->impl == 5, "blur-down by-product: impl 2 / 5");
         xs_dev = dv.alloc<half_t>(nxs);
         p.xs_out = xs_dev;
     }
     float* yrgb = nullptr;
     const size_t nrgb = (size_t)d->B * 3 * d->Ho * d->Wo;
     if (d->trgb_yout) {
-        OPREQ((d->impl == 4 || d->impl == 2 || d->impl == 5) && d->trgb_w && d->trgb_b && d->trgb_sn && d->trgb_smax,
-              "fused toRGB: impl 2 / 4 / 5 and all of w / b / sn / smax");
+        OPREQ(d->trgb_w && d->trgb_b && d->trgb_sn && d->trgb_smax, "fused toRGB: all of w / b / sn / smax");
         p.trgb_w = dv.up32(d->trgb_w, 3 * (size_t)d->Cout); p.trgb_b = dv.up32(d->trgb_b, 3);
         p.trgb_sn = dv.up32(d->trgb_sn, (size_t)d->B * d->Cout); p.trgb_sn_stride = d->Cout;
         p.trgb_smax = dv.up32(d->trgb_smax, d->B); p.trgb_smax_stride = 1;
         p.trgb_yprev = dv.up32(d->trgb_yprev, (size_t)d->B * 3 * (d->Ho / 2) * (d->Wo / 2));
         yrgb = dv.alloc<float>(nrgb);
         p.trgb_yout = yrgb;
-        if (d->impl == 4) {
+        if (d->impl == 4 && !d->trgb_keep_map) {
             p.y = nullptr;                       // the streaming form never stores the map
-        } else {                                 // tiled / LDS-DMA forms: weight tables from the table kernel
+        } else {                                 // the forms that store it too: weight tables from the table kernel
             half_t* tab = dv.alloc<half_t>((size_t)d->B * 32 * d->Cout);
             launch_trgb_tables(p.trgb_w, p.trgb_sn, p.trgb_sn_stride, p.trgb_smax, p.trgb_smax_stride, d->B, d->Cout, tab, 0);
             p.trgb_tab = tab;
@@ -201,34 +197,46 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     const float* part_yprev = p.trgb_yprev;
     const int ntn = d->Cout / 128;
     if (d->trgb_partial) {   // toRGB partial sums per 128-wide n tile, as torgb_conv_params sets ToRgb::partial up; launch_trgb_finish below
-        OPREQ(yrgb && d->impl == 5 && d->Cout % 128 == 0 && d->Ho == d->Wo, "toRGB partial sums: impl 5 with the trgb inputs, Cout % 128 == 0, Ho == Wo");
+        OPREQ(yrgb && d->Cout % 128 == 0 && d->Ho == d->Wo, "toRGB partial sums: the trgb inputs, Cout % 128 == 0, Ho == Wo");
         const size_t npart = (size_t)ntn * nrgb;
         part = dv.alloc<float>(npart);
         OPREQ(part, "device allocation failed");
         GLASS_HIP(hipMemset(part, 0xFF, npart * sizeof(float)));      // NaN: a partial the conv does not write shows in the sum
         p.trgb_part = part; p.trgb_yout = nullptr; p.trgb_yprev = nullptr;
     }
-    if (ytanh) {              // run_conv: one kernel family writes this output
-        if (!launch_conv_tiled(p, 0)) { glass_set_error("tiled conv: no instance writes the planar tanh output of this shape"); return GLASS_ERR_ARG; }
-    } else if (d->impl == 1) { if (!launch_conv_direct(p, 0)) { glass_set_error("direct conv: unsupported launch"); return GLASS_ERR_ARG; } }
-    else if (d->impl == 3) {
-        if (!launch_upconv_fused(p, 0)) { glass_set_error("fused up-conv: unsupported shape"); return GLASS_ERR_ARG; }
-    } else if (d->impl == 2) {
-        if (!launch_conv_tiled(p, 0)) { glass_set_error("tiled conv: unsupported shape"); return GLASS_ERR_ARG; }
-    } else if (d->impl == 4) {
-        if (!launch_conv_stream(p, 0)) { glass_set_error("streaming conv: unsupported shape"); return GLASS_ERR_ARG; }
-    } else if (d->impl == 6) {
-        // per candidate; room for the four split-K slices the launcher may choose, as the engine's scratch (256 * 4 * cmax floats) always has
+    // ask the families of `impl` in order; a refusal names every family asked and the features it lacks
+    static const char* const labels[7] = {"no kernel accepts this convolution", "direct conv: unsupported launch", "tiled conv: unsupported shape", "fused up-conv: unsupported shape",
+                                          "streaming conv: unsupported shape", "LDS-DMA conv: unsupported shape", "im2col + GEMM conv: unsupported shape"};
+    std::string why;
+    ConvKernel k;
+    auto refused = [&](const char* family, uint32_t outside) {
+        why += std::string(why.empty() ? " (" : "; ") + family + (outside ? " does not implement" : " does not take this shape or this combination of");
+        for (int bit = 0; bit < CF_COUNT; ++bit)
+            if ((outside ? outside : conv_features(p)) >> bit & 1) why += std::string(" [") + conv_feature_name(bit) + "]";
+        return false;
+    };
+    auto ask = [&](const char* family, const ConvKernel& c) { return c ? (k = c, true) : refused(family, c.outside); };
+    bool ran = false;
+    switch (d->impl) {
+    case 1: ask("conv_direct", choose_conv_direct(p)); break;
+    case 2: ask("conv_s2", choose_conv_s2(p)) || ask("conv_tiled", choose_conv_tiled(p)); break;
+    case 3: ask("upfir", choose_conv_upfir(p)); break;
+    case 4: ask("conv_stream", choose_conv_stream(p)); break;
+    case 5: p.skip_x ? ask("conv_s2", choose_conv_s2(p, true)) : ask("conv_wreg", choose_conv_wreg(p)) || ask("conv_glds", choose_conv_glds(p)); break;
+    case 6: {   // scratch per candidate; room for the four split-K slices the launcher may choose, as the engine's scratch (256 * 4 * cmax floats) always has
         const long long cap_a = (long long)p.Hc * p.Wc * p.KS * p.KS * p.Cin, cap_c = 4LL * p.Hc * p.Wc * p.Neff;
-        half_t* wa = dv.alloc<half_t>((size_t)(cap_a * p.B));
-        float* wc = dv.alloc<float>((size_t)(cap_c * p.B));
-        if (!launch_conv_gemm(p, wa, cap_a, wc, cap_c, 0)) { glass_set_error("im2col + GEMM conv: unsupported shape"); return GLASS_ERR_ARG; }
-    } else if (d->impl == 5) {
-        if (p.skip_x) {
-            if (!launch_conv_s2(p, 0, true)) { glass_set_error("LDS-DMA stride-2 conv: unsupported shape"); return GLASS_ERR_ARG; }
-        } else if (!launch_conv_glds(p, 0)) { glass_set_error("LDS-DMA conv: unsupported shape"); return GLASS_ERR_ARG; }
-    } else if (!(d->up && launch_upconv_fused(p, 0)) && !launch_conv_stream(p, 0) && !launch_conv_tiled(p, 0) && !launch_conv_direct(p, 0)) {
-        glass_set_error("no kernel accepts this convolution");
+        uint32_t outside = 0;
+        ran = conv_gemm_admits(p, cap_a, cap_c, &outside) &&
+              launch_conv_gemm(p, dv.alloc<half_t>((size_t)(cap_a * p.B)), cap_a, dv.alloc<float>((size_t)(cap_c * p.B)), cap_c, 0);
+        if (!ran) refused("conv_gemm", outside);
+    } break;
+    default:
+        (d->up && ask("upfir", choose_conv_upfir(p))) || ask("conv_stream", choose_conv_stream(p)) || ask("conv_s2", choose_conv_s2(p)) ||
+            ask("conv_tiled", choose_conv_tiled(p)) || ask("conv_direct", choose_conv_direct(p));
+    }
+    if (k) k.launch(p, 0);
+    else if (!ran) {   // (the planar tanh keeps the words its earlier refusal had)
+        glass_set_error(((ytanh ? "rgb_tanh: conv_tiled only; " : "") + std::string(labels[d->impl >= 1 && d->impl <= 6 ? d->impl : 0]) + why + ")").c_str());
         return GLASS_ERR_ARG;
     }
     int rc = finish();
@@ -398,7 +406,9 @@ extern "C" int glass_op_dblock0(int32_t device, int32_t B, int32_t R, int32_t im
         p.x = dh; p.x_bstride = (long long)R * R * Cin; p.B = B; p.H = p.W = R; p.Cin = Cin; p.Hc = p.Wc = R; p.KS = 3; p.pad = 1;
         p.w = dw0; p.Cout = p.Neff = Cin; p.Ho = p.Wo = R; p.bias = db0; p.act = 1; p.y = dh;
         p.rgb_y = dy; p.rgb_w = dfw; p.rgb_b = dfb; p.rgb_xs_out = dxs;
-        OPREQ(launch_conv_stream(p, 0) != nullptr, "dblock0 (two-kernel form): conv_stream<fromrgb> does not take this shape");
+        const ConvKernel k = choose_conv_stream(p);
+        OPREQ(k, "dblock0 (two-kernel form): conv_stream<fromrgb> does not take this shape");
+        k.launch(p, 0);
         OPREQ(launch_conv_down(dh, dxs, dw1, dws, db1, dout, B, R, Cin, Cout, 0) != nullptr, "dblock0 (two-kernel form): conv_down does not take this shape");
     }
     int rc = finish();

@@ -323,17 +323,17 @@ static GCost g_conv_cost(const GConv& g, int B) {
 //   post_style: where the fused up-conv kernel runs and that conv modulates on the activation side, its style is applied once, to the
 //     up-conv's output.
 //   planar: conv_wreg reads its input one 32-channel chunk at a time, so the up-conv writes the map chunk-planar for it (common.h
-//     x_planar8) — where the up-conv instance that can runs and the conv has no activation-side style.  (A launcher that does not read the
-//     layout refuses the layer: run_conv reports it.)
+//     x_planar8) — where the up-conv instance that can runs and conv_wreg takes the consumer as it will be launched.
 struct UpLink { bool post_style = false, planar = false; };
-static UpLink up_link(const GConv& g, const GConv& next, const ConvParams& p) {
+// p: the up-conv; next: its consumer as g_conv_params builds it
+static UpLink up_link(const ConvParams& p, ConvParams next, bool next_premod) {
     UpLink k;
-    k.post_style = !next.premod && would_run(launch_upconv_fused, p);
-    if ((k.post_style || next.premod) && conv_wreg_supported(next.cin, next.cout, g.res_out, g.res_out)) {
-        ConvParams q = p;
-        q.y_planar8 = 1;
-        k.planar = would_run(launch_upconv_fused, q);
-    }
+    k.post_style = !next_premod && choose_conv_upfir(p);
+    if (!k.post_style && !next_premod) return k;
+    next.sn = nullptr; next.sn16 = nullptr; next.x_planar8 = 1;      // (as run_g_blocks launches it behind a post_style up-conv)
+    ConvParams q = p;
+    q.y_planar8 = 1;
+    k.planar = choose_conv_wreg(next) && choose_conv_upfir(q);
     return k;
 }
 
@@ -361,16 +361,14 @@ static ConvParams torgb_conv_params(glass_engine* e, ConvParams q, const GRgb& r
 static void run_trgb_tables(glass_engine* e, const ConvParams& q, half_t* tab) {
     launch_trgb_tables(q.trgb_w, q.trgb_sn, q.trgb_sn_stride, q.trgb_smax, q.trgb_smax_stride, q.B, q.Cout, tab, e->cur);
 }
-static const char* launch_torgb_conv(const ConvParams& q, hipStream_t st) {
-    const char* k = launch_conv_glds(q, st);
-    return (k || q.trgb_part) ? k : launch_conv_tiled(q, st);
-}
-static ToRgb choose_torgb(glass_engine* e, const ConvParams& p, const GRgb& r, int c0, bool last_block, const float* yprev, float* yout) {
-    if (last_block && conv_stream_applies(torgb_conv_params(e, p, r, c0, ToRgb::stream_only, yprev, yout))) return ToRgb::stream_only;
+// the form, and for every form but `separate` the kernel that runs the conv in it
+static ToRgb choose_torgb(glass_engine* e, const ConvParams& p, const GRgb& r, int c0, bool last_block, const float* yprev, float* yout, ConvKernel* k) {
+    if (last_block && (*k = choose_conv_stream(torgb_conv_params(e, p, r, c0, ToRgb::stream_only, yprev, yout)))) return ToRgb::stream_only;
     const bool wide = r.cin > 128;
     if (wide && !(e->d_trgb_part && r.cin % 128 == 0 && r.cin <= 512)) return ToRgb::separate;
     const ToRgb form = wide ? ToRgb::partial : ToRgb::epilogue;
-    return would_run(launch_torgb_conv, torgb_conv_params(e, p, r, c0, form, yprev, yout)) ? form : ToRgb::separate;
+    *k = choose_conv(torgb_conv_params(e, p, r, c0, form, yprev, yout));
+    return *k ? form : ToRgb::separate;
 }
 
 // ------------------------------------------------------------------------------------
@@ -390,7 +388,7 @@ void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, const half
             const GConv &g = e->gconv[2 * b - 1], &next = e->gconv[2 * b];
             half_t* out = pp[(x == pp[0]) ? 1 : 0];
             ConvParams p = g_conv_params(e, g, c0, B, x, xbs, out);
-            link = up_link(g, next, p);
+            link = up_link(p, g_conv_params(e, next, c0, B, out, (long long)g.res_out * g.res_out * g.cout, pp[out == pp[0] ? 1 : 0]), next.premod);
             if (link.post_style) { p.post_scale16 = e->d_s16 + (size_t)c0 * e->S_total + next.style_off; p.post_stride = e->S_total; }
             p.y_planar8 = link.planar;
             const GCost k = g_conv_cost(g, B);
@@ -406,29 +404,30 @@ void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, const half
         p.x_planar8 = link.planar;
         const GCost k = g_conv_cost(g, B);
         const double px = B * (double)r.res * r.res, tflops = k.flops + 2.0 * px * 3 * r.cin, yup = b ? 3.0 : 0.0;
-        const ToRgb form = choose_torgb(e, p, r, c0, b == e->cfg.n_blocks - 1, yprev, yb[yi]);
+        ConvKernel fused;
+        const ToRgb form = choose_torgb(e, p, r, c0, b == e->cfg.n_blocks - 1, yprev, yb[yi], &fused);
         const ConvParams q = torgb_conv_params(e, p, r, c0, form, yprev, yb[yi]);
         x = out;
         xbs = (long long)g.res_out * g.res_out * g.cout;
         switch (form) {
         case ToRgb::stream_only: {
-            Prof pr(e, k.tag, tflops, 2.0 * B * (double)g.res_in * g.res_in * g.cin + px * (12.0 + yup));
-            pr.ran(k.tag, launch_conv_stream(q, e->cur));
+            run_chosen(e, fused, q, k.tag, tflops, 2.0 * B * (double)g.res_in * g.res_in * g.cin + px * (12.0 + yup));
             x = nullptr;   // not produced
             break;
         }
         case ToRgb::epilogue: {
             Prof pr(e, k.tag, tflops, k.bytes + px * (12.0 + yup));
             run_trgb_tables(e, q, trgb_tab(e, c0, form));
-            pr.ran(k.tag, launch_torgb_conv(q, e->cur));
+            fused.launch(q, e->cur);
+            pr.ran(k.tag, fused.name);
             break;
         }
         case ToRgb::partial: {
             Prof pr(e, k.tag, tflops, k.bytes + px * (12.0 * (1 + 2 * (r.cin / 128)) + yup));
             run_trgb_tables(e, q, trgb_tab(e, c0, form));
-            const char* kernel = launch_torgb_conv(q, e->cur);
+            fused.launch(q, e->cur);
             launch_trgb_finish(e->d_trgb_part, r.cin / 128, B, r.res, r.bias, yprev, yb[yi], e->cur);
-            pr.ran(k.tag, kernel);
+            pr.ran(k.tag, fused.name);
             break;
         }
         case ToRgb::separate: {
@@ -469,6 +468,16 @@ static bool run_d_block0(glass_engine* e, int B, const DBlock& d, const float* r
     return k != nullptr;
 }
 
+// The block's first conv, h = conv0(x) in Hb, as run_d_conv0 launches it.  XS != nullptr: with the blur-down of x (the skip branch's input) as a by-product
+static ConvParams d_conv0_params(int B, const DBlock& d, const half_t* X, bool x_planar, half_t* Hb, half_t* XS) {
+    const int r = d.res;
+    ConvParams p = conv_defaults();
+    p.x = X; p.x_bstride = (long long)r * r * d.cin; p.B = B; p.H = p.W = r; p.Cin = d.cin;
+    p.Hc = p.Wc = r; p.KS = 3; p.pad = 1; p.w = d.w0; p.Cout = p.Neff = d.cin; p.Ho = p.Wo = r;
+    p.bias = d.b0; p.act = 1; p.y = Hb; p.x_planar8 = x_planar; p.xs_out = XS;
+    return p;
+}
+
 // First half of a block: h = conv0(x) in Hb.  Returns whether the launch also wrote XS, the blur-down of x that the skip branch reads.
 // rgb_y != nullptr: X has NOT been produced yet — the conv builds the fromRGB map from the skip image on the fly and writes it to X
 // (or, where the fused second half follows, its blur-down to XS) as a side output (conv_stream<fromrgb>), or, where that kernel does not
@@ -476,34 +485,28 @@ static bool run_d_block0(glass_engine* e, int B, const DBlock& d, const float* r
 static bool run_d_conv0(glass_engine* e, int B, const DBlock& d, half_t* X, bool x_planar, const float* rgb_y, half_t* Hb, half_t* XS) {
     char tag[64];
     const int r = d.res;
-    ConvParams p = conv_defaults();
-    p.x = X; p.x_bstride = (long long)r * r * d.cin; p.B = B; p.H = p.W = r; p.Cin = d.cin;
-    p.Hc = p.Wc = r; p.KS = 3; p.pad = 1; p.w = d.w0; p.Cout = p.Neff = d.cin; p.Ho = p.Wo = r;
-    p.bias = d.b0; p.act = 1; p.y = Hb;
-    p.x_planar8 = x_planar;
+    const ConvParams p = d_conv0_params(B, d, X, x_planar, Hb, nullptr);
     if (rgb_y) {
         const bool fuse_down = conv_down_supported(r, d.cin, d.cout);
         ConvParams q = p;
         q.rgb_y = rgb_y; q.rgb_w = e->d_frgb_w; q.rgb_b = e->d_frgb_b;
         q.rgb_x_out = fuse_down ? nullptr : X;       // the fused second half reads the down-sampled skip input only
         q.rgb_xs_out = fuse_down ? XS : nullptr;
-        snprintf(tag, sizeof tag, "D.fromrgb+conv0.r%d.%dx%d", r, d.cin, d.cin);
-        const double px = (double)B * r * r;
-        Prof pr(e, tag, 2.0 * px * (9.0 * d.cin * d.cin + 3.0 * d.cin), px * (12.0 + 2.0 * d.cin + (fuse_down ? 0.5 : 2.0) * d.cin));
-        if (const char* k = launch_conv_stream(q, e->cur)) {
-            pr.ran(tag, k);
+        if (const ConvKernel k = choose_conv_stream(q)) {
+            snprintf(tag, sizeof tag, "D.fromrgb+conv0.r%d.%dx%d", r, d.cin, d.cin);
+            const double px = (double)B * r * r;
+            run_chosen(e, k, q, tag, 2.0 * px * (9.0 * d.cin * d.cin + 3.0 * d.cin), px * (12.0 + 2.0 * d.cin + (fuse_down ? 0.5 : 2.0) * d.cin));
             return fuse_down;
         }
-        pr.drop();
         run_fromrgb(e, B, rgb_y, X);
     }
-    ConvParams qx = p;
-    qx.xs_out = XS;
-    const bool have_xs = would_run(launch_conv_glds, qx) || would_run(launch_conv_tiled, qx);   // the skip branch's blur-down rides in the first conv
+    const ConvParams qx = d_conv0_params(B, d, X, x_planar, Hb, XS);
+    const ConvKernel kx = choose_conv(qx);           // the skip branch's blur-down rides in the first conv where a family does that
     snprintf(tag, sizeof tag, "D.conv0.r%d.%dx%d", r, d.cin, d.cin);
-    run_conv(e, have_xs ? qx : p, tag, 2.0 * B * (double)r * r * 9 * d.cin * d.cin, 4.0 * B * (double)r * r * d.cin + (have_xs ? 0.5 * B * (double)r * r * d.cin : 0.0));
-    if (!have_xs && x_planar && e->launch_error.empty()) e->launch_error = std::string("chunk-planar block input without the fused blur-down: ") + tag;
-    return have_xs;
+    const double flops = 2.0 * B * (double)r * r * 9 * d.cin * d.cin, bytes = 4.0 * B * (double)r * r * d.cin;
+    if (kx) run_chosen(e, kx, qx, tag, flops, bytes + 0.5 * B * (double)r * r * d.cin);
+    else run_conv(e, p, tag, flops, bytes);
+    return (bool)kx;
 }
 
 // Second half of a block: out = (lrelu(conv1 stride 2 (blur(h)) + b1) * sqrt2 + skip(XS)) / sqrt2 in O, from h in Hb and (have_xs) XS
@@ -534,9 +537,9 @@ static void run_d_conv1(glass_engine* e, int B, const DBlock& d, const half_t* X
     ConvParams qs = q;
     qs.skip_x = XS; qs.skip_w = d.wskip; qs.x_planar32 = 1;
     // blur -> conv_s2 link: that kernel stages its input one 32-channel chunk per K step, so (where it runs) the blur writes 32-channel planes
-    const auto conv_s2 = +[](const ConvParams& p, hipStream_t st) { return launch_conv_s2(p, st); };
-    const bool hb_planar = blur_pad2_planar32_ok(d.cin) && would_run(conv_s2, qs);
+    const bool hb_planar = blur_pad2_planar32_ok(d.cin) && choose_conv_s2(qs);
     qs.x_planar32 = hb_planar;
+    const ConvKernel fused = choose_conv(qs);
     {
         snprintf(tag, sizeof tag, "D.blur.r%d", r);
         Prof pr(e, tag, 2.0 * B * (double)(r + 1) * (r + 1) * d.cin * 16, 4.0 * B * (double)r * r * d.cin);
@@ -544,10 +547,8 @@ static void run_d_conv1(glass_engine* e, int B, const DBlock& d, const half_t* X
     }
     snprintf(tag, sizeof tag, "D.conv1.r%d.%dx%d", r2, d.cin, d.cout);
     const double f1 = 2.0 * B * (double)r2 * r2 * 9 * d.cin * d.cout, fs = 2.0 * B * (double)r2 * r2 * d.cin * d.cout;
-    const auto fused = hb_planar ? conv_s2 : launch_conv_tiled;
-    if (hb_planar || would_run(launch_conv_tiled, qs)) {
-        Prof pr(e, tag, f1 + fs, 2.0 * B * ((double)(r + 1) * (r + 1) * d.cin + (double)r2 * r2 * (d.cin + d.cout)));
-        pr.ran(tag, fused(qs, e->cur));
+    if (fused) {
+        run_chosen(e, fused, qs, tag, f1 + fs, 2.0 * B * ((double)(r + 1) * (r + 1) * d.cin + (double)r2 * r2 * (d.cin + d.cout)));
         return;
     }
     ConvParams s = conv_defaults();
@@ -570,7 +571,7 @@ half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* X, half
         const DBlock& d = e->dblk[i];
         const float* y = i == 0 ? rgb_y : nullptr;
         // the next block's first conv on conv_wreg (with the blur-down by-product: nothing else reads this map): chunk-planar output
-        const bool planar = y && i + 1 < i_hi && e->dblk[i + 1].cin == d.cout && conv_wreg_supported(d.cout, d.cout, d.res / 2, d.res / 2);
+        const bool planar = y && i + 1 < i_hi && e->dblk[i + 1].cin == d.cout && choose_conv_wreg(d_conv0_params(B, e->dblk[i + 1], O, true, Hb, XS));
         const bool whole = y && run_d_block0(e, B, d, y, O, planar);
         if (!whole) {
             const bool have_xs = run_d_conv0(e, B, d, X, x_planar, y, Hb, XS);

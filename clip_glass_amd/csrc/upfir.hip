@@ -599,20 +599,16 @@ static int upfir2_model_steps(int per_seg, int out_rows, int TR, int slots, int 
     return best;
 }
 
-static const char* launch_upfir2(const ConvParams& p, hipStream_t st) {
-    if (p.Cin > 512 || p.H < 8 || p.W < 8) return nullptr;
-    if ((long long)p.B * p.H * p.W * p.Cin >= (1LL << 31) || 9LL * p.Cout * p.Cin >= (1LL << 31)) return nullptr;
-    if (p.x_bstride != (long long)p.H * p.W * p.Cin) return nullptr;
-    // per-sample weights carry style and demodulation: the lean single-image instance; anything else goes through the tables
-    const bool lean = p.w_bstride && !p.sn16 && !p.dscale;
-    if (p.y_planar8 && !lean) return nullptr;    // the chunk-planar output (common.h) is the single-image instance's
+// what upfir2_kernel implements: the up-convolution from the un-folded weights; <false> is the lean single-image instance
+static constexpr uint32_t UPFIR_FEATURES = CF_UP | CF_STYLE | CF_DEMOD | CF_NOISE | CF_SAMPLE_W | CF_POST_SCALE | CF_Y_PLANAR8;
+// per-sample weights carry style and demodulation: the lean single-image instance; anything else goes through the tables
+static bool upfir2_lean(const ConvParams& p) { return p.w_bstride && !p.sn16 && !p.dscale; }
+
+template <bool TABLES>
+static void launch_upfir2(const ConvParams& p, hipStream_t st) {
     constexpr int LDS = UStep::LDS, TR = UStep::TR;
-    if (!glass_lds_fits(LDS)) return nullptr;                 // (the caller falls through to the folded form)
     static DevOnce once;
-    once.run([&] {
-        (void)hipFuncSetAttribute((const void*)upfir2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute((const void*)upfir2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    });
+    once.run([&] { (void)hipFuncSetAttribute((const void*)upfir2_kernel<TABLES>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); });
     UpGeo g;
     g.NTn = p.Cout / 32;
     // candidates per virtual grid: per-sample weights -> one (its tiles share a weight set); shared weights -> up to 8 x 8
@@ -645,7 +641,7 @@ static const char* launch_upfir2(const ConvParams& p, hipStream_t st) {
     // S = 5 and 10, maximum at 8, as measured: 457 / 455 / 588 us against 514 at the old S = 2; r32: 183 -> 143 us at S = 3): S = the model's
     // minimum among the lengths that still fill every slot once — where the count rule ends at S <= 2 (at S = 4 / 8, r128 / r256, the model's pick measured
     // 1-3 % slower than the rule's: those launches have enough rounds to average out).  (S only decides which t rows are recomputed: results do not depend on it.)
-    if (!lean && S <= 2) S = upfir2_model_steps(g.n_grids * g.tiles_x * g.NTn, out_rows, TR, 2 * glass_cu_count(), S);
+    if (TABLES && S <= 2) S = upfir2_model_steps(g.n_grids * g.tiles_x * g.NTn, out_rows, TR, 2 * glass_cu_count(), S);
     g.S = S;
     const int R = (TR - 4) + TR * (S - 1);
     g.n_seg = (out_rows + R - 1) / R;
@@ -659,19 +655,22 @@ static const char* launch_upfir2(const ConvParams& p, hipStream_t st) {
     }
     g.ngroups = ng;
     g.invPX = u_inv(PX); g.invPY = u_inv(PY); g.inv2PX = u_inv(2 * PX); g.inv2PY = u_inv(2 * PY);
-    const char* name = lean ? "upfir2_kernel<false>" : "upfir2_kernel<true>";
-    if (p.dry_run) return name;
     const int Pp = 8 / ng;
     const int grid = 8 * ((g.WT + Pp - 1) / Pp) * (g.NTn / ng);
-    if (lean) hipLaunchKernelGGL((upfir2_kernel<false>), dim3(grid), dim3(256), LDS, st, p, g);
-    else hipLaunchKernelGGL((upfir2_kernel<true>), dim3(grid), dim3(256), LDS, st, p, g);
-    return name;
+    hipLaunchKernelGGL((upfir2_kernel<TABLES>), dim3(grid), dim3(256), LDS, st, p, g);
 }
 
-// The up-convolution as one upfir2 launch, or nullptr: the caller then runs the folded form (conv_tiled with Neff = 4 Cout)
-const char* launch_upconv_fused(const ConvParams& p, hipStream_t st) {
-    if (!p.up || !p.w_up || p.y32 || !p.y || p.res || (p.sn && !p.sn16)) return nullptr;
-    if (p.Cin % 32 != 0 || p.Cout % 32 != 0 || p.KS != 3) return nullptr;
-    if (p.x_planar8 || p.x_planar32) return nullptr;   // chunk-planar input (common.h): not implemented here
-    return launch_upfir2(p, st);
+// The up-convolution as one upfir2 launch, or refused: the caller then runs the folded form (conv_tiled with Neff = 4 Cout)
+ConvKernel choose_conv_upfir(const ConvParams& p) {
+    const uint32_t f = conv_features(p);
+    if (f & ~UPFIR_FEATURES) return conv_refused(f & ~UPFIR_FEATURES);
+    if (!p.up || !p.w_up || !p.y || ((f & CF_STYLE) && !p.sn16)) return conv_refused();
+    if (p.Cin % 32 != 0 || p.Cout % 32 != 0 || p.KS != 3) return conv_refused();
+    if (p.Cin > 512 || p.H < 8 || p.W < 8) return conv_refused();
+    if ((long long)p.B * p.H * p.W * p.Cin >= (1LL << 31) || 9LL * p.Cout * p.Cin >= (1LL << 31)) return conv_refused();
+    if (p.x_bstride != (long long)p.H * p.W * p.Cin) return conv_refused();
+    const bool lean = upfir2_lean(p);
+    if (p.y_planar8 && !lean) return conv_refused();    // the chunk-planar output (common.h) is the single-image instance's
+    if (!glass_lds_fits(UStep::LDS)) return conv_refused();                 // (the caller falls through to the folded form)
+    return lean ? ConvKernel{"upfir2_kernel<false>", launch_upfir2<false>} : ConvKernel{"upfir2_kernel<true>", launch_upfir2<true>};
 }

@@ -28,7 +28,7 @@ class ConvDesc(C.Structure):
                 ("premod", C.c_int32), ("post_scale", C.POINTER(C.c_float)), ("y_planar8", C.c_int32),
                 ("trgb_partial", C.c_int32),
                 ("pre_shift", C.POINTER(C.c_float)), ("in_up", C.c_int32), ("shift", C.POINTER(C.c_float)),
-                ("res_cs", C.c_int32), ("res_up", C.c_int32), ("rgb_tanh", C.POINTER(C.c_float))]
+                ("res_cs", C.c_int32), ("res_up", C.c_int32), ("rgb_tanh", C.POINTER(C.c_float)), ("trgb_keep_map", C.c_int32)]
 
 
 def to_planar8(a):
@@ -64,7 +64,7 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
          planar_y=False, trgb_partial=False, pre_shift=None, in_up=False, shift=None, res_cs=0, res_up=False, rgb_tanh=False):
     """x [B,H,W,Cin] NHWC; w [Cout,Cin,KS,KS] (reference layout).  Returns y [B,Ho,Wo,Cout].
     torgb = dict(w [3,Cout], b [3], sn [B,Cout], smax [B], yprev [B,3,Ho/2,Wo/2] or None) with impl=4: the fused conv + toRGB
-    form of the streaming kernel — returns the skip image [B,3,Ho,Wo] instead of y.
+    form of the streaming kernel — returns the skip image [B,3,Ho,Wo] instead of y (with both=True it is asked for the map too, and refuses).
     planar_x: the device gets x chunk-planar (the permutation happens here; impl 5, 64 -> 64).
     The forms the StyleGAN2 host builds (csrc/stylegan2.cpp): premod — sn / dscale go into per-sample weights first
     (modulate_weights_kernel) and the conv runs without them; post_scale [B,Cout] — the consumer's style applied to the finished
@@ -100,6 +100,7 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
     d.x_planar32 = int(planar32_x)
     d.premod, d.y_planar8, d.trgb_partial = int(premod), int(planar_y), int(trgb_partial)
     d.in_up, d.res_cs, d.res_up = int(in_up), int(res_cs), int(res_up)
+    d.trgb_keep_map = int(both)     # (impl 4 writes the skip image INSTEAD of the map: with both it refuses)
     keep = []
     d.x, d.w, d.y = _fp(x), _fp(w), _fp(y)
     for name, val in (("sn", sn), ("dscale", dscale), ("noise", noise), ("bias", bias), ("res", res), ("post_scale", post_scale),

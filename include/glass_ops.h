@@ -25,7 +25,8 @@ typedef struct glass_conv_desc {
     int32_t broadcast_x;   /* x is [1,H,W,Cin], shared by all B (the learned const) */
     int32_t act;           /* leaky-relu 0.2 * sqrt(2) */
     int32_t batch_size;    /* candidates per noise plane */
-    int32_t impl;          /* 0 auto, 1 direct, 2 tiled, 3 fused up-conv, 4 streaming 32->32, 5 LDS-DMA, 6 im2col + GEMM (error if unsupported) */
+    int32_t impl;          /* 0 auto, 1 direct, 2 tiled (behind conv_s2 where that fills the chip), 3 fused up-conv, 4 streaming 32->32, 5 LDS-DMA (conv_wreg, conv_glds; conv_s2 with skip_x), 6 im2col + GEMM.
+                            * A refusal is an error that names the families asked and the features they lack */
     float noise_strength, out_scale;
     const float* x;        /* [B,H,W,Cin] */
     const float* w;        /* reference layout [Cout,Cin,KS,KS], un-scaled (coef applied inside) */
@@ -69,7 +70,8 @@ typedef struct glass_conv_desc {
     int32_t res_cs;          /* channel stride of the residual rows (0 = Cout): the first Cout of res_cs channels are added (channel-drop skip) */
     int32_t res_up;          /* res is [B,Ho/2,Wo/2,res_cs ? res_cs : Cout], read through a nearest x2 upsample */
     float* rgb_tanh;         /* [B,3,Ho,Wo] or NULL: tanh of output channels 0..2 from the accumulators (ConvParams::rgb_tanh_out), y is not written.
-                              * As run_conv: conv_tiled only (impl 0 / 2); any other impl, or a refusal, is an error */
+                              * Only conv_tiled implements it (impl 0 / 2); any other impl, or a refusal, is an error */
+    int32_t trgb_keep_map;   /* impl 4 with the trgb_* inputs: ask for the skip image AND the stored map (conv_stream writes one of them: it refuses) */
 } glass_conv_desc;
 
 int glass_op_conv(int32_t device, const glass_conv_desc* d);

@@ -151,7 +151,7 @@ def test_conv1_form(impl, B, h, w_, C, up):
 
 # ---- conv2 form: 3x3, bn + relu in the epilogue ---------------------------------------------------------------------------------------
 def _stream_shape():
-    """The smallest map conv_stream_applies accepts: 64 nominal candidates x (W / 32) (H / 8) tiles >= 6 per slot, 3 slots per CU."""
+    """The smallest map choose_conv_stream accepts: 64 nominal candidates x (W / 32) (H / 8) tiles >= 6 per slot, 3 slots per CU."""
     from clip_glass_amd.engine import device_info
     need = -(-device_info(0)["cus"] * 3 * 6 // 64)
     return 64, 32 * -(-need // 8)

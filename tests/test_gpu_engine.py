@@ -240,7 +240,9 @@ def test_launch_table_is_pinned():
     against tests/golden/launch_table.json, recorded on the MI355X from the commit BEFORE the block walkers were rewritten.  A walker that
     falls back to a slower but correct path passes every parity test; it does not pass this one.  `mid` and `r128` (glass_models.py) are
     the smallest networks that reach the walkers' branches; the conditions below say which.  Not reachable at 128 px or below:
-    conv_stream_kernel<torgb> (its admission wants 72 tiles per image: 256 px) and dblock0's chunk-planar output for conv_wreg (256 px)."""
+    conv_stream_kernel<torgb> (its admission wants 72 tiles per image: 256 px) and dblock0's chunk-planar output for conv_wreg (256 px) —
+    so `ffhq` at one minibatch (P = 4: instance choice is made at the nominal population, so this is the benchmark's table) and `bg256`
+    are pinned too, recorded from the commit BEFORE the conv families got their feature masks and choosers."""
     import json
     import os
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_table.json")) as f:
@@ -260,12 +262,22 @@ def test_launch_table_is_pinned():
     assert any(n.startswith("D.conv1.") and n.endswith("skip>") for n in every)
     assert any(n.startswith("D.skip.") for n in every)                                  # separate skip + residual
     assert "D.fromrgb" in names["r128"] and any(n.startswith("D.blurdown.") for n in every)
-    for name in ("mid", "r128"):
-        c = M.CONFIGS[name]
-        e = M.make_engine(name, M.make_state(name, 0), batch_size=4, use_discriminator=True, max_pop=4, noise_mode=1)
+    assert "G.conv.r1024.32x32@conv_stream_kernel<torgb>" in names["ffhq"]               # the map of the last G conv is never stored
+    assert follows(names["ffhq"], "@dblock0_kernel", "D.conv0.r512.64x64@conv_wreg_kernel<false,true>")   # dblock0's chunk-planar output
+    assert any(n.endswith("@conv_down64_kernel") for n in names["ffhq"])
+    assert "bg.final.conv_to_rgb+tanh@conv_tiled_kernel<3,1,8,32>" in names["bg256"]    # the planar tanh: conv_tiled's alone
+    for name in ("mid", "r128", "ffhq", "bg256"):
+        if name in M.BIGGAN_CONFIGS:
+            c = M.BIGGAN_CONFIGS[name]
+            e = M.make_biggan_engine(name, M.make_biggan_state(name, 0), batch_size=4, max_pop=4)
+            x = synth.biggan_population(1, 4, c["z_dim"], c["num_classes"])
+        else:
+            c = M.CONFIGS[name]
+            e = M.make_engine(name, M.make_state(name, 0), batch_size=4, use_discriminator=True, max_pop=4, noise_mode=1)
+            x = synth.latents(1, 4, c["latent"])
         e.set_target(np.ones(c["clip"][5], np.float32))
         e.set_profiling(True)
-        e.evaluate(synth.latents(1, 4, c["latent"]))
+        e.evaluate(x)
         rows = [[r["name"], r["launches"]] for r in e.profile()]
         e.close()
         diff = [(i, a, b) for i, (a, b) in enumerate(zip(rows, golden[name])) if a != b]
