@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <string>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -93,6 +94,24 @@ struct DevOnce {
         }
     }
 };
+// Where a launcher sends its kernel: a stream — or, with `list` set, a text that receives one line per launch (the kernel's profile name, its
+// grid and its block) while nothing is launched and no pointer is followed: the same host code then tells what it would run.
+struct LaunchTo {
+    hipStream_t st = nullptr;
+    std::string* list = nullptr;
+    LaunchTo(hipStream_t s) : st(s) {}
+    explicit LaunchTo(std::string* l) : list(l) {}
+};
+template <class... P, class... A>
+inline void launch_kernel(const LaunchTo& to, const char* name, void (*kernel)(P...), dim3 g, dim3 b, size_t lds, A... args) {
+    if (to.list) {
+        char line[192];
+        snprintf(line, sizeof line, "%s grid=%u,%u,%u block=%u,%u,%u\n", name, g.x, g.y, g.z, b.x, b.y, b.z);
+        *to.list += line;
+        return;
+    }
+    hipLaunchKernelGGL(kernel, g, b, lds, to.st, static_cast<P>(args)...);
+}
 struct GlassDevProps { int cus, lds_optin; };
 inline GlassDevProps glass_dev_props() {   // CU count and the largest dynamic-LDS block a kernel may opt in to, current device
     static std::atomic<int> cus[32] = {}, lds[32] = {};

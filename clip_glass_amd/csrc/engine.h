@@ -83,6 +83,16 @@ int glass_biggan_prepare(glass_engine* e, int P); // cond vectors + batch-norm t
 // synthesize candidates [c0, c0 + B) -> planar fp32 RGB in (-1, 1) at `y` [B][3][R][R]
 int glass_biggan_chunk(glass_engine* e, int c0, int B, float* y);
 
+// What one GPT-2 token step launches for a geometry (gpt2_host.cpp, plan_gpt2_step): every choice is made here, before the step runs.
+struct Gpt2StepPlan {
+    bool fused = false;       // LayerNorm inside the products, residual + statistics passes; false: the unfused step, which takes every shape
+    bool rowblk = false;      // o / fc in the complete-output form (no finishing launch behind them)
+    bool att_step = false;    // Tmax <= 64: one wave per (sequence, head), which sums the qkv slices itself
+    StepGemm qkv, o, fc, pr;  // per layer: qkv, attention output, MLP first, MLP second
+    Gpt2Head head;            // head + its pick (a tail where the width allows); empty: `logits`, then launch_argmax / launch_gpt2_sample
+    StepGemm logits;
+};
+
 struct ProfEvent {
     std::string name;
     double flops, bytes;
@@ -141,7 +151,8 @@ struct glass_engine {
     struct Gpt2Work {
         int P = 0, nctx = 0, length = 0;
         int *d_tok = nullptr, *d_gen = nullptr, *d_state = nullptr, *d_samp = nullptr;   // d_samp: the sampler's per-call words (GPT2_SP_*)
-        int sample = 0;           // mode the captured step graph was recorded in: 0 greedy, 1 stochastic
+        int sample = -1;          // mode the step was planned and its graph recorded in: 0 greedy, 1 stochastic (-1: neither yet)
+        Gpt2StepPlan plan;        // the token step of this geometry in that mode
         float *x = nullptr, *ln = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *last = nullptr, *logits = nullptr,
               *kc = nullptr, *vc = nullptr, *part = nullptr, *stats = nullptr, *pairs = nullptr, *pst = nullptr;   // stats: [P][2] LayerNorm {mean, rstd} of the fused step
         size_t part_elems = 0;

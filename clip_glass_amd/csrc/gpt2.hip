@@ -53,19 +53,19 @@ __global__ __launch_bounds__(256) void gpt2_embed_step_kernel(const int* gen, co
     const float m2 = block_sum(q), var = m2 / (float)D;
     if (t == 0) { stats[2 * row] = mean; stats[2 * row + 1] = partial_fmt ? m2 : rsqrtf(var + 1e-5f); }      // partial_fmt: ONE (mean, M2) partial over the row
 }
-void launch_gpt2_embed_step(const int* gen, const int* state, int P, const float* wte, const float* wpe, int D, float* x, hipStream_t st,
+void launch_gpt2_embed_step(const int* gen, const int* state, int P, const float* wte, const float* wpe, int D, float* x, const LaunchTo& to,
                             float* stats, bool partial_fmt) {
-    hipLaunchKernelGGL(gpt2_embed_step_kernel, dim3(P), dim3(256), 0, st, gen, state, P, wte, wpe, D, x, D <= 1024 ? stats : nullptr, partial_fmt ? 1 : 0);
+    launch_kernel(to, "gpt2_embed_step_kernel", gpt2_embed_step_kernel, dim3(P), dim3(256), 0, gen, state, P, wte, wpe, D, x, D <= 1024 ? stats : nullptr, partial_fmt ? 1 : 0);
 }
 __global__ void gpt2_advance_kernel(int* state) {
     state[0] += 1;
     state[1] += 1;
 }
-void launch_gpt2_advance(int* state, hipStream_t st) { hipLaunchKernelGGL(gpt2_advance_kernel, dim3(1), dim3(1), 0, st, state); }
+void launch_gpt2_advance(int* state, const LaunchTo& to) { launch_kernel(to, "gpt2_advance_kernel", gpt2_advance_kernel, dim3(1), dim3(1), 0, state); }
 
 void launch_gpt2_embed(const int* tok, const float* wte, const float* wpe, int rows, int L, int pos0, int D, float* x,
-                       hipStream_t st) {
-    hipLaunchKernelGGL(gpt2_embed_kernel, dim3(rows), dim3(128), 0, st, tok, wte, wpe, L, pos0, D, x);
+                       const LaunchTo& to) {
+    launch_kernel(to, "gpt2_embed_kernel", gpt2_embed_kernel, dim3(rows), dim3(128), 0, tok, wte, wpe, L, pos0, D, x);
 }
 
 // ---- fp32 GEMM: out[M][N] = A[M][K] @ W[N][K]^T (+bias) with epilogue ------------------------------------
@@ -302,16 +302,18 @@ __global__ __launch_bounds__(128 * NK) void gemm_f32_stream_kernel(const float* 
         out[oi] = v;
     }
 }
-template <int NK>
-static void launch_stream_inst(const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int lda, int ldo, int mode,
-                               hipStream_t st, float* part, int S, const float* stats = nullptr, const float* lng = nullptr,
-                               const float* lnb = nullptr) {
-    const bool one = K / S / NK == GS_KC;
-    const dim3 g((N + 31) / 32, S), b(128 * NK);
-#define GS_LAUNCH(LN, ON) hipLaunchKernelGGL((gemm_f32_stream_kernel<NK, LN, ON>), g, b, 0, st, A, W, bias, out, M, N, K, lda, ldo, mode, part, K / S, stats, lng, lnb)
-    if (stats) { if (one) GS_LAUNCH(true, true); else GS_LAUNCH(true, false); }
-    else { if (one) GS_LAUNCH(false, true); else GS_LAUNCH(false, false); }
-#undef GS_LAUNCH
+// the instance for (NK, LNX, ONE): its profile name and its kernel
+struct StreamInst {
+    const char* name;
+    decltype(&gemm_f32_stream_kernel<1, false, false>) kernel;
+};
+static StreamInst stream_inst(int NK, bool ln, bool one) {
+#define GS_INST(NK, LN, ON) {"gemm_f32_stream_kernel<" #NK "," #LN "," #ON ">", gemm_f32_stream_kernel<NK, LN, ON>}
+#define GS_ROW(NK) {GS_INST(NK, false, false), GS_INST(NK, false, true), GS_INST(NK, true, false), GS_INST(NK, true, true)}
+    static const StreamInst inst[4][4] = {GS_ROW(1), GS_ROW(2), GS_ROW(4), GS_ROW(6)};
+#undef GS_ROW
+#undef GS_INST
+    return inst[NK == 6 ? 3 : NK == 4 ? 2 : NK == 2 ? 1 : 0][2 * ln + one];
 }
 
 // ---- single-token steps, complete-output form (round 4) ---------------------------------------------------------------------------------
@@ -456,18 +458,30 @@ __global__ __launch_bounds__(64 * NK) void gemm_f32_rowblk_kernel(const float* A
 bool gemm_f32_rowblk_supported(int M, int N, int K, int lda, bool ln_fused, bool stats_out) {
     return M > 0 && M <= 64 && N % 32 == 0 && K % (12 * GS_KC) == 0 && lda % 4 == 0 && !(ln_fused && K > 1024) && !(stats_out && N / 32 > 24);
 }
-// false: shape not covered, nothing launched.  pst_in / np_in: the LayerNorm-fused operand's row partials; pst_out: [M][N / 32][2]
-bool launch_gemm_f32_rowblk(const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int lda, int ldo, int mode,
-                            hipStream_t st, const float* pst_in, int np_in, const float* lng, const float* lnb, float* pst_out) {
-    if (!gemm_f32_rowblk_supported(M, N, K, lda, pst_in != nullptr, pst_out != nullptr) || (pst_in && (np_in < 1 || np_in > 24 || K % np_in != 0)))
-        return false;
-    const dim3 g(N / 32, (M + 31) / 32), b(64 * 12);
-    const bool one = K == 12 * GS_KC;
-#define RB_LAUNCH(LN, ON) hipLaunchKernelGGL((gemm_f32_rowblk_kernel<12, LN, ON>), g, b, 0, st, A, W, bias, out, M, N, K, lda, ldo, mode, pst_in, np_in, lng, lnb, pst_out)
-    if (pst_in) { if (one) RB_LAUNCH(true, true); else RB_LAUNCH(true, false); }
-    else { if (one) RB_LAUNCH(false, true); else RB_LAUNCH(false, false); }
-#undef RB_LAUNCH
-    return true;
+struct RowblkInst {
+    const char* name;
+    decltype(&gemm_f32_rowblk_kernel<12, false, false>) kernel;
+};
+static RowblkInst rowblk_inst(bool ln, bool one) {
+#define RB_INST(LN, ON) {"gemm_f32_rowblk_kernel<12," #LN "," #ON ">", gemm_f32_rowblk_kernel<12, LN, ON>}
+    static const RowblkInst inst[4] = {RB_INST(false, false), RB_INST(false, true), RB_INST(true, false), RB_INST(true, true)};
+#undef RB_INST
+    return inst[2 * ln + one];
+}
+// The row-block form's answer for a product, or an empty value.  np_in: the row partials per row a LayerNorm-fused operand combines (it
+// divides K; at most 24); stats_out: the epilogue leaves [M][N / 32][2] row partials.
+StepGemm choose_gemm_f32_rowblk(int M, int N, int K, int lda, bool ln_fused, int np_in, bool stats_out) {
+    if (!gemm_f32_rowblk_supported(M, N, K, lda, ln_fused, stats_out) || (ln_fused && (np_in < 1 || np_in > 24 || K % np_in != 0))) return StepGemm();
+    StepGemm c;
+    c.S = 1; c.NK = 12; c.LN = ln_fused; c.ONE = K == 12 * GS_KC;
+    c.M = M; c.N = N; c.K = K; c.lda = lda; c.np_in = ln_fused ? np_in : 0;
+    c.grid = dim3(N / 32, (M + 31) / 32); c.block = dim3(64 * 12);
+    c.name = rowblk_inst(c.LN, c.ONE).name;
+    return c;
+}
+// o.stats: the LayerNorm-fused operand's row partials [M][np_in][2]
+void launch_gemm_f32_rowblk(const StepGemmOperands& o, const StepGemm& c, const LaunchTo& to) {
+    launch_kernel(to, c.name, rowblk_inst(c.LN, c.ONE).kernel, c.grid, c.block, 0, o.A, o.W, o.bias, o.out, c.M, c.N, c.K, c.lda, o.ldo, o.mode, o.stats, c.np_in, o.lng, o.lnb, o.pst_out);
 }
 
 // x[m][:] += bias + sum_s part[s][m][:] (split-K slices in a fixed order; part == nullptr: x as it is), then the row's LayerNorm statistics
@@ -519,8 +533,8 @@ __global__ __launch_bounds__(256) void gpt2_finalize_kernel(const float* part, i
     const float var = block_sum(q) / (float)D;
     if (t == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rsqrtf(var + 1e-5f); }
 }
-void launch_gpt2_finalize(const float* part, int S, const float* bias, float* x, int M, int D, float* stats, hipStream_t st) {
-    hipLaunchKernelGGL(gpt2_finalize_kernel, dim3(M), dim3(256), 0, st, part, S, bias, x, M, D, stats);
+void launch_gpt2_finalize(const float* part, int S, const float* bias, float* x, int M, int D, float* stats, const LaunchTo& to) {
+    launch_kernel(to, "gpt2_finalize_kernel", gpt2_finalize_kernel, dim3(M), dim3(256), 0, part, S, bias, x, M, D, stats);
 }
 
 // ---- vocabulary projection of a single-token step: LayerNorm and the greedy pick's first stage fused -----------------------------------
@@ -722,26 +736,6 @@ __global__ __launch_bounds__(256) void gpt2_pick_embed_kernel(const float* pv, c
     gpt2_step_tail(bi[0], row, past, step, gen, state, P, wte, wpe, D, x, stats, red);
 }
 bool gpt2_head_supported(int M, int N, int K, int lda) { return M <= 64 && K % GS_KC == 0 && lda % 4 == 0 && N >= 4096; }
-// the vocabulary projection + the fused pick / embed / advance tail (D <= 1024); false: shape not covered, nothing launched
-bool launch_gpt2_head_tail(const float* A, const float* W, int M, int N, int K, int lda, const float* stats_in, const float* lng, const float* lnb,
-                           float* pairs, int* gen, int* state, const float* wte, const float* wpe, float* x, float* stats_out, hipStream_t st) {
-    if (!gpt2_head_supported(M, N, K, lda) || !pairs || K > 1024) return false;
-    const int NB = (N + 31) / 32;
-    int* pi = (int*)(pairs + (size_t)M * NB);
-    hipLaunchKernelGGL(gpt2_head_kernel, dim3((NB + HD_NW - 1) / HD_NW), dim3(64 * HD_NW), 0, st, A, W, M, N, K, lda, stats_in, lng, lnb, (float*)nullptr, pairs, pi, NB);
-    hipLaunchKernelGGL(gpt2_pick_embed_kernel, dim3(M), dim3(256), 0, st, pairs, pi, NB, gen, state, M, wte, wpe, K, x, stats_out);
-    return true;
-}
-// false: shape not covered (caller: generic product + launch_argmax).  pairs: scratch of 2 * M * ceil(N / 32) words.
-bool launch_gpt2_head(const float* A, const float* W, int M, int N, int K, int lda, const float* stats, const float* lng, const float* lnb,
-                      float* logits, float* pairs, int* out, const int* step_dev, hipStream_t st) {
-    if (!gpt2_head_supported(M, N, K, lda) || !pairs) return false;
-    const int NB = (N + 31) / 32;
-    int* pi = (int*)(pairs + (size_t)M * NB);
-    hipLaunchKernelGGL(gpt2_head_kernel, dim3((NB + HD_NW - 1) / HD_NW), dim3(64 * HD_NW), 0, st, A, W, M, N, K, lda, stats, lng, lnb, logits, pairs, pi, NB);
-    hipLaunchKernelGGL(argmax_pairs_kernel, dim3(M), dim3(256), 0, st, pairs, pi, NB, out, step_dev);
-    return true;
-}
 
 // ---- stochastic pick (gpt2/sample.py:21-36 with sample=True; models.py:45-60 with config.stochastic) --------------------------------------
 // The rule, per row r at step s (numpy mirror: synth.gpt2_sample_uniform + tests/test_gpt2_sampling.py):
@@ -941,100 +935,109 @@ __global__ __launch_bounds__(256) void gpt2_sample_kernel(const float* logits, c
 }
 bool gpt2_sample_supported(int V) { return V > 0 && V <= 32 * GS_NBMAX; }
 // generic form: sampler over full logits rows [rows][V]
-void launch_gpt2_sample(const float* logits, int rows, int V, const int* sp, int* out, int* state, hipStream_t st) {
-    hipLaunchKernelGGL((gpt2_sample_kernel<false, false>), dim3(rows), dim3(256), 0, st, logits, (const float*)nullptr, (V + 31) / 32, V, sp, out,
-                       state, (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, (float*)nullptr);
+void launch_gpt2_sample(const float* logits, int rows, int V, const int* sp, int* out, int* state, const LaunchTo& to) {
+    launch_kernel(to, "gpt2_sample_kernel<false,false>", gpt2_sample_kernel<false, false>, dim3(rows), dim3(256), 0, logits, nullptr, (V + 31) / 32, V, sp,
+                  out, state, nullptr, nullptr, 0, nullptr, nullptr);
 }
-// the vocabulary projection writing its logits as well as its pairs, then the sampler from the pairs; tail: + the fused pick / embed /
-// advance tail of launch_gpt2_head_tail (wte / wpe / x / stats_out; D <= 1024), else the token goes to gen[step][row].  false: not covered.
-bool launch_gpt2_head_sample(const float* A, const float* W, int M, int N, int K, int lda, const float* stats_in, const float* lng, const float* lnb,
-                             float* logits, float* pairs, const int* sp, int* gen, int* state, bool tail, const float* wte, const float* wpe, float* x,
-                             float* stats_out, hipStream_t st) {
-    if (!gpt2_head_supported(M, N, K, lda) || !pairs || !logits || !gpt2_sample_supported(N) || (tail && K > 1024)) return false;
-    const int NB = (N + 31) / 32;
-    int* pi = (int*)(pairs + (size_t)M * NB);
-    hipLaunchKernelGGL(gpt2_head_kernel, dim3((NB + HD_NW - 1) / HD_NW), dim3(64 * HD_NW), 0, st, A, W, M, N, K, lda, stats_in, lng, lnb, logits, pairs, pi, NB);
-    if (tail)
-        hipLaunchKernelGGL((gpt2_sample_kernel<true, true>), dim3(M), dim3(256), 0, st, logits, pairs, NB, N, sp, gen, state, wte, wpe, K, x, stats_out);
-    else
-        hipLaunchKernelGGL((gpt2_sample_kernel<true, false>), dim3(M), dim3(256), 0, st, logits, pairs, NB, N, sp, gen, state, wte, wpe, K, x, stats_out);
-    return true;
+// The vocabulary head: gpt2_head_kernel (pairs always, logits where o.logits is given) and the pick behind it.  A tail (the pick also embeds
+// the next token, leaves its LayerNorm statistics and advances the state) needs K <= 1024; a sampling pick reads the stored logits.
+Gpt2Head choose_gpt2_head(int M, int N, int K, int lda, Gpt2Pick pick, bool logits_stored) {
+    Gpt2Head h;
+    h.pick = pick;
+    if (!gpt2_head_supported(M, N, K, lda) || (h.tail() && K > 1024) || (h.sample() && !(logits_stored && gpt2_sample_supported(N)))) return Gpt2Head();
+    static const char* const picks[] = {"argmax_pairs_kernel", "gpt2_pick_embed_kernel", "gpt2_sample_kernel<true,false>", "gpt2_sample_kernel<true,true>"};
+    h.ok = true;
+    h.M = M; h.N = N; h.K = K; h.lda = lda; h.NB = (N + 31) / 32;
+    h.grid = dim3((h.NB + HD_NW - 1) / HD_NW); h.block = dim3(64 * HD_NW);
+    h.pick_grid = dim3(M); h.pick_block = dim3(256);
+    h.name = "gpt2_head_kernel"; h.pick_name = picks[pick];
+    return h;
+}
+// o.pairs: scratch of 2 * M * ceil(N / 32) words.  The token goes to gen[state ? state[1] : 0][row]; a tail writes x / stats_out and advances state.
+void launch_gpt2_head(const Gpt2HeadOperands& o, const Gpt2Head& h, const LaunchTo& to) {
+    int* pi = (int*)(o.pairs + (size_t)h.M * h.NB);
+    launch_kernel(to, h.name, gpt2_head_kernel, h.grid, h.block, 0, o.A, o.W, h.M, h.N, h.K, h.lda, o.stats_in, o.lng, o.lnb, o.logits, o.pairs, pi, h.NB);
+    switch (h.pick) {
+        case GPT2_PICK_ARGMAX:
+            launch_kernel(to, h.pick_name, argmax_pairs_kernel, h.pick_grid, h.pick_block, 0, o.pairs, pi, h.NB, o.gen, o.state);
+            break;
+        case GPT2_PICK_ARGMAX_TAIL:
+            launch_kernel(to, h.pick_name, gpt2_pick_embed_kernel, h.pick_grid, h.pick_block, 0, o.pairs, pi, h.NB, o.gen, o.state, h.M, o.wte, o.wpe, h.K, o.x, o.stats_out);
+            break;
+        case GPT2_PICK_SAMPLE:
+            launch_kernel(to, h.pick_name, gpt2_sample_kernel<true, false>, h.pick_grid, h.pick_block, 0, o.logits, o.pairs, h.NB, h.N, o.sp, o.gen, o.state, o.wte,
+                          o.wpe, h.K, o.x, o.stats_out);
+            break;
+        case GPT2_PICK_SAMPLE_TAIL:
+            launch_kernel(to, h.pick_name, gpt2_sample_kernel<true, true>, h.pick_grid, h.pick_block, 0, o.logits, o.pairs, h.NB, h.N, o.sp, o.gen, o.state, o.wte,
+                          o.wpe, h.K, o.x, o.stats_out);
+            break;
+    }
 }
 
-// A single-token-step product of the fused step (engine.cpp): launch_gemm_f32's split policy, but the caller finishes the slices — returns
-// the global split S: S == 1: bias / mode were applied by the kernel; S > 1: raw sums are in `part` (splitk_reduce_kernel via
-// launch_gpt2_reduce, or gpt2_finalize_kernel for the residual products).  stats != nullptr: LayerNorm fused on the activation operand
-// (K <= 1024).  Returns 0 when the shape does not fit (caller: unfused path).
+// A single-token-step product in the weight-streaming form: the choice of its split, made before anything is launched.  The caller finishes
+// the slices — S == 1: bias / mode are applied by the kernel; S > 1: raw sums go to `part` (splitk_reduce_kernel via launch_gpt2_reduce, or
+// gpt2_finalize_kernel for the residual products).  ln_fused: LayerNorm on the activation operand (K <= 1024).  part_elems: the split-K
+// scratch the caller holds (0: never split).  n_cu: the CUs one round of workgroups is weighed against.  cand_only: launch_gemm_f32's
+// policy, the candidate walk alone.  An empty value: the shape does not fit (caller: unfused path).
 bool gemm_f32_step_supported(int M, int K, int lda, bool ln_fused) {
     return M <= 64 && K % GS_KC == 0 && lda % 4 == 0 && !(ln_fused && K > 1024);
 }
-int launch_gemm_f32_step(const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int lda, int ldo, int mode,
-                         hipStream_t st, float* part, size_t part_elems, const float* stats, const float* lng, const float* lnb) {
-    if (!gemm_f32_step_supported(M, K, lda, stats != nullptr)) return 0;
+StepGemm choose_gemm_f32_step(int M, int N, int K, int lda, bool ln_fused, size_t part_elems, int n_cu, bool cand_only) {
+    if (!gemm_f32_step_supported(M, K, lda, ln_fused)) return StepGemm();
     const int nb = (N + 31) / 32;
     // K = C chunks of 64 = S global slices x NK parts inside a workgroup (one chunk per wave).  Of the factorizations with NK in
     // {1, 2, 4, 6} take the one with the most workgroups that still fit the chip in ONE round (nb * S <= CUs: 288 workgroups on 256 CUs
     // ran the MLP products at 14 us against 9.7 us for the 216 of the qkv product), fewest slices among equals; a product too small to
     // fill the CUs either way takes the most slices its scratch allows.
-    const int C = K / GS_KC, n_cu = glass_cu_count();
+    const int C = K / GS_KC;
     int S = 0, NK = 1;
-    if (nb < 1024) {
+    if (nb < 1024 && !cand_only) {
         static const int nks[] = {6, 4, 2, 1};          // (8 parts = 1024 threads = a 128-VGPR budget: spills)
         int best_wg = -1;
         for (int nk : nks) {
             if (C % nk != 0) continue;
             const int sl = C / nk;
-            if (sl > 1 && (!part || (size_t)sl * M * N > part_elems || sl > 16)) continue;
+            if (sl > 1 && ((size_t)sl * M * N > part_elems || sl > 16)) continue;
             const int wg = nb * sl;
             const bool fits = wg <= n_cu;
             const int score = fits ? wg : -wg;              // prefer fitting grids, then the larger one; non-fitting: the smaller
             if (S == 0 || score > best_wg) { best_wg = score; S = sl; NK = nk; }
         }
     }
-    if (S == 0) {      // the vocabulary projection (never split globally) and shapes the rule above does not cover
-        S = 1; NK = 1;
+    if (S == 0) {      // the vocabulary projection (never split globally) and shapes the rule above does not cover: global K split S
+        S = 1; NK = 1; // (small: the partial sums are traffic) x NK parts so that a wave's share is one or two 64-deep chunks
         static const int cand[] = {1, 2, 3, 4, 6, 8, 12, 16};
         for (int c : cand) {
-            if (K % (c * GS_KC) != 0 || (c > 1 && (!part || (size_t)c * M * N > part_elems || nb >= 1024))) continue;
+            if (K % (c * GS_KC) != 0 || (c > 1 && ((size_t)c * M * N > part_elems || nb >= 1024))) continue;
             S = c;
             const int ks = K / c;
             NK = ks % (4 * GS_KC) == 0 ? 4 : (ks % (2 * GS_KC) == 0 ? 2 : 1);
             if (nb * c >= 200 && ks / NK <= 2 * GS_KC) break;
         }
     }
-    switch (NK) {
-        case 6: launch_stream_inst<6>(A, W, bias, out, M, N, K, lda, ldo, mode, st, part, S, stats, lng, lnb); break;
-        case 4: launch_stream_inst<4>(A, W, bias, out, M, N, K, lda, ldo, mode, st, part, S, stats, lng, lnb); break;
-        case 2: launch_stream_inst<2>(A, W, bias, out, M, N, K, lda, ldo, mode, st, part, S, stats, lng, lnb); break;
-        default: launch_stream_inst<1>(A, W, bias, out, M, N, K, lda, ldo, mode, st, part, S, stats, lng, lnb); break;
-    }
-    return S;
+    StepGemm c;
+    c.S = S; c.NK = NK; c.LN = ln_fused; c.ONE = K / S / NK == GS_KC;
+    c.M = M; c.N = N; c.K = K; c.lda = lda;
+    c.grid = dim3(nb, S); c.block = dim3(128 * NK);
+    c.name = stream_inst(NK, c.LN, c.ONE).name;
+    return c;
 }
-void launch_gpt2_reduce(const float* part, int S, const float* bias, float* out, int M, int N, int ldo, int mode, hipStream_t st) {
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long long)M * N + 255) / 256)), dim3(256), 0, st, part, S, bias, out, M, N, ldo, mode);
+// o.stats: the LayerNorm-fused operand's row statistics [M][2]
+void launch_gemm_f32_step(const StepGemmOperands& o, const StepGemm& c, const LaunchTo& to) {
+    launch_kernel(to, c.name, stream_inst(c.NK, c.LN, c.ONE).kernel, c.grid, c.block, 0, o.A, o.W, o.bias, o.out, c.M, c.N, c.K, c.lda, o.ldo, o.mode, o.part,
+                  c.K / c.S, o.stats, o.lng, o.lnb);
+}
+void launch_gpt2_reduce(const float* part, int S, const float* bias, float* out, int M, int N, int ldo, int mode, const LaunchTo& to) {
+    launch_kernel(to, "splitk_reduce_kernel", splitk_reduce_kernel, dim3((unsigned)(((long long)M * N + 255) / 256)), dim3(256), 0, part, S, bias, out, M, N, ldo, mode);
 }
 // `part`: scratch for split-K partial sums (nullable = never split); sized by the caller for GPT2_SPLITK_MAX slices of M x N.
 void launch_gemm_f32(const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int lda, int ldo,
-                     int mode, hipStream_t st, float* part, size_t part_elems, bool prefill) {
-    if (!prefill && M <= 64 && K % GS_KC == 0 && lda % 4 == 0) {
-        // a workgroup per 32 weight rows; global K split S (small: the partial sums are traffic) x NK K parts inside the workgroup so
-        // that a wave's share is one or two 64-deep chunks; the vocabulary projection (1571 workgroups) is not split globally
-        const int nb = (N + 31) / 32;
-        int S = 1, NK = 1;
-        static const int cand[] = {1, 2, 3, 4, 6, 8, 12, 16};
-        for (int c : cand) {
-            if (K % (c * GS_KC) != 0 || (c > 1 && (!part || (size_t)c * M * N > part_elems || nb >= 1024))) continue;
-            S = c;
-            const int ks = K / c;
-            NK = ks % (4 * GS_KC) == 0 ? 4 : (ks % (2 * GS_KC) == 0 ? 2 : 1);
-            if (nb * c >= 200 && ks / NK <= 2 * GS_KC) break;
-        }
-        if (NK == 4) launch_stream_inst<4>(A, W, bias, out, M, N, K, lda, ldo, mode, st, part, S);
-        else if (NK == 2) launch_stream_inst<2>(A, W, bias, out, M, N, K, lda, ldo, mode, st, part, S);
-        else launch_stream_inst<1>(A, W, bias, out, M, N, K, lda, ldo, mode, st, part, S);
-        if (S > 1)
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long long)M * N + 255) / 256)), dim3(256), 0, st, part, S, bias, out,
-                               M, N, ldo, mode);
+                     int mode, const LaunchTo& to, float* part, size_t part_elems, bool prefill) {
+    // a workgroup per 32 weight rows, as the fused step's products but with the candidate walk's split (n_cu is not asked)
+    if (const StepGemm c = prefill ? StepGemm() : choose_gemm_f32_step(M, N, K, lda, false, part ? part_elems : 0, 0, true)) {
+        launch_gemm_f32_step({A, W, bias, out, ldo, mode, part}, c, to);
+        if (c.S > 1) launch_gpt2_reduce(part, c.S, bias, out, M, N, ldo, mode, to);
         return;
     }
     if (!prefill && M <= 64) {
@@ -1046,17 +1049,15 @@ void launch_gemm_f32(const float* A, const float* W, const float* bias, float* o
             while (tiles * S < 192 && S < 16 && K / (2 * S) >= 2 * F32_BK && (size_t)(2 * S) * M * N <= part_elems) S *= 2;
         }
         dim3 g((M + 63) / 64, tiles, S);
-        hipLaunchKernelGGL((gemm_f32_kernel<64, 64>), g, dim3(256), 0, st, A, W, bias, out, M, N, K, lda, ldo, mode, part);
-        if (S > 1)
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long long)M * N + 255) / 256)), dim3(256), 0, st, part, S, bias, out,
-                               M, N, ldo, mode);
+        launch_kernel(to, "gemm_f32_kernel<64,64>", gemm_f32_kernel<64, 64>, g, dim3(256), 0, A, W, bias, out, M, N, K, lda, ldo, mode, part);
+        if (S > 1) launch_gpt2_reduce(part, S, bias, out, M, N, ldo, mode, to);
     } else {
         // prefill: 64 x 64 tiles for every product.  Measured per shape over the whole decode (M = 64 x 23 rows): 128 x 128
         // everywhere 30.4 ms, 128 x 64 28.3, the shape whose grid quantises best on the CUs 28.2, 64 x 64 27.8 — a 64 x 64 workgroup is 17 KB
         // of LDS and 32 VGPRs, so a CU holds many of them and their barriers / LDS round trips overlap; the larger tiles run one
         // workgroup (one wave per SIMD) per CU.  Every shape adds an element's k terms in the same order: the choice never changes a value.
         const dim3 g((M + 63) / 64, (N + 63) / 64, 1);
-        hipLaunchKernelGGL((gemm_f32_kernel<64, 64>), g, dim3(256), 0, st, A, W, bias, out, M, N, K, lda, ldo, mode, part);
+        launch_kernel(to, "gemm_f32_kernel<64,64>", gemm_f32_kernel<64, 64>, g, dim3(256), 0, A, W, bias, out, M, N, K, lda, ldo, mode, part);
     }
 }
 
@@ -1127,12 +1128,12 @@ __global__ __launch_bounds__(256) void gpt2_attention_kernel(const float* qkv, f
 // positions, a single-token step (nd == 1) any history the engine accepts (ns <= 256: 134 KB).
 size_t gpt2_attention_lds_bytes(int nd, int ns) { return ((size_t)nd * 65 + (size_t)2 * ns * 65 + (size_t)nd * (ns + 1)) * sizeof(float); }
 void launch_gpt2_attention(const float* qkv, float* kc, float* vc, int P, int nd, int past, int Tmax, int heads,
-                           float* out, hipStream_t st, const int* past_dev) {
+                           float* out, const LaunchTo& to, const int* past_dev) {
     const int ns = past_dev ? Tmax : past + nd;      // graph replay: LDS sized for the longest history
     const size_t lds = gpt2_attention_lds_bytes(nd, ns);
     static DevOnce once;
-    once.run([&] { (void)hipFuncSetAttribute((const void*)gpt2_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GPT2_ATTENTION_LDS_MAX); });
-    hipLaunchKernelGGL(gpt2_attention_kernel, dim3(P * heads), dim3(256), lds, st, qkv, kc, vc, nd, past, Tmax, heads, out, past_dev);
+    if (!to.list) once.run([&] { (void)hipFuncSetAttribute((const void*)gpt2_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GPT2_ATTENTION_LDS_MAX); });
+    launch_kernel(to, "gpt2_attention_kernel", gpt2_attention_kernel, dim3(P * heads), dim3(256), lds, qkv, kc, vc, nd, past, Tmax, heads, out, past_dev);
 }
 
 // Single-token step (nd = 1, history <= 64 positions): ONE WAVE per (sequence, head), and the split-K slices of the qkv product are
@@ -1253,8 +1254,8 @@ __global__ __launch_bounds__(256) void gpt2_attention_step_kernel(const float* q
     out[(long long)seq * D + h * 64 + lane] = a;
 }
 void launch_gpt2_attention_step(const float* qkv, const float* part, int S, const float* bias, float* kc, float* vc, int P, int Tmax, int heads,
-                                float* out, hipStream_t st, const int* past_dev) {
-    hipLaunchKernelGGL(gpt2_attention_step_kernel, dim3((P * heads + 3) / 4), dim3(256), 0, st, qkv, part, S, bias, kc, vc, P, Tmax, heads, out, past_dev);
+                                float* out, const LaunchTo& to, const int* past_dev) {
+    launch_kernel(to, "gpt2_attention_step_kernel", gpt2_attention_step_kernel, dim3((P * heads + 3) / 4), dim3(256), 0, qkv, part, S, bias, kc, vc, P, Tmax, heads, out, past_dev);
 }
 
 // ---- greedy pick (sample.py:28-34 with sample=False): arg-max of softmax(top_k(logits / T)) == arg-max of the
@@ -1316,12 +1317,12 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* logits, int N,
     if (threadIdx.x == 0) out[(step_dev ? (long long)step_dev[1] * gridDim.x : 0) + blockIdx.x] = bi[0];
 }
 // scratch: rows * ARGMAX_SEG floats + as many ints (nullptr: the one-stage kernel)
-void launch_argmax(const float* logits, int rows, int N, int* out, hipStream_t st, const int* step_dev, float* scratch) {
+void launch_argmax(const float* logits, int rows, int N, int* out, const LaunchTo& to, const int* step_dev, float* scratch) {
     if (scratch && N >= 8192) {
         int* pi = (int*)(scratch + (size_t)rows * ARGMAX_SEG);
-        hipLaunchKernelGGL(argmax_seg_kernel, dim3(rows * ARGMAX_SEG), dim3(256), 0, st, logits, N, scratch, pi);
-        hipLaunchKernelGGL(argmax_final_kernel, dim3(rows), dim3(64), 0, st, scratch, pi, out, step_dev);
+        launch_kernel(to, "argmax_seg_kernel", argmax_seg_kernel, dim3(rows * ARGMAX_SEG), dim3(256), 0, logits, N, scratch, pi);
+        launch_kernel(to, "argmax_final_kernel", argmax_final_kernel, dim3(rows), dim3(64), 0, scratch, pi, out, step_dev);
         return;
     }
-    hipLaunchKernelGGL(argmax_kernel, dim3(rows), dim3(256), 0, st, logits, N, out, step_dev);
+    launch_kernel(to, "argmax_kernel", argmax_kernel, dim3(rows), dim3(256), 0, logits, N, out, step_dev);
 }

@@ -63,13 +63,148 @@ void gpt2_work_free(glass_engine* e) {
     w = glass_engine::Gpt2Work();
 }
 
+// What a token step of this geometry launches, decided from the launchers' own choosers before anything runs.  Fused step (round 3):
+// LayerNorm applied on the activation operand of the next product from row statistics, split-K slices of the residual products finished
+// together with the residual add and the next statistics.  Round 4: the attention output product and the MLP's first product in the
+// complete-output form where the width allows — no slices, so no finishing launch behind them: 6 launches per layer instead of 8 (the qkv
+// product and the MLP's second one stay split: complete, they were 12-14 us against 9.5 and 34 against 12 + 5) — and the pick also writes
+// the NEXT step's embedding + first LayerNorm statistics and advances the state: a step starts at layer 0's qkv product.  A product
+// a chooser refuses leaves the step unfused: that path takes every shape.
+Gpt2StepPlan plan_gpt2_step(int P, int D, int V, int Tmax, bool sample, size_t part_elems, int n_cu) {
+    Gpt2StepPlan pl;
+    pl.qkv = choose_gemm_f32_step(P, 3 * D, D, D, true, part_elems, n_cu);
+    pl.pr = choose_gemm_f32_step(P, D, 4 * D, 4 * D, false, part_elems, n_cu);
+    if (D % 32 == 0 && D / 32 <= 24) {       // x += att @ Wo + b with the row partials of LayerNorm 2 in the epilogue; hid = gelu(LN2(x) @ Wfc + b)
+        pl.o = choose_gemm_f32_rowblk(P, D, D, D, false, 0, true);
+        pl.fc = choose_gemm_f32_rowblk(P, 4 * D, D, D, true, D / 32, false);
+    }
+    pl.rowblk = pl.o && pl.fc;
+    if (!pl.rowblk) {
+        pl.o = choose_gemm_f32_step(P, D, D, D, false, part_elems, n_cu);
+        pl.fc = choose_gemm_f32_step(P, 4 * D, D, D, true, part_elems, n_cu);
+    }
+    pl.head = choose_gpt2_head(P, V, D, D, sample ? GPT2_PICK_SAMPLE_TAIL : GPT2_PICK_ARGMAX_TAIL, sample);
+    if (!pl.head) pl.head = choose_gpt2_head(P, V, D, D, sample ? GPT2_PICK_SAMPLE : GPT2_PICK_ARGMAX, sample);
+    // ln_f fused; the real vocabulary (1571 column blocks) is never split, a small one may be
+    if (!pl.head) pl.logits = choose_gemm_f32_step(P, V, D, D, true, part_elems, n_cu);
+    pl.fused = pl.qkv && pl.o && pl.fc && pl.pr && (pl.head || pl.logits);
+    pl.att_step = pl.fused && Tmax <= 64;
+    return pl;
+}
+
+static float* layer_cache(float* cache, const glass_engine::Gpt2Work& w, int l, int D) { return cache + (size_t)l * w.P * (w.nctx + w.length) * D; }
+
+// One unfused transformer pass over the nd new positions per sequence that lie embedded in w.x, and the pick -> d_gen[step][P].
+// state == nullptr: the prefill (past = 0); else a single-token step whose past length / step index are read from device memory.
+static void gpt2_layers_unfused(const glass_engine* e, const glass_engine::Gpt2Work& w, int nd, const int* state, const LaunchTo& to) {
+    const int P = w.P, D = e->g_dim, V = e->g_vocab, heads = D / 64, Tmax = w.nctx + w.length, M = P * nd;
+    for (size_t l = 0; l < e->gblk.size(); ++l) {
+        const auto& b = e->gblk[l];
+        launch_layernorm(w.x, D, M, D, b.ln1_g, b.ln1_b, nullptr, w.ln, to);
+        launch_gemm_f32(w.ln, b.w_qkv, b.b_qkv, w.qkv, M, 3 * D, D, D, 3 * D, 0, to, w.part, w.part_elems, nd > 1);
+        launch_gpt2_attention(w.qkv, layer_cache(w.kc, w, l, D), layer_cache(w.vc, w, l, D), P, nd, 0, Tmax, heads, w.att, to, state);
+        launch_gemm_f32(w.att, b.w_o, b.b_o, w.x, M, D, D, D, D, 2, to, w.part, w.part_elems, nd > 1);
+        launch_layernorm(w.x, D, M, D, b.ln2_g, b.ln2_b, nullptr, w.ln, to);
+        launch_gemm_f32(w.ln, b.w_fc, b.b_fc, w.hid, M, 4 * D, D, D, 4 * D, 1, to, w.part, w.part_elems, nd > 1);
+        launch_gemm_f32(w.hid, b.w_pr, b.b_pr, w.x, M, D, 4 * D, 4 * D, D, 2, to, w.part, w.part_elems, nd > 1);
+    }
+    // ln_f on the last position of each sequence, tied lm_head, pick
+    launch_layernorm(w.x + (size_t)(nd - 1) * D, (long long)nd * D, P, D, e->g_lnf_g, e->g_lnf_b, nullptr, w.last, to);
+    launch_gemm_f32(w.last, e->g_wte, nullptr, w.logits, P, V, D, D, V, 0, to, w.part, w.part_elems);
+    if (w.sample) launch_gpt2_sample(w.logits, P, V, w.d_samp, w.d_gen, w.d_state, to);
+    else launch_argmax(w.logits, P, V, w.d_gen, to, w.d_state, w.stats + 2 * P);
+    launch_gpt2_advance(w.d_state, to);
+}
+
+static void gpt2_prefill(const glass_engine* e, const glass_engine::Gpt2Work& w, int nd, const LaunchTo& to) {
+    launch_gpt2_embed(w.d_tok, e->g_wte, e->g_wpe, w.P * nd, nd, 0, e->g_dim, w.x, to);
+    gpt2_layers_unfused(e, w, nd, nullptr, to);
+}
+
+static void gpt2_step_unfused(const glass_engine* e, const glass_engine::Gpt2Work& w, const LaunchTo& to) {
+    launch_gpt2_embed_step(w.d_gen, w.d_state, w.P, e->g_wte, e->g_wpe, e->g_dim, w.x, to);
+    gpt2_layers_unfused(e, w, 1, w.d_state, to);
+}
+
+// The fused token step: w.plan, launched.  Every product was chosen by plan_gpt2_step: nothing here can refuse.
+static void gpt2_step_fused(const glass_engine* e, const glass_engine::Gpt2Work& w, const LaunchTo& to) {
+    const Gpt2StepPlan& pl = w.plan;
+    const int P = w.P, D = e->g_dim, V = e->g_vocab, heads = D / 64, Tmax = w.nctx + w.length;
+    auto slices = [&](const StepGemm& c) { return c.S > 1 ? w.part : nullptr; };
+    // (a tail left this step's embedding and the first layer's LayerNorm statistics; the first step's come from one eager launch after the prefill)
+    if (!pl.head.tail()) launch_gpt2_embed_step(w.d_gen, w.d_state, P, e->g_wte, e->g_wpe, D, w.x, to, w.stats);
+    for (size_t l = 0; l < e->gblk.size(); ++l) {
+        const auto& b = e->gblk[l];
+        float *kcl = layer_cache(w.kc, w, l, D), *vcl = layer_cache(w.vc, w, l, D);
+        launch_gemm_f32_step({w.x, b.w_qkv, b.b_qkv, w.qkv, 3 * D, 0, w.part, w.stats, b.ln1_g, b.ln1_b}, pl.qkv, to);
+        if (pl.att_step) {
+            launch_gpt2_attention_step(w.qkv, slices(pl.qkv), pl.qkv.S, b.b_qkv, kcl, vcl, P, Tmax, heads, w.att, to, w.d_state);
+        } else {
+            if (pl.qkv.S > 1) launch_gpt2_reduce(w.part, pl.qkv.S, b.b_qkv, w.qkv, P, 3 * D, 3 * D, 0, to);
+            launch_gpt2_attention(w.qkv, kcl, vcl, P, 1, 0, Tmax, heads, w.att, to, w.d_state);
+        }
+        if (pl.rowblk) {
+            launch_gemm_f32_rowblk({w.att, b.w_o, b.b_o, w.x, D, 2, nullptr, nullptr, nullptr, nullptr, w.pst}, pl.o, to);
+            launch_gemm_f32_rowblk({w.x, b.w_fc, b.b_fc, w.hid, 4 * D, 1, nullptr, w.pst, b.ln2_g, b.ln2_b}, pl.fc, to);
+        } else {
+            launch_gemm_f32_step({w.att, b.w_o, b.b_o, w.x, D, 2, w.part}, pl.o, to);
+            launch_gpt2_finalize(slices(pl.o), pl.o.S, b.b_o, w.x, P, D, w.stats, to);        // residual + LayerNorm 2 statistics
+            launch_gemm_f32_step({w.x, b.w_fc, b.b_fc, w.hid, 4 * D, 1, w.part, w.stats, b.ln2_g, b.ln2_b}, pl.fc, to);
+            if (pl.fc.S > 1) launch_gpt2_reduce(w.part, pl.fc.S, b.b_fc, w.hid, P, 4 * D, 4 * D, 1, to);
+        }
+        launch_gemm_f32_step({w.hid, b.w_pr, b.b_pr, w.x, D, 2, w.part}, pl.pr, to);
+        launch_gpt2_finalize(slices(pl.pr), pl.pr.S, b.b_pr, w.x, P, D, w.stats, to);         // residual + next LayerNorm's statistics
+    }
+    if (pl.head) {      // a sampling pick reads the logits, so the head stores them too; a tail writes the next step's x / statistics
+        launch_gpt2_head({w.x, e->g_wte, w.stats, e->g_lnf_g, e->g_lnf_b, w.sample ? w.logits : nullptr, w.pairs, w.d_samp, w.d_gen, w.d_state, e->g_wte,
+                          e->g_wpe, w.x, w.stats}, pl.head, to);
+        if (pl.head.tail()) return;
+    } else {
+        launch_gemm_f32_step({w.x, e->g_wte, nullptr, w.logits, V, 0, w.part, w.stats, e->g_lnf_g, e->g_lnf_b}, pl.logits, to);
+        if (pl.logits.S > 1) launch_gpt2_reduce(w.part, pl.logits.S, nullptr, w.logits, P, V, V, 0, to);
+        if (w.sample) launch_gpt2_sample(w.logits, P, V, w.d_samp, w.d_gen, w.d_state, to);
+        else launch_argmax(w.logits, P, V, w.d_gen, to, w.d_state, w.stats + 2 * P);
+    }
+    launch_gpt2_advance(w.d_state, to);
+}
+
+static void gpt2_step(const glass_engine* e, const glass_engine::Gpt2Work& w, const LaunchTo& to) {
+    if (w.plan.fused) gpt2_step_fused(e, w, to);
+    else gpt2_step_unfused(e, w, to);
+}
+
+// Host only: the launches of one token step, one line each in launch order — the step functions above, run into a text instead of a stream
+// over a workspace of placeholder pointers that nothing follows.
+extern "C" int glass_host_gpt2_step_plan(int32_t P, int32_t D, int32_t V, int32_t n_layer, int32_t Tmax, int32_t sample, int32_t n_cu, char* out,
+                                         int32_t cap) {
+    REQUIRE(out && cap > 0, GLASS_ERR_ARG, "bad argument");
+    REQUIRE(P > 0 && P <= 64 && D > 0 && D % 64 == 0 && V > 0 && n_layer > 0 && Tmax >= 2 && Tmax <= 256 && n_cu > 0, GLASS_ERR_ARG,
+            "bad geometry (1 <= P <= 64 rows of a group, D % 64 == 0, 2 <= Tmax <= 256)");
+    static float nowhere;
+    static int nowhere_i;
+    glass_engine e;
+    e.g_dim = D; e.g_vocab = V;
+    e.gblk.assign(n_layer, glass_engine::Gpt2Block());
+    auto& w = e.gwork;
+    w.P = P; w.nctx = 1; w.length = Tmax - 1; w.sample = sample ? 1 : 0;
+    w.part_elems = (size_t)16 * P * 4 * D;
+    w.d_tok = w.d_gen = w.d_state = w.d_samp = &nowhere_i;
+    w.x = w.ln = w.qkv = w.att = w.hid = w.last = w.logits = w.kc = w.vc = w.part = w.stats = w.pairs = w.pst = &nowhere;
+    w.plan = plan_gpt2_step(P, D, V, Tmax, sample != 0, w.part_elems, n_cu);
+    std::string text;
+    gpt2_step(&e, w, LaunchTo(&text));
+    REQUIRE(text.size() < (size_t)cap, GLASS_ERR_ARG, "the plan needs " + std::to_string(text.size() + 1) + " bytes, more than the caller's " + std::to_string(cap));
+    memcpy(out, text.c_str(), text.size() + 1);
+    return GLASS_OK;
+}
+
 // samp: the sampler's GPT2_SP_* words (host), nullptr = greedy
 static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P, int32_t nctx, int32_t length, int32_t* out_tokens,
                              const int32_t* samp) {
     REQUIRE(e && context && out_tokens && P > 0 && nctx > 0 && length > 0, GLASS_ERR_ARG, "bad argument");
     REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
     REQUIRE(e->g_wte != nullptr, GLASS_ERR_STATE, "GPT-2 weights were not loaded (gpt2.transformer.*)");
-    const int D = e->g_dim, V = e->g_vocab, heads = D / 64, Tmax = nctx + length;
+    const int D = e->g_dim, V = e->g_vocab, Tmax = nctx + length;
     REQUIRE(Tmax <= e->g_npos && Tmax <= 256, GLASS_ERR_ARG, "sequence longer than the position table / 256");
     // the prefill attention holds a sequence's keys, values and its whole score matrix in LDS: 4 * (n^2 + 196 n) bytes of the 160 KB
     REQUIRE(gpt2_attention_lds_bytes(nctx, nctx) <= GPT2_ATTENTION_LDS_MAX, GLASS_ERR_ARG,
@@ -119,109 +254,17 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
         if (w.exec) { hipGraphExecDestroy(w.exec); w.exec = nullptr; }
         if (w.graph) { hipGraphDestroy(w.graph); w.graph = nullptr; }
         w.sample = sample;
+        w.plan = plan_gpt2_step(P, D, V, Tmax, sample != 0, w.part_elems, glass_cu_count());
     }
-    // one transformer pass over `nd` new positions per sequence; step_state != nullptr: single-token step whose past length /
-    // step index are read from device memory (the form that is captured into a hipGraph and replayed)
-    // single-token steps, fused form (round 3): LayerNorm applied on the activation operand of the next
-    // product from row statistics, products with complete outputs (no split-K reduce launch) except the MLP's second one, whose
-    // split-K slices of the residual products finished together with the residual add and the next statistics: 9 launches per layer
-    // instead of 11 (complete-output products — 72 / 24 / 96 workgroups walking three chunks each — were 21 us against 9 + 4: dropped)
-    // (the launcher's own shape conditions, asked through the launcher's predicate: a product it refuses returns 0 slices and nothing written)
-    const bool fuse_ok = gemm_f32_step_supported(P, D, D, true) && gemm_f32_step_supported(P, 4 * D, 4 * D, false);
-    bool step_refused = false;
-    // fused step tail (round 4): the pick also writes the NEXT step's embedding + first LayerNorm statistics and advances the state — a step
-    // starts at layer 0's qkv product; the first step's embedding is one eager launch after the prefill.
-    const bool tail_fused = fuse_ok && D <= 1024 && gpt2_head_supported(P, V, D, D);
-    auto pass = [&](int nd, int past, const int* step_state) {
-        const int M = P * nd;
-        // round 4 (gpt2.hip): the attention output product and the MLP's first product in the complete-output form — no slices, so no
-        // gpt2_finalize / splitk_reduce launch behind them: 6 launches per layer instead of 8.  (The qkv product and the MLP's second one
-        // stay split: complete, they were 12-14 us against 9.5 and 34 against 12 + 5.)
-        const bool rowblk = step_state && fuse_ok && D % 32 == 0 && D / 32 <= 24 &&
-                            gemm_f32_rowblk_supported(P, D, D, D, false, true) && gemm_f32_rowblk_supported(P, 4 * D, D, D, true, false);
-        if (step_state) { if (!tail_fused) launch_gpt2_embed_step(w.d_gen, step_state, P, e->g_wte, e->g_wpe, D, w.x, st, fuse_ok ? w.stats : nullptr); }
-        else launch_gpt2_embed(w.d_tok, e->g_wte, e->g_wpe, M, nd, past, D, w.x, st);
-        if (step_state && fuse_ok) {      // (the embedding kernel left the first layer's LayerNorm statistics)
-            for (int l = 0; l < nl; ++l) {
-                const auto& b = e->gblk[l];
-                float* kcl = w.kc + (size_t)l * P * Tmax * D;
-                float* vcl = w.vc + (size_t)l * P * Tmax * D;
-                int S = launch_gemm_f32_step(w.x, b.w_qkv, b.b_qkv, w.qkv, P, 3 * D, D, D, 3 * D, 0, st, w.part, w.part_elems, w.stats, b.ln1_g, b.ln1_b);
-                step_refused |= S == 0;
-                if (Tmax <= 64) {      // one wave per (sequence, head); it sums the product's slices itself
-                    launch_gpt2_attention_step(w.qkv, S > 1 ? w.part : nullptr, S, b.b_qkv, kcl, vcl, P, Tmax, heads, w.att, st, step_state);
-                } else {
-                    if (S > 1) launch_gpt2_reduce(w.part, S, b.b_qkv, w.qkv, P, 3 * D, 3 * D, 0, st);
-                    launch_gpt2_attention(w.qkv, kcl, vcl, P, 1, past, Tmax, heads, w.att, st, step_state);
-                }
-                if (rowblk) {       // x += att @ Wo + b (row partials of LayerNorm 2 in the epilogue); hid = gelu(LN2(x) @ Wfc + b)
-                    bool ok = launch_gemm_f32_rowblk(w.att, b.w_o, b.b_o, w.x, P, D, D, D, D, 2, st, nullptr, 0, nullptr, nullptr, w.pst);
-                    ok &= launch_gemm_f32_rowblk(w.x, b.w_fc, b.b_fc, w.hid, P, 4 * D, D, D, 4 * D, 1, st, w.pst, D / 32, b.ln2_g, b.ln2_b, nullptr);
-                    step_refused |= !ok;
-                } else {
-                    S = launch_gemm_f32_step(w.att, b.w_o, b.b_o, w.x, P, D, D, D, D, 2, st, w.part, w.part_elems, nullptr, nullptr, nullptr);
-                    step_refused |= S == 0;
-                    launch_gpt2_finalize(S > 1 ? w.part : nullptr, S, b.b_o, w.x, P, D, w.stats, st);       // residual + LayerNorm 2 statistics
-                    S = launch_gemm_f32_step(w.x, b.w_fc, b.b_fc, w.hid, P, 4 * D, D, D, 4 * D, 1, st, w.part, w.part_elems, w.stats, b.ln2_g, b.ln2_b);
-                    step_refused |= S == 0;
-                    if (S > 1) launch_gpt2_reduce(w.part, S, b.b_fc, w.hid, P, 4 * D, 4 * D, 1, st);
-                }
-                S = launch_gemm_f32_step(w.hid, b.w_pr, b.b_pr, w.x, P, D, 4 * D, 4 * D, D, 2, st, w.part, w.part_elems, nullptr, nullptr, nullptr);
-                step_refused |= S == 0;
-                launch_gpt2_finalize(S > 1 ? w.part : nullptr, S, b.b_pr, w.x, P, D, w.stats, st);      // residual + next LayerNorm's statistics
-            }
-            if (tail_fused) {
-                if (samp)       // the sampling twin: logits written too, the sampler from the pairs, the same embed / advance tail
-                    step_refused |= !launch_gpt2_head_sample(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.logits, w.pairs, w.d_samp,
-                                                             w.d_gen, w.d_state, true, e->g_wte, e->g_wpe, w.x, w.stats, st);
-                else
-                    step_refused |= !launch_gpt2_head_tail(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.pairs, w.d_gen, w.d_state, e->g_wte,
-                                                           e->g_wpe, w.x, w.stats, st);
-                return;
-            }
-            const bool head = samp ? launch_gpt2_head_sample(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, w.logits, w.pairs,
-                                                             w.d_samp, w.d_gen, w.d_state, false, nullptr, nullptr, nullptr, nullptr, st)
-                                   : launch_gpt2_head(w.x, e->g_wte, P, V, D, D, w.stats, e->g_lnf_g, e->g_lnf_b, nullptr, w.pairs, w.d_gen,
-                                                      w.d_state, st);
-            if (!head) {
-                // ln_f fused; the real vocabulary (1571 column blocks) is never split, a small one may be
-                const int S = launch_gemm_f32_step(w.x, e->g_wte, nullptr, w.logits, P, V, D, D, V, 0, st, w.part, w.part_elems, w.stats, e->g_lnf_g, e->g_lnf_b);
-                step_refused |= S == 0;
-                if (S > 1) launch_gpt2_reduce(w.part, S, nullptr, w.logits, P, V, V, 0, st);
-                if (samp) launch_gpt2_sample(w.logits, P, V, w.d_samp, w.d_gen, w.d_state, st);
-                else launch_argmax(w.logits, P, V, w.d_gen, st, w.d_state, w.stats + 2 * P);
-            }
-            launch_gpt2_advance(w.d_state, st);
-            return;
-        }
-        for (int l = 0; l < nl; ++l) {
-            const auto& b = e->gblk[l];
-            float* kcl = w.kc + (size_t)l * P * Tmax * D;
-            float* vcl = w.vc + (size_t)l * P * Tmax * D;
-            launch_layernorm(w.x, D, M, D, b.ln1_g, b.ln1_b, nullptr, w.ln, st);
-            launch_gemm_f32(w.ln, b.w_qkv, b.b_qkv, w.qkv, M, 3 * D, D, D, 3 * D, 0, st, w.part, w.part_elems, nd > 1);
-            launch_gpt2_attention(w.qkv, kcl, vcl, P, nd, past, Tmax, heads, w.att, st, step_state);
-            launch_gemm_f32(w.att, b.w_o, b.b_o, w.x, M, D, D, D, D, 2, st, w.part, w.part_elems, nd > 1);
-            launch_layernorm(w.x, D, M, D, b.ln2_g, b.ln2_b, nullptr, w.ln, st);
-            launch_gemm_f32(w.ln, b.w_fc, b.b_fc, w.hid, M, 4 * D, D, D, 4 * D, 1, st, w.part, w.part_elems, nd > 1);
-            launch_gemm_f32(w.hid, b.w_pr, b.b_pr, w.x, M, D, 4 * D, 4 * D, D, 2, st, w.part, w.part_elems, nd > 1);
-        }
-        // ln_f on the last position of each sequence, tied lm_head, greedy pick -> d_gen[step][P]
-        launch_layernorm(w.x + (size_t)(nd - 1) * D, (long long)nd * D, P, D, e->g_lnf_g, e->g_lnf_b, nullptr, w.last, st);
-        launch_gemm_f32(w.last, e->g_wte, nullptr, w.logits, P, V, D, D, V, 0, st, w.part, w.part_elems);
-        if (samp) launch_gpt2_sample(w.logits, P, V, w.d_samp, w.d_gen, w.d_state, st);
-        else launch_argmax(w.logits, P, V, w.d_gen, st, w.d_state, w.stats + 2 * P);
-        launch_gpt2_advance(w.d_state, st);
-    };
     std::vector<int32_t> gen((size_t)P * length);
     GLASS_HIP(hipEventRecord(e->ev0, st));
     hipMemcpyAsync(w.d_tok, context, rows * sizeof(int), hipMemcpyHostToDevice, st);
     const int state0[3] = {0, 0, 0}, state1[3] = {nctx, 1, 0};
     hipMemcpyAsync(w.d_state, state0, sizeof state0, hipMemcpyHostToDevice, st);
     if (samp) hipMemcpyAsync(w.d_samp, samp, GPT2_SP_WORDS * sizeof(int), hipMemcpyHostToDevice, st);
-    pass(nctx, 0, nullptr);                                 // prefill = step 0 (writes d_gen[0 .. P))
+    gpt2_prefill(e, w, nctx, st);                           // prefill = step 0 (writes d_gen[0 .. P))
     hipMemcpyAsync(w.d_state, state1, sizeof state1, hipMemcpyHostToDevice, st);
-    if (tail_fused && length > 1) launch_gpt2_embed_step(w.d_gen, w.d_state, P, e->g_wte, e->g_wpe, D, w.x, st, w.stats);   // step 1's embedding (later ones: the step tail)
+    if (w.plan.fused && w.plan.head.tail() && length > 1) launch_gpt2_embed_step(w.d_gen, w.d_state, P, e->g_wte, e->g_wpe, D, w.x, st, w.stats);   // step 1's embedding (later ones: the step tail)
     hipError_t err = hipSuccess;
     if (length > 1) {
         // the 29 single-token steps are the same ~190 launches each: capture one step once, replay it (launch latency, not work,
@@ -229,7 +272,7 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
         if (!w.exec) {
             err = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
             if (err == hipSuccess) {
-                pass(1, 0, w.d_state);
+                gpt2_step(e, w, st);
                 err = hipStreamEndCapture(st, &w.graph);
                 if (err == hipSuccess) err = hipGraphInstantiate(&w.exec, w.graph, nullptr, nullptr, 0);
             }
@@ -242,7 +285,7 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
         }
         for (int step = 1; step < length && err == hipSuccess; ++step) {
             if (w.exec) err = hipGraphLaunch(w.exec, st);
-            else pass(1, 0, w.d_state);
+            else gpt2_step(e, w, st);
         }
     }
     if (err == hipSuccess) err = hipEventRecord(e->ev1, st);
@@ -253,11 +296,6 @@ static int gpt2_decode_group(glass_engine* e, const int32_t* context, int32_t P,
         gpt2_work_free(e);
         glass_set_error(std::string("gpt2_decode failed: ") + hipGetErrorString(err));
         return GLASS_ERR_HIP;
-    }
-    if (step_refused) {        // fuse_ok and the launcher disagreed about a shape: buffers were consumed unwritten — never a silent result
-        gpt2_work_free(e);
-        glass_set_error("gpt2_decode: a fused step product refused its shape (launch_gemm_f32_step returned 0)");
-        return GLASS_ERR_STATE;
     }
     (void)hipEventElapsedTime(&w.last_ms, e->ev0, e->ev1);
     e->last_ms = w.last_ms;

@@ -128,7 +128,7 @@ void launch_embed_lnpre(const float* patch_emb, const float* cls, const float* p
 void launch_embed_text(const int* tokens, const float* tok_emb, const float* pos, int n_rows, int ctx, int D, float* x,
                        hipStream_t st);
 void launch_layernorm(const float* x, long long row_stride, int M, int D, const float* g, const float* b,
-                      half_t* out16, float* out32, hipStream_t st);
+                      half_t* out16, float* out32, const LaunchTo& to);
 void launch_layernorm_rows(const float* x, const int* rows, int M, int D, const float* g, const float* b, float* out32, hipStream_t st);
 void launch_attention(const half_t* qkv, int n_img, int L, int heads, int hd, int causal, half_t* out,
                       hipStream_t st);
@@ -164,50 +164,83 @@ struct BgTailParams {
 bool bg_tail_supported(int R, int mid, int cout, int cin, int up, int cpad);
 bool launch_bg_tail(const BgTailParams& p, hipStream_t st);
 // --- GPT-2 (fp32, gpt2.hip) ----------------------------------------------------------
+// Every launcher takes a LaunchTo (common.h): a stream, or a text list that receives the launch's name, grid and block instead.
 void launch_gpt2_embed(const int* tok, const float* wte, const float* wpe, int rows, int L, int pos0, int D, float* x,
-                       hipStream_t st);
+                       const LaunchTo& to);
 // part / part_elems: split-K scratch for the single-token (M <= 64) steps (nullptr = never split)
 // prefill: the rows are P sequences x nd > 1 positions — always the tiled kernels, so that the kernel (and with it the summation order)
 // a sequence's prefill runs on does not depend on how many sequences the launch holds
 void launch_gemm_f32(const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int lda, int ldo,
-                     int mode, hipStream_t st, float* part = nullptr, size_t part_elems = 0, bool prefill = false);
-bool gemm_f32_step_supported(int M, int K, int lda, bool ln_fused);   // launch_gemm_f32_step's shape conditions
-// fused single-token step (round 3): products with LayerNorm on the activation operand / complete outputs, and the residual + statistics pass
-int launch_gemm_f32_step(const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int lda, int ldo, int mode,
-                         hipStream_t st, float* part, size_t part_elems, const float* stats, const float* lng, const float* lnb);
+                     int mode, const LaunchTo& to, float* part = nullptr, size_t part_elems = 0, bool prefill = false);
+// A single-token-step product (M <= 64 rows), decided before it is launched.  The choosers (choose_gemm_f32_step: the weight-streaming
+// form with a global K split S; choose_gemm_f32_rowblk: the complete-output form, a workgroup = 32 rows x 32 columns over the whole K)
+// launch nothing and return the instance's template arguments, its profile name and its grid — or an empty value: refused.  The launchers
+// launch exactly that and cannot refuse.
+struct StepGemm {
+    int S = 0, NK = 1;                // global K split (0: refused), K parts inside a workgroup
+    bool LN = false, ONE = false;
+    int M = 0, N = 0, K = 0, lda = 0, np_in = 0;
+    dim3 grid, block;
+    const char* name = nullptr;
+    explicit operator bool() const { return S > 0; }
+};
+struct StepGemmOperands {
+    const float *A, *W, *bias;
+    float* out;
+    int ldo, mode;                    // 0 plain, 1 GELU-tanh, 2 out +=
+    float* part;                      // streaming form: the slices' raw sums (S > 1)
+    const float *stats, *lng, *lnb;   // LayerNorm fused on A: row statistics [M][2] (streaming form) / row partials [M][np_in][2] (row-block form)
+    float* pst_out;                   // row-block form, nullable: the epilogue's row partials [M][N / 32][2]
+};
+bool gemm_f32_step_supported(int M, int K, int lda, bool ln_fused);   // choose_gemm_f32_step's shape conditions
+StepGemm choose_gemm_f32_step(int M, int N, int K, int lda, bool ln_fused, size_t part_elems, int n_cu, bool cand_only = false);
+void launch_gemm_f32_step(const StepGemmOperands& o, const StepGemm& c, const LaunchTo& to);
+bool gemm_f32_rowblk_supported(int M, int N, int K, int lda, bool ln_fused, bool stats_out);
+StepGemm choose_gemm_f32_rowblk(int M, int N, int K, int lda, bool ln_fused, int np_in, bool stats_out);
+void launch_gemm_f32_rowblk(const StepGemmOperands& o, const StepGemm& c, const LaunchTo& to);
+// vocabulary projection of a single-token step (LayerNorm fused, (max, index) pairs per 32-column block) + the pick behind it; a tail
+// also writes the next step's embedding / first LayerNorm statistics and advances the state (state[2] = ticket counter, zero)
+enum Gpt2Pick { GPT2_PICK_ARGMAX, GPT2_PICK_ARGMAX_TAIL, GPT2_PICK_SAMPLE, GPT2_PICK_SAMPLE_TAIL };
+struct Gpt2Head {
+    bool ok = false;
+    Gpt2Pick pick = GPT2_PICK_ARGMAX;
+    int M = 0, N = 0, K = 0, lda = 0, NB = 0;
+    dim3 grid, block, pick_grid, pick_block;
+    const char *name = nullptr, *pick_name = nullptr;
+    explicit operator bool() const { return ok; }
+    bool tail() const { return pick == GPT2_PICK_ARGMAX_TAIL || pick == GPT2_PICK_SAMPLE_TAIL; }
+    bool sample() const { return pick == GPT2_PICK_SAMPLE || pick == GPT2_PICK_SAMPLE_TAIL; }
+};
+struct Gpt2HeadOperands {
+    const float *A, *W, *stats_in, *lng, *lnb;
+    float *logits, *pairs;            // logits: nullable for the arg-max picks
+    const int* sp;                    // sampling picks: the sampler's words
+    int *gen, *state;
+    const float *wte, *wpe;           // tails
+    float *x, *stats_out;
+};
 bool gpt2_head_supported(int M, int N, int K, int lda);
-// vocabulary projection + pick + the next step's embedding / first LayerNorm statistics + state advance (state[2] = ticket counter, zero)
-bool launch_gpt2_head_tail(const float* A, const float* W, int M, int N, int K, int lda, const float* stats_in, const float* lng, const float* lnb,
-                           float* pairs, int* gen, int* state, const float* wte, const float* wpe, float* x, float* stats_out, hipStream_t st);
-bool launch_gpt2_head(const float* A, const float* W, int M, int N, int K, int lda, const float* stats, const float* lng, const float* lnb,
-                      float* logits, float* pairs, int* out, const int* step_dev, hipStream_t st);
-void launch_gpt2_reduce(const float* part, int S, const float* bias, float* out, int M, int N, int ldo, int mode, hipStream_t st);
-void launch_gpt2_finalize(const float* part, int S, const float* bias, float* x, int M, int D, float* stats, hipStream_t st);
+Gpt2Head choose_gpt2_head(int M, int N, int K, int lda, Gpt2Pick pick, bool logits_stored);
+void launch_gpt2_head(const Gpt2HeadOperands& o, const Gpt2Head& h, const LaunchTo& to);
+void launch_gpt2_reduce(const float* part, int S, const float* bias, float* out, int M, int N, int ldo, int mode, const LaunchTo& to);
+void launch_gpt2_finalize(const float* part, int S, const float* bias, float* x, int M, int D, float* stats, const LaunchTo& to);
 #define GPT2_ATTENTION_LDS_MAX (160 * 1024)
 size_t gpt2_attention_lds_bytes(int nd, int ns);      // dynamic LDS of one launch_gpt2_attention (ns = history + new positions)
 // past_dev / step_dev: device-resident step state {past length, step index} for the captured single-token step
 void launch_gpt2_attention(const float* qkv, float* kc, float* vc, int P, int nd, int past, int Tmax, int heads,
-                           float* out, hipStream_t st, const int* past_dev = nullptr);
+                           float* out, const LaunchTo& to, const int* past_dev = nullptr);
 void launch_gpt2_attention_step(const float* qkv, const float* part, int S, const float* bias, float* kc, float* vc, int P, int Tmax, int heads,
-                                float* out, hipStream_t st, const int* past_dev);
-void launch_argmax(const float* logits, int rows, int N, int* out, hipStream_t st, const int* step_dev = nullptr, float* scratch = nullptr);
-void launch_gpt2_embed_step(const int* gen, const int* state, int P, const float* wte, const float* wpe, int D, float* x, hipStream_t st,
+                                float* out, const LaunchTo& to, const int* past_dev);
+void launch_argmax(const float* logits, int rows, int N, int* out, const LaunchTo& to, const int* step_dev = nullptr, float* scratch = nullptr);
+void launch_gpt2_embed_step(const int* gen, const int* state, int P, const float* wte, const float* wpe, int D, float* x, const LaunchTo& to,
                             float* stats = nullptr, bool partial_fmt = false);
-// complete-output step product: a workgroup = 32 rows x 32 columns over the whole K (gpt2.hip); false = shape not covered, nothing launched
-bool gemm_f32_rowblk_supported(int M, int N, int K, int lda, bool ln_fused, bool stats_out);
-bool launch_gemm_f32_rowblk(const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int lda, int ldo, int mode,
-                            hipStream_t st, const float* pst_in, int np_in, const float* lng, const float* lnb, float* pst_out);
-void launch_gpt2_advance(int* state, hipStream_t st);
+void launch_gpt2_advance(int* state, const LaunchTo& to);
 // stochastic pick (top-k temperature sampling, gpt2.hip): the per-call values are int32 words in device memory, sp[GPT2_SP_WORDS]
 // (temperature as its float bits; STEP is read only without a device step state — the diagnostic op)
 enum { GPT2_SP_SEED_LO, GPT2_SP_SEED_HI, GPT2_SP_GEN, GPT2_SP_ROW0, GPT2_SP_PURPOSE, GPT2_SP_TEMP, GPT2_SP_TOPK, GPT2_SP_STEP, GPT2_SP_WORDS };
 #define GPT2_SAMPLE_TOPK_MAX 256
 bool gpt2_sample_supported(int V);
 // logits [rows][V] -> out[(state ? state[1] : 0) * rows + row]
-void launch_gpt2_sample(const float* logits, int rows, int V, const int* sp, int* out, int* state, hipStream_t st);
-// vocabulary projection (logits + pairs written) + sampler from the pairs; tail: launch_gpt2_head_tail's pick / embed / advance tail
-bool launch_gpt2_head_sample(const float* A, const float* W, int M, int N, int K, int lda, const float* stats_in, const float* lng, const float* lnb,
-                             float* logits, float* pairs, const int* sp, int* gen, int* state, bool tail, const float* wte, const float* wpe, float* x,
-                             float* stats_out, hipStream_t st);
+void launch_gpt2_sample(const float* logits, int rows, int V, const int* sp, int* out, int* state, const LaunchTo& to);
 // NCHW fp32 image [n][3][S][S] -> CLIP patch matrix [n*G*G][3*ps*ps] fp16
 void launch_image_patches(const float* img, int n, int S, int ps, int ld, half_t* patches, hipStream_t st);

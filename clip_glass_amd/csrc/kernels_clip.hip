@@ -92,9 +92,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, long lon
            o32 ? o32 + (long long)row * D : nullptr);
 }
 void launch_layernorm(const float* x, long long row_stride, int M, int D, const float* g, const float* b,
-                      half_t* out16, float* out32, hipStream_t st) {
-    hipLaunchKernelGGL(layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, x, row_stride, M, D, g, b, out16,
-                       out32);
+                      half_t* out16, float* out32, const LaunchTo& to) {
+    launch_kernel(to, "layernorm_kernel", layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, x, row_stride, M, D, g, b, out16, out32);
 }
 
 // LayerNorm of gathered rows: out[m] = LN(x[rows[m]]) (the text tower's ln_final on each text's EOT row, clip/model.py:316-318)

@@ -553,7 +553,7 @@ extern "C" int glass_op_gpt2_sample(int32_t device, int32_t rows, int32_t V, con
     return GLASS_OK;
 }
 
-// ---- GPT-2 trunk kernels (gpt2.hip), launched exactly as gpt2_decode_group (engine.cpp) launches them ---------------------------------
+// ---- GPT-2 trunk kernels (gpt2.hip), launched exactly as the passes of gpt2_host.cpp launch them ---------------------------------
 extern "C" int glass_op_gpt2_gemm(int32_t device, int32_t form, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t mode, int32_t width,
                                   const float* a, const float* w, const float* bias, const float* lng, const float* lnb, const float* pst_in,
                                   int32_t np_in, float* out, float* stats_out, float* pst_out, int32_t* splits) {
@@ -595,12 +595,16 @@ extern "C" int glass_op_gpt2_gemm(int32_t device, int32_t form, int32_t M, int32
         launch_gemm_f32(da, dw, db, dout, M, N, K, lda, N, mode, 0, part, part_elems, form == 0);
     } else if (form == 2) {
         if (ln) launch_gpt2_finalize(nullptr, 0, nullptr, da, M, K, dstats, 0);
-        S = launch_gemm_f32_step(da, dw, db, dout, M, N, K, lda, N, mode, 0, part, part_elems, ln ? dstats : nullptr, dg, dlb);
-        OPREQ(S > 0, "launch_gemm_f32_step refused the shape");
+        const StepGemm c = choose_gemm_f32_step(M, N, K, lda, ln, part_elems, glass_cu_count());
+        OPREQ(c, "choose_gemm_f32_step refused the shape");
+        launch_gemm_f32_step({da, dw, db, dout, N, mode, part, ln ? dstats : nullptr, dg, dlb}, c, 0);
+        S = c.S;
         if (mode == 2) launch_gpt2_finalize(S > 1 ? part : nullptr, S, db, dout, M, N, dstats, 0);
         else if (S > 1) launch_gpt2_reduce(part, S, db, dout, M, N, N, mode, 0);
     } else {
-        OPREQ(launch_gemm_f32_rowblk(da, dw, db, dout, M, N, K, lda, N, mode, 0, dpi, np_in, dg, dlb, dpo), "launch_gemm_f32_rowblk refused the shape");
+        const StepGemm c = choose_gemm_f32_rowblk(M, N, K, lda, ln, np_in, dpo != nullptr);
+        OPREQ(c, "choose_gemm_f32_rowblk refused the shape");
+        launch_gemm_f32_rowblk({da, dw, db, dout, N, mode, nullptr, dpi, dg, dlb, dpo}, c, 0);
     }
     int rc = finish();
     if (rc) return rc;
@@ -675,7 +679,9 @@ extern "C" int glass_op_gpt2_head(int32_t device, int32_t M, int32_t V, int32_t 
         OPREQ(dl && dtok, "hipMalloc failed");
         GLASS_HIP(hipMemset(dl, 0xff, (size_t)M * V * sizeof(float)));
         GLASS_HIP(hipMemset(pairs, 0xff, (size_t)2 * M * NB * sizeof(float)));
-        OPREQ(launch_gpt2_head(dx, dw, M, V, K, K, dstats, dg, db, dl, pairs, dtok, nullptr, 0), "launch_gpt2_head refused the shape");
+        const Gpt2Head h = choose_gpt2_head(M, V, K, K, GPT2_PICK_ARGMAX, true);
+        OPREQ(h, "choose_gpt2_head refused the shape");
+        launch_gpt2_head({dx, dw, dstats, dg, db, dl, pairs, nullptr, dtok, nullptr}, h, 0);
         int rc = finish();
         if (rc) return rc;
         GLASS_HIP(hipMemcpy(stats, dstats, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost));
@@ -693,7 +699,9 @@ extern "C" int glass_op_gpt2_head(int32_t device, int32_t M, int32_t V, int32_t 
     GLASS_HIP(hipMemcpy(dstate, st0, sizeof st0, hipMemcpyHostToDevice));
     GLASS_HIP(hipMemcpy(stats, dstats, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost));
     // as the engine: the residual stream and its statistics are the head's operands AND the buffers the tail leaves the next step's in
-    OPREQ(launch_gpt2_head_tail(dx, dw, M, V, K, K, dstats, dg, db, pairs, dgen, dstate, dw, dpe, dx, dstats, 0), "launch_gpt2_head_tail refused the shape");
+    const Gpt2Head h = choose_gpt2_head(M, V, K, K, GPT2_PICK_ARGMAX_TAIL, false);
+    OPREQ(h, "choose_gpt2_head refused the shape");
+    launch_gpt2_head({dx, dw, dstats, dg, db, nullptr, pairs, nullptr, dgen, dstate, dw, dpe, dx, dstats}, h, 0);
     int rc = finish();
     if (rc) return rc;
     GLASS_HIP(hipMemcpy(token, dgen + (size_t)step * M, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
@@ -921,5 +929,13 @@ extern "C" int glass_host_resize_taps(int32_t R, int32_t S, int32_t mode, int32_
         count[i] = t.count[i];
         for (int k = 0; k < max; ++k) taps[(size_t)i * max + k] = k < GLASS_RESIZE_MAX_TAPS ? t.taps[(size_t)i * GLASS_RESIZE_MAX_TAPS + k] : 0.f;
     }
+    return GLASS_OK;
+}
+
+extern "C" int glass_host_gpt2_gemm_choice(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ln, int32_t width, int32_t n_cu, int32_t* S, int32_t* NK) {
+    OPREQ(S && NK && M > 0 && N > 0 && K > 0 && width > 0 && n_cu > 0, "bad argument");
+    const StepGemm c = choose_gemm_f32_step(M, N, K, lda, ln != 0, (size_t)16 * M * 4 * width, n_cu);
+    *S = c.S;
+    *NK = c.NK;
     return GLASS_OK;
 }

@@ -391,8 +391,8 @@ def gpt2_attention(qkv, kc, vc, past, heads, form="general", bias=None, device=0
 
 
 def gpt2_head(x, wte, lng, lnb, tail=False, wpe=None, past=0, step=0, device=0):
-    """The vocabulary head of a single-token step (gpt2.hip): row statistics by gpt2_finalize_kernel, then launch_gpt2_head (tail=False:
-    returns logits [M, V], pair_val / pair_idx [M, ceil(V/32)], token [M], stats [M, 2]) or launch_gpt2_head_tail at the state
+    """The vocabulary head of a single-token step (gpt2.hip): row statistics by gpt2_finalize_kernel, then launch_gpt2_head with the arg-max pick (tail=False:
+    returns logits [M, V], pair_val / pair_idx [M, ceil(V/32)], token [M], stats [M, 2]) or with the arg-max + embed / advance tail at the state
     {past, step, 0} (tail=True: token, stats, x_next [M, K], stats_next [M, 2], state [3])."""
     lib = load_library()
     x, wte, lng, lnb = _f32(x), _f32(wte), _f32(lng), _f32(lnb)
@@ -569,3 +569,28 @@ def host_resize_taps(R, S, mode, max_taps=RESIZE_MAX_TAPS):
     lib.glass_host_resize_taps.argtypes = [C.c_int32] * 3 + [ip, ip, C.POINTER(C.c_float), C.c_int32]
     _check(lib, lib.glass_host_resize_taps(R, S, int(mode), start.ctypes.data_as(ip), count.ctypes.data_as(ip), _fp(taps), max_taps))
     return start, count, taps
+
+
+def host_gpt2_step_plan(P, D, V, n_layer, Tmax, sample=False, n_cu=256):
+    """The launches of one GPT-2 token step as the engine's host code makes them, host only: a list of (kernel name, grid (x, y, z),
+    block (x, y, z)) in launch order.  n_cu: the compute units the step products' grids are weighed against."""
+    lib = load_library()
+    buf = C.create_string_buffer(1 << 16)
+    lib.glass_host_gpt2_step_plan.argtypes = [C.c_int32] * 7 + [C.c_char_p, C.c_int32]
+    _check(lib, lib.glass_host_gpt2_step_plan(P, D, V, n_layer, Tmax, int(bool(sample)), n_cu, buf, len(buf)))
+    plan = []
+    for line in buf.value.decode().splitlines():
+        name, grid, block = line.rsplit(" ", 2)
+        plan.append((name, tuple(int(v) for v in grid.split("=")[1].split(",")), tuple(int(v) for v in block.split("=")[1].split(","))))
+    return plan
+
+
+def host_gpt2_gemm_choice(M, N, K, ln=False, width=None, n_cu=256):
+    """choose_gemm_f32_step's answer for a [M, K] x [N, K]^T step product, host only: (S, NK) — the global K split (0: refused) and the K parts
+    per workgroup — with the split-K scratch gpt2_gemm gives it (width: as there) on a device of n_cu compute units."""
+    lib = load_library()
+    S, NK = C.c_int32(-1), C.c_int32(-1)
+    ip = C.POINTER(C.c_int32)
+    lib.glass_host_gpt2_gemm_choice.argtypes = [C.c_int32] * 7 + [ip, ip]
+    _check(lib, lib.glass_host_gpt2_gemm_choice(M, N, K, K, int(bool(ln)), int(width or min(N, K)), n_cu, C.byref(S), C.byref(NK)))
+    return S.value, NK.value

@@ -121,12 +121,12 @@ int glass_op_noise(int32_t device, int32_t n_mb, int32_t hw, uint32_t layer, uin
  * (temperature > 0, top_k in [0, 256], 0 = keep all; V <= 131072); out: int32 [rows]. */
 int glass_op_gpt2_sample(int32_t device, int32_t rows, int32_t V, const float* logits, float temperature, int32_t top_k,
                          uint64_t seed, int32_t generation, int32_t first_row, int32_t step, int32_t purpose, int32_t* out);
-/* The GPT-2 trunk's fp32 kernels (gpt2.hip), each launched as gpt2_decode_group (engine.cpp) launches it.  A shape a launcher does not
+/* The GPT-2 trunk's fp32 kernels (gpt2.hip), each launched as the passes of gpt2_host.cpp launch it.  A shape a launcher does not
  * take is an error (glass_last_error names the condition), never a different kernel.
  *
  * glass_op_gpt2_gemm: out[M,N] = A[M,K] (row stride lda >= K) @ W[N,K]^T (+ bias[N], nullable); mode 0 plain, 1 GELU-tanh, 2 out += (out
- * holds the residual on entry).  form 0: launch_gemm_f32(prefill = true); 1: launch_gemm_f32(prefill = false); 2: launch_gemm_f32_step,
- * finished by launch_gpt2_reduce (modes 0 / 1) or launch_gpt2_finalize (mode 2; N <= 1024); 3: launch_gemm_f32_rowblk.  The split-K scratch
+ * holds the residual on entry).  form 0: launch_gemm_f32(prefill = true); 1: launch_gemm_f32(prefill = false); 2: choose_gemm_f32_step (with the device's
+ * CU count) + launch_gemm_f32_step, finished by launch_gpt2_reduce (modes 0 / 1) or launch_gpt2_finalize (mode 2; N <= 1024); 3: choose_gemm_f32_rowblk + launch_gemm_f32_rowblk.  The split-K scratch
  * holds 16 * M * 4 * width floats, as the engine sizes it for a model of that width.  lng / lnb [K] (forms 2 / 3, modes 0 / 1): the operand
  * is LayerNorm(A) with the row statistics of the device's own producers — form 2: gpt2_finalize_kernel over A (lda == K), returned in
  * stats_out [M,2] = {mean, rstd}; form 3: the (mean, M2) partials pst_in [M, np_in, 2] an earlier form-3 call returned.  stats_out
@@ -144,8 +144,8 @@ int glass_op_gpt2_attention(int32_t device, int32_t form, int32_t P, int32_t nd,
                             const float* qkv, const float* bias, float* kc, float* vc, float* out);
 /* The vocabulary head of a single-token step on x [M, K] (M <= 64, K % 64 == 0, K <= 1024, V >= 4096): launch_gpt2_finalize(part = nullptr)
  * for the row statistics (returned in stats [M,2]), then
- * tail == 0: launch_gpt2_head with logits -> logits [M, V], the block (max, lowest index) pairs pair_val / pair_idx [M, ceil(V/32)], token [M];
- * tail != 0: launch_gpt2_head_tail with the state {past, step, 0} -> token [M], the next step's embedding x_next [M, K] (wte[token] +
+ * tail == 0: launch_gpt2_head with the arg-max pick and logits -> logits [M, V], the block (max, lowest index) pairs pair_val / pair_idx [M, ceil(V/32)], token [M];
+ * tail != 0: launch_gpt2_head with the arg-max + embed / advance tail at the state {past, step, 0} -> token [M], the next step's embedding x_next [M, K] (wte[token] +
  *            wpe[past + 1]; wpe [npos, K]), its statistics stats_next [M, 2] and the state words state [3] afterwards. */
 int glass_op_gpt2_head(int32_t device, int32_t M, int32_t V, int32_t K, int32_t tail, const float* x, const float* wte, const float* lng,
                        const float* lnb, const float* wpe, int32_t npos, int32_t past, int32_t step, float* logits, float* pair_val,
@@ -186,6 +186,15 @@ int glass_host_pack_conv(const float* w, int32_t Cout, int32_t Cin, int32_t KS, 
  * i reads inputs start[i] .. start[i] + count[i] - 1 with weights taps[i * max + k] (fp32 roundings of the float64 weights; zero past count).
  * GLASS_ERR_ARG when (R, S, mode) is refused (glass_clip_preprocess_supported) or a row needs more than `max` taps. */
 int glass_host_resize_taps(int32_t R, int32_t S, int32_t mode, int32_t* start, int32_t* count, float* taps, int32_t max);
+/* Host-only (no GPU): choose_gemm_f32_step's answer for one product — what glass_op_gpt2_gemm's form 2 would launch on a device of n_cu compute
+ * units with the scratch of a model of that width: the global K split *S (0: the shape is refused) and the K parts per workgroup *NK. */
+int glass_host_gpt2_gemm_choice(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ln, int32_t width, int32_t n_cu, int32_t* S, int32_t* NK);
+/* Host-only (no GPU): what one GPT-2 token step launches for rows P (one group: <= 64), width D, vocabulary V, n_layer blocks, sequence
+ * length Tmax (context + generated) and the pick (sample != 0: the stochastic one), with the grids weighed against n_cu compute units
+ * (the engine passes the device's).  out receives one line per launch, in launch order: "<kernel's profile name> grid=x,y,z block=x,y,z".
+ * The lines come from the step's own host code (gpt2_host.cpp) run into a text instead of a stream.  GLASS_ERR_ARG when cap is too small. */
+int glass_host_gpt2_step_plan(int32_t P, int32_t D, int32_t V, int32_t n_layer, int32_t Tmax, int32_t sample, int32_t n_cu, char* out,
+                              int32_t cap);
 
 #ifdef __cplusplus
 }

@@ -132,8 +132,9 @@ def test_engine_gpt2_decode_matches_oracle(geo, P, n_ctx, length):
     _assert_token_parity("decode P=%d L=%d" % (P, length), got, ora, detail["margins"].numpy() if hasattr(detail["margins"], "numpy") else detail["margins"], n_ctx)
 
 
-# Geometries that reach the branches of gpt2_decode_group the cases above do not (all n_layer = 2, weight seed 2, context seed 1).
-# id -> (n_embd, vocab, P, n_ctx, length, n_positions); the step path each one takes, from the launch conditions in gpt2_host.cpp:
+# Geometries that reach the branches of the GPT-2 decode host (gpt2_host.cpp) the cases above do not (all n_layer = 2, weight seed 2, context seed 1).
+# id -> (n_embd, vocab, P, n_ctx, length, n_positions); the step path each one takes, as plan_gpt2_step (gpt2_host.cpp) decides it on 256 CUs —
+# asserted statement by statement, without a device, in test_gpt2_plan.py:
 #   D64     fused + tail-fused, not rowblk; every step product unsplit but the MLP's second (S = 4); step attention, P * heads = 33 (the
 #           last workgroup has one live wave); prefill rows 33 * 23
 #   D192    fused + tail-fused; three 64-deep chunks: S = 3 with one K part per workgroup (qkv, attention output, MLP first), S = 12 (MLP second)

@@ -1,5 +1,5 @@
 """Per-kernel parity of the GPT-2 trunk (csrc/gpt2.hip) through the diagnostic ops glass_op_gpt2_* (include/glass_ops.h), which launch
-each kernel as gpt2_decode_group launches it.  References: float64 numpy of the same operation (tests/gpt2_ops_ref.py, pinned to the
+each kernel as the passes of gpt2_host.cpp launch it.  References: float64 numpy of the same operation (tests/gpt2_ops_ref.py, pinned to the
 oracle by tests/test_gpt2_ops_ref.py).
 
 Two kinds of input:
@@ -490,8 +490,8 @@ def test_head_logits_pairs_and_pick(M, V, K):
 
 @pytest.mark.parametrize("M,V,K", [(1, 4096, 128), (33, 5000, 768), (64, 4096, 1024), (64, 50257, 768)])
 def test_head_tail_matches_pick_and_embed_step(M, V, K):
-    """launch_gpt2_head_tail: the token of launch_gpt2_head, the next step's x / statistics bitwise as launch_gpt2_embed_step leaves
-    them, the state advanced to {past + 1, step + 1, 0}."""
+    """launch_gpt2_head with the arg-max + embed / advance tail: the token of the plain arg-max pick, the next step's x / statistics bitwise
+    as launch_gpt2_embed_step leaves them, the state advanced to {past + 1, step + 1, 0}."""
     ops = _ops()
     x, g, b, wte = _head_inputs(M, V, K, _tie_plan(M, V))
     wpe = (0.01 * np.random.RandomState(5).standard_normal((64, K))).astype(np.float32)
