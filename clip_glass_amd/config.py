@@ -1,7 +1,8 @@
 """Config table — mirror of /root/reference/config.py (same keys and values for the
 StyleGAN2 configs; `latent` / `model` point at this package's classes).
 
-Optional keys the table leaves unset (run.py copies them in from its flags): `clip_model` (generator.CLIP_MODELS, default ViT-B/32) and
+Optional keys the table leaves unset (run.py copies them in from its flags): `clip_model` (generator.CLIP_MODELS, default ViT-B/32),
+`clip_resnet` (generator.CLIP_RESNET_MODELS: RN50 / RN101 instead of a ViT; `clip_resnet_geometry` = (layers4, width, res, embed) wins over the name) and
 `clip_preprocess` — "reference" (default: the reference's resize, generator.py:45), "antialias" or "clip" (generator.CLIP_PREPROCESS)."""
 from .latent import DeepMindBigGANLatentSpace, GPT2LatentSpace, StyleGAN2LatentSpace
 from .models import GPT2, DeepMindBigGAN, StyleGAN2

@@ -28,6 +28,29 @@ extern "C" int glass_clip_geometry_supported(int32_t width, int32_t layers, int3
 #undef GEOM_REQ
     return GLASS_OK;
 }
+// The one rule for a ModifiedResNet image tower (host only).  Every GEMM of the tower has K and N in {w, 2w, ... 32w} (w / 2 only in the stem's
+// own kernels), so a stem width that is a multiple of 64 makes all of them multiples of gemm_tiled's 64-wide tiles and K steps, and the
+// attention pool (32 w channels, w / 2 heads) has head dimension 64.
+extern "C" int glass_clip_resnet_supported(const int32_t layers[4], int32_t width, int32_t res, int32_t embed) {
+    char msg[256];
+#define GEOM_REQ(cond, ...)                       \
+    if (!(cond)) {                                \
+        snprintf(msg, sizeof msg, __VA_ARGS__);   \
+        glass_set_error(msg);                     \
+        return GLASS_ERR_ARG;                     \
+    }
+    GEOM_REQ(layers != nullptr, "unsupported CLIP ResNet geometry: null layers");
+    GEOM_REQ(width > 0 && res > 0 && embed > 0, "unsupported CLIP ResNet geometry: width, resolution and embed must be positive");
+    for (int i = 0; i < 4; ++i)
+        GEOM_REQ(layers[i] >= 1 && layers[i] <= 64, "unsupported CLIP ResNet geometry: stage %d has %d bottlenecks (1 .. 64)", i + 1, layers[i]);
+    GEOM_REQ(width % 64 == 0, "unsupported CLIP ResNet geometry: stem width %d is not a multiple of 64 (RN50x4 / RN50x16, widths 80 / 96, are not "
+             "supported: every GEMM K and N must be a multiple of 64 and the attention pool's head dimension 64)", width);
+    GEOM_REQ(res % 32 == 0, "unsupported CLIP ResNet geometry: resolution %d is not a multiple of 32 (the tower's total stride)", res);
+    GEOM_REQ(width <= 256 && res <= 1024 && embed <= 4096, "unsupported CLIP ResNet geometry: width %d / resolution %d / embed %d out of range "
+             "(width <= 256, resolution <= 1024, embed <= 4096)", width, res, embed);
+#undef GEOM_REQ
+    return GLASS_OK;
+}
 int clip_patch_k(const glass_config& c) { return (3 * c.clip_patch * c.clip_patch + 63) / 64 * 64; }   // patch rows padded to gemm_tiled's K step
 
 // The one rule for the opt-in CLIP preprocessing (host only).  gen_res: side of the generated image, 0 for an engine without a generator
@@ -91,7 +114,136 @@ static int load_clip_blocks(glass_engine* e, const char* prefix, int layers, int
     return GLASS_OK;
 }
 
+static int finalize_clip_text(glass_engine* e);
+
+std::vector<_Float16> rn_pack_conv(const float* w, int cout, int cin, int ks) {
+    std::vector<_Float16> out((size_t)ks * ks * cout * cin);
+    for (int o = 0; o < cout; ++o)
+        for (int i = 0; i < cin; ++i)
+            for (int t = 0; t < ks * ks; ++t) out[((size_t)t * cout + o) * cin + i] = (_Float16)w[((size_t)o * cin + i) * ks * ks + t];
+    return out;
+}
+// inference BatchNorm (eps 1e-5) under `bn` + ".weight / .bias / .running_mean / .running_var" -> fp32 scale and shift on the device
+// (computed in float64, kept out of the fp16 weights: a channel with a tiny running variance would cost them their range)
+static int load_rn_bn(glass_engine* e, const std::string& bn, int C, float** a_out, float** s_out) {
+    GET(g, bn + ".weight");
+    GET(b, bn + ".bias");
+    GET(mu, bn + ".running_mean");
+    GET(var, bn + ".running_var");
+    REQUIRE(numel(g) == (size_t)C && numel(b) == (size_t)C && numel(mu) == (size_t)C && numel(var) == (size_t)C, GLASS_ERR_ARG,
+            "bad BatchNorm shapes: " + bn);
+    std::vector<float> A(C), S(C);
+    for (int i = 0; i < C; ++i) {
+        REQUIRE(var->data[i] >= 0.f, GLASS_ERR_ARG, "negative running_var: " + bn);
+        const double a = (double)g->data[i] / sqrt((double)var->data[i] + 1e-5);
+        A[i] = (float)a;
+        S[i] = (float)((double)b->data[i] - (double)mu->data[i] * a);
+    }
+    int rc = upload(e, a_out, A);
+    if (rc) return rc;
+    return upload(e, s_out, S);
+}
+static int load_rn_conv(glass_engine* e, const std::string& conv, const std::string& bn, int cin, int cout, int ks, RnConv& c) {
+    GET(w, conv + ".weight");
+    REQUIRE(numel(w) == (size_t)cout * cin * ks * ks && w->dims.size() == 4 && w->dims[0] == cout, GLASS_ERR_ARG, "bad conv shape: " + conv);
+    c.cin = cin; c.cout = cout; c.ks = ks;
+    int rc = upload(e, &c.w, rn_pack_conv(w->data.data(), cout, cin, ks));
+    if (rc) return rc;
+    return load_rn_bn(e, bn, cout, &c.a, &c.s);
+}
+// the ModifiedResNet tower under the reference's keys (clip/model.py:100-132); num_batches_tracked is never asked for
+static int finalize_clip_resnet(glass_engine* e) {
+    const glass_config& c = e->cfg;
+    const int w = c.clip_width, G = c.clip_res / 32, T = G * G + 1, C = 32 * w, E = c.clip_embed;
+    const std::string v = "clip.visual.";
+    RnState& rn = e->rn;
+    int rc;
+    {
+        GET(w1, v + "conv1.weight");
+        REQUIRE(numel(w1) == (size_t)(w / 2) * 27, GLASS_ERR_ARG, "bad CLIP ResNet stem conv1 shape");
+        std::vector<_Float16> t((size_t)27 * (w / 2));       // [ci][ky][kx] rows, output channel contiguous
+        for (int o = 0; o < w / 2; ++o)
+            for (int k = 0; k < 27; ++k) t[(size_t)k * (w / 2) + o] = (_Float16)w1->data[(size_t)o * 27 + k];
+        if ((rc = upload(e, &rn.stem_w1, t))) return rc;
+        if ((rc = load_rn_bn(e, v + "bn1", w / 2, &rn.stem_a1, &rn.stem_s1))) return rc;
+    }
+    if ((rc = load_rn_conv(e, v + "conv2", v + "bn2", w / 2, w / 2, 3, rn.stem2))) return rc;
+    if ((rc = load_rn_conv(e, v + "conv3", v + "bn3", w / 2, w, 3, rn.stem3))) return rc;
+    int inplanes = w, res = c.clip_res / 4;
+    for (int st = 0; st < 4; ++st) {
+        const int planes = w << st;
+        for (int i = 0; i < c.clip_rn_layers[st]; ++i) {
+            char nm[96];
+            snprintf(nm, sizeof nm, "layer%d.%d.", st + 1, i);
+            const std::string p = v + nm;
+            RnBlock b;
+            b.stride = (st > 0 && i == 0) ? 2 : 1;
+            b.res_in = res;
+            b.has_down = b.stride > 1 || inplanes != 4 * planes;
+            if ((rc = load_rn_conv(e, p + "conv1", p + "bn1", inplanes, planes, 1, b.c1))) return rc;
+            if ((rc = load_rn_conv(e, p + "conv2", p + "bn2", planes, planes, 3, b.c2))) return rc;
+            if ((rc = load_rn_conv(e, p + "conv3", p + "bn3", planes, 4 * planes, 1, b.c3))) return rc;
+            if (b.has_down && (rc = load_rn_conv(e, p + "downsample.0", p + "downsample.1", inplanes, 4 * planes, 1, b.down))) return rc;
+            rn.blocks.push_back(b);
+            inplanes = 4 * planes;
+            res /= b.stride;
+        }
+    }
+    const std::string ap = v + "attnpool.";
+    GET(pos, ap + "positional_embedding");
+    GET(qw, ap + "q_proj.weight");
+    GET(kw, ap + "k_proj.weight");
+    GET(vw, ap + "v_proj.weight");
+    GET(cw, ap + "c_proj.weight");
+    GET(qb, ap + "q_proj.bias");
+    GET(kb, ap + "k_proj.bias");
+    GET(vb, ap + "v_proj.bias");
+    GET(cb, ap + "c_proj.bias");
+    REQUIRE(numel(pos) == (size_t)T * C && numel(qw) == (size_t)C * C && numel(kw) == (size_t)C * C && numel(vw) == (size_t)C * C &&
+                numel(cw) == (size_t)E * C && numel(qb) == (size_t)C && numel(kb) == (size_t)C && numel(vb) == (size_t)C && numel(cb) == (size_t)E,
+            GLASS_ERR_ARG, "bad CLIP ResNet attention pool shapes");
+    std::vector<_Float16> wqkv((size_t)3 * C * C);
+    std::vector<float> bqkv((size_t)3 * C);
+    const HostTensor* ws[3] = {qw, kw, vw};
+    const HostTensor* bs[3] = {qb, kb, vb};
+    for (int j = 0; j < 3; ++j) {
+        for (size_t i = 0; i < (size_t)C * C; ++i) wqkv[(size_t)j * C * C + i] = (_Float16)ws[j]->data[i];
+        std::copy(bs[j]->data.begin(), bs[j]->data.end(), bqkv.begin() + (size_t)j * C);
+    }
+    if ((rc = upload(e, &rn.w_qkv, wqkv))) return rc;
+    if ((rc = upload(e, &rn.b_qkv, bqkv))) return rc;
+    if ((rc = upload(e, &rn.pos, pos->data))) return rc;
+    if ((rc = upload(e, &rn.cproj_wt, transposed(cw->data.data(), E, C, 1.f)))) return rc;
+    if ((rc = upload(e, &rn.cproj_b, cb->data))) return rc;
+    return GLASS_OK;
+}
+int alloc_clip_resnet(glass_engine* e) {
+    const glass_config& c = e->cfg;
+    if (c.clip_arch != 1) return GLASS_OK;
+    const size_t P = c.max_pop, w = c.clip_width, G = c.clip_res / 32, T = G * G + 1, C = 32 * w;
+    RnState& rn = e->rn;
+    // the largest maps: the stem's (res/2)^2 x w and layer1's (res/4)^2 x 4w, the same size; never below 64 rows of the widest map
+    rn.cap = std::max(P * (size_t)(c.clip_res / 2) * (c.clip_res / 2) * w, (size_t)64 * C);
+    int rc;
+    for (int i = 0; i < 7; ++i) {
+        if ((rc = dev_alloc(e, &rn.buf[i], rn.cap))) return rc;
+        GLASS_HIP(hipMemset(rn.buf[i], 0, rn.cap * sizeof(half_t)));      // (rows past a short M are read by the padded GEMMs: keep them finite)
+    }
+    const size_t rows = std::max(P * T, (size_t)64);
+    if ((rc = dev_alloc(e, &rn.tok, rows * C))) return rc;
+    GLASS_HIP(hipMemset(rn.tok, 0, rows * C * sizeof(half_t)));
+    if ((rc = dev_alloc(e, &rn.qkv, rows * 3 * C))) return rc;
+    if ((rc = dev_alloc(e, &rn.att, rows * C))) return rc;
+    if ((rc = dev_alloc(e, &rn.cls, P * C))) return rc;
+    GLASS_HIP(hipDeviceSynchronize());      // the fills ran on the null stream; the engine's streams do not wait for it
+    return GLASS_OK;
+}
+
 int finalize_clip(glass_engine* e) {
+    if (e->cfg.clip_arch == 1) {
+        int rc = finalize_clip_resnet(e);
+        return rc ? rc : finalize_clip_text(e);
+    }
     const glass_config& c = e->cfg;
     const int W = c.clip_width, ps = c.clip_patch, G = c.clip_res / ps, T = G * G + 1, E = c.clip_embed;
     const std::string v = "clip.visual.";
@@ -124,7 +276,13 @@ int finalize_clip(glass_engine* e) {
     if ((rc = upload(e, &e->c_proj, proj->data))) return rc;  // already [K=W][N=E]
     int rc2 = load_clip_blocks(e, "clip.visual.transformer.resblocks.", c.clip_layers, W, e->cblk);
     if (rc2) return rc2;
-    // ---- optional text tower (clip/model.py:277-290) ----
+    return finalize_clip_text(e);
+}
+
+// ---- optional text tower (clip/model.py:277-290) ----
+static int finalize_clip_text(glass_engine* e) {
+    const int E = e->cfg.clip_embed;
+    int rc;
     if (find(e, "clip.token_embedding.weight") != nullptr) {
         GET(tok, "clip.token_embedding.weight");
         GET(tpos, "clip.positional_embedding");
@@ -202,8 +360,107 @@ static void run_blocks(glass_engine* e, const std::vector<ClipBlock>& blk, int l
     }
 }
 
+// ---- the ResNet image tower (clip/model.py:134-149, :39-52, :65-89) ----
+GemmParams rn_gemm_1x1(const half_t* x, const RnConv& c, int M, int cand_rows, const half_t* res, int relu, half_t* y) {
+    GemmParams g = gemm_params(x, c.w, std::max(M, 64), c.cout, c.cin, nullptr, 5, y, nullptr, cand_rows);
+    g.bn_a = c.a; g.bn_s = c.s; g.res16 = res; g.bn_relu = relu;
+    return g;
+}
+GemmParams rn_gemm_3x3(const half_t* x, const RnConv& c, int B, int H, int W, half_t* y) {
+    GemmParams g = gemm_params(x, c.w, B * H * W, c.cout, 9 * c.cin, nullptr, 5, y, nullptr, H * W);
+    g.bn_a = c.a; g.bn_s = c.s; g.bn_relu = 1;
+    g.kpt = c.cin; g.w_tap_stride = (long long)c.cout * c.cin;
+    g.g_on = 1; g.g_h = H; g.g_w = W; g.g_hc = H; g.g_wc = W; g.g_stride = 1; g.g_pad = 1; g.g_ks = 3; g.g_cin = c.cin;
+    g.g_xbs = (long long)H * W * c.cin;
+    return g;
+}
+static void rn_refused(glass_engine* e, const char* tag) {      // a missing kernel is an error of the pass, never another path
+    if (e->launch_error.empty()) e->launch_error = std::string("no kernel accepts layer ") + tag;
+}
+static void rn_gemm(glass_engine* e, const GemmParams& g, const char* tag) {
+    const double rows_a = g.g_on ? (double)g.M * g.g_cin : (double)g.M * g.K;     // the map is read once, not once per tap
+    Prof pr(e, tag, 2.0 * g.M * g.N * g.K, 2.0 * (rows_a + (double)g.N * g.K + (double)g.M * g.N * (g.res16 ? 2 : 1)));
+    const char* k = launch_gemm_tiled(g, e->cur);
+    if (!k) { rn_refused(e, tag); k = "(refused)"; }
+    pr.ran(tag, k);
+}
+static void rn_pool(glass_engine* e, const half_t* x, int B, int H, int C, half_t* y, const char* tag) {
+    Prof pr(e, tag, 0, 2.5 * B * H * H * C);
+    if (!launch_rn_avgpool2(x, B, H, H, C, y, e->cur)) rn_refused(e, tag);
+}
+static void run_rn_stem(glass_engine* e, int P) {
+    const glass_config& c = e->cfg;
+    RnState& rn = e->rn;
+    const int w = c.clip_width, S = c.clip_res, H = S / 2;
+    {
+        Prof pr(e, "clip.stem_conv1", 2.0 * P * H * H * 27 * (w / 2), 2.0 * P * (3.0 * S * S + (double)H * H * (w / 2)));
+        if (!launch_rn_stem_conv1(e->d_patches, rn.stem_w1, rn.stem_a1, rn.stem_s1, P, S, w / 2, rn.buf[2], e->cur)) rn_refused(e, "clip.stem_conv1");
+    }
+    auto conv = [&](const RnConv& k, const half_t* x, half_t* y, const char* tag) {
+        Prof pr(e, tag, 2.0 * P * H * H * 9 * k.cin * k.cout, 2.0 * ((double)P * H * H * (k.cin + k.cout) + 9.0 * k.cin * k.cout));
+        const char* name = launch_rn_conv3x3(x, k.w, k.a, k.s, P, H, H, k.cin, k.cout, y, e->cur);
+        if (!name) { rn_refused(e, tag); name = "(refused)"; }
+        pr.ran(tag, name);
+    };
+    conv(rn.stem2, rn.buf[2], rn.buf[3], "clip.stem_conv2");
+    conv(rn.stem3, rn.buf[3], rn.buf[2], "clip.stem_conv3");
+    rn_pool(e, rn.buf[2], P, H, w, rn.buf[0], "clip.stem_pool");
+}
+// bottleneck i reads its input from buf[i & 1] and writes buf[(i + 1) & 1]; buf[2 .. 6] are its temporaries
+static void run_rn_blocks(glass_engine* e, int P, int l0, int l1) {
+    RnState& rn = e->rn;
+    for (int i = l0; i < l1; ++i) {
+        const RnBlock& b = rn.blocks[i];
+        const int H = b.res_in, Ho = H / b.stride, M = P * H * H, Mo = P * Ho * Ho;
+        const half_t* x = rn.buf[i & 1];
+        half_t* y = rn.buf[(i + 1) & 1];
+        rn_gemm(e, rn_gemm_1x1(x, b.c1, M, H * H, nullptr, 1, rn.buf[2]), "clip.rn_conv1");
+        rn_gemm(e, rn_gemm_3x3(rn.buf[2], b.c2, P, H, H, rn.buf[3]), "clip.rn_conv2");
+        const half_t* t = rn.buf[3];
+        if (b.stride > 1) {
+            rn_pool(e, rn.buf[3], P, H, b.c2.cout, rn.buf[4], "clip.rn_pool");
+            t = rn.buf[4];
+        }
+        const half_t* id = x;
+        if (b.has_down) {
+            const half_t* xd = x;
+            if (b.stride > 1) {
+                rn_pool(e, x, P, H, b.c1.cin, rn.buf[5], "clip.rn_pool");
+                xd = rn.buf[5];
+            }
+            rn_gemm(e, rn_gemm_1x1(xd, b.down, Mo, Ho * Ho, nullptr, 0, rn.buf[6]), "clip.rn_down");
+            id = rn.buf[6];
+        }
+        rn_gemm(e, rn_gemm_1x1(t, b.c3, Mo, Ho * Ho, id, 1, y), "clip.rn_conv3");      // the residual goes in BEFORE the ReLU
+    }
+}
+static void run_rn_head(glass_engine* e, int P) {
+    const glass_config& c = e->cfg;
+    RnState& rn = e->rn;
+    const int G = c.clip_res / 32, HW = G * G, T = HW + 1, C = 32 * c.clip_width, heads = c.clip_heads, E = c.clip_embed;
+    const half_t* x = rn.buf[rn.blocks.size() & 1];
+    {
+        Prof pr(e, "clip.attnpool_tokens", 0, 2.0 * P * (HW + T) * C + 4.0 * T * C);
+        launch_rn_attnpool_tokens(x, rn.pos, P, HW, C, rn.tok, e->cur);
+    }
+    {
+        GemmParams g = gemm_params(rn.tok, rn.w_qkv, std::max(P * T, 64), 3 * C, C, rn.b_qkv, 0, rn.qkv, nullptr, T);
+        rn_gemm(e, g, "clip.attnpool_qkv");
+    }
+    {
+        Prof pr(e, "clip.attnpool_attention", 4.0 * P * heads * (double)T * T * 64, 8.0 * P * T * C);
+        launch_attention(rn.qkv, P, T, heads, 64, 0, rn.att, e->cur);
+    }
+    Prof pr(e, "clip.attnpool_head", 2.0 * P * C * E, 4.0 * C * E);
+    launch_rn_token0_rows(rn.att, P, T, C, rn.cls, e->cur);
+    launch_dense(rn.cls, C, P, C, rn.cproj_wt, E, rn.cproj_b, e->d_feat, E, 0, 0, nullptr, 0, e->cur);
+    launch_cosine(e->d_feat, e->d_target, P, E, e->d_sim, e->cur);
+}
+
 // ---- the image tower (declared in engine.h) ----
+int clip_n_layers(const glass_engine* e) { return e->cfg.clip_arch == 1 ? (int)e->rn.blocks.size() : (int)e->cblk.size(); }
 void run_clip_embed(glass_engine* e, int P) {
+    if (e->cfg.clip_arch == 1) return run_rn_stem(e, P);
     const glass_config& c = e->cfg;
     const int W = c.clip_width, G = c.clip_res / c.clip_patch, T = G * G + 1;
     run_gemm(e, gemm_params(e->d_patches, e->c_patch_w, P * G * G, W, clip_patch_k(c), nullptr, 3, nullptr, e->d_pe, G * G), "clip.patch_embed");
@@ -211,11 +468,13 @@ void run_clip_embed(glass_engine* e, int P) {
     launch_embed_lnpre(e->d_pe, e->c_cls, e->c_pos, e->c_lnpre_g, e->c_lnpre_b, P, T, W, e->d_x, e->cur);
 }
 void run_clip_layers(glass_engine* e, int P, int l0, int l1) {
+    if (e->cfg.clip_arch == 1) return run_rn_blocks(e, P, l0, std::min(l1, clip_n_layers(e)));
     const glass_config& c = e->cfg;
     const int G = c.clip_res / c.clip_patch;
     run_blocks(e, e->cblk, l0, std::min(l1, (int)e->cblk.size()), e->d_x, e->d_ln16, e->d_qkv, e->d_attn, e->d_hid, G * G + 1, P, c.clip_width, c.clip_heads, 0, e->cur, "clip");
 }
 void run_clip_head(glass_engine* e, int P) {
+    if (e->cfg.clip_arch == 1) return run_rn_head(e, P);
     const glass_config& c = e->cfg;
     const int W = c.clip_width, G = c.clip_res / c.clip_patch, T = G * G + 1;
     Prof pr(e, "clip.head", 2.0 * P * W * c.clip_embed, 4.0 * W * c.clip_embed);
@@ -226,7 +485,7 @@ void run_clip_head(glass_engine* e, int P) {
 }
 void run_clip(glass_engine* e, int P) {
     run_clip_embed(e, P);
-    run_clip_layers(e, P, 0, (int)e->cblk.size());
+    run_clip_layers(e, P, 0, clip_n_layers(e));
     run_clip_head(e, P);
 }
 
@@ -319,6 +578,7 @@ extern "C" int glass_engine_encode_image(glass_engine* e, const float* images, i
     GLASS_HIP(hipMalloc(&d_img, elems * sizeof(float)));
     hipError_t err = hipMemcpyAsync(d_img, images, elems * sizeof(float), hipMemcpyHostToDevice, e->stream);
     e->cur = e->stream;
+    e->launch_error.clear();
     launch_image_patches(d_img, n, c.clip_res, c.clip_patch, clip_patch_k(c), e->d_patches, e->stream);
     run_clip(e, n);
     if (err == hipSuccess)
@@ -331,6 +591,12 @@ extern "C" int glass_engine_encode_image(glass_engine* e, const float* images, i
     if (err != hipSuccess) {
         glass_set_error(std::string("encode_image failed: ") + hipGetErrorString(err));
         return GLASS_ERR_HIP;
+    }
+    if (!e->launch_error.empty()) {      // a launcher of the tower refused a layer
+        const std::string msg = e->launch_error;
+        e->launch_error.clear();
+        glass_set_error(msg);
+        return GLASS_ERR_STATE;
     }
     return GLASS_OK;
 }

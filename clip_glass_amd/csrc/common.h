@@ -335,7 +335,7 @@ struct GemmParams {
     const half_t* w;  // [N][K]
     int M, N, K;
     const float* bias;  // [N] nullable
-    int mode;           // 0: out16 = v ; 1: out16 = quickgelu(v) ; 2: x32 += v (in place) ; 3: out32 = v ; 4: out32 = lrelu(v)*sqrt2
+    int mode;           // 0: out16 = v ; 1: out16 = quickgelu(v) ; 2: x32 += v (in place) ; 3: out32 = v ; 4: out32 = lrelu(v)*sqrt2 ; 5: BatchNorm epilogue (bn_* below)
     half_t* out16;
     float* out32;
     int ldo;
@@ -351,4 +351,10 @@ struct GemmParams {
     long long g_xbs;        // elements between the images of x
     int ld;                 // 0: rows of a and w are K long.  > 0: their row stride (a K slice of longer rows: split-K as `batch` slices,
                             // a_bs = w_bs = K, raw partial sums to out32 + z * o_bs; gemm_tiled only.  With kpt: w_bs = 0, slice z starts at k = z * K of the tap walk)
+    // mode 5 (gemm_tiled only): out16 = act(v * bn_a[n] + bn_s[n] (+ res16[m][n])) — inference BatchNorm as an fp32 per-channel scale and shift,
+    // the residual added BEFORE the ReLU (CLIP's ResNet bottlenecks, clip/model.py:39-52); bias is not read
+    const float* bn_a;      // [N]
+    const float* bn_s;      // [N]
+    const half_t* res16;    // [M][ldo] (nullable)
+    int bn_relu;            // 1: ReLU, 0: none
 };

@@ -108,9 +108,17 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
         REQUIRE(cfg->mbstd_group >= 2 && cfg->mbstd_group <= 8 && cfg->batch_size % cfg->mbstd_group == 0, GLASS_ERR_ARG,
                 "batch_size must be a multiple of mbstd_group (modules.py:716)");
     }
-    if (int grc = glass_clip_geometry_supported(cfg->clip_width, cfg->clip_layers, cfg->clip_heads, cfg->clip_patch, cfg->clip_res,
-                                                cfg->clip_embed))
-        return grc;
+    if (cfg->clip_arch == 1) {       // ModifiedResNet: its own rule, and the shared fields as include/glass.h defines them for it
+        if (int grc = glass_clip_resnet_supported(cfg->clip_rn_layers, cfg->clip_width, cfg->clip_res, cfg->clip_embed)) return grc;
+        const int nb = cfg->clip_rn_layers[0] + cfg->clip_rn_layers[1] + cfg->clip_rn_layers[2] + cfg->clip_rn_layers[3];
+        REQUIRE(cfg->clip_heads == cfg->clip_width / 2 && cfg->clip_patch == 32 && cfg->clip_layers == nb, GLASS_ERR_ARG,
+                "CLIP ResNet: clip_heads must be width * 32 / 64, clip_patch 32 and clip_layers the sum of clip_rn_layers");
+    } else {
+        REQUIRE(cfg->clip_arch == 0, GLASS_ERR_ARG, "clip_arch must be 0 (ViT) or 1 (ModifiedResNet)");
+        if (int grc = glass_clip_geometry_supported(cfg->clip_width, cfg->clip_layers, cfg->clip_heads, cfg->clip_patch, cfg->clip_res,
+                                                    cfg->clip_embed))
+            return grc;
+    }
     REQUIRE(cfg->noise_mode >= 0 && cfg->noise_mode <= 2, GLASS_ERR_ARG, "noise_mode must be 0,1,2");
     int bg_res = 0;
     if (cfg->generator == GLASS_GEN_BIGGAN_DEEP) {
@@ -325,6 +333,7 @@ static int alloc_buffers(glass_engine* e) {
     if ((rc = dev_alloc(e, &e->d_attn, (size_t)P * T * W))) return rc;
     if ((rc = dev_alloc(e, &e->d_hid, (size_t)P * T * 4 * W))) return rc;
     if ((rc = dev_alloc(e, &e->d_cls, (size_t)P * W))) return rc;
+    if ((rc = alloc_clip_resnet(e))) return rc;
     if ((rc = dev_alloc(e, &e->d_feat, (size_t)P * c.clip_embed))) return rc;
     if ((rc = dev_alloc(e, &e->d_sim, (size_t)P))) return rc;
     if ((rc = dev_alloc(e, &e->d_dis, (size_t)P))) return rc;

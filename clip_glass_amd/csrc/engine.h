@@ -55,6 +55,32 @@ struct ClipBlock {
     float *b_qkv, *b_out, *b_fc, *b_proj;
 };
 
+// CLIP's ModifiedResNet image tower (clip.cpp, clip_resnet.hip; clip/model.py:9-149)
+struct RnConv {            // a convolution and the BatchNorm behind it
+    int cin = 0, cout = 0, ks = 1;
+    half_t* w = nullptr;   // [ks*ks][cout][cin] fp16, un-scaled: BatchNorm is NOT folded in
+    float *a = nullptr, *s = nullptr;   // [cout] fp32: A = gamma / sqrt(var + 1e-5), S = beta - mean * A
+};
+struct RnBlock {           // Bottleneck: 1x1 - 3x3 - [avgpool] - 1x1, + identity or BN(1x1(avgpool(x)))
+    int res_in = 0, stride = 1;
+    bool has_down = false;
+    RnConv c1, c2, c3, down;
+};
+struct RnState {
+    half_t* stem_w1 = nullptr;          // [27][w/2]
+    float *stem_a1 = nullptr, *stem_s1 = nullptr;
+    RnConv stem2, stem3;
+    std::vector<RnBlock> blocks;
+    float *pos = nullptr, *b_qkv = nullptr, *cproj_wt = nullptr, *cproj_b = nullptr;   // cproj_wt [C][embed]
+    half_t* w_qkv = nullptr;            // [3 C][C]: q_proj | k_proj | v_proj
+    // activations: every buffer holds `cap` halfs — the largest map of the tower for max_pop images, at least 64 rows of the widest one
+    // (a GEMM of fewer than 64 rows runs on rows padded to 64 in these buffers)
+    half_t* buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    half_t *tok = nullptr, *qkv = nullptr, *att = nullptr;
+    float* cls = nullptr;
+    size_t cap = 0;
+};
+
 // BigGAN-deep generator (biggan.cpp)
 struct BgBlock {   // GenBlock: bn0-relu-conv1x1 / bn1-relu-[up]-conv3x3 / bn2-relu-conv3x3 / bn3-relu-conv1x1 + skip
     int cin, cout, mid, up, res_in;
@@ -142,6 +168,7 @@ struct glass_engine {
     float *c_lnpost_g = nullptr, *c_lnpost_b = nullptr, *c_proj = nullptr;
     std::vector<ClipBlock> cblk;
     ResizeTapsDev rz;          // clip_resize 1 / 2: the antialiased resize's tap table (finalize_preprocess)
+    RnState rn;                // clip_arch 1: the ResNet tower instead of c_* / cblk
     // GPT-2 (optional, fp32; config C5)
     struct Gpt2Block { float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *w_qkv, *b_qkv, *w_o, *b_o, *w_fc, *b_fc, *w_pr, *b_pr; };
     std::vector<Gpt2Block> gblk;
@@ -344,6 +371,14 @@ void run_clip_embed(glass_engine* e, int P);
 void run_clip_layers(glass_engine* e, int P, int l0, int l1);
 void run_clip_head(glass_engine* e, int P);
 void run_clip(glass_engine* e, int P);
+int clip_n_layers(const glass_engine* e);     // what run_clip_layers counts: transformer blocks (ViT) or bottlenecks (ResNet)
+int alloc_clip_resnet(glass_engine* e);       // the ResNet tower's activation buffers (clip_arch 1)
+// The ResNet tower's GEMMs as the walker sets them up (shared with the diagnostic ops).  1 x 1 conv + BN (+ res) (+ ReLU) over M rows: fewer than
+// 64 rows are run as 64 — x, res and y must hold max(M, 64) rows.  3 x 3 (stride 1, pad 1, Cin % 64 == 0) + BN + ReLU through the implicit patch matrix.
+GemmParams rn_gemm_1x1(const half_t* x, const RnConv& c, int M, int cand_rows, const half_t* res, int relu, half_t* y);
+GemmParams rn_gemm_3x3(const half_t* x, const RnConv& c, int B, int H, int W, half_t* y);
+// reference conv weight [cout][cin][ks][ks] -> [ks*ks][cout][cin] fp16
+std::vector<_Float16> rn_pack_conv(const float* w, int cout, int cin, int ks);
 // Stream mode 2: the patch embedding and this many layers of CLIP's image tower run on the MAIN stream, alone on the chip, before the
 // discriminator starts; the rest of the tower runs on the second stream beside it.  Forked right behind the resize (rounds 2-5), the tower's
 // first launch raced the discriminator's first kernel — a persistent kernel that fills every CU for 3.9 ms — and lost about every other

@@ -12,7 +12,8 @@
 
 // GATHER (round 6): the A operand is the IMPLICIT patch matrix of a convolution (GemmParams::g_*): the loader walks x itself, the im2col
 // pass of conv_gemm.hip (a 9x copy of the map to HBM and back) disappears for the layers without an activation-side style
-template <int BN, bool GATHER = false>
+// BNE: the BatchNorm epilogue (GemmParams mode 5) as instances of their own — the instances of the other modes carry none of it
+template <int BN, bool GATHER = false, bool BNE = false>
 __global__ __launch_bounds__(256, 2) void gemm_tiled_kernel(GemmParams p) {
     if (p.batch > 1) {   // batched problems (BigGAN self-attention): one z-slice per problem
         p.a += (long long)blockIdx.z * p.a_bs;
@@ -119,6 +120,44 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_kernel(GemmParams p) {
                 for (int j = 0; j < NJ; ++j) acc[i][j] = mfma32(wf[j], xf[i], acc[i][j]);
         }
     }
+    if (BNE) {   // out16 = act(v * A[n] + S[n] (+ res16[m][n])): scale / shift quads up front, the row's residual quads as one batch of loads
+        f4 aq[NJ][4], sq[NJ][4];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                aq[j][g] = *(const f4*)(p.bn_a + n0 + wn * (BN / 2) + j * 32 + 8 * g + 4 * kh);
+                sq[j][g] = *(const f4*)(p.bn_s + n0 + wn * (BN / 2) + j * 32 + 8 * g + 4 * kh);
+            }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int m = m0 + wm * 64 + i * 32 + lr;
+            if (m >= p.M) continue;
+            h4 rq[NJ][4];
+            if (p.res16) {
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        rq[j][g] = *(const h4*)(p.res16 + (long long)m * p.ldo + n0 + wn * (BN / 2) + j * 32 + 8 * g + 4 * kh);
+            }
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int n = n0 + wn * (BN / 2) + j * 32 + 8 * g + 4 * kh;
+                    h4 o;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        float v = acc[i][j][g * 4 + q] * aq[j][g][q] + sq[j][g][q];
+                        if (p.res16) v += (float)rq[j][g][q];
+                        o[q] = (half_t)(p.bn_relu ? fmaxf(v, 0.f) : v);
+                    }
+                    *(h4*)(p.out16 + (long long)m * p.ldo + n) = o;
+                }
+        }
+        return;
+    }
     // epilogue: lane = output row m, quads of 4 consecutive n.  Bias quads and (mode 2) the residual quads of a row are
     // fetched as one batch of unconditional loads: a load consumed right after it is issued costs a full round trip, and
     // there were two of them per accumulator quad here.
@@ -185,6 +224,26 @@ const char* launch_gemm_tiled(const GemmParams& p, hipStream_t st) {
     const long long gz_n = p.cand_batch ? GLASS_NOMINAL_POP : gz;
     const bool fills = gx_n * (p.N / 128) * gz_n >= 256;
     if (p.g_on && (!p.kpt || p.kpt != p.g_cin || p.g_cin % 64 != 0)) return nullptr;      // (a K step must sit inside one tap)
+    if (p.mode == 5) {      // BatchNorm epilogue: the instances built for it
+        if (!p.bn_a || !p.bn_s || !p.out16 || gz != 1 || p.ld) return nullptr;
+        if (p.N % 128 == 0 && fills) {
+            const dim3 grid(8 * ((gx * (p.N / 128) + 7) / 8), 1, 1);
+            if (p.g_on) {
+                hipLaunchKernelGGL((gemm_tiled_kernel<128, true, true>), grid, dim3(256), 0, st, p);
+                return "gemm_tiled_kernel<128,true,bn>";
+            }
+            hipLaunchKernelGGL((gemm_tiled_kernel<128, false, true>), grid, dim3(256), 0, st, p);
+            return "gemm_tiled_kernel<128,false,bn>";
+        }
+        if (p.N % 64 != 0) return nullptr;
+        const dim3 grid(8 * ((gx * (p.N / 64) + 7) / 8), 1, 1);
+        if (p.g_on) {
+            hipLaunchKernelGGL((gemm_tiled_kernel<64, true, true>), grid, dim3(256), 0, st, p);
+            return "gemm_tiled_kernel<64,true,bn>";
+        }
+        hipLaunchKernelGGL((gemm_tiled_kernel<64, false, true>), grid, dim3(256), 0, st, p);
+        return "gemm_tiled_kernel<64,false,bn>";
+    }
     if (p.N % 128 == 0 && fills) {
         if (p.g_on) {
             hipLaunchKernelGGL((gemm_tiled_kernel<128, true>), dim3(8 * ((gx * (p.N / 128) + 7) / 8), 1, gz), dim3(256), 0, st, p);

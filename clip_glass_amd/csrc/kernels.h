@@ -135,6 +135,18 @@ void launch_attention(const half_t* qkv, int n_img, int L, int heads, int hd, in
 void launch_cosine(const float* feat, const float* target, int P, int D, float* sim, hipStream_t st);
 void launch_assemble_F(const float* sim, const float* dis, int P, int n_obj, float* F, hipStream_t st);
 
+// --- CLIP's ResNet towers (clip_resnet.hip); BatchNorm = fp32 per-channel scale bn_a and shift bn_s in the epilogue ---------------------
+// stem conv1 (3 x 3 stride 2 pad 1, 3 -> C1, + BN + ReLU) from the 32-pixel patch operand of an S x S image -> [B][S/2][S/2][C1]; w [27][C1] fp16,
+// row (ci, ky, kx).  false: refused (S % 32, C1 % 8)
+bool launch_rn_stem_conv1(const half_t* img, const half_t* w, const float* bn_a, const float* bn_s, int B, int S, int C1, half_t* y, hipStream_t st);
+// 3 x 3 stride 1 pad 1 + BN + ReLU for Cin % 16 == 0, Cout % 32 == 0 (the stem's conv2 / conv3); w [9][Cout][Cin].  nullptr: refused
+const char* launch_rn_conv3x3(const half_t* x, const half_t* w, const float* bn_a, const float* bn_s, int B, int H, int W, int Cin, int Cout, half_t* y,
+                              hipStream_t st);
+bool launch_rn_avgpool2(const half_t* x, int B, int H, int W, int C, half_t* y, hipStream_t st);      // AvgPool2d(2), NHWC; false: odd side or C % 8
+// tok [B][HW + 1][C] = [mean over HW ; the HW pixels] + pos [HW + 1][C]
+void launch_rn_attnpool_tokens(const half_t* x, const float* pos, int B, int HW, int C, half_t* tok, hipStream_t st);
+void launch_rn_token0_rows(const half_t* att, int B, int T, int C, float* out, hipStream_t st);      // out [B][C] fp32 = att[b T][:]
+
 // --- BigGAN-deep glue (biggan_kernels.hip) ---------------------------------------------------------
 void launch_bg_cond(const float* x, int P, int L, int zd, int nc, const float* et, float* cond, hipStream_t st);
 void launch_bg_bn_tables(float* tab, int P, int C, const float* inv_std, const float* mean, const float* prebias,

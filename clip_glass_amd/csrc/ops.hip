@@ -893,6 +893,90 @@ __global__ void mfma_probe_kernel(const half_t* a, const half_t* b, float* d) {
     acc = mfma32(av, bv, acc);
     for (int reg = 0; reg < 16; ++reg) d[mfma32_row(reg, lane) * 32 + (lane & 31)] = acc[reg];
 }
+// ---- CLIP's ResNet towers ----
+extern "C" int glass_op_rn_avgpool(int32_t device, int32_t B, int32_t H, int32_t W, int32_t C, const float* x, float* out) {
+    OPREQ(x && out && B > 0 && H > 0 && W > 0 && C > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t no = (size_t)B * (H / 2) * (W / 2) * C;
+    half_t* dx = dv.up16(x, (size_t)B * H * W * C);
+    half_t* dy = dv.alloc<half_t>(no);
+    OPREQ(dx && dy, "allocation failed");
+    OPREQ(launch_rn_avgpool2(dx, B, H, W, C, dy, 0), "rn_avgpool2: refused (even H and W, C a multiple of 8)");
+    int rc = finish();
+    return rc ? rc : down16(out, dy, no);
+}
+
+extern "C" int glass_op_rn_stem_conv1(int32_t device, int32_t B, int32_t S, int32_t C1, const float* img, const float* w, const float* bn_a,
+                                      const float* bn_s, float* out) {
+    OPREQ(img && w && bn_a && bn_s && out && B > 0 && S > 0 && S % 32 == 0 && C1 > 0, "bad argument (S a multiple of 32)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t ni = (size_t)B * 3 * S * S, no = (size_t)B * (S / 2) * (S / 2) * C1;
+    std::vector<_Float16> wt((size_t)27 * C1);
+    for (int o = 0; o < C1; ++o)
+        for (int k = 0; k < 27; ++k) wt[(size_t)k * C1 + o] = (_Float16)w[(size_t)o * 27 + k];
+    float* dimg = dv.up32(img, ni);
+    half_t* dp = dv.alloc<half_t>(ni);
+    half_t* dw = dv.up16v(wt);
+    float *da = dv.up32(bn_a, C1), *ds = dv.up32(bn_s, C1);
+    half_t* dy = dv.alloc<half_t>(no);
+    OPREQ(dimg && dp && dw && da && ds && dy, "allocation failed");
+    launch_image_patches(dimg, B, S, 32, 3072, dp, 0);
+    OPREQ(launch_rn_stem_conv1(dp, dw, da, ds, B, S, C1, dy, 0), "rn_stem_conv1: refused (C1 a multiple of 8)");
+    int rc = finish();
+    return rc ? rc : down16(out, dy, no);
+}
+
+extern "C" int glass_op_rn_conv_bn(int32_t device, int32_t form, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t relu,
+                                   const float* x, const float* w, const float* bn_a, const float* bn_s, const float* res, float* out) {
+    OPREQ(x && w && bn_a && bn_s && out && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "bad argument");
+    OPREQ((form == 0 && (KS == 1 || KS == 3)) || (form == 1 && KS == 3), "rn_conv_bn: form 0 takes KS 1 or 3, form 1 KS 3");
+    OPREQ(KS == 1 || (relu && !res), "rn_conv_bn: the 3 x 3 forms are conv + BN + ReLU without a residual");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const int M = B * H * W, Mp = std::max(M, 64);
+    RnConv c;
+    c.cin = Cin; c.cout = Cout; c.ks = KS;
+    c.w = dv.up16v(rn_pack_conv(w, Cout, Cin, KS));
+    c.a = dv.up32(bn_a, Cout);
+    c.s = dv.up32(bn_s, Cout);
+    // M rows of data in buffers of max(M, 64) rows, the tail zero: what the engine's buffers hold
+    half_t* dx = dv.alloc<half_t>((size_t)Mp * Cin);
+    half_t* dr = res ? dv.alloc<half_t>((size_t)Mp * Cout) : nullptr;
+    half_t* dy = dv.alloc<half_t>((size_t)Mp * Cout);
+    OPREQ(c.w && c.a && c.s && dx && dy && (!res || dr), "allocation failed");
+    auto fill = [&](half_t* d, const float* src, size_t rowlen) {
+        std::vector<_Float16> h((size_t)Mp * rowlen, (_Float16)0.f);
+        for (size_t i = 0; i < (size_t)M * rowlen; ++i) h[i] = (_Float16)src[i];
+        return hipMemcpy(d, h.data(), h.size() * sizeof(half_t), hipMemcpyHostToDevice);
+    };
+    GLASS_HIP(fill(dx, x, Cin));
+    if (res) GLASS_HIP(fill(dr, res, Cout));
+    if (form == 1) {
+        OPREQ(launch_rn_conv3x3(dx, c.w, c.a, c.s, B, H, W, Cin, Cout, dy, 0) != nullptr, "rn_conv3x3: refused (Cin % 16, Cout % 32)");
+    } else {
+        const GemmParams g = KS == 1 ? rn_gemm_1x1(dx, c, M, H * W, dr, relu, dy) : rn_gemm_3x3(dx, c, B, H, W, dy);
+        OPREQ(launch_gemm_tiled(g, 0) != nullptr, "rn_conv_bn: gemm_tiled refused the shape (Cin and Cout multiples of 64)");
+    }
+    int rc = finish();
+    return rc ? rc : down16(out, dy, (size_t)M * Cout);
+}
+
+extern "C" int glass_op_rn_tokens(int32_t device, int32_t B, int32_t HW, int32_t C, const float* x, const float* pos, float* out) {
+    OPREQ(x && pos && out && B > 0 && HW > 0 && C > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t no = (size_t)B * (HW + 1) * C;
+    half_t* dx = dv.up16(x, (size_t)B * HW * C);
+    float* dp = dv.up32(pos, (size_t)(HW + 1) * C);
+    half_t* dy = dv.alloc<half_t>(no);
+    OPREQ(dx && dp && dy, "allocation failed");
+    launch_rn_attnpool_tokens(dx, dp, B, HW, C, dy, 0);
+    int rc = finish();
+    return rc ? rc : down16(out, dy, no);
+}
+
 extern "C" int glass_op_mfma_probe(int32_t device, const float* a, const float* b, float* d) {
     OPREQ(a && b && d, "null argument");
     GLASS_HIP(hipSetDevice(device));

@@ -32,6 +32,12 @@ class GlassConfig(C.Structure):
                 ("clip_resize", C.c_int32), ("clip_normalize", C.c_int32)]
 
 
+class GlassConfigResnet(C.Structure):
+    """glass_config as the library defines it now: GlassConfig's fields, then the ResNet tower's, appended as clip_resize was (zero: a ViT).
+    GlassConfig itself stays the struct up to clip_normalize — what a library built before the ResNet towers reads of this one."""
+    _fields_ = GlassConfig._fields_ + [("clip_arch", C.c_int32), ("clip_rn_layers", C.c_int32 * 4)]
+
+
 class GlassNoise(C.Structure):
     _fields_ = [("n_minibatches", C.c_int32), ("n_layers", C.c_int32),
                 ("planes", C.POINTER(C.POINTER(C.c_float)))]
@@ -58,11 +64,13 @@ def load_library(path=None):
     fp = C.POINTER(C.c_float)
     lib.glass_last_error.restype = C.c_char_p
     lib.glass_version.restype = C.c_char_p
-    lib.glass_engine_create.argtypes = [C.POINTER(GlassConfig), C.POINTER(C.c_void_p)]
+    lib.glass_engine_create.argtypes = [C.POINTER(GlassConfigResnet), C.POINTER(C.c_void_p)]
     if hasattr(lib, "glass_clip_geometry_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
         lib.glass_clip_geometry_supported.argtypes = [C.c_int32] * 6
     if hasattr(lib, "glass_clip_preprocess_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
         lib.glass_clip_preprocess_supported.argtypes = [C.c_int32] * 4
+    if hasattr(lib, "glass_clip_resnet_supported"):     # (absent from older A/B builds loaded through GLASS_LIB)
+        lib.glass_clip_resnet_supported.argtypes = [C.POINTER(C.c_int32)] + [C.c_int32] * 3
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -119,6 +127,18 @@ def clip_preprocess_supported(gen_res, clip_res, clip_resize, clip_normalize):
     return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
 
 
+def clip_resnet_supported(geometry):
+    """(ok, message) for a CLIP ResNet image tower (layers4, width, input_res, embed): the library's own rule, the one
+    glass_engine_create applies.  Host only: needs the built library, not a GPU."""
+    lib = load_library()
+    layers, width, res, embed = geometry
+    if len(layers) != 4:
+        return False, "unsupported CLIP ResNet geometry: layers must hold four stage depths, got %r" % (tuple(layers),)
+    arr = (C.c_int32 * 4)(*[int(v) for v in layers])
+    rc = lib.glass_clip_resnet_supported(arr, int(width), int(res), int(embed))
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
 def device_info(device=0):
     lib = load_library()
     name = C.create_string_buffer(256)
@@ -133,12 +153,14 @@ class Engine:
 
     def __init__(self, channels, latent_size=512, mapping_layers=8, batch_size=4, use_discriminator=True,
                  n_obj=2, max_pop=64, chunk=0, clip=(768, 12, 12, 32, 224, 512), noise_mode=1, noise_seed=0,
-                 mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0):
+                 mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0, clip_resnet=None):
         """`biggan` = dict(layers=[(up, in_mult, out_mult), ...], attention_pos, ch, z_dim, num_classes, n_stats, eps,
         truncation) selects the BigGAN-deep generator (channels must then be empty, no discriminator).
-        clip_resize / clip_normalize: how a generated image is prepared for CLIP (include/glass.h); (0, 0) is the reference's way."""
+        clip_resize / clip_normalize: how a generated image is prepared for CLIP (include/glass.h); (0, 0) is the reference's way.
+        clip_resnet = (layers4, width, res, embed) selects CLIP's ModifiedResNet image tower (RN50: ((3, 4, 6, 3), 64, 224, 1024));
+        `clip` is ignored then."""
         self.lib = load_library()
-        cfg = GlassConfig()
+        cfg = GlassConfigResnet()
         cfg.device = device
         if biggan is not None:
             layers = list(biggan["layers"])
@@ -159,6 +181,14 @@ class Engine:
         cfg.latent_size, cfg.mapping_layers, cfg.batch_size = latent_size, mapping_layers, batch_size
         cfg.mbstd_group, cfg.use_discriminator, cfg.n_obj = mbstd_group, int(bool(use_discriminator)), n_obj
         cfg.max_pop, cfg.chunk = max_pop, chunk
+        if clip_resnet is not None:
+            layers, width, res, embed = clip_resnet
+            if len(layers) != 4:
+                raise ValueError("clip_resnet: layers must hold four stage depths, got %r" % (tuple(layers),))
+            cfg.clip_arch = 1
+            for i, n in enumerate(layers):
+                cfg.clip_rn_layers[i] = int(n)
+            clip = (int(width), sum(int(n) for n in layers), int(width) * 32 // 64, 32, int(res), int(embed))
         (cfg.clip_width, cfg.clip_layers, cfg.clip_heads, cfg.clip_patch, cfg.clip_res, cfg.clip_embed) = clip
         cfg.noise_mode, cfg.noise_seed = noise_mode, noise_seed
         cfg.clip_resize, cfg.clip_normalize = int(clip_resize), int(clip_normalize)

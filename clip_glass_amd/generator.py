@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import synth
-from .engine import Engine, clip_geometry_supported
+from .engine import Engine, clip_geometry_supported, clip_resnet_supported
 from .utils import save_grid, save_image
 
 CLIP_VIT_B32 = (768, 12, 12, 32, 224, 512)
@@ -30,6 +30,17 @@ CLIP_TEXT_MODELS = {
     "ViT-L/14@336": dict(width=768, layers=12),
 }
 DEFAULT_CLIP_MODEL = "ViT-B/32"
+# CLIP's ResNet image towers (clip/model.py:92-149), named on their own (`config.clip_resnet` / `--clip-resnet`): (layers per stage, stem
+# width, input_res, embed) as clip/model.py:373-379 derives them from the released checkpoints, and the text tower of each.  The engine
+# runs any such tower whose width is a multiple of 64 (glass_clip_resnet_supported): RN50x4 / x16 (widths 80 / 96) are not among them.
+CLIP_RESNET_MODELS = {
+    "RN50": ((3, 4, 6, 3), 64, 224, 1024),
+    "RN101": ((3, 4, 23, 3), 64, 224, 512),
+}
+CLIP_RESNET_TEXT_MODELS = {
+    "RN50": dict(width=512, layers=12),
+    "RN101": dict(width=512, layers=12),
+}
 # How a generated image is prepared for CLIP, `config.clip_preprocess` / `--clip-preprocess` -> (clip_resize, clip_normalize) of
 # include/glass.h.  "reference": generator.py:45, a point-sampled bilinear resize and no normalisation — what every parity number of this
 # project is quoted for.  "antialias": the same bilinear filter widened to the down-scale, so every input pixel counts.  "clip": the transform
@@ -62,8 +73,52 @@ def clip_preprocess_fields(name):
     return CLIP_PREPROCESS[name]
 
 
+def clip_resnet_geometry(name):
+    """Geometry of a named ResNet image tower; ValueError lists the names when it is not one of them."""
+    if name not in CLIP_RESNET_MODELS:
+        raise ValueError("unknown CLIP ResNet model %r: expected one of %s" % (name, ", ".join(sorted(CLIP_RESNET_MODELS))))
+    return CLIP_RESNET_MODELS[name]
+
+
+def clip_resnet_name(geometry):
+    """Name of the ResNet tower with this geometry, or None."""
+    geometry = normalize_resnet_geometry(geometry)
+    for name, g in CLIP_RESNET_MODELS.items():
+        if g == geometry:
+            return name
+    return None
+
+
+def normalize_resnet_geometry(geometry):
+    """(layers4, width, res, embed) as plain ints; ValueError when it is not of that form."""
+    try:
+        layers, width, res, embed = geometry
+        layers = tuple(int(v) for v in layers)
+    except (TypeError, ValueError):
+        raise ValueError("a CLIP ResNet geometry is (layers4, width, input_res, embed), got %r" % (geometry,))
+    if len(layers) != 4:
+        raise ValueError("a CLIP ResNet geometry holds four stage depths, got %r" % (layers,))
+    return (layers, int(width), int(res), int(embed))
+
+
+def is_resnet_geometry(geometry):
+    """True for a ResNet tower's (layers4, width, res, embed), False for a ViT's six fields."""
+    return len(geometry) == 4
+
+
+def resnet_engine_fields(geometry):
+    """The six shared glass_config fields of a ResNet tower: (width, bottlenecks, heads, 32, res, embed) (include/glass.h)."""
+    layers, width, res, embed = normalize_resnet_geometry(geometry)
+    return (width, sum(layers), width * 32 // 64, 32, res, embed)
+
+
 def check_clip_geometry(geometry):
     """Raise ValueError with the library's message when the engine cannot run this image tower — before any engine is built."""
+    if is_resnet_geometry(geometry):
+        ok, msg = clip_resnet_supported(geometry)
+        if not ok:
+            raise ValueError("CLIP ResNet image tower %s: %s" % (normalize_resnet_geometry(geometry), msg))
+        return
     ok, msg = clip_geometry_supported(geometry)
     if not ok:
         raise ValueError("CLIP image tower %s: %s" % (tuple(int(v) for v in geometry), msg))
@@ -77,6 +132,23 @@ def clip_geometry_from_state(state):
     grid = round((state["clip.visual.positional_embedding"].shape[0] - 1) ** 0.5)
     layers = len([k for k in state if k.startswith("clip.visual.") and k.endswith(".attn.in_proj_weight")])
     return (width, layers, width // 64, patch, patch * grid, state["clip.visual.proj"].shape[1])
+
+
+def clip_state_is_resnet(state):
+    """A checkpoint decides for itself, as build_model does (clip/model.py:364): no visual.proj means a ModifiedResNet."""
+    return "clip.visual.proj" not in state
+
+
+def clip_resnet_geometry_from_state(state):
+    """(layers4, width, input_res, embed) of a ResNet VISUAL tower, read as clip/model.py:373-379 reads it; the embed dim from the
+    attention pool's output projection (a visual-only state has no text_projection)."""
+    layers = tuple(len(set(k.split(".")[3] for k in state if k.startswith("clip.visual.layer%d." % b))) for b in (1, 2, 3, 4))
+    width = state["clip.visual.layer1.0.conv1.weight"].shape[0]
+    n_tok = state["clip.visual.attnpool.positional_embedding"].shape[0]
+    grid = round((n_tok - 1) ** 0.5)
+    if grid * grid + 1 != n_tok:
+        raise ValueError("clip.visual.attnpool.positional_embedding has %d rows: not a square grid plus one" % n_tok)
+    return (layers, int(width), 32 * grid, int(state["clip.visual.attnpool.c_proj.weight"].shape[0]))
 
 
 def clip_state_from_checkpoint(sd, with_text):
@@ -100,8 +172,25 @@ def _load_clip_state(config, with_text):
         raise RuntimeError("config.clip_weights is not set: pass a CLIP ViT checkpoint (--clip-weights PATH), or "
                            "'synthetic:<seed>' explicitly for tests / benchmarks")
     w = str(w)
+    rn_name, rn_geom = getattr(config, "clip_resnet", None), getattr(config, "clip_resnet_geometry", None)
+    if (rn_name is not None or rn_geom is not None) and (getattr(config, "clip_model", None) is not None
+                                                          or getattr(config, "clip_geometry", None) is not None):
+        raise ValueError("clip_model / clip_geometry (a ViT image tower) and clip_resnet / clip_resnet_geometry (a ResNet one) are both "
+                         "set: choose one")
+    if rn_name is not None:
+        clip_resnet_geometry(rn_name)        # an unknown name fails here, whatever the weights are
     if w.startswith("synthetic"):
         seed = int(w.split(":")[1]) if ":" in w else 0
+        if rn_name is not None or rn_geom is not None:
+            # an explicit clip_resnet_geometry wins over the name, as clip_geometry does for the ViTs
+            geom = normalize_resnet_geometry(clip_resnet_geometry(rn_name) if rn_geom is None else rn_geom)
+            state = synth.make_state(synth.clip_resnet_spec(*geom), seed)
+            if with_text:
+                tg = getattr(config, "clip_text_geometry", None) or (CLIP_RESNET_TEXT_MODELS[rn_name] if rn_geom is None
+                                                                     else dict(width=512, layers=12))
+                state.update(synth.make_state(synth.clip_text_spec(width=tg["width"], layers=tg["layers"],
+                                                                   vocab=tg.get("vocab", 49408), out_dim=geom[3]), seed))
+            return state, geom
         # an explicit clip_geometry wins; otherwise the named model (default ViT-B/32) gives both towers' geometry
         model = getattr(config, "clip_model", None) or DEFAULT_CLIP_MODEL
         geom = getattr(config, "clip_geometry", None)
@@ -119,8 +208,21 @@ def _load_clip_state(config, with_text):
     except RuntimeError:
         sd = torch.load(w, map_location="cpu")
     state = clip_state_from_checkpoint(sd, with_text)
-    geom = clip_geometry_from_state(state)
     model = getattr(config, "clip_model", None)
+    if clip_state_is_resnet(state):      # the checkpoint decides (clip/model.py:364); a name that disagrees is a mistake
+        geom = clip_resnet_geometry_from_state(state)
+        held = "%s %s" % (clip_resnet_name(geom) or "an unnamed ResNet tower", geom)
+        if model is not None:
+            raise ValueError("clip_model %r is a ViT %s, but the checkpoint %s holds %s" % (model, clip_model_geometry(model), w, held))
+        want = None if rn_name is None and rn_geom is None else normalize_resnet_geometry(
+            clip_resnet_geometry(rn_name) if rn_geom is None else rn_geom)
+        if want is not None and want != geom:
+            raise ValueError("clip_resnet %r is %s, but the checkpoint %s holds %s" % (rn_name or "(geometry)", want, w, held))
+        return state, geom
+    geom = clip_geometry_from_state(state)
+    if rn_name is not None or rn_geom is not None:
+        raise ValueError("clip_resnet %r names a ResNet image tower, but the checkpoint %s holds the ViT %s %s"
+                         % (rn_name or "(geometry)", w, clip_model_name(geom) or "an unnamed tower", geom))
     if model is not None and clip_model_geometry(model) != geom:      # the checkpoint decides; a name that disagrees is a mistake
         raise ValueError("clip_model %r is %s, but the checkpoint %s holds %s %s"
                          % (model, clip_model_geometry(model), w, clip_model_name(geom) or "an unnamed tower", geom))
@@ -184,9 +286,9 @@ class Generator:
                                  % (self.clip_preprocess, DEFAULT_CLIP_PREPROCESS))
             clip_state, geom = _load_clip_state(config, True)
             check_clip_geometry(geom)
-            self.clip_geometry = tuple(int(v) for v in geom)
+            tower = self._clip_tower(geom)
             self.engine = Engine([], latent_size=4, mapping_layers=0, batch_size=1, use_discriminator=False, n_obj=1,
-                                 max_pop=pop, clip=geom, noise_mode=0, device=device)
+                                 max_pop=pop, noise_mode=0, device=device, **tower)
             self.engine.load_state(self.model.state)
             self.engine.load_state(clip_state)
             self.engine.finalize()
@@ -194,27 +296,27 @@ class Generator:
             if getattr(config, "target_features", None) is not None:
                 self.image_features = np.asarray(config.target_features, np.float32).reshape(1, -1)
             else:
-                self.image_features = self.engine.encode_image(clip_preprocess(config.target, geom[4])[None])
+                self.image_features = self.engine.encode_image(clip_preprocess(config.target, self.clip_geometry[4])[None])
             from .tokenizer import DEFAULT_BPE, ClipTokenizer
             self.tokenizer = ClipTokenizer(getattr(config, "bpe_path", DEFAULT_BPE))
             return
         need_text = getattr(config, "target_features", None) is None
         clip_state, geom = _load_clip_state(config, need_text)
         check_clip_geometry(geom)        # an unsupported checkpoint fails here, not in generation 1
-        self.clip_geometry = tuple(int(v) for v in geom)
+        tower = self._clip_tower(geom)
         pop = (pop + config.batch_size - 1) // config.batch_size * config.batch_size
         if hasattr(self.model, "geometry"):     # BigGAN-deep (models.py:64-86)
             self.engine = Engine([], batch_size=config.batch_size, max_pop=pop, chunk=getattr(config, "chunk", 0),
-                                 clip=geom, device=device, biggan=self.model.geometry, clip_resize=clip_resize,
-                                 clip_normalize=clip_normalize)
+                                 device=device, biggan=self.model.geometry, clip_resize=clip_resize,
+                                 clip_normalize=clip_normalize, **tower)
         else:
             self.engine = Engine(self.model.channels[::-1], latent_size=config.dim_z,
                                  mapping_layers=getattr(config, "mapping_layers", 8), batch_size=config.batch_size,
                                  use_discriminator=bool(config.use_discriminator and config.problem_args["n_obj"] == 2),
                                  n_obj=config.problem_args["n_obj"], max_pop=pop, chunk=getattr(config, "chunk", 0),
-                                 clip=geom, noise_mode=getattr(config, "noise_mode", 1),
+                                 noise_mode=getattr(config, "noise_mode", 1),
                                  noise_seed=getattr(config, "noise_seed", 0), device=device, clip_resize=clip_resize,
-                                 clip_normalize=clip_normalize)
+                                 clip_normalize=clip_normalize, **tower)
         self.engine.load_state(self.model.state)
         self.engine.load_state(clip_state)
         self.engine.finalize()
@@ -230,6 +332,17 @@ class Generator:
             from .parallel import ShardedEvaluator
             self.sharder = ShardedEvaluator(self.engine, dist, dist.get_rank(), dist.get_world_size(), config.batch_size,
                                             device=device)
+
+    def _clip_tower(self, geom):
+        """Record the chosen image tower (clip_geometry: the engine's six shared fields; clip_resnet: the ResNet tuple or None) and
+        return the Engine keywords that select it."""
+        if is_resnet_geometry(geom):
+            self.clip_resnet = normalize_resnet_geometry(geom)
+            self.clip_geometry = resnet_engine_fields(geom)
+            return dict(clip_resnet=self.clip_resnet)
+        self.clip_resnet = None
+        self.clip_geometry = tuple(int(v) for v in geom)
+        return dict(clip=self.clip_geometry)
 
     def clip_similarity_texts(self, texts):
         """generator.py:52-59 (img2txt branch): tokenize -> encode_text -> cosine vs the target image feature;

@@ -534,6 +534,55 @@ def bg_tail(h, x0, w3, b3, bn_a, bn_s, rgb_w, rgb_b, device=0):
     return y
 
 
+# ---- CLIP's ResNet towers (glass_op_rn_*): each piece as the tower's walker launches it; BatchNorm as fp32 scale bn_a / shift bn_s ----
+def rn_avgpool(x, device=0):
+    """AvgPool2d(2) of x [B,H,W,C] -> [B,H/2,W/2,C]."""
+    lib = load_library()
+    x = _f32(x)
+    B, H, W, Cc = x.shape
+    out = np.empty((B, H // 2, W // 2, Cc), np.float32)
+    lib.glass_op_rn_avgpool.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_float)] * 2
+    _check(lib, lib.glass_op_rn_avgpool(device, B, H, W, Cc, _fp(x), _fp(out)))
+    return out
+
+
+def rn_stem_conv1(img, w, bn_a, bn_s, device=0):
+    """img [B,3,S,S], w [C1,3,3,3] -> relu(bn(conv 3x3 stride 2 pad 1)) [B,S/2,S/2,C1], read through the 32-pixel patch operand."""
+    lib = load_library()
+    img, w, bn_a, bn_s = _f32(img), _f32(w), _f32(bn_a), _f32(bn_s)
+    B, S, C1 = img.shape[0], img.shape[2], w.shape[0]
+    out = np.empty((B, S // 2, S // 2, C1), np.float32)
+    lib.glass_op_rn_stem_conv1.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_float)] * 5
+    _check(lib, lib.glass_op_rn_stem_conv1(device, B, S, C1, _fp(img), _fp(w), _fp(bn_a), _fp(bn_s), _fp(out)))
+    return out
+
+
+def rn_conv_bn(x, w, bn_a, bn_s, res=None, relu=True, form=0, device=0):
+    """act(conv(x, w) * bn_a + bn_s (+ res)), x [B,H,W,Cin], w [Cout,Cin,KS,KS] (KS 1 or 3, stride 1, pad KS // 2).  form 0: gemm_tiled as the
+    bottlenecks run it; form 1: the stem's 3 x 3 kernel."""
+    lib = load_library()
+    x, w, bn_a, bn_s = _f32(x), _f32(w), _f32(bn_a), _f32(bn_s)
+    B, H, W, Cin = x.shape
+    Cout, KS = w.shape[0], w.shape[2]
+    r, rp = _opt(res)
+    out = np.empty((B, H, W, Cout), np.float32)
+    lib.glass_op_rn_conv_bn.argtypes = [C.c_int32] * 9 + [C.POINTER(C.c_float)] * 6
+    _check(lib, lib.glass_op_rn_conv_bn(device, int(form), B, H, W, Cin, Cout, KS, int(bool(relu)), _fp(x), _fp(w), _fp(bn_a), _fp(bn_s), rp,
+                                        _fp(out)))
+    return out
+
+
+def rn_tokens(x, pos, device=0):
+    """x [B,HW,C], pos [HW+1,C] -> the attention pool's tokens [B,HW+1,C]."""
+    lib = load_library()
+    x, pos = _f32(x), _f32(pos)
+    B, HW, Cc = x.shape
+    out = np.empty((B, HW + 1, Cc), np.float32)
+    lib.glass_op_rn_tokens.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_float)] * 3
+    _check(lib, lib.glass_op_rn_tokens(device, B, HW, Cc, _fp(x), _fp(pos), _fp(out)))
+    return out
+
+
 def mfma_probe(a, b, device=0):
     lib = load_library()
     a, b = _f32(a), _f32(b)

@@ -14,7 +14,7 @@ import pickle
 import numpy as np
 
 from .config import get_config
-from .generator import CLIP_MODELS, CLIP_PREPROCESS
+from .generator import CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS
 from .operators import get_operators
 from .problem import GenerationProblem
 from . import search
@@ -31,10 +31,14 @@ def build_parser():
     # additions (no checkpoints / vocab in this environment)
     p.add_argument("--weights", type=str, default=None, help="directory with G.pth/D.pth, or synthetic:<seed>")
     p.add_argument("--clip-weights", type=str, default=None,
-                   help="a CLIP ViT checkpoint (ViT-B-32.pt, ViT-B-16.pt, ViT-L-14.pt, ...: the geometry is read from it), or synthetic:<seed>")
+                   help="a CLIP checkpoint (ViT-B-32.pt, ViT-B-16.pt, ViT-L-14.pt, RN50.pt, RN101.pt ...: the tower and its geometry are read from it), "
+                        "or synthetic:<seed>")
     p.add_argument("--clip-model", type=str, default=None, choices=sorted(CLIP_MODELS),
                    help="CLIP image tower: selects the geometry of synthetic weights (default ViT-B/32); with a checkpoint it must "
                         "agree with what the checkpoint holds")
+    p.add_argument("--clip-resnet", type=str, default=None, choices=sorted(CLIP_RESNET_MODELS),
+                   help="CLIP ResNet image tower instead of a ViT: selects the geometry of synthetic weights; with a checkpoint (RN50.pt, "
+                        "RN101.pt: detected by their keys) it must agree with what the checkpoint holds.  Not together with --clip-model")
     p.add_argument("--clip-preprocess", type=str, default=None, choices=list(CLIP_PREPROCESS),
                    help="how a generated image is prepared for CLIP: reference (default: the reference's point-sampled bilinear resize, no "
                         "normalisation), antialias (antialiased bilinear resize), clip (CLIP's own transform: antialiased bicubic resize + "
@@ -55,7 +59,7 @@ def main(argv=None, extra_config=None):
     config = build_parser().parse_args(argv)
     over = {k: v for k, v in vars(config).items() if v is not None}
     vars(config).update(get_config(config.config))                             # run.py:25
-    for k in ("weights", "clip_weights", "clip_model", "clip_preprocess", "bpe_path", "pop_size", "stochastic"):
+    for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "bpe_path", "pop_size", "stochastic"):
         if k in over:
             setattr(config, k, over[k])
     if extra_config:

@@ -133,6 +133,46 @@ def clip_visual_spec(width=768, layers=12, patch=32, res=224, out_dim=512):
     return spec
 
 
+def clip_resnet_spec(layers=(3, 4, 6, 3), width=64, res=224, out_dim=1024):
+    """(name, shape, kind) of CLIP's ModifiedResNet visual tower under the reference's keys (clip/model.py:9-149).  Convolutions are
+    He-initialised and stored as fp16; every BatchNorm has non-trivial statistics (mean != 0, var != 1, gain != 1) so that a wrong scale /
+    shift epilogue cannot pass.  The gains of each bottleneck's last BatchNorm (0.3) and of the downsample branch (0.7) are damped, as a
+    trained residual network's are: with gains of 1 the activations of 16 stacked blocks grow past 100 and fp16 storage alone costs more
+    than the feature bar."""
+    spec = []
+
+    def bn(p, c, gain=1.0):
+        return [(p + ".weight", (c,), ("bn_w", gain)), (p + ".bias", (c,), ("n", 0.1)),
+                (p + ".running_mean", (c,), ("n", 0.2)), (p + ".running_var", (c,), "bn_var"),
+                (p + ".num_batches_tracked", (), "count")]
+
+    def conv(p, cout, cin, ks):
+        return [(p + ".weight", (cout, cin, ks, ks), ("n16", (2.0 / (cin * ks * ks)) ** 0.5))]
+
+    v = "clip.visual."
+    for i, (cin, cout) in enumerate([(3, width // 2), (width // 2, width // 2), (width // 2, width)]):
+        spec += conv(v + "conv%d" % (i + 1), cout, cin, 3) + bn(v + "bn%d" % (i + 1), cout)
+    inplanes = width
+    for st, n in enumerate(layers):
+        planes = width << st
+        for i in range(n):
+            p = v + "layer%d.%d." % (st + 1, i)
+            stride = 2 if (st > 0 and i == 0) else 1
+            spec += conv(p + "conv1", planes, inplanes, 1) + bn(p + "bn1", planes)
+            spec += conv(p + "conv2", planes, planes, 3) + bn(p + "bn2", planes)
+            spec += conv(p + "conv3", 4 * planes, planes, 1) + bn(p + "bn3", 4 * planes, 0.3)
+            if stride > 1 or inplanes != 4 * planes:
+                spec += conv(p + "downsample.0", 4 * planes, inplanes, 1) + bn(p + "downsample.1", 4 * planes, 0.7)
+            inplanes = 4 * planes
+    C = 32 * width
+    s = C ** -0.5
+    a = v + "attnpool."
+    spec.append((a + "positional_embedding", ((res // 32) ** 2 + 1, C), ("n", s)))
+    for name, n_out in (("q_proj", C), ("k_proj", C), ("v_proj", C), ("c_proj", out_dim)):
+        spec += [(a + name + ".weight", (n_out, C), ("n16", s)), (a + name + ".bias", (n_out,), ("n16", 0.02))]
+    return spec
+
+
 def clip_text_spec(width=512, layers=12, ctx=77, vocab=49408, out_dim=512):
     """(name, shape, kind) of the CLIP text tower (clip/model.py:277-290); init stds follow
     OpenAI's initialize_parameters (not in the vendored file)."""
@@ -180,6 +220,8 @@ def make_tensor(seed, name, shape, kind, map_lr_mul=0.01):
         k, std = kind
         if k == "ln_w":
             return normal(seed, name, shape, std, 1.0)
+        if k == "bn_w":   # BatchNorm gain around `std` (here: the mean), +- 10 %
+            return (np.float32(std) * normal(seed, name, shape, 0.1, 1.0)).astype(np.float32)
         t = normal(seed, name, shape, std)
         if k == "n16":  # convert_weights (clip/model.py:339-360): stored as fp16
             t = t.astype(np.float16).astype(np.float32)
@@ -198,6 +240,10 @@ def make_tensor(seed, name, shape, kind, map_lr_mul=0.01):
         return normal(seed, name, shape, 0.2)
     if kind == "const":
         return normal(seed, name, shape, 1.0)
+    if kind == "bn_var":   # running variance: strictly positive, away from 1 on both sides (0.4 .. 1.6)
+        return (0.4 + 1.2 * _rng(seed, name).random(shape, dtype=np.float32)).astype(np.float32)
+    if kind == "count":    # BatchNorm's num_batches_tracked: a key of the reference's state dict that no forward reads
+        return np.zeros(shape, dtype=np.float32)
     raise ValueError(kind)
 
 

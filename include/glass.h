@@ -78,6 +78,12 @@ typedef struct glass_config {
                                      2: antialiased bicubic (a = -0.5), then clamp to [0, 1] — both as torch F.interpolate(antialias=True) */
     int32_t clip_normalize;       /* 0: none (the reference, default); 1: (v - mean_c) / std_c with the constants of clip/clip.py:73,
                                      after the resize (and the clamp), before the fp16 store */
+    /* --- CLIP's ResNet image towers (clip/model.py:92-149: RN50, RN101).  Appended last: zero selects the ViT engine.  With clip_arch = 1
+     * the fields above mean: clip_width = stem width (64), clip_heads = width * 32 / 64 (the attention pool's heads), clip_layers = number
+     * of bottlenecks (the sum of clip_rn_layers), clip_patch = 32 (the tower's total stride: (clip_res / clip_patch)^2 + 1 is the attention
+     * pool's token count, as it is for a ViT), clip_res and clip_embed as before.  See glass_clip_resnet_supported. */
+    int32_t clip_arch;            /* 0: VisualTransformer (default); 1: ModifiedResNet */
+    int32_t clip_rn_layers[4];    /* bottlenecks per stage: (3, 4, 6, 3) RN50, (3, 4, 23, 3) RN101 */
 } glass_config;
 
 /* Caller-provided noise (noise_mode 2): planes[m * n_layers + l] points at a host
@@ -98,6 +104,12 @@ const char* glass_version(void);
  * glass_last_error().  glass_engine_create applies the same rule. */
 int glass_clip_geometry_supported(int32_t width, int32_t layers, int32_t heads, int32_t patch, int32_t res,
                                   int32_t embed);
+
+/* Which ModifiedResNet image towers (glass_config::clip_arch = 1) the engine runs (host only: callable without a GPU): stem width a
+ * multiple of 64 (every GEMM K and N of the tower is then a multiple of 64 and the attention pool's head dimension is 64: RN50 and RN101;
+ * RN50x4 / x16 with widths 80 / 96 are refused), input resolution a multiple of 32.  layers: bottlenecks per stage.  Returns GLASS_OK, or
+ * GLASS_ERR_ARG with the reason in glass_last_error().  glass_engine_create applies the same rule. */
+int glass_clip_resnet_supported(const int32_t layers[4], int32_t width, int32_t res, int32_t embed);
 
 /* Whether the engine runs the preprocessing (clip_resize, clip_normalize) from a gen_res x gen_res generated image to clip_res (host
  * only: callable without a GPU; gen_res 0 checks the ranges of the two fields alone).  The antialiased modes take an image side that is a

@@ -176,6 +176,21 @@ int glass_op_bg_rgb_tanh(int32_t device, int32_t B, int32_t hw, int32_t C, const
 int glass_op_bg_to_half(int32_t device, int64_t n, const float* x, float* out);
 int glass_op_bg_tail(int32_t device, int32_t B, int32_t R, int32_t mid, const float* h, const float* x0, const float* w3, const float* b3,
                      const float* bn_a, const float* bn_s, const float* rgb_w, const float* rgb_b, float* y);
+/* CLIP's ResNet image towers (clip_resnet.hip, gemm_tiled.hip mode 5), each piece launched as the tower's walker (clip.cpp) launches it.
+ * BatchNorm is given as the fp32 per-channel scale bn_a and shift bn_s the engine keeps.  A launcher that refuses is an error.
+ * glass_op_rn_avgpool: AvgPool2d(2) of x [B,H,W,C] -> [B,H/2,W/2,C].
+ * glass_op_rn_stem_conv1: img [B,3,S,S] -> launch_image_patches (32-pixel patches, the layout every preprocessing mode writes) -> conv 3x3
+ *   stride 2 pad 1 with w [C1,3,3,3] + BN + ReLU -> [B,S/2,S/2,C1].
+ * glass_op_rn_conv_bn: out = act(conv(x, w) * bn_a + bn_s (+ res)), x [B,H,W,Cin], w [Cout,Cin,KS,KS], res [B,H,W,Cout] or NULL, stride 1.
+ *   form 0, the bottlenecks' convolutions on gemm_tiled: KS 1 (fewer than 64 rows run as 64 in padded buffers), KS 3 through the implicit
+ *   patch matrix (Cin % 64 == 0, ReLU, no res); form 1, the stem's conv2 / conv3 kernel: KS 3, Cin % 16 == 0, ReLU, no res.
+ * glass_op_rn_tokens: x [B,HW,C], pos [HW+1,C] -> the attention pool's tokens [B,HW+1,C] = [mean ; pixels] + pos. */
+int glass_op_rn_avgpool(int32_t device, int32_t B, int32_t H, int32_t W, int32_t C, const float* x, float* out);
+int glass_op_rn_stem_conv1(int32_t device, int32_t B, int32_t S, int32_t C1, const float* img, const float* w, const float* bn_a,
+                           const float* bn_s, float* out);
+int glass_op_rn_conv_bn(int32_t device, int32_t form, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t relu,
+                        const float* x, const float* w, const float* bn_a, const float* bn_s, const float* res, float* out);
+int glass_op_rn_tokens(int32_t device, int32_t B, int32_t HW, int32_t C, const float* x, const float* pos, float* out);
 /* raw MFMA layout probe: D = A[32x16] * B[16x32] through the fragment mapping of common.h */
 int glass_op_mfma_probe(int32_t device, const float* a /*[32,16]*/, const float* b /*[16,32]*/, float* d /*[32,32]*/);
 
