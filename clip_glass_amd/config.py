@@ -3,7 +3,10 @@ StyleGAN2 configs; `latent` / `model` point at this package's classes).
 
 Optional keys the table leaves unset (run.py copies them in from its flags): `clip_model` (generator.CLIP_MODELS, default ViT-B/32),
 `clip_resnet` (generator.CLIP_RESNET_MODELS: RN50 / RN101 instead of a ViT; `clip_resnet_geometry` = (layers4, width, res, embed) wins over the name) and
-`clip_preprocess` — "reference" (default: the reference's resize, generator.py:45), "antialias" or "clip" (generator.CLIP_PREPROCESS)."""
+`clip_preprocess` — "reference" (default: the reference's resize, generator.py:45), "antialias" or "clip" (generator.CLIP_PREPROCESS);
+`clip_views` (0, the default: one whole-image score as the reference computes it; N >= 1: the mean similarity over N crop views of each
+image, include/glass.h), with `clip_view_min` (smallest crop side as a fraction of the image side, 0.5), `clip_view_flip` (mirror crops at
+random, True) and `clip_view_fixed` (the same crops in every generation, False)."""
 from .latent import DeepMindBigGANLatentSpace, GPT2LatentSpace, StyleGAN2LatentSpace
 from .models import GPT2, DeepMindBigGAN, StyleGAN2
 from .utils import biggan_denorm, biggan_norm

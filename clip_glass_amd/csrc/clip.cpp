@@ -75,6 +75,65 @@ extern "C" int glass_clip_preprocess_supported(int32_t gen_res, int32_t clip_res
     return GLASS_OK;
 }
 
+// The one rule for crop views (host only), applied by glass_engine_set_clip_views too.  tokens x width: the tower's rows per image and their
+// width — a ViT's (res / patch)^2 + 1 tokens of clip_width; for a ResNet tower the (res / 4)^2 positions of layer1 and the stem width, whose
+// 4 x width channels make its largest map.  tokens * 4 * width is the largest activation of either tower per image (the MLP's hidden rows).
+extern "C" int glass_clip_views_supported(int32_t max_pop, int32_t tokens, int32_t width, int32_t clip_resize, int32_t views, int32_t min_permille) {
+    char msg[320];
+#define VIEW_REQ(cond, ...)                       \
+    if (!(cond)) {                                \
+        snprintf(msg, sizeof msg, __VA_ARGS__);   \
+        glass_set_error(msg);                     \
+        return GLASS_ERR_ARG;                     \
+    }
+    VIEW_REQ(max_pop > 0 && tokens > 0 && width > 0, "clip views: max_pop, tokens and width must be positive");
+    VIEW_REQ(views >= 0 && views <= GLASS_MAX_CLIP_VIEWS, "clip views: views must be in [0, %d] (0: off), got %d", GLASS_MAX_CLIP_VIEWS, views);
+    VIEW_REQ(min_permille >= 1 && min_permille <= 1000, "clip views: the smallest crop side must be 1 .. 1000 per mille of the image side, got %d",
+             min_permille);
+    if (views == 0) return GLASS_OK;
+    VIEW_REQ(clip_resize == 0, "clip views need clip_resize 0 (the point-sampled resize), got %d: the antialiased kernels build one tap table per "
+             "(image side, CLIP side) at finalize; a table per view is a follow-up", clip_resize);
+    const double largest = (double)max_pop * views * tokens * 4.0 * width;      // (in double: the product of five int32 does not fit an int64)
+    VIEW_REQ(largest < 2147483648.0, "clip views: max_pop %d x views %d images of %d rows x 4 x width %d are %.3g activation elements, the "
+             "tower's kernels index fewer than 2^31: lower max_pop or views", max_pop, views, tokens, width, largest);
+#undef VIEW_REQ
+    return GLASS_OK;
+}
+
+// Philox4x32-10 on the host (common.h philox4x32_10, synth.philox4x32)
+static void philox4x32_10_host(uint32_t c[4], uint32_t k0, uint32_t k1) {
+    for (int i = 0; i < 10; ++i) {
+        const uint64_t p0 = (uint64_t)c[0] * 0xD2511F53ull, p1 = (uint64_t)c[2] * 0xCD9E8D57ull;
+        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+#define CLIP_VIEW_TAG 0x56494557u          // "VIEW", XOR-ed into the key's high word: disjoint from the noise planes' stream and from GPT2_SAMPLE_TAG
+// The boxes (x0, y0, s, flip) of a pass: a function of (seed, generation, view) alone — every candidate of a generation is judged through the
+// same crops.  View 0 is the whole image; numpy mirror: synth.clip_view_boxes.
+extern "C" int glass_host_clip_view_boxes(uint64_t seed, int32_t generation, int32_t views, int32_t gen_res, int32_t min_permille, int32_t flip,
+                                          int32_t fixed, int32_t* boxes) {
+    REQUIRE(boxes, GLASS_ERR_ARG, "null boxes");
+    REQUIRE(views >= 1 && views <= GLASS_MAX_CLIP_VIEWS, GLASS_ERR_ARG, "clip view boxes: views must be in [1, 16]");
+    REQUIRE(gen_res >= 2 && gen_res <= 65536, GLASS_ERR_ARG, "clip view boxes: image side out of range");
+    REQUIRE(min_permille >= 1 && min_permille <= 1000, GLASS_ERR_ARG, "clip view boxes: min_permille must be in [1, 1000]");
+    const uint32_t R = (uint32_t)gen_res;
+    const uint32_t smin = std::max<uint32_t>(2u, (uint32_t)(((uint64_t)R * (uint32_t)min_permille + 999) / 1000));
+    boxes[0] = 0; boxes[1] = 0; boxes[2] = gen_res; boxes[3] = 0;
+    for (int v = 1; v < views; ++v) {
+        uint32_t w[4] = {(uint32_t)v, fixed ? 0u : (uint32_t)generation, 0u, 0u};
+        philox4x32_10_host(w, (uint32_t)seed, (uint32_t)(seed >> 32) ^ CLIP_VIEW_TAG);
+        const uint32_t s = smin + w[0] % (R - smin + 1);
+        boxes[4 * v + 0] = (int32_t)(w[1] % (R - s + 1));
+        boxes[4 * v + 1] = (int32_t)(w[2] % (R - s + 1));
+        boxes[4 * v + 2] = (int32_t)s;
+        boxes[4 * v + 3] = flip ? (int32_t)(w[3] & 1u) : 0;
+    }
+    return GLASS_OK;
+}
+
 static int load_clip_blocks(glass_engine* e, const char* prefix, int layers, int W, std::vector<ClipBlock>& out) {
     char nm[256];
     int rc;
@@ -220,7 +279,7 @@ static int finalize_clip_resnet(glass_engine* e) {
 int alloc_clip_resnet(glass_engine* e) {
     const glass_config& c = e->cfg;
     if (c.clip_arch != 1) return GLASS_OK;
-    const size_t P = c.max_pop, w = c.clip_width, G = c.clip_res / 32, T = G * G + 1, C = 32 * w;
+    const size_t P = clip_max_images(e), w = c.clip_width, G = c.clip_res / 32, T = G * G + 1, C = 32 * w;
     RnState& rn = e->rn;
     // the largest maps: the stem's (res/2)^2 x w and layer1's (res/4)^2 x 4w, the same size; never below 64 rows of the widest map
     rn.cap = std::max(P * (size_t)(c.clip_res / 2) * (c.clip_res / 2) * w, (size_t)64 * C);
@@ -434,7 +493,12 @@ static void run_rn_blocks(glass_engine* e, int P, int l0, int l1) {
         rn_gemm(e, rn_gemm_1x1(t, b.c3, Mo, Ho * Ho, id, 1, y), "clip.rn_conv3");      // the residual goes in BEFORE the ReLU
     }
 }
-static void run_rn_head(glass_engine* e, int P) {
+static void clip_cosine(glass_engine* e, int P, int views) {      // the end of both towers' heads: d_feat [P][embed] against the target
+    const int E = e->cfg.clip_embed;
+    if (views > 0) launch_cosine_views(e->d_feat, e->d_target, P / views, views, E, e->d_view_sim, e->d_sim, e->cur);
+    else launch_cosine(e->d_feat, e->d_target, P, E, e->d_sim, e->cur);
+}
+static void run_rn_head(glass_engine* e, int P, int views) {
     const glass_config& c = e->cfg;
     RnState& rn = e->rn;
     const int G = c.clip_res / 32, HW = G * G, T = HW + 1, C = 32 * c.clip_width, heads = c.clip_heads, E = c.clip_embed;
@@ -454,7 +518,7 @@ static void run_rn_head(glass_engine* e, int P) {
     Prof pr(e, "clip.attnpool_head", 2.0 * P * C * E, 4.0 * C * E);
     launch_rn_token0_rows(rn.att, P, T, C, rn.cls, e->cur);
     launch_dense(rn.cls, C, P, C, rn.cproj_wt, E, rn.cproj_b, e->d_feat, E, 0, 0, nullptr, 0, e->cur);
-    launch_cosine(e->d_feat, e->d_target, P, E, e->d_sim, e->cur);
+    clip_cosine(e, P, views);
 }
 
 // ---- the image tower (declared in engine.h) ----
@@ -473,32 +537,35 @@ void run_clip_layers(glass_engine* e, int P, int l0, int l1) {
     const int G = c.clip_res / c.clip_patch;
     run_blocks(e, e->cblk, l0, std::min(l1, (int)e->cblk.size()), e->d_x, e->d_ln16, e->d_qkv, e->d_attn, e->d_hid, G * G + 1, P, c.clip_width, c.clip_heads, 0, e->cur, "clip");
 }
-void run_clip_head(glass_engine* e, int P) {
-    if (e->cfg.clip_arch == 1) return run_rn_head(e, P);
+void run_clip_head(glass_engine* e, int P, int views) {
+    if (e->cfg.clip_arch == 1) return run_rn_head(e, P, views);
     const glass_config& c = e->cfg;
     const int W = c.clip_width, G = c.clip_res / c.clip_patch, T = G * G + 1;
     Prof pr(e, "clip.head", 2.0 * P * W * c.clip_embed, 4.0 * W * c.clip_embed);
     launch_layernorm(e->d_x, (long long)T * W, P, W, e->c_lnpost_g, e->c_lnpost_b, nullptr, e->d_cls, e->cur);
     launch_dense(e->d_cls, W, P, W, e->c_proj, c.clip_embed, nullptr, e->d_feat, c.clip_embed, 0, 0, nullptr, 0,
                  e->cur);
-    launch_cosine(e->d_feat, e->d_target, P, c.clip_embed, e->d_sim, e->cur);
+    clip_cosine(e, P, views);
 }
-void run_clip(glass_engine* e, int P) {
+void run_clip(glass_engine* e, int P, int views) {
     run_clip_embed(e, P);
     run_clip_layers(e, P, 0, clip_n_layers(e));
-    run_clip_head(e, P);
+    run_clip_head(e, P, views);
 }
 
 // Generated images y [B][3][R][R] -> CLIP's patch operand.  The default (clip_resize 0, clip_normalize 0) launches resize_patches_kernel, which
 // reads four input pixels per output; the antialiased modes read the whole image.
 double clip_resize_bytes(const glass_engine* e, int B) {
     const glass_config& c = e->cfg;
+    if (e->views) return (double)B * e->views * 3 * c.clip_res * c.clip_res * (16 + 2);
     const double out = 2.0 * 3 * c.clip_res * c.clip_res;
     return B * ((c.clip_resize ? 4.0 * 3 * e->R * e->R : 16.0 * c.clip_res * c.clip_res * 3) + out);
 }
 void run_clip_resize(glass_engine* e, const float* y, int B, half_t* patches) {
     const glass_config& c = e->cfg;
-    if (c.clip_resize == 0 && c.clip_normalize == 0)
+    if (e->views)      // (clip_resize is 0 here: glass_clip_views_supported)
+        launch_view_patches(y, B, e->R, c.clip_res, c.clip_patch, clip_patch_k(c), c.clip_normalize, e->views, e->view_boxes, patches, e->cur);
+    else if (c.clip_resize == 0 && c.clip_normalize == 0)
         launch_resize_patches(y, B, e->R, c.clip_res, c.clip_patch, clip_patch_k(c), patches, e->cur);
     else
         launch_preprocess_patches(y, B, e->R, c.clip_res, c.clip_patch, clip_patch_k(c), c.clip_resize, c.clip_normalize, e->rz, patches, e->cur);

@@ -324,17 +324,19 @@ static int alloc_buffers(glass_engine* e) {
     if ((rc = dev_alloc(e, &e->d_img, (size_t)CH * 3 * e->R * e->R))) return rc;
     const int W = c.clip_width, ps = c.clip_patch, G = c.clip_res / ps, T = G * G + 1;
     const size_t Kp = (size_t)clip_patch_k(c);
-    if ((rc = dev_alloc(e, &e->d_patches, (size_t)P * G * G * Kp))) return rc;
-    if (Kp != (size_t)3 * ps * ps) GLASS_HIP(hipMemset(e->d_patches, 0, (size_t)P * G * G * Kp * sizeof(half_t)));   // the row tails stay zero: no kernel writes them
-    if ((rc = dev_alloc(e, &e->d_pe, (size_t)P * G * G * W))) return rc;
-    if ((rc = dev_alloc(e, &e->d_x, (size_t)P * T * W))) return rc;
-    if ((rc = dev_alloc(e, &e->d_ln16, (size_t)P * T * W))) return rc;
-    if ((rc = dev_alloc(e, &e->d_qkv, (size_t)P * T * 3 * W))) return rc;
-    if ((rc = dev_alloc(e, &e->d_attn, (size_t)P * T * W))) return rc;
-    if ((rc = dev_alloc(e, &e->d_hid, (size_t)P * T * 4 * W))) return rc;
-    if ((rc = dev_alloc(e, &e->d_cls, (size_t)P * W))) return rc;
+    const size_t PI = clip_max_images(e);      // the tower's side holds every view of every candidate (max_pop images with the views off)
+    if ((rc = dev_alloc(e, &e->d_patches, PI * G * G * Kp))) return rc;
+    if (Kp != (size_t)3 * ps * ps) GLASS_HIP(hipMemset(e->d_patches, 0, PI * G * G * Kp * sizeof(half_t)));   // the row tails stay zero: no kernel writes them
+    if ((rc = dev_alloc(e, &e->d_pe, PI * G * G * W))) return rc;
+    if ((rc = dev_alloc(e, &e->d_x, PI * T * W))) return rc;
+    if ((rc = dev_alloc(e, &e->d_ln16, PI * T * W))) return rc;
+    if ((rc = dev_alloc(e, &e->d_qkv, PI * T * 3 * W))) return rc;
+    if ((rc = dev_alloc(e, &e->d_attn, PI * T * W))) return rc;
+    if ((rc = dev_alloc(e, &e->d_hid, PI * T * 4 * W))) return rc;
+    if ((rc = dev_alloc(e, &e->d_cls, PI * W))) return rc;
     if ((rc = alloc_clip_resnet(e))) return rc;
-    if ((rc = dev_alloc(e, &e->d_feat, (size_t)P * c.clip_embed))) return rc;
+    if ((rc = dev_alloc(e, &e->d_feat, PI * c.clip_embed))) return rc;
+    if (e->views && (rc = dev_alloc(e, &e->d_view_sim, PI))) return rc;
     if ((rc = dev_alloc(e, &e->d_sim, (size_t)P))) return rc;
     if ((rc = dev_alloc(e, &e->d_dis, (size_t)P))) return rc;
     if ((rc = dev_alloc(e, &e->d_F, (size_t)P * 2))) return rc;
@@ -498,7 +500,7 @@ GemmParams gemm_params(const half_t* a, const half_t* w, int M, int N, int K, co
 static int finish_pass(glass_engine* e, int P, float* out_F, bool clip_done, hipStream_t d_join) {
     const glass_config& c = e->cfg;
     if (out_F) {
-        if (!clip_done) run_clip(e, P);
+        if (!clip_done) run_clip(e, pass_images(e, P), e->views);
         if (d_join) {   // join: D head finished
             GLASS_HIP(hipEventRecord(e->ev_g[0], d_join));
             GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_g[0], 0));
@@ -543,6 +545,17 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
     GLASS_HIP(hipMemcpyAsync(e->d_z, e->h_pinned, (size_t)P * L * sizeof(float), hipMemcpyHostToDevice, e->cur));
     const int ps = c.clip_patch, G = c.clip_res / ps;
     const size_t img_elems = (size_t)3 * e->R * e->R;
+    // crop views: the boxes of this pass, from (noise_seed, generation) alone — first_mb plays no part, so shards and slices of a population
+    // see the same crops; V images per candidate from the resize on
+    const int V = std::max(e->views, 1), PV = P * V;
+    const char* resize_tag = e->views ? "clip.views" : "clip.resize";
+    const size_t cand_patches = (size_t)V * G * G * clip_patch_k(c);      // patch-operand elements per candidate
+    if (e->views && out_F) {
+        if (int brc = glass_host_clip_view_boxes(c.noise_seed, generation, e->views, e->R, e->view_min_permille, e->view_flip, e->view_fixed,
+                                                 &e->view_boxes.box[0][0]))
+            return brc;
+        REQUIRE(view_boxes_valid(e->view_boxes, e->views, e->R), GLASS_ERR_STATE, "clip views: a box leaves the image");
+    }
     if (biggan) {
         // BigGAN-deep (models.py:75-86): no noise inputs, no discriminator; candidates are independent, so the
         // reference's minibatch loop has no semantic effect and the population is walked in engine chunks.
@@ -558,8 +571,8 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
                                          hipMemcpyDeviceToHost, e->cur));
             }
             if (out_F) {
-                Prof pr(e, "clip.resize", 0, clip_resize_bytes(e, B));
-                run_clip_resize(e, y, B, e->d_patches + (size_t)c0 * G * G * clip_patch_k(c));
+                Prof pr(e, resize_tag, 0, clip_resize_bytes(e, B));
+                run_clip_resize(e, y, B, e->d_patches + (size_t)c0 * cand_patches);
             }
         }
         return finish_pass(e, P, out_F, false, nullptr);
@@ -638,18 +651,18 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
             }
             e->cur = sd;
             {
-                Prof pr(e, "clip.resize", 0, clip_resize_bytes(e, B));
-                run_clip_resize(e, y, B, e->d_patches + (size_t)c0 * G * G * clip_patch_k(c));
+                Prof pr(e, resize_tag, 0, clip_resize_bytes(e, B));
+                run_clip_resize(e, y, B, e->d_patches + (size_t)c0 * cand_patches);
             }
             if (clip_ov && c0 + e->chunk >= P) {   // last chunk's patches are in place: CLIP starts now
                 // its first layers on the MAIN stream (alone on the chip), the rest on the second stream beside the discriminator
-                run_clip_embed(e, P);
-                run_clip_layers(e, P, 0, GLASS_CLIP_SERIAL_LAYERS);
+                run_clip_embed(e, PV);
+                run_clip_layers(e, PV, 0, GLASS_CLIP_SERIAL_LAYERS);
                 GLASS_HIP(hipEventRecord(e->ev_g[0], e->stream));
                 GLASS_HIP(hipStreamWaitEvent(e->stream_d, e->ev_g[0], 0));
                 e->cur = e->stream_d;
-                run_clip_layers(e, P, GLASS_CLIP_SERIAL_LAYERS, c.clip_layers);
-                run_clip_head(e, P);
+                run_clip_layers(e, PV, GLASS_CLIP_SERIAL_LAYERS, c.clip_layers);
+                run_clip_head(e, PV, e->views);
                 GLASS_HIP(hipEventRecord(e->ev_d[0], e->stream_d));
                 e->cur = e->stream;
             }
@@ -699,10 +712,41 @@ extern "C" int glass_engine_last_details(glass_engine* e, int32_t P, float* feat
     REQUIRE(e && e->finalized, GLASS_ERR_STATE, "engine not ready");
     REQUIRE(P > 0 && P <= e->last_P, GLASS_ERR_ARG, "P exceeds the last evaluated population");
     GLASS_HIP(hipSetDevice(e->cfg.device));
-    if (features)
-        GLASS_HIP(hipMemcpy(features, e->d_feat, (size_t)P * e->cfg.clip_embed * sizeof(float), hipMemcpyDeviceToHost));
+    const size_t frow = (size_t)e->cfg.clip_embed * sizeof(float);
+    if (features && e->views)      // crop views: a candidate's field is view 0's feature — the whole image, as without views
+        GLASS_HIP(hipMemcpy2D(features, frow, e->d_feat, frow * e->views, frow, (size_t)P, hipMemcpyDeviceToHost));
+    else if (features)
+        GLASS_HIP(hipMemcpy(features, e->d_feat, (size_t)P * frow, hipMemcpyDeviceToHost));
     if (dis) GLASS_HIP(hipMemcpy(dis, e->d_dis, (size_t)P * sizeof(float), hipMemcpyDeviceToHost));
     if (sim) GLASS_HIP(hipMemcpy(sim, e->d_sim, (size_t)P * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_clip_views(glass_engine* e, int32_t views, int32_t min_permille, int32_t flip, int32_t fixed) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(!e->finalized, GLASS_ERR_STATE, "set_clip_views: the engine is finalized (its buffers are sized in finalize: call it before)");
+    REQUIRE(e->R > 0, GLASS_ERR_STATE, "set_clip_views: this engine has no generator (img2txt): there is no generated image to crop");
+    REQUIRE((flip == 0 || flip == 1) && (fixed == 0 || fixed == 1), GLASS_ERR_ARG, "set_clip_views: flip and fixed must be 0 or 1");
+    const glass_config& c = e->cfg;
+    const int G = c.clip_res / c.clip_patch;
+    const int tokens = c.clip_arch == 1 ? (c.clip_res / 4) * (c.clip_res / 4) : G * G + 1;
+    if (int rc = glass_clip_views_supported(c.max_pop, tokens, c.clip_width, c.clip_resize, views, min_permille)) return rc;
+    e->views = views;
+    e->view_min_permille = min_permille;
+    e->view_flip = flip;
+    e->view_fixed = fixed;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_last_view_details(glass_engine* e, int32_t P, float* features, float* sims, int32_t* boxes) {
+    REQUIRE(e && e->finalized, GLASS_ERR_STATE, "engine not ready");
+    REQUIRE(e->views > 0, GLASS_ERR_STATE, "crop views are off (glass_engine_set_clip_views)");
+    REQUIRE(P > 0 && P <= e->last_P, GLASS_ERR_ARG, "P exceeds the last evaluated population");
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    const size_t n = (size_t)P * e->views;
+    if (features) GLASS_HIP(hipMemcpy(features, e->d_feat, n * e->cfg.clip_embed * sizeof(float), hipMemcpyDeviceToHost));
+    if (sims) GLASS_HIP(hipMemcpy(sims, e->d_view_sim, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (boxes) memcpy(boxes, &e->view_boxes.box[0][0], (size_t)e->views * 4 * sizeof(int32_t));
     return GLASS_OK;
 }
 

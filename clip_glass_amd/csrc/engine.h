@@ -169,6 +169,10 @@ struct glass_engine {
     std::vector<ClipBlock> cblk;
     ResizeTapsDev rz;          // clip_resize 1 / 2: the antialiased resize's tap table (finalize_preprocess)
     RnState rn;                // clip_arch 1: the ResNet tower instead of c_* / cblk
+    // crop views (glass_engine_set_clip_views; views 0: off — one image per candidate, nothing below is touched)
+    int views = 0, view_min_permille = 0, view_flip = 0, view_fixed = 0;
+    ViewBoxes view_boxes = {};          // the boxes of the current / last evaluate(): one set for every candidate of the pass
+    float* d_view_sim = nullptr;        // [max_pop][views]
     // GPT-2 (optional, fp32; config C5)
     struct Gpt2Block { float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *w_qkv, *b_qkv, *w_o, *b_o, *w_fc, *b_fc, *w_pr, *b_pr; };
     std::vector<Gpt2Block> gblk;
@@ -365,12 +369,16 @@ int finalize_preprocess(glass_engine* e);
 void text_work_free(glass_engine* e);
 double clip_resize_bytes(const glass_engine* e, int B);
 void run_clip_resize(glass_engine* e, const float* y, int B, half_t* patches);
-// the image tower on e->cur, for the P candidates whose patch operand is in d_patches: patch embedding + ln_pre, layers [l0, l1), and the
-// head (ln_post, projection, cosine against the target); run_clip is all of it
+// the image tower on e->cur, for the P images whose patch operand is in d_patches: patch embedding + ln_pre, layers [l0, l1), and the
+// head (ln_post, projection, cosine against the target); run_clip is all of it.  views > 0 (the pass with crop views): the P images are
+// P / views candidates' views, and the head ends in the per-view cosines and their mean per candidate.
 void run_clip_embed(glass_engine* e, int P);
 void run_clip_layers(glass_engine* e, int P, int l0, int l1);
-void run_clip_head(glass_engine* e, int P);
-void run_clip(glass_engine* e, int P);
+void run_clip_head(glass_engine* e, int P, int views = 0);
+void run_clip(glass_engine* e, int P, int views = 0);
+// images the tower's buffers hold: max_pop, times the views when they are on
+inline size_t clip_max_images(const glass_engine* e) { return (size_t)e->cfg.max_pop * (size_t)std::max(e->views, 1); }
+inline int pass_images(const glass_engine* e, int P) { return P * std::max(e->views, 1); }      // images of a pass over P candidates
 int clip_n_layers(const glass_engine* e);     // what run_clip_layers counts: transformer blocks (ViT) or bottlenecks (ResNet)
 int alloc_clip_resnet(glass_engine* e);       // the ResNet tower's activation buffers (clip_arch 1)
 // The ResNet tower's GEMMs as the walker sets them up (shared with the diagnostic ops).  1 x 1 conv + BN (+ res) (+ ReLU) over M rows: fewer than

@@ -110,6 +110,17 @@ bool build_resize_taps(int R, int S, int mode, ResizeTaps& t, std::string& why);
 // resize_mode 0 (with normalize 1): resize_patches_norm_kernel, `t` unused; 1 / 2: preprocess_patches_kernel
 void launch_preprocess_patches(const float* y, int B, int R, int clip_res, int ps, int ld, int resize_mode, int normalize,
                                const ResizeTapsDev& t, half_t* patches, hipStream_t st);
+// Crop views (glass_engine_set_clip_views): image b seen through box v = (x0, y0, s, flip) of its R x R pixels — launch_resize_patches'
+// point-sampled bilinear resize of the s x s crop to clip_res, columns reversed where flip is set — into patch rows (b V + v) G G ...; the
+// box (0, 0, R, 0) gives launch_resize_patches' values bit for bit.  normalize: Normalize(mean, std) before the fp16 store.  The boxes travel
+// in the kernel arguments; every box must lie inside the image (view_boxes_valid).
+#define GLASS_MAX_CLIP_VIEWS 16
+struct ViewBoxes {
+    int box[GLASS_MAX_CLIP_VIEWS][4];
+};
+bool view_boxes_valid(const ViewBoxes& vb, int V, int R);
+void launch_view_patches(const float* y, int B, int R, int clip_res, int ps, int ld, int normalize, int V, const ViewBoxes& vb, half_t* patches,
+                         hipStream_t st);
 void launch_fromrgb(const float* y, int B, int R, int Cout, const float* w, const float* bias,
                     half_t* out, hipStream_t st);
 // 4x4 FIR [1,3,3,1]^2/64, zero pad 2, stride 1: [B,H,W,C] -> [B,H+1,W+1,C]
@@ -133,6 +144,8 @@ void launch_layernorm_rows(const float* x, const int* rows, int M, int D, const 
 void launch_attention(const half_t* qkv, int n_img, int L, int heads, int hd, int causal, half_t* out,
                       hipStream_t st);
 void launch_cosine(const float* feat, const float* target, int P, int D, float* sim, hipStream_t st);
+// crop views: feat [P][V][D]; view_sim[p V + v] = launch_cosine's value of that row, sim[p] = their fp32 mean summed in the order v = 0 .. V - 1
+void launch_cosine_views(const float* feat, const float* target, int P, int V, int D, float* view_sim, float* sim, hipStream_t st);
 void launch_assemble_F(const float* sim, const float* dis, int P, int n_obj, float* F, hipStream_t st);
 
 // --- CLIP's ResNet towers (clip_resnet.hip); BatchNorm = fp32 per-channel scale bn_a and shift bn_s in the epilogue ---------------------

@@ -428,6 +428,28 @@ void launch_cosine(const float* feat, const float* target, int P, int D, float* 
     hipLaunchKernelGGL(cosine_kernel, dim3(P), dim3(64), 0, st, feat, target, D, sim);
 }
 
+// crop views: one wave per candidate walks its V feature rows; each cosine is cosine_kernel's, their mean is summed in the order v = 0 .. V - 1
+__global__ void cosine_views_kernel(const float* feat, const float* target, int V, int D, float* view_sim, float* sim) {
+    const int p = blockIdx.x, lane = threadIdx.x;
+    float acc = 0.f;
+    for (int v = 0; v < V; ++v) {
+        const long long r = (long long)p * V + v;
+        float xy = 0.f, xx = 0.f, yy = 0.f;
+        for (int i = lane; i < D; i += 64) {
+            const float a = feat[r * D + i], b = target[i];
+            xy += a * b; xx += a * a; yy += b * b;
+        }
+        xy = wsum(xy); xx = wsum(xx); yy = wsum(yy);
+        const float c = xy / fmaxf(sqrtf(xx) * sqrtf(yy), 1e-8f);
+        if (lane == 0) view_sim[r] = c;
+        acc += c;
+    }
+    if (lane == 0) sim[p] = acc / (float)V;
+}
+void launch_cosine_views(const float* feat, const float* target, int P, int V, int D, float* view_sim, float* sim, hipStream_t st) {
+    hipLaunchKernelGGL(cosine_views_kernel, dim3(P), dim3(64), 0, st, feat, target, V, D, view_sim, sim);
+}
+
 // problem.py:23-27: F = column_stack(-sim, relu(1 - dis)) or F = -sim
 __global__ void assemble_F_kernel(const float* sim, const float* dis, int P, int n_obj, float* F) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;

@@ -639,6 +639,69 @@ __global__ void resize_patches_norm_kernel(const float* y, int B, int R, int S, 
     patches[row * ld + ((long long)c * ps + iy) * ps + ix] = (half_t)clip_normalize_px(v, c);
 }
 
+// ---- crop views (opt-in: glass_engine_set_clip_views): resize_patches_kernel's resize applied to the crop [y0, y0 + s) x [x0, x0 + s) of image b,
+// F.interpolate(img01[:, :, y0:y0+s, x0:x0+s], (S, S), "bilinear", align_corners=False), mirrored left-right where flip is set, written to
+// the patch rows of (image b, view v).  A workgroup works on ONE (image, view): the box is four scalars.  One thread = one output pixel of all
+// three channels: the coordinates are computed once and the twelve loads go out as one unconditional batch (a thread past the last pixel
+// reads the last pixel's taps and stores nothing).  The coordinates are the crop's own, so with the box (0, 0, R, 0) every expression is
+// resize_patches_kernel's — rounded where the compiler rounds that kernel's — and the values are equal bit for bit.
+__global__ __launch_bounds__(256) void view_patches_kernel(const float* y, int R, int S, int ps, int ld, int normalize, int V, int nb, ViewBoxes vb,
+                                                           half_t* patches) {
+    const int G = S / ps;
+    const int bv = blockIdx.x / nb, b = bv / V, v = bv - b * V;      // uniform
+    const int bx0 = vb.box[v][0], by0 = vb.box[v][1], bs = vb.box[v][2], flip = vb.box[v][3];
+    const int idx = (blockIdx.x - bv * nb) * 256 + threadIdx.x;
+    const int pix = min(idx, S * S - 1);
+    const int Y = pix / S, X = pix - Y * S;
+    const int Xs = flip ? S - 1 - X : X;             // out[X] = unflipped[S - 1 - X]
+    const float scale = (float)bs / (float)S;
+    float sy = __fmaf_rn(scale, (float)Y + 0.5f, -0.5f), sx = __fmaf_rn(scale, (float)Xs + 0.5f, -0.5f);      // scale (i + 0.5) - 0.5, fused as it is there
+    sy = fmaxf(sy, 0.f); sx = fmaxf(sx, 0.f);
+    const int y0 = min((int)sy, bs - 1), x0 = min((int)sx, bs - 1);
+    const int y1 = min(y0 + 1, bs - 1), x1 = min(x0 + 1, bs - 1);
+    const float ly = sy - (float)y0, lx = sx - (float)x0;
+    const float* yp = y + (long long)b * 3 * R * R;
+    const long long o00 = (long long)(by0 + y0) * R + bx0 + x0, o01 = (long long)(by0 + y0) * R + bx0 + x1;
+    const long long o10 = (long long)(by0 + y1) * R + bx0 + x0, o11 = (long long)(by0 + y1) * R + bx0 + x1;
+    float t[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float* yc = yp + (long long)c * R * R;
+        t[c][0] = yc[o00]; t[c][1] = yc[o01]; t[c][2] = yc[o10]; t[c][3] = yc[o11];
+    }
+    if (idx >= S * S) return;
+    auto nrm = [](float v) { return fminf(fmaxf((v + 1.f) * 0.5f, 0.f), 1.f); };
+    const int gy = Y / ps, iy = Y - gy * ps, gx = X / ps, ix = X - gx * ps;
+    const long long row = ((long long)bv * G + gy) * G + gx;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float v00 = nrm(t[c][0]), v01 = nrm(t[c][1]);
+        const float v10 = nrm(t[c][2]), v11 = nrm(t[c][3]);
+        // v = (1 - ly) ((1 - lx) v00 + lx v01) + ly ((1 - lx) v10 + lx v11), with the roundings spelled out as the compiler contracts that
+        // expression in resize_patches_kernel (one fused product per row — the lx term above, the 1 - lx term below — and a plain sum of the
+        // two rounded row products): left to itself it contracts this loop differently, and the whole-image view must equal the default
+        // pass to the bit (tests/test_gpu_clip_views.py holds the two kernels against each other)
+        const float top = __fmaf_rn(lx, v01, __fmul_rn(1.f - lx, v00));
+        const float bot = __fmaf_rn(1.f - lx, v10, __fmul_rn(lx, v11));
+        const float v = __fadd_rn(__fmul_rn(1.f - ly, top), __fmul_rn(ly, bot));
+        patches[row * ld + ((long long)c * ps + iy) * ps + ix] = (half_t)(normalize ? clip_normalize_px(v, c) : v);
+    }
+}
+bool view_boxes_valid(const ViewBoxes& vb, int V, int R) {
+    if (V < 1 || V > GLASS_MAX_CLIP_VIEWS) return false;
+    for (int v = 0; v < V; ++v) {
+        const int x0 = vb.box[v][0], y0 = vb.box[v][1], s = vb.box[v][2], flip = vb.box[v][3];
+        if (x0 < 0 || y0 < 0 || s < 1 || s > R || x0 > R - s || y0 > R - s || (flip != 0 && flip != 1)) return false;
+    }
+    return true;
+}
+void launch_view_patches(const float* y, int B, int R, int clip_res, int ps, int ld, int normalize, int V, const ViewBoxes& vb, half_t* patches,
+                         hipStream_t st) {
+    const int nb = (clip_res * clip_res + 255) / 256;      // workgroups per (image, view)
+    hipLaunchKernelGGL(view_patches_kernel, dim3((unsigned)((long long)B * V * nb)), dim3(256), 0, st, y, R, clip_res, ps, ld, normalize, V, nb, vb,
+                       patches);
+}
+
 // The tap table of one axis of an antialiased resize R -> S, as torch's upsample_bilinear2d_aa / upsample_bicubic2d_aa build it
 // (align_corners = False): scale = R / S, m = max(scale, 1), support = r m (r = 1 triangle, 2 cubic with a = -0.5); for output i:
 // c = scale (i + 0.5), taps j in [max(int(c - support + 0.5), 0), min(int(c + support + 0.5), R)) with weight f((j - c + 0.5) / m),

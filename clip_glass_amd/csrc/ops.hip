@@ -484,6 +484,26 @@ extern "C" int glass_op_preprocess(int32_t device, int32_t B, int32_t R, int32_t
     return down16(patches, dp, n);
 }
 
+extern "C" int glass_op_view_patches(int32_t device, int32_t B, int32_t R, int32_t S, int32_t ps, int32_t normalize, int32_t V, const int32_t* boxes,
+                                     const float* y, float* patches) {
+    OPREQ(y && patches && boxes && B > 0 && R > 0 && ps > 0 && S > 0 && S % ps == 0 && S <= 4096 && (normalize == 0 || normalize == 1), "bad argument");
+    OPREQ(V >= 1 && V <= GLASS_MAX_CLIP_VIEWS, "views must be in [1, 16]");
+    ViewBoxes vb = {};
+    for (int i = 0; i < 4 * V; ++i) vb.box[i / 4][i % 4] = boxes[i];
+    OPREQ(view_boxes_valid(vb, V, R), "a box (x0, y0, s, flip) leaves the image or has flip outside {0, 1}");
+    OPREQ((long long)B * V * ((S * S + 255) / 256) < (1LL << 31), "too many images");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dy = dv.up32(y, (size_t)B * 3 * R * R);
+    const size_t n = (size_t)B * V * 3 * S * S;
+    half_t* dp = dv.alloc<half_t>(n);
+    OPREQ(dy && dp, "device allocation failed");
+    launch_view_patches(dy, B, R, S, ps, 3 * ps * ps, normalize, V, vb, dp, 0);
+    int rc = finish();
+    if (rc) return rc;
+    return down16(patches, dp, n);
+}
+
 extern "C" int glass_op_layernorm(int32_t device, int32_t M, int32_t D, const float* x, const float* g, const float* b, float* out) {
     OPREQ(x && g && b && out, "null argument");
     GLASS_HIP(hipSetDevice(device));

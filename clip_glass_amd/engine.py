@@ -71,6 +71,12 @@ def load_library(path=None):
         lib.glass_clip_preprocess_supported.argtypes = [C.c_int32] * 4
     if hasattr(lib, "glass_clip_resnet_supported"):     # (absent from older A/B builds loaded through GLASS_LIB)
         lib.glass_clip_resnet_supported.argtypes = [C.POINTER(C.c_int32)] + [C.c_int32] * 3
+    if hasattr(lib, "glass_clip_views_supported"):      # (absent from older A/B builds loaded through GLASS_LIB)
+        ip = C.POINTER(C.c_int32)
+        lib.glass_clip_views_supported.argtypes = [C.c_int32] * 6
+        lib.glass_host_clip_view_boxes.argtypes = [C.c_uint64] + [C.c_int32] * 6 + [ip]
+        lib.glass_engine_set_clip_views.argtypes = [C.c_void_p] + [C.c_int32] * 4
+        lib.glass_engine_last_view_details.argtypes = [C.c_void_p, C.c_int32, fp, fp, ip]
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -139,6 +145,39 @@ def clip_resnet_supported(geometry):
     return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
 
 
+def clip_view_permille(fraction):
+    """The smallest crop side as the library takes it: per mille of the image side."""
+    return int(round(1000 * float(fraction)))
+
+
+def clip_views_tower_rows(clip=None, clip_resnet=None):
+    """(tokens, width) of an image tower as glass_clip_views_supported counts them: a ViT's (res / patch)^2 + 1 tokens and its width; a ResNet
+    tower's (res / 4)^2 positions of layer1 and its stem width."""
+    if clip_resnet is not None:
+        _, width, res, _ = clip_resnet
+        return (int(res) // 4) ** 2, int(width)
+    width, _, _, patch, res, _ = clip
+    return (int(res) // int(patch)) ** 2 + 1, int(width)
+
+
+def clip_views_supported(max_pop, tokens, width, clip_resize, views, min_permille):
+    """(ok, message) for crop views over a tower of `tokens` rows x `width` per image (clip_views_tower_rows): the library's own rule, the
+    one glass_engine_set_clip_views applies.  Host only."""
+    lib = load_library()
+    rc = lib.glass_clip_views_supported(int(max_pop), int(tokens), int(width), int(clip_resize), int(views), int(min_permille))
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
+def host_clip_view_boxes(seed, generation, views, gen_res, min_permille, flip, fixed):
+    """int32 [views, 4] = (x0, y0, s, flip): the library's own boxes of a pass (glass_host_clip_view_boxes; numpy mirror:
+    synth.clip_view_boxes).  Host only."""
+    lib = load_library()
+    out = np.empty((int(views), 4), dtype=np.int32)
+    _check(lib, lib.glass_host_clip_view_boxes(int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation), int(views), int(gen_res), int(min_permille),
+                                               int(bool(flip)), int(bool(fixed)), out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
+
+
 def device_info(device=0):
     lib = load_library()
     name = C.create_string_buffer(256)
@@ -153,12 +192,16 @@ class Engine:
 
     def __init__(self, channels, latent_size=512, mapping_layers=8, batch_size=4, use_discriminator=True,
                  n_obj=2, max_pop=64, chunk=0, clip=(768, 12, 12, 32, 224, 512), noise_mode=1, noise_seed=0,
-                 mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0, clip_resnet=None):
+                 mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0, clip_resnet=None,
+                 clip_views=0, clip_view_min=0.5, clip_view_flip=True, clip_view_fixed=False):
         """`biggan` = dict(layers=[(up, in_mult, out_mult), ...], attention_pos, ch, z_dim, num_classes, n_stats, eps,
         truncation) selects the BigGAN-deep generator (channels must then be empty, no discriminator).
         clip_resize / clip_normalize: how a generated image is prepared for CLIP (include/glass.h); (0, 0) is the reference's way.
         clip_resnet = (layers4, width, res, embed) selects CLIP's ModifiedResNet image tower (RN50: ((3, 4, 6, 3), 64, 224, 1024));
-        `clip` is ignored then."""
+        `clip` is ignored then.
+        clip_views = V >= 1 scores a candidate as the mean similarity over V crop views of its image (include/glass.h: view 0 is the whole
+        image, the others random boxes at least clip_view_min of the side, mirrored at random unless clip_view_flip is False, redrawn
+        every generation unless clip_view_fixed); 0 (default) is the reference's single whole-image score."""
         self.lib = load_library()
         cfg = GlassConfigResnet()
         cfg.device = device
@@ -200,6 +243,14 @@ class Engine:
         self.n_noise = 1 + 2 * (len(channels) - 1) if channels else 0
         self._h = C.c_void_p()
         _check(self.lib, self.lib.glass_engine_create(C.byref(cfg), C.byref(self._h)))
+        self.clip_views = int(clip_views)
+        if self.clip_views:
+            rc = self.lib.glass_engine_set_clip_views(self._h, self.clip_views, clip_view_permille(clip_view_min), int(bool(clip_view_flip)),
+                                                      int(bool(clip_view_fixed)))
+            if rc != 0:
+                msg = self.lib.glass_last_error().decode()
+                self.close()
+                raise RuntimeError("libglass error %d: %s" % (rc, msg))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -303,6 +354,17 @@ class Engine:
         sim = np.empty((P,), dtype=np.float32)
         _check(self.lib, self.lib.glass_engine_last_details(self._h, P, _fp(feat), _fp(dis), _fp(sim)))
         return dict(features=feat, dis=dis, sim=sim)
+
+    def view_details(self, P):
+        """Crop views: per-view outputs of the last evaluate() — features [P, V, embed], sims [P, V], boxes int32 [V, 4] = (x0, y0, s, flip)."""
+        V = self.clip_views
+        if V < 1:
+            raise RuntimeError("crop views are off (Engine(clip_views=...))")
+        feat = np.empty((P, V, self.cfg.clip_embed), dtype=np.float32)
+        sims = np.empty((P, V), dtype=np.float32)
+        boxes = np.empty((V, 4), dtype=np.int32)
+        _check(self.lib, self.lib.glass_engine_last_view_details(self._h, P, _fp(feat), _fp(sims), boxes.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(features=feat, sims=sims, boxes=boxes)
 
     def last_F_device(self, P):
         """The last evaluate()'s fitness rows as a torch CUDA tensor VIEW [P, n_obj] of the engine's own buffer (no copy; valid until the

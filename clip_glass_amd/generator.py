@@ -10,7 +10,8 @@ import os
 import numpy as np
 
 from . import synth
-from .engine import Engine, clip_geometry_supported, clip_resnet_supported
+from .engine import (Engine, clip_geometry_supported, clip_resnet_supported, clip_view_permille, clip_views_supported,
+                     clip_views_tower_rows)
 from .utils import save_grid, save_image
 
 CLIP_VIT_B32 = (768, 12, 12, 32, 224, 512)
@@ -279,7 +280,18 @@ class Generator:
         self.sharder = None
         self.clip_preprocess = getattr(config, "clip_preprocess", None) or DEFAULT_CLIP_PREPROCESS
         clip_resize, clip_normalize = clip_preprocess_fields(self.clip_preprocess)
+        # crop views (opt-in, include/glass.h): a candidate's score is the mean similarity over `clip_views` views of its image
+        self.clip_views = int(getattr(config, "clip_views", 0) or 0)
+        def view_opt(key, default):      # (a flag the command line left unset arrives as None)
+            v = getattr(config, key, None)
+            return default if v is None else v
+        view_kw = dict(clip_views=self.clip_views, clip_view_min=float(view_opt("clip_view_min", 0.5)),
+                       clip_view_flip=bool(view_opt("clip_view_flip", True)),
+                       clip_view_fixed=bool(view_opt("clip_view_fixed", False))) if self.clip_views else {}
         if config.task == "img2txt":                                        # generator.py:25-27, 52-59
+            if self.clip_views:
+                raise ValueError("clip_views=%d scores crops of generated images (txt2img); the img2txt task has none: leave it at 0"
+                                 % self.clip_views)
             if (clip_resize, clip_normalize) != (0, 0):
                 # no image is generated here: the target image goes through clip_preprocess() below (clip/clip.py:68-74) either way
                 raise ValueError("clip_preprocess=%r applies to generated images (txt2img); the img2txt task has none: leave it at %r"
@@ -305,6 +317,13 @@ class Generator:
         check_clip_geometry(geom)        # an unsupported checkpoint fails here, not in generation 1
         tower = self._clip_tower(geom)
         pop = (pop + config.batch_size - 1) // config.batch_size * config.batch_size
+        if self.clip_views:                     # refused here with the library's reason, not in the engine's constructor
+            tokens, width = clip_views_tower_rows(clip=self.clip_geometry, clip_resnet=self.clip_resnet)
+            ok, msg = clip_views_supported(pop, tokens, width, clip_resize, self.clip_views, clip_view_permille(view_kw["clip_view_min"]))
+            if not ok:
+                raise ValueError("clip_views=%d (clip_preprocess=%r): %s" % (self.clip_views, self.clip_preprocess, msg))
+            self.augmentation = dict(kind="crop_views", **view_kw)      # the reference's hook (generator.py:14, 46-47), filled by the engine
+        tower.update(view_kw)
         if hasattr(self.model, "geometry"):     # BigGAN-deep (models.py:64-86)
             self.engine = Engine([], batch_size=config.batch_size, max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  device=device, biggan=self.model.geometry, clip_resize=clip_resize,

@@ -268,6 +268,21 @@ def resize(y, S, ps, device=0):
     return out
 
 
+def view_patches(y, S, ps, boxes, normalize=0, device=0):
+    """The engine's crop-view resize on images [B,3,R,R] in (-1, 1) and boxes int [V,4] = (x0, y0, s, flip); rows (b V + v) G G + g, columns
+    as `resize`."""
+    lib = load_library()
+    y = _f32(y)
+    B, _, R, _ = y.shape
+    bx = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+    V, G = bx.shape[0], S // ps
+    out = np.empty((B * V * G * G, 3 * ps * ps), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.glass_op_view_patches.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32), fp, fp]
+    _check(lib, lib.glass_op_view_patches(device, B, R, S, ps, int(normalize), V, bx.ctypes.data_as(C.POINTER(C.c_int32)), _fp(y), _fp(out)))
+    return out
+
+
 def preprocess(y, S, ps, resize_mode=0, normalize=0, device=0):
     """The engine's CLIP preprocessing (glass_config.clip_resize / clip_normalize) on images [B,3,R,R] in (-1, 1); output as `resize`."""
     lib = load_library()

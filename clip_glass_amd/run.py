@@ -43,6 +43,13 @@ def build_parser():
                    help="how a generated image is prepared for CLIP: reference (default: the reference's point-sampled bilinear resize, no "
                         "normalisation), antialias (antialiased bilinear resize), clip (CLIP's own transform: antialiased bicubic resize + "
                         "mean / std normalisation — departs from the reference on purpose)")
+    p.add_argument("--clip-views", type=int, default=None,
+                   help="score each image as the mean similarity over N views: the whole image and N - 1 random crops, the same for every "
+                        "candidate of a generation (0, the default: the reference's single whole-image score — this departs from it on purpose)")
+    p.add_argument("--clip-view-min", type=float, default=None, help="smallest crop side as a fraction of the image side (default 0.5)")
+    p.add_argument("--no-clip-view-flip", dest="clip_view_flip", action="store_false", default=None,
+                   help="never mirror a crop (default: each crop is mirrored with probability 1/2)")
+    p.add_argument("--clip-view-fixed", action="store_true", default=None, help="the same crops in every generation (default: redrawn per generation)")
     p.add_argument("--bpe-path", type=str, default=None)
     p.add_argument("--pop-size", type=int, default=None)
     p.add_argument("--stochastic", action="store_true", default=None,
@@ -59,7 +66,8 @@ def main(argv=None, extra_config=None):
     config = build_parser().parse_args(argv)
     over = {k: v for k, v in vars(config).items() if v is not None}
     vars(config).update(get_config(config.config))                             # run.py:25
-    for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "bpe_path", "pop_size", "stochastic"):
+    for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "clip_views", "clip_view_min", "clip_view_flip",
+              "clip_view_fixed", "bpe_path", "pop_size", "stochastic"):
         if k in over:
             setattr(config, k, over[k])
     if extra_config:

@@ -309,6 +309,26 @@ def gpt2_sample_uniform(seed, generation, row, step, purpose=GPT2_SAMPLE_EVALUAT
     return (x.astype(np.float64) + 0.5) * 2.0 ** -32
 
 
+# Crop views (csrc/clip.cpp, glass_host_clip_view_boxes): the boxes through which a pass sees every candidate's image — one Philox block per
+# (view, generation) under the seed with this tag XOR-ed into the key's high word.
+CLIP_VIEW_TAG = 0x56494557
+
+
+def clip_view_boxes(seed, generation, views, R, min_permille, flip, fixed):
+    """int32 [views, 4] = (x0, y0, s, flip) in pixels of the R x R image — the library's boxes for that pass.  View 0 is the whole image;
+    fixed: every generation uses generation 0's boxes."""
+    smin = max(2, (R * int(min_permille) + 999) // 1000)
+    out = np.zeros((views, 4), np.int32)
+    out[0] = (0, 0, R, 0)
+    gen = np.uint32(0 if fixed else int(generation) & 0xFFFFFFFF)
+    for v in range(1, views):
+        w = [int(x) for x in philox4x32(np.uint32(v), gen, np.uint32(0), np.uint32(0), np.uint32(seed & 0xFFFFFFFF),
+                                        np.uint32(((seed >> 32) & 0xFFFFFFFF) ^ CLIP_VIEW_TAG))]
+        s = smin + w[0] % (R - smin + 1)
+        out[v] = (w[1] % (R - s + 1), w[2] % (R - s + 1), s, (w[3] & 1) if flip else 0)
+    return out
+
+
 def g_noise_planes(seed, generation, minibatch, channels=FFHQ_CHANNELS):
     """The 1+2*(n-1) noise planes of one G call (one minibatch), execution order."""
     convs, _ = g_layers(channels)

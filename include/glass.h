@@ -117,7 +117,29 @@ int glass_clip_resnet_supported(const int32_t layers[4], int32_t width, int32_t 
  * Returns GLASS_OK, or GLASS_ERR_ARG with the reason in glass_last_error().  glass_engine_create applies the same rule. */
 int glass_clip_preprocess_supported(int32_t gen_res, int32_t clip_res, int32_t clip_resize, int32_t clip_normalize);
 
+/* Crop views (opt-in; off unless glass_engine_set_clip_views is called): a pass scores candidate p as the mean, over `views` views of its
+ * generated image, of the cosine between the view's CLIP feature and the target: sim[p] = (1 / V) sum_v cos(encode_image(view_v(image_p)),
+ * target), summed in fp32 in the order v = 0 .. V - 1; F[p][0] = -sim[p].  The discriminator still sees the whole image.  A view is a box
+ * (x0, y0, s, flip) in pixels of the R x R image: the point-sampled bilinear resize of the default pass (F.interpolate(..., "bilinear",
+ * align_corners=False)) applied to the crop [y0, y0 + s) x [x0, x0 + s), columns reversed where flip = 1.  The boxes are the same for every
+ * candidate of a pass — a function of (noise_seed, generation, view) alone, so candidates are ranked through common crops and chunks, slices
+ * and shards of a population agree.  View 0 is the whole image (0, 0, R, 0).  For v >= 1, with smin = max(2, (R * min_permille + 999) / 1000)
+ * and (w0, w1, w2, w3) = Philox4x32-10 at counter (v, generation, 0, 0) under key (seed_lo, seed_hi ^ 0x56494557): s = smin + w0 % (R - smin
+ * + 1), x0 = w1 % (R - s + 1), y0 = w2 % (R - s + 1), flip = flip_enabled ? w3 & 1 : 0; with fixed = 1 the generation word is 0.
+ *
+ * glass_clip_views_supported: the one rule (host only: callable without a GPU), applied by the setter too.  views in [0, 16] (0: off),
+ * min_permille in [1, 1000], clip_resize 0 (the antialiased modes keep one tap table per image side), and max_pop * views * tokens * 4 *
+ * width — the tower's largest activation — below 2^31 elements.  tokens, width: a ViT's (res / patch)^2 + 1 and clip_width; for a ResNet
+ * tower (res / 4)^2 and the stem width.  Returns GLASS_OK, or GLASS_ERR_ARG with the reason in glass_last_error(). */
+int glass_clip_views_supported(int32_t max_pop, int32_t tokens, int32_t width, int32_t clip_resize, int32_t views, int32_t min_permille);
+/* The boxes of a pass, int32 [views][4] = (x0, y0, s, flip) (host only; the function the pass itself calls).  views in [1, 16]. */
+int glass_host_clip_view_boxes(uint64_t seed, int32_t generation, int32_t views, int32_t gen_res, int32_t min_permille, int32_t flip,
+                               int32_t fixed, int32_t* boxes /*[views][4]*/);
+
 int glass_engine_create(const glass_config* cfg, glass_engine** out);
+/* Turn crop views on (views >= 1; 1 = the whole image alone) or off (0) — between create and finalize, which sizes the CLIP-side buffers for
+ * max_pop * views images: GLASS_ERR_STATE after finalize, and for an engine without a generator.  seed of the boxes: glass_config::noise_seed. */
+int glass_engine_set_clip_views(glass_engine* e, int32_t views, int32_t min_permille, int32_t flip, int32_t fixed);
 void glass_engine_destroy(glass_engine* e);
 
 /* Hand one reference tensor to the engine: `name` is the reference state-dict key
@@ -177,6 +199,9 @@ int glass_engine_evaluate(glass_engine* e, const float* latents, int32_t P, int3
 /* Extra outputs of the same pass (nullable each): CLIP image features [P, clip_embed],
  * raw discriminator logits [P], cosine similarities [P]. Valid after evaluate(). */
 int glass_engine_last_details(glass_engine* e, int32_t P, float* features, float* dis, float* sim);
+/* Crop views: per-view outputs of the last evaluate() (nullable each): features [P][views][clip_embed], cosines [P][views], and the pass's
+ * boxes [views][4].  glass_engine_last_details keeps its shapes then: features[p] is view 0's feature (the whole image), sim[p] the mean. */
+int glass_engine_last_view_details(glass_engine* e, int32_t P, float* features, float* sims, int32_t* boxes);
 
 /* Generator.generate (generator.py:29-34): images host float32 [P,3,R,R] NCHW after
  * biggan_norm (utils.py:14-17).  Used by run.py's callbacks (run.py:45,118). */

@@ -107,6 +107,10 @@ int glass_op_mbstd(int32_t device, int32_t B, int32_t hw, int32_t C, int32_t Cpa
                    const float* x, float* out);
 int glass_op_resize(int32_t device, int32_t B, int32_t R, int32_t S, int32_t ps, const float* y /*[B,3,R,R]*/,
                     float* patches /*[B*G*G, 3*ps*ps]*/);
+/* The crop-view resize of the engine (glass_engine_set_clip_views) on caller images and boxes int32 [V][4] = (x0, y0, s, flip), each inside
+ * the image.  Dense output as glass_op_resize; the row of (image b, view v, patch g) is (b V + v) G G + g. */
+int glass_op_view_patches(int32_t device, int32_t B, int32_t R, int32_t S, int32_t ps, int32_t normalize, int32_t V, const int32_t* boxes,
+                          const float* y /*[B,3,R,R]*/, float* patches /*[B*V*G*G, 3*ps*ps]*/);
 /* The engine's CLIP preprocessing (glass_config::clip_resize / clip_normalize) on caller images: (0, 0) launches what glass_op_resize
  * launches, (0, 1) the normalising instance of that kernel, resize_mode 1 / 2 preprocess_patches_kernel.  Dense output as glass_op_resize. */
 int glass_op_preprocess(int32_t device, int32_t B, int32_t R, int32_t S, int32_t ps, int32_t resize_mode, int32_t normalize,
