@@ -6,7 +6,10 @@ Optional keys the table leaves unset (run.py copies them in from its flags): `cl
 `clip_preprocess` — "reference" (default: the reference's resize, generator.py:45), "antialias" or "clip" (generator.CLIP_PREPROCESS);
 `clip_views` (0, the default: one whole-image score as the reference computes it; N >= 1: the mean similarity over N crop views of each
 image, include/glass.h), with `clip_view_min` (smallest crop side as a fraction of the image side, 0.5), `clip_view_flip` (mirror crops at
-random, True) and `clip_view_fixed` (the same crops in every generation, False)."""
+random, True) and `clip_view_fixed` (the same crops in every generation, False);
+`latent_space` ("z", the default: the reference's search; "w": rows are dlatents, the mapping network is skipped; "w+": one dlatent per
+style layer), `truncation_psi` (1.0: off) and `truncation_cutoff` (None: every layer) — the StyleGAN2 configs only (include/glass.h);
+refused for the BigGAN and GPT2 configs."""
 from .latent import DeepMindBigGANLatentSpace, GPT2LatentSpace, StyleGAN2LatentSpace
 from .models import GPT2, DeepMindBigGAN, StyleGAN2
 from .utils import biggan_denorm, biggan_norm

@@ -7,6 +7,7 @@
 #include "engine.h"
 
 #include <math.h>
+#include <cmath>
 #include <string.h>
 
 #include <stdlib.h>
@@ -154,6 +155,7 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     glass_engine* e = new glass_engine();
     e->cfg = *cfg;
     e->R = gen_res;
+    e->n_lat = cfg->generator == GLASS_GEN_STYLEGAN2 ? 2 * cfg->n_blocks : 0;
     int chunk = cfg->chunk > 0 ? cfg->chunk : std::max(cfg->batch_size, (64 / cfg->batch_size) * cfg->batch_size);   // 288 GB of HBM: one chunk of 64 candidates (36 GB of activations at 1024 px) keeps every launch large
     chunk = std::min(chunk, cfg->max_pop);
     if (chunk % cfg->batch_size != 0) {
@@ -360,7 +362,7 @@ static int alloc_buffers(glass_engine* e) {
         e->d_demod_desc = dptr;
     }
     GLASS_HIP(hipMemset(e->d_dis, 0, (size_t)P * sizeof(float)));
-    e->h_pinned_bytes = std::max((size_t)P * L, (size_t)P * (c.clip_embed + 8)) * sizeof(float);
+    e->h_pinned_bytes = std::max((size_t)P * latent_row_floats(e), (size_t)P * (c.clip_embed + 8)) * sizeof(float);
     GLASS_HIP(hipHostMalloc((void**)&e->h_pinned, e->h_pinned_bytes, hipHostMallocDefault));
     return GLASS_OK;
 }
@@ -539,10 +541,12 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
     if (out_F) REQUIRE(e->has_target, GLASS_ERR_STATE, "set_target() first");
     GLASS_HIP(hipSetDevice(c.device));
     e->launch_error.clear();      // (a pass that returned early through GLASS_HIP must not leave its message to the next one)
-    const int L = c.latent_size;
-    memcpy(e->h_pinned, latents, (size_t)P * L * sizeof(float));
+    // the rows go where run_styles reads them: z rows in front of the mapping network, w rows in its output's place, w+ rows per layer
+    const size_t row = latent_row_floats(e);
+    float* d_rows = e->latent_space == GLASS_LATENT_WPLUS ? e->d_dlat : e->latent_space == GLASS_LATENT_W ? e->d_w0 : e->d_z;
+    memcpy(e->h_pinned, latents, (size_t)P * row * sizeof(float));
     GLASS_HIP(hipEventRecord(e->ev0, e->cur));
-    GLASS_HIP(hipMemcpyAsync(e->d_z, e->h_pinned, (size_t)P * L * sizeof(float), hipMemcpyHostToDevice, e->cur));
+    GLASS_HIP(hipMemcpyAsync(d_rows, e->h_pinned, (size_t)P * row * sizeof(float), hipMemcpyHostToDevice, e->cur));
     const int ps = c.clip_patch, G = c.clip_res / ps;
     const size_t img_elems = (size_t)3 * e->R * e->R;
     // crop views: the boxes of this pass, from (noise_seed, generation) alone — first_mb plays no part, so shards and slices of a population
@@ -735,6 +739,79 @@ extern "C" int glass_engine_set_clip_views(glass_engine* e, int32_t views, int32
     e->view_min_permille = min_permille;
     e->view_flip = flip;
     e->view_fixed = fixed;
+    return GLASS_OK;
+}
+
+// ---- latent spaces / truncation ----------------------------------------------------------------
+extern "C" int glass_host_layer_psi(int32_t n_lat, float psi, int32_t cutoff, float* out) {
+    REQUIRE(out && n_lat >= 1, GLASS_ERR_ARG, "layer_psi: null output or no style layers");
+    REQUIRE(std::isfinite(psi), GLASS_ERR_ARG, "truncation psi must be finite");
+    REQUIRE(psi >= 0.f, GLASS_ERR_ARG, "truncation psi < 0 extrapolates past the average dlatent, away from the candidate: psi must be in [0, 1]");
+    REQUIRE(psi <= 1.f, GLASS_ERR_ARG, "truncation psi > 1 extrapolates away from the average dlatent instead of towards it: psi must be in [0, 1]");
+    REQUIRE(cutoff >= -1 && cutoff <= n_lat, GLASS_ERR_ARG,
+            "truncation cutoff must be in [-1, n_lat] (-1: every layer; n_lat = " + std::to_string(n_lat) + " style layers)");
+    const int ncut = cutoff < 0 ? n_lat : cutoff;
+    for (int l = 0; l < n_lat; ++l) out[l] = l < ncut ? psi : 1.f;       // stylegan2/models.py:276-284
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_latent_space(glass_engine* e, int32_t space) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(!e->finalized, GLASS_ERR_STATE, "set_latent_space: the engine is finalized (its buffers are sized in finalize: call it before)");
+    REQUIRE(e->n_lat > 0, GLASS_ERR_STATE, "set_latent_space: W / W+ are latent spaces of a StyleGAN2 generator; this engine has none");
+    REQUIRE(space == GLASS_LATENT_Z || space == GLASS_LATENT_W || space == GLASS_LATENT_WPLUS, GLASS_ERR_ARG,
+            "set_latent_space: space must be 0 (z), 1 (w) or 2 (w+)");
+    e->latent_space = space;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_truncation(glass_engine* e, float psi, int32_t cutoff) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(e->n_lat > 0, GLASS_ERR_STATE, "set_truncation: the truncation trick belongs to a StyleGAN2 generator; this engine has none");
+    std::vector<float> lp(e->n_lat);
+    if (int rc = glass_host_layer_psi(e->n_lat, psi, cutoff, lp.data())) return rc;
+    if (!e->finalized) {      // recorded; finalize checks dlatent_avg and sizes the per-layer buffer
+        e->trunc_psi = psi;
+        e->trunc_cutoff = cutoff;
+        e->trunc_before_finalize = true;
+        return GLASS_OK;
+    }
+    const LatPlan plan = plan_dlatents(e->latent_space, psi, cutoff, e->n_lat);
+    REQUIRE(!plan.expand || !e->dlatent_avg.empty(), GLASS_ERR_STATE,
+            "set_truncation: missing tensor: dlatent_avg (psi != 1 interpolates towards it; load it before finalize)");
+    REQUIRE(!plan.layered || e->d_dlat, GLASS_ERR_STATE,
+            "set_truncation: a cutoff inside (0, n_lat) gives every style layer its own row, and this engine was finalized without the "
+            "per-layer buffer: call set_truncation (any values) before finalize, or use space w+");
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    e->trunc_psi = psi;
+    e->trunc_cutoff = cutoff;
+    return plan.expand ? upload_lat_table(e) : GLASS_OK;
+}
+
+extern "C" int glass_engine_latent_row(glass_engine* e, int32_t* floats_per_row, int32_t* n_lat) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    if (floats_per_row) *floats_per_row = (int32_t)latent_row_floats(e);
+    if (n_lat) *n_lat = e->n_lat;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_map_latents(glass_engine* e, const float* z, int32_t P, float* out_w) {
+    REQUIRE(e && z && out_w, GLASS_ERR_ARG, "null argument");
+    REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first (weights not loaded)");
+    REQUIRE(e->n_lat > 0, GLASS_ERR_STATE, "map_latents: this engine has no StyleGAN2 mapping network");
+    REQUIRE(P > 0 && P <= e->cfg.max_pop, GLASS_ERR_ARG, "map_latents: P out of range (1 .. max_pop)");
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    const size_t bytes = (size_t)P * e->cfg.latent_size * sizeof(float);
+    memcpy(e->h_pinned, z, bytes);
+    GLASS_HIP(hipMemcpyAsync(e->d_z, e->h_pinned, bytes, hipMemcpyHostToDevice, e->cur));
+    const bool prof = e->profiling;
+    e->profiling = false;           // (profile rows belong to a pass)
+    run_mapping(e, P);
+    e->profiling = prof;
+    GLASS_HIP(hipMemcpyAsync(e->h_pinned, e->d_w0, bytes, hipMemcpyDeviceToHost, e->cur));
+    GLASS_HIP(hipStreamSynchronize(e->cur));
+    GLASS_HIP(hipGetLastError());
+    memcpy(out_w, e->h_pinned, bytes);
     return GLASS_OK;
 }
 

@@ -154,6 +154,17 @@ struct glass_engine {
     std::vector<GConv> gconv;
     std::vector<GRgb> grgb;
     BgState bg;
+    // ---- dlatents: latent space + truncation trick (glass_engine_set_latent_space / set_truncation; stylegan2.cpp plan_dlatents) ----
+    int latent_space = GLASS_LATENT_Z, n_lat = 0;   // n_lat = 2 n_blocks style layers (stylegan2/models.py:890-896); 0: not a StyleGAN2 engine
+    float trunc_psi = 1.f;
+    int trunc_cutoff = -1;
+    bool trunc_before_finalize = false;   // set_truncation was called before finalize: the per-layer buffer below is allocated
+    std::vector<float> dlatent_avg;       // host [L]; empty: the tensor was not loaded
+    float* d_lat_tab = nullptr;           // psi[lat_pad] | dlatent_avg[L]: allocated with the first truncation that needs it
+    int lat_pad = 0;
+    float* d_dlat = nullptr;              // [max_pop][n_lat][L] per-layer dlatents: only for space W+ or after trunc_before_finalize
+    StyleTile* d_style_tiles = nullptr;   // (segment, n0) tiles of styles_layered_kernel, built with d_dlat
+    int n_style_tiles = 0;
     // ---- D ----
     float *d_frgb_w = nullptr, *d_frgb_b = nullptr;
     std::vector<DBlock> dblk;
@@ -354,6 +365,15 @@ GemmParams gemm_params(const half_t* a, const half_t* w, int M, int N, int K, co
 int finalize_generator(glass_engine* e);
 int finalize_discriminator(glass_engine* e);
 int upload_noise(glass_engine* e, int P, int generation, int first_mb, const glass_noise* noise);
+// What a pass launches between the uploaded rows and the style table, decided before anything is launched:
+//   map: pixel norm + mapping network (space z).  expand: dlatent_expand_kernel applies layer_psi (psi != 1 on at least one layer).
+//   layered: the rows differ per style layer (space w+, or a cutoff inside (0, n_lat)): [P][n_lat][L] in d_dlat and
+//   styles_layered_kernel; otherwise ONE row per candidate in d_w0 and the single launch_dense styles launch.
+struct LatPlan { bool map, expand, layered; };
+LatPlan plan_dlatents(int space, float psi, int cutoff, int n_lat);
+size_t latent_row_floats(const glass_engine* e);   // floats evaluate / generate read per row
+int upload_lat_table(glass_engine* e);             // layer_psi | dlatent_avg -> d_lat_tab (allocates it on first use)
+void run_mapping(glass_engine* e, int P);          // d_z -> d_w0
 void run_styles(glass_engine* e, int P);
 void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, const half_t* x, long long xbs, half_t* const pp[2],
                   const float* yprev, float* const yb[2], const half_t** x_out, const float** y_out);

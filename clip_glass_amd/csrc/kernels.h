@@ -62,6 +62,16 @@ struct DenseDesc {
     const float* eps_row; int eps_stride;
 };
 void launch_dense_multi(const DenseDesc* d_desc, int n_desc, int max_N, int P, int in_sq, int mode, hipStream_t st);
+// --- dlatents (dlatent.hip): truncation trick, W / W+ latent spaces ------------------
+// dst[P][n_layers][L] = lerp(avg, src, psi[l]) with torch.lerp's rule; the row of (p, l) is read at src + p * src_row + l * src_layer
+// (src_layer 0: one row per candidate), in place allowed.  tab = psi[n_pad] | avg[L], n_pad = n_layers rounded up to 4.  L % 4 == 0.
+void launch_dlatent_expand(const float* src, long long src_row, long long src_layer, float* dst, const float* tab, int n_pad, int n_layers,
+                           int P, int L, hipStream_t st);
+// one 64-wide piece of a style segment: columns [col0, col0 + n) of the [P][S_total] style table read dlatent row `lat`
+struct StyleTile { int col0, n, lat, pad; };
+// out[p][col] = sum_k dlat[p][lat(col)][k] * wt[k][col] + bias[col] over the tile list: dense_kernel's bits per element
+void launch_styles_layered(const float* dlat, int n_lat, int L, int P, const float* wt, int S_total, const float* bias, float* out,
+                           const StyleTile* d_tiles, int n_tiles, hipStream_t st);
 // per (p, layer): smax = max|s|, s /= smax, eps_row = eps / smax^2
 void launch_style_norm(float* s, int ld, int P, int n_layers, const int* d_off, const int* d_len,
                        float* smax, float* eps_row, float eps, hipStream_t st);

@@ -3,6 +3,7 @@
 // NHWC fp16 activations, wave64 reductions.
 #include "common.h"
 #include "kernels.h"
+#include "dense_body.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -33,69 +34,17 @@ void launch_pixelnorm(const float* z, float* out, int P, int L, float eps, hipSt
 }
 
 // ---- small-M fp32 dense: DenseLayer (modules.py:786-798) for the mapping network,
-// the 26 style affines (one launch), demodulation coefficients, CLIP proj, D dense1.
-#define DENSE_PB 16
-#define DENSE_KT 128
-__device__ __forceinline__ void dense_body(const float* x, int ldx, int P, int K, const float* wt, int N,
-                                           const float* bias, float* out, int ldo, int in_sq, int mode,
-                                           const float* eps_row, int eps_stride, int bx, int by) {
-    __shared__ float xs[DENSE_PB][DENSE_KT];
-    const int t = threadIdx.x;
-    const int n = bx * 64 + (t & 63);
-    const int pg = t >> 6;
-    const int p0 = by * DENSE_PB;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < K; k0 += DENSE_KT) {
-        for (int e = t; e < DENSE_PB * DENSE_KT; e += 256) {
-            const int pr = e / DENSE_KT, kk = e - pr * DENSE_KT;
-            float v = 0.f;
-            if (p0 + pr < P && k0 + kk < K) v = x[(long long)(p0 + pr) * ldx + k0 + kk];
-            xs[pr][kk] = in_sq ? v * v : v;
-        }
-        __syncthreads();
-        if (n < N) {
-            const int kmax = min(DENSE_KT, K - k0);
-            int kk = 0;
-            for (; kk + 16 <= kmax; kk += 16) {      // 16 weight loads in flight (a one-load-per-iteration loop is a chain
-                float w[16];                         // of L2 round trips: 512 of them per mapping layer)
-#pragma unroll
-                for (int u = 0; u < 16; ++u) w[u] = wt[(long long)(k0 + kk + u) * N + n];
-#pragma unroll
-                for (int u = 0; u < 16; ++u)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(w[u], xs[pg * 4 + j][kk + u], acc[j]);   // explicit FMA for every row:
-                // left to -ffp-contract the compiler packed rows (0, 1) as v_pk_fma_f32 and rows (2, 3) as mul + add, so a row's last bit
-                // depended on its POSITION in the launch (found by the full-size text-tower test, r04)
-            }
-            for (; kk < kmax; ++kk) {
-                const float w = wt[(long long)(k0 + kk) * N + n];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(w, xs[pg * 4 + j][kk], acc[j]);
-            }
-        }
-        __syncthreads();
-    }
-    if (n >= N) return;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int p = p0 + pg * 4 + j;
-        if (p >= P) continue;
-        float v = acc[j] + (bias ? bias[n] : 0.f);
-        if (mode == 1) v = lrelu_sqrt2(v);
-        else if (mode == 2) v = rsqrtf(v + eps_row[(long long)p * eps_stride]);
-        out[(long long)p * ldo + n] = v;
-    }
-}
+// the 26 style affines (one launch), demodulation coefficients, CLIP proj, D dense1.  The tile itself: dense_body.h.
 __global__ __launch_bounds__(256) void dense_kernel(const float* x, int ldx, int P, int K, const float* wt,
                                                     int N, const float* bias, float* out, int ldo, int in_sq,
                                                     int mode, const float* eps_row, int eps_stride) {
-    dense_body(x, ldx, P, K, wt, N, bias, out, ldo, in_sq, mode, eps_row, eps_stride, blockIdx.x, blockIdx.y);
+    dense_body(x, ldx, P, K, wt, N, N, bias, out, ldo, in_sq, mode, eps_row, eps_stride, blockIdx.x, blockIdx.y);
 }
 // many independent small problems in ONE launch (blockIdx.z = problem): the 17 demodulation tables
 __global__ __launch_bounds__(256) void dense_multi_kernel(const DenseDesc* d, int P, int in_sq, int mode) {
     const DenseDesc q = d[blockIdx.z];
     if ((int)blockIdx.x * 64 >= q.N) return;
-    dense_body(q.x, q.ldx, P, q.K, q.wt, q.N, q.bias, q.out, q.ldo, in_sq, mode, q.eps_row, q.eps_stride, blockIdx.x,
+    dense_body(q.x, q.ldx, P, q.K, q.wt, q.N, q.N, q.bias, q.out, q.ldo, in_sq, mode, q.eps_row, q.eps_stride, blockIdx.x,
                blockIdx.y);
 }
 void launch_dense_multi(const DenseDesc* d_desc, int n_desc, int max_N, int P, int in_sq, int mode, hipStream_t st) {

@@ -144,7 +144,55 @@ int finalize_generator(glass_engine* e) {
     rc = upload(e, &e->d_style_off, e->style_off);
     if (rc) return rc;
     rc = upload(e, &e->d_style_len, e->style_len);
-    return rc;
+    if (rc) return rc;
+    // dlatent_avg (stylegan2/models.py:225-226: a buffer of the Generator itself), optional: only the truncation trick reads it
+    if (const HostTensor* avg = find(e, "dlatent_avg")) {
+        REQUIRE(numel(avg) == (size_t)L, GLASS_ERR_ARG, "bad shape: dlatent_avg (expected [latent_size])");
+        e->dlatent_avg = avg->data;
+    }
+    const LatPlan lp = plan_dlatents(e->latent_space, e->trunc_psi, e->trunc_cutoff, e->n_lat);
+    REQUIRE(!lp.expand || !e->dlatent_avg.empty(), GLASS_ERR_STATE, "missing tensor: dlatent_avg (truncation psi != 1 interpolates towards it)");
+    if (e->latent_space == GLASS_LATENT_WPLUS || e->trunc_before_finalize) {
+        // per-layer rows: the [max_pop][n_lat][L] buffer, and the (segment, n0) tiles of styles_layered_kernel.  Style layer -> dlatent index
+        // (models.py:969-1014): conv i in execution order reads row i; the toRGB of block b reads the row of the next block's first conv,
+        // 2 b + 1 — which for the last block is the last row.
+        std::vector<int> lat(e->n_style, 0);
+        for (size_t i = 0; i < e->gconv.size(); ++i) lat[e->gconv[i].style_idx] = (int)i;
+        for (int b = 0; b < c.n_blocks; ++b) lat[e->grgb[b].style_idx] = 2 * b + 1;
+        std::vector<StyleTile> tiles;
+        for (int j = 0; j < e->n_style; ++j)
+            for (int n0 = 0; n0 < e->style_len[j]; n0 += 64)
+                tiles.push_back(StyleTile{e->style_off[j] + n0, std::min(64, e->style_len[j] - n0), lat[j], 0});
+        e->n_style_tiles = (int)tiles.size();
+        if ((rc = upload(e, &e->d_style_tiles, tiles))) return rc;
+        if ((rc = dev_alloc(e, &e->d_dlat, (size_t)c.max_pop * e->n_lat * L))) return rc;
+    }
+    return lp.expand ? upload_lat_table(e) : GLASS_OK;
+}
+
+LatPlan plan_dlatents(int space, float psi, int cutoff, int n_lat) {
+    const int ncut = cutoff < 0 ? n_lat : cutoff;
+    LatPlan lp;
+    lp.map = space == GLASS_LATENT_Z;
+    lp.expand = psi != 1.f && ncut > 0;                                          // models.py:276
+    lp.layered = space == GLASS_LATENT_WPLUS || (lp.expand && ncut < n_lat);    // otherwise one row serves every layer
+    return lp;
+}
+
+size_t latent_row_floats(const glass_engine* e) {
+    return (size_t)e->cfg.latent_size * (e->latent_space == GLASS_LATENT_WPLUS ? (size_t)e->n_lat : 1);
+}
+
+int upload_lat_table(glass_engine* e) {
+    const int L = e->cfg.latent_size;
+    e->lat_pad = (e->n_lat + 3) / 4 * 4;
+    std::vector<float> tab((size_t)e->lat_pad + L, 1.f);
+    if (int rc = glass_host_layer_psi(e->n_lat, e->trunc_psi, e->trunc_cutoff, tab.data())) return rc;
+    std::copy(e->dlatent_avg.begin(), e->dlatent_avg.end(), tab.begin() + e->lat_pad);
+    if (!e->d_lat_tab)
+        if (int rc = dev_alloc(e, &e->d_lat_tab, tab.size())) return rc;
+    GLASS_HIP(hipMemcpy(e->d_lat_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    return GLASS_OK;
 }
 
 int finalize_discriminator(glass_engine* e) {
@@ -254,28 +302,47 @@ int upload_noise(glass_engine* e, int P, int generation, int first_mb, const gla
     return GLASS_OK;
 }
 
-void run_styles(glass_engine* e, int P) {
+void run_mapping(glass_engine* e, int P) {
     const glass_config& c = e->cfg;
     const int L = c.latent_size;
-    {
-        Prof pr(e, "mapping", 2.0 * P * L * L * c.mapping_layers, 4.0 * L * L * c.mapping_layers);
-        if (c.mapping_layers < 1 ||
-            !launch_mapping_fused(e->d_z, e->d_w0, P, L, 1e-8f, e->map_wt.data(), e->map_b.data(), c.mapping_layers, e->cur)) {
-            launch_pixelnorm(e->d_z, e->d_w0, P, L, 1e-8f, e->cur);
-            float *a = e->d_w0, *b = e->d_w1;
-            for (int i = 0; i < c.mapping_layers; ++i) {
-                if (L % 64 == 0 && L <= 768) launch_dense_splitk(a, L, P, L, e->map_wt[i], L, e->map_b[i], b, L, 1, e->cur);
-                else launch_dense(a, L, P, L, e->map_wt[i], L, e->map_b[i], b, L, 0, 1, nullptr, 0, e->cur);
-                std::swap(a, b);
-            }
-            if (a != e->d_w0)  // result must end in d_w0
-                hipMemcpyAsync(e->d_w0, a, (size_t)P * L * sizeof(float), hipMemcpyDeviceToDevice, e->cur);
+    Prof pr(e, "mapping", 2.0 * P * L * L * c.mapping_layers, 4.0 * L * L * c.mapping_layers);
+    if (c.mapping_layers < 1 ||
+        !launch_mapping_fused(e->d_z, e->d_w0, P, L, 1e-8f, e->map_wt.data(), e->map_b.data(), c.mapping_layers, e->cur)) {
+        launch_pixelnorm(e->d_z, e->d_w0, P, L, 1e-8f, e->cur);
+        float *a = e->d_w0, *b = e->d_w1;
+        for (int i = 0; i < c.mapping_layers; ++i) {
+            if (L % 64 == 0 && L <= 768) launch_dense_splitk(a, L, P, L, e->map_wt[i], L, e->map_b[i], b, L, 1, e->cur);
+            else launch_dense(a, L, P, L, e->map_wt[i], L, e->map_b[i], b, L, 0, 1, nullptr, 0, e->cur);
+            std::swap(a, b);
         }
+        if (a != e->d_w0)  // result must end in d_w0
+            hipMemcpyAsync(e->d_w0, a, (size_t)P * L * sizeof(float), hipMemcpyDeviceToDevice, e->cur);
+    }
+}
+
+// The uploaded rows are in d_z (space z), d_w0 (w) or d_dlat (w+): run_pass put them there.
+void run_styles(glass_engine* e, int P) {
+    const glass_config& c = e->cfg;
+    const int L = c.latent_size, NL = e->n_lat;
+    const LatPlan lp = plan_dlatents(e->latent_space, e->trunc_psi, e->trunc_cutoff, NL);
+    if (lp.layered && !e->d_dlat) {   // (the setters refuse this; a pass never reads a buffer that is not there)
+        if (e->launch_error.empty()) e->launch_error = "per-layer dlatents without their buffer";
+        return;
+    }
+    if (lp.map) run_mapping(e, P);
+    if (lp.expand) {
+        const int nl = lp.layered ? NL : 1;
+        Prof pr(e, "dlatents", 3.0 * P * nl * L, 4.0 * L * (P * (double)(nl + (e->latent_space == GLASS_LATENT_WPLUS ? nl : 1)) + 1));
+        if (!lp.layered) launch_dlatent_expand(e->d_w0, L, 0, e->d_w0, e->d_lat_tab, e->lat_pad, 1, P, L, e->cur);                       // in place
+        else if (e->latent_space == GLASS_LATENT_WPLUS) launch_dlatent_expand(e->d_dlat, (long long)NL * L, L, e->d_dlat, e->d_lat_tab, e->lat_pad, NL, P, L, e->cur);   // in place
+        else launch_dlatent_expand(e->d_w0, L, 0, e->d_dlat, e->d_lat_tab, e->lat_pad, NL, P, L, e->cur);
     }
     {
-        Prof pr(e, "styles", 2.0 * P * L * e->S_total, 4.0 * L * e->S_total);
-        launch_dense(e->d_w0, L, P, L, e->style_wt, e->S_total, e->style_b, e->d_s, e->S_total, 0, 0, nullptr, 0,
-                     e->cur);
+        Prof pr(e, "styles", 2.0 * P * L * e->S_total, 4.0 * L * e->S_total + (lp.layered ? 4.0 * P * NL * L : 0.0));
+        if (lp.layered)
+            launch_styles_layered(e->d_dlat, NL, L, P, e->style_wt, e->S_total, e->style_b, e->d_s, e->d_style_tiles, e->n_style_tiles, e->cur);
+        else
+            launch_dense(e->d_w0, L, P, L, e->style_wt, e->S_total, e->style_b, e->d_s, e->S_total, 0, 0, nullptr, 0, e->cur);
         launch_style_norm(e->d_s, e->S_total, P, e->n_style, e->d_style_off, e->d_style_len, e->d_smax, e->d_epsrow,
                           1e-8f, e->cur);
         launch_bg_to_half(e->d_s, e->d_s16, (long long)P * e->S_total, e->cur);   // fp16 table for the LDS-tiled kernels

@@ -77,6 +77,13 @@ def load_library(path=None):
         lib.glass_host_clip_view_boxes.argtypes = [C.c_uint64] + [C.c_int32] * 6 + [ip]
         lib.glass_engine_set_clip_views.argtypes = [C.c_void_p] + [C.c_int32] * 4
         lib.glass_engine_last_view_details.argtypes = [C.c_void_p, C.c_int32, fp, fp, ip]
+    if hasattr(lib, "glass_engine_set_latent_space"):   # (absent from older A/B builds loaded through GLASS_LIB)
+        ip = C.POINTER(C.c_int32)
+        lib.glass_host_layer_psi.argtypes = [C.c_int32, C.c_float, C.c_int32, fp]
+        lib.glass_engine_set_latent_space.argtypes = [C.c_void_p, C.c_int32]
+        lib.glass_engine_set_truncation.argtypes = [C.c_void_p, C.c_float, C.c_int32]
+        lib.glass_engine_latent_row.argtypes = [C.c_void_p, ip, ip]
+        lib.glass_engine_map_latents.argtypes = [C.c_void_p, fp, C.c_int32, fp]
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -178,6 +185,30 @@ def host_clip_view_boxes(seed, generation, views, gen_res, min_permille, flip, f
     return out
 
 
+LATENT_SPACES = {"z": 0, "w": 1, "w+": 2}     # GLASS_LATENT_Z / _W / _WPLUS
+
+
+def latent_space_id(name):
+    """GLASS_LATENT_* of a latent space's name; ValueError lists the names otherwise."""
+    if name not in LATENT_SPACES:
+        raise ValueError("unknown latent_space %r: expected one of %s" % (name, ", ".join(LATENT_SPACES)))
+    return LATENT_SPACES[name]
+
+
+def truncation_cutoff_arg(cutoff):
+    """None (every layer, as the reference's set_truncation takes it) -> the ABI's -1."""
+    return -1 if cutoff is None else int(cutoff)
+
+
+def host_layer_psi(n_lat, psi, cutoff=None):
+    """float32 [n_lat]: the per-layer psi of the truncation trick (glass_host_layer_psi: the rule the setter and the pass use).  Host only;
+    RuntimeError with the library's reason for a psi outside [0, 1] or a cutoff outside [-1, n_lat]."""
+    lib = load_library()
+    out = np.empty((max(int(n_lat), 1),), dtype=np.float32)
+    _check(lib, lib.glass_host_layer_psi(int(n_lat), float(psi), truncation_cutoff_arg(cutoff), _fp(out)))
+    return out
+
+
 def device_info(device=0):
     lib = load_library()
     name = C.create_string_buffer(256)
@@ -193,7 +224,8 @@ class Engine:
     def __init__(self, channels, latent_size=512, mapping_layers=8, batch_size=4, use_discriminator=True,
                  n_obj=2, max_pop=64, chunk=0, clip=(768, 12, 12, 32, 224, 512), noise_mode=1, noise_seed=0,
                  mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0, clip_resnet=None,
-                 clip_views=0, clip_view_min=0.5, clip_view_flip=True, clip_view_fixed=False):
+                 clip_views=0, clip_view_min=0.5, clip_view_flip=True, clip_view_fixed=False,
+                 latent_space="z", truncation_psi=1.0, truncation_cutoff=None):
         """`biggan` = dict(layers=[(up, in_mult, out_mult), ...], attention_pos, ch, z_dim, num_classes, n_stats, eps,
         truncation) selects the BigGAN-deep generator (channels must then be empty, no discriminator).
         clip_resize / clip_normalize: how a generated image is prepared for CLIP (include/glass.h); (0, 0) is the reference's way.
@@ -201,7 +233,11 @@ class Engine:
         `clip` is ignored then.
         clip_views = V >= 1 scores a candidate as the mean similarity over V crop views of its image (include/glass.h: view 0 is the whole
         image, the others random boxes at least clip_view_min of the side, mirrored at random unless clip_view_flip is False, redrawn
-        every generation unless clip_view_fixed); 0 (default) is the reference's single whole-image score."""
+        every generation unless clip_view_fixed); 0 (default) is the reference's single whole-image score.
+        latent_space "z" (default) / "w" / "w+" and truncation_psi / truncation_cutoff (StyleGAN2 only; include/glass.h): what a row of
+        evaluate / generate is, and the truncation trick applied to it.  The defaults call neither setter: the reference's raw generator
+        on z.  A psi or cutoff given here is set before finalize, which then keeps the per-layer buffer a later set_truncation with a
+        cutoff needs."""
         self.lib = load_library()
         cfg = GlassConfigResnet()
         cfg.device = device
@@ -251,6 +287,16 @@ class Engine:
                 msg = self.lib.glass_last_error().decode()
                 self.close()
                 raise RuntimeError("libglass error %d: %s" % (rc, msg))
+
+        self.latent_space = latent_space
+        try:
+            if latent_space != "z":
+                _check(self.lib, self.lib.glass_engine_set_latent_space(self._h, latent_space_id(latent_space)))
+            if float(truncation_psi) != 1.0 or truncation_cutoff is not None:
+                self.set_truncation(truncation_psi, truncation_cutoff)
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -316,6 +362,42 @@ class Engine:
                                                             int(purpose), out.ctypes.data_as(ip)))
         return out
 
+    # --- latent spaces / truncation -------------------------------------------
+    def set_latent_space(self, name):
+        """Between construction and finalize(): "z", "w" or "w+" (include/glass.h)."""
+        _check(self.lib, self.lib.glass_engine_set_latent_space(self._h, latent_space_id(name)))
+        self.latent_space = name
+
+    def set_truncation(self, psi, cutoff=None):
+        """The truncation trick: dlatents = lerp(dlatent_avg, dlatents, layer_psi); psi in [0, 1], cutoff None = every layer."""
+        _check(self.lib, self.lib.glass_engine_set_truncation(self._h, float(psi), truncation_cutoff_arg(cutoff)))
+
+    def latent_row(self):
+        """(floats_per_row, n_lat): what evaluate / generate read per row, and the number of style layers (0: not a StyleGAN2 engine)."""
+        if not hasattr(self.lib, "glass_engine_latent_row"):     # (an older A/B build loaded through GLASS_LIB: z rows only)
+            return int(self.cfg.latent_size), 0
+        w, n = C.c_int32(), C.c_int32()
+        _check(self.lib, self.lib.glass_engine_latent_row(self._h, C.byref(w), C.byref(n)))
+        return w.value, n.value
+
+    def map_latents(self, z):
+        """Pixel norm + mapping network, untruncated: z float32 [P, latent_size] -> w [P, latent_size], P <= max_pop."""
+        z = _f32(z)
+        if z.ndim != 2 or z.shape[1] != self.cfg.latent_size:
+            raise ValueError("map_latents: z must be [P, %d], got %r" % (self.cfg.latent_size, z.shape))
+        out = np.empty_like(z)
+        _check(self.lib, self.lib.glass_engine_map_latents(self._h, _fp(z), z.shape[0], _fp(out)))
+        return out
+
+    def _rows(self, x):
+        """The population as contiguous float32 rows of the engine's width — checked HERE: the library sees a pointer, and a short row
+        would be read past its end."""
+        z = _f32(x)
+        width = self.latent_row()[0]
+        if z.ndim != 2 or z.shape[1] != width:
+            raise ValueError("latent rows of space %r must be [P, %d], got %r" % (self.latent_space, width, z.shape))
+        return z
+
     # --- the pass ------------------------------------------------------------
     def _noise_arg(self, noise):
         """noise: list (per minibatch) of lists (per layer) of [res,res] float32 planes."""
@@ -328,7 +410,7 @@ class Engine:
 
     def evaluate(self, x, generation=0, first_minibatch=0, noise=None):
         """problem.py:14-29 — returns F float32 [P, n_obj]."""
-        z = _f32(x)
+        z = self._rows(x)
         P = z.shape[0]
         out = np.empty((P, self.cfg.n_obj), dtype=np.float32)
         gn, keep = self._noise_arg(noise)
@@ -339,7 +421,7 @@ class Engine:
 
     def generate(self, x, generation=0, first_minibatch=0, noise=None):
         """generator.py:29-34 — images float32 [P,3,R,R] in [0,1]."""
-        z = _f32(x)
+        z = self._rows(x)
         P = z.shape[0]
         out = np.empty((P, 3, self.res, self.res), dtype=np.float32)
         gn, keep = self._noise_arg(noise)

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import synth
-from .engine import (Engine, clip_geometry_supported, clip_resnet_supported, clip_view_permille, clip_views_supported,
+from .engine import (LATENT_SPACES, Engine, clip_geometry_supported, clip_resnet_supported, clip_view_permille, clip_views_supported,
                      clip_views_tower_rows)
 from .utils import save_grid, save_image
 
@@ -48,6 +48,29 @@ CLIP_RESNET_TEXT_MODELS = {
 # CLIP was trained with (clip/clip.py:68-74), antialiased bicubic Resize + Normalize — a deliberate departure from the reference.
 CLIP_PREPROCESS = {"reference": (0, 0), "antialias": (1, 0), "clip": (2, 1)}
 DEFAULT_CLIP_PREPROCESS = "reference"
+
+
+DEFAULT_LATENT_SPACE = "z"
+
+
+def latent_options(config):
+    """(latent_space, truncation_psi, truncation_cutoff) of a config, defaults ("z", 1.0, None) — the reference's search: z through the raw
+    generator.  ValueError with a plain message for an unknown space, and for any non-default value on a config whose generator is not a
+    StyleGAN2 (BigGAN has its own `truncation`; GPT2 has no dlatents)."""
+    def opt(key, default):       # (a flag the command line left unset arrives as None)
+        v = getattr(config, key, None)
+        return default if v is None else v
+    space = opt("latent_space", DEFAULT_LATENT_SPACE)
+    psi = float(opt("truncation_psi", 1.0))
+    cutoff = getattr(config, "truncation_cutoff", None)
+    cutoff = None if cutoff is None else int(cutoff)
+    if space not in LATENT_SPACES:
+        raise ValueError("unknown latent_space %r: expected one of %s" % (space, ", ".join(LATENT_SPACES)))
+    name = str(getattr(config, "config", ""))
+    if (space != DEFAULT_LATENT_SPACE or psi != 1.0 or cutoff is not None) and name.split("_")[0] != "StyleGAN2":
+        raise ValueError("latent_space / truncation_psi / truncation_cutoff belong to the StyleGAN2 configs (a mapping network and an "
+                         "average dlatent); config %r has neither: leave them unset" % name)
+    return space, psi, cutoff
 
 
 def clip_model_geometry(name):
@@ -282,6 +305,8 @@ class Generator:
         clip_resize, clip_normalize = clip_preprocess_fields(self.clip_preprocess)
         # crop views (opt-in, include/glass.h): a candidate's score is the mean similarity over `clip_views` views of its image
         self.clip_views = int(getattr(config, "clip_views", 0) or 0)
+        # latent space / truncation trick (opt-in, include/glass.h); refused here for the BigGAN and GPT2 configs, before anything is loaded
+        self.latent_space, self.truncation_psi, self.truncation_cutoff = latent_options(config)
         def view_opt(key, default):      # (a flag the command line left unset arrives as None)
             v = getattr(config, key, None)
             return default if v is None else v
@@ -335,10 +360,15 @@ class Generator:
                                  n_obj=config.problem_args["n_obj"], max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  noise_mode=getattr(config, "noise_mode", 1),
                                  noise_seed=getattr(config, "noise_seed", 0), device=device, clip_resize=clip_resize,
-                                 clip_normalize=clip_normalize, **tower)
+                                 clip_normalize=clip_normalize, latent_space=self.latent_space,
+                                 truncation_psi=self.truncation_psi, truncation_cutoff=self.truncation_cutoff, **tower)
+            if getattr(self.model, "dlatent_avg", None) is not None:
+                self.engine.load_state({"dlatent_avg": self.model.dlatent_avg})     # the Generator's own buffer: no sub-model prefix
         self.engine.load_state(self.model.state)
         self.engine.load_state(clip_state)
         self.engine.finalize()
+        if self.latent_space != DEFAULT_LATENT_SPACE:       # the row width of latent.StyleGAN2LatentSpace / operators follows the loaded network
+            config.n_lat = self.engine.latent_row()[1]
         if getattr(config, "target_features", None) is not None:            # pre-computed text feature
             self.text_features = np.asarray(config.target_features, np.float32).reshape(1, -1)
         else:                                                               # generator.py:23-24
@@ -351,6 +381,16 @@ class Generator:
             from .parallel import ShardedEvaluator
             self.sharder = ShardedEvaluator(self.engine, dist, dist.get_rank(), dist.get_world_size(), config.batch_size,
                                             device=device)
+
+    def map_latents(self, z):
+        """z [N, dim_z] -> untruncated dlatents w [N, dim_z] through the engine's mapping network, in slices of its capacity."""
+        z = np.asarray(z, dtype=np.float32)
+        cap = int(self.engine.cfg.max_pop)
+        return np.concatenate([self.engine.map_latents(z[i:i + cap]) for i in range(0, z.shape[0], cap)]) if z.shape[0] else z
+
+    def latent_width(self):
+        """Floats per population row in this Generator's latent space."""
+        return self.engine.latent_row()[0]
 
     def _clip_tower(self, geom):
         """Record the chosen image tower (clip_geometry: the engine's six shared fields; clip_resnet: the ResNet tuple or None) and

@@ -3,12 +3,24 @@ the device copy happens inside glass_engine_evaluate)."""
 import numpy as np
 
 
+def stylegan2_n_lat(config):
+    """Style layers of the config's generator, 2 per resolution (stylegan2/models.py:890-896): 18 at 1024 px.  `config.n_lat` — what
+    the Generator read from the loaded network — wins over the channel table."""
+    from . import synth
+    n_lat = getattr(config, "n_lat", None)
+    return int(n_lat) if n_lat else 2 * len(getattr(config, "channels", synth.FFHQ_CHANNELS))
+
+
 class StyleGAN2LatentSpace:
-    """latent.py:27-41"""
+    """latent.py:27-41.  Rows of the config's latent space (`config.latent_space`, default "z"): dim_z floats for z and w, n_lat * dim_z
+    (layer-major) for w+.  The attribute keeps the reference's name `z` whatever the space; state_dict() says what the rows are."""
+    STATE_KEYS = {"z": "z", "w": "w", "w+": "w_plus"}
 
     def __init__(self, config):
         self.config = config
-        self.z = np.random.randn(self.config.batch_size, self.config.dim_z).astype(np.float32)
+        self.space = getattr(config, "latent_space", None) or "z"
+        self.width = self.config.dim_z * (stylegan2_n_lat(config) if self.space == "w+" else 1)
+        self.z = np.random.randn(self.config.batch_size, self.width).astype(np.float32)
 
     def set_values(self, z):
         self.z = np.asarray(z, dtype=np.float32)
@@ -25,7 +37,7 @@ class StyleGAN2LatentSpace:
         return self.z
 
     def state_dict(self):       # run.py:101 torch.save(ls.state_dict()) (the reference's nn.Module holds z as a plain tensor: its
-        return {"z": self.z}    # state_dict is empty; the latents are kept here so ls_result is usable)
+        return {self.STATE_KEYS[self.space]: self.z}    # state_dict is empty; the latents are kept here so ls_result is usable)
 
 
 class DeepMindBigGANLatentSpace:

@@ -27,6 +27,14 @@ def _flatten_container(state, prefix):
     return out
 
 
+def _container_dlatent_avg(container):
+    """The Generator's average dlatent [L] float32 from a G.pth container's top-level state_dict, or None."""
+    v = container.get("state_dict", {}).get("dlatent_avg")
+    if v is None:
+        return None
+    return np.asarray(v.float().cpu().numpy() if hasattr(v, "float") else v, dtype=np.float32).reshape(-1)
+
+
 def _channels_from_state(sd):
     """Recover the channel list (reference G order: last -> first) from G_synthesis weight shapes."""
     ch, b = [], 0
@@ -37,7 +45,9 @@ def _channels_from_state(sd):
 
 
 class StyleGAN2:
-    """models.py:90-129.  Holds host tensors; the device copy lives in the engine."""
+    """models.py:90-129.  Holds host tensors; the device copy lives in the engine.
+    `dlatent_avg` ([dim_z] float32 or None: the truncation trick's average dlatent) is kept beside `state`, not in it: `state` holds
+    the sub-models' weights under their reference keys and nothing else."""
 
     def __init__(self, config):
         self.config = config
@@ -47,6 +57,7 @@ class StyleGAN2:
             channels = list(getattr(config, "channels", synth.FFHQ_CHANNELS))
             self.state = synth.make_state(synth.stylegan2_g_spec(channels, config.dim_z, getattr(config, "mapping_layers", 8)), seed)
             self.state.update(synth.make_state(synth.stylegan2_d_spec(channels), seed))
+            self.dlatent_avg = synth.dlatent_avg(config.dim_z, seed)
         else:
             if not os.path.exists(os.path.join(w, "G.pth")):
                 print("Weights not found!\nRun : ./download-weights.sh StyleGAN2-<model>")   # models.py:93-101
@@ -55,6 +66,7 @@ class StyleGAN2:
             g = torch.load(os.path.join(w, "G.pth"), map_location="cpu", weights_only=False)
             d = torch.load(os.path.join(w, "D.pth"), map_location="cpu", weights_only=False)
             self.state = _flatten_container(g, "")
+            self.dlatent_avg = _container_dlatent_avg(g)
             self.state.update(_flatten_container(d, "D."))
             channels = _channels_from_state(self.state)
         self.channels = channels            # reference G order (last -> first)

@@ -53,6 +53,21 @@ class NormalRandomSampling(Sampling):
         return np.random.normal(self.mu, self.std, size=(n_samples, problem.n_var))
 
 
+class MappedNormalSampling(Sampling):
+    """Sampling for a search in w / w+: z ~ N(0, 1) drawn as NormalRandomSampling draws it, sent through the generator's mapping network
+    (problem.generator.map_latents) — the population starts where a z search starts, expressed as dlatents.  tile = n_lat repeats the
+    dlatent for every style layer of a w+ row (layer-major)."""
+
+    def __init__(self, dim_z, tile=1):
+        super().__init__()
+        self.dim_z, self.tile = int(dim_z), int(tile)
+
+    def _do(self, problem, n_samples, **kwargs):
+        z = np.random.normal(0, 1, size=(n_samples, self.dim_z))
+        w = np.asarray(problem.generator.map_latents(z.astype(np.float32)), dtype=float)
+        return np.tile(w, (1, self.tile))
+
+
 class BinaryRandomSampling(Sampling):
     """operators.py:27-34"""
 
@@ -99,6 +114,12 @@ def get_operators(config):
     """operators.py:37-81.  The extra "mask" entry (variable types) is what the native driver (search.py)
     needs to apply the same per-type operators when pymoo is absent."""
     if config.config.split("_")[0] == "StyleGAN2":
+        space = getattr(config, "latent_space", None) or "z"
+        if space != "z":      # same crossover and mutation; the initial population comes through the mapping network
+            from .latent import stylegan2_n_lat
+            return dict(sampling=MappedNormalSampling(config.dim_z, stylegan2_n_lat(config) if space == "w+" else 1),
+                        crossover=get_crossover("real_sbx", prob=1.0, eta=3.0),
+                        mutation=get_mutation("real_pm", prob=0.5, eta=3.0))
         return dict(sampling=NormalRandomSampling(),
                     crossover=get_crossover("real_sbx", prob=1.0, eta=3.0),
                     mutation=get_mutation("real_pm", prob=0.5, eta=3.0))

@@ -29,6 +29,20 @@ except ImportError:
 from .generator import Generator
 
 
+PROBE_ROWS = 4096
+
+
+def dlatent_problem_args(config, generator):
+    """n_var / n_constr / xl / xu of a search in w or w+ (z keeps the config's own, +-10).  The variables are dlatents, whose range is the
+    mapping network's: probed with 4096 rows of z ~ N(0, 1) drawn from config.seed, lo / hi the extremes of every mapped value, and half
+    that span allowed beyond each (scalar bounds, as the reference's)."""
+    z = np.random.RandomState(int(getattr(config, "seed", 0) or 0)).normal(size=(PROBE_ROWS, config.dim_z)).astype(np.float32)
+    w = generator.map_latents(z)
+    lo, hi = float(w.min()), float(w.max())
+    n_var = int(generator.latent_width())
+    return dict(n_var=n_var, n_constr=n_var, xl=lo - (hi - lo) / 2, xu=hi + (hi - lo) / 2)     # (the reference sets n_constr = n_var)
+
+
 class GenerationProblem(Problem):
     def __init__(self, config, dist=None):
         """dist: an initialised torch.distributed module (one process per GPU; backend "nccl" = RCCL), or None = use the default
@@ -36,7 +50,10 @@ class GenerationProblem(Problem):
         each scores its contiguous shard and one all-gather returns all rows (parallel.py)."""
         self.generator = Generator(config, dist=dist)
         self.config = config
-        super().__init__(**self.config.problem_args)
+        args = dict(self.config.problem_args)
+        if getattr(self.generator, "latent_space", "z") != "z":
+            args.update(dlatent_problem_args(config, self.generator))
+        super().__init__(**args)
 
     def _evaluate(self, x, out, *args, **kwargs):
         ls = self.config.latent(self.config)

@@ -14,7 +14,8 @@ import pickle
 import numpy as np
 
 from .config import get_config
-from .generator import CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS
+from .engine import LATENT_SPACES
+from .generator import CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, latent_options
 from .operators import get_operators
 from .problem import GenerationProblem
 from . import search
@@ -50,6 +51,13 @@ def build_parser():
     p.add_argument("--no-clip-view-flip", dest="clip_view_flip", action="store_false", default=None,
                    help="never mirror a crop (default: each crop is mirrored with probability 1/2)")
     p.add_argument("--clip-view-fixed", action="store_true", default=None, help="the same crops in every generation (default: redrawn per generation)")
+    p.add_argument("--latent-space", type=str, default=None, choices=list(LATENT_SPACES),
+                   help="StyleGAN2 configs: what the search varies — z (default: the reference's search, through the mapping network), w (the "
+                        "dlatent itself) or w+ (one dlatent per style layer).  w / w+ depart from the reference's run.py on purpose")
+    p.add_argument("--truncation-psi", type=float, default=None,
+                   help="StyleGAN2 configs: the truncation trick, dlatents pulled towards the average dlatent; in [0, 1], 1 (default) is off")
+    p.add_argument("--truncation-cutoff", type=int, default=None,
+                   help="StyleGAN2 configs: truncate only the style layers below this index (default: every layer)")
     p.add_argument("--bpe-path", type=str, default=None)
     p.add_argument("--pop-size", type=int, default=None)
     p.add_argument("--stochastic", action="store_true", default=None,
@@ -67,11 +75,12 @@ def main(argv=None, extra_config=None):
     over = {k: v for k, v in vars(config).items() if v is not None}
     vars(config).update(get_config(config.config))                             # run.py:25
     for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "clip_views", "clip_view_min", "clip_view_flip",
-              "clip_view_fixed", "bpe_path", "pop_size", "stochastic"):
+              "clip_view_fixed", "latent_space", "truncation_psi", "truncation_cutoff", "bpe_path", "pop_size", "stochastic"):
         if k in over:
             setattr(config, k, over[k])
     if extra_config:
         vars(config).update(extra_config)
+    latent_options(config)      # a latent space / truncation on a BigGAN or GPT2 config is refused here, before anything is loaded
     state = dict(iteration=0)
     dist, rank0 = None, True
     if getattr(config, "dist", False):

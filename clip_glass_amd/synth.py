@@ -251,6 +251,13 @@ def make_state(spec, seed=0):
     return OrderedDict((name, make_tensor(seed, name, shape, kind)) for name, shape, kind in spec)
 
 
+def dlatent_avg(latent_size=512, seed=0):
+    """Synthetic average dlatent [latent_size] float32 (the Generator's own buffer, stylegan2/models.py:225-226), for the truncation trick.
+    Its own RNG stream, outside every *_spec: make_state returns what it returned before this existed.  N(0, 0.5): the size of a
+    mapped dlatent's entries, and nowhere zero."""
+    return normal(seed, "dlatent_avg", (int(latent_size),), 0.5)
+
+
 # --------------------------------------------------------------------------
 # Counter-based noise: Philox4x32-10 + Box-Muller.  Numpy mirror of the device
 # generator in csrc/noise.hip, so the oracle can be fed bit-compatible noise

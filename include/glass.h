@@ -142,8 +142,42 @@ int glass_engine_create(const glass_config* cfg, glass_engine** out);
 int glass_engine_set_clip_views(glass_engine* e, int32_t views, int32_t min_permille, int32_t flip, int32_t fixed);
 void glass_engine_destroy(glass_engine* e);
 
+/* Latent spaces and the truncation trick (StyleGAN2 engines; both depart from what the reference's run.py ever calls — it searches z with
+ * the raw generator — and are pinned to what its Generator computes, stylegan2/models.py:264-285, 314-324, 393-458).
+ * n_lat = 2 * n_blocks style layers (models.py:890-896): the convs take dlatent indices 0, 1, 2 ... in execution order, the toRGB of a
+ * block the index of the next block's first conv, the last toRGB the last index.
+ *   GLASS_LATENT_Z (default): rows [latent_size].  Pixel norm + mapping network, then truncation, then synthesis.
+ *   GLASS_LATENT_W: rows [latent_size] are dlatents: no pixel norm, no mapping; the row goes to every style layer.
+ *   GLASS_LATENT_WPLUS: rows [n_lat * latent_size], layer-major: row l goes to the style layers with index l.
+ * Truncation: dlatents = lerp(dlatent_avg, dlatents, layer_psi) with torch.lerp's fp32 rule (weight < 0.5: a + w (b - a), otherwise
+ * b - (b - a)(1 - w)); layer_psi[l] = psi for l < cutoff (cutoff -1: every layer), 1 elsewhere; a layer with psi 1 keeps its row bit
+ * for bit, and psi = 1 or cutoff = 0 is truncation off (models.py:276).  The engine applies layer_psi in EVERY space, whereas the
+ * reference truncates explicit dlatents only when the caller calls truncate() itself: in w / w+, psi = 1 (the default) is the
+ * reference's forward(dlatents=d), and psi != 1 is forward(dlatents=G.truncate(d)).
+ *
+ * glass_engine_set_latent_space: between create and finalize (GLASS_ERR_STATE after it, and for a BigGAN or generator-less engine).
+ * glass_engine_set_truncation: any time.  psi must be finite and in [0, 1] (the reference takes any float; psi < 0 or > 1 extrapolates
+ * away from the average and is refused, GLASS_ERR_ARG); cutoff in [-1, n_lat].  psi != 1 needs the tensor "dlatent_avg" ([latent_size],
+ * optional at finalize): after finalize the call fails without it (GLASS_ERR_STATE), and finalize fails the same way when the setter
+ * came first.  Rows that differ per layer (space w+, or psi != 1 with 0 < cutoff < n_lat) need a [max_pop][n_lat][latent_size] fp32
+ * buffer, which finalize allocates when the space is w+ or set_truncation was called (with any values) before it; a cutoff that
+ * needs the buffer on an engine finalized without it is refused (GLASS_ERR_STATE).
+ * glass_host_layer_psi: the one rule the setter and the pass use (host only: callable without a GPU); out [n_lat]. */
+#define GLASS_LATENT_Z 0
+#define GLASS_LATENT_W 1
+#define GLASS_LATENT_WPLUS 2
+int glass_host_layer_psi(int32_t n_lat, float psi, int32_t cutoff, float* out);
+int glass_engine_set_latent_space(glass_engine* e, int32_t space);
+int glass_engine_set_truncation(glass_engine* e, float psi, int32_t cutoff);
+/* What evaluate / generate read per row: floats_per_row = latent_size (z, w; BigGAN: z_dim + num_classes) or n_lat * latent_size (w+);
+ * n_lat = 0 for an engine that is not a StyleGAN2 one.  Nullable each. */
+int glass_engine_latent_row(glass_engine* e, int32_t* floats_per_row, int32_t* n_lat);
+/* Pixel norm + mapping network, untruncated, with the kernels the pass uses: z host float32 [P][latent_size] -> out_w [P][latent_size].
+ * P in [1, max_pop] (no multiple of batch_size needed).  Seeds W / W+ populations. */
+int glass_engine_map_latents(glass_engine* e, const float* z, int32_t P, float* out_w);
+
 /* Hand one reference tensor to the engine: `name` is the reference state-dict key
- * prefixed with its sub-model ("G_mapping.", "G_synthesis.", "D.", "clip."), data is
+ * prefixed with its sub-model ("G_mapping.", "G_synthesis.", "D.", "clip."; the generator's own "dlatent_avg" unprefixed), data is
  * host float32, row-major, dims[rank].  Replaces stylegan2.models.load (models.py:183-196)
  * + clip.load/build_model (clip/model.py:363-399).  Tensors are repacked into kernel
  * layouts (pre-scaled, fp16, folded FIR) by glass_engine_finalize. */
@@ -187,7 +221,8 @@ int glass_engine_gpt2_sample(glass_engine* e, const int32_t* context, int32_t P,
                              int32_t purpose, int32_t* out_tokens);
 
 /* THE HOT PATH — replaces GenerationProblem._evaluate (problem.py:14-29).
- * latents: host float32 [P, latent_size] row-major (latent.py:37-38);
+ * latents: host float32 [P, floats_per_row] row-major (latent.py:37-38): floats_per_row as glass_engine_latent_row reports it —
+ *   latent_size unless glass_engine_set_latent_space chose w+; the library cannot see the buffer's size, the caller checks it;
  * generation: index folded into the device noise stream (noise_mode 1);
  * first_minibatch: global index of this call's first minibatch (population shards);
  * noise: nullable, used when noise_mode == 2;
@@ -204,7 +239,7 @@ int glass_engine_last_details(glass_engine* e, int32_t P, float* features, float
 int glass_engine_last_view_details(glass_engine* e, int32_t P, float* features, float* sims, int32_t* boxes);
 
 /* Generator.generate (generator.py:29-34): images host float32 [P,3,R,R] NCHW after
- * biggan_norm (utils.py:14-17).  Used by run.py's callbacks (run.py:45,118). */
+ * biggan_norm (utils.py:14-17).  Used by run.py's callbacks (run.py:45,118).  latents: [P, floats_per_row], as for evaluate. */
 int glass_engine_generate(glass_engine* e, const float* latents, int32_t P, int32_t generation,
                           int32_t first_minibatch, const glass_noise* noise, float* images);
 
