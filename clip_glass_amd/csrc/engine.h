@@ -380,6 +380,17 @@ void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, const half
 void run_fromrgb(glass_engine* e, int B, const float* y, half_t* X);
 half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* X, half_t* const bufs[5], const float* rgb_y = nullptr);
 void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch);
+// D's dense head as run_d_head launches it, shared with the diagnostic op: dfin [P][16 CL] fp16, w0 [CL][16 CL] fp16, b0 [CL], w1t [CL][1],
+// b1 [1]; part: 16 P CL floats (nullptr: no split form), dh [P][CL] (the unsplit form's first layer), dis [P]
+struct DHead {
+    const half_t *dfin, *w0;
+    const float *b0, *w1t, *b1;
+    float *part, *dh, *dis;
+    int P, CL;
+};
+GemmParams d_head_dense0(const DHead& h);                         // the first layer as one product (bias + lrelu * sqrt2 -> dh)
+const char* launch_d_head_split(const DHead& h, hipStream_t st);  // split-K first layer + dense01_finish; nullptr: not applicable, nothing launched
+void launch_d_head_dense1(const DHead& h, hipStream_t st);        // dh -> dis
 #pragma GCC visibility pop
 
 // ---- CLIP (clip.cpp) ----

@@ -57,6 +57,12 @@ void launch_dense(const float* x, int ldx, int P, int K, const float* wt, int N,
 // pixel norm + every mapping layer in one launch (L = 256 / 512, <= 8 layers); false: not applicable, run the per-layer path
 bool launch_mapping_fused(const float* z, float* out, int P, int L, float eps, const float* const* wt, const float* const* b, int n_layers,
                           hipStream_t st);
+// The mapping network's launches (stylegan2/models.py:590-627), z [P][L] -> w0 [P][L]; w1: the per-layer path's second [P][L] buffer.
+// path 0: mapping_fused_kernel where it applies, else per layer (pixel norm, then dense_splitk_kernel for L % 64 == 0, L <= 768, dense_kernel
+// otherwise); 1: per layer; 2: fused or nothing.  Returns the MAP_* bits of what was launched (0: path 2 where the fused kernel refuses).
+enum { MAP_FUSED = 1, MAP_PIXELNORM = 2, MAP_SPLITK = 4, MAP_DENSE = 8 };
+int launch_mapping(const float* z, float* w0, float* w1, int P, int L, float eps, const float* const* wt, const float* const* b, int n_layers,
+                   int path, hipStream_t st);
 struct DenseDesc {
     const float* x; int ldx; int K; const float* wt; int N; const float* bias; float* out; int ldo;
     const float* eps_row; int eps_stride;

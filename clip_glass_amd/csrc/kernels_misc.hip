@@ -230,6 +230,23 @@ void launch_dense(const float* x, int ldx, int P, int K, const float* wt, int N,
                        eps_row, eps_stride);
 }
 
+int launch_mapping(const float* z, float* w0, float* w1, int P, int L, float eps, const float* const* wt, const float* const* b, int n_layers,
+                   int path, hipStream_t st) {
+    if (path != 1 && n_layers >= 1 && launch_mapping_fused(z, w0, P, L, eps, wt, b, n_layers, st)) return MAP_FUSED;
+    if (path == 2) return 0;
+    int ran = MAP_PIXELNORM;
+    launch_pixelnorm(z, w0, P, L, eps, st);
+    float *a = w0, *o = w1;
+    for (int i = 0; i < n_layers; ++i) {
+        if (L % 64 == 0 && L <= 768) { launch_dense_splitk(a, L, P, L, wt[i], L, b[i], o, L, 1, st); ran |= MAP_SPLITK; }
+        else { launch_dense(a, L, P, L, wt[i], L, b[i], o, L, 0, 1, nullptr, 0, st); ran |= MAP_DENSE; }
+        std::swap(a, o);
+    }
+    if (a != w0)  // result must end in w0
+        hipMemcpyAsync(w0, a, (size_t)P * L * sizeof(float), hipMemcpyDeviceToDevice, st);
+    return ran;
+}
+
 // ---- style normalisation: keeps x*s inside fp16 range; exact algebra:
 //   d*conv(x*s) == (d*smax) * conv(x * (s/smax)),  d*smax = rsqrt(sum (s/smax)^2 Wsq + eps/smax^2)
 __global__ void style_norm_kernel(float* s, int ld, const int* off, const int* len, int n_layers, float* smax,

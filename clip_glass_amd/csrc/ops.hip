@@ -900,6 +900,339 @@ extern "C" int glass_op_bg_tail(int32_t device, int32_t B, int32_t R, int32_t mi
     return GLASS_OK;
 }
 
+// ---- the small fp32 kernels around StyleGAN2 and the CLIP towers, each launched as the engine's host code launches it ------------------------
+// (tests/test_gpu_small_ops.py against the float64 restatements of tests/small_ops_ref.py).  Strided operands arrive with their padding
+// as the caller filled it (NaN); outputs wider than what a kernel writes are uploaded first, so that what it leaves alone comes back unchanged.
+extern "C" int glass_op_mapping(int32_t device, int32_t P, int32_t L, int32_t n_layers, const float* z, const float* wt, const float* b,
+                                int32_t path, float* out, int32_t* ran) {
+    OPREQ(z && wt && b && out && ran && P > 0 && L > 0 && n_layers >= 1 && n_layers <= 8, "bad argument (1 .. 8 layers)");
+    OPREQ(path >= 0 && path <= 2, "path must lie in [0, 2]");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)P * L;
+    float* dz = dv.up32(z, n); float* w0 = dv.alloc<float>(n); float* w1 = dv.alloc<float>(n);
+    OPREQ(dz && w0 && w1, "device allocation failed");
+    std::vector<const float*> dw(n_layers), db(n_layers);
+    for (int i = 0; i < n_layers; ++i) {
+        dw[i] = dv.up32(wt + (size_t)i * L * L, (size_t)L * L);
+        db[i] = dv.up32(b + (size_t)i * L, L);
+        OPREQ(dw[i] && db[i], "device allocation failed");
+    }
+    GLASS_HIP(hipMemset(w0, 0xFF, n * sizeof(float)));      // NaN: an element nobody stores shows
+    GLASS_HIP(hipMemset(w1, 0xFF, n * sizeof(float)));
+    *ran = launch_mapping(dz, w0, w1, P, L, 1e-8f, dw.data(), db.data(), n_layers, path, 0);
+    OPREQ(*ran != 0, "mapping_fused_kernel does not take this network (L = 256 / 512, its LDS within the device's limit)");
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, w0, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_pixelnorm(int32_t device, int32_t P, int32_t L, const float* z, float* out) {
+    OPREQ(z && out && P > 0 && L > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)P * L;
+    float* dz = dv.up32(z, n); float* dout = dv.alloc<float>(n);
+    OPREQ(dz && dout, "device allocation failed");
+    GLASS_HIP(hipMemset(dout, 0xFF, n * sizeof(float)));
+    launch_pixelnorm(dz, dout, P, L, 1e-8f, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, dout, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_dense_splitk(int32_t device, int32_t P, int32_t K, int32_t N, int32_t ldx, int32_t ldo, int32_t mode, const float* x,
+                                     const float* wt, const float* bias, float* out) {
+    OPREQ(x && wt && out && P > 0 && N > 0, "bad argument");
+    OPREQ(K > 0 && K % 64 == 0 && K <= 768, "dense_splitk_kernel: K a multiple of 64, at most 768 (64 KB of LDS)");
+    OPREQ(ldx >= K && ldo >= N && (mode == 0 || mode == 1), "ldx >= K, ldo >= N, mode 0 or 1");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dx = dv.up32(x, (size_t)P * ldx); float* dw = dv.up32(wt, (size_t)K * N); float* db = dv.up32(bias, N);
+    float* dout = dv.up32(out, (size_t)P * ldo);
+    OPREQ(dx && dw && dout && (!bias || db), "device allocation failed");
+    launch_dense_splitk(dx, ldx, P, K, dw, N, db, dout, ldo, mode, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, dout, (size_t)P * ldo * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_dense_ex(int32_t device, int32_t P, int32_t K, int32_t N, int32_t ldx, int32_t ldo, const float* x, const float* wt,
+                                 const float* bias, int32_t in_sq, int32_t mode, const float* eps_row, int32_t eps_stride, float* out) {
+    OPREQ(x && wt && out && P > 0 && K > 0 && N > 0 && ldx >= K && ldo >= N, "bad argument (ldx >= K, ldo >= N)");
+    OPREQ(mode >= 0 && mode <= 2 && (mode != 2 || (eps_row && eps_stride >= 1)), "mode 2 reads eps_row [P, eps_stride]");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dx = dv.up32(x, (size_t)P * ldx); float* dw = dv.up32(wt, (size_t)K * N); float* db = dv.up32(bias, N);
+    float* de = dv.up32(eps_row, (size_t)P * eps_stride); float* dout = dv.up32(out, (size_t)P * ldo);
+    OPREQ(dx && dw && dout && (!bias || db) && (!eps_row || de), "device allocation failed");
+    launch_dense(dx, ldx, P, K, dw, N, db, dout, ldo, in_sq, mode, de, eps_stride, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, dout, (size_t)P * ldo * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_dense_multi(int32_t device, int32_t n, int32_t P, int32_t ldx, int32_t ldo, int32_t eps_stride, const int32_t* K,
+                                    const int32_t* N, const int32_t* x_off, const int32_t* out_off, const int32_t* eps_idx, const float* x,
+                                    const float* wt, const float* eps_rows, float* out) {
+    OPREQ(K && N && x_off && out_off && eps_idx && x && wt && eps_rows && out && n > 0 && P > 0 && eps_stride > 0, "bad argument");
+    size_t wtot = 0;
+    int max_N = 0;
+    for (int i = 0; i < n; ++i) {
+        OPREQ(K[i] > 0 && N[i] > 0 && x_off[i] >= 0 && x_off[i] + K[i] <= ldx && out_off[i] >= 0 && out_off[i] + N[i] <= ldo &&
+                  eps_idx[i] >= 0 && eps_idx[i] < eps_stride, "a problem leaves its table");
+        wtot += (size_t)K[i] * N[i];
+        max_N = std::max(max_N, N[i]);
+    }
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dx = dv.up32(x, (size_t)P * ldx); float* dw = dv.up32(wt, wtot); float* de = dv.up32(eps_rows, (size_t)P * eps_stride);
+    float* dout = dv.up32(out, (size_t)P * ldo);
+    OPREQ(dx && dw && de && dout, "device allocation failed");
+    std::vector<DenseDesc> dd(n);       // as finalize builds the demodulation table (engine.cpp)
+    size_t woff = 0;
+    for (int i = 0; i < n; ++i) {
+        DenseDesc& q = dd[i];
+        q.x = dx + x_off[i]; q.ldx = ldx; q.K = K[i]; q.wt = dw + woff; q.N = N[i]; q.bias = nullptr;
+        q.out = dout + out_off[i]; q.ldo = ldo; q.eps_row = de + eps_idx[i]; q.eps_stride = eps_stride;
+        woff += (size_t)K[i] * N[i];
+    }
+    DenseDesc* ddev = dv.alloc<DenseDesc>(n);
+    OPREQ(ddev, "device allocation failed");
+    GLASS_HIP(hipMemcpy(ddev, dd.data(), (size_t)n * sizeof(DenseDesc), hipMemcpyHostToDevice));
+    launch_dense_multi(ddev, n, max_N, P, 1, 2, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, dout, (size_t)P * ldo * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_style_norm(int32_t device, int32_t P, int32_t ld, int32_t n_layers, const int32_t* off, const int32_t* len, float* s,
+                                   float* smax, float* eps_row) {
+    OPREQ(off && len && s && smax && eps_row && P > 0 && n_layers > 0, "bad argument");
+    for (int l = 0; l < n_layers; ++l) OPREQ(off[l] >= 0 && len[l] > 0 && off[l] + len[l] <= ld, "a segment leaves the row");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)P * ld, m = (size_t)P * n_layers;
+    float* ds = dv.up32(s, n); float* dm = dv.alloc<float>(m); float* de = dv.alloc<float>(m);
+    int* doff = dv.alloc<int>(n_layers); int* dlen = dv.alloc<int>(n_layers);
+    OPREQ(ds && dm && de && doff && dlen, "device allocation failed");
+    GLASS_HIP(hipMemcpy(doff, off, n_layers * sizeof(int), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemcpy(dlen, len, n_layers * sizeof(int), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemset(dm, 0xFF, m * sizeof(float)));
+    GLASS_HIP(hipMemset(de, 0xFF, m * sizeof(float)));
+    launch_style_norm(ds, ld, P, n_layers, doff, dlen, dm, de, 1e-8f, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(s, ds, n * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(smax, dm, m * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(eps_row, de, m * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_d_head(int32_t device, int32_t P, int32_t CL, const float* dfin, const float* w0, const float* b0, const float* w1,
+                               const float* b1, float* dis, int32_t* split) {
+    OPREQ(dfin && w0 && b0 && w1 && b1 && dis && split && P > 0 && CL > 0 && CL % 4 == 0, "bad argument (CL a multiple of 4)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t K = 16 * (size_t)CL;
+    DHead h;
+    h.dfin = dv.up16(dfin, (size_t)P * K); h.w0 = dv.up16(w0, (size_t)CL * K);
+    h.b0 = dv.up32(b0, CL); h.w1t = dv.up32(w1, CL); h.b1 = dv.up32(b1, 1);
+    h.part = dv.alloc<float>((size_t)16 * P * CL); h.dh = dv.alloc<float>((size_t)P * CL); h.dis = dv.alloc<float>(P);
+    h.P = P; h.CL = CL;
+    OPREQ(h.dfin && h.w0 && h.b0 && h.w1t && h.b1 && h.part && h.dh && h.dis, "device allocation failed");
+    GLASS_HIP(hipMemset(h.part, 0xFF, (size_t)16 * P * CL * sizeof(float)));      // NaN: a slice element nobody stores shows in the sum
+    GLASS_HIP(hipMemset(h.dh, 0xFF, (size_t)P * CL * sizeof(float)));
+    GLASS_HIP(hipMemset(h.dis, 0xFF, (size_t)P * sizeof(float)));
+    *split = launch_d_head_split(h, 0) != nullptr;
+    if (!*split) {                        // as run_d_head: the whole product (run_gemm's order: gemm_tiled, then gemm_direct), then the second layer
+        const GemmParams g = d_head_dense0(h);
+        if (!launch_gemm_tiled(g, 0)) launch_gemm_direct(g, 0);
+        launch_d_head_dense1(h, 0);
+    }
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(dis, h.dis, (size_t)P * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_finalize_image(int32_t device, int64_t n, const float* y, float* img) {
+    OPREQ(y && img && n > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dy = dv.up32(y, (size_t)n); float* di = dv.alloc<float>((size_t)n + 4);      // four guard elements behind the output
+    OPREQ(dy && di, "device allocation failed");
+    GLASS_HIP(hipMemset(di, 0xFF, ((size_t)n + 4) * sizeof(float)));
+    launch_finalize_image(dy, di, n, 0);
+    int rc = finish();
+    if (rc) return rc;
+    uint32_t guard[4];
+    GLASS_HIP(hipMemcpy(guard, di + n, sizeof guard, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) OPREQ(guard[i] == 0xFFFFFFFFu, "finalize_image stored past element n");
+    GLASS_HIP(hipMemcpy(img, di, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_embed_lnpre(int32_t device, int32_t P, int32_t T, int32_t D, const float* patch_emb, const float* cls, const float* pos,
+                                    const float* g, const float* b, float* x) {
+    OPREQ(patch_emb && cls && pos && g && b && x && P > 0 && T >= 2 && D > 0, "bad argument (T = 1 + patches >= 2)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)P * T * D;
+    float* dpe = dv.up32(patch_emb, (size_t)P * (T - 1) * D); float* dc = dv.up32(cls, D); float* dp = dv.up32(pos, (size_t)T * D);
+    float* dg = dv.up32(g, D); float* db = dv.up32(b, D); float* dx = dv.alloc<float>(n);
+    OPREQ(dpe && dc && dp && dg && db && dx, "device allocation failed");
+    GLASS_HIP(hipMemset(dx, 0xFF, n * sizeof(float)));
+    launch_embed_lnpre(dpe, dc, dp, dg, db, P, T, D, dx, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(x, dx, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_embed_text(int32_t device, int32_t n_texts, int32_t ctx, int32_t D, int32_t V, const int32_t* tokens, const float* tok_emb,
+                                   const float* pos, float* x) {
+    OPREQ(tokens && tok_emb && pos && x && n_texts > 0 && ctx > 0 && D > 0 && V > 0, "bad argument");
+    const int rows = n_texts * ctx;
+    for (int i = 0; i < rows; ++i) OPREQ(tokens[i] >= 0 && tokens[i] < V, "token id out of range");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)rows * D;
+    int* dt = dv.alloc<int>(rows);
+    float* de = dv.up32(tok_emb, (size_t)V * D); float* dp = dv.up32(pos, (size_t)ctx * D); float* dx = dv.alloc<float>(n);
+    OPREQ(dt && de && dp && dx, "device allocation failed");
+    GLASS_HIP(hipMemcpy(dt, tokens, rows * sizeof(int), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemset(dx, 0xFF, n * sizeof(float)));
+    launch_embed_text(dt, de, dp, rows, ctx, D, dx, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(x, dx, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_layernorm_ex(int32_t device, int32_t M, int32_t D, int64_t row_stride, int32_t half_out, const float* x, const float* g,
+                                     const float* b, float* out) {
+    OPREQ(x && g && b && out && M > 0 && D > 0 && row_stride >= D, "bad argument (row_stride >= D)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)M * D;
+    float* dx = dv.up32(x, (size_t)(M - 1) * row_stride + D); float* dg = dv.up32(g, D); float* db = dv.up32(b, D);
+    float* o32 = half_out ? nullptr : dv.alloc<float>(n);
+    half_t* o16 = half_out ? dv.alloc<half_t>(n) : nullptr;
+    OPREQ(dx && dg && db && (o32 || o16), "device allocation failed");
+    GLASS_HIP(hipMemset(half_out ? (void*)o16 : (void*)o32, 0xFF, n * (half_out ? sizeof(half_t) : sizeof(float))));
+    launch_layernorm(dx, row_stride, M, D, dg, db, o16, o32, 0);
+    int rc = finish();
+    if (rc) return rc;
+    if (o16) return down16(out, o16, n);
+    GLASS_HIP(hipMemcpy(out, o32, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_layernorm_rows(int32_t device, int32_t n_rows, int32_t M, int32_t D, const float* x, const int32_t* rows, const float* g,
+                                       const float* b, float* out) {
+    OPREQ(x && rows && g && b && out && n_rows > 0 && M > 0 && D > 0, "bad argument");
+    for (int i = 0; i < M; ++i) OPREQ(rows[i] >= 0 && rows[i] < n_rows, "row index out of range");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)M * D;
+    float* dx = dv.up32(x, (size_t)n_rows * D); float* dg = dv.up32(g, D); float* db = dv.up32(b, D); float* dout = dv.alloc<float>(n);
+    int* dr = dv.alloc<int>(M);
+    OPREQ(dx && dg && db && dout && dr, "device allocation failed");
+    GLASS_HIP(hipMemcpy(dr, rows, M * sizeof(int), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemset(dout, 0xFF, n * sizeof(float)));
+    launch_layernorm_rows(dx, dr, M, D, dg, db, dout, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, dout, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_cosine(int32_t device, int32_t P, int32_t D, const float* feat, const float* target, float* sim) {
+    OPREQ(feat && target && sim && P > 0 && D > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* df = dv.up32(feat, (size_t)P * D); float* dt = dv.up32(target, D); float* ds = dv.alloc<float>(P);
+    OPREQ(df && dt && ds, "device allocation failed");
+    GLASS_HIP(hipMemset(ds, 0xFF, (size_t)P * sizeof(float)));
+    launch_cosine(df, dt, P, D, ds, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(sim, ds, (size_t)P * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_cosine_views(int32_t device, int32_t P, int32_t V, int32_t D, const float* feat, const float* target, float* view_sim,
+                                     float* sim) {
+    OPREQ(feat && target && view_sim && sim && P > 0 && V > 0 && D > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* df = dv.up32(feat, (size_t)P * V * D); float* dt = dv.up32(target, D);
+    float* dvs = dv.alloc<float>((size_t)P * V); float* ds = dv.alloc<float>(P);
+    OPREQ(df && dt && dvs && ds, "device allocation failed");
+    GLASS_HIP(hipMemset(dvs, 0xFF, (size_t)P * V * sizeof(float)));
+    GLASS_HIP(hipMemset(ds, 0xFF, (size_t)P * sizeof(float)));
+    launch_cosine_views(df, dt, P, V, D, dvs, ds, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(view_sim, dvs, (size_t)P * V * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(sim, ds, (size_t)P * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_assemble_F(int32_t device, int32_t P, int32_t n_obj, const float* sim, const float* dis, float* F) {
+    OPREQ(sim && F && P > 0 && (n_obj == 1 || (n_obj == 2 && dis)), "bad argument (n_obj 1, or 2 with dis)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t n = (size_t)P * n_obj;
+    float* ds = dv.up32(sim, P); float* dd = dv.up32(dis, P); float* dF = dv.alloc<float>(n + 4);      // four guard elements behind the output
+    OPREQ(ds && dF && (!dis || dd), "device allocation failed");
+    GLASS_HIP(hipMemset(dF, 0xFF, (n + 4) * sizeof(float)));
+    launch_assemble_F(ds, dd, P, n_obj, dF, 0);
+    int rc = finish();
+    if (rc) return rc;
+    uint32_t guard[4];
+    GLASS_HIP(hipMemcpy(guard, dF + n, sizeof guard, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) OPREQ(guard[i] == 0xFFFFFFFFu, "assemble_F stored past row P");
+    GLASS_HIP(hipMemcpy(F, dF, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_image_patches(int32_t device, int32_t n, int32_t S, int32_t ps, int32_t ld, const float* img, float sentinel,
+                                      float* patches) {
+    OPREQ(img && patches && n > 0 && S > 0 && ps > 0 && S % ps == 0 && ld >= 3 * ps * ps, "bad argument (S % ps == 0, ld >= 3 ps ps)");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const int G = S / ps;
+    const size_t tot = (size_t)n * G * G * ld;
+    float* di = dv.up32(img, (size_t)n * 3 * S * S);
+    half_t* dp = dv.up16v(std::vector<_Float16>(tot, (_Float16)sentinel));      // what the kernel does not write keeps the sentinel
+    OPREQ(di && dp, "device allocation failed");
+    launch_image_patches(di, n, S, ps, ld, dp, 0);
+    int rc = finish();
+    if (rc) return rc;
+    return down16(patches, dp, tot);
+}
+
+extern "C" int glass_op_rn_token0_rows(int32_t device, int32_t B, int32_t T, int32_t C, const float* att, float* out) {
+    OPREQ(att && out && B > 0 && T > 0 && C > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    half_t* da = dv.up16(att, (size_t)B * T * C); float* dout = dv.alloc<float>((size_t)B * C);
+    OPREQ(da && dout, "device allocation failed");
+    GLASS_HIP(hipMemset(dout, 0xFF, (size_t)B * C * sizeof(float)));
+    launch_rn_token0_rows(da, B, T, C, dout, 0);
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, dout, (size_t)B * C * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
 __global__ void mfma_probe_kernel(const half_t* a, const half_t* b, float* d) {
     const int lane = threadIdx.x;
     const int r = lane & 31, kh = lane >> 5;

@@ -306,18 +306,7 @@ void run_mapping(glass_engine* e, int P) {
     const glass_config& c = e->cfg;
     const int L = c.latent_size;
     Prof pr(e, "mapping", 2.0 * P * L * L * c.mapping_layers, 4.0 * L * L * c.mapping_layers);
-    if (c.mapping_layers < 1 ||
-        !launch_mapping_fused(e->d_z, e->d_w0, P, L, 1e-8f, e->map_wt.data(), e->map_b.data(), c.mapping_layers, e->cur)) {
-        launch_pixelnorm(e->d_z, e->d_w0, P, L, 1e-8f, e->cur);
-        float *a = e->d_w0, *b = e->d_w1;
-        for (int i = 0; i < c.mapping_layers; ++i) {
-            if (L % 64 == 0 && L <= 768) launch_dense_splitk(a, L, P, L, e->map_wt[i], L, e->map_b[i], b, L, 1, e->cur);
-            else launch_dense(a, L, P, L, e->map_wt[i], L, e->map_b[i], b, L, 0, 1, nullptr, 0, e->cur);
-            std::swap(a, b);
-        }
-        if (a != e->d_w0)  // result must end in d_w0
-            hipMemcpyAsync(e->d_w0, a, (size_t)P * L * sizeof(float), hipMemcpyDeviceToDevice, e->cur);
-    }
+    launch_mapping(e->d_z, e->d_w0, e->d_w1, P, L, 1e-8f, e->map_wt.data(), e->map_b.data(), c.mapping_layers, 0, e->cur);
 }
 
 // The uploaded rows are in d_z (space z), d_w0 (w) or d_dlat (w+): run_pass put them there.
@@ -650,6 +639,29 @@ half_t* run_d_blocks(glass_engine* e, int B, int i_lo, int i_hi, half_t* X, half
     return X;
 }
 
+// D's dense head (stylegan2/models.py:1339-1350) on dfin [P][16 CL]: the launches run_d_head and the diagnostic op share.
+GemmParams d_head_dense0(const DHead& h) {
+    return gemm_params(h.dfin, h.w0, h.P, h.CL, 16 * h.CL, h.b0, 4, nullptr, h.dh, 1);
+}
+// M = P rows, K = 16 CL = 8192: the 128 x 64 tiles are 8 workgroups walking 128 K steps each (97 us for 0.5 GFLOP).  Split K into 16
+// slices (blockIdx.z) with raw partial sums, finished in a fixed order with bias + activation: 128+ workgroups, 8 steps each; the finish
+// and the second dense layer (CL -> 1) are one launch.  nullptr: the shape has no split form (16 CL % 1024, or gemm_tiled refuses it) and
+// nothing was launched — d_head_dense0 through gemm_tiled / gemm_direct, then launch_d_head_dense1.
+const char* launch_d_head_split(const DHead& h, hipStream_t st) {
+    const int S0 = 16;
+    const GemmParams g = d_head_dense0(h);
+    if (!h.part || g.K % (S0 * 64) != 0) return nullptr;
+    GemmParams q = g;
+    q.ld = g.K; q.K = g.K / S0; q.batch = S0; q.a_bs = q.K; q.w_bs = q.K; q.o_bs = (long long)h.P * h.CL;
+    q.bias = nullptr; q.mode = 3; q.out32 = h.part;
+    const char* k = launch_gemm_tiled(q, st);
+    if (k) launch_dense01_finish(h.part, S0, q.o_bs, g.bias, h.w1t, h.b1, h.dis, h.P, h.CL, st);
+    return k;
+}
+void launch_d_head_dense1(const DHead& h, hipStream_t st) {
+    launch_dense(h.dh, h.CL, h.P, h.CL, h.w1t, 1, h.b1, h.dis, 1, 0, 0, nullptr, 0, st);
+}
+
 // mbstd + final conv + dense head for the whole population: X is [P][4][4][C0]
 void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch) {
     const glass_config& c = e->cfg;
@@ -663,26 +675,20 @@ void run_d_head(glass_engine* e, int P, const half_t* X, half_t* scratch) {
     p.KS = 3; p.pad = 1; p.w = e->d_final_w; p.Cout = p.Neff = CL; p.Ho = p.Wo = 4; p.bias = e->d_final_b; p.act = 1;
     p.y = e->d_dfin;
     run_conv(e, p, "D.final_conv", 2.0 * P * 16 * 9.0 * (CL + 1) * CL, 2.0 * 9 * CL * (CL + 1));
-    const GemmParams g = gemm_params(e->d_dfin, e->d_dense0_w, P, CL, 16 * CL, e->d_dense0_b, 4, nullptr, e->d_dh, 1);
-    // M = P rows, K = 16 CL = 8192: the 128 x 64 tiles are 8 workgroups walking 128 K steps each (97 us for 0.5 GFLOP).  Split K into 16
-    // slices (blockIdx.z) with raw partial sums, finished in a fixed order with bias + activation: 128+ workgroups, 8 steps each.
-    const int S0 = 16;
-    if (e->d_dh_part && g.K % (S0 * 64) == 0 && P <= e->cfg.max_pop) {
-        GemmParams q = g;
-        q.ld = g.K; q.K = g.K / S0; q.batch = S0; q.a_bs = q.K; q.w_bs = q.K; q.o_bs = (long long)P * CL;
-        q.bias = nullptr; q.mode = 3; q.out32 = e->d_dh_part;
-        Prof pr(e, "D.dense0", 2.0 * P * (double)g.K * CL, 2.0 * (double)g.K * CL);
-        const char* k = launch_gemm_tiled(q, e->cur);
-        if (k) {    // finish + the second dense layer (CL -> 1) in one launch
-            launch_dense01_finish(e->d_dh_part, S0, q.o_bs, g.bias, e->d_dense1_wt, e->d_dense1_b, e->d_dis, P, CL, e->cur);
+    const DHead h = {e->d_dfin, e->d_dense0_w, e->d_dense0_b, e->d_dense1_wt, e->d_dense1_b, e->d_dh_part, e->d_dh, e->d_dis, P, CL};
+    if (e->d_dh_part && P <= e->cfg.max_pop) {
+        Prof pr(e, "D.dense0", 2.0 * P * 16.0 * CL * CL, 2.0 * 16.0 * CL * CL);
+        const char* k = launch_d_head_split(h, e->cur);
+        if (k) {
             if (pr.on) pr.pe.name = std::string("D.dense0+1@") + k + "+dense01_finish";
             return;
         }
         pr.drop();
     }
+    const GemmParams g = d_head_dense0(h);
     run_gemm(e, g, "D.dense0");
     {
         Prof pr(e, "D.dense1", 2.0 * P * CL, 0);
-        launch_dense(e->d_dh, CL, P, CL, e->d_dense1_wt, 1, e->d_dense1_b, e->d_dis, 1, 0, 0, nullptr, 0, e->cur);
+        launch_d_head_dense1(h, e->cur);
     }
 }

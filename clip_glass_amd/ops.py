@@ -598,6 +598,244 @@ def rn_tokens(x, pos, device=0):
     return out
 
 
+# ---- the small fp32 kernels around StyleGAN2 and the CLIP towers (glass_op_mapping ... glass_op_rn_token0_rows) ----
+_FP, _IP = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+MAP_FUSED, MAP_PIXELNORM, MAP_SPLITK, MAP_DENSE = 1, 2, 4, 8
+MAPPING_PATHS = {"auto": 0, "layers": 1, "fused": 2}
+
+
+def _i32(a):
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    return a, a.ctypes.data_as(_IP)
+
+
+def _strided(a, ld, fill=np.nan):
+    """[rows, n] -> a [rows, ld] float32 buffer with `fill` between the rows: a read outside a row shows."""
+    a = np.asarray(a, dtype=np.float32)
+    buf = np.full((a.shape[0], ld), fill, dtype=np.float32)
+    buf[:, :a.shape[1]] = a
+    return buf
+
+
+def mapping(z, wt, b, path="auto", device=0):
+    """The mapping network through the launcher run_mapping calls: z [P, L], wt [n_layers, L, L] (each [k, n], coefficient folded), b
+    [n_layers, L] -> (w [P, L], the set of kernels that ran).  path "auto": as the engine decides; "layers": pixel norm + one dense launch
+    per layer; "fused": mapping_fused_kernel or an error."""
+    lib = load_library()
+    z, wt, b = _f32(z), _f32(wt), _f32(b)
+    P, L = z.shape
+    n = wt.shape[0]
+    assert wt.shape == (n, L, L) and b.shape == (n, L)
+    out = np.empty((P, L), dtype=np.float32)
+    ran = C.c_int32(0)
+    lib.glass_op_mapping.argtypes = [C.c_int32] * 4 + [_FP] * 3 + [C.c_int32, _FP, _IP]
+    _check(lib, lib.glass_op_mapping(device, P, L, n, _fp(z), _fp(wt), _fp(b), MAPPING_PATHS[path], _fp(out), C.byref(ran)))
+    names = {MAP_FUSED: "mapping_fused_kernel", MAP_PIXELNORM: "pixelnorm_kernel", MAP_SPLITK: "dense_splitk_kernel", MAP_DENSE: "dense_kernel"}
+    return out, {v for k, v in names.items() if ran.value & k}
+
+
+def pixelnorm(z, device=0):
+    lib = load_library()
+    z = _f32(z)
+    out = np.empty_like(z)
+    lib.glass_op_pixelnorm.argtypes = [C.c_int32] * 3 + [_FP, _FP]
+    _check(lib, lib.glass_op_pixelnorm(device, z.shape[0], z.shape[1], _fp(z), _fp(out)))
+    return out
+
+
+def dense_splitk(x, wt, bias=None, mode=0, ldx=None, ldo=None, device=0):
+    """dense_splitk_kernel on x [P, K] stored with row stride ldx (NaN between the rows) -> the whole output table [P, ldo]; the columns
+    past N come back as the NaN they were uploaded with."""
+    lib = load_library()
+    wt = _f32(wt)
+    P, K = np.shape(x)
+    N = wt.shape[1]
+    ldx, ldo = ldx or K, ldo or N
+    xb = _strided(x, ldx)
+    out = np.full((P, ldo), np.nan, dtype=np.float32)
+    bb, bp = _opt(bias)
+    lib.glass_op_dense_splitk.argtypes = [C.c_int32] * 7 + [_FP] * 4
+    _check(lib, lib.glass_op_dense_splitk(device, P, K, N, ldx, ldo, mode, _fp(xb), _fp(wt), bp, _fp(out)))
+    return out
+
+
+def dense_ex(x, wt, bias=None, in_sq=False, mode=0, eps_row=None, ldx=None, out=None, col0=0, device=0):
+    """dense_kernel with the strides the style path uses: x [P, K] stored with row stride ldx (NaN between the rows); the result goes to
+    columns col0 .. col0 + N of the table `out` [P, ldo] (default: a NaN table of width N), which is returned whole.  eps_row [P, stride]:
+    mode 2 reads column 0."""
+    lib = load_library()
+    wt = _f32(wt)
+    P, K = np.shape(x)
+    N = wt.shape[1]
+    xb = _strided(x, ldx or K)
+    out = np.full((P, N), np.nan, dtype=np.float32) if out is None else np.array(out, dtype=np.float32, order="C")
+    ldo = out.shape[1]
+    assert col0 + N <= ldo
+    bb, bp = _opt(bias)
+    e, ep = _opt(None if eps_row is None else np.reshape(eps_row, (P, -1)))
+    buf = np.concatenate([out.reshape(-1), np.full(col0, np.nan, np.float32)])
+    win = buf[col0:]                                    # the launch's `out` pointer is column col0 of row 0: [P, ldo] floats from there on
+    lib.glass_op_dense_ex.argtypes = [C.c_int32] * 6 + [_FP] * 3 + [C.c_int32, C.c_int32, _FP, C.c_int32, _FP]
+    _check(lib, lib.glass_op_dense_ex(device, P, K, N, xb.shape[1], ldo, _fp(xb), _fp(wt), bp, int(in_sq), mode, ep,
+                                      0 if e is None else e.shape[1], win.ctypes.data_as(_FP)))
+    return buf[:out.size].reshape(out.shape)
+
+
+def dense_multi(x, problems, eps_rows, ldo, device=0):
+    """The demodulation launch (dense_multi_kernel, in_sq 1, mode 2): x [P, ldx] the shared style table, problems a list of (x_off, wt [K, N],
+    out_off, eps_idx), eps_rows [P, n_style] -> the output table [P, ldo] (NaN where no problem writes)."""
+    lib = load_library()
+    x, eps_rows = _f32(x), _f32(eps_rows)
+    P, ldx = x.shape
+    wts = [_f32(q[1]) for q in problems]
+    K, Kp = _i32([w.shape[0] for w in wts]); N, Np = _i32([w.shape[1] for w in wts])
+    xo, xop = _i32([q[0] for q in problems]); oo, oop = _i32([q[2] for q in problems]); ei, eip = _i32([q[3] for q in problems])
+    wt = np.concatenate([w.reshape(-1) for w in wts])
+    out = np.full((P, ldo), np.nan, dtype=np.float32)
+    lib.glass_op_dense_multi.argtypes = [C.c_int32] * 6 + [_IP] * 5 + [_FP] * 4
+    _check(lib, lib.glass_op_dense_multi(device, len(problems), P, ldx, ldo, eps_rows.shape[1], Kp, Np, xop, oop, eip, _fp(x), _fp(wt),
+                                         _fp(eps_rows), _fp(out)))
+    return out
+
+
+def style_norm(s, segments, device=0):
+    """style_norm_kernel (eps 1e-8) over the (offset, length) segments of each row of s [P, ld] -> (s normalised, smax [P, n], eps_row [P, n])."""
+    lib = load_library()
+    s = np.array(s, dtype=np.float32, order="C")
+    P, ld = s.shape
+    off, offp = _i32([q[0] for q in segments]); ln, lnp = _i32([q[1] for q in segments])
+    n = len(segments)
+    smax, eps_row = np.empty((P, n), np.float32), np.empty((P, n), np.float32)
+    lib.glass_op_style_norm.argtypes = [C.c_int32] * 4 + [_IP, _IP] + [_FP] * 3
+    _check(lib, lib.glass_op_style_norm(device, P, ld, n, offp, lnp, _fp(s), _fp(smax), _fp(eps_row)))
+    return s, smax, eps_row
+
+
+def d_head(dfin, w0, b0, w1, b1, device=0):
+    """D's dense head through the launchers run_d_head calls: dfin [P, 16 CL], w0 [CL, 16 CL] (both rounded to fp16 on upload), b0 [CL],
+    w1 [CL], b1 [1] -> (dis [P], "split" | "whole": the form that ran)."""
+    lib = load_library()
+    dfin, w0, b0, w1, b1 = (_f32(a) for a in (dfin, w0, b0, w1, b1))
+    P, CL = dfin.shape[0], w0.shape[0]
+    assert dfin.shape == (P, 16 * CL) and w0.shape == (CL, 16 * CL) and b0.shape == (CL,) and w1.shape == (CL,) and b1.shape == (1,)
+    dis = np.empty(P, dtype=np.float32)
+    split = C.c_int32(-1)
+    lib.glass_op_d_head.argtypes = [C.c_int32] * 3 + [_FP] * 6 + [_IP]
+    _check(lib, lib.glass_op_d_head(device, P, CL, _fp(dfin), _fp(w0), _fp(b0), _fp(w1), _fp(b1), _fp(dis), C.byref(split)))
+    return dis, "split" if split.value == 1 else "whole"
+
+
+def finalize_image(y, device=0):
+    lib = load_library()
+    y = _f32(y)
+    img = np.empty_like(y)
+    lib.glass_op_finalize_image.argtypes = [C.c_int32, C.c_int64, _FP, _FP]
+    _check(lib, lib.glass_op_finalize_image(device, y.size, _fp(y), _fp(img)))
+    return img
+
+
+def embed_lnpre(patch_emb, cls, pos, g, b, device=0):
+    """patch_emb [P, T - 1, D], cls [D], pos [T, D], ln_pre g / b [D] -> tokens [P, T, D]."""
+    lib = load_library()
+    patch_emb, cls, pos, g, b = (_f32(a) for a in (patch_emb, cls, pos, g, b))
+    P, T1, D = patch_emb.shape
+    assert pos.shape == (T1 + 1, D)
+    x = np.empty((P, T1 + 1, D), dtype=np.float32)
+    lib.glass_op_embed_lnpre.argtypes = [C.c_int32] * 4 + [_FP] * 6
+    _check(lib, lib.glass_op_embed_lnpre(device, P, T1 + 1, D, _fp(patch_emb), _fp(cls), _fp(pos), _fp(g), _fp(b), _fp(x)))
+    return x
+
+
+def embed_text(tokens, tok_emb, pos, device=0):
+    """tokens int [n, ctx], tok_emb [V, D], pos [ctx, D] -> [n * ctx, D]."""
+    lib = load_library()
+    tok, tokp = _i32(tokens)
+    tok_emb, pos = _f32(tok_emb), _f32(pos)
+    n, ctx = tok.shape
+    V, D = tok_emb.shape
+    x = np.empty((n * ctx, D), dtype=np.float32)
+    lib.glass_op_embed_text.argtypes = [C.c_int32] * 5 + [_IP, _FP, _FP, _FP]
+    _check(lib, lib.glass_op_embed_text(device, n, ctx, D, V, tokp, _fp(tok_emb), _fp(pos), _fp(x)))
+    return x
+
+
+def layernorm_ex(x, g, b, row_stride=None, half_out=False, device=0):
+    """layernorm_kernel on the rows of x [M, D] stored row_stride apart (NaN between them); half_out: the fp16 output (as float32 values)."""
+    lib = load_library()
+    g, b = _f32(g), _f32(b)
+    M, D = np.shape(x)
+    xb = _strided(x, row_stride or D)
+    out = np.empty((M, D), dtype=np.float32)
+    lib.glass_op_layernorm_ex.argtypes = [C.c_int32] * 3 + [C.c_int64, C.c_int32] + [_FP] * 4
+    _check(lib, lib.glass_op_layernorm_ex(device, M, D, xb.shape[1], int(half_out), _fp(xb), _fp(g), _fp(b), _fp(out)))
+    return out
+
+
+def layernorm_rows(x, rows, g, b, device=0):
+    lib = load_library()
+    x, g, b = _f32(x), _f32(g), _f32(b)
+    r, rp = _i32(rows)
+    out = np.empty((r.shape[0], x.shape[1]), dtype=np.float32)
+    lib.glass_op_layernorm_rows.argtypes = [C.c_int32] * 4 + [_FP, _IP, _FP, _FP, _FP]
+    _check(lib, lib.glass_op_layernorm_rows(device, x.shape[0], r.shape[0], x.shape[1], _fp(x), rp, _fp(g), _fp(b), _fp(out)))
+    return out
+
+
+def cosine(feat, target, device=0):
+    lib = load_library()
+    feat, target = _f32(feat), _f32(target)
+    P, D = feat.shape
+    sim = np.empty(P, dtype=np.float32)
+    lib.glass_op_cosine.argtypes = [C.c_int32] * 3 + [_FP] * 3
+    _check(lib, lib.glass_op_cosine(device, P, D, _fp(feat), _fp(target), _fp(sim)))
+    return sim
+
+
+def cosine_views(feat, target, device=0):
+    """feat [P, V, D] -> (view_sim [P, V], sim [P])."""
+    lib = load_library()
+    feat, target = _f32(feat), _f32(target)
+    P, V, D = feat.shape
+    vs, sim = np.empty((P, V), np.float32), np.empty(P, np.float32)
+    lib.glass_op_cosine_views.argtypes = [C.c_int32] * 4 + [_FP] * 4
+    _check(lib, lib.glass_op_cosine_views(device, P, V, D, _fp(feat), _fp(target), _fp(vs), _fp(sim)))
+    return vs, sim
+
+
+def assemble_F(sim, dis=None, device=0):
+    lib = load_library()
+    sim = _f32(sim)
+    d, dp = _opt(dis)
+    n_obj = 1 if dis is None else 2
+    Fv = np.empty((sim.shape[0], n_obj), dtype=np.float32)
+    lib.glass_op_assemble_F.argtypes = [C.c_int32] * 3 + [_FP] * 3
+    _check(lib, lib.glass_op_assemble_F(device, sim.shape[0], n_obj, _fp(sim), dp, _fp(Fv)))
+    return Fv
+
+
+def image_patches(img, ps, ld, sentinel=-7.0, device=0):
+    """img [n, 3, S, S] -> the patch operand [n (S / ps)^2, ld] as fp16 values; the columns the kernel does not write hold `sentinel`."""
+    lib = load_library()
+    img = _f32(img)
+    n, _, S, _ = img.shape
+    G = S // ps
+    out = np.empty((n * G * G, ld), dtype=np.float32)
+    lib.glass_op_image_patches.argtypes = [C.c_int32] * 5 + [_FP, C.c_float, _FP]
+    _check(lib, lib.glass_op_image_patches(device, n, S, ps, ld, _fp(img), float(sentinel), _fp(out)))
+    return out
+
+
+def rn_token0_rows(att, device=0):
+    """att [B, T, C] (rounded to fp16) -> [B, C] float32 = att[:, 0, :]."""
+    lib = load_library()
+    att = _f32(att)
+    B, T, Cc = att.shape
+    out = np.empty((B, Cc), dtype=np.float32)
+    lib.glass_op_rn_token0_rows.argtypes = [C.c_int32] * 4 + [_FP, _FP]
+    _check(lib, lib.glass_op_rn_token0_rows(device, B, T, Cc, _fp(att), _fp(out)))
+    return out
+
+
 def mfma_probe(a, b, device=0):
     lib = load_library()
     a, b = _f32(a), _f32(b)

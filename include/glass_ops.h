@@ -8,7 +8,8 @@
  *
  * Families: the convolution forms of the StyleGAN2 and BigGAN hosts (glass_op_conv), the GEMMs (glass_op_gemm, glass_op_gemm_batched),
  * the StyleGAN2 / CLIP glue kernels, the GPT-2 trunk (glass_op_gpt2_*) and the BigGAN-deep glue kernels and fused tail (glass_op_bg_*;
- * tests/test_gpu_biggan_ops.py against the float64 restatements of tests/biggan_ops_ref.py).
+ * tests/test_gpu_biggan_ops.py against the float64 restatements of tests/biggan_ops_ref.py),
+ * and the small fp32 kernels of the mapping network, the style path, D's dense head and the CLIP glue (tests/test_gpu_small_ops.py).
  */
 #ifndef GLASS_OPS_H
 #define GLASS_OPS_H
@@ -195,6 +196,57 @@ int glass_op_rn_stem_conv1(int32_t device, int32_t B, int32_t S, int32_t C1, con
 int glass_op_rn_conv_bn(int32_t device, int32_t form, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t relu,
                         const float* x, const float* w, const float* bn_a, const float* bn_s, const float* res, float* out);
 int glass_op_rn_tokens(int32_t device, int32_t B, int32_t HW, int32_t C, const float* x, const float* pos, float* out);
+/* The small fp32 kernels around StyleGAN2 and the CLIP towers (kernels_misc.hip, kernels_clip.hip, clip_resnet.hip), each launched as the
+ * engine's host code launches it (tests/test_gpu_small_ops.py against the float64 restatements of tests/small_ops_ref.py).  Operands with a
+ * row stride hold whatever the caller put between the rows; an output wider than what the kernel writes is uploaded first and comes back
+ * whole, so that the caller sees what the kernel left alone.
+ *
+ * glass_op_mapping: launch_mapping, the launcher run_mapping calls — z [P,L], wt [n_layers][L(k)][L(n)] (transposed, coefficient folded), b
+ *   [n_layers][L] -> out [P,L].  path 0: as run_mapping decides; 1: the per-layer path (pixelnorm_kernel + dense_splitk_kernel, or
+ *   dense_kernel where L % 64 != 0 or L > 768); 2: mapping_fused_kernel, an error where it refuses.  *ran: 1 fused | 2 pixelnorm | 4
+ *   dense_splitk | 8 dense.
+ * glass_op_dense_splitk: launch_dense_splitk (K % 64 == 0, K <= 768; mode 0 / 1) on x [P,ldx], out [P,ldo] (in and out).
+ * glass_op_dense_ex: launch_dense with its strides: x [P,ldx], out [P,ldo] (in and out), eps_row [P,eps_stride] (mode 2 reads column 0).
+ * glass_op_dense_multi: n problems in one launch_dense_multi (in_sq 1, mode 2, no bias, as the demodulation launch): problem i reads columns
+ *   x_off[i] .. + K[i] of x [P,ldx], its weights wt_i [K[i],N[i]] (concatenated in wt) and eps_rows[p, eps_idx[i]] (eps_rows [P,eps_stride]),
+ *   and writes columns out_off[i] .. + N[i] of out [P,ldo] (in and out).
+ * glass_op_style_norm: launch_style_norm (eps 1e-8) on s [P,ld] in place over the segments (off[l], len[l]) -> smax, eps_row [P,n_layers].
+ * glass_op_d_head: D's dense head on dfin [P,16 CL] and w0 [CL,16 CL] (both rounded to fp16), b0 [CL], w1 [CL], b1 [1] -> dis [P], through
+ *   the launchers run_d_head calls: the split-K gemm_tiled + dense01_finish_kernel form where it applies (*split = 1), else gemm_tiled /
+ *   gemm_direct + dense_kernel (*split = 0).
+ * glass_op_layernorm_ex: launch_layernorm on rows row_stride apart (x holds (M - 1) row_stride + D floats); half_out: the fp16 output.
+ * glass_op_layernorm_rows: out[m] = LN(x[rows[m]]), x [n_rows,D].
+ * glass_op_cosine_views: feat [P,V,D] -> view_sim [P,V], sim [P].
+ * glass_op_image_patches: img [n,3,S,S] -> patches [n (S/ps)^2, ld] (fp16 values), pre-filled with `sentinel`.
+ * glass_op_rn_token0_rows: att [B,T,C] (fp16) -> out [B,C] = att[b, 0, :]. */
+int glass_op_mapping(int32_t device, int32_t P, int32_t L, int32_t n_layers, const float* z, const float* wt, const float* b, int32_t path,
+                     float* out, int32_t* ran);
+int glass_op_pixelnorm(int32_t device, int32_t P, int32_t L, const float* z, float* out);
+int glass_op_dense_splitk(int32_t device, int32_t P, int32_t K, int32_t N, int32_t ldx, int32_t ldo, int32_t mode, const float* x, const float* wt,
+                          const float* bias, float* out);
+int glass_op_dense_ex(int32_t device, int32_t P, int32_t K, int32_t N, int32_t ldx, int32_t ldo, const float* x, const float* wt, const float* bias,
+                      int32_t in_sq, int32_t mode, const float* eps_row, int32_t eps_stride, float* out);
+int glass_op_dense_multi(int32_t device, int32_t n, int32_t P, int32_t ldx, int32_t ldo, int32_t eps_stride, const int32_t* K, const int32_t* N,
+                         const int32_t* x_off, const int32_t* out_off, const int32_t* eps_idx, const float* x, const float* wt,
+                         const float* eps_rows, float* out);
+int glass_op_style_norm(int32_t device, int32_t P, int32_t ld, int32_t n_layers, const int32_t* off, const int32_t* len, float* s, float* smax,
+                        float* eps_row);
+int glass_op_d_head(int32_t device, int32_t P, int32_t CL, const float* dfin, const float* w0, const float* b0, const float* w1, const float* b1,
+                    float* dis, int32_t* split);
+int glass_op_finalize_image(int32_t device, int64_t n, const float* y, float* img);
+int glass_op_embed_lnpre(int32_t device, int32_t P, int32_t T, int32_t D, const float* patch_emb, const float* cls, const float* pos, const float* g,
+                         const float* b, float* x);
+int glass_op_embed_text(int32_t device, int32_t n_texts, int32_t ctx, int32_t D, int32_t V, const int32_t* tokens, const float* tok_emb,
+                        const float* pos, float* x);
+int glass_op_layernorm_ex(int32_t device, int32_t M, int32_t D, int64_t row_stride, int32_t half_out, const float* x, const float* g, const float* b,
+                          float* out);
+int glass_op_layernorm_rows(int32_t device, int32_t n_rows, int32_t M, int32_t D, const float* x, const int32_t* rows, const float* g, const float* b,
+                            float* out);
+int glass_op_cosine(int32_t device, int32_t P, int32_t D, const float* feat, const float* target, float* sim);
+int glass_op_cosine_views(int32_t device, int32_t P, int32_t V, int32_t D, const float* feat, const float* target, float* view_sim, float* sim);
+int glass_op_assemble_F(int32_t device, int32_t P, int32_t n_obj, const float* sim, const float* dis, float* F);
+int glass_op_image_patches(int32_t device, int32_t n, int32_t S, int32_t ps, int32_t ld, const float* img, float sentinel, float* patches);
+int glass_op_rn_token0_rows(int32_t device, int32_t B, int32_t T, int32_t C, const float* att, float* out);
 /* raw MFMA layout probe: D = A[32x16] * B[16x32] through the fragment mapping of common.h */
 int glass_op_mfma_probe(int32_t device, const float* a /*[32,16]*/, const float* b /*[16,32]*/, float* d /*[32,32]*/);
 
