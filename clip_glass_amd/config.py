@@ -9,7 +9,11 @@ image, include/glass.h), with `clip_view_min` (smallest crop side as a fraction 
 random, True) and `clip_view_fixed` (the same crops in every generation, False);
 `latent_space` ("z", the default: the reference's search; "w": rows are dlatents, the mapping network is skipped; "w+": one dlatent per
 style layer), `truncation_psi` (1.0: off) and `truncation_cutoff` (None: every layer) — the StyleGAN2 configs only (include/glass.h);
-refused for the BigGAN and GPT2 configs."""
+refused for the BigGAN and GPT2 configs;
+`lpips_target` (unset, the default: off; a path or an array [3, H, W] in [0, 1]: the LPIPS-VGG16 distance to that image becomes a search
+objective, include/glass.h), with `lpips_size` (256), `lpips_lambda` (0: an objective of its own — the Generator then searches a copy of the
+config with `n_obj` one higher and `algorithm` "nsga2", this table is not touched; > 0: added to the similarity objective) and
+`lpips_weights` (a torch file or "synthetic:<seed>") — the StyleGAN2 and BigGAN configs; refused for GPT2."""
 from .latent import DeepMindBigGANLatentSpace, GPT2LatentSpace, StyleGAN2LatentSpace
 from .models import GPT2, DeepMindBigGAN, StyleGAN2
 from .utils import biggan_denorm, biggan_norm

@@ -104,7 +104,19 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     REQUIRE(cfg->latent_size > 0 && cfg->latent_size % 4 == 0, GLASS_ERR_ARG, "latent_size must be a multiple of 4");
     REQUIRE(cfg->batch_size > 0 && cfg->max_pop > 0, GLASS_ERR_ARG, "batch_size/max_pop must be positive");
     REQUIRE(cfg->max_pop % cfg->batch_size == 0, GLASS_ERR_ARG, "max_pop must be a multiple of batch_size");
-    REQUIRE(cfg->n_obj == 1 || cfg->n_obj == 2, GLASS_ERR_ARG, "n_obj must be 1 or 2");
+    const bool lpips = cfg->lpips_size != 0;      // the perceptual objective (opt-in): its own last column unless lpips_lambda folds it into column 0
+    if (!lpips) {
+        REQUIRE(cfg->n_obj == 1 || cfg->n_obj == 2, GLASS_ERR_ARG, "n_obj must be 1 or 2");
+    } else {
+        REQUIRE(cfg->n_blocks > 0 || cfg->generator == GLASS_GEN_BIGGAN_DEEP, GLASS_ERR_ARG,
+                "lpips_size > 0 needs a generator: this engine has none (GPT-2 / img2txt), so there is no generated image to compare");
+        if (int lrc = glass_lpips_supported(0, cfg->lpips_size)) return lrc;
+        REQUIRE(std::isfinite(cfg->lpips_lambda) && cfg->lpips_lambda >= 0.f, GLASS_ERR_ARG, "lpips_lambda must be finite and >= 0");
+        const int want = 1 + (cfg->use_discriminator ? 1 : 0) + (cfg->lpips_lambda == 0.f ? 1 : 0);
+        REQUIRE(cfg->n_obj == want, GLASS_ERR_ARG,
+                "with lpips_size > 0, n_obj must be 1 + use_discriminator + (lpips_lambda == 0) = " + std::to_string(want) + ", got " +
+                    std::to_string(cfg->n_obj));
+    }
     if (cfg->use_discriminator) {
         REQUIRE(cfg->mbstd_group >= 2 && cfg->mbstd_group <= 8 && cfg->batch_size % cfg->mbstd_group == 0, GLASS_ERR_ARG,
                 "batch_size must be a multiple of mbstd_group (modules.py:716)");
@@ -123,7 +135,7 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     REQUIRE(cfg->noise_mode >= 0 && cfg->noise_mode <= 2, GLASS_ERR_ARG, "noise_mode must be 0,1,2");
     int bg_res = 0;
     if (cfg->generator == GLASS_GEN_BIGGAN_DEEP) {
-        REQUIRE(cfg->n_blocks == 0 && !cfg->use_discriminator && cfg->n_obj == 1, GLASS_ERR_ARG,
+        REQUIRE(cfg->n_blocks == 0 && !cfg->use_discriminator && (lpips || cfg->n_obj == 1), GLASS_ERR_ARG,
                 "BigGAN-deep: n_blocks must be 0, no discriminator, n_obj 1 (config.py:31-74)");
         REQUIRE(cfg->bg_n_layers > 0 && cfg->bg_n_layers <= GLASS_MAX_BG_LAYERS, GLASS_ERR_ARG, "bg_n_layers out of range");
         REQUIRE(cfg->bg_ch > 0 && cfg->bg_ch % 32 == 0 && cfg->bg_z_dim > 0 && cfg->bg_z_dim % 4 == 0 && cfg->bg_num_classes > 0,
@@ -148,6 +160,8 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     }
     const int gen_res = cfg->n_blocks > 0 ? 4 << (cfg->n_blocks - 1) : bg_res;
     if (int prc = glass_clip_preprocess_supported(gen_res, cfg->clip_res, cfg->clip_resize, cfg->clip_normalize)) return prc;
+    if (lpips)
+        if (int lrc = glass_lpips_supported(gen_res, cfg->lpips_size)) return lrc;
     int ndev = 0;
     GLASS_HIP(hipGetDeviceCount(&ndev));
     REQUIRE(cfg->device >= 0 && cfg->device < ndev, GLASS_ERR_ARG, "no such HIP device");
@@ -341,7 +355,7 @@ static int alloc_buffers(glass_engine* e) {
     if (e->views && (rc = dev_alloc(e, &e->d_view_sim, PI))) return rc;
     if ((rc = dev_alloc(e, &e->d_sim, (size_t)P))) return rc;
     if ((rc = dev_alloc(e, &e->d_dis, (size_t)P))) return rc;
-    if ((rc = dev_alloc(e, &e->d_F, (size_t)P * 2))) return rc;
+    if ((rc = dev_alloc(e, &e->d_F, (size_t)P * (c.lpips_size ? 3 : 2)))) return rc;
     if ((rc = dev_alloc(e, &e->d_target, (size_t)c.clip_embed))) return rc;
     if (c.use_discriminator && c.n_blocks > 0) {
         if ((rc = dev_alloc(e, &e->d_dfin, (size_t)P * 16 * c.channels[0]))) return rc;
@@ -380,6 +394,7 @@ extern "C" int glass_engine_finalize(glass_engine* e) {
     if ((rc = finalize_gpt2(e))) return rc;
     if ((rc = finalize_clip(e))) return rc;
     if ((rc = finalize_preprocess(e))) return rc;
+    if ((rc = finalize_lpips(e))) return rc;
     if ((rc = alloc_buffers(e))) return rc;
     e->host.clear();  // host copies no longer needed
     e->finalized = true;
@@ -507,7 +522,8 @@ static int finish_pass(glass_engine* e, int P, float* out_F, bool clip_done, hip
             GLASS_HIP(hipEventRecord(e->ev_g[0], d_join));
             GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_g[0], 0));
         }
-        launch_assemble_F(e->d_sim, e->d_dis, P, c.n_obj, e->d_F, e->cur);
+        if (c.lpips_size) launch_assemble_F_lpips(e->d_sim, e->d_dis, e->lp.d, c.lpips_lambda, c.use_discriminator ? 1 : 0, P, c.n_obj, e->d_F, e->cur);
+        else launch_assemble_F(e->d_sim, e->d_dis, P, c.n_obj, e->d_F, e->cur);
         GLASS_HIP(hipMemcpyAsync(e->h_pinned, e->d_F, (size_t)P * c.n_obj * sizeof(float), hipMemcpyDeviceToHost,
                                  e->cur));
     }
@@ -539,6 +555,8 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
     const bool biggan = c.generator == GLASS_GEN_BIGGAN_DEEP;
     REQUIRE(e->cfg.n_blocks > 0 || biggan, GLASS_ERR_STATE, "this engine was created without a GAN (n_blocks = 0)");
     if (out_F) REQUIRE(e->has_target, GLASS_ERR_STATE, "set_target() first");
+    const bool lpips = out_F && c.lpips_size > 0;
+    if (lpips) REQUIRE(e->lp.has_target, GLASS_ERR_STATE, "set_lpips_target() first");
     GLASS_HIP(hipSetDevice(c.device));
     e->launch_error.clear();      // (a pass that returned early through GLASS_HIP must not leave its message to the next one)
     // the rows go where run_styles reads them: z rows in front of the mapping network, w rows in its output's place, w+ rows per layer
@@ -578,6 +596,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
                 Prof pr(e, resize_tag, 0, clip_resize_bytes(e, B));
                 run_clip_resize(e, y, B, e->d_patches + (size_t)c0 * cand_patches);
             }
+            if (lpips) run_lpips_chunk(e, y, c0, B);
         }
         return finish_pass(e, P, out_F, false, nullptr);
     }
@@ -598,7 +617,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
         rc = upload_noise(e, P, generation, first_mb, noise);
         if (rc) return rc;
     }
-    const bool want_d = out_F && c.use_discriminator && c.n_obj == 2;
+    const bool want_d = out_F && c.use_discriminator && (c.lpips_size > 0 || c.n_obj == 2);      // (with the perceptual objective n_obj counts its column too)
     const int n = c.n_blocks;
     const int nlow = std::min(n, e->n_low);           // G blocks 0..nlow-1 run for the whole population
     const int nd = (int)e->dblk.size();               // D conv blocks (n - 1)
@@ -680,6 +699,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
                     run_fromrgb(e, B, y, dmid + (size_t)c0 * dmid_bs);
                 }
             }
+            if (lpips) run_lpips_chunk(e, y, c0, B);      // VGG16 on the discriminator's stream, behind it: the chunk's image is complete
             if (overlap) GLASS_HIP(hipEventRecord(e->ev_d[k], sd));
         }
     }

@@ -81,6 +81,24 @@ struct RnState {
     size_t cap = 0;
 };
 
+// Perceptual objective: LPIPS on VGG16 (lpips.cpp, lpips.hip; stylegan2/external_models/lpips.py:34-78).  All of it is allocated only
+// with glass_config::lpips_size > 0.
+struct LpState {
+    int S = 0, box = 0, sub = 0;         // VGG input side; R / S; images one walk carries (GLASS_LPIPS_SUB at most — results do not depend on it)
+    half_t* w1 = nullptr;                // features.0: [27][64], row (ci, ky, kx)
+    float* b1 = nullptr;
+    RnConv conv[12];                     // features.2 .. 28 as gemm_tiled's BatchNorm form: a = 1, s = bias
+    float* ones = nullptr;               // [512]
+    float* lin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    half_t* in = nullptr;                // [sub][S][S][4]
+    half_t* buf[2] = {nullptr, nullptr}; // ping-pong, sub S S 64 halfs each (the first slice's map, the largest)
+    half_t* tgt[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};    // the target's five slice outputs (set_lpips_target)
+    half_t* pair[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // glass_engine_lpips: x1's maps of the pair in flight
+    float *stage = nullptr, *part = nullptr, *d = nullptr, *d_one = nullptr;   // one caller image fp32; head partials; d [max_pop]; the utility's value
+    bool has_target = false;
+};
+#define GLASS_LPIPS_SUB 16
+
 // BigGAN-deep generator (biggan.cpp)
 struct BgBlock {   // GenBlock: bn0-relu-conv1x1 / bn1-relu-[up]-conv3x3 / bn2-relu-conv3x3 / bn3-relu-conv1x1 + skip
     int cin, cout, mid, up, res_in;
@@ -184,6 +202,7 @@ struct glass_engine {
     int views = 0, view_min_permille = 0, view_flip = 0, view_fixed = 0;
     ViewBoxes view_boxes = {};          // the boxes of the current / last evaluate(): one set for every candidate of the pass
     float* d_view_sim = nullptr;        // [max_pop][views]
+    LpState lp;                // perceptual objective (cfg.lpips_size > 0; nothing of it exists otherwise)
     // GPT-2 (optional, fp32; config C5)
     struct Gpt2Block { float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *w_qkv, *b_qkv, *w_o, *b_o, *w_fc, *b_fc, *w_pr, *b_pr; };
     std::vector<Gpt2Block> gblk;
@@ -428,6 +447,11 @@ std::vector<_Float16> to_half(const float* p, size_t n, float scale = 1.f);
 std::vector<float> scaled(const float* p, size_t n, float scale);
 std::vector<float> transposed(const float* W, int N, int K, float coef);
 
+
+// ---- perceptual objective (lpips.cpp) ----
+int finalize_lpips(glass_engine* e);          // weights -> device layouts + buffers (nothing with lpips_size 0)
+// d[c0 + i] for the B candidates whose raw images are at y [B][3][R][R], on e->cur: box mean + VGG16 + head against the stored target
+void run_lpips_chunk(glass_engine* e, const float* y, int c0, int B);
 
 // ---- GPT-2 (gpt2_host.cpp) ----
 int finalize_gpt2(glass_engine* e);

@@ -163,6 +163,21 @@ void launch_cosine(const float* feat, const float* target, int P, int D, float* 
 // crop views: feat [P][V][D]; view_sim[p V + v] = launch_cosine's value of that row, sim[p] = their fp32 mean summed in the order v = 0 .. V - 1
 void launch_cosine_views(const float* feat, const float* target, int P, int V, int D, float* view_sim, float* sim, hipStream_t st);
 void launch_assemble_F(const float* sim, const float* dis, int P, int n_obj, float* F, hipStream_t st);
+// the same rows with the perceptual distance lp [P]: lambda == 0: its own LAST column; lambda > 0: F[:, 0] = fmaf(lambda, lp, -sim), no column.
+// has_d: column 1 is the discriminator hinge
+void launch_assemble_F_lpips(const float* sim, const float* dis, const float* lp, float lambda, int has_d, int P, int n_obj, float* F, hipStream_t st);
+
+// --- perceptual objective: LPIPS on VGG16 (lpips.hip); the 3 x 3 convolutions behind the first are gemm_tiled (mode 5, A = 1, S = bias) ---
+#define GLASS_LPIPS_PIXB 256      // pixels of one image a workgroup of the head owns
+// box mean R -> S (R % S == 0, box <= 8) of planar fp32 y [B][3][R][R], then (v - shift_c) / scale_c -> [B][S][S][4] fp16 (channel 3 = 0)
+bool launch_lpips_input(const float* y, int B, int R, int S, half_t* out, hipStream_t st);
+// features.0 (3 x 3 pad 1, 3 -> 64, + bias + ReLU): x [B][S][S][4], w [27][64] fp16 with row (ci, ky, kx) -> y [B][S][S][64]
+bool launch_vgg_conv1(const half_t* x, const half_t* w, const float* bias, int B, int S, half_t* y, hipStream_t st);
+bool launch_maxpool2(const half_t* x, int B, int H, int W, int C, half_t* y, hipStream_t st);      // MaxPool2d(2), NHWC; false: odd side or C % 8
+// one slice's term of n images: x0 [n][HW][C] against x1 + i x1_bs (x1_bs 0: one map for all), lin [C]; part: n ceil(HW / GLASS_LPIPS_PIXB)
+// floats of scratch; d[i] = term (first) or d[i] += term.  false: C is not one of 64 / 128 / 256 / 512
+bool launch_lpips_head(const half_t* x0, const half_t* x1, long long x1_bs, const float* lin, int n, int HW, int C, float* part, int first, float* d,
+                       hipStream_t st);
 
 // --- CLIP's ResNet towers (clip_resnet.hip); BatchNorm = fp32 per-channel scale bn_a and shift bn_s in the epilogue ---------------------
 // stem conv1 (3 x 3 stride 2 pad 1, 3 -> C1, + BN + ReLU) from the 32-pixel patch operand of an S x S image -> [B][S/2][S/2][C1]; w [27][C1] fp16,

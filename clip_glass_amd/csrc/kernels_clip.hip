@@ -451,14 +451,19 @@ void launch_cosine_views(const float* feat, const float* target, int P, int V, i
 }
 
 // problem.py:23-27: F = column_stack(-sim, relu(1 - dis)) or F = -sim
-__global__ void assemble_F_kernel(const float* sim, const float* dis, int P, int n_obj, float* F) {
+// lp (nullable): the perceptual distance — lambda == 0: the last column; lambda > 0: folded into column 0
+__global__ void assemble_F_kernel(const float* sim, const float* dis, const float* lp, float lambda, int has_d, int P, int n_obj, float* F) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
-    F[(long long)p * n_obj] = -sim[p];
-    if (n_obj == 2) F[(long long)p * n_obj + 1] = fmaxf(1.f - dis[p], 0.f);
+    F[(long long)p * n_obj] = (lp && lambda > 0.f) ? fmaf(lambda, lp[p], -sim[p]) : -sim[p];
+    if (has_d) F[(long long)p * n_obj + 1] = fmaxf(1.f - dis[p], 0.f);
+    if (lp && !(lambda > 0.f)) F[(long long)p * n_obj + n_obj - 1] = lp[p];
 }
 void launch_assemble_F(const float* sim, const float* dis, int P, int n_obj, float* F, hipStream_t st) {
-    hipLaunchKernelGGL(assemble_F_kernel, dim3((P + 63) / 64), dim3(64), 0, st, sim, dis, P, n_obj, F);
+    hipLaunchKernelGGL(assemble_F_kernel, dim3((P + 63) / 64), dim3(64), 0, st, sim, dis, (const float*)nullptr, 0.f, n_obj == 2 ? 1 : 0, P, n_obj, F);
+}
+void launch_assemble_F_lpips(const float* sim, const float* dis, const float* lp, float lambda, int has_d, int P, int n_obj, float* F, hipStream_t st) {
+    hipLaunchKernelGGL(assemble_F_kernel, dim3((P + 63) / 64), dim3(64), 0, st, sim, dis, lp, lambda, has_d, P, n_obj, F);
 }
 
 // images already resized / normalised by the caller (clip.py:68-74 preprocess) -> patch-embedding operand

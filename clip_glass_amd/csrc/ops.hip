@@ -1330,6 +1330,71 @@ extern "C" int glass_op_rn_tokens(int32_t device, int32_t B, int32_t HW, int32_t
     return rc ? rc : down16(out, dy, no);
 }
 
+// ---- perceptual objective (lpips.hip) ----
+extern "C" int glass_op_lpips_input(int32_t device, int32_t B, int32_t R, int32_t S, const float* y, float* out) {
+    OPREQ(y && out && B > 0 && R > 0 && S > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t no = (size_t)B * S * S * 4;
+    float* dy = dv.up32(y, (size_t)B * 3 * R * R);
+    half_t* dout = dv.alloc<half_t>(no);
+    OPREQ(dy && dout, "allocation failed");
+    OPREQ(launch_lpips_input(dy, B, R, S, dout, 0), "lpips_input: refused (R a multiple of S, box R / S at most 8)");
+    int rc = finish();
+    return rc ? rc : down16(out, dout, no);
+}
+
+extern "C" int glass_op_vgg_conv1(int32_t device, int32_t B, int32_t S, const float* x, const float* w, const float* bias, float* out) {
+    OPREQ(x && w && bias && out && B > 0 && S > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t no = (size_t)B * S * S * 64;
+    std::vector<_Float16> wt((size_t)27 * 64);
+    for (int o = 0; o < 64; ++o)
+        for (int k = 0; k < 27; ++k) wt[(size_t)k * 64 + o] = (_Float16)w[(size_t)o * 27 + k];
+    half_t* dx = dv.up16(x, (size_t)B * S * S * 4);
+    half_t* dw = dv.up16v(wt);
+    float* db = dv.up32(bias, 64);
+    half_t* dy = dv.alloc<half_t>(no);
+    OPREQ(dx && dw && db && dy, "allocation failed");
+    OPREQ(launch_vgg_conv1(dx, dw, db, B, S, dy, 0), "vgg_conv1: refused");
+    int rc = finish();
+    return rc ? rc : down16(out, dy, no);
+}
+
+extern "C" int glass_op_maxpool2(int32_t device, int32_t B, int32_t H, int32_t W, int32_t C, const float* x, float* out) {
+    OPREQ(x && out && B > 0 && H > 0 && W > 0 && C > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t no = (size_t)B * (H / 2) * (W / 2) * C;
+    half_t* dx = dv.up16(x, (size_t)B * H * W * C);
+    half_t* dy = dv.alloc<half_t>(no);
+    OPREQ(dx && dy, "allocation failed");
+    OPREQ(launch_maxpool2(dx, B, H, W, C, dy, 0), "maxpool2: refused (even H and W, C a multiple of 8)");
+    int rc = finish();
+    return rc ? rc : down16(out, dy, no);
+}
+
+extern "C" int glass_op_lpips_head(int32_t device, int32_t n, int32_t HW, int32_t C, int32_t shared_x1, const float* x0, const float* x1, const float* lin,
+                                   float* out) {
+    OPREQ(x0 && x1 && lin && out && n > 0 && HW > 0 && C > 0, "bad argument");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t map = (size_t)HW * C, nblk = ((size_t)HW + GLASS_LPIPS_PIXB - 1) / GLASS_LPIPS_PIXB;
+    half_t* d0 = dv.up16(x0, (size_t)n * map);
+    half_t* d1 = dv.up16(x1, (shared_x1 ? 1 : (size_t)n) * map);
+    float* dl = dv.up32(lin, C);
+    float* part = dv.alloc<float>((size_t)n * nblk);
+    float* dd = dv.alloc<float>(n);
+    OPREQ(d0 && d1 && dl && part && dd, "allocation failed");
+    GLASS_HIP(hipMemset(dd, 0xFF, (size_t)n * sizeof(float)));
+    OPREQ(launch_lpips_head(d0, d1, shared_x1 ? 0 : (long long)map, dl, n, HW, C, part, 1, dd, 0), "lpips_head: refused (C one of 64, 128, 256, 512)");
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(out, dd, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
 extern "C" int glass_op_mfma_probe(int32_t device, const float* a, const float* b, float* d) {
     OPREQ(a && b && d, "null argument");
     GLASS_HIP(hipSetDevice(device));

@@ -38,6 +38,12 @@ class GlassConfigResnet(C.Structure):
     _fields_ = GlassConfig._fields_ + [("clip_arch", C.c_int32), ("clip_rn_layers", C.c_int32 * 4)]
 
 
+class GlassConfigLpips(C.Structure):
+    """glass_config as the library defines it now: GlassConfigResnet's fields, then the perceptual objective's, appended as the ResNet
+    tower's were (zero: off).  The two shorter structs stay what libraries built before each addition read."""
+    _fields_ = GlassConfigResnet._fields_ + [("lpips_size", C.c_int32), ("lpips_lambda", C.c_float)]
+
+
 class GlassNoise(C.Structure):
     _fields_ = [("n_minibatches", C.c_int32), ("n_layers", C.c_int32),
                 ("planes", C.POINTER(C.POINTER(C.c_float)))]
@@ -64,7 +70,7 @@ def load_library(path=None):
     fp = C.POINTER(C.c_float)
     lib.glass_last_error.restype = C.c_char_p
     lib.glass_version.restype = C.c_char_p
-    lib.glass_engine_create.argtypes = [C.POINTER(GlassConfigResnet), C.POINTER(C.c_void_p)]
+    lib.glass_engine_create.argtypes = [C.POINTER(GlassConfigLpips), C.POINTER(C.c_void_p)]
     if hasattr(lib, "glass_clip_geometry_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
         lib.glass_clip_geometry_supported.argtypes = [C.c_int32] * 6
     if hasattr(lib, "glass_clip_preprocess_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
@@ -84,6 +90,11 @@ def load_library(path=None):
         lib.glass_engine_set_truncation.argtypes = [C.c_void_p, C.c_float, C.c_int32]
         lib.glass_engine_latent_row.argtypes = [C.c_void_p, ip, ip]
         lib.glass_engine_map_latents.argtypes = [C.c_void_p, fp, C.c_int32, fp]
+    if hasattr(lib, "glass_lpips_supported"):           # (absent from older A/B builds loaded through GLASS_LIB)
+        lib.glass_lpips_supported.argtypes = [C.c_int32] * 2
+        lib.glass_engine_set_lpips_target.argtypes = [C.c_void_p, fp, C.c_int32]
+        lib.glass_engine_lpips.argtypes = [C.c_void_p, fp, fp, C.c_int32, fp]
+        lib.glass_engine_last_lpips.argtypes = [C.c_void_p, C.c_int32, fp]
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -150,6 +161,19 @@ def clip_resnet_supported(geometry):
     arr = (C.c_int32 * 4)(*[int(v) for v in layers])
     rc = lib.glass_clip_resnet_supported(arr, int(width), int(res), int(embed))
     return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
+def lpips_supported(gen_res, lpips_size):
+    """(ok, message) for the perceptual objective at VGG input side lpips_size on a gen_res px generator (0: the side alone): the
+    library's own rule, the one glass_engine_create applies.  Host only."""
+    lib = load_library()
+    rc = lib.glass_lpips_supported(int(gen_res), int(lpips_size))
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
+def lpips_n_obj(use_discriminator, lpips_lambda):
+    """Columns of F with the perceptual objective on (include/glass.h): -sim, the hinge with D, and the distance unless lambda folds it in."""
+    return 1 + int(bool(use_discriminator)) + int(float(lpips_lambda) == 0.0)
 
 
 def clip_view_permille(fraction):
@@ -225,7 +249,7 @@ class Engine:
                  n_obj=2, max_pop=64, chunk=0, clip=(768, 12, 12, 32, 224, 512), noise_mode=1, noise_seed=0,
                  mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0, clip_resnet=None,
                  clip_views=0, clip_view_min=0.5, clip_view_flip=True, clip_view_fixed=False,
-                 latent_space="z", truncation_psi=1.0, truncation_cutoff=None):
+                 latent_space="z", truncation_psi=1.0, truncation_cutoff=None, lpips_size=0, lpips_lambda=0.0):
         """`biggan` = dict(layers=[(up, in_mult, out_mult), ...], attention_pos, ch, z_dim, num_classes, n_stats, eps,
         truncation) selects the BigGAN-deep generator (channels must then be empty, no discriminator).
         clip_resize / clip_normalize: how a generated image is prepared for CLIP (include/glass.h); (0, 0) is the reference's way.
@@ -237,9 +261,13 @@ class Engine:
         latent_space "z" (default) / "w" / "w+" and truncation_psi / truncation_cutoff (StyleGAN2 only; include/glass.h): what a row of
         evaluate / generate is, and the truncation trick applied to it.  The defaults call neither setter: the reference's raw generator
         on z.  A psi or cutoff given here is set before finalize, which then keeps the per-layer buffer a later set_truncation with a
-        cutoff needs."""
+        cutoff needs.
+        lpips_size = S > 0 turns the perceptual objective on (include/glass.h): the LPIPS-VGG16 distance between a candidate's image,
+        area-downscaled to S px, and the image given to set_lpips_target().  lpips_lambda = 0: the distance is one more, last, column
+        of F and n_obj must count it (lpips_n_obj); > 0: F[:, 0] = -sim + lambda * d and n_obj stays.  Needs the "lpips.*" tensors."""
         self.lib = load_library()
-        cfg = GlassConfigResnet()
+        cfg = GlassConfigLpips()
+        cfg.lpips_size, cfg.lpips_lambda = int(lpips_size), float(lpips_lambda)
         cfg.device = device
         if biggan is not None:
             layers = list(biggan["layers"])
@@ -253,7 +281,8 @@ class Engine:
             cfg.bg_n_stats, cfg.bg_eps = int(biggan.get("n_stats", 51)), float(biggan.get("eps", 1e-4))
             cfg.bg_truncation = float(biggan.get("truncation", 1.0))
             latent_size = cfg.bg_z_dim + cfg.bg_num_classes
-            channels, use_discriminator, n_obj, noise_mode = [], False, 1, 0
+            channels, use_discriminator, noise_mode = [], False, 0
+            n_obj = lpips_n_obj(False, lpips_lambda) if cfg.lpips_size else 1
         cfg.n_blocks = len(channels)
         for i, c in enumerate(channels):  # LOW -> HIGH resolution
             cfg.channels[i] = int(c)
@@ -325,6 +354,31 @@ class Engine:
     def set_target(self, feat):
         f = _f32(feat).reshape(-1)
         _check(self.lib, self.lib.glass_engine_set_target(self._h, _fp(f), f.size))
+
+    # --- perceptual objective --------------------------------------------------
+    def set_lpips_target(self, image):
+        """The target of the perceptual objective: float32 [3, S, S] in [-1, 1], S = lpips_size.  After finalize()."""
+        a = _f32(image)
+        S = int(self.cfg.lpips_size)
+        if a.shape != (3, S, S):
+            raise ValueError("set_lpips_target: the image must be [3, %d, %d], got %r" % (S, S, a.shape))
+        _check(self.lib, self.lib.glass_engine_set_lpips_target(self._h, _fp(a), S))
+
+    def lpips(self, x0, x1):
+        """LPIPS_VGG16.forward(x0, x1) on caller images float32 [n, 3, S, S] in [-1, 1], through the kernels of the pass -> [n]."""
+        a, b = _f32(x0), _f32(x1)
+        S = int(self.cfg.lpips_size)
+        if a.ndim != 4 or a.shape[1:] != (3, S, S) or b.shape != a.shape:
+            raise ValueError("lpips: both image stacks must be [n, 3, %d, %d], got %r and %r" % (S, S, a.shape, b.shape))
+        out = np.empty((a.shape[0],), dtype=np.float32)
+        _check(self.lib, self.lib.glass_engine_lpips(self._h, _fp(a), _fp(b), a.shape[0], _fp(out)))
+        return out
+
+    def last_lpips(self, P):
+        """The distances [P] of the last evaluate()."""
+        d = np.empty((P,), dtype=np.float32)
+        _check(self.lib, self.lib.glass_engine_last_lpips(self._h, P, _fp(d)))
+        return d
 
     def encode_text(self, tokens):
         """CLIP.encode_text (clip/model.py:307-320): tokens int [n, ctx] -> float32 [n, clip_embed]."""

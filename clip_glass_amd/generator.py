@@ -5,13 +5,14 @@ and exposes generate / clip_similarity / discriminate / save.  Here the GAN, the
 CLIP live on the device behind ONE call (`evaluate`), so `_evaluate` makes a single trip;
 `generate` / `save` serve run.py's callbacks (run.py:45-51,118-125).
 """
+import copy
 import os
 
 import numpy as np
 
 from . import synth
 from .engine import (LATENT_SPACES, Engine, clip_geometry_supported, clip_resnet_supported, clip_view_permille, clip_views_supported,
-                     clip_views_tower_rows)
+                     clip_views_tower_rows, lpips_n_obj, lpips_supported)
 from .utils import save_grid, save_image
 
 CLIP_VIT_B32 = (768, 12, 12, 32, 224, 512)
@@ -71,6 +72,92 @@ def latent_options(config):
         raise ValueError("latent_space / truncation_psi / truncation_cutoff belong to the StyleGAN2 configs (a mapping network and an "
                          "average dlatent); config %r has neither: leave them unset" % name)
     return space, psi, cutoff
+
+
+# ---- perceptual objective (opt-in, include/glass.h): LPIPS-VGG16 distance of every candidate's image to a target image ----
+DEFAULT_LPIPS_SIZE = 256       # what the reference's projector feeds its LPIPS (stylegan2/project.py:107)
+LPIPS_KEYS = ("lpips_target", "lpips_size", "lpips_lambda", "lpips_weights")
+
+
+def lpips_options(config):
+    """None while `lpips_target` is unset (the default: today's pass), else dict(target, size, lam, weights) from the config keys
+    lpips_target (a path opened with PIL, or an array [3, H, W] in [0, 1]), lpips_size (256), lpips_lambda (0: the distance is one more
+    objective; > 0: it is added to the first, times lambda) and lpips_weights (a torch file with the keys of include/glass.h, or
+    "synthetic:<seed>").  ValueError, before any weight is looked for, on the GPT2 config (no image is generated there), for the other
+    keys without a target, and for a size the library refuses."""
+    vals = {k: getattr(config, k, None) for k in LPIPS_KEYS}
+    given = [k for k in LPIPS_KEYS if vals[k] is not None]
+    if not given:
+        return None
+    if getattr(config, "task", "txt2img") == "img2txt":
+        raise ValueError("%s: the perceptual objective compares generated images with a target image; the img2txt task (config %r) "
+                         "generates none: leave the lpips_* keys unset" % (", ".join(given), str(getattr(config, "config", "GPT2"))))
+    if vals["lpips_target"] is None:
+        raise ValueError("%s set without lpips_target: the perceptual objective is off unless a target image is given" % ", ".join(given))
+    size = DEFAULT_LPIPS_SIZE if vals["lpips_size"] is None else int(vals["lpips_size"])
+    lam = 0.0 if vals["lpips_lambda"] is None else float(vals["lpips_lambda"])
+    if not (lam >= 0.0 and np.isfinite(lam)):
+        raise ValueError("lpips_lambda must be finite and >= 0, got %r" % (vals["lpips_lambda"],))
+    ok, msg = lpips_supported(0, size)
+    if not ok:
+        raise ValueError("lpips_size=%d: %s" % (size, msg))
+    if vals["lpips_weights"] is None:       # as for CLIP: a silent random-weight VGG16 would steer a whole search by a meaningless distance
+        raise RuntimeError("config.lpips_weights is not set: pass the VGG16 + LPIPS linear weights (--lpips-weights PATH), or "
+                           "'synthetic:<seed>' explicitly for tests / benchmarks")
+    return dict(target=vals["lpips_target"], size=size, lam=lam, weights=str(vals["lpips_weights"]))
+
+
+def lpips_config(config, opts):
+    """The config a search with the perceptual objective runs on: a COPY (the caller's namespace and the config table keep their
+    values).  lambda = 0: problem_args["n_obj"] one higher and algorithm "nsga2"; lambda > 0: both as they are."""
+    if opts is None or opts["lam"] > 0.0:
+        return config
+    out = copy.copy(config)
+    out.problem_args = dict(config.problem_args, n_obj=int(config.problem_args["n_obj"]) + 1)
+    out.algorithm = "nsga2"
+    return out
+
+
+def prepare_lpips_target(target, size):
+    """The target image as the engine takes it: float32 [3, size, size] in [-1, 1].  target: a path (opened with PIL, RGB, / 255), a PIL
+    image, or an array [3, H, W] in [0, 1].  Centre-crop to the largest square, then down to `size`: where the square's side is a multiple
+    of size, the exact box mean — the area downscale the generated images get (stylegan2/project.py:113-122); otherwise (and when the
+    square is smaller than size) PIL's antialiased bicubic resize of the float channels, which is NOT that filter: prefer a target whose
+    shorter side is a multiple of size.  Then 2 x - 1."""
+    if isinstance(target, (str, os.PathLike)) or hasattr(target, "convert"):
+        from PIL import Image
+        img = Image.open(target) if not hasattr(target, "convert") else target
+        a = np.asarray(img.convert("RGB"), dtype=np.float32).transpose(2, 0, 1) / 255.0
+    else:
+        a = np.asarray(target, dtype=np.float32)
+    if a.ndim != 3 or a.shape[0] != 3:
+        raise ValueError("lpips_target must be an image [3, H, W] in [0, 1], got shape %r" % (a.shape,))
+    _, H, W = a.shape
+    side = min(H, W)
+    top, left = (H - side) // 2, (W - side) // 2
+    a = a[:, top:top + side, left:left + side]
+    if side % size == 0:
+        b = side // size
+        a = a.reshape(3, size, b, size, b).astype(np.float64).mean(axis=(2, 4))
+    else:
+        from PIL import Image
+        a = np.stack([np.asarray(Image.fromarray(np.ascontiguousarray(ch), mode="F").resize((size, size), Image.BICUBIC)) for ch in a])
+    return np.ascontiguousarray(2.0 * a - 1.0, dtype=np.float32)
+
+
+def load_lpips_state(weights):
+    """Engine tensors of the perceptual objective: "synthetic[:seed]" -> synth.lpips_state; otherwise a torch file holding
+    "lpips.features.N.{weight,bias}" (torchvision's vgg16 `features` keys; the prefix may be missing) and "lpips.lin.K.weight"."""
+    if weights.startswith("synthetic"):
+        return synth.lpips_state(int(weights.split(":")[1]) if ":" in weights else 0)
+    import torch
+    sd = torch.load(weights, map_location="cpu")
+    state = {}
+    for k, v in sd.items():
+        k = k if k.startswith("lpips.") else "lpips." + k
+        a = np.asarray(v.float().numpy() if hasattr(v, "float") else v, dtype=np.float32)
+        state[k] = a.reshape(-1) if k.startswith("lpips.lin.") else a
+    return state
 
 
 def clip_model_geometry(name):
@@ -274,6 +361,11 @@ def clip_preprocess(path_or_image, n_px=224):
 
 class Generator:
     def __init__(self, config, dist=None):
+        # perceptual objective (opt-in): refused for the GPT2 config here, before any weight is looked for; with lambda = 0 the search gets
+        # one more objective — on a copy of the config, which callers read back as `generator.config`
+        self.lpips = lpips_options(config)
+        base_n_obj = int((getattr(config, "problem_args", None) or {}).get("n_obj", 1))
+        config = lpips_config(config, self.lpips)
         self.config = config
         self.augmentation = None
         self.model = config.model(config)                                   # generator.py:19
@@ -349,6 +441,8 @@ class Generator:
                 raise ValueError("clip_views=%d (clip_preprocess=%r): %s" % (self.clip_views, self.clip_preprocess, msg))
             self.augmentation = dict(kind="crop_views", **view_kw)      # the reference's hook (generator.py:14, 46-47), filled by the engine
         tower.update(view_kw)
+        if self.lpips is not None:
+            tower.update(lpips_size=self.lpips["size"], lpips_lambda=self.lpips["lam"])
         if hasattr(self.model, "geometry"):     # BigGAN-deep (models.py:64-86)
             self.engine = Engine([], batch_size=config.batch_size, max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  device=device, biggan=self.model.geometry, clip_resize=clip_resize,
@@ -356,8 +450,9 @@ class Generator:
         else:
             self.engine = Engine(self.model.channels[::-1], latent_size=config.dim_z,
                                  mapping_layers=getattr(config, "mapping_layers", 8), batch_size=config.batch_size,
-                                 use_discriminator=bool(config.use_discriminator and config.problem_args["n_obj"] == 2),
-                                 n_obj=config.problem_args["n_obj"], max_pop=pop, chunk=getattr(config, "chunk", 0),
+                                 use_discriminator=bool(config.use_discriminator and base_n_obj == 2),
+                                 n_obj=(lpips_n_obj(config.use_discriminator and base_n_obj == 2, self.lpips["lam"])
+                                        if self.lpips is not None else base_n_obj), max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  noise_mode=getattr(config, "noise_mode", 1),
                                  noise_seed=getattr(config, "noise_seed", 0), device=device, clip_resize=clip_resize,
                                  clip_normalize=clip_normalize, latent_space=self.latent_space,
@@ -366,7 +461,16 @@ class Generator:
                 self.engine.load_state({"dlatent_avg": self.model.dlatent_avg})     # the Generator's own buffer: no sub-model prefix
         self.engine.load_state(self.model.state)
         self.engine.load_state(clip_state)
+        if self.lpips is not None:
+            ok, msg = lpips_supported(self.engine.res, self.lpips["size"])
+            if not ok:
+                self.engine.close()
+                raise ValueError("lpips_size=%d: %s" % (self.lpips["size"], msg))
+            self.engine.load_state(load_lpips_state(self.lpips["weights"]))
         self.engine.finalize()
+        if self.lpips is not None:
+            self.lpips_target = prepare_lpips_target(self.lpips["target"], self.lpips["size"])
+            self.engine.set_lpips_target(self.lpips_target)
         if self.latent_space != DEFAULT_LATENT_SPACE:       # the row width of latent.StyleGAN2LatentSpace / operators follows the loaded network
             config.n_lat = self.engine.latent_row()[1]
         if getattr(config, "target_features", None) is not None:            # pre-computed text feature

@@ -599,6 +599,52 @@ def rn_tokens(x, pos, device=0):
 
 
 # ---- the small fp32 kernels around StyleGAN2 and the CLIP towers (glass_op_mapping ... glass_op_rn_token0_rows) ----
+# ---- perceptual objective (csrc/lpips.hip) ----
+def lpips_input(y, S, device=0):
+    """y [B,3,R,R] fp32 -> [B,S,S,4]: box mean to S, (v - shift_c) / scale_c, rounded to fp16; channel 3 = 0."""
+    lib = load_library()
+    y = _f32(y)
+    B, _, R, _ = y.shape
+    out = np.empty((B, S, S, 4), dtype=np.float32)
+    lib.glass_op_lpips_input.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_float)] * 2
+    _check(lib, lib.glass_op_lpips_input(device, B, R, S, _fp(y), _fp(out)))
+    return out
+
+
+def vgg_conv1(x, w, bias, device=0):
+    """x [B,S,S,4] (lpips_input's layout), w [64,3,3,3], bias [64] -> relu(conv3x3 pad 1 + bias) [B,S,S,64]."""
+    lib = load_library()
+    x, w, bias = _f32(x), _f32(w), _f32(bias)
+    B, S = x.shape[0], x.shape[1]
+    out = np.empty((B, S, S, 64), dtype=np.float32)
+    lib.glass_op_vgg_conv1.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_float)] * 4
+    _check(lib, lib.glass_op_vgg_conv1(device, B, S, _fp(x), _fp(w), _fp(bias), _fp(out)))
+    return out
+
+
+def maxpool2(x, device=0):
+    """MaxPool2d(2) of x [B,H,W,C] -> [B,H/2,W/2,C]."""
+    lib = load_library()
+    x = _f32(x)
+    B, H, W, Cc = x.shape
+    out = np.empty((B, H // 2, W // 2, Cc), dtype=np.float32)
+    lib.glass_op_maxpool2.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_float)] * 2
+    _check(lib, lib.glass_op_maxpool2(device, B, H, W, Cc, _fp(x), _fp(out)))
+    return out
+
+
+def lpips_head(x0, x1, lin, device=0):
+    """x0 [n,HW,C], x1 [n,HW,C] or [1,HW,C] (one map for all), lin [C] -> [n]: one slice's term of the distance."""
+    lib = load_library()
+    x0, x1, lin = _f32(x0), _f32(x1), _f32(lin)
+    n, HW, Cc = x0.shape
+    shared = int(x1.shape[0] == 1 and n > 1)
+    out = np.empty((n,), dtype=np.float32)
+    lib.glass_op_lpips_head.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_float)] * 4
+    _check(lib, lib.glass_op_lpips_head(device, n, HW, Cc, shared, _fp(x0), _fp(x1), _fp(lin), _fp(out)))
+    return out
+
+
 _FP, _IP = C.POINTER(C.c_float), C.POINTER(C.c_int32)
 MAP_FUSED, MAP_PIXELNORM, MAP_SPLITK, MAP_DENSE = 1, 2, 4, 8
 MAPPING_PATHS = {"auto": 0, "layers": 1, "fused": 2}

@@ -49,7 +49,7 @@ class GenerationProblem(Problem):
         process group if one is initialised with more than one rank (generator.py).  Every rank calls _evaluate with the SAME x;
         each scores its contiguous shard and one all-gather returns all rows (parallel.py)."""
         self.generator = Generator(config, dist=dist)
-        self.config = config
+        self.config = self.generator.config       # the caller's config, or the copy with one more objective (perceptual objective, lambda = 0)
         args = dict(self.config.problem_args)
         if getattr(self.generator, "latent_space", "z") != "z":
             args.update(dlatent_problem_args(config, self.generator))
@@ -74,7 +74,9 @@ class GenerationProblem(Problem):
             x = np.concatenate([x, np.repeat(x[-1:], pad, axis=0)])
         ls.set_from_population(x)
         F = self.generator.evaluate(ls)[:P]
-        if self.config.problem_args["n_obj"] == 2 and self.config.use_discriminator:
+        if getattr(self.generator, "lpips", None) is not None and self.config.problem_args["n_obj"] >= 2:
+            out["F"] = F                                # (-sim, [hinge], perceptual distance)
+        elif self.config.problem_args["n_obj"] == 2 and self.config.use_discriminator:
             out["F"] = F                                # column_stack((-sim, hinge)) (problem.py:25)
         else:
             out["F"] = F[:, 0]                          # -sim (problem.py:27)

@@ -15,7 +15,7 @@ import numpy as np
 
 from .config import get_config
 from .engine import LATENT_SPACES
-from .generator import CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, latent_options
+from .generator import CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, latent_options, lpips_options
 from .operators import get_operators
 from .problem import GenerationProblem
 from . import search
@@ -58,6 +58,14 @@ def build_parser():
                    help="StyleGAN2 configs: the truncation trick, dlatents pulled towards the average dlatent; in [0, 1], 1 (default) is off")
     p.add_argument("--truncation-cutoff", type=int, default=None,
                    help="StyleGAN2 configs: truncate only the style layers below this index (default: every layer)")
+    p.add_argument("--lpips-target", type=str, default=None,
+                   help="an image to stay close to: adds the LPIPS-VGG16 distance between each generated image and this one as a search "
+                        "objective (off by default — the reference's run.py has no such objective; this departs from it on purpose)")
+    p.add_argument("--lpips-size", type=int, default=None, help="side the images are area-downscaled to in front of VGG16 (default 256)")
+    p.add_argument("--lpips-lambda", type=float, default=None,
+                   help="0 (default): the distance is an objective of its own (NSGA-II); > 0: it is added to the similarity objective, times lambda")
+    p.add_argument("--lpips-weights", type=str, default=None,
+                   help="a torch file with torchvision's vgg16 features.N.{weight,bias} and LPIPS's lin.K.weight, or synthetic:<seed>")
     p.add_argument("--bpe-path", type=str, default=None)
     p.add_argument("--pop-size", type=int, default=None)
     p.add_argument("--stochastic", action="store_true", default=None,
@@ -70,17 +78,42 @@ def build_parser():
     return p
 
 
+def objective_names(config):
+    """Column names of F for this config: similarity, then discriminator (with D), then lpips (perceptual objective, lambda = 0)."""
+    n = int(config.problem_args["n_obj"])
+    lp_col = getattr(config, "lpips_target", None) is not None and not float(getattr(config, "lpips_lambda", None) or 0.0) > 0.0
+    names = ["similarity"] + (["discriminator"] if n - 1 - int(lp_col) >= 1 else []) + (["lpips"] if lp_col else [])
+    return names
+
+
+def scatter_pairs(names):
+    """(i, j, file name) of the Pareto scatters: F.jpg for two objectives (run.py:86-89), one F-<x>-<y>.jpg per pair for three."""
+    if len(names) == 2:
+        return [(0, 1, "F.jpg")]
+    return [(i, j, "F-%s-%s.jpg" % (names[i], names[j])) for i in range(len(names)) for j in range(i + 1, len(names))]
+
+
+def final_pick_weights(names):
+    """Pseudo-weights of the final pick among the Pareto set.  The reference takes (0, 1) on (similarity, discriminator): the most
+    realistic point (run.py:103-113).  With the perceptual distance as a third objective the weight is split evenly between realism and
+    closeness to the target, (0, .5, .5); without D it goes to the distance, (0, 1).  A default, not a result: the whole front is in
+    genetic_result."""
+    return [0.0, 0.5, 0.5] if len(names) == 3 else [0.0, 1.0]
+
+
 def main(argv=None, extra_config=None):
     config = build_parser().parse_args(argv)
     over = {k: v for k, v in vars(config).items() if v is not None}
     vars(config).update(get_config(config.config))                             # run.py:25
     for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "clip_views", "clip_view_min", "clip_view_flip",
-              "clip_view_fixed", "latent_space", "truncation_psi", "truncation_cutoff", "bpe_path", "pop_size", "stochastic"):
+              "clip_view_fixed", "latent_space", "truncation_psi", "truncation_cutoff", "lpips_target", "lpips_size", "lpips_lambda", "lpips_weights",
+              "bpe_path", "pop_size", "stochastic"):
         if k in over:
             setattr(config, k, over[k])
     if extra_config:
         vars(config).update(extra_config)
     latent_options(config)      # a latent space / truncation on a BigGAN or GPT2 config is refused here, before anything is loaded
+    lpips_options(config)       # ... and so is the perceptual objective on the GPT2 config
     state = dict(iteration=0)
     dist, rank0 = None, True
     if getattr(config, "dist", False):
@@ -110,6 +143,7 @@ def main(argv=None, extra_config=None):
             algorithm.problem.generator.save(generated, os.path.join(config.tmp_folder, name))
 
     problem = GenerationProblem(config, dist=dist)
+    config = problem.config     # (the perceptual objective with lambda = 0 searches one more objective: the Generator's copy says so)
     operators = get_operators(config)
     os.makedirs(config.tmp_folder, exist_ok=True)
     # (same seed on every rank => identical GA state everywhere: no broadcast of the population is needed)
@@ -119,17 +153,19 @@ def main(argv=None, extra_config=None):
         return res
     with open(os.path.join(config.tmp_folder, "genetic_result"), "wb") as f:   # run.py:79-84
         pickle.dump(dict(X=res.X, F=res.F, G=res.G, CV=res.CV), f)
-    if config.problem_args["n_obj"] == 2:
-        try:                                                                   # run.py:86-89
+    names = objective_names(config)
+    if len(names) >= 2:
+        try:                                                                   # run.py:86-89; three objectives: one scatter per pair
             import matplotlib
             matplotlib.use("Agg")
             import matplotlib.pyplot as plt
             Fp = np.atleast_2d(res.F)
-            plt.figure()
-            plt.scatter(Fp[:, 0], Fp[:, 1], color="red")
-            plt.xlabel("similarity"); plt.ylabel("discriminator")
-            plt.savefig(os.path.join(config.tmp_folder, "F.jpg"))
-            plt.close()
+            for i, j, fname in scatter_pairs(names):
+                plt.figure()
+                plt.scatter(Fp[:, i], Fp[:, j], color="red")
+                plt.xlabel(names[i]); plt.ylabel(names[j])
+                plt.savefig(os.path.join(config.tmp_folder, fname))
+                plt.close()
         except Exception as ex:   # plotting is cosmetic
             print("Warning: could not write F.jpg (%s)" % ex)
     if config.problem_args["n_obj"] == 1:
@@ -143,7 +179,7 @@ def main(argv=None, extra_config=None):
     if config.problem_args["n_obj"] == 1:
         X = np.atleast_2d(res.X)
     else:
-        X = np.atleast_2d(np.atleast_2d(res.X)[search.pseudo_weights_choice(np.atleast_2d(res.F), [0, 1])])  # run.py:103-113
+        X = np.atleast_2d(np.atleast_2d(res.X)[search.pseudo_weights_choice(np.atleast_2d(res.F), final_pick_weights(names))])  # run.py:103-113
     ls.set_from_population(X)
     generated = problem.generator.generate(ls)                                 # run.py:118
     ext = "txt" if config.task == "img2txt" else "jpg"                         # run.py:120-125

@@ -523,3 +523,29 @@ def write_bpe_assets(out_dir, gpt2_vocab=50257, clip_vocab=49408, seed=0, init_t
     with gzip.open(cb, "wt", encoding="utf-8") as f:
         f.write("#version: synthetic\n" + "\n".join(a + " " + b for a, b in c_merges) + "\n")
     return ej, vb, cb
+
+
+# --------------------------------------------------------------------------
+# Perceptual objective: LPIPS on VGG16 (stylegan2/external_models/lpips.py:34-78).
+# The layer list is the public VGG16 configuration D under torchvision's `features`
+# indices (own restatement: torchvision is not a dependency).
+# --------------------------------------------------------------------------
+VGG16_CONVS = [(0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256),
+               (17, 256, 512), (19, 512, 512), (21, 512, 512), (24, 512, 512), (26, 512, 512), (28, 512, 512)]   # (features index, cin, cout)
+LPIPS_SLICE_CHANNELS = [64, 128, 256, 512, 512]
+
+
+def lpips_state(seed=0):
+    """Synthetic weights of the perceptual objective under the keys the engine loads ("lpips.features.N.{weight,bias}" as torchvision's
+    vgg16 names them, "lpips.lin.K.weight" [C_K]).  Convolutions are He-scaled (std sqrt(2 / fan_in), the scale that keeps a ReLU
+    network's activation variance from layer to layer), biases N(0, 0.05): through 13 layers the activations stay orders of magnitude
+    below fp16's 65504.  The lin weights are uniform in [0, 1) / C: non-negative, as the released ones are."""
+    sd = OrderedDict()
+    for idx, cin, cout in VGG16_CONVS:
+        k = "lpips.features.%d" % idx
+        sd[k + ".weight"] = normal(seed, k + ".weight", (cout, cin, 3, 3), std=float(np.sqrt(2.0 / (cin * 9))))
+        sd[k + ".bias"] = normal(seed, k + ".bias", (cout,), std=0.05)
+    for i, c in enumerate(LPIPS_SLICE_CHANNELS):
+        k = "lpips.lin.%d.weight" % i
+        sd[k] = (_rng(seed, k).random((c,), dtype=np.float32) / np.float32(c)).astype(np.float32)
+    return sd

@@ -84,6 +84,11 @@ typedef struct glass_config {
      * pool's token count, as it is for a ViT), clip_res and clip_embed as before.  See glass_clip_resnet_supported. */
     int32_t clip_arch;            /* 0: VisualTransformer (default); 1: ModifiedResNet */
     int32_t clip_rn_layers[4];    /* bottlenecks per stage: (3, 4, 6, 3) RN50, (3, 4, 23, 3) RN101 */
+    /* --- opt-in: perceptual distance to a target image (LPIPS on VGG16, stylegan2/external_models/lpips.py:34-78, fed as the reference's
+     * projector feeds it, stylegan2/project.py:113-122,263).  Appended last: zero selects today's pass.  See glass_lpips_supported and
+     * glass_engine_set_lpips_target.  With lpips_size > 0, n_obj must be 1 + use_discriminator + (lpips_lambda == 0). */
+    int32_t lpips_size;           /* 0: off (default); S: the generated image is area-downscaled to S x S in front of VGG16 */
+    float lpips_lambda;           /* 0: the distance d is its own LAST column, F = [-sim, (hinge), d]; > 0: no column, F[:,0] = fmaf(lambda, d, -sim) */
 } glass_config;
 
 /* Caller-provided noise (noise_mode 2): planes[m * n_layers + l] points at a host
@@ -136,7 +141,29 @@ int glass_clip_views_supported(int32_t max_pop, int32_t tokens, int32_t width, i
 int glass_host_clip_view_boxes(uint64_t seed, int32_t generation, int32_t views, int32_t gen_res, int32_t min_permille, int32_t flip,
                                int32_t fixed, int32_t* boxes /*[views][4]*/);
 
+/* Perceptual objective (opt-in, glass_config::lpips_size > 0; departs from what the reference's run.py calls — it never wires its LPIPS in):
+ * d[p] = LPIPS_VGG16(pixel_min=-1, pixel_max=1).forward(area(y_p), t).  y_p: the raw generator output [3][R][R], nominally in [-1, 1], before
+ * biggan_norm and unclamped; area(): the (R / S) x (R / S) box mean; t: the target [3][S][S] in [-1, 1].  forward: (v - shift_c) / scale_c,
+ * the five VGG16 slices features[0:4], [4:9], [9:16], [16:23], [23:30], each followed by x rsqrt(sum_c x^2 + 1e-8), the squared difference
+ * averaged over H x W and weighted per channel by the slice's lin vector, the five terms summed.  Activations are fp16, sums fp32 in a fixed
+ * order: a candidate's d does not depend on its row, the chunk or the shard.
+ * Tensors (glass_engine_load_tensor; finalize names a missing one, GLASS_ERR_STATE): "lpips.features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.
+ * {weight,bias}" (torchvision's vgg16 keys) and "lpips.lin.{0..4}.weight" [C_k].
+ *
+ * glass_lpips_supported: the one rule (host only: callable without a GPU), applied by create too.  lpips_size a multiple of 16 in [16, 512]
+ * (four max pools need even sides); gen_res % lpips_size == 0 with a box of at most 8; gen_res 0 checks lpips_size alone.  Returns GLASS_OK,
+ * or GLASS_ERR_ARG with the reason in glass_last_error().  An engine without a generator (GPT-2) refuses lpips_size > 0. */
+int glass_lpips_supported(int32_t gen_res, int32_t lpips_size);
+
 int glass_engine_create(const glass_config* cfg, glass_engine** out);
+/* The target image of the perceptual objective: img host float32 [3][S][S] in [-1, 1], S = lpips_size.  After finalize; runs VGG16 on it once
+ * and keeps its five activation maps.  evaluate() fails (GLASS_ERR_STATE, "set_lpips_target() first") while none is set. */
+int glass_engine_set_lpips_target(glass_engine* e, const float* img, int32_t S);
+/* The reference's forward(x0, x1) on caller images, host float32 [n][3][S][S] each, through the kernels of the pass (box 1, no stored target):
+ * out [n].  A utility, and the parity entry point. */
+int glass_engine_lpips(glass_engine* e, const float* x0, const float* x1, int32_t n, float* out);
+/* The distances d [P] of the last evaluate() (whether they are a column of F or folded into column 0). */
+int glass_engine_last_lpips(glass_engine* e, int32_t P, float* d);
 /* Turn crop views on (views >= 1; 1 = the whole image alone) or off (0) — between create and finalize, which sizes the CLIP-side buffers for
  * max_pop * views images: GLASS_ERR_STATE after finalize, and for an engine without a generator.  seed of the boxes: glass_config::noise_seed. */
 int glass_engine_set_clip_views(glass_engine* e, int32_t views, int32_t min_permille, int32_t flip, int32_t fixed);
@@ -226,7 +253,8 @@ int glass_engine_gpt2_sample(glass_engine* e, const int32_t* context, int32_t P,
  * generation: index folded into the device noise stream (noise_mode 1);
  * first_minibatch: global index of this call's first minibatch (population shards);
  * noise: nullable, used when noise_mode == 2;
- * out_F: host float32 [P, n_obj]: F[:,0] = -cosine, F[:,1] = relu(1 - D) (problem.py:23-27).
+ * out_F: host float32 [P, n_obj]: F[:,0] = -cosine, F[:,1] = relu(1 - D) (problem.py:23-27); with the perceptual objective and
+ *   lpips_lambda == 0 the distance is one more, last, column (n_obj up to 3).
  * P must be a multiple of batch_size (reference asserts: models.py:112). */
 int glass_engine_evaluate(glass_engine* e, const float* latents, int32_t P, int32_t generation,
                           int32_t first_minibatch, const glass_noise* noise, float* out_F);

@@ -247,6 +247,18 @@ int glass_op_cosine_views(int32_t device, int32_t P, int32_t V, int32_t D, const
 int glass_op_assemble_F(int32_t device, int32_t P, int32_t n_obj, const float* sim, const float* dis, float* F);
 int glass_op_image_patches(int32_t device, int32_t n, int32_t S, int32_t ps, int32_t ld, const float* img, float sentinel, float* patches);
 int glass_op_rn_token0_rows(int32_t device, int32_t B, int32_t T, int32_t C, const float* att, float* out);
+/* The perceptual objective's own kernels (lpips.hip), each through the launcher the walker (lpips.cpp) calls; a shape the launcher does not
+ * take is refused by name (GLASS_ERR_ARG).
+ * glass_op_lpips_input: y [B,3,R,R] fp32 -> box mean to S (R % S == 0, box <= 8), (v - shift_c) / scale_c -> out [B,S,S,4] (fp16 values; channel 3 = 0).
+ * glass_op_vgg_conv1: x [B,S,S,4] (that layout), w [64,3,3,3], bias [64] -> relu(conv3x3 pad 1 + bias) [B,S,S,64].
+ * glass_op_maxpool2: MaxPool2d(2) of x [B,H,W,C] -> [B,H/2,W/2,C].
+ * glass_op_lpips_head: x0 [n,HW,C], x1 [n,HW,C] (shared_x1 = 0) or [1,HW,C] (1: one map for all), lin [C] -> out[i] = sum_c lin_c
+ *   mean_hw (x0 / |x0| - x1 / |x1|)^2, one slice's term. */
+int glass_op_lpips_input(int32_t device, int32_t B, int32_t R, int32_t S, const float* y, float* out);
+int glass_op_vgg_conv1(int32_t device, int32_t B, int32_t S, const float* x, const float* w, const float* bias, float* out);
+int glass_op_maxpool2(int32_t device, int32_t B, int32_t H, int32_t W, int32_t C, const float* x, float* out);
+int glass_op_lpips_head(int32_t device, int32_t n, int32_t HW, int32_t C, int32_t shared_x1, const float* x0, const float* x1, const float* lin,
+                        float* out);
 /* raw MFMA layout probe: D = A[32x16] * B[16x32] through the fragment mapping of common.h */
 int glass_op_mfma_probe(int32_t device, const float* a /*[32,16]*/, const float* b /*[16,32]*/, float* d /*[32,32]*/);
 
