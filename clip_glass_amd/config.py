@@ -13,7 +13,12 @@ refused for the BigGAN and GPT2 configs;
 `lpips_target` (unset, the default: off; a path or an array [3, H, W] in [0, 1]: the LPIPS-VGG16 distance to that image becomes a search
 objective, include/glass.h), with `lpips_size` (256), `lpips_lambda` (0: an objective of its own — the Generator then searches a copy of the
 config with `n_obj` one higher and `algorithm` "nsga2", this table is not touched; > 0: added to the similarity objective) and
-`lpips_weights` (a torch file or "synthetic:<seed>") — the StyleGAN2 and BigGAN configs; refused for GPT2."""
+`lpips_weights` (a torch file or "synthetic:<seed>") — the StyleGAN2 and BigGAN configs; refused for GPT2;
+`prompts` (unset, the default: the one `target`; a list of (value, weight) pairs — value a text, ("image", path_or_array) or a ready feature
+[clip_embed]; a negative weight steers away from the prompt, include/glass.h "Prompt sets"), with `target_weight` (1: the weight of `target`,
+which is always the set's first entry) and `prompt_mode` ("sum", the default: the entries blend into the one similarity objective,
+sum_t w_t sim_t / sum_t |w_t|; "pareto": one objective per entry, 2 to 4 — the Generator then searches a copy of the config with `n_obj` =
+entries + discriminator + LPIPS column and `algorithm` "nsga2") — the StyleGAN2 and BigGAN configs; refused for GPT2."""
 from .latent import DeepMindBigGANLatentSpace, GPT2LatentSpace, StyleGAN2LatentSpace
 from .models import GPT2, DeepMindBigGAN, StyleGAN2
 from .utils import biggan_denorm, biggan_norm

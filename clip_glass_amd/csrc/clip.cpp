@@ -495,7 +495,13 @@ static void run_rn_blocks(glass_engine* e, int P, int l0, int l1) {
 }
 static void clip_cosine(glass_engine* e, int P, int views) {      // the end of both towers' heads: d_feat [P][embed] against the target
     const int E = e->cfg.clip_embed;
-    if (views > 0) launch_cosine_views(e->d_feat, e->d_target, P / views, views, E, e->d_view_sim, e->d_sim, e->cur);
+    const glass_engine::PromptSet& ps = e->pset;
+    if (ps.T > 0) {           // a prompt set: every row against every entry, still one launch
+        const int V = std::max(views, 1);
+        if (!launch_cosine_set(e->d_feat, ps.d_targets, ps.d_weights, ps.W, P / V, V, ps.T, E, views > 0 ? e->d_view_sim : nullptr, ps.d_sim, e->d_sim, e->cur) &&
+            e->launch_error.empty())
+            e->launch_error = "no kernel accepts layer clip.head (cosine_set: shape outside its limits)";
+    } else if (views > 0) launch_cosine_views(e->d_feat, e->d_target, P / views, views, E, e->d_view_sim, e->d_sim, e->cur);
     else launch_cosine(e->d_feat, e->d_target, P, E, e->d_sim, e->cur);
 }
 static void run_rn_head(glass_engine* e, int P, int views) {
@@ -657,6 +663,49 @@ extern "C" int glass_engine_encode_image(glass_engine* e, const float* images, i
     e->event_next = 0;
     if (err != hipSuccess) {
         glass_set_error(std::string("encode_image failed: ") + hipGetErrorString(err));
+        return GLASS_ERR_HIP;
+    }
+    if (!e->launch_error.empty()) {      // a launcher of the tower refused a layer
+        const std::string msg = e->launch_error;
+        e->launch_error.clear();
+        glass_set_error(msg);
+        return GLASS_ERR_STATE;
+    }
+    return GLASS_OK;
+}
+
+// The feature a generated image with these pixels gets in the pass: the pass's own preprocessing (run_clip_resize's branches without views, so
+// the whole image) and the tower.  What makes an image a prompt (glass_engine_set_targets) that is comparable with the candidates.
+extern "C" int glass_engine_encode_generated(glass_engine* e, const float* images, int32_t n, float* out_feat) {
+    REQUIRE(e && images && out_feat && n > 0, GLASS_ERR_ARG, "null argument");
+    REQUIRE(e->R > 0, GLASS_ERR_STATE, "encode_generated: this engine has no generator (GPT-2 / img2txt): there is no generated-image preprocessing to apply");
+    REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
+    REQUIRE(n <= e->cfg.max_pop, GLASS_ERR_ARG, "more images than max_pop");
+    const glass_config& c = e->cfg;
+    GLASS_HIP(hipSetDevice(c.device));
+    const int G = c.clip_res / c.clip_patch;
+    const size_t img_elems = (size_t)3 * e->R * e->R, img_patches = (size_t)G * G * clip_patch_k(c);
+    const int views = e->views;
+    const bool prof = e->profiling;
+    e->views = 0;             // the whole image through the non-view preprocessing
+    e->profiling = false;     // (profile rows belong to a pass)
+    e->cur = e->stream;
+    e->launch_error.clear();
+    hipError_t err = hipSuccess;
+    for (int c0 = 0; c0 < n && err == hipSuccess; c0 += e->chunk) {
+        const int B = std::min(e->chunk, n - c0);
+        err = hipMemcpyAsync(e->ybuf[0], images + (size_t)c0 * img_elems, (size_t)B * img_elems * sizeof(float), hipMemcpyHostToDevice, e->stream);
+        run_clip_resize(e, e->ybuf[0], B, e->d_patches + (size_t)c0 * img_patches);
+    }
+    run_clip(e, n);
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(out_feat, e->d_feat, (size_t)n * c.clip_embed * sizeof(float), hipMemcpyDeviceToHost, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    if (err == hipSuccess) err = hipGetLastError();
+    e->views = views;
+    e->profiling = prof;
+    if (err != hipSuccess) {
+        glass_set_error(std::string("encode_generated failed: ") + hipGetErrorString(err));
         return GLASS_ERR_HIP;
     }
     if (!e->launch_error.empty()) {      // a launcher of the tower refused a layer

@@ -105,14 +105,24 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     REQUIRE(cfg->batch_size > 0 && cfg->max_pop > 0, GLASS_ERR_ARG, "batch_size/max_pop must be positive");
     REQUIRE(cfg->max_pop % cfg->batch_size == 0, GLASS_ERR_ARG, "max_pop must be a multiple of batch_size");
     const bool lpips = cfg->lpips_size != 0;      // the perceptual objective (opt-in): its own last column unless lpips_lambda folds it into column 0
+    REQUIRE(cfg->sim_columns >= 0 && cfg->sim_columns <= 4, GLASS_ERR_ARG, "sim_columns must be 0 or 1 (one similarity column) or 2 .. 4 (a pareto prompt set)");
+    const int K = sim_columns(*cfg);              // similarity columns: 1 unless the engine is made for a pareto prompt set
+    if (K >= 2) {
+        REQUIRE(!lpips || cfg->lpips_lambda == 0.f, GLASS_ERR_ARG,
+                "lpips_lambda > 0 folds the distance into THE similarity column; with sim_columns >= 2 there is no single one: use lpips_lambda = 0 (its own column)");
+        const int want = K + (cfg->use_discriminator ? 1 : 0) + (lpips ? 1 : 0);
+        REQUIRE(cfg->n_obj == want, GLASS_ERR_ARG,
+                "with sim_columns >= 2, n_obj must be sim_columns + use_discriminator + (lpips_size > 0 && lpips_lambda == 0) = " + std::to_string(want) +
+                    ", got " + std::to_string(cfg->n_obj));
+    }
     if (!lpips) {
-        REQUIRE(cfg->n_obj == 1 || cfg->n_obj == 2, GLASS_ERR_ARG, "n_obj must be 1 or 2");
+        REQUIRE(K >= 2 || cfg->n_obj == 1 || cfg->n_obj == 2, GLASS_ERR_ARG, "n_obj must be 1 or 2");
     } else {
         REQUIRE(cfg->n_blocks > 0 || cfg->generator == GLASS_GEN_BIGGAN_DEEP, GLASS_ERR_ARG,
                 "lpips_size > 0 needs a generator: this engine has none (GPT-2 / img2txt), so there is no generated image to compare");
         if (int lrc = glass_lpips_supported(0, cfg->lpips_size)) return lrc;
         REQUIRE(std::isfinite(cfg->lpips_lambda) && cfg->lpips_lambda >= 0.f, GLASS_ERR_ARG, "lpips_lambda must be finite and >= 0");
-        const int want = 1 + (cfg->use_discriminator ? 1 : 0) + (cfg->lpips_lambda == 0.f ? 1 : 0);
+        const int want = K + (cfg->use_discriminator ? 1 : 0) + (cfg->lpips_lambda == 0.f ? 1 : 0);
         REQUIRE(cfg->n_obj == want, GLASS_ERR_ARG,
                 "with lpips_size > 0, n_obj must be 1 + use_discriminator + (lpips_lambda == 0) = " + std::to_string(want) + ", got " +
                     std::to_string(cfg->n_obj));
@@ -135,7 +145,7 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     REQUIRE(cfg->noise_mode >= 0 && cfg->noise_mode <= 2, GLASS_ERR_ARG, "noise_mode must be 0,1,2");
     int bg_res = 0;
     if (cfg->generator == GLASS_GEN_BIGGAN_DEEP) {
-        REQUIRE(cfg->n_blocks == 0 && !cfg->use_discriminator && (lpips || cfg->n_obj == 1), GLASS_ERR_ARG,
+        REQUIRE(cfg->n_blocks == 0 && !cfg->use_discriminator && (lpips || K >= 2 || cfg->n_obj == 1), GLASS_ERR_ARG,
                 "BigGAN-deep: n_blocks must be 0, no discriminator, n_obj 1 (config.py:31-74)");
         REQUIRE(cfg->bg_n_layers > 0 && cfg->bg_n_layers <= GLASS_MAX_BG_LAYERS, GLASS_ERR_ARG, "bg_n_layers out of range");
         REQUIRE(cfg->bg_ch > 0 && cfg->bg_ch % 32 == 0 && cfg->bg_z_dim > 0 && cfg->bg_z_dim % 4 == 0 && cfg->bg_num_classes > 0,
@@ -355,7 +365,7 @@ static int alloc_buffers(glass_engine* e) {
     if (e->views && (rc = dev_alloc(e, &e->d_view_sim, PI))) return rc;
     if ((rc = dev_alloc(e, &e->d_sim, (size_t)P))) return rc;
     if ((rc = dev_alloc(e, &e->d_dis, (size_t)P))) return rc;
-    if ((rc = dev_alloc(e, &e->d_F, (size_t)P * (c.lpips_size ? 3 : 2)))) return rc;
+    if ((rc = dev_alloc(e, &e->d_F, (size_t)P * std::max(c.lpips_size ? 3 : 2, c.n_obj)))) return rc;
     if ((rc = dev_alloc(e, &e->d_target, (size_t)c.clip_embed))) return rc;
     if (c.use_discriminator && c.n_blocks > 0) {
         if ((rc = dev_alloc(e, &e->d_dfin, (size_t)P * 16 * c.channels[0]))) return rc;
@@ -406,8 +416,65 @@ extern "C" int glass_engine_set_target(glass_engine* e, const float* feat, int32
     REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
     REQUIRE(n == e->cfg.clip_embed, GLASS_ERR_ARG, "target feature length != clip_embed");
     GLASS_HIP(hipSetDevice(e->cfg.device));
+    REQUIRE(sim_columns(e->cfg) < 2, GLASS_ERR_STATE,
+            "set_target: this engine has sim_columns >= 2 (one column per prompt): give it a prompt set with set_targets()");
     GLASS_HIP(hipMemcpy(e->d_target, feat, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     e->has_target = true;
+    e->pset.T = 0;      // one target again: the head ends in cosine_kernel / cosine_views_kernel
+    return GLASS_OK;
+}
+
+// ---- prompt sets --------------------------------------------------------------------------------
+extern "C" int glass_prompt_set_supported(int32_t n_entries, int32_t mode, int32_t sim_columns) {
+    REQUIRE(n_entries >= 1 && n_entries <= GLASS_PROMPT_MAX, GLASS_ERR_ARG,
+            "a prompt set holds 1 .. " + std::to_string(GLASS_PROMPT_MAX) + " entries, got " + std::to_string(n_entries));
+    REQUIRE(mode == 0 || mode == 1, GLASS_ERR_ARG, "prompt set mode must be 0 (sum) or 1 (pareto)");
+    REQUIRE(sim_columns >= 0 && sim_columns <= 4, GLASS_ERR_ARG, "sim_columns must be in [0, 4]");
+    if (mode == 0) {
+        REQUIRE(sim_columns <= 1, GLASS_ERR_ARG,
+                "mode sum blends the set into one similarity column, and this engine has sim_columns = " + std::to_string(sim_columns) +
+                    ": use mode pareto, or an engine with sim_columns 0");
+    } else {
+        REQUIRE(n_entries >= 2 && n_entries <= 4, GLASS_ERR_ARG,
+                "mode pareto gives every entry its own column of F: 2 .. 4 entries, got " + std::to_string(n_entries));
+        REQUIRE(n_entries == sim_columns, GLASS_ERR_ARG,
+                "mode pareto needs an engine created with sim_columns = the number of entries (" + std::to_string(n_entries) + "), this one has " +
+                    std::to_string(sim_columns));
+    }
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_targets(glass_engine* e, const float* feats, const float* weights, int32_t T, int32_t E, int32_t mode) {
+    REQUIRE(e && feats && weights, GLASS_ERR_ARG, "null argument");
+    REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first");
+    REQUIRE(E == e->cfg.clip_embed, GLASS_ERR_ARG, "set_targets: feature length != clip_embed");
+    if (int rc = glass_prompt_set_supported(T, mode, e->cfg.sim_columns)) return rc;
+    for (int t = 0; t < T; ++t)
+        REQUIRE(std::isfinite(weights[t]) && weights[t] != 0.f, GLASS_ERR_ARG,
+                "set_targets: weight " + std::to_string(t) + " must be finite and non-zero (negative: away from the prompt)");
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    glass_engine::PromptSet& ps = e->pset;
+    if (!ps.d_targets) {      // the first set of this engine
+        int rc;
+        if ((rc = dev_alloc(e, &ps.d_sim, (size_t)e->cfg.max_pop * GLASS_PROMPT_MAX))) return rc;
+        if ((rc = dev_alloc(e, &ps.d_weights, (size_t)GLASS_PROMPT_MAX))) return rc;
+        if ((rc = dev_alloc(e, &ps.d_targets, (size_t)GLASS_PROMPT_MAX * E))) return rc;
+    }
+    GLASS_HIP(hipMemcpy(ps.d_targets, feats, (size_t)T * E * sizeof(float), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemcpy(ps.d_weights, weights, (size_t)T * sizeof(float), hipMemcpyHostToDevice));
+    ps.W = prompt_weight_sum(weights, T);
+    ps.T = T;
+    ps.mode = mode;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_last_set_details(glass_engine* e, int32_t P, float* set_sim) {
+    REQUIRE(e && e->finalized, GLASS_ERR_STATE, "engine not ready");
+    REQUIRE(set_sim, GLASS_ERR_ARG, "null argument");
+    REQUIRE(e->pset.T > 0, GLASS_ERR_STATE, "no prompt set is active (glass_engine_set_targets)");
+    REQUIRE(P > 0 && P <= e->last_P, GLASS_ERR_ARG, "P exceeds the last evaluated population");
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    GLASS_HIP(hipMemcpy(set_sim, e->pset.d_sim, (size_t)P * e->pset.T * sizeof(float), hipMemcpyDeviceToHost));
     return GLASS_OK;
 }
 
@@ -522,7 +589,10 @@ static int finish_pass(glass_engine* e, int P, float* out_F, bool clip_done, hip
             GLASS_HIP(hipEventRecord(e->ev_g[0], d_join));
             GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_g[0], 0));
         }
-        if (c.lpips_size) launch_assemble_F_lpips(e->d_sim, e->d_dis, e->lp.d, c.lpips_lambda, c.use_discriminator ? 1 : 0, P, c.n_obj, e->d_F, e->cur);
+        if (e->pset.T > 0 && e->pset.mode == 1)
+            launch_assemble_F_set(e->pset.d_sim, e->pset.d_weights, c.use_discriminator ? e->d_dis : nullptr, c.lpips_size ? e->lp.d : nullptr, e->pset.T, P,
+                                  e->d_F, e->cur);
+        else if (c.lpips_size) launch_assemble_F_lpips(e->d_sim, e->d_dis, e->lp.d, c.lpips_lambda, c.use_discriminator ? 1 : 0, P, c.n_obj, e->d_F, e->cur);
         else launch_assemble_F(e->d_sim, e->d_dis, P, c.n_obj, e->d_F, e->cur);
         GLASS_HIP(hipMemcpyAsync(e->h_pinned, e->d_F, (size_t)P * c.n_obj * sizeof(float), hipMemcpyDeviceToHost,
                                  e->cur));
@@ -554,7 +624,8 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
             "population size must be a multiple of batch_size (reference asserts: models.py:112)");
     const bool biggan = c.generator == GLASS_GEN_BIGGAN_DEEP;
     REQUIRE(e->cfg.n_blocks > 0 || biggan, GLASS_ERR_STATE, "this engine was created without a GAN (n_blocks = 0)");
-    if (out_F) REQUIRE(e->has_target, GLASS_ERR_STATE, "set_target() first");
+    if (out_F && sim_columns(c) >= 2) REQUIRE(e->pset.T > 0, GLASS_ERR_STATE, "set_targets() first (this engine has sim_columns >= 2: one column of F per prompt)");
+    else if (out_F) REQUIRE(e->has_target || e->pset.T > 0, GLASS_ERR_STATE, "set_target() first");
     const bool lpips = out_F && c.lpips_size > 0;
     if (lpips) REQUIRE(e->lp.has_target, GLASS_ERR_STATE, "set_lpips_target() first");
     GLASS_HIP(hipSetDevice(c.device));
@@ -617,7 +688,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
         rc = upload_noise(e, P, generation, first_mb, noise);
         if (rc) return rc;
     }
-    const bool want_d = out_F && c.use_discriminator && (c.lpips_size > 0 || c.n_obj == 2);      // (with the perceptual objective n_obj counts its column too)
+    const bool want_d = out_F && c.use_discriminator && (c.lpips_size > 0 || sim_columns(c) >= 2 || c.n_obj == 2);      // (with the perceptual objective n_obj counts its column too)
     const int n = c.n_blocks;
     const int nlow = std::min(n, e->n_low);           // G blocks 0..nlow-1 run for the whole population
     const int nd = (int)e->dblk.size();               // D conv blocks (n - 1)

@@ -273,6 +273,13 @@ struct glass_engine {
     std::vector<glass_prof_row> prof_rows;
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
+    // ---- prompt set (glass_engine_set_targets; T 0: none — the head ends in cosine_kernel / cosine_views_kernel against d_target).  The
+    // three buffers are allocated by the first set_targets call: an engine that never calls it holds nothing of this ----
+    struct PromptSet {
+        int T = 0, mode = 0;                // entries; 0 sum, 1 pareto
+        float W = 0.f;                      // sum |w_t|
+        float *d_targets = nullptr, *d_weights = nullptr, *d_sim = nullptr;    // [16][clip_embed], [16], [max_pop][16] (rows of T in use)
+    } pset;
 };
 
 // ------------------------------------------------------------------------------------
@@ -429,6 +436,7 @@ void run_clip(glass_engine* e, int P, int views = 0);
 // images the tower's buffers hold: max_pop, times the views when they are on
 inline size_t clip_max_images(const glass_engine* e) { return (size_t)e->cfg.max_pop * (size_t)std::max(e->views, 1); }
 inline int pass_images(const glass_engine* e, int P) { return P * std::max(e->views, 1); }      // images of a pass over P candidates
+inline int sim_columns(const glass_config& c) { return std::max(c.sim_columns, 1); }      // similarity columns of F (0 and 1: the one of today)
 int clip_n_layers(const glass_engine* e);     // what run_clip_layers counts: transformer blocks (ViT) or bottlenecks (ResNet)
 int alloc_clip_resnet(glass_engine* e);       // the ResNet tower's activation buffers (clip_arch 1)
 // The ResNet tower's GEMMs as the walker sets them up (shared with the diagnostic ops).  1 x 1 conv + BN (+ res) (+ ReLU) over M rows: fewer than

@@ -166,6 +166,16 @@ void launch_assemble_F(const float* sim, const float* dis, int P, int n_obj, flo
 // the same rows with the perceptual distance lp [P]: lambda == 0: its own LAST column; lambda > 0: F[:, 0] = fmaf(lambda, lp, -sim), no column.
 // has_d: column 1 is the discriminator hinge
 void launch_assemble_F_lpips(const float* sim, const float* dis, const float* lp, float lambda, int has_d, int P, int n_obj, float* F, hipStream_t st);
+// --- prompt sets (prompt_set.hip; include/glass.h "Prompt sets") ---
+#define GLASS_PROMPT_MAX 16         // entries of a set
+#define GLASS_PROMPT_MAX_VIEWS 16   // glass_clip_views_supported's limit
+// feat [P][V][D] (V = 1: no views), targets [T][D], weights [T], W = prompt_weight_sum -> view_sim [P][V] (nullable: entry 0's per-view cosines),
+// set_sim [P][T] (the ordered means), sim [P] (the combination of mode `sum`).  One launch; false: a shape outside the limits, nothing launched
+bool launch_cosine_set(const float* feat, const float* targets, const float* weights, float W, int P, int V, int T, int D, float* view_sim,
+                       float* set_sim, float* sim, hipStream_t st);
+float prompt_weight_sum(const float* weights, int T);      // sum |w_t| in fp32, t = 0 .. T - 1 (host)
+// F [P][K + (dis != 0) + (lp != 0)]: F[p][t] = w_t < 0 ? set_sim[p][t] : -set_sim[p][t], then relu(1 - dis), then lp (nullable each)
+void launch_assemble_F_set(const float* set_sim, const float* weights, const float* dis, const float* lp, int K, int P, float* F, hipStream_t st);
 
 // --- perceptual objective: LPIPS on VGG16 (lpips.hip); the 3 x 3 convolutions behind the first are gemm_tiled (mode 5, A = 1, S = bias) ---
 #define GLASS_LPIPS_PIXB 256      // pixels of one image a workgroup of the head owns

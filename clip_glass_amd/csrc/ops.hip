@@ -1203,6 +1203,48 @@ extern "C" int glass_op_assemble_F(int32_t device, int32_t P, int32_t n_obj, con
     return GLASS_OK;
 }
 
+extern "C" int glass_op_cosine_set(int32_t device, int32_t P, int32_t V, int32_t T, int32_t D, const float* feat, const float* targets,
+                                   const float* weights, float* view_sim, float* set_sim, float* sim) {
+    OPREQ(feat && targets && weights && view_sim && set_sim && sim && P > 0 && D > 0, "bad argument");
+    OPREQ(V >= 1 && V <= GLASS_PROMPT_MAX_VIEWS && T >= 1 && T <= GLASS_PROMPT_MAX, "cosine_set: V and T must be in [1, 16]");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* df = dv.up32(feat, (size_t)P * V * D); float* dt = dv.up32(targets, (size_t)T * D); float* dw = dv.up32(weights, T);
+    float* dvs = dv.alloc<float>((size_t)P * V); float* dss = dv.alloc<float>((size_t)P * T); float* ds = dv.alloc<float>(P);
+    OPREQ(df && dt && dw && dvs && dss && ds, "device allocation failed");
+    GLASS_HIP(hipMemset(dvs, 0xFF, (size_t)P * V * sizeof(float)));
+    GLASS_HIP(hipMemset(dss, 0xFF, (size_t)P * T * sizeof(float)));
+    GLASS_HIP(hipMemset(ds, 0xFF, (size_t)P * sizeof(float)));
+    OPREQ(launch_cosine_set(df, dt, dw, prompt_weight_sum(weights, T), P, V, T, D, dvs, dss, ds, 0), "cosine_set refused the shape");
+    int rc = finish();
+    if (rc) return rc;
+    GLASS_HIP(hipMemcpy(view_sim, dvs, (size_t)P * V * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(set_sim, dss, (size_t)P * T * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(sim, ds, (size_t)P * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_assemble_F_set(int32_t device, int32_t P, int32_t K, const float* set_sim, const float* weights, const float* dis,
+                                       const float* lp, float* F) {
+    OPREQ(set_sim && weights && F && P > 0 && K >= 1 && K <= GLASS_PROMPT_MAX, "bad argument (K in [1, 16])");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const int n_obj = K + (dis ? 1 : 0) + (lp ? 1 : 0);
+    const size_t n = (size_t)P * n_obj;
+    float* dss = dv.up32(set_sim, (size_t)P * K); float* dw = dv.up32(weights, K); float* dd = dv.up32(dis, P); float* dl = dv.up32(lp, P);
+    float* dF = dv.alloc<float>(n + 4);      // four guard elements behind the output
+    OPREQ(dss && dw && dF && (!dis || dd) && (!lp || dl), "device allocation failed");
+    GLASS_HIP(hipMemset(dF, 0xFF, (n + 4) * sizeof(float)));
+    launch_assemble_F_set(dss, dw, dd, dl, K, P, dF, 0);
+    int rc = finish();
+    if (rc) return rc;
+    uint32_t guard[4];
+    GLASS_HIP(hipMemcpy(guard, dF + n, sizeof guard, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) OPREQ(guard[i] == 0xFFFFFFFFu, "assemble_F_set stored past row P");
+    GLASS_HIP(hipMemcpy(F, dF, n * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
 extern "C" int glass_op_image_patches(int32_t device, int32_t n, int32_t S, int32_t ps, int32_t ld, const float* img, float sentinel,
                                       float* patches) {
     OPREQ(img && patches && n > 0 && S > 0 && ps > 0 && S % ps == 0 && ld >= 3 * ps * ps, "bad argument (S % ps == 0, ld >= 3 ps ps)");

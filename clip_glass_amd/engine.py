@@ -44,6 +44,16 @@ class GlassConfigLpips(C.Structure):
     _fields_ = GlassConfigResnet._fields_ + [("lpips_size", C.c_int32), ("lpips_lambda", C.c_float)]
 
 
+class GlassConfigPrompt(C.Structure):
+    """glass_config as the library defines it now: GlassConfigLpips's fields, then the prompt sets' column count, appended as the others
+    were (zero: one similarity column).  The shorter structs stay what libraries built before each addition read."""
+    _fields_ = GlassConfigLpips._fields_ + [("sim_columns", C.c_int32)]
+
+
+PROMPT_MODES = {"sum": 0, "pareto": 1}      # include/glass.h "Prompt sets"
+PROMPT_MAX = 16
+
+
 class GlassNoise(C.Structure):
     _fields_ = [("n_minibatches", C.c_int32), ("n_layers", C.c_int32),
                 ("planes", C.POINTER(C.POINTER(C.c_float)))]
@@ -70,7 +80,7 @@ def load_library(path=None):
     fp = C.POINTER(C.c_float)
     lib.glass_last_error.restype = C.c_char_p
     lib.glass_version.restype = C.c_char_p
-    lib.glass_engine_create.argtypes = [C.POINTER(GlassConfigLpips), C.POINTER(C.c_void_p)]
+    lib.glass_engine_create.argtypes = [C.POINTER(GlassConfigPrompt), C.POINTER(C.c_void_p)]
     if hasattr(lib, "glass_clip_geometry_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
         lib.glass_clip_geometry_supported.argtypes = [C.c_int32] * 6
     if hasattr(lib, "glass_clip_preprocess_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
@@ -95,6 +105,11 @@ def load_library(path=None):
         lib.glass_engine_set_lpips_target.argtypes = [C.c_void_p, fp, C.c_int32]
         lib.glass_engine_lpips.argtypes = [C.c_void_p, fp, fp, C.c_int32, fp]
         lib.glass_engine_last_lpips.argtypes = [C.c_void_p, C.c_int32, fp]
+    if hasattr(lib, "glass_prompt_set_supported"):      # (absent from older A/B builds loaded through GLASS_LIB)
+        lib.glass_prompt_set_supported.argtypes = [C.c_int32] * 3
+        lib.glass_engine_set_targets.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.c_int32]
+        lib.glass_engine_last_set_details.argtypes = [C.c_void_p, C.c_int32, fp]
+        lib.glass_engine_encode_generated.argtypes = [C.c_void_p, fp, C.c_int32, fp]
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -176,6 +191,29 @@ def lpips_n_obj(use_discriminator, lpips_lambda):
     return 1 + int(bool(use_discriminator)) + int(float(lpips_lambda) == 0.0)
 
 
+def prompt_mode_id(mode):
+    """The ABI's mode of a prompt set: "sum" -> 0, "pareto" -> 1 (ints pass through); ValueError lists the names otherwise."""
+    if mode in PROMPT_MODES:
+        return PROMPT_MODES[mode]
+    if isinstance(mode, (int, np.integer)) and not isinstance(mode, bool):
+        return int(mode)
+    raise ValueError("unknown prompt_mode %r: expected one of %s" % (mode, ", ".join(PROMPT_MODES)))
+
+
+def prompt_set_supported(n_entries, mode="sum", sim_columns=0):
+    """(ok, message) for a prompt set of n_entries in `mode` on an engine with `sim_columns`: the library's own rule, the one
+    glass_engine_set_targets applies.  Host only."""
+    lib = load_library()
+    rc = lib.glass_prompt_set_supported(int(n_entries), prompt_mode_id(mode), int(sim_columns))
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
+def prompt_n_obj(sim_columns, use_discriminator, lpips_column=False):
+    """Columns of F on an engine with `sim_columns` similarity columns (include/glass.h): those, the hinge with D, the LPIPS distance when
+    it is its own column."""
+    return max(int(sim_columns), 1) + int(bool(use_discriminator)) + int(bool(lpips_column))
+
+
 def clip_view_permille(fraction):
     """The smallest crop side as the library takes it: per mille of the image side."""
     return int(round(1000 * float(fraction)))
@@ -249,7 +287,7 @@ class Engine:
                  n_obj=2, max_pop=64, chunk=0, clip=(768, 12, 12, 32, 224, 512), noise_mode=1, noise_seed=0,
                  mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0, clip_resnet=None,
                  clip_views=0, clip_view_min=0.5, clip_view_flip=True, clip_view_fixed=False,
-                 latent_space="z", truncation_psi=1.0, truncation_cutoff=None, lpips_size=0, lpips_lambda=0.0):
+                 latent_space="z", truncation_psi=1.0, truncation_cutoff=None, lpips_size=0, lpips_lambda=0.0, sim_columns=0):
         """`biggan` = dict(layers=[(up, in_mult, out_mult), ...], attention_pos, ch, z_dim, num_classes, n_stats, eps,
         truncation) selects the BigGAN-deep generator (channels must then be empty, no discriminator).
         clip_resize / clip_normalize: how a generated image is prepared for CLIP (include/glass.h); (0, 0) is the reference's way.
@@ -264,9 +302,12 @@ class Engine:
         cutoff needs.
         lpips_size = S > 0 turns the perceptual objective on (include/glass.h): the LPIPS-VGG16 distance between a candidate's image,
         area-downscaled to S px, and the image given to set_lpips_target().  lpips_lambda = 0: the distance is one more, last, column
-        of F and n_obj must count it (lpips_n_obj); > 0: F[:, 0] = -sim + lambda * d and n_obj stays.  Needs the "lpips.*" tensors."""
+        of F and n_obj must count it (lpips_n_obj); > 0: F[:, 0] = -sim + lambda * d and n_obj stays.  Needs the "lpips.*" tensors.
+        sim_columns = K in [2, 4] makes an engine for a pareto prompt set (include/glass.h "Prompt sets"): K similarity columns, one per
+        entry of set_targets(..., mode="pareto"), and n_obj must be prompt_n_obj(K, ...); 0 (default): the one similarity column."""
         self.lib = load_library()
-        cfg = GlassConfigLpips()
+        cfg = GlassConfigPrompt()
+        cfg.sim_columns = int(sim_columns)
         cfg.lpips_size, cfg.lpips_lambda = int(lpips_size), float(lpips_lambda)
         cfg.device = device
         if biggan is not None:
@@ -283,6 +324,8 @@ class Engine:
             latent_size = cfg.bg_z_dim + cfg.bg_num_classes
             channels, use_discriminator, noise_mode = [], False, 0
             n_obj = lpips_n_obj(False, lpips_lambda) if cfg.lpips_size else 1
+            if cfg.sim_columns >= 2:
+                n_obj = prompt_n_obj(cfg.sim_columns, False, bool(cfg.lpips_size) and float(lpips_lambda) == 0.0)
         cfg.n_blocks = len(channels)
         for i, c in enumerate(channels):  # LOW -> HIGH resolution
             cfg.channels[i] = int(c)
@@ -354,6 +397,38 @@ class Engine:
     def set_target(self, feat):
         f = _f32(feat).reshape(-1)
         _check(self.lib, self.lib.glass_engine_set_target(self._h, _fp(f), f.size))
+        self.n_prompts = 0
+
+    # --- prompt sets -----------------------------------------------------------
+    def set_targets(self, features, weights, mode="sum"):
+        """A prompt set as the target (include/glass.h "Prompt sets"): features float32 [T, clip_embed], weights [T] (negative: away from the
+        entry), mode "sum" (one blended similarity column) or "pareto" (one column per entry; Engine(sim_columns=T)).  After finalize()."""
+        f, w = _f32(features), _f32(weights).reshape(-1)
+        if f.ndim != 2 or f.shape[0] != w.size:
+            raise ValueError("set_targets: features must be [T, clip_embed] with one weight per row, got %r and %d weights" % (f.shape, w.size))
+        _check(self.lib, self.lib.glass_engine_set_targets(self._h, _fp(f), _fp(w), f.shape[0], f.shape[1], prompt_mode_id(mode)))
+        self.n_prompts = int(f.shape[0])
+
+    def set_details(self, P):
+        """Per-entry similarities [P, T] of the last evaluate() with a prompt set (the means over the views where they are on)."""
+        T = int(getattr(self, "n_prompts", 0))
+        out = np.empty((P, max(T, 1)), dtype=np.float32)
+        _check(self.lib, self.lib.glass_engine_last_set_details(self._h, P, _fp(out)))
+        return out
+
+    def encode_generated(self, images):
+        """The CLIP feature a generated image with these pixels gets in the pass: images float32 [n, 3, R, R] in [-1, 1] through the engine's
+        own clip_resize / clip_normalize (whole image, no crop views) and the tower -> [n, clip_embed].  n <= max_pop."""
+        a = _f32(images)
+        if a.ndim != 4 or a.shape[1:] != (3, self.res, self.res):
+            raise ValueError("encode_generated: images must be [n, 3, %d, %d], got %r" % (self.res, self.res, a.shape))
+        out = np.empty((a.shape[0], self.cfg.clip_embed), dtype=np.float32)
+        _check(self.lib, self.lib.glass_engine_encode_generated(self._h, _fp(a), a.shape[0], _fp(out)))
+        return out
+
+    @staticmethod
+    def prompt_set_supported(n_entries, mode="sum", sim_columns=0):
+        return prompt_set_supported(n_entries, mode, sim_columns)
 
     # --- perceptual objective --------------------------------------------------
     def set_lpips_target(self, image):

@@ -11,8 +11,8 @@ import os
 import numpy as np
 
 from . import synth
-from .engine import (LATENT_SPACES, Engine, clip_geometry_supported, clip_resnet_supported, clip_view_permille, clip_views_supported,
-                     clip_views_tower_rows, lpips_n_obj, lpips_supported)
+from .engine import (LATENT_SPACES, PROMPT_MAX, PROMPT_MODES, Engine, clip_geometry_supported, clip_resnet_supported, clip_view_permille,
+                     clip_views_supported, clip_views_tower_rows, lpips_n_obj, lpips_supported, prompt_n_obj)
 from .utils import save_grid, save_image
 
 CLIP_VIT_B32 = (768, 12, 12, 32, 224, 512)
@@ -114,6 +114,84 @@ def lpips_config(config, opts):
         return config
     out = copy.copy(config)
     out.problem_args = dict(config.problem_args, n_obj=int(config.problem_args["n_obj"]) + 1)
+    out.algorithm = "nsga2"
+    return out
+
+
+# ---- prompt sets (opt-in, include/glass.h "Prompt sets"): weighted, negative and image prompts; the reference's run.py has one target ----
+PROMPT_KEYS = ("prompts", "prompt_mode", "target_weight")
+DEFAULT_PROMPT_MODE = "sum"
+
+
+def parse_weighted(text):
+    """"TEXT[::WEIGHT]" of --prompt / --image-prompt -> (TEXT, weight), weight 1 when absent.  The LAST "::" splits, and only where a number
+    follows it: a prompt may hold "::" itself."""
+    head, sep, tail = str(text).rpartition("::")
+    if sep:
+        try:
+            return head, float(tail)
+        except ValueError:
+            pass
+    return str(text), 1.0
+
+
+def prompt_options(config):
+    """None while `prompts`, `prompt_mode` and `target_weight` are unset (the default: one target through set_target), else
+    dict(mode, entries) with entries = [(kind, value, weight), ...]: the config's own target first — ("target", None, target_weight or 1) —
+    then config.prompts, a list of (value, weight) pairs whose value is a string (kind "text"), ("image", path_or_array) (kind "image") or a
+    float array [clip_embed] (kind "feature").  ValueError with the reason, before any weight is looked for: the GPT2 / img2txt config (its
+    cosine is taken on the host, against one image), more than 16 entries, a zero or non-finite weight, an unknown mode, pareto with fewer
+    than 2 or more than 4 entries, pareto with lpips_lambda > 0."""
+    vals = {k: getattr(config, k, None) for k in PROMPT_KEYS}
+    given = [k for k in PROMPT_KEYS if vals[k] is not None]
+    if not given:
+        return None
+    if getattr(config, "task", "txt2img") == "img2txt":
+        raise ValueError("%s: prompt sets steer generated images (txt2img); the img2txt task (config %r) compares generated texts with one "
+                         "image on the host: leave these keys unset" % (", ".join(given), str(getattr(config, "config", "GPT2"))))
+    mode = DEFAULT_PROMPT_MODE if vals["prompt_mode"] is None else vals["prompt_mode"]
+    if mode not in PROMPT_MODES:
+        raise ValueError("unknown prompt_mode %r: expected one of %s" % (mode, ", ".join(PROMPT_MODES)))
+    entries = [("target", None, 1.0 if vals["target_weight"] is None else float(vals["target_weight"]))]
+    for i, item in enumerate(vals["prompts"] or []):
+        try:
+            value, weight = item
+        except (TypeError, ValueError):
+            raise ValueError("prompts[%d] must be a (value, weight) pair, got %r" % (i, item))
+        if isinstance(value, str):
+            entries.append(("text", value, float(weight)))
+        elif isinstance(value, tuple) and len(value) == 2 and isinstance(value[0], str) and value[0] == "image":
+            entries.append(("image", value[1], float(weight)))
+        else:
+            entries.append(("feature", np.asarray(value, dtype=np.float32).reshape(-1), float(weight)))
+    if len(entries) > PROMPT_MAX:
+        raise ValueError("a prompt set holds at most %d entries (the target and the prompts), got %d" % (PROMPT_MAX, len(entries)))
+    for i, (kind, _, w) in enumerate(entries):
+        if not np.isfinite(w) or w == 0.0:
+            raise ValueError("prompt weight %d (%s) must be finite and non-zero, got %r: a negative weight steers away from the prompt, "
+                             "an entry to ignore is left out" % (i, "target_weight" if kind == "target" else kind, w))
+    if mode == "pareto":
+        if not 2 <= len(entries) <= 4:
+            raise ValueError("prompt_mode 'pareto' gives every entry its own objective: 2 to 4 entries (the target and the prompts), got %d"
+                             % len(entries))
+        lam = getattr(config, "lpips_lambda", None)
+        if getattr(config, "lpips_target", None) is not None and lam is not None and float(lam) > 0.0:
+            raise ValueError("prompt_mode 'pareto' with lpips_lambda > 0: lambda folds the distance into THE similarity objective, and a "
+                             "pareto set has one per prompt: use lpips_lambda 0 (the distance as an objective of its own)")
+    return dict(mode=mode, entries=entries)
+
+
+def prompt_config(config, opts):
+    """The config a pareto prompt set searches: a COPY (as lpips_config's, and applied AFTER it: prompt_config(lpips_config(config, lp),
+    opts)) with problem_args["n_obj"] = K + discriminator + (the LPIPS distance as a column) and algorithm "nsga2".  Mode sum, and no set,
+    search the config as it is."""
+    if opts is None or opts["mode"] != "pareto":
+        return config
+    lam = getattr(config, "lpips_lambda", None)
+    lp_col = getattr(config, "lpips_target", None) is not None and not float(lam or 0.0) > 0.0
+    has_d = bool(getattr(config, "use_discriminator", False)) and int(config.problem_args["n_obj"]) - int(lp_col) == 2
+    out = copy.copy(config)
+    out.problem_args = dict(config.problem_args, n_obj=prompt_n_obj(len(opts["entries"]), has_d, lp_col))
     out.algorithm = "nsga2"
     return out
 
@@ -364,8 +442,10 @@ class Generator:
         # perceptual objective (opt-in): refused for the GPT2 config here, before any weight is looked for; with lambda = 0 the search gets
         # one more objective — on a copy of the config, which callers read back as `generator.config`
         self.lpips = lpips_options(config)
+        # prompt set (opt-in): refused for the GPT2 config the same way; a pareto set searches one objective per entry, on a copy too
+        self.prompts = prompt_options(config)
         base_n_obj = int((getattr(config, "problem_args", None) or {}).get("n_obj", 1))
-        config = lpips_config(config, self.lpips)
+        config = prompt_config(lpips_config(config, self.lpips), self.prompts)
         self.config = config
         self.augmentation = None
         self.model = config.model(config)                                   # generator.py:19
@@ -429,7 +509,10 @@ class Generator:
             from .tokenizer import DEFAULT_BPE, ClipTokenizer
             self.tokenizer = ClipTokenizer(getattr(config, "bpe_path", DEFAULT_BPE))
             return
-        need_text = getattr(config, "target_features", None) is None
+        need_text = getattr(config, "target_features", None) is None or any(
+            kind == "text" for kind, _, _ in (self.prompts["entries"] if self.prompts else []))
+        pareto = self.prompts is not None and self.prompts["mode"] == "pareto"
+        sim_columns = len(self.prompts["entries"]) if pareto else 0
         clip_state, geom = _load_clip_state(config, need_text)
         check_clip_geometry(geom)        # an unsupported checkpoint fails here, not in generation 1
         tower = self._clip_tower(geom)
@@ -443,6 +526,8 @@ class Generator:
         tower.update(view_kw)
         if self.lpips is not None:
             tower.update(lpips_size=self.lpips["size"], lpips_lambda=self.lpips["lam"])
+        if pareto:
+            tower.update(sim_columns=sim_columns)
         if hasattr(self.model, "geometry"):     # BigGAN-deep (models.py:64-86)
             self.engine = Engine([], batch_size=config.batch_size, max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  device=device, biggan=self.model.geometry, clip_resize=clip_resize,
@@ -451,7 +536,8 @@ class Generator:
             self.engine = Engine(self.model.channels[::-1], latent_size=config.dim_z,
                                  mapping_layers=getattr(config, "mapping_layers", 8), batch_size=config.batch_size,
                                  use_discriminator=bool(config.use_discriminator and base_n_obj == 2),
-                                 n_obj=(lpips_n_obj(config.use_discriminator and base_n_obj == 2, self.lpips["lam"])
+                                 n_obj=(int(config.problem_args["n_obj"]) if pareto
+                                        else lpips_n_obj(config.use_discriminator and base_n_obj == 2, self.lpips["lam"])
                                         if self.lpips is not None else base_n_obj), max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  noise_mode=getattr(config, "noise_mode", 1),
                                  noise_seed=getattr(config, "noise_seed", 0), device=device, clip_resize=clip_resize,
@@ -473,18 +559,50 @@ class Generator:
             self.engine.set_lpips_target(self.lpips_target)
         if self.latent_space != DEFAULT_LATENT_SPACE:       # the row width of latent.StyleGAN2LatentSpace / operators follows the loaded network
             config.n_lat = self.engine.latent_row()[1]
+        texts = [v for kind, v, _ in (self.prompts["entries"] if self.prompts else []) if kind == "text"]
         if getattr(config, "target_features", None) is not None:            # pre-computed text feature
             self.text_features = np.asarray(config.target_features, np.float32).reshape(1, -1)
-        else:                                                               # generator.py:23-24
+        else:
+            texts = [self.config.target] + texts
+        if texts:                                                           # generator.py:23-24; the set's texts in the same call
             from .tokenizer import DEFAULT_BPE, ClipTokenizer
             tok = ClipTokenizer(getattr(config, "bpe_path", DEFAULT_BPE))
-            self.tokens = tok.tokenize([self.config.target])
-            self.text_features = self.engine.encode_text(self.tokens)
-        self.engine.set_target(self.text_features[0])
+            self.tokens = tok.tokenize(texts)
+            encoded = self.engine.encode_text(self.tokens)
+            if getattr(config, "target_features", None) is None:
+                self.text_features, encoded = encoded[:1], encoded[1:]
+        if self.prompts is None:
+            self.engine.set_target(self.text_features[0])
+        else:
+            self._set_prompts(encoded if texts else None)
         if sharded:
             from .parallel import ShardedEvaluator
             self.sharder = ShardedEvaluator(self.engine, dist, dist.get_rank(), dist.get_world_size(), config.batch_size,
                                             device=device)
+
+    def _set_prompts(self, text_features):
+        """Build the set's features [T, E] in the order of prompt_options' entries and hand it to the engine.  text_features: the encoded
+        "text" entries, in order.  An image goes through prepare_lpips_target (centre crop, resize to the generator's side, [-1, 1]) and
+        the engine's encode_generated: the feature a generated image with those pixels would get."""
+        E = int(self.engine.cfg.clip_embed)
+        rows, n_text = [], 0
+        for kind, value, _ in self.prompts["entries"]:
+            if kind == "target":
+                f = self.text_features[0]
+            elif kind == "text":
+                f, n_text = text_features[n_text], n_text + 1
+            elif kind == "image":
+                f = self.engine.encode_generated(prepare_lpips_target(value, self.engine.res)[None])[0]
+            else:
+                f = value
+            f = np.asarray(f, dtype=np.float32).reshape(-1)
+            if f.size != E:
+                raise ValueError("a prompt feature must hold clip_embed = %d floats, got %d" % (E, f.size))
+            rows.append(f)
+        self.prompt_features = np.stack(rows)
+        self.prompt_weights = np.asarray([w for _, _, w in self.prompts["entries"]], dtype=np.float32)
+        self.prompt_mode = self.prompts["mode"]
+        self.engine.set_targets(self.prompt_features, self.prompt_weights, self.prompt_mode)
 
     def map_latents(self, z):
         """z [N, dim_z] -> untruncated dlatents w [N, dim_z] through the engine's mapping network, in slices of its capacity."""

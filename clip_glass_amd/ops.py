@@ -848,6 +848,31 @@ def cosine_views(feat, target, device=0):
     return vs, sim
 
 
+def cosine_set(feat, targets, weights, device=0):
+    """feat [P, V, D], targets [T, D], weights [T] -> (view_sim [P, V], set_sim [P, T], sim [P]): cosine_set_kernel (prompt sets)."""
+    lib = load_library()
+    feat, targets, weights = _f32(feat), _f32(targets), _f32(weights)
+    P, V, D = feat.shape
+    T = targets.shape[0]
+    vs, ss, sim = np.empty((P, V), np.float32), np.empty((P, T), np.float32), np.empty(P, np.float32)
+    lib.glass_op_cosine_set.argtypes = [C.c_int32] * 5 + [_FP] * 6
+    _check(lib, lib.glass_op_cosine_set(device, P, V, T, D, _fp(feat), _fp(targets), _fp(weights), _fp(vs), _fp(ss), _fp(sim)))
+    return vs, ss, sim
+
+
+def assemble_F_set(set_sim, weights, dis=None, lp=None, device=0):
+    """set_sim [P, K], weights [K], dis / lp [P] or None -> F [P, K + (dis is not None) + (lp is not None)]: the pareto layout."""
+    lib = load_library()
+    set_sim, weights = _f32(set_sim), _f32(weights)
+    P, K = set_sim.shape
+    d, dp = _opt(dis)
+    l, lpp = _opt(lp)
+    Fv = np.empty((P, K + (dis is not None) + (lp is not None)), dtype=np.float32)
+    lib.glass_op_assemble_F_set.argtypes = [C.c_int32] * 3 + [_FP] * 5
+    _check(lib, lib.glass_op_assemble_F_set(device, P, K, _fp(set_sim), _fp(weights), dp, lpp, _fp(Fv)))
+    return Fv
+
+
 def assemble_F(sim, dis=None, device=0):
     lib = load_library()
     sim = _f32(sim)

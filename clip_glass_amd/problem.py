@@ -74,7 +74,9 @@ class GenerationProblem(Problem):
             x = np.concatenate([x, np.repeat(x[-1:], pad, axis=0)])
         ls.set_from_population(x)
         F = self.generator.evaluate(ls)[:P]
-        if getattr(self.generator, "lpips", None) is not None and self.config.problem_args["n_obj"] >= 2:
+        if getattr(self.generator, "prompt_mode", None) == "pareto" or self.config.problem_args["n_obj"] >= 3:
+            out["F"] = F                                # (one similarity column per prompt, [hinge], [perceptual distance])
+        elif getattr(self.generator, "lpips", None) is not None and self.config.problem_args["n_obj"] >= 2:
             out["F"] = F                                # (-sim, [hinge], perceptual distance)
         elif self.config.problem_args["n_obj"] == 2 and self.config.use_discriminator:
             out["F"] = F                                # column_stack((-sim, hinge)) (problem.py:25)

@@ -15,7 +15,8 @@ import numpy as np
 
 from .config import get_config
 from .engine import LATENT_SPACES
-from .generator import CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, latent_options, lpips_options
+from .engine import PROMPT_MODES
+from .generator import CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, latent_options, lpips_options, parse_weighted, prompt_options
 from .operators import get_operators
 from .problem import GenerationProblem
 from . import search
@@ -66,6 +67,15 @@ def build_parser():
                    help="0 (default): the distance is an objective of its own (NSGA-II); > 0: it is added to the similarity objective, times lambda")
     p.add_argument("--lpips-weights", type=str, default=None,
                    help="a torch file with torchvision's vgg16 features.N.{weight,bias} and LPIPS's lin.K.weight, or synthetic:<seed>")
+    p.add_argument("--prompt", action="append", default=None, metavar="TEXT[::WEIGHT]",
+                   help="one more text prompt next to --target, repeatable; a negative weight steers away from it (\"glasses::-0.5\").  Off by "
+                        "default — the reference's run.py has one target; this departs from it on purpose")
+    p.add_argument("--image-prompt", action="append", default=None, metavar="PATH[::WEIGHT]",
+                   help="a picture as a prompt, repeatable: centre-cropped, resized to the generator's side and encoded as a generated image is")
+    p.add_argument("--target-weight", type=float, default=None, help="weight of --target within the prompt set (default 1)")
+    p.add_argument("--prompt-mode", type=str, default=None, choices=list(PROMPT_MODES),
+                   help="sum (default): the prompts blend into the one similarity objective, sum_t w_t sim_t / sum_t |w_t|; pareto: one objective "
+                        "per prompt (2 to 4, NSGA-II)")
     p.add_argument("--bpe-path", type=str, default=None)
     p.add_argument("--pop-size", type=int, default=None)
     p.add_argument("--stochastic", action="store_true", default=None,
@@ -78,12 +88,31 @@ def build_parser():
     return p
 
 
+def similarity_columns(config):
+    """Similarity columns of F for this config: one, or one per entry of a pareto prompt set (the target and config.prompts)."""
+    if getattr(config, "prompt_mode", None) == "pareto":
+        return 1 + len(getattr(config, "prompts", None) or [])
+    return 1
+
+
 def objective_names(config):
-    """Column names of F for this config: similarity, then discriminator (with D), then lpips (perceptual objective, lambda = 0)."""
+    """Column names of F for this config: similarity (similarity-0 .. similarity-(K - 1) for a pareto prompt set of K entries), then
+    discriminator (with D), then lpips (perceptual objective, lambda = 0)."""
     n = int(config.problem_args["n_obj"])
+    K = similarity_columns(config)
     lp_col = getattr(config, "lpips_target", None) is not None and not float(getattr(config, "lpips_lambda", None) or 0.0) > 0.0
-    names = ["similarity"] + (["discriminator"] if n - 1 - int(lp_col) >= 1 else []) + (["lpips"] if lp_col else [])
+    sims = ["similarity"] if K == 1 else ["similarity-%d" % t for t in range(K)]
+    names = sims + (["discriminator"] if n - K - int(lp_col) >= 1 else []) + (["lpips"] if lp_col else [])
     return names
+
+
+def cli_prompts(prompts, image_prompts):
+    """config.prompts of the --prompt / --image-prompt flags: the texts first, then the pictures, each as (value, weight)."""
+    out = [parse_weighted(t) for t in (prompts or [])]
+    for item in (image_prompts or []):
+        path, w = parse_weighted(item)
+        out.append((("image", path), w))
+    return out
 
 
 def scatter_pairs(names):
@@ -98,7 +127,11 @@ def final_pick_weights(names):
     realistic point (run.py:103-113).  With the perceptual distance as a third objective the weight is split evenly between realism and
     closeness to the target, (0, .5, .5); without D it goes to the distance, (0, 1).  A default, not a result: the whole front is in
     genetic_result."""
-    return [0.0, 0.5, 0.5] if len(names) == 3 else [0.0, 1.0]
+    sims = [n.startswith("similarity") for n in names]
+    rest = len(names) - sum(sims)
+    if rest == 0:           # nothing but similarities (a pareto prompt set without D or LPIPS): no column is preferred
+        return [1.0 / len(names)] * len(names)
+    return [0.0 if s else 1.0 / rest for s in sims]
 
 
 def main(argv=None, extra_config=None):
@@ -107,13 +140,16 @@ def main(argv=None, extra_config=None):
     vars(config).update(get_config(config.config))                             # run.py:25
     for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "clip_views", "clip_view_min", "clip_view_flip",
               "clip_view_fixed", "latent_space", "truncation_psi", "truncation_cutoff", "lpips_target", "lpips_size", "lpips_lambda", "lpips_weights",
-              "bpe_path", "pop_size", "stochastic"):
+              "bpe_path", "pop_size", "stochastic", "target_weight", "prompt_mode"):
         if k in over:
             setattr(config, k, over[k])
+    if "prompt" in over or "image_prompt" in over:
+        config.prompts = cli_prompts(over.get("prompt"), over.get("image_prompt"))
     if extra_config:
         vars(config).update(extra_config)
     latent_options(config)      # a latent space / truncation on a BigGAN or GPT2 config is refused here, before anything is loaded
     lpips_options(config)       # ... and so is the perceptual objective on the GPT2 config
+    prompt_options(config)      # ... and a prompt set there, or one the engine would refuse
     state = dict(iteration=0)
     dist, rank0 = None, True
     if getattr(config, "dist", False):

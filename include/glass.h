@@ -89,6 +89,10 @@ typedef struct glass_config {
      * glass_engine_set_lpips_target.  With lpips_size > 0, n_obj must be 1 + use_discriminator + (lpips_lambda == 0). */
     int32_t lpips_size;           /* 0: off (default); S: the generated image is area-downscaled to S x S in front of VGG16 */
     float lpips_lambda;           /* 0: the distance d is its own LAST column, F = [-sim, (hinge), d]; > 0: no column, F[:,0] = fmaf(lambda, d, -sim) */
+    /* --- opt-in: one similarity column per prompt (mode pareto of a prompt set, see "Prompt sets" below).  Appended last: zero, or a caller built
+     * against the shorter struct, selects the one similarity column of today. */
+    int32_t sim_columns;          /* 0 or 1: one similarity column (default); K in [2, 4]: K columns, n_obj = K + use_discriminator + (lpips_size > 0 &&
+                                     lpips_lambda == 0); lpips_lambda > 0 is refused then */
 } glass_config;
 
 /* Caller-provided noise (noise_mode 2): planes[m * n_layers + l] points at a host
@@ -154,6 +158,41 @@ int glass_host_clip_view_boxes(uint64_t seed, int32_t generation, int32_t views,
  * (four max pools need even sides); gen_res % lpips_size == 0 with a box of at most 8; gen_res 0 checks lpips_size alone.  Returns GLASS_OK,
  * or GLASS_ERR_ARG with the reason in glass_last_error().  An engine without a generator (GPT-2) refuses lpips_size > 0. */
 int glass_lpips_supported(int32_t gen_res, int32_t lpips_size);
+
+/* Prompt sets (opt-in; off until glass_engine_set_targets is called; departs from the reference's run.py, which has one target): weighted,
+ * negative and image prompts.  A set is T entries, 1 <= T <= 16; entry t is a vector g_t (float32 [clip_embed]) and a weight w_t, finite and
+ * non-zero; a negative weight means "away from".
+ * One feature row f against entry t: c = xy / max(sqrt(xx) * sqrt(yy), 1e-8), the three sums taken as the single-target pass takes them —
+ * lane-strided partial sums (i = lane; i < D; i += 64), then the wave sum: the same bits as the single-target cosine of (f, g_t).
+ * Crop views on: cbar[p][t] = (sum_v c[p][v][t]) / V, summed in fp32 in the order v = 0 .. V - 1 (the views' own rule, per entry); without
+ * views cbar = c.
+ * Mode sum (0, default): sim[p] = acc / W; acc starts at 0 and, for t = 0 .. T - 1, acc = acc + w_t * cbar[p][t], the product and the sum each
+ * rounded to fp32 (never one fused multiply-add, so numpy float32 reproduces the bits); W = sum_t |w_t| in fp32 in the order t = 0 .. T - 1.
+ * F[:,0] is built from sim exactly as with one target (the lpips_lambda > 0 fold included): T = 1 with w = 1 gives the single target's bits.
+ * Mode pareto (1): one column per entry, K = T columns with 2 <= K <= 4 on an engine created with sim_columns = K:
+ * F[p][t] = w_t < 0 ? cbar[p][t] : -cbar[p][t] (the weight's magnitude has no meaning on a front), then the hinge column with a discriminator,
+ * then the LPIPS distance when it is its own column: n_obj = K + use_discriminator + (lpips_size > 0 && lpips_lambda == 0).  lpips_lambda > 0
+ * with K >= 2 is refused: there is no single similarity column to fold into.
+ * sim[p], as glass_engine_last_details returns it, is the mode-sum value in both modes; glass_engine_last_view_details reports entry 0's
+ * per-view cosines.  The pass launches as many kernels with a set as without one.
+ *
+ * glass_prompt_set_supported: the one rule (host only: callable without a GPU), applied by the setter too.  n_entries in [1, 16]; mode 0 needs
+ * sim_columns <= 1; mode 1 needs n_entries == sim_columns (in [2, 4]).  Returns GLASS_OK, or GLASS_ERR_ARG with the reason. */
+int glass_prompt_set_supported(int32_t n_entries, int32_t mode, int32_t sim_columns);
+/* Make a prompt set the target (after finalize; any time between passes).  feats host float32 [T][E], weights [T].  GLASS_ERR_ARG for
+ * E != clip_embed, a weight that is zero or not finite, and whatever glass_prompt_set_supported refuses.  The buffers of a set (16 entries,
+ * [max_pop][16] similarities) are allocated by the first call: an engine that never calls it allocates nothing for sets.
+ * glass_engine_set_target clears the set; on an engine with sim_columns >= 2 set_target is refused (GLASS_ERR_STATE) and evaluate() fails
+ * (GLASS_ERR_STATE, "set_targets() first") while no set is active. */
+int glass_engine_set_targets(glass_engine* e, const float* feats /*[T][E]*/, const float* weights /*[T]*/, int32_t T, int32_t E, int32_t mode);
+/* cbar [P][T] of the last evaluate() (GLASS_ERR_STATE without an active set). */
+int glass_engine_last_set_details(glass_engine* e, int32_t P, float* set_sim /*[P][T]*/);
+/* The feature a generated image with these pixels gets in the pass: images host float32 [n][3][R][R] in [-1, 1] (the generator's raw range) go
+ * through the pass's own preprocessing (clip_resize / clip_normalize; crop views are ignored: the whole image) and the image tower; out_feat
+ * [n][clip_embed].  n <= max_pop; engines with a generator only (GLASS_ERR_STATE otherwise).  This is what makes an image a prompt that is
+ * comparable with the candidates: by default they reach CLIP without mean / std normalisation, so a picture encoded through clip.py's
+ * transform (glass_engine_encode_image) sits in another input distribution.  Overwrites the per-candidate outputs of the last evaluate(). */
+int glass_engine_encode_generated(glass_engine* e, const float* images /*[n][3][R][R] in [-1,1]*/, int32_t n, float* out_feat);
 
 int glass_engine_create(const glass_config* cfg, glass_engine** out);
 /* The target image of the perceptual objective: img host float32 [3][S][S] in [-1, 1], S = lpips_size.  After finalize; runs VGG16 on it once
@@ -254,7 +293,7 @@ int glass_engine_gpt2_sample(glass_engine* e, const int32_t* context, int32_t P,
  * first_minibatch: global index of this call's first minibatch (population shards);
  * noise: nullable, used when noise_mode == 2;
  * out_F: host float32 [P, n_obj]: F[:,0] = -cosine, F[:,1] = relu(1 - D) (problem.py:23-27); with the perceptual objective and
- *   lpips_lambda == 0 the distance is one more, last, column (n_obj up to 3).
+ *   lpips_lambda == 0 the distance is one more, last, column (n_obj up to 3); with a pareto prompt set, sim_columns similarity columns first.
  * P must be a multiple of batch_size (reference asserts: models.py:112). */
 int glass_engine_evaluate(glass_engine* e, const float* latents, int32_t P, int32_t generation,
                           int32_t first_minibatch, const glass_noise* noise, float* out_F);

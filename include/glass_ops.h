@@ -217,6 +217,9 @@ int glass_op_rn_tokens(int32_t device, int32_t B, int32_t HW, int32_t C, const f
  * glass_op_layernorm_ex: launch_layernorm on rows row_stride apart (x holds (M - 1) row_stride + D floats); half_out: the fp16 output.
  * glass_op_layernorm_rows: out[m] = LN(x[rows[m]]), x [n_rows,D].
  * glass_op_cosine_views: feat [P,V,D] -> view_sim [P,V], sim [P].
+ * glass_op_cosine_set: launch_cosine_set (prompt sets, include/glass.h): feat [P,V,D], targets [T,D], weights [T] (W = their ordered sum of
+ *   magnitudes, taken inside) -> view_sim [P,V] (entry 0's cosines), set_sim [P,T], sim [P].  V, T in [1, 16].
+ * glass_op_assemble_F_set: the pareto layout: set_sim [P,K], weights [K], dis / lp [P] (nullable each) -> F [P, K + (dis != 0) + (lp != 0)].
  * glass_op_image_patches: img [n,3,S,S] -> patches [n (S/ps)^2, ld] (fp16 values), pre-filled with `sentinel`.
  * glass_op_rn_token0_rows: att [B,T,C] (fp16) -> out [B,C] = att[b, 0, :]. */
 int glass_op_mapping(int32_t device, int32_t P, int32_t L, int32_t n_layers, const float* z, const float* wt, const float* b, int32_t path,
@@ -245,6 +248,10 @@ int glass_op_layernorm_rows(int32_t device, int32_t n_rows, int32_t M, int32_t D
 int glass_op_cosine(int32_t device, int32_t P, int32_t D, const float* feat, const float* target, float* sim);
 int glass_op_cosine_views(int32_t device, int32_t P, int32_t V, int32_t D, const float* feat, const float* target, float* view_sim, float* sim);
 int glass_op_assemble_F(int32_t device, int32_t P, int32_t n_obj, const float* sim, const float* dis, float* F);
+int glass_op_cosine_set(int32_t device, int32_t P, int32_t V, int32_t T, int32_t D, const float* feat, const float* targets, const float* weights,
+                        float* view_sim, float* set_sim, float* sim);
+int glass_op_assemble_F_set(int32_t device, int32_t P, int32_t K, const float* set_sim, const float* weights, const float* dis, const float* lp,
+                            float* F);
 int glass_op_image_patches(int32_t device, int32_t n, int32_t S, int32_t ps, int32_t ld, const float* img, float sentinel, float* patches);
 int glass_op_rn_token0_rows(int32_t device, int32_t B, int32_t T, int32_t C, const float* att, float* out);
 /* The perceptual objective's own kernels (lpips.hip), each through the launcher the walker (lpips.cpp) calls; a shape the launcher does not
