@@ -18,7 +18,10 @@ config with `n_obj` one higher and `algorithm` "nsga2", this table is not touche
 [clip_embed]; a negative weight steers away from the prompt, include/glass.h "Prompt sets"), with `target_weight` (1: the weight of `target`,
 which is always the set's first entry) and `prompt_mode` ("sum", the default: the entries blend into the one similarity objective,
 sum_t w_t sim_t / sum_t |w_t|; "pareto": one objective per entry, 2 to 4 — the Generator then searches a copy of the config with `n_obj` =
-entries + discriminator + LPIPS column and `algorithm` "nsga2") — the StyleGAN2 and BigGAN configs; refused for GPT2."""
+entries + discriminator + LPIPS column and `algorithm` "nsga2") — the StyleGAN2 and BigGAN configs; refused for GPT2;
+`device_search` (False, the default: search.py's host operators; True: the population stays on the GPU and the generation step — tournament,
+SBX, polynomial mutation, duplicate flags, survival — runs there, include/glass.h "Device search") — the StyleGAN2 configs on one rank;
+refused for the BigGAN and GPT2 configs, whose rows are not all real."""
 from .latent import DeepMindBigGANLatentSpace, GPT2LatentSpace, StyleGAN2LatentSpace
 from .models import GPT2, DeepMindBigGAN, StyleGAN2
 from .utils import biggan_denorm, biggan_norm

@@ -406,6 +406,7 @@ extern "C" int glass_engine_finalize(glass_engine* e) {
     if ((rc = finalize_preprocess(e))) return rc;
     if ((rc = finalize_lpips(e))) return rc;
     if ((rc = alloc_buffers(e))) return rc;
+    if ((rc = alloc_search(e))) return rc;
     e->host.clear();  // host copies no longer needed
     e->finalized = true;
     return GLASS_OK;
@@ -578,26 +579,8 @@ GemmParams gemm_params(const half_t* a, const half_t* w, int M, int N, int K, co
 // ------------------------------------------------------------------------------------
 // the pass
 // ------------------------------------------------------------------------------------
-// The end of a pass for both generators, on e->cur (the main stream): CLIP unless it already ran on the second stream (clip_done; the main
-// stream waits for it), F, the copy, the wait, the launchers' verdict, the profile.  d_join: the stream the discriminator's head is on when
-// that is not the main one (stream mode 1); joined behind CLIP.
-static int finish_pass(glass_engine* e, int P, float* out_F, bool clip_done, hipStream_t d_join) {
-    const glass_config& c = e->cfg;
-    if (out_F) {
-        if (!clip_done) run_clip(e, pass_images(e, P), e->views);
-        if (d_join) {   // join: D head finished
-            GLASS_HIP(hipEventRecord(e->ev_g[0], d_join));
-            GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_g[0], 0));
-        }
-        if (e->pset.T > 0 && e->pset.mode == 1)
-            launch_assemble_F_set(e->pset.d_sim, e->pset.d_weights, c.use_discriminator ? e->d_dis : nullptr, c.lpips_size ? e->lp.d : nullptr, e->pset.T, P,
-                                  e->d_F, e->cur);
-        else if (c.lpips_size) launch_assemble_F_lpips(e->d_sim, e->d_dis, e->lp.d, c.lpips_lambda, c.use_discriminator ? 1 : 0, P, c.n_obj, e->d_F, e->cur);
-        else launch_assemble_F(e->d_sim, e->d_dis, P, c.n_obj, e->d_F, e->cur);
-        GLASS_HIP(hipMemcpyAsync(e->h_pinned, e->d_F, (size_t)P * c.n_obj * sizeof(float), hipMemcpyDeviceToHost,
-                                 e->cur));
-    }
-    GLASS_HIP(hipEventRecord(e->ev1, e->cur));
+// The wait at the end of a pass: the stream, the launchers' verdict, the profile.
+int wait_pass(glass_engine* e, int P) {
     GLASS_HIP(hipStreamSynchronize(e->cur));
     GLASS_HIP(hipGetLastError());
     GLASS_HIP(hipEventElapsedTime(&e->last_ms, e->ev0, e->ev1));
@@ -608,15 +591,45 @@ static int finish_pass(glass_engine* e, int P, float* out_F, bool clip_done, hip
         glass_set_error(msg);
         return GLASS_ERR_STATE;
     }
-    if (out_F) memcpy(out_F, e->h_pinned, (size_t)P * c.n_obj * sizeof(float));
     e->last_P = P;
     if (e->profiling) collect_profile(e);
     return GLASS_OK;
 }
 
-static int run_pass(glass_engine* e, const float* latents, int P, int generation, int first_mb,
-                    const glass_noise* noise, float* out_F, float* images) {
-    REQUIRE(e && latents, GLASS_ERR_ARG, "null argument");
+// The end of a pass for both generators, on e->cur (the main stream): CLIP unless it already ran on the second stream (clip_done; the main
+// stream waits for it), F, the copy, the wait, the launchers' verdict, the profile.  d_join: the stream the discriminator's head is on when
+// that is not the main one (stream mode 1); joined behind CLIP.
+// out_F: the rows are copied back to the host and the call waits.  d_F_dst (the device search): they are copied to that device buffer on the
+// stream instead, and with no_wait the stream is left running — the caller launches survival behind the pass and calls wait_pass once.
+static int finish_pass(glass_engine* e, int P, float* out_F, bool clip_done, hipStream_t d_join, float* d_F_dst = nullptr, bool no_wait = false) {
+    const glass_config& c = e->cfg;
+    if (out_F || d_F_dst) {
+        if (!clip_done) run_clip(e, pass_images(e, P), e->views);
+        if (d_join) {   // join: D head finished
+            GLASS_HIP(hipEventRecord(e->ev_g[0], d_join));
+            GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_g[0], 0));
+        }
+        if (e->pset.T > 0 && e->pset.mode == 1)
+            launch_assemble_F_set(e->pset.d_sim, e->pset.d_weights, c.use_discriminator ? e->d_dis : nullptr, c.lpips_size ? e->lp.d : nullptr, e->pset.T, P,
+                                  e->d_F, e->cur);
+        else if (c.lpips_size) launch_assemble_F_lpips(e->d_sim, e->d_dis, e->lp.d, c.lpips_lambda, c.use_discriminator ? 1 : 0, P, c.n_obj, e->d_F, e->cur);
+        else launch_assemble_F(e->d_sim, e->d_dis, P, c.n_obj, e->d_F, e->cur);
+        if (d_F_dst)
+            GLASS_HIP(hipMemcpyAsync(d_F_dst, e->d_F, (size_t)P * c.n_obj * sizeof(float), hipMemcpyDeviceToDevice, e->cur));
+        else
+            GLASS_HIP(hipMemcpyAsync(e->h_pinned, e->d_F, (size_t)P * c.n_obj * sizeof(float), hipMemcpyDeviceToHost, e->cur));
+    }
+    GLASS_HIP(hipEventRecord(e->ev1, e->cur));
+    if (no_wait) return GLASS_OK;
+    if (int rc = wait_pass(e, P)) return rc;
+    if (out_F) memcpy(out_F, e->h_pinned, (size_t)P * c.n_obj * sizeof(float));
+    return GLASS_OK;
+}
+
+int run_pass(glass_engine* e, const float* latents, int P, int generation, int first_mb, const glass_noise* noise, float* host_F, float* images,
+             const float* d_latents, float* d_F_dst, bool no_wait) {
+    REQUIRE(e && (latents || d_latents), GLASS_ERR_ARG, "null argument");
+    const bool out_F = host_F || d_F_dst;      // a scoring pass
     REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first (weights not loaded)");
     const glass_config& c = e->cfg;
     REQUIRE(P > 0 && P <= c.max_pop, GLASS_ERR_ARG, "population size out of range (max_pop)");
@@ -633,9 +646,15 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
     // the rows go where run_styles reads them: z rows in front of the mapping network, w rows in its output's place, w+ rows per layer
     const size_t row = latent_row_floats(e);
     float* d_rows = e->latent_space == GLASS_LATENT_WPLUS ? e->d_dlat : e->latent_space == GLASS_LATENT_W ? e->d_w0 : e->d_z;
-    memcpy(e->h_pinned, latents, (size_t)P * row * sizeof(float));
+    if (latents) memcpy(e->h_pinned, latents, (size_t)P * row * sizeof(float));
     GLASS_HIP(hipEventRecord(e->ev0, e->cur));
-    GLASS_HIP(hipMemcpyAsync(d_rows, e->h_pinned, (size_t)P * row * sizeof(float), hipMemcpyHostToDevice, e->cur));
+    if (latents) {
+        GLASS_HIP(hipMemcpyAsync(d_rows, e->h_pinned, (size_t)P * row * sizeof(float), hipMemcpyHostToDevice, e->cur));
+        e->latent_uploads += 1;
+        e->latent_upload_rows += P;
+    } else {      // the device search's rows: already on the device
+        GLASS_HIP(hipMemcpyAsync(d_rows, d_latents, (size_t)P * row * sizeof(float), hipMemcpyDeviceToDevice, e->cur));
+    }
     const int ps = c.clip_patch, G = c.clip_res / ps;
     const size_t img_elems = (size_t)3 * e->R * e->R;
     // crop views: the boxes of this pass, from (noise_seed, generation) alone — first_mb plays no part, so shards and slices of a population
@@ -669,7 +688,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
             }
             if (lpips) run_lpips_chunk(e, y, c0, B);
         }
-        return finish_pass(e, P, out_F, false, nullptr);
+        return finish_pass(e, P, host_F, false, nullptr, d_F_dst, no_wait);
     }
     // device-generated noise planes depend on nothing but (seed, generation, minibatch, layer): their 17 short launches run on the
     // second stream next to the mapping network / style / demodulation chain instead of ahead of it
@@ -788,7 +807,7 @@ static int run_pass(glass_engine* e, const float* latents, int P, int generation
         if (clip_ov) GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_d[0], 0));   // join: CLIP finished on the second stream
     }
     e->cur = e->stream;
-    return finish_pass(e, P, out_F, clip_ov, overlap ? sd : nullptr);
+    return finish_pass(e, P, host_F, clip_ov, overlap ? sd : nullptr, d_F_dst, no_wait);
 }
 
 extern "C" int glass_engine_evaluate(glass_engine* e, const float* latents, int32_t P, int32_t generation,

@@ -280,6 +280,17 @@ struct glass_engine {
         float W = 0.f;                      // sum |w_t|
         float *d_targets = nullptr, *d_weights = nullptr, *d_sim = nullptr;    // [16][clip_embed], [16], [max_pop][16] (rows of T in use)
     } pset;
+    // ---- device search (glass_engine_set_search; pop 0: off — nothing below is allocated or touched) ----
+    struct Search {
+        int nsga = 0, n_var = 0, cur = 0;   // cur: which of X[2] holds the population
+        GaParams g = {};                    // g.pop 0: off
+        bool ready = false;                 // search_init has run
+        int varied_gen = -1;                // the generation whose offspring Xoff holds
+        float *X[2] = {nullptr, nullptr}, *Xoff = nullptr, *F = nullptr;   // [pop][n_var] x 3; F [2 pop][n_obj]: population rows, then offspring rows
+        int *rank = nullptr, *flags = nullptr, *chosen = nullptr, *counts = nullptr;
+        double* cd = nullptr;
+    } search;
+    long long latent_uploads = 0, latent_upload_rows = 0;   // host-to-device latent copies of the pass so far (glass_engine_latent_uploads)
 };
 
 // ------------------------------------------------------------------------------------
@@ -457,6 +468,17 @@ std::vector<float> transposed(const float* W, int N, int K, float coef);
 
 
 // ---- perceptual objective (lpips.cpp) ----
+// ---- the pass (engine.cpp) and the device search around it (search.cpp) ----
+// latents: host rows, uploaded — or nullptr with d_latents: device rows, copied on the stream.  host_F: the rows are copied back and the
+// call waits — or nullptr with d_F_dst: they are copied to that device buffer; no_wait then leaves the stream running (finish_search_pass
+// waits once, behind whatever the caller launched after the pass)
+#pragma GCC visibility push(hidden)
+int run_pass(glass_engine* e, const float* latents, int P, int generation, int first_mb, const glass_noise* noise, float* host_F, float* images,
+             const float* d_latents = nullptr, float* d_F_dst = nullptr, bool no_wait = false);
+int wait_pass(glass_engine* e, int P);        // the wait no_wait left out: synchronise, the launchers' verdict, the profile
+int alloc_search(glass_engine* e);            // the search's buffers (nothing without glass_engine_set_search)
+#pragma GCC visibility pop
+
 int finalize_lpips(glass_engine* e);          // weights -> device layouts + buffers (nothing with lpips_size 0)
 // d[c0 + i] for the B candidates whose raw images are at y [B][3][R][R], on e->cur: box mean + VGG16 + head against the stored target
 void run_lpips_chunk(glass_engine* e, const float* y, int c0, int B);

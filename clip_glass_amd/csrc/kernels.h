@@ -177,6 +177,31 @@ float prompt_weight_sum(const float* weights, int T);      // sum |w_t| in fp32,
 // F [P][K + (dis != 0) + (lp != 0)]: F[p][t] = w_t < 0 ? set_sim[p][t] : -set_sim[p][t], then relu(1 - dis), then lp (nullable each)
 void launch_assemble_F_set(const float* set_sim, const float* weights, const float* dis, const float* lp, int K, int P, float* F, hipStream_t st);
 
+// --- device search (search.hip; include/glass.h "Device search") ---
+#define GLASS_SEARCH_MAX_POP 1024      // population rows (2048 merged rows in survival)
+#define GLASS_SEARCH_MAX_OBJ 6
+#define GLASS_SEARCH_TAG 0x53524348u   // XOR-ed into the Philox key's high word: the search's own stream
+#define GLASS_SEARCH_DRAW_TOURNAMENT 0u   // purpose words (the counter's fourth): index = mating, variable = 0
+#define GLASS_SEARCH_DRAW_SBX 1u          // index = mating
+#define GLASS_SEARCH_DRAW_MUTATION 2u     // index = offspring row
+struct GaParams {
+    int pop;
+    double xl, xu, eta_c, eta_m, prob_m;
+    uint64_t seed;
+};
+// Every launcher returns the name of the kernel it launched, or nullptr: a shape outside the limits, nothing launched.
+// offspring rows [row0, row0 + rows) of generation `generation` from the population X [pop][n_var] with rank [pop], cd [pop] -> Xoff rows
+const char* launch_ga_vary(const float* X, const int* rank, const double* cd, const GaParams& g, int n_var, int generation, int row0, int rows,
+                           float* Xoff, hipStream_t st);
+// flags[r] = 1: Xoff row r equals, by value in every variable, a row of X [pop] or an Xoff row below r
+const char* launch_ga_duplicates(const float* X, const float* Xoff, int pop, int n_off, int n_var, int* flags, hipStream_t st);
+// survival over F [n_pop + n_off][n_obj] (population first; flags [n_off] nullable): chosen / rank_out / cd_out [pop_out], F's first pop_out
+// rows rewritten as the survivors', counts = {flagged, non-finite rows}.  One workgroup; nsga 0: GA
+const char* launch_ga_survive(float* F, const int* flags, int n_pop, int n_off, int n_obj, int pop_out, int nsga, int* chosen, int* rank_out,
+                              double* cd_out, int* counts, hipStream_t st);
+void launch_ga_gather(const float* X, const float* Xoff, const int* chosen, int n_pop, int pop_out, int n_var, float* Xnext, hipStream_t st);
+size_t ga_survive_lds_bytes(int n_rows, int n_obj);
+
 // --- perceptual objective: LPIPS on VGG16 (lpips.hip); the 3 x 3 convolutions behind the first are gemm_tiled (mode 5, A = 1, S = bias) ---
 #define GLASS_LPIPS_PIXB 256      // pixels of one image a workgroup of the head owns
 // box mean R -> S (R % S == 0, box <= 8) of planar fp32 y [B][3][R][R], then (v - shift_c) / scale_c -> [B][S][S][4] fp16 (channel 3 = 0)

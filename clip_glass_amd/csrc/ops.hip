@@ -1483,3 +1483,90 @@ extern "C" int glass_host_gpt2_gemm_choice(int32_t M, int32_t N, int32_t K, int3
     *NK = c.NK;
     return GLASS_OK;
 }
+
+// ---- device search (search.hip) ---------------------------------------------------------------------------------------------------
+extern "C" int glass_op_ga_vary(int32_t device, int32_t pop, int32_t n_var, const float* X, const int32_t* rank, const double* cd, double xl, double xu,
+                                double eta_c, double eta_m, double prob_m, uint64_t seed, int32_t generation, int32_t row0, int32_t rows, float* out) {
+    OPREQ(X && rank && cd && out, "null argument");
+    if (int rc = glass_search_supported(pop, n_var, 1, GLASS_SEARCH_NSGA2)) return rc;
+    OPREQ(rows > 0 && row0 >= 0 && row0 + rows <= pop, "ga_vary: [row0, row0 + rows) must lie inside the pop offspring rows");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t xn = (size_t)pop * n_var;
+    float* dX = dv.up32(X, xn);
+    int* dr = dv.alloc<int>(pop); double* dc = dv.alloc<double>(pop);
+    float* dO = dv.alloc<float>(xn + 4);      // every offspring row, and four guard elements behind them
+    OPREQ(dX && dr && dc && dO, "device allocation failed");
+    GLASS_HIP(hipMemcpy(dr, rank, (size_t)pop * sizeof(int), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemcpy(dc, cd, (size_t)pop * sizeof(double), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemset(dO, 0xFF, (xn + 4) * sizeof(float)));
+    GaParams g;
+    g.pop = pop; g.xl = xl; g.xu = xu; g.eta_c = eta_c; g.eta_m = eta_m; g.prob_m = prob_m; g.seed = seed;
+    OPREQ(launch_ga_vary(dX, dr, dc, g, n_var, generation, row0, rows, dO, 0), "ga_vary refused the shape");
+    int rc = finish();
+    if (rc) return rc;
+    uint32_t guard[4];
+    GLASS_HIP(hipMemcpy(guard, dO + xn, sizeof guard, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) OPREQ(guard[i] == 0xFFFFFFFFu, "ga_vary stored past the last row");
+    GLASS_HIP(hipMemcpy(out, dO + (size_t)row0 * n_var, (size_t)rows * n_var * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_ga_duplicates(int32_t device, int32_t pop, int32_t n_off, int32_t n_var, const float* X, const float* Xoff, int32_t* flags) {
+    OPREQ(X && Xoff && flags, "null argument");
+    OPREQ(pop >= 1 && pop <= GLASS_SEARCH_MAX_POP && n_off >= 1 && n_off <= GLASS_SEARCH_MAX_POP && n_var >= 1, "ga_duplicates: pop and n_off in [1, 1024]");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    float* dX = dv.up32(X, (size_t)pop * n_var); float* dO = dv.up32(Xoff, (size_t)n_off * n_var);
+    int* df = dv.alloc<int>(n_off + 4);
+    OPREQ(dX && dO && df, "device allocation failed");
+    GLASS_HIP(hipMemset(df, 0xFF, (size_t)(n_off + 4) * sizeof(int)));
+    OPREQ(launch_ga_duplicates(dX, dO, pop, n_off, n_var, df, 0), "ga_duplicates refused the shape");
+    int rc = finish();
+    if (rc) return rc;
+    uint32_t guard[4];
+    GLASS_HIP(hipMemcpy(guard, df + n_off, sizeof guard, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) OPREQ(guard[i] == 0xFFFFFFFFu, "ga_duplicates stored past row n_off");
+    GLASS_HIP(hipMemcpy(flags, df, (size_t)n_off * sizeof(int), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off, int32_t n_obj, int32_t pop_out, int32_t nsga, const float* F,
+                                   const int32_t* flags, int32_t* chosen, int32_t* rank, double* cd, float* F_out, int32_t* counts, int32_t n_var,
+                                   const float* X, const float* Xoff, float* X_out) {
+    OPREQ(F && chosen && rank && cd && F_out && counts, "null argument");
+    OPREQ(n_pop >= 1 && n_off >= 0 && n_obj >= 1 && pop_out >= 1, "ga_survive: bad sizes");
+    const bool gather = X != nullptr;
+    OPREQ(!gather || (X_out && n_var >= 1 && (Xoff || n_off == 0)), "ga_survive: X needs Xoff, X_out and n_var");
+    GLASS_HIP(hipSetDevice(device));
+    Dev dv;
+    const size_t N = (size_t)n_pop + n_off;
+    float* dF = dv.up32(F, N * n_obj);
+    int* dfl = flags && n_off ? dv.alloc<int>(n_off) : nullptr;
+    int* dch = dv.alloc<int>(pop_out + 4); int* drk = dv.alloc<int>(pop_out); double* dcd = dv.alloc<double>(pop_out); int* dcn = dv.alloc<int>(2);
+    OPREQ(dF && dch && drk && dcd && dcn && (!(flags && n_off) || dfl), "device allocation failed");
+    if (dfl) GLASS_HIP(hipMemcpy(dfl, flags, (size_t)n_off * sizeof(int), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemset(dch, 0xFF, (size_t)(pop_out + 4) * sizeof(int)));
+    OPREQ(launch_ga_survive(dF, dfl, n_pop, n_off, n_obj, pop_out, nsga, dch, drk, dcd, dcn, 0),
+          "ga_survive refused the shape (up to 2048 merged rows, 6 objectives, pop_out <= 1024 and <= the merged rows)");
+    float* dXo = nullptr;
+    if (gather) {
+        float* dX = dv.up32(X, (size_t)n_pop * n_var); float* dO = n_off ? dv.up32(Xoff, (size_t)n_off * n_var) : nullptr;
+        dXo = dv.alloc<float>((size_t)pop_out * n_var);
+        OPREQ(dX && dXo && (!n_off || dO), "device allocation failed");
+        GLASS_HIP(hipMemset(dXo, 0xFF, (size_t)pop_out * n_var * sizeof(float)));
+        launch_ga_gather(dX, dO, dch, n_pop, pop_out, n_var, dXo, 0);
+    }
+    int rc = finish();
+    if (rc) return rc;
+    uint32_t guard[4];
+    GLASS_HIP(hipMemcpy(guard, dch + pop_out, sizeof guard, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) OPREQ(guard[i] == 0xFFFFFFFFu, "ga_survive stored past slot pop_out");
+    GLASS_HIP(hipMemcpy(chosen, dch, (size_t)pop_out * sizeof(int), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(rank, drk, (size_t)pop_out * sizeof(int), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(cd, dcd, (size_t)pop_out * sizeof(double), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(F_out, dF, (size_t)pop_out * n_obj * sizeof(float), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(counts, dcn, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    if (gather) GLASS_HIP(hipMemcpy(X_out, dXo, (size_t)pop_out * n_var * sizeof(float), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}

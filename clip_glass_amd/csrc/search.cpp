@@ -1,0 +1,232 @@
+// search.cpp — the device search's entry points (include/glass.h "Device search"): the population stays in device buffers and a generation is
+// variation, one scoring pass and survival on the engine's stream with one wait at its end.  Kernels: search.hip.
+#include <math.h>
+#include <string.h>
+
+#include <string>
+
+#include "engine.h"
+
+extern "C" int glass_search_supported(int32_t pop, int32_t n_var, int32_t n_obj, int32_t algorithm) {
+    REQUIRE(algorithm == GLASS_SEARCH_GA || algorithm == GLASS_SEARCH_NSGA2, GLASS_ERR_ARG, "device search: algorithm must be 0 (ga) or 1 (nsga2)");
+    REQUIRE(pop >= 2 && pop <= GLASS_SEARCH_MAX_POP, GLASS_ERR_ARG,
+            "device search: pop must be in [2, " + std::to_string(GLASS_SEARCH_MAX_POP) + "] (survival ranks 2 pop merged rows in one workgroup), got " +
+                std::to_string(pop));
+    REQUIRE(n_var >= 1 && (long long)n_var * pop < (1LL << 31), GLASS_ERR_ARG, "device search: n_var must be positive with pop * n_var below 2^31");
+    REQUIRE(n_obj >= 1 && n_obj <= GLASS_SEARCH_MAX_OBJ, GLASS_ERR_ARG,
+            "device search: n_obj must be in [1, " + std::to_string(GLASS_SEARCH_MAX_OBJ) + "], got " + std::to_string(n_obj));
+    REQUIRE(algorithm == GLASS_SEARCH_NSGA2 || n_obj == 1, GLASS_ERR_ARG, "device search: ga ranks by F[:, 0] alone and needs n_obj = 1 (use nsga2)");
+    return GLASS_OK;
+}
+
+// what the operators take, whichever setter brings it
+static int check_operators(const char* what, double xl, double xu, double eta_c, double eta_m, double prob_m) {
+    REQUIRE(isfinite(xl) && isfinite(xu) && xl < xu && (double)(float)xl == xl && (double)(float)xu == xu, GLASS_ERR_ARG,
+            std::string(what) + ": xl < xu, both finite and exact in fp32 (the rows are fp32 and are clipped to the bounds)");
+    REQUIRE(eta_c >= 0.0 && eta_m >= 0.0 && isfinite(eta_c) && isfinite(eta_m), GLASS_ERR_ARG, std::string(what) + ": eta_c and eta_m must be finite and >= 0");
+    REQUIRE(prob_m >= 0.0 && prob_m <= 1.0, GLASS_ERR_ARG, std::string(what) + ": prob_m must be in [0, 1]");
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_search(glass_engine* e, int32_t algorithm, int32_t pop, double xl, double xu, double eta_c, double eta_m,
+                                       double prob_m, uint64_t seed) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(!e->finalized, GLASS_ERR_STATE, "set_search: the engine is finalized (its buffers are sized in finalize: call it before)");
+    REQUIRE(e->cfg.generator != GLASS_GEN_BIGGAN_DEEP, GLASS_ERR_STATE,
+            "set_search: the device search varies real-valued rows; a BigGAN row holds boolean class bits (HUX / bit-flip): it keeps the host search");
+    REQUIRE(e->n_lat > 0, GLASS_ERR_STATE,
+            "set_search: the device search varies real-valued latent rows of a StyleGAN2 generator; this engine has none (GPT-2 rows are integers): "
+            "it keeps the host search");
+    REQUIRE(e->cfg.noise_mode != 2, GLASS_ERR_STATE, "set_search: caller-provided noise planes (noise_mode 2) come from the host every pass; use noise_mode 0 or 1");
+    if (int rc = glass_search_supported(pop, 1, e->cfg.n_obj, algorithm)) return rc;
+    REQUIRE(pop <= e->cfg.max_pop && pop % e->cfg.batch_size == 0, GLASS_ERR_ARG,
+            "set_search: pop must be a multiple of batch_size and at most max_pop (a generation's offspring are scored in one pass)");
+    if (int rc = check_operators("set_search", xl, xu, eta_c, eta_m, prob_m)) return rc;
+    glass_engine::Search& s = e->search;
+    s.nsga = algorithm == GLASS_SEARCH_NSGA2;
+    s.g.pop = pop;
+    s.g.xl = xl; s.g.xu = xu; s.g.eta_c = eta_c; s.g.eta_m = eta_m; s.g.prob_m = prob_m;
+    s.g.seed = seed;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_search_operators(glass_engine* e, double xl, double xu, double eta_c, double eta_m, double prob_m, uint64_t seed) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(e->search.g.pop > 0, GLASS_ERR_STATE, "set_search_operators: the device search is off (glass_engine_set_search before finalize)");
+    if (int rc = check_operators("set_search_operators", xl, xu, eta_c, eta_m, prob_m)) return rc;
+    GaParams& g = e->search.g;
+    g.xl = xl; g.xu = xu; g.eta_c = eta_c; g.eta_m = eta_m; g.prob_m = prob_m;
+    g.seed = seed;
+    return GLASS_OK;
+}
+
+int alloc_search(glass_engine* e) {
+    glass_engine::Search& s = e->search;
+    if (!s.g.pop) return GLASS_OK;
+    const int pop = s.g.pop, M = e->cfg.n_obj;
+    s.n_var = (int)latent_row_floats(e);
+    if (int rc = glass_search_supported(pop, s.n_var, M, s.nsga)) return rc;
+    int rc;
+    const size_t xn = (size_t)pop * s.n_var;
+    if ((rc = dev_alloc(e, &s.X[0], xn))) return rc;
+    if ((rc = dev_alloc(e, &s.X[1], xn))) return rc;
+    if ((rc = dev_alloc(e, &s.Xoff, xn))) return rc;
+    if ((rc = dev_alloc(e, &s.F, (size_t)2 * pop * M))) return rc;
+    if ((rc = dev_alloc(e, &s.rank, (size_t)pop))) return rc;
+    if ((rc = dev_alloc(e, &s.cd, (size_t)pop))) return rc;
+    if ((rc = dev_alloc(e, &s.flags, (size_t)pop))) return rc;
+    if ((rc = dev_alloc(e, &s.chosen, (size_t)pop))) return rc;
+    if ((rc = dev_alloc(e, &s.counts, (size_t)2))) return rc;
+    GLASS_HIP(hipMemset(s.flags, 0, (size_t)pop * sizeof(int)));
+    GLASS_HIP(hipMemset(s.counts, 0, 2 * sizeof(int)));
+    GLASS_HIP(hipMemset(s.F, 0, (size_t)2 * pop * M * sizeof(float)));
+    return GLASS_OK;
+}
+
+namespace {
+int search_ready(glass_engine* e, const char* what, bool need_init) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(e->finalized, GLASS_ERR_STATE, std::string(what) + ": finalize() first");
+    REQUIRE(e->search.g.pop > 0, GLASS_ERR_STATE, std::string(what) + ": the device search is off (glass_engine_set_search before finalize)");
+    if (need_init) REQUIRE(e->search.ready, GLASS_ERR_STATE, std::string(what) + ": search_init() first (there is no population on the device)");
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    e->cur = e->stream;
+    return GLASS_OK;
+}
+// the launches of the three phases, on e->cur; nothing here waits
+void launch_vary(glass_engine* e, int generation) {
+    glass_engine::Search& s = e->search;
+    const int pop = s.g.pop;
+    const double xbytes = (double)pop * s.n_var * sizeof(float);
+    {
+        Prof pr(e, "search.vary", 0, 3 * xbytes);
+        const char* k = launch_ga_vary(s.X[s.cur], s.rank, s.cd, s.g, s.n_var, generation, 0, pop, s.Xoff, e->cur);
+        if (k) pr.ran("search.vary", k);
+        else { pr.drop(); e->launch_error = "search.vary: the launcher refused the shape"; }
+    }
+    {
+        Prof pr(e, "search.duplicates", 0, 2 * xbytes);
+        const char* k = launch_ga_duplicates(s.X[s.cur], s.Xoff, pop, pop, s.n_var, s.flags, e->cur);
+        if (k) pr.ran("search.duplicates", k);
+        else { pr.drop(); e->launch_error = "search.duplicates: the launcher refused the shape"; }
+    }
+    s.varied_gen = generation;
+}
+void launch_survive(glass_engine* e, int n_off) {
+    glass_engine::Search& s = e->search;
+    const int pop = s.g.pop;
+    Prof pr(e, "search.survive", 0, 2.0 * pop * s.n_var * sizeof(float));
+    const char* k = launch_ga_survive(s.F, n_off ? s.flags : nullptr, pop, n_off, e->cfg.n_obj, pop, s.nsga, s.chosen, s.rank, s.cd, s.counts, e->cur);
+    if (!k) {
+        pr.drop();
+        e->launch_error = "search.survive: the launcher refused the shape (or the device offers too little LDS)";
+        return;
+    }
+    pr.ran("search.survive", k);
+    launch_ga_gather(s.X[s.cur], s.Xoff, s.chosen, pop, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
+    s.cur ^= 1;
+}
+// the wait behind launches made outside a pass
+int search_wait(glass_engine* e) {
+    GLASS_HIP(hipStreamSynchronize(e->cur));
+    GLASS_HIP(hipGetLastError());
+    if (e->profiling) collect_profile(e);
+    if (!e->launch_error.empty()) {
+        const std::string msg = e->launch_error;
+        e->launch_error.clear();
+        glass_set_error(msg);
+        return GLASS_ERR_STATE;
+    }
+    return GLASS_OK;
+}
+int check_rows(glass_engine* e, const char* what, int generation, int first_row, int rows) {
+    const glass_engine::Search& s = e->search;
+    REQUIRE(s.varied_gen == generation, GLASS_ERR_STATE,
+            std::string(what) + ": the offspring buffer holds generation " + std::to_string(s.varied_gen) + " (search_vary of this generation first)");
+    REQUIRE(rows > 0 && first_row >= 0 && first_row + rows <= s.g.pop && first_row % e->cfg.batch_size == 0 && rows % e->cfg.batch_size == 0,
+            GLASS_ERR_ARG, std::string(what) + ": [first_row, first_row + rows) must be whole minibatches inside the offspring rows");
+    return GLASS_OK;
+}
+}  // namespace
+
+extern "C" int glass_engine_search_init(glass_engine* e, const float* X0) {
+    if (int rc = search_ready(e, "search_init", false)) return rc;
+    REQUIRE(X0, GLASS_ERR_ARG, "search_init: null population");
+    glass_engine::Search& s = e->search;
+    const int pop = s.g.pop;
+    s.ready = false;
+    s.cur = 0;
+    s.varied_gen = -1;
+    GLASS_HIP(hipMemcpy(s.X[0], X0, (size_t)pop * s.n_var * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = run_pass(e, nullptr, pop, 0, 0, nullptr, nullptr, nullptr, s.X[0], s.F, true)) return rc;
+    launch_survive(e, 0);      // ranks (and orders) the initial population, as minimize's first survive() does
+    if (int rc = wait_pass(e, pop)) return rc;
+    int counts[2];
+    GLASS_HIP(hipMemcpy(counts, s.counts, sizeof counts, hipMemcpyDeviceToHost));
+    REQUIRE(counts[1] == 0, GLASS_ERR_STATE,
+            "search_init: " + std::to_string(counts[1]) + " rows of the initial population have a non-finite F: a population row is never left out");
+    s.ready = true;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_search_vary(glass_engine* e, int32_t generation) {
+    if (int rc = search_ready(e, "search_vary", true)) return rc;
+    e->launch_error.clear();
+    launch_vary(e, generation);
+    return search_wait(e);
+}
+
+extern "C" int glass_engine_search_evaluate(glass_engine* e, int32_t generation, int32_t first_row, int32_t rows) {
+    if (int rc = search_ready(e, "search_evaluate", true)) return rc;
+    if (int rc = check_rows(e, "search_evaluate", generation, first_row, rows)) return rc;
+    glass_engine::Search& s = e->search;
+    return run_pass(e, nullptr, rows, generation, first_row / e->cfg.batch_size, nullptr, nullptr, nullptr, s.Xoff + (size_t)first_row * s.n_var,
+                    s.F + (size_t)(s.g.pop + first_row) * e->cfg.n_obj, false);
+}
+
+extern "C" int glass_engine_search_survive(glass_engine* e, int32_t generation) {
+    if (int rc = search_ready(e, "search_survive", true)) return rc;
+    REQUIRE(e->search.varied_gen == generation, GLASS_ERR_STATE, "search_survive: search_vary and search_evaluate of this generation first");
+    e->launch_error.clear();
+    launch_survive(e, e->search.g.pop);
+    e->search.varied_gen = -1;      // the offspring are spent: the next survival needs a new search_vary
+    return search_wait(e);
+}
+
+extern "C" int glass_engine_search_step(glass_engine* e, int32_t generation) {
+    if (int rc = search_ready(e, "search_step", true)) return rc;
+    glass_engine::Search& s = e->search;
+    const int pop = s.g.pop;
+    e->launch_error.clear();
+    launch_vary(e, generation);
+    const std::string refused = e->launch_error;      // (run_pass clears the message on entry)
+    if (int rc = run_pass(e, nullptr, pop, generation, 0, nullptr, nullptr, nullptr, s.Xoff, s.F + (size_t)pop * e->cfg.n_obj, true)) return rc;
+    if (!refused.empty()) e->launch_error = refused;
+    launch_survive(e, pop);
+    s.varied_gen = -1;
+    return wait_pass(e, pop);
+}
+
+extern "C" int glass_engine_search_read(glass_engine* e, float* pop_X, float* pop_F, int32_t* rank, double* cd, float* off_X, float* off_F,
+                                        int32_t* flags, int32_t* counts) {
+    if (int rc = search_ready(e, "search_read", true)) return rc;
+    const glass_engine::Search& s = e->search;
+    const size_t pop = (size_t)s.g.pop, xb = pop * s.n_var * sizeof(float), fb = pop * e->cfg.n_obj * sizeof(float);
+    GLASS_HIP(hipStreamSynchronize(e->stream));
+    if (pop_X) GLASS_HIP(hipMemcpy(pop_X, s.X[s.cur], xb, hipMemcpyDeviceToHost));
+    if (pop_F) GLASS_HIP(hipMemcpy(pop_F, s.F, fb, hipMemcpyDeviceToHost));
+    if (rank) GLASS_HIP(hipMemcpy(rank, s.rank, pop * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (cd) GLASS_HIP(hipMemcpy(cd, s.cd, pop * sizeof(double), hipMemcpyDeviceToHost));
+    if (off_X) GLASS_HIP(hipMemcpy(off_X, s.Xoff, xb, hipMemcpyDeviceToHost));
+    if (off_F) GLASS_HIP(hipMemcpy(off_F, s.F + pop * e->cfg.n_obj, fb, hipMemcpyDeviceToHost));
+    if (flags) GLASS_HIP(hipMemcpy(flags, s.flags, pop * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (counts) GLASS_HIP(hipMemcpy(counts, s.counts, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_latent_uploads(glass_engine* e, int64_t* calls, int64_t* rows) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    if (calls) *calls = e->latent_uploads;
+    if (rows) *rows = e->latent_upload_rows;
+    return GLASS_OK;
+}

@@ -1,0 +1,342 @@
+// search.hip — the GA / NSGA-II generation step on the device (include/glass.h "Device search"): binary tournament + bounded SBX +
+// polynomial mutation (ga_vary_kernel), exact duplicate flags (ga_duplicates_kernel), rank-and-crowding / fitness survival in ONE
+// workgroup (ga_survive_kernel) and the gather of the surviving rows (ga_gather_kernel).  Numpy mirror: tests/search_device_ref.py.
+#include <math.h>
+
+#include "../../include/glass.h"
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+// ---- draws: u = (word + 0.5) 2^-32 of Philox4x32-10 at counter (index, variable, generation, purpose) under (seed_lo, seed_hi ^ tag) ----
+struct Draw4 { double u[4]; };
+__device__ __forceinline__ Draw4 ga_draw(const GaParams& g, uint32_t index, uint32_t var, uint32_t generation, uint32_t purpose) {
+    uint32_t c[4] = {index, var, generation, purpose};
+    philox4x32_10(c, (uint32_t)(g.seed & 0xFFFFFFFFu), (uint32_t)(g.seed >> 32) ^ GLASS_SEARCH_TAG);
+    Draw4 d;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d.u[i] = ((double)c[i] + 0.5) * (1.0 / 4294967296.0);
+    return d;
+}
+
+// the winner of a binary tournament between rows a and b: lower rank, then larger crowding distance, `>=` going to a (search.py:221)
+__device__ __forceinline__ int ga_better(const int* rank, const double* cd, int a, int b) {
+    const int ra = rank[a], rb = rank[b];
+    return (ra < rb || (ra == rb && cd[a] >= cd[b])) ? a : b;
+}
+__device__ __forceinline__ void ga_parents(const GaParams& g, const int* rank, const double* cd, int m, uint32_t generation, int* pa, int* pb) {
+    const Draw4 d = ga_draw(g, (uint32_t)m, 0u, generation, GLASS_SEARCH_DRAW_TOURNAMENT);
+    int idx[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) idx[i] = min((int)floor(d.u[i] * (double)g.pop), g.pop - 1);
+    *pa = ga_better(rank, cd, idx[0], idx[1]);
+    *pb = ga_better(rank, cd, idx[2], idx[3]);
+}
+
+// One variable of one offspring row: the child of (pa, pb) this row keeps (child 0: the first, 1: the second), mutated, rounded ONCE to
+// fp32.  Double arithmetic in search.py's own order of operations, without fused multiply-adds: a float64 mirror then agrees to the last
+// bits of pow().
+__device__ float ga_vary_one(const GaParams& g, float paf, float pbf, int m, int r, int j, uint32_t generation) {
+#pragma clang fp contract(off)
+    const double pa = (double)paf, pb = (double)pbf, xl = g.xl, xu = g.xu;
+    const Draw4 s = ga_draw(g, (uint32_t)m, (uint32_t)j, generation, GLASS_SEARCH_DRAW_SBX);      // u[0] beta, u[1] swap, u[2] per-variable gate
+    const double y1 = fmin(pa, pb), y2 = fmax(pa, pb);
+    double x = (r & 1) ? pb : pa;
+    if (s.u[2] < 0.5 && (y2 - y1) > 1e-14) {
+        const double d = fmax(y2 - y1, 1e-300), u = s.u[0], ex = 1.0 / (g.eta_c + 1.0);
+        const double bound1 = 1.0 + 2.0 * (y1 - xl) / d, bound2 = 1.0 + 2.0 * (xu - y2) / d;
+        const double alpha1 = 2.0 - pow(bound1, -(g.eta_c + 1.0)), alpha2 = 2.0 - pow(bound2, -(g.eta_c + 1.0));
+        const double bq1 = u <= 1.0 / alpha1 ? pow(u * alpha1, ex) : pow(1.0 / fmax(2.0 - u * alpha1, 1e-300), ex);
+        const double bq2 = u <= 1.0 / alpha2 ? pow(u * alpha2, ex) : pow(1.0 / fmax(2.0 - u * alpha2, 1e-300), ex);
+        const double c1 = fmin(fmax(0.5 * ((y1 + y2) - bq1 * d), xl), xu);
+        const double c2 = fmin(fmax(0.5 * ((y1 + y2) + bq2 * d), xl), xu);
+        const bool swap = s.u[1] < 0.5;
+        x = ((r & 1) != 0) == swap ? c1 : c2;      // child 0 keeps c1 unless swapped, child 1 keeps c2 unless swapped
+    }
+    const Draw4 q = ga_draw(g, (uint32_t)r, (uint32_t)j, generation, GLASS_SEARCH_DRAW_MUTATION);  // u[0] the perturbation, u[1] the gate
+    if (q.u[1] < g.prob_m) {
+        const double span = xu - xl, u = q.u[0], ep = g.eta_m + 1.0, mpow = 1.0 / ep;
+        const double d1 = (x - xl) / span, d2 = (xu - x) / span;
+        const double dq = u <= 0.5 ? pow(2.0 * u + (1.0 - 2.0 * u) * pow(1.0 - d1, ep), mpow) - 1.0
+                                   : 1.0 - pow(2.0 * (1.0 - u) + 2.0 * (u - 0.5) * pow(1.0 - d2, ep), mpow);
+        x = fmin(fmax(x + dq * span, xl), xu);
+    }
+    return (float)x;
+}
+
+// grid (ceil(n_var / (256 VEC)), rows): offspring row r = row0 + blockIdx.y is child r & 1 of mating r >> 1.  VEC 4 where n_var % 4 == 0
+// (every row is then 16-byte aligned), 1 otherwise.  Nothing depends on the grid: a draw is a function of (seed, generation, row, variable).
+template <int VEC>
+__global__ __launch_bounds__(256) void ga_vary_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
+                                                      GaParams g, int n_var, int generation, int row0, float* __restrict__ Xoff) {
+    const int r = row0 + blockIdx.y, m = r >> 1;
+    const int j0 = (blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (j0 >= n_var) return;
+    int ia, ib;
+    ga_parents(g, rank, cd, m, (uint32_t)generation, &ia, &ib);
+    const float* pa = X + (size_t)ia * n_var + j0;
+    const float* pb = X + (size_t)ib * n_var + j0;
+    float* out = Xoff + (size_t)r * n_var + j0;
+    if (VEC == 4) {
+        const f4 a = *(const f4*)pa, b = *(const f4*)pb;
+        f4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = ga_vary_one(g, a[i], b[i], m, r, j0 + i, (uint32_t)generation);
+        *(f4*)out = o;
+    } else {
+        out[0] = ga_vary_one(g, pa[0], pb[0], m, r, j0, (uint32_t)generation);
+    }
+}
+
+// One workgroup per offspring row r; its four waves walk the candidate rows (the population, then offspring rows BELOW r — "earlier" is the
+// row index, whatever the schedule).  A pair is compared 64 VEC variables at a time and left at the first chunk that differs, which for
+// unrelated rows is the first: the whole of both rows is read only for a pair that is equal.  Equality is by value (-0.0 == 0.0).
+template <int VEC>
+__global__ __launch_bounds__(256) void ga_duplicates_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, int pop, int n_var,
+                                                            int* __restrict__ flags) {
+    __shared__ int hit[4];
+    const int r = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float* a = Xoff + (size_t)r * n_var;
+    bool found = false;
+    for (int c = wave; c < pop + r && !found; c += 4) {
+        const float* b = c < pop ? X + (size_t)c * n_var : Xoff + (size_t)(c - pop) * n_var;
+        bool eq = true;
+        for (int j0 = 0; j0 < n_var && eq; j0 += 64 * VEC) {
+            const int j = j0 + lane * VEC;
+            bool ne = false;
+            if (j < n_var) {
+                if (VEC == 4) {
+                    const f4 va = *(const f4*)(a + j), vb = *(const f4*)(b + j);
+                    ne = !(va[0] == vb[0] && va[1] == vb[1] && va[2] == vb[2] && va[3] == vb[3]);
+                } else {
+                    ne = !(a[j] == b[j]);
+                }
+            }
+            eq = __ballot(ne) == 0ull;
+        }
+        found = eq;
+    }
+    if (lane == 0) hit[wave] = found ? 1 : 0;
+    __syncthreads();
+    if (threadIdx.x == 0) flags[r] = hit[0] | hit[1] | hit[2] | hit[3];
+}
+
+// ---- survival: one workgroup, everything in LDS -------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t ga_fkey(float f) {      // order-preserving bits of a float; -0.0 and 0.0 share a key (they tie, by index)
+    const uint32_t u = __float_as_uint(f + 0.0f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ void ga_sort(unsigned long long* keys, int N2) {      // bitonic, ascending; the keys are distinct (they end in the row index)
+    for (int k = 2; k <= N2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (N2 >> 1); t += blockDim.x) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long a = keys[i], b = keys[l];
+                if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[l] = a; }
+            }
+            __syncthreads();
+        }
+}
+__device__ __forceinline__ bool ga_dominates(const float* Fs, int M, int i, int j) {
+    bool all_le = true, any_lt = false;
+    for (int k = 0; k < M; ++k) {
+        const float a = Fs[i * M + k], b = Fs[j * M + k];
+        all_le = all_le && a <= b;
+        any_lt = any_lt || a < b;
+    }
+    return all_le && any_lt;
+}
+
+__host__ __device__ inline int ga_pow2(int n) { int p = 2; while (p < n) p <<= 1; return p; }
+
+// F [n_pop + n_off][M]: the population's rows, then the offspring's.  Left out of survival: offspring rows with a flag or a non-finite F.
+// Out: chosen [pop_out] merged indices in survival order (-1: fewer rows than pop_out were eligible), their rank and distance, and F's
+// first pop_out rows rewritten as the survivors' (the kernel has read all of F before it writes).  counts = {flagged, non-finite rows}.
+__global__ __launch_bounds__(1024) void ga_survive_kernel(float* __restrict__ F, const int* __restrict__ flags, int n_pop, int n_off, int M,
+                                                          int pop_out, int nsga, int* __restrict__ chosen, int* __restrict__ rank_out,
+                                                          double* __restrict__ cd_out, int* __restrict__ counts) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ int s_ncur, s_cnt[2];
+    const int N = n_pop + n_off, N2 = ga_pow2(N), T = blockDim.x, tid = threadIdx.x;
+    unsigned long long* keys = (unsigned long long*)smem;        // [N2]
+    double* cd = (double*)(keys + N2);                           // [N]
+    float* Fs = (float*)(cd + N);                                // [N][M]
+    int* rk = (int*)(Fs + (size_t)N * M);                        // [N]: front, -1 not ranked, -2 left out
+    int* nd = rk + N;                                            // [N]: rows that dominate it and are not ranked yet
+    int* cur = nd + N;                                           // [N]: the current front; later the survivors by slot
+    int* seg = cur + N;                                          // [N + 2]: first sorted position of every front
+    for (int i = tid; i < N * M; i += T) Fs[i] = F[i];
+    if (tid == 0) s_cnt[0] = s_cnt[1] = 0;
+    __syncthreads();
+    for (int i = tid; i < N; i += T) {
+        bool fin = true;
+        for (int k = 0; k < M; ++k) fin = fin && isfinite(Fs[i * M + k]);
+        const bool flg = i >= n_pop && flags && flags[i - n_pop] != 0;
+        if (flg) atomicAdd(&s_cnt[0], 1);
+        if (!fin) atomicAdd(&s_cnt[1], 1);
+        rk[i] = (i < n_pop || (!flg && fin)) ? -1 : -2;
+        cd[i] = 0.0;
+    }
+    __syncthreads();
+    if (!nsga) {      // GA: the first pop_out rows by (F0, index); rank 0, distance -F0
+        for (int i = tid; i < N2; i += T)
+            keys[i] = (i < N && rk[i] == -1) ? (((unsigned long long)ga_fkey(Fs[i * M]) << 32) | (unsigned)i) : ~0ull;
+        __syncthreads();
+        ga_sort(keys, N2);
+        for (int s = tid; s < pop_out; s += T) {
+            const bool ok = s < N2 && keys[s] != ~0ull;
+            const int i = ok ? (int)(keys[s] & 0xFFFFFFFFu) : -1;
+            cur[s] = i;
+            if (ok) { rk[i] = 0; cd[i] = -(double)Fs[i * M]; }
+        }
+        __syncthreads();
+    } else {
+        // domination counts
+        for (int j = tid; j < N; j += T) {
+            int c = 0;
+            if (rk[j] == -1)
+                for (int i = 0; i < N; ++i) c += (rk[i] == -1 && ga_dominates(Fs, M, i, j)) ? 1 : 0;
+            nd[j] = c;
+        }
+        // front peeling, until pop_out rows are ranked: a chain of short steps between workgroup barriers
+        int r = 0, ranked = 0;
+        while (true) {
+            if (tid == 0) s_ncur = 0;
+            __syncthreads();
+            for (int j = tid; j < N; j += T)
+                if (rk[j] == -1 && nd[j] == 0) cur[atomicAdd(&s_ncur, 1)] = j;
+            __syncthreads();
+            const int ncur = s_ncur;
+            if (ncur == 0) break;
+            for (int p = tid; p < ncur; p += T) rk[cur[p]] = r;
+            __syncthreads();
+            ranked += ncur;
+            ++r;
+            if (ranked >= pop_out) break;
+            for (int j = tid; j < N; j += T)
+                if (rk[j] == -1) {
+                    int c = 0;
+                    for (int p = 0; p < ncur; ++p) c += ga_dominates(Fs, M, cur[p], j) ? 1 : 0;
+                    nd[j] -= c;
+                }
+            __syncthreads();
+        }
+        const int n_fronts = r;
+        __syncthreads();
+        // crowding of every front at once: one sort per objective keyed (front, F_k, index); the distance is summed in objective order
+        for (int k = 0; k < M; ++k) {
+            for (int i = tid; i < N2; i += T)
+                keys[i] = (i < N && rk[i] >= 0)
+                              ? (((unsigned long long)rk[i] << 44) | ((unsigned long long)ga_fkey(Fs[i * M + k]) << 12) | (unsigned)i) : ~0ull;
+            __syncthreads();
+            ga_sort(keys, N2);
+            if (k == 0) {
+                for (int p = tid; p < ranked; p += T) {
+                    const int rr = (int)(keys[p] >> 44);
+                    if (p == 0 || (int)(keys[p - 1] >> 44) != rr) seg[rr] = p;
+                }
+                if (tid == 0) seg[n_fronts] = ranked;
+                __syncthreads();
+            }
+            for (int p = tid; p < ranked; p += T) {
+                const int rr = (int)(keys[p] >> 44), i = (int)(keys[p] & 0xFFFu), s0 = seg[rr], s1 = seg[rr + 1];
+                if (s1 - s0 <= 2 || p == s0 || p == s1 - 1) {
+                    cd[i] = INFINITY;
+                } else {
+                    const double span = (double)Fs[(int)(keys[s1 - 1] & 0xFFFu) * M + k] - (double)Fs[(int)(keys[s0] & 0xFFFu) * M + k];
+                    if (span > 0.0)
+                        cd[i] += ((double)Fs[(int)(keys[p + 1] & 0xFFFu) * M + k] - (double)Fs[(int)(keys[p - 1] & 0xFFFu) * M + k]) / span;
+                }
+            }
+            __syncthreads();
+        }
+        // slots: the fronts in order, rows by index; the front that does not fit is cut by (-distance, index)
+        for (int s = tid; s < pop_out; s += T) cur[s] = -1;
+        __syncthreads();
+        for (int i = tid; i < N; i += T) {
+            const int rr = rk[i];
+            if (rr < 0 || seg[rr] >= pop_out) continue;
+            const bool cut = seg[rr + 1] > pop_out;
+            const double ci = cd[i];
+            int c = 0;
+            for (int o = 0; o < N; ++o)
+                if (rk[o] == rr) c += cut ? ((cd[o] > ci || (cd[o] == ci && o < i)) ? 1 : 0) : (o < i ? 1 : 0);
+            if (seg[rr] + c < pop_out) cur[seg[rr] + c] = i;
+        }
+        __syncthreads();
+    }
+    for (int s = tid; s < pop_out; s += T) {
+        const int i = cur[s];
+        chosen[s] = i;
+        rank_out[s] = i >= 0 ? rk[i] : -1;
+        cd_out[s] = i >= 0 ? cd[i] : 0.0;
+        if (i >= 0)
+            for (int k = 0; k < M; ++k) F[s * M + k] = Fs[i * M + k];
+    }
+    if (tid == 0) { counts[0] = s_cnt[0]; counts[1] = s_cnt[1]; }
+}
+
+// Xnext[s] = the merged row chosen[s] of (X ; Xoff).  grid (ceil(n_var / (256 VEC)), pop_out)
+template <int VEC>
+__global__ __launch_bounds__(256) void ga_gather_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, const int* __restrict__ chosen,
+                                                        int n_pop, int n_var, float* __restrict__ Xnext) {
+    const int s = blockIdx.y, j0 = (blockIdx.x * 256 + threadIdx.x) * VEC, i = chosen[s];
+    if (j0 >= n_var || i < 0) return;
+    const float* src = (i < n_pop ? X + (size_t)i * n_var : Xoff + (size_t)(i - n_pop) * n_var) + j0;
+    float* dst = Xnext + (size_t)s * n_var + j0;
+    if (VEC == 4) *(f4*)dst = *(const f4*)src;
+    else dst[0] = src[0];
+}
+}  // namespace
+
+size_t ga_survive_lds_bytes(int n_rows, int n_obj) {
+    const size_t N = (size_t)n_rows, N2 = (size_t)ga_pow2(n_rows);
+    return N2 * 8 + N * 8 + N * (size_t)n_obj * 4 + 3 * N * 4 + (N + 2) * 4;
+}
+
+const char* launch_ga_vary(const float* X, const int* rank, const double* cd, const GaParams& g, int n_var, int generation, int row0, int rows,
+                           float* Xoff, hipStream_t st) {
+    if (rows <= 0 || row0 < 0 || row0 + rows > g.pop || n_var <= 0) return nullptr;
+    if (n_var % 4 == 0) {
+        hipLaunchKernelGGL(ga_vary_kernel<4>, dim3((n_var / 4 + 255) / 256, rows), dim3(256), 0, st, X, rank, cd, g, n_var, generation, row0, Xoff);
+        return "ga_vary_kernel<4>";
+    }
+    hipLaunchKernelGGL(ga_vary_kernel<1>, dim3((n_var + 255) / 256, rows), dim3(256), 0, st, X, rank, cd, g, n_var, generation, row0, Xoff);
+    return "ga_vary_kernel<1>";
+}
+
+const char* launch_ga_duplicates(const float* X, const float* Xoff, int pop, int n_off, int n_var, int* flags, hipStream_t st) {
+    if (pop < 0 || n_off <= 0 || n_var <= 0) return nullptr;
+    if (n_var % 4 == 0) {
+        hipLaunchKernelGGL(ga_duplicates_kernel<4>, dim3(n_off), dim3(256), 0, st, X, Xoff, pop, n_var, flags);
+        return "ga_duplicates_kernel<4>";
+    }
+    hipLaunchKernelGGL(ga_duplicates_kernel<1>, dim3(n_off), dim3(256), 0, st, X, Xoff, pop, n_var, flags);
+    return "ga_duplicates_kernel<1>";
+}
+
+const char* launch_ga_survive(float* F, const int* flags, int n_pop, int n_off, int n_obj, int pop_out, int nsga, int* chosen, int* rank_out,
+                              double* cd_out, int* counts, hipStream_t st) {
+    const int N = n_pop + n_off;
+    if (n_pop < 1 || n_off < 0 || N > 2 * GLASS_SEARCH_MAX_POP || n_obj < 1 || n_obj > GLASS_SEARCH_MAX_OBJ || pop_out < 1 || pop_out > N ||
+        pop_out > GLASS_SEARCH_MAX_POP)
+        return nullptr;
+    const size_t lds = ga_survive_lds_bytes(N, n_obj);
+    if (lds > 64 * 1024) {
+        if (!glass_lds_fits((int)lds)) return nullptr;
+        static DevOnce once;
+        once.run([&] {
+            (void)hipFuncSetAttribute((const void*)ga_survive_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)ga_survive_lds_bytes(2 * GLASS_SEARCH_MAX_POP, GLASS_SEARCH_MAX_OBJ));
+        });
+    }
+    hipLaunchKernelGGL(ga_survive_kernel, dim3(1), dim3(1024), lds, st, F, flags, n_pop, n_off, n_obj, pop_out, nsga, chosen, rank_out, cd_out, counts);
+    return "ga_survive_kernel";
+}
+
+void launch_ga_gather(const float* X, const float* Xoff, const int* chosen, int n_pop, int pop_out, int n_var, float* Xnext, hipStream_t st) {
+    if (n_var % 4 == 0)
+        hipLaunchKernelGGL(ga_gather_kernel<4>, dim3((n_var / 4 + 255) / 256, pop_out), dim3(256), 0, st, X, Xoff, chosen, n_pop, n_var, Xnext);
+    else
+        hipLaunchKernelGGL(ga_gather_kernel<1>, dim3((n_var + 255) / 256, pop_out), dim3(256), 0, st, X, Xoff, chosen, n_pop, n_var, Xnext);
+}

@@ -110,6 +110,18 @@ def load_library(path=None):
         lib.glass_engine_set_targets.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.c_int32]
         lib.glass_engine_last_set_details.argtypes = [C.c_void_p, C.c_int32, fp]
         lib.glass_engine_encode_generated.argtypes = [C.c_void_p, fp, C.c_int32, fp]
+    if hasattr(lib, "glass_search_supported"):          # (absent from older A/B builds loaded through GLASS_LIB)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        lib.glass_search_supported.argtypes = [C.c_int32] * 4
+        lib.glass_engine_set_search.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_double] * 5 + [C.c_uint64]
+        lib.glass_engine_set_search_operators.argtypes = [C.c_void_p] + [C.c_double] * 5 + [C.c_uint64]
+        lib.glass_engine_search_init.argtypes = [C.c_void_p, fp]
+        lib.glass_engine_search_vary.argtypes = [C.c_void_p, C.c_int32]
+        lib.glass_engine_search_evaluate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        lib.glass_engine_search_survive.argtypes = [C.c_void_p, C.c_int32]
+        lib.glass_engine_search_step.argtypes = [C.c_void_p, C.c_int32]
+        lib.glass_engine_search_read.argtypes = [C.c_void_p, fp, fp, ip, dp, fp, fp, ip, ip]
+        lib.glass_engine_latent_uploads.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -245,6 +257,20 @@ def host_clip_view_boxes(seed, generation, views, gen_res, min_permille, flip, f
     _check(lib, lib.glass_host_clip_view_boxes(int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation), int(views), int(gen_res), int(min_permille),
                                                int(bool(flip)), int(bool(fixed)), out.ctypes.data_as(C.POINTER(C.c_int32))))
     return out
+
+
+SEARCH_ALGORITHMS = {"ga": 0, "nsga2": 1}     # GLASS_SEARCH_GA / _NSGA2
+SEARCH_MAX_POP = 1024
+
+
+def search_supported(pop, n_var, n_obj, algorithm):
+    """(ok, message) for a device search of `pop` rows of n_var variables with n_obj objectives under "ga" / "nsga2": the library's own rule
+    (glass_search_supported), the one glass_engine_set_search and finalize apply.  Host only."""
+    if algorithm not in SEARCH_ALGORITHMS:
+        return False, "device search: unknown algorithm %r (expected one of %s)" % (algorithm, ", ".join(SEARCH_ALGORITHMS))
+    lib = load_library()
+    rc = lib.glass_search_supported(int(pop), int(n_var), int(n_obj), SEARCH_ALGORITHMS[algorithm])
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
 
 
 LATENT_SPACES = {"z": 0, "w": 1, "w+": 2}     # GLASS_LATENT_Z / _W / _WPLUS
@@ -490,6 +516,63 @@ class Engine:
                                                             int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation), int(first_row),
                                                             int(purpose), out.ctypes.data_as(ip)))
         return out
+
+    # --- device search (include/glass.h "Device search") ------------------------
+    def set_search(self, algorithm, pop, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, seed=1):
+        """Between construction and finalize(): turn the device search on for `pop` rows under "ga" / "nsga2" with scalar bounds xl / xu."""
+        if algorithm not in SEARCH_ALGORITHMS:
+            raise ValueError("unknown search algorithm %r: expected one of %s" % (algorithm, ", ".join(SEARCH_ALGORITHMS)))
+        _check(self.lib, self.lib.glass_engine_set_search(self._h, SEARCH_ALGORITHMS[algorithm], int(pop), float(xl), float(xu), float(eta_c),
+                                                           float(eta_m), float(prob_m), int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self.search_pop = int(pop)
+
+    def set_search_operators(self, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, seed=1):
+        """Any time after set_search: the values that size nothing (the bounds of a w / w+ search are known only after finalize())."""
+        _check(self.lib, self.lib.glass_engine_set_search_operators(self._h, float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m),
+                                                                     int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def search_init(self, X0):
+        """Upload the initial population [pop, floats_per_row], score it as generation 0 and rank it."""
+        z = self._rows(X0)
+        pop = getattr(self, "search_pop", None)      # (None: set_search was never called — the library says so)
+        if pop is not None and z.shape[0] != pop:
+            raise ValueError("search_init: the initial population must have exactly pop = %d rows, got %d" % (pop, z.shape[0]))
+        _check(self.lib, self.lib.glass_engine_search_init(self._h, _fp(z)))
+
+    def search_vary(self, generation):
+        _check(self.lib, self.lib.glass_engine_search_vary(self._h, int(generation)))
+
+    def search_evaluate(self, generation, first_row=0, rows=None):
+        rows = self.search_pop - int(first_row) if rows is None else int(rows)
+        _check(self.lib, self.lib.glass_engine_search_evaluate(self._h, int(generation), int(first_row), rows))
+
+    def search_survive(self, generation):
+        _check(self.lib, self.lib.glass_engine_search_survive(self._h, int(generation)))
+
+    def search_step(self, generation):
+        """One generation on the device: variation, the scoring pass, survival; one wait at the end."""
+        _check(self.lib, self.lib.glass_engine_search_step(self._h, int(generation)))
+
+    def search_read(self, *fields):
+        """dict of the named device-search buffers: "X", "F", "rank", "cd" (the population), "off_X", "off_F", "flags" (the last offspring),
+        "counts" = (flagged, non-finite rows of the last survival).  Only what is named is copied back."""
+        pop, nv, no = self.search_pop, self.latent_row()[0], int(self.cfg.n_obj)
+        shapes = dict(X=((pop, nv), np.float32), F=((pop, no), np.float32), rank=((pop,), np.int32), cd=((pop,), np.float64),
+                      off_X=((pop, nv), np.float32), off_F=((pop, no), np.float32), flags=((pop,), np.int32), counts=((2,), np.int32))
+        unknown = [f for f in fields if f not in shapes]
+        if unknown:
+            raise ValueError("search_read: unknown field(s) %r (expected some of %s)" % (unknown, ", ".join(shapes)))
+        out = {f: np.empty(*shapes[f]) for f in fields}
+        ctype = {np.float32: C.c_float, np.int32: C.c_int32, np.float64: C.c_double}
+        args = [out[f].ctypes.data_as(C.POINTER(ctype[shapes[f][1]])) if f in out else None for f in shapes]
+        _check(self.lib, self.lib.glass_engine_search_read(self._h, *args))
+        return out
+
+    def latent_uploads(self):
+        """(calls, rows): host-to-device latent copies the pass has made on this engine so far."""
+        calls, rows = C.c_int64(), C.c_int64()
+        _check(self.lib, self.lib.glass_engine_latent_uploads(self._h, C.byref(calls), C.byref(rows)))
+        return calls.value, rows.value
 
     # --- latent spaces / truncation -------------------------------------------
     def set_latent_space(self, name):

@@ -485,6 +485,16 @@ class Generator:
         view_kw = dict(clip_views=self.clip_views, clip_view_min=float(view_opt("clip_view_min", 0.5)),
                        clip_view_flip=bool(view_opt("clip_view_flip", True)),
                        clip_view_fixed=bool(view_opt("clip_view_fixed", False))) if self.clip_views else {}
+        # device search (opt-in, include/glass.h "Device search"): the engine keeps the population and runs the generation step; its buffers
+        # are sized in finalize, so the engine is told here.  Real-valued rows only: refused by name for the GPT2 and BigGAN configs
+        self.device_search = bool(getattr(config, "device_search", False))
+        if self.device_search and config.task == "img2txt":
+            raise ValueError("device_search: the GPT2 config searches integer token rows (int_sbx / int_pm): it keeps the host search")
+        if self.device_search and hasattr(self.model, "geometry"):
+            raise ValueError("device_search: the BigGAN configs search [z | boolean class bits] rows (HUX / bit-flip on the bits): they keep the "
+                             "host search")
+        if self.device_search and sharded:
+            raise ValueError("device_search: more than one rank (--dist) is not wired to the device search yet: run one rank, or the host search")
         if config.task == "img2txt":                                        # generator.py:25-27, 52-59
             if self.clip_views:
                 raise ValueError("clip_views=%d scores crops of generated images (txt2img); the img2txt task has none: leave it at 0"
@@ -543,6 +553,13 @@ class Generator:
                                  noise_seed=getattr(config, "noise_seed", 0), device=device, clip_resize=clip_resize,
                                  clip_normalize=clip_normalize, latent_space=self.latent_space,
                                  truncation_psi=self.truncation_psi, truncation_cutoff=self.truncation_cutoff, **tower)
+            if self.device_search:
+                try:      # bounds: the config's own (z); a search in w / w+ sets its probed bounds after finalize (set_search_operators)
+                    self.engine.set_search(config.algorithm, int(config.pop_size), float(np.float32(config.problem_args["xl"])),
+                                           float(np.float32(config.problem_args["xu"])), seed=int(getattr(config, "seed", 1) or 1))
+                except RuntimeError as ex:
+                    self.engine.close()
+                    raise ValueError("device_search: %s" % ex)
             if getattr(self.model, "dlatent_avg", None) is not None:
                 self.engine.load_state({"dlatent_avg": self.model.dlatent_avg})     # the Generator's own buffer: no sub-model prefix
         self.engine.load_state(self.model.state)

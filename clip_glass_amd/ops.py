@@ -967,3 +967,55 @@ def host_gpt2_gemm_choice(M, N, K, ln=False, width=None, n_cu=256):
     lib.glass_host_gpt2_gemm_choice.argtypes = [C.c_int32] * 7 + [ip, ip]
     _check(lib, lib.glass_host_gpt2_gemm_choice(M, N, K, K, int(bool(ln)), int(width or min(N, K)), n_cu, C.byref(S), C.byref(NK)))
     return S.value, NK.value
+
+
+# ---- device search (csrc/search.hip; include/glass.h "Device search") ------------------------------------------------------------
+def ga_vary(X, rank, cd, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, seed=1, generation=1, row0=0, rows=None, device=0):
+    """Offspring rows [row0, row0 + rows) of the population X float32 [pop, n_var] with rank int32 [pop] and cd float64 [pop]."""
+    lib = load_library()
+    X = _f32(X)
+    pop, nv = X.shape
+    rows = pop - row0 if rows is None else rows
+    rank = np.ascontiguousarray(rank, dtype=np.int32)
+    cd = np.ascontiguousarray(cd, dtype=np.float64)
+    out = np.empty((rows, nv), dtype=np.float32)
+    lib.glass_op_ga_vary.argtypes = ([C.c_int32] * 3 + [_FP, C.POINTER(C.c_int32), C.POINTER(C.c_double)] + [C.c_double] * 5 + [C.c_uint64] +
+                                     [C.c_int32] * 3 + [_FP])
+    _check(lib, lib.glass_op_ga_vary(device, pop, nv, _fp(X), rank.ctypes.data_as(C.POINTER(C.c_int32)), cd.ctypes.data_as(C.POINTER(C.c_double)),
+                                     float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     int(generation), int(row0), int(rows), _fp(out)))
+    return out
+
+
+def ga_duplicates(X, Xoff, device=0):
+    """flags int32 [n_off]: offspring row equals a population row or an offspring row below it."""
+    lib = load_library()
+    X, Xoff = _f32(X), _f32(Xoff)
+    flags = np.empty((Xoff.shape[0],), dtype=np.int32)
+    lib.glass_op_ga_duplicates.argtypes = [C.c_int32] * 4 + [_FP, _FP, C.POINTER(C.c_int32)]
+    _check(lib, lib.glass_op_ga_duplicates(device, X.shape[0], Xoff.shape[0], X.shape[1], _fp(X), _fp(Xoff), flags.ctypes.data_as(C.POINTER(C.c_int32))))
+    return flags
+
+
+def ga_survive(F, n_pop, pop_out, nsga=True, flags=None, X=None, device=0):
+    """Survival over the merged rows F float32 [n_pop + n_off, n_obj] -> dict(chosen, rank, cd, F, counts[, X]); X: merged rows [N, n_var]."""
+    lib = load_library()
+    F = _f32(F)
+    N, M = F.shape
+    n_off = N - n_pop
+    ip = C.POINTER(C.c_int32)
+    fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.int32)
+    out = dict(chosen=np.empty((pop_out,), np.int32), rank=np.empty((pop_out,), np.int32), cd=np.empty((pop_out,), np.float64),
+               F=np.empty((pop_out, M), np.float32), counts=np.empty((2,), np.int32))
+    nv, Xp, Xo, Xout = 0, None, None, None
+    if X is not None:
+        X = _f32(X)
+        nv = X.shape[1]
+        Xp, Xo = np.ascontiguousarray(X[:n_pop]), np.ascontiguousarray(X[n_pop:])
+        Xout = out["X"] = np.empty((pop_out, nv), np.float32)
+    lib.glass_op_ga_survive.argtypes = [C.c_int32] * 6 + [_FP, ip, ip, ip, C.POINTER(C.c_double), _FP, ip, C.c_int32, _FP, _FP, _FP]
+    _check(lib, lib.glass_op_ga_survive(device, n_pop, n_off, M, pop_out, int(bool(nsga)), _fp(F), None if fl is None else fl.ctypes.data_as(ip),
+                                        out["chosen"].ctypes.data_as(ip), out["rank"].ctypes.data_as(ip), out["cd"].ctypes.data_as(C.POINTER(C.c_double)),
+                                        _fp(out["F"]), out["counts"].ctypes.data_as(ip), nv, None if Xp is None else _fp(Xp),
+                                        None if Xo is None or not n_off else _fp(Xo), None if Xout is None else _fp(Xout)))
+    return out

@@ -53,7 +53,20 @@ class GenerationProblem(Problem):
         args = dict(self.config.problem_args)
         if getattr(self.generator, "latent_space", "z") != "z":
             args.update(dlatent_problem_args(config, self.generator))
+        if getattr(self.generator, "device_search", False):     # the device's rows are fp32 and are clipped to the bounds: bounds exact in fp32
+            args.update(xl=float(np.float32(args["xl"])), xu=float(np.float32(args["xu"])))
         super().__init__(**args)
+
+    @property
+    def engine(self):
+        """The engine behind the fitness pass (search.minimize(device=True) keeps the population on it)."""
+        return getattr(self.generator, "engine", None)
+
+    @property
+    def ranks(self):
+        """Processes that share a population (one per GPU under --dist)."""
+        sharder = getattr(self.generator, "sharder", None)
+        return int(getattr(sharder, "world", 1)) if sharder is not None else 1
 
     def _evaluate(self, x, out, *args, **kwargs):
         ls = self.config.latent(self.config)

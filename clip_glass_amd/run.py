@@ -80,6 +80,9 @@ def build_parser():
     p.add_argument("--pop-size", type=int, default=None)
     p.add_argument("--stochastic", action="store_true", default=None,
                    help="GPT2 config: top-k temperature sampling instead of greedy decoding (the config table's `stochastic`)")
+    p.add_argument("--device-search", action="store_true", default=None,
+                   help="StyleGAN2 configs, one rank: keep the population on the GPU and run selection, crossover, mutation, duplicate flags and "
+                        "survival there between the passes (off by default: the host search of search.py)")
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--dist", action="store_true",
                    help="multi-GPU: run under `torchrun --nproc-per-node N -m clip_glass_amd.run --dist ...` (one process per GPU, "
@@ -140,7 +143,7 @@ def main(argv=None, extra_config=None):
     vars(config).update(get_config(config.config))                             # run.py:25
     for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "clip_views", "clip_view_min", "clip_view_flip",
               "clip_view_fixed", "latent_space", "truncation_psi", "truncation_cutoff", "lpips_target", "lpips_size", "lpips_lambda", "lpips_weights",
-              "bpe_path", "pop_size", "stochastic", "target_weight", "prompt_mode"):
+              "bpe_path", "pop_size", "stochastic", "target_weight", "prompt_mode", "device_search"):
         if k in over:
             setattr(config, k, over[k])
     if "prompt" in over or "image_prompt" in over:
@@ -184,7 +187,8 @@ def main(argv=None, extra_config=None):
     os.makedirs(config.tmp_folder, exist_ok=True)
     # (same seed on every rank => identical GA state everywhere: no broadcast of the population is needed)
     res = search.minimize(problem, config.algorithm, config.pop_size, config.generations, operators["sampling"],
-                          seed=config.seed, callback=save_callback, verbose=rank0, mask=operators.get("mask"))
+                          seed=config.seed, callback=save_callback, verbose=rank0, mask=operators.get("mask"),
+                          device=bool(getattr(config, "device_search", False)))
     if not rank0:
         return res
     with open(os.path.join(config.tmp_folder, "genetic_result"), "wb") as f:   # run.py:79-84

@@ -166,14 +166,107 @@ class Result:
     pass
 
 
+DEVICE_MAX_POP = 1024      # include/glass.h "Device search": survival ranks 2 pop merged rows in one workgroup
+
+
+class _DeviceAlgorithm:
+    """What a callback sees of a device search: `pop` is read back from the device only when something asks for it."""
+
+    def __init__(self, problem, engine, nsga):
+        self.problem, self._engine, self._nsga, self.n_gen = problem, engine, nsga, 0
+
+    @property
+    def pop(self):
+        r = self._engine.search_read("X", "F")
+        return _individuals(r["X"].astype(float), r["F"].astype(float), self._nsga)
+
+
+def _individuals(X, F, nsga):
+    return [Individual(x, f if nsga else f[0]) for x, f in zip(X, F)]
+
+
+def _result(X, F, nsga):
+    res = Result()
+    res.pop = _individuals(X, F, nsga)
+    if nsga:
+        front = fast_non_dominated_sort(F)[0][0]
+        res.X, res.F = X[front], F[front]
+    else:
+        best = int(np.argmin(F[:, 0]))
+        res.X, res.F = X[best], F[best]
+    res.G = np.zeros(np.atleast_2d(res.X).shape[0])
+    res.CV = np.zeros(np.atleast_2d(res.X).shape[0])
+    return res
+
+
+def _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callback, eta_c, eta_m, prob_m, verbose, mask):
+    """The generation step on the device (include/glass.h "Device search"): generation 0 is sampled, de-duplicated and refilled on the host
+    as below, then every generation is one engine.search_step and a read of F.  Refusals come first and name their reason."""
+    mask = np.asarray(["real"] * problem.n_var if mask is None else list(mask))
+    if (mask != "real").any():
+        raise ValueError("device search: every variable must be real, and this mask has %s ones (the BigGAN configs' class bits use HUX / "
+                         "bit-flip, GPT2's tokens the integer operators): they keep the host search"
+                         % " / ".join(sorted(set(mask[mask != "real"].tolist()))))
+    ranks = int(getattr(problem, "ranks", 1) or 1)
+    if ranks > 1:
+        raise ValueError("device search: %d ranks (--dist): the multi-rank wiring is not built yet; run one rank, or the host search" % ranks)
+    bs = int(getattr(getattr(problem, "config", None), "batch_size", 1))
+    if pop_size > DEVICE_MAX_POP:
+        raise ValueError("device search: pop_size %d is over %d, the most the survival kernel ranks" % (pop_size, DEVICE_MAX_POP))
+    if pop_size < 2 or pop_size % bs:
+        raise ValueError("device search: pop_size %d must be a multiple of batch_size %d (the shapes on the device are static)" % (pop_size, bs))
+    engine = getattr(problem, "engine", None)
+    if engine is None:
+        raise ValueError("device search: this problem has no engine to keep the population on (GenerationProblem has one)")
+    xl, xu = np.unique(np.asarray(problem.xl, float)), np.unique(np.asarray(problem.xu, float))
+    if xl.size != 1 or xu.size != 1:
+        raise ValueError("device search: the bounds must be scalar (one xl and one xu for every variable), as the reference's are")
+    if algorithm not in ("ga", "nsga2"):
+        raise ValueError("device search: unknown algorithm %r" % (algorithm,))
+    if getattr(engine, "search_pop", None) != pop_size:
+        raise ValueError("device search: the engine was built without it, or for another pop_size (its buffers are sized in finalize): set "
+                         "config.device_search = True (run.py --device-search) before the problem is constructed")
+    nsga = algorithm == "nsga2"
+    np.random.seed(seed)   # the reference's Sampling classes draw from numpy's global RNG (operators.py:24-25)
+    X = np.asarray(sampling._do(problem, pop_size), dtype=float)
+    X = X[_eliminate_duplicates(X)]
+    for _ in range(16):    # exactly pop_size rows: refill from the sampler where elimination shrank the population
+        if X.shape[0] >= pop_size:
+            break
+        X = np.concatenate([X, np.asarray(sampling._do(problem, pop_size - X.shape[0]), dtype=float)])
+        X = X[_eliminate_duplicates(X)]
+    if X.shape[0] != pop_size:
+        raise ValueError("device search: the sampler keeps returning duplicate rows: %d distinct of %d" % (X.shape[0], pop_size))
+    engine.set_search_operators(float(xl[0]), float(xu[0]), eta_c, eta_m, prob_m, seed)
+    engine.search_init(X)
+    generator = getattr(problem, "generator", None)
+    algo = _DeviceAlgorithm(problem, engine, nsga)
+    for gen in range(1, n_gen + 1):
+        engine.search_step(gen)
+        if generator is not None:
+            generator.generation = gen + 1      # what the host search's evaluate() calls leave behind: the save callback's noise stream
+        algo.n_gen = gen
+        if verbose:
+            F = engine.search_read("F")["F"]
+            print("gen %4d | n_eval %6d | best %s" % (gen, gen * pop_size, np.array2string(F.min(axis=0), precision=5)))
+        if callback is not None:
+            callback(algo)
+    r = engine.search_read("X", "F")
+    return _result(r["X"].astype(float), r["F"].astype(float), nsga)
+
+
 def minimize(problem, algorithm, pop_size, n_gen, sampling, seed=1, callback=None, eta_c=3.0, eta_m=3.0,
-             prob_m=0.5, verbose=False, mask=None):
+             prob_m=0.5, verbose=False, mask=None, device=False):
     """pymoo.optimize.minimize(problem, algorithm, ("n_gen", n_gen)) stand-in.
 
     problem: has n_var, n_obj, xl, xu and _evaluate(x, out) (GenerationProblem);
     algorithm: "ga" | "nsga2"; sampling: object with _do(problem, n) (operators.get_operators);
     mask: per-variable type "real" | "int" | "bool" (None = all real) — the BigGAN configs mix real z with
-    boolean class bits (operators.py:39), the GPT2 config is all-int."""
+    boolean class bits (operators.py:39), the GPT2 config is all-int.
+    device=True (opt-in; real-valued StyleGAN2 searches on one rank): selection, variation, duplicate flags and survival run on the
+    problem's engine between the passes (include/glass.h "Device search"); the result has the same shapes."""
+    if device:
+        return _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callback, eta_c, eta_m, prob_m, verbose, mask)
     rng = np.random.default_rng(seed)
     np.random.seed(seed)   # the reference's Sampling classes draw from numpy's global RNG (operators.py:24-25)
     xl = np.broadcast_to(np.asarray(problem.xl, float), (problem.n_var,))

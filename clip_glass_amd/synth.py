@@ -316,6 +316,20 @@ def gpt2_sample_uniform(seed, generation, row, step, purpose=GPT2_SAMPLE_EVALUAT
     return (x.astype(np.float64) + 0.5) * 2.0 ** -32
 
 
+# Device search (csrc/search.hip; include/glass.h "Device search"): four uniforms per Philox block at counter (index, variable, generation,
+# purpose) under the seed with this tag XOR-ed into the key's high word.
+SEARCH_TAG = 0x53524348
+SEARCH_DRAW_TOURNAMENT, SEARCH_DRAW_SBX, SEARCH_DRAW_MUTATION = 0, 1, 2      # purpose words
+
+
+def search_uniforms(seed, generation, index, variable, purpose):
+    """(u0, u1, u2, u3) in (0, 1), float64, broadcast over the array arguments — the device's draws for that counter.  index: the mating
+    (tournament, crossover) or the offspring row (mutation); variable: 0 for the tournament."""
+    x = philox4x32(index, variable, np.asarray(generation, np.int64).astype(np.uint32), purpose, np.uint32(seed & 0xFFFFFFFF),
+                   np.uint32(((seed >> 32) & 0xFFFFFFFF) ^ SEARCH_TAG))
+    return tuple((w.astype(np.float64) + 0.5) * 2.0 ** -32 for w in x)
+
+
 # Crop views (csrc/clip.cpp, glass_host_clip_view_boxes): the boxes through which a pass sees every candidate's image — one Philox block per
 # (view, generation) under the seed with this tag XOR-ed into the key's high word.
 CLIP_VIEW_TAG = 0x56494557

@@ -346,6 +346,90 @@ int glass_engine_set_overlap(glass_engine* e, int32_t on);
 int glass_engine_set_biggan_tap(glass_engine* e, int32_t block);
 int glass_engine_get_biggan_tap(glass_engine* e, float* out, int64_t capacity, int32_t dims[4]);
 
+/* Device search (opt-in; off unless glass_engine_set_search is called): the GA / NSGA-II generation step — mating, variation, duplicate
+ * flags, survival — on the device, between two passes, in static shapes and with no host decision.  The population (pop rows of
+ * floats_per_row fp32 variables), its F, rank and crowding distance stay in device buffers; a generation is glass_engine_search_step.
+ * Real-valued rows only: StyleGAN2 engines in z, w and w+.  A BigGAN engine (boolean class bits: HUX / bit-flip) and an engine without a
+ * generator (GPT-2: integer rows) are refused by name and keep the host search of clip_glass_amd/search.py, which this section restates
+ * operator by operator; where it departs from it, it says so.
+ *
+ * Random numbers.  Philox4x32-10 under key (seed_lo, seed_hi ^ 0x53524348); a draw is u = (word + 0.5) 2^-32, exact in double.  The counter
+ * is (index, variable, generation, purpose) and words (w0, w1, w2, w3) give (u0, u1, u2, u3):
+ *   purpose 0, tournament: index = mating m, variable = 0.  u0, u1: the contestants of parent A; u2, u3: those of parent B.
+ *   purpose 1, crossover:  index = mating m, variable = j.  u0: the SBX spread, u1: the swap, u2: the per-variable gate.
+ *   purpose 2, mutation:   index = offspring row r, variable = j.  u0: the perturbation, u1: the gate.
+ * A draw is a pure function of (seed, generation, m or r, j, purpose): nothing depends on the launch geometry, and offspring rows produced in
+ * one launch or in several agree bit for bit.  Numpy mirror: synth.search_uniforms.
+ *
+ * Mating.  Offspring rows 2m and 2m + 1 are the two children of mating m (an odd pop drops the last mating's second child).  Each of the two
+ * parents is the winner of a binary tournament between population rows a = floor(u n) and b = floor(u' n) (n = pop, double arithmetic): a wins
+ * when rank[a] < rank[b], or the ranks are equal and cd[a] >= cd[b]; otherwise b (search.py:221).  GA: rank is 0 and cd is -F[:, 0].
+ * This is pymoo's count — pop / 2 matings, both children kept.  search.vary draws pop matings and keeps a random half of their 2 pop
+ * children; a child's distribution is the same, the pairing of siblings is not.
+ *
+ * Variation.  With y1 = min, y2 = max of the parents' variable, d = max(y2 - y1, 1e-300), the scalar bounds xl / xu and u = u0:
+ *   betaq(b) = (u alpha)^(1 / (eta_c + 1)) where u <= 1 / alpha, else (1 / max(2 - u alpha, 1e-300))^(1 / (eta_c + 1)); alpha = 2 - b^-(eta_c + 1)
+ *   c1 = clip(0.5 ((y1 + y2) - betaq(1 + 2 (y1 - xl) / d) d)), c2 = clip(0.5 ((y1 + y2) + betaq(1 + 2 (xu - y2) / d) d))
+ * swapped where u1 < 0.5; the variable is crossed where u2 < 0.5 and y2 - y1 > 1e-14 (child 0 takes c1, child 1 c2), otherwise child 0
+ * keeps parent A's value and child 1 parent B's — search.sbx_vectorised with crossover probability 1.  Then search.polynomial_mutation on
+ * each child x where u1 < prob_m, with u = u0, span = xu - xl, d1 = (x - xl) / span, d2 = (xu - x) / span:
+ *   dq = (2u + (1 - 2u)(1 - d1)^(eta_m + 1))^(1 / (eta_m + 1)) - 1 where u <= 0.5, else 1 - (2(1 - u) + 2(u - 0.5)(1 - d2)^(eta_m + 1))^(1 / (eta_m + 1))
+ *   x = clip(x + dq span).
+ * All of it is evaluated in double, in search.py's order of operations and without fused multiply-adds, and rounded ONCE to the fp32 row:
+ * a float64 mirror agrees to that rounding and the last bit of pow().  xl and xu must be exact in fp32.
+ *
+ * Duplicates.  Offspring row r is flagged when it equals, by value in every variable (-0.0 equals 0.0), a row of the current population or
+ * an offspring row with a lower index.  A flagged row is still scored — the shapes stay static — and is left out of survival.  search.py
+ * drops such rows and refills the batch with fresh matings instead (and compares with a tolerance of 1e-16): the device search may
+ * therefore rank fewer than pop new candidates in a generation.  An offspring row whose F is not finite is left out the same way.  Both
+ * counts are readable (glass_engine_search_read).  A population row is never left out: search_init refuses a non-finite F.
+ *
+ * Survival over the merged rows — the population first, then the offspring that are not left out; "index" is the merged index.
+ * GA: the first pop rows by (F[:, 0], index); rank 0, cd = -F[:, 0].
+ * NSGA-II, as minimize's survive() with fast_non_dominated_sort and crowding_distance: fronts are peeled from the domination counts until
+ * pop rows are ranked; within a front of more than two rows and for every objective k, in the order of (F_k, index), the two ends get an
+ * infinite distance and an inner row adds (F_k[next] - F_k[previous]) / (F_k[last] - F_k[first]) where that span is positive; a front of one
+ * or two rows is all infinite.  The distance is a double, summed in the order k = 0 .. n_obj - 1 by one writer per row (no atomics: the
+ * bits do not depend on the schedule), with -0.0 and 0.0 tied.  The survivors are the fronts in order, rows by index; the front that does
+ * not fit is cut by (-cd, index).  Their X, F, rank and cd become the next population, in that order.
+ *
+ * glass_search_supported: the one rule (host only: callable without a GPU), applied by the setter and by finalize.  algorithm 0 (GA, n_obj
+ * 1) or 1 (NSGA-II); pop in [2, 1024] (2048 merged rows are ranked by one workgroup); n_obj in [1, 6]; pop * n_var below 2^31.
+ *
+ * glass_engine_set_search: between create and finalize, which sizes the buffers (GLASS_ERR_STATE after it).  pop <= max_pop and a
+ * multiple of batch_size; noise_mode 0 or 1 (caller-provided planes would come from the host every pass).  n_var is the engine's
+ * floats_per_row.
+ * glass_engine_set_search_operators: any time after set_search — the values that size nothing (bounds, eta, prob_m, seed).  The bounds of a
+ *   search in w / w+ come from the mapping network and are known only after finalize.
+ * glass_engine_search_init: X0 host float32 [pop][floats_per_row]: uploads it, scores it as generation 0 and ranks (and orders) it as
+ *   minimize's first survive() does.
+ * glass_engine_search_vary(generation): the offspring of the current population and their duplicate flags.
+ * glass_engine_search_evaluate(generation, first_row, rows): scores offspring rows [first_row, first_row + rows) — whole minibatches — as
+ *   glass_engine_evaluate would score them with first_minibatch = first_row / batch_size, and writes their F to the offspring's F rows.
+ *   Rows scored in one call or in several (or, later, on several GPUs) get the same bits.
+ * glass_engine_search_survive(generation): survival and the gather of the surviving rows into the next population.
+ * glass_engine_search_step(generation): the three above for all rows — no device-to-host copy and no host wait between them, one wait at
+ *   its end.
+ * glass_engine_search_read: nullable outputs — the population's X [pop][floats_per_row], F [pop][n_obj], rank int32 [pop], cd double
+ *   [pop]; the last offspring's X, F and flags int32 [pop]; counts int32 [2] = {flagged, non-finite} rows of the last survival.
+ * Calls out of order (anything before search_init; evaluate / survive without the generation's vary) return GLASS_ERR_STATE by name.
+ * glass_engine_latent_uploads: how many host-to-device latent copies the pass has made on this engine, and their rows — a device-search
+ * generation makes none. */
+#define GLASS_SEARCH_GA 0
+#define GLASS_SEARCH_NSGA2 1
+int glass_search_supported(int32_t pop, int32_t n_var, int32_t n_obj, int32_t algorithm);
+int glass_engine_set_search(glass_engine* e, int32_t algorithm, int32_t pop, double xl, double xu, double eta_c, double eta_m, double prob_m,
+                            uint64_t seed);
+int glass_engine_set_search_operators(glass_engine* e, double xl, double xu, double eta_c, double eta_m, double prob_m, uint64_t seed);
+int glass_engine_search_init(glass_engine* e, const float* X0 /*[pop][floats_per_row]*/);
+int glass_engine_search_vary(glass_engine* e, int32_t generation);
+int glass_engine_search_evaluate(glass_engine* e, int32_t generation, int32_t first_row, int32_t rows);
+int glass_engine_search_survive(glass_engine* e, int32_t generation);
+int glass_engine_search_step(glass_engine* e, int32_t generation);
+int glass_engine_search_read(glass_engine* e, float* pop_X, float* pop_F, int32_t* rank, double* cd, float* off_X, float* off_F, int32_t* flags,
+                             int32_t* counts);
+int glass_engine_latent_uploads(glass_engine* e, int64_t* calls, int64_t* rows);
+
 /* Device info for bench.py (CU count, name, HBM bytes). */
 int glass_device_info(int32_t device, char* name, int32_t name_len, int32_t* cus, int64_t* hbm_bytes);
 
