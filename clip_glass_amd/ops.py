@@ -31,6 +31,91 @@ class ConvDesc(C.Structure):
                 ("res_cs", C.c_int32), ("res_up", C.c_int32), ("rgb_tanh", C.POINTER(C.c_float)), ("trgb_keep_map", C.c_int32)]
 
 
+# The C signature of every function of include/glass_ops.h, argument by argument (all return int32).  _lib() sets them once;
+# tests/test_ops_signatures.py holds this table and ConvDesc against the header.
+i32, u32, i64, u64, f32, f64 = C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+fp, ip, dp = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_double)
+SIGNATURES = {
+    "glass_op_conv": [i32, C.POINTER(ConvDesc)],
+    "glass_op_gemm": [i32, i32, i32, i32, fp, fp, fp, i32, i32, fp],
+    "glass_op_gemm_batched": [i32, i32, i32, i32, i32, fp, fp, i32, i32, i32, fp],
+    "glass_op_dense": [i32, i32, i32, i32, fp, fp, fp, i32, i32, fp, fp],
+    "glass_op_torgb": [i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp],
+    "glass_op_blur": [i32, i32, i32, i32, i32, fp, fp],
+    "glass_op_dblock_down": [i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp],
+    "glass_op_dblock0": [i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp],
+    "glass_op_fromrgb": [i32, i32, i32, i32, fp, fp, fp, fp],
+    "glass_op_mbstd": [i32, i32, i32, i32, i32, i32, i32, fp, fp],
+    "glass_op_resize": [i32, i32, i32, i32, i32, fp, fp],
+    "glass_op_view_patches": [i32, i32, i32, i32, i32, i32, i32, ip, fp, fp],
+    "glass_op_preprocess": [i32, i32, i32, i32, i32, i32, i32, fp, fp],
+    "glass_op_layernorm": [i32, i32, i32, fp, fp, fp, fp],
+    "glass_op_attention": [i32, i32, i32, i32, i32, fp, fp],
+    "glass_op_noise": [i32, i32, i32, u32, u32, u32, u64, fp],
+    "glass_op_gpt2_sample": [i32, i32, i32, fp, f32, i32, u64, i32, i32, i32, i32, ip],
+    "glass_op_gpt2_gemm": [i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, i32, fp, fp, fp, ip],
+    "glass_op_gpt2_attention": [i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, fp],
+    "glass_op_gpt2_head": [i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, i32, i32, i32, fp, fp, ip, ip, fp, fp, fp, ip],
+    "glass_op_gpt2_embed_step": [i32, i32, i32, i32, ip, fp, fp, i32, i32, i32, fp, fp],
+    "glass_op_bg_cond": [i32, i32, i32, i32, i32, fp, fp, fp],
+    "glass_op_bg_bn_tables": [i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp],
+    "glass_op_bg_attn_split": [i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, ip],
+    "glass_op_bg_softmax": [i32, i32, i32, fp, fp],
+    "glass_op_bg_rgb_tanh": [i32, i32, i32, i32, fp, fp],
+    "glass_op_bg_to_half": [i32, i64, fp, fp],
+    "glass_op_bg_tail": [i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp],
+    "glass_op_rn_avgpool": [i32, i32, i32, i32, i32, fp, fp],
+    "glass_op_rn_stem_conv1": [i32, i32, i32, i32, fp, fp, fp, fp, fp],
+    "glass_op_rn_conv_bn": [i32, i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp],
+    "glass_op_rn_tokens": [i32, i32, i32, i32, fp, fp, fp],
+    "glass_op_mapping": [i32, i32, i32, i32, fp, fp, fp, i32, fp, ip],
+    "glass_op_pixelnorm": [i32, i32, i32, fp, fp],
+    "glass_op_dense_splitk": [i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp],
+    "glass_op_dense_ex": [i32, i32, i32, i32, i32, i32, fp, fp, fp, i32, i32, fp, i32, fp],
+    "glass_op_dense_multi": [i32, i32, i32, i32, i32, i32, ip, ip, ip, ip, ip, fp, fp, fp, fp],
+    "glass_op_style_norm": [i32, i32, i32, i32, ip, ip, fp, fp, fp],
+    "glass_op_d_head": [i32, i32, i32, fp, fp, fp, fp, fp, fp, ip],
+    "glass_op_finalize_image": [i32, i64, fp, fp],
+    "glass_op_embed_lnpre": [i32, i32, i32, i32, fp, fp, fp, fp, fp, fp],
+    "glass_op_embed_text": [i32, i32, i32, i32, i32, ip, fp, fp, fp],
+    "glass_op_layernorm_ex": [i32, i32, i32, i64, i32, fp, fp, fp, fp],
+    "glass_op_layernorm_rows": [i32, i32, i32, i32, fp, ip, fp, fp, fp],
+    "glass_op_cosine": [i32, i32, i32, fp, fp, fp],
+    "glass_op_cosine_views": [i32, i32, i32, i32, fp, fp, fp, fp],
+    "glass_op_assemble_F": [i32, i32, i32, fp, fp, fp],
+    "glass_op_cosine_set": [i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp],
+    "glass_op_assemble_F_set": [i32, i32, i32, fp, fp, fp, fp, fp],
+    "glass_op_image_patches": [i32, i32, i32, i32, i32, fp, f32, fp],
+    "glass_op_rn_token0_rows": [i32, i32, i32, i32, fp, fp],
+    "glass_op_lpips_input": [i32, i32, i32, i32, fp, fp],
+    "glass_op_vgg_conv1": [i32, i32, i32, fp, fp, fp, fp],
+    "glass_op_maxpool2": [i32, i32, i32, i32, i32, fp, fp],
+    "glass_op_lpips_head": [i32, i32, i32, i32, i32, fp, fp, fp, fp],
+    "glass_op_ga_vary": [i32, i32, i32, fp, ip, dp, f64, f64, f64, f64, f64, u64, i32, i32, i32, fp],
+    "glass_op_ga_duplicates": [i32, i32, i32, i32, fp, fp, ip],
+    "glass_op_ga_survive": [i32, i32, i32, i32, i32, i32, fp, ip, ip, ip, dp, fp, ip, i32, fp, fp, fp],
+    "glass_op_mfma_probe": [i32, fp, fp, fp],
+    "glass_host_pack_conv": [fp, i32, i32, i32, i32, fp],
+    "glass_host_resize_taps": [i32, i32, i32, ip, ip, fp, i32],
+    "glass_host_gpt2_gemm_choice": [i32, i32, i32, i32, i32, i32, i32, ip, ip],
+    "glass_host_gpt2_step_plan": [i32, i32, i32, i32, i32, i32, i32, C.c_char_p, i32],
+}
+_signed = None      # the library SIGNATURES was last applied to
+
+
+def _lib():
+    """load_library() with SIGNATURES applied (a second build loaded through GLASS_LIB may lack the newer functions)."""
+    global _signed
+    lib = load_library()
+    if lib is not _signed:
+        for name, argtypes in SIGNATURES.items():
+            if hasattr(lib, name):
+                fn = getattr(lib, name)
+                fn.argtypes, fn.restype = argtypes, C.c_int32
+        _signed = lib
+    return lib
+
+
 def to_planar8(a):
     """[B,H,W,C] -> the chunk-planar layout [B,C/8,H,W,8] conv_wreg's producers write (csrc/common.h x_planar8)."""
     B, H, W, Cc = a.shape
@@ -74,7 +159,7 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
     padding stays zero; in_up — x is [B,H/2,W/2,Cin], read through a nearest x2 upsample; shift [B,Cout] — added after the bias (act=2:
     ReLU); res [B,Ho >> res_up,Wo >> res_up,res_cs or Cout] — the first Cout channels, nearest x2 with res_up; rgb_tanh — returns
     tanh(channels 0..2) [B,3,Ho,Wo] from the accumulators instead of y (conv_tiled only)."""
-    lib = load_library()
+    lib = _lib()
     x = _f32(x); w = _f32(w)
     Bx, H, W, Cin = x.shape
     if in_up:
@@ -129,7 +214,6 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
     if rgb_tanh:
         ytanh = np.empty((B, 3, Ho, Wo), dtype=np.float32)
         d.rgb_tanh = _fp(ytanh)
-    lib.glass_op_conv.argtypes = [C.c_int32, C.POINTER(ConvDesc)]
     _check(lib, lib.glass_op_conv(device, C.byref(d)))
     if rgb_tanh:
         return ytanh
@@ -141,13 +225,12 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
 
 
 def gemm(a, w, bias=None, mode=3, impl=0, acc=None, device=0):
-    lib = load_library()
+    lib = _lib()
     a = _f32(a); w = _f32(w)
     M, K = a.shape
     N = w.shape[0]
     out = _f32(acc).copy() if acc is not None else np.empty((M, N), dtype=np.float32)
     b, bp = _opt(bias)
-    lib.glass_op_gemm.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_float)] * 3 + [C.c_int32, C.c_int32, C.POINTER(C.c_float)]
     _check(lib, lib.glass_op_gemm(device, M, N, K, _fp(a), _fp(w), bp, mode, impl, _fp(out)))
     return out
 
@@ -155,66 +238,56 @@ def gemm(a, w, bias=None, mode=3, impl=0, acc=None, device=0):
 def gemm_batched(a, w, mode=3, cand_batch=True, impl=0, device=0):
     """a [batch,M,K], w [batch,N,K] -> out [batch,M,N] = a[z] @ w[z]^T, set up as the BigGAN self-attention products (csrc/biggan.cpp
     bg_attention).  mode 3: fp32 out, 0: fp16 out.  impl 0: gemm_tiled, then gemm_direct where it refuses; 1: direct; 2: tiled."""
-    lib = load_library()
+    lib = _lib()
     a = _f32(a); w = _f32(w)
     batch, M, K = a.shape
     N = w.shape[1]
     assert w.shape == (batch, N, K)
     out = np.empty((batch, M, N), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_gemm_batched.argtypes = [C.c_int32] * 5 + [fp, fp] + [C.c_int32] * 3 + [fp]
     _check(lib, lib.glass_op_gemm_batched(device, batch, M, N, K, _fp(a), _fp(w), int(mode), int(cand_batch), int(impl), _fp(out)))
     return out
 
 
 def dense(x, wt, bias=None, in_sq=False, mode=0, eps_row=None, device=0):
-    lib = load_library()
+    lib = _lib()
     x = _f32(x); wt = _f32(wt)
     P, K = x.shape
     N = wt.shape[1]
     out = np.empty((P, N), dtype=np.float32)
     b, bp = _opt(bias)
     e, ep = _opt(eps_row)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_dense.argtypes = [C.c_int32] * 4 + [fp, fp, fp, C.c_int32, C.c_int32, fp, fp]
     _check(lib, lib.glass_op_dense(device, P, K, N, _fp(x), _fp(wt), bp, int(in_sq), mode, ep, _fp(out)))
     return out
 
 
 def torgb(x, wrgb, bias, sn, smax, yprev=None, device=0):
-    lib = load_library()
+    lib = _lib()
     x = _f32(x)
     B, H, _, Cc = x.shape
     wrgb, bias, sn, smax = _f32(wrgb), _f32(bias), _f32(sn), _f32(smax)
     yp, ypp = _opt(yprev)
     out = np.empty((B, 3, H, H), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_torgb.argtypes = [C.c_int32] * 4 + [fp] * 7
     _check(lib, lib.glass_op_torgb(device, B, H, Cc, _fp(x), _fp(wrgb), _fp(bias), _fp(sn), _fp(smax), ypp, _fp(out)))
     return out
 
 
 def blur(x, mode, device=0):
-    lib = load_library()
+    lib = _lib()
     x = _f32(x)
     B, H, _, Cc = x.shape
     Ho = H + 1 if mode != 1 else H // 2      # mode 2: pad 2 written in 32-channel planes (un-permuted here)
     out = np.empty((B, Ho, Ho, Cc), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_blur.argtypes = [C.c_int32] * 5 + [fp, fp]
     _check(lib, lib.glass_op_blur(device, mode, B, H, Cc, _fp(x), _fp(out)))
     return from_planar32(out, B, Ho, Ho, Cc) if mode == 2 else out
 
 
 def dblock_down(h, x, w1, wskip, b1, device=0):
     """Fused second half of a D block (conv_down.hip).  h, x [B,R,R,Cin] NHWC; w1 [Cout,Cin,3,3]; wskip [Cout,Cin,1,1]."""
-    lib = load_library()
+    lib = _lib()
     h, x, w1, wskip, b1 = _f32(h), _f32(x), _f32(w1), _f32(wskip), _f32(b1)
     B, R, _, Cin = h.shape
     Cout = w1.shape[0]
     out = np.empty((B, R // 2, R // 2, Cout), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_dblock_down.argtypes = [C.c_int32] * 5 + [fp] * 6
     _check(lib, lib.glass_op_dblock_down(device, B, R, Cin, Cout, _fp(h), _fp(x), _fp(w1), _fp(wskip), _fp(b1), _fp(out)))
     return out
 
@@ -222,48 +295,40 @@ def dblock_down(h, x, w1, wskip, b1, device=0):
 def dblock0(y, frgb_w, frgb_b, w0, b0, w1, wskip, b1, impl=0, device=0):
     """The discriminator's whole full-resolution block (conv_d0.hip): y [B,3,R,R] -> [B,R/2,R/2,64].  impl 1: the two-kernel form;
     2: the fused kernel writing chunk-planar (un-permuted here)."""
-    lib = load_library()
+    lib = _lib()
     y, frgb_w, frgb_b, w0, b0, w1, wskip, b1 = (_f32(a) for a in (y, frgb_w, frgb_b, w0, b0, w1, wskip, b1))
     B, _, R, _ = y.shape
     out = np.empty((B, R // 2, R // 2, 64), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_dblock0.argtypes = [C.c_int32] * 4 + [fp] * 9
     _check(lib, lib.glass_op_dblock0(device, B, R, impl, _fp(y), _fp(frgb_w), _fp(frgb_b), _fp(w0), _fp(b0), _fp(w1), _fp(wskip),
                                      _fp(b1), _fp(out)))
     return from_planar8(out, B, R // 2, R // 2, 64) if impl == 2 else out
 
 
 def fromrgb(y, w, bias, device=0):
-    lib = load_library()
+    lib = _lib()
     y, w, bias = _f32(y), _f32(w), _f32(bias)
     B, _, R, _ = y.shape
     Cout = w.shape[0]
     out = np.empty((B, R, R, Cout), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_fromrgb.argtypes = [C.c_int32] * 4 + [fp] * 4
     _check(lib, lib.glass_op_fromrgb(device, B, R, Cout, _fp(y), _fp(w), _fp(bias), _fp(out)))
     return out
 
 
 def mbstd(x, Cpad, batch_size, group=4, device=0):
-    lib = load_library()
+    lib = _lib()
     x = _f32(x)
     B, hw, Cc = x.shape
     out = np.empty((B, hw, Cpad), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_mbstd.argtypes = [C.c_int32] * 7 + [fp, fp]
     _check(lib, lib.glass_op_mbstd(device, B, hw, Cc, Cpad, batch_size, group, _fp(x), _fp(out)))
     return out
 
 
 def resize(y, S, ps, device=0):
-    lib = load_library()
+    lib = _lib()
     y = _f32(y)
     B, _, R, _ = y.shape
     G = S // ps
     out = np.empty((B * G * G, 3 * ps * ps), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_resize.argtypes = [C.c_int32] * 5 + [fp, fp]
     _check(lib, lib.glass_op_resize(device, B, R, S, ps, _fp(y), _fp(out)))
     return out
 
@@ -271,69 +336,56 @@ def resize(y, S, ps, device=0):
 def view_patches(y, S, ps, boxes, normalize=0, device=0):
     """The engine's crop-view resize on images [B,3,R,R] in (-1, 1) and boxes int [V,4] = (x0, y0, s, flip); rows (b V + v) G G + g, columns
     as `resize`."""
-    lib = load_library()
+    lib = _lib()
     y = _f32(y)
     B, _, R, _ = y.shape
     bx = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
     V, G = bx.shape[0], S // ps
     out = np.empty((B * V * G * G, 3 * ps * ps), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_view_patches.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32), fp, fp]
-    _check(lib, lib.glass_op_view_patches(device, B, R, S, ps, int(normalize), V, bx.ctypes.data_as(C.POINTER(C.c_int32)), _fp(y), _fp(out)))
+    _check(lib, lib.glass_op_view_patches(device, B, R, S, ps, int(normalize), V, bx.ctypes.data_as(ip), _fp(y), _fp(out)))
     return out
 
 
 def preprocess(y, S, ps, resize_mode=0, normalize=0, device=0):
     """The engine's CLIP preprocessing (glass_config.clip_resize / clip_normalize) on images [B,3,R,R] in (-1, 1); output as `resize`."""
-    lib = load_library()
+    lib = _lib()
     y = _f32(y)
     B, _, R, _ = y.shape
     G = S // ps
     out = np.empty((B * G * G, 3 * ps * ps), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_preprocess.argtypes = [C.c_int32] * 7 + [fp, fp]
     _check(lib, lib.glass_op_preprocess(device, B, R, S, ps, int(resize_mode), int(normalize), _fp(y), _fp(out)))
     return out
 
 
 def layernorm(x, g, b, device=0):
-    lib = load_library()
+    lib = _lib()
     x, g, b = _f32(x), _f32(g), _f32(b)
     out = np.empty_like(x)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_layernorm.argtypes = [C.c_int32] * 3 + [fp] * 4
     _check(lib, lib.glass_op_layernorm(device, x.shape[0], x.shape[1], _fp(x), _fp(g), _fp(b), _fp(out)))
     return out
 
 
 def attention(qkv, n_img, L, heads, causal=False, device=0):
-    lib = load_library()
+    lib = _lib()
     qkv = _f32(qkv)
     out = np.empty((n_img * L, heads * 64), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_attention.argtypes = [C.c_int32] * 5 + [fp, fp]
     _check(lib, lib.glass_op_attention(device, n_img, L, heads, int(causal), _fp(qkv), _fp(out)))
     return out
 
 
 def noise(n_mb, hw, layer, mb0, generation, seed, device=0):
-    lib = load_library()
+    lib = _lib()
     out = np.empty((n_mb, hw), dtype=np.float32)
-    lib.glass_op_noise.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
-                                   C.POINTER(C.c_float)]
     _check(lib, lib.glass_op_noise(device, n_mb, hw, layer, mb0, generation, seed, _fp(out)))
     return out
 
 
 def gpt2_sample(logits, temperature, top_k, seed, generation, first_row, step, purpose=0, device=0):
     """The GPT-2 stochastic pick on logits [rows, V] float32 (gpt2.hip, generic path) -> int32 tokens [rows]."""
-    lib = load_library()
+    lib = _lib()
     lg = _f32(logits)
     rows, V = lg.shape
     out = np.empty(rows, dtype=np.int32)
-    ip = C.POINTER(C.c_int32)
-    lib.glass_op_gpt2_sample.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_int32, C.c_uint64,
-                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip]
     _check(lib, lib.glass_op_gpt2_sample(device, rows, V, _fp(lg), float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                          int(generation), int(first_row), int(step), int(purpose), out.ctypes.data_as(ip)))
     return out
@@ -349,7 +401,7 @@ def gpt2_gemm(a, w, bias=None, mode=0, form="step", res=None, ln=None, pst_in=No
     from the device's own row statistics ("step": gpt2_finalize_kernel; "rowblk": pst_in, the partials an earlier rowblk call returned).
     Returns a dict: out [M, N], S (the global K split), stats [M, 2] (step form: the fused LayerNorm's, or those a residual product
     leaves), pst [M, N/32, 2] (rowblk with want_pst)."""
-    lib = load_library()
+    lib = _lib()
     a = np.asarray(a, dtype=np.float32)
     assert a.ndim == 2 and a.strides[1] == 4 and a.strides[0] % 4 == 0
     M, K = a.shape
@@ -365,7 +417,6 @@ def gpt2_gemm(a, w, bias=None, mode=0, form="step", res=None, ln=None, pst_in=No
     out = np.empty((M, N), dtype=np.float32)
     if mode == 2:
         out[...] = res
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     bias_a, bias_p = _opt(bias)
     g_a, g_p = _opt(None if ln is None else ln[0])
     b_a, b_p = _opt(None if ln is None else ln[1])
@@ -374,7 +425,6 @@ def gpt2_gemm(a, w, bias=None, mode=0, form="step", res=None, ln=None, pst_in=No
     stats = np.full((M, 2), np.nan, dtype=np.float32)
     pst = np.full((M, max(N // 32, 1), 2), np.nan, dtype=np.float32) if want_pst else None
     S = C.c_int32(0)
-    lib.glass_op_gpt2_gemm.argtypes = [C.c_int32] * 8 + [fp] * 6 + [C.c_int32, fp, fp, fp, ip]
     _check(lib, lib.glass_op_gpt2_gemm(device, f, M, N, K, lda, int(mode), int(width or min(N, K)), _fp(abuf), _fp(w), bias_p, g_p, b_p, pi_p,
                                        np_in, _fp(out), _fp(stats), None if pst is None else _fp(pst), C.byref(S)))
     return dict(out=out, S=int(S.value), stats=stats, pst=pst)
@@ -385,7 +435,7 @@ def gpt2_attention(qkv, kc, vc, past, heads, form="general", bias=None, device=0
     past; "general_dev": the same kernel with `past` in device memory (the graph-replay form); "step": gpt2_attention_step_kernel.
     qkv: [P * nd, 3 D] finished values, or for "step" [S, P, 3 D] split-K slices (summed by the kernel, + bias [3 D]).
     Returns (out [P * nd, D], kc, vc) — the caches after the call."""
-    lib = load_library()
+    lib = _lib()
     kc, vc = np.array(kc, dtype=np.float32, order="C"), np.array(vc, dtype=np.float32, order="C")
     P, Tmax, D = kc.shape
     assert vc.shape == kc.shape and D == heads * 64
@@ -398,9 +448,7 @@ def gpt2_attention(qkv, kc, vc, past, heads, form="general", bias=None, device=0
         S, nd = 0, qkv.shape[0] // P
         assert qkv.shape == (P * nd, 3 * D)
     out = np.empty((P * nd, D), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
     bias_a, bias_p = _opt(bias)
-    lib.glass_op_gpt2_attention.argtypes = [C.c_int32] * 8 + [fp] * 5
     _check(lib, lib.glass_op_gpt2_attention(device, f, P, nd, int(past), Tmax, heads, S, _fp(qkv), bias_p, _fp(kc), _fp(vc), _fp(out)))
     return out, kc, vc
 
@@ -409,15 +457,13 @@ def gpt2_head(x, wte, lng, lnb, tail=False, wpe=None, past=0, step=0, device=0):
     """The vocabulary head of a single-token step (gpt2.hip): row statistics by gpt2_finalize_kernel, then launch_gpt2_head with the arg-max pick (tail=False:
     returns logits [M, V], pair_val / pair_idx [M, ceil(V/32)], token [M], stats [M, 2]) or with the arg-max + embed / advance tail at the state
     {past, step, 0} (tail=True: token, stats, x_next [M, K], stats_next [M, 2], state [3])."""
-    lib = load_library()
+    lib = _lib()
     x, wte, lng, lnb = _f32(x), _f32(wte), _f32(lng), _f32(lnb)
     M, K = x.shape
     V = wte.shape[0]
     NB = (V + 31) // 32
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     token = np.full(M, -1, dtype=np.int32)
     stats = np.full((M, 2), np.nan, dtype=np.float32)
-    lib.glass_op_gpt2_head.argtypes = [C.c_int32] * 5 + [fp] * 5 + [C.c_int32] * 3 + [fp, fp, ip, ip, fp, fp, fp, ip]
     if not tail:
         logits = np.empty((M, V), dtype=np.float32)
         pv = np.empty((M, NB), dtype=np.float32)
@@ -437,14 +483,12 @@ def gpt2_head(x, wte, lng, lnb, tail=False, wpe=None, past=0, step=0, device=0):
 
 def gpt2_embed_step(token, wte, wpe, past, step, device=0):
     """launch_gpt2_embed_step with statistics at the state {past, step}: (x [M, K] = wte[token] + wpe[past], stats [M, 2])."""
-    lib = load_library()
+    lib = _lib()
     wte, wpe = _f32(wte), _f32(wpe)
     tok = np.ascontiguousarray(token, dtype=np.int32)
     M, (V, K) = tok.shape[0], wte.shape
     x = np.full((M, K), np.nan, dtype=np.float32)
     stats = np.full((M, 2), np.nan, dtype=np.float32)
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-    lib.glass_op_gpt2_embed_step.argtypes = [C.c_int32] * 4 + [ip, fp, fp] + [C.c_int32] * 3 + [fp, fp]
     _check(lib, lib.glass_op_gpt2_embed_step(device, M, V, K, tok.ctypes.data_as(ip), _fp(wte), _fp(wpe), wpe.shape[0], int(past), int(step),
                                              _fp(x), _fp(stats)))
     return x, stats
@@ -452,14 +496,12 @@ def gpt2_embed_step(token, wte, wpe, past, step, device=0):
 
 def bg_cond(x, et, zd, device=0):
     """bg_cond_kernel: population rows x [P, zd + nc] = [z | class bits], et = E^T [nc, zd] -> cond [P, 2 zd] = [clip(z, -2, 2) | softmax @ E^T]."""
-    lib = load_library()
+    lib = _lib()
     x, et = _f32(x), _f32(et)
     P, L = x.shape
     nc = et.shape[0]
     assert et.shape == (nc, zd) and L >= zd + nc
     cond = np.empty((P, 2 * zd), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_bg_cond.argtypes = [C.c_int32] * 5 + [fp] * 3
     _check(lib, lib.glass_op_bg_cond(device, P, L, zd, nc, _fp(x), _fp(et), _fp(cond)))
     return cond
 
@@ -467,15 +509,13 @@ def bg_cond(x, et, zd, device=0):
 def bg_bn_tables(cond, wt, bias, inv_std, mean, prebias, device=0):
     """The three launches of glass_biggan_prepare (dense + bg_bn_tables_kernel + bg_to_half_kernel): cond [P, cd], wt [cd, 2C] (gain | offset
     columns), bias [2C], inv_std / mean / prebias [C] -> (tab [P, 2C] = [A | S] float32, tab16: its fp16 copy as float32 values)."""
-    lib = load_library()
+    lib = _lib()
     cond, wt, bias, inv_std, mean, prebias = (_f32(a) for a in (cond, wt, bias, inv_std, mean, prebias))
     P, cd = cond.shape
     Cc = inv_std.shape[0]
     assert wt.shape == (cd, 2 * Cc) and bias.shape == (2 * Cc,) and mean.shape == (Cc,) and prebias.shape == (Cc,)
     tab = np.empty((P, 2 * Cc), dtype=np.float32)
     tab16 = np.empty((P, 2 * Cc), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_bg_bn_tables.argtypes = [C.c_int32] * 4 + [fp] * 8
     _check(lib, lib.glass_op_bg_bn_tables(device, P, cd, Cc, _fp(cond), _fp(wt), _fp(bias), _fp(inv_std), _fp(mean), _fp(prebias), _fp(tab),
                                           _fp(tab16)))
     return tab, tab16
@@ -484,7 +524,7 @@ def bg_bn_tables(cond, wt, bias, inv_std, mean, prebias, device=0):
 def bg_attn_split(T, c8, c2, device=0):
     """T [B,H,W,2 c8 + c2] (theta | phi | g) -> (theta [B,HW,c8], phi [B,HW/4,c8], gT [B,c2,HW/4], kernel name): the split + 2x2
     max-pool + transpose of the self-attention block; the name says which of the launcher's two kernels ran."""
-    lib = load_library()
+    lib = _lib()
     T = _f32(T)
     B, H, W, CT = T.shape
     assert CT == 2 * c8 + c2
@@ -493,43 +533,35 @@ def bg_attn_split(T, c8, c2, device=0):
     phi = np.empty((B, hw // 4, c8), dtype=np.float32)
     gT = np.empty((B, c2, hw // 4), dtype=np.float32)
     vec = C.c_int32(-1)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_bg_attn_split.argtypes = [C.c_int32] * 6 + [fp] * 4 + [C.POINTER(C.c_int32)]
     _check(lib, lib.glass_op_bg_attn_split(device, B, H, W, c8, c2, _fp(T), _fp(theta), _fp(phi), _fp(gT), C.byref(vec)))
     return theta, phi, gT, "bg_attn_split_vec_kernel" if vec.value == 1 else "bg_attn_split_kernel"
 
 
 def bg_softmax(S, device=0):
     """Row softmax S [rows, n] float32 -> [rows, n] (the kernel's fp16 values)."""
-    lib = load_library()
+    lib = _lib()
     S = _f32(S)
     rows, n = S.shape
     out = np.empty((rows, n), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_bg_softmax.argtypes = [C.c_int32] * 3 + [fp, fp]
     _check(lib, lib.glass_op_bg_softmax(device, rows, n, _fp(S), _fp(out)))
     return out
 
 
 def bg_rgb_tanh(x, device=0):
     """x [B, hw, C] (rounded to fp16) -> [B, 3, hw] = tanh of channels 0..2, planar float32."""
-    lib = load_library()
+    lib = _lib()
     x = _f32(x)
     B, hw, Cc = x.shape
     y = np.empty((B, 3, hw), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_bg_rgb_tanh.argtypes = [C.c_int32] * 4 + [fp, fp]
     _check(lib, lib.glass_op_bg_rgb_tanh(device, B, hw, Cc, _fp(x), _fp(y)))
     return y
 
 
 def bg_to_half(x, device=0):
     """bg_to_half_kernel on a flat float32 array of any length -> its fp16 values (as float32)."""
-    lib = load_library()
+    lib = _lib()
     x = _f32(x).reshape(-1)
     out = np.empty(x.shape, dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_bg_to_half.argtypes = [C.c_int32, C.c_int64, fp, fp]
     _check(lib, lib.glass_op_bg_to_half(device, x.shape[0], _fp(x), _fp(out)))
     return out
 
@@ -537,14 +569,12 @@ def bg_to_half(x, device=0):
 def bg_tail(h, x0, w3, b3, bn_a, bn_s, rgb_w, rgb_b, device=0):
     """BigGAN-deep's fused last stage (bg_tail.hip): h [B,R,R,mid] (= relu(bn_3(conv_2))), x0 [B,R/2,R/2,128] (the block input), w3 [128,mid],
     b3 [128], the final bn's folded A / S [128], rgb_w [3,128,3,3], rgb_b [3] -> tanh(conv_to_rgb(relu(bn(conv_3(h) + up(x0))))) [B,3,R,R]."""
-    lib = load_library()
+    lib = _lib()
     h, x0, w3, b3, bn_a, bn_s, rgb_w, rgb_b = (_f32(a) for a in (h, x0, w3, b3, bn_a, bn_s, rgb_w, rgb_b))
     B, R, _, mid = h.shape
     assert w3.shape[0] == 128 and w3.size == 128 * mid and rgb_w.shape == (3, 128, 3, 3) and b3.shape == bn_a.shape == bn_s.shape == (128,)
     assert x0.shape == (B, R // 2, R // 2, 128) and rgb_b.shape == (3,)
     y = np.empty((B, 3, R, R), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_bg_tail.argtypes = [C.c_int32] * 4 + [fp] * 9
     _check(lib, lib.glass_op_bg_tail(device, B, R, mid, _fp(h), _fp(x0), _fp(w3), _fp(b3), _fp(bn_a), _fp(bn_s), _fp(rgb_w), _fp(rgb_b), _fp(y)))
     return y
 
@@ -552,22 +582,20 @@ def bg_tail(h, x0, w3, b3, bn_a, bn_s, rgb_w, rgb_b, device=0):
 # ---- CLIP's ResNet towers (glass_op_rn_*): each piece as the tower's walker launches it; BatchNorm as fp32 scale bn_a / shift bn_s ----
 def rn_avgpool(x, device=0):
     """AvgPool2d(2) of x [B,H,W,C] -> [B,H/2,W/2,C]."""
-    lib = load_library()
+    lib = _lib()
     x = _f32(x)
     B, H, W, Cc = x.shape
     out = np.empty((B, H // 2, W // 2, Cc), np.float32)
-    lib.glass_op_rn_avgpool.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_float)] * 2
     _check(lib, lib.glass_op_rn_avgpool(device, B, H, W, Cc, _fp(x), _fp(out)))
     return out
 
 
 def rn_stem_conv1(img, w, bn_a, bn_s, device=0):
     """img [B,3,S,S], w [C1,3,3,3] -> relu(bn(conv 3x3 stride 2 pad 1)) [B,S/2,S/2,C1], read through the 32-pixel patch operand."""
-    lib = load_library()
+    lib = _lib()
     img, w, bn_a, bn_s = _f32(img), _f32(w), _f32(bn_a), _f32(bn_s)
     B, S, C1 = img.shape[0], img.shape[2], w.shape[0]
     out = np.empty((B, S // 2, S // 2, C1), np.float32)
-    lib.glass_op_rn_stem_conv1.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_float)] * 5
     _check(lib, lib.glass_op_rn_stem_conv1(device, B, S, C1, _fp(img), _fp(w), _fp(bn_a), _fp(bn_s), _fp(out)))
     return out
 
@@ -575,13 +603,12 @@ def rn_stem_conv1(img, w, bn_a, bn_s, device=0):
 def rn_conv_bn(x, w, bn_a, bn_s, res=None, relu=True, form=0, device=0):
     """act(conv(x, w) * bn_a + bn_s (+ res)), x [B,H,W,Cin], w [Cout,Cin,KS,KS] (KS 1 or 3, stride 1, pad KS // 2).  form 0: gemm_tiled as the
     bottlenecks run it; form 1: the stem's 3 x 3 kernel."""
-    lib = load_library()
+    lib = _lib()
     x, w, bn_a, bn_s = _f32(x), _f32(w), _f32(bn_a), _f32(bn_s)
     B, H, W, Cin = x.shape
     Cout, KS = w.shape[0], w.shape[2]
     r, rp = _opt(res)
     out = np.empty((B, H, W, Cout), np.float32)
-    lib.glass_op_rn_conv_bn.argtypes = [C.c_int32] * 9 + [C.POINTER(C.c_float)] * 6
     _check(lib, lib.glass_op_rn_conv_bn(device, int(form), B, H, W, Cin, Cout, KS, int(bool(relu)), _fp(x), _fp(w), _fp(bn_a), _fp(bn_s), rp,
                                         _fp(out)))
     return out
@@ -589,11 +616,10 @@ def rn_conv_bn(x, w, bn_a, bn_s, res=None, relu=True, form=0, device=0):
 
 def rn_tokens(x, pos, device=0):
     """x [B,HW,C], pos [HW+1,C] -> the attention pool's tokens [B,HW+1,C]."""
-    lib = load_library()
+    lib = _lib()
     x, pos = _f32(x), _f32(pos)
     B, HW, Cc = x.shape
     out = np.empty((B, HW + 1, Cc), np.float32)
-    lib.glass_op_rn_tokens.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_float)] * 3
     _check(lib, lib.glass_op_rn_tokens(device, B, HW, Cc, _fp(x), _fp(pos), _fp(out)))
     return out
 
@@ -602,57 +628,52 @@ def rn_tokens(x, pos, device=0):
 # ---- perceptual objective (csrc/lpips.hip) ----
 def lpips_input(y, S, device=0):
     """y [B,3,R,R] fp32 -> [B,S,S,4]: box mean to S, (v - shift_c) / scale_c, rounded to fp16; channel 3 = 0."""
-    lib = load_library()
+    lib = _lib()
     y = _f32(y)
     B, _, R, _ = y.shape
     out = np.empty((B, S, S, 4), dtype=np.float32)
-    lib.glass_op_lpips_input.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_float)] * 2
     _check(lib, lib.glass_op_lpips_input(device, B, R, S, _fp(y), _fp(out)))
     return out
 
 
 def vgg_conv1(x, w, bias, device=0):
     """x [B,S,S,4] (lpips_input's layout), w [64,3,3,3], bias [64] -> relu(conv3x3 pad 1 + bias) [B,S,S,64]."""
-    lib = load_library()
+    lib = _lib()
     x, w, bias = _f32(x), _f32(w), _f32(bias)
     B, S = x.shape[0], x.shape[1]
     out = np.empty((B, S, S, 64), dtype=np.float32)
-    lib.glass_op_vgg_conv1.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_float)] * 4
     _check(lib, lib.glass_op_vgg_conv1(device, B, S, _fp(x), _fp(w), _fp(bias), _fp(out)))
     return out
 
 
 def maxpool2(x, device=0):
     """MaxPool2d(2) of x [B,H,W,C] -> [B,H/2,W/2,C]."""
-    lib = load_library()
+    lib = _lib()
     x = _f32(x)
     B, H, W, Cc = x.shape
     out = np.empty((B, H // 2, W // 2, Cc), dtype=np.float32)
-    lib.glass_op_maxpool2.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_float)] * 2
     _check(lib, lib.glass_op_maxpool2(device, B, H, W, Cc, _fp(x), _fp(out)))
     return out
 
 
 def lpips_head(x0, x1, lin, device=0):
     """x0 [n,HW,C], x1 [n,HW,C] or [1,HW,C] (one map for all), lin [C] -> [n]: one slice's term of the distance."""
-    lib = load_library()
+    lib = _lib()
     x0, x1, lin = _f32(x0), _f32(x1), _f32(lin)
     n, HW, Cc = x0.shape
     shared = int(x1.shape[0] == 1 and n > 1)
     out = np.empty((n,), dtype=np.float32)
-    lib.glass_op_lpips_head.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_float)] * 4
     _check(lib, lib.glass_op_lpips_head(device, n, HW, Cc, shared, _fp(x0), _fp(x1), _fp(lin), _fp(out)))
     return out
 
 
-_FP, _IP = C.POINTER(C.c_float), C.POINTER(C.c_int32)
 MAP_FUSED, MAP_PIXELNORM, MAP_SPLITK, MAP_DENSE = 1, 2, 4, 8
 MAPPING_PATHS = {"auto": 0, "layers": 1, "fused": 2}
 
 
 def _i32(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
-    return a, a.ctypes.data_as(_IP)
+    return a, a.ctypes.data_as(ip)
 
 
 def _strided(a, ld, fill=np.nan):
@@ -667,24 +688,22 @@ def mapping(z, wt, b, path="auto", device=0):
     """The mapping network through the launcher run_mapping calls: z [P, L], wt [n_layers, L, L] (each [k, n], coefficient folded), b
     [n_layers, L] -> (w [P, L], the set of kernels that ran).  path "auto": as the engine decides; "layers": pixel norm + one dense launch
     per layer; "fused": mapping_fused_kernel or an error."""
-    lib = load_library()
+    lib = _lib()
     z, wt, b = _f32(z), _f32(wt), _f32(b)
     P, L = z.shape
     n = wt.shape[0]
     assert wt.shape == (n, L, L) and b.shape == (n, L)
     out = np.empty((P, L), dtype=np.float32)
     ran = C.c_int32(0)
-    lib.glass_op_mapping.argtypes = [C.c_int32] * 4 + [_FP] * 3 + [C.c_int32, _FP, _IP]
     _check(lib, lib.glass_op_mapping(device, P, L, n, _fp(z), _fp(wt), _fp(b), MAPPING_PATHS[path], _fp(out), C.byref(ran)))
     names = {MAP_FUSED: "mapping_fused_kernel", MAP_PIXELNORM: "pixelnorm_kernel", MAP_SPLITK: "dense_splitk_kernel", MAP_DENSE: "dense_kernel"}
     return out, {v for k, v in names.items() if ran.value & k}
 
 
 def pixelnorm(z, device=0):
-    lib = load_library()
+    lib = _lib()
     z = _f32(z)
     out = np.empty_like(z)
-    lib.glass_op_pixelnorm.argtypes = [C.c_int32] * 3 + [_FP, _FP]
     _check(lib, lib.glass_op_pixelnorm(device, z.shape[0], z.shape[1], _fp(z), _fp(out)))
     return out
 
@@ -692,7 +711,7 @@ def pixelnorm(z, device=0):
 def dense_splitk(x, wt, bias=None, mode=0, ldx=None, ldo=None, device=0):
     """dense_splitk_kernel on x [P, K] stored with row stride ldx (NaN between the rows) -> the whole output table [P, ldo]; the columns
     past N come back as the NaN they were uploaded with."""
-    lib = load_library()
+    lib = _lib()
     wt = _f32(wt)
     P, K = np.shape(x)
     N = wt.shape[1]
@@ -700,7 +719,6 @@ def dense_splitk(x, wt, bias=None, mode=0, ldx=None, ldo=None, device=0):
     xb = _strided(x, ldx)
     out = np.full((P, ldo), np.nan, dtype=np.float32)
     bb, bp = _opt(bias)
-    lib.glass_op_dense_splitk.argtypes = [C.c_int32] * 7 + [_FP] * 4
     _check(lib, lib.glass_op_dense_splitk(device, P, K, N, ldx, ldo, mode, _fp(xb), _fp(wt), bp, _fp(out)))
     return out
 
@@ -709,7 +727,7 @@ def dense_ex(x, wt, bias=None, in_sq=False, mode=0, eps_row=None, ldx=None, out=
     """dense_kernel with the strides the style path uses: x [P, K] stored with row stride ldx (NaN between the rows); the result goes to
     columns col0 .. col0 + N of the table `out` [P, ldo] (default: a NaN table of width N), which is returned whole.  eps_row [P, stride]:
     mode 2 reads column 0."""
-    lib = load_library()
+    lib = _lib()
     wt = _f32(wt)
     P, K = np.shape(x)
     N = wt.shape[1]
@@ -721,16 +739,15 @@ def dense_ex(x, wt, bias=None, in_sq=False, mode=0, eps_row=None, ldx=None, out=
     e, ep = _opt(None if eps_row is None else np.reshape(eps_row, (P, -1)))
     buf = np.concatenate([out.reshape(-1), np.full(col0, np.nan, np.float32)])
     win = buf[col0:]                                    # the launch's `out` pointer is column col0 of row 0: [P, ldo] floats from there on
-    lib.glass_op_dense_ex.argtypes = [C.c_int32] * 6 + [_FP] * 3 + [C.c_int32, C.c_int32, _FP, C.c_int32, _FP]
     _check(lib, lib.glass_op_dense_ex(device, P, K, N, xb.shape[1], ldo, _fp(xb), _fp(wt), bp, int(in_sq), mode, ep,
-                                      0 if e is None else e.shape[1], win.ctypes.data_as(_FP)))
+                                      0 if e is None else e.shape[1], win.ctypes.data_as(fp)))
     return buf[:out.size].reshape(out.shape)
 
 
 def dense_multi(x, problems, eps_rows, ldo, device=0):
     """The demodulation launch (dense_multi_kernel, in_sq 1, mode 2): x [P, ldx] the shared style table, problems a list of (x_off, wt [K, N],
     out_off, eps_idx), eps_rows [P, n_style] -> the output table [P, ldo] (NaN where no problem writes)."""
-    lib = load_library()
+    lib = _lib()
     x, eps_rows = _f32(x), _f32(eps_rows)
     P, ldx = x.shape
     wts = [_f32(q[1]) for q in problems]
@@ -738,7 +755,6 @@ def dense_multi(x, problems, eps_rows, ldo, device=0):
     xo, xop = _i32([q[0] for q in problems]); oo, oop = _i32([q[2] for q in problems]); ei, eip = _i32([q[3] for q in problems])
     wt = np.concatenate([w.reshape(-1) for w in wts])
     out = np.full((P, ldo), np.nan, dtype=np.float32)
-    lib.glass_op_dense_multi.argtypes = [C.c_int32] * 6 + [_IP] * 5 + [_FP] * 4
     _check(lib, lib.glass_op_dense_multi(device, len(problems), P, ldx, ldo, eps_rows.shape[1], Kp, Np, xop, oop, eip, _fp(x), _fp(wt),
                                          _fp(eps_rows), _fp(out)))
     return out
@@ -746,13 +762,12 @@ def dense_multi(x, problems, eps_rows, ldo, device=0):
 
 def style_norm(s, segments, device=0):
     """style_norm_kernel (eps 1e-8) over the (offset, length) segments of each row of s [P, ld] -> (s normalised, smax [P, n], eps_row [P, n])."""
-    lib = load_library()
+    lib = _lib()
     s = np.array(s, dtype=np.float32, order="C")
     P, ld = s.shape
     off, offp = _i32([q[0] for q in segments]); ln, lnp = _i32([q[1] for q in segments])
     n = len(segments)
     smax, eps_row = np.empty((P, n), np.float32), np.empty((P, n), np.float32)
-    lib.glass_op_style_norm.argtypes = [C.c_int32] * 4 + [_IP, _IP] + [_FP] * 3
     _check(lib, lib.glass_op_style_norm(device, P, ld, n, offp, lnp, _fp(s), _fp(smax), _fp(eps_row)))
     return s, smax, eps_row
 
@@ -760,171 +775,154 @@ def style_norm(s, segments, device=0):
 def d_head(dfin, w0, b0, w1, b1, device=0):
     """D's dense head through the launchers run_d_head calls: dfin [P, 16 CL], w0 [CL, 16 CL] (both rounded to fp16 on upload), b0 [CL],
     w1 [CL], b1 [1] -> (dis [P], "split" | "whole": the form that ran)."""
-    lib = load_library()
+    lib = _lib()
     dfin, w0, b0, w1, b1 = (_f32(a) for a in (dfin, w0, b0, w1, b1))
     P, CL = dfin.shape[0], w0.shape[0]
     assert dfin.shape == (P, 16 * CL) and w0.shape == (CL, 16 * CL) and b0.shape == (CL,) and w1.shape == (CL,) and b1.shape == (1,)
     dis = np.empty(P, dtype=np.float32)
     split = C.c_int32(-1)
-    lib.glass_op_d_head.argtypes = [C.c_int32] * 3 + [_FP] * 6 + [_IP]
     _check(lib, lib.glass_op_d_head(device, P, CL, _fp(dfin), _fp(w0), _fp(b0), _fp(w1), _fp(b1), _fp(dis), C.byref(split)))
     return dis, "split" if split.value == 1 else "whole"
 
 
 def finalize_image(y, device=0):
-    lib = load_library()
+    lib = _lib()
     y = _f32(y)
     img = np.empty_like(y)
-    lib.glass_op_finalize_image.argtypes = [C.c_int32, C.c_int64, _FP, _FP]
     _check(lib, lib.glass_op_finalize_image(device, y.size, _fp(y), _fp(img)))
     return img
 
 
 def embed_lnpre(patch_emb, cls, pos, g, b, device=0):
     """patch_emb [P, T - 1, D], cls [D], pos [T, D], ln_pre g / b [D] -> tokens [P, T, D]."""
-    lib = load_library()
+    lib = _lib()
     patch_emb, cls, pos, g, b = (_f32(a) for a in (patch_emb, cls, pos, g, b))
     P, T1, D = patch_emb.shape
     assert pos.shape == (T1 + 1, D)
     x = np.empty((P, T1 + 1, D), dtype=np.float32)
-    lib.glass_op_embed_lnpre.argtypes = [C.c_int32] * 4 + [_FP] * 6
     _check(lib, lib.glass_op_embed_lnpre(device, P, T1 + 1, D, _fp(patch_emb), _fp(cls), _fp(pos), _fp(g), _fp(b), _fp(x)))
     return x
 
 
 def embed_text(tokens, tok_emb, pos, device=0):
     """tokens int [n, ctx], tok_emb [V, D], pos [ctx, D] -> [n * ctx, D]."""
-    lib = load_library()
+    lib = _lib()
     tok, tokp = _i32(tokens)
     tok_emb, pos = _f32(tok_emb), _f32(pos)
     n, ctx = tok.shape
     V, D = tok_emb.shape
     x = np.empty((n * ctx, D), dtype=np.float32)
-    lib.glass_op_embed_text.argtypes = [C.c_int32] * 5 + [_IP, _FP, _FP, _FP]
     _check(lib, lib.glass_op_embed_text(device, n, ctx, D, V, tokp, _fp(tok_emb), _fp(pos), _fp(x)))
     return x
 
 
 def layernorm_ex(x, g, b, row_stride=None, half_out=False, device=0):
     """layernorm_kernel on the rows of x [M, D] stored row_stride apart (NaN between them); half_out: the fp16 output (as float32 values)."""
-    lib = load_library()
+    lib = _lib()
     g, b = _f32(g), _f32(b)
     M, D = np.shape(x)
     xb = _strided(x, row_stride or D)
     out = np.empty((M, D), dtype=np.float32)
-    lib.glass_op_layernorm_ex.argtypes = [C.c_int32] * 3 + [C.c_int64, C.c_int32] + [_FP] * 4
     _check(lib, lib.glass_op_layernorm_ex(device, M, D, xb.shape[1], int(half_out), _fp(xb), _fp(g), _fp(b), _fp(out)))
     return out
 
 
 def layernorm_rows(x, rows, g, b, device=0):
-    lib = load_library()
+    lib = _lib()
     x, g, b = _f32(x), _f32(g), _f32(b)
     r, rp = _i32(rows)
     out = np.empty((r.shape[0], x.shape[1]), dtype=np.float32)
-    lib.glass_op_layernorm_rows.argtypes = [C.c_int32] * 4 + [_FP, _IP, _FP, _FP, _FP]
     _check(lib, lib.glass_op_layernorm_rows(device, x.shape[0], r.shape[0], x.shape[1], _fp(x), rp, _fp(g), _fp(b), _fp(out)))
     return out
 
 
 def cosine(feat, target, device=0):
-    lib = load_library()
+    lib = _lib()
     feat, target = _f32(feat), _f32(target)
     P, D = feat.shape
     sim = np.empty(P, dtype=np.float32)
-    lib.glass_op_cosine.argtypes = [C.c_int32] * 3 + [_FP] * 3
     _check(lib, lib.glass_op_cosine(device, P, D, _fp(feat), _fp(target), _fp(sim)))
     return sim
 
 
 def cosine_views(feat, target, device=0):
     """feat [P, V, D] -> (view_sim [P, V], sim [P])."""
-    lib = load_library()
+    lib = _lib()
     feat, target = _f32(feat), _f32(target)
     P, V, D = feat.shape
     vs, sim = np.empty((P, V), np.float32), np.empty(P, np.float32)
-    lib.glass_op_cosine_views.argtypes = [C.c_int32] * 4 + [_FP] * 4
     _check(lib, lib.glass_op_cosine_views(device, P, V, D, _fp(feat), _fp(target), _fp(vs), _fp(sim)))
     return vs, sim
 
 
 def cosine_set(feat, targets, weights, device=0):
     """feat [P, V, D], targets [T, D], weights [T] -> (view_sim [P, V], set_sim [P, T], sim [P]): cosine_set_kernel (prompt sets)."""
-    lib = load_library()
+    lib = _lib()
     feat, targets, weights = _f32(feat), _f32(targets), _f32(weights)
     P, V, D = feat.shape
     T = targets.shape[0]
     vs, ss, sim = np.empty((P, V), np.float32), np.empty((P, T), np.float32), np.empty(P, np.float32)
-    lib.glass_op_cosine_set.argtypes = [C.c_int32] * 5 + [_FP] * 6
     _check(lib, lib.glass_op_cosine_set(device, P, V, T, D, _fp(feat), _fp(targets), _fp(weights), _fp(vs), _fp(ss), _fp(sim)))
     return vs, ss, sim
 
 
 def assemble_F_set(set_sim, weights, dis=None, lp=None, device=0):
     """set_sim [P, K], weights [K], dis / lp [P] or None -> F [P, K + (dis is not None) + (lp is not None)]: the pareto layout."""
-    lib = load_library()
+    lib = _lib()
     set_sim, weights = _f32(set_sim), _f32(weights)
     P, K = set_sim.shape
     d, dp = _opt(dis)
     l, lpp = _opt(lp)
     Fv = np.empty((P, K + (dis is not None) + (lp is not None)), dtype=np.float32)
-    lib.glass_op_assemble_F_set.argtypes = [C.c_int32] * 3 + [_FP] * 5
     _check(lib, lib.glass_op_assemble_F_set(device, P, K, _fp(set_sim), _fp(weights), dp, lpp, _fp(Fv)))
     return Fv
 
 
 def assemble_F(sim, dis=None, device=0):
-    lib = load_library()
+    lib = _lib()
     sim = _f32(sim)
     d, dp = _opt(dis)
     n_obj = 1 if dis is None else 2
     Fv = np.empty((sim.shape[0], n_obj), dtype=np.float32)
-    lib.glass_op_assemble_F.argtypes = [C.c_int32] * 3 + [_FP] * 3
     _check(lib, lib.glass_op_assemble_F(device, sim.shape[0], n_obj, _fp(sim), dp, _fp(Fv)))
     return Fv
 
 
 def image_patches(img, ps, ld, sentinel=-7.0, device=0):
     """img [n, 3, S, S] -> the patch operand [n (S / ps)^2, ld] as fp16 values; the columns the kernel does not write hold `sentinel`."""
-    lib = load_library()
+    lib = _lib()
     img = _f32(img)
     n, _, S, _ = img.shape
     G = S // ps
     out = np.empty((n * G * G, ld), dtype=np.float32)
-    lib.glass_op_image_patches.argtypes = [C.c_int32] * 5 + [_FP, C.c_float, _FP]
     _check(lib, lib.glass_op_image_patches(device, n, S, ps, ld, _fp(img), float(sentinel), _fp(out)))
     return out
 
 
 def rn_token0_rows(att, device=0):
     """att [B, T, C] (rounded to fp16) -> [B, C] float32 = att[:, 0, :]."""
-    lib = load_library()
+    lib = _lib()
     att = _f32(att)
     B, T, Cc = att.shape
     out = np.empty((B, Cc), dtype=np.float32)
-    lib.glass_op_rn_token0_rows.argtypes = [C.c_int32] * 4 + [_FP, _FP]
     _check(lib, lib.glass_op_rn_token0_rows(device, B, T, Cc, _fp(att), _fp(out)))
     return out
 
 
 def mfma_probe(a, b, device=0):
-    lib = load_library()
+    lib = _lib()
     a, b = _f32(a), _f32(b)
     d = np.empty((32, 32), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_op_mfma_probe.argtypes = [C.c_int32, fp, fp, fp]
     _check(lib, lib.glass_op_mfma_probe(device, _fp(a), _fp(b), _fp(d)))
     return d
 
 
 def host_pack_conv(w, up=False):
     """finalize()'s weight repacking, host only: returns [KS*KS][Neff][Cin] float32 (fp16-rounded)."""
-    lib = load_library()
+    lib = _lib()
     w = _f32(w)
     Cout, Cin, KS, _ = w.shape
     out = np.empty((KS * KS, (4 if up else 1) * Cout, Cin), dtype=np.float32)
-    fp = C.POINTER(C.c_float)
-    lib.glass_host_pack_conv.argtypes = [fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]
     _check(lib, lib.glass_host_pack_conv(_fp(w), Cout, Cin, KS, int(up), _fp(out)))
     return out
 
@@ -935,11 +933,9 @@ RESIZE_MAX_TAPS = 32      # GLASS_RESIZE_MAX_TAPS (csrc/kernels.h): taps per out
 def host_resize_taps(R, S, mode, max_taps=RESIZE_MAX_TAPS):
     """finalize()'s tap table of one axis of the antialiased resize R -> S (mode 1 bilinear, 2 bicubic), host only:
     (start int32 [S], count int32 [S], taps float32 [S, max_taps])."""
-    lib = load_library()
+    lib = _lib()
     start, count = np.empty(S, np.int32), np.empty(S, np.int32)
     taps = np.empty((S, max_taps), np.float32)
-    ip = C.POINTER(C.c_int32)
-    lib.glass_host_resize_taps.argtypes = [C.c_int32] * 3 + [ip, ip, C.POINTER(C.c_float), C.c_int32]
     _check(lib, lib.glass_host_resize_taps(R, S, int(mode), start.ctypes.data_as(ip), count.ctypes.data_as(ip), _fp(taps), max_taps))
     return start, count, taps
 
@@ -947,9 +943,8 @@ def host_resize_taps(R, S, mode, max_taps=RESIZE_MAX_TAPS):
 def host_gpt2_step_plan(P, D, V, n_layer, Tmax, sample=False, n_cu=256):
     """The launches of one GPT-2 token step as the engine's host code makes them, host only: a list of (kernel name, grid (x, y, z),
     block (x, y, z)) in launch order.  n_cu: the compute units the step products' grids are weighed against."""
-    lib = load_library()
+    lib = _lib()
     buf = C.create_string_buffer(1 << 16)
-    lib.glass_host_gpt2_step_plan.argtypes = [C.c_int32] * 7 + [C.c_char_p, C.c_int32]
     _check(lib, lib.glass_host_gpt2_step_plan(P, D, V, n_layer, Tmax, int(bool(sample)), n_cu, buf, len(buf)))
     plan = []
     for line in buf.value.decode().splitlines():
@@ -961,10 +956,8 @@ def host_gpt2_step_plan(P, D, V, n_layer, Tmax, sample=False, n_cu=256):
 def host_gpt2_gemm_choice(M, N, K, ln=False, width=None, n_cu=256):
     """choose_gemm_f32_step's answer for a [M, K] x [N, K]^T step product, host only: (S, NK) — the global K split (0: refused) and the K parts
     per workgroup — with the split-K scratch gpt2_gemm gives it (width: as there) on a device of n_cu compute units."""
-    lib = load_library()
+    lib = _lib()
     S, NK = C.c_int32(-1), C.c_int32(-1)
-    ip = C.POINTER(C.c_int32)
-    lib.glass_host_gpt2_gemm_choice.argtypes = [C.c_int32] * 7 + [ip, ip]
     _check(lib, lib.glass_host_gpt2_gemm_choice(M, N, K, K, int(bool(ln)), int(width or min(N, K)), n_cu, C.byref(S), C.byref(NK)))
     return S.value, NK.value
 
@@ -972,16 +965,14 @@ def host_gpt2_gemm_choice(M, N, K, ln=False, width=None, n_cu=256):
 # ---- device search (csrc/search.hip; include/glass.h "Device search") ------------------------------------------------------------
 def ga_vary(X, rank, cd, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, seed=1, generation=1, row0=0, rows=None, device=0):
     """Offspring rows [row0, row0 + rows) of the population X float32 [pop, n_var] with rank int32 [pop] and cd float64 [pop]."""
-    lib = load_library()
+    lib = _lib()
     X = _f32(X)
     pop, nv = X.shape
     rows = pop - row0 if rows is None else rows
     rank = np.ascontiguousarray(rank, dtype=np.int32)
     cd = np.ascontiguousarray(cd, dtype=np.float64)
     out = np.empty((rows, nv), dtype=np.float32)
-    lib.glass_op_ga_vary.argtypes = ([C.c_int32] * 3 + [_FP, C.POINTER(C.c_int32), C.POINTER(C.c_double)] + [C.c_double] * 5 + [C.c_uint64] +
-                                     [C.c_int32] * 3 + [_FP])
-    _check(lib, lib.glass_op_ga_vary(device, pop, nv, _fp(X), rank.ctypes.data_as(C.POINTER(C.c_int32)), cd.ctypes.data_as(C.POINTER(C.c_double)),
+    _check(lib, lib.glass_op_ga_vary(device, pop, nv, _fp(X), rank.ctypes.data_as(ip), cd.ctypes.data_as(dp),
                                      float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                      int(generation), int(row0), int(rows), _fp(out)))
     return out
@@ -989,21 +980,19 @@ def ga_vary(X, rank, cd, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, seed=1, gener
 
 def ga_duplicates(X, Xoff, device=0):
     """flags int32 [n_off]: offspring row equals a population row or an offspring row below it."""
-    lib = load_library()
+    lib = _lib()
     X, Xoff = _f32(X), _f32(Xoff)
     flags = np.empty((Xoff.shape[0],), dtype=np.int32)
-    lib.glass_op_ga_duplicates.argtypes = [C.c_int32] * 4 + [_FP, _FP, C.POINTER(C.c_int32)]
-    _check(lib, lib.glass_op_ga_duplicates(device, X.shape[0], Xoff.shape[0], X.shape[1], _fp(X), _fp(Xoff), flags.ctypes.data_as(C.POINTER(C.c_int32))))
+    _check(lib, lib.glass_op_ga_duplicates(device, X.shape[0], Xoff.shape[0], X.shape[1], _fp(X), _fp(Xoff), flags.ctypes.data_as(ip)))
     return flags
 
 
 def ga_survive(F, n_pop, pop_out, nsga=True, flags=None, X=None, device=0):
     """Survival over the merged rows F float32 [n_pop + n_off, n_obj] -> dict(chosen, rank, cd, F, counts[, X]); X: merged rows [N, n_var]."""
-    lib = load_library()
+    lib = _lib()
     F = _f32(F)
     N, M = F.shape
     n_off = N - n_pop
-    ip = C.POINTER(C.c_int32)
     fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.int32)
     out = dict(chosen=np.empty((pop_out,), np.int32), rank=np.empty((pop_out,), np.int32), cd=np.empty((pop_out,), np.float64),
                F=np.empty((pop_out, M), np.float32), counts=np.empty((2,), np.int32))
@@ -1013,9 +1002,8 @@ def ga_survive(F, n_pop, pop_out, nsga=True, flags=None, X=None, device=0):
         nv = X.shape[1]
         Xp, Xo = np.ascontiguousarray(X[:n_pop]), np.ascontiguousarray(X[n_pop:])
         Xout = out["X"] = np.empty((pop_out, nv), np.float32)
-    lib.glass_op_ga_survive.argtypes = [C.c_int32] * 6 + [_FP, ip, ip, ip, C.POINTER(C.c_double), _FP, ip, C.c_int32, _FP, _FP, _FP]
     _check(lib, lib.glass_op_ga_survive(device, n_pop, n_off, M, pop_out, int(bool(nsga)), _fp(F), None if fl is None else fl.ctypes.data_as(ip),
-                                        out["chosen"].ctypes.data_as(ip), out["rank"].ctypes.data_as(ip), out["cd"].ctypes.data_as(C.POINTER(C.c_double)),
+                                        out["chosen"].ctypes.data_as(ip), out["rank"].ctypes.data_as(ip), out["cd"].ctypes.data_as(dp),
                                         _fp(out["F"]), out["counts"].ctypes.data_as(ip), nv, None if Xp is None else _fp(Xp),
                                         None if Xo is None or not n_off else _fp(Xo), None if Xout is None else _fp(Xout)))
     return out

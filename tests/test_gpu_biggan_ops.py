@@ -423,8 +423,7 @@ def test_biggan_ops_refuse_unsupported_forms_by_name():
         d.B, d.H, d.W, d.Cin, d.Cout, d.KS, d.stride, d.pad, d.Ho, d.Wo, d.in_up, d.impl = 2, 7, 64, 128, 128, 3, 1, 1, 7, 64, 1, 2
         d.out_scale, d.batch_size = 1.0, 1
         d.x, d.w, d.y = ops._fp(xs), ops._fp(ws), ops._fp(ys)
-        lib = ops.load_library()
-        lib.glass_op_conv.argtypes = [ops.C.c_int32, ops.C.POINTER(ops.ConvDesc)]
+        lib = ops._lib()
         ops._check(lib, lib.glass_op_conv(0, ops.C.byref(d)))
     ops.conv(x, w, impl=5)                                  # conv_glds takes the plain layer ...
     with pytest.raises(RuntimeError, match="LDS-DMA conv: unsupported shape"):
