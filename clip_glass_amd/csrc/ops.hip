@@ -328,6 +328,9 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     return st.fetch(d->y, y);
 }
 
+// the rows behind an output that no GEMM / attention kernel may touch (one whole m tile of the widest kernel)
+constexpr size_t GUARD_ROWS = 128;
+
 extern "C" int glass_op_gemm(int32_t device, int32_t M, int32_t N, int32_t K, const float* a, const float* w,
                              const float* bias, int32_t mode, int32_t impl, float* out) {
     OPREQ(a && w && out && K % 16 == 0, "bad argument");
@@ -339,10 +342,61 @@ extern "C" int glass_op_gemm(int32_t device, int32_t M, int32_t N, int32_t K, co
     const size_t n = (size_t)M * N;
     Buf<half_t> o16;
     Buf<float> o32;
-    if (mode <= 1) g.out16 = o16 = st.raw<half_t>(n);
-    else g.out32 = o32 = mode == 2 ? st.in32(out, n) : st.raw<float>(n);
+    if (mode <= 1) g.out16 = o16 = st.poisoned<half_t>(n, GUARD_ROWS * N);
+    else {
+        g.out32 = o32 = st.poisoned<float>(n, GUARD_ROWS * N);
+        if (mode == 2) st.put(o32, 0, out, n);
+    }
     TRY(st.run([&] { return launch_gemm_impl(g, impl); }));
-    return o16 ? st.fetch(out, o16) : st.fetch(out, o32);
+    TRY(o16 ? st.fetch(out, o16) : st.fetch(out, o32));
+    return o16 ? st.intact(o16, "gemm: a store behind the output (row >= M)") : st.intact(o32, "gemm: a store behind the output (row >= M)");
+}
+
+// what gemm_direct implements of GemmParams: not the `ld` split-K slices, not the BatchNorm epilogue, not the implicit patch matrix
+static bool gemm_direct_implements(const GemmParams& g) { return !g.ld && g.mode != 5 && !g.g_on; }
+
+extern "C" int glass_op_gemm_ex(int32_t device, int32_t batch, int32_t M, int32_t N, int32_t K, int32_t ldo, const float* a, const float* w,
+                                const float* bias, int32_t mode, int32_t impl, int32_t cand_rows, int32_t cand_batch, float* out, char* kernel,
+                                int32_t cap) {
+    OPREQ(a && w && out && kernel, "null argument");
+    OPREQ(batch >= 1 && M > 0 && N > 0 && K > 0 && K % 16 == 0 && ldo >= N, "bad shape (batch >= 1, K a multiple of 16, ldo >= N)");
+    OPREQ(mode >= 0 && mode <= 4, "mode must lie in [0, 4] (mode 5, the BatchNorm epilogue, and the ld split-K form are gemm_tiled's alone: glass_op_rn_conv_bn, glass_op_d_head)");
+    OPREQ(impl >= 0 && impl <= 2, "impl must lie in [0, 2]");
+    OPREQ(cand_rows >= 0 && cap >= 64, "cand_rows >= 0, room for 64 characters of kernel name");
+    kernel[0] = 0;
+    Stage st(device);
+    const size_t n = (size_t)batch * M * ldo, guard = GUARD_ROWS * ldo;
+    GemmParams g = gemm_params(st.in16(a, (size_t)batch * M * K), st.in16(w, (size_t)batch * N * K), M, N, K, st.in32(bias, N), mode, nullptr, nullptr, cand_rows);
+    g.ldo = ldo;
+    g.cand_batch = cand_batch ? 1 : 0;
+    g.batch = batch; g.a_bs = (long long)M * K; g.w_bs = (long long)N * K; g.o_bs = (long long)M * ldo;
+    // the whole [batch][M][ldo] array travels in (mode 2's accumulator, the ldo padding, the caller's sentinels) and comes back
+    Buf<half_t> o16;
+    Buf<float> o32;
+    if (mode <= 1) {
+        std::vector<_Float16> h(n);
+        for (size_t i = 0; i < n; ++i) h[i] = (_Float16)out[i];      // (a NaN stays a NaN)
+        g.out16 = o16 = st.poisoned<half_t>(n, guard);
+        st.put(o16, 0, h.data(), n);
+    } else {
+        g.out32 = o32 = st.poisoned<float>(n, guard);
+        st.put(o32, 0, out, n);
+    }
+    const char* name = nullptr;
+    const int rc = st.run([&]() -> int {
+        if (impl != 1) name = launch_gemm_tiled(g, 0);
+        if (!name && impl == 2) OPREQ(false, "tiled gemm: unsupported shape");
+        if (!name) {
+            OPREQ(gemm_direct_implements(g), "gemm_tiled refused a form that gemm_direct does not implement");
+            name = launch_gemm_direct(g, 0);
+        }
+        return GLASS_OK;
+    });
+    if (rc == GLASS_OK || rc == GLASS_ERR_ARG) TRY(o16 ? st.fetch(out, o16) : st.fetch(out, o32));      // (a refusal: what no kernel touched)
+    if (rc) return rc;
+    snprintf(kernel, (size_t)cap, "%s", name);
+    return o16 ? st.intact(o16, GLASS_ERR_STATE, [&](size_t i) { return "gemm_ex: a store " + std::to_string(i) + " elements behind the output"; })
+               : st.intact(o32, GLASS_ERR_STATE, [&](size_t i) { return "gemm_ex: a store " + std::to_string(i) + " elements behind the output"; });
 }
 
 extern "C" int glass_op_gemm_batched(int32_t device, int32_t batch, int32_t M, int32_t N, int32_t K, const float* a, const float* w, int32_t mode,
@@ -537,9 +591,10 @@ extern "C" int glass_op_attention(int32_t device, int32_t n_img, int32_t L, int3
     Stage st(device);
     const int D = heads * 64;
     const auto dq = st.in16(qkv, (size_t)n_img * L * 3 * D);
-    const auto dout = st.raw<half_t>((size_t)n_img * L * D);
+    const auto dout = st.poisoned<half_t>((size_t)n_img * L * D, GUARD_ROWS * D);
     TRY(st.run([&] { launch_attention(dq, n_img, L, heads, 64, causal, dout, 0); }));
-    return st.fetch(out, dout);
+    TRY(st.fetch(out, dout));
+    return st.intact(dout, "attention: a store behind the output (token >= n_img L)");
 }
 
 extern "C" int glass_op_noise(int32_t device, int32_t n_mb, int32_t hw, uint32_t layer, uint32_t mb0,

@@ -39,6 +39,7 @@ SIGNATURES = {
     "glass_op_conv": [i32, C.POINTER(ConvDesc)],
     "glass_op_gemm": [i32, i32, i32, i32, fp, fp, fp, i32, i32, fp],
     "glass_op_gemm_batched": [i32, i32, i32, i32, i32, fp, fp, i32, i32, i32, fp],
+    "glass_op_gemm_ex": [i32, i32, i32, i32, i32, i32, fp, fp, fp, i32, i32, i32, i32, fp, C.c_char_p, i32],
     "glass_op_dense": [i32, i32, i32, i32, fp, fp, fp, i32, i32, fp, fp],
     "glass_op_torgb": [i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp],
     "glass_op_blur": [i32, i32, i32, i32, i32, fp, fp],
@@ -246,6 +247,28 @@ def gemm_batched(a, w, mode=3, cand_batch=True, impl=0, device=0):
     out = np.empty((batch, M, N), dtype=np.float32)
     _check(lib, lib.glass_op_gemm_batched(device, batch, M, N, K, _fp(a), _fp(w), int(mode), int(cand_batch), int(impl), _fp(out)))
     return out
+
+
+def gemm_ex(a, w, out, bias=None, mode=3, impl=2, cand_rows=0, cand_batch=False, device=0):
+    """a [M,K] / [batch,M,K], w [N,K] / [batch,N,K], bias [N] -> the name of the kernel that ran, exactly as the launcher returned it.  out
+    [M,ldo] / [batch,M,ldo] (C-contiguous float32, ldo >= N) is written IN PLACE: the device output is preloaded from it, so mode 2's
+    accumulator, the ldo padding and the caller's sentinels come back as the kernel left them — also when the call raises on a refusal.
+    impl 0: gemm_tiled, then gemm_direct where it refuses; 1: gemm_direct; 2: gemm_tiled, a refusal raises.  cand_rows / cand_batch: GemmParams'."""
+    lib = _lib()
+    a = _f32(a); w = _f32(w)
+    if a.ndim == 2:
+        a, w = a[None], w[None]
+    batch, M, K = a.shape
+    N = w.shape[1]
+    assert w.shape == (batch, N, K)
+    assert isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable
+    assert out.ndim >= 2 and out.size == batch * M * out.shape[-1], "out must be [batch, M, ldo]"
+    b, bp = _opt(bias)
+    assert b is None or b.shape == (N,)
+    name = C.create_string_buffer(128)
+    _check(lib, lib.glass_op_gemm_ex(device, batch, M, N, K, out.shape[-1], _fp(a), _fp(w), bp, int(mode), int(impl), int(cand_rows),
+                                     int(bool(cand_batch)), _fp(out), name, len(name)))
+    return name.value.decode()
 
 
 def dense(x, wt, bias=None, in_sq=False, mode=0, eps_row=None, device=0):

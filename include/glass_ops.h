@@ -6,7 +6,8 @@
  * the oracle's corresponding torch op in isolation.  All return GLASS_OK or a negative
  * status (glass_last_error()).  Layouts are NHWC for activations.
  *
- * Families: the convolution forms of the StyleGAN2 and BigGAN hosts (glass_op_conv), the GEMMs (glass_op_gemm, glass_op_gemm_batched),
+ * Families: the convolution forms of the StyleGAN2 and BigGAN hosts (glass_op_conv), the GEMMs (glass_op_gemm, glass_op_gemm_batched,
+ * glass_op_gemm_ex: every plain form with the launcher's answer; tests/test_gpu_vit_block_ops.py against tests/vit_block_ref.py),
  * the StyleGAN2 / CLIP glue kernels, the GPT-2 trunk (glass_op_gpt2_*) and the BigGAN-deep glue kernels and fused tail (glass_op_bg_*;
  * tests/test_gpu_biggan_ops.py against the float64 restatements of tests/biggan_ops_ref.py),
  * and the small fp32 kernels of the mapping network, the style path, D's dense head and the CLIP glue (tests/test_gpu_small_ops.py).
@@ -84,6 +85,16 @@ int glass_op_gemm(int32_t device, int32_t M, int32_t N, int32_t K, const float* 
  * impl 0: gemm_tiled, then gemm_direct where it refuses (as the host); 1: gemm_direct; 2: gemm_tiled (error if it refuses) */
 int glass_op_gemm_batched(int32_t device, int32_t batch, int32_t M, int32_t N, int32_t K, const float* a, const float* w, int32_t mode,
                           int32_t cand_batch, int32_t impl, float* out);
+/* Everything GemmParams exposes for the plain forms, with the launcher's answer: `batch` problems out[z] [M,ldo] = epi(a[z] [M,K] @ w[z] [N,K]^T
+ * + bias [N] (nullable, shared)), a_bs = M K / w_bs = N K / o_bs = M ldo elements apart, ldo >= N, modes 0 .. 4 as glass_op_gemm, cand_rows /
+ * cand_batch as GemmParams (what launch_gemm_tiled's fill rule looks at).  impl as glass_op_gemm_batched; with impl 0 a form that gemm_direct
+ * does not implement is an error, not a launch.  out [batch,M,ldo] is in and out: the device array is preloaded from it (rounded to fp16 for
+ * modes 0 / 1: a NaN stays a NaN), so mode 2's accumulator, the ldo padding and whatever the caller put where the kernel should store come
+ * back as the kernel left them — also after a refusal (GLASS_ERR_ARG), when nothing ran.  The device array is followed by 128 guard rows
+ * that no kernel may touch (GLASS_ERR_STATE).  kernel [cap >= 64] receives the name the launcher returned. */
+int glass_op_gemm_ex(int32_t device, int32_t batch, int32_t M, int32_t N, int32_t K, int32_t ldo, const float* a, const float* w,
+                     const float* bias, int32_t mode, int32_t impl, int32_t cand_rows, int32_t cand_batch, float* out, char* kernel,
+                     int32_t cap);
 int glass_op_dense(int32_t device, int32_t P, int32_t K, int32_t N, const float* x, const float* wt /*[K,N]*/,
                    const float* bias, int32_t in_sq, int32_t mode, const float* eps_row, float* out);
 int glass_op_torgb(int32_t device, int32_t B, int32_t H, int32_t C, const float* x, const float* wrgb /*[3,C] scaled*/,
