@@ -21,7 +21,16 @@ sum_t w_t sim_t / sum_t |w_t|; "pareto": one objective per entry, 2 to 4 — the
 entries + discriminator + LPIPS column and `algorithm` "nsga2") — the StyleGAN2 and BigGAN configs; refused for GPT2;
 `device_search` (False, the default: search.py's host operators; True: the population stays on the GPU and the generation step — tournament,
 SBX, polynomial mutation, duplicate flags, survival — runs there, include/glass.h "Device search") — the StyleGAN2 configs on one rank;
-refused for the BigGAN and GPT2 configs, whose rows are not all real."""
+refused for the BigGAN and GPT2 configs, whose rows are not all real;
+`edit_image` (unset, the default: off; a path or an array [3, H, W] in [0, 1], centre-cropped and resized to the generator's side as an image
+prompt is: the similarity becomes directional — how the generated image moved away from this source against how the target moved away
+from `source_text`, include/glass.h "Image editing"), `edit_latent` (a path to a .npy, or an array, of one row in the current latent space:
+the source image is generated from it, the row is the latent anchor — the mean squared distance between a candidate's dlatents and the
+row's — and generation 0 starts at it), `source_text` (what the source shows: required as soon as a source is set), `anchor_lambda` (0:
+the anchor distance is an objective of its own — the Generator then searches a copy of the config with `n_obj` one higher and `algorithm`
+"nsga2"; > 0: added to the similarity objective) and `edit_sigma` (0.1: the spread of generation 0 around the source row; row 0 is the
+source itself) — `edit_image` with the StyleGAN2 and BigGAN configs, `edit_latent` / `anchor_lambda` with the StyleGAN2 configs only; every
+key is refused for GPT2."""
 from .latent import DeepMindBigGANLatentSpace, GPT2LatentSpace, StyleGAN2LatentSpace
 from .models import GPT2, DeepMindBigGAN, StyleGAN2
 from .utils import biggan_denorm, biggan_norm

@@ -494,9 +494,16 @@ static void run_rn_blocks(glass_engine* e, int P, int l0, int l1) {
     }
 }
 static void clip_cosine(glass_engine* e, int P, int views) {      // the end of both towers' heads: d_feat [P][embed] against the target
+    if (views < 0) return;    // the features alone (the direction source's own encoding)
     const int E = e->cfg.clip_embed;
     const glass_engine::PromptSet& ps = e->pset;
-    if (ps.T > 0) {           // a prompt set: every row against every entry, still one launch
+    if (e->edit.has_source && ps.T > 0 && e->edit.d_src) {      // image editing: the set's entries are directions, the rows move away from the source's
+        const int V = std::max(views, 1);
+        if (!launch_cosine_set_dir(e->d_feat, ps.d_targets, ps.d_weights, ps.W, P / V, V, ps.T, E, e->edit.d_src, views > 0 ? e->d_view_sim : nullptr, ps.d_sim,
+                                   e->d_sim, e->cur) &&
+            e->launch_error.empty())
+            e->launch_error = "no kernel accepts layer clip.head (cosine_set_dir: shape outside its limits)";
+    } else if (ps.T > 0) {           // a prompt set: every row against every entry, still one launch
         const int V = std::max(views, 1);
         if (!launch_cosine_set(e->d_feat, ps.d_targets, ps.d_weights, ps.W, P / V, V, ps.T, E, views > 0 ? e->d_view_sim : nullptr, ps.d_sim, e->d_sim, e->cur) &&
             e->launch_error.empty())

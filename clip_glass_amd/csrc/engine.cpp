@@ -107,25 +107,30 @@ extern "C" int glass_engine_create(const glass_config* cfg, glass_engine** out) 
     const bool lpips = cfg->lpips_size != 0;      // the perceptual objective (opt-in): its own last column unless lpips_lambda folds it into column 0
     REQUIRE(cfg->sim_columns >= 0 && cfg->sim_columns <= 4, GLASS_ERR_ARG, "sim_columns must be 0 or 1 (one similarity column) or 2 .. 4 (a pareto prompt set)");
     const int K = sim_columns(*cfg);              // similarity columns: 1 unless the engine is made for a pareto prompt set
+    // the latent anchor (opt-in): its own rule, which counts every column; the rules below then see n_obj without the anchor's column
+    if (int erc = glass_edit_supported(cfg->generator, cfg->n_blocks, cfg->sim_columns, cfg->use_discriminator, lpips && cfg->lpips_lambda == 0.f, cfg->anchor,
+                                       cfg->anchor_lambda, cfg->n_obj))
+        return erc;
+    const int n_obj = cfg->n_obj - anchor_column(*cfg);
     if (K >= 2) {
         REQUIRE(!lpips || cfg->lpips_lambda == 0.f, GLASS_ERR_ARG,
                 "lpips_lambda > 0 folds the distance into THE similarity column; with sim_columns >= 2 there is no single one: use lpips_lambda = 0 (its own column)");
         const int want = K + (cfg->use_discriminator ? 1 : 0) + (lpips ? 1 : 0);
-        REQUIRE(cfg->n_obj == want, GLASS_ERR_ARG,
+        REQUIRE(n_obj == want, GLASS_ERR_ARG,
                 "with sim_columns >= 2, n_obj must be sim_columns + use_discriminator + (lpips_size > 0 && lpips_lambda == 0) = " + std::to_string(want) +
-                    ", got " + std::to_string(cfg->n_obj));
+                    ", got " + std::to_string(n_obj));
     }
     if (!lpips) {
-        REQUIRE(K >= 2 || cfg->n_obj == 1 || cfg->n_obj == 2, GLASS_ERR_ARG, "n_obj must be 1 or 2");
+        REQUIRE(K >= 2 || n_obj == 1 || n_obj == 2, GLASS_ERR_ARG, "n_obj must be 1 or 2");
     } else {
         REQUIRE(cfg->n_blocks > 0 || cfg->generator == GLASS_GEN_BIGGAN_DEEP, GLASS_ERR_ARG,
                 "lpips_size > 0 needs a generator: this engine has none (GPT-2 / img2txt), so there is no generated image to compare");
         if (int lrc = glass_lpips_supported(0, cfg->lpips_size)) return lrc;
         REQUIRE(std::isfinite(cfg->lpips_lambda) && cfg->lpips_lambda >= 0.f, GLASS_ERR_ARG, "lpips_lambda must be finite and >= 0");
         const int want = K + (cfg->use_discriminator ? 1 : 0) + (cfg->lpips_lambda == 0.f ? 1 : 0);
-        REQUIRE(cfg->n_obj == want, GLASS_ERR_ARG,
+        REQUIRE(n_obj == want, GLASS_ERR_ARG,
                 "with lpips_size > 0, n_obj must be 1 + use_discriminator + (lpips_lambda == 0) = " + std::to_string(want) + ", got " +
-                    std::to_string(cfg->n_obj));
+                    std::to_string(n_obj));
     }
     if (cfg->use_discriminator) {
         REQUIRE(cfg->mbstd_group >= 2 && cfg->mbstd_group <= 8 && cfg->batch_size % cfg->mbstd_group == 0, GLASS_ERR_ARG,
@@ -609,7 +614,14 @@ static int finish_pass(glass_engine* e, int P, float* out_F, bool clip_done, hip
             GLASS_HIP(hipEventRecord(e->ev_g[0], d_join));
             GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_g[0], 0));
         }
-        if (e->pset.T > 0 && e->pset.mode == 1)
+        if (c.anchor) {       // image editing: the layout with the anchor distance in it (its own last column, or folded into column 0)
+            const bool pareto = e->pset.T > 0 && e->pset.mode == 1;
+            if (!launch_assemble_F_edit(e->d_sim, pareto ? e->pset.d_sim : nullptr, pareto ? e->pset.d_weights : nullptr, pareto ? e->pset.T : 1,
+                                        c.use_discriminator ? e->d_dis : nullptr, c.lpips_size ? e->lp.d : nullptr, c.lpips_lambda, e->edit.d_dist, c.anchor_lambda, P,
+                                        c.n_obj, e->d_F, e->cur) &&
+                e->launch_error.empty())
+                e->launch_error = "no kernel accepts layer assemble_F (assemble_F_edit: the columns do not add up to n_obj)";
+        } else if (e->pset.T > 0 && e->pset.mode == 1)
             launch_assemble_F_set(e->pset.d_sim, e->pset.d_weights, c.use_discriminator ? e->d_dis : nullptr, c.lpips_size ? e->lp.d : nullptr, e->pset.T, P,
                                   e->d_F, e->cur);
         else if (c.lpips_size) launch_assemble_F_lpips(e->d_sim, e->d_dis, e->lp.d, c.lpips_lambda, c.use_discriminator ? 1 : 0, P, c.n_obj, e->d_F, e->cur);
@@ -641,6 +653,9 @@ int run_pass(glass_engine* e, const float* latents, int P, int generation, int f
     else if (out_F) REQUIRE(e->has_target || e->pset.T > 0, GLASS_ERR_STATE, "set_target() first");
     const bool lpips = out_F && c.lpips_size > 0;
     if (lpips) REQUIRE(e->lp.has_target, GLASS_ERR_STATE, "set_lpips_target() first");
+    const bool anchor = out_F && c.anchor, source = out_F && e->edit.has_source;      // image editing (opt-in)
+    if (anchor) REQUIRE(e->edit.has_anchor, GLASS_ERR_STATE, "set_anchor() first (this engine was created with anchor = 1)");
+    if (source) REQUIRE(e->pset.T > 0, GLASS_ERR_STATE, "set_targets() first (a direction source is set: the targets are the directions of a prompt set)");
     GLASS_HIP(hipSetDevice(c.device));
     e->launch_error.clear();      // (a pass that returned early through GLASS_HIP must not leave its message to the next one)
     // the rows go where run_styles reads them: z rows in front of the mapping network, w rows in its output's place, w+ rows per layer
@@ -668,6 +683,9 @@ int run_pass(glass_engine* e, const float* latents, int P, int generation, int f
             return brc;
         REQUIRE(view_boxes_valid(e->view_boxes, e->views, e->R), GLASS_ERR_STATE, "clip views: a box leaves the image");
     }
+    // the direction source's rows under this pass's boxes, through the tower's buffers before the candidates' patches go there
+    if (source)
+        if (int src_rc = refresh_direction_source(e)) return src_rc;
     if (biggan) {
         // BigGAN-deep (models.py:75-86): no noise inputs, no discriminator; candidates are independent, so the
         // reference's minibatch loop has no semantic effect and the population is walked in engine chunks.
@@ -707,7 +725,8 @@ int run_pass(glass_engine* e, const float* latents, int P, int generation, int f
         rc = upload_noise(e, P, generation, first_mb, noise);
         if (rc) return rc;
     }
-    const bool want_d = out_F && c.use_discriminator && (c.lpips_size > 0 || sim_columns(c) >= 2 || c.n_obj == 2);      // (with the perceptual objective n_obj counts its column too)
+    if (anchor) run_anchor(e, P);      // the dlatents run_styles made are in place until the next pass
+    const bool want_d = out_F && c.use_discriminator && (c.lpips_size > 0 || sim_columns(c) >= 2 || c.anchor || c.n_obj == 2);      // (with the perceptual objective n_obj counts its column too; so it does with an anchor)
     const int n = c.n_blocks;
     const int nlow = std::min(n, e->n_low);           // G blocks 0..nlow-1 run for the whole population
     const int nd = (int)e->dblk.size();               // D conv blocks (n - 1)
@@ -895,7 +914,9 @@ extern "C" int glass_engine_set_truncation(glass_engine* e, float psi, int32_t c
     GLASS_HIP(hipSetDevice(e->cfg.device));
     e->trunc_psi = psi;
     e->trunc_cutoff = cutoff;
-    return plan.expand ? upload_lat_table(e) : GLASS_OK;
+    if (plan.expand)
+        if (int rc = upload_lat_table(e)) return rc;
+    return e->edit.has_anchor ? compute_anchor(e) : GLASS_OK;      // the stored anchor is the row's dlatents under the truncation in force
 }
 
 extern "C" int glass_engine_latent_row(glass_engine* e, int32_t* floats_per_row, int32_t* n_lat) {

@@ -291,7 +291,23 @@ struct glass_engine {
         double* cd = nullptr;
     } search;
     long long latent_uploads = 0, latent_upload_rows = 0;   // host-to-device latent copies of the pass so far (glass_engine_latent_uploads)
+    // ---- image editing (include/glass.h "Image editing"; edit.cpp).  Nothing below is allocated or touched by an engine that has no
+    // anchor (cfg.anchor 0) and never calls glass_engine_set_direction_source ----
+    struct Edit {
+        // latent anchor
+        std::vector<float> anchor_row;      // the caller's row (floats_per_row), kept so that set_truncation can recompute the dlatents
+        float* d_anchor = nullptr;          // [n_lat][L]: the row's dlatents, after mapping and truncation
+        float* d_dist = nullptr;            // [max_pop]: d of the last pass
+        bool has_anchor = false;
+        // direction source
+        bool has_source = false;            // a source image is set: the similarity is cosine_set_dir_kernel's
+        bool rows_valid = false;            // d_src holds the rows of d_img under `boxes`
+        float* d_img = nullptr;             // [3][R][R] in [-1, 1]
+        float* d_src = nullptr;             // [max(views, 1)][clip_embed] unit rows
+        ViewBoxes boxes = {};               // crop views: the boxes d_src was made with
+    } edit;
 };
+inline int anchor_column(const glass_config& c) { return c.anchor && c.anchor_lambda == 0.f ? 1 : 0; }      // the anchor distance is its own (last) column of F
 
 // ------------------------------------------------------------------------------------
 // helpers shared by the host files (engine.cpp, stylegan2.cpp, clip.cpp, gpt2_host.cpp, biggan.cpp)
@@ -411,7 +427,8 @@ LatPlan plan_dlatents(int space, float psi, int cutoff, int n_lat);
 size_t latent_row_floats(const glass_engine* e);   // floats evaluate / generate read per row
 int upload_lat_table(glass_engine* e);             // layer_psi | dlatent_avg -> d_lat_tab (allocates it on first use)
 void run_mapping(glass_engine* e, int P);          // d_z -> d_w0
-void run_styles(glass_engine* e, int P);
+bool run_dlatents(glass_engine* e, int P);         // the uploaded rows -> the dlatents the styles are made from (mapping, truncation); false: refused
+void run_styles(glass_engine* e, int P);           // run_dlatents, then the style table, demodulation and the per-sample weights
 void run_g_blocks(glass_engine* e, int c0, int B, int b_lo, int b_hi, const half_t* x, long long xbs, half_t* const pp[2],
                   const float* yprev, float* const yb[2], const half_t** x_out, const float** y_out);
 void run_fromrgb(glass_engine* e, int B, const float* y, half_t* X);
@@ -439,7 +456,8 @@ double clip_resize_bytes(const glass_engine* e, int B);
 void run_clip_resize(glass_engine* e, const float* y, int B, half_t* patches);
 // the image tower on e->cur, for the P images whose patch operand is in d_patches: patch embedding + ln_pre, layers [l0, l1), and the
 // head (ln_post, projection, cosine against the target); run_clip is all of it.  views > 0 (the pass with crop views): the P images are
-// P / views candidates' views, and the head ends in the per-view cosines and their mean per candidate.
+// P / views candidates' views, and the head ends in the per-view cosines and their mean per candidate.  views < 0: the features alone, no
+// cosine launch (the direction source's own encoding, edit.cpp).
 void run_clip_embed(glass_engine* e, int P);
 void run_clip_layers(glass_engine* e, int P, int l0, int l1);
 void run_clip_head(glass_engine* e, int P, int views = 0);
@@ -477,6 +495,14 @@ int run_pass(glass_engine* e, const float* latents, int P, int generation, int f
              const float* d_latents = nullptr, float* d_F_dst = nullptr, bool no_wait = false);
 int wait_pass(glass_engine* e, int P);        // the wait no_wait left out: synchronise, the launchers' verdict, the profile
 int alloc_search(glass_engine* e);            // the search's buffers (nothing without glass_engine_set_search)
+#pragma GCC visibility pop
+
+// ---- image editing (edit.cpp) ----
+#pragma GCC visibility push(hidden)
+int compute_anchor(glass_engine* e);          // edit.anchor_row -> edit.d_anchor through the pass's latent path (set_anchor, and set_truncation after it)
+// the source rows of this pass (a direction source is set): encodes the image under the pass's boxes where the stored rows are not those; on e->cur
+int refresh_direction_source(glass_engine* e);
+void run_anchor(glass_engine* e, int P);      // edit.d_dist of the P candidates whose dlatents run_styles left, on e->cur
 #pragma GCC visibility pop
 
 int finalize_lpips(glass_engine* e);          // weights -> device layouts + buffers (nothing with lpips_size 0)

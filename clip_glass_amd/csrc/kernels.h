@@ -176,6 +176,25 @@ bool launch_cosine_set(const float* feat, const float* targets, const float* wei
 float prompt_weight_sum(const float* weights, int T);      // sum |w_t| in fp32, t = 0 .. T - 1 (host)
 // F [P][K + (dis != 0) + (lp != 0)]: F[p][t] = w_t < 0 ? set_sim[p][t] : -set_sim[p][t], then relu(1 - dis), then lp (nullable each)
 void launch_assemble_F_set(const float* set_sim, const float* weights, const float* dis, const float* lp, int K, int P, float* F, hipStream_t st);
+// --- image editing (edit.hip; include/glass.h "Image editing") ---
+#define GLASS_ANCHOR_MAX_LAYERS 64  // style layers of a latent anchor (2 * GLASS_MAX_BLOCKS = 24 at most in an engine)
+// launch_cosine_set's directional twin: the same arguments plus src [V][D], unit rows; every (row, view, entry) value is the cosine between
+// f / max(|f|, 1e-8) - src[v] and the entry.  One launch; false: a shape outside the limits (launch_cosine_set's), nothing launched
+bool launch_cosine_set_dir(const float* feat, const float* targets, const float* weights, float W, int P, int V, int T, int D, const float* src,
+                           float* view_sim, float* set_sim, float* sim, hipStream_t st);
+// the form that streams the set from memory, at any shape (launch_cosine_set_dir chooses it above 64 KB): the same bits
+bool launch_cosine_set_dir_streamed(const float* feat, const float* targets, const float* weights, float W, int P, int V, int T, int D,
+                                    const float* src, float* view_sim, float* set_sim, float* sim, hipStream_t st);
+// out[r] = feat[r] / max(|feat[r]|, 1e-8), n rows of D: the source rows, by the arithmetic the kernel above applies to a feature row
+bool launch_unit_rows(const float* feat, int n, int D, float* out, hipStream_t st);
+// d[p] = mean over (l, i) of (w[p * cand_stride + l * layer_stride + i] - a[l * L + i])^2; layer_stride 0: one row for every layer.
+// false: n_lat outside [1, GLASS_ANCHOR_MAX_LAYERS], L outside [1, 65536], a layer stride inside (0, L): nothing launched
+bool launch_latent_anchor(const float* w, long long cand_stride, int layer_stride, const float* a, int n_lat, int L, int P, float* d, hipStream_t st);
+// F [P][n_obj] with the anchor distance: K <= 1: column 0 = -sim (lp_lambda > 0: fmaf(lp_lambda, lp, -sim); anchor_lambda > 0: then
+// fmaf(anchor_lambda, anchor, F0)); K >= 2: the pareto columns of set_sim [P][K] by the weights' signs; then relu(1 - dis), lp as its own column
+// (lp_lambda == 0), anchor as its own LAST column (anchor_lambda == 0); dis / lp nullable.  false: n_obj is not that count, or a fold with K >= 2
+bool launch_assemble_F_edit(const float* sim, const float* set_sim, const float* weights, int K, const float* dis, const float* lp, float lp_lambda,
+                            const float* anchor, float anchor_lambda, int P, int n_obj, float* F, hipStream_t st);
 
 // --- device search (search.hip; include/glass.h "Device search") ---
 #define GLASS_SEARCH_MAX_POP 1024      // population rows (2048 merged rows in survival)

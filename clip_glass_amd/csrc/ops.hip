@@ -1121,6 +1121,39 @@ extern "C" int glass_op_assemble_F_set(int32_t device, int32_t P, int32_t K, con
     return st.fetch(F, dF);
 }
 
+extern "C" int glass_op_cosine_set_dir(int32_t device, int32_t P, int32_t V, int32_t T, int32_t D, const float* feat, const float* targets,
+                                       const float* weights, const float* src, int32_t streamed, float* view_sim, float* set_sim, float* sim) {
+    OPREQ(feat && targets && weights && src && view_sim && set_sim && sim && P > 0 && V > 0 && T > 0 && D > 0, "bad argument");
+    OPREQ((int64_t)P * V * D < (1LL << 31) && (int64_t)T * D < (1LL << 31), "cosine_set_dir: operand too large");
+    Stage st(device);
+    const auto df = st.in32(feat, (size_t)P * V * D), dt = st.in32(targets, (size_t)T * D), dw = st.in32(weights, T), dsrc = st.in32(src, (size_t)V * D);
+    const auto dvs = st.poisoned<float>((size_t)P * V), dss = st.poisoned<float>((size_t)P * T), ds = st.poisoned<float>(P);
+    TRY(st.run([&] {
+        const float W = prompt_weight_sum(weights, T);
+        return accepted(streamed ? launch_cosine_set_dir_streamed(df, dt, dw, W, P, V, T, D, dsrc, dvs, dss, ds, 0)
+                                 : launch_cosine_set_dir(df, dt, dw, W, P, V, T, D, dsrc, dvs, dss, ds, 0),
+                        "cosine_set_dir refused the shape (V and T must be in [1, 16])");
+    }));
+    TRY(st.fetch(view_sim, dvs));
+    TRY(st.fetch(set_sim, dss));
+    return st.fetch(sim, ds);
+}
+
+extern "C" int glass_op_latent_anchor(int32_t device, int32_t P, int32_t n_lat, int32_t L, int32_t layered, const float* w, const float* a, float* d) {
+    OPREQ(w && a && d && P > 0 && n_lat > 0 && L > 0, "bad argument");
+    OPREQ((int64_t)P * n_lat * L < (1LL << 31), "latent_anchor: operand too large");
+    Stage st(device);
+    const int nl = layered ? n_lat : 1;      // rows of w per candidate
+    const auto dw = st.in32(w, (size_t)P * nl * L), da = st.in32(a, (size_t)n_lat * L);
+    const auto dd = st.poisoned<float>(P, 4);
+    TRY(st.run([&] {
+        return accepted(launch_latent_anchor(dw, (long long)nl * L, layered ? L : 0, da, n_lat, L, P, dd, 0),
+                        "latent_anchor refused the shape (n_lat in [1, 64], L in [1, 65536])");
+    }));
+    TRY(st.intact(dd, "latent_anchor stored past row P"));
+    return st.fetch(d, dd);
+}
+
 extern "C" int glass_op_image_patches(int32_t device, int32_t n, int32_t S, int32_t ps, int32_t ld, const float* img, float sentinel,
                                       float* patches) {
     OPREQ(img && patches && n > 0 && S > 0 && ps > 0 && S % ps == 0 && ld >= 3 * ps * ps, "bad argument (S % ps == 0, ld >= 3 ps ps)");

@@ -310,13 +310,13 @@ void run_mapping(glass_engine* e, int P) {
 }
 
 // The uploaded rows are in d_z (space z), d_w0 (w) or d_dlat (w+): run_pass put them there.
-void run_styles(glass_engine* e, int P) {
+bool run_dlatents(glass_engine* e, int P) {
     const glass_config& c = e->cfg;
     const int L = c.latent_size, NL = e->n_lat;
     const LatPlan lp = plan_dlatents(e->latent_space, e->trunc_psi, e->trunc_cutoff, NL);
     if (lp.layered && !e->d_dlat) {   // (the setters refuse this; a pass never reads a buffer that is not there)
         if (e->launch_error.empty()) e->launch_error = "per-layer dlatents without their buffer";
-        return;
+        return false;
     }
     if (lp.map) run_mapping(e, P);
     if (lp.expand) {
@@ -326,6 +326,14 @@ void run_styles(glass_engine* e, int P) {
         else if (e->latent_space == GLASS_LATENT_WPLUS) launch_dlatent_expand(e->d_dlat, (long long)NL * L, L, e->d_dlat, e->d_lat_tab, e->lat_pad, NL, P, L, e->cur);   // in place
         else launch_dlatent_expand(e->d_w0, L, 0, e->d_dlat, e->d_lat_tab, e->lat_pad, NL, P, L, e->cur);
     }
+    return true;
+}
+
+void run_styles(glass_engine* e, int P) {
+    const glass_config& c = e->cfg;
+    const int L = c.latent_size, NL = e->n_lat;
+    const LatPlan lp = plan_dlatents(e->latent_space, e->trunc_psi, e->trunc_cutoff, NL);
+    if (!run_dlatents(e, P)) return;
     {
         Prof pr(e, "styles", 2.0 * P * L * e->S_total, 4.0 * L * e->S_total + (lp.layered ? 4.0 * P * NL * L : 0.0));
         if (lp.layered)

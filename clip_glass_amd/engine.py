@@ -50,6 +50,12 @@ class GlassConfigPrompt(C.Structure):
     _fields_ = GlassConfigLpips._fields_ + [("sim_columns", C.c_int32)]
 
 
+class GlassConfigEdit(C.Structure):
+    """glass_config as the library defines it now: GlassConfigPrompt's fields, then the latent anchor's (include/glass.h "Image editing"),
+    appended as the others were (zero: off).  The shorter structs stay what libraries built before each addition read."""
+    _fields_ = GlassConfigPrompt._fields_ + [("anchor", C.c_int32), ("anchor_lambda", C.c_float)]
+
+
 PROMPT_MODES = {"sum": 0, "pareto": 1}      # include/glass.h "Prompt sets"
 PROMPT_MAX = 16
 
@@ -80,7 +86,7 @@ def load_library(path=None):
     fp = C.POINTER(C.c_float)
     lib.glass_last_error.restype = C.c_char_p
     lib.glass_version.restype = C.c_char_p
-    lib.glass_engine_create.argtypes = [C.POINTER(GlassConfigPrompt), C.POINTER(C.c_void_p)]
+    lib.glass_engine_create.argtypes = [C.POINTER(GlassConfigEdit), C.POINTER(C.c_void_p)]
     if hasattr(lib, "glass_clip_geometry_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
         lib.glass_clip_geometry_supported.argtypes = [C.c_int32] * 6
     if hasattr(lib, "glass_clip_preprocess_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
@@ -110,6 +116,12 @@ def load_library(path=None):
         lib.glass_engine_set_targets.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.c_int32]
         lib.glass_engine_last_set_details.argtypes = [C.c_void_p, C.c_int32, fp]
         lib.glass_engine_encode_generated.argtypes = [C.c_void_p, fp, C.c_int32, fp]
+    if hasattr(lib, "glass_edit_supported"):            # (absent from older A/B builds loaded through GLASS_LIB)
+        lib.glass_edit_supported.argtypes = [C.c_int32] * 6 + [C.c_float, C.c_int32]
+        lib.glass_engine_set_anchor.argtypes = [C.c_void_p, fp]
+        lib.glass_engine_last_anchor.argtypes = [C.c_void_p, C.c_int32, fp]
+        lib.glass_engine_set_direction_source.argtypes = [C.c_void_p, fp]
+        lib.glass_engine_last_direction_source.argtypes = [C.c_void_p, fp]
     if hasattr(lib, "glass_search_supported"):          # (absent from older A/B builds loaded through GLASS_LIB)
         ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
         lib.glass_search_supported.argtypes = [C.c_int32] * 4
@@ -226,6 +238,24 @@ def prompt_n_obj(sim_columns, use_discriminator, lpips_column=False):
     return max(int(sim_columns), 1) + int(bool(use_discriminator)) + int(bool(lpips_column))
 
 
+def edit_n_obj(sim_columns, use_discriminator, lpips_column=False, anchor=False, anchor_lambda=0.0):
+    """Columns of F with the latent anchor (include/glass.h "Image editing"): prompt_n_obj's, and the anchor distance when it is its own
+    column (anchor on, anchor_lambda 0)."""
+    return prompt_n_obj(sim_columns, use_discriminator, lpips_column) + int(bool(anchor) and float(anchor_lambda) == 0.0)
+
+
+def edit_supported(generator="stylegan2", n_blocks=9, sim_columns=0, use_discriminator=False, lpips_column=False, anchor=False, anchor_lambda=0.0,
+                   n_obj=1):
+    """(ok, message) for the latent anchor's fields on an engine of that kind ("stylegan2", "biggan", or None: no generator — n_blocks is
+    then taken as 0): the library's own rule (glass_edit_supported), the one glass_engine_create applies.  Host only."""
+    lib = load_library()
+    gen = GEN_BIGGAN_DEEP if generator == "biggan" else GEN_STYLEGAN2
+    nb = int(n_blocks) if generator == "stylegan2" else 0
+    rc = lib.glass_edit_supported(gen, nb, int(sim_columns), int(bool(use_discriminator)), int(bool(lpips_column)), int(anchor), float(anchor_lambda),
+                                  int(n_obj))
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
 def clip_view_permille(fraction):
     """The smallest crop side as the library takes it: per mille of the image side."""
     return int(round(1000 * float(fraction)))
@@ -313,7 +343,8 @@ class Engine:
                  n_obj=2, max_pop=64, chunk=0, clip=(768, 12, 12, 32, 224, 512), noise_mode=1, noise_seed=0,
                  mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0, clip_resnet=None,
                  clip_views=0, clip_view_min=0.5, clip_view_flip=True, clip_view_fixed=False,
-                 latent_space="z", truncation_psi=1.0, truncation_cutoff=None, lpips_size=0, lpips_lambda=0.0, sim_columns=0):
+                 latent_space="z", truncation_psi=1.0, truncation_cutoff=None, lpips_size=0, lpips_lambda=0.0, sim_columns=0,
+                 anchor=False, anchor_lambda=0.0):
         """`biggan` = dict(layers=[(up, in_mult, out_mult), ...], attention_pos, ch, z_dim, num_classes, n_stats, eps,
         truncation) selects the BigGAN-deep generator (channels must then be empty, no discriminator).
         clip_resize / clip_normalize: how a generated image is prepared for CLIP (include/glass.h); (0, 0) is the reference's way.
@@ -330,9 +361,13 @@ class Engine:
         area-downscaled to S px, and the image given to set_lpips_target().  lpips_lambda = 0: the distance is one more, last, column
         of F and n_obj must count it (lpips_n_obj); > 0: F[:, 0] = -sim + lambda * d and n_obj stays.  Needs the "lpips.*" tensors.
         sim_columns = K in [2, 4] makes an engine for a pareto prompt set (include/glass.h "Prompt sets"): K similarity columns, one per
-        entry of set_targets(..., mode="pareto"), and n_obj must be prompt_n_obj(K, ...); 0 (default): the one similarity column."""
+        entry of set_targets(..., mode="pareto"), and n_obj must be prompt_n_obj(K, ...); 0 (default): the one similarity column.
+        anchor = True turns the latent anchor on (include/glass.h "Image editing"; StyleGAN2 only): the mean squared distance between a
+        candidate's dlatents and those of the row given to set_anchor().  anchor_lambda = 0: one more, last, column of F and n_obj must
+        count it (edit_n_obj); > 0: F[:, 0] += anchor_lambda * d and n_obj stays."""
         self.lib = load_library()
-        cfg = GlassConfigPrompt()
+        cfg = GlassConfigEdit()
+        cfg.anchor, cfg.anchor_lambda = int(bool(anchor)), float(anchor_lambda)
         cfg.sim_columns = int(sim_columns)
         cfg.lpips_size, cfg.lpips_lambda = int(lpips_size), float(lpips_lambda)
         cfg.device = device
@@ -455,6 +490,35 @@ class Engine:
     @staticmethod
     def prompt_set_supported(n_entries, mode="sum", sim_columns=0):
         return prompt_set_supported(n_entries, mode, sim_columns)
+
+    # --- image editing (include/glass.h "Image editing") --------------------------
+    def set_anchor(self, row):
+        """The latent anchor: one row of the current latent space, float32 [floats_per_row].  After finalize(), on Engine(anchor=True)."""
+        r = self._rows(np.asarray(row, dtype=np.float32).reshape(1, -1))
+        _check(self.lib, self.lib.glass_engine_set_anchor(self._h, _fp(r)))
+
+    def last_anchor(self, P):
+        """The anchor distances [P] of the last evaluate()."""
+        d = np.empty((P,), dtype=np.float32)
+        _check(self.lib, self.lib.glass_engine_last_anchor(self._h, P, _fp(d)))
+        return d
+
+    def set_direction_source(self, image):
+        """The source image of the directional similarity: float32 [3, R, R] in [-1, 1] (the generator's raw range), or None: off.  While
+        one is set, the entries of set_targets() are directions.  After finalize()."""
+        if image is None:
+            _check(self.lib, self.lib.glass_engine_set_direction_source(self._h, None))
+            return
+        a = _f32(image)
+        if a.shape != (3, self.res, self.res):
+            raise ValueError("set_direction_source: the image must be [3, %d, %d], got %r" % (self.res, self.res, a.shape))
+        _check(self.lib, self.lib.glass_engine_set_direction_source(self._h, _fp(a)))
+
+    def last_direction_source(self):
+        """The unit rows [max(clip_views, 1), clip_embed] the last pass subtracted from the candidates' unit features."""
+        out = np.empty((max(self.clip_views, 1), self.cfg.clip_embed), dtype=np.float32)
+        _check(self.lib, self.lib.glass_engine_last_direction_source(self._h, _fp(out)))
+        return out
 
     # --- perceptual objective --------------------------------------------------
     def set_lpips_target(self, image):

@@ -196,6 +196,111 @@ def prompt_config(config, opts):
     return out
 
 
+# ---- image editing (opt-in, include/glass.h "Image editing"): a directional objective relative to a source image, a latent anchor, and a
+# search that starts at the source; the reference's run.py has none of it ----
+EDIT_KEYS = ("edit_image", "edit_latent", "source_text", "anchor_lambda", "edit_sigma")
+# The spread of generation 0 around the source row, in the row's own units: a search setting, not a measurement.  z rows are N(0, 1) and
+# dlatents have a spread of the same order, so 0.1 starts every candidate a tenth of a typical coordinate away from the source — close
+# enough to be the same face, far enough for crossover to have something to combine.
+DEFAULT_EDIT_SIGMA = 0.1
+
+
+def load_edit_latent(value):
+    """config.edit_latent as one float32 row: a path to a .npy, or an array of one row."""
+    row = np.load(value) if isinstance(value, (str, os.PathLike)) else np.asarray(value)
+    row = np.asarray(row, dtype=np.float32)
+    if row.ndim == 2 and row.shape[0] == 1:
+        row = row[0]
+    if row.ndim != 1 or not np.isfinite(row).all():
+        raise ValueError("edit_latent must be ONE finite row of the current latent space, got shape %r" % (row.shape,))
+    return np.ascontiguousarray(row)
+
+
+def edit_options(config):
+    """None while every key of EDIT_KEYS is unset (the default: today's search), else dict(image, latent, source_text, lam, sigma, anchor,
+    anchor_column): edit_image (a path or an array [3, H, W] in [0, 1]: the source of the directional objective), edit_latent (a path to a
+    .npy or an array: one row of the current latent space — the source image is generated from it, the latent anchor is that row, and
+    generation 0 starts at it), source_text (what the source shows: required as soon as a source is set), anchor_lambda (0: the anchor is an
+    objective of its own; > 0: added to the similarity objective, times lambda) and edit_sigma (the spread of generation 0 around the
+    source row, DEFAULT_EDIT_SIGMA).  ValueError by name, before any weight is looked for: the GPT2 / img2txt config refuses every key; the
+    BigGAN configs refuse edit_latent and anchor_lambda (no dlatents); a source without source_text; the other keys without a source;
+    anchor_lambda or edit_sigma without edit_latent; anchor_lambda > 0 with a pareto prompt set."""
+    vals = {k: getattr(config, k, None) for k in EDIT_KEYS}
+    given = [k for k in EDIT_KEYS if vals[k] is not None]
+    if not given:
+        return None
+    name = str(getattr(config, "config", ""))
+    if getattr(config, "task", "txt2img") == "img2txt":
+        raise ValueError("%s: image editing moves generated images away from a source image; the img2txt task (config %r) generates none: "
+                         "leave these keys unset" % (", ".join(given), name or "GPT2"))
+    if name.split("_")[0] != "StyleGAN2":
+        bad = [k for k in ("edit_latent", "anchor_lambda") if vals[k] is not None]
+        if bad:
+            raise ValueError("%s: the latent anchor is a distance between dlatents of a StyleGAN2 generator; config %r has none (give the "
+                             "source as edit_image)" % (", ".join(bad), name))
+    if vals["edit_image"] is None and vals["edit_latent"] is None:
+        raise ValueError("%s set without a source: give edit_image (a picture) or edit_latent (a latent row)" % ", ".join(given))
+    if vals["source_text"] is None or not str(vals["source_text"]).strip():
+        raise ValueError("source_text is required with %s: the objective follows the direction from what the source shows to the target"
+                         % ("edit_image" if vals["edit_image"] is not None else "edit_latent"))
+    for k in ("anchor_lambda", "edit_sigma"):
+        if vals[k] is not None and vals["edit_latent"] is None:
+            raise ValueError("%s set without edit_latent: the anchor and the start of the search are a latent row" % k)
+    lam = 0.0 if vals["anchor_lambda"] is None else float(vals["anchor_lambda"])
+    if not (lam >= 0.0 and np.isfinite(lam)):
+        raise ValueError("anchor_lambda must be finite and >= 0, got %r" % (vals["anchor_lambda"],))
+    sigma = DEFAULT_EDIT_SIGMA if vals["edit_sigma"] is None else float(vals["edit_sigma"])
+    if not (sigma > 0.0 and np.isfinite(sigma)):
+        raise ValueError("edit_sigma must be finite and > 0, got %r" % (vals["edit_sigma"],))
+    if lam > 0.0 and getattr(config, "prompt_mode", None) == "pareto":
+        raise ValueError("anchor_lambda > 0 with prompt_mode 'pareto': lambda folds the distance into THE similarity objective, and a pareto "
+                         "set has one per prompt: use anchor_lambda 0 (the distance as an objective of its own)")
+    anchor = vals["edit_latent"] is not None
+    return dict(image=vals["edit_image"], latent=vals["edit_latent"], source_text=str(vals["source_text"]), lam=lam, sigma=sigma, anchor=anchor,
+                anchor_column=anchor and lam == 0.0)
+
+
+def edit_config(config, opts):
+    """The config a search with the anchor as its own objective runs on: a COPY (as lpips_config's and prompt_config's, applied AFTER both)
+    with problem_args["n_obj"] one higher and algorithm "nsga2".  No anchor, or anchor_lambda > 0: the config as it is."""
+    if opts is None or not opts["anchor_column"]:
+        return config
+    out = copy.copy(config)
+    out.problem_args = dict(config.problem_args, n_obj=int(config.problem_args["n_obj"]) + 1)
+    out.algorithm = "nsga2"
+    return out
+
+
+def _unit64(v):
+    v = np.asarray(v, dtype=np.float64)
+    return v / max(float(np.linalg.norm(v)), 1e-8)
+
+
+def edit_directions(features, kinds, source_text_feature, source_image_feature):
+    """The entries of the set as directions (float32 [T, E]): for a text entry (kinds "target", "text", "feature")
+    normalise(unit(g_t) - unit(g_source_text)); for an image prompt (kind "image") normalise(unit(g_t) - unit(s_whole_image)).  Computed in
+    float64 on the host.  ValueError for an entry that IS its source (a zero direction: nothing to follow)."""
+    rows = []
+    for t, (f, kind) in enumerate(zip(features, kinds)):
+        base = source_image_feature if kind == "image" else source_text_feature
+        d = _unit64(f) - _unit64(base)
+        n = float(np.linalg.norm(d))
+        if not n > 1e-6:
+            raise ValueError("prompt %d (%s) is the same as its source (%s): the direction between them is zero" %
+                             (t, kind, "the source image" if kind == "image" else "source_text"))
+        rows.append(d / n)
+    return np.asarray(rows, dtype=np.float32)
+
+
+def edit_start_population(source_row, n_samples, sigma, xl, xu, normal):
+    """Generation 0 of a search that starts at the source: row 0 is the source row itself, rows 1 and up are source + sigma * N(0, 1)
+    (normal(size) draws them), everything clipped to [xl, xu] — which problem.edit_bounds has widened to contain the source."""
+    src = np.asarray(source_row, dtype=np.float64).reshape(1, -1)
+    X = src + float(sigma) * np.asarray(normal((int(n_samples), src.shape[1])), dtype=np.float64)
+    X[0] = src[0]
+    return np.clip(X, xl, xu)
+
+
 def prepare_lpips_target(target, size):
     """The target image as the engine takes it: float32 [3, size, size] in [-1, 1].  target: a path (opened with PIL, RGB, / 255), a PIL
     image, or an array [3, H, W] in [0, 1].  Centre-crop to the largest square, then down to `size`: where the square's side is a multiple
@@ -444,8 +549,11 @@ class Generator:
         self.lpips = lpips_options(config)
         # prompt set (opt-in): refused for the GPT2 config the same way; a pareto set searches one objective per entry, on a copy too
         self.prompts = prompt_options(config)
+        # image editing (opt-in): refused by name for the GPT2 config (every key) and the BigGAN configs (the anchor's keys) here, before any
+        # engine is built; the anchor as its own objective searches one more column, on a copy as well
+        self.edit = edit_options(config)
         base_n_obj = int((getattr(config, "problem_args", None) or {}).get("n_obj", 1))
-        config = prompt_config(lpips_config(config, self.lpips), self.prompts)
+        config = edit_config(prompt_config(lpips_config(config, self.lpips), self.prompts), self.edit)
         self.config = config
         self.augmentation = None
         self.model = config.model(config)                                   # generator.py:19
@@ -520,7 +628,8 @@ class Generator:
             self.tokenizer = ClipTokenizer(getattr(config, "bpe_path", DEFAULT_BPE))
             return
         need_text = getattr(config, "target_features", None) is None or any(
-            kind == "text" for kind, _, _ in (self.prompts["entries"] if self.prompts else []))
+            kind == "text" for kind, _, _ in (self.prompts["entries"] if self.prompts else [])) or (
+            self.edit is not None and getattr(config, "source_text_features", None) is None)
         pareto = self.prompts is not None and self.prompts["mode"] == "pareto"
         sim_columns = len(self.prompts["entries"]) if pareto else 0
         clip_state, geom = _load_clip_state(config, need_text)
@@ -538,6 +647,9 @@ class Generator:
             tower.update(lpips_size=self.lpips["size"], lpips_lambda=self.lpips["lam"])
         if pareto:
             tower.update(sim_columns=sim_columns)
+        anchor_col = int(self.edit is not None and self.edit["anchor_column"])
+        if self.edit is not None and self.edit["anchor"]:
+            tower.update(anchor=True, anchor_lambda=self.edit["lam"])
         if hasattr(self.model, "geometry"):     # BigGAN-deep (models.py:64-86)
             self.engine = Engine([], batch_size=config.batch_size, max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  device=device, biggan=self.model.geometry, clip_resize=clip_resize,
@@ -546,9 +658,9 @@ class Generator:
             self.engine = Engine(self.model.channels[::-1], latent_size=config.dim_z,
                                  mapping_layers=getattr(config, "mapping_layers", 8), batch_size=config.batch_size,
                                  use_discriminator=bool(config.use_discriminator and base_n_obj == 2),
-                                 n_obj=(int(config.problem_args["n_obj"]) if pareto
-                                        else lpips_n_obj(config.use_discriminator and base_n_obj == 2, self.lpips["lam"])
-                                        if self.lpips is not None else base_n_obj), max_pop=pop, chunk=getattr(config, "chunk", 0),
+                                 n_obj=(int(config.problem_args["n_obj"]) if pareto          # (the copy's: it counts the anchor's column)
+                                        else lpips_n_obj(config.use_discriminator and base_n_obj == 2, self.lpips["lam"]) + anchor_col
+                                        if self.lpips is not None else base_n_obj + anchor_col), max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  noise_mode=getattr(config, "noise_mode", 1),
                                  noise_seed=getattr(config, "noise_seed", 0), device=device, clip_resize=clip_resize,
                                  clip_normalize=clip_normalize, latent_space=self.latent_space,
@@ -581,14 +693,21 @@ class Generator:
             self.text_features = np.asarray(config.target_features, np.float32).reshape(1, -1)
         else:
             texts = [self.config.target] + texts
+        source_feature = getattr(config, "source_text_features", None) if self.edit is not None else None     # pre-computed, as target_features
+        if self.edit is not None and source_feature is None:
+            texts = texts + [self.edit["source_text"]]                      # the source's text, encoded in the same call, last
         if texts:                                                           # generator.py:23-24; the set's texts in the same call
             from .tokenizer import DEFAULT_BPE, ClipTokenizer
             tok = ClipTokenizer(getattr(config, "bpe_path", DEFAULT_BPE))
             self.tokens = tok.tokenize(texts)
             encoded = self.engine.encode_text(self.tokens)
+            if self.edit is not None and source_feature is None:
+                source_feature, encoded = encoded[-1], encoded[:-1]
             if getattr(config, "target_features", None) is None:
                 self.text_features, encoded = encoded[:1], encoded[1:]
-        if self.prompts is None:
+        if self.edit is not None:
+            self._set_edit(np.asarray(source_feature, dtype=np.float32).reshape(-1), encoded if texts else None)
+        elif self.prompts is None:
             self.engine.set_target(self.text_features[0])
         else:
             self._set_prompts(encoded if texts else None)
@@ -601,9 +720,15 @@ class Generator:
         """Build the set's features [T, E] in the order of prompt_options' entries and hand it to the engine.  text_features: the encoded
         "text" entries, in order.  An image goes through prepare_lpips_target (centre crop, resize to the generator's side, [-1, 1]) and
         the engine's encode_generated: the feature a generated image with those pixels would get."""
+        self._prompt_rows(self.prompts["entries"], text_features)
+        self.prompt_mode = self.prompts["mode"]
+        self.engine.set_targets(self.prompt_features, self.prompt_weights, self.prompt_mode)
+
+    def _prompt_rows(self, entries, text_features):
+        """prompt_features [T, E] and prompt_weights [T] of `entries`, in their order (see _set_prompts)."""
         E = int(self.engine.cfg.clip_embed)
         rows, n_text = [], 0
-        for kind, value, _ in self.prompts["entries"]:
+        for kind, value, _ in entries:
             if kind == "target":
                 f = self.text_features[0]
             elif kind == "text":
@@ -617,9 +742,35 @@ class Generator:
                 raise ValueError("a prompt feature must hold clip_embed = %d floats, got %d" % (E, f.size))
             rows.append(f)
         self.prompt_features = np.stack(rows)
-        self.prompt_weights = np.asarray([w for _, _, w in self.prompts["entries"]], dtype=np.float32)
-        self.prompt_mode = self.prompts["mode"]
-        self.engine.set_targets(self.prompt_features, self.prompt_weights, self.prompt_mode)
+        self.prompt_weights = np.asarray([w for _, _, w in entries], dtype=np.float32)
+
+    def _set_edit(self, source_text_feature, text_features):
+        """Image editing: the source image (edit_image, or the image generated from edit_latent) becomes the engine's direction source, the
+        entries of the set — the single target is a set of one — become directions away from the source's text (an image prompt: away from
+        the source image's own whole-image feature), and edit_latent's row becomes the latent anchor."""
+        ed = self.edit
+        if ed["latent"] is not None:
+            self.edit_row = load_edit_latent(ed["latent"])
+            width = self.latent_width()
+            if self.edit_row.size != width:
+                raise ValueError("edit_latent holds %d floats; a row of latent space %r has %d" % (self.edit_row.size, self.latent_space, width))
+        if ed["image"] is not None:
+            source = prepare_lpips_target(ed["image"], self.engine.res)          # centre crop, resize to the generator's side, [-1, 1]
+            self.source_image = np.ascontiguousarray((source + 1.0) / 2.0, dtype=np.float32)
+        else:       # the row's own picture: generation 0, minibatch 0, first image of a minibatch of copies (that fixes its noise planes)
+            tiled = np.tile(self.edit_row[None], (int(self.config.batch_size), 1))
+            self.source_image = self.engine.generate(tiled, generation=0, first_minibatch=0)[0]
+            source = np.ascontiguousarray(2.0 * self.source_image - 1.0, dtype=np.float32)
+        self.source_feature = self.engine.encode_generated(source[None])[0]
+        entries = self.prompts["entries"] if self.prompts is not None else [("target", None, 1.0)]
+        self._prompt_rows(entries, text_features)
+        self.prompt_mode = self.prompts["mode"] if self.prompts is not None else DEFAULT_PROMPT_MODE
+        self.source_text_feature = source_text_feature
+        self.prompt_directions = edit_directions(self.prompt_features, [k for k, _, _ in entries], source_text_feature, self.source_feature)
+        self.engine.set_targets(self.prompt_directions, self.prompt_weights, self.prompt_mode)
+        self.engine.set_direction_source(source)
+        if ed["anchor"]:
+            self.engine.set_anchor(self.edit_row)
 
     def map_latents(self, z):
         """z [N, dim_z] -> untruncated dlatents w [N, dim_z] through the engine's mapping network, in slices of its capacity."""

@@ -68,6 +68,25 @@ class MappedNormalSampling(Sampling):
         return np.tile(w, (1, self.tile))
 
 
+class EditSampling(Sampling):
+    """Sampling for a search that starts at a source row (config.edit_latent; generator.edit_start_population): the first call returns the
+    source itself as row 0 and source + sigma * N(0, 1) below it, clipped to the problem's bounds; later calls (the refill after duplicate
+    elimination) return perturbed rows only.  Draws come from numpy's global RNG, as the other samplings' do."""
+
+    def __init__(self, source_row, sigma):
+        super().__init__()
+        self.source_row, self.sigma, self.started = np.asarray(source_row, dtype=np.float32), float(sigma), False
+
+    def _do(self, problem, n_samples, **kwargs):
+        from .generator import edit_start_population
+        if problem.n_var != self.source_row.size:
+            raise ValueError("edit_latent holds %d floats; the search varies %d" % (self.source_row.size, problem.n_var))
+        X = edit_start_population(self.source_row, n_samples + int(self.started), self.sigma, problem.xl, problem.xu,
+                                  lambda size: np.random.normal(0, 1, size=size))
+        first, self.started = (1 if self.started else 0), True
+        return X[first:]
+
+
 class BinaryRandomSampling(Sampling):
     """operators.py:27-34"""
 
@@ -115,6 +134,12 @@ def get_operators(config):
     needs to apply the same per-type operators when pymoo is absent."""
     if config.config.split("_")[0] == "StyleGAN2":
         space = getattr(config, "latent_space", None) or "z"
+        if getattr(config, "edit_latent", None) is not None:      # image editing: the search starts at the source row, in any space
+            from .generator import DEFAULT_EDIT_SIGMA, load_edit_latent
+            sigma = getattr(config, "edit_sigma", None)
+            return dict(sampling=EditSampling(load_edit_latent(config.edit_latent), DEFAULT_EDIT_SIGMA if sigma is None else sigma),
+                        crossover=get_crossover("real_sbx", prob=1.0, eta=3.0),
+                        mutation=get_mutation("real_pm", prob=0.5, eta=3.0))
         if space != "z":      # same crossover and mutation; the initial population comes through the mapping network
             from .latent import stylegan2_n_lat
             return dict(sampling=MappedNormalSampling(config.dim_z, stylegan2_n_lat(config) if space == "w+" else 1),

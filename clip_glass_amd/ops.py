@@ -86,6 +86,8 @@ SIGNATURES = {
     "glass_op_assemble_F": [i32, i32, i32, fp, fp, fp],
     "glass_op_cosine_set": [i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp],
     "glass_op_assemble_F_set": [i32, i32, i32, fp, fp, fp, fp, fp],
+    "glass_op_cosine_set_dir": [i32, i32, i32, i32, i32, fp, fp, fp, fp, i32, fp, fp, fp],
+    "glass_op_latent_anchor": [i32, i32, i32, i32, i32, fp, fp, fp],
     "glass_op_image_patches": [i32, i32, i32, i32, i32, fp, f32, fp],
     "glass_op_rn_token0_rows": [i32, i32, i32, i32, fp, fp],
     "glass_op_lpips_input": [i32, i32, i32, i32, fp, fp],
@@ -899,6 +901,34 @@ def assemble_F_set(set_sim, weights, dis=None, lp=None, device=0):
     Fv = np.empty((P, K + (dis is not None) + (lp is not None)), dtype=np.float32)
     _check(lib, lib.glass_op_assemble_F_set(device, P, K, _fp(set_sim), _fp(weights), dp, lpp, _fp(Fv)))
     return Fv
+
+
+def cosine_set_dir(feat, targets, weights, src, streamed=False, device=0):
+    """feat [P, V, D], targets [T, D], weights [T], src [V, D] (unit rows) -> (view_sim [P, V], set_sim [P, T], sim [P]): cosine_set_dir_kernel
+    (image editing), the cosine of f / |f| - src[v] with every entry.  streamed: the form that reads the set from memory at any shape."""
+    lib = _lib()
+    feat, targets, weights, src = _f32(feat), _f32(targets), _f32(weights), _f32(src)
+    P, V, D = feat.shape
+    T = targets.shape[0]
+    if targets.shape != (T, D) or weights.shape != (T,) or src.shape != (V, D):
+        raise ValueError("cosine_set_dir: targets [T, %d], weights [T] and src [%d, %d] expected, got %r, %r, %r"
+                         % (D, V, D, targets.shape, weights.shape, src.shape))
+    vs, ss, sim = np.empty((P, V), np.float32), np.empty((P, T), np.float32), np.empty(P, np.float32)
+    _check(lib, lib.glass_op_cosine_set_dir(device, P, V, T, D, _fp(feat), _fp(targets), _fp(weights), _fp(src), int(bool(streamed)), _fp(vs),
+                                            _fp(ss), _fp(sim)))
+    return vs, ss, sim
+
+
+def latent_anchor(w, a, device=0):
+    """w [P, n_lat, L], or [P, L] (one row for every layer), a [n_lat, L] -> d [P] = mean (w - a)^2: latent_anchor_kernel (image editing)."""
+    lib = _lib()
+    w, a = _f32(w), _f32(a)
+    n_lat, L = a.shape
+    if w.shape[1:] not in ((n_lat, L), (L,)):
+        raise ValueError("latent_anchor: w must be [P, %d, %d] or [P, %d], got %r" % (n_lat, L, L, w.shape))
+    d = np.empty(w.shape[0], np.float32)
+    _check(lib, lib.glass_op_latent_anchor(device, w.shape[0], n_lat, L, int(w.ndim == 3), _fp(w), _fp(a), _fp(d)))
+    return d
 
 
 def assemble_F(sim, dis=None, device=0):

@@ -43,6 +43,13 @@ def dlatent_problem_args(config, generator):
     return dict(n_var=n_var, n_constr=n_var, xl=lo - (hi - lo) / 2, xu=hi + (hi - lo) / 2)     # (the reference sets n_constr = n_var)
 
 
+def edit_bounds(xl, xu, source_row):
+    """The scalar bounds of a search that starts at a source row (edit_latent), widened to contain it: whatever the config or the probe of
+    the mapping network gave, the source itself is a legal candidate."""
+    row = np.asarray(source_row, dtype=np.float64)
+    return min(float(xl), float(row.min())), max(float(xu), float(row.max()))
+
+
 class GenerationProblem(Problem):
     def __init__(self, config, dist=None):
         """dist: an initialised torch.distributed module (one process per GPU; backend "nccl" = RCCL), or None = use the default
@@ -53,6 +60,9 @@ class GenerationProblem(Problem):
         args = dict(self.config.problem_args)
         if getattr(self.generator, "latent_space", "z") != "z":
             args.update(dlatent_problem_args(config, self.generator))
+        if getattr(self.generator, "edit_row", None) is not None:      # image editing: generation 0 starts at this row
+            lo, hi = edit_bounds(args["xl"], args["xu"], self.generator.edit_row)
+            args.update(xl=lo, xu=hi)
         if getattr(self.generator, "device_search", False):     # the device's rows are fp32 and are clipped to the bounds: bounds exact in fp32
             args.update(xl=float(np.float32(args["xl"])), xu=float(np.float32(args["xu"])))
         super().__init__(**args)
@@ -91,6 +101,8 @@ class GenerationProblem(Problem):
             out["F"] = F                                # (one similarity column per prompt, [hinge], [perceptual distance])
         elif getattr(self.generator, "lpips", None) is not None and self.config.problem_args["n_obj"] >= 2:
             out["F"] = F                                # (-sim, [hinge], perceptual distance)
+        elif (getattr(self.generator, "edit", None) or {}).get("anchor_column") and self.config.problem_args["n_obj"] >= 2:
+            out["F"] = F                                # (-sim, latent anchor distance)
         elif self.config.problem_args["n_obj"] == 2 and self.config.use_discriminator:
             out["F"] = F                                # column_stack((-sim, hinge)) (problem.py:25)
         else:

@@ -16,7 +16,8 @@ import numpy as np
 from .config import get_config
 from .engine import LATENT_SPACES
 from .engine import PROMPT_MODES
-from .generator import CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, latent_options, lpips_options, parse_weighted, prompt_options
+from .generator import (CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, edit_options, latent_options, lpips_options, parse_weighted,
+                        prompt_options)
 from .operators import get_operators
 from .problem import GenerationProblem
 from . import search
@@ -76,6 +77,19 @@ def build_parser():
     p.add_argument("--prompt-mode", type=str, default=None, choices=list(PROMPT_MODES),
                    help="sum (default): the prompts blend into the one similarity objective, sum_t w_t sim_t / sum_t |w_t|; pareto: one objective "
                         "per prompt (2 to 4, NSGA-II)")
+    p.add_argument("--edit-image", type=str, default=None,
+                   help="edit this picture: the similarity becomes directional — how the generated image moved away from this one against how "
+                        "--target moved away from --source-text (off by default; the reference's run.py has no such objective: this departs from "
+                        "it on purpose)")
+    p.add_argument("--edit-latent", type=str, default=None,
+                   help="StyleGAN2 configs: a .npy with one row of the current latent space.  Its generated image is the source of the directional "
+                        "similarity, the row is the latent anchor, and generation 0 starts at it")
+    p.add_argument("--source-text", type=str, default=None, help="what the source image shows (required with --edit-image / --edit-latent)")
+    p.add_argument("--anchor-lambda", type=float, default=None,
+                   help="with --edit-latent.  0 (default): the mean squared distance to the source's dlatents is an objective of its own (NSGA-II); "
+                        "> 0: it is added to the similarity objective, times lambda")
+    p.add_argument("--edit-sigma", type=float, default=None,
+                   help="with --edit-latent: spread of generation 0 around the source row (default 0.1; row 0 is the source itself)")
     p.add_argument("--bpe-path", type=str, default=None)
     p.add_argument("--pop-size", type=int, default=None)
     p.add_argument("--stochastic", action="store_true", default=None,
@@ -100,12 +114,13 @@ def similarity_columns(config):
 
 def objective_names(config):
     """Column names of F for this config: similarity (similarity-0 .. similarity-(K - 1) for a pareto prompt set of K entries), then
-    discriminator (with D), then lpips (perceptual objective, lambda = 0)."""
+    discriminator (with D), then lpips (perceptual objective, lambda = 0), then anchor (edit_latent, anchor_lambda = 0)."""
     n = int(config.problem_args["n_obj"])
     K = similarity_columns(config)
     lp_col = getattr(config, "lpips_target", None) is not None and not float(getattr(config, "lpips_lambda", None) or 0.0) > 0.0
+    an_col = getattr(config, "edit_latent", None) is not None and not float(getattr(config, "anchor_lambda", None) or 0.0) > 0.0
     sims = ["similarity"] if K == 1 else ["similarity-%d" % t for t in range(K)]
-    names = sims + (["discriminator"] if n - K - int(lp_col) >= 1 else []) + (["lpips"] if lp_col else [])
+    names = sims + (["discriminator"] if n - K - int(lp_col) - int(an_col) >= 1 else []) + (["lpips"] if lp_col else []) + (["anchor"] if an_col else [])
     return names
 
 
@@ -128,8 +143,9 @@ def scatter_pairs(names):
 def final_pick_weights(names):
     """Pseudo-weights of the final pick among the Pareto set.  The reference takes (0, 1) on (similarity, discriminator): the most
     realistic point (run.py:103-113).  With the perceptual distance as a third objective the weight is split evenly between realism and
-    closeness to the target, (0, .5, .5); without D it goes to the distance, (0, 1).  A default, not a result: the whole front is in
-    genetic_result."""
+    closeness to the target, (0, .5, .5); without D it goes to the distance, (0, 1).  The latent anchor is one more such column: every
+    column that is not a similarity gets the same weight (with D, LPIPS and the anchor a third each).  A default, not a result: the whole
+    front is in genetic_result."""
     sims = [n.startswith("similarity") for n in names]
     rest = len(names) - sum(sims)
     if rest == 0:           # nothing but similarities (a pareto prompt set without D or LPIPS): no column is preferred
@@ -143,7 +159,8 @@ def main(argv=None, extra_config=None):
     vars(config).update(get_config(config.config))                             # run.py:25
     for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "clip_views", "clip_view_min", "clip_view_flip",
               "clip_view_fixed", "latent_space", "truncation_psi", "truncation_cutoff", "lpips_target", "lpips_size", "lpips_lambda", "lpips_weights",
-              "bpe_path", "pop_size", "stochastic", "target_weight", "prompt_mode", "device_search"):
+              "bpe_path", "pop_size", "stochastic", "target_weight", "prompt_mode", "device_search", "edit_image", "edit_latent", "source_text",
+              "anchor_lambda", "edit_sigma"):
         if k in over:
             setattr(config, k, over[k])
     if "prompt" in over or "image_prompt" in over:
@@ -153,6 +170,7 @@ def main(argv=None, extra_config=None):
     latent_options(config)      # a latent space / truncation on a BigGAN or GPT2 config is refused here, before anything is loaded
     lpips_options(config)       # ... and so is the perceptual objective on the GPT2 config
     prompt_options(config)      # ... and a prompt set there, or one the engine would refuse
+    edit_options(config)        # ... and image editing there, or its anchor on a BigGAN config
     state = dict(iteration=0)
     dist, rank0 = None, True
     if getattr(config, "dist", False):
@@ -185,6 +203,8 @@ def main(argv=None, extra_config=None):
     config = problem.config     # (the perceptual objective with lambda = 0 searches one more objective: the Generator's copy says so)
     operators = get_operators(config)
     os.makedirs(config.tmp_folder, exist_ok=True)
+    if rank0 and getattr(problem.generator, "source_image", None) is not None:      # image editing: what the search moves away from
+        problem.generator.save(problem.generator.source_image[None], os.path.join(config.tmp_folder, "source.jpg"))
     # (same seed on every rank => identical GA state everywhere: no broadcast of the population is needed)
     res = search.minimize(problem, config.algorithm, config.pop_size, config.generations, operators["sampling"],
                           seed=config.seed, callback=save_callback, verbose=rank0, mask=operators.get("mask"),

@@ -93,6 +93,9 @@ typedef struct glass_config {
      * against the shorter struct, selects the one similarity column of today. */
     int32_t sim_columns;          /* 0 or 1: one similarity column (default); K in [2, 4]: K columns, n_obj = K + use_discriminator + (lpips_size > 0 &&
                                      lpips_lambda == 0); lpips_lambda > 0 is refused then */
+    /* --- opt-in: the latent anchor of image editing (see "Image editing" below).  Appended last: zero selects today's pass. */
+    int32_t anchor;               /* 0: off (default); 1: d[p], the mean squared distance between candidate p's dlatents and the anchor's (glass_engine_set_anchor) */
+    float anchor_lambda;          /* 0: d is its own LAST column of F, after the LPIPS column; > 0: no column, F[:,0] = fmaf(anchor_lambda, d, F0) after the LPIPS fold */
 } glass_config;
 
 /* Caller-provided noise (noise_mode 2): planes[m * n_layers + l] points at a host
@@ -193,6 +196,59 @@ int glass_engine_last_set_details(glass_engine* e, int32_t P, float* set_sim /*[
  * comparable with the candidates: by default they reach CLIP without mean / std normalisation, so a picture encoded through clip.py's
  * transform (glass_engine_encode_image) sits in another input distribution.  Overwrites the per-candidate outputs of the last evaluate(). */
 int glass_engine_encode_generated(glass_engine* e, const float* images /*[n][3][R][R] in [-1,1]*/, int32_t n, float* out_feat);
+
+/* Image editing (opt-in; off unless glass_config::anchor is set or glass_engine_set_direction_source is called; departs from the reference's
+ * run.py, which has one text and one objective): a directional CLIP objective relative to a source image, and a latent anchor.
+ *
+ * Directional similarity (StyleGAN-NADA / StyleCLIP's global direction).  While a direction source is set, the entries g_t of the active prompt
+ * set are DIRECTIONS (the host builds them: normalise(g_target - g_source_text)), and feature row f of view v scores against entry t as
+ *   x = f / max(|f|, 1e-8) - src[v],   c = (x . g_t) / max(|x| |g_t|, 1e-8),
+ * src[v] being the unit-length feature of view v of the source image.  A row with x = 0 gives exactly 0.  The mean over views, the weighted sum
+ * acc / W of mode sum and the sign rule of the pareto layout are those of "Prompt sets" above: cbar[p][t] = (sum_v c[p][v][t]) / V in the order
+ * v = 0 .. V - 1; acc = acc + w_t * cbar[p][t] for t = 0 .. T - 1, the product and the sum each rounded to fp32; W = sum_t |w_t|;
+ * F[p][t] = w_t < 0 ? cbar[p][t] : -cbar[p][t] on a front.
+ * Summation order: every sum over the D components — f . f, x . x, x . g_t, g_t . g_t — is taken by one wave as lane-strided partial sums
+ * (i = lane; i < D; i += 64), then the butterfly over lane offsets 32, 16, .. 1; x_i is f_i / nf - src[v][i] with nf = max(sqrt(f . f), 1e-8), one
+ * correctly rounded division and one subtraction; every product and sum is rounded to fp32 on its own (no fused multiply-add), the divisions
+ * and square roots are correctly rounded.  A value is a pure function of (row, view, entry): it does not depend on P, on the row's position,
+ * on how entries share a sweep, or on whether the set was staged in LDS (up to 64 KB) or streamed — and numpy float32 written in this order
+ * reproduces its bits (tests/edit_ref.py).  The source rows are made by the same arithmetic, f_src / max(|f_src|, 1e-8): a candidate whose
+ * feature has the source feature's bits scores exactly 0.  Limits as for a prompt set: V <= 16 views, T <= 16 entries.
+ * Near x = 0 the cosine is that of a rounding-noise vector and means nothing; a search started at the source (the Python layer's edit_latent)
+ * holds row 0 of generation 0 there on purpose, and every other row a step away.
+ *
+ * glass_engine_set_direction_source: after finalize, any time between passes; NULL turns it off.  image host float32 [3][R][R] in [-1, 1] (the
+ * generator's raw range) is kept on the device and encoded through the pass's own preprocessing and image tower (glass_engine_encode_generated's
+ * path) into the unit rows src[v].  Crop views off: once, in this call.  Crop views on: the V features are those of the pass's own boxes, made
+ * at the start of evaluate() whenever the boxes differ from the ones the stored rows were made with — every generation unless the views are
+ * fixed.  With a source set and no active prompt set, evaluate() fails (GLASS_ERR_STATE, "set_targets() first").  An engine without a
+ * generator is refused (GLASS_ERR_STATE); a BigGAN engine is allowed: the source is an image.
+ * glass_engine_last_direction_source: the rows the last pass subtracted, feats [max(views, 1)][clip_embed].
+ *
+ * Latent anchor (StyleCLIP's |w - w_src|^2), glass_config::anchor = 1: d[p] = (1 / (n_lat L)) sum_l sum_i (w[p][l][i] - a[l][i])^2 over the
+ * dlatents the styles are made from — after mapping and truncation, per the latent space — and the anchor's, a [n_lat][L].  fp32; one wave per
+ * candidate sums the flattened index j = l L + i as lane-strided partial sums (j = lane; j < n_lat L; j += 64), difference, product and sum each
+ * rounded on its own, then the butterfly over lane offsets 32, 16, .. 1 and ONE division by float(n_lat L); one writer per candidate.
+ * F: anchor_lambda == 0: d is one more, LAST, column (after the LPIPS column); > 0: F[:,0] = fmaf(anchor_lambda, d, F0), F0 being column 0 after
+ * the LPIPS fold.  n_obj = max(sim_columns, 1) + use_discriminator + (lpips_size > 0 && lpips_lambda == 0) + (anchor && anchor_lambda == 0).
+ *
+ * glass_edit_supported: the one rule (host only: callable without a GPU), applied by create too.  generator: GLASS_GEN_*; lpips_column: the
+ * LPIPS distance is its own column.  anchor 0 needs anchor_lambda 0 and says nothing about n_obj.  anchor 1: a StyleGAN2 engine (a BigGAN
+ * engine and an engine without a generator are refused by name); anchor_lambda finite and >= 0; anchor_lambda > 0 with sim_columns >= 2 is
+ * refused (no single column to fold into); n_obj as above.  Returns GLASS_OK, or GLASS_ERR_ARG with the reason in glass_last_error().
+ * glass_engine_set_anchor: after finalize, on an engine created with anchor = 1 (GLASS_ERR_STATE otherwise).  row [floats_per_row] goes through
+ * the pass's own latent path (pixel norm, mapping and truncation, per the current space) with the kernels the pass uses, and the resulting
+ * [n_lat][L] stays on the device: a candidate whose row equals the anchor's gets d = 0 exactly.  glass_engine_set_truncation after it
+ * recomputes the stored anchor from the row.  evaluate() on an engine created with anchor = 1 fails (GLASS_ERR_STATE, "set_anchor() first")
+ * until it is set.
+ * glass_engine_last_anchor: the distances d [P] of the last evaluate() (whether they are a column of F or folded into column 0).
+ * The device search needs nothing new: the anchor is one more column of F, and search_evaluate scores through the same pass. */
+int glass_edit_supported(int32_t generator, int32_t n_blocks, int32_t sim_columns, int32_t use_discriminator, int32_t lpips_column, int32_t anchor,
+                         float anchor_lambda, int32_t n_obj);
+int glass_engine_set_anchor(glass_engine* e, const float* row /*[floats_per_row]*/);
+int glass_engine_last_anchor(glass_engine* e, int32_t P, float* d);
+int glass_engine_set_direction_source(glass_engine* e, const float* image /*[3][R][R] in [-1,1], or NULL*/);
+int glass_engine_last_direction_source(glass_engine* e, float* feats /*[max(views,1)][clip_embed]*/);
 
 int glass_engine_create(const glass_config* cfg, glass_engine** out);
 /* The target image of the perceptual objective: img host float32 [3][S][S] in [-1, 1], S = lpips_size.  After finalize; runs VGG16 on it once

@@ -231,6 +231,11 @@ int glass_op_rn_tokens(int32_t device, int32_t B, int32_t HW, int32_t C, const f
  * glass_op_cosine_set: launch_cosine_set (prompt sets, include/glass.h): feat [P,V,D], targets [T,D], weights [T] (W = their ordered sum of
  *   magnitudes, taken inside) -> view_sim [P,V] (entry 0's cosines), set_sim [P,T], sim [P].  V, T in [1, 16].
  * glass_op_assemble_F_set: the pareto layout: set_sim [P,K], weights [K], dis / lp [P] (nullable each) -> F [P, K + (dis != 0) + (lp != 0)].
+ * glass_op_cosine_set_dir: launch_cosine_set_dir (image editing, include/glass.h): glass_op_cosine_set's operands plus src [V,D] (unit rows) ->
+ *   the same three outputs for x = f / max(|f|, 1e-8) - src[v] in f's place.  streamed 1: the form that streams the set from memory, at any
+ *   shape (the launcher chooses it above 64 KB).  A shape the launcher does not take (V or T above 16) is refused by name, nothing launched.
+ * glass_op_latent_anchor: launch_latent_anchor: w [P,n_lat,L] (layered 1) or [P,L] (layered 0: the one row serves every layer), a [n_lat,L] ->
+ *   d [P], the mean squared difference.
  * glass_op_image_patches: img [n,3,S,S] -> patches [n (S/ps)^2, ld] (fp16 values), pre-filled with `sentinel`.
  * glass_op_rn_token0_rows: att [B,T,C] (fp16) -> out [B,C] = att[b, 0, :]. */
 int glass_op_mapping(int32_t device, int32_t P, int32_t L, int32_t n_layers, const float* z, const float* wt, const float* b, int32_t path,
@@ -263,6 +268,9 @@ int glass_op_cosine_set(int32_t device, int32_t P, int32_t V, int32_t T, int32_t
                         float* view_sim, float* set_sim, float* sim);
 int glass_op_assemble_F_set(int32_t device, int32_t P, int32_t K, const float* set_sim, const float* weights, const float* dis, const float* lp,
                             float* F);
+int glass_op_cosine_set_dir(int32_t device, int32_t P, int32_t V, int32_t T, int32_t D, const float* feat, const float* targets, const float* weights,
+                            const float* src, int32_t streamed, float* view_sim, float* set_sim, float* sim);
+int glass_op_latent_anchor(int32_t device, int32_t P, int32_t n_lat, int32_t L, int32_t layered, const float* w, const float* a, float* d);
 int glass_op_image_patches(int32_t device, int32_t n, int32_t S, int32_t ps, int32_t ld, const float* img, float sentinel, float* patches);
 int glass_op_rn_token0_rows(int32_t device, int32_t B, int32_t T, int32_t C, const float* att, float* out);
 /* The perceptual objective's own kernels (lpips.hip), each through the launcher the walker (lpips.cpp) calls; a shape the launcher does not
