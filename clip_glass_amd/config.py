@@ -20,8 +20,10 @@ which is always the set's first entry) and `prompt_mode` ("sum", the default: th
 sum_t w_t sim_t / sum_t |w_t|; "pareto": one objective per entry, 2 to 4 — the Generator then searches a copy of the config with `n_obj` =
 entries + discriminator + LPIPS column and `algorithm` "nsga2") — the StyleGAN2 and BigGAN configs; refused for GPT2;
 `device_search` (False, the default: search.py's host operators; True: the population stays on the GPU and the generation step — tournament,
-SBX, polynomial mutation, duplicate flags, survival — runs there, include/glass.h "Device search") — the StyleGAN2 configs on one rank;
-refused for the BigGAN and GPT2 configs, whose rows are not all real;
+SBX, polynomial mutation, duplicate flags, survival — runs there, include/glass.h "Device search") — the StyleGAN2 configs and, with
+half-uniform crossover (probability 0.2 per mating) and bit-flip (10 / 1000 per bit) on the class bits behind the `dim_z` real columns
+("Mixed rows" there), the BigGAN configs, on one rank; refused for the GPT2 config (integer rows, scored through the host tokenizer every
+generation: a device step would not remove the round trip) and with `--dist`;
 `edit_image` (unset, the default: off; a path or an array [3, H, W] in [0, 1], centre-cropped and resized to the generator's side as an image
 prompt is: the similarity becomes directional — how the generated image moved away from this source against how the target moved away
 from `source_text`, include/glass.h "Image editing"), `edit_latent` (a path to a .npy, or an array, of one row in the current latent space:

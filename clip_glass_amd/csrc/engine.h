@@ -283,6 +283,7 @@ struct glass_engine {
     // ---- device search (glass_engine_set_search; pop 0: off — nothing below is allocated or touched) ----
     struct Search {
         int nsga = 0, n_var = 0, cur = 0;   // cur: which of X[2] holds the population
+        int n_real = 0;                     // mixed rows (glass_engine_set_search_mixed): the real columns in front of the bits; 0: all real
         GaParams g = {};                    // g.pop 0: off
         bool ready = false;                 // search_init has run
         int varied_gen = -1;                // the generation whose offspring Xoff holds

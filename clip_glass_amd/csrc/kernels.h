@@ -203,15 +203,26 @@ bool launch_assemble_F_edit(const float* sim, const float* set_sim, const float*
 #define GLASS_SEARCH_DRAW_TOURNAMENT 0u   // purpose words (the counter's fourth): index = mating, variable = 0
 #define GLASS_SEARCH_DRAW_SBX 1u          // index = mating
 #define GLASS_SEARCH_DRAW_MUTATION 2u     // index = offspring row
+#define GLASS_SEARCH_DRAW_BIT_GATE 3u     // mixed rows: index = mating, variable = 0; the mating exchanges bits iff u0 < prob_x
+#define GLASS_SEARCH_DRAW_BIT_KEY 4u      // index = mating, variable = the bit's column; the raw word w0 is the column's key
+#define GLASS_SEARCH_DRAW_BIT_FLIP 5u     // index = offspring row, variable = the bit's column; the bit flips iff u0 < prob_flip
+#define GLASS_SEARCH_MAX_BITS 4096        // bit columns of a mixed row (the bit kernel's LDS holds one key per column)
 struct GaParams {
     int pop;
     double xl, xu, eta_c, eta_m, prob_m;
     uint64_t seed;
+    double prob_x, prob_flip;      // mixed rows only: HUX per mating, bit-flip per bit
 };
 // Every launcher returns the name of the kernel it launched, or nullptr: a shape outside the limits, nothing launched.
 // offspring rows [row0, row0 + rows) of generation `generation` from the population X [pop][n_var] with rank [pop], cd [pop] -> Xoff rows
 const char* launch_ga_vary(const float* X, const int* rank, const double* cd, const GaParams& g, int n_var, int generation, int row0, int rows,
                            float* Xoff, hipStream_t st);
+// the same for mixed rows [n_real real | n_bits bit columns] (include/glass.h "Mixed rows"): `parts` chooses the real columns' kernel, the
+// bit columns' kernel or both (the engine launches them one by one, under a profile row each); nullptr: n_real < 1, n_bits outside
+// [1, GLASS_SEARCH_MAX_BITS], rows outside the pop offspring rows
+enum { GA_VARY_REAL = 1, GA_VARY_BITS = 2, GA_VARY_BOTH = 3 };
+const char* launch_ga_vary_mixed(const float* X, const int* rank, const double* cd, const GaParams& g, int n_real, int n_bits, int generation, int row0,
+                                 int rows, int parts, float* Xoff, hipStream_t st);
 // flags[r] = 1: Xoff row r equals, by value in every variable, a row of X [pop] or an Xoff row below r
 const char* launch_ga_duplicates(const float* X, const float* Xoff, int pop, int n_off, int n_var, int* flags, hipStream_t st);
 // survival over F [n_pop + n_off][n_obj] (population first; flags [n_off] nullable): chosen / rank_out / cd_out [pop_out], F's first pop_out

@@ -1364,6 +1364,30 @@ extern "C" int glass_op_ga_vary(int32_t device, int32_t pop, int32_t n_var, cons
     return st.fetch(out, dO, (size_t)rows * n_var, (size_t)row0 * n_var);
 }
 
+extern "C" int glass_op_ga_vary_mixed(int32_t device, int32_t pop, int32_t n_real, int32_t n_bits, const float* X, const int32_t* rank, const double* cd,
+                                      double xl, double xu, double eta_c, double eta_m, double prob_m, double prob_x, double prob_flip, uint64_t seed,
+                                      int32_t generation, int32_t row0, int32_t rows, float* out) {
+    OPREQ(X && rank && cd && out, "null argument");
+    OPREQ(n_real >= 0 && n_bits >= 0 && n_bits <= (1 << 20), "ga_vary_mixed: bad sizes");
+    const int n_var = n_real + n_bits;
+    TRY(glass_search_supported(pop, n_var, 1, GLASS_SEARCH_NSGA2));
+    OPREQ(rows > 0 && row0 >= 0 && row0 + rows <= pop, "ga_vary_mixed: [row0, row0 + rows) must lie inside the pop offspring rows");
+    Stage st(device);
+    const auto dX = st.in32(X, (size_t)pop * n_var);
+    const auto dr = st.in_i32(rank, pop);
+    const auto dc = st.in(cd, pop);
+    const auto dO = st.poisoned<float>((size_t)pop * n_var, 4);      // every offspring row, and four guard elements behind them
+    GaParams g;
+    g.pop = pop; g.xl = xl; g.xu = xu; g.eta_c = eta_c; g.eta_m = eta_m; g.prob_m = prob_m; g.seed = seed;
+    g.prob_x = prob_x; g.prob_flip = prob_flip;
+    TRY(st.run([&] {
+        return accepted(launch_ga_vary_mixed(dX, dr, dc, g, n_real, n_bits, generation, row0, rows, GA_VARY_BOTH, dO, 0),
+                        "ga_vary_mixed refused the shape (n_real >= 1, n_bits in [1, 4096])");
+    }));
+    TRY(st.intact(dO, "ga_vary_mixed stored past the last row"));
+    return st.fetch(out, dO, (size_t)rows * n_var, (size_t)row0 * n_var);
+}
+
 extern "C" int glass_op_ga_duplicates(int32_t device, int32_t pop, int32_t n_off, int32_t n_var, const float* X, const float* Xoff, int32_t* flags) {
     OPREQ(X && Xoff && flags, "null argument");
     OPREQ(pop >= 1 && pop <= GLASS_SEARCH_MAX_POP && n_off >= 1 && n_off <= GLASS_SEARCH_MAX_POP && n_var >= 1, "ga_duplicates: pop and n_off in [1, 1024]");

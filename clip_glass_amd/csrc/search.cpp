@@ -19,6 +19,14 @@ extern "C" int glass_search_supported(int32_t pop, int32_t n_var, int32_t n_obj,
     return GLASS_OK;
 }
 
+extern "C" int glass_search_mixed_supported(int32_t pop, int32_t n_real, int32_t n_bits, int32_t n_obj, int32_t algorithm) {
+    REQUIRE(n_real >= 1, GLASS_ERR_ARG, "device search: a mixed row needs at least one real column in front of its bits (n_real >= 1), got " + std::to_string(n_real));
+    REQUIRE(n_bits >= 1 && n_bits <= GLASS_SEARCH_MAX_BITS, GLASS_ERR_ARG,
+            "device search: a mixed row has n_bits in [1, " + std::to_string(GLASS_SEARCH_MAX_BITS) + "] (the bit kernel ranks them in one workgroup's LDS), got " +
+                std::to_string(n_bits));
+    return glass_search_supported(pop, n_real + n_bits, n_obj, algorithm);
+}
+
 // what the operators take, whichever setter brings it
 static int check_operators(const char* what, double xl, double xu, double eta_c, double eta_m, double prob_m) {
     REQUIRE(isfinite(xl) && isfinite(xu) && xl < xu && (double)(float)xl == xl && (double)(float)xu == xu, GLASS_ERR_ARG,
@@ -27,13 +35,17 @@ static int check_operators(const char* what, double xl, double xu, double eta_c,
     REQUIRE(prob_m >= 0.0 && prob_m <= 1.0, GLASS_ERR_ARG, std::string(what) + ": prob_m must be in [0, 1]");
     return GLASS_OK;
 }
+static int check_bit_operators(const char* what, double prob_x, double prob_flip) {
+    REQUIRE(prob_x >= 0.0 && prob_x <= 1.0 && prob_flip >= 0.0 && prob_flip <= 1.0, GLASS_ERR_ARG, std::string(what) + ": prob_x and prob_flip must be in [0, 1]");
+    return GLASS_OK;
+}
 
 extern "C" int glass_engine_set_search(glass_engine* e, int32_t algorithm, int32_t pop, double xl, double xu, double eta_c, double eta_m,
                                        double prob_m, uint64_t seed) {
     REQUIRE(e, GLASS_ERR_ARG, "null engine");
     REQUIRE(!e->finalized, GLASS_ERR_STATE, "set_search: the engine is finalized (its buffers are sized in finalize: call it before)");
     REQUIRE(e->cfg.generator != GLASS_GEN_BIGGAN_DEEP, GLASS_ERR_STATE,
-            "set_search: the device search varies real-valued rows; a BigGAN row holds boolean class bits (HUX / bit-flip): it keeps the host search");
+            "set_search: this setter varies real-valued rows; a BigGAN row holds boolean class bits (HUX / bit-flip): use set_search_mixed");
     REQUIRE(e->n_lat > 0, GLASS_ERR_STATE,
             "set_search: the device search varies real-valued latent rows of a StyleGAN2 generator; this engine has none (GPT-2 rows are integers): "
             "it keeps the host search");
@@ -47,6 +59,45 @@ extern "C" int glass_engine_set_search(glass_engine* e, int32_t algorithm, int32
     s.g.pop = pop;
     s.g.xl = xl; s.g.xu = xu; s.g.eta_c = eta_c; s.g.eta_m = eta_m; s.g.prob_m = prob_m;
     s.g.seed = seed;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_search_mixed(glass_engine* e, int32_t algorithm, int32_t pop, int32_t n_real, double xl, double xu, double eta_c,
+                                             double eta_m, double prob_m, double prob_x, double prob_flip, uint64_t seed) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(!e->finalized, GLASS_ERR_STATE, "set_search_mixed: the engine is finalized (its buffers are sized in finalize: call it before)");
+    REQUIRE(e->n_lat == 0, GLASS_ERR_STATE, "set_search_mixed: a StyleGAN2 row has no bit columns: use set_search");
+    REQUIRE(e->cfg.generator == GLASS_GEN_BIGGAN_DEEP, GLASS_ERR_STATE,
+            "set_search_mixed: the device search varies the latent rows of a generator; this engine has none (GPT-2 rows are integers): it keeps the host "
+            "search");
+    REQUIRE(n_real == e->cfg.bg_z_dim, GLASS_ERR_ARG,
+            "set_search_mixed: a BigGAN row is [z | class bits]: n_real must be z_dim = " + std::to_string(e->cfg.bg_z_dim) + ", got " + std::to_string(n_real));
+    if (int rc = glass_search_mixed_supported(pop, n_real, e->cfg.bg_num_classes, e->cfg.n_obj, algorithm)) return rc;
+    REQUIRE(pop <= e->cfg.max_pop && pop % e->cfg.batch_size == 0, GLASS_ERR_ARG,
+            "set_search_mixed: pop must be a multiple of batch_size and at most max_pop (a generation's offspring are scored in one pass)");
+    if (int rc = check_operators("set_search_mixed", xl, xu, eta_c, eta_m, prob_m)) return rc;
+    if (int rc = check_bit_operators("set_search_mixed", prob_x, prob_flip)) return rc;
+    glass_engine::Search& s = e->search;
+    s.nsga = algorithm == GLASS_SEARCH_NSGA2;
+    s.n_real = n_real;
+    s.g.pop = pop;
+    s.g.xl = xl; s.g.xu = xu; s.g.eta_c = eta_c; s.g.eta_m = eta_m; s.g.prob_m = prob_m;
+    s.g.prob_x = prob_x; s.g.prob_flip = prob_flip;
+    s.g.seed = seed;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_search_operators_mixed(glass_engine* e, double xl, double xu, double eta_c, double eta_m, double prob_m, double prob_x,
+                                                       double prob_flip, uint64_t seed) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(e->search.g.pop > 0 && e->search.n_real > 0, GLASS_ERR_STATE,
+            "set_search_operators_mixed: no mixed device search is on (glass_engine_set_search_mixed before finalize)");
+    if (int rc = check_operators("set_search_operators_mixed", xl, xu, eta_c, eta_m, prob_m)) return rc;
+    if (int rc = check_bit_operators("set_search_operators_mixed", prob_x, prob_flip)) return rc;
+    GaParams& g = e->search.g;
+    g.xl = xl; g.xu = xu; g.eta_c = eta_c; g.eta_m = eta_m; g.prob_m = prob_m;
+    g.prob_x = prob_x; g.prob_flip = prob_flip;
+    g.seed = seed;
     return GLASS_OK;
 }
 
@@ -65,7 +116,8 @@ int alloc_search(glass_engine* e) {
     if (!s.g.pop) return GLASS_OK;
     const int pop = s.g.pop, M = e->cfg.n_obj;
     s.n_var = (int)latent_row_floats(e);
-    if (int rc = glass_search_supported(pop, s.n_var, M, s.nsga)) return rc;
+    if (int rc = s.n_real ? glass_search_mixed_supported(pop, s.n_real, s.n_var - s.n_real, M, s.nsga) : glass_search_supported(pop, s.n_var, M, s.nsga))
+        return rc;
     int rc;
     const size_t xn = (size_t)pop * s.n_var;
     if ((rc = dev_alloc(e, &s.X[0], xn))) return rc;
@@ -98,11 +150,19 @@ void launch_vary(glass_engine* e, int generation) {
     glass_engine::Search& s = e->search;
     const int pop = s.g.pop;
     const double xbytes = (double)pop * s.n_var * sizeof(float);
+    const double real_share = s.n_real ? (double)s.n_real / s.n_var : 1.0;
     {
-        Prof pr(e, "search.vary", 0, 3 * xbytes);
-        const char* k = launch_ga_vary(s.X[s.cur], s.rank, s.cd, s.g, s.n_var, generation, 0, pop, s.Xoff, e->cur);
+        Prof pr(e, "search.vary", 0, 3 * xbytes * real_share);
+        const char* k = s.n_real ? launch_ga_vary_mixed(s.X[s.cur], s.rank, s.cd, s.g, s.n_real, s.n_var - s.n_real, generation, 0, pop, GA_VARY_REAL, s.Xoff, e->cur)
+                                 : launch_ga_vary(s.X[s.cur], s.rank, s.cd, s.g, s.n_var, generation, 0, pop, s.Xoff, e->cur);
         if (k) pr.ran("search.vary", k);
         else { pr.drop(); e->launch_error = "search.vary: the launcher refused the shape"; }
+    }
+    if (s.n_real) {      // mixed rows: HUX and bit-flip on the bit columns behind the real ones
+        Prof pr(e, "search.vary_bits", 0, 3 * xbytes * (1.0 - real_share));
+        const char* k = launch_ga_vary_mixed(s.X[s.cur], s.rank, s.cd, s.g, s.n_real, s.n_var - s.n_real, generation, 0, pop, GA_VARY_BITS, s.Xoff, e->cur);
+        if (k) pr.ran("search.vary_bits", k);
+        else { pr.drop(); e->launch_error = "search.vary_bits: the launcher refused the shape"; }
     }
     {
         Prof pr(e, "search.duplicates", 0, 2 * xbytes);
@@ -157,6 +217,14 @@ extern "C" int glass_engine_search_init(glass_engine* e, const float* X0) {
     s.ready = false;
     s.cur = 0;
     s.varied_gen = -1;
+    if (s.n_real)      // mixed rows: a bit column holds exactly 0.0 or 1.0
+        for (int r = 0; r < pop; ++r)
+            for (int j = s.n_real; j < s.n_var; ++j) {
+                const float v = X0[(size_t)r * s.n_var + j];
+                REQUIRE(v == 0.0f || v == 1.0f, GLASS_ERR_ARG,
+                        "search_init: row " + std::to_string(r) + " column " + std::to_string(j) + " is a bit column and holds " + std::to_string(v) +
+                            " (a bit is exactly 0.0 or 1.0)");
+            }
     GLASS_HIP(hipMemcpy(s.X[0], X0, (size_t)pop * s.n_var * sizeof(float), hipMemcpyHostToDevice));
     if (int rc = run_pass(e, nullptr, pop, 0, 0, nullptr, nullptr, nullptr, s.X[0], s.F, true)) return rc;
     launch_survive(e, 0);      // ranks (and orders) the initial population, as minimize's first survive() does

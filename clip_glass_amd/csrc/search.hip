@@ -1,6 +1,7 @@
 // search.hip — the GA / NSGA-II generation step on the device (include/glass.h "Device search"): binary tournament + bounded SBX +
-// polynomial mutation (ga_vary_kernel), exact duplicate flags (ga_duplicates_kernel), rank-and-crowding / fitness survival in ONE
-// workgroup (ga_survive_kernel) and the gather of the surviving rows (ga_gather_kernel).  Numpy mirror: tests/search_device_ref.py.
+// polynomial mutation (ga_vary_kernel), HUX + bit-flip on the bit columns of a mixed row (ga_vary_bits_kernel), exact duplicate flags
+// (ga_duplicates_kernel), rank-and-crowding / fitness survival in ONE workgroup (ga_survive_kernel) and the gather of the surviving rows
+// (ga_gather_kernel).  Numpy mirrors: tests/search_device_ref.py, tests/search_mixed_ref.py.
 #include <math.h>
 
 #include "../../include/glass.h"
@@ -17,6 +18,12 @@ __device__ __forceinline__ Draw4 ga_draw(const GaParams& g, uint32_t index, uint
 #pragma unroll
     for (int i = 0; i < 4; ++i) d.u[i] = ((double)c[i] + 0.5) * (1.0 / 4294967296.0);
     return d;
+}
+// the raw first word of the same block (the bit key of a mixed row's HUX)
+__device__ __forceinline__ uint32_t ga_word(const GaParams& g, uint32_t index, uint32_t var, uint32_t generation, uint32_t purpose) {
+    uint32_t c[4] = {index, var, generation, purpose};
+    philox4x32_10(c, (uint32_t)(g.seed & 0xFFFFFFFFu), (uint32_t)(g.seed >> 32) ^ GLASS_SEARCH_TAG);
+    return c[0];
 }
 
 // the winner of a binary tournament between rows a and b: lower rank, then larger crowding distance, `>=` going to a (search.py:221)
@@ -64,19 +71,21 @@ __device__ float ga_vary_one(const GaParams& g, float paf, float pbf, int m, int
     return (float)x;
 }
 
-// grid (ceil(n_var / (256 VEC)), rows): offspring row r = row0 + blockIdx.y is child r & 1 of mating r >> 1.  VEC 4 where n_var % 4 == 0
-// (every row is then 16-byte aligned), 1 otherwise.  Nothing depends on the grid: a draw is a function of (seed, generation, row, variable).
+// grid (ceil(n_var / (256 VEC)), rows): offspring row r = row0 + blockIdx.y is child r & 1 of mating r >> 1.  The rows are `stride` floats
+// apart and columns [0, n_var) of them are varied (an all-real row: stride = n_var; a mixed row: its real columns).  VEC 4 where n_var % 4
+// == 0 and stride % 4 == 0 (every row is then 16-byte aligned), 1 otherwise.  Nothing depends on the grid: a draw is a function of (seed,
+// generation, row, variable).
 template <int VEC>
 __global__ __launch_bounds__(256) void ga_vary_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
-                                                      GaParams g, int n_var, int generation, int row0, float* __restrict__ Xoff) {
+                                                      GaParams g, int n_var, int stride, int generation, int row0, float* __restrict__ Xoff) {
     const int r = row0 + blockIdx.y, m = r >> 1;
     const int j0 = (blockIdx.x * 256 + threadIdx.x) * VEC;
     if (j0 >= n_var) return;
     int ia, ib;
     ga_parents(g, rank, cd, m, (uint32_t)generation, &ia, &ib);
-    const float* pa = X + (size_t)ia * n_var + j0;
-    const float* pb = X + (size_t)ib * n_var + j0;
-    float* out = Xoff + (size_t)r * n_var + j0;
+    const float* pa = X + (size_t)ia * stride + j0;
+    const float* pb = X + (size_t)ib * stride + j0;
+    float* out = Xoff + (size_t)r * stride + j0;
     if (VEC == 4) {
         const f4 a = *(const f4*)pa, b = *(const f4*)pb;
         f4 o;
@@ -148,6 +157,52 @@ __device__ __forceinline__ bool ga_dominates(const float* Fs, int M, int i, int 
 }
 
 __host__ __device__ inline int ga_pow2(int n) { int p = 2; while (p < n) p <<= 1; return p; }
+
+// The bit columns [n_real, n_real + n_bits) of offspring row r = row0 + blockIdx.x (include/glass.h "Mixed rows"): half-uniform crossover of
+// the mating's parents, then bit-flip.  One workgroup per row; both children of a mating redo the selection, so a slice of rows stands
+// alone.  The differing columns D go to LDS as (key << 32 | column) in whatever order the atomics give — only the keys' ranks matter —
+// padded to a power of two and sorted; the first (|D| + 1) >> 1 of them are exchanged.  LDS holds the worst case (|D| = n_bits <=
+// GLASS_SEARCH_MAX_BITS), the sort runs over the actual |D|.
+__global__ __launch_bounds__(256) void ga_vary_bits_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
+                                                           GaParams g, int n_real, int n_bits, int generation, int row0, float* __restrict__ Xoff) {
+#pragma clang fp contract(off)
+    __shared__ unsigned long long keys[GLASS_SEARCH_MAX_BITS];
+    __shared__ unsigned char xchg[GLASS_SEARCH_MAX_BITS];
+    __shared__ int s_n;
+    const int r = row0 + blockIdx.x, m = r >> 1, child = r & 1, stride = n_real + n_bits, tid = threadIdx.x;
+    int ia, ib;
+    ga_parents(g, rank, cd, m, (uint32_t)generation, &ia, &ib);
+    const float* A = X + (size_t)ia * stride + n_real;
+    const float* B = X + (size_t)ib * stride + n_real;
+    float* out = Xoff + (size_t)r * stride + n_real;
+    const bool open = ga_draw(g, (uint32_t)m, 0u, (uint32_t)generation, GLASS_SEARCH_DRAW_BIT_GATE).u[0] < g.prob_x;      // uniform over the workgroup
+    if (tid == 0) s_n = 0;
+    for (int j = tid; j < n_bits; j += 256) xchg[j] = 0;
+    __syncthreads();
+    if (open) {
+        for (int j = tid; j < n_bits; j += 256)
+            if (A[j] != B[j]) {
+                const uint32_t col = (uint32_t)(n_real + j);
+                keys[atomicAdd(&s_n, 1)] = ((unsigned long long)ga_word(g, (uint32_t)m, col, (uint32_t)generation, GLASS_SEARCH_DRAW_BIT_KEY) << 32) | col;
+            }
+        __syncthreads();
+        const int nD = s_n, take = (nD + 1) >> 1;
+        if (nD > 1) {      // (one differing column is exchanged whatever its key)
+            const int N2 = ga_pow2(nD);
+            for (int i = nD + tid; i < N2; i += 256) keys[i] = ~0ull;
+            __syncthreads();
+            ga_sort(keys, N2);
+        }
+        for (int p = tid; p < take; p += 256) xchg[(int)(keys[p] & 0xFFFFFFFFu) - n_real] = 1;
+        __syncthreads();
+    }
+    for (int j = tid; j < n_bits; j += 256) {
+        const float a = A[j], b = B[j];
+        float x = (child != 0) == (xchg[j] != 0) ? a : b;      // child 0 keeps A's bit and child 1 B's, unless the column is exchanged
+        if (ga_draw(g, (uint32_t)r, (uint32_t)(n_real + j), (uint32_t)generation, GLASS_SEARCH_DRAW_BIT_FLIP).u[0] < g.prob_flip) x = 1.0f - x;
+        out[j] = x;
+    }
+}
 
 // F [n_pop + n_off][M]: the population's rows, then the offspring's.  Left out of survival: offspring rows with a flag or a non-finite F.
 // Out: chosen [pop_out] merged indices in survival order (-1: fewer rows than pop_out were eligible), their rank and distance, and F's
@@ -294,15 +349,33 @@ size_t ga_survive_lds_bytes(int n_rows, int n_obj) {
     return N2 * 8 + N * 8 + N * (size_t)n_obj * 4 + 3 * N * 4 + (N + 2) * 4;
 }
 
+// columns [0, n_var) of rows `stride` floats apart
+static const char* launch_ga_vary_cols(const float* X, const int* rank, const double* cd, const GaParams& g, int n_var, int stride, int generation,
+                                       int row0, int rows, float* Xoff, hipStream_t st) {
+    if (n_var % 4 == 0 && stride % 4 == 0) {
+        hipLaunchKernelGGL(ga_vary_kernel<4>, dim3((n_var / 4 + 255) / 256, rows), dim3(256), 0, st, X, rank, cd, g, n_var, stride, generation, row0, Xoff);
+        return "ga_vary_kernel<4>";
+    }
+    hipLaunchKernelGGL(ga_vary_kernel<1>, dim3((n_var + 255) / 256, rows), dim3(256), 0, st, X, rank, cd, g, n_var, stride, generation, row0, Xoff);
+    return "ga_vary_kernel<1>";
+}
+
 const char* launch_ga_vary(const float* X, const int* rank, const double* cd, const GaParams& g, int n_var, int generation, int row0, int rows,
                            float* Xoff, hipStream_t st) {
     if (rows <= 0 || row0 < 0 || row0 + rows > g.pop || n_var <= 0) return nullptr;
-    if (n_var % 4 == 0) {
-        hipLaunchKernelGGL(ga_vary_kernel<4>, dim3((n_var / 4 + 255) / 256, rows), dim3(256), 0, st, X, rank, cd, g, n_var, generation, row0, Xoff);
-        return "ga_vary_kernel<4>";
-    }
-    hipLaunchKernelGGL(ga_vary_kernel<1>, dim3((n_var + 255) / 256, rows), dim3(256), 0, st, X, rank, cd, g, n_var, generation, row0, Xoff);
-    return "ga_vary_kernel<1>";
+    return launch_ga_vary_cols(X, rank, cd, g, n_var, n_var, generation, row0, rows, Xoff, st);
+}
+
+const char* launch_ga_vary_mixed(const float* X, const int* rank, const double* cd, const GaParams& g, int n_real, int n_bits, int generation, int row0,
+                                 int rows, int parts, float* Xoff, hipStream_t st) {
+    if (rows <= 0 || row0 < 0 || row0 + rows > g.pop || n_real < 1 || n_bits < 1 || n_bits > GLASS_SEARCH_MAX_BITS || !(parts & GA_VARY_BOTH)) return nullptr;
+    const char* real = nullptr;
+    if (parts & GA_VARY_REAL) real = launch_ga_vary_cols(X, rank, cd, g, n_real, n_real + n_bits, generation, row0, rows, Xoff, st);
+    if (parts & GA_VARY_BITS)
+        hipLaunchKernelGGL(ga_vary_bits_kernel, dim3(rows), dim3(256), 0, st, X, rank, cd, g, n_real, n_bits, generation, row0, Xoff);
+    if (!(parts & GA_VARY_BITS)) return real;
+    if (!(parts & GA_VARY_REAL)) return "ga_vary_bits_kernel";
+    return n_real % 4 == 0 && n_bits % 4 == 0 ? "ga_vary_kernel<4> + ga_vary_bits_kernel" : "ga_vary_kernel<1> + ga_vary_bits_kernel";
 }
 
 const char* launch_ga_duplicates(const float* X, const float* Xoff, int pop, int n_off, int n_var, int* flags, hipStream_t st) {

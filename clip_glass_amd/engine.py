@@ -134,6 +134,10 @@ def load_library(path=None):
         lib.glass_engine_search_step.argtypes = [C.c_void_p, C.c_int32]
         lib.glass_engine_search_read.argtypes = [C.c_void_p, fp, fp, ip, dp, fp, fp, ip, ip]
         lib.glass_engine_latent_uploads.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(lib, "glass_search_mixed_supported"):    # (absent from older A/B builds loaded through GLASS_LIB)
+        lib.glass_search_mixed_supported.argtypes = [C.c_int32] * 5
+        lib.glass_engine_set_search_mixed.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_double] * 7 + [C.c_uint64]
+        lib.glass_engine_set_search_operators_mixed.argtypes = [C.c_void_p] + [C.c_double] * 7 + [C.c_uint64]
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -300,6 +304,19 @@ def search_supported(pop, n_var, n_obj, algorithm):
         return False, "device search: unknown algorithm %r (expected one of %s)" % (algorithm, ", ".join(SEARCH_ALGORITHMS))
     lib = load_library()
     rc = lib.glass_search_supported(int(pop), int(n_var), int(n_obj), SEARCH_ALGORITHMS[algorithm])
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
+SEARCH_MAX_BITS = 4096
+
+
+def mixed_search_supported(pop, n_real, n_bits, n_obj, algorithm):
+    """(ok, message) for a device search of `pop` mixed rows — n_real real columns, then n_bits bit columns: the library's own rule
+    (glass_search_mixed_supported), the one glass_engine_set_search_mixed and finalize apply.  Host only."""
+    if algorithm not in SEARCH_ALGORITHMS:
+        return False, "device search: unknown algorithm %r (expected one of %s)" % (algorithm, ", ".join(SEARCH_ALGORITHMS))
+    lib = load_library()
+    rc = lib.glass_search_mixed_supported(int(pop), int(n_real), int(n_bits), int(n_obj), SEARCH_ALGORITHMS[algorithm])
     return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
 
 
@@ -594,6 +611,22 @@ class Engine:
         """Any time after set_search: the values that size nothing (the bounds of a w / w+ search are known only after finalize())."""
         _check(self.lib, self.lib.glass_engine_set_search_operators(self._h, float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m),
                                                                      int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def set_search_mixed(self, algorithm, pop, n_real, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, prob_x=0.2, prob_flip=0.01, seed=1):
+        """Between construction and finalize(), BigGAN engines: turn the device search on for `pop` mixed rows — n_real (= z_dim) real
+        columns with scalar bounds xl / xu, then the class bits, varied by HUX (prob_x per mating) and bit-flip (prob_flip per bit)."""
+        if algorithm not in SEARCH_ALGORITHMS:
+            raise ValueError("unknown search algorithm %r: expected one of %s" % (algorithm, ", ".join(SEARCH_ALGORITHMS)))
+        _check(self.lib, self.lib.glass_engine_set_search_mixed(self._h, SEARCH_ALGORITHMS[algorithm], int(pop), int(n_real), float(xl), float(xu),
+                                                                 float(eta_c), float(eta_m), float(prob_m), float(prob_x), float(prob_flip),
+                                                                 int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self.search_pop = int(pop)
+        self.search_n_real = int(n_real)
+
+    def set_search_operators_mixed(self, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, prob_x=0.2, prob_flip=0.01, seed=1):
+        """Any time after set_search_mixed: the values that size nothing."""
+        _check(self.lib, self.lib.glass_engine_set_search_operators_mixed(self._h, float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m),
+                                                                           float(prob_x), float(prob_flip), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
     def search_init(self, X0):
         """Upload the initial population [pop, floats_per_row], score it as generation 0 and rank it."""

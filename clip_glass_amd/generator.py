@@ -594,13 +594,11 @@ class Generator:
                        clip_view_flip=bool(view_opt("clip_view_flip", True)),
                        clip_view_fixed=bool(view_opt("clip_view_fixed", False))) if self.clip_views else {}
         # device search (opt-in, include/glass.h "Device search"): the engine keeps the population and runs the generation step; its buffers
-        # are sized in finalize, so the engine is told here.  Real-valued rows only: refused by name for the GPT2 and BigGAN configs
+        # are sized in finalize, so the engine is told here.  StyleGAN2 rows are real-valued (set_search), BigGAN rows are [z | class bits]
+        # (set_search_mixed); the GPT2 config is refused by name: its scoring goes through the host tokenizer every generation
         self.device_search = bool(getattr(config, "device_search", False))
         if self.device_search and config.task == "img2txt":
             raise ValueError("device_search: the GPT2 config searches integer token rows (int_sbx / int_pm): it keeps the host search")
-        if self.device_search and hasattr(self.model, "geometry"):
-            raise ValueError("device_search: the BigGAN configs search [z | boolean class bits] rows (HUX / bit-flip on the bits): they keep the "
-                             "host search")
         if self.device_search and sharded:
             raise ValueError("device_search: more than one rank (--dist) is not wired to the device search yet: run one rank, or the host search")
         if config.task == "img2txt":                                        # generator.py:25-27, 52-59
@@ -654,6 +652,15 @@ class Generator:
             self.engine = Engine([], batch_size=config.batch_size, max_pop=pop, chunk=getattr(config, "chunk", 0),
                                  device=device, biggan=self.model.geometry, clip_resize=clip_resize,
                                  clip_normalize=clip_normalize, **tower)
+            if self.device_search:
+                from .search import DEVICE_PROB_FLIP, DEVICE_PROB_HUX
+                try:      # the reference's operators.py:50-58: HUX with probability 0.2 per mating, bit-flip with 10 / 1000 per bit
+                    self.engine.set_search_mixed(config.algorithm, int(config.pop_size), int(config.dim_z),
+                                                 float(np.float32(config.problem_args["xl"])), float(np.float32(config.problem_args["xu"])),
+                                                 prob_x=DEVICE_PROB_HUX, prob_flip=DEVICE_PROB_FLIP, seed=int(getattr(config, "seed", 1) or 1))
+                except RuntimeError as ex:
+                    self.engine.close()
+                    raise ValueError("device_search: %s" % ex)
         else:
             self.engine = Engine(self.model.channels[::-1], latent_size=config.dim_z,
                                  mapping_layers=getattr(config, "mapping_layers", 8), batch_size=config.batch_size,

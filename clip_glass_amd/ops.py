@@ -95,6 +95,7 @@ SIGNATURES = {
     "glass_op_maxpool2": [i32, i32, i32, i32, i32, fp, fp],
     "glass_op_lpips_head": [i32, i32, i32, i32, i32, fp, fp, fp, fp],
     "glass_op_ga_vary": [i32, i32, i32, fp, ip, dp, f64, f64, f64, f64, f64, u64, i32, i32, i32, fp],
+    "glass_op_ga_vary_mixed": [i32, i32, i32, i32, fp, ip, dp, f64, f64, f64, f64, f64, f64, f64, u64, i32, i32, i32, fp],
     "glass_op_ga_duplicates": [i32, i32, i32, i32, fp, fp, ip],
     "glass_op_ga_survive": [i32, i32, i32, i32, i32, i32, fp, ip, ip, ip, dp, fp, ip, i32, fp, fp, fp],
     "glass_op_mfma_probe": [i32, fp, fp, fp],
@@ -1028,6 +1029,22 @@ def ga_vary(X, rank, cd, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, seed=1, gener
     _check(lib, lib.glass_op_ga_vary(device, pop, nv, _fp(X), rank.ctypes.data_as(ip), cd.ctypes.data_as(dp),
                                      float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                      int(generation), int(row0), int(rows), _fp(out)))
+    return out
+
+
+def ga_vary_mixed(X, n_real, rank, cd, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, prob_x=0.2, prob_flip=0.01, seed=1, generation=1, row0=0,
+                  rows=None, device=0):
+    """Offspring rows [row0, row0 + rows) of the mixed population X float32 [pop, n_real + n_bits] (bit columns 0.0 / 1.0)."""
+    lib = _lib()
+    X = _f32(X)
+    pop, nv = X.shape
+    rows = pop - row0 if rows is None else rows
+    rank = np.ascontiguousarray(rank, dtype=np.int32)
+    cd = np.ascontiguousarray(cd, dtype=np.float64)
+    out = np.empty((rows, nv), dtype=np.float32)
+    _check(lib, lib.glass_op_ga_vary_mixed(device, pop, int(n_real), nv - int(n_real), _fp(X), rank.ctypes.data_as(ip), cd.ctypes.data_as(dp),
+                                           float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m), float(prob_x), float(prob_flip),
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation), int(row0), int(rows), _fp(out)))
     return out
 
 

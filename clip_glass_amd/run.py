@@ -95,8 +95,9 @@ def build_parser():
     p.add_argument("--stochastic", action="store_true", default=None,
                    help="GPT2 config: top-k temperature sampling instead of greedy decoding (the config table's `stochastic`)")
     p.add_argument("--device-search", action="store_true", default=None,
-                   help="StyleGAN2 configs, one rank: keep the population on the GPU and run selection, crossover, mutation, duplicate flags and "
-                        "survival there between the passes (off by default: the host search of search.py)")
+                   help="StyleGAN2 and BigGAN configs, one rank: keep the population on the GPU and run selection, crossover, mutation (on a "
+                        "BigGAN row: SBX / polynomial mutation on z, half-uniform crossover / bit-flip on the class bits), duplicate flags and "
+                        "survival there between the passes (off by default: the host search of search.py; refused for GPT2 and with --dist)")
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--dist", action="store_true",
                    help="multi-GPU: run under `torchrun --nproc-per-node N -m clip_glass_amd.run --dist ...` (one process per GPU, "

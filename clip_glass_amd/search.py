@@ -167,6 +167,7 @@ class Result:
 
 
 DEVICE_MAX_POP = 1024      # include/glass.h "Device search": survival ranks 2 pop merged rows in one workgroup
+DEVICE_PROB_HUX, DEVICE_PROB_FLIP = 0.2, 10 / 1000      # what vary() above gives hux and bitflip (operators.py:50-58), for a mixed device search
 
 
 class _DeviceAlgorithm:
@@ -203,10 +204,21 @@ def _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callba
     """The generation step on the device (include/glass.h "Device search"): generation 0 is sampled, de-duplicated and refilled on the host
     as below, then every generation is one engine.search_step and a read of F.  Refusals come first and name their reason."""
     mask = np.asarray(["real"] * problem.n_var if mask is None else list(mask))
+    n_real = None      # a mixed search: the real columns in front of the bits
     if (mask != "real").any():
-        raise ValueError("device search: every variable must be real, and this mask has %s ones (the BigGAN configs' class bits use HUX / "
-                         "bit-flip, GPT2's tokens the integer operators): they keep the host search"
-                         % " / ".join(sorted(set(mask[mask != "real"].tolist()))))
+        others = sorted(set(mask[mask != "real"].tolist()))
+        if others != ["bool"]:
+            raise ValueError("device search: the variables must be real, or real followed by bool, and this mask has %s ones (GPT2's int tokens "
+                             "use the integer operators and are scored through the host tokenizer): they keep the host search" % " / ".join(others))
+        n_real = int((mask == "real").sum())
+        if n_real == 0 or (mask[:n_real] != "real").any():
+            raise ValueError("device search: a mixed row is its real columns followed only by its bool columns (a BigGAN row: [z | class "
+                             "bits]); this mask has a bool column in front of a real one: it keeps the host search")
+        have = getattr(getattr(problem, "engine", None), "search_n_real", None)
+        if have != n_real:
+            raise ValueError("device search: this mask has %d real columns followed by %d bool ones, and the engine's search was set up for %s: "
+                             "Engine.set_search_mixed(..., n_real=%d, ...) before finalize (config.device_search = True on a BigGAN config does it)"
+                             % (n_real, mask.size - n_real, "all-real rows" if have is None else "%d real columns" % have, n_real))
     ranks = int(getattr(problem, "ranks", 1) or 1)
     if ranks > 1:
         raise ValueError("device search: %d ranks (--dist): the multi-rank wiring is not built yet; run one rank, or the host search" % ranks)
@@ -237,7 +249,10 @@ def _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callba
         X = X[_eliminate_duplicates(X)]
     if X.shape[0] != pop_size:
         raise ValueError("device search: the sampler keeps returning duplicate rows: %d distinct of %d" % (X.shape[0], pop_size))
-    engine.set_search_operators(float(xl[0]), float(xu[0]), eta_c, eta_m, prob_m, seed)
+    if n_real is None:
+        engine.set_search_operators(float(xl[0]), float(xu[0]), eta_c, eta_m, prob_m, seed)
+    else:
+        engine.set_search_operators_mixed(float(xl[0]), float(xu[0]), eta_c, eta_m, prob_m, DEVICE_PROB_HUX, DEVICE_PROB_FLIP, seed)
     engine.search_init(X)
     generator = getattr(problem, "generator", None)
     algo = _DeviceAlgorithm(problem, engine, nsga)
@@ -263,7 +278,7 @@ def minimize(problem, algorithm, pop_size, n_gen, sampling, seed=1, callback=Non
     algorithm: "ga" | "nsga2"; sampling: object with _do(problem, n) (operators.get_operators);
     mask: per-variable type "real" | "int" | "bool" (None = all real) — the BigGAN configs mix real z with
     boolean class bits (operators.py:39), the GPT2 config is all-int.
-    device=True (opt-in; real-valued StyleGAN2 searches on one rank): selection, variation, duplicate flags and survival run on the
+    device=True (opt-in; real-valued StyleGAN2 searches and the BigGAN configs' [real | bool] rows, on one rank): selection, variation, duplicate flags and survival run on the
     problem's engine between the passes (include/glass.h "Device search"); the result has the same shapes."""
     if device:
         return _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callback, eta_c, eta_m, prob_m, verbose, mask)

@@ -320,6 +320,7 @@ def gpt2_sample_uniform(seed, generation, row, step, purpose=GPT2_SAMPLE_EVALUAT
 # purpose) under the seed with this tag XOR-ed into the key's high word.
 SEARCH_TAG = 0x53524348
 SEARCH_DRAW_TOURNAMENT, SEARCH_DRAW_SBX, SEARCH_DRAW_MUTATION = 0, 1, 2      # purpose words
+SEARCH_DRAW_BIT_GATE, SEARCH_DRAW_BIT_KEY, SEARCH_DRAW_BIT_FLIP = 3, 4, 5     # mixed rows: HUX gate (mating, 0), bit key (mating, j: the raw w0), bit-flip (row, j)
 
 
 def search_uniforms(seed, generation, index, variable, purpose):

@@ -405,9 +405,11 @@ int glass_engine_get_biggan_tap(glass_engine* e, float* out, int64_t capacity, i
 /* Device search (opt-in; off unless glass_engine_set_search is called): the GA / NSGA-II generation step — mating, variation, duplicate
  * flags, survival — on the device, between two passes, in static shapes and with no host decision.  The population (pop rows of
  * floats_per_row fp32 variables), its F, rank and crowding distance stay in device buffers; a generation is glass_engine_search_step.
- * Real-valued rows only: StyleGAN2 engines in z, w and w+.  A BigGAN engine (boolean class bits: HUX / bit-flip) and an engine without a
- * generator (GPT-2: integer rows) are refused by name and keep the host search of clip_glass_amd/search.py, which this section restates
- * operator by operator; where it departs from it, it says so.
+ * Real-valued rows: StyleGAN2 engines in z, w and w+ (glass_engine_set_search).  Mixed rows — real columns, then boolean bit columns: a
+ * BigGAN engine's [z | class bits] — through glass_engine_set_search_mixed ("Mixed rows" below); glass_engine_set_search refuses a BigGAN
+ * engine by name.  An engine without a generator (GPT-2: integer rows, scored through the host tokenizer every generation) is refused by
+ * name and keeps the host search of clip_glass_amd/search.py, which this section restates operator by operator; where it departs from it,
+ * it says so.
  *
  * Random numbers.  Philox4x32-10 under key (seed_lo, seed_hi ^ 0x53524348); a draw is u = (word + 0.5) 2^-32, exact in double.  The counter
  * is (index, variable, generation, purpose) and words (w0, w1, w2, w3) give (u0, u1, u2, u3):
@@ -434,6 +436,25 @@ int glass_engine_get_biggan_tap(glass_engine* e, float* out, int64_t capacity, i
  * All of it is evaluated in double, in search.py's order of operations and without fused multiply-adds, and rounded ONCE to the fp32 row:
  * a float64 mirror agrees to that rounding and the last bit of pow().  xl and xu must be exact in fp32.
  *
+ * Mixed rows.  A mixed row is n_real real columns followed by n_bits bit columns (fp32 0.0 / 1.0); n_var = n_real + n_bits, and "variable j"
+ * is always the column index in the whole row.  The real columns behave exactly as above — the same tournament, the same draws at counter
+ * (index, j, generation, purpose 1 / 2), the same double arithmetic rounded once: columns [0, n_real) of a mixed search equal, bit for bit,
+ * the offspring of an all-real search of width n_real with the same seed, generation, ranks and parents' values.  The bit columns take three
+ * more purpose words:
+ *   purpose 3, bit-crossover gate: index = mating m, variable = 0.  The mating exchanges bits iff u0 < prob_x.
+ *   purpose 4, bit key:            index = mating m, variable = j.  The raw 32-bit word w0 is column j's key.
+ *   purpose 5, bit-flip:           index = offspring row r, variable = j.  The bit flips iff u0 < prob_flip.
+ * Half-uniform crossover (search.hux with prob_hux = 0.5): D is the set of bit columns where the two parents differ by value and n =
+ * (|D| + 1) >> 1.  If the gate is open, column j of D is exchanged iff fewer than n columns j' of D have (key[j'], j') < (key[j], j): child 0
+ * (row 2m) then takes parent B's bit and child 1 (row 2m + 1) parent A's.  Every other bit column is copied, child 0 from A and child 1 from
+ * B.  Independent keys rank D in a uniformly random order, so the exchanged columns are a uniformly random n-subset of D, as
+ * rng.permutation(diff)[:n] is; equal keys are broken by the column index, a bias of order |D|^2 / 2^33.  Then bit-flip on each child: x ->
+ * 1 - x where the purpose-5 gate fires (search.bitflip).  Bits are never clipped and never touched by SBX or the polynomial mutation.  As
+ * for the real columns, a draw is a pure function of (seed, generation, m or r, j, purpose): offspring rows made in one launch or in
+ * several, in any grid, agree bit for bit.  An odd pop drops the last mating's second child.  Duplicate flags, survival and the gather do
+ * not care what a column means and are used unchanged.  search_init checks on the host that every bit column of X0 holds exactly 0.0 or
+ * 1.0 (GLASS_ERR_ARG otherwise, naming the first offending row and column).  Numpy mirror: tests/search_mixed_ref.py.
+ *
  * Duplicates.  Offspring row r is flagged when it equals, by value in every variable (-0.0 equals 0.0), a row of the current population or
  * an offspring row with a lower index.  A flagged row is still scored — the shapes stay static — and is left out of survival.  search.py
  * drops such rows and refills the batch with fresh matings instead (and compares with a tolerance of 1e-16): the device search may
@@ -452,11 +473,18 @@ int glass_engine_get_biggan_tap(glass_engine* e, float* out, int64_t capacity, i
  * glass_search_supported: the one rule (host only: callable without a GPU), applied by the setter and by finalize.  algorithm 0 (GA, n_obj
  * 1) or 1 (NSGA-II); pop in [2, 1024] (2048 merged rows are ranked by one workgroup); n_obj in [1, 6]; pop * n_var below 2^31.
  *
+ * glass_search_mixed_supported: the same for mixed rows (host only) — everything glass_search_supported says for n_var = n_real + n_bits,
+ *   n_real >= 1 and 1 <= n_bits <= 4096 (one workgroup ranks a row's differing bits in LDS).
+ *
  * glass_engine_set_search: between create and finalize, which sizes the buffers (GLASS_ERR_STATE after it).  pop <= max_pop and a
  * multiple of batch_size; noise_mode 0 or 1 (caller-provided planes would come from the host every pass).  n_var is the engine's
  * floats_per_row.
  * glass_engine_set_search_operators: any time after set_search — the values that size nothing (bounds, eta, prob_m, seed).  The bounds of a
  *   search in w / w+ come from the mapping network and are known only after finalize.
+ * glass_engine_set_search_mixed: the same for a BigGAN engine, whose rows are mixed: n_real must be the engine's z_dim (n_bits is then its
+ *   num_classes); prob_x (HUX, per mating) and prob_flip (per bit) in [0, 1].  A StyleGAN2 engine (no bits) and an engine without a
+ *   generator are refused by name (GLASS_ERR_STATE).  The search_* entry points below work unchanged on a mixed search.
+ * glass_engine_set_search_operators_mixed: any time after set_search_mixed — the values that size nothing, prob_x and prob_flip among them.
  * glass_engine_search_init: X0 host float32 [pop][floats_per_row]: uploads it, scores it as generation 0 and ranks (and orders) it as
  *   minimize's first survive() does.
  * glass_engine_search_vary(generation): the offspring of the current population and their duplicate flags.
@@ -477,6 +505,11 @@ int glass_search_supported(int32_t pop, int32_t n_var, int32_t n_obj, int32_t al
 int glass_engine_set_search(glass_engine* e, int32_t algorithm, int32_t pop, double xl, double xu, double eta_c, double eta_m, double prob_m,
                             uint64_t seed);
 int glass_engine_set_search_operators(glass_engine* e, double xl, double xu, double eta_c, double eta_m, double prob_m, uint64_t seed);
+int glass_search_mixed_supported(int32_t pop, int32_t n_real, int32_t n_bits, int32_t n_obj, int32_t algorithm);
+int glass_engine_set_search_mixed(glass_engine* e, int32_t algorithm, int32_t pop, int32_t n_real, double xl, double xu, double eta_c, double eta_m,
+                                  double prob_m, double prob_x, double prob_flip, uint64_t seed);
+int glass_engine_set_search_operators_mixed(glass_engine* e, double xl, double xu, double eta_c, double eta_m, double prob_m, double prob_x,
+                                            double prob_flip, uint64_t seed);
 int glass_engine_search_init(glass_engine* e, const float* X0 /*[pop][floats_per_row]*/);
 int glass_engine_search_vary(glass_engine* e, int32_t generation);
 int glass_engine_search_evaluate(glass_engine* e, int32_t generation, int32_t first_row, int32_t rows);

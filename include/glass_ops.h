@@ -288,12 +288,17 @@ int glass_op_lpips_head(int32_t device, int32_t n, int32_t HW, int32_t C, int32_
 /* The device search's kernels (search.hip; include/glass.h "Device search"), each through the launcher the engine calls; a shape the launcher
  * does not take is refused by name (GLASS_ERR_ARG).
  * glass_op_ga_vary: X [pop,n_var], rank int32 [pop], cd double [pop] -> offspring rows [row0, row0 + rows) of `generation`, out [rows,n_var].
+ * glass_op_ga_vary_mixed: the same for mixed rows of n_real real columns and n_bits bit columns (0.0 / 1.0), X and out [.,n_real + n_bits]:
+ *   both kernels of launch_ga_vary_mixed.
  * glass_op_ga_duplicates: X [pop,n_var], Xoff [n_off,n_var] -> flags int32 [n_off].
  * glass_op_ga_survive: F [n_pop + n_off, n_obj] (population first), flags int32 [n_off] (nullable) -> chosen int32 [pop_out] (merged indices in
  *   survival order), rank int32 [pop_out], cd double [pop_out], F_out [pop_out,n_obj], counts int32 [2] = {flagged, non-finite rows}; with X
  *   [n_pop,n_var] and Xoff [n_off,n_var] (nullable together) the gathered rows X_out [pop_out,n_var] too.  nsga 0: GA. */
 int glass_op_ga_vary(int32_t device, int32_t pop, int32_t n_var, const float* X, const int32_t* rank, const double* cd, double xl, double xu,
                      double eta_c, double eta_m, double prob_m, uint64_t seed, int32_t generation, int32_t row0, int32_t rows, float* out);
+int glass_op_ga_vary_mixed(int32_t device, int32_t pop, int32_t n_real, int32_t n_bits, const float* X, const int32_t* rank, const double* cd, double xl,
+                           double xu, double eta_c, double eta_m, double prob_m, double prob_x, double prob_flip, uint64_t seed, int32_t generation,
+                           int32_t row0, int32_t rows, float* out);
 int glass_op_ga_duplicates(int32_t device, int32_t pop, int32_t n_off, int32_t n_var, const float* X, const float* Xoff, int32_t* flags);
 int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off, int32_t n_obj, int32_t pop_out, int32_t nsga, const float* F,
                         const int32_t* flags, int32_t* chosen, int32_t* rank, double* cd, float* F_out, int32_t* counts, int32_t n_var, const float* X,
