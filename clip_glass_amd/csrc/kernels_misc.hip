@@ -479,8 +479,9 @@ bool launch_torgb(const half_t* x, int B, int H, int W, int C, const float* wrgb
     TORGB_PIX(16) TORGB_PIX(32) TORGB_PIX(64)
 #undef TORGB_PIX
 #define TORGB_CASE(L) case L: launch_torgb_t<L>(x, B, H, W, C, wrgb, bias, sn, sn_stride, smax, smax_stride, yprev, yout, st); break;
-    switch (C / 8) {
-        TORGB_CASE(2) TORGB_CASE(4) TORGB_CASE(8) TORGB_CASE(16) TORGB_CASE(32) TORGB_CASE(64)
+    if (C % 8 != 0) return false;
+    switch (C / 8) {      // (C = 16, 32, 64 left above: lanes-per-pixel instances below 16 lanes would be unreachable)
+        TORGB_CASE(16) TORGB_CASE(32) TORGB_CASE(64)
         default: return false;  // not instantiated (the engine checks its channel widths at creation; the diagnostic ABI reports it)
     }
 #undef TORGB_CASE

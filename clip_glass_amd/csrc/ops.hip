@@ -435,9 +435,10 @@ extern "C" int glass_op_torgb(int32_t device, int32_t B, int32_t H, int32_t C, c
     const auto dx = st.in16(x, (size_t)B * H * H * C);
     const auto dw = st.in32(wrgb, 3 * C), db = st.in32(bias, 3), ds = st.in32(sn, (size_t)B * C), dm = st.in32(smax, B);
     const auto dp = st.in32(yprev, (size_t)B * 3 * (H / 2) * (H / 2));
-    const auto dy = st.raw<float>((size_t)B * 3 * H * H);
+    const auto dy = st.poisoned<float>((size_t)B * 3 * H * H, GUARD_ROWS * H);      // NaN: a pixel no thread stores shows
     TRY(st.run([&] { return accepted(launch_torgb(dx, B, H, H, C, dw, db, ds, C, dm, 1, dp, dy, 0), "toRGB: channel width not instantiated"); }));
-    return st.fetch(yout, dy);
+    TRY(st.fetch(yout, dy));
+    return st.intact(dy, "toRGB: stored behind the output (pixel >= H W of the last sample)");
 }
 
 extern "C" int glass_op_blur(int32_t device, int32_t mode, int32_t B, int32_t H, int32_t C, const float* x, float* out) {
@@ -446,12 +447,13 @@ extern "C" int glass_op_blur(int32_t device, int32_t mode, int32_t B, int32_t H,
     Stage st(device);
     const int Ho = mode != 1 ? H + 1 : H / 2;
     const auto dx = st.in16(x, (size_t)B * H * H * C);
-    const auto dy = st.raw<half_t>((size_t)B * Ho * Ho * C);
+    const auto dy = st.poisoned<half_t>((size_t)B * Ho * Ho * C, GUARD_ROWS * C);
     TRY(st.run([&] {
         if (mode != 1) launch_blur_pad2(dx, B, H, H, C, dy, 0, mode == 2);
         else launch_blur_down(dx, B, H, H, C, dy, 0);
     }));
-    return st.fetch(out, dy);
+    TRY(st.fetch(out, dy));
+    return st.intact(dy, "blur: stored behind the output (row >= Ho or column >= Wo of the last sample)");
 }
 
 extern "C" int glass_op_dblock_down(int32_t device, int32_t B, int32_t R, int32_t Cin, int32_t Cout, const float* h,
@@ -515,9 +517,10 @@ extern "C" int glass_op_fromrgb(int32_t device, int32_t B, int32_t R, int32_t Co
     OPREQ(y && w && bias && out && Cout % 8 == 0, "bad argument");
     Stage st(device);
     const auto dy = st.in32(y, (size_t)B * 3 * R * R), dw = st.in32(w, Cout * 3), db = st.in32(bias, Cout);
-    const auto dout = st.raw<half_t>((size_t)B * R * R * Cout);
+    const auto dout = st.poisoned<half_t>((size_t)B * R * R * Cout, GUARD_ROWS * Cout);
     TRY(st.run([&] { launch_fromrgb(dy, B, R, Cout, dw, db, dout, 0); }));
-    return st.fetch(out, dout);
+    TRY(st.fetch(out, dout));
+    return st.intact(dout, "fromRGB: stored behind the output (pixel >= R R of the last sample)");
 }
 
 extern "C" int glass_op_mbstd(int32_t device, int32_t B, int32_t hw, int32_t C, int32_t Cpad, int32_t batch_size,
@@ -601,9 +604,10 @@ extern "C" int glass_op_noise(int32_t device, int32_t n_mb, int32_t hw, uint32_t
                               uint32_t generation, uint64_t seed, float* out) {
     OPREQ(out, "null argument");
     Stage st(device);
-    const auto d = st.raw<float>((size_t)n_mb * hw);
+    const auto d = st.poisoned<float>((size_t)n_mb * hw, GUARD_ROWS * 4);
     TRY(st.run([&] { launch_noise(d, n_mb, hw, layer, mb0, generation, seed, 0); }));
-    return st.fetch(out, d);
+    TRY(st.fetch(out, d));
+    return st.intact(d, "noise: stored behind the output (element >= hw of the last plane)");
 }
 
 extern "C" int glass_op_gpt2_sample(int32_t device, int32_t rows, int32_t V, const float* logits, float temperature, int32_t top_k,

@@ -97,6 +97,10 @@ int glass_op_gemm_ex(int32_t device, int32_t batch, int32_t M, int32_t N, int32_
                      int32_t cap);
 int glass_op_dense(int32_t device, int32_t P, int32_t K, int32_t N, const float* x, const float* wt /*[K,N]*/,
                    const float* bias, int32_t in_sq, int32_t mode, const float* eps_row, float* out);
+/* The StyleGAN2 glue kernels (kernels_misc.hip): glass_op_torgb, glass_op_blur, glass_op_fromrgb and glass_op_noise stage their output
+ * poisoned (every byte 0xFF: an element no thread stores comes back as NaN) and followed by guard elements; a store behind the output is
+ * an error (GLASS_ERR_ARG, "... stored behind the output").  toRGB has instances for C = 16, 32, 64, 128, 256, 512; another width is
+ * refused (GLASS_ERR_ARG), nothing runs. */
 int glass_op_torgb(int32_t device, int32_t B, int32_t H, int32_t C, const float* x, const float* wrgb /*[3,C] scaled*/,
                    const float* bias, const float* sn, const float* smax, const float* yprev, float* yout);
 int glass_op_blur(int32_t device, int32_t mode /*0: pad2 stride1, 1: pad1 + ::2, 2: pad2 stride1 written as [B,C/32,H+1,H+1,32]*/, int32_t B, int32_t H, int32_t C,
