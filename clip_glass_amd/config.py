@@ -32,7 +32,11 @@ row's — and generation 0 starts at it), `source_text` (what the source shows: 
 the anchor distance is an objective of its own — the Generator then searches a copy of the config with `n_obj` one higher and `algorithm`
 "nsga2"; > 0: added to the similarity objective) and `edit_sigma` (0.1: the spread of generation 0 around the source row; row 0 is the
 source itself) — `edit_image` with the StyleGAN2 and BigGAN configs, `edit_latent` / `anchor_lambda` with the StyleGAN2 configs only; every
-key is refused for GPT2."""
+key is refused for GPT2;
+`algorithm` "cmaes" (instead of the table's "ga": separable CMA-ES, include/glass.h "Device search: sep-CMA-ES" — one objective and
+real-valued rows, so the StyleGAN2 `_nod` configs, with `lpips_lambda` / `anchor_lambda` > 0 where those objectives are on; on the host, or
+on the GPU with `device_search`) and `cma_sigma` (1.0: the initial step size; the initial mean and variances come from 4096 rows of the
+config's own sampling) — refused by name for a config with more than one objective, the BigGAN configs, GPT2 and `--dist`."""
 from .latent import DeepMindBigGANLatentSpace, GPT2LatentSpace, StyleGAN2LatentSpace
 from .models import GPT2, DeepMindBigGAN, StyleGAN2
 from .utils import biggan_denorm, biggan_norm

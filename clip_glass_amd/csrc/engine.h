@@ -290,6 +290,10 @@ struct glass_engine {
         float *X[2] = {nullptr, nullptr}, *Xoff = nullptr, *F = nullptr;   // [pop][n_var] x 3; F [2 pop][n_obj]: population rows, then offspring rows
         int *rank = nullptr, *flags = nullptr, *chosen = nullptr, *counts = nullptr;
         double* cd = nullptr;
+        // sep-CMA-ES (algorithm GLASS_SEARCH_CMAES; include/glass.h "Device search: sep-CMA-ES"): the generation's rows are Xoff and their F the
+        // offspring half of F, so search_evaluate is the GA's; of the buffers above only Xoff, F and counts are allocated
+        bool cma = false;
+        CmaState cs = {};                   // cs.m holds m, d, p_sigma, p_c back to back ([4][n_var])
     } search;
     long long latent_uploads = 0, latent_upload_rows = 0;   // host-to-device latent copies of the pass so far (glass_engine_latent_uploads)
     // ---- image editing (include/glass.h "Image editing"; edit.cpp).  Nothing below is allocated or touched by an engine that has no
@@ -496,6 +500,14 @@ int run_pass(glass_engine* e, const float* latents, int P, int generation, int f
              const float* d_latents = nullptr, float* d_F_dst = nullptr, bool no_wait = false);
 int wait_pass(glass_engine* e, int P);        // the wait no_wait left out: synchronise, the launchers' verdict, the profile
 int alloc_search(glass_engine* e);            // the search's buffers (nothing without glass_engine_set_search)
+int search_ready(glass_engine* e, const char* what, bool need_init);      // the checks in front of every search_* entry point; selects e->cur
+int search_wait(glass_engine* e);             // the wait behind launches made outside a pass
+// sep-CMA-ES (cmaes.cpp), reached through the search_* entry points of search.cpp when the engine's search is one
+int cma_set_search(glass_engine* e, int pop, double xl, double xu, uint64_t seed);
+int alloc_cma(glass_engine* e);
+int cma_vary(glass_engine* e, int generation);
+int cma_survive(glass_engine* e, int generation);
+int cma_step(glass_engine* e, int generation);
 #pragma GCC visibility pop
 
 // ---- image editing (edit.cpp) ----

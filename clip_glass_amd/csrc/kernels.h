@@ -232,6 +232,43 @@ const char* launch_ga_survive(float* F, const int* flags, int n_pop, int n_off, 
 void launch_ga_gather(const float* X, const float* Xoff, const int* chosen, int n_pop, int pop_out, int n_var, float* Xnext, hipStream_t st);
 size_t ga_survive_lds_bytes(int n_rows, int n_obj);
 
+// --- device search: sep-CMA-ES (cmaes.hip; include/glass.h "Device search: sep-CMA-ES") ---
+#define GLASS_SEARCH_DRAW_NORMAL 6u       // index = sampled row, variable = column; z = sqrt(-2 ln u0) cos(2 pi u1)
+#define GLASS_CMA_MIN_POP 4
+#define GLASS_CMA_BLOCK 256               // variables per workgroup of the update: the partition of ||p_sigma||^2, a function of n alone
+struct CmaParams {      // what a launch takes by value: sizes, bounds, seed and the constants of the header's "Setup" (cma_params)
+    int lambda, mu, n;
+    double xl, xu;
+    uint64_t seed;
+    double mu_eff, c_sigma, d_sigma, c_c, c_1, c_mu, chi;
+};
+struct CmaScalars {     // device; every field has one writer: thread 0 of the rank kernel or thread 0 of block 0 of the second update phase
+    double sigma, ps_norm;
+    float best_F;
+    int best_src;       // the row of this generation that became the best seen, -1: none (the best-row copy then leaves best_X alone)
+    int h, finite, updated, skipped, updates;      // updated: this generation had >= mu finite rows; skipped / updates count generations
+};
+struct CmaState {       // device pointers
+    double *m, *d, *ps, *pc;      // [n] each
+    double* w;                    // [mu] recombination weights
+    double *yw, *s2;              // [n]: y_w and sum w y^2 of the generation, from the first update phase to the second
+    double* part;                 // [ceil(n / GLASS_CMA_BLOCK)] partial sums of p_sigma^2
+    CmaScalars* sc;
+    int* order;                   // [lambda] rows by (F, index)
+    float* best_X;                // [n]
+    int* counts;                  // nullable int [2] = {0, non-finite rows of the last rank} (glass_engine_search_read's counts)
+};
+CmaParams cma_params(int lambda, int n, double xl, double xu, uint64_t seed);      // host; the header's constants, in double
+void cma_weights(int lambda, double* w /*[lambda / 2]*/);                           // host; normalised, in double
+inline int cma_blocks(int n) { return (n + GLASS_CMA_BLOCK - 1) / GLASS_CMA_BLOCK; }
+// Every launcher returns the name of the kernel it launched, or nullptr: a shape outside the limits, nothing launched.
+// rows [row0, row0 + rows) of generation `generation` from (m, d, sigma) -> X [lambda][n]
+const char* launch_cma_sample(const CmaState& s, const CmaParams& p, int generation, int row0, int rows, float* X, hipStream_t st);
+// F [lambda] -> order, the finite count, the counters and the best-so-far decision.  One workgroup
+const char* launch_cma_rank(const CmaState& s, const CmaParams& p, const float* F, hipStream_t st);
+// the two update phases (a kernel boundary stands for the grid-wide dependency on ||p_sigma||) and the best-row copy, from the rank just made
+const char* launch_cma_update(const CmaState& s, const CmaParams& p, const float* X, int generation, hipStream_t st);
+
 // --- perceptual objective: LPIPS on VGG16 (lpips.hip); the 3 x 3 convolutions behind the first are gemm_tiled (mode 5, A = 1, S = bias) ---
 #define GLASS_LPIPS_PIXB 256      // pixels of one image a workgroup of the head owns
 // box mean R -> S (R % S == 0, box <= 8) of planar fp32 y [B][3][R][R], then (v - shift_c) / scale_c -> [B][S][S][4] fp16 (channel 3 = 0)

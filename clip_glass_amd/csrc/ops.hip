@@ -1436,3 +1436,104 @@ extern "C" int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off,
     TRY(st.fetch(counts, dcn));
     return gather ? st.fetch(X_out, dXo) : GLASS_OK;
 }
+
+// ---- device search: sep-CMA-ES (cmaes.hip) -----------------------------------------------------------------------------------------
+namespace {
+// the device side of a CMA state for one op: state [4][n] (m, d, p_sigma, p_c), the weights, the scratch and the scalars
+struct CmaStage {
+    CmaState s = {};
+    Buf<double> state, w, scratch, part;
+    Buf<CmaScalars> sc;
+    Buf<int32_t> order, counts;
+    Buf<float> best;
+    CmaStage(Stage& st, int lambda, int n, const double* state_in, const CmaScalars& scalars, const float* best_in) {
+        std::vector<double> wh((size_t)std::max(lambda / 2, 1));
+        cma_weights(lambda, wh.data());
+        state = st.in(state_in, (size_t)4 * n);
+        w = st.in(wh.data(), wh.size());
+        scratch = st.poisoned<double>((size_t)2 * n);
+        part = st.poisoned<double>((size_t)cma_blocks(n));
+        sc = st.in(&scalars, 1);
+        order = st.poisoned<int32_t>((size_t)lambda, 4);
+        counts = st.poisoned<int32_t>(2);
+        best = st.poisoned<float>((size_t)n, 4);
+        if (best_in) st.put(best, 0, best_in, (size_t)n);
+        s.m = state.at(0); s.d = state.at((size_t)n); s.ps = state.at((size_t)2 * n); s.pc = state.at((size_t)3 * n);
+        s.w = w; s.yw = scratch.at(0); s.s2 = scratch.at((size_t)n); s.part = part; s.sc = sc; s.order = order; s.best_X = best; s.counts = counts;
+    }
+};
+}  // namespace
+
+extern "C" int glass_op_cma_sample(int32_t device, int32_t lambda, int32_t n, const double* mean, const double* diag, double sigma, double xl, double xu,
+                                   uint64_t seed, int32_t generation, int32_t row0, int32_t rows, float* X) {
+    OPREQ(mean && diag && X, "null argument");
+    TRY(glass_search_supported(lambda, n, 1, GLASS_SEARCH_CMAES));
+    OPREQ(rows > 0 && row0 >= 0 && row0 + rows <= lambda, "cma_sample: [row0, row0 + rows) must lie inside the lambda rows");
+    std::vector<double> state((size_t)4 * n, 0.0);
+    memcpy(state.data(), mean, (size_t)n * sizeof(double));
+    memcpy(state.data() + n, diag, (size_t)n * sizeof(double));
+    CmaScalars sc = {};
+    sc.sigma = sigma;
+    Stage st(device);
+    CmaStage cs(st, lambda, n, state.data(), sc, nullptr);
+    const auto dX = st.poisoned<float>((size_t)lambda * n, 4);      // every row preloaded from the caller's, and four guard elements behind them
+    st.put(dX, 0, X, (size_t)lambda * n);
+    const CmaParams p = cma_params(lambda, n, xl, xu, seed);
+    TRY(st.run([&] { return accepted(launch_cma_sample(cs.s, p, generation, row0, rows, dX, 0), "cma_sample refused the shape"); }));
+    TRY(st.intact(dX, "cma_sample stored past the last row"));
+    return st.fetch(X, dX);
+}
+
+extern "C" int glass_op_cma_rank(int32_t device, int32_t lambda, const float* F, float best_F, int32_t* order, int32_t* info, float* best_F_out) {
+    OPREQ(F && order && info && best_F_out, "null argument");
+    TRY(glass_search_supported(lambda, 1, 1, GLASS_SEARCH_CMAES));
+    const double zero[4] = {0.0, 1.0, 0.0, 0.0};
+    CmaScalars sc = {};
+    sc.sigma = 1.0;
+    sc.best_F = best_F;
+    sc.best_src = -1;
+    Stage st(device);
+    CmaStage cs(st, lambda, 1, zero, sc, nullptr);
+    const auto dF = st.in32(F, (size_t)lambda);
+    const CmaParams p = cma_params(lambda, 1, -1.0, 1.0, 0);
+    TRY(st.run([&] { return accepted(launch_cma_rank(cs.s, p, dF, 0), "cma_rank refused the shape"); }));
+    TRY(st.intact(cs.order, "cma_rank stored past slot lambda"));
+    TRY(st.fetch(order, cs.order));
+    TRY(st.fetch(&sc, cs.sc));
+    int32_t counts[2];
+    TRY(st.fetch(counts, cs.counts));
+    info[0] = sc.finite; info[1] = sc.updated; info[2] = sc.best_src; info[3] = sc.skipped; info[4] = counts[1];
+    *best_F_out = sc.best_F;
+    return GLASS_OK;
+}
+
+extern "C" int glass_op_cma_update(int32_t device, int32_t lambda, int32_t n, const float* X, const float* F, double* state, double* scalars_d,
+                                   int32_t* scalars_i, double xl, double xu, int32_t generation, float* best_X, float* best_F, int32_t* order) {
+    OPREQ(X && F && state && scalars_d && scalars_i && best_X && best_F && order, "null argument");
+    TRY(glass_search_supported(lambda, n, 1, GLASS_SEARCH_CMAES));
+    OPREQ(generation >= 0, "cma_update: a generation is 0, 1, ...");
+    CmaScalars sc = {};
+    sc.sigma = scalars_d[0]; sc.ps_norm = scalars_d[1];
+    sc.h = scalars_i[0]; sc.finite = scalars_i[1]; sc.updated = scalars_i[2]; sc.skipped = scalars_i[3]; sc.updates = scalars_i[4];
+    sc.best_F = *best_F;
+    sc.best_src = -1;
+    Stage st(device);
+    CmaStage cs(st, lambda, n, state, sc, best_X);
+    const auto dX = st.in32(X, (size_t)lambda * n), dF = st.in32(F, (size_t)lambda);
+    const CmaParams p = cma_params(lambda, n, xl, xu, 0);
+    TRY(st.run([&]() -> int {
+        OPREQ(launch_cma_rank(cs.s, p, dF, 0), "cma_rank refused the shape");
+        OPREQ(launch_cma_update(cs.s, p, dX, generation, 0), "cma_update refused the shape");
+        return GLASS_OK;
+    }));
+    TRY(st.intact(cs.order, "cma_rank stored past slot lambda"));
+    TRY(st.intact(cs.best, "cma_best stored past variable n"));
+    TRY(st.fetch(state, cs.state));
+    TRY(st.fetch(order, cs.order));
+    TRY(st.fetch(best_X, cs.best));
+    TRY(st.fetch(&sc, cs.sc));
+    scalars_d[0] = sc.sigma; scalars_d[1] = sc.ps_norm;
+    scalars_i[0] = sc.h; scalars_i[1] = sc.finite; scalars_i[2] = sc.updated; scalars_i[3] = sc.skipped; scalars_i[4] = sc.updates; scalars_i[5] = sc.best_src;
+    *best_F = sc.best_F;
+    return GLASS_OK;
+}

@@ -8,7 +8,17 @@
 #include "engine.h"
 
 extern "C" int glass_search_supported(int32_t pop, int32_t n_var, int32_t n_obj, int32_t algorithm) {
-    REQUIRE(algorithm == GLASS_SEARCH_GA || algorithm == GLASS_SEARCH_NSGA2, GLASS_ERR_ARG, "device search: algorithm must be 0 (ga) or 1 (nsga2)");
+    REQUIRE(algorithm == GLASS_SEARCH_GA || algorithm == GLASS_SEARCH_NSGA2 || algorithm == GLASS_SEARCH_CMAES, GLASS_ERR_ARG,
+            "device search: algorithm must be 0 (ga), 1 (nsga2) or 2 (cmaes)");
+    if (algorithm == GLASS_SEARCH_CMAES) {
+        REQUIRE(n_obj == 1, GLASS_ERR_ARG,
+                "device search: cmaes minimises one objective and this search has " + std::to_string(n_obj) + " (use nsga2, or fold the others into one)");
+        REQUIRE(pop >= GLASS_CMA_MIN_POP && pop <= GLASS_SEARCH_MAX_POP, GLASS_ERR_ARG,
+                "device search: cmaes takes pop in [" + std::to_string(GLASS_CMA_MIN_POP) + ", " + std::to_string(GLASS_SEARCH_MAX_POP) +
+                    "] (mu = pop / 2 >= 2 rows recombine; one workgroup ranks the rows), got " + std::to_string(pop));
+        REQUIRE(n_var >= 1 && (long long)n_var * pop < (1LL << 31), GLASS_ERR_ARG, "device search: n_var must be positive with pop * n_var below 2^31");
+        return GLASS_OK;
+    }
     REQUIRE(pop >= 2 && pop <= GLASS_SEARCH_MAX_POP, GLASS_ERR_ARG,
             "device search: pop must be in [2, " + std::to_string(GLASS_SEARCH_MAX_POP) + "] (survival ranks 2 pop merged rows in one workgroup), got " +
                 std::to_string(pop));
@@ -44,6 +54,7 @@ extern "C" int glass_engine_set_search(glass_engine* e, int32_t algorithm, int32
                                        double prob_m, uint64_t seed) {
     REQUIRE(e, GLASS_ERR_ARG, "null engine");
     REQUIRE(!e->finalized, GLASS_ERR_STATE, "set_search: the engine is finalized (its buffers are sized in finalize: call it before)");
+    if (algorithm == GLASS_SEARCH_CMAES) return cma_set_search(e, pop, xl, xu, seed);      // (eta_c, eta_m and prob_m belong to the GA's operators)
     REQUIRE(e->cfg.generator != GLASS_GEN_BIGGAN_DEEP, GLASS_ERR_STATE,
             "set_search: this setter varies real-valued rows; a BigGAN row holds boolean class bits (HUX / bit-flip): use set_search_mixed");
     REQUIRE(e->n_lat > 0, GLASS_ERR_STATE,
@@ -116,6 +127,7 @@ int alloc_search(glass_engine* e) {
     if (!s.g.pop) return GLASS_OK;
     const int pop = s.g.pop, M = e->cfg.n_obj;
     s.n_var = (int)latent_row_floats(e);
+    if (s.cma) return alloc_cma(e);
     if (int rc = s.n_real ? glass_search_mixed_supported(pop, s.n_real, s.n_var - s.n_real, M, s.nsga) : glass_search_supported(pop, s.n_var, M, s.nsga))
         return rc;
     int rc;
@@ -135,16 +147,18 @@ int alloc_search(glass_engine* e) {
     return GLASS_OK;
 }
 
-namespace {
 int search_ready(glass_engine* e, const char* what, bool need_init) {
     REQUIRE(e, GLASS_ERR_ARG, "null engine");
     REQUIRE(e->finalized, GLASS_ERR_STATE, std::string(what) + ": finalize() first");
     REQUIRE(e->search.g.pop > 0, GLASS_ERR_STATE, std::string(what) + ": the device search is off (glass_engine_set_search before finalize)");
+    if (need_init && e->search.cma)
+        REQUIRE(e->search.ready, GLASS_ERR_STATE, std::string(what) + ": search_init_cma() first (there is no distribution on the device)");
     if (need_init) REQUIRE(e->search.ready, GLASS_ERR_STATE, std::string(what) + ": search_init() first (there is no population on the device)");
     GLASS_HIP(hipSetDevice(e->cfg.device));
     e->cur = e->stream;
     return GLASS_OK;
 }
+namespace {
 // the launches of the three phases, on e->cur; nothing here waits
 void launch_vary(glass_engine* e, int generation) {
     glass_engine::Search& s = e->search;
@@ -186,6 +200,7 @@ void launch_survive(glass_engine* e, int n_off) {
     launch_ga_gather(s.X[s.cur], s.Xoff, s.chosen, pop, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
     s.cur ^= 1;
 }
+}  // namespace
 // the wait behind launches made outside a pass
 int search_wait(glass_engine* e) {
     GLASS_HIP(hipStreamSynchronize(e->cur));
@@ -199,6 +214,7 @@ int search_wait(glass_engine* e) {
     }
     return GLASS_OK;
 }
+namespace {
 int check_rows(glass_engine* e, const char* what, int generation, int first_row, int rows) {
     const glass_engine::Search& s = e->search;
     REQUIRE(s.varied_gen == generation, GLASS_ERR_STATE,
@@ -212,6 +228,8 @@ int check_rows(glass_engine* e, const char* what, int generation, int first_row,
 extern "C" int glass_engine_search_init(glass_engine* e, const float* X0) {
     if (int rc = search_ready(e, "search_init", false)) return rc;
     REQUIRE(X0, GLASS_ERR_ARG, "search_init: null population");
+    REQUIRE(!e->search.cma, GLASS_ERR_STATE,
+            "search_init: a cmaes search keeps a distribution, not a population: search_init_cma(mean, diag, sigma)");
     glass_engine::Search& s = e->search;
     const int pop = s.g.pop;
     s.ready = false;
@@ -239,6 +257,7 @@ extern "C" int glass_engine_search_init(glass_engine* e, const float* X0) {
 
 extern "C" int glass_engine_search_vary(glass_engine* e, int32_t generation) {
     if (int rc = search_ready(e, "search_vary", true)) return rc;
+    if (e->search.cma) return cma_vary(e, generation);
     e->launch_error.clear();
     launch_vary(e, generation);
     return search_wait(e);
@@ -255,6 +274,7 @@ extern "C" int glass_engine_search_evaluate(glass_engine* e, int32_t generation,
 extern "C" int glass_engine_search_survive(glass_engine* e, int32_t generation) {
     if (int rc = search_ready(e, "search_survive", true)) return rc;
     REQUIRE(e->search.varied_gen == generation, GLASS_ERR_STATE, "search_survive: search_vary and search_evaluate of this generation first");
+    if (e->search.cma) return cma_survive(e, generation);
     e->launch_error.clear();
     launch_survive(e, e->search.g.pop);
     e->search.varied_gen = -1;      // the offspring are spent: the next survival needs a new search_vary
@@ -263,6 +283,7 @@ extern "C" int glass_engine_search_survive(glass_engine* e, int32_t generation) 
 
 extern "C" int glass_engine_search_step(glass_engine* e, int32_t generation) {
     if (int rc = search_ready(e, "search_step", true)) return rc;
+    if (e->search.cma) return cma_step(e, generation);
     glass_engine::Search& s = e->search;
     const int pop = s.g.pop;
     e->launch_error.clear();
@@ -279,6 +300,8 @@ extern "C" int glass_engine_search_read(glass_engine* e, float* pop_X, float* po
                                         int32_t* flags, int32_t* counts) {
     if (int rc = search_ready(e, "search_read", true)) return rc;
     const glass_engine::Search& s = e->search;
+    REQUIRE(!s.cma || !(pop_X || pop_F || rank || cd || flags), GLASS_ERR_STATE,
+            "search_read: a cmaes search has no population, ranks, distances or flags: its rows are off_X / off_F, its state search_read_cma");
     const size_t pop = (size_t)s.g.pop, xb = pop * s.n_var * sizeof(float), fb = pop * e->cfg.n_obj * sizeof(float);
     GLASS_HIP(hipStreamSynchronize(e->stream));
     if (pop_X) GLASS_HIP(hipMemcpy(pop_X, s.X[s.cur], xb, hipMemcpyDeviceToHost));

@@ -138,6 +138,10 @@ def load_library(path=None):
         lib.glass_search_mixed_supported.argtypes = [C.c_int32] * 5
         lib.glass_engine_set_search_mixed.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_double] * 7 + [C.c_uint64]
         lib.glass_engine_set_search_operators_mixed.argtypes = [C.c_void_p] + [C.c_double] * 7 + [C.c_uint64]
+    if hasattr(lib, "glass_engine_search_init_cma"):    # (absent from older A/B builds loaded through GLASS_LIB)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        lib.glass_engine_search_init_cma.argtypes = [C.c_void_p, dp, dp, C.c_double]
+        lib.glass_engine_search_read_cma.argtypes = [C.c_void_p, dp, dp, dp, dp, dp, ip, fp, fp]
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -293,12 +297,13 @@ def host_clip_view_boxes(seed, generation, views, gen_res, min_permille, flip, f
     return out
 
 
-SEARCH_ALGORITHMS = {"ga": 0, "nsga2": 1}     # GLASS_SEARCH_GA / _NSGA2
+SEARCH_ALGORITHMS = {"ga": 0, "nsga2": 1, "cmaes": 2}     # GLASS_SEARCH_GA / _NSGA2 / _CMAES
 SEARCH_MAX_POP = 1024
+CMA_MIN_POP = 4
 
 
 def search_supported(pop, n_var, n_obj, algorithm):
-    """(ok, message) for a device search of `pop` rows of n_var variables with n_obj objectives under "ga" / "nsga2": the library's own rule
+    """(ok, message) for a device search of `pop` rows of n_var variables with n_obj objectives under "ga" / "nsga2" / "cmaes": the library's own rule
     (glass_search_supported), the one glass_engine_set_search and finalize apply.  Host only."""
     if algorithm not in SEARCH_ALGORITHMS:
         return False, "device search: unknown algorithm %r (expected one of %s)" % (algorithm, ", ".join(SEARCH_ALGORITHMS))
@@ -600,12 +605,14 @@ class Engine:
 
     # --- device search (include/glass.h "Device search") ------------------------
     def set_search(self, algorithm, pop, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, seed=1):
-        """Between construction and finalize(): turn the device search on for `pop` rows under "ga" / "nsga2" with scalar bounds xl / xu."""
+        """Between construction and finalize(): turn the device search on for `pop` rows under "ga" / "nsga2" / "cmaes" (sep-CMA-ES: one
+        objective; eta_c, eta_m and prob_m are ignored) with scalar bounds xl / xu."""
         if algorithm not in SEARCH_ALGORITHMS:
             raise ValueError("unknown search algorithm %r: expected one of %s" % (algorithm, ", ".join(SEARCH_ALGORITHMS)))
         _check(self.lib, self.lib.glass_engine_set_search(self._h, SEARCH_ALGORITHMS[algorithm], int(pop), float(xl), float(xu), float(eta_c),
                                                            float(eta_m), float(prob_m), int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.search_pop = int(pop)
+        self.search_algorithm = algorithm
 
     def set_search_operators(self, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, seed=1):
         """Any time after set_search: the values that size nothing (the bounds of a w / w+ search are known only after finalize())."""
@@ -635,6 +642,31 @@ class Engine:
         if pop is not None and z.shape[0] != pop:
             raise ValueError("search_init: the initial population must have exactly pop = %d rows, got %d" % (pop, z.shape[0]))
         _check(self.lib, self.lib.glass_engine_search_init(self._h, _fp(z)))
+
+    def search_init_cma(self, mean, diag=None, sigma=1.0):
+        """A "cmaes" search: the distribution of generation 0 — mean [floats_per_row], diag (None: ones) and the step sigma, float64."""
+        nv = self.latent_row()[0]
+        m = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        d = None if diag is None else np.ascontiguousarray(diag, dtype=np.float64).reshape(-1)
+        if m.size != nv or (d is not None and d.size != nv):
+            raise ValueError("search_init_cma: mean and diag must hold %d values (a row of latent space %r)" % (nv, self.latent_space))
+        dp = C.POINTER(C.c_double)
+        _check(self.lib, self.lib.glass_engine_search_init_cma(self._h, m.ctypes.data_as(dp), None if d is None else d.ctypes.data_as(dp),
+                                                                float(sigma)))
+
+    def search_read_cma(self):
+        """The state of a "cmaes" search: dict(mean, diag, p_sigma, p_c float64 [floats_per_row]; sigma, ps_norm; h, finite, updated, skipped,
+        updates; best_X float32 [floats_per_row], best_F)."""
+        nv = self.latent_row()[0]
+        out = {k: np.empty((nv,), np.float64) for k in ("mean", "diag", "p_sigma", "p_c")}
+        sd, si = np.empty((2,), np.float64), np.empty((5,), np.int32)
+        best_X, best_F = np.empty((nv,), np.float32), np.empty((1,), np.float32)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        _check(self.lib, self.lib.glass_engine_search_read_cma(self._h, *[out[k].ctypes.data_as(dp) for k in ("mean", "diag", "p_sigma", "p_c")],
+                                                                sd.ctypes.data_as(dp), si.ctypes.data_as(ip), _fp(best_X), _fp(best_F)))
+        out.update(sigma=float(sd[0]), ps_norm=float(sd[1]), best_X=best_X, best_F=float(best_F[0]))
+        out.update(zip(("h", "finite", "updated", "skipped", "updates"), (int(v) for v in si)))
+        return out
 
     def search_vary(self, generation):
         _check(self.lib, self.lib.glass_engine_search_vary(self._h, int(generation)))

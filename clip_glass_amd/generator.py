@@ -542,8 +542,40 @@ def clip_preprocess(path_or_image, n_px=224):
     return (a - mean) / std
 
 
+# ---- search rule (opt-in, include/glass.h "Device search: sep-CMA-ES"): config.algorithm "cmaes" next to the reference's "ga" / "nsga2" ----
+def search_options(config):
+    """Refuses, by name and before any weight is looked for, what config.algorithm = "cmaes" cannot search — more than one objective, the
+    BigGAN configs' class bits, GPT2's tokens, --dist — each with what to use instead; checks config.cma_sigma.  Any other algorithm: nothing."""
+    if getattr(config, "algorithm", None) != "cmaes":
+        return None
+    name = str(getattr(config, "config", ""))
+    if getattr(config, "task", None) == "img2txt":
+        raise ValueError("algorithm cmaes samples real-valued rows; the GPT2 config searches integer tokens: use ga")
+    if name.startswith("DeepMindBigGAN") or getattr(config, "num_classes", None):
+        raise ValueError("algorithm cmaes samples real-valued rows; a BigGAN row is [z | boolean class bits] (HUX / bit-flip): use ga")
+    if getattr(config, "dist", False):
+        raise ValueError("algorithm cmaes: more than one rank (--dist) is not wired to it: run one rank, or ga / nsga2")
+    n_obj = int((getattr(config, "problem_args", None) or {}).get("n_obj", 1))
+    if n_obj > 1:
+        raise ValueError("algorithm cmaes minimises one objective and config %s has %d (the discriminator's hinge is one of its own): use a _nod "
+                         "config, or nsga2" % (name, n_obj))
+    if getattr(config, "lpips_target", None) is not None and not float(getattr(config, "lpips_lambda", None) or 0.0) > 0.0:
+        raise ValueError("algorithm cmaes minimises one objective; lpips_lambda = 0 makes the LPIPS distance a column of its own: fold it in "
+                         "with lpips_lambda > 0, or use nsga2")
+    if getattr(config, "edit_latent", None) is not None and not float(getattr(config, "anchor_lambda", None) or 0.0) > 0.0:
+        raise ValueError("algorithm cmaes minimises one objective; anchor_lambda = 0 makes the latent anchor a column of its own: fold it in "
+                         "with anchor_lambda > 0, or use nsga2")
+    if getattr(config, "prompt_mode", None) == "pareto":
+        raise ValueError("algorithm cmaes minimises one objective; a pareto prompt set has one per prompt: use prompt_mode sum, or nsga2")
+    sigma = getattr(config, "cma_sigma", None)
+    if sigma is not None and not (np.isfinite(float(sigma)) and float(sigma) > 0.0):
+        raise ValueError("cma_sigma must be finite and positive, got %r" % (sigma,))
+    return dict(sigma=1.0 if sigma is None else float(sigma))
+
+
 class Generator:
     def __init__(self, config, dist=None):
+        search_options(config)      # algorithm "cmaes": what it cannot search is refused here, before any weight is looked for
         # perceptual objective (opt-in): refused for the GPT2 config here, before any weight is looked for; with lambda = 0 the search gets
         # one more objective — on a copy of the config, which callers read back as `generator.config`
         self.lpips = lpips_options(config)
@@ -599,6 +631,8 @@ class Generator:
         self.device_search = bool(getattr(config, "device_search", False))
         if self.device_search and config.task == "img2txt":
             raise ValueError("device_search: the GPT2 config searches integer token rows (int_sbx / int_pm): it keeps the host search")
+        if sharded and getattr(config, "algorithm", None) == "cmaes":
+            raise ValueError("algorithm cmaes: more than one rank (--dist) is not wired to it: run one rank, or ga / nsga2")
         if self.device_search and sharded:
             raise ValueError("device_search: more than one rank (--dist) is not wired to the device search yet: run one rank, or the host search")
         if config.task == "img2txt":                                        # generator.py:25-27, 52-59

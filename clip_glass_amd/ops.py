@@ -98,6 +98,9 @@ SIGNATURES = {
     "glass_op_ga_vary_mixed": [i32, i32, i32, i32, fp, ip, dp, f64, f64, f64, f64, f64, f64, f64, u64, i32, i32, i32, fp],
     "glass_op_ga_duplicates": [i32, i32, i32, i32, fp, fp, ip],
     "glass_op_ga_survive": [i32, i32, i32, i32, i32, i32, fp, ip, ip, ip, dp, fp, ip, i32, fp, fp, fp],
+    "glass_op_cma_sample": [i32, i32, i32, dp, dp, f64, f64, f64, u64, i32, i32, i32, fp],
+    "glass_op_cma_rank": [i32, i32, fp, f32, ip, ip, fp],
+    "glass_op_cma_update": [i32, i32, i32, fp, fp, dp, dp, ip, f64, f64, i32, fp, fp, ip],
     "glass_op_mfma_probe": [i32, fp, fp, fp],
     "glass_host_pack_conv": [fp, i32, i32, i32, i32, fp],
     "glass_host_resize_taps": [i32, i32, i32, ip, ip, fp, i32],
@@ -1076,4 +1079,49 @@ def ga_survive(F, n_pop, pop_out, nsga=True, flags=None, X=None, device=0):
                                         out["chosen"].ctypes.data_as(ip), out["rank"].ctypes.data_as(ip), out["cd"].ctypes.data_as(dp),
                                         _fp(out["F"]), out["counts"].ctypes.data_as(ip), nv, None if Xp is None else _fp(Xp),
                                         None if Xo is None or not n_off else _fp(Xo), None if Xout is None else _fp(Xout)))
+    return out
+
+
+# ---- device search: sep-CMA-ES (csrc/cmaes.hip; include/glass.h "Device search: sep-CMA-ES") ---------------------------------------
+def cma_sample(mean, diag, sigma, lam, xl, xu, seed=1, generation=0, row0=0, rows=None, X=None, device=0):
+    """Rows [row0, row0 + rows) of the generation's lam samples from (mean, diag float64 [n], sigma) -> X float32 [lam, n]; the other rows
+    come back as they went in (X: the caller's rows, default NaN)."""
+    lib = _lib()
+    m = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+    d = np.ascontiguousarray(diag, dtype=np.float64).reshape(-1)
+    n = m.size
+    rows = lam - row0 if rows is None else rows
+    out = np.full((lam, n), np.nan, np.float32) if X is None else _f32(X).copy()
+    _check(lib, lib.glass_op_cma_sample(device, int(lam), n, m.ctypes.data_as(dp), d.ctypes.data_as(dp), float(sigma), float(xl), float(xu),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation), int(row0), int(rows), _fp(out)))
+    return out
+
+
+def cma_rank(F, best_F=np.inf, device=0):
+    """F float32 [lam] -> dict(order int32 [lam], finite, updated, best_src, skipped, nonfinite, best_F)."""
+    lib = _lib()
+    F = _f32(F).reshape(-1)
+    order, info, best = np.empty((F.size,), np.int32), np.empty((5,), np.int32), np.empty((1,), np.float32)
+    _check(lib, lib.glass_op_cma_rank(device, F.size, _fp(F), float(best_F), order.ctypes.data_as(ip), info.ctypes.data_as(ip), _fp(best)))
+    return dict(order=order, finite=int(info[0]), updated=int(info[1]), best_src=int(info[2]), skipped=int(info[3]), nonfinite=int(info[4]),
+                best_F=float(best[0]))
+
+
+def cma_update(X, F, state, xl, xu, generation, device=0):
+    """Rank + update of one generation.  X float32 [lam, n], F float32 [lam]; state: dict(m, d, ps, pc float64 [n]; sigma, ps_norm; h, finite,
+    updated, skipped, updates; best_X float32 [n], best_F) -> the same dict after the generation, plus order int32 [lam] and best_src."""
+    lib = _lib()
+    X, F = _f32(X), _f32(F).reshape(-1)
+    lam, n = X.shape
+    st = np.ascontiguousarray(np.concatenate([np.asarray(state[k], np.float64).reshape(-1) for k in ("m", "d", "ps", "pc")]))
+    sd = np.array([state["sigma"], state.get("ps_norm", 0.0)], np.float64)
+    si = np.array([state.get(k, 0) for k in ("h", "finite", "updated", "skipped", "updates")] + [-1], np.int32)
+    best_X = _f32(state["best_X"]).reshape(-1).copy()
+    best_F = np.array([state["best_F"]], np.float32)
+    order = np.empty((lam,), np.int32)
+    _check(lib, lib.glass_op_cma_update(device, lam, n, _fp(X), _fp(F), st.ctypes.data_as(dp), sd.ctypes.data_as(dp), si.ctypes.data_as(ip),
+                                        float(xl), float(xu), int(generation), _fp(best_X), _fp(best_F), order.ctypes.data_as(ip)))
+    out = dict(zip(("m", "d", "ps", "pc"), st.reshape(4, n)))
+    out.update(sigma=float(sd[0]), ps_norm=float(sd[1]), best_X=best_X, best_F=float(best_F[0]), order=order, best_src=int(si[5]))
+    out.update(zip(("h", "finite", "updated", "skipped", "updates"), (int(v) for v in si[:5])))
     return out

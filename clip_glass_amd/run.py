@@ -17,7 +17,7 @@ from .config import get_config
 from .engine import LATENT_SPACES
 from .engine import PROMPT_MODES
 from .generator import (CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, edit_options, latent_options, lpips_options, parse_weighted,
-                        prompt_options)
+                        prompt_options, search_options)
 from .operators import get_operators
 from .problem import GenerationProblem
 from . import search
@@ -98,6 +98,13 @@ def build_parser():
                    help="StyleGAN2 and BigGAN configs, one rank: keep the population on the GPU and run selection, crossover, mutation (on a "
                         "BigGAN row: SBX / polynomial mutation on z, half-uniform crossover / bit-flip on the class bits), duplicate flags and "
                         "survival there between the passes (off by default: the host search of search.py; refused for GPT2 and with --dist)")
+    p.add_argument("--algorithm", type=str, default=None, choices=["ga", "nsga2", "cmaes"],
+                   help="the search rule (default: the config's own — nsga2 with the discriminator, ga without).  cmaes: separable CMA-ES, one "
+                        "objective and real-valued rows (the StyleGAN2 _nod configs, in z, w or w+; an LPIPS / anchor distance folded in with "
+                        "lambda > 0); with --device-search its generation step runs on the GPU.  Off by default — the reference has GA / NSGA-II")
+    p.add_argument("--cma-sigma", type=float, default=None,
+                   help="with --algorithm cmaes: the initial step size (default 1: in z, generation 0 is then drawn from the reference's own "
+                        "N(0, 1); the mean and per-variable variances come from 4096 rows of the config's own sampling)")
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--dist", action="store_true",
                    help="multi-GPU: run under `torchrun --nproc-per-node N -m clip_glass_amd.run --dist ...` (one process per GPU, "
@@ -161,7 +168,7 @@ def main(argv=None, extra_config=None):
     for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "clip_views", "clip_view_min", "clip_view_flip",
               "clip_view_fixed", "latent_space", "truncation_psi", "truncation_cutoff", "lpips_target", "lpips_size", "lpips_lambda", "lpips_weights",
               "bpe_path", "pop_size", "stochastic", "target_weight", "prompt_mode", "device_search", "edit_image", "edit_latent", "source_text",
-              "anchor_lambda", "edit_sigma"):
+              "anchor_lambda", "edit_sigma", "algorithm", "cma_sigma"):
         if k in over:
             setattr(config, k, over[k])
     if "prompt" in over or "image_prompt" in over:
@@ -172,6 +179,7 @@ def main(argv=None, extra_config=None):
     lpips_options(config)       # ... and so is the perceptual objective on the GPT2 config
     prompt_options(config)      # ... and a prompt set there, or one the engine would refuse
     edit_options(config)        # ... and image editing there, or its anchor on a BigGAN config
+    search_options(config)      # ... and what --algorithm cmaes cannot search (several objectives, class bits, tokens, --dist)
     state = dict(iteration=0)
     dist, rank0 = None, True
     if getattr(config, "dist", False):
@@ -209,7 +217,8 @@ def main(argv=None, extra_config=None):
     # (same seed on every rank => identical GA state everywhere: no broadcast of the population is needed)
     res = search.minimize(problem, config.algorithm, config.pop_size, config.generations, operators["sampling"],
                           seed=config.seed, callback=save_callback, verbose=rank0, mask=operators.get("mask"),
-                          device=bool(getattr(config, "device_search", False)))
+                          device=bool(getattr(config, "device_search", False)),
+                          **(dict(cma_sigma=getattr(config, "cma_sigma", None)) if config.algorithm == "cmaes" else {}))
     if not rank0:
         return res
     with open(os.path.join(config.tmp_folder, "genetic_result"), "wb") as f:   # run.py:79-84

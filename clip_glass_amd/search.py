@@ -270,16 +270,214 @@ def _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callba
     return _result(r["X"].astype(float), r["F"].astype(float), nsga)
 
 
+# ----------------------------- separable CMA-ES --------------------------------------------
+# include/glass.h "Device search: sep-CMA-ES" is the rule; this is its float64 host form, and csrc/cmaes.hip its device form.
+CMA_MIN_POP, CMA_BLOCK, CMA_INIT_ROWS, DEFAULT_CMA_SIGMA = 4, 256, 4096, 1.0
+
+
+def cma_constants(lam, n):
+    """The weights and constants of the header's "Setup" for lam rows of n variables."""
+    mu = lam // 2
+    w = np.log(mu + 0.5) - np.log(np.arange(1, mu + 1, dtype=float))
+    w = w / w.sum()
+    me = 1.0 / (w * w).sum()
+    c_sigma = (me + 2.0) / (n + me + 5.0)
+    d_sigma = 1.0 + 2.0 * max(0.0, np.sqrt((me - 1.0) / (n + 1.0)) - 1.0) + c_sigma
+    c_c = (4.0 + me / n) / (n + 4.0 + 2.0 * me / n)
+    c_1 = 2.0 / ((n + 1.3) ** 2 + me)
+    c_mu = min(1.0 - c_1, 2.0 * (me - 2.0 + 1.0 / me) / ((n + 2.0) ** 2 + me))
+    c_1 = min(1.0, c_1 * (n + 2.0) / 3.0)
+    c_mu = min(1.0 - c_1, c_mu * (n + 2.0) / 3.0)
+    chi = np.sqrt(float(n)) * (1.0 - 1.0 / (4.0 * n) + 1.0 / (21.0 * n * n))
+    return dict(mu=mu, w=w, mu_eff=me, c_sigma=c_sigma, d_sigma=d_sigma, c_c=c_c, c_1=c_1, c_mu=c_mu, chi=chi)
+
+
+def cma_rank(F):
+    """(order, finite): the rows by (F, index) — -0.0 ties 0.0, a non-finite F goes last by index — and how many are finite."""
+    F = np.asarray(F, float).reshape(-1) + 0.0
+    fin = np.nonzero(np.isfinite(F))[0]
+    return np.concatenate([fin[np.argsort(F[fin], kind="stable")], np.nonzero(~np.isfinite(F))[0]]), fin.size
+
+
+class CMAState:
+    """m, d, p_sigma, p_c float64 [n], sigma, and the best row seen with its F; `skipped` counts generations with fewer than mu finite rows."""
+
+    def __init__(self, mean, diag, sigma):
+        self.m, self.d = np.array(mean, dtype=float), np.array(diag, dtype=float)
+        self.ps, self.pc = np.zeros_like(self.m), np.zeros_like(self.m)
+        self.sigma, self.ps_norm, self.h, self.skipped, self.updates = float(sigma), 0.0, 0, 0, 0
+        self.best_X, self.best_F = np.zeros(self.m.size, np.float32), np.inf
+
+
+def cma_sample(state, lam, xl, xu, seed, generation):
+    """The generation's rows, float32 [lam, n]: clip(m + (sigma sqrt(d)) z) in double, rounded once."""
+    from .synth import search_normals
+    z = search_normals(seed, generation, np.arange(lam)[:, None], np.arange(state.m.size)[None, :])
+    return np.minimum(np.maximum(state.m + (state.sigma * np.sqrt(state.d)) * z, xl), xu).astype(np.float32)
+
+
+def cma_update(state, c, X, F, xl, xu, generation):
+    """Rank and update from the rows as they were evaluated (X float32 [lam, n], F [lam]); False: fewer than mu finite rows, nothing moved."""
+    order, finite = cma_rank(F)
+    if finite < c["mu"]:
+        state.skipped += 1
+        return False
+    state.updates += 1
+    if F[order[0]] < state.best_F:
+        state.best_X, state.best_F = X[order[0]].copy(), float(F[order[0]])
+    n, w = state.m.size, c["w"]
+    yw, s2 = np.zeros(n), np.zeros(n)
+    for i in range(c["mu"]):                     # the order i = 1 .. mu, one writer per variable
+        y = (X[order[i]].astype(float) - state.m) / state.sigma
+        yw = yw + w[i] * y
+        s2 = s2 + w[i] * (y * y)
+    state.m = state.m + state.sigma * yw
+    state.ps = (1.0 - c["c_sigma"]) * state.ps + np.sqrt(c["c_sigma"] * (2.0 - c["c_sigma"]) * c["mu_eff"]) * yw / np.sqrt(state.d)
+    sq, acc = state.ps * state.ps, 0.0
+    for b in range(0, n, CMA_BLOCK):             # parts of 256 variables in index order (cumsum adds sequentially), then the parts in order
+        acc = acc + np.cumsum(sq[b:b + CMA_BLOCK])[-1]
+    norm = np.sqrt(acc)
+    h = 1.0 if norm / np.sqrt(1.0 - np.power(1.0 - c["c_sigma"], 2.0 * (generation + 1.0))) < (1.4 + 2.0 / (n + 1.0)) * c["chi"] else 0.0
+    state.pc = (1.0 - c["c_c"]) * state.pc + (h * np.sqrt(c["c_c"] * (2.0 - c["c_c"]) * c["mu_eff"])) * yw
+    state.d = (((1.0 - c["c_1"]) - c["c_mu"]) * state.d + c["c_1"] * (state.pc * state.pc + (((1.0 - h) * c["c_c"]) * (2.0 - c["c_c"])) * state.d)
+               + c["c_mu"] * s2)
+    sigma = state.sigma * np.exp(min(1.0, (c["c_sigma"] / c["d_sigma"]) * (norm / c["chi"] - 1.0)))
+    state.sigma, state.ps_norm, state.h = float(min(max(sigma, 1e-10), xu - xl)), float(norm), int(h)
+    return True
+
+
+def _cma_checks(problem, pop_size, mask):
+    """What "cmaes" refuses, by name, on the host and on the device; returns the scalar bounds."""
+    if int(problem.n_obj) != 1:
+        raise ValueError("cmaes: minimises one objective and this problem has n_obj = %d: use nsga2 (or a _nod config, or the LPIPS / anchor "
+                         "distance folded in with lambda > 0)" % problem.n_obj)
+    if mask is not None and (np.asarray(list(mask)) != "real").any():
+        others = sorted(set(np.asarray(list(mask))[np.asarray(list(mask)) != "real"].tolist()))
+        raise ValueError("cmaes: samples real-valued rows and this mask has %s columns (BigGAN's class bits, GPT2's tokens): use ga" % " / ".join(others))
+    if pop_size < CMA_MIN_POP:
+        raise ValueError("cmaes: pop_size %d is under %d (mu = pop / 2 >= 2 rows recombine)" % (pop_size, CMA_MIN_POP))
+    xl, xu = np.unique(np.asarray(problem.xl, float)), np.unique(np.asarray(problem.xu, float))
+    if xl.size != 1 or xu.size != 1:
+        raise ValueError("cmaes: the bounds must be scalar (one xl and one xu for every variable), as the reference's are")
+    return float(xl[0]), float(xu[0])
+
+
+def cma_initial(problem, sampling, seed, mean=None, diag=None, sigma=None):
+    """(m0, d0, sigma0): what is not given comes from CMA_INIT_ROWS rows of the search's own sampling under np.random.seed(seed) — their column
+    mean and variance — and sigma0 from the problem's config (cma_sigma, default 1): in z, generation 0 is then the reference's distribution."""
+    if mean is None or diag is None:
+        np.random.seed(seed)
+        S = np.asarray(sampling._do(problem, CMA_INIT_ROWS), dtype=float)
+        mean = S.mean(axis=0) if mean is None else mean
+        diag = S.var(axis=0) if diag is None else diag
+    mean, diag = np.broadcast_to(np.asarray(mean, float), (problem.n_var,)).copy(), np.broadcast_to(np.asarray(diag, float), (problem.n_var,)).copy()
+    if not (np.isfinite(mean).all() and np.isfinite(diag).all() and (diag > 0).all()):
+        raise ValueError("cmaes: the initial mean must be finite and the initial variances finite and positive (a sampling that never moves a "
+                         "column gives it no scale)")
+    if sigma is None:
+        sigma = getattr(getattr(problem, "config", None), "cma_sigma", None)
+    sigma = DEFAULT_CMA_SIGMA if sigma is None else float(sigma)
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError("cmaes: cma_sigma must be finite and positive, got %r" % (sigma,))
+    return mean, diag, sigma
+
+
+def _cma_result(X, F, best_X, best_F, mean, sigma):
+    res = Result()
+    res.pop = _individuals(np.asarray(X, float), np.asarray(F, float).reshape(-1, 1), False)
+    res.X, res.F = np.asarray(best_X, float), np.array([best_F], float)
+    res.mean, res.sigma = np.asarray(mean, float), float(sigma)
+    res.G, res.CV = np.zeros(1), np.zeros(1)
+    return res
+
+
+def _minimize_cmaes(problem, pop_size, n_gen, sampling, seed, callback, verbose, mask, init):
+    """Generations 0 .. n_gen of the rule on the host: (n_gen + 1) pop_size evaluations, the GA's count."""
+    xl, xu = _cma_checks(problem, pop_size, mask)
+    state = CMAState(*cma_initial(problem, sampling, seed, *init))
+    c = cma_constants(pop_size, problem.n_var)
+    algo = Result()
+    algo.problem, algo.state = problem, state
+    for gen in range(n_gen + 1):
+        X = cma_sample(state, pop_size, xl, xu, seed, gen)
+        out = {}
+        problem._evaluate(X.astype(float), out)
+        F = np.asarray(out["F"], dtype=float).reshape(pop_size, -1)[:, 0]
+        cma_update(state, c, X, F, xl, xu, gen)
+        algo.pop, algo.n_gen = _individuals(X.astype(float), F.reshape(-1, 1), False), gen
+        if verbose:
+            print("gen %4d | n_eval %6d | best %.5g | sigma %.3g" % (gen, (gen + 1) * pop_size, state.best_F, state.sigma))
+        if callback is not None and gen >= 1:
+            callback(algo)
+    res = _cma_result(X, F, state.best_X, state.best_F, state.m, state.sigma)
+    res.state = state
+    return res
+
+
+class _DeviceCMA:
+    """What a callback sees of a device CMA search: `pop` is the generation's rows and F, read back only when something asks for it."""
+
+    def __init__(self, problem, engine):
+        self.problem, self._engine, self.n_gen = problem, engine, 0
+
+    @property
+    def pop(self):
+        r = self._engine.search_read("off_X", "off_F")
+        return _individuals(r["off_X"].astype(float), r["off_F"].astype(float), False)
+
+
+def _minimize_cmaes_device(problem, pop_size, n_gen, sampling, seed, callback, verbose, mask, init):
+    """The same generations on the problem's engine: every generation is one engine.search_step (sample, the pass, rank, update)."""
+    xl, xu = _cma_checks(problem, pop_size, mask)
+    ranks = int(getattr(problem, "ranks", 1) or 1)
+    if ranks > 1:
+        raise ValueError("device search: %d ranks (--dist): the multi-rank wiring is not built yet; run one rank, or the host search" % ranks)
+    bs = int(getattr(getattr(problem, "config", None), "batch_size", 1))
+    if pop_size > DEVICE_MAX_POP or pop_size % bs:
+        raise ValueError("device search: pop_size %d must be a multiple of batch_size %d and at most %d" % (pop_size, bs, DEVICE_MAX_POP))
+    engine = getattr(problem, "engine", None)
+    if engine is None:
+        raise ValueError("device search: this problem has no engine to keep the distribution on (GenerationProblem has one)")
+    if getattr(engine, "search_pop", None) != pop_size or getattr(engine, "search_algorithm", None) != "cmaes":
+        raise ValueError("device search: the engine was built without it, for another pop_size or for another algorithm (its buffers are sized in "
+                         "finalize): set config.device_search = True and config.algorithm = \"cmaes\" before the problem is constructed")
+    m0, d0, s0 = cma_initial(problem, sampling, seed, *init)
+    engine.set_search_operators(xl, xu, seed=seed)
+    engine.search_init_cma(m0, d0, s0)
+    generator = getattr(problem, "generator", None)
+    algo = _DeviceCMA(problem, engine)
+    for gen in range(n_gen + 1):
+        engine.search_step(gen)
+        if generator is not None:
+            generator.generation = gen + 1      # what the host search's evaluate() calls leave behind: the save callback's noise stream
+        algo.n_gen = gen
+        if verbose:
+            c = engine.search_read_cma()
+            print("gen %4d | n_eval %6d | best %.5g | sigma %.3g" % (gen, (gen + 1) * pop_size, c["best_F"], c["sigma"]))
+        if callback is not None and gen >= 1:
+            callback(algo)
+    r, c = engine.search_read("off_X", "off_F"), engine.search_read_cma()
+    res = _cma_result(r["off_X"], r["off_F"][:, 0], c["best_X"], c["best_F"], c["mean"], c["sigma"])
+    res.state = c
+    return res
+
+
 def minimize(problem, algorithm, pop_size, n_gen, sampling, seed=1, callback=None, eta_c=3.0, eta_m=3.0,
-             prob_m=0.5, verbose=False, mask=None, device=False):
+             prob_m=0.5, verbose=False, mask=None, device=False, cma_mean=None, cma_diag=None, cma_sigma=None):
     """pymoo.optimize.minimize(problem, algorithm, ("n_gen", n_gen)) stand-in.
 
     problem: has n_var, n_obj, xl, xu and _evaluate(x, out) (GenerationProblem);
-    algorithm: "ga" | "nsga2"; sampling: object with _do(problem, n) (operators.get_operators);
+    algorithm: "ga" | "nsga2" | "cmaes"; sampling: object with _do(problem, n) (operators.get_operators);
     mask: per-variable type "real" | "int" | "bool" (None = all real) — the BigGAN configs mix real z with
     boolean class bits (operators.py:39), the GPT2 config is all-int.
     device=True (opt-in; real-valued StyleGAN2 searches and the BigGAN configs' [real | bool] rows, on one rank): selection, variation, duplicate flags and survival run on the
-    problem's engine between the passes (include/glass.h "Device search"); the result has the same shapes."""
+    problem's engine between the passes (include/glass.h "Device search"); the result has the same shapes.
+    algorithm "cmaes" (opt-in): separable CMA-ES (include/glass.h "Device search: sep-CMA-ES") — one objective, real variables, scalar bounds;
+    generations 0 .. n_gen of pop_size rows, the callback after generations 1 .. n_gen.  cma_mean / cma_diag / cma_sigma: the initial
+    distribution (default: cma_initial).  The Result has X / F = the best row seen, pop = the last generation, and mean and sigma."""
+    if algorithm == "cmaes":
+        run = _minimize_cmaes_device if device else _minimize_cmaes
+        return run(problem, pop_size, n_gen, sampling, seed, callback, verbose, mask, (cma_mean, cma_diag, cma_sigma))
     if device:
         return _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callback, eta_c, eta_m, prob_m, verbose, mask)
     rng = np.random.default_rng(seed)

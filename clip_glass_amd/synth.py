@@ -331,6 +331,16 @@ def search_uniforms(seed, generation, index, variable, purpose):
     return tuple((w.astype(np.float64) + 0.5) * 2.0 ** -32 for w in x)
 
 
+SEARCH_DRAW_NORMAL = 6      # sep-CMA-ES (csrc/cmaes.hip): index = the sampled row, variable = the column
+
+
+def search_normals(seed, generation, row, column):
+    """z = sqrt(-2 ln u0) cos(2 pi u1), float64, broadcast over the array arguments — the device's N(0, 1) draw of a sep-CMA-ES sample at
+    counter (row, column, generation, purpose 6) (include/glass.h "Device search: sep-CMA-ES"); u2 and u3 are unused."""
+    u0, u1, _, _ = search_uniforms(seed, generation, row, column, SEARCH_DRAW_NORMAL)
+    return np.sqrt(-2.0 * np.log(u0)) * np.cos(6.283185307179586 * u1)
+
+
 # Crop views (csrc/clip.cpp, glass_host_clip_view_boxes): the boxes through which a pass sees every candidate's image — one Philox block per
 # (view, generation) under the seed with this tag XOR-ed into the key's high word.
 CLIP_VIEW_TAG = 0x56494557

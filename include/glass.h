@@ -471,7 +471,8 @@ int glass_engine_get_biggan_tap(glass_engine* e, float* out, int64_t capacity, i
  * not fit is cut by (-cd, index).  Their X, F, rank and cd become the next population, in that order.
  *
  * glass_search_supported: the one rule (host only: callable without a GPU), applied by the setter and by finalize.  algorithm 0 (GA, n_obj
- * 1) or 1 (NSGA-II); pop in [2, 1024] (2048 merged rows are ranked by one workgroup); n_obj in [1, 6]; pop * n_var below 2^31.
+ * 1) or 1 (NSGA-II); pop in [2, 1024] (2048 merged rows are ranked by one workgroup); n_obj in [1, 6]; pop * n_var below 2^31.  (Algorithm
+ * 2, sep-CMA-ES, has its own limits: "Device search: sep-CMA-ES" below.)
  *
  * glass_search_mixed_supported: the same for mixed rows (host only) — everything glass_search_supported says for n_var = n_real + n_bits,
  *   n_real >= 1 and 1 <= n_bits <= 4096 (one workgroup ranks a row's differing bits in LDS).
@@ -518,6 +519,64 @@ int glass_engine_search_step(glass_engine* e, int32_t generation);
 int glass_engine_search_read(glass_engine* e, float* pop_X, float* pop_F, int32_t* rank, double* cd, float* off_X, float* off_F, int32_t* flags,
                              int32_t* counts);
 int glass_engine_latent_uploads(glass_engine* e, int64_t* calls, int64_t* rows);
+
+/* Device search: sep-CMA-ES (opt-in: glass_engine_set_search with algorithm GLASS_SEARCH_CMAES).  The separable CMA-ES of Ros & Hansen
+ * (2008) — a diagonal covariance, O(n) state — as a third search rule next to the GA and NSGA-II above: what stays on the device is a
+ * distribution, not a population.  One objective, minimised; real-valued rows only (a StyleGAN2 engine in z, w or w+).  With n = n_var,
+ * lambda = pop and mu = lambda / 2 (integer division):
+ *
+ * Setup.  Weights w_i = ln(mu + 1/2) - ln i for i = 1 .. mu, normalised to sum to 1; mu_eff = 1 / sum w_i^2.  Constants:
+ *   c_sigma = (mu_eff + 2) / (n + mu_eff + 5)
+ *   d_sigma = 1 + 2 max(0, sqrt((mu_eff - 1) / (n + 1)) - 1) + c_sigma
+ *   c_c     = (4 + mu_eff / n) / (n + 4 + 2 mu_eff / n)
+ *   c_1     = 2 / ((n + 1.3)^2 + mu_eff)
+ *   c_mu    = min(1 - c_1, 2 (mu_eff - 2 + 1 / mu_eff) / ((n + 2)^2 + mu_eff))
+ *   the separable speed-up: c_1 <- min(1, c_1 (n + 2) / 3), then c_mu <- min(1 - c_1, c_mu (n + 2) / 3)
+ *   chi     = sqrt(n) (1 - 1 / (4 n) + 1 / (21 n^2))
+ * State, all double: the mean m [n], the diagonal d [n], the paths p_sigma [n] and p_c [n] (zero at the start), the step sigma, and the
+ * best row seen (fp32 [n]) with its F (+inf at the start).
+ *
+ * Generation g = 0, 1, ...
+ * 1. Sample.  Row r, column j: z = sqrt(-2 ln u0) cos(2 pi u1) from the Philox draw at counter (r, j, g, purpose 6) — the key and the u =
+ *    (word + 0.5) 2^-32 convention of "Random numbers" above; u2 and u3 are unused, 2 pi is the double 6.283185307179586.  x = clip(m_j +
+ *    (sigma sqrt(d_j)) z, xl, xu) = min(max(., xl), xu), evaluated in double without fused multiply-adds and rounded ONCE to the fp32 row.  A
+ *    draw is a pure function of (seed, g, r, j): rows sampled in one launch or in several agree bit for bit.  Numpy mirror:
+ *    synth.search_normals.
+ * 2. Score the lambda rows as glass_engine_search_evaluate scores offspring (whole minibatches, first_minibatch = first_row / batch_size).
+ * 3. Rank the rows by (F, index); -0.0 ties 0.0; a non-finite F goes last, by index.  If fewer than mu rows have a finite F the generation
+ *    updates nothing — every bit of the state stays — and a readable counter (skipped) goes up.  Otherwise the best row seen and its F are
+ *    replaced when the generation's best F is strictly smaller.
+ * 4. Update from the rows as they were evaluated — the fp32 rows, clipped: clipping is a repair — with y_i = (x_{i:lambda} - m) / sigma for
+ *    the mu best, everything per variable j and in this order of operations:
+ *      y_w   = sum w_i y_i and s_2 = sum w_i (y_i y_i), both summed in the order i = 1 .. mu by one writer per variable
+ *      m       <- m + sigma y_w
+ *      p_sigma <- (1 - c_sigma) p_sigma + sqrt(c_sigma (2 - c_sigma) mu_eff) y_w / sqrt(d)              (the old d; left to right)
+ *      h       = 1 if ||p_sigma|| / sqrt(1 - (1 - c_sigma)^(2 (g + 1))) < (1.4 + 2 / (n + 1)) chi, else 0
+ *      p_c     <- (1 - c_c) p_c + (h sqrt(c_c (2 - c_c) mu_eff)) y_w
+ *      d       <- ((1 - c_1) - c_mu) d + c_1 (p_c^2 + (((1 - h) c_c) (2 - c_c)) d) + c_mu s_2                     (the new p_c, the old d)
+ *      sigma   <- sigma exp(min(1, (c_sigma / d_sigma) (||p_sigma|| / chi - 1))), then kept inside [1e-10, xu - xl]
+ *    ||p_sigma||^2 (of the new p_sigma) is summed from partial sums: variables [256 b, 256 b + 256) form part b, summed in index order, and
+ *    the parts are added in the order of b.  The partition is a function of n alone, so the bits do not depend on the grid; there are no
+ *    floating-point atomics.  The dependency of p_c, d and sigma on ||p_sigma|| is a kernel boundary.
+ * The scalars (sigma, ||p_sigma||, h, the counters) live in a small device struct that one thread writes; nothing in a generation reads
+ * the host.  Numpy mirror: tests/cma_ref.py; the host search of clip_glass_amd/search.py ("cmaes" without device=True) is the same rule.
+ *
+ * glass_search_supported(pop, n_var, n_obj, 2): n_obj = 1, pop in [4, 1024] (mu >= 2; one workgroup ranks the rows), pop * n_var below 2^31.
+ * glass_engine_set_search with algorithm 2: as for the GA — between create and finalize, pop <= max_pop and a multiple of batch_size, xl < xu
+ *   exact in fp32; eta_c, eta_m and prob_m are ignored.  Refused by name: an engine with n_obj > 1, a BigGAN engine (its bit columns), an
+ *   engine without a generator, noise_mode 2.  glass_engine_set_search_operators sets the bounds and the seed, as for the GA.
+ * glass_engine_search_init_cma: mean0 [n], diag0 [n] (NULL: ones; every entry positive), sigma0 > 0: the distribution of generation 0.
+ *   Zeroes the paths, the counters and the best row.  (glass_engine_search_init is refused by name on a CMA search, and this on a GA one.)
+ * glass_engine_search_step(g) is sample -> evaluate -> rank -> update; search_vary(g) is the sample, search_evaluate is unchanged and
+ *   search_survive(g) is rank + update.  Calls out of order return GLASS_ERR_STATE by name.
+ * glass_engine_search_read keeps its meaning for off_X (the generation's rows), off_F and counts = {0, non-finite rows of the last rank};
+ *   the population's outputs (pop_X, pop_F, rank, cd, flags) must be NULL.
+ * glass_engine_search_read_cma: nullable outputs — m, d, p_sigma, p_c double [n]; scalars_d double [2] = {sigma, ||p_sigma||}; scalars_i
+ *   int32 [5] = {h, finite rows of the last rank, whether it updated, skipped generations, updated generations}; best_X [n]; best_F [1]. */
+#define GLASS_SEARCH_CMAES 2
+int glass_engine_search_init_cma(glass_engine* e, const double* mean0, const double* diag0, double sigma0);
+int glass_engine_search_read_cma(glass_engine* e, double* mean, double* diag, double* p_sigma, double* p_c, double* scalars_d, int32_t* scalars_i,
+                                 float* best_X, float* best_F);
 
 /* Device info for bench.py (CU count, name, HBM bytes). */
 int glass_device_info(int32_t device, char* name, int32_t name_len, int32_t* cus, int64_t* hbm_bytes);

@@ -307,6 +307,21 @@ int glass_op_ga_duplicates(int32_t device, int32_t pop, int32_t n_off, int32_t n
 int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off, int32_t n_obj, int32_t pop_out, int32_t nsga, const float* F,
                         const int32_t* flags, int32_t* chosen, int32_t* rank, double* cd, float* F_out, int32_t* counts, int32_t n_var, const float* X,
                         const float* Xoff, float* X_out);
+/* The sep-CMA-ES kernels (cmaes.hip; include/glass.h "Device search: sep-CMA-ES") on caller-supplied state and F, each through the launcher
+ * the engine calls; the weights and constants are the library's own for (lambda, n).
+ * glass_op_cma_sample: mean [n], diag [n], sigma -> rows [row0, row0 + rows) of `generation` into X [lambda,n], which comes in with the
+ *   caller's values: every other row comes back untouched.
+ * glass_op_cma_rank: F [lambda] and the best F seen so far -> order int32 [lambda] (rows by (F, index), non-finite last), info int32 [5] =
+ *   {finite rows, updated (finite >= mu), the row that became the best seen or -1, skipped generations (0 / 1), non-finite rows},
+ *   best_F_out [1].
+ * glass_op_cma_update: rank, both update phases and the best-row copy.  X [lambda,n] and F [lambda] are the generation's rows as they were
+ *   evaluated; in and out: state double [4,n] = (m, d, p_sigma, p_c), scalars_d double [2] = {sigma, ||p_sigma||}, scalars_i int32 [6] = {h,
+ *   finite, updated, skipped, updates, best row of this generation or -1 (out only)}, best_X [n], best_F [1]; out: order int32 [lambda]. */
+int glass_op_cma_sample(int32_t device, int32_t lambda, int32_t n, const double* mean, const double* diag, double sigma, double xl, double xu,
+                        uint64_t seed, int32_t generation, int32_t row0, int32_t rows, float* X);
+int glass_op_cma_rank(int32_t device, int32_t lambda, const float* F, float best_F, int32_t* order, int32_t* info, float* best_F_out);
+int glass_op_cma_update(int32_t device, int32_t lambda, int32_t n, const float* X, const float* F, double* state, double* scalars_d,
+                        int32_t* scalars_i, double xl, double xu, int32_t generation, float* best_X, float* best_F, int32_t* order);
 /* raw MFMA layout probe: D = A[32x16] * B[16x32] through the fragment mapping of common.h */
 int glass_op_mfma_probe(int32_t device, const float* a /*[32,16]*/, const float* b /*[16,32]*/, float* d /*[32,32]*/);
 
