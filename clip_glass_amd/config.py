@@ -36,7 +36,13 @@ key is refused for GPT2;
 `algorithm` "cmaes" (instead of the table's "ga": separable CMA-ES, include/glass.h "Device search: sep-CMA-ES" — one objective and
 real-valued rows, so the StyleGAN2 `_nod` configs, with `lpips_lambda` / `anchor_lambda` > 0 where those objectives are on; on the host, or
 on the GPU with `device_search`) and `cma_sigma` (1.0: the initial step size; the initial mean and variances come from 4096 rows of the
-config's own sampling) — refused by name for a config with more than one objective, the BigGAN configs, GPT2 and `--dist`."""
+config's own sampling) — refused by name for a config with more than one objective, the BigGAN configs, GPT2 and `--dist`;
+`islands` (unset, the default: one population; K: with `device_search`, K populations of `pop_size` rows each — `pop_size` stays the
+per-island size, the engine is built for K pop_size rows — in one engine and one pass per generation, island i under seed + i,
+include/glass.h "Device search: islands"), with `migrate_every` (0: never; M: every M generations the best rows of island i - 1 replace the
+worst of island i), `migrants` (1: rows per migration, at most pop_size / 2) and `island_prompts` (a list of texts or ready features:
+`target` is island 0's prompt and each entry adds an island that searches it alone — not with migration, `prompt_mode` "pareto" or an edit
+source) — the StyleGAN2 and BigGAN configs with "ga" / "nsga2" on one rank; refused by name for GPT2, `--dist`, "cmaes" and the host search."""
 from .latent import DeepMindBigGANLatentSpace, GPT2LatentSpace, StyleGAN2LatentSpace
 from .models import GPT2, DeepMindBigGAN, StyleGAN2
 from .utils import biggan_denorm, biggan_norm

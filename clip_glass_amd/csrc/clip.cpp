@@ -505,7 +505,10 @@ static void clip_cosine(glass_engine* e, int P, int views) {      // the end of 
             e->launch_error = "no kernel accepts layer clip.head (cosine_set_dir: shape outside its limits)";
     } else if (ps.T > 0) {           // a prompt set: every row against every entry, still one launch
         const int V = std::max(views, 1);
-        if (!launch_cosine_set(e->d_feat, ps.d_targets, ps.d_weights, ps.W, P / V, V, ps.T, E, views > 0 ? e->d_view_sim : nullptr, ps.d_sim, e->d_sim, e->cur) &&
+        CosineIslands isl;      // a pass of an island search with own prompts: the rows' weights by island
+        if (e->island_row0 >= 0 && e->search.own_prompts) isl = {ps.d_isl_weights, ps.d_isl_W, e->search.g.pop, e->island_row0};
+        if (!launch_cosine_set(e->d_feat, ps.d_targets, ps.d_weights, ps.W, P / V, V, ps.T, E, views > 0 ? e->d_view_sim : nullptr, ps.d_sim, e->d_sim, e->cur,
+                               isl) &&
             e->launch_error.empty())
             e->launch_error = "no kernel accepts layer clip.head (cosine_set: shape outside its limits)";
     } else if (views > 0) launch_cosine_views(e->d_feat, e->d_target, P / views, views, E, e->d_view_sim, e->d_sim, e->cur);

@@ -279,6 +279,9 @@ struct glass_engine {
         int T = 0, mode = 0;                // entries; 0 sum, 1 pareto
         float W = 0.f;                      // sum |w_t|
         float *d_targets = nullptr, *d_weights = nullptr, *d_sim = nullptr;    // [16][clip_embed], [16], [max_pop][16] (rows of T in use)
+        // own prompts of an island search (glass_engine_set_island_weights; allocated by its first call): weights [islands][isl_T], sum |w| [islands]
+        float *d_isl_weights = nullptr, *d_isl_W = nullptr;
+        int isl_T = 0;
     } pset;
     // ---- device search (glass_engine_set_search; pop 0: off — nothing below is allocated or touched) ----
     struct Search {
@@ -294,7 +297,16 @@ struct glass_engine {
         // offspring half of F, so search_evaluate is the GA's; of the buffers above only Xoff, F and counts are allocated
         bool cma = false;
         CmaState cs = {};                   // cs.m holds m, d, p_sigma, p_c back to back ([4][n_var])
+        // islands (include/glass.h "Device search: islands"; glass_engine_set_search_islands): 0 — the setter was never called, every buffer
+        // and launch above is a single search's.  K >= 1: the buffers hold K populations of g.pop rows back to back, F is the populations'
+        // plane [K pop][n_obj] followed by the offspring's, counts is [K][3], and the island forms of the kernels run
+        int islands = 0, migrate_every = 0, migrants = 1;
+        int survived_gen = -1;              // the generation whose survival the populations hold and whose migration has not run
+        bool own_prompts = false;           // glass_engine_set_island_weights: pset's island table is in use
+        int rows() const { return (islands ? islands : 1) * g.pop; }
     } search;
+    int noise_period = 0;                   // minibatches per island while a pass of an island search runs (upload_noise); 0 otherwise
+    int island_row0 = -1;                   // the first search row of such a pass (the rows' islands in the head); -1 otherwise
     long long latent_uploads = 0, latent_upload_rows = 0;   // host-to-device latent copies of the pass so far (glass_engine_latent_uploads)
     // ---- image editing (include/glass.h "Image editing"; edit.cpp).  Nothing below is allocated or touched by an engine that has no
     // anchor (cfg.anchor 0) and never calls glass_engine_set_direction_source ----

@@ -84,8 +84,9 @@ void launch_style_norm(float* s, int ld, int P, int n_layers, const int* d_off, 
 // per-sample modulated+demodulated weights: wm[b][e] = w[e] * sn[b][e % Cin] * dscale[b][(e / Cin) % Cout]
 void launch_modulate_weights(const half_t* w, long long elems, int Cin, int Cout, const float* sn, int sn_stride,
                               const float* dscale, int ds_stride, int P, half_t* wm, hipStream_t st);
+// plane m of the launch is that of minibatch mb0 + m, or with a period > 0 of minibatch (mb0 + m) % period (the device search's islands)
 void launch_noise(float* out, int n_mb, int hw, uint32_t layer, uint32_t mb0, uint32_t generation,
-                  uint64_t seed, hipStream_t st);
+                  uint64_t seed, hipStream_t st, uint32_t period = 0);
 
 // --- image-space ops ---------------------------------------------------------------
 // y[b][c][p] = bias[c] + smax[b]*sum_i wrgb[c][i]*sn[b][i]*x[b][p][i] + upfir(yprev)
@@ -171,8 +172,15 @@ void launch_assemble_F_lpips(const float* sim, const float* dis, const float* lp
 #define GLASS_PROMPT_MAX_VIEWS 16   // glass_clip_views_supported's limit
 // feat [P][V][D] (V = 1: no views), targets [T][D], weights [T], W = prompt_weight_sum -> view_sim [P][V] (nullable: entry 0's per-view cosines),
 // set_sim [P][T] (the ordered means), sim [P] (the combination of mode `sum`).  One launch; false: a shape outside the limits, nothing launched
+// isl (the device search's islands with own prompts): row p combines its entries with row (row0 + p) / pop of weights [islands][T] and that
+// island's W [islands] instead; weights nullptr: none
+struct CosineIslands {
+    const float* weights = nullptr;
+    const float* W = nullptr;
+    int pop = 0, row0 = 0;
+};
 bool launch_cosine_set(const float* feat, const float* targets, const float* weights, float W, int P, int V, int T, int D, float* view_sim,
-                       float* set_sim, float* sim, hipStream_t st);
+                       float* set_sim, float* sim, hipStream_t st, CosineIslands isl = {});
 float prompt_weight_sum(const float* weights, int T);      // sum |w_t| in fp32, t = 0 .. T - 1 (host)
 // F [P][K + (dis != 0) + (lp != 0)]: F[p][t] = w_t < 0 ? set_sim[p][t] : -set_sim[p][t], then relu(1 - dis), then lp (nullable each)
 void launch_assemble_F_set(const float* set_sim, const float* weights, const float* dis, const float* lp, int K, int P, float* F, hipStream_t st);
@@ -231,6 +239,21 @@ const char* launch_ga_survive(float* F, const int* flags, int n_pop, int n_off, 
                               double* cd_out, int* counts, hipStream_t st);
 void launch_ga_gather(const float* X, const float* Xoff, const int* chosen, int n_pop, int pop_out, int n_var, float* Xnext, hipStream_t st);
 size_t ga_survive_lds_bytes(int n_rows, int n_obj);
+// The island forms (include/glass.h "Device search: islands"): every buffer holds `islands` populations of g.pop / pop rows back to back,
+// island i runs under seed + i with local indices, and the island is a grid dimension.  nullptr: a shape outside the limits.
+#define GLASS_SEARCH_MAX_ISLANDS 64
+// every offspring row of every island; all-real rows: n_bits 0 and parts GA_VARY_REAL
+const char* launch_ga_vary_islands(const float* X, const int* rank, const double* cd, const GaParams& g, int islands, int n_real, int n_bits,
+                                   int generation, int parts, float* Xoff, hipStream_t st);
+const char* launch_ga_duplicates_islands(const float* X, const float* Xoff, int islands, int pop, int n_var, int* flags, hipStream_t st);
+// F [islands pop][n_obj] the populations' plane (rewritten), Foff the offspring's (n_off = pop) or unused (n_off = 0); counts [islands][3] =
+// {flagged, non-finite, migrants accepted}.  gated (n_off 0 only): islands whose third counter is 0 keep their state, chosen = identity
+const char* launch_ga_survive_islands(float* F, const float* Foff, const int* flags, int islands, int pop, int n_off, int n_obj, int nsga, int gated,
+                                      int* chosen, int* rank_out, double* cd_out, int* counts, hipStream_t st);
+void launch_ga_gather_islands(const float* X, const float* Xoff, const int* chosen, int islands, int pop, int n_var, float* Xnext, hipStream_t st);
+// ring migration of the `migrants` best rows of island i - 1 onto the worst rows of island i, X and F in place; writes counts[i][2]
+const char* launch_ga_migrate(float* X, float* F, const int* rank, const double* cd, int islands, int pop, int n_var, int n_obj, int migrants, int* counts,
+                              hipStream_t st);
 
 // --- device search: sep-CMA-ES (cmaes.hip; include/glass.h "Device search: sep-CMA-ES") ---
 #define GLASS_SEARCH_DRAW_NORMAL 6u       // index = sampled row, variable = column; z = sqrt(-2 ln u0) cos(2 pi u1)

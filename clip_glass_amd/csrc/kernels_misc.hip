@@ -296,12 +296,13 @@ void launch_modulate_weights(const half_t* w, long long elems, int Cin, int Cout
 }
 
 // ---- noise planes: Philox4x32-10 (common.h) + Box-Muller (numpy mirror: clip_glass_amd/synth.py) --
+// plane blockIdx.y is that of minibatch mb0 + blockIdx.y; period > 0 (include/glass.h "Device search: islands"): of (mb0 + blockIdx.y) % period
 __global__ void noise_kernel(float* out, int hw, uint32_t layer, uint32_t mb0, uint32_t generation, uint32_t k0,
-                             uint32_t k1) {
+                             uint32_t k1, uint32_t period) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     const int nq = (hw + 3) / 4;
     if (q >= nq) return;
-    const uint32_t mb = mb0 + blockIdx.y;
+    const uint32_t mb = period ? (mb0 + blockIdx.y) % period : mb0 + blockIdx.y;
     uint32_t c[4] = {(uint32_t)q, layer, mb, generation};
     philox4x32_10(c, k0, k1);
     float u[4];
@@ -321,10 +322,10 @@ __global__ void noise_kernel(float* out, int hw, uint32_t layer, uint32_t mb0, u
         if (q * 4 + j < hw) op[q * 4 + j] = o[j];
 }
 void launch_noise(float* out, int n_mb, int hw, uint32_t layer, uint32_t mb0, uint32_t generation, uint64_t seed,
-                  hipStream_t st) {
+                  hipStream_t st, uint32_t period) {
     const int nq = (hw + 3) / 4;
     hipLaunchKernelGGL(noise_kernel, dim3((nq + 255) / 256, n_mb), dim3(256), 0, st, out, hw, layer, mb0,
-                       generation, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32));
+                       generation, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), period);
 }
 
 // ---- toRGB (1x1 modulated conv, no demod: stylegan2/models.py:852-870) fused with the

@@ -610,6 +610,17 @@ extern "C" int glass_op_noise(int32_t device, int32_t n_mb, int32_t hw, uint32_t
     return st.intact(d, "noise: stored behind the output (element >= hw of the last plane)");
 }
 
+// launch_noise with a period: plane m is that of minibatch (mb0 + m) % period (period 0: glass_op_noise)
+extern "C" int glass_op_noise_period(int32_t device, int32_t n_mb, int32_t hw, uint32_t layer, uint32_t mb0, uint32_t generation, uint64_t seed,
+                                     uint32_t period, float* out) {
+    OPREQ(out && n_mb > 0 && hw > 0, "bad argument");
+    Stage st(device);
+    const auto d = st.poisoned<float>((size_t)n_mb * hw, GUARD_ROWS * 4);
+    TRY(st.run([&] { launch_noise(d, n_mb, hw, layer, mb0, generation, seed, 0, period); }));
+    TRY(st.fetch(out, d));
+    return st.intact(d, "noise: stored behind the output (element >= hw of the last plane)");
+}
+
 extern "C" int glass_op_gpt2_sample(int32_t device, int32_t rows, int32_t V, const float* logits, float temperature, int32_t top_k,
                                     uint64_t seed, int32_t generation, int32_t first_row, int32_t step, int32_t purpose, int32_t* out) {
     OPREQ(logits && out && rows > 0 && V > 0, "bad argument");
@@ -1113,6 +1124,27 @@ extern "C" int glass_op_cosine_set(int32_t device, int32_t P, int32_t V, int32_t
     return st.fetch(sim, ds);
 }
 
+// launch_cosine_set with an island table: row p takes row (row0 + p) / pop of weights [islands, T] (include/glass.h "Device search: islands")
+extern "C" int glass_op_cosine_set_islands(int32_t device, int32_t P, int32_t V, int32_t T, int32_t D, const float* feat, const float* targets,
+                                           const float* weights, int32_t islands, int32_t pop, int32_t row0, float* view_sim, float* set_sim, float* sim) {
+    OPREQ(feat && targets && weights && view_sim && set_sim && sim && P > 0 && D > 0, "bad argument");
+    OPREQ(V >= 1 && V <= GLASS_PROMPT_MAX_VIEWS && T >= 1 && T <= GLASS_PROMPT_MAX, "cosine_set: V and T must be in [1, 16]");
+    OPREQ(islands >= 1 && islands <= GLASS_SEARCH_MAX_ISLANDS && pop >= 1 && row0 >= 0 && (long long)row0 + P <= (long long)islands * pop,
+          "cosine_set_islands: rows [row0, row0 + P) must lie inside the islands * pop rows, islands in [1, 64]");
+    std::vector<float> W(islands);
+    for (int i = 0; i < islands; ++i) W[i] = prompt_weight_sum(weights + (size_t)i * T, T);
+    Stage st(device);
+    const auto df = st.in32(feat, (size_t)P * V * D), dt = st.in32(targets, (size_t)T * D), dw = st.in32(weights, (size_t)islands * T);
+    const auto dW = st.in32(W.data(), islands);
+    const auto dvs = st.poisoned<float>((size_t)P * V), dss = st.poisoned<float>((size_t)P * T), ds = st.poisoned<float>(P);
+    CosineIslands isl;
+    isl.weights = dw; isl.W = dW; isl.pop = pop; isl.row0 = row0;
+    TRY(st.run([&] { return accepted(launch_cosine_set(df, dt, nullptr, 0.f, P, V, T, D, dvs, dss, ds, 0, isl), "cosine_set refused the shape"); }));
+    TRY(st.fetch(view_sim, dvs));
+    TRY(st.fetch(set_sim, dss));
+    return st.fetch(sim, ds);
+}
+
 extern "C" int glass_op_assemble_F_set(int32_t device, int32_t P, int32_t K, const float* set_sim, const float* weights, const float* dis,
                                        const float* lp, float* F) {
     OPREQ(set_sim && weights && F && P > 0 && K >= 1 && K <= GLASS_PROMPT_MAX, "bad argument (K in [1, 16])");
@@ -1435,6 +1467,42 @@ extern "C" int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off,
     TRY(st.fetch(F_out, dF, (size_t)pop_out * n_obj));
     TRY(st.fetch(counts, dcn));
     return gather ? st.fetch(X_out, dXo) : GLASS_OK;
+}
+
+// the whole migration of include/glass.h "Device search: islands": ga_migrate_kernel in place, the gated ranking of the islands that accepted a
+// row and the gather.  X [islands pop, n_var], F [islands pop, n_obj], rank, cd as survival left them -> the same four after the migration,
+// accepted int32 [islands]
+extern "C" int glass_op_ga_migrate(int32_t device, int32_t islands, int32_t pop, int32_t n_var, int32_t n_obj, int32_t nsga, int32_t migrants,
+                                   const float* X, const float* F, const int32_t* rank, const double* cd, float* X_out, float* F_out, int32_t* rank_out,
+                                   double* cd_out, int32_t* accepted) {
+    OPREQ(X && F && rank && cd && X_out && F_out && rank_out && cd_out && accepted, "null argument");
+    TRY(glass_search_islands_supported(islands, pop, n_var, n_obj, nsga ? GLASS_SEARCH_NSGA2 : GLASS_SEARCH_GA, 1, migrants));
+    OPREQ(islands >= 2, "ga_migrate: a ring has at least two islands");
+    const size_t R = (size_t)islands * pop;
+    Stage st(device);
+    const auto dX = st.in32(X, R * n_var), dF = st.in32(F, R * n_obj);
+    const auto dr = st.in_i32(rank, R);
+    const auto dc = st.in(cd, R);
+    const std::vector<int32_t> zero((size_t)3 * islands, 0);
+    const auto dcn = st.in_i32(zero.data(), zero.size());
+    const auto dch = st.poisoned<int32_t>(R, 4);
+    const auto dXo = st.poisoned<float>(R * n_var, 4);
+    TRY(st.run([&]() -> int {
+        OPREQ(launch_ga_migrate(dX, dF, dr, dc, islands, pop, n_var, n_obj, migrants, dcn, 0), "ga_migrate refused the shape");
+        OPREQ(launch_ga_survive_islands(dF, nullptr, nullptr, islands, pop, 0, n_obj, nsga, 1, dch, dr, dc, dcn, 0), "ga_survive_islands refused the shape");
+        launch_ga_gather_islands(dX, nullptr, dch, islands, pop, n_var, dXo, 0);
+        return GLASS_OK;
+    }));
+    TRY(st.intact(dch, "ga_survive_islands stored past the last island's slots"));
+    TRY(st.intact(dXo, "ga_gather_islands stored past the last island's rows"));
+    TRY(st.fetch(X_out, dXo, R * n_var));
+    TRY(st.fetch(F_out, dF));
+    TRY(st.fetch(rank_out, dr));
+    TRY(st.fetch(cd_out, dc));
+    std::vector<int32_t> cn((size_t)3 * islands);
+    TRY(st.fetch(cn.data(), dcn));
+    for (int i = 0; i < islands; ++i) accepted[i] = cn[(size_t)3 * i + 2];
+    return GLASS_OK;
 }
 
 // ---- device search: sep-CMA-ES (cmaes.hip) -----------------------------------------------------------------------------------------

@@ -15,13 +15,21 @@ __device__ __forceinline__ float ps_wsum(float v) {
 // (four independent accumulator pairs per lane; each one runs i = lane, lane + 64, ... and the wave sum, cosine_kernel's order).  STAGED: the
 // T D floats of the set are copied to LDS once per workgroup; otherwise (more than 64 KB) they stream from L2.  After one barrier, lane t of wave 0
 // forms entry t's mean over v = 0 .. V - 1 and the wave combines them in the order t = 0 .. T - 1.
+// isl.weights (include/glass.h "Device search: islands", own prompts): candidate p belongs to island (isl.row0 + p) / isl.pop and combines its
+// entries with that island's row of the table [islands][T] and its sum of |w|; nullptr: weights and W, as ever.
 template <bool STAGED>
 __global__ __launch_bounds__(256) void cosine_set_kernel(const float* __restrict__ feat, const float* __restrict__ targets,
                                                          const float* __restrict__ weights, float W, int V, int T, int D,
-                                                         float* __restrict__ view_sim, float* __restrict__ set_sim, float* __restrict__ sim) {
+                                                         float* __restrict__ view_sim, float* __restrict__ set_sim, float* __restrict__ sim,
+                                                         CosineIslands isl) {
     extern __shared__ float ps_targets[];                               // STAGED: [T][D]
     __shared__ float c[GLASS_PROMPT_MAX_VIEWS][GLASS_PROMPT_MAX];       // c[v][t]
     const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if (isl.weights) {
+        const int island = (isl.row0 + p) / isl.pop;
+        weights = isl.weights + (size_t)island * T;
+        W = isl.W[island];
+    }
     if (STAGED) {
         for (int i = tid; i < T * D; i += 256) ps_targets[i] = targets[i];
         __syncthreads();
@@ -90,15 +98,16 @@ float prompt_weight_sum(const float* weights, int T) {
 }
 
 bool launch_cosine_set(const float* feat, const float* targets, const float* weights, float W, int P, int V, int T, int D, float* view_sim,
-                       float* set_sim, float* sim, hipStream_t st) {
+                       float* set_sim, float* sim, hipStream_t st, CosineIslands isl) {
+    if (isl.weights && (!isl.W || isl.pop < 1 || isl.row0 < 0)) return false;
     if (P < 1 || V < 1 || V > GLASS_PROMPT_MAX_VIEWS || T < 1 || T > GLASS_PROMPT_MAX || D < 1 || D > (1 << 20)) return false;
     const size_t bytes = (size_t)T * D * sizeof(float);
     if (bytes <= (64u << 10)) {
         static DevOnce once;
         once.run([&] { (void)hipFuncSetAttribute((const void*)cosine_set_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10); });
-        hipLaunchKernelGGL(cosine_set_kernel<true>, dim3(P), dim3(256), bytes, st, feat, targets, weights, W, V, T, D, view_sim, set_sim, sim);
+        hipLaunchKernelGGL(cosine_set_kernel<true>, dim3(P), dim3(256), bytes, st, feat, targets, weights, W, V, T, D, view_sim, set_sim, sim, isl);
     } else {
-        hipLaunchKernelGGL(cosine_set_kernel<false>, dim3(P), dim3(256), 0, st, feat, targets, weights, W, V, T, D, view_sim, set_sim, sim);
+        hipLaunchKernelGGL(cosine_set_kernel<false>, dim3(P), dim3(256), 0, st, feat, targets, weights, W, V, T, D, view_sim, set_sim, sim, isl);
     }
     return true;
 }

@@ -122,28 +122,104 @@ extern "C" int glass_engine_set_search_operators(glass_engine* e, double xl, dou
     return GLASS_OK;
 }
 
+// ---- islands (include/glass.h "Device search: islands") ----
+extern "C" int glass_search_islands_supported(int32_t islands, int32_t pop, int32_t n_var, int32_t n_obj, int32_t algorithm, int32_t migrate_every,
+                                              int32_t migrants) {
+    REQUIRE(algorithm != GLASS_SEARCH_CMAES, GLASS_ERR_ARG,
+            "device search islands: cmaes keeps one distribution, not populations; islands of distributions are a different feature (use ga or nsga2)");
+    if (int rc = glass_search_supported(pop, n_var, n_obj, algorithm)) return rc;
+    REQUIRE(islands >= 1 && islands <= GLASS_SEARCH_MAX_ISLANDS, GLASS_ERR_ARG,
+            "device search islands: islands must be in [1, " + std::to_string(GLASS_SEARCH_MAX_ISLANDS) + "], got " + std::to_string(islands));
+    REQUIRE((long long)islands * pop * n_var < (1LL << 31), GLASS_ERR_ARG,
+            "device search islands: islands * pop * n_var must be below 2^31, got " + std::to_string((long long)islands * pop * n_var));
+    REQUIRE(migrate_every >= 0, GLASS_ERR_ARG, "device search islands: migrate_every must be >= 0 (0: never), got " + std::to_string(migrate_every));
+    REQUIRE(migrants >= 1 && migrants <= pop / 2, GLASS_ERR_ARG,
+            "device search islands: migrants must be in [1, pop / 2 = " + std::to_string(pop / 2) +
+                "] (an island's best rows leave and its worst are replaced: the two must be disjoint), got " + std::to_string(migrants));
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_search_islands(glass_engine* e, int32_t islands, int32_t migrate_every, int32_t migrants) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(!e->finalized, GLASS_ERR_STATE, "set_search_islands: the engine is finalized (its buffers are sized in finalize: call it before)");
+    glass_engine::Search& s = e->search;
+    REQUIRE(s.g.pop > 0, GLASS_ERR_STATE, "set_search_islands: the device search is off (glass_engine_set_search or set_search_mixed first)");
+    REQUIRE(!s.cma, GLASS_ERR_STATE,
+            "set_search_islands: this is a cmaes search, which keeps one distribution, not populations; islands of distributions are a different feature");
+    if (int rc = glass_search_islands_supported(islands, s.g.pop, 1, e->cfg.n_obj, s.nsga, migrate_every, migrants)) return rc;
+    REQUIRE((long long)islands * s.g.pop <= e->cfg.max_pop, GLASS_ERR_ARG,
+            "set_search_islands: islands * pop = " + std::to_string((long long)islands * s.g.pop) + " rows are scored in one pass and max_pop is " +
+                std::to_string(e->cfg.max_pop));
+    s.islands = islands;
+    s.migrate_every = migrate_every;
+    s.migrants = migrants;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_island_weights(glass_engine* e, const float* w, int32_t islands, int32_t T) {
+    REQUIRE(e && w, GLASS_ERR_ARG, "null argument");
+    REQUIRE(e->finalized, GLASS_ERR_STATE, "set_island_weights: finalize() and set_targets() first (the weights are over the entries of a prompt set)");
+    glass_engine::Search& s = e->search;
+    glass_engine::PromptSet& ps = e->pset;
+    REQUIRE(s.islands >= 1, GLASS_ERR_STATE, "set_island_weights: this search has no islands (glass_engine_set_search_islands before finalize)");
+    REQUIRE(islands == s.islands, GLASS_ERR_ARG,
+            "set_island_weights: the table has " + std::to_string(islands) + " rows and the search " + std::to_string(s.islands) + " islands");
+    REQUIRE(ps.T > 0, GLASS_ERR_STATE, "set_island_weights: set_targets() first (the islands' prompts are the entries of a prompt set)");
+    REQUIRE(T == ps.T, GLASS_ERR_ARG,
+            "set_island_weights: the table has " + std::to_string(T) + " columns and the prompt set " + std::to_string(ps.T) + " entries");
+    REQUIRE(ps.mode == 0, GLASS_ERR_STATE,
+            "set_island_weights: own prompts combine the entries per island in mode sum; this prompt set is in mode pareto (one column of F per entry)");
+    REQUIRE(!e->edit.has_source, GLASS_ERR_STATE,
+            "set_island_weights: own prompts are not combined with a direction source (the set's entries are then directions from one source)");
+    REQUIRE(!(s.islands > 1 && s.migrate_every > 0), GLASS_ERR_STATE,
+            "set_island_weights: own prompts are not combined with migration (a migrant's F would be stale under another island's objective): "
+            "set_search_islands with migrate_every 0");
+    float W[GLASS_SEARCH_MAX_ISLANDS];
+    for (int i = 0; i < islands; ++i) {
+        for (int t = 0; t < T; ++t)
+            REQUIRE(isfinite(w[(size_t)i * T + t]), GLASS_ERR_ARG, "set_island_weights: island " + std::to_string(i) + " weight " + std::to_string(t) + " is not finite");
+        W[i] = prompt_weight_sum(w + (size_t)i * T, T);
+        REQUIRE(W[i] > 0.f, GLASS_ERR_ARG, "set_island_weights: island " + std::to_string(i) + " has no non-zero weight");
+    }
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    if (!ps.d_isl_weights) {
+        int rc;
+        if ((rc = dev_alloc(e, &ps.d_isl_weights, (size_t)GLASS_SEARCH_MAX_ISLANDS * GLASS_PROMPT_MAX))) return rc;
+        if ((rc = dev_alloc(e, &ps.d_isl_W, (size_t)GLASS_SEARCH_MAX_ISLANDS))) return rc;
+    }
+    GLASS_HIP(hipMemcpy(ps.d_isl_weights, w, (size_t)islands * T * sizeof(float), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemcpy(ps.d_isl_W, W, (size_t)islands * sizeof(float), hipMemcpyHostToDevice));
+    ps.isl_T = T;
+    s.own_prompts = true;
+    return GLASS_OK;
+}
+
 int alloc_search(glass_engine* e) {
     glass_engine::Search& s = e->search;
     if (!s.g.pop) return GLASS_OK;
     const int pop = s.g.pop, M = e->cfg.n_obj;
     s.n_var = (int)latent_row_floats(e);
+    REQUIRE(!(s.cma && s.islands), GLASS_ERR_STATE, "finalize: a cmaes search keeps one distribution and has no islands (set_search_islands is for ga / nsga2)");
     if (s.cma) return alloc_cma(e);
+    REQUIRE(s.rows() <= e->cfg.max_pop, GLASS_ERR_ARG, "finalize: islands * pop rows are scored in one pass and exceed max_pop");
     if (int rc = s.n_real ? glass_search_mixed_supported(pop, s.n_real, s.n_var - s.n_real, M, s.nsga) : glass_search_supported(pop, s.n_var, M, s.nsga))
         return rc;
+    if (s.islands)
+        if (int rc = glass_search_islands_supported(s.islands, pop, s.n_var, M, s.nsga, s.migrate_every, s.migrants)) return rc;
     int rc;
-    const size_t xn = (size_t)pop * s.n_var;
+    const size_t R = (size_t)s.rows(), xn = R * s.n_var, nc = s.islands ? (size_t)3 * s.islands : 2;      // (no islands: R = pop, a single search's sizes)
     if ((rc = dev_alloc(e, &s.X[0], xn))) return rc;
     if ((rc = dev_alloc(e, &s.X[1], xn))) return rc;
     if ((rc = dev_alloc(e, &s.Xoff, xn))) return rc;
-    if ((rc = dev_alloc(e, &s.F, (size_t)2 * pop * M))) return rc;
-    if ((rc = dev_alloc(e, &s.rank, (size_t)pop))) return rc;
-    if ((rc = dev_alloc(e, &s.cd, (size_t)pop))) return rc;
-    if ((rc = dev_alloc(e, &s.flags, (size_t)pop))) return rc;
-    if ((rc = dev_alloc(e, &s.chosen, (size_t)pop))) return rc;
-    if ((rc = dev_alloc(e, &s.counts, (size_t)2))) return rc;
-    GLASS_HIP(hipMemset(s.flags, 0, (size_t)pop * sizeof(int)));
-    GLASS_HIP(hipMemset(s.counts, 0, 2 * sizeof(int)));
-    GLASS_HIP(hipMemset(s.F, 0, (size_t)2 * pop * M * sizeof(float)));
+    if ((rc = dev_alloc(e, &s.F, 2 * R * M))) return rc;
+    if ((rc = dev_alloc(e, &s.rank, R))) return rc;
+    if ((rc = dev_alloc(e, &s.cd, R))) return rc;
+    if ((rc = dev_alloc(e, &s.flags, R))) return rc;
+    if ((rc = dev_alloc(e, &s.chosen, R))) return rc;
+    if ((rc = dev_alloc(e, &s.counts, nc))) return rc;
+    GLASS_HIP(hipMemset(s.flags, 0, R * sizeof(int)));
+    GLASS_HIP(hipMemset(s.counts, 0, nc * sizeof(int)));
+    GLASS_HIP(hipMemset(s.F, 0, 2 * R * M * sizeof(float)));
     return GLASS_OK;
 }
 
@@ -162,25 +238,28 @@ namespace {
 // the launches of the three phases, on e->cur; nothing here waits
 void launch_vary(glass_engine* e, int generation) {
     glass_engine::Search& s = e->search;
-    const int pop = s.g.pop;
-    const double xbytes = (double)pop * s.n_var * sizeof(float);
+    const int pop = s.g.pop, K = s.islands, n_real = s.n_real ? s.n_real : s.n_var;
+    const double xbytes = (double)s.rows() * s.n_var * sizeof(float);
     const double real_share = s.n_real ? (double)s.n_real / s.n_var : 1.0;
     {
         Prof pr(e, "search.vary", 0, 3 * xbytes * real_share);
-        const char* k = s.n_real ? launch_ga_vary_mixed(s.X[s.cur], s.rank, s.cd, s.g, s.n_real, s.n_var - s.n_real, generation, 0, pop, GA_VARY_REAL, s.Xoff, e->cur)
-                                 : launch_ga_vary(s.X[s.cur], s.rank, s.cd, s.g, s.n_var, generation, 0, pop, s.Xoff, e->cur);
+        const char* k = K         ? launch_ga_vary_islands(s.X[s.cur], s.rank, s.cd, s.g, K, n_real, s.n_var - n_real, generation, GA_VARY_REAL, s.Xoff, e->cur)
+                        : s.n_real ? launch_ga_vary_mixed(s.X[s.cur], s.rank, s.cd, s.g, s.n_real, s.n_var - s.n_real, generation, 0, pop, GA_VARY_REAL, s.Xoff, e->cur)
+                                   : launch_ga_vary(s.X[s.cur], s.rank, s.cd, s.g, s.n_var, generation, 0, pop, s.Xoff, e->cur);
         if (k) pr.ran("search.vary", k);
         else { pr.drop(); e->launch_error = "search.vary: the launcher refused the shape"; }
     }
     if (s.n_real) {      // mixed rows: HUX and bit-flip on the bit columns behind the real ones
         Prof pr(e, "search.vary_bits", 0, 3 * xbytes * (1.0 - real_share));
-        const char* k = launch_ga_vary_mixed(s.X[s.cur], s.rank, s.cd, s.g, s.n_real, s.n_var - s.n_real, generation, 0, pop, GA_VARY_BITS, s.Xoff, e->cur);
+        const char* k = K ? launch_ga_vary_islands(s.X[s.cur], s.rank, s.cd, s.g, K, n_real, s.n_var - n_real, generation, GA_VARY_BITS, s.Xoff, e->cur)
+                          : launch_ga_vary_mixed(s.X[s.cur], s.rank, s.cd, s.g, s.n_real, s.n_var - s.n_real, generation, 0, pop, GA_VARY_BITS, s.Xoff, e->cur);
         if (k) pr.ran("search.vary_bits", k);
         else { pr.drop(); e->launch_error = "search.vary_bits: the launcher refused the shape"; }
     }
     {
         Prof pr(e, "search.duplicates", 0, 2 * xbytes);
-        const char* k = launch_ga_duplicates(s.X[s.cur], s.Xoff, pop, pop, s.n_var, s.flags, e->cur);
+        const char* k = K ? launch_ga_duplicates_islands(s.X[s.cur], s.Xoff, K, pop, s.n_var, s.flags, e->cur)
+                          : launch_ga_duplicates(s.X[s.cur], s.Xoff, pop, pop, s.n_var, s.flags, e->cur);
         if (k) pr.ran("search.duplicates", k);
         else { pr.drop(); e->launch_error = "search.duplicates: the launcher refused the shape"; }
     }
@@ -188,17 +267,62 @@ void launch_vary(glass_engine* e, int generation) {
 }
 void launch_survive(glass_engine* e, int n_off) {
     glass_engine::Search& s = e->search;
-    const int pop = s.g.pop;
-    Prof pr(e, "search.survive", 0, 2.0 * pop * s.n_var * sizeof(float));
-    const char* k = launch_ga_survive(s.F, n_off ? s.flags : nullptr, pop, n_off, e->cfg.n_obj, pop, s.nsga, s.chosen, s.rank, s.cd, s.counts, e->cur);
+    const int pop = s.g.pop, K = s.islands, M = e->cfg.n_obj;
+    Prof pr(e, "search.survive", 0, 2.0 * s.rows() * s.n_var * sizeof(float));
+    const char* k = K ? launch_ga_survive_islands(s.F, s.F + (size_t)s.rows() * M, s.flags, K, pop, n_off, M, s.nsga, 0, s.chosen, s.rank, s.cd, s.counts, e->cur)
+                      : launch_ga_survive(s.F, n_off ? s.flags : nullptr, pop, n_off, M, pop, s.nsga, s.chosen, s.rank, s.cd, s.counts, e->cur);
     if (!k) {
         pr.drop();
         e->launch_error = "search.survive: the launcher refused the shape (or the device offers too little LDS)";
         return;
     }
     pr.ran("search.survive", k);
-    launch_ga_gather(s.X[s.cur], s.Xoff, s.chosen, pop, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
+    if (K) launch_ga_gather_islands(s.X[s.cur], s.Xoff, s.chosen, K, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
+    else launch_ga_gather(s.X[s.cur], s.Xoff, s.chosen, pop, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
     s.cur ^= 1;
+}
+// whether the rule has a migration behind the survival of this generation
+bool migration_due(const glass_engine::Search& s, int generation) {
+    return s.islands > 1 && s.migrate_every > 0 && generation >= 1 && generation % s.migrate_every == 0;
+}
+// migration in place, then the islands that accepted a row ranked (and ordered) again as search_init ranks a population
+void launch_migrate(glass_engine* e) {
+    glass_engine::Search& s = e->search;
+    const int pop = s.g.pop, K = s.islands, M = e->cfg.n_obj;
+    {
+        Prof pr(e, "search.migrate", 0, 2.0 * K * s.migrants * s.n_var * sizeof(float));
+        const char* k = launch_ga_migrate(s.X[s.cur], s.F, s.rank, s.cd, K, pop, s.n_var, M, s.migrants, s.counts, e->cur);
+        if (!k) {
+            pr.drop();
+            e->launch_error = "search.migrate: the launcher refused the shape";
+            return;
+        }
+        pr.ran("search.migrate", k);
+    }
+    Prof pr(e, "search.rerank", 0, 2.0 * s.rows() * s.n_var * sizeof(float));
+    const char* k = launch_ga_survive_islands(s.F, nullptr, nullptr, K, pop, 0, M, s.nsga, 1, s.chosen, s.rank, s.cd, s.counts, e->cur);
+    if (!k) {
+        pr.drop();
+        e->launch_error = "search.rerank: the launcher refused the shape (or the device offers too little LDS)";
+        return;
+    }
+    pr.ran("search.rerank", k);
+    launch_ga_gather_islands(s.X[s.cur], nullptr, s.chosen, K, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
+    s.cur ^= 1;
+}
+// a scoring pass of search rows [first_row, first_row + P): with islands the noise planes are those of the minibatch's index within its island
+int search_pass(glass_engine* e, int P, int generation, int first_row, const float* d_rows, float* d_F, bool no_wait) {
+    const glass_engine::Search& s = e->search;
+    if (s.own_prompts)
+        REQUIRE(e->pset.T == e->pset.isl_T && e->pset.mode == 0 && !e->edit.has_source, GLASS_ERR_STATE,
+                "device search islands: the islands' own weights were set for a prompt set of " + std::to_string(e->pset.isl_T) +
+                    " entries in mode sum without a direction source, and the engine's targets have changed: set_island_weights again");
+    e->noise_period = s.islands ? s.g.pop / e->cfg.batch_size : 0;
+    e->island_row0 = s.islands ? first_row : -1;
+    const int rc = run_pass(e, nullptr, P, generation, first_row / e->cfg.batch_size, nullptr, nullptr, nullptr, d_rows, d_F, no_wait);
+    e->noise_period = 0;
+    e->island_row0 = -1;
+    return rc;
 }
 }  // namespace
 // the wait behind launches made outside a pass
@@ -214,12 +338,26 @@ int search_wait(glass_engine* e) {
     }
     return GLASS_OK;
 }
+// counts [2] = {flagged, non-finite} rows of the last survival (islands: summed over them); per_island [islands][3] nullable
+static int read_counts(glass_engine* e, int* counts, int* per_island) {
+    const glass_engine::Search& s = e->search;
+    if (!s.islands) {
+        GLASS_HIP(hipMemcpy(counts, s.counts, 2 * sizeof(int), hipMemcpyDeviceToHost));
+        return GLASS_OK;
+    }
+    int h[3 * GLASS_SEARCH_MAX_ISLANDS];
+    GLASS_HIP(hipMemcpy(h, s.counts, (size_t)3 * s.islands * sizeof(int), hipMemcpyDeviceToHost));
+    if (counts) counts[0] = counts[1] = 0;
+    for (int i = 0; i < s.islands && counts; ++i) { counts[0] += h[3 * i]; counts[1] += h[3 * i + 1]; }
+    if (per_island) memcpy(per_island, h, (size_t)3 * s.islands * sizeof(int));
+    return GLASS_OK;
+}
 namespace {
 int check_rows(glass_engine* e, const char* what, int generation, int first_row, int rows) {
     const glass_engine::Search& s = e->search;
     REQUIRE(s.varied_gen == generation, GLASS_ERR_STATE,
             std::string(what) + ": the offspring buffer holds generation " + std::to_string(s.varied_gen) + " (search_vary of this generation first)");
-    REQUIRE(rows > 0 && first_row >= 0 && first_row + rows <= s.g.pop && first_row % e->cfg.batch_size == 0 && rows % e->cfg.batch_size == 0,
+    REQUIRE(rows > 0 && first_row >= 0 && first_row + rows <= s.rows() && first_row % e->cfg.batch_size == 0 && rows % e->cfg.batch_size == 0,
             GLASS_ERR_ARG, std::string(what) + ": [first_row, first_row + rows) must be whole minibatches inside the offspring rows");
     return GLASS_OK;
 }
@@ -231,10 +369,10 @@ extern "C" int glass_engine_search_init(glass_engine* e, const float* X0) {
     REQUIRE(!e->search.cma, GLASS_ERR_STATE,
             "search_init: a cmaes search keeps a distribution, not a population: search_init_cma(mean, diag, sigma)");
     glass_engine::Search& s = e->search;
-    const int pop = s.g.pop;
+    const int pop = s.rows();      // (islands: every island's rows, island-major)
     s.ready = false;
     s.cur = 0;
-    s.varied_gen = -1;
+    s.varied_gen = s.survived_gen = -1;
     if (s.n_real)      // mixed rows: a bit column holds exactly 0.0 or 1.0
         for (int r = 0; r < pop; ++r)
             for (int j = s.n_real; j < s.n_var; ++j) {
@@ -244,11 +382,11 @@ extern "C" int glass_engine_search_init(glass_engine* e, const float* X0) {
                             " (a bit is exactly 0.0 or 1.0)");
             }
     GLASS_HIP(hipMemcpy(s.X[0], X0, (size_t)pop * s.n_var * sizeof(float), hipMemcpyHostToDevice));
-    if (int rc = run_pass(e, nullptr, pop, 0, 0, nullptr, nullptr, nullptr, s.X[0], s.F, true)) return rc;
+    if (int rc = search_pass(e, pop, 0, 0, s.X[0], s.F, true)) return rc;
     launch_survive(e, 0);      // ranks (and orders) the initial population, as minimize's first survive() does
     if (int rc = wait_pass(e, pop)) return rc;
     int counts[2];
-    GLASS_HIP(hipMemcpy(counts, s.counts, sizeof counts, hipMemcpyDeviceToHost));
+    if (int rc = read_counts(e, counts, nullptr)) return rc;
     REQUIRE(counts[1] == 0, GLASS_ERR_STATE,
             "search_init: " + std::to_string(counts[1]) + " rows of the initial population have a non-finite F: a population row is never left out");
     s.ready = true;
@@ -267,8 +405,7 @@ extern "C" int glass_engine_search_evaluate(glass_engine* e, int32_t generation,
     if (int rc = search_ready(e, "search_evaluate", true)) return rc;
     if (int rc = check_rows(e, "search_evaluate", generation, first_row, rows)) return rc;
     glass_engine::Search& s = e->search;
-    return run_pass(e, nullptr, rows, generation, first_row / e->cfg.batch_size, nullptr, nullptr, nullptr, s.Xoff + (size_t)first_row * s.n_var,
-                    s.F + (size_t)(s.g.pop + first_row) * e->cfg.n_obj, false);
+    return search_pass(e, rows, generation, first_row, s.Xoff + (size_t)first_row * s.n_var, s.F + (size_t)(s.rows() + first_row) * e->cfg.n_obj, false);
 }
 
 extern "C" int glass_engine_search_survive(glass_engine* e, int32_t generation) {
@@ -278,6 +415,20 @@ extern "C" int glass_engine_search_survive(glass_engine* e, int32_t generation) 
     e->launch_error.clear();
     launch_survive(e, e->search.g.pop);
     e->search.varied_gen = -1;      // the offspring are spent: the next survival needs a new search_vary
+    e->search.survived_gen = generation;
+    return search_wait(e);
+}
+
+extern "C" int glass_engine_search_migrate(glass_engine* e, int32_t generation) {
+    if (int rc = search_ready(e, "search_migrate", true)) return rc;
+    glass_engine::Search& s = e->search;
+    REQUIRE(s.islands >= 1, GLASS_ERR_STATE, "search_migrate: this search has no islands (glass_engine_set_search_islands before finalize)");
+    REQUIRE(s.survived_gen == generation, GLASS_ERR_STATE,
+            "search_migrate: search_survive of this generation first (migration follows a generation's survival, once)");
+    s.survived_gen = -1;
+    if (!migration_due(s, generation)) return GLASS_OK;
+    e->launch_error.clear();
+    launch_migrate(e);
     return search_wait(e);
 }
 
@@ -285,14 +436,15 @@ extern "C" int glass_engine_search_step(glass_engine* e, int32_t generation) {
     if (int rc = search_ready(e, "search_step", true)) return rc;
     if (e->search.cma) return cma_step(e, generation);
     glass_engine::Search& s = e->search;
-    const int pop = s.g.pop;
+    const int pop = s.rows();
     e->launch_error.clear();
     launch_vary(e, generation);
     const std::string refused = e->launch_error;      // (run_pass clears the message on entry)
-    if (int rc = run_pass(e, nullptr, pop, generation, 0, nullptr, nullptr, nullptr, s.Xoff, s.F + (size_t)pop * e->cfg.n_obj, true)) return rc;
+    if (int rc = search_pass(e, pop, generation, 0, s.Xoff, s.F + (size_t)pop * e->cfg.n_obj, true)) return rc;
     if (!refused.empty()) e->launch_error = refused;
-    launch_survive(e, pop);
-    s.varied_gen = -1;
+    launch_survive(e, s.g.pop);
+    s.varied_gen = s.survived_gen = -1;
+    if (migration_due(s, generation) && e->launch_error.empty()) launch_migrate(e);
     return wait_pass(e, pop);
 }
 
@@ -302,7 +454,7 @@ extern "C" int glass_engine_search_read(glass_engine* e, float* pop_X, float* po
     const glass_engine::Search& s = e->search;
     REQUIRE(!s.cma || !(pop_X || pop_F || rank || cd || flags), GLASS_ERR_STATE,
             "search_read: a cmaes search has no population, ranks, distances or flags: its rows are off_X / off_F, its state search_read_cma");
-    const size_t pop = (size_t)s.g.pop, xb = pop * s.n_var * sizeof(float), fb = pop * e->cfg.n_obj * sizeof(float);
+    const size_t pop = (size_t)s.rows(), xb = pop * s.n_var * sizeof(float), fb = pop * e->cfg.n_obj * sizeof(float);
     GLASS_HIP(hipStreamSynchronize(e->stream));
     if (pop_X) GLASS_HIP(hipMemcpy(pop_X, s.X[s.cur], xb, hipMemcpyDeviceToHost));
     if (pop_F) GLASS_HIP(hipMemcpy(pop_F, s.F, fb, hipMemcpyDeviceToHost));
@@ -311,8 +463,17 @@ extern "C" int glass_engine_search_read(glass_engine* e, float* pop_X, float* po
     if (off_X) GLASS_HIP(hipMemcpy(off_X, s.Xoff, xb, hipMemcpyDeviceToHost));
     if (off_F) GLASS_HIP(hipMemcpy(off_F, s.F + pop * e->cfg.n_obj, fb, hipMemcpyDeviceToHost));
     if (flags) GLASS_HIP(hipMemcpy(flags, s.flags, pop * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (counts) GLASS_HIP(hipMemcpy(counts, s.counts, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (counts)
+        if (int rc = read_counts(e, counts, nullptr)) return rc;
     return GLASS_OK;
+}
+
+extern "C" int glass_engine_search_read_islands(glass_engine* e, int32_t* counts) {
+    if (int rc = search_ready(e, "search_read_islands", true)) return rc;
+    REQUIRE(e->search.islands >= 1, GLASS_ERR_STATE, "search_read_islands: this search has no islands (glass_engine_set_search_islands before finalize)");
+    REQUIRE(counts, GLASS_ERR_ARG, "search_read_islands: null counts");
+    GLASS_HIP(hipStreamSynchronize(e->stream));
+    return read_counts(e, nullptr, counts);
 }
 
 extern "C" int glass_engine_latent_uploads(glass_engine* e, int64_t* calls, int64_t* rows) {

@@ -76,9 +76,9 @@ __device__ float ga_vary_one(const GaParams& g, float paf, float pbf, int m, int
 // == 0 and stride % 4 == 0 (every row is then 16-byte aligned), 1 otherwise.  Nothing depends on the grid: a draw is a function of (seed,
 // generation, row, variable).
 template <int VEC>
-__global__ __launch_bounds__(256) void ga_vary_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
-                                                      GaParams g, int n_var, int stride, int generation, int row0, float* __restrict__ Xoff) {
-    const int r = row0 + blockIdx.y, m = r >> 1;
+__device__ __forceinline__ void ga_vary_row(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd, const GaParams& g,
+                                            int n_var, int stride, int generation, int r, float* __restrict__ Xoff) {
+    const int m = r >> 1;
     const int j0 = (blockIdx.x * 256 + threadIdx.x) * VEC;
     if (j0 >= n_var) return;
     int ia, ib;
@@ -96,38 +96,68 @@ __global__ __launch_bounds__(256) void ga_vary_kernel(const float* __restrict__ 
         out[0] = ga_vary_one(g, pa[0], pb[0], m, r, j0, (uint32_t)generation);
     }
 }
+template <int VEC>
+__global__ __launch_bounds__(256) void ga_vary_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
+                                                      GaParams g, int n_var, int stride, int generation, int row0, float* __restrict__ Xoff) {
+    ga_vary_row<VEC>(X, rank, cd, g, n_var, stride, generation, row0 + blockIdx.y, Xoff);
+}
+// The island form (include/glass.h "Device search: islands"), grid (ceil(n_var / (256 VEC)), pop, islands): island i = blockIdx.z is the
+// kernel above on rows [i pop, (i + 1) pop) of every buffer under seed + i; every index inside is local to the island.
+template <int VEC>
+__global__ __launch_bounds__(256) void ga_vary_islands_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
+                                                              GaParams g, int n_var, int stride, int generation, float* __restrict__ Xoff) {
+    const size_t o = (size_t)blockIdx.z * g.pop;
+    g.seed += (uint64_t)blockIdx.z;
+    ga_vary_row<VEC>(X + o * stride, rank + o, cd + o, g, n_var, stride, generation, blockIdx.y, Xoff + o * stride);
+}
 
 // One workgroup per offspring row r; its four waves walk the candidate rows (the population, then offspring rows BELOW r — "earlier" is the
 // row index, whatever the schedule).  A pair is compared 64 VEC variables at a time and left at the first chunk that differs, which for
 // unrelated rows is the first: the whole of both rows is read only for a pair that is equal.  Equality is by value (-0.0 == 0.0).
+// whether row a equals, by value in every variable, row b: the whole wave compares 64 VEC variables at a time and leaves at the first chunk
+// that differs (uniform over the wave)
 template <int VEC>
-__global__ __launch_bounds__(256) void ga_duplicates_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, int pop, int n_var,
-                                                            int* __restrict__ flags) {
+__device__ __forceinline__ bool ga_rows_equal(const float* __restrict__ a, const float* __restrict__ b, int n_var, int lane) {
+    bool eq = true;
+    for (int j0 = 0; j0 < n_var && eq; j0 += 64 * VEC) {
+        const int j = j0 + lane * VEC;
+        bool ne = false;
+        if (j < n_var) {
+            if (VEC == 4) {
+                const f4 va = *(const f4*)(a + j), vb = *(const f4*)(b + j);
+                ne = !(va[0] == vb[0] && va[1] == vb[1] && va[2] == vb[2] && va[3] == vb[3]);
+            } else {
+                ne = !(a[j] == b[j]);
+            }
+        }
+        eq = __ballot(ne) == 0ull;
+    }
+    return eq;
+}
+template <int VEC>
+__device__ __forceinline__ void ga_duplicates_row(const float* __restrict__ X, const float* __restrict__ Xoff, int pop, int n_var, int r,
+                                                  int* __restrict__ flags) {
     __shared__ int hit[4];
-    const int r = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float* a = Xoff + (size_t)r * n_var;
     bool found = false;
-    for (int c = wave; c < pop + r && !found; c += 4) {
-        const float* b = c < pop ? X + (size_t)c * n_var : Xoff + (size_t)(c - pop) * n_var;
-        bool eq = true;
-        for (int j0 = 0; j0 < n_var && eq; j0 += 64 * VEC) {
-            const int j = j0 + lane * VEC;
-            bool ne = false;
-            if (j < n_var) {
-                if (VEC == 4) {
-                    const f4 va = *(const f4*)(a + j), vb = *(const f4*)(b + j);
-                    ne = !(va[0] == vb[0] && va[1] == vb[1] && va[2] == vb[2] && va[3] == vb[3]);
-                } else {
-                    ne = !(a[j] == b[j]);
-                }
-            }
-            eq = __ballot(ne) == 0ull;
-        }
-        found = eq;
-    }
+    for (int c = wave; c < pop + r && !found; c += 4)
+        found = ga_rows_equal<VEC>(a, c < pop ? X + (size_t)c * n_var : Xoff + (size_t)(c - pop) * n_var, n_var, lane);
     if (lane == 0) hit[wave] = found ? 1 : 0;
     __syncthreads();
     if (threadIdx.x == 0) flags[r] = hit[0] | hit[1] | hit[2] | hit[3];
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void ga_duplicates_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, int pop, int n_var,
+                                                            int* __restrict__ flags) {
+    ga_duplicates_row<VEC>(X, Xoff, pop, n_var, blockIdx.x, flags);
+}
+// the island form, grid (pop, islands): an offspring row is compared with its own island's rows only
+template <int VEC>
+__global__ __launch_bounds__(256) void ga_duplicates_islands_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, int pop, int n_var,
+                                                                    int* __restrict__ flags) {
+    const size_t o = (size_t)blockIdx.y * pop;
+    ga_duplicates_row<VEC>(X + o * n_var, Xoff + o * n_var, pop, n_var, blockIdx.x, flags + o);
 }
 
 // ---- survival: one workgroup, everything in LDS -------------------------------------------------------------------------------
@@ -163,13 +193,13 @@ __host__ __device__ inline int ga_pow2(int n) { int p = 2; while (p < n) p <<= 1
 // alone.  The differing columns D go to LDS as (key << 32 | column) in whatever order the atomics give — only the keys' ranks matter —
 // padded to a power of two and sorted; the first (|D| + 1) >> 1 of them are exchanged.  LDS holds the worst case (|D| = n_bits <=
 // GLASS_SEARCH_MAX_BITS), the sort runs over the actual |D|.
-__global__ __launch_bounds__(256) void ga_vary_bits_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
-                                                           GaParams g, int n_real, int n_bits, int generation, int row0, float* __restrict__ Xoff) {
+__device__ __forceinline__ void ga_vary_bits_row(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
+                                                 const GaParams& g, int n_real, int n_bits, int generation, int r, float* __restrict__ Xoff) {
 #pragma clang fp contract(off)
     __shared__ unsigned long long keys[GLASS_SEARCH_MAX_BITS];
     __shared__ unsigned char xchg[GLASS_SEARCH_MAX_BITS];
     __shared__ int s_n;
-    const int r = row0 + blockIdx.x, m = r >> 1, child = r & 1, stride = n_real + n_bits, tid = threadIdx.x;
+    const int m = r >> 1, child = r & 1, stride = n_real + n_bits, tid = threadIdx.x;
     int ia, ib;
     ga_parents(g, rank, cd, m, (uint32_t)generation, &ia, &ib);
     const float* A = X + (size_t)ia * stride + n_real;
@@ -203,13 +233,26 @@ __global__ __launch_bounds__(256) void ga_vary_bits_kernel(const float* __restri
         out[j] = x;
     }
 }
+__global__ __launch_bounds__(256) void ga_vary_bits_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
+                                                           GaParams g, int n_real, int n_bits, int generation, int row0, float* __restrict__ Xoff) {
+    ga_vary_bits_row(X, rank, cd, g, n_real, n_bits, generation, row0 + blockIdx.x, Xoff);
+}
+// the island form, grid (pop, islands): local rows and matings under seed + island
+__global__ __launch_bounds__(256) void ga_vary_bits_islands_kernel(const float* __restrict__ X, const int* __restrict__ rank,
+                                                                   const double* __restrict__ cd, GaParams g, int n_real, int n_bits, int generation,
+                                                                   float* __restrict__ Xoff) {
+    const size_t o = (size_t)blockIdx.y * g.pop, stride = (size_t)(n_real + n_bits);
+    g.seed += (uint64_t)blockIdx.y;
+    ga_vary_bits_row(X + o * stride, rank + o, cd + o, g, n_real, n_bits, generation, blockIdx.x, Xoff + o * stride);
+}
 
-// F [n_pop + n_off][M]: the population's rows, then the offspring's.  Left out of survival: offspring rows with a flag or a non-finite F.
-// Out: chosen [pop_out] merged indices in survival order (-1: fewer rows than pop_out were eligible), their rank and distance, and F's
-// first pop_out rows rewritten as the survivors' (the kernel has read all of F before it writes).  counts = {flagged, non-finite rows}.
-__global__ __launch_bounds__(1024) void ga_survive_kernel(float* __restrict__ F, const int* __restrict__ flags, int n_pop, int n_off, int M,
-                                                          int pop_out, int nsga, int* __restrict__ chosen, int* __restrict__ rank_out,
-                                                          double* __restrict__ cd_out, int* __restrict__ counts) {
+// The merged rows are Fpop [n_pop][M], the population's, then Foff [n_off][M], the offspring's.  Left out of survival: offspring rows with a
+// flag or a non-finite F.  Out: chosen [pop_out] merged indices in survival order (-1: fewer rows than pop_out were eligible), their rank
+// and distance, and Fout's first pop_out rows written as the survivors' (Fout may be Fpop: the workgroup has read every F before it
+// writes).  counts = {flagged, non-finite rows} (nullable).
+__device__ __forceinline__ void ga_survive_rows(const float* Fpop, const float* Foff, float* Fout, const int* __restrict__ flags, int n_pop, int n_off,
+                                                int M, int pop_out, int nsga, int* __restrict__ chosen, int* __restrict__ rank_out,
+                                                double* __restrict__ cd_out, int* __restrict__ counts) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_ncur, s_cnt[2];
     const int N = n_pop + n_off, N2 = ga_pow2(N), T = blockDim.x, tid = threadIdx.x;
@@ -220,7 +263,7 @@ __global__ __launch_bounds__(1024) void ga_survive_kernel(float* __restrict__ F,
     int* nd = rk + N;                                            // [N]: rows that dominate it and are not ranked yet
     int* cur = nd + N;                                           // [N]: the current front; later the survivors by slot
     int* seg = cur + N;                                          // [N + 2]: first sorted position of every front
-    for (int i = tid; i < N * M; i += T) Fs[i] = F[i];
+    for (int i = tid; i < N * M; i += T) Fs[i] = i < n_pop * M ? Fpop[i] : Foff[i - n_pop * M];
     if (tid == 0) s_cnt[0] = s_cnt[1] = 0;
     __syncthreads();
     for (int i = tid; i < N; i += T) {
@@ -326,9 +369,32 @@ __global__ __launch_bounds__(1024) void ga_survive_kernel(float* __restrict__ F,
         rank_out[s] = i >= 0 ? rk[i] : -1;
         cd_out[s] = i >= 0 ? cd[i] : 0.0;
         if (i >= 0)
-            for (int k = 0; k < M; ++k) F[s * M + k] = Fs[i * M + k];
+            for (int k = 0; k < M; ++k) Fout[s * M + k] = Fs[i * M + k];
     }
-    if (tid == 0) { counts[0] = s_cnt[0]; counts[1] = s_cnt[1]; }
+    if (tid == 0 && counts) { counts[0] = s_cnt[0]; counts[1] = s_cnt[1]; }
+}
+// F [n_pop + n_off][M]: the population's rows, then the offspring's, in one plane; F's first pop_out rows are rewritten as the survivors'
+__global__ __launch_bounds__(1024) void ga_survive_kernel(float* __restrict__ F, const int* __restrict__ flags, int n_pop, int n_off, int M,
+                                                          int pop_out, int nsga, int* __restrict__ chosen, int* __restrict__ rank_out,
+                                                          double* __restrict__ cd_out, int* __restrict__ counts) {
+    ga_survive_rows(F, F + (size_t)n_pop * M, F, flags, n_pop, n_off, M, pop_out, nsga, chosen, rank_out, cd_out, counts);
+}
+// The island form, one workgroup per island: island i ranks its pop population rows of F with its n_off (pop or 0) offspring rows of Foff —
+// two planes, the pass writes the islands' offspring F contiguously — and rewrites its rows of F, chosen, rank and cd; the algorithm and
+// the LDS layout are the kernel's above.  counts [islands][3] = {flagged, non-finite, migrants accepted}.  gated (the ranking behind a
+// migration, n_off 0): an island that accepted no migrant keeps every bit of its state — ranking a population again would reorder a cut
+// last front — and gets the identity for the gather; the first two counters stay the generation's.
+__global__ __launch_bounds__(1024) void ga_survive_islands_kernel(float* __restrict__ F, const float* __restrict__ Foff, const int* __restrict__ flags,
+                                                                  int pop, int n_off, int M, int nsga, int gated, int* __restrict__ chosen,
+                                                                  int* __restrict__ rank_out, double* __restrict__ cd_out, int* __restrict__ counts) {
+    const size_t o = (size_t)blockIdx.x * pop;
+    int* cnt = counts + blockIdx.x * 3;
+    if (gated && cnt[2] == 0) {      // (uniform over the workgroup, ahead of every barrier)
+        for (int s = threadIdx.x; s < pop; s += blockDim.x) chosen[o + s] = s;
+        return;
+    }
+    ga_survive_rows(F + o * M, n_off ? Foff + o * M : nullptr, F + o * M, n_off ? flags + o : nullptr, pop, n_off, M, pop, nsga, chosen + o, rank_out + o,
+                    cd_out + o, gated ? nullptr : cnt);
 }
 
 // Xnext[s] = the merged row chosen[s] of (X ; Xoff).  grid (ceil(n_var / (256 VEC)), pop_out)
@@ -341,6 +407,88 @@ __global__ __launch_bounds__(256) void ga_gather_kernel(const float* __restrict_
     float* dst = Xnext + (size_t)s * n_var + j0;
     if (VEC == 4) *(f4*)dst = *(const f4*)src;
     else dst[0] = src[0];
+}
+// the island form, grid (ceil(n_var / (256 VEC)), pop, islands): chosen holds island-local merged indices
+template <int VEC>
+__global__ __launch_bounds__(256) void ga_gather_islands_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, const int* __restrict__ chosen,
+                                                                int pop, int n_var, float* __restrict__ Xnext) {
+    const size_t o = (size_t)blockIdx.z * pop;
+    const int s = blockIdx.y, j0 = (blockIdx.x * 256 + threadIdx.x) * VEC, i = chosen[o + s];
+    if (j0 >= n_var || i < 0) return;
+    const float* src = (i < pop ? X + (o + i) * n_var : Xoff + (o + i - pop) * n_var) + j0;
+    float* dst = Xnext + (o + s) * n_var + j0;
+    if (VEC == 4) *(f4*)dst = *(const f4*)src;
+    else dst[0] = src[0];
+}
+
+// ---- migration (include/glass.h "Device search: islands") -----------------------------------------------------------------------
+// position of row a in the tournament's order (rank, -cd, index) of an island whose rank / cd lie in LDS
+__device__ __forceinline__ int ga_order_pos(const int* rk, const double* cd, int pop, int a) {
+    const int ra = rk[a];
+    const double ca = cd[a];
+    int c = 0;
+    for (int b = 0; b < pop; ++b) {
+        const int rb = rk[b];
+        const double cb = cd[b];
+        c += (rb < ra || (rb == ra && (cb > ca || (cb == ca && b < a)))) ? 1 : 0;
+    }
+    return c;
+}
+// One workgroup per RECEIVING island i; its source is island (i - 1 + K) mod K.  Candidate k is the source's k-th best row and is aimed at
+// the receiver's k-th worst.  Sixteen waves walk the candidates; a candidate is compared (ga_rows_equal) with the receiver's pop rows and
+// with the candidates below k, and only then — behind a barrier — are the accepted rows and their F copied.  With n <= pop / 2 the rows a
+// workgroup writes (its island's n worst) are never rows another workgroup reads (that island's n best, and only the receiver reads the
+// rest), so every source is read as survival left it whatever the schedule.  counts[i][2] = accepted migrants.
+template <int VEC>
+__global__ __launch_bounds__(1024) void ga_migrate_kernel(float* X, float* F, const int* __restrict__ rank,
+                                                          const double* __restrict__ cd, int K, int pop, int n_var, int M, int n,
+                                                          int* __restrict__ counts) {
+    __shared__ double s_cd[GLASS_SEARCH_MAX_POP];
+    __shared__ int s_rk[GLASS_SEARCH_MAX_POP];
+    __shared__ int s_src[GLASS_SEARCH_MAX_POP / 2], s_dst[GLASS_SEARCH_MAX_POP / 2];
+    __shared__ int s_ok[GLASS_SEARCH_MAX_POP / 2];
+    const int isl = blockIdx.x, from = (isl - 1 + K) % K, tid = threadIdx.x, T = blockDim.x;
+    const size_t o_to = (size_t)isl * pop, o_from = (size_t)from * pop;
+    // the source's n best rows
+    for (int a = tid; a < pop; a += T) { s_rk[a] = rank[o_from + a]; s_cd[a] = cd[o_from + a]; }
+    __syncthreads();
+    for (int a = tid; a < pop; a += T) {
+        const int p = ga_order_pos(s_rk, s_cd, pop, a);
+        if (p < n) s_src[p] = a;
+    }
+    __syncthreads();
+    // the receiver's n worst rows, worst first
+    for (int a = tid; a < pop; a += T) { s_rk[a] = rank[o_to + a]; s_cd[a] = cd[o_to + a]; }
+    __syncthreads();
+    for (int a = tid; a < pop; a += T) {
+        const int p = pop - 1 - ga_order_pos(s_rk, s_cd, pop, a);
+        if (p < n) s_dst[p] = a;
+    }
+    __syncthreads();
+    const float* Xs = X + o_from * n_var;
+    float* Xr = X + o_to * n_var;
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int k = wave; k < n; k += (T >> 6)) {
+        const float* a = Xs + (size_t)s_src[k] * n_var;
+        bool found = false;
+        for (int c = 0; c < pop + k && !found; ++c)
+            found = ga_rows_equal<VEC>(a, c < pop ? Xr + (size_t)c * n_var : Xs + (size_t)s_src[c - pop] * n_var, n_var, lane);
+        if (lane == 0) s_ok[k] = found ? 0 : 1;
+    }
+    __syncthreads();
+    int accepted = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!s_ok[k]) continue;
+        ++accepted;
+        const float* src = Xs + (size_t)s_src[k] * n_var;
+        float* dst = Xr + (size_t)s_dst[k] * n_var;
+        for (int j = tid * VEC; j < n_var; j += T * VEC) {
+            if (VEC == 4) *(f4*)(dst + j) = *(const f4*)(src + j);
+            else dst[j] = src[j];
+        }
+        if (tid < M) F[(o_to + s_dst[k]) * M + tid] = F[(o_from + s_src[k]) * M + tid];
+    }
+    if (tid == 0) counts[isl * 3 + 2] = accepted;
 }
 }  // namespace
 
@@ -412,4 +560,77 @@ void launch_ga_gather(const float* X, const float* Xoff, const int* chosen, int 
         hipLaunchKernelGGL(ga_gather_kernel<4>, dim3((n_var / 4 + 255) / 256, pop_out), dim3(256), 0, st, X, Xoff, chosen, n_pop, n_var, Xnext);
     else
         hipLaunchKernelGGL(ga_gather_kernel<1>, dim3((n_var + 255) / 256, pop_out), dim3(256), 0, st, X, Xoff, chosen, n_pop, n_var, Xnext);
+}
+
+// ---- the island forms (include/glass.h "Device search: islands"): nullptr / false where the shape is outside the limits ----
+static bool ga_islands_ok(int islands, int pop, int n_var) {
+    return islands >= 1 && islands <= GLASS_SEARCH_MAX_ISLANDS && pop >= 2 && pop <= GLASS_SEARCH_MAX_POP && n_var >= 1 &&
+           (long long)islands * pop * n_var < (1LL << 31);
+}
+
+const char* launch_ga_vary_islands(const float* X, const int* rank, const double* cd, const GaParams& g, int islands, int n_real, int n_bits,
+                                   int generation, int parts, float* Xoff, hipStream_t st) {
+    const int stride = n_real + n_bits;
+    if (!ga_islands_ok(islands, g.pop, stride) || n_real < 1 || n_bits < 0 || n_bits > GLASS_SEARCH_MAX_BITS || !(parts & GA_VARY_BOTH)) return nullptr;
+    if ((parts & GA_VARY_BITS) && n_bits < 1) return nullptr;
+    const bool v4 = n_real % 4 == 0 && stride % 4 == 0;
+    if (parts & GA_VARY_REAL) {
+        if (v4)
+            hipLaunchKernelGGL(ga_vary_islands_kernel<4>, dim3((n_real / 4 + 255) / 256, g.pop, islands), dim3(256), 0, st, X, rank, cd, g, n_real, stride,
+                               generation, Xoff);
+        else
+            hipLaunchKernelGGL(ga_vary_islands_kernel<1>, dim3((n_real + 255) / 256, g.pop, islands), dim3(256), 0, st, X, rank, cd, g, n_real, stride,
+                               generation, Xoff);
+    }
+    if (parts & GA_VARY_BITS)
+        hipLaunchKernelGGL(ga_vary_bits_islands_kernel, dim3(g.pop, islands), dim3(256), 0, st, X, rank, cd, g, n_real, n_bits, generation, Xoff);
+    if (!(parts & GA_VARY_BITS)) return v4 ? "ga_vary_islands_kernel<4>" : "ga_vary_islands_kernel<1>";
+    if (!(parts & GA_VARY_REAL)) return "ga_vary_bits_islands_kernel";
+    return v4 ? "ga_vary_islands_kernel<4> + ga_vary_bits_islands_kernel" : "ga_vary_islands_kernel<1> + ga_vary_bits_islands_kernel";
+}
+
+const char* launch_ga_duplicates_islands(const float* X, const float* Xoff, int islands, int pop, int n_var, int* flags, hipStream_t st) {
+    if (!ga_islands_ok(islands, pop, n_var)) return nullptr;
+    if (n_var % 4 == 0) {
+        hipLaunchKernelGGL(ga_duplicates_islands_kernel<4>, dim3(pop, islands), dim3(256), 0, st, X, Xoff, pop, n_var, flags);
+        return "ga_duplicates_islands_kernel<4>";
+    }
+    hipLaunchKernelGGL(ga_duplicates_islands_kernel<1>, dim3(pop, islands), dim3(256), 0, st, X, Xoff, pop, n_var, flags);
+    return "ga_duplicates_islands_kernel<1>";
+}
+
+const char* launch_ga_survive_islands(float* F, const float* Foff, const int* flags, int islands, int pop, int n_off, int n_obj, int nsga, int gated,
+                                      int* chosen, int* rank_out, double* cd_out, int* counts, hipStream_t st) {
+    if (!ga_islands_ok(islands, pop, 1) || (n_off != 0 && n_off != pop) || (n_off && !Foff) || n_obj < 1 || n_obj > GLASS_SEARCH_MAX_OBJ || (gated && n_off))
+        return nullptr;
+    const size_t lds = ga_survive_lds_bytes(pop + n_off, n_obj);
+    if (lds > 64 * 1024) {
+        if (!glass_lds_fits((int)lds)) return nullptr;
+        static DevOnce once;
+        once.run([&] {
+            (void)hipFuncSetAttribute((const void*)ga_survive_islands_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)ga_survive_lds_bytes(2 * GLASS_SEARCH_MAX_POP, GLASS_SEARCH_MAX_OBJ));
+        });
+    }
+    hipLaunchKernelGGL(ga_survive_islands_kernel, dim3(islands), dim3(1024), lds, st, F, Foff, flags, pop, n_off, n_obj, nsga, gated, chosen, rank_out,
+                       cd_out, counts);
+    return "ga_survive_islands_kernel";
+}
+
+void launch_ga_gather_islands(const float* X, const float* Xoff, const int* chosen, int islands, int pop, int n_var, float* Xnext, hipStream_t st) {
+    if (n_var % 4 == 0)
+        hipLaunchKernelGGL(ga_gather_islands_kernel<4>, dim3((n_var / 4 + 255) / 256, pop, islands), dim3(256), 0, st, X, Xoff, chosen, pop, n_var, Xnext);
+    else
+        hipLaunchKernelGGL(ga_gather_islands_kernel<1>, dim3((n_var + 255) / 256, pop, islands), dim3(256), 0, st, X, Xoff, chosen, pop, n_var, Xnext);
+}
+
+const char* launch_ga_migrate(float* X, float* F, const int* rank, const double* cd, int islands, int pop, int n_var, int n_obj, int migrants, int* counts,
+                              hipStream_t st) {
+    if (!ga_islands_ok(islands, pop, n_var) || islands < 2 || migrants < 1 || migrants > pop / 2 || n_obj < 1 || n_obj > GLASS_SEARCH_MAX_OBJ) return nullptr;
+    if (n_var % 4 == 0) {
+        hipLaunchKernelGGL(ga_migrate_kernel<4>, dim3(islands), dim3(1024), 0, st, X, F, rank, cd, islands, pop, n_var, n_obj, migrants, counts);
+        return "ga_migrate_kernel<4>";
+    }
+    hipLaunchKernelGGL(ga_migrate_kernel<1>, dim3(islands), dim3(1024), 0, st, X, F, rank, cd, islands, pop, n_var, n_obj, migrants, counts);
+    return "ga_migrate_kernel<1>";
 }

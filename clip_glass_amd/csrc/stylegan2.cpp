@@ -283,7 +283,7 @@ int upload_noise(glass_engine* e, int P, int generation, int first_mb, const gla
             const int hw = e->gconv[l].res_out * e->gconv[l].res_out;
             Prof pr(e, "noise", 0, (double)n_mb * hw * 4);
             launch_noise(e->d_noise[l], n_mb, hw, (uint32_t)l, (uint32_t)first_mb, (uint32_t)generation, c.noise_seed,
-                         e->cur);
+                         e->cur, (uint32_t)e->noise_period);
         }
     } else if (c.noise_mode == 2) {
         REQUIRE(noise && noise->planes, GLASS_ERR_ARG, "noise_mode 2 requires caller-provided noise planes");

@@ -142,6 +142,12 @@ def load_library(path=None):
         ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
         lib.glass_engine_search_init_cma.argtypes = [C.c_void_p, dp, dp, C.c_double]
         lib.glass_engine_search_read_cma.argtypes = [C.c_void_p, dp, dp, dp, dp, dp, ip, fp, fp]
+    if hasattr(lib, "glass_search_islands_supported"):  # (absent from older A/B builds loaded through GLASS_LIB)
+        lib.glass_search_islands_supported.argtypes = [C.c_int32] * 7
+        lib.glass_engine_set_search_islands.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        lib.glass_engine_set_island_weights.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32]
+        lib.glass_engine_search_migrate.argtypes = [C.c_void_p, C.c_int32]
+        lib.glass_engine_search_read_islands.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     lib.glass_engine_destroy.argtypes = [C.c_void_p]
     lib.glass_engine_destroy.restype = None
     lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
@@ -309,6 +315,21 @@ def search_supported(pop, n_var, n_obj, algorithm):
         return False, "device search: unknown algorithm %r (expected one of %s)" % (algorithm, ", ".join(SEARCH_ALGORITHMS))
     lib = load_library()
     rc = lib.glass_search_supported(int(pop), int(n_var), int(n_obj), SEARCH_ALGORITHMS[algorithm])
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
+SEARCH_MAX_ISLANDS = 64
+
+
+def search_islands_supported(islands, pop, n_var, n_obj, algorithm, migrate_every=0, migrants=1):
+    """(ok, message) for `islands` populations of `pop` rows each with ring migration of `migrants` rows every `migrate_every` generations
+    (0: never): the library's own rule (glass_search_islands_supported), the one glass_engine_set_search_islands and finalize apply.  Host
+    only."""
+    if algorithm not in SEARCH_ALGORITHMS:
+        return False, "device search: unknown algorithm %r (expected one of %s)" % (algorithm, ", ".join(SEARCH_ALGORITHMS))
+    lib = load_library()
+    rc = lib.glass_search_islands_supported(int(islands), int(pop), int(n_var), int(n_obj), SEARCH_ALGORITHMS[algorithm], int(migrate_every),
+                                            int(migrants))
     return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
 
 
@@ -635,10 +656,31 @@ class Engine:
         _check(self.lib, self.lib.glass_engine_set_search_operators_mixed(self._h, float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m),
                                                                            float(prob_x), float(prob_flip), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
+    def set_search_islands(self, islands, migrate_every=0, migrants=1):
+        """After set_search / set_search_mixed and before finalize() (include/glass.h "Device search: islands"): `islands` populations of pop
+        rows each, island i under seed + i, in one pass per generation; the `migrants` best rows of island i - 1 replace the worst of island i
+        every `migrate_every` generations (0: never).  Every search_* buffer then holds islands * pop rows, island-major."""
+        _check(self.lib, self.lib.glass_engine_set_search_islands(self._h, int(islands), int(migrate_every), int(migrants)))
+        self.search_islands = int(islands)
+
+    def set_island_weights(self, weights):
+        """Own prompts: weights float32 [islands, T] over the T entries of the prompt set (set_targets, mode "sum"; after finalize()).  The
+        rows of island i are scored with row i of the table; a single 1 searches that entry alone.  Not with migration, "pareto" or a
+        direction source."""
+        w = _f32(weights)
+        if w.ndim != 2:
+            raise ValueError("set_island_weights: weights must be [islands, T], got shape %r" % (w.shape,))
+        _check(self.lib, self.lib.glass_engine_set_island_weights(self._h, _fp(w), w.shape[0], w.shape[1]))
+
+    def search_rows(self):
+        """Rows of the device search's buffers: pop, or islands * pop."""
+        return self.search_pop * getattr(self, "search_islands", 1)
+
     def search_init(self, X0):
-        """Upload the initial population [pop, floats_per_row], score it as generation 0 and rank it."""
+        """Upload the initial population [pop, floats_per_row] (islands: [islands * pop, floats_per_row], island-major), score it as generation 0
+        and rank it."""
         z = self._rows(X0)
-        pop = getattr(self, "search_pop", None)      # (None: set_search was never called — the library says so)
+        pop = self.search_rows() if hasattr(self, "search_pop") else None      # (None: set_search was never called — the library says so)
         if pop is not None and z.shape[0] != pop:
             raise ValueError("search_init: the initial population must have exactly pop = %d rows, got %d" % (pop, z.shape[0]))
         _check(self.lib, self.lib.glass_engine_search_init(self._h, _fp(z)))
@@ -672,20 +714,31 @@ class Engine:
         _check(self.lib, self.lib.glass_engine_search_vary(self._h, int(generation)))
 
     def search_evaluate(self, generation, first_row=0, rows=None):
-        rows = self.search_pop - int(first_row) if rows is None else int(rows)
+        rows = self.search_rows() - int(first_row) if rows is None else int(rows)
         _check(self.lib, self.lib.glass_engine_search_evaluate(self._h, int(generation), int(first_row), rows))
 
     def search_survive(self, generation):
         _check(self.lib, self.lib.glass_engine_search_survive(self._h, int(generation)))
 
+    def search_migrate(self, generation):
+        """The migration behind search_survive(generation), as a phase of its own (search_step runs it itself); nothing where none is due."""
+        _check(self.lib, self.lib.glass_engine_search_migrate(self._h, int(generation)))
+
+    def search_read_islands(self):
+        """int32 [islands, 3]: per island the flagged and the non-finite rows of its last survival and the migrants it accepted last."""
+        out = np.empty((getattr(self, "search_islands", 1), 3), np.int32)
+        _check(self.lib, self.lib.glass_engine_search_read_islands(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
     def search_step(self, generation):
-        """One generation on the device: variation, the scoring pass, survival; one wait at the end."""
+        """One generation on the device: variation, the scoring pass, survival (islands: then the migration, where due); one wait at the end."""
         _check(self.lib, self.lib.glass_engine_search_step(self._h, int(generation)))
 
-    def search_read(self, *fields):
+    def search_read(self, *fields, islands=False):
         """dict of the named device-search buffers: "X", "F", "rank", "cd" (the population), "off_X", "off_F", "flags" (the last offspring),
-        "counts" = (flagged, non-finite rows of the last survival).  Only what is named is copied back."""
-        pop, nv, no = self.search_pop, self.latent_row()[0], int(self.cfg.n_obj)
+        "counts" = (flagged, non-finite rows of the last survival).  Only what is named is copied back.  An island search returns islands * pop
+        rows, island-major; islands=True views every row buffer as [islands, pop, ...]."""
+        pop, nv, no = self.search_rows(), self.latent_row()[0], int(self.cfg.n_obj)
         shapes = dict(X=((pop, nv), np.float32), F=((pop, no), np.float32), rank=((pop,), np.int32), cd=((pop,), np.float64),
                       off_X=((pop, nv), np.float32), off_F=((pop, no), np.float32), flags=((pop,), np.int32), counts=((2,), np.int32))
         unknown = [f for f in fields if f not in shapes]
@@ -695,6 +748,9 @@ class Engine:
         ctype = {np.float32: C.c_float, np.int32: C.c_int32, np.float64: C.c_double}
         args = [out[f].ctypes.data_as(C.POINTER(ctype[shapes[f][1]])) if f in out else None for f in shapes]
         _check(self.lib, self.lib.glass_engine_search_read(self._h, *args))
+        if islands:
+            K = getattr(self, "search_islands", 1)
+            out = {f: a if f == "counts" else a.reshape((K, self.search_pop) + a.shape[1:]) for f, a in out.items()}
         return out
 
     def latent_uploads(self):

@@ -573,9 +573,87 @@ def search_options(config):
     return dict(sigma=1.0 if sigma is None else float(sigma))
 
 
+# ---- island populations (opt-in, include/glass.h "Device search: islands"): several populations in one engine and one pass ----
+ISLAND_KEYS = ("islands", "migrate_every", "migrants", "island_prompts")
+ISLANDS_MAX = 64
+
+
+def island_options(config):
+    """None while every key of ISLAND_KEYS is unset (the default: one population), else dict(islands, migrate_every, migrants, prompts):
+    `islands` populations of pop_size rows each in one engine (island i under seed + i), ring migration of `migrants` rows every
+    `migrate_every` generations (0, the default: never), and `island_prompts`: a list of texts (or ready features [clip_embed]) — `target` is
+    island 0's prompt and each further entry adds an island that searches it alone.  ValueError by name, before any weight is looked for:
+    the GPT2 / img2txt config, --dist, algorithm cmaes, the host search (islands need device_search), an `islands` that disagrees with the
+    prompts, and own prompts together with migration, prompt_mode pareto or an edit source."""
+    vals = {k: getattr(config, k, None) for k in ISLAND_KEYS}
+    given = [k for k in ISLAND_KEYS if vals[k] is not None]
+    if not given:
+        return None
+    prompts = list(vals["island_prompts"] or [])
+    K = int(vals["islands"]) if vals["islands"] is not None else 1 + len(prompts)
+    if prompts and K != 1 + len(prompts):
+        raise ValueError("islands=%d does not agree with island_prompts: target is island 0's prompt and each of the %d island prompts adds an "
+                         "island, which makes %d" % (K, len(prompts), 1 + len(prompts)))
+    if not 1 <= K <= ISLANDS_MAX:
+        raise ValueError("islands must be in [1, %d], got %d" % (ISLANDS_MAX, K))
+    M = 0 if vals["migrate_every"] is None else int(vals["migrate_every"])
+    n = 1 if vals["migrants"] is None else int(vals["migrants"])
+    if M < 0:
+        raise ValueError("migrate_every must be >= 0 (0: never), got %d" % M)
+    pop = int(getattr(config, "pop_size", 0) or 0)
+    if not 1 <= n <= max(pop // 2, 1):
+        raise ValueError("migrants must be in [1, pop_size / 2 = %d] (an island's best rows leave and its worst are replaced), got %d" % (pop // 2, n))
+    if getattr(config, "task", "txt2img") == "img2txt":
+        raise ValueError("%s: islands are populations of the device search, and the GPT2 config searches integer token rows on the host: "
+                         "leave these keys unset" % ", ".join(given))
+    if getattr(config, "dist", False):
+        raise ValueError("%s: islands run on one rank (--dist is not wired to the device search): run one rank" % ", ".join(given))
+    if getattr(config, "algorithm", None) == "cmaes":
+        raise ValueError("%s: algorithm cmaes keeps one distribution, not populations; islands of distributions are a different feature: use "
+                         "ga or nsga2" % ", ".join(given))
+    if not getattr(config, "device_search", False):
+        raise ValueError("%s: the host search has no islands: set device_search (run.py --device-search)" % ", ".join(given))
+    if prompts:
+        if M > 0 and K > 1:
+            raise ValueError("island_prompts with migrate_every=%d: a migrant's F would be stale under another island's prompt: use "
+                             "migrate_every 0" % M)
+        if getattr(config, "prompt_mode", None) == "pareto":
+            raise ValueError("island_prompts with prompt_mode 'pareto': an island combines the set's entries into one similarity (mode sum), "
+                             "and a pareto set has a column per entry")
+        if getattr(config, "edit_image", None) is not None or getattr(config, "edit_latent", None) is not None:
+            raise ValueError("island_prompts with an edit source: the set's entries are then directions from one source; give the islands one "
+                             "target")
+    return dict(islands=K, migrate_every=M, migrants=n, prompts=prompts)
+
+
+def island_config(config, opts):
+    """The config an island search with own prompts runs on: a COPY whose prompt set holds the island prompts behind the caller's entries,
+    with weight 1 each (the islands' weight table decides which island looks at which)."""
+    if opts is None or not opts["prompts"]:
+        return config
+    out = copy.copy(config)
+    out.prompts = list(getattr(config, "prompts", None) or []) + [(p, 1.0) for p in opts["prompts"]]
+    return out
+
+
+def island_weight_table(weights, n_islands):
+    """The islands' weights [K, T] over a prompt set whose last K - 1 entries are the island prompts: island 0 keeps the caller's own
+    entries (the target and its prompts, with their weights), island i >= 1 a single 1 on its own entry."""
+    w = np.asarray(weights, np.float32).reshape(-1)
+    K, T = int(n_islands), w.size
+    table = np.zeros((K, T), np.float32)
+    table[0, :T - (K - 1)] = w[:T - (K - 1)]
+    for i in range(1, K):
+        table[i, T - K + i] = 1.0
+    return table
+
+
 class Generator:
     def __init__(self, config, dist=None):
         search_options(config)      # algorithm "cmaes": what it cannot search is refused here, before any weight is looked for
+        # island populations (opt-in): refused by name here for GPT2, --dist, cmaes and the host search; own prompts join the prompt set
+        self.islands = island_options(config)
+        config = island_config(config, self.islands)
         # perceptual objective (opt-in): refused for the GPT2 config here, before any weight is looked for; with lambda = 0 the search gets
         # one more objective — on a copy of the config, which callers read back as `generator.config`
         self.lpips = lpips_options(config)
@@ -610,7 +688,7 @@ class Generator:
             device = int(str(device).split(":")[1])
         elif not isinstance(device, int):       # bare "cuda"
             device = 0
-        pop = int(getattr(config, "max_pop", max(config.pop_size, config.batch_size)))
+        pop = int(getattr(config, "max_pop", max(config.pop_size, config.batch_size) * (self.islands["islands"] if self.islands else 1)))
         self.generation = 0
         self.sharder = None
         self.clip_preprocess = getattr(config, "clip_preprocess", None) or DEFAULT_CLIP_PREPROCESS
@@ -715,6 +793,12 @@ class Generator:
                     raise ValueError("device_search: %s" % ex)
             if getattr(self.model, "dlatent_avg", None) is not None:
                 self.engine.load_state({"dlatent_avg": self.model.dlatent_avg})     # the Generator's own buffer: no sub-model prefix
+        if self.islands is not None:
+            try:
+                self.engine.set_search_islands(self.islands["islands"], self.islands["migrate_every"], self.islands["migrants"])
+            except RuntimeError as ex:
+                self.engine.close()
+                raise ValueError("islands: %s" % ex)
         self.engine.load_state(self.model.state)
         self.engine.load_state(clip_state)
         if self.lpips is not None:
@@ -752,6 +836,9 @@ class Generator:
             self.engine.set_target(self.text_features[0])
         else:
             self._set_prompts(encoded if texts else None)
+        if self.islands is not None and self.islands["prompts"]:      # own prompts: which island looks at which entry of the set
+            self.island_weights = island_weight_table(self.prompt_weights, self.islands["islands"])
+            self.engine.set_island_weights(self.island_weights)
         if sharded:
             from .parallel import ShardedEvaluator
             self.sharder = ShardedEvaluator(self.engine, dist, dist.get_rank(), dist.get_world_size(), config.batch_size,

@@ -53,6 +53,7 @@ SIGNATURES = {
     "glass_op_layernorm": [i32, i32, i32, fp, fp, fp, fp],
     "glass_op_attention": [i32, i32, i32, i32, i32, fp, fp],
     "glass_op_noise": [i32, i32, i32, u32, u32, u32, u64, fp],
+    "glass_op_noise_period": [i32, i32, i32, u32, u32, u32, u64, u32, fp],
     "glass_op_gpt2_sample": [i32, i32, i32, fp, f32, i32, u64, i32, i32, i32, i32, ip],
     "glass_op_gpt2_gemm": [i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, i32, fp, fp, fp, ip],
     "glass_op_gpt2_attention": [i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, fp],
@@ -85,6 +86,7 @@ SIGNATURES = {
     "glass_op_cosine_views": [i32, i32, i32, i32, fp, fp, fp, fp],
     "glass_op_assemble_F": [i32, i32, i32, fp, fp, fp],
     "glass_op_cosine_set": [i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp],
+    "glass_op_cosine_set_islands": [i32, i32, i32, i32, i32, fp, fp, fp, i32, i32, i32, fp, fp, fp],
     "glass_op_assemble_F_set": [i32, i32, i32, fp, fp, fp, fp, fp],
     "glass_op_cosine_set_dir": [i32, i32, i32, i32, i32, fp, fp, fp, fp, i32, fp, fp, fp],
     "glass_op_latent_anchor": [i32, i32, i32, i32, i32, fp, fp, fp],
@@ -98,6 +100,7 @@ SIGNATURES = {
     "glass_op_ga_vary_mixed": [i32, i32, i32, i32, fp, ip, dp, f64, f64, f64, f64, f64, f64, f64, u64, i32, i32, i32, fp],
     "glass_op_ga_duplicates": [i32, i32, i32, i32, fp, fp, ip],
     "glass_op_ga_survive": [i32, i32, i32, i32, i32, i32, fp, ip, ip, ip, dp, fp, ip, i32, fp, fp, fp],
+    "glass_op_ga_migrate": [i32, i32, i32, i32, i32, i32, i32, fp, fp, ip, dp, fp, fp, ip, dp, ip],
     "glass_op_cma_sample": [i32, i32, i32, dp, dp, f64, f64, f64, u64, i32, i32, i32, fp],
     "glass_op_cma_rank": [i32, i32, fp, f32, ip, ip, fp],
     "glass_op_cma_update": [i32, i32, i32, fp, fp, dp, dp, ip, f64, f64, i32, fp, fp, ip],
@@ -406,6 +409,14 @@ def noise(n_mb, hw, layer, mb0, generation, seed, device=0):
     lib = _lib()
     out = np.empty((n_mb, hw), dtype=np.float32)
     _check(lib, lib.glass_op_noise(device, n_mb, hw, layer, mb0, generation, seed, _fp(out)))
+    return out
+
+
+def noise_period(n_mb, hw, layer, mb0, generation, seed, period, device=0):
+    """noise() with launch_noise's period: plane m is that of minibatch (mb0 + m) % period (the device search's islands)."""
+    lib = _lib()
+    out = np.empty((n_mb, hw), dtype=np.float32)
+    _check(lib, lib.glass_op_noise_period(device, n_mb, hw, layer, mb0, generation, seed, int(period), _fp(out)))
     return out
 
 
@@ -895,6 +906,19 @@ def cosine_set(feat, targets, weights, device=0):
     return vs, ss, sim
 
 
+def cosine_set_islands(feat, targets, weights, pop, row0=0, device=0):
+    """cosine_set with an island table (include/glass.h "Device search: islands", own prompts): weights [islands, T]; row p of feat [P, V, D]
+    is search row row0 + p and takes the weights of island (row0 + p) // pop."""
+    lib = _lib()
+    feat, targets, weights = _f32(feat), _f32(targets), _f32(weights)
+    P, V, D = feat.shape
+    T = targets.shape[0]
+    vs, ss, sim = np.empty((P, V), np.float32), np.empty((P, T), np.float32), np.empty(P, np.float32)
+    _check(lib, lib.glass_op_cosine_set_islands(device, P, V, T, D, _fp(feat), _fp(targets), _fp(weights), weights.shape[0], int(pop), int(row0),
+                                                _fp(vs), _fp(ss), _fp(sim)))
+    return vs, ss, sim
+
+
 def assemble_F_set(set_sim, weights, dis=None, lp=None, device=0):
     """set_sim [P, K], weights [K], dis / lp [P] or None -> F [P, K + (dis is not None) + (lp is not None)]: the pareto layout."""
     lib = _lib()
@@ -1079,6 +1103,21 @@ def ga_survive(F, n_pop, pop_out, nsga=True, flags=None, X=None, device=0):
                                         out["chosen"].ctypes.data_as(ip), out["rank"].ctypes.data_as(ip), out["cd"].ctypes.data_as(dp),
                                         _fp(out["F"]), out["counts"].ctypes.data_as(ip), nv, None if Xp is None else _fp(Xp),
                                         None if Xo is None or not n_off else _fp(Xo), None if Xout is None else _fp(Xout)))
+    return out
+
+
+def ga_migrate(X, F, rank, cd, migrants, nsga=True, device=0):
+    """One ring migration (include/glass.h "Device search: islands") of the islands X float32 [K, pop, n_var], F [K, pop, n_obj], rank int32 and
+    cd float64 [K, pop] as survival left them -> dict(X, F, rank, cd after it, accepted int32 [K])."""
+    lib = _lib()
+    X, F = _f32(X), _f32(F)
+    K, pop, nv = X.shape
+    rank = np.ascontiguousarray(rank, dtype=np.int32)
+    cd = np.ascontiguousarray(cd, dtype=np.float64)
+    out = dict(X=np.empty_like(X), F=np.empty_like(F), rank=np.empty_like(rank), cd=np.empty_like(cd), accepted=np.empty((K,), np.int32))
+    _check(lib, lib.glass_op_ga_migrate(device, K, pop, nv, F.shape[2], int(bool(nsga)), int(migrants), _fp(X), _fp(F), rank.ctypes.data_as(ip),
+                                        cd.ctypes.data_as(dp), _fp(out["X"]), _fp(out["F"]), out["rank"].ctypes.data_as(ip),
+                                        out["cd"].ctypes.data_as(dp), out["accepted"].ctypes.data_as(ip)))
     return out
 
 

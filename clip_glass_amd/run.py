@@ -16,8 +16,8 @@ import numpy as np
 from .config import get_config
 from .engine import LATENT_SPACES
 from .engine import PROMPT_MODES
-from .generator import (CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, edit_options, latent_options, lpips_options, parse_weighted,
-                        prompt_options, search_options)
+from .generator import (CLIP_MODELS, CLIP_PREPROCESS, CLIP_RESNET_MODELS, edit_options, island_options, latent_options, lpips_options,
+                        parse_weighted, prompt_options, search_options)
 from .operators import get_operators
 from .problem import GenerationProblem
 from . import search
@@ -98,6 +98,15 @@ def build_parser():
                    help="StyleGAN2 and BigGAN configs, one rank: keep the population on the GPU and run selection, crossover, mutation (on a "
                         "BigGAN row: SBX / polynomial mutation on z, half-uniform crossover / bit-flip on the class bits), duplicate flags and "
                         "survival there between the passes (off by default: the host search of search.py; refused for GPT2 and with --dist)")
+    p.add_argument("--islands", type=int, default=None,
+                   help="with --device-search: K populations of --pop-size rows each in one engine and one pass per generation, island i under "
+                        "seed + i (off by default: one population; refused for GPT2, with --dist and with --algorithm cmaes)")
+    p.add_argument("--migrate-every", type=int, default=None,
+                   help="with --islands: every M generations the best rows of island i - 1 replace the worst of island i (default 0: never)")
+    p.add_argument("--migrants", type=int, default=None, help="with --migrate-every: rows per migration, 1 (default) .. pop-size / 2")
+    p.add_argument("--island-prompt", action="append", default=None, metavar="TEXT",
+                   help="repeatable: --target is island 0's prompt and each TEXT adds an island that searches it alone, all in the one pass "
+                        "(--islands, if given, must agree; not with migration, --prompt-mode pareto or an edit source)")
     p.add_argument("--algorithm", type=str, default=None, choices=["ga", "nsga2", "cmaes"],
                    help="the search rule (default: the config's own — nsga2 with the discriminator, ga without).  cmaes: separable CMA-ES, one "
                         "objective and real-valued rows (the StyleGAN2 _nod configs, in z, w or w+; an LPIPS / anchor distance folded in with "
@@ -168,13 +177,16 @@ def main(argv=None, extra_config=None):
     for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "clip_views", "clip_view_min", "clip_view_flip",
               "clip_view_fixed", "latent_space", "truncation_psi", "truncation_cutoff", "lpips_target", "lpips_size", "lpips_lambda", "lpips_weights",
               "bpe_path", "pop_size", "stochastic", "target_weight", "prompt_mode", "device_search", "edit_image", "edit_latent", "source_text",
-              "anchor_lambda", "edit_sigma", "algorithm", "cma_sigma"):
+              "anchor_lambda", "edit_sigma", "algorithm", "cma_sigma", "islands", "migrate_every", "migrants"):
         if k in over:
             setattr(config, k, over[k])
     if "prompt" in over or "image_prompt" in over:
         config.prompts = cli_prompts(over.get("prompt"), over.get("image_prompt"))
+    if "island_prompt" in over:
+        config.island_prompts = list(over["island_prompt"])
     if extra_config:
         vars(config).update(extra_config)
+    isl = island_options(config)      # islands where no device search holds them, or own prompts with what they exclude, are refused here
     latent_options(config)      # a latent space / truncation on a BigGAN or GPT2 config is refused here, before anything is loaded
     lpips_options(config)       # ... and so is the perceptual objective on the GPT2 config
     prompt_options(config)      # ... and a prompt set there, or one the engine would refuse
@@ -218,11 +230,13 @@ def main(argv=None, extra_config=None):
     res = search.minimize(problem, config.algorithm, config.pop_size, config.generations, operators["sampling"],
                           seed=config.seed, callback=save_callback, verbose=rank0, mask=operators.get("mask"),
                           device=bool(getattr(config, "device_search", False)),
+                          **(dict(islands=isl["islands"], migrate_every=isl["migrate_every"], migrants=isl["migrants"]) if isl else {}),
                           **(dict(cma_sigma=getattr(config, "cma_sigma", None)) if config.algorithm == "cmaes" else {}))
     if not rank0:
         return res
     with open(os.path.join(config.tmp_folder, "genetic_result"), "wb") as f:   # run.py:79-84
-        pickle.dump(dict(X=res.X, F=res.F, G=res.G, CV=res.CV), f)
+        pickle.dump(dict(X=res.X, F=res.F, G=res.G, CV=res.CV,
+                         **(dict(islands=[dict(X=r.X, F=r.F, G=r.G, CV=r.CV) for r in res.islands]) if isl else {})), f)
     names = objective_names(config)
     if len(names) >= 2:
         try:                                                                   # run.py:86-89; three objectives: one scatter per pair
@@ -254,6 +268,13 @@ def main(argv=None, extra_config=None):
     generated = problem.generator.generate(ls)                                 # run.py:118
     ext = "txt" if config.task == "img2txt" else "jpg"                         # run.py:120-125
     problem.generator.save(generated, os.path.join(config.tmp_folder, "output.%s" % ext))
+    for i, r in enumerate(res.islands if isl else []):      # every island's own pick, chosen as the overall one is
+        if config.problem_args["n_obj"] == 1:
+            X = np.atleast_2d(r.X)
+        else:
+            X = np.atleast_2d(np.atleast_2d(r.X)[search.pseudo_weights_choice(np.atleast_2d(r.F), final_pick_weights(names))])
+        ls.set_from_population(X)
+        problem.generator.save(problem.generator.generate(ls), os.path.join(config.tmp_folder, "output-island-%d.%s" % (i, ext)))
     return res
 
 

@@ -200,9 +200,36 @@ def _result(X, F, nsga):
     return res
 
 
-def _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callback, eta_c, eta_m, prob_m, verbose, mask):
+def _device_initial(problem, sampling, pop_size, seed):
+    """Generation 0 of a device search under `seed`: sampled, de-duplicated and refilled to exactly pop_size rows."""
+    np.random.seed(seed)   # the reference's Sampling classes draw from numpy's global RNG (operators.py:24-25)
+    X = np.asarray(sampling._do(problem, pop_size), dtype=float)
+    X = X[_eliminate_duplicates(X)]
+    for _ in range(16):    # exactly pop_size rows: refill from the sampler where elimination shrank the population
+        if X.shape[0] >= pop_size:
+            break
+        X = np.concatenate([X, np.asarray(sampling._do(problem, pop_size - X.shape[0]), dtype=float)])
+        X = X[_eliminate_duplicates(X)]
+    if X.shape[0] != pop_size:
+        raise ValueError("device search: the sampler keeps returning duplicate rows: %d distinct of %d" % (X.shape[0], pop_size))
+    return X
+
+
+def _island_result(X, F, nsga, islands, pop_size, own_prompts):
+    """The Result of an island search from its rows, island-major: islands[i] is island i's Result; X / F / pop are the best row (GA) or the
+    non-dominated front (NSGA-II) of the union where the islands share one objective, and island 0's where each has its own prompt."""
+    per = [_result(X[i * pop_size:(i + 1) * pop_size], F[i * pop_size:(i + 1) * pop_size], nsga) for i in range(islands)]
+    res = _result(X[:pop_size], F[:pop_size], nsga) if own_prompts else _result(X, F, nsga)
+    res.islands = per
+    return res
+
+
+def _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callback, eta_c, eta_m, prob_m, verbose, mask, islands=1,
+                     migrate_every=0, migrants=1):
     """The generation step on the device (include/glass.h "Device search"): generation 0 is sampled, de-duplicated and refilled on the host
-    as below, then every generation is one engine.search_step and a read of F.  Refusals come first and name their reason."""
+    as below, then every generation is one engine.search_step and a read of F.  Refusals come first and name their reason.
+    islands > 1 ("Device search: islands"): generation 0 of island i is what this function samples under seed + i; the engine must have been
+    set up for the same islands, migrate_every and migrants (Engine.set_search_islands before finalize)."""
     mask = np.asarray(["real"] * problem.n_var if mask is None else list(mask))
     n_real = None      # a mixed search: the real columns in front of the bits
     if (mask != "real").any():
@@ -239,16 +266,15 @@ def _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callba
         raise ValueError("device search: the engine was built without it, or for another pop_size (its buffers are sized in finalize): set "
                          "config.device_search = True (run.py --device-search) before the problem is constructed")
     nsga = algorithm == "nsga2"
-    np.random.seed(seed)   # the reference's Sampling classes draw from numpy's global RNG (operators.py:24-25)
-    X = np.asarray(sampling._do(problem, pop_size), dtype=float)
-    X = X[_eliminate_duplicates(X)]
-    for _ in range(16):    # exactly pop_size rows: refill from the sampler where elimination shrank the population
-        if X.shape[0] >= pop_size:
-            break
-        X = np.concatenate([X, np.asarray(sampling._do(problem, pop_size - X.shape[0]), dtype=float)])
-        X = X[_eliminate_duplicates(X)]
-    if X.shape[0] != pop_size:
-        raise ValueError("device search: the sampler keeps returning duplicate rows: %d distinct of %d" % (X.shape[0], pop_size))
+    have_islands = getattr(engine, "search_islands", None)
+    if islands != (have_islands or 1) or (islands > 1 and have_islands is None):
+        raise ValueError("device search: islands=%d, and the engine's search was set up %s (its buffers are sized in finalize): "
+                         "Engine.set_search_islands(%d, migrate_every, migrants) before finalize (config.islands does it)"
+                         % (islands, "without islands" if have_islands is None else "for %d" % have_islands, islands))
+    if have_islands is None:
+        X = _device_initial(problem, sampling, pop_size, seed)
+    else:
+        X = np.concatenate([_device_initial(problem, sampling, pop_size, seed + i) for i in range(islands)])
     if n_real is None:
         engine.set_search_operators(float(xl[0]), float(xu[0]), eta_c, eta_m, prob_m, seed)
     else:
@@ -263,11 +289,14 @@ def _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callba
         algo.n_gen = gen
         if verbose:
             F = engine.search_read("F")["F"]
-            print("gen %4d | n_eval %6d | best %s" % (gen, gen * pop_size, np.array2string(F.min(axis=0), precision=5)))
+            print("gen %4d | n_eval %6d | best %s" % (gen, gen * pop_size * islands, np.array2string(F.min(axis=0), precision=5)))
         if callback is not None:
             callback(algo)
     r = engine.search_read("X", "F")
-    return _result(r["X"].astype(float), r["F"].astype(float), nsga)
+    if have_islands is None:
+        return _result(r["X"].astype(float), r["F"].astype(float), nsga)
+    own = getattr(getattr(problem, "generator", None), "island_weights", None) is not None
+    return _island_result(r["X"].astype(float), r["F"].astype(float), nsga, islands, pop_size, own)
 
 
 # ----------------------------- separable CMA-ES --------------------------------------------
@@ -463,7 +492,8 @@ def _minimize_cmaes_device(problem, pop_size, n_gen, sampling, seed, callback, v
 
 
 def minimize(problem, algorithm, pop_size, n_gen, sampling, seed=1, callback=None, eta_c=3.0, eta_m=3.0,
-             prob_m=0.5, verbose=False, mask=None, device=False, cma_mean=None, cma_diag=None, cma_sigma=None):
+             prob_m=0.5, verbose=False, mask=None, device=False, cma_mean=None, cma_diag=None, cma_sigma=None, islands=1, migrate_every=0,
+             migrants=1):
     """pymoo.optimize.minimize(problem, algorithm, ("n_gen", n_gen)) stand-in.
 
     problem: has n_var, n_obj, xl, xu and _evaluate(x, out) (GenerationProblem);
@@ -474,12 +504,25 @@ def minimize(problem, algorithm, pop_size, n_gen, sampling, seed=1, callback=Non
     problem's engine between the passes (include/glass.h "Device search"); the result has the same shapes.
     algorithm "cmaes" (opt-in): separable CMA-ES (include/glass.h "Device search: sep-CMA-ES") — one objective, real variables, scalar bounds;
     generations 0 .. n_gen of pop_size rows, the callback after generations 1 .. n_gen.  cma_mean / cma_diag / cma_sigma: the initial
-    distribution (default: cma_initial).  The Result has X / F = the best row seen, pop = the last generation, and mean and sigma."""
+    distribution (default: cma_initial).  The Result has X / F = the best row seen, pop = the last generation, and mean and sigma.
+    islands=K (opt-in, device=True and "ga" / "nsga2" only; include/glass.h "Device search: islands"): K populations of pop_size rows in the
+    problem's engine, island i under seed + i, with ring migration of `migrants` rows every `migrate_every` generations (0: never).
+    res.islands[i] is island i's Result; res.X / res.F / res.pop are the best row (GA) or the non-dominated front (NSGA-II) of the union —
+    or island 0's, where each island has its own prompt."""
+    islands = int(islands)
+    if islands < 1:
+        raise ValueError("islands must be >= 1, got %d" % islands)
+    if islands > 1 and algorithm == "cmaes":
+        raise ValueError("islands=%d with algorithm cmaes: it keeps one distribution, not populations; islands of distributions are a "
+                         "different feature: use ga or nsga2" % islands)
+    if islands > 1 and not device:
+        raise ValueError("islands=%d without device=True: the host search has no islands (they are populations of the device search)" % islands)
     if algorithm == "cmaes":
         run = _minimize_cmaes_device if device else _minimize_cmaes
         return run(problem, pop_size, n_gen, sampling, seed, callback, verbose, mask, (cma_mean, cma_diag, cma_sigma))
     if device:
-        return _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callback, eta_c, eta_m, prob_m, verbose, mask)
+        return _minimize_device(problem, algorithm, pop_size, n_gen, sampling, seed, callback, eta_c, eta_m, prob_m, verbose, mask, islands,
+                                migrate_every, migrants)
     rng = np.random.default_rng(seed)
     np.random.seed(seed)   # the reference's Sampling classes draw from numpy's global RNG (operators.py:24-25)
     xl = np.broadcast_to(np.asarray(problem.xl, float), (problem.n_var,))

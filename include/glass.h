@@ -520,6 +520,72 @@ int glass_engine_search_read(glass_engine* e, float* pop_X, float* pop_F, int32_
                              int32_t* counts);
 int glass_engine_latent_uploads(glass_engine* e, int64_t* calls, int64_t* rows);
 
+/* Device search: islands (opt-in on top of a GA / NSGA-II device search: glass_engine_set_search_islands; without it the engine launches,
+ * allocates and returns exactly what the section above says).  K populations evolve side by side in ONE engine — one copy of the weights,
+ * one scoring pass per generation — under different seeds, with rare migration round a ring: the island model, the usual remedy for a
+ * small population converging into one basin of a multimodal landscape.  Each island is ranked by one workgroup, so the rows of a search
+ * are limited by max_pop and no longer by what one workgroup ranks.
+ *
+ * Layout and seeds.  K islands of pop rows each; pop keeps its meaning and its limits per island ([2, 1024], a multiple of batch_size).
+ * Every buffer is island-major: rows live as [K][pop][n_var], and island i owns rows [i pop, (i + 1) pop) of the population, the
+ * offspring, F, rank, cd, flags and chosen.  Island i's Philox seed is seed + i (uint64, wrapping), and inside an island every index the
+ * rule above speaks of is LOCAL: mating m, offspring row r, population rows a / b, the merged index.  Island i is therefore, bit for bit,
+ * the single search glass_engine_set_search(..., seed + i) on its own rows; real-valued and mixed rows alike.
+ *
+ * Noise.  With noise_mode 1 the noise plane of a minibatch is that of its index WITHIN its island, (first_minibatch + m) mod (pop /
+ * batch_size): every island sees the planes a single search of pop rows sees, and the islands are ranked under common noise, as
+ * candidates already are under common crop views (whose boxes do not depend on the row).
+ *
+ * One pass per generation.  Generation g varies all K pop offspring rows in one launch per kernel (the island is a grid dimension), scores
+ * them in one pass of K pop rows, runs survival as K workgroups — each reads its island's population F and offspring F, two planes now
+ * that the pass writes K pop offspring rows contiguously — and gathers per island.  No host wait and no latent upload in between.
+ *
+ * Migration.  Ring topology; `migrants` = n rows every `migrate_every` = M generations (M = 0: never).  It is due after the survival of
+ * generation g when g >= 1 and g mod M = 0; K = 1 ignores it.
+ *   Order: the rows of an island are ordered by (rank, -cd, index), the tournament's order; for the GA that is by F.
+ *   Sources: island i receives the n best rows of island (i - 1 + K) mod K; all sources are read from the populations as survival left
+ *     them.
+ *   Placement: migrant k, the k-th best, is aimed at the receiver's k-th worst row, worst first.
+ *   Duplicates: a migrant is dropped when it equals, by value in every variable (-0.0 equals 0.0), a row of the receiving population as
+ *     survival left it, or an earlier migrant of the same migration into that island (accepted or not: a dropped one equals a row that
+ *     drops the later one too).  Its slot then keeps its row.
+ *   An accepted migrant brings its X and its F.  Every island that accepted a migrant is then ranked again by the survival rule over its pop
+ *     rows with no offspring, as glass_engine_search_init ranks a population, which also reorders it; an island that accepted none keeps
+ *     every bit of its state (ranking it again would reorder a last front that was cut).
+ *   1 <= n <= pop / 2, so that the rows an island sends and the rows it replaces are disjoint.  The accepted migrants per island are
+ *     readable (glass_engine_search_read_islands).
+ * No atomics on floating-point data; the result does not depend on the schedule.  Numpy mirror: tests/search_islands_ref.py.
+ *
+ * Own prompts (optional).  A prompt set already scores every candidate against every entry in the pass it runs anyway; a weight table
+ * [K][T] over the set's T entries lets every island search its own combination: row p of a search pass combines its set_sim with the
+ * weights and the sum of |w| of island (first_row + p) / pop, in "Prompt sets"' order of operations.  One non-zero weight of 1 gives the
+ * single-target pass against that entry: adding the other entries' +-0 products changes no value.  Mode sum only, and only without a
+ * direction source; refused by name with mode pareto, with a direction source and together with migration (a migrant's F would be
+ * stale under another island's objective).  A pass outside the search (glass_engine_evaluate) keeps the set's own weights.
+ *
+ * glass_search_islands_supported (host only): GA and NSGA-II (sep-CMA-ES is refused by name: several distributions are a different
+ *   feature); everything glass_search_supported says for (pop, n_var, n_obj); islands in [1, 64]; islands * pop * n_var below 2^31;
+ *   migrate_every >= 0; migrants in [1, pop / 2].
+ * glass_engine_set_search_islands: after set_search / set_search_mixed and before finalize, which sizes K pop buffers; islands * pop <=
+ *   max_pop.  Refused by name: a cmaes search; noise_mode 2 is refused by set_search as before.
+ * With islands on: glass_engine_search_init takes [K pop][floats_per_row], island-major, and ranks every island;
+ *   glass_engine_search_evaluate(first_row, rows) accepts whole minibatches anywhere in the K pop rows; glass_engine_search_step is vary ->
+ *   one pass -> survive -> migrate if due, with one wait at its end; glass_engine_search_read returns K pop rows, island-major, and counts
+ *   summed over the islands.
+ * glass_engine_set_island_weights: after finalize and glass_engine_set_targets (mode sum): w [islands][T], finite, at least one non-zero
+ *   weight per island (zeros are allowed here: an island need not look at every entry); islands and T must be the search's and the set's.
+ *   A later set_targets that changes T or the mode makes the next search pass fail by name until the table is set again.
+ * glass_engine_search_migrate(generation): the migration as a phase of its own, behind glass_engine_search_survive(generation) (once;
+ *   GLASS_ERR_STATE otherwise); it does nothing where the rule has none due.
+ * glass_engine_search_read_islands: counts int32 [K][3] = {flagged, non-finite rows of the island's last survival, migrants it accepted in
+ *   the last migration}. */
+int glass_search_islands_supported(int32_t islands, int32_t pop, int32_t n_var, int32_t n_obj, int32_t algorithm, int32_t migrate_every,
+                                   int32_t migrants);
+int glass_engine_set_search_islands(glass_engine* e, int32_t islands, int32_t migrate_every, int32_t migrants);
+int glass_engine_set_island_weights(glass_engine* e, const float* w /*[islands][T]*/, int32_t islands, int32_t T);
+int glass_engine_search_migrate(glass_engine* e, int32_t generation);
+int glass_engine_search_read_islands(glass_engine* e, int32_t* counts /*[islands][3]*/);
+
 /* Device search: sep-CMA-ES (opt-in: glass_engine_set_search with algorithm GLASS_SEARCH_CMAES).  The separable CMA-ES of Ros & Hansen
  * (2008) — a diagonal covariance, O(n) state — as a third search rule next to the GA and NSGA-II above: what stays on the device is a
  * distribution, not a population.  One objective, minimised; real-valued rows only (a StyleGAN2 engine in z, w or w+).  With n = n_var,

@@ -307,6 +307,19 @@ int glass_op_ga_duplicates(int32_t device, int32_t pop, int32_t n_off, int32_t n
 int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off, int32_t n_obj, int32_t pop_out, int32_t nsga, const float* F,
                         const int32_t* flags, int32_t* chosen, int32_t* rank, double* cd, float* F_out, int32_t* counts, int32_t n_var, const float* X,
                         const float* Xoff, float* X_out);
+/* The island kernels (search.hip; include/glass.h "Device search: islands").
+ * glass_op_ga_migrate: the whole migration — ga_migrate_kernel, the gated island survival and the island gather, as the engine launches them:
+ *   X [islands pop,n_var], F [islands pop,n_obj], rank int32 and cd double [islands pop] as survival left them -> the same four after the
+ *   migration, accepted int32 [islands].  islands >= 2, migrants in [1, pop / 2].
+ * glass_op_noise_period: glass_op_noise with launch_noise's period: plane m is that of minibatch (mb0 + m) % period (period 0: mb0 + m). */
+int glass_op_ga_migrate(int32_t device, int32_t islands, int32_t pop, int32_t n_var, int32_t n_obj, int32_t nsga, int32_t migrants, const float* X,
+                        const float* F, const int32_t* rank, const double* cd, float* X_out, float* F_out, int32_t* rank_out, double* cd_out,
+                        int32_t* accepted);
+/* glass_op_cosine_set_islands: glass_op_cosine_set with launch_cosine_set's island table: weights [islands,T], row p takes row (row0 + p) / pop. */
+int glass_op_cosine_set_islands(int32_t device, int32_t P, int32_t V, int32_t T, int32_t D, const float* feat, const float* targets,
+                                const float* weights, int32_t islands, int32_t pop, int32_t row0, float* view_sim, float* set_sim, float* sim);
+int glass_op_noise_period(int32_t device, int32_t n_mb, int32_t hw, uint32_t layer, uint32_t mb0, uint32_t generation, uint64_t seed,
+                          uint32_t period, float* out);
 /* The sep-CMA-ES kernels (cmaes.hip; include/glass.h "Device search: sep-CMA-ES") on caller-supplied state and F, each through the launcher
  * the engine calls; the weights and constants are the library's own for (lambda, n).
  * glass_op_cma_sample: mean [n], diag [n], sigma -> rows [row0, row0 + rows) of `generation` into X [lambda,n], which comes in with the
