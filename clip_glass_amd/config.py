@@ -10,6 +10,12 @@ random, True) and `clip_view_fixed` (the same crops in every generation, False);
 `latent_space` ("z", the default: the reference's search; "w": rows are dlatents, the mapping network is skipped; "w+": one dlatent per
 style layer), `truncation_psi` (1.0: off) and `truncation_cutoff` (None: every layer) — the StyleGAN2 configs only (include/glass.h);
 refused for the BigGAN and GPT2 configs;
+`latent_space` "sub" (rows are coefficients of principal directions of W per group of style layers, include/glass.h "Subspace latent
+space") with `subspace_components` (64: directions per group, capped at `dim_z`), `subspace_layers` (unset: one group of every layer; a
+spec like "0-3,4-7,8-17": one group per inclusive range, layers not named frozen), `subspace_samples` (4096: rows of z the mapping network
+is probed with for the PCA) and `subspace_basis` (an npz with mean, components, stdev[, layer_group] to use instead of probing: the
+subspace.npz of an earlier run, or a GANSpace export) — the StyleGAN2 configs only; the `subspace_*` keys are refused without the space,
+and all of it for the BigGAN and GPT2 configs.  The bounds stay the config's own (+-10): the coefficients are unit-variance, as z's variables;
 `lpips_target` (unset, the default: off; a path or an array [3, H, W] in [0, 1]: the LPIPS-VGG16 distance to that image becomes a search
 objective, include/glass.h), with `lpips_size` (256), `lpips_lambda` (0: an objective of its own — the Generator then searches a copy of the
 config with `n_obj` one higher and `algorithm` "nsga2", this table is not touched; > 0: added to the similarity objective) and

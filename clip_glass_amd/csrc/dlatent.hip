@@ -39,6 +39,87 @@ void launch_dlatent_expand(const float* src, long long src_row, long long src_la
                        n_pad, n_layers, L / 4, total4);
 }
 
+// Latent space `sub` (include/glass.h "Subspace latent space"): dst[p][l][:] = base[l][:] + sum_k c[p][g][k] B[k][:], g = layer_group[l];
+// a frozen layer (g = -1) gets base[l][:] bit for bit.  c [P][G][K], B [K][L], base [n_lat][L], dst dense [P][n_lat][L].
+//   blockIdx.z: a tile of SUB_PB = 16 candidates, whose K coefficients of group blockIdx.y are staged once in LDS as cs[k][candidate]
+//   (K <= 512: 32 KB), so that one 16-byte LDS read gives a k's coefficients of four candidates to every lane at once;
+//   wave w of the workgroup owns the columns [256 (4 blockIdx.x + w), + 256), four per lane: one 16-byte load of B[k][j .. j + 3] feeds
+//   the 64 FMAs of all 16 candidates — a B element is loaded once per (group, candidate tile) and never per layer.
+// The product of (candidate, group) is ONE fp32 FMA chain over k = 0 .. K - 1 from 0.f (explicit FMAs: see dense_body.h on what
+// -ffp-contract does to rows otherwise), held in registers and then added to base[l] for every layer l of the group: one fp32 add and one
+// 16-byte store per layer.  The workgroups of group 0 copy the frozen layers too — the launch writes every element of dst[0 .. P).  A
+// candidate's values depend on its own row alone: not on P, its slot in the tile or the tile.
+#define SUB_PB 16
+#define SUB_KMAX 512
+__global__ __launch_bounds__(256) void dlatent_subspace_kernel(const float* __restrict__ c, int G, int K, const int* __restrict__ layer_group,
+                                                               int n_lat, int L, const float* __restrict__ B, const float* __restrict__ base,
+                                                               float* __restrict__ dst, int P) {
+    __shared__ f4 cs[SUB_KMAX][SUB_PB / 4];
+    const int t = threadIdx.x, g = blockIdx.y, p0 = blockIdx.z * SUB_PB;
+    float* csf = (float*)cs;
+    for (int e = t; e < SUB_PB * K; e += 256) {      // coalesced along k; a slot past P holds zeros and is never stored
+        const int pr = e / K, k = e - pr * K;
+        csf[k * SUB_PB + pr] = p0 + pr < P ? c[((long long)(p0 + pr) * G + g) * K + k] : 0.f;
+    }
+    __syncthreads();
+    const int j = (blockIdx.x * 4 + (t >> 6)) * 256 + (t & 63) * 4;
+    if (j >= L) return;      // (after the only barrier; L % 4 == 0: a lane's four columns are inside or outside together)
+    f4 acc[SUB_PB];
+#pragma unroll
+    for (int q = 0; q < SUB_PB; ++q) acc[q] = f4{0.f, 0.f, 0.f, 0.f};
+    const float* Bj = B + j;
+    int k = 0;
+    for (; k + 4 <= K; k += 4) {      // four 16-byte loads of B in flight
+        f4 b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) b[u] = *(const f4*)(Bj + (long long)(k + u) * L);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int q4 = 0; q4 < SUB_PB / 4; ++q4) {
+                const f4 cv = cs[k + u][q4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc[q4 * 4 + q][i] = __builtin_fmaf(cv[q], b[u][i], acc[q4 * 4 + q][i]);
+            }
+    }
+    for (; k < K; ++k) {
+        const f4 b = *(const f4*)(Bj + (long long)k * L);
+#pragma unroll
+        for (int q4 = 0; q4 < SUB_PB / 4; ++q4) {
+            const f4 cv = cs[k][q4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[q4 * 4 + q][i] = __builtin_fmaf(cv[q], b[i], acc[q4 * 4 + q][i]);
+        }
+    }
+    const int np = min(SUB_PB, P - p0);
+    for (int l = 0; l < n_lat; ++l) {
+        const int lg = layer_group[l];      // uniform over the workgroup
+        if (lg != g && !(lg < 0 && g == 0)) continue;
+        const f4 bs = *(const f4*)(base + (long long)l * L + j);
+#pragma unroll
+        for (int q = 0; q < SUB_PB; ++q) {
+            f4 o = bs;
+            if (lg >= 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] = bs[i] + acc[q][i];
+            }
+            if (q < np) *(f4*)(dst + ((long long)(p0 + q) * n_lat + l) * L + j) = o;      // (no break: acc stays in registers under a full unroll)
+        }
+    }
+}
+// false: the shape is outside the kernel's limits (glass_subspace_supported's, which the engine has asked before), nothing launched
+bool launch_dlatent_subspace(const float* c, int P, int G, int K, const int* layer_group, int n_lat, int L, const float* B, const float* base,
+                             float* dst, hipStream_t st) {
+    if (P < 1 || G < 1 || G > n_lat || K < 1 || K > SUB_KMAX || K > L || L % 4 || (P + SUB_PB - 1) / SUB_PB > 65535) return false;
+    hipLaunchKernelGGL(dlatent_subspace_kernel, dim3((L + 1023) / 1024, G, (P + SUB_PB - 1) / SUB_PB), dim3(256), 0, st, c, G, K, layer_group,
+                       n_lat, L, B, base, dst, P);
+    return true;
+}
+
 // Style affines when the dlatent rows differ per layer: columns [col0, col0 + n) of the concatenated [P][S_total] table — one 64-wide
 // piece of one style segment — read dlatent row `lat` of their candidate.  blockIdx.x walks the (segment, n0) tile list built at
 // finalize (StyleTile: no workgroup starts only to leave), blockIdx.y the groups of 16 candidates.  The tile is dense_body's, so an

@@ -41,7 +41,7 @@ int compute_anchor(glass_engine* e) {
     GLASS_HIP(hipSetDevice(e->cfg.device));
     e->cur = e->stream;
     e->launch_error.clear();
-    float* d_rows = e->latent_space == GLASS_LATENT_WPLUS ? e->d_dlat : e->latent_space == GLASS_LATENT_W ? e->d_w0 : e->d_z;
+    float* d_rows = latent_rows_dst(e);
     memcpy(e->h_pinned, ed.anchor_row.data(), row * sizeof(float));
     GLASS_HIP(hipMemcpyAsync(d_rows, e->h_pinned, row * sizeof(float), hipMemcpyHostToDevice, e->cur));
     const bool prof = e->profiling;
@@ -73,6 +73,7 @@ extern "C" int glass_engine_set_anchor(glass_engine* e, const float* row) {
     REQUIRE(e && row, GLASS_ERR_ARG, "null argument");
     REQUIRE(e->finalized, GLASS_ERR_STATE, "set_anchor: finalize() first (the row goes through the mapping network)");
     REQUIRE(e->cfg.anchor, GLASS_ERR_STATE, "set_anchor: this engine was created without an anchor (glass_config::anchor = 0): F has no place for the distance");
+    REQUIRE(e->latent_space != GLASS_LATENT_SUB || e->has_subspace, GLASS_ERR_STATE, "set_anchor: set_subspace() first (the row's dlatents are base + coefficients . basis)");
     glass_engine::Edit& ed = e->edit;
     GLASS_HIP(hipSetDevice(e->cfg.device));
     if (!ed.d_anchor) {

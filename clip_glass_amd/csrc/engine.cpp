@@ -656,11 +656,12 @@ int run_pass(glass_engine* e, const float* latents, int P, int generation, int f
     const bool anchor = out_F && c.anchor, source = out_F && e->edit.has_source;      // image editing (opt-in)
     if (anchor) REQUIRE(e->edit.has_anchor, GLASS_ERR_STATE, "set_anchor() first (this engine was created with anchor = 1)");
     if (source) REQUIRE(e->pset.T > 0, GLASS_ERR_STATE, "set_targets() first (a direction source is set: the targets are the directions of a prompt set)");
+    REQUIRE(e->latent_space != GLASS_LATENT_SUB || e->has_subspace, GLASS_ERR_STATE, "set_subspace() first (latent space sub: a row is coefficients of a basis the engine does not have yet)");
     GLASS_HIP(hipSetDevice(c.device));
     e->launch_error.clear();      // (a pass that returned early through GLASS_HIP must not leave its message to the next one)
     // the rows go where run_styles reads them: z rows in front of the mapping network, w rows in its output's place, w+ rows per layer
     const size_t row = latent_row_floats(e);
-    float* d_rows = e->latent_space == GLASS_LATENT_WPLUS ? e->d_dlat : e->latent_space == GLASS_LATENT_W ? e->d_w0 : e->d_z;
+    float* d_rows = latent_rows_dst(e);
     if (latents) memcpy(e->h_pinned, latents, (size_t)P * row * sizeof(float));
     GLASS_HIP(hipEventRecord(e->ev0, e->cur));
     if (latents) {
@@ -888,9 +889,108 @@ extern "C" int glass_engine_set_latent_space(glass_engine* e, int32_t space) {
     REQUIRE(e, GLASS_ERR_ARG, "null engine");
     REQUIRE(!e->finalized, GLASS_ERR_STATE, "set_latent_space: the engine is finalized (its buffers are sized in finalize: call it before)");
     REQUIRE(e->n_lat > 0, GLASS_ERR_STATE, "set_latent_space: W / W+ are latent spaces of a StyleGAN2 generator; this engine has none");
-    REQUIRE(space == GLASS_LATENT_Z || space == GLASS_LATENT_W || space == GLASS_LATENT_WPLUS, GLASS_ERR_ARG,
-            "set_latent_space: space must be 0 (z), 1 (w) or 2 (w+)");
+    REQUIRE(space == GLASS_LATENT_Z || space == GLASS_LATENT_W || space == GLASS_LATENT_WPLUS || space == GLASS_LATENT_SUB, GLASS_ERR_ARG,
+            "set_latent_space: space must be 0 (z), 1 (w), 2 (w+) or 3 (sub)");
     e->latent_space = space;
+    if (space != GLASS_LATENT_SUB) e->sub_G = e->sub_K = 0;      // a shape belongs to sub alone
+    return GLASS_OK;
+}
+
+// ---- latent space sub ----------------------------------------------------------------------------
+extern "C" int glass_subspace_supported(int32_t n_lat, int32_t latent_size, int32_t groups, int32_t components, const int32_t* layer_group,
+                                        char* why, int32_t why_len) {
+    std::string msg;
+    const std::string gk = "subspace (groups " + std::to_string(groups) + ", components " + std::to_string(components) + "): ";
+    if (n_lat < 1) msg = gk + "n_lat must be at least 1: the subspace is one of a StyleGAN2 generator's W";
+    else if (latent_size < 4 || latent_size % 4) msg = gk + "latent_size " + std::to_string(latent_size) + " must be a multiple of 4 (the kernel moves 16 bytes along a dlatent)";
+    else if (components < 1) msg = gk + "components must be at least 1";
+    else if (components > latent_size) msg = gk + "components must not exceed latent_size " + std::to_string(latent_size) + " (W has no more directions)";
+    else if (components > 512) msg = gk + "components must not exceed 512 (a tile of 16 candidates' coefficients is staged in 32 KB of LDS)";
+    else if (groups < 1) msg = gk + "groups must be at least 1";
+    else if (groups > n_lat) msg = gk + "groups must not exceed n_lat " + std::to_string(n_lat) + " (every group holds at least one style layer)";
+    else if (layer_group) {
+        std::vector<int> count(groups, 0);
+        for (int l = 0; l < n_lat && msg.empty(); ++l) {
+            const int g = layer_group[l];
+            if (g < -1 || g >= groups)
+                msg = gk + "layer_group[" + std::to_string(l) + "] = " + std::to_string(g) + " must be -1 (frozen) or a group index in [0, " + std::to_string(groups) + ")";
+            else if (g >= 0) count[g]++;
+        }
+        for (int g = 0; g < groups && msg.empty(); ++g)
+            if (!count[g]) msg = gk + "group " + std::to_string(g) + " is empty: every group needs at least one style layer";
+    }
+    if (why && why_len > 0) snprintf(why, (size_t)why_len, "%s", msg.c_str());
+    REQUIRE(msg.empty(), GLASS_ERR_ARG, msg);
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_subspace_shape(glass_engine* e, int32_t groups, int32_t components) {
+    REQUIRE(e, GLASS_ERR_ARG, "null engine");
+    REQUIRE(e->n_lat > 0, GLASS_ERR_STATE,
+            e->cfg.generator == GLASS_GEN_BIGGAN_DEEP
+                ? "set_subspace_shape: the subspace is one of a StyleGAN2 generator's W; a BigGAN-deep engine has none (its row is z and class bits)"
+                : "set_subspace_shape: the subspace is one of a StyleGAN2 generator's W; this engine has no generator (GPT-2 / img2txt)");
+    REQUIRE(!e->finalized, GLASS_ERR_STATE, "set_subspace_shape: the engine is finalized (its buffers are sized in finalize: call it before)");
+    REQUIRE(e->latent_space == GLASS_LATENT_SUB, GLASS_ERR_STATE, "set_subspace_shape: the engine's latent space is not sub: set_latent_space(3) first");
+    if (int rc = glass_subspace_supported(e->n_lat, e->cfg.latent_size, groups, components, nullptr, nullptr, 0)) return rc;
+    REQUIRE((long long)e->cfg.max_pop * groups * components < (1LL << 31), GLASS_ERR_ARG,
+            "set_subspace_shape: max_pop * groups * components must stay below 2^31");
+    e->sub_G = groups;
+    e->sub_K = components;
+    return GLASS_OK;
+}
+
+extern "C" int glass_engine_set_subspace(glass_engine* e, const int32_t* layer_group, const float* basis, const float* base) {
+    REQUIRE(e && layer_group && basis && base, GLASS_ERR_ARG, "null argument");
+    REQUIRE(e->latent_space == GLASS_LATENT_SUB, GLASS_ERR_STATE, "set_subspace: the engine's latent space is not sub (set_latent_space before finalize)");
+    REQUIRE(e->finalized, GLASS_ERR_STATE, "set_subspace: finalize() first (it allocates the basis)");
+    const int L = e->cfg.latent_size, NL = e->n_lat;
+    if (int rc = glass_subspace_supported(NL, L, e->sub_G, e->sub_K, layer_group, nullptr, 0)) return rc;
+    for (size_t i = 0; i < (size_t)e->sub_K * L; ++i) REQUIRE(std::isfinite(basis[i]), GLASS_ERR_ARG, "set_subspace: the basis holds a value that is not finite");
+    for (size_t i = 0; i < (size_t)NL * L; ++i) REQUIRE(std::isfinite(base[i]), GLASS_ERR_ARG, "set_subspace: the base holds a value that is not finite");
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    GLASS_HIP(hipStreamSynchronize(e->stream));
+    GLASS_HIP(hipMemcpy(e->d_sub_group, layer_group, (size_t)NL * sizeof(int32_t), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemcpy(e->d_sub_basis, basis, (size_t)e->sub_K * L * sizeof(float), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemcpy(e->d_sub_base, base, (size_t)NL * L * sizeof(float), hipMemcpyHostToDevice));
+    e->has_subspace = true;
+    return e->edit.has_anchor ? compute_anchor(e) : GLASS_OK;      // the stored anchor is the row's dlatents under the subspace in force
+}
+
+// The dlatents the pass makes its styles from, through run_dlatents — the launches of a pass.
+extern "C" int glass_engine_expand_latents(glass_engine* e, const float* rows, int32_t P, float* out_dlat) {
+    REQUIRE(e && rows && out_dlat, GLASS_ERR_ARG, "null argument");
+    REQUIRE(e->finalized, GLASS_ERR_STATE, "finalize() first (weights not loaded)");
+    REQUIRE(e->n_lat > 0, GLASS_ERR_STATE, "expand_latents: dlatents belong to a StyleGAN2 generator; this engine has none");
+    REQUIRE(P > 0 && P <= e->cfg.max_pop, GLASS_ERR_ARG, "expand_latents: P out of range (1 .. max_pop)");
+    REQUIRE(e->latent_space != GLASS_LATENT_SUB || e->has_subspace, GLASS_ERR_STATE, "expand_latents: set_subspace() first");
+    GLASS_HIP(hipSetDevice(e->cfg.device));
+    const int L = e->cfg.latent_size, NL = e->n_lat;
+    const size_t row = latent_row_floats(e);
+    e->cur = e->stream;
+    e->launch_error.clear();
+    memcpy(e->h_pinned, rows, (size_t)P * row * sizeof(float));
+    GLASS_HIP(hipMemcpyAsync(latent_rows_dst(e), e->h_pinned, (size_t)P * row * sizeof(float), hipMemcpyHostToDevice, e->cur));
+    const bool prof = e->profiling;
+    e->profiling = false;           // (profile rows belong to a pass)
+    const bool ok = run_dlatents(e, P);
+    e->profiling = prof;
+    GLASS_HIP(hipStreamSynchronize(e->cur));
+    GLASS_HIP(hipGetLastError());
+    if (!ok || !e->launch_error.empty()) {
+        const std::string msg = e->launch_error.empty() ? "expand_latents: the dlatents were refused" : e->launch_error;
+        e->launch_error.clear();
+        glass_set_error(msg);
+        return GLASS_ERR_STATE;
+    }
+    const LatPlan lp = plan_dlatents(e->latent_space, e->trunc_psi, e->trunc_cutoff, NL);
+    if (lp.layered) {
+        GLASS_HIP(hipMemcpy(out_dlat, e->d_dlat, (size_t)P * NL * L * sizeof(float), hipMemcpyDeviceToHost));
+    } else {      // one row serves every layer
+        const size_t rb = (size_t)L * sizeof(float);
+        for (int l = 0; l < NL; ++l)
+            GLASS_HIP(hipMemcpy2D(out_dlat + (size_t)l * L, rb * NL, e->d_w0, rb, rb, (size_t)P, hipMemcpyDeviceToHost));
+    }
     return GLASS_OK;
 }
 

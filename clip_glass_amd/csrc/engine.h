@@ -183,6 +183,12 @@ struct glass_engine {
     float* d_dlat = nullptr;              // [max_pop][n_lat][L] per-layer dlatents: only for space W+ or after trunc_before_finalize
     StyleTile* d_style_tiles = nullptr;   // (segment, n0) tiles of styles_layered_kernel, built with d_dlat
     int n_style_tiles = 0;
+    // ---- latent space sub (include/glass.h "Subspace latent space"): nothing here is allocated unless the space is GLASS_LATENT_SUB ----
+    int sub_G = 0, sub_K = 0;             // glass_engine_set_subspace_shape; 0: not set
+    bool has_subspace = false;            // glass_engine_set_subspace was called
+    float* d_sub_c = nullptr;             // [max_pop][G][K] coefficient rows: where run_pass puts the rows of a pass
+    int* d_sub_group = nullptr;           // [n_lat]
+    float *d_sub_basis = nullptr, *d_sub_base = nullptr;   // [K][L], [n_lat][L]
     // ---- D ----
     float *d_frgb_w = nullptr, *d_frgb_b = nullptr;
     std::vector<DBlock> dblk;
@@ -437,11 +443,12 @@ int finalize_discriminator(glass_engine* e);
 int upload_noise(glass_engine* e, int P, int generation, int first_mb, const glass_noise* noise);
 // What a pass launches between the uploaded rows and the style table, decided before anything is launched:
 //   map: pixel norm + mapping network (space z).  expand: dlatent_expand_kernel applies layer_psi (psi != 1 on at least one layer).
-//   layered: the rows differ per style layer (space w+, or a cutoff inside (0, n_lat)): [P][n_lat][L] in d_dlat and
+//   layered: the rows differ per style layer (space w+ or sub, or a cutoff inside (0, n_lat)): [P][n_lat][L] in d_dlat and
 //   styles_layered_kernel; otherwise ONE row per candidate in d_w0 and the single launch_dense styles launch.
 struct LatPlan { bool map, expand, layered; };
 LatPlan plan_dlatents(int space, float psi, int cutoff, int n_lat);
 size_t latent_row_floats(const glass_engine* e);   // floats evaluate / generate read per row
+float* latent_rows_dst(const glass_engine* e);     // where the rows of a pass go: d_z (z), d_w0 (w), d_dlat (w+), d_sub_c (sub)
 int upload_lat_table(glass_engine* e);             // layer_psi | dlatent_avg -> d_lat_tab (allocates it on first use)
 void run_mapping(glass_engine* e, int P);          // d_z -> d_w0
 bool run_dlatents(glass_engine* e, int P);         // the uploaded rows -> the dlatents the styles are made from (mapping, truncation); false: refused

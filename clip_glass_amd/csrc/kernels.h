@@ -73,6 +73,10 @@ void launch_dense_multi(const DenseDesc* d_desc, int n_desc, int max_N, int P, i
 // (src_layer 0: one row per candidate), in place allowed.  tab = psi[n_pad] | avg[L], n_pad = n_layers rounded up to 4.  L % 4 == 0.
 void launch_dlatent_expand(const float* src, long long src_row, long long src_layer, float* dst, const float* tab, int n_pad, int n_layers,
                            int P, int L, hipStream_t st);
+// latent space `sub`: dst[P][n_lat][L] = base[l] + c[p][layer_group[l]] . B (one fp32 FMA chain over k, then one add); a layer of group -1
+// gets base[l].  c [P][G][K], B [K][L], base [n_lat][L].  false: outside the limits (K <= min(L, 512), L % 4 == 0, 1 <= G <= n_lat).
+bool launch_dlatent_subspace(const float* c, int P, int G, int K, const int* layer_group, int n_lat, int L, const float* B, const float* base,
+                             float* dst, hipStream_t st);
 // one 64-wide piece of a style segment: columns [col0, col0 + n) of the [P][S_total] style table read dlatent row `lat`
 struct StyleTile { int col0, n, lat, pad; };
 // out[p][col] = sum_k dlat[p][lat(col)][k] * wt[k][col] + bias[col] over the tile list: dense_kernel's bits per element

@@ -1190,6 +1190,21 @@ extern "C" int glass_op_latent_anchor(int32_t device, int32_t P, int32_t n_lat, 
     return st.fetch(d, dd);
 }
 
+extern "C" int glass_op_dlatent_subspace(int32_t device, const float* c, int32_t P, int32_t G, int32_t K, const int32_t* layer_group, int32_t n_lat,
+                                         int32_t L, const float* basis, const float* base, float* out) {
+    OPREQ(layer_group && P > 0, "bad argument");
+    TRY(glass_subspace_supported(n_lat, L, G, K, layer_group, nullptr, 0));      // (first: an empty operand of a refused shape may be a null pointer)
+    OPREQ(c && basis && base && out, "bad argument");
+    OPREQ((int64_t)P * G * K < (1LL << 31) && (int64_t)P * n_lat * L < (1LL << 31), "dlatent_subspace: operand too large");
+    Stage st(device);
+    const auto dc = st.in32(c, (size_t)P * G * K), dB = st.in32(basis, (size_t)K * L), db = st.in32(base, (size_t)n_lat * L);
+    const auto dg = st.in_i32(layer_group, n_lat);
+    const auto dout = st.poisoned<float>((size_t)P * n_lat * L, 4 * (size_t)L);      // NaN: an element the launch does not write shows
+    TRY(st.run([&] { return accepted(launch_dlatent_subspace(dc, P, G, K, dg, n_lat, L, dB, db, dout, 0), "dlatent_subspace refused the shape"); }));
+    TRY(st.intact(dout, "dlatent_subspace stored past row P"));
+    return st.fetch(out, dout);
+}
+
 extern "C" int glass_op_image_patches(int32_t device, int32_t n, int32_t S, int32_t ps, int32_t ld, const float* img, float sentinel,
                                       float* patches) {
     OPREQ(img && patches && n > 0 && S > 0 && ps > 0 && S % ps == 0 && ld >= 3 * ps * ps, "bad argument (S % ps == 0, ld >= 3 ps ps)");

@@ -227,6 +227,7 @@ int search_ready(glass_engine* e, const char* what, bool need_init) {
     REQUIRE(e, GLASS_ERR_ARG, "null engine");
     REQUIRE(e->finalized, GLASS_ERR_STATE, std::string(what) + ": finalize() first");
     REQUIRE(e->search.g.pop > 0, GLASS_ERR_STATE, std::string(what) + ": the device search is off (glass_engine_set_search before finalize)");
+    REQUIRE(e->latent_space != GLASS_LATENT_SUB || e->has_subspace, GLASS_ERR_STATE, std::string(what) + ": set_subspace() first (latent space sub)");
     if (need_init && e->search.cma)
         REQUIRE(e->search.ready, GLASS_ERR_STATE, std::string(what) + ": search_init_cma() first (there is no distribution on the device)");
     if (need_init) REQUIRE(e->search.ready, GLASS_ERR_STATE, std::string(what) + ": search_init() first (there is no population on the device)");

@@ -152,7 +152,12 @@ int finalize_generator(glass_engine* e) {
     }
     const LatPlan lp = plan_dlatents(e->latent_space, e->trunc_psi, e->trunc_cutoff, e->n_lat);
     REQUIRE(!lp.expand || !e->dlatent_avg.empty(), GLASS_ERR_STATE, "missing tensor: dlatent_avg (truncation psi != 1 interpolates towards it)");
-    if (e->latent_space == GLASS_LATENT_WPLUS || e->trunc_before_finalize) {
+    const bool sub = e->latent_space == GLASS_LATENT_SUB;
+    if (sub) {
+        REQUIRE(e->sub_K > 0, GLASS_ERR_STATE, "finalize: latent space sub needs its shape: set_subspace_shape(groups, components) before finalize");
+        REQUIRE((long long)c.max_pop * e->sub_G * e->sub_K < (1LL << 31), GLASS_ERR_ARG, "finalize: max_pop * groups * components must stay below 2^31");
+    }
+    if (e->latent_space == GLASS_LATENT_WPLUS || sub || e->trunc_before_finalize) {
         // per-layer rows: the [max_pop][n_lat][L] buffer, and the (segment, n0) tiles of styles_layered_kernel.  Style layer -> dlatent index
         // (models.py:969-1014): conv i in execution order reads row i; the toRGB of block b reads the row of the next block's first conv,
         // 2 b + 1 — which for the last block is the last row.
@@ -167,6 +172,12 @@ int finalize_generator(glass_engine* e) {
         if ((rc = upload(e, &e->d_style_tiles, tiles))) return rc;
         if ((rc = dev_alloc(e, &e->d_dlat, (size_t)c.max_pop * e->n_lat * L))) return rc;
     }
+    if (sub) {      // coefficient rows, and the operands glass_engine_set_subspace fills
+        if ((rc = dev_alloc(e, &e->d_sub_c, (size_t)c.max_pop * e->sub_G * e->sub_K))) return rc;
+        if ((rc = dev_alloc(e, &e->d_sub_group, (size_t)e->n_lat))) return rc;
+        if ((rc = dev_alloc(e, &e->d_sub_basis, (size_t)e->sub_K * L))) return rc;
+        if ((rc = dev_alloc(e, &e->d_sub_base, (size_t)e->n_lat * L))) return rc;
+    }
     return lp.expand ? upload_lat_table(e) : GLASS_OK;
 }
 
@@ -175,12 +186,22 @@ LatPlan plan_dlatents(int space, float psi, int cutoff, int n_lat) {
     LatPlan lp;
     lp.map = space == GLASS_LATENT_Z;
     lp.expand = psi != 1.f && ncut > 0;                                          // models.py:276
-    lp.layered = space == GLASS_LATENT_WPLUS || (lp.expand && ncut < n_lat);    // otherwise one row serves every layer
+    lp.layered = space == GLASS_LATENT_WPLUS || space == GLASS_LATENT_SUB || (lp.expand && ncut < n_lat);    // otherwise one row serves every layer
     return lp;
 }
 
 size_t latent_row_floats(const glass_engine* e) {
+    if (e->latent_space == GLASS_LATENT_SUB) return (size_t)e->sub_G * e->sub_K;      // coefficients, group-major (0 until the shape is set)
     return (size_t)e->cfg.latent_size * (e->latent_space == GLASS_LATENT_WPLUS ? (size_t)e->n_lat : 1);
+}
+
+float* latent_rows_dst(const glass_engine* e) {
+    switch (e->latent_space) {
+        case GLASS_LATENT_SUB: return e->d_sub_c;
+        case GLASS_LATENT_WPLUS: return e->d_dlat;
+        case GLASS_LATENT_W: return e->d_w0;
+        default: return e->d_z;
+    }
 }
 
 int upload_lat_table(glass_engine* e) {
@@ -309,7 +330,7 @@ void run_mapping(glass_engine* e, int P) {
     launch_mapping(e->d_z, e->d_w0, e->d_w1, P, L, 1e-8f, e->map_wt.data(), e->map_b.data(), c.mapping_layers, 0, e->cur);
 }
 
-// The uploaded rows are in d_z (space z), d_w0 (w) or d_dlat (w+): run_pass put them there.
+// The uploaded rows are in d_z (space z), d_w0 (w), d_dlat (w+) or d_sub_c (sub): run_pass put them there.
 bool run_dlatents(glass_engine* e, int P) {
     const glass_config& c = e->cfg;
     const int L = c.latent_size, NL = e->n_lat;
@@ -319,11 +340,25 @@ bool run_dlatents(glass_engine* e, int P) {
         return false;
     }
     if (lp.map) run_mapping(e, P);
+    const bool sub = e->latent_space == GLASS_LATENT_SUB;
+    if (sub) {      // coefficients -> per-layer dlatents, frozen layers included; truncation then runs on them as on w+ rows
+        const int G = e->sub_G, K = e->sub_K;
+        if (!e->has_subspace) {      // (run_pass and the setters refuse this)
+            if (e->launch_error.empty()) e->launch_error = "set_subspace() first";
+            return false;
+        }
+        Prof pr(e, "dlatents.sub", 2.0 * P * G * K * L, 4.0 * ((double)P * G * K + (double)K * L + (double)NL * L + (double)P * NL * L));
+        if (!launch_dlatent_subspace(e->d_sub_c, P, G, K, e->d_sub_group, NL, L, e->d_sub_basis, e->d_sub_base, e->d_dlat, e->cur)) {
+            pr.drop();
+            if (e->launch_error.empty()) e->launch_error = "no kernel accepts layer dlatents.sub (dlatent_subspace: shape outside its limits)";
+            return false;
+        }
+    }
     if (lp.expand) {
         const int nl = lp.layered ? NL : 1;
-        Prof pr(e, "dlatents", 3.0 * P * nl * L, 4.0 * L * (P * (double)(nl + (e->latent_space == GLASS_LATENT_WPLUS ? nl : 1)) + 1));
+        Prof pr(e, "dlatents", 3.0 * P * nl * L, 4.0 * L * (P * (double)(nl + (e->latent_space == GLASS_LATENT_WPLUS || sub ? nl : 1)) + 1));
         if (!lp.layered) launch_dlatent_expand(e->d_w0, L, 0, e->d_w0, e->d_lat_tab, e->lat_pad, 1, P, L, e->cur);                       // in place
-        else if (e->latent_space == GLASS_LATENT_WPLUS) launch_dlatent_expand(e->d_dlat, (long long)NL * L, L, e->d_dlat, e->d_lat_tab, e->lat_pad, NL, P, L, e->cur);   // in place
+        else if (e->latent_space == GLASS_LATENT_WPLUS || sub) launch_dlatent_expand(e->d_dlat, (long long)NL * L, L, e->d_dlat, e->d_lat_tab, e->lat_pad, NL, P, L, e->cur);   // in place
         else launch_dlatent_expand(e->d_w0, L, 0, e->d_dlat, e->d_lat_tab, e->lat_pad, NL, P, L, e->cur);
     }
     return true;

@@ -106,6 +106,12 @@ def load_library(path=None):
         lib.glass_engine_set_truncation.argtypes = [C.c_void_p, C.c_float, C.c_int32]
         lib.glass_engine_latent_row.argtypes = [C.c_void_p, ip, ip]
         lib.glass_engine_map_latents.argtypes = [C.c_void_p, fp, C.c_int32, fp]
+    if hasattr(lib, "glass_subspace_supported"):        # (absent from older A/B builds loaded through GLASS_LIB)
+        ip = C.POINTER(C.c_int32)
+        lib.glass_subspace_supported.argtypes = [C.c_int32] * 4 + [ip, C.c_char_p, C.c_int32]
+        lib.glass_engine_set_subspace_shape.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        lib.glass_engine_set_subspace.argtypes = [C.c_void_p, ip, fp, fp]
+        lib.glass_engine_expand_latents.argtypes = [C.c_void_p, fp, C.c_int32, fp]
     if hasattr(lib, "glass_lpips_supported"):           # (absent from older A/B builds loaded through GLASS_LIB)
         lib.glass_lpips_supported.argtypes = [C.c_int32] * 2
         lib.glass_engine_set_lpips_target.argtypes = [C.c_void_p, fp, C.c_int32]
@@ -346,7 +352,24 @@ def mixed_search_supported(pop, n_real, n_bits, n_obj, algorithm):
     return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
 
 
-LATENT_SPACES = {"z": 0, "w": 1, "w+": 2}     # GLASS_LATENT_Z / _W / _WPLUS
+LATENT_SPACES = {"z": 0, "w": 1, "w+": 2, "sub": 3}     # GLASS_LATENT_Z / _W / _WPLUS / _SUB
+SUBSPACE_MAX_COMPONENTS = 512
+
+
+def subspace_supported(n_lat, latent_size, groups, components, layer_group=None):
+    """(ok, message) for latent space "sub" with `groups` groups of style layers and `components` directions on a generator of n_lat style
+    layers (layer_group: int [n_lat], -1 = frozen; None checks the shape alone): the library's own rule (glass_subspace_supported), the one
+    set_subspace_shape and set_subspace apply.  Host only."""
+    lib = load_library()
+    lg = None
+    if layer_group is not None:
+        lg = np.ascontiguousarray(layer_group, dtype=np.int32).reshape(-1)
+        if lg.size != int(n_lat):
+            return False, "subspace: layer_group must hold n_lat = %d values, got %d" % (int(n_lat), lg.size)
+    why = C.create_string_buffer(512)
+    rc = lib.glass_subspace_supported(int(n_lat), int(latent_size), int(groups), int(components),
+                                      lg.ctypes.data_as(C.POINTER(C.c_int32)) if lg is not None else None, why, len(why))
+    return (True, "") if rc == 0 else (False, why.value.decode())
 
 
 def latent_space_id(name):
@@ -387,7 +410,7 @@ class Engine:
                  mbstd_group=4, device=0, biggan=None, clip_resize=0, clip_normalize=0, clip_resnet=None,
                  clip_views=0, clip_view_min=0.5, clip_view_flip=True, clip_view_fixed=False,
                  latent_space="z", truncation_psi=1.0, truncation_cutoff=None, lpips_size=0, lpips_lambda=0.0, sim_columns=0,
-                 anchor=False, anchor_lambda=0.0):
+                 anchor=False, anchor_lambda=0.0, subspace_shape=None):
         """`biggan` = dict(layers=[(up, in_mult, out_mult), ...], attention_pos, ch, z_dim, num_classes, n_stats, eps,
         truncation) selects the BigGAN-deep generator (channels must then be empty, no discriminator).
         clip_resize / clip_normalize: how a generated image is prepared for CLIP (include/glass.h); (0, 0) is the reference's way.
@@ -407,7 +430,9 @@ class Engine:
         entry of set_targets(..., mode="pareto"), and n_obj must be prompt_n_obj(K, ...); 0 (default): the one similarity column.
         anchor = True turns the latent anchor on (include/glass.h "Image editing"; StyleGAN2 only): the mean squared distance between a
         candidate's dlatents and those of the row given to set_anchor().  anchor_lambda = 0: one more, last, column of F and n_obj must
-        count it (edit_n_obj); > 0: F[:, 0] += anchor_lambda * d and n_obj stays."""
+        count it (edit_n_obj); > 0: F[:, 0] += anchor_lambda * d and n_obj stays.
+        latent_space "sub" with subspace_shape = (G, K) (include/glass.h "Subspace latent space"): a row is G * K coefficients of K
+        directions of W for each of G groups of style layers; set_subspace(layer_group, basis, base) after finalize() gives the directions."""
         self.lib = load_library()
         cfg = GlassConfigEdit()
         cfg.anchor, cfg.anchor_lambda = int(bool(anchor)), float(anchor_lambda)
@@ -468,6 +493,12 @@ class Engine:
         try:
             if latent_space != "z":
                 _check(self.lib, self.lib.glass_engine_set_latent_space(self._h, latent_space_id(latent_space)))
+            if latent_space == "sub" and subspace_shape is None:
+                raise ValueError('latent_space "sub" needs subspace_shape=(groups, components)')
+            if subspace_shape is not None:
+                if latent_space != "sub":
+                    raise ValueError('subspace_shape belongs to latent_space "sub", not %r' % (latent_space,))
+                self.set_subspace_shape(*subspace_shape)
             if float(truncation_psi) != 1.0 or truncation_cutoff is not None:
                 self.set_truncation(truncation_psi, truncation_cutoff)
         except Exception:
@@ -761,9 +792,41 @@ class Engine:
 
     # --- latent spaces / truncation -------------------------------------------
     def set_latent_space(self, name):
-        """Between construction and finalize(): "z", "w" or "w+" (include/glass.h)."""
+        """Between construction and finalize(): "z", "w", "w+" or "sub" (include/glass.h; "sub" needs set_subspace_shape after it)."""
         _check(self.lib, self.lib.glass_engine_set_latent_space(self._h, latent_space_id(name)))
         self.latent_space = name
+
+    def set_subspace_shape(self, groups, components):
+        """Between set_latent_space("sub") and finalize(): a row is groups * components coefficients."""
+        _check(self.lib, self.lib.glass_engine_set_subspace_shape(self._h, int(groups), int(components)))
+        self.subspace_shape = (int(groups), int(components))
+
+    def set_subspace(self, layer_group, basis, base):
+        """After finalize(), any time: layer_group int [n_lat] (group of each style layer, -1 = frozen), basis float32 [K, L], base [n_lat, L] or
+        [L] (tiled over the layers): dlatents[p][l] = base[l] + c[p][layer_group[l]] . basis (include/glass.h)."""
+        G, K = getattr(self, "subspace_shape", (0, 0))
+        n_lat, L = self.latent_row()[1], int(self.cfg.latent_size)
+        lg = np.ascontiguousarray(layer_group, dtype=np.int32).reshape(-1)
+        B, b = _f32(basis), _f32(base)
+        if b.shape == (L,):
+            b = np.ascontiguousarray(np.broadcast_to(b, (n_lat, L)))
+        if lg.shape != (n_lat,) or B.shape != (K, L) or b.shape != (n_lat, L):
+            raise ValueError("set_subspace: layer_group [%d], basis [%d, %d] and base [%d, %d] (or [%d]) expected, got %r, %r, %r"
+                             % (n_lat, K, L, n_lat, L, L, lg.shape, B.shape, b.shape))
+        _check(self.lib, self.lib.glass_engine_set_subspace(self._h, lg.ctypes.data_as(C.POINTER(C.c_int32)), _fp(B), _fp(b)))
+
+    def expand_latents(self, rows):
+        """The dlatents the pass makes its styles from, after truncation: rows [P, floats_per_row] of the engine's space -> float32
+        [P, n_lat, L], P <= max_pop (StyleGAN2 engines; the kernels of the pass).  Flattened, a result is a w+ row."""
+        z = self._rows(rows)
+        n_lat, L = self.latent_row()[1], int(self.cfg.latent_size)
+        out = np.empty((z.shape[0], n_lat, L), dtype=np.float32)
+        _check(self.lib, self.lib.glass_engine_expand_latents(self._h, _fp(z), z.shape[0], _fp(out)))
+        return out
+
+    @staticmethod
+    def subspace_supported(n_lat, latent_size, groups, components, layer_group=None):
+        return subspace_supported(n_lat, latent_size, groups, components, layer_group)
 
     def set_truncation(self, psi, cutoff=None):
         """The truncation trick: dlatents = lerp(dlatent_avg, dlatents, layer_psi); psi in [0, 1], cutoff None = every layer."""

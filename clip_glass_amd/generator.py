@@ -12,7 +12,7 @@ import numpy as np
 
 from . import synth
 from .engine import (LATENT_SPACES, PROMPT_MAX, PROMPT_MODES, Engine, clip_geometry_supported, clip_resnet_supported, clip_view_permille,
-                     clip_views_supported, clip_views_tower_rows, lpips_n_obj, lpips_supported, prompt_n_obj)
+                     clip_views_supported, clip_views_tower_rows, lpips_n_obj, lpips_supported, prompt_n_obj, subspace_supported)
 from .utils import save_grid, save_image
 
 CLIP_VIT_B32 = (768, 12, 12, 32, 224, 512)
@@ -71,7 +71,42 @@ def latent_options(config):
     if (space != DEFAULT_LATENT_SPACE or psi != 1.0 or cutoff is not None) and name.split("_")[0] != "StyleGAN2":
         raise ValueError("latent_space / truncation_psi / truncation_cutoff belong to the StyleGAN2 configs (a mapping network and an "
                          "average dlatent); config %r has neither: leave them unset" % name)
+    subspace_options(config)        # the subspace_* keys: refused without latent_space "sub", and on the configs refused above
     return space, psi, cutoff
+
+
+def subspace_options(config):
+    """The options of latent space "sub" (include/glass.h "Subspace latent space"): None unless config.latent_space is "sub", else
+    dict(components, layers, samples, basis) from subspace_components (K, default 64, capped at dim_z), subspace_layers (a spec for
+    subspace.parse_layer_groups, default: one group of every layer), subspace_samples (rows of z the mapping network is probed with, default
+    problem.PROBE_ROWS) and subspace_basis (an npz of subspace.save to use instead of probing).  ValueError by name: a subspace_* key
+    without latent_space "sub"; any of it on a BigGAN or GPT2 config; a K or sample count out of range; a basis file whose directions do not
+    have the network's dim_z entries."""
+    from . import subspace
+    vals = {k: getattr(config, k, None) for k in subspace.SUBSPACE_KEYS}
+    given = [k for k in subspace.SUBSPACE_KEYS if vals[k] is not None]
+    space = getattr(config, "latent_space", None) or DEFAULT_LATENT_SPACE
+    name = str(getattr(config, "config", ""))
+    if (given or space == "sub") and name.split("_")[0] != "StyleGAN2":
+        what = "a BigGAN row is z and class bits" if name.startswith("DeepMindBigGAN") else "the GPT2 config searches token rows"
+        raise ValueError("%s: latent space sub is a subspace of a StyleGAN2 generator's W; config %r has none (%s): leave these keys unset"
+                         % (", ".join(given or ["latent_space"]), name, what))
+    if space != "sub":
+        if given:
+            raise ValueError("%s set without latent_space 'sub': the subspace keys describe that space alone" % ", ".join(given))
+        return None
+    K = subspace.components_of(config)
+    if K < 1:
+        raise ValueError("subspace_components must be at least 1, got %r" % (vals["subspace_components"],))
+    N = vals["subspace_samples"]
+    if N is not None and vals["subspace_basis"] is None and int(N) < K + 1:
+        raise ValueError("subspace_samples=%d rows cannot carry %d principal directions: at least components + 1 are needed" % (int(N), K))
+    if vals["subspace_basis"] is not None:
+        got = subspace.load(vals["subspace_basis"], latent_size=int(config.dim_z))      # (a file of another network's L is refused here)
+        if got["components"].shape[0] < K and vals["subspace_components"] is not None:
+            raise ValueError("subspace_basis %r holds %d directions and subspace_components asks for %d"
+                             % (str(vals["subspace_basis"]), got["components"].shape[0], K))
+    return dict(components=K, layers=vals["subspace_layers"], samples=None if N is None else int(N), basis=vals["subspace_basis"])
 
 
 # ---- perceptual objective (opt-in, include/glass.h): LPIPS-VGG16 distance of every candidate's image to a target image ----
@@ -697,6 +732,7 @@ class Generator:
         self.clip_views = int(getattr(config, "clip_views", 0) or 0)
         # latent space / truncation trick (opt-in, include/glass.h); refused here for the BigGAN and GPT2 configs, before anything is loaded
         self.latent_space, self.truncation_psi, self.truncation_cutoff = latent_options(config)
+        self.subspace = subspace_options(config)       # latent space "sub" (opt-in): None in every other space
         def view_opt(key, default):      # (a flag the command line left unset arrives as None)
             v = getattr(config, key, None)
             return default if v is None else v
@@ -774,6 +810,10 @@ class Generator:
                     self.engine.close()
                     raise ValueError("device_search: %s" % ex)
         else:
+            sub_kw = {}
+            if self.subspace is not None:       # asked before an engine is built: the library's own rule
+                self._plan_subspace(config)
+                sub_kw = dict(subspace_shape=self.subspace["shape"])
             self.engine = Engine(self.model.channels[::-1], latent_size=config.dim_z,
                                  mapping_layers=getattr(config, "mapping_layers", 8), batch_size=config.batch_size,
                                  use_discriminator=bool(config.use_discriminator and base_n_obj == 2),
@@ -783,7 +823,7 @@ class Generator:
                                  noise_mode=getattr(config, "noise_mode", 1),
                                  noise_seed=getattr(config, "noise_seed", 0), device=device, clip_resize=clip_resize,
                                  clip_normalize=clip_normalize, latent_space=self.latent_space,
-                                 truncation_psi=self.truncation_psi, truncation_cutoff=self.truncation_cutoff, **tower)
+                                 truncation_psi=self.truncation_psi, truncation_cutoff=self.truncation_cutoff, **sub_kw, **tower)
             if self.device_search:
                 try:      # bounds: the config's own (z); a search in w / w+ sets its probed bounds after finalize (set_search_operators)
                     self.engine.set_search(config.algorithm, int(config.pop_size), float(np.float32(config.problem_args["xl"])),
@@ -813,6 +853,8 @@ class Generator:
             self.engine.set_lpips_target(self.lpips_target)
         if self.latent_space != DEFAULT_LATENT_SPACE:       # the row width of latent.StyleGAN2LatentSpace / operators follows the loaded network
             config.n_lat = self.engine.latent_row()[1]
+        if self.subspace is not None:
+            self._set_subspace(config)
         texts = [v for kind, v, _ in (self.prompts["entries"] if self.prompts else []) if kind == "text"]
         if getattr(config, "target_features", None) is not None:            # pre-computed text feature
             self.text_features = np.asarray(config.target_features, np.float32).reshape(1, -1)
@@ -843,6 +885,62 @@ class Generator:
             from .parallel import ShardedEvaluator
             self.sharder = ShardedEvaluator(self.engine, dist, dist.get_rank(), dist.get_world_size(), config.batch_size,
                                             device=device)
+
+    def _plan_subspace(self, config):
+        """Latent space "sub", before the engine exists: the groups of the style layers (subspace_layers; else the basis file's own; else one
+        group of every layer), the number of directions, and the library's verdict on both (subspace_supported) — ValueError with its words."""
+        from . import subspace
+        sub = self.subspace
+        n_lat, L = 2 * len(self.model.channels), int(config.dim_z)
+        sub["file"] = subspace.load(sub["basis"], latent_size=L) if sub["basis"] is not None else None
+        if sub["layers"] is None and sub["file"] is not None and sub["file"]["layer_group"] is not None:
+            lg = np.asarray(sub["file"]["layer_group"], np.int32)
+            if lg.shape != (n_lat,):
+                raise ValueError("subspace_basis %r: its layer_group holds %d layers and the network has %d: give subspace_layers"
+                                 % (str(sub["basis"]), lg.size, n_lat))
+        else:
+            lg = subspace.parse_layer_groups(sub["layers"], n_lat)
+        K = sub["components"]
+        if sub["file"] is not None:
+            K = min(K, sub["file"]["components"].shape[0])
+        G = subspace.n_groups(lg)
+        ok, msg = subspace_supported(n_lat, L, G, K, lg)
+        if not ok:
+            raise ValueError("latent_space 'sub': %s" % msg)
+        sub.update(layer_group=lg, shape=(G, K), n_lat=n_lat)
+
+    def _set_subspace(self, config):
+        """After finalize: the basis — the file's, or the PCA of the probed mapping network —, the base (the mean dlatent on every layer; with
+        edit_latent the file's w or w+ row: the source, whose coefficients are the zero row), into the engine and into subspace.npz."""
+        from . import subspace
+        sub = self.subspace
+        G, K = sub["shape"]
+        if sub["file"] is not None:
+            mean, comp, std = sub["file"]["mean"], sub["file"]["components"][:K], sub["file"]["stdev"][:K]
+        else:
+            mean, comp, std = subspace.build(self, config)
+        base = None
+        if self.edit is not None and self.edit["latent"] is not None:
+            base = load_edit_latent(self.edit["latent"])
+            L = int(config.dim_z)
+            if base.size not in (L, sub["n_lat"] * L):
+                raise ValueError("edit_latent holds %d floats; with latent_space 'sub' it is the base of the subspace: a w row (%d floats) or a "
+                                 "w+ row (%d floats)" % (base.size, L, sub["n_lat"] * L))
+        basis, base = subspace.operands(mean, comp, std, sub["n_lat"], base)
+        self.engine.set_subspace(sub["layer_group"], basis, base)
+        sub.update(mean=mean, components=comp, stdev=std, basis=basis, base=base)
+        config.subspace_shape = (G, K)        # the row width of latent.StyleGAN2LatentSpace / operators follows it
+        folder = getattr(config, "tmp_folder", None)
+        if folder is not None and int(os.environ.get("RANK", "0")) == 0:      # (under --dist every rank computes the same basis: rank 0 writes it)
+            os.makedirs(folder, exist_ok=True)
+            subspace.save(os.path.join(folder, "subspace.npz"), mean, comp, std, sub["layer_group"])
+
+    def expand_latents(self, rows):
+        """rows of this Generator's latent space -> the dlatents the pass makes its styles from, [N, n_lat, L], in slices of the engine's
+        capacity.  Flattened, a result is a w+ row (what edit_latent takes)."""
+        x = np.asarray(rows, dtype=np.float32)
+        cap = int(self.engine.cfg.max_pop)
+        return np.concatenate([self.engine.expand_latents(x[i:i + cap]) for i in range(0, x.shape[0], cap)])
 
     def _set_prompts(self, text_features):
         """Build the set's features [T, E] in the order of prompt_options' entries and hand it to the engine.  text_features: the encoded
@@ -877,7 +975,9 @@ class Generator:
         entries of the set — the single target is a set of one — become directions away from the source's text (an image prompt: away from
         the source image's own whole-image feature), and edit_latent's row becomes the latent anchor."""
         ed = self.edit
-        if ed["latent"] is not None:
+        if ed["latent"] is not None and self.latent_space == "sub":
+            self.edit_row = np.zeros(self.latent_width(), np.float32)      # the file's row is the subspace's base: the source is the zero row
+        elif ed["latent"] is not None:
             self.edit_row = load_edit_latent(ed["latent"])
             width = self.latent_width()
             if self.edit_row.size != width:

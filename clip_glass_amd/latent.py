@@ -13,13 +13,18 @@ def stylegan2_n_lat(config):
 
 class StyleGAN2LatentSpace:
     """latent.py:27-41.  Rows of the config's latent space (`config.latent_space`, default "z"): dim_z floats for z and w, n_lat * dim_z
-    (layer-major) for w+.  The attribute keeps the reference's name `z` whatever the space; state_dict() says what the rows are."""
-    STATE_KEYS = {"z": "z", "w": "w", "w+": "w_plus"}
+    (layer-major) for w+, groups * components coefficients (group-major) for sub.  The attribute keeps the reference's name `z` whatever
+    the space; state_dict() says what the rows are."""
+    STATE_KEYS = {"z": "z", "w": "w", "w+": "w_plus", "sub": "sub"}
 
     def __init__(self, config):
         self.config = config
         self.space = getattr(config, "latent_space", None) or "z"
-        self.width = self.config.dim_z * (stylegan2_n_lat(config) if self.space == "w+" else 1)
+        if self.space == "sub":
+            from .subspace import row_width
+            self.width = row_width(config)
+        else:
+            self.width = self.config.dim_z * (stylegan2_n_lat(config) if self.space == "w+" else 1)
         self.z = np.random.randn(self.config.batch_size, self.width).astype(np.float32)
 
     def set_values(self, z):

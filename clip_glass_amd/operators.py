@@ -137,10 +137,16 @@ def get_operators(config):
         if getattr(config, "edit_latent", None) is not None:      # image editing: the search starts at the source row, in any space
             from .generator import DEFAULT_EDIT_SIGMA, load_edit_latent
             sigma = getattr(config, "edit_sigma", None)
-            return dict(sampling=EditSampling(load_edit_latent(config.edit_latent), DEFAULT_EDIT_SIGMA if sigma is None else sigma),
+            if space == "sub":        # the file's row is the subspace's base: the search starts at the zero row of coefficients
+                from .subspace import row_width
+                source = np.zeros(row_width(config), np.float32)
+            else:
+                source = load_edit_latent(config.edit_latent)
+            return dict(sampling=EditSampling(source, DEFAULT_EDIT_SIGMA if sigma is None else sigma),
                         crossover=get_crossover("real_sbx", prob=1.0, eta=3.0),
                         mutation=get_mutation("real_pm", prob=0.5, eta=3.0))
-        if space != "z":      # same crossover and mutation; the initial population comes through the mapping network
+        if space not in ("z", "sub"):      # same crossover and mutation; the initial population comes through the mapping network
+            # (sub: unit-variance coefficients, drawn as z's variables are — NormalRandomSampling below)
             from .latent import stylegan2_n_lat
             return dict(sampling=MappedNormalSampling(config.dim_z, stylegan2_n_lat(config) if space == "w+" else 1),
                         crossover=get_crossover("real_sbx", prob=1.0, eta=3.0),

@@ -90,6 +90,7 @@ SIGNATURES = {
     "glass_op_assemble_F_set": [i32, i32, i32, fp, fp, fp, fp, fp],
     "glass_op_cosine_set_dir": [i32, i32, i32, i32, i32, fp, fp, fp, fp, i32, fp, fp, fp],
     "glass_op_latent_anchor": [i32, i32, i32, i32, i32, fp, fp, fp],
+    "glass_op_dlatent_subspace": [i32, fp, i32, i32, i32, ip, i32, i32, fp, fp, fp],
     "glass_op_image_patches": [i32, i32, i32, i32, i32, fp, f32, fp],
     "glass_op_rn_token0_rows": [i32, i32, i32, i32, fp, fp],
     "glass_op_lpips_input": [i32, i32, i32, i32, fp, fp],
@@ -957,6 +958,24 @@ def latent_anchor(w, a, device=0):
     d = np.empty(w.shape[0], np.float32)
     _check(lib, lib.glass_op_latent_anchor(device, w.shape[0], n_lat, L, int(w.ndim == 3), _fp(w), _fp(a), _fp(d)))
     return d
+
+
+def dlatent_subspace(c, layer_group, basis, base, device=0):
+    """c [P, G, K] coefficients, layer_group int [n_lat] (-1: frozen), basis [K, L], base [n_lat, L] -> dlatents [P, n_lat, L]:
+    dlatent_subspace_kernel (latent space sub, include/glass.h).  The rule's refusals come back as RuntimeError with its words."""
+    lib = _lib()
+    c, basis, base = _f32(c), _f32(basis), _f32(base)
+    lg = np.ascontiguousarray(layer_group, dtype=np.int32)
+    if c.ndim != 3 or basis.ndim != 2 or base.ndim != 2 or lg.ndim != 1:
+        raise ValueError("dlatent_subspace: c [P, G, K], layer_group [n_lat], basis [K, L] and base [n_lat, L] expected, got %r, %r, %r, %r"
+                         % (c.shape, lg.shape, basis.shape, base.shape))
+    P, G, K = c.shape
+    n_lat, L = base.shape
+    if basis.shape != (K, L) or lg.shape != (n_lat,):
+        raise ValueError("dlatent_subspace: basis must be [%d, %d] and layer_group [%d], got %r and %r" % (K, L, n_lat, basis.shape, lg.shape))
+    out = np.empty((P, n_lat, L), np.float32)
+    _check(lib, lib.glass_op_dlatent_subspace(device, _fp(c), P, G, K, lg.ctypes.data_as(ip), n_lat, L, _fp(basis), _fp(base), _fp(out)))
+    return out
 
 
 def assemble_F(sim, dis=None, device=0):

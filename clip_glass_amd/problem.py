@@ -58,7 +58,11 @@ class GenerationProblem(Problem):
         self.generator = Generator(config, dist=dist)
         self.config = self.generator.config       # the caller's config, or the copy with one more objective (perceptual objective, lambda = 0)
         args = dict(self.config.problem_args)
-        if getattr(self.generator, "latent_space", "z") != "z":
+        if getattr(self.generator, "latent_space", "z") == "sub":
+            # coefficients of unit-variance directions, as z's variables are: the config's own bounds (+-10), no probe of w's range
+            n_var = int(self.generator.latent_width())
+            args.update(n_var=n_var, n_constr=n_var)
+        elif getattr(self.generator, "latent_space", "z") != "z":
             args.update(dlatent_problem_args(config, self.generator))
         if getattr(self.generator, "edit_row", None) is not None:      # image editing: generation 0 starts at this row
             lo, hi = edit_bounds(args["xl"], args["xu"], self.generator.edit_row)

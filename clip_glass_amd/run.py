@@ -55,7 +55,18 @@ def build_parser():
     p.add_argument("--clip-view-fixed", action="store_true", default=None, help="the same crops in every generation (default: redrawn per generation)")
     p.add_argument("--latent-space", type=str, default=None, choices=list(LATENT_SPACES),
                    help="StyleGAN2 configs: what the search varies — z (default: the reference's search, through the mapping network), w (the "
-                        "dlatent itself) or w+ (one dlatent per style layer).  w / w+ depart from the reference's run.py on purpose")
+                        "dlatent itself), w+ (one dlatent per style layer) or sub (coefficients of the principal directions of W, per group of "
+                        "style layers: --subspace-*).  w / w+ / sub depart from the reference's run.py on purpose")
+    p.add_argument("--subspace-components", type=int, default=None,
+                   help="with --latent-space sub: directions per group of style layers (default 64, capped at the dlatent's size)")
+    p.add_argument("--subspace-layers", type=str, default=None, metavar="SPEC",
+                   help="with --latent-space sub: comma-separated inclusive ranges of style layers, one group of coefficients per range "
+                        "(\"0-3,4-7,8-17\"); layers not named keep the base's dlatent.  Default: one group of every layer")
+    p.add_argument("--subspace-samples", type=int, default=None,
+                   help="with --latent-space sub: rows of z the mapping network is probed with for the PCA (default 4096)")
+    p.add_argument("--subspace-basis", type=str, default=None, metavar="FILE.npz",
+                   help="with --latent-space sub: use this basis (mean, components, stdev[, layer_group]: the subspace.npz of an earlier run, "
+                        "or a GANSpace export) instead of probing the mapping network")
     p.add_argument("--truncation-psi", type=float, default=None,
                    help="StyleGAN2 configs: the truncation trick, dlatents pulled towards the average dlatent; in [0, 1], 1 (default) is off")
     p.add_argument("--truncation-cutoff", type=int, default=None,
@@ -109,7 +120,7 @@ def build_parser():
                         "(--islands, if given, must agree; not with migration, --prompt-mode pareto or an edit source)")
     p.add_argument("--algorithm", type=str, default=None, choices=["ga", "nsga2", "cmaes"],
                    help="the search rule (default: the config's own — nsga2 with the discriminator, ga without).  cmaes: separable CMA-ES, one "
-                        "objective and real-valued rows (the StyleGAN2 _nod configs, in z, w or w+; an LPIPS / anchor distance folded in with "
+                        "objective and real-valued rows (the StyleGAN2 _nod configs, in z, w, w+ or sub; an LPIPS / anchor distance folded in with "
                         "lambda > 0); with --device-search its generation step runs on the GPU.  Off by default — the reference has GA / NSGA-II")
     p.add_argument("--cma-sigma", type=float, default=None,
                    help="with --algorithm cmaes: the initial step size (default 1: in z, generation 0 is then drawn from the reference's own "
@@ -175,7 +186,7 @@ def main(argv=None, extra_config=None):
     over = {k: v for k, v in vars(config).items() if v is not None}
     vars(config).update(get_config(config.config))                             # run.py:25
     for k in ("weights", "clip_weights", "clip_model", "clip_resnet", "clip_preprocess", "clip_views", "clip_view_min", "clip_view_flip",
-              "clip_view_fixed", "latent_space", "truncation_psi", "truncation_cutoff", "lpips_target", "lpips_size", "lpips_lambda", "lpips_weights",
+              "clip_view_fixed", "latent_space", "subspace_components", "subspace_layers", "subspace_samples", "subspace_basis", "truncation_psi", "truncation_cutoff", "lpips_target", "lpips_size", "lpips_lambda", "lpips_weights",
               "bpe_path", "pop_size", "stochastic", "target_weight", "prompt_mode", "device_search", "edit_image", "edit_latent", "source_text",
               "anchor_lambda", "edit_sigma", "algorithm", "cma_sigma", "islands", "migrate_every", "migrants"):
         if k in over:
@@ -258,8 +269,11 @@ def main(argv=None, extra_config=None):
         X = np.stack([p.X for p in res.pop])
     ls = config.latent(config)
     ls.set_from_population(X)
+    saved = ls.state_dict()
+    if getattr(problem.generator, "latent_space", None) == "sub":      # next to the coefficients: the dlatents they stand for, which --edit-latent takes
+        saved = dict(saved, w_plus=problem.generator.expand_latents(saved["sub"]).reshape(len(saved["sub"]), -1))
     with open(os.path.join(config.tmp_folder, "ls_result"), "wb") as f:        # run.py:101 (same file name, npz payload)
-        np.savez(f, **ls.state_dict())
+        np.savez(f, **saved)
     if config.problem_args["n_obj"] == 1:
         X = np.atleast_2d(res.X)
     else:

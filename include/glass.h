@@ -271,6 +271,7 @@ void glass_engine_destroy(glass_engine* e);
  *   GLASS_LATENT_Z (default): rows [latent_size].  Pixel norm + mapping network, then truncation, then synthesis.
  *   GLASS_LATENT_W: rows [latent_size] are dlatents: no pixel norm, no mapping; the row goes to every style layer.
  *   GLASS_LATENT_WPLUS: rows [n_lat * latent_size], layer-major: row l goes to the style layers with index l.
+ *   GLASS_LATENT_SUB: rows [groups * components] are coefficients of directions of W per group of style layers ("Subspace latent space" below).
  * Truncation: dlatents = lerp(dlatent_avg, dlatents, layer_psi) with torch.lerp's fp32 rule (weight < 0.5: a + w (b - a), otherwise
  * b - (b - a)(1 - w)); layer_psi[l] = psi for l < cutoff (cutoff -1: every layer), 1 elsewhere; a layer with psi 1 keeps its row bit
  * for bit, and psi = 1 or cutoff = 0 is truncation off (models.py:276).  The engine applies layer_psi in EVERY space, whereas the
@@ -291,12 +292,49 @@ void glass_engine_destroy(glass_engine* e);
 int glass_host_layer_psi(int32_t n_lat, float psi, int32_t cutoff, float* out);
 int glass_engine_set_latent_space(glass_engine* e, int32_t space);
 int glass_engine_set_truncation(glass_engine* e, float psi, int32_t cutoff);
-/* What evaluate / generate read per row: floats_per_row = latent_size (z, w; BigGAN: z_dim + num_classes) or n_lat * latent_size (w+);
+/* What evaluate / generate read per row: floats_per_row = latent_size (z, w; BigGAN: z_dim + num_classes), n_lat * latent_size (w+) or
+ * groups * components (sub; 0 until glass_engine_set_subspace_shape);
  * n_lat = 0 for an engine that is not a StyleGAN2 one.  Nullable each. */
 int glass_engine_latent_row(glass_engine* e, int32_t* floats_per_row, int32_t* n_lat);
 /* Pixel norm + mapping network, untruncated, with the kernels the pass uses: z host float32 [P][latent_size] -> out_w [P][latent_size].
  * P in [1, max_pop] (no multiple of batch_size needed).  Seeds W / W+ populations. */
 int glass_engine_map_latents(glass_engine* e, const float* z, int32_t P, float* out_w);
+
+/* Subspace latent space (opt-in; off unless glass_engine_set_latent_space(GLASS_LATENT_SUB) is called, and then nothing below is allocated
+ * or launched; departs from the reference's run.py, which searches z): a fourth StyleGAN2 space whose rows are COEFFICIENTS of a few
+ * directions of W (GANSpace: the principal ones), applied to ranges of style layers only (StyleCLIP's coarse / middle / fine edits).
+ *
+ * The rule.  The style layers 0 .. n_lat - 1 are assigned to G groups by layer_group[n_lat]: a value in [0, G), or -1 for a frozen layer;
+ * every group is non-empty and need not be contiguous.  A row is [G][K] float32 coefficients, group-major: floats_per_row = G K.  With a
+ * basis B [K][L], a base [n_lat][L] and g = layer_group[l]:
+ *   acc[p][g][j]  = fma(c[p][g][K-1], B[K-1][j], ... fma(c[p][g][1], B[1][j], fma(c[p][g][0], B[0][j], 0.f)) ...)
+ *                   ONE fp32 FMA chain, k ascending
+ *   dlat[p][l][j] = base[l][j] + acc[p][g][j]      (one fp32 add)          for g >= 0
+ *   dlat[p][l][j] = base[l][j]                     (a copy, bit for bit)   for g == -1
+ * The truncation trick (layer_psi) then runs on dlat exactly as it does on w+ rows, in place, and everything after it is the w+ path: the
+ * layered style affines, the latent anchor on the per-layer dlatents.  A candidate's dlatents depend on its own row alone — not on P, its
+ * position in the launch, the chunk or the shard —, the product of (candidate, group) is computed once and written to every layer of the
+ * group, and a row of zeros gives base bit for bit.  Numpy mirror: tests/subspace_ref.py.
+ *
+ * glass_subspace_supported: the one rule (host only: callable without a GPU), applied by both setters.  latent_size % 4 == 0; 1 <=
+ * components <= min(latent_size, 512); 1 <= groups <= n_lat; each layer_group value -1 or in [0, groups) and every group non-empty
+ * (layer_group NULL: the shape alone).  max_pop * groups * components < 2^31 is checked where max_pop is known (set_subspace_shape,
+ * finalize).  Returns GLASS_OK, or GLASS_ERR_ARG with the reason in glass_last_error() and, when why is not NULL, in why[why_len].
+ * glass_engine_set_subspace_shape: between set_latent_space(GLASS_LATENT_SUB) and finalize, which sizes the coefficient buffer
+ * [max_pop][G K], the per-layer dlatents, the style tiles and the device search's buffers (row width G K); glass_engine_latent_row
+ * reports G K after it.  GLASS_ERR_STATE after finalize, in another space, and on a BigGAN or generator-less engine, by name.
+ * glass_engine_set_subspace: after finalize, any time between passes, as set_truncation is: validates through the rule and uploads;
+ * a stored anchor is recomputed from its row.  evaluate, generate, search_*, expand_latents and set_anchor on a sub engine before it fail
+ * (GLASS_ERR_STATE, "set_subspace() first").
+ * glass_engine_expand_latents: the dlatents the pass makes its styles from, after truncation, by the kernels of the pass: rows
+ * [P][floats_per_row] -> out_dlat [P][n_lat][L], P in [1, max_pop].  Works in every StyleGAN2 space (z goes through the mapping network, w
+ * is tiled over the layers, w+ comes back as given where psi = 1).  The parity entry point; its output is a w+ row. */
+#define GLASS_LATENT_SUB 3
+int glass_subspace_supported(int32_t n_lat, int32_t latent_size, int32_t groups, int32_t components, const int32_t* layer_group, char* why,
+                             int32_t why_len);
+int glass_engine_set_subspace_shape(glass_engine* e, int32_t groups, int32_t components);
+int glass_engine_set_subspace(glass_engine* e, const int32_t* layer_group /*[n_lat]*/, const float* basis /*[K][L]*/, const float* base /*[n_lat][L]*/);
+int glass_engine_expand_latents(glass_engine* e, const float* rows, int32_t P, float* out_dlat /*[P][n_lat][L]*/);
 
 /* Hand one reference tensor to the engine: `name` is the reference state-dict key
  * prefixed with its sub-model ("G_mapping.", "G_synthesis.", "D.", "clip."; the generator's own "dlatent_avg" unprefixed), data is

@@ -240,6 +240,8 @@ int glass_op_rn_tokens(int32_t device, int32_t B, int32_t HW, int32_t C, const f
  *   shape (the launcher chooses it above 64 KB).  A shape the launcher does not take (V or T above 16) is refused by name, nothing launched.
  * glass_op_latent_anchor: launch_latent_anchor: w [P,n_lat,L] (layered 1) or [P,L] (layered 0: the one row serves every layer), a [n_lat,L] ->
  *   d [P], the mean squared difference.
+ * glass_op_dlatent_subspace: launch_dlatent_subspace (latent space sub, include/glass.h): c [P,G,K], layer_group [n_lat], basis [K,L], base
+ *   [n_lat,L] -> out [P,n_lat,L].  What glass_subspace_supported refuses is refused with its words, nothing launched.
  * glass_op_image_patches: img [n,3,S,S] -> patches [n (S/ps)^2, ld] (fp16 values), pre-filled with `sentinel`.
  * glass_op_rn_token0_rows: att [B,T,C] (fp16) -> out [B,C] = att[b, 0, :]. */
 int glass_op_mapping(int32_t device, int32_t P, int32_t L, int32_t n_layers, const float* z, const float* wt, const float* b, int32_t path,
@@ -275,6 +277,8 @@ int glass_op_assemble_F_set(int32_t device, int32_t P, int32_t K, const float* s
 int glass_op_cosine_set_dir(int32_t device, int32_t P, int32_t V, int32_t T, int32_t D, const float* feat, const float* targets, const float* weights,
                             const float* src, int32_t streamed, float* view_sim, float* set_sim, float* sim);
 int glass_op_latent_anchor(int32_t device, int32_t P, int32_t n_lat, int32_t L, int32_t layered, const float* w, const float* a, float* d);
+int glass_op_dlatent_subspace(int32_t device, const float* c, int32_t P, int32_t G, int32_t K, const int32_t* layer_group, int32_t n_lat, int32_t L,
+                              const float* basis, const float* base, float* out);
 int glass_op_image_patches(int32_t device, int32_t n, int32_t S, int32_t ps, int32_t ld, const float* img, float sentinel, float* patches);
 int glass_op_rn_token0_rows(int32_t device, int32_t B, int32_t T, int32_t C, const float* att, float* out);
 /* The perceptual objective's own kernels (lpips.hip), each through the launcher the walker (lpips.cpp) calls; a shape the launcher does not
