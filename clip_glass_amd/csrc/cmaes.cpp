@@ -44,7 +44,7 @@ int alloc_cma(glass_engine* e) {
     CmaState& c = s.cs;
     if ((rc = dev_alloc(e, &s.Xoff, (size_t)pop * n))) return rc;
     if ((rc = dev_alloc(e, &s.F, (size_t)2 * pop * M))) return rc;      // the GA's layout: a generation's F is the second half
-    if ((rc = dev_alloc(e, &s.counts, (size_t)2))) return rc;
+    if ((rc = dev_alloc(e, &s.counts, (size_t)3))) return rc;           // the GA's layout, [1][3]: the generation's two counters, the third unused
     if ((rc = dev_alloc(e, &c.m, (size_t)4 * n))) return rc;
     c.d = c.m + n; c.ps = c.m + 2 * (size_t)n; c.pc = c.m + 3 * (size_t)n;
     if ((rc = dev_alloc(e, &c.yw, (size_t)2 * n))) return rc;
@@ -57,7 +57,7 @@ int alloc_cma(glass_engine* e) {
     std::vector<double> w((size_t)pop / 2);
     cma_weights(pop, w.data());
     if ((rc = upload(e, &c.w, w))) return rc;
-    GLASS_HIP(hipMemset(s.counts, 0, 2 * sizeof(int)));
+    GLASS_HIP(hipMemset(s.counts, 0, 3 * sizeof(int)));
     GLASS_HIP(hipMemset(s.F, 0, (size_t)2 * pop * M * sizeof(float)));
     GLASS_HIP(hipMemset(c.order, 0, (size_t)pop * sizeof(int)));
     GLASS_HIP(hipMemset(c.sc, 0, sizeof(CmaScalars)));
@@ -72,30 +72,18 @@ CmaParams params_of(const glass_engine* e) {
 // the launches of the phases, on e->cur; nothing here waits
 void launch_sample(glass_engine* e, int generation) {
     glass_engine::Search& s = e->search;
-    Prof pr(e, "search.cma_sample", 0, (double)s.g.pop * s.n_var * sizeof(float));
-    const char* k = launch_cma_sample(s.cs, params_of(e), generation, 0, s.g.pop, s.Xoff, e->cur);
-    if (k) pr.ran("search.cma_sample", k);
-    else { pr.drop(); e->launch_error = "search.cma_sample: the launcher refused the shape"; }
+    profiled_launch(e, "search.cma_sample", (double)s.g.pop * s.n_var * sizeof(float),
+                    [&] { return launch_cma_sample(s.cs, params_of(e), generation, 0, s.g.pop, s.Xoff, e->cur); });
     s.varied_gen = generation;
 }
 void launch_rank_update(glass_engine* e, int generation) {
     glass_engine::Search& s = e->search;
     const CmaParams p = params_of(e);
     const float* F = s.F + (size_t)s.g.pop * e->cfg.n_obj;
-    {
-        Prof pr(e, "search.cma_rank", 0, (double)s.g.pop * sizeof(float));
-        const char* k = launch_cma_rank(s.cs, p, F, e->cur);
-        if (!k) {      // (no rank: no update either — it would read an order nobody wrote)
-            pr.drop();
-            e->launch_error = "search.cma_rank: the launcher refused the shape";
-            return;
-        }
-        pr.ran("search.cma_rank", k);
-    }
-    Prof pr(e, "search.cma_update", 0, (0.5 * s.g.pop + 1.0) * s.n_var * sizeof(float) + 10.0 * s.n_var * sizeof(double));
-    const char* k = launch_cma_update(s.cs, p, s.Xoff, generation, e->cur);
-    if (k) pr.ran("search.cma_update", k);
-    else { pr.drop(); e->launch_error = "search.cma_update: the launcher refused the shape"; }
+    // (no rank: no update either — it would read an order nobody wrote)
+    if (!profiled_launch(e, "search.cma_rank", (double)s.g.pop * sizeof(float), [&] { return launch_cma_rank(s.cs, p, F, e->cur); })) return;
+    profiled_launch(e, "search.cma_update", (0.5 * s.g.pop + 1.0) * s.n_var * sizeof(float) + 10.0 * s.n_var * sizeof(double),
+                    [&] { return launch_cma_update(s.cs, p, s.Xoff, generation, e->cur); });
 }
 }  // namespace
 

@@ -303,13 +303,15 @@ struct glass_engine {
         // offspring half of F, so search_evaluate is the GA's; of the buffers above only Xoff, F and counts are allocated
         bool cma = false;
         CmaState cs = {};                   // cs.m holds m, d, p_sigma, p_c back to back ([4][n_var])
-        // islands (include/glass.h "Device search: islands"; glass_engine_set_search_islands): 0 — the setter was never called, every buffer
-        // and launch above is a single search's.  K >= 1: the buffers hold K populations of g.pop rows back to back, F is the populations'
-        // plane [K pop][n_obj] followed by the offspring's, counts is [K][3], and the island forms of the kernels run
+        // islands (include/glass.h "Device search: islands"; glass_engine_set_search_islands): 0 — the setter was never called, which the
+        // island entry points, the islands' own prompts and the noise planes of a pass look at.  Every buffer and launch knows k() alone: the
+        // buffers hold k() populations of g.pop rows back to back, F is the populations' plane [k() pop][n_obj] followed by the offspring's,
+        // counts is [k()][3], and the island is the kernels' last grid dimension — a single search is the one island 0
         int islands = 0, migrate_every = 0, migrants = 1;
         int survived_gen = -1;              // the generation whose survival the populations hold and whose migration has not run
         bool own_prompts = false;           // glass_engine_set_island_weights: pset's island table is in use
-        int rows() const { return (islands ? islands : 1) * g.pop; }
+        int k() const { return islands ? islands : 1; }
+        int rows() const { return k() * g.pop; }
     } search;
     int noise_period = 0;                   // minibatches per island while a pass of an island search runs (upload_noise); 0 otherwise
     int island_row0 = -1;                   // the first search row of such a pass (the rows' islands in the head); -1 otherwise
@@ -425,6 +427,16 @@ struct Prof {
     }
     void drop() { on = false; }   // the launcher refused: nothing ran in this scope
 };
+// One profile row around `launch`, which launches on e->cur and returns the kernel's name, or nullptr where its launcher refused the shape:
+// the row is then dropped and the refusal kept for the wait behind the launches (`why`: what else the refusal can mean).  Whether it ran.
+template <class Launch>
+bool profiled_launch(glass_engine* e, const char* tag, double bytes, Launch launch, const char* why = "") {
+    Prof pr(e, tag, 0, bytes);
+    const char* k = launch();
+    if (k) pr.ran(tag, k);
+    else { pr.drop(); e->launch_error = std::string(tag) + ": the launcher refused the shape" + why; }
+    return k != nullptr;
+}
 
 void collect_profile(glass_engine* e);
 ConvKernel choose_conv(const ConvParams& p);   // the single-kernel conv families in the engine's order; empty: conv_gemm / conv_direct (run_conv)

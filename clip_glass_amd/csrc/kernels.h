@@ -225,36 +225,29 @@ struct GaParams {
     uint64_t seed;
     double prob_x, prob_flip;      // mixed rows only: HUX per mating, bit-flip per bit
 };
-// Every launcher returns the name of the kernel it launched, or nullptr: a shape outside the limits, nothing launched.
-// offspring rows [row0, row0 + rows) of generation `generation` from the population X [pop][n_var] with rank [pop], cd [pop] -> Xoff rows
-const char* launch_ga_vary(const float* X, const int* rank, const double* cd, const GaParams& g, int n_var, int generation, int row0, int rows,
-                           float* Xoff, hipStream_t st);
-// the same for mixed rows [n_real real | n_bits bit columns] (include/glass.h "Mixed rows"): `parts` chooses the real columns' kernel, the
-// bit columns' kernel or both (the engine launches them one by one, under a profile row each); nullptr: n_real < 1, n_bits outside
-// [1, GLASS_SEARCH_MAX_BITS], rows outside the pop offspring rows
-enum { GA_VARY_REAL = 1, GA_VARY_BITS = 2, GA_VARY_BOTH = 3 };
-const char* launch_ga_vary_mixed(const float* X, const int* rank, const double* cd, const GaParams& g, int n_real, int n_bits, int generation, int row0,
-                                 int rows, int parts, float* Xoff, hipStream_t st);
-// flags[r] = 1: Xoff row r equals, by value in every variable, a row of X [pop] or an Xoff row below r
-const char* launch_ga_duplicates(const float* X, const float* Xoff, int pop, int n_off, int n_var, int* flags, hipStream_t st);
-// survival over F [n_pop + n_off][n_obj] (population first; flags [n_off] nullable): chosen / rank_out / cd_out [pop_out], F's first pop_out
-// rows rewritten as the survivors', counts = {flagged, non-finite rows}.  One workgroup; nsga 0: GA
-const char* launch_ga_survive(float* F, const int* flags, int n_pop, int n_off, int n_obj, int pop_out, int nsga, int* chosen, int* rank_out,
-                              double* cd_out, int* counts, hipStream_t st);
-void launch_ga_gather(const float* X, const float* Xoff, const int* chosen, int n_pop, int pop_out, int n_var, float* Xnext, hipStream_t st);
-size_t ga_survive_lds_bytes(int n_rows, int n_obj);
-// The island forms (include/glass.h "Device search: islands"): every buffer holds `islands` populations of g.pop / pop rows back to back,
-// island i runs under seed + i with local indices, and the island is a grid dimension.  nullptr: a shape outside the limits.
+// Every launcher returns the name of the kernel it launched, or nullptr: a shape outside the limits, nothing launched.  Every buffer holds
+// `islands` populations back to back, island i runs under seed + i with local indices, and the island is the kernels' last grid dimension
+// (include/glass.h "Device search: islands"); a single search is islands = 1.  More than one island: the island search's limits, with as
+// many offspring as population rows per island and pop_out = n_pop.
 #define GLASS_SEARCH_MAX_ISLANDS 64
-// every offspring row of every island; all-real rows: n_bits 0 and parts GA_VARY_REAL
-const char* launch_ga_vary_islands(const float* X, const int* rank, const double* cd, const GaParams& g, int islands, int n_real, int n_bits,
-                                   int generation, int parts, float* Xoff, hipStream_t st);
-const char* launch_ga_duplicates_islands(const float* X, const float* Xoff, int islands, int pop, int n_var, int* flags, hipStream_t st);
-// F [islands pop][n_obj] the populations' plane (rewritten), Foff the offspring's (n_off = pop) or unused (n_off = 0); counts [islands][3] =
-// {flagged, non-finite, migrants accepted}.  gated (n_off 0 only): islands whose third counter is 0 keep their state, chosen = identity
-const char* launch_ga_survive_islands(float* F, const float* Foff, const int* flags, int islands, int pop, int n_off, int n_obj, int nsga, int gated,
-                                      int* chosen, int* rank_out, double* cd_out, int* counts, hipStream_t st);
-void launch_ga_gather_islands(const float* X, const float* Xoff, const int* chosen, int islands, int pop, int n_var, float* Xnext, hipStream_t st);
+// offspring rows [row0, row0 + rows) of every island, generation `generation`, from the populations X [islands g.pop][n_real + n_bits] with
+// rank, cd [islands g.pop] -> Xoff rows.  A mixed row is [n_real real | n_bits bit columns] (include/glass.h "Mixed rows"): `parts` chooses
+// the real columns' kernel, the bit columns' kernel or both (the engine launches them one by one, under a profile row each); an all-real
+// row is n_bits 0 with GA_VARY_REAL.  nullptr also: n_real < 1, n_bits above GLASS_SEARCH_MAX_BITS, GA_VARY_BITS with n_bits < 1, rows
+// outside the g.pop offspring rows
+enum { GA_VARY_REAL = 1, GA_VARY_BITS = 2, GA_VARY_BOTH = 3 };
+const char* launch_ga_vary(const float* X, const int* rank, const double* cd, const GaParams& g, int islands, int n_real, int n_bits, int generation,
+                           int row0, int rows, int parts, float* Xoff, hipStream_t st);
+// flags[r] = 1: Xoff row r equals, by value in every variable, a row of its island's X [pop] or an Xoff row of its island below r
+const char* launch_ga_duplicates(const float* X, const float* Xoff, int islands, int pop, int n_off, int n_var, int* flags, hipStream_t st);
+// survival, one workgroup per island, of its n_pop rows of F [islands n_pop][n_obj] with its n_off rows of Foff (a second plane, or F +
+// n_pop n_obj behind a single population; flags [islands n_off] nullable): chosen / rank_out / cd_out [islands pop_out], the island's first
+// pop_out rows of F rewritten as the survivors', counts [islands][3] = {flagged, non-finite rows, migrants accepted (ga_migrate_kernel's)}.
+// nsga 0: GA.  gated (n_off 0 and pop_out = n_pop only): islands whose third counter is 0 keep their state, chosen = identity
+const char* launch_ga_survive(float* F, const float* Foff, const int* flags, int islands, int n_pop, int n_off, int n_obj, int pop_out, int nsga, int gated,
+                              int* chosen, int* rank_out, double* cd_out, int* counts, hipStream_t st);
+void launch_ga_gather(const float* X, const float* Xoff, const int* chosen, int islands, int n_pop, int pop_out, int n_var, float* Xnext, hipStream_t st);
+size_t ga_survive_lds_bytes(int n_rows, int n_obj);
 // ring migration of the `migrants` best rows of island i - 1 onto the worst rows of island i, X and F in place; writes counts[i][2]
 const char* launch_ga_migrate(float* X, float* F, const int* rank, const double* cd, int islands, int pop, int n_var, int n_obj, int migrants, int* counts,
                               hipStream_t st);

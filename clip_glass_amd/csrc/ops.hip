@@ -1410,7 +1410,7 @@ extern "C" int glass_op_ga_vary(int32_t device, int32_t pop, int32_t n_var, cons
     const auto dO = st.poisoned<float>((size_t)pop * n_var, 4);      // every offspring row, and four guard elements behind them
     GaParams g;
     g.pop = pop; g.xl = xl; g.xu = xu; g.eta_c = eta_c; g.eta_m = eta_m; g.prob_m = prob_m; g.seed = seed;
-    TRY(st.run([&] { return accepted(launch_ga_vary(dX, dr, dc, g, n_var, generation, row0, rows, dO, 0), "ga_vary refused the shape"); }));
+    TRY(st.run([&] { return accepted(launch_ga_vary(dX, dr, dc, g, 1, n_var, 0, generation, row0, rows, GA_VARY_REAL, dO, 0), "ga_vary refused the shape"); }));
     TRY(st.intact(dO, "ga_vary stored past the last row"));
     return st.fetch(out, dO, (size_t)rows * n_var, (size_t)row0 * n_var);
 }
@@ -1432,7 +1432,7 @@ extern "C" int glass_op_ga_vary_mixed(int32_t device, int32_t pop, int32_t n_rea
     g.pop = pop; g.xl = xl; g.xu = xu; g.eta_c = eta_c; g.eta_m = eta_m; g.prob_m = prob_m; g.seed = seed;
     g.prob_x = prob_x; g.prob_flip = prob_flip;
     TRY(st.run([&] {
-        return accepted(launch_ga_vary_mixed(dX, dr, dc, g, n_real, n_bits, generation, row0, rows, GA_VARY_BOTH, dO, 0),
+        return accepted(launch_ga_vary(dX, dr, dc, g, 1, n_real, n_bits, generation, row0, rows, GA_VARY_BOTH, dO, 0),
                         "ga_vary_mixed refused the shape (n_real >= 1, n_bits in [1, 4096])");
     }));
     TRY(st.intact(dO, "ga_vary_mixed stored past the last row"));
@@ -1445,7 +1445,7 @@ extern "C" int glass_op_ga_duplicates(int32_t device, int32_t pop, int32_t n_off
     Stage st(device);
     const auto dX = st.in32(X, (size_t)pop * n_var), dO = st.in32(Xoff, (size_t)n_off * n_var);
     const auto df = st.poisoned<int32_t>(n_off, 4);
-    TRY(st.run([&] { return accepted(launch_ga_duplicates(dX, dO, pop, n_off, n_var, df, 0), "ga_duplicates refused the shape"); }));
+    TRY(st.run([&] { return accepted(launch_ga_duplicates(dX, dO, 1, pop, n_off, n_var, df, 0), "ga_duplicates refused the shape"); }));
     TRY(st.intact(df, "ga_duplicates stored past row n_off"));
     return st.fetch(flags, df);
 }
@@ -1461,7 +1461,7 @@ extern "C" int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off,
     const auto dF = st.in32(F, ((size_t)n_pop + n_off) * n_obj);
     const auto dfl = st.in_i32(n_off ? flags : nullptr, n_off);
     const auto dch = st.poisoned<int32_t>(pop_out, 4);
-    const auto drk = st.raw<int32_t>(pop_out), dcn = st.raw<int32_t>(2);
+    const auto drk = st.raw<int32_t>(pop_out), dcn = st.raw<int32_t>(3);      // (counts [1][3]: the third is the migration's)
     const auto dcd = st.raw<double>(pop_out);
     Buf<float> dX, dO, dXo;
     if (gather) {
@@ -1470,9 +1470,9 @@ extern "C" int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off,
         dXo = st.poisoned<float>((size_t)pop_out * n_var);
     }
     TRY(st.run([&]() -> int {
-        OPREQ(launch_ga_survive(dF, dfl, n_pop, n_off, n_obj, pop_out, nsga, dch, drk, dcd, dcn, 0),
+        OPREQ(launch_ga_survive(dF, dF + (size_t)n_pop * n_obj, dfl, 1, n_pop, n_off, n_obj, pop_out, nsga, 0, dch, drk, dcd, dcn, 0),
               "ga_survive refused the shape (up to 2048 merged rows, 6 objectives, pop_out <= 1024 and <= the merged rows)");
-        if (gather) launch_ga_gather(dX, dO, dch, n_pop, pop_out, n_var, dXo, 0);
+        if (gather) launch_ga_gather(dX, dO, dch, 1, n_pop, pop_out, n_var, dXo, 0);
         return GLASS_OK;
     }));
     TRY(st.intact(dch, "ga_survive stored past slot pop_out"));
@@ -1480,7 +1480,7 @@ extern "C" int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off,
     TRY(st.fetch(rank, drk));
     TRY(st.fetch(cd, dcd));
     TRY(st.fetch(F_out, dF, (size_t)pop_out * n_obj));
-    TRY(st.fetch(counts, dcn));
+    TRY(st.fetch(counts, dcn, 2));
     return gather ? st.fetch(X_out, dXo) : GLASS_OK;
 }
 
@@ -1504,12 +1504,12 @@ extern "C" int glass_op_ga_migrate(int32_t device, int32_t islands, int32_t pop,
     const auto dXo = st.poisoned<float>(R * n_var, 4);
     TRY(st.run([&]() -> int {
         OPREQ(launch_ga_migrate(dX, dF, dr, dc, islands, pop, n_var, n_obj, migrants, dcn, 0), "ga_migrate refused the shape");
-        OPREQ(launch_ga_survive_islands(dF, nullptr, nullptr, islands, pop, 0, n_obj, nsga, 1, dch, dr, dc, dcn, 0), "ga_survive_islands refused the shape");
-        launch_ga_gather_islands(dX, nullptr, dch, islands, pop, n_var, dXo, 0);
+        OPREQ(launch_ga_survive(dF, nullptr, nullptr, islands, pop, 0, n_obj, pop, nsga, 1, dch, dr, dc, dcn, 0), "ga_survive refused the shape");
+        launch_ga_gather(dX, nullptr, dch, islands, pop, pop, n_var, dXo, 0);
         return GLASS_OK;
     }));
-    TRY(st.intact(dch, "ga_survive_islands stored past the last island's slots"));
-    TRY(st.intact(dXo, "ga_gather_islands stored past the last island's rows"));
+    TRY(st.intact(dch, "ga_survive stored past the last island's slots"));
+    TRY(st.intact(dXo, "ga_gather stored past the last island's rows"));
     TRY(st.fetch(X_out, dXo, R * n_var));
     TRY(st.fetch(F_out, dF));
     TRY(st.fetch(rank_out, dr));

@@ -49,6 +49,11 @@ static int check_bit_operators(const char* what, double prob_x, double prob_flip
     REQUIRE(prob_x >= 0.0 && prob_x <= 1.0 && prob_flip >= 0.0 && prob_flip <= 1.0, GLASS_ERR_ARG, std::string(what) + ": prob_x and prob_flip must be in [0, 1]");
     return GLASS_OK;
 }
+// the checked operators into GaParams (prob_x and prob_flip are the mixed setters' own and stay what they are under the others)
+static void store_operators(GaParams& g, double xl, double xu, double eta_c, double eta_m, double prob_m, uint64_t seed) {
+    g.xl = xl; g.xu = xu; g.eta_c = eta_c; g.eta_m = eta_m; g.prob_m = prob_m;
+    g.seed = seed;
+}
 
 extern "C" int glass_engine_set_search(glass_engine* e, int32_t algorithm, int32_t pop, double xl, double xu, double eta_c, double eta_m,
                                        double prob_m, uint64_t seed) {
@@ -68,8 +73,7 @@ extern "C" int glass_engine_set_search(glass_engine* e, int32_t algorithm, int32
     glass_engine::Search& s = e->search;
     s.nsga = algorithm == GLASS_SEARCH_NSGA2;
     s.g.pop = pop;
-    s.g.xl = xl; s.g.xu = xu; s.g.eta_c = eta_c; s.g.eta_m = eta_m; s.g.prob_m = prob_m;
-    s.g.seed = seed;
+    store_operators(s.g, xl, xu, eta_c, eta_m, prob_m, seed);
     return GLASS_OK;
 }
 
@@ -92,9 +96,8 @@ extern "C" int glass_engine_set_search_mixed(glass_engine* e, int32_t algorithm,
     s.nsga = algorithm == GLASS_SEARCH_NSGA2;
     s.n_real = n_real;
     s.g.pop = pop;
-    s.g.xl = xl; s.g.xu = xu; s.g.eta_c = eta_c; s.g.eta_m = eta_m; s.g.prob_m = prob_m;
+    store_operators(s.g, xl, xu, eta_c, eta_m, prob_m, seed);
     s.g.prob_x = prob_x; s.g.prob_flip = prob_flip;
-    s.g.seed = seed;
     return GLASS_OK;
 }
 
@@ -106,9 +109,8 @@ extern "C" int glass_engine_set_search_operators_mixed(glass_engine* e, double x
     if (int rc = check_operators("set_search_operators_mixed", xl, xu, eta_c, eta_m, prob_m)) return rc;
     if (int rc = check_bit_operators("set_search_operators_mixed", prob_x, prob_flip)) return rc;
     GaParams& g = e->search.g;
-    g.xl = xl; g.xu = xu; g.eta_c = eta_c; g.eta_m = eta_m; g.prob_m = prob_m;
+    store_operators(g, xl, xu, eta_c, eta_m, prob_m, seed);
     g.prob_x = prob_x; g.prob_flip = prob_flip;
-    g.seed = seed;
     return GLASS_OK;
 }
 
@@ -116,9 +118,7 @@ extern "C" int glass_engine_set_search_operators(glass_engine* e, double xl, dou
     REQUIRE(e, GLASS_ERR_ARG, "null engine");
     REQUIRE(e->search.g.pop > 0, GLASS_ERR_STATE, "set_search_operators: the device search is off (glass_engine_set_search before finalize)");
     if (int rc = check_operators("set_search_operators", xl, xu, eta_c, eta_m, prob_m)) return rc;
-    GaParams& g = e->search.g;
-    g.xl = xl; g.xu = xu; g.eta_c = eta_c; g.eta_m = eta_m; g.prob_m = prob_m;
-    g.seed = seed;
+    store_operators(e->search.g, xl, xu, eta_c, eta_m, prob_m, seed);
     return GLASS_OK;
 }
 
@@ -207,7 +207,7 @@ int alloc_search(glass_engine* e) {
     if (s.islands)
         if (int rc = glass_search_islands_supported(s.islands, pop, s.n_var, M, s.nsga, s.migrate_every, s.migrants)) return rc;
     int rc;
-    const size_t R = (size_t)s.rows(), xn = R * s.n_var, nc = s.islands ? (size_t)3 * s.islands : 2;      // (no islands: R = pop, a single search's sizes)
+    const size_t R = (size_t)s.rows(), xn = R * s.n_var, nc = (size_t)3 * s.k();
     if ((rc = dev_alloc(e, &s.X[0], xn))) return rc;
     if ((rc = dev_alloc(e, &s.X[1], xn))) return rc;
     if ((rc = dev_alloc(e, &s.Xoff, xn))) return rc;
@@ -239,48 +239,31 @@ namespace {
 // the launches of the three phases, on e->cur; nothing here waits
 void launch_vary(glass_engine* e, int generation) {
     glass_engine::Search& s = e->search;
-    const int pop = s.g.pop, K = s.islands, n_real = s.n_real ? s.n_real : s.n_var;
+    const int pop = s.g.pop, K = s.k(), n_real = s.n_real ? s.n_real : s.n_var, n_bits = s.n_var - n_real;
     const double xbytes = (double)s.rows() * s.n_var * sizeof(float);
-    const double real_share = s.n_real ? (double)s.n_real / s.n_var : 1.0;
-    {
-        Prof pr(e, "search.vary", 0, 3 * xbytes * real_share);
-        const char* k = K         ? launch_ga_vary_islands(s.X[s.cur], s.rank, s.cd, s.g, K, n_real, s.n_var - n_real, generation, GA_VARY_REAL, s.Xoff, e->cur)
-                        : s.n_real ? launch_ga_vary_mixed(s.X[s.cur], s.rank, s.cd, s.g, s.n_real, s.n_var - s.n_real, generation, 0, pop, GA_VARY_REAL, s.Xoff, e->cur)
-                                   : launch_ga_vary(s.X[s.cur], s.rank, s.cd, s.g, s.n_var, generation, 0, pop, s.Xoff, e->cur);
-        if (k) pr.ran("search.vary", k);
-        else { pr.drop(); e->launch_error = "search.vary: the launcher refused the shape"; }
-    }
-    if (s.n_real) {      // mixed rows: HUX and bit-flip on the bit columns behind the real ones
-        Prof pr(e, "search.vary_bits", 0, 3 * xbytes * (1.0 - real_share));
-        const char* k = K ? launch_ga_vary_islands(s.X[s.cur], s.rank, s.cd, s.g, K, n_real, s.n_var - n_real, generation, GA_VARY_BITS, s.Xoff, e->cur)
-                          : launch_ga_vary_mixed(s.X[s.cur], s.rank, s.cd, s.g, s.n_real, s.n_var - s.n_real, generation, 0, pop, GA_VARY_BITS, s.Xoff, e->cur);
-        if (k) pr.ran("search.vary_bits", k);
-        else { pr.drop(); e->launch_error = "search.vary_bits: the launcher refused the shape"; }
-    }
-    {
-        Prof pr(e, "search.duplicates", 0, 2 * xbytes);
-        const char* k = K ? launch_ga_duplicates_islands(s.X[s.cur], s.Xoff, K, pop, s.n_var, s.flags, e->cur)
-                          : launch_ga_duplicates(s.X[s.cur], s.Xoff, pop, pop, s.n_var, s.flags, e->cur);
-        if (k) pr.ran("search.duplicates", k);
-        else { pr.drop(); e->launch_error = "search.duplicates: the launcher refused the shape"; }
-    }
+    const double real_share = (double)n_real / s.n_var;
+    profiled_launch(e, "search.vary", 3 * xbytes * real_share,
+                    [&] { return launch_ga_vary(s.X[s.cur], s.rank, s.cd, s.g, K, n_real, n_bits, generation, 0, pop, GA_VARY_REAL, s.Xoff, e->cur); });
+    if (n_bits)      // mixed rows: HUX and bit-flip on the bit columns behind the real ones
+        profiled_launch(e, "search.vary_bits", 3 * xbytes * (1.0 - real_share),
+                        [&] { return launch_ga_vary(s.X[s.cur], s.rank, s.cd, s.g, K, n_real, n_bits, generation, 0, pop, GA_VARY_BITS, s.Xoff, e->cur); });
+    profiled_launch(e, "search.duplicates", 2 * xbytes, [&] { return launch_ga_duplicates(s.X[s.cur], s.Xoff, K, pop, pop, s.n_var, s.flags, e->cur); });
     s.varied_gen = generation;
 }
-void launch_survive(glass_engine* e, int n_off) {
+// survival of every island and the gather of the survivors' rows, under one profile row.  rerank (n_off 0, behind a migration): only the
+// islands that accepted a migrant, ranked (and ordered) again as search_init ranks a population
+bool launch_survive(glass_engine* e, int n_off, bool rerank = false) {
     glass_engine::Search& s = e->search;
-    const int pop = s.g.pop, K = s.islands, M = e->cfg.n_obj;
-    Prof pr(e, "search.survive", 0, 2.0 * s.rows() * s.n_var * sizeof(float));
-    const char* k = K ? launch_ga_survive_islands(s.F, s.F + (size_t)s.rows() * M, s.flags, K, pop, n_off, M, s.nsga, 0, s.chosen, s.rank, s.cd, s.counts, e->cur)
-                      : launch_ga_survive(s.F, n_off ? s.flags : nullptr, pop, n_off, M, pop, s.nsga, s.chosen, s.rank, s.cd, s.counts, e->cur);
-    if (!k) {
-        pr.drop();
-        e->launch_error = "search.survive: the launcher refused the shape (or the device offers too little LDS)";
-        return;
-    }
-    pr.ran("search.survive", k);
-    if (K) launch_ga_gather_islands(s.X[s.cur], s.Xoff, s.chosen, K, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
-    else launch_ga_gather(s.X[s.cur], s.Xoff, s.chosen, pop, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
-    s.cur ^= 1;
+    const int pop = s.g.pop, K = s.k(), M = e->cfg.n_obj;
+    return profiled_launch(e, rerank ? "search.rerank" : "search.survive", 2.0 * s.rows() * s.n_var * sizeof(float), [&] {
+        const char* k = launch_ga_survive(s.F, s.F + (size_t)s.rows() * M, n_off ? s.flags : nullptr, K, pop, n_off, M, pop, s.nsga, rerank, s.chosen, s.rank,
+                                          s.cd, s.counts, e->cur);
+        if (k) {
+            launch_ga_gather(s.X[s.cur], s.Xoff, s.chosen, K, pop, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
+            s.cur ^= 1;
+        }
+        return k;
+    }, " (or the device offers too little LDS)");
 }
 // whether the rule has a migration behind the survival of this generation
 bool migration_due(const glass_engine::Search& s, int generation) {
@@ -289,27 +272,11 @@ bool migration_due(const glass_engine::Search& s, int generation) {
 // migration in place, then the islands that accepted a row ranked (and ordered) again as search_init ranks a population
 void launch_migrate(glass_engine* e) {
     glass_engine::Search& s = e->search;
-    const int pop = s.g.pop, K = s.islands, M = e->cfg.n_obj;
-    {
-        Prof pr(e, "search.migrate", 0, 2.0 * K * s.migrants * s.n_var * sizeof(float));
-        const char* k = launch_ga_migrate(s.X[s.cur], s.F, s.rank, s.cd, K, pop, s.n_var, M, s.migrants, s.counts, e->cur);
-        if (!k) {
-            pr.drop();
-            e->launch_error = "search.migrate: the launcher refused the shape";
-            return;
-        }
-        pr.ran("search.migrate", k);
-    }
-    Prof pr(e, "search.rerank", 0, 2.0 * s.rows() * s.n_var * sizeof(float));
-    const char* k = launch_ga_survive_islands(s.F, nullptr, nullptr, K, pop, 0, M, s.nsga, 1, s.chosen, s.rank, s.cd, s.counts, e->cur);
-    if (!k) {
-        pr.drop();
-        e->launch_error = "search.rerank: the launcher refused the shape (or the device offers too little LDS)";
-        return;
-    }
-    pr.ran("search.rerank", k);
-    launch_ga_gather_islands(s.X[s.cur], nullptr, s.chosen, K, pop, s.n_var, s.X[s.cur ^ 1], e->cur);
-    s.cur ^= 1;
+    const int K = s.k();
+    if (profiled_launch(e, "search.migrate", 2.0 * K * s.migrants * s.n_var * sizeof(float), [&] {
+            return launch_ga_migrate(s.X[s.cur], s.F, s.rank, s.cd, K, s.g.pop, s.n_var, e->cfg.n_obj, s.migrants, s.counts, e->cur);
+        }))
+        launch_survive(e, 0, true);
 }
 // a scoring pass of search rows [first_row, first_row + P): with islands the noise planes are those of the minibatch's index within its island
 int search_pass(glass_engine* e, int P, int generation, int first_row, const float* d_rows, float* d_F, bool no_wait) {
@@ -339,18 +306,15 @@ int search_wait(glass_engine* e) {
     }
     return GLASS_OK;
 }
-// counts [2] = {flagged, non-finite} rows of the last survival (islands: summed over them); per_island [islands][3] nullable
+// counts [2] = {flagged, non-finite} rows of the last survival, summed over the islands; per_island [islands][3]; both nullable
 static int read_counts(glass_engine* e, int* counts, int* per_island) {
     const glass_engine::Search& s = e->search;
-    if (!s.islands) {
-        GLASS_HIP(hipMemcpy(counts, s.counts, 2 * sizeof(int), hipMemcpyDeviceToHost));
-        return GLASS_OK;
-    }
+    const int K = s.k();
     int h[3 * GLASS_SEARCH_MAX_ISLANDS];
-    GLASS_HIP(hipMemcpy(h, s.counts, (size_t)3 * s.islands * sizeof(int), hipMemcpyDeviceToHost));
+    GLASS_HIP(hipMemcpy(h, s.counts, (size_t)3 * K * sizeof(int), hipMemcpyDeviceToHost));
     if (counts) counts[0] = counts[1] = 0;
-    for (int i = 0; i < s.islands && counts; ++i) { counts[0] += h[3 * i]; counts[1] += h[3 * i + 1]; }
-    if (per_island) memcpy(per_island, h, (size_t)3 * s.islands * sizeof(int));
+    for (int i = 0; i < K && counts; ++i) { counts[0] += h[3 * i]; counts[1] += h[3 * i + 1]; }
+    if (per_island) memcpy(per_island, h, (size_t)3 * K * sizeof(int));
     return GLASS_OK;
 }
 namespace {

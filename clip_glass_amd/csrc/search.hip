@@ -96,19 +96,15 @@ __device__ __forceinline__ void ga_vary_row(const float* __restrict__ X, const i
         out[0] = ga_vary_one(g, pa[0], pb[0], m, r, j0, (uint32_t)generation);
     }
 }
+// The island is the last grid dimension in every kernel of a phase (include/glass.h "Device search: islands"), here grid (ceil(n_var / (256
+// VEC)), rows, islands): island i = blockIdx.z works on rows [i pop, (i + 1) pop) of every buffer under seed + i, and every index inside is
+// local to the island.  A single search is the one island 0.
 template <int VEC>
 __global__ __launch_bounds__(256) void ga_vary_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
                                                       GaParams g, int n_var, int stride, int generation, int row0, float* __restrict__ Xoff) {
-    ga_vary_row<VEC>(X, rank, cd, g, n_var, stride, generation, row0 + blockIdx.y, Xoff);
-}
-// The island form (include/glass.h "Device search: islands"), grid (ceil(n_var / (256 VEC)), pop, islands): island i = blockIdx.z is the
-// kernel above on rows [i pop, (i + 1) pop) of every buffer under seed + i; every index inside is local to the island.
-template <int VEC>
-__global__ __launch_bounds__(256) void ga_vary_islands_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
-                                                              GaParams g, int n_var, int stride, int generation, float* __restrict__ Xoff) {
     const size_t o = (size_t)blockIdx.z * g.pop;
     g.seed += (uint64_t)blockIdx.z;
-    ga_vary_row<VEC>(X + o * stride, rank + o, cd + o, g, n_var, stride, generation, blockIdx.y, Xoff + o * stride);
+    ga_vary_row<VEC>(X + o * stride, rank + o, cd + o, g, n_var, stride, generation, row0 + blockIdx.y, Xoff + o * stride);
 }
 
 // One workgroup per offspring row r; its four waves walk the candidate rows (the population, then offspring rows BELOW r — "earlier" is the
@@ -147,17 +143,12 @@ __device__ __forceinline__ void ga_duplicates_row(const float* __restrict__ X, c
     __syncthreads();
     if (threadIdx.x == 0) flags[r] = hit[0] | hit[1] | hit[2] | hit[3];
 }
+// grid (n_off, islands): an offspring row is compared with its own island's rows only
 template <int VEC>
-__global__ __launch_bounds__(256) void ga_duplicates_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, int pop, int n_var,
+__global__ __launch_bounds__(256) void ga_duplicates_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, int pop, int n_off, int n_var,
                                                             int* __restrict__ flags) {
-    ga_duplicates_row<VEC>(X, Xoff, pop, n_var, blockIdx.x, flags);
-}
-// the island form, grid (pop, islands): an offspring row is compared with its own island's rows only
-template <int VEC>
-__global__ __launch_bounds__(256) void ga_duplicates_islands_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, int pop, int n_var,
-                                                                    int* __restrict__ flags) {
-    const size_t o = (size_t)blockIdx.y * pop;
-    ga_duplicates_row<VEC>(X + o * n_var, Xoff + o * n_var, pop, n_var, blockIdx.x, flags + o);
+    const size_t o = (size_t)blockIdx.y * pop, oo = (size_t)blockIdx.y * n_off;
+    ga_duplicates_row<VEC>(X + o * n_var, Xoff + oo * n_var, pop, n_var, blockIdx.x, flags + oo);
 }
 
 // ---- survival: one workgroup, everything in LDS -------------------------------------------------------------------------------
@@ -233,17 +224,12 @@ __device__ __forceinline__ void ga_vary_bits_row(const float* __restrict__ X, co
         out[j] = x;
     }
 }
+// grid (rows, islands): local rows and matings under seed + island
 __global__ __launch_bounds__(256) void ga_vary_bits_kernel(const float* __restrict__ X, const int* __restrict__ rank, const double* __restrict__ cd,
                                                            GaParams g, int n_real, int n_bits, int generation, int row0, float* __restrict__ Xoff) {
-    ga_vary_bits_row(X, rank, cd, g, n_real, n_bits, generation, row0 + blockIdx.x, Xoff);
-}
-// the island form, grid (pop, islands): local rows and matings under seed + island
-__global__ __launch_bounds__(256) void ga_vary_bits_islands_kernel(const float* __restrict__ X, const int* __restrict__ rank,
-                                                                   const double* __restrict__ cd, GaParams g, int n_real, int n_bits, int generation,
-                                                                   float* __restrict__ Xoff) {
     const size_t o = (size_t)blockIdx.y * g.pop, stride = (size_t)(n_real + n_bits);
     g.seed += (uint64_t)blockIdx.y;
-    ga_vary_bits_row(X + o * stride, rank + o, cd + o, g, n_real, n_bits, generation, blockIdx.x, Xoff + o * stride);
+    ga_vary_bits_row(X + o * stride, rank + o, cd + o, g, n_real, n_bits, generation, row0 + blockIdx.x, Xoff + o * stride);
 }
 
 // The merged rows are Fpop [n_pop][M], the population's, then Foff [n_off][M], the offspring's.  Left out of survival: offspring rows with a
@@ -373,50 +359,37 @@ __device__ __forceinline__ void ga_survive_rows(const float* Fpop, const float* 
     }
     if (tid == 0 && counts) { counts[0] = s_cnt[0]; counts[1] = s_cnt[1]; }
 }
-// F [n_pop + n_off][M]: the population's rows, then the offspring's, in one plane; F's first pop_out rows are rewritten as the survivors'
-__global__ __launch_bounds__(1024) void ga_survive_kernel(float* __restrict__ F, const int* __restrict__ flags, int n_pop, int n_off, int M,
-                                                          int pop_out, int nsga, int* __restrict__ chosen, int* __restrict__ rank_out,
+// One workgroup per island: island i ranks its n_pop population rows of F with its n_off offspring rows of Foff — two planes, the pass
+// writes the islands' offspring F contiguously; a single search's Foff is F + n_pop M, which aliases F (hence no __restrict__ on the two:
+// the barriers of ga_survive_rows stand between every read and the writes) — and rewrites its first pop_out rows of F, chosen, rank and cd.
+// counts [islands][3] = {flagged, non-finite, migrants accepted}.  gated (the ranking behind a migration; n_off 0, pop_out = n_pop): an
+// island that accepted no migrant keeps every bit of its state — ranking a population again would reorder a cut last front — and gets the
+// identity for the gather; the first two counters stay the generation's.
+__global__ __launch_bounds__(1024) void ga_survive_kernel(float* F, const float* Foff, const int* __restrict__ flags, int n_pop, int n_off, int M,
+                                                          int pop_out, int nsga, int gated, int* __restrict__ chosen, int* __restrict__ rank_out,
                                                           double* __restrict__ cd_out, int* __restrict__ counts) {
-    ga_survive_rows(F, F + (size_t)n_pop * M, F, flags, n_pop, n_off, M, pop_out, nsga, chosen, rank_out, cd_out, counts);
-}
-// The island form, one workgroup per island: island i ranks its pop population rows of F with its n_off (pop or 0) offspring rows of Foff —
-// two planes, the pass writes the islands' offspring F contiguously — and rewrites its rows of F, chosen, rank and cd; the algorithm and
-// the LDS layout are the kernel's above.  counts [islands][3] = {flagged, non-finite, migrants accepted}.  gated (the ranking behind a
-// migration, n_off 0): an island that accepted no migrant keeps every bit of its state — ranking a population again would reorder a cut
-// last front — and gets the identity for the gather; the first two counters stay the generation's.
-__global__ __launch_bounds__(1024) void ga_survive_islands_kernel(float* __restrict__ F, const float* __restrict__ Foff, const int* __restrict__ flags,
-                                                                  int pop, int n_off, int M, int nsga, int gated, int* __restrict__ chosen,
-                                                                  int* __restrict__ rank_out, double* __restrict__ cd_out, int* __restrict__ counts) {
-    const size_t o = (size_t)blockIdx.x * pop;
-    int* cnt = counts + blockIdx.x * 3;
+    // (a nullable pointer is null only where its island stride is 0 or the island is 0 — the launcher sees to it — so the offsets need no test)
+    const size_t isl = blockIdx.x, o = isl * pop_out;
+    int* cnt = counts + isl * 3;
     if (gated && cnt[2] == 0) {      // (uniform over the workgroup, ahead of every barrier)
-        for (int s = threadIdx.x; s < pop; s += blockDim.x) chosen[o + s] = s;
+        for (int s = threadIdx.x; s < pop_out; s += blockDim.x) chosen[o + s] = s;
         return;
     }
-    ga_survive_rows(F + o * M, n_off ? Foff + o * M : nullptr, F + o * M, n_off ? flags + o : nullptr, pop, n_off, M, pop, nsga, chosen + o, rank_out + o,
-                    cd_out + o, gated ? nullptr : cnt);
+    F += isl * n_pop * M;
+    ga_survive_rows(F, Foff + isl * n_off * M, F, flags + isl * n_off, n_pop, n_off, M, pop_out, nsga, chosen + o, rank_out + o, cd_out + o,
+                    gated ? nullptr : cnt);
 }
 
-// Xnext[s] = the merged row chosen[s] of (X ; Xoff).  grid (ceil(n_var / (256 VEC)), pop_out)
+// Xnext[s] = the merged row chosen[s] of (X ; Xoff), island by island: chosen holds island-local merged indices and an island's offspring
+// rows lie n_pop rows apart, as its population's.  grid (ceil(n_var / (256 VEC)), pop_out, islands)
 template <int VEC>
 __global__ __launch_bounds__(256) void ga_gather_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, const int* __restrict__ chosen,
-                                                        int n_pop, int n_var, float* __restrict__ Xnext) {
-    const int s = blockIdx.y, j0 = (blockIdx.x * 256 + threadIdx.x) * VEC, i = chosen[s];
+                                                        int n_pop, int pop_out, int n_var, float* __restrict__ Xnext) {
+    const size_t o = (size_t)blockIdx.z * n_pop, oo = (size_t)blockIdx.z * pop_out;
+    const int s = blockIdx.y, j0 = (blockIdx.x * 256 + threadIdx.x) * VEC, i = chosen[oo + s];
     if (j0 >= n_var || i < 0) return;
-    const float* src = (i < n_pop ? X + (size_t)i * n_var : Xoff + (size_t)(i - n_pop) * n_var) + j0;
-    float* dst = Xnext + (size_t)s * n_var + j0;
-    if (VEC == 4) *(f4*)dst = *(const f4*)src;
-    else dst[0] = src[0];
-}
-// the island form, grid (ceil(n_var / (256 VEC)), pop, islands): chosen holds island-local merged indices
-template <int VEC>
-__global__ __launch_bounds__(256) void ga_gather_islands_kernel(const float* __restrict__ X, const float* __restrict__ Xoff, const int* __restrict__ chosen,
-                                                                int pop, int n_var, float* __restrict__ Xnext) {
-    const size_t o = (size_t)blockIdx.z * pop;
-    const int s = blockIdx.y, j0 = (blockIdx.x * 256 + threadIdx.x) * VEC, i = chosen[o + s];
-    if (j0 >= n_var || i < 0) return;
-    const float* src = (i < pop ? X + (o + i) * n_var : Xoff + (o + i - pop) * n_var) + j0;
-    float* dst = Xnext + (o + s) * n_var + j0;
+    const float* src = (i < n_pop ? X + (o + i) * n_var : Xoff + (o + i - n_pop) * n_var) + j0;
+    float* dst = Xnext + (oo + s) * n_var + j0;
     if (VEC == 4) *(f4*)dst = *(const f4*)src;
     else dst[0] = src[0];
 }
@@ -497,51 +470,53 @@ size_t ga_survive_lds_bytes(int n_rows, int n_obj) {
     return N2 * 8 + N * 8 + N * (size_t)n_obj * 4 + 3 * N * 4 + (N + 2) * 4;
 }
 
-// columns [0, n_var) of rows `stride` floats apart
-static const char* launch_ga_vary_cols(const float* X, const int* rank, const double* cd, const GaParams& g, int n_var, int stride, int generation,
-                                       int row0, int rows, float* Xoff, hipStream_t st) {
-    if (n_var % 4 == 0 && stride % 4 == 0) {
-        hipLaunchKernelGGL(ga_vary_kernel<4>, dim3((n_var / 4 + 255) / 256, rows), dim3(256), 0, st, X, rank, cd, g, n_var, stride, generation, row0, Xoff);
-        return "ga_vary_kernel<4>";
+// One island: nothing beyond each launcher's own limits (a single search, and the diagnostic ops' shapes).  More: the island search's
+// limits (include/glass.h "Device search: islands").  nullptr from a launcher: the shape is outside them, nothing was launched.
+static bool ga_islands_ok(int islands, int pop, int n_var) {
+    return islands == 1 || (islands >= 2 && islands <= GLASS_SEARCH_MAX_ISLANDS && pop >= 2 && pop <= GLASS_SEARCH_MAX_POP && n_var >= 1 &&
+                            (long long)islands * pop * n_var < (1LL << 31));
+}
+
+const char* launch_ga_vary(const float* X, const int* rank, const double* cd, const GaParams& g, int islands, int n_real, int n_bits, int generation,
+                           int row0, int rows, int parts, float* Xoff, hipStream_t st) {
+    const int stride = n_real + n_bits;
+    if (rows <= 0 || row0 < 0 || row0 + rows > g.pop || n_real < 1 || n_bits < 0 || n_bits > GLASS_SEARCH_MAX_BITS || !(parts & GA_VARY_BOTH) ||
+        ((parts & GA_VARY_BITS) && n_bits < 1) || !ga_islands_ok(islands, g.pop, stride))
+        return nullptr;
+    const bool v4 = n_real % 4 == 0 && stride % 4 == 0;      // (every row is then 16-byte aligned)
+    if (parts & GA_VARY_REAL) {
+        if (v4)
+            hipLaunchKernelGGL(ga_vary_kernel<4>, dim3((n_real / 4 + 255) / 256, rows, islands), dim3(256), 0, st, X, rank, cd, g, n_real, stride, generation,
+                               row0, Xoff);
+        else
+            hipLaunchKernelGGL(ga_vary_kernel<1>, dim3((n_real + 255) / 256, rows, islands), dim3(256), 0, st, X, rank, cd, g, n_real, stride, generation,
+                               row0, Xoff);
     }
-    hipLaunchKernelGGL(ga_vary_kernel<1>, dim3((n_var + 255) / 256, rows), dim3(256), 0, st, X, rank, cd, g, n_var, stride, generation, row0, Xoff);
-    return "ga_vary_kernel<1>";
-}
-
-const char* launch_ga_vary(const float* X, const int* rank, const double* cd, const GaParams& g, int n_var, int generation, int row0, int rows,
-                           float* Xoff, hipStream_t st) {
-    if (rows <= 0 || row0 < 0 || row0 + rows > g.pop || n_var <= 0) return nullptr;
-    return launch_ga_vary_cols(X, rank, cd, g, n_var, n_var, generation, row0, rows, Xoff, st);
-}
-
-const char* launch_ga_vary_mixed(const float* X, const int* rank, const double* cd, const GaParams& g, int n_real, int n_bits, int generation, int row0,
-                                 int rows, int parts, float* Xoff, hipStream_t st) {
-    if (rows <= 0 || row0 < 0 || row0 + rows > g.pop || n_real < 1 || n_bits < 1 || n_bits > GLASS_SEARCH_MAX_BITS || !(parts & GA_VARY_BOTH)) return nullptr;
-    const char* real = nullptr;
-    if (parts & GA_VARY_REAL) real = launch_ga_vary_cols(X, rank, cd, g, n_real, n_real + n_bits, generation, row0, rows, Xoff, st);
     if (parts & GA_VARY_BITS)
-        hipLaunchKernelGGL(ga_vary_bits_kernel, dim3(rows), dim3(256), 0, st, X, rank, cd, g, n_real, n_bits, generation, row0, Xoff);
-    if (!(parts & GA_VARY_BITS)) return real;
+        hipLaunchKernelGGL(ga_vary_bits_kernel, dim3(rows, islands), dim3(256), 0, st, X, rank, cd, g, n_real, n_bits, generation, row0, Xoff);
+    if (!(parts & GA_VARY_BITS)) return v4 ? "ga_vary_kernel<4>" : "ga_vary_kernel<1>";
     if (!(parts & GA_VARY_REAL)) return "ga_vary_bits_kernel";
-    return n_real % 4 == 0 && n_bits % 4 == 0 ? "ga_vary_kernel<4> + ga_vary_bits_kernel" : "ga_vary_kernel<1> + ga_vary_bits_kernel";
+    return v4 ? "ga_vary_kernel<4> + ga_vary_bits_kernel" : "ga_vary_kernel<1> + ga_vary_bits_kernel";
 }
 
-const char* launch_ga_duplicates(const float* X, const float* Xoff, int pop, int n_off, int n_var, int* flags, hipStream_t st) {
-    if (pop < 0 || n_off <= 0 || n_var <= 0) return nullptr;
+const char* launch_ga_duplicates(const float* X, const float* Xoff, int islands, int pop, int n_off, int n_var, int* flags, hipStream_t st) {
+    if (pop < 0 || n_off <= 0 || n_var <= 0 || !ga_islands_ok(islands, pop, n_var) || (islands > 1 && n_off != pop)) return nullptr;
     if (n_var % 4 == 0) {
-        hipLaunchKernelGGL(ga_duplicates_kernel<4>, dim3(n_off), dim3(256), 0, st, X, Xoff, pop, n_var, flags);
+        hipLaunchKernelGGL(ga_duplicates_kernel<4>, dim3(n_off, islands), dim3(256), 0, st, X, Xoff, pop, n_off, n_var, flags);
         return "ga_duplicates_kernel<4>";
     }
-    hipLaunchKernelGGL(ga_duplicates_kernel<1>, dim3(n_off), dim3(256), 0, st, X, Xoff, pop, n_var, flags);
+    hipLaunchKernelGGL(ga_duplicates_kernel<1>, dim3(n_off, islands), dim3(256), 0, st, X, Xoff, pop, n_off, n_var, flags);
     return "ga_duplicates_kernel<1>";
 }
 
-const char* launch_ga_survive(float* F, const int* flags, int n_pop, int n_off, int n_obj, int pop_out, int nsga, int* chosen, int* rank_out,
-                              double* cd_out, int* counts, hipStream_t st) {
+const char* launch_ga_survive(float* F, const float* Foff, const int* flags, int islands, int n_pop, int n_off, int n_obj, int pop_out, int nsga, int gated,
+                              int* chosen, int* rank_out, double* cd_out, int* counts, hipStream_t st) {
     const int N = n_pop + n_off;
     if (n_pop < 1 || n_off < 0 || N > 2 * GLASS_SEARCH_MAX_POP || n_obj < 1 || n_obj > GLASS_SEARCH_MAX_OBJ || pop_out < 1 || pop_out > N ||
-        pop_out > GLASS_SEARCH_MAX_POP)
+        pop_out > GLASS_SEARCH_MAX_POP || (n_off && !Foff) || (gated && (n_off || pop_out != n_pop || !counts)))
         return nullptr;
+    // (more islands: an island's first pop_out rows of F stay inside its own n_pop, and the kernel offsets flags and counts untested)
+    if (!ga_islands_ok(islands, n_pop, 1) || (islands > 1 && ((n_off && (n_off != n_pop || !flags)) || pop_out != n_pop || !counts))) return nullptr;
     const size_t lds = ga_survive_lds_bytes(N, n_obj);
     if (lds > 64 * 1024) {
         if (!glass_lds_fits((int)lds)) return nullptr;
@@ -551,82 +526,22 @@ const char* launch_ga_survive(float* F, const int* flags, int n_pop, int n_off, 
                                       (int)ga_survive_lds_bytes(2 * GLASS_SEARCH_MAX_POP, GLASS_SEARCH_MAX_OBJ));
         });
     }
-    hipLaunchKernelGGL(ga_survive_kernel, dim3(1), dim3(1024), lds, st, F, flags, n_pop, n_off, n_obj, pop_out, nsga, chosen, rank_out, cd_out, counts);
+    hipLaunchKernelGGL(ga_survive_kernel, dim3(islands), dim3(1024), lds, st, F, Foff, flags, n_pop, n_off, n_obj, pop_out, nsga, gated, chosen, rank_out,
+                       cd_out, counts);
     return "ga_survive_kernel";
 }
 
-void launch_ga_gather(const float* X, const float* Xoff, const int* chosen, int n_pop, int pop_out, int n_var, float* Xnext, hipStream_t st) {
+void launch_ga_gather(const float* X, const float* Xoff, const int* chosen, int islands, int n_pop, int pop_out, int n_var, float* Xnext, hipStream_t st) {
     if (n_var % 4 == 0)
-        hipLaunchKernelGGL(ga_gather_kernel<4>, dim3((n_var / 4 + 255) / 256, pop_out), dim3(256), 0, st, X, Xoff, chosen, n_pop, n_var, Xnext);
+        hipLaunchKernelGGL(ga_gather_kernel<4>, dim3((n_var / 4 + 255) / 256, pop_out, islands), dim3(256), 0, st, X, Xoff, chosen, n_pop, pop_out, n_var,
+                           Xnext);
     else
-        hipLaunchKernelGGL(ga_gather_kernel<1>, dim3((n_var + 255) / 256, pop_out), dim3(256), 0, st, X, Xoff, chosen, n_pop, n_var, Xnext);
-}
-
-// ---- the island forms (include/glass.h "Device search: islands"): nullptr / false where the shape is outside the limits ----
-static bool ga_islands_ok(int islands, int pop, int n_var) {
-    return islands >= 1 && islands <= GLASS_SEARCH_MAX_ISLANDS && pop >= 2 && pop <= GLASS_SEARCH_MAX_POP && n_var >= 1 &&
-           (long long)islands * pop * n_var < (1LL << 31);
-}
-
-const char* launch_ga_vary_islands(const float* X, const int* rank, const double* cd, const GaParams& g, int islands, int n_real, int n_bits,
-                                   int generation, int parts, float* Xoff, hipStream_t st) {
-    const int stride = n_real + n_bits;
-    if (!ga_islands_ok(islands, g.pop, stride) || n_real < 1 || n_bits < 0 || n_bits > GLASS_SEARCH_MAX_BITS || !(parts & GA_VARY_BOTH)) return nullptr;
-    if ((parts & GA_VARY_BITS) && n_bits < 1) return nullptr;
-    const bool v4 = n_real % 4 == 0 && stride % 4 == 0;
-    if (parts & GA_VARY_REAL) {
-        if (v4)
-            hipLaunchKernelGGL(ga_vary_islands_kernel<4>, dim3((n_real / 4 + 255) / 256, g.pop, islands), dim3(256), 0, st, X, rank, cd, g, n_real, stride,
-                               generation, Xoff);
-        else
-            hipLaunchKernelGGL(ga_vary_islands_kernel<1>, dim3((n_real + 255) / 256, g.pop, islands), dim3(256), 0, st, X, rank, cd, g, n_real, stride,
-                               generation, Xoff);
-    }
-    if (parts & GA_VARY_BITS)
-        hipLaunchKernelGGL(ga_vary_bits_islands_kernel, dim3(g.pop, islands), dim3(256), 0, st, X, rank, cd, g, n_real, n_bits, generation, Xoff);
-    if (!(parts & GA_VARY_BITS)) return v4 ? "ga_vary_islands_kernel<4>" : "ga_vary_islands_kernel<1>";
-    if (!(parts & GA_VARY_REAL)) return "ga_vary_bits_islands_kernel";
-    return v4 ? "ga_vary_islands_kernel<4> + ga_vary_bits_islands_kernel" : "ga_vary_islands_kernel<1> + ga_vary_bits_islands_kernel";
-}
-
-const char* launch_ga_duplicates_islands(const float* X, const float* Xoff, int islands, int pop, int n_var, int* flags, hipStream_t st) {
-    if (!ga_islands_ok(islands, pop, n_var)) return nullptr;
-    if (n_var % 4 == 0) {
-        hipLaunchKernelGGL(ga_duplicates_islands_kernel<4>, dim3(pop, islands), dim3(256), 0, st, X, Xoff, pop, n_var, flags);
-        return "ga_duplicates_islands_kernel<4>";
-    }
-    hipLaunchKernelGGL(ga_duplicates_islands_kernel<1>, dim3(pop, islands), dim3(256), 0, st, X, Xoff, pop, n_var, flags);
-    return "ga_duplicates_islands_kernel<1>";
-}
-
-const char* launch_ga_survive_islands(float* F, const float* Foff, const int* flags, int islands, int pop, int n_off, int n_obj, int nsga, int gated,
-                                      int* chosen, int* rank_out, double* cd_out, int* counts, hipStream_t st) {
-    if (!ga_islands_ok(islands, pop, 1) || (n_off != 0 && n_off != pop) || (n_off && !Foff) || n_obj < 1 || n_obj > GLASS_SEARCH_MAX_OBJ || (gated && n_off))
-        return nullptr;
-    const size_t lds = ga_survive_lds_bytes(pop + n_off, n_obj);
-    if (lds > 64 * 1024) {
-        if (!glass_lds_fits((int)lds)) return nullptr;
-        static DevOnce once;
-        once.run([&] {
-            (void)hipFuncSetAttribute((const void*)ga_survive_islands_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)ga_survive_lds_bytes(2 * GLASS_SEARCH_MAX_POP, GLASS_SEARCH_MAX_OBJ));
-        });
-    }
-    hipLaunchKernelGGL(ga_survive_islands_kernel, dim3(islands), dim3(1024), lds, st, F, Foff, flags, pop, n_off, n_obj, nsga, gated, chosen, rank_out,
-                       cd_out, counts);
-    return "ga_survive_islands_kernel";
-}
-
-void launch_ga_gather_islands(const float* X, const float* Xoff, const int* chosen, int islands, int pop, int n_var, float* Xnext, hipStream_t st) {
-    if (n_var % 4 == 0)
-        hipLaunchKernelGGL(ga_gather_islands_kernel<4>, dim3((n_var / 4 + 255) / 256, pop, islands), dim3(256), 0, st, X, Xoff, chosen, pop, n_var, Xnext);
-    else
-        hipLaunchKernelGGL(ga_gather_islands_kernel<1>, dim3((n_var + 255) / 256, pop, islands), dim3(256), 0, st, X, Xoff, chosen, pop, n_var, Xnext);
+        hipLaunchKernelGGL(ga_gather_kernel<1>, dim3((n_var + 255) / 256, pop_out, islands), dim3(256), 0, st, X, Xoff, chosen, n_pop, pop_out, n_var, Xnext);
 }
 
 const char* launch_ga_migrate(float* X, float* F, const int* rank, const double* cd, int islands, int pop, int n_var, int n_obj, int migrants, int* counts,
                               hipStream_t st) {
-    if (!ga_islands_ok(islands, pop, n_var) || islands < 2 || migrants < 1 || migrants > pop / 2 || n_obj < 1 || n_obj > GLASS_SEARCH_MAX_OBJ) return nullptr;
+    if (islands < 2 || !ga_islands_ok(islands, pop, n_var) || migrants < 1 || migrants > pop / 2 || n_obj < 1 || n_obj > GLASS_SEARCH_MAX_OBJ) return nullptr;
     if (n_var % 4 == 0) {
         hipLaunchKernelGGL(ga_migrate_kernel<4>, dim3(islands), dim3(1024), 0, st, X, F, rank, cd, islands, pop, n_var, n_obj, migrants, counts);
         return "ga_migrate_kernel<4>";

@@ -297,7 +297,7 @@ int glass_op_lpips_head(int32_t device, int32_t n, int32_t HW, int32_t C, int32_
  * does not take is refused by name (GLASS_ERR_ARG).
  * glass_op_ga_vary: X [pop,n_var], rank int32 [pop], cd double [pop] -> offspring rows [row0, row0 + rows) of `generation`, out [rows,n_var].
  * glass_op_ga_vary_mixed: the same for mixed rows of n_real real columns and n_bits bit columns (0.0 / 1.0), X and out [.,n_real + n_bits]:
- *   both kernels of launch_ga_vary_mixed.
+ *   both kernels of launch_ga_vary (parts GA_VARY_BOTH).  These four run one island, as a single search does.
  * glass_op_ga_duplicates: X [pop,n_var], Xoff [n_off,n_var] -> flags int32 [n_off].
  * glass_op_ga_survive: F [n_pop + n_off, n_obj] (population first), flags int32 [n_off] (nullable) -> chosen int32 [pop_out] (merged indices in
  *   survival order), rank int32 [pop_out], cd double [pop_out], F_out [pop_out,n_obj], counts int32 [2] = {flagged, non-finite rows}; with X
@@ -312,7 +312,8 @@ int glass_op_ga_survive(int32_t device, int32_t n_pop, int32_t n_off, int32_t n_
                         const int32_t* flags, int32_t* chosen, int32_t* rank, double* cd, float* F_out, int32_t* counts, int32_t n_var, const float* X,
                         const float* Xoff, float* X_out);
 /* The island kernels (search.hip; include/glass.h "Device search: islands").
- * glass_op_ga_migrate: the whole migration — ga_migrate_kernel, the gated island survival and the island gather, as the engine launches them:
+ * glass_op_ga_migrate: the whole migration — ga_migrate_kernel, then launch_ga_survive gated and launch_ga_gather over the islands, as the
+ *   engine launches them:
  *   X [islands pop,n_var], F [islands pop,n_obj], rank int32 and cd double [islands pop] as survival left them -> the same four after the
  *   migration, accepted int32 [islands].  islands >= 2, migrants in [1, pop / 2].
  * glass_op_noise_period: glass_op_noise with launch_noise's period: plane m is that of minibatch (mb0 + m) % period (period 0: mb0 + m). */

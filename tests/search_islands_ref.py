@@ -1,4 +1,4 @@
-"""Numpy mirror of the island rule (include/glass.h "Device search: islands"; csrc/search.hip ga_migrate_kernel and the island forms), built on
+"""Numpy mirror of the island rule (include/glass.h "Device search: islands"; csrc/search.hip ga_migrate_kernel and the island dimension of every phase's kernel), built on
 search_device_ref.py and search_mixed_ref.py: island i is the single search under seed + i on its own rows, and migrate() is the ring.
 
 Not a test module: tests/test_search_islands_ref.py pins it to known answers and shows that its checker fails on planted faults; the GPU

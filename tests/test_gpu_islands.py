@@ -228,8 +228,8 @@ def test_own_prompts_refusals():
 
 
 def test_off_means_off():
-    """An engine that never calls the setter launches the single search's kernels and nothing else; set_search_islands(1, 0, 1) runs the island
-    forms and gives the same search, bit for bit."""
+    """An engine that never calls the setter and one under set_search_islands(1, 0, 1) launch the same three kernels — there is one instance per
+    phase, and a single search is its island 0 — and are the same search, bit for bit; only the island entry points tell them apart."""
     off, k1 = make(True, 4), make(True, 4, islands=1)
     rows = {}
     for name, e in (("off", off), ("k1", k1)):
@@ -239,8 +239,7 @@ def test_off_means_off():
             e.search_step(gen)
         rows[name] = sorted(r["name"] for r in e.profile() if r["name"].startswith("search."))
     assert rows["off"] == ["search.duplicates@ga_duplicates_kernel<4>", "search.survive@ga_survive_kernel", "search.vary@ga_vary_kernel<4>"]
-    assert rows["k1"] == ["search.duplicates@ga_duplicates_islands_kernel<4>", "search.survive@ga_survive_islands_kernel",
-                          "search.vary@ga_vary_islands_kernel<4>"]
+    assert rows["k1"] == ["search.duplicates@ga_duplicates_kernel<4>", "search.survive@ga_survive_kernel", "search.vary@ga_vary_kernel<4>"]
     a, b = off.search_read(*ALL, "counts"), k1.search_read(*ALL, "counts")
     for k in a:
         assert same(a[k], b[k]), k

@@ -2,9 +2,10 @@
 kernels"), against the numpy mirror tests/search_islands_ref.py.  Everything is exact: rows, F, ranks and the accepted counts as they are,
 distances and noise planes bit for bit.
 
-glass_op_ga_migrate runs what the engine launches behind a due migration — ga_migrate_kernel, the gated island survival, the island gather —
-on the hand-made cases of tests/test_search_islands_ref.py (ring direction at K = 2 and 3, n = pop / 2, duplicates, -0.0, the NSGA-II order
-through infinite distances) and on K = 3, pop 8 at n_var 513 (rows off the 16-byte vector) and 512 (on it)."""
+glass_op_ga_migrate runs what the engine launches behind a due migration — ga_migrate_kernel, the gated ga_survive_kernel and ga_gather_kernel
+over the islands — on the hand-made cases of tests/test_search_islands_ref.py (ring direction at K = 2 and 3, n = pop / 2, duplicates, -0.0,
+the NSGA-II order through infinite distances) and on K = 3, pop 8 at n_var 513 (rows off the 16-byte vector) and 512 (on it).  The rows that
+are no multiple of 4 wide are the only place where the VEC = 1 instances run with more than one island: the mini models' rows are."""
 import os
 
 import numpy as np
