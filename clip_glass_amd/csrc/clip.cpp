@@ -494,25 +494,20 @@ static void run_rn_blocks(glass_engine* e, int P, int l0, int l1) {
     }
 }
 static void clip_cosine(glass_engine* e, int P, int views) {      // the end of both towers' heads: d_feat [P][embed] against the target
-    if (views < 0) return;    // the features alone (the direction source's own encoding)
-    const int E = e->cfg.clip_embed;
-    const glass_engine::PromptSet& ps = e->pset;
-    if (e->edit.has_source && ps.T > 0 && e->edit.d_src) {      // image editing: the set's entries are directions, the rows move away from the source's
-        const int V = std::max(views, 1);
-        if (!launch_cosine_set_dir(e->d_feat, ps.d_targets, ps.d_weights, ps.W, P / V, V, ps.T, E, e->edit.d_src, views > 0 ? e->d_view_sim : nullptr, ps.d_sim,
-                                   e->d_sim, e->cur) &&
-            e->launch_error.empty())
-            e->launch_error = "no kernel accepts layer clip.head (cosine_set_dir: shape outside its limits)";
-    } else if (ps.T > 0) {           // a prompt set: every row against every entry, still one launch
-        const int V = std::max(views, 1);
-        CosineIslands isl;      // a pass of an island search with own prompts: the rows' weights by island
-        if (e->island_row0 >= 0 && e->search.own_prompts) isl = {ps.d_isl_weights, ps.d_isl_W, e->search.g.pop, e->island_row0};
-        if (!launch_cosine_set(e->d_feat, ps.d_targets, ps.d_weights, ps.W, P / V, V, ps.T, E, views > 0 ? e->d_view_sim : nullptr, ps.d_sim, e->d_sim, e->cur,
-                               isl) &&
-            e->launch_error.empty())
-            e->launch_error = "no kernel accepts layer clip.head (cosine_set: shape outside its limits)";
-    } else if (views > 0) launch_cosine_views(e->d_feat, e->d_target, P / views, views, E, e->d_view_sim, e->d_sim, e->cur);
-    else launch_cosine(e->d_feat, e->d_target, P, E, e->d_sim, e->cur);
+    const glass_engine::PromptSet& ps = e->pset;      // set_target's feature is the set of one
+    if (views < 0 || ps.T == 0) return;    // the features alone (the direction source's own encoding; an encode_* call before any target)
+    CosineSet a;
+    a.feat = e->d_feat, a.targets = ps.d_targets, a.weights = ps.d_weights, a.W = ps.W;
+    a.V = std::max(views, 1), a.P = P / a.V, a.T = ps.T, a.D = e->cfg.clip_embed;
+    if (views > 0) a.view_sim = e->d_view_sim;
+    a.set_sim = ps.d_sim, a.sim = e->d_sim;
+    // image editing: the set's entries are directions, the rows move away from the source's
+    if (e->edit.has_source && ps.given()) a.src = e->edit.d_src;
+    // a pass of an island search with own prompts: the rows' weights by island
+    else if (ps.given() && e->island_row0 >= 0 && e->search.own_prompts) a.isl = {ps.d_isl_weights, ps.d_isl_W, e->search.g.pop, e->island_row0};
+    if (!launch_cosine_set(a, e->cur) && e->launch_error.empty())
+        e->launch_error = a.src ? "no kernel accepts layer clip.head (cosine_set_dir: shape outside its limits)"
+                                : "no kernel accepts layer clip.head (cosine_set: shape outside its limits)";
 }
 static void run_rn_head(glass_engine* e, int P, int views) {
     const glass_config& c = e->cfg;

@@ -38,6 +38,37 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
     }
 }
 
+// ---- wave64 reductions: the butterfly over offsets 32, 16, .. 1 leaves the result in every lane.  The ONE wave sum of the library: values
+// that tests compare bit for bit across kernels (the cosines of score.hip, unit_rows_kernel) are summed in this order
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+// acc + a * b.  FUSED: one rounding (fmaf).  Otherwise the product and the sum are rounded on their own, as numpy float32 does — the operators
+// are written in a block with contraction off (HIP's __fmul_rn / __fadd_rn are plain * and + and fuse where contraction is on)
+template <bool FUSED>
+__device__ __forceinline__ float mac(float acc, float a, float b) {
+    if constexpr (FUSED) return fmaf(a, b, acc);
+    else {
+#pragma clang fp contract(off)
+        const float prod = a * b;
+        return acc + prod;
+    }
+}
+// max(|f|, 1e-8) of one row by one wave: lane-strided partial sums (i = lane; i < D; i += 64) of separately rounded products, then the wave
+// sum.  unit_rows_kernel (edit.hip) and the directional cosine (score.hip) both divide by it: a feature with the source's bits gives x = 0
+__device__ __forceinline__ float unit_row_norm(const float* __restrict__ f, int D, int lane) {
+    float xx = 0.f;
+    for (int i = lane; i < D; i += 64) xx = mac<false>(xx, f[i], f[i]);
+    return fmaxf(sqrtf(wave_sum(xx)), 1e-8f);
+}
+
 // ---- toRGB applied to a wave's output tile while it is still in registers (conv_stream / conv_tiled / conv_glds) -------------
 // The activated fp16 quads a lane holds after the epilogue math (lane (px, kh): channels j*32 + 8g + 4kh + q of pixel px) are a
 // valid MFMA B operand as they stand — the K order of an MFMA is free as long as A uses the same one.  A = 16-row weight table

@@ -371,7 +371,9 @@ static int alloc_buffers(glass_engine* e) {
     if ((rc = dev_alloc(e, &e->d_sim, (size_t)P))) return rc;
     if ((rc = dev_alloc(e, &e->d_dis, (size_t)P))) return rc;
     if ((rc = dev_alloc(e, &e->d_F, (size_t)P * std::max(c.lpips_size ? 3 : 2, c.n_obj)))) return rc;
-    if ((rc = dev_alloc(e, &e->d_target, (size_t)c.clip_embed))) return rc;
+    if ((rc = dev_alloc(e, &e->pset.d_targets, (size_t)GLASS_PROMPT_MAX * c.clip_embed))) return rc;
+    if ((rc = dev_alloc(e, &e->pset.d_weights, (size_t)GLASS_PROMPT_MAX))) return rc;
+    if ((rc = dev_alloc(e, &e->pset.d_sim, (size_t)P * GLASS_PROMPT_MAX))) return rc;
     if (c.use_discriminator && c.n_blocks > 0) {
         if ((rc = dev_alloc(e, &e->d_dfin, (size_t)P * 16 * c.channels[0]))) return rc;
         if ((rc = dev_alloc(e, &e->d_dh, (size_t)P * c.channels[0]))) return rc;
@@ -424,9 +426,14 @@ extern "C" int glass_engine_set_target(glass_engine* e, const float* feat, int32
     GLASS_HIP(hipSetDevice(e->cfg.device));
     REQUIRE(sim_columns(e->cfg) < 2, GLASS_ERR_STATE,
             "set_target: this engine has sim_columns >= 2 (one column per prompt): give it a prompt set with set_targets()");
-    GLASS_HIP(hipMemcpy(e->d_target, feat, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    e->has_target = true;
-    e->pset.T = 0;      // one target again: the head ends in cosine_kernel / cosine_views_kernel
+    glass_engine::PromptSet& ps = e->pset;      // the set of one: entry 0, weight 1, W = 1, mode sum — (0 + 1 c) / 1 is c in fp32
+    const float one = 1.f;
+    GLASS_HIP(hipMemcpy(ps.d_targets, feat, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    GLASS_HIP(hipMemcpy(ps.d_weights, &one, sizeof(float), hipMemcpyHostToDevice));
+    ps.W = 1.f;
+    ps.T = 1;
+    ps.mode = 0;
+    ps.single = true;
     return GLASS_OK;
 }
 
@@ -460,24 +467,19 @@ extern "C" int glass_engine_set_targets(glass_engine* e, const float* feats, con
                 "set_targets: weight " + std::to_string(t) + " must be finite and non-zero (negative: away from the prompt)");
     GLASS_HIP(hipSetDevice(e->cfg.device));
     glass_engine::PromptSet& ps = e->pset;
-    if (!ps.d_targets) {      // the first set of this engine
-        int rc;
-        if ((rc = dev_alloc(e, &ps.d_sim, (size_t)e->cfg.max_pop * GLASS_PROMPT_MAX))) return rc;
-        if ((rc = dev_alloc(e, &ps.d_weights, (size_t)GLASS_PROMPT_MAX))) return rc;
-        if ((rc = dev_alloc(e, &ps.d_targets, (size_t)GLASS_PROMPT_MAX * E))) return rc;
-    }
     GLASS_HIP(hipMemcpy(ps.d_targets, feats, (size_t)T * E * sizeof(float), hipMemcpyHostToDevice));
     GLASS_HIP(hipMemcpy(ps.d_weights, weights, (size_t)T * sizeof(float), hipMemcpyHostToDevice));
     ps.W = prompt_weight_sum(weights, T);
     ps.T = T;
     ps.mode = mode;
+    ps.single = false;
     return GLASS_OK;
 }
 
 extern "C" int glass_engine_last_set_details(glass_engine* e, int32_t P, float* set_sim) {
     REQUIRE(e && e->finalized, GLASS_ERR_STATE, "engine not ready");
     REQUIRE(set_sim, GLASS_ERR_ARG, "null argument");
-    REQUIRE(e->pset.T > 0, GLASS_ERR_STATE, "no prompt set is active (glass_engine_set_targets)");
+    REQUIRE(e->pset.given(), GLASS_ERR_STATE, "no prompt set is active (glass_engine_set_targets)");
     REQUIRE(P > 0 && P <= e->last_P, GLASS_ERR_ARG, "P exceeds the last evaluated population");
     GLASS_HIP(hipSetDevice(e->cfg.device));
     GLASS_HIP(hipMemcpy(set_sim, e->pset.d_sim, (size_t)P * e->pset.T * sizeof(float), hipMemcpyDeviceToHost));
@@ -614,18 +616,19 @@ static int finish_pass(glass_engine* e, int P, float* out_F, bool clip_done, hip
             GLASS_HIP(hipEventRecord(e->ev_g[0], d_join));
             GLASS_HIP(hipStreamWaitEvent(e->stream, e->ev_g[0], 0));
         }
-        if (c.anchor) {       // image editing: the layout with the anchor distance in it (its own last column, or folded into column 0)
-            const bool pareto = e->pset.T > 0 && e->pset.mode == 1;
-            if (!launch_assemble_F_edit(e->d_sim, pareto ? e->pset.d_sim : nullptr, pareto ? e->pset.d_weights : nullptr, pareto ? e->pset.T : 1,
-                                        c.use_discriminator ? e->d_dis : nullptr, c.lpips_size ? e->lp.d : nullptr, c.lpips_lambda, e->edit.d_dist, c.anchor_lambda, P,
-                                        c.n_obj, e->d_F, e->cur) &&
-                e->launch_error.empty())
-                e->launch_error = "no kernel accepts layer assemble_F (assemble_F_edit: the columns do not add up to n_obj)";
-        } else if (e->pset.T > 0 && e->pset.mode == 1)
-            launch_assemble_F_set(e->pset.d_sim, e->pset.d_weights, c.use_discriminator ? e->d_dis : nullptr, c.lpips_size ? e->lp.d : nullptr, e->pset.T, P,
-                                  e->d_F, e->cur);
-        else if (c.lpips_size) launch_assemble_F_lpips(e->d_sim, e->d_dis, e->lp.d, c.lpips_lambda, c.use_discriminator ? 1 : 0, P, c.n_obj, e->d_F, e->cur);
-        else launch_assemble_F(e->d_sim, e->d_dis, P, c.n_obj, e->d_F, e->cur);
+        const glass_engine::PromptSet& ps = e->pset;
+        const bool pareto = ps.given() && ps.mode == 1;
+        AssembleF a;
+        a.sim = e->d_sim;
+        if (pareto) a.set_sim = ps.d_sim, a.weights = ps.d_weights, a.K = ps.T;
+        if (c.lpips_size) a.lp = e->lp.d, a.lp_lambda = c.lpips_lambda;
+        if (c.anchor) a.anchor = e->edit.d_dist, a.anchor_lambda = c.anchor_lambda;      // image editing: its own last column, or folded into column 0
+        a.P = P, a.n_obj = c.n_obj, a.F = e->d_F;
+        // the hinge is the column n_obj has beyond the others: without LPIPS and anchor, glass_engine_create takes n_obj 1 or 2 as it comes
+        const int others = (pareto ? ps.T : 1) + (a.lp && !(a.lp_lambda > 0.f) ? 1 : 0) + (a.anchor && !(a.anchor_lambda > 0.f) ? 1 : 0);
+        if (c.n_obj > others) a.dis = e->d_dis;
+        if (!launch_assemble_F(a, e->cur) && e->launch_error.empty())
+            e->launch_error = "no kernel accepts layer assemble_F (assemble_F_edit: the columns do not add up to n_obj)";
         if (d_F_dst)
             GLASS_HIP(hipMemcpyAsync(d_F_dst, e->d_F, (size_t)P * c.n_obj * sizeof(float), hipMemcpyDeviceToDevice, e->cur));
         else
@@ -649,13 +652,13 @@ int run_pass(glass_engine* e, const float* latents, int P, int generation, int f
             "population size must be a multiple of batch_size (reference asserts: models.py:112)");
     const bool biggan = c.generator == GLASS_GEN_BIGGAN_DEEP;
     REQUIRE(e->cfg.n_blocks > 0 || biggan, GLASS_ERR_STATE, "this engine was created without a GAN (n_blocks = 0)");
-    if (out_F && sim_columns(c) >= 2) REQUIRE(e->pset.T > 0, GLASS_ERR_STATE, "set_targets() first (this engine has sim_columns >= 2: one column of F per prompt)");
-    else if (out_F) REQUIRE(e->has_target || e->pset.T > 0, GLASS_ERR_STATE, "set_target() first");
+    if (out_F && sim_columns(c) >= 2) REQUIRE(e->pset.given(), GLASS_ERR_STATE, "set_targets() first (this engine has sim_columns >= 2: one column of F per prompt)");
+    else if (out_F) REQUIRE(e->pset.T > 0, GLASS_ERR_STATE, "set_target() first");
     const bool lpips = out_F && c.lpips_size > 0;
     if (lpips) REQUIRE(e->lp.has_target, GLASS_ERR_STATE, "set_lpips_target() first");
     const bool anchor = out_F && c.anchor, source = out_F && e->edit.has_source;      // image editing (opt-in)
     if (anchor) REQUIRE(e->edit.has_anchor, GLASS_ERR_STATE, "set_anchor() first (this engine was created with anchor = 1)");
-    if (source) REQUIRE(e->pset.T > 0, GLASS_ERR_STATE, "set_targets() first (a direction source is set: the targets are the directions of a prompt set)");
+    if (source) REQUIRE(e->pset.given(), GLASS_ERR_STATE, "set_targets() first (a direction source is set: the targets are the directions of a prompt set)");
     REQUIRE(e->latent_space != GLASS_LATENT_SUB || e->has_subspace, GLASS_ERR_STATE, "set_subspace() first (latent space sub: a row is coefficients of a basis the engine does not have yet)");
     GLASS_HIP(hipSetDevice(c.device));
     e->launch_error.clear();      // (a pass that returned early through GLASS_HIP must not leave its message to the next one)

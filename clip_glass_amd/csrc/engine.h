@@ -149,7 +149,7 @@ struct glass_engine {
     int n_style = 0;  // number of style (affine) layers
     int S_total = 0, D_total = 0;
     int chunk = 0;
-    bool finalized = false, has_target = false;
+    bool finalized = false;
     hipStream_t stream = nullptr, stream_d = nullptr, cur = nullptr;  // main, second (D/resize), current target
     bool overlap = false, clip_overlap = false;
     std::vector<hipEvent_t> ev_g, ev_d;
@@ -239,7 +239,6 @@ struct glass_engine {
         std::vector<void*> owned;   // every buffer above (owned_alloc), freed by text_work_free
     } twork;
     int t_width = 0, t_ctx = 0, t_vocab = 0;
-    float* d_target = nullptr;
 
     // ---- activations / scratch ----
     half_t* d_s16 = nullptr;   // fp16 copy of d_s (normalised styles)
@@ -279,12 +278,14 @@ struct glass_engine {
     std::vector<glass_prof_row> prof_rows;
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
-    // ---- prompt set (glass_engine_set_targets; T 0: none — the head ends in cosine_kernel / cosine_views_kernel against d_target).  The
-    // three buffers are allocated by the first set_targets call: an engine that never calls it holds nothing of this ----
+    // ---- the CLIP targets: a prompt set (glass_engine_set_targets), or glass_engine_set_target's one feature as entry 0 with weight 1,
+    // W = 1, mode sum (`single`); T 0: none yet.  The head ends in one cosine_set_kernel launch either way (score.hip) ----
     struct PromptSet {
         int T = 0, mode = 0;                // entries; 0 sum, 1 pareto
+        bool single = false;                // set_target's set of one: no prompt set as far as the API is concerned
+        bool given() const { return T > 0 && !single; }      // a set given by set_targets
         float W = 0.f;                      // sum |w_t|
-        float *d_targets = nullptr, *d_weights = nullptr, *d_sim = nullptr;    // [16][clip_embed], [16], [max_pop][16] (rows of T in use)
+        float *d_targets = nullptr, *d_weights = nullptr, *d_sim = nullptr;    // [16][clip_embed], [16], [max_pop][16] (rows of T in use): alloc_buffers
         // own prompts of an island search (glass_engine_set_island_weights; allocated by its first call): weights [islands][isl_T], sum |w| [islands]
         float *d_isl_weights = nullptr, *d_isl_W = nullptr;
         int isl_T = 0;
@@ -325,7 +326,7 @@ struct glass_engine {
         float* d_dist = nullptr;            // [max_pop]: d of the last pass
         bool has_anchor = false;
         // direction source
-        bool has_source = false;            // a source image is set: the similarity is cosine_set_dir_kernel's
+        bool has_source = false;            // a source image is set: the similarity is cosine_set_kernel's directional form
         bool rows_valid = false;            // d_src holds the rows of d_img under `boxes`
         float* d_img = nullptr;             // [3][R][R] in [-1, 1]
         float* d_src = nullptr;             // [max(views, 1)][clip_embed] unit rows

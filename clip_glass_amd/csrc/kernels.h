@@ -164,49 +164,56 @@ void launch_layernorm(const float* x, long long row_stride, int M, int D, const 
 void launch_layernorm_rows(const float* x, const int* rows, int M, int D, const float* g, const float* b, float* out32, hipStream_t st);
 void launch_attention(const half_t* qkv, int n_img, int L, int heads, int hd, int causal, half_t* out,
                       hipStream_t st);
-void launch_cosine(const float* feat, const float* target, int P, int D, float* sim, hipStream_t st);
-// crop views: feat [P][V][D]; view_sim[p V + v] = launch_cosine's value of that row, sim[p] = their fp32 mean summed in the order v = 0 .. V - 1
-void launch_cosine_views(const float* feat, const float* target, int P, int V, int D, float* view_sim, float* sim, hipStream_t st);
-void launch_assemble_F(const float* sim, const float* dis, int P, int n_obj, float* F, hipStream_t st);
-// the same rows with the perceptual distance lp [P]: lambda == 0: its own LAST column; lambda > 0: F[:, 0] = fmaf(lambda, lp, -sim), no column.
-// has_d: column 1 is the discriminator hinge
-void launch_assemble_F_lpips(const float* sim, const float* dis, const float* lp, float lambda, int has_d, int P, int n_obj, float* F, hipStream_t st);
-// --- prompt sets (prompt_set.hip; include/glass.h "Prompt sets") ---
+// --- the score tail (score.hip): one cosine kernel, one assemble_F kernel ---
 #define GLASS_PROMPT_MAX 16         // entries of a set
 #define GLASS_PROMPT_MAX_VIEWS 16   // glass_clip_views_supported's limit
-// feat [P][V][D] (V = 1: no views), targets [T][D], weights [T], W = prompt_weight_sum -> view_sim [P][V] (nullable: entry 0's per-view cosines),
-// set_sim [P][T] (the ordered means), sim [P] (the combination of mode `sum`).  One launch; false: a shape outside the limits, nothing launched
-// isl (the device search's islands with own prompts): row p combines its entries with row (row0 + p) / pop of weights [islands][T] and that
-// island's W [islands] instead; weights nullptr: none
+// the device search's islands with own prompts: row p combines its entries with row (row0 + p) / pop of weights [islands][T] and that
+// island's W [islands] instead of the set's; weights nullptr: none
 struct CosineIslands {
     const float* weights = nullptr;
     const float* W = nullptr;
     int pop = 0, row0 = 0;
 };
-bool launch_cosine_set(const float* feat, const float* targets, const float* weights, float W, int P, int V, int T, int D, float* view_sim,
-                       float* set_sim, float* sim, hipStream_t st, CosineIslands isl = {});
+// feat [P][V][D] (V = 1: no views), targets [T][D], weights [T], W = prompt_weight_sum -> view_sim [P][V] (nullable: entry 0's per-view cosines),
+// set_sim [P][T] (the ordered means over the views), sim [P] (the combination of mode `sum`).  A single target is T = 1, weight 1, W = 1:
+// sim = set_sim = the cosine.  src [V][D] (nullable; unit rows, launch_unit_rows): the directional form — every (row, view, entry) value is the
+// cosine between f / max(|f|, 1e-8) - src[v] and the entry, every product and sum rounded on its own.  streamed: the form that reads the set
+// from memory at any shape (the launcher chooses it above 64 KB): the same bits
+struct CosineSet {
+    const float *feat = nullptr, *targets = nullptr, *weights = nullptr;
+    float W = 0.f;
+    int P = 0, V = 1, T = 0, D = 0;
+    const float* src = nullptr;
+    float *view_sim = nullptr, *set_sim = nullptr, *sim = nullptr;
+    CosineIslands isl;
+    bool streamed = false;
+};
+// One launch; false: a shape outside the limits (V, T in [1, 16], D <= 2^20) or a broken island table, nothing launched
+bool launch_cosine_set(const CosineSet& a, hipStream_t st);
 float prompt_weight_sum(const float* weights, int T);      // sum |w_t| in fp32, t = 0 .. T - 1 (host)
-// F [P][K + (dis != 0) + (lp != 0)]: F[p][t] = w_t < 0 ? set_sim[p][t] : -set_sim[p][t], then relu(1 - dis), then lp (nullable each)
-void launch_assemble_F_set(const float* set_sim, const float* weights, const float* dis, const float* lp, int K, int P, float* F, hipStream_t st);
+// F [P][n_obj].  The similarity columns: -sim (lp_lambda > 0: fmaf(lp_lambda, lp, -sim); anchor_lambda > 0: then fmaf(anchor_lambda, anchor, F0))
+// — or, with set_sim [P][K] and weights [K], the pareto layout: F[p][t] = w_t < 0 ? set_sim[p][t] : -set_sim[p][t].  Then relu(1 - dis), lp as
+// its own column (lp_lambda == 0), anchor as its own LAST column (anchor_lambda == 0); dis / lp / anchor nullable
+struct AssembleF {
+    const float* sim = nullptr;
+    const float *set_sim = nullptr, *weights = nullptr;
+    int K = 0;
+    const float *dis = nullptr, *lp = nullptr;
+    float lp_lambda = 0.f;
+    const float* anchor = nullptr;
+    float anchor_lambda = 0.f;
+    int P = 0, n_obj = 0;
+    float* F = nullptr;
+};
+// false: the columns do not add up to n_obj, or a fold with the pareto layout: nothing launched
+bool launch_assemble_F(const AssembleF& a, hipStream_t st);
 // --- image editing (edit.hip; include/glass.h "Image editing") ---
 #define GLASS_ANCHOR_MAX_LAYERS 64  // style layers of a latent anchor (2 * GLASS_MAX_BLOCKS = 24 at most in an engine)
-// launch_cosine_set's directional twin: the same arguments plus src [V][D], unit rows; every (row, view, entry) value is the cosine between
-// f / max(|f|, 1e-8) - src[v] and the entry.  One launch; false: a shape outside the limits (launch_cosine_set's), nothing launched
-bool launch_cosine_set_dir(const float* feat, const float* targets, const float* weights, float W, int P, int V, int T, int D, const float* src,
-                           float* view_sim, float* set_sim, float* sim, hipStream_t st);
-// the form that streams the set from memory, at any shape (launch_cosine_set_dir chooses it above 64 KB): the same bits
-bool launch_cosine_set_dir_streamed(const float* feat, const float* targets, const float* weights, float W, int P, int V, int T, int D,
-                                    const float* src, float* view_sim, float* set_sim, float* sim, hipStream_t st);
-// out[r] = feat[r] / max(|feat[r]|, 1e-8), n rows of D: the source rows, by the arithmetic the kernel above applies to a feature row
+// out[r] = feat[r] / max(|feat[r]|, 1e-8), n rows of D: the source rows, by the arithmetic the directional cosine applies to a feature row
 bool launch_unit_rows(const float* feat, int n, int D, float* out, hipStream_t st);
 // d[p] = mean over (l, i) of (w[p * cand_stride + l * layer_stride + i] - a[l * L + i])^2; layer_stride 0: one row for every layer.
 // false: n_lat outside [1, GLASS_ANCHOR_MAX_LAYERS], L outside [1, 65536], a layer stride inside (0, L): nothing launched
 bool launch_latent_anchor(const float* w, long long cand_stride, int layer_stride, const float* a, int n_lat, int L, int P, float* d, hipStream_t st);
-// F [P][n_obj] with the anchor distance: K <= 1: column 0 = -sim (lp_lambda > 0: fmaf(lp_lambda, lp, -sim); anchor_lambda > 0: then
-// fmaf(anchor_lambda, anchor, F0)); K >= 2: the pareto columns of set_sim [P][K] by the weights' signs; then relu(1 - dis), lp as its own column
-// (lp_lambda == 0), anchor as its own LAST column (anchor_lambda == 0); dis / lp nullable.  false: n_obj is not that count, or a fold with K >= 2
-bool launch_assemble_F_edit(const float* sim, const float* set_sim, const float* weights, int K, const float* dis, const float* lp, float lp_lambda,
-                            const float* anchor, float anchor_lambda, int P, int n_obj, float* F, hipStream_t st);
 
 // --- device search (search.hip; include/glass.h "Device search") ---
 #define GLASS_SEARCH_MAX_POP 1024      // population rows (2048 merged rows in survival)

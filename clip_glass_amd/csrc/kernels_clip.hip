@@ -1,17 +1,11 @@
 // kernels_clip.hip — CLIP ViT glue kernels: token assembly + ln_pre, LayerNorm,
-// multi-head attention (whole-sequence MFMA kernels for L <= 96: 50 visual tokens, 77 text tokens; a streaming one above that),
-// cosine similarity and objective assembly.  GEMMs live in conv_direct.hip / gemm_tiled.hip.
+// multi-head attention (whole-sequence MFMA kernels for L <= 96: 50 visual tokens, 77 text tokens; a streaming one above that).
+// GEMMs live in conv_direct.hip / gemm_tiled.hip; the cosine and the rows of F in score.hip.
 // Reference: clip/model.py:152-187 (LayerNorm, QuickGELU, ResidualAttentionBlock),
-// :218-235 (VisualTransformer.forward), generator.py:51 (cosine), problem.py:21-27.
+// :218-235 (VisualTransformer.forward).
 #include "common.h"
 #include "kernels.h"
 #include <stdlib.h>
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // One wave per row; two-pass mean/variance in fp32 (clip/model.py:152-158, eps 1e-5).  Rows up to 1024 wide are read from
 // global memory ONCE and held in registers (16 values per lane) for the three passes.
@@ -25,11 +19,11 @@ __device__ __forceinline__ void ln_row(LoadF load, int D, const float* g, const 
         float s = 0.f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) s += v[k];
-        const float mean = wsum(s) / (float)D;
+        const float mean = wave_sum(s) / (float)D;
         float q = 0.f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) { const float d = lane + 64 * k < D ? v[k] - mean : 0.f; q += d * d; }
-        const float rstd = rsqrtf(wsum(q) / (float)D + 1e-5f);
+        const float rstd = rsqrtf(wave_sum(q) / (float)D + 1e-5f);
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             const int i = lane + 64 * k;
@@ -43,10 +37,10 @@ __device__ __forceinline__ void ln_row(LoadF load, int D, const float* g, const 
     }
     float s = 0.f;
     for (int i = lane; i < D; i += 64) s += load(i);
-    const float mean = wsum(s) / (float)D;
+    const float mean = wave_sum(s) / (float)D;
     float q = 0.f;
     for (int i = lane; i < D; i += 64) { const float d = load(i) - mean; q += d * d; }
-    const float rstd = rsqrtf(wsum(q) / (float)D + 1e-5f);
+    const float rstd = rsqrtf(wave_sum(q) / (float)D + 1e-5f);
     for (int i = lane; i < D; i += 64) {
         const float v = (load(i) - mean) * rstd * g[i] + b[i];
         if (o16) o16[i] = (half_t)v;
@@ -411,59 +405,6 @@ void launch_attention(const half_t* qkv, int n_img, int L, int heads, int hd, in
     }
     const int nqb = (L + 127) / 128;     // any longer sequence: ViT-B/16 197 tokens, ViT-L/14 257, ViT-L/14@336 577
     hipLaunchKernelGGL(attention_stream_kernel, dim3((unsigned)((long long)n_img * heads * nqb)), dim3(256), 0, st, qkv, L, heads, causal, out);
-}
-
-// torch.cosine_similarity(feat[P,D], target[1,D]) (generator.py:51): x.y / max(|x||y|, 1e-8)
-__global__ void cosine_kernel(const float* feat, const float* target, int D, float* sim) {
-    const int p = blockIdx.x, lane = threadIdx.x;
-    float xy = 0.f, xx = 0.f, yy = 0.f;
-    for (int i = lane; i < D; i += 64) {
-        const float a = feat[(long long)p * D + i], b = target[i];
-        xy += a * b; xx += a * a; yy += b * b;
-    }
-    xy = wsum(xy); xx = wsum(xx); yy = wsum(yy);
-    if (lane == 0) sim[p] = xy / fmaxf(sqrtf(xx) * sqrtf(yy), 1e-8f);
-}
-void launch_cosine(const float* feat, const float* target, int P, int D, float* sim, hipStream_t st) {
-    hipLaunchKernelGGL(cosine_kernel, dim3(P), dim3(64), 0, st, feat, target, D, sim);
-}
-
-// crop views: one wave per candidate walks its V feature rows; each cosine is cosine_kernel's, their mean is summed in the order v = 0 .. V - 1
-__global__ void cosine_views_kernel(const float* feat, const float* target, int V, int D, float* view_sim, float* sim) {
-    const int p = blockIdx.x, lane = threadIdx.x;
-    float acc = 0.f;
-    for (int v = 0; v < V; ++v) {
-        const long long r = (long long)p * V + v;
-        float xy = 0.f, xx = 0.f, yy = 0.f;
-        for (int i = lane; i < D; i += 64) {
-            const float a = feat[r * D + i], b = target[i];
-            xy += a * b; xx += a * a; yy += b * b;
-        }
-        xy = wsum(xy); xx = wsum(xx); yy = wsum(yy);
-        const float c = xy / fmaxf(sqrtf(xx) * sqrtf(yy), 1e-8f);
-        if (lane == 0) view_sim[r] = c;
-        acc += c;
-    }
-    if (lane == 0) sim[p] = acc / (float)V;
-}
-void launch_cosine_views(const float* feat, const float* target, int P, int V, int D, float* view_sim, float* sim, hipStream_t st) {
-    hipLaunchKernelGGL(cosine_views_kernel, dim3(P), dim3(64), 0, st, feat, target, V, D, view_sim, sim);
-}
-
-// problem.py:23-27: F = column_stack(-sim, relu(1 - dis)) or F = -sim
-// lp (nullable): the perceptual distance — lambda == 0: the last column; lambda > 0: folded into column 0
-__global__ void assemble_F_kernel(const float* sim, const float* dis, const float* lp, float lambda, int has_d, int P, int n_obj, float* F) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    F[(long long)p * n_obj] = (lp && lambda > 0.f) ? fmaf(lambda, lp[p], -sim[p]) : -sim[p];
-    if (has_d) F[(long long)p * n_obj + 1] = fmaxf(1.f - dis[p], 0.f);
-    if (lp && !(lambda > 0.f)) F[(long long)p * n_obj + n_obj - 1] = lp[p];
-}
-void launch_assemble_F(const float* sim, const float* dis, int P, int n_obj, float* F, hipStream_t st) {
-    hipLaunchKernelGGL(assemble_F_kernel, dim3((P + 63) / 64), dim3(64), 0, st, sim, dis, (const float*)nullptr, 0.f, n_obj == 2 ? 1 : 0, P, n_obj, F);
-}
-void launch_assemble_F_lpips(const float* sim, const float* dis, const float* lp, float lambda, int has_d, int P, int n_obj, float* F, hipStream_t st) {
-    hipLaunchKernelGGL(assemble_F_kernel, dim3((P + 63) / 64), dim3(64), 0, st, sim, dis, lp, lambda, has_d, P, n_obj, F);
 }
 
 // images already resized / normalised by the caller (clip.py:68-74 preprocess) -> patch-embedding operand

@@ -9,17 +9,6 @@
 
 #include <algorithm>
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 // ---- mapping network input normalisation: stylegan2/models.py:625-626 --------------
 __global__ void pixelnorm_kernel(const float* z, float* out, int L, float eps) {
     const int p = blockIdx.x, lane = threadIdx.x;

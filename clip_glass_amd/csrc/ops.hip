@@ -1081,32 +1081,48 @@ extern "C" int glass_op_layernorm_rows(int32_t device, int32_t n_rows, int32_t M
     return st.fetch(out, dout);
 }
 
+// The five cosine ops: the operands staged, the one launcher (score.hip), the outputs the caller asked for.  weights: [T], or with islands > 0 the
+// table [islands, T]; src (nullable): the directional form; refusal: the text of the launcher's `false`
+static int cosine_op(int device, int P, int V, int T, int D, const float* feat, const float* targets, const float* weights, int islands, int pop,
+                     int row0, const float* src, bool streamed, const char* refusal, float* view_sim, float* set_sim, float* sim) {
+    std::vector<float> W(std::max(islands, 1));
+    for (size_t i = 0; i < W.size(); ++i) W[i] = prompt_weight_sum(weights + i * T, T);
+    Stage st(device);
+    CosineSet a;
+    a.feat = st.in32(feat, (size_t)P * V * D), a.targets = st.in32(targets, (size_t)T * D), a.src = st.in32(src, (size_t)V * D);
+    const auto dw = st.in32(weights, W.size() * T);
+    if (islands > 0) a.isl.weights = dw, a.isl.W = st.in32(W.data(), islands), a.isl.pop = pop, a.isl.row0 = row0;
+    else a.weights = dw, a.W = W[0];
+    a.P = P, a.V = V, a.T = T, a.D = D, a.streamed = streamed;
+    const auto dvs = st.poisoned<float>((size_t)P * V), dss = st.poisoned<float>((size_t)P * T), ds = st.poisoned<float>(P);
+    a.view_sim = dvs, a.set_sim = dss, a.sim = ds;
+    TRY(st.run([&] { return accepted(launch_cosine_set(a, 0), refusal); }));
+    if (view_sim) TRY(st.fetch(view_sim, dvs));
+    if (set_sim) TRY(st.fetch(set_sim, dss));
+    return st.fetch(sim, ds);
+}
+static const float ONE_WEIGHT[1] = {1.f};      // a single target is the set of one entry of weight 1
+
 extern "C" int glass_op_cosine(int32_t device, int32_t P, int32_t D, const float* feat, const float* target, float* sim) {
     OPREQ(feat && target && sim && P > 0 && D > 0, "bad argument");
-    Stage st(device);
-    const auto df = st.in32(feat, (size_t)P * D), dt = st.in32(target, D);
-    const auto ds = st.poisoned<float>(P);
-    TRY(st.run([&] { launch_cosine(df, dt, P, D, ds, 0); }));
-    return st.fetch(sim, ds);
+    return cosine_op(device, P, 1, 1, D, feat, target, ONE_WEIGHT, 0, 0, 0, nullptr, false, "cosine_set refused the shape", nullptr, nullptr, sim);
 }
 
 extern "C" int glass_op_cosine_views(int32_t device, int32_t P, int32_t V, int32_t D, const float* feat, const float* target, float* view_sim,
                                      float* sim) {
     OPREQ(feat && target && view_sim && sim && P > 0 && V > 0 && D > 0, "bad argument");
-    Stage st(device);
-    const auto df = st.in32(feat, (size_t)P * V * D), dt = st.in32(target, D);
-    const auto dvs = st.poisoned<float>((size_t)P * V), ds = st.poisoned<float>(P);
-    TRY(st.run([&] { launch_cosine_views(df, dt, P, V, D, dvs, ds, 0); }));
-    TRY(st.fetch(view_sim, dvs));
-    return st.fetch(sim, ds);
+    OPREQ(V <= GLASS_PROMPT_MAX_VIEWS, "cosine_set: V and T must be in [1, 16]");
+    return cosine_op(device, P, V, 1, D, feat, target, ONE_WEIGHT, 0, 0, 0, nullptr, false, "cosine_set refused the shape", view_sim, nullptr, sim);
 }
 
 extern "C" int glass_op_assemble_F(int32_t device, int32_t P, int32_t n_obj, const float* sim, const float* dis, float* F) {
     OPREQ(sim && F && P > 0 && (n_obj == 1 || (n_obj == 2 && dis)), "bad argument (n_obj 1, or 2 with dis)");
     Stage st(device);
-    const auto ds = st.in32(sim, P), dd = st.in32(dis, P);
+    AssembleF a;
+    a.sim = st.in32(sim, P), a.dis = n_obj == 2 ? st.in32(dis, P) : Buf<float>(), a.P = P, a.n_obj = n_obj;
     const auto dF = st.poisoned<float>((size_t)P * n_obj, 4);
-    TRY(st.run([&] { launch_assemble_F(ds, dd, P, n_obj, dF, 0); }));
+    a.F = dF;
+    TRY(st.run([&] { return accepted(launch_assemble_F(a, 0), "assemble_F refused the layout"); }));
     TRY(st.intact(dF, "assemble_F stored past row P"));
     return st.fetch(F, dF);
 }
@@ -1115,34 +1131,17 @@ extern "C" int glass_op_cosine_set(int32_t device, int32_t P, int32_t V, int32_t
                                    const float* weights, float* view_sim, float* set_sim, float* sim) {
     OPREQ(feat && targets && weights && view_sim && set_sim && sim && P > 0 && D > 0, "bad argument");
     OPREQ(V >= 1 && V <= GLASS_PROMPT_MAX_VIEWS && T >= 1 && T <= GLASS_PROMPT_MAX, "cosine_set: V and T must be in [1, 16]");
-    Stage st(device);
-    const auto df = st.in32(feat, (size_t)P * V * D), dt = st.in32(targets, (size_t)T * D), dw = st.in32(weights, T);
-    const auto dvs = st.poisoned<float>((size_t)P * V), dss = st.poisoned<float>((size_t)P * T), ds = st.poisoned<float>(P);
-    TRY(st.run([&] { return accepted(launch_cosine_set(df, dt, dw, prompt_weight_sum(weights, T), P, V, T, D, dvs, dss, ds, 0), "cosine_set refused the shape"); }));
-    TRY(st.fetch(view_sim, dvs));
-    TRY(st.fetch(set_sim, dss));
-    return st.fetch(sim, ds);
+    return cosine_op(device, P, V, T, D, feat, targets, weights, 0, 0, 0, nullptr, false, "cosine_set refused the shape", view_sim, set_sim, sim);
 }
 
-// launch_cosine_set with an island table: row p takes row (row0 + p) / pop of weights [islands, T] (include/glass.h "Device search: islands")
+// the cosine with an island table: row p takes row (row0 + p) / pop of weights [islands, T] (include/glass.h "Device search: islands")
 extern "C" int glass_op_cosine_set_islands(int32_t device, int32_t P, int32_t V, int32_t T, int32_t D, const float* feat, const float* targets,
                                            const float* weights, int32_t islands, int32_t pop, int32_t row0, float* view_sim, float* set_sim, float* sim) {
     OPREQ(feat && targets && weights && view_sim && set_sim && sim && P > 0 && D > 0, "bad argument");
     OPREQ(V >= 1 && V <= GLASS_PROMPT_MAX_VIEWS && T >= 1 && T <= GLASS_PROMPT_MAX, "cosine_set: V and T must be in [1, 16]");
     OPREQ(islands >= 1 && islands <= GLASS_SEARCH_MAX_ISLANDS && pop >= 1 && row0 >= 0 && (long long)row0 + P <= (long long)islands * pop,
           "cosine_set_islands: rows [row0, row0 + P) must lie inside the islands * pop rows, islands in [1, 64]");
-    std::vector<float> W(islands);
-    for (int i = 0; i < islands; ++i) W[i] = prompt_weight_sum(weights + (size_t)i * T, T);
-    Stage st(device);
-    const auto df = st.in32(feat, (size_t)P * V * D), dt = st.in32(targets, (size_t)T * D), dw = st.in32(weights, (size_t)islands * T);
-    const auto dW = st.in32(W.data(), islands);
-    const auto dvs = st.poisoned<float>((size_t)P * V), dss = st.poisoned<float>((size_t)P * T), ds = st.poisoned<float>(P);
-    CosineIslands isl;
-    isl.weights = dw; isl.W = dW; isl.pop = pop; isl.row0 = row0;
-    TRY(st.run([&] { return accepted(launch_cosine_set(df, dt, nullptr, 0.f, P, V, T, D, dvs, dss, ds, 0, isl), "cosine_set refused the shape"); }));
-    TRY(st.fetch(view_sim, dvs));
-    TRY(st.fetch(set_sim, dss));
-    return st.fetch(sim, ds);
+    return cosine_op(device, P, V, T, D, feat, targets, weights, islands, pop, row0, nullptr, false, "cosine_set refused the shape", view_sim, set_sim, sim);
 }
 
 extern "C" int glass_op_assemble_F_set(int32_t device, int32_t P, int32_t K, const float* set_sim, const float* weights, const float* dis,
@@ -1150,9 +1149,12 @@ extern "C" int glass_op_assemble_F_set(int32_t device, int32_t P, int32_t K, con
     OPREQ(set_sim && weights && F && P > 0 && K >= 1 && K <= GLASS_PROMPT_MAX, "bad argument (K in [1, 16])");
     Stage st(device);
     const int n_obj = K + (dis ? 1 : 0) + (lp ? 1 : 0);
-    const auto dss = st.in32(set_sim, (size_t)P * K), dw = st.in32(weights, K), dd = st.in32(dis, P), dl = st.in32(lp, P);
+    AssembleF a;
+    a.set_sim = st.in32(set_sim, (size_t)P * K), a.weights = st.in32(weights, K), a.K = K, a.dis = st.in32(dis, P), a.lp = st.in32(lp, P);
+    a.P = P, a.n_obj = n_obj;
     const auto dF = st.poisoned<float>((size_t)P * n_obj, 4);
-    TRY(st.run([&] { launch_assemble_F_set(dss, dw, dd, dl, K, P, dF, 0); }));
+    a.F = dF;
+    TRY(st.run([&] { return accepted(launch_assemble_F(a, 0), "assemble_F_set refused the layout"); }));
     TRY(st.intact(dF, "assemble_F_set stored past row P"));
     return st.fetch(F, dF);
 }
@@ -1161,18 +1163,8 @@ extern "C" int glass_op_cosine_set_dir(int32_t device, int32_t P, int32_t V, int
                                        const float* weights, const float* src, int32_t streamed, float* view_sim, float* set_sim, float* sim) {
     OPREQ(feat && targets && weights && src && view_sim && set_sim && sim && P > 0 && V > 0 && T > 0 && D > 0, "bad argument");
     OPREQ((int64_t)P * V * D < (1LL << 31) && (int64_t)T * D < (1LL << 31), "cosine_set_dir: operand too large");
-    Stage st(device);
-    const auto df = st.in32(feat, (size_t)P * V * D), dt = st.in32(targets, (size_t)T * D), dw = st.in32(weights, T), dsrc = st.in32(src, (size_t)V * D);
-    const auto dvs = st.poisoned<float>((size_t)P * V), dss = st.poisoned<float>((size_t)P * T), ds = st.poisoned<float>(P);
-    TRY(st.run([&] {
-        const float W = prompt_weight_sum(weights, T);
-        return accepted(streamed ? launch_cosine_set_dir_streamed(df, dt, dw, W, P, V, T, D, dsrc, dvs, dss, ds, 0)
-                                 : launch_cosine_set_dir(df, dt, dw, W, P, V, T, D, dsrc, dvs, dss, ds, 0),
-                        "cosine_set_dir refused the shape (V and T must be in [1, 16])");
-    }));
-    TRY(st.fetch(view_sim, dvs));
-    TRY(st.fetch(set_sim, dss));
-    return st.fetch(sim, ds);
+    return cosine_op(device, P, V, T, D, feat, targets, weights, 0, 0, 0, src, streamed != 0, "cosine_set_dir refused the shape (V and T must be in [1, 16])",
+                     view_sim, set_sim, sim);
 }
 
 extern "C" int glass_op_latent_anchor(int32_t device, int32_t P, int32_t n_lat, int32_t L, int32_t layered, const float* w, const float* a, float* d) {

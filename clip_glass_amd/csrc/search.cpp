@@ -164,7 +164,7 @@ extern "C" int glass_engine_set_island_weights(glass_engine* e, const float* w, 
     REQUIRE(s.islands >= 1, GLASS_ERR_STATE, "set_island_weights: this search has no islands (glass_engine_set_search_islands before finalize)");
     REQUIRE(islands == s.islands, GLASS_ERR_ARG,
             "set_island_weights: the table has " + std::to_string(islands) + " rows and the search " + std::to_string(s.islands) + " islands");
-    REQUIRE(ps.T > 0, GLASS_ERR_STATE, "set_island_weights: set_targets() first (the islands' prompts are the entries of a prompt set)");
+    REQUIRE(ps.given(), GLASS_ERR_STATE, "set_island_weights: set_targets() first (the islands' prompts are the entries of a prompt set)");
     REQUIRE(T == ps.T, GLASS_ERR_ARG,
             "set_island_weights: the table has " + std::to_string(T) + " columns and the prompt set " + std::to_string(ps.T) + " entries");
     REQUIRE(ps.mode == 0, GLASS_ERR_STATE,
@@ -282,7 +282,7 @@ void launch_migrate(glass_engine* e) {
 int search_pass(glass_engine* e, int P, int generation, int first_row, const float* d_rows, float* d_F, bool no_wait) {
     const glass_engine::Search& s = e->search;
     if (s.own_prompts)
-        REQUIRE(e->pset.T == e->pset.isl_T && e->pset.mode == 0 && !e->edit.has_source, GLASS_ERR_STATE,
+        REQUIRE(e->pset.given() && e->pset.T == e->pset.isl_T && e->pset.mode == 0 && !e->edit.has_source, GLASS_ERR_STATE,
                 "device search islands: the islands' own weights were set for a prompt set of " + std::to_string(e->pset.isl_T) +
                     " entries in mode sum without a direction source, and the engine's targets have changed: set_island_weights again");
     e->noise_period = s.islands ? s.g.pop / e->cfg.batch_size : 0;

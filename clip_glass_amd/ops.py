@@ -933,7 +933,7 @@ def assemble_F_set(set_sim, weights, dis=None, lp=None, device=0):
 
 
 def cosine_set_dir(feat, targets, weights, src, streamed=False, device=0):
-    """feat [P, V, D], targets [T, D], weights [T], src [V, D] (unit rows) -> (view_sim [P, V], set_sim [P, T], sim [P]): cosine_set_dir_kernel
+    """feat [P, V, D], targets [T, D], weights [T], src [V, D] (unit rows) -> (view_sim [P, V], set_sim [P, T], sim [P]): cosine_set_kernel's directional form
     (image editing), the cosine of f / |f| - src[v] with every entry.  streamed: the form that reads the set from memory at any shape."""
     lib = _lib()
     feat, targets, weights, src = _f32(feat), _f32(targets), _f32(weights), _f32(src)

@@ -232,10 +232,11 @@ int glass_op_rn_tokens(int32_t device, int32_t B, int32_t HW, int32_t C, const f
  * glass_op_layernorm_ex: launch_layernorm on rows row_stride apart (x holds (M - 1) row_stride + D floats); half_out: the fp16 output.
  * glass_op_layernorm_rows: out[m] = LN(x[rows[m]]), x [n_rows,D].
  * glass_op_cosine_views: feat [P,V,D] -> view_sim [P,V], sim [P].
- * glass_op_cosine_set: launch_cosine_set (prompt sets, include/glass.h): feat [P,V,D], targets [T,D], weights [T] (W = their ordered sum of
+ * glass_op_cosine_set: launch_cosine_set (csrc/score.hip — the one cosine launcher, which glass_op_cosine and glass_op_cosine_views reach with
+ *   T = 1 and weight 1, so V <= 16 there too; prompt sets, include/glass.h): feat [P,V,D], targets [T,D], weights [T] (W = their ordered sum of
  *   magnitudes, taken inside) -> view_sim [P,V] (entry 0's cosines), set_sim [P,T], sim [P].  V, T in [1, 16].
  * glass_op_assemble_F_set: the pareto layout: set_sim [P,K], weights [K], dis / lp [P] (nullable each) -> F [P, K + (dis != 0) + (lp != 0)].
- * glass_op_cosine_set_dir: launch_cosine_set_dir (image editing, include/glass.h): glass_op_cosine_set's operands plus src [V,D] (unit rows) ->
+ * glass_op_cosine_set_dir: launch_cosine_set with a direction source (image editing, include/glass.h): glass_op_cosine_set's operands plus src [V,D] (unit rows) ->
  *   the same three outputs for x = f / max(|f|, 1e-8) - src[v] in f's place.  streamed 1: the form that streams the set from memory, at any
  *   shape (the launcher chooses it above 64 KB).  A shape the launcher does not take (V or T above 16) is refused by name, nothing launched.
  * glass_op_latent_anchor: launch_latent_anchor: w [P,n_lat,L] (layered 1) or [P,L] (layered 0: the one row serves every layer), a [n_lat,L] ->

@@ -1,4 +1,4 @@
-"""Float64 restatements of the prompt-set kernels (csrc/prompt_set.hip; include/glass.h "Prompt sets"), each with its float32 twin
+"""Float64 restatements of the prompt-set kernels (csrc/score.hip; include/glass.h "Prompt sets"), each with its float32 twin
 (test infrastructure).  Built on small_ops_ref.cosine / seq_sum: a column of a set is that file's cosine against the entry, the mean over
 the views its cosine_views, so tests/test_small_ops_ref.py's pins (torch.cosine_similarity, the oracle's fitness) carry over.
 tests/test_prompt_set_ref.py pins what is new here — the weighted combination and the sign rule."""

@@ -1,4 +1,4 @@
-"""cosine_set_dir_kernel and latent_anchor_kernel (csrc/edit.hip) in isolation, through the diagnostic ops.
+"""The directional form of cosine_set_kernel (csrc/score.hip) and latent_anchor_kernel (csrc/edit.hip) in isolation, through the diagnostic ops.
 
 Against float64 (tests/edit_ref.py): the project's general bar — |got - ref64| <= 4 * max|ref32 - ref64| on the same inputs, one spacing of
 max|ref| where the float32 twin is exact.  tests/test_edit_ref.py shows that the bar bites at these inputs.  The twin is written in the
@@ -8,7 +8,8 @@ Directional cosine: D = 32, 100, 512, 1024; T = 1, 4, 5 (a ragged last group of 
 D = 1040, whose set exceeds 64 KB and streams from memory.  Inputs are independent normal rows, |x| of order 1.  The near-source regime is
 checked by properties only: a feature row that is an exact positive power-of-two multiple of its (exactly unit-length) source row gives
 exactly 0.  Bit-equalities: a row moved to another position and another P; T = 1 against the first column of T = 16; the staged against the
-streamed form at a D both accept.  Shapes outside the limits come back as the launcher's refusal.
+streamed form at a D both accept; every case of the D / T / V / P grid, staged and streamed, against what cosine_set_dir_kernel of the commit
+before score.hip returned (tests/score_tail_golden.py).  Shapes outside the limits come back as the launcher's refusal.
 
 Latent anchor: L = 64, 512; n_lat = 1, 4, 18; the [P, n_lat, L] form and the one-row-for-every-layer form; exact 0 for w = a; bit-equality
 across positions.
@@ -23,6 +24,7 @@ import numpy as np
 import pytest
 
 import edit_ref as E
+from score_tail_golden import golden, pack
 from util import diag
 
 pytestmark = [pytest.mark.gpu,
@@ -71,12 +73,21 @@ def _check_dir(ops, tag, feat, targets, weights, src):
     return vs, ss, sim
 
 
-@pytest.mark.parametrize("D", [32, 100, 512, 1024])
-@pytest.mark.parametrize("T", [1, 4, 5, 16])
+DIR_D, DIR_T, DIR_V, DIR_P = [32, 100, 512, 1024], [1, 4, 5, 16], (1, 3, 16), (1, 5)
+
+
+@pytest.mark.parametrize("D", DIR_D)
+@pytest.mark.parametrize("T", DIR_T)
 def test_cosine_set_dir(ops, D, T):
-    for V in (1, 3, 16):
-        for P in (1, 5):
-            _check_dir(ops, "D%d T%d V%d P%d" % (D, T, V, P), *E.dir_inputs(P, V, T, D))
+    got = {False: [], True: []}
+    for V in DIR_V:
+        for P in DIR_P:
+            case = E.dir_inputs(P, V, T, D)
+            got[False] += _check_dir(ops, "D%d T%d V%d P%d" % (D, T, V, P), *case)
+            got[True] += ops.cosine_set_dir(*case, streamed=True)
+    for streamed in (False, True):
+        _bit_equal("D%d T%d %s == the parent's cosine_set_dir_kernel" % (D, T, "streamed" if streamed else "staged"), pack(*got[streamed]),
+                   golden("cosine_set_dir_D%d_T%d" % (D, T)))
 
 
 def test_a_set_beyond_the_staging_limit_streams_from_memory(ops):

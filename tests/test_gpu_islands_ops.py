@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import search_islands_ref as IR
+from score_tail_golden import golden, pack
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(bool(os.environ.get("GLASS_EMULATE")), reason="launches the library's own kernels: no emulated form")]
@@ -69,16 +70,28 @@ def test_noise_period(ops):
     assert np.array_equal(ops.noise_period(4, hw, layer, 0, gen, seed, 0).view(np.uint32), plain.view(np.uint32))
 
 
-@pytest.mark.parametrize("V", [1, 3])
-def test_island_cosine(ops, V):
-    """Every island's rows equal glass_op_cosine_set on those rows with the island's own weights, by value; an island with a single weight of 1
-    equals the set that holds that entry alone; a launch that starts inside the table (row0 > 0) finds its islands."""
+ISLAND_V = [1, 3]
+
+
+def _island_cosine_case(V):
     K, pop, T, D = 3, 4, 3, 70
     rng = np.random.default_rng(V)
     feat = rng.standard_normal((K * pop, V, D)).astype(np.float32)
     targets = rng.standard_normal((T, D)).astype(np.float32)
     table = np.array([[1, 0, 0], [0, 0, 1], [0.5, -2, 0.25]], np.float32)
+    return feat, targets, table, pop
+
+
+@pytest.mark.parametrize("V", ISLAND_V)
+def test_island_cosine(ops, V):
+    """Every island's rows equal glass_op_cosine_set on those rows with the island's own weights, by value; an island with a single weight of 1
+    equals the set that holds that entry alone; a launch that starts inside the table (row0 > 0) finds its islands; the whole launch has the
+    bits of the commit before csrc/score.hip (tests/score_tail_golden.py)."""
+    feat, targets, table, pop = _island_cosine_case(V)
+    K = table.shape[0]
     vs, ss, sim = ops.cosine_set_islands(feat, targets, table, pop)
+    got, want = pack(vs, ss, sim), golden("island_cosine_V%d" % V)
+    assert got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
     assert np.isfinite(sim).all() and (sim != sim[0]).any()
     for i in range(K):
         rows = slice(i * pop, (i + 1) * pop)

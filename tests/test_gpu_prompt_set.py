@@ -214,7 +214,7 @@ def test_encode_generated_of_a_candidates_image_scores_one(preprocess):
 # ---- (g) the profile of the pass ----------------------------------------------------------------------------------------------------
 def test_profile_rows_default_and_with_a_set():
     """The default engine's pass: row for row the pinned table of tests/test_gpu_engine.py::test_launch_table_is_pinned.  With a set active: the
-    same rows and launches — the set's cosine runs inside clip.head in the single cosine's place, assemble_F_set in assemble_F's."""
+    same rows and launches — the one cosine kernel inside clip.head and the one assemble_F kernel (csrc/score.hip) end both."""
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_table.json")) as f:
         golden = json.load(f)["mid"]
     c = M.CONFIGS["mid"]

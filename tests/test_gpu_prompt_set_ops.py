@@ -1,8 +1,11 @@
-"""cosine_set_kernel and assemble_F_set_kernel (csrc/prompt_set.hip) in isolation, through the diagnostic ops.
+"""cosine_set_kernel and assemble_F_kernel's pareto layout (csrc/score.hip) in isolation, through the diagnostic ops.
 
-Bit-equalities (the contract of include/glass.h "Prompt sets"): column t of a set is cosine_views_kernel's answer for entry t alone; one entry
-of weight 1 is cosine_kernel / cosine_views_kernel; `sim` is the numpy float32 recombination of the kernel's own columns (product and sum
+Bit-equalities (the contract of include/glass.h "Prompt sets"): column t of a set is the cosine_views op's answer for entry t alone; one entry
+of weight 1 is the cosine / cosine_views op; `sim` is the numpy float32 recombination of the kernel's own columns (product and sum
 rounded separately, divided by the ordered sum of |w|); a row's bits do not depend on the launch it is in; assemble_F_set is its float32 twin.
+The cosine ops are one kernel now, so the equalities between them compare it with itself at T = 1: every case is also compared with what the
+separate kernels of the commit before score.hip returned (tests/score_tail_golden.py), and so are two shapes that only the directional tests
+had: T = 5 without views (a ragged last accumulator group) and V = T = 16 (c[v][t] full).
 
 Against float64 (tests/prompt_set_ref.py): the general bar of tests/test_gpu_small_ops.py — |got - ref64| <= 4 * max|ref32 - ref64| on the
 same inputs, one ulp of max|ref| where the float32 twin is exact.
@@ -21,6 +24,7 @@ import numpy as np
 import pytest
 
 import prompt_set_ref as PR
+from score_tail_golden import golden, pack
 from util import diag
 
 pytestmark = [pytest.mark.gpu,
@@ -83,14 +87,20 @@ def _recombine(set_sim, weights):
     return (acc / W).astype(F32)
 
 
-@pytest.mark.parametrize("D", [100, 512, 640])
-@pytest.mark.parametrize("V", [1, 3])
-@pytest.mark.parametrize("T", [1, 2, 16])
+SET_D, SET_V, SET_T = [100, 512, 640], [1, 3], [1, 2, 16]
+STREAMED = (2, 2, 16, 1088)                                 # P, V, T, D
+EDGES = [(5, 1, 5, 100), (1, 16, 16, 64)]                   # a ragged last accumulator group without views; c[v][t] full
+
+
+@pytest.mark.parametrize("D", SET_D)
+@pytest.mark.parametrize("V", SET_V)
+@pytest.mark.parametrize("T", SET_T)
 def test_cosine_set(ops, D, V, T):
     tag = "D%d V%d T%d" % (D, V, T)
     feat, targets, weights = _inputs(P, V, T, D)
     vs, ss, sim = ops.cosine_set(feat, targets, weights)
     assert vs.shape == (P, V) and ss.shape == (P, T) and sim.shape == (P,)
+    _bit_equal("%s == the parent's cosine_set_kernel" % tag, pack(vs, ss, sim), golden("cosine_set_P%d_V%d_T%d_D%d" % (P, V, T, D)))
     for t in range(T):
         vt, mt = ops.cosine_views(feat, targets[t])
         _bit_equal("%s column %d == cosine_views" % (tag, t), ss[:, t], mt)
@@ -132,24 +142,48 @@ def test_a_row_does_not_depend_on_its_launch(ops, V, T, D):
 
 def test_targets_beyond_the_staging_limit_stream_from_memory(ops):
     """T * D * 4 bytes > 64 KB: the kernel's other path, the same bits per column."""
-    feat, targets, weights = _inputs(2, 2, 16, 1088)
+    feat, targets, weights = _inputs(*STREAMED)
     vs, ss, sim = ops.cosine_set(feat, targets, weights)
+    _bit_equal("streamed == the parent's cosine_set_kernel", pack(vs, ss, sim), golden("cosine_set_P%d_V%d_T%d_D%d" % STREAMED))
     for t in (0, 7, 15):
         _bit_equal("streamed column %d == cosine_views" % t, ss[:, t], ops.cosine_views(feat, targets[t])[1])
     _bit_equal("streamed sim == recombination", sim, _recombine(ss, weights))
 
 
-@pytest.mark.parametrize("Pn", [1, 65])
-@pytest.mark.parametrize("K", [2, 4])
-@pytest.mark.parametrize("has_d,has_lp", [(False, False), (True, False), (False, True), (True, True)])
-def test_assemble_F_set(ops, Pn, K, has_d, has_lp):
+@pytest.mark.parametrize("Pn,V,T,D", EDGES)
+def test_shapes_that_only_the_directional_tests_had(ops, Pn, V, T, D):
+    tag = "P%d V%d T%d D%d" % (Pn, V, T, D)
+    feat, targets, weights = _inputs(Pn, V, T, D)
+    vs, ss, sim = ops.cosine_set(feat, targets, weights)
+    _bit_equal("%s == the parent's cosine_set_kernel" % tag, pack(vs, ss, sim), golden("cosine_set_P%d_V%d_T%d_D%d" % (Pn, V, T, D)))
+    _bit_equal("%s sim == float32 recombination of the columns" % tag, sim, _recombine(ss, weights))
+    r64, r32 = PR.cosine_set(feat, targets, weights), PR.cosine_set(feat, targets, weights, dt=F32)
+    _bar("%s columns" % tag, ss, r64[1], r32[1])
+    _bar("%s entry 0 per view" % tag, vs, r64[0], r32[0])
+    _bar("%s sim" % tag, sim, r64[2], r32[2])
+
+
+F_SET_P, F_SET_K, F_SET_COLS = [1, 65], [2, 4], [(False, False), (True, False), (False, True), (True, True)]
+
+
+def _assemble_F_set_case(Pn, K, has_d, has_lp):
     rng = np.random.default_rng(3 + Pn + K)
     c = rng.uniform(-1, 1, (Pn, K)).astype(F32)
     w = np.array([2.0, -0.5, 1e-3, -40.0], F32)[:K]
     dis = rng.uniform(-2, 3, Pn).astype(F32) if has_d else None      # both sides of the hinge
     lp = rng.uniform(0, 1, Pn).astype(F32) if has_lp else None
+    return c, w, dis, lp
+
+
+@pytest.mark.parametrize("Pn", F_SET_P)
+@pytest.mark.parametrize("K", F_SET_K)
+@pytest.mark.parametrize("has_d,has_lp", F_SET_COLS)
+def test_assemble_F_set(ops, Pn, K, has_d, has_lp):
+    c, w, dis, lp = _assemble_F_set_case(Pn, K, has_d, has_lp)
     got = ops.assemble_F_set(c, w, dis, lp)
     assert got.shape == (Pn, K + has_d + has_lp)
+    _bit_equal("assemble_F_set P%d K%d d%d lp%d == the parent's" % (Pn, K, has_d, has_lp), pack(got),
+               golden("assemble_F_set_P%d_K%d_d%d_lp%d" % (Pn, K, has_d, has_lp)))
     _bit_equal("assemble_F_set P%d K%d d%d lp%d" % (Pn, K, has_d, has_lp), got, PR.assemble_F_set(c, w, dis, lp, dt=F32))
     assert (np.sign(got[:, 1]) == np.sign(c[:, 1])).all() and (np.sign(got[:, 0]) == -np.sign(c[:, 0])).all()
 

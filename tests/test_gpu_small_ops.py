@@ -10,8 +10,8 @@ Kernel instances reached (the launchers' own rules, csrc/kernels_misc.hip, kerne
   dense_multi_kernel (4 problems, early-return workgroups, N = 8, K = 136), style_norm_kernel, gemm_tiled_kernel<64> / <128> in its `ld` / `batch`
   split-K form + dense01_finish_kernel, gemm_direct + dense_kernel (the unsplit D head), mbstd_kernel (C = 12), mbstd_vec_kernel (groups 2,
   4, 8; C = 512), finalize_image_kernel, embed_lnpre_kernel, embed_text_kernel, layernorm_kernel (register branch up to D = 1024, streaming
-  branch above; row_stride 3 D; fp16 output), layernorm_rows_kernel, cosine_kernel, cosine_views_kernel, assemble_F_kernel,
-  image_patches_kernel, rn_token0_rows_kernel.
+  branch above; row_stride 3 D; fp16 output), layernorm_rows_kernel, cosine_set_kernel at T = 1 (csrc/score.hip: the cosine and cosine_views ops),
+  assemble_F_kernel (score.hip), image_patches_kernel, rn_token0_rows_kernel.
 
 The D head's split form.  run_d_head takes it where 16 CL is a multiple of 1024 AND gemm_tiled takes the slices, and gemm_tiled refuses
 fewer than 64 rows: at P = 8 and P = 5 every CL runs the unsplit form (gemm_direct + dense_kernel), as in the engine.  The cases P = 8 / 5
@@ -24,8 +24,9 @@ Bars (none is taken from the device).
   * mapping: 4 x the error of oracle.g_mapping in torch fp32 against float64, the rule of test_map_latents_matches_float64.
   * D head: the general rule, reference and twin on the fp16-rounded operands.
   * Bit-equality: embed_text (one float32 add), assemble_F, finalize_image, image_patches (numpy's float16 rounding), rn_token0_rows, style_norm's
-    smax, the fp16 LayerNorm output against float16(the fp32 output), cosine_views' per-view values against cosine_kernel's and its mean
-    against their float32 sum in the order v = 0 .. V - 1, layernorm_rows against layernorm_kernel on the gathered rows.
+    smax, the fp16 LayerNorm output against float16(the fp32 output), cosine_views' per-view values against the cosine op's and its mean
+    against their float32 sum in the order v = 0 .. V - 1, layernorm_rows against layernorm_kernel on the gathered rows; cosine, cosine_views
+    and assemble_F against what the separate kernels of the commit before csrc/score.hip returned (tests/score_tail_golden.py).
   * Position independence: a row's bits in launches of P = 5, 16, 19 at positions 0, 3, 15, 18 equal its bits in a launch of P = 1.
 
 Measured on an MI355X (max abs error against float64 / the bar, absolute unless stated; every figure is also logged through util.diag):
@@ -61,6 +62,7 @@ import pytest
 import torch
 
 import small_ops_ref as R
+from score_tail_golden import golden, pack
 from clip_glass_amd import synth
 from oracle import stylegan2_ref as sg
 from util import diag
@@ -356,22 +358,47 @@ def test_embed_text():
     _bit_equal("embed_text", ops.embed_text(tokens, tok_emb, pos), R.embed_text(tokens, tok_emb, pos, dt=F32))
 
 
-@pytest.mark.parametrize("D", [512, 100, 640])
-def test_cosine(D):
+COSINE_D, COSINE_VIEWS_V, ASSEMBLE_F_P = [512, 100, 640], [1, 3, 16], [1, 64, 65, 130]
+
+
+def _cosine_case(D):
     rng = _rng(D)
     feat, target = _rows(rng, 5, D), rng.standard_normal(D).astype(F32)
     feat[3] = 0.0                                           # an all-zero feature row
+    return feat, target
+
+
+def _cosine_views_case(V):
+    P, D = 5, 100
+    rng = _rng(50 + V)
+    return _rows(rng, P * V, D).reshape(P, V, D), rng.standard_normal(D).astype(F32)
+
+
+def _assemble_F_case(P, n_obj):
+    rng = _rng(P)
+    sim = rng.uniform(-1, 1, P).astype(F32)
+    dis = (1.0 + 2.0 * rng.standard_normal(P)).astype(F32)  # both sides of 1
+    dis[0] = 1.0
+    if P > 2:
+        dis[1], dis[2] = 3.5, -2.0
+    return sim, dis if n_obj == 2 else None
+
+
+@pytest.mark.parametrize("D", COSINE_D)
+def test_cosine(D):
+    feat, target = _cosine_case(D)
     got = ops.cosine(feat, target)
     assert got[3] == 0.0
+    _bit_equal("cosine D%d == the parent's cosine_kernel" % D, got, golden("cosine_D%d" % D))
     _bar("cosine D%d" % D, got, R.cosine(feat, target), R.cosine(feat, target, dt=F32))
 
 
-@pytest.mark.parametrize("V", [1, 3, 16])
+@pytest.mark.parametrize("V", COSINE_VIEWS_V)
 def test_cosine_views(V):
-    P, D = 5, 100
-    rng = _rng(50 + V)
-    feat, target = _rows(rng, P * V, D).reshape(P, V, D), rng.standard_normal(D).astype(F32)
+    feat, target = _cosine_views_case(V)
+    P, _, D = feat.shape
     vs, sim = ops.cosine_views(feat, target)
+    _bit_equal("cosine_views V%d == the parent's cosine_views_kernel" % V, pack(vs, sim), golden("cosine_views_V%d" % V))
     _bit_equal("cosine_views V%d per view == cosine_kernel" % V, vs, ops.cosine(feat.reshape(P * V, D), target).reshape(P, V))
     acc = np.zeros(P, F32)
     for v in range(V):
@@ -382,16 +409,12 @@ def test_cosine_views(V):
 
 
 @pytest.mark.parametrize("n_obj", [1, 2])
-@pytest.mark.parametrize("P", [1, 64, 65, 130])
+@pytest.mark.parametrize("P", ASSEMBLE_F_P)
 def test_assemble_F(P, n_obj):
-    rng = _rng(P)
-    sim = rng.uniform(-1, 1, P).astype(F32)
-    dis = (1.0 + 2.0 * rng.standard_normal(P)).astype(F32)  # both sides of 1
-    dis[0] = 1.0
-    if P > 2:
-        dis[1], dis[2] = 3.5, -2.0
-    d = dis if n_obj == 2 else None
-    _bit_equal("assemble_F P%d n_obj%d" % (P, n_obj), ops.assemble_F(sim, d), R.assemble_F(sim, d, dt=F32))
+    sim, d = _assemble_F_case(P, n_obj)
+    got = ops.assemble_F(sim, d)
+    _bit_equal("assemble_F P%d n_obj%d" % (P, n_obj), got, R.assemble_F(sim, d, dt=F32))
+    _bit_equal("assemble_F P%d n_obj%d == the parent's" % (P, n_obj), pack(got), golden("assemble_F_P%d_n%d" % (P, n_obj)))
 
 
 @pytest.mark.parametrize("n", [1, 255, 257, 3 * 32 * 32])
