@@ -16,11 +16,12 @@
     } while (0)
 
 namespace {
-// A device buffer of a Stage: n elements, then `guard` more that no kernel may touch.  Converts to the pointer the launchers take.
+// A device buffer of a Stage: `front` elements that no kernel may touch, n elements, then `guard` more that no kernel may touch either.
+// p is the first of the n (the allocation starts at p - front).  Converts to the pointer the launchers take.
 template <typename T>
 struct Buf {
     T* p = nullptr;
-    size_t n = 0, guard = 0;
+    size_t n = 0, guard = 0, front = 0;
     operator T*() const { return p; }
     T* at(size_t off) const { return p ? p + off : nullptr; }
 };
@@ -45,19 +46,23 @@ struct Stage {
         return e == hipSuccess;
     }
 
-    // outputs and scratch.  raw: whatever the allocation holds
+    // outputs and scratch.  raw: whatever the allocation holds.  A front guard is rounded up to whole 4096-byte pages, so that the pointer
+    // the launchers get keeps the alignment of an allocation's first byte (the LDS-DMA and 16-byte vector paths rely on it)
+    static constexpr size_t FRONT_ALIGN = 4096;
     template <typename T>
-    Buf<T> raw(size_t n, size_t guard = 0) {
+    Buf<T> raw(size_t n, size_t guard = 0, size_t front = 0) {
+        if constexpr (FRONT_ALIGN % sizeof(T) == 0) front = (front * sizeof(T) + FRONT_ALIGN - 1) / FRONT_ALIGN * (FRONT_ALIGN / sizeof(T));
+        else front = 0;      // (a struct that does not divide a page: no front guard)
         void* q = nullptr;
-        if (failed || !ok(hipMalloc(&q, std::max<size_t>(n + guard, 1) * sizeof(T)), GLASS_ERR_NOMEM, "hipMalloc")) return {};
-        owned.push_back(q);
-        return {(T*)q, n, guard};
+        if (failed || !ok(hipMalloc(&q, std::max<size_t>(front + n + guard, 1) * sizeof(T)), GLASS_ERR_NOMEM, "hipMalloc")) return {};
+        owned.push_back(q);      // (the base pointer: what ~Stage frees)
+        return {(T*)q + front, n, guard, front};
     }
     // poisoned: every byte 0xFF (NaN as fp16 / fp32, -1 as int32), so that an element nobody stores shows; the guard elements too (intact())
     template <typename T>
-    Buf<T> poisoned(size_t n, size_t guard = 0) {
-        const Buf<T> b = raw<T>(n, guard);
-        if (b.p) ok(hipMemset(b.p, 0xFF, (n + guard) * sizeof(T)), GLASS_ERR_HIP, "hipMemset");
+    Buf<T> poisoned(size_t n, size_t guard = 0, size_t front = 0) {
+        const Buf<T> b = raw<T>(n, guard, front);
+        if (b.p) ok(hipMemset(b.p - b.front, 0xFF, (b.front + n + guard) * sizeof(T)), GLASS_ERR_HIP, "hipMemset");
         return b;
     }
     // n host elements to element `off` of b
@@ -110,19 +115,44 @@ struct Stage {
         for (size_t i = 0; i < h.size(); ++i) dst[i] = (float)h[i];
         return GLASS_OK;
     }
-    // the guard elements behind b still hold the poison — or `code`, with msg(i) for the first guard element i that does not
-    template <typename T, typename F>
-    int intact(const Buf<T>& b, int code, F msg) {
+    // the guard elements on both sides of b still hold the poison — or `code`, with behind(i) for the first rear guard element i that does
+    // not, before(i) for the front guard element i elements ahead of b's first (the nearest one that does not)
+    template <typename T, typename F, typename G>
+    int intact(const Buf<T>& b, int code, F behind, G before) {
         std::vector<unsigned char> g(b.guard * sizeof(T));
         GLASS_HIP(hipMemcpy(g.data(), b.p + b.n, g.size(), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < g.size(); ++i) REQUIRE(g[i] == 0xFF, code, msg(i / sizeof(T)));
+        for (size_t i = 0; i < g.size(); ++i) REQUIRE(g[i] == 0xFF, code, behind(i / sizeof(T)));
+        g.resize(b.front * sizeof(T));
+        GLASS_HIP(hipMemcpy(g.data(), b.p - b.front, g.size(), hipMemcpyDeviceToHost));
+        for (size_t i = g.size(); i-- > 0;) REQUIRE(g[i] == 0xFF, code, before(b.front - i / sizeof(T)));
         return GLASS_OK;
+    }
+    template <typename T, typename F>
+    int intact(const Buf<T>& b, int code, F behind) {
+        return intact(b, code, behind, [](size_t i) { return "a store " + std::to_string(i) + " elements in front of the buffer"; });
     }
     template <typename T>
     int intact(const Buf<T>& b, const char* msg) {
         return intact(b, GLASS_ERR_ARG, [msg](size_t) { return msg; });
     }
+    // the same for a buffer with a name: the message says which buffer, which side and which element
+    template <typename T>
+    int intact_named(const Buf<T>& b, const std::string& name) {
+        return intact(b, GLASS_ERR_STATE,
+                      [&](size_t i) { return name + ": a store behind the buffer, at element n + " + std::to_string(i) + " (n = " + std::to_string(b.n) + ")"; },
+                      [&](size_t i) { return name + ": a store in front of the buffer, at element -" + std::to_string(i); });
+    }
 };
+
+// The symbol(s) of the last conv / dblock_down / dblock0 launch of the calling thread (glass_op_last_kernel): what ConvKernel::name,
+// launch_conv_gemm, launch_conv_down and launch_dblock0 return; two launches of one op are joined by " + ".  Empty: the op launched nothing.
+thread_local std::string g_last_kernel;
+const char* ran_kernel(const char* name) {
+    if (name) g_last_kernel += (g_last_kernel.empty() ? "" : " + ") + std::string(name);
+    return name;
+}
+// the guard on each side of an image-shaped conv output: one tile of the tallest family (conv_glds, Geo::TH = 16 rows) of `row` elements a row
+constexpr size_t CONV_GUARD_ROWS = 16;
 
 // a launcher's answer as a status: false / nullptr is its refusal
 template <typename R>
@@ -149,6 +179,7 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
           "in_up: H and W are the upsampled dims and must be even (not with up / broadcast_x)");
     OPREQ(d->res_up == 0 || (d->res_up == 1 && d->res && d->Ho % 2 == 0 && d->Wo % 2 == 0), "res_up: needs res, Ho and Wo even");
     OPREQ(d->res_cs == 0 || (d->res && d->res_cs >= d->Cout), "res_cs: needs res, res_cs >= Cout");
+    g_last_kernel.clear();
     Stage st(device);
     ConvParams p = conv_defaults();
     const int Hx = d->H >> d->in_up, Wx = d->W >> d->in_up;      // the stored input map
@@ -208,7 +239,9 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     p.res_cs = d->res_cs; p.res_up = d->res_up;
     p.res = st.in16(d->res, (size_t)d->B * (d->Ho >> d->res_up) * (d->Wo >> d->res_up) * (d->res_cs ? d->res_cs : d->Cout));
     p.out_scale = d->out_scale;
-    const auto y = st.raw<half_t>((size_t)d->B * d->Ho * d->Wo * d->Cout);
+    // NaN: an element no thread stores shows; a tile of guard elements on both sides: a store outside the output shows (intact_named below)
+    const size_t gy = CONV_GUARD_ROWS * d->Wo * d->Cout;
+    const auto y = st.poisoned<half_t>((size_t)d->B * d->Ho * d->Wo * d->Cout, gy, gy);
     p.y = y;
     if (d->skip_x) {
         OPREQ(d->skip_w, "fused skip branch: skip_x and skip_w");
@@ -219,7 +252,8 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     }
     Buf<half_t> xs_dev;
     if (d->xs_out) {
-        xs_dev = st.raw<half_t>((size_t)d->B * (d->H / 2) * (d->W / 2) * d->Cin);
+        const size_t gx = CONV_GUARD_ROWS * (d->W / 2) * d->Cin;
+        xs_dev = st.poisoned<half_t>((size_t)d->B * (d->H / 2) * (d->W / 2) * d->Cin, gx, gx);
         p.xs_out = xs_dev;
     }
     Buf<float> yrgb;
@@ -231,12 +265,12 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
         p.trgb_sn = st.in32(d->trgb_sn, (size_t)d->B * d->Cout); p.trgb_sn_stride = d->Cout;
         p.trgb_smax = st.in32(d->trgb_smax, d->B); p.trgb_smax_stride = 1;
         p.trgb_yprev = st.in32(d->trgb_yprev, (size_t)d->B * 3 * (d->Ho / 2) * (d->Wo / 2));
-        yrgb = st.raw<float>(nrgb);
+        yrgb = st.poisoned<float>(nrgb, CONV_GUARD_ROWS * d->Wo * 3, CONV_GUARD_ROWS * d->Wo * 3);
         p.trgb_yout = yrgb;
         if (d->impl == 4 && !d->trgb_keep_map) {
             p.y = nullptr;                       // the streaming form never stores the map
         } else {                                 // the forms that store it too: weight tables from the table kernel (the first launch below)
-            trgb_tab = st.raw<half_t>((size_t)d->B * 32 * d->Cout);
+            trgb_tab = st.poisoned<half_t>((size_t)d->B * 32 * d->Cout);      // (scratch: a row the table kernel leaves out reaches the image as NaN)
             p.trgb_tab = trgb_tab;
         }
     }
@@ -254,7 +288,7 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     if (d->premod) {
         OPREQ(d->sn && d->KS == 3 && !d->broadcast_x, "premod: 3x3 with sn, not with broadcast_x");
         OPREQ(!d->up || d->impl == 3, "premod up-conv: impl 3 only (the folded table is not modulated)");
-        wm = st.raw<half_t>((size_t)d->B * welems);
+        wm = st.poisoned<half_t>((size_t)d->B * welems);
         mod_w = d->up ? p.w_up : p.w; mod_sn = p.sn; mod_ds = p.dscale;
         p.sn = nullptr; p.sn16 = nullptr; p.dscale = nullptr; p.w_bstride = welems;
         if (d->up) { p.w_up = wm; p.w = nullptr; }
@@ -280,8 +314,9 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     Buf<half_t> gemm_a;
     Buf<float> gemm_c;
     if (gemm_admits) {
-        gemm_a = st.raw<half_t>((size_t)(cap_a * p.B));
-        gemm_c = st.raw<float>((size_t)(cap_c * p.B));
+        // poisoned like the engine's reused scratch holds arbitrary bits: an element the GEMM reads and im2col / a split-K slice did not write is NaN
+        gemm_a = st.poisoned<half_t>((size_t)(cap_a * p.B));
+        gemm_c = st.poisoned<float>((size_t)(cap_c * p.B));
     }
     TRY(st.run([&]() -> int {
         if (trgb_tab) launch_trgb_tables(p.trgb_w, p.trgb_sn, p.trgb_sn_stride, p.trgb_smax, p.trgb_smax_stride, d->B, d->Cout, trgb_tab, 0);
@@ -306,26 +341,35 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
         case 4: ask("conv_stream", choose_conv_stream(p)); break;
         case 5: p.skip_x ? ask("conv_s2", choose_conv_s2(p, true)) : ask("conv_wreg", choose_conv_wreg(p)) || ask("conv_glds", choose_conv_glds(p)); break;
         case 6:
-            ran = gemm_admits && launch_conv_gemm(p, gemm_a, cap_a, gemm_c, cap_c, 0);
+            ran = gemm_admits && ran_kernel(launch_conv_gemm(p, gemm_a, cap_a, gemm_c, cap_c, 0));
             if (!ran) refused("conv_gemm", gemm_outside);
             break;
         default:
             (d->up && ask("upfir", choose_conv_upfir(p))) || ask("conv_stream", choose_conv_stream(p)) || ask("conv_s2", choose_conv_s2(p)) ||
                 ask("conv_tiled", choose_conv_tiled(p)) || ask("conv_direct", choose_conv_direct(p));
         }
-        if (k) k.launch(p, 0);
+        if (k) ran_kernel(k.name), k.launch(p, 0);
         else   // (the planar tanh keeps the words its earlier refusal had)
             OPREQ(ran, (ytanh ? "rgb_tanh: conv_tiled only; " : "") + std::string(labels[d->impl >= 1 && d->impl <= 6 ? d->impl : 0]) + why + ")");
         return GLASS_OK;
     }));
     if (part) TRY(st.run([&] { launch_trgb_finish(part, ntn, d->B, d->Ho, p.trgb_b, part_yprev, yrgb, 0); }));
-    if (ytanh) return st.fetch(d->rgb_tanh, ytanh);              // (p.y is not written)
+    if (ytanh) {                                                 // (p.y is not written)
+        TRY(st.fetch(d->rgb_tanh, ytanh));
+        return st.intact_named(y, "conv: y (rgb_tanh form, not an output)");
+    }
     if (yrgb) {
         TRY(st.fetch(d->trgb_yout, yrgb));
-        return p.y ? st.fetch(d->y, y) : GLASS_OK;      // (the forms that also store the feature map hand it back too)
+        TRY(st.intact_named(yrgb, "conv: trgb_yout"));
+        if (p.y) TRY(st.fetch(d->y, y));                // (the forms that also store the feature map hand it back too)
+        return st.intact_named(y, "conv: y");
     }
-    if (xs_dev) TRY(st.fetch(d->xs_out, xs_dev));
-    return st.fetch(d->y, y);
+    if (xs_dev) {
+        TRY(st.fetch(d->xs_out, xs_dev));
+        TRY(st.intact_named(xs_dev, "conv: xs_out"));
+    }
+    TRY(st.fetch(d->y, y));
+    return st.intact_named(y, "conv: y");
 }
 
 // the rows behind an output that no GEMM / attention kernel may touch (one whole m tile of the widest kernel)
@@ -460,6 +504,7 @@ extern "C" int glass_op_dblock_down(int32_t device, int32_t B, int32_t R, int32_
                                     const float* x, const float* w1, const float* wskip, const float* b1, float* y) {
     OPREQ(h && x && w1 && wskip && b1 && y, "bad argument");
     OPREQ(conv_down_supported(R, Cin, Cout), "conv_down: unsupported shape");
+    g_last_kernel.clear();
     Stage st(device);
     const auto dh = st.in16(h, (size_t)B * R * R * Cin), dx = st.in16(x, (size_t)B * R * R * Cin);
     std::vector<_Float16> pk;
@@ -469,17 +514,21 @@ extern "C" int glass_op_dblock_down(int32_t device, int32_t B, int32_t R, int32_
     const auto dws = st.in16(pk);
     const auto db = st.in32(b1, Cout);
     const int Ro = R / 2;
-    const auto dxs = st.raw<half_t>((size_t)B * Ro * Ro * Cin), dy = st.raw<half_t>((size_t)B * Ro * Ro * Cout);
+    const size_t gxs = CONV_GUARD_ROWS * Ro * Cin, gy = CONV_GUARD_ROWS * Ro * Cout;
+    const auto dxs = st.poisoned<half_t>((size_t)B * Ro * Ro * Cin, gxs, gxs), dy = st.poisoned<half_t>((size_t)B * Ro * Ro * Cout, gy, gy);
     TRY(st.run([&]() -> int {
         launch_blur_down(dx, B, R, R, Cin, dxs, 0);          // the skip branch's FIR (pad 1) + ::2 (conv_stream<fromrgb> emits it in the engine)
-        return accepted(launch_conv_down(dh, dxs, dw1, dws, db, dy, B, R, Cin, Cout, 0) != nullptr, "conv_down: unsupported shape");
+        return accepted(ran_kernel(launch_conv_down(dh, dxs, dw1, dws, db, dy, B, R, Cin, Cout, 0)) != nullptr, "conv_down: unsupported shape");
     }));
-    return st.fetch(y, dy);
+    TRY(st.fetch(y, dy));
+    TRY(st.intact_named(dxs, "dblock_down: xs (the blur-down of x)"));
+    return st.intact_named(dy, "dblock_down: y");
 }
 
 extern "C" int glass_op_dblock0(int32_t device, int32_t B, int32_t R, int32_t impl, const float* y, const float* frgb_w, const float* frgb_b,
                                 const float* w0, const float* b0, const float* w1, const float* wskip, const float* b1, float* out) {
     OPREQ(y && frgb_w && frgb_b && w0 && b0 && w1 && wskip && b1 && out && B > 0 && R > 0, "bad argument");
+    g_last_kernel.clear();
     Stage st(device);
     const int Cin = 32, Cout = 64, Ro = R / 2;
     const bool fused = impl == 0 || impl == 2;      // conv_d0.hip: the whole block in one kernel (2: chunk-planar output)
@@ -492,24 +541,38 @@ extern "C" int glass_op_dblock0(int32_t device, int32_t B, int32_t R, int32_t im
     glass_pack_conv(wskip, Cout, Cin, 1, Cin, pk);
     const auto dws = st.in16(pk);
     const auto db0 = st.in32(b0, Cin), db1 = st.in32(b1, Cout);
-    const auto dout = st.raw<half_t>((size_t)B * Ro * Ro * Cout);
+    const size_t gout = CONV_GUARD_ROWS * Ro * Cout, gh = CONV_GUARD_ROWS * R * Cin, gxs = CONV_GUARD_ROWS * Ro * Cin;
+    const auto dout = st.poisoned<half_t>((size_t)B * Ro * Ro * Cout, gout, gout);
     Buf<half_t> dh, dxs;      // the two-kernel form it replaces: conv_stream<fromrgb> (h + the skip input to HBM) + conv_down
-    if (!fused) {
-        dh = st.raw<half_t>((size_t)B * R * R * Cin);
-        dxs = st.raw<half_t>((size_t)B * Ro * Ro * Cin);
+    if (!fused) {             // dh is conv_stream<fromrgb>'s x AND its y: the kernel builds its input from the skip image and never reads x — the poison proves it
+        dh = st.poisoned<half_t>((size_t)B * R * R * Cin, gh, gh);
+        dxs = st.poisoned<half_t>((size_t)B * Ro * Ro * Cin, gxs, gxs);
     }
     TRY(st.run([&]() -> int {
-        if (fused) return accepted(launch_dblock0(dy, dfw, dfb, dw0, db0, dw1, dws, db1, dout, B, R, Cin, Cout, 0, impl == 2) != nullptr, "dblock0: unsupported shape");
+        if (fused) return accepted(ran_kernel(launch_dblock0(dy, dfw, dfb, dw0, db0, dw1, dws, db1, dout, B, R, Cin, Cout, 0, impl == 2)) != nullptr, "dblock0: unsupported shape");
         ConvParams p = conv_defaults();
         p.x = dh; p.x_bstride = (long long)R * R * Cin; p.B = B; p.H = p.W = R; p.Cin = Cin; p.Hc = p.Wc = R; p.KS = 3; p.pad = 1;
         p.w = dw0; p.Cout = p.Neff = Cin; p.Ho = p.Wo = R; p.bias = db0; p.act = 1; p.y = dh;
         p.rgb_y = dy; p.rgb_w = dfw; p.rgb_b = dfb; p.rgb_xs_out = dxs;
         const ConvKernel k = choose_conv_stream(p);
         OPREQ(k, "dblock0 (two-kernel form): conv_stream<fromrgb> does not take this shape");
+        ran_kernel(k.name);
         k.launch(p, 0);
-        return accepted(launch_conv_down(dh, dxs, dw1, dws, db1, dout, B, R, Cin, Cout, 0) != nullptr, "dblock0 (two-kernel form): conv_down does not take this shape");
+        return accepted(ran_kernel(launch_conv_down(dh, dxs, dw1, dws, db1, dout, B, R, Cin, Cout, 0)) != nullptr, "dblock0 (two-kernel form): conv_down does not take this shape");
     }));
-    return st.fetch(out, dout);
+    TRY(st.fetch(out, dout));
+    if (!fused) {
+        TRY(st.intact_named(dh, "dblock0: h (conv_stream<fromrgb>'s map)"));
+        TRY(st.intact_named(dxs, "dblock0: xs (the skip branch's input)"));
+    }
+    return st.intact_named(dout, "dblock0: out");
+}
+
+extern "C" int glass_op_last_kernel(char* buf, int32_t cap) {
+    OPREQ(buf && cap > 0, "last_kernel: a buffer of cap > 0 characters");
+    OPREQ(g_last_kernel.size() < (size_t)cap, "last_kernel: the name needs " + std::to_string(g_last_kernel.size() + 1) + " characters");
+    memcpy(buf, g_last_kernel.c_str(), g_last_kernel.size() + 1);
+    return GLASS_OK;
 }
 
 extern "C" int glass_op_fromrgb(int32_t device, int32_t B, int32_t R, int32_t Cout, const float* y, const float* w,

@@ -45,6 +45,7 @@ SIGNATURES = {
     "glass_op_blur": [i32, i32, i32, i32, i32, fp, fp],
     "glass_op_dblock_down": [i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, fp],
     "glass_op_dblock0": [i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp],
+    "glass_op_last_kernel": [C.c_char_p, i32],
     "glass_op_fromrgb": [i32, i32, i32, i32, fp, fp, fp, fp],
     "glass_op_mbstd": [i32, i32, i32, i32, i32, i32, i32, fp, fp],
     "glass_op_resize": [i32, i32, i32, i32, i32, fp, fp],
@@ -186,7 +187,7 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
         Ho, Wo = 2 * H, 2 * W
     else:
         Ho, Wo = (H + 2 * pad - KS) // stride + 1, (W + 2 * pad - KS) // stride + 1
-    y = np.empty((B, Ho, Wo, Cout), dtype=np.float32)
+    y = np.full((B, Ho, Wo, Cout), np.nan, dtype=np.float32)      # (NaN: what the op does not fetch shows)
     d = ConvDesc()
     d.B, d.H, d.W, d.Cin, d.Cout = B, H, W, Cin, Cout
     d.KS, d.stride, d.pad, d.up, d.Ho, d.Wo = KS, stride, pad, int(up), Ho, Wo
@@ -214,7 +215,7 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
         d.xs_out = _fp(xs_out)
     yrgb = None
     if torgb is not None:
-        yrgb = np.empty((B, 3, Ho, Wo), dtype=np.float32)
+        yrgb = np.full((B, 3, Ho, Wo), np.nan, dtype=np.float32)
         for name in ("w", "b", "sn", "smax", "yprev"):
             a, p = _opt(torgb.get(name))
             keep.append(a)
@@ -223,7 +224,7 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
         d.trgb_yout = _fp(yrgb)
     ytanh = None
     if rgb_tanh:
-        ytanh = np.empty((B, 3, Ho, Wo), dtype=np.float32)
+        ytanh = np.full((B, 3, Ho, Wo), np.nan, dtype=np.float32)
         d.rgb_tanh = _fp(ytanh)
     _check(lib, lib.glass_op_conv(device, C.byref(d)))
     if rgb_tanh:
@@ -233,6 +234,14 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
     if both:                  # fused toRGB forms that store the feature map too (impl 2 / 5): (skip image, feature map)
         return yrgb, y
     return yrgb if yrgb is not None else y
+
+
+def last_kernel():
+    """The kernel symbol(s) the last conv / dblock_down / dblock0 of this thread launched ("a + b" for two launches; "" for none)."""
+    lib = _lib()
+    buf = C.create_string_buffer(512)
+    _check(lib, lib.glass_op_last_kernel(buf, len(buf)))
+    return buf.value.decode()
 
 
 def gemm(a, w, bias=None, mode=3, impl=0, acc=None, device=0):
@@ -320,7 +329,7 @@ def dblock_down(h, x, w1, wskip, b1, device=0):
     h, x, w1, wskip, b1 = _f32(h), _f32(x), _f32(w1), _f32(wskip), _f32(b1)
     B, R, _, Cin = h.shape
     Cout = w1.shape[0]
-    out = np.empty((B, R // 2, R // 2, Cout), dtype=np.float32)
+    out = np.full((B, R // 2, R // 2, Cout), np.nan, dtype=np.float32)
     _check(lib, lib.glass_op_dblock_down(device, B, R, Cin, Cout, _fp(h), _fp(x), _fp(w1), _fp(wskip), _fp(b1), _fp(out)))
     return out
 
@@ -331,7 +340,7 @@ def dblock0(y, frgb_w, frgb_b, w0, b0, w1, wskip, b1, impl=0, device=0):
     lib = _lib()
     y, frgb_w, frgb_b, w0, b0, w1, wskip, b1 = (_f32(a) for a in (y, frgb_w, frgb_b, w0, b0, w1, wskip, b1))
     B, _, R, _ = y.shape
-    out = np.empty((B, R // 2, R // 2, 64), dtype=np.float32)
+    out = np.full((B, R // 2, R // 2, 64), np.nan, dtype=np.float32)
     _check(lib, lib.glass_op_dblock0(device, B, R, impl, _fp(y), _fp(frgb_w), _fp(frgb_b), _fp(w0), _fp(b0), _fp(w1), _fp(wskip),
                                      _fp(b1), _fp(out)))
     return from_planar8(out, B, R // 2, R // 2, 64) if impl == 2 else out

@@ -117,6 +117,15 @@ int glass_op_dblock_down(int32_t device, int32_t B, int32_t R, int32_t Cin, int3
  * 2: the fused kernel writing out chunk-planar, [B,8,R/2,R/2,8] */
 int glass_op_dblock0(int32_t device, int32_t B, int32_t R, int32_t impl, const float* y, const float* frgb_w, const float* frgb_b,
                      const float* w0, const float* b0, const float* w1, const float* wskip, const float* b1, float* out);
+/* glass_op_conv, glass_op_dblock_down and glass_op_dblock0 stage every device output poisoned (every byte 0xFF: an element no thread stores
+ * comes back as NaN), and so the scratch one launch of the op writes for the next (toRGB weight tables, pre-modulated weights, the im2col
+ * matrix and the split-K slices): a consumer that reads what its producer left out yields NaN.  The image-shaped outputs (y, trgb_yout,
+ * xs_out; xs, y; h, xs, out) have one 16-row tile of guard elements in front and behind; a store there is GLASS_ERR_STATE, and the message
+ * names the buffer, the side and the element.
+ * glass_op_last_kernel: the symbol of the kernel the calling thread's last glass_op_conv / glass_op_dblock_down / glass_op_dblock0 chose
+ * (what ConvKernel::name, launch_conv_gemm, launch_conv_down and launch_dblock0 return; the two launches of dblock0 impl 1 joined by
+ * " + "), NUL-terminated into buf [cap]; empty if that op launched nothing.  GLASS_ERR_ARG: cap too small. */
+int glass_op_last_kernel(char* buf, int32_t cap);
 int glass_op_fromrgb(int32_t device, int32_t B, int32_t R, int32_t Cout, const float* y /*[B,3,R,R]*/,
                      const float* w /*[Cout,3] scaled*/, const float* bias, float* out /*[B,R,R,Cout]*/);
 int glass_op_mbstd(int32_t device, int32_t B, int32_t hw, int32_t C, int32_t Cpad, int32_t batch_size, int32_t group,

@@ -36,6 +36,12 @@ def h16(a):
     return np.asarray(a, dtype=np.float32).astype(np.float16).astype(np.float32)
 
 
+def _ran(symbol):
+    """The last conv / dblock launch ran the kernel this test is about (ops.last_kernel(); the emulated ops have no kernels to name)."""
+    if hasattr(ops, "last_kernel"):
+        assert ops.last_kernel() == symbol, "the launch ran %r, this test is about %r" % (ops.last_kernel(), symbol)
+
+
 def test_mfma_fragment_layout():
     a = rnd(1, "a", (32, 16)); b = rnd(1, "b", (16, 32))
     d = ops.mfma_probe(a, b)
@@ -47,8 +53,8 @@ def test_mfma_fragment_layout():
     (2, 2, 32, 64, 128),    # conv_tiled<3,1,8,128>
     (2, 1, 64, 32, 256),    # conv_tiled<3,1,8,128>, 2 n-tiles, 16 pixel tiles
     (2, 2, 32, 64, 64),     # conv_tiled<3,1,8,64>
-    (2, 3, 32, 32, 32),     # conv_tiled<3,1,16,32>
-    (2, 1, 64, 96, 96),     # conv_tiled<3,1,16,32>, 3 n-tiles, 3 chunks
+    (2, 3, 32, 32, 32),     # conv_tiled<3,1,8,32>
+    (2, 1, 64, 96, 96),     # conv_tiled<3,1,8,32>, 3 n-tiles, 3 chunks
 ])
 def test_conv_plain_bias_act(impl, B, H, Cin, Cout):
     x = rnd(2, "x", (B, Cin, H, H)); w = rnd(2, "w", (Cout, Cin, 3, 3)); bias = rnd(2, "b", (Cout,), 0.3)
@@ -114,6 +120,7 @@ def test_conv_stream_matches_tiled_and_direct():
     res = rng.standard_normal((B, H, W, C)).astype(np.float16).astype(np.float32)
     kw = dict(sn=sn, dscale=ds, noise=noise, noise_strength=0.3, batch_size=1, bias=bias, act=True, out_scale=0.7)
     got = ops.conv(x, w, impl=4, **kw)
+    _ran("conv_stream_kernel")
     ref_t = ops.conv(x, w, impl=2, **kw)
     ref_d = ops.conv(x, w, impl=1, **kw)
     # same staging and MFMA order as the tiled kernel; the streaming epilogue rounds the activation INPUT to fp16 and applies
@@ -158,6 +165,8 @@ def _stride2_skip_case(B, R, Cin, Cout, impl, label):
     b1 = rng.standard_normal(Cout).astype(np.float32) * 0.2
     kw = dict(stride=2, pad=0, bias=b1, act=True, out_scale=2.0 ** -0.5)
     got = ops.conv(hb, w1, skip=(xs, ws), impl=impl, **kw)
+    if impl == 5:
+        _ran("conv_s2_kernel")
     s = ops.conv(xs, ws, pad=0, impl=2)
     ref2 = ops.conv(hb, w1, res=s, impl=2, **kw)
     t = lambda a: torch.tensor(np.ascontiguousarray(a.transpose(0, 3, 1, 2)), dtype=torch.float64)
@@ -313,15 +322,19 @@ def test_conv_glds_persistent_matches_tiled():
     res = rng.standard_normal((B, H, W, Cout)).astype(np.float16).astype(np.float32)
     kw = dict(dscale=ds, noise=noise, noise_strength=0.3, batch_size=1, bias=bias, act=True, res=res, out_scale=0.7)
     got = ops.conv(x, w, impl=5, **kw)
+    _ran("conv_gldsp_kernel<false,false,false>")
     ref_t = ops.conv(x, w, impl=2, **kw)
     assert np.abs(got - ref_t).max() <= 2.0 ** -8 * max(1.0, float(np.abs(ref_t).max()))
     check("persistent conv_glds vs oracle", got, _oracle_conv(x, w, **kw), 5e-3)
     sn = rng.uniform(-1.0, 1.0, (B, Cin)).astype(np.float32)
-    check("persistent conv_glds (style on weights) vs direct", ops.conv(x, w, impl=5, sn=sn, **kw), ops.conv(x, w, impl=1, sn=sn, **kw), 4e-3)
+    got_s = ops.conv(x, w, impl=5, sn=sn, **kw)
+    _ran("conv_gldsp_kernel<false,false,true>")
+    check("persistent conv_glds (style on weights) vs direct", got_s, ops.conv(x, w, impl=1, sn=sn, **kw), 4e-3)
     # blur-down of the input as a by-product of the staged patches (two n tiles per pixel tile: chunk c is written by n tile c % 2)
     xs = np.full((B, H // 2, W // 2, Cin), np.nan, dtype=np.float32)
     kw2 = dict(bias=bias, act=True, out_scale=0.7)
     y2 = ops.conv(x, w, impl=5, xs_out=xs, **kw2)
+    _ran("conv_gldsp_kernel<false,true,false>")
     np.testing.assert_array_equal(y2, ops.conv(x, w, impl=5, **kw2))
     f = np.array([1, 3, 3, 1], dtype=np.float64) / 8
     xp = np.pad(x.astype(np.float64), ((0, 0), (1, 1), (1, 1), (0, 0)))
@@ -340,6 +353,7 @@ def test_conv_glds_persistent_matches_tiled():
     smax = rng.uniform(0.5, 3.0, B).astype(np.float32)
     yprev = rng.standard_normal((B, 3, H // 2, W // 2)).astype(np.float32)
     got = ops.conv(x, w, impl=5, torgb=dict(w=wrgb, b=brgb, sn=srgb, smax=smax, yprev=yprev), **kw)
+    _ran("conv_gldsp_kernel<true,false,true>")
     feat = ops.conv(x, w, impl=5, **kw)
     check("persistent conv_glds fused toRGB", got, _torgb_ref(feat, wrgb, brgb, srgb, smax, yprev), 2e-5)
 
@@ -359,6 +373,7 @@ def test_conv_wreg_matches_tiled(B, H, W):
     res = rng.standard_normal((B, H, W, C)).astype(np.float16).astype(np.float32)
     kw = dict(dscale=ds, noise=noise, noise_strength=0.3, batch_size=1, bias=bias, act=True, out_scale=0.7)
     got = ops.conv(x, w, impl=5, **kw)
+    _ran("conv_wreg_kernel<false,false>")
     ref_t = ops.conv(x, w, impl=2, **kw)
     diag("[wreg] B%d %dx%d max|wreg-tiled| %.3e" % (B, H, W, np.abs(got - ref_t).max()))
     assert np.abs(got - ref_t).max() <= 2.0 ** -8 * max(1.0, float(np.abs(ref_t).max()))
@@ -375,6 +390,7 @@ def test_conv_wreg_matches_tiled(B, H, W):
     xs = np.full((B, H // 2, W // 2, C), np.nan, dtype=np.float32)
     kw2 = dict(bias=bias, act=True, out_scale=0.7)
     y2 = ops.conv(x, w, impl=5, xs_out=xs, **kw2)
+    _ran("conv_wreg_kernel<false,true>")
     np.testing.assert_array_equal(y2, ops.conv(x, w, impl=5, **kw2))
     xs_p = np.full_like(xs, np.nan)
     np.testing.assert_array_equal(y2, ops.conv(x, w, impl=5, xs_out=xs_p, planar_x=True, **kw2))
@@ -394,6 +410,7 @@ def test_conv_wreg_matches_tiled(B, H, W):
     feat = ops.conv(x, w, impl=5, **kw3)
     for yprev in (rng.standard_normal((B, 3, H // 2, W // 2)).astype(np.float32), None):
         got_rgb = ops.conv(x, w, impl=5, torgb=dict(w=wrgb, b=brgb, sn=srgb, smax=smax, yprev=yprev), **kw3)
+        _ran("conv_wreg_kernel<true,false>")
         check("conv_wreg fused toRGB", got_rgb, _torgb_ref(feat, wrgb, brgb, srgb, smax, yprev), 2e-5)
 
 
@@ -475,6 +492,7 @@ def test_d_block_down_fused(B, R, Cin, Cout):
     xs = sg._filter(xt, sg._fir(), 1, 1)[:, :, ::2, ::2]
     ref = ((h1 + sg._conv(xs, torch.tensor(ws))) / math.sqrt(2)).numpy()
     got = ops.dblock_down(nhwc(h), nhwc(x), w1, ws, b1)
+    _ran("conv_down_kernel")
     check("D down fused B%d R%d %d->%d" % (B, R, Cin, Cout), nchw(got), ref, 6e-3)
     # image borders carry the zero padding of both FIRs: check them on their own (a wrong mask hides in a global norm)
     for name, sl in (("top", np.s_[:, :, :2, :]), ("bottom", np.s_[:, :, -2:, :]), ("left", np.s_[:, :, :, :2]), ("right", np.s_[:, :, :, -2:])):
@@ -506,12 +524,14 @@ def test_dblock0_fused(B, R):
     1587-1601) against the oracle's UNFUSED ops, and — where the two-kernel form applies — against conv_stream<fromrgb> + conv_down."""
     args, ref = _dblock0_case(B, R)
     got = ops.dblock0(*args)
+    _ran("dblock0_kernel")
     check("D block0 fused B%d R%d" % (B, R), nchw(got), ref, 6e-3)
     np.testing.assert_array_equal(got, ops.dblock0(*args, impl=2))     # the chunk-planar output (for conv_wreg): same values, other addresses
     for name, sl in (("top", np.s_[:, :, :2, :]), ("bottom", np.s_[:, :, -2:, :]), ("left", np.s_[:, :, :, :2]), ("right", np.s_[:, :, :, -2:])):
         check("D block0 fused border " + name, nchw(got)[sl], ref[sl], 8e-3)
     if R >= 192 and R % 64 == 0 and ops is not None and hasattr(ops, "load_library"):
         two = ops.dblock0(*args, impl=1)
+        _ran("conv_stream_kernel<fromrgb> + conv_down_kernel")
         # same fromRGB / conv0 arithmetic bit for bit; the FIR runs horizontally first here and vertically first in conv_down (one fp16
         # rounding each way), so outputs agree to a couple of fp16 ulps
         d = np.abs(got - two)
