@@ -5,6 +5,8 @@ poisoned with NaN at every priming point (the kernel finds stale data there), so
 not written comes out NaN.  The formulas restate the kernel; a change there must be mirrored here."""
 import numpy as np
 
+from fir_ops_ref import fir4      # fma(b + c, 3/8, (a + d) / 8) in fp16, as built: the one copy of it
+
 TW, CIN, COUT = 29, 64, 128
 ROWB = 64 * 128
 V_BYTES, A_BYTES, XS_BYTES, O_BYTES = 4 * ROWB, 8 * ROWB, 2 * 32 * 128, 2 * 32 * 256
@@ -21,14 +23,6 @@ def aaddr(rslot, slot, lc):
 
 def oaddr(row, px, c16):
     return row * (32 * 256) + (px << 8) + ((c16 ^ (px & 15)) << 4)
-
-
-def fir4(a, b, c, d):
-    """fma(b + c, 3/8, (a + d) / 8) in fp16: the sums and the product by 1/8 round (the latter exactly), the fma rounds once."""
-    with np.errstate(invalid="ignore", over="ignore"):
-        m = ((a + d).astype(np.float16) * np.float16(0.125)).astype(np.float16)
-        s = (b + c).astype(np.float16)
-        return (s.astype(np.float64) * 0.375 + m.astype(np.float64)).astype(np.float16)
 
 
 def gate(R, Cin, Cout):
@@ -147,18 +141,19 @@ def dblock_down64(h, xs, w1, ws, b1, n_cus=256, stats=None):
             # MFMA phase: wave (r, nb), lane (lr, kh)
             lr = np.arange(32)
             for r in range(2):
-                acc = np.zeros((32, COUT), np.float32)
+                acc = np.zeros((32, COUT), np.float64)      # float64 sums (order-free), rounded to fp32 where the kernel's accumulator is read
                 with np.errstate(invalid="ignore"):
                     for ky in range(3):
                         rs = (4 * s + 2 * r + ky) & 7
                         for kx in range(3):
                             slot = (32 if kx == 1 else (kx >> 1)) + lr
-                            frag = np.concatenate([lds[As + aaddr(rs, slot, lc) // 16] for lc in range(8)], axis=1).astype(np.float32)   # [px][ci]
-                            acc += frag @ Wm[ky * 3 + kx].T
-                    acc = acc + b1.astype(np.float32)[None]
-                    acc = np.maximum(acc, np.float32(0.2) * acc)
-                    frag = np.concatenate([lds[Xs + aaddr(0, r * 32 + lr, lc) // 16] for lc in range(8)], axis=1).astype(np.float32)
-                    acc += frag @ Wk.T
+                            frag = np.concatenate([lds[As + aaddr(rs, slot, lc) // 16] for lc in range(8)], axis=1).astype(np.float64)   # [px][ci]
+                            acc += frag @ Wm[ky * 3 + kx].astype(np.float64).T
+                    acc = acc.astype(np.float32) + b1.astype(np.float32)[None]
+                    acc = np.maximum(acc, np.float32(0.2) * acc).astype(np.float64)
+                    frag = np.concatenate([lds[Xs + aaddr(0, r * 32 + lr, lc) // 16] for lc in range(8)], axis=1).astype(np.float64)
+                    acc += frag @ Wk.astype(np.float64).T
+                    acc = acc.astype(np.float32)
                 out = acc.astype(np.float16)
                 for c16 in range(16):
                     lds[Os + oaddr(r, lr, c16) // 16] = out[:, c16 * 8:(c16 + 1) * 8]

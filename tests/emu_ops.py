@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 from clip_glass_amd import ops as real_ops
 from clip_glass_amd import synth
+from fir_ops_ref import fir4 as _fir4      # (a + d) * 0.125 + (b + c) * 0.375 as v_pk_add / v_pk_mul / v_pk_fma f16 do it
 
 
 def _h(a):
@@ -220,15 +221,6 @@ def _aaddr(row, slot, lc):
 
 def _waddr(row, lc):
     return (row << 6) + ((lc ^ ((row >> 2) & 3)) << 4)
-
-
-def _fir4(a, b, c, d):
-    """(a + d) * 0.125 + (b + c) * 0.375 as v_pk_add / v_pk_mul / v_pk_fma f16 do it."""
-    f16 = np.float16
-    t1 = (a.astype(np.float32) + d.astype(np.float32)).astype(f16)
-    t2 = (t1.astype(np.float32) * 0.125).astype(f16)
-    t3 = (b.astype(np.float32) + c.astype(np.float32)).astype(f16)
-    return (t3.astype(np.float64) * 0.375 + t2.astype(np.float64)).astype(f16)
 
 
 def dblock_down(h, x, w1, wskip, b1, device=0):
@@ -438,8 +430,7 @@ def upfir2(x, w, *, sn=None, dscale=None, noise=None, noise_strength=0.0, batch_
     written = np.zeros((B, Ho, Wo), np.int32)
     sn16 = None if sn is None else np.asarray(sn, np.float32).astype(f16)
     ps16 = None if post_scale is None else np.asarray(post_scale, np.float32).astype(f16)
-    k1 = f16((math.sqrt(2) if act else 1.0) * out_scale)
-    k2 = f16((0.2 * math.sqrt(2) if act else 1.0) * out_scale)
+    k1 = f16((np.float32(1.41421356237309504880) if act else np.float32(1)) * np.float32(out_scale))      # the kernel's fp32 product, then fp16
     lr = np.arange(32)
 
     def pk(a):                    # result of one packed-fp16 instruction
@@ -514,7 +505,7 @@ def upfir2(x, w, *, sn=None, dscale=None, noise=None, noise_strength=0.0, batch_
                             img = img0 + iyo * NXI + ixo
                             if not (ox < Wo and ixo < NXI and img < B):
                                 continue
-                            nz = 0.0 if noise is None else noise_strength * float(np.asarray(noise, np.float32)[img // batch_size, oy, ox])
+                            nz = 0.0 if noise is None else np.float32(noise_strength) * np.asarray(noise, np.float32)[img // batch_size, oy, ox]      # fp32 product
                             bn = pk((0.0 if bias is None else np.asarray(bias, np.float32)).astype(f16).astype(np.float32) + np.float32(f16(nz)))
                             vv = pk(a[oxl].astype(np.float32) * 0.0625 + pk(m[oxl].astype(np.float32) * 0.1875 + bn.astype(np.float32)).astype(np.float32))
                             # upfir.hip (r05): max(v, slope v) * (gain * consumer style), gain * style rounded once to fp16

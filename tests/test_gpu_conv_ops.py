@@ -35,8 +35,8 @@ the tests pin"):
 Every case sits below 1.  The bound's leading term is the fp16 store's half ulp, which some element of any output attains; the ratios near
 0.9 are outputs just above a power of two, where 2^-11 |out| IS that half ulp.
 
-Out of scope here (they keep their bars in test_gpu_ops.py and get the poison, the guards and the symbol check): the up-conv, the stride-2
-and skip kernels, conv_down, conv_down64, conv_d0 — their packed-fp16 FIR chains need a rounding model of their own."""
+The up-conv, the stride-2 and skip kernels, conv_down, conv_down64 and conv_d0 — whose packed-fp16 FIR chains need a rounding model of their own —
+are in tests/test_gpu_fir_ops.py, against tests/fir_ops_ref.py."""
 import os
 
 import numpy as np
