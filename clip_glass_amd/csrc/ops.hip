@@ -1294,32 +1294,45 @@ __global__ void mfma_probe_kernel(const half_t* a, const half_t* b, float* d) {
     for (int reg = 0; reg < 16; ++reg) d[mfma32_row(reg, lane) * 32 + (lane & 31)] = acc[reg];
 }
 // ---- CLIP's ResNet towers ----
+// Every output and scratch buffer below is poisoned (an element no thread stores comes back as NaN) and guarded on both sides (a store outside
+// it fails the op, intact_named): image-shaped outputs by CONV_GUARD_ROWS image rows, gemm_tiled's rows by one 128-row m tile, the tokens by
+// one token row.  Each op clears g_last_kernel and records the symbol it launched (glass_op_last_kernel).
+namespace {
+constexpr size_t GEMM_GUARD_ROWS = 128;      // one m tile of gemm_tiled
+}
+
 extern "C" int glass_op_rn_avgpool(int32_t device, int32_t B, int32_t H, int32_t W, int32_t C, const float* x, float* out) {
     OPREQ(x && out && B > 0 && H > 0 && W > 0 && C > 0, "bad argument");
+    g_last_kernel.clear();
     Stage st(device);
     const auto dx = st.in16(x, (size_t)B * H * W * C);
-    const auto dy = st.raw<half_t>((size_t)B * (H / 2) * (W / 2) * C);
-    TRY(st.run([&] { return accepted(launch_rn_avgpool2(dx, B, H, W, C, dy, 0), "rn_avgpool2: refused (even H and W, C a multiple of 8)"); }));
+    const size_t gy = CONV_GUARD_ROWS * (W / 2) * C;
+    const auto dy = st.poisoned<half_t>((size_t)B * (H / 2) * (W / 2) * C, gy, gy);
+    TRY(st.run([&] { return accepted(launch_rn_avgpool2(dx, B, H, W, C, dy, 0) && ran_kernel("rn_avgpool2_kernel"), "rn_avgpool2: refused (even H and W, C a multiple of 8)"); }));
+    TRY(st.intact_named(dy, "rn_avgpool: out"));
     return st.fetch(out, dy);
 }
 
 extern "C" int glass_op_rn_stem_conv1(int32_t device, int32_t B, int32_t S, int32_t C1, const float* img, const float* w, const float* bn_a,
                                       const float* bn_s, float* out) {
     OPREQ(img && w && bn_a && bn_s && out && B > 0 && S > 0 && S % 32 == 0 && C1 > 0, "bad argument (S a multiple of 32)");
+    g_last_kernel.clear();
     Stage st(device);
     const size_t ni = (size_t)B * 3 * S * S;
     std::vector<_Float16> wt((size_t)27 * C1);
     for (int o = 0; o < C1; ++o)
         for (int k = 0; k < 27; ++k) wt[(size_t)k * C1 + o] = (_Float16)w[(size_t)o * 27 + k];
     const auto dimg = st.in32(img, ni);
-    const auto dp = st.raw<half_t>(ni);
+    const auto dp = st.poisoned<half_t>(ni);      // (the patch operand: a pixel launch_image_patches leaves out reaches the conv as NaN)
     const auto dw = st.in16(wt);
     const auto da = st.in32(bn_a, C1), ds = st.in32(bn_s, C1);
-    const auto dy = st.raw<half_t>((size_t)B * (S / 2) * (S / 2) * C1);
+    const size_t gy = CONV_GUARD_ROWS * (S / 2) * C1;
+    const auto dy = st.poisoned<half_t>((size_t)B * (S / 2) * (S / 2) * C1, gy, gy);
     TRY(st.run([&]() -> int {
-        launch_image_patches(dimg, B, S, 32, 3072, dp, 0);
-        return accepted(launch_rn_stem_conv1(dp, dw, da, ds, B, S, C1, dy, 0), "rn_stem_conv1: refused (C1 a multiple of 8)");
+        launch_image_patches(dimg, B, S, 32, 3072, dp, 0);      // (the operand's preparation: not the op's kernel, not recorded)
+        return accepted(launch_rn_stem_conv1(dp, dw, da, ds, B, S, C1, dy, 0) && ran_kernel("rn_stem_conv1_kernel"), "rn_stem_conv1: refused (C1 a multiple of 8)");
     }));
+    TRY(st.intact_named(dy, "rn_stem_conv1: out"));
     return st.fetch(out, dy);
 }
 
@@ -1328,6 +1341,7 @@ extern "C" int glass_op_rn_conv_bn(int32_t device, int32_t form, int32_t B, int3
     OPREQ(x && w && bn_a && bn_s && out && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "bad argument");
     OPREQ((form == 0 && (KS == 1 || KS == 3)) || (form == 1 && KS == 3), "rn_conv_bn: form 0 takes KS 1 or 3, form 1 KS 3");
     OPREQ(KS == 1 || (relu && !res), "rn_conv_bn: the 3 x 3 forms are conv + BN + ReLU without a residual");
+    g_last_kernel.clear();
     Stage st(device);
     const int M = B * H * W, Mp = std::max(M, 64);
     RnConv c;
@@ -1335,45 +1349,61 @@ extern "C" int glass_op_rn_conv_bn(int32_t device, int32_t form, int32_t B, int3
     c.w = st.in16(rn_pack_conv(w, Cout, Cin, KS));
     c.a = st.in32(bn_a, Cout);
     c.s = st.in32(bn_s, Cout);
-    // M rows of data in buffers of max(M, 64) rows, the tail zero: what the engine's buffers hold
+    // M rows of data in buffers of max(M, 64) rows.  The tail rows M .. Mp - 1 hold the 0xFF poison (fp16 NaN), not zeros: in the engine they hold
+    // whatever the layer before left in its ping-pong buffer.  The 1 x 1 form runs gemm_tiled over all Mp rows, so it reads these rows of x and
+    // res and stores them; the gather form may fetch them for lanes past M.  None of the M rows that come back may depend on them: a valid
+    // row that does is NaN here.
     auto padded = [&](const float* src, size_t rowlen) {
-        std::vector<_Float16> h((size_t)Mp * rowlen, (_Float16)0.f);
+        std::vector<_Float16> h((size_t)Mp * rowlen);
+        memset(h.data(), 0xFF, h.size() * sizeof(_Float16));
         for (size_t i = 0; i < (size_t)M * rowlen; ++i) h[i] = (_Float16)src[i];
         return st.in16(h);
     };
     const auto dx = padded(x, Cin);
     const auto dr = res ? padded(res, Cout) : Buf<half_t>{};
-    const auto dy = st.raw<half_t>((size_t)Mp * Cout);
+    // guard: the taller of CONV_GUARD_ROWS image rows and one m tile of gemm_tiled, behind the max(M, 64) rows and in front of them
+    const size_t gy = std::max(CONV_GUARD_ROWS * W, GEMM_GUARD_ROWS) * Cout;
+    const auto dy = st.poisoned<half_t>((size_t)Mp * Cout, gy, gy);
     TRY(st.run([&] {
-        if (form == 1) return accepted(launch_rn_conv3x3(dx, c.w, c.a, c.s, B, H, W, Cin, Cout, dy, 0) != nullptr, "rn_conv3x3: refused (Cin % 16, Cout % 32)");
+        if (form == 1) return accepted(ran_kernel(launch_rn_conv3x3(dx, c.w, c.a, c.s, B, H, W, Cin, Cout, dy, 0)) != nullptr, "rn_conv3x3: refused (Cin % 16, Cout % 32)");
         const GemmParams g = KS == 1 ? rn_gemm_1x1(dx, c, M, H * W, dr, relu, dy) : rn_gemm_3x3(dx, c, B, H, W, dy);
-        return accepted(launch_gemm_tiled(g, 0) != nullptr, "rn_conv_bn: gemm_tiled refused the shape (Cin and Cout multiples of 64)");
+        return accepted(ran_kernel(launch_gemm_tiled(g, 0)) != nullptr, "rn_conv_bn: gemm_tiled refused the shape (Cin and Cout multiples of 64)");
     }));
+    TRY(st.intact_named(dy, "rn_conv_bn: out"));
     return st.fetch(out, dy, (size_t)M * Cout);      // (the rows of data)
 }
 
 extern "C" int glass_op_rn_tokens(int32_t device, int32_t B, int32_t HW, int32_t C, const float* x, const float* pos, float* out) {
     OPREQ(x && pos && out && B > 0 && HW > 0 && C > 0, "bad argument");
+    g_last_kernel.clear();
     Stage st(device);
     const auto dx = st.in16(x, (size_t)B * HW * C);
     const auto dp = st.in32(pos, (size_t)(HW + 1) * C);
-    const auto dy = st.raw<half_t>((size_t)B * (HW + 1) * C);
-    TRY(st.run([&] { launch_rn_attnpool_tokens(dx, dp, B, HW, C, dy, 0); }));
+    const auto dy = st.poisoned<half_t>((size_t)B * (HW + 1) * C, C, C);      // (guard: one token row)
+    TRY(st.run([&] {
+        launch_rn_attnpool_tokens(dx, dp, B, HW, C, dy, 0);
+        ran_kernel("rn_attnpool_tokens_kernel");
+    }));
+    TRY(st.intact_named(dy, "rn_tokens: out"));
     return st.fetch(out, dy);
 }
 
 // ---- perceptual objective (lpips.hip) ----
 extern "C" int glass_op_lpips_input(int32_t device, int32_t B, int32_t R, int32_t S, const float* y, float* out) {
     OPREQ(y && out && B > 0 && R > 0 && S > 0, "bad argument");
+    g_last_kernel.clear();
     Stage st(device);
     const auto dy = st.in32(y, (size_t)B * 3 * R * R);
-    const auto dout = st.raw<half_t>((size_t)B * S * S * 4);
-    TRY(st.run([&] { return accepted(launch_lpips_input(dy, B, R, S, dout, 0), "lpips_input: refused (R a multiple of S, box R / S at most 8)"); }));
+    const size_t go = CONV_GUARD_ROWS * S * 4;
+    const auto dout = st.poisoned<half_t>((size_t)B * S * S * 4, go, go);
+    TRY(st.run([&] { return accepted(launch_lpips_input(dy, B, R, S, dout, 0) && ran_kernel("lpips_input_kernel"), "lpips_input: refused (R a multiple of S, box R / S at most 8)"); }));
+    TRY(st.intact_named(dout, "lpips_input: out"));
     return st.fetch(out, dout);
 }
 
 extern "C" int glass_op_vgg_conv1(int32_t device, int32_t B, int32_t S, const float* x, const float* w, const float* bias, float* out) {
     OPREQ(x && w && bias && out && B > 0 && S > 0, "bad argument");
+    g_last_kernel.clear();
     Stage st(device);
     std::vector<_Float16> wt((size_t)27 * 64);
     for (int o = 0; o < 64; ++o)
@@ -1381,17 +1411,22 @@ extern "C" int glass_op_vgg_conv1(int32_t device, int32_t B, int32_t S, const fl
     const auto dx = st.in16(x, (size_t)B * S * S * 4);
     const auto dw = st.in16(wt);
     const auto db = st.in32(bias, 64);
-    const auto dy = st.raw<half_t>((size_t)B * S * S * 64);
-    TRY(st.run([&] { return accepted(launch_vgg_conv1(dx, dw, db, B, S, dy, 0), "vgg_conv1: refused"); }));
+    const size_t gy = CONV_GUARD_ROWS * S * 64;
+    const auto dy = st.poisoned<half_t>((size_t)B * S * S * 64, gy, gy);
+    TRY(st.run([&] { return accepted(launch_vgg_conv1(dx, dw, db, B, S, dy, 0) && ran_kernel("vgg_conv1_kernel"), "vgg_conv1: refused"); }));
+    TRY(st.intact_named(dy, "vgg_conv1: out"));
     return st.fetch(out, dy);
 }
 
 extern "C" int glass_op_maxpool2(int32_t device, int32_t B, int32_t H, int32_t W, int32_t C, const float* x, float* out) {
     OPREQ(x && out && B > 0 && H > 0 && W > 0 && C > 0, "bad argument");
+    g_last_kernel.clear();
     Stage st(device);
     const auto dx = st.in16(x, (size_t)B * H * W * C);
-    const auto dy = st.raw<half_t>((size_t)B * (H / 2) * (W / 2) * C);
-    TRY(st.run([&] { return accepted(launch_maxpool2(dx, B, H, W, C, dy, 0), "maxpool2: refused (even H and W, C a multiple of 8)"); }));
+    const size_t gy = CONV_GUARD_ROWS * (W / 2) * C;
+    const auto dy = st.poisoned<half_t>((size_t)B * (H / 2) * (W / 2) * C, gy, gy);
+    TRY(st.run([&] { return accepted(launch_maxpool2(dx, B, H, W, C, dy, 0) && ran_kernel("maxpool2_kernel"), "maxpool2: refused (even H and W, C a multiple of 8)"); }));
+    TRY(st.intact_named(dy, "maxpool2: out"));
     return st.fetch(out, dy);
 }
 
@@ -1402,7 +1437,7 @@ extern "C" int glass_op_lpips_head(int32_t device, int32_t n, int32_t HW, int32_
     const size_t map = (size_t)HW * C, nblk = ((size_t)HW + GLASS_LPIPS_PIXB - 1) / GLASS_LPIPS_PIXB;
     const auto d0 = st.in16(x0, (size_t)n * map), d1 = st.in16(x1, (shared_x1 ? 1 : (size_t)n) * map);
     const auto dl = st.in32(lin, C);
-    const auto part = st.raw<float>((size_t)n * nblk);
+    const auto part = st.poisoned<float>((size_t)n * nblk);      // NaN: a workgroup sum the head does not write shows in the distance
     const auto dd = st.poisoned<float>(n);
     TRY(st.run([&] { return accepted(launch_lpips_head(d0, d1, shared_x1 ? 0 : (long long)map, dl, n, HW, C, part, 1, dd, 0), "lpips_head: refused (C one of 64, 128, 256, 512)"); }));
     return st.fetch(out, dd);

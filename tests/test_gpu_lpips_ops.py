@@ -1,15 +1,18 @@
 """The perceptual objective's own kernels (csrc/lpips.hip), each alone through its diagnostic op against tests/lpips_ref.py.
 
 Bars: the input kernel sums the box in fp32 and rounds once to fp16 — at most one fp16 ulp of the float64 value; the first convolution is
-an fp16-output conv op of the project (4e-3 * max|ref|, tests/test_gpu_ops.py); the max pool is exact; the head is all fp32 on fp16 inputs
-it reads exactly — 1e-5 relative (fp32 sums of at most 512 x 1024 terms of one sign)."""
+held to tests/tower_ops_ref.py's error bound per element (27 fp32 FMAs, the bias, one fp16 store); the max pool is exact; the head is all
+fp32 on fp16 inputs it reads exactly — 1e-5 relative (fp32 sums of at most 512 x 1024 terms of one sign).  The twelve gather convolutions
+of the walk are tests/test_gpu_tower_ops.py's "vgg" cases."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import lpips_ref as R
+import tower_ops_ref as T
 from clip_glass_amd import ops, synth
+from util import check_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -48,12 +51,11 @@ def test_vgg_conv1(S):
     got = ops.vgg_conv1(x, w, b)
     ref = torch.relu(F.conv2d(torch.tensor(x[..., :3].transpose(0, 3, 1, 2), dtype=torch.float64), torch.tensor(w, dtype=torch.float64),
                               torch.tensor(b, dtype=torch.float64), padding=1)).numpy().transpose(0, 2, 3, 1)
-    assert got.shape == ref.shape == (B, S, S, 64)
-    bar = 4e-3 * np.abs(ref).max()
+    assert got.shape == ref.shape == (B, S, S, 64) and ops.last_kernel() == "vgg_conv1_kernel"
+    ref64, tol = T.conv_bn_ref(x[..., :3], w, np.ones(64), b, mfma=False)
+    assert np.abs(ref64 - ref).max() <= 1e-12 * np.abs(ref).max()      # (the bound's reference is the float64 conv above)
     for name, sl in (("all", np.s_[:]), ("top", np.s_[:, 0]), ("bottom", np.s_[:, -1]), ("left", np.s_[:, :, 0]), ("right", np.s_[:, :, -1])):
-        err = np.abs(got[sl] - ref[sl]).max()
-        print("vgg_conv1 S%d %s: max err %.3e (bar %.3e)" % (S, name, err, bar))
-        assert err <= bar
+        check_bound("vgg_conv1 S%d %s" % (S, name), got[sl], ref64[sl], tol[sl])
     assert (ref > 0).mean() > 0.2 and (ref == 0).mean() > 0.2       # both sides of the ReLU
 
 
