@@ -4,6 +4,9 @@ The library is built in-tree by `__graft_entry__.build()` / `make -C clip_glass_
 There is NO CPU fallback: if the shared library is missing or the HIP device is
 absent, construction raises (the reference would `sys.exit(1)` on missing weights,
 models.py:18-20,93-101; here errors surface as RuntimeError with glass_last_error()).
+
+The C side of every function is one entry of SIGNATURES (RESTYPES where it does not return int) and the three structs are mirrored once;
+tests/test_engine_signatures.py holds all of it against the header's text.
 """
 import ctypes as C
 import os
@@ -18,6 +21,8 @@ GEN_STYLEGAN2, GEN_BIGGAN_DEEP = 0, 1
 
 
 class GlassConfig(C.Structure):
+    """glass_config, every field in header order.  Each feature appended its fields last and zero means off, so a library built before a
+    field (an A/B build loaded through GLASS_LIB) reads a prefix of this struct."""
     _fields_ = [("device", C.c_int32), ("n_blocks", C.c_int32), ("channels", C.c_int32 * MAX_BLOCKS),
                 ("latent_size", C.c_int32), ("mapping_layers", C.c_int32), ("batch_size", C.c_int32),
                 ("mbstd_group", C.c_int32), ("use_discriminator", C.c_int32), ("n_obj", C.c_int32),
@@ -29,31 +34,11 @@ class GlassConfig(C.Structure):
                 ("bg_n_layers", C.c_int32), ("bg_layers", (C.c_int32 * 3) * MAX_BG_LAYERS),
                 ("bg_attention_pos", C.c_int32), ("bg_n_stats", C.c_int32), ("bg_eps", C.c_float),
                 ("bg_truncation", C.c_float),
-                ("clip_resize", C.c_int32), ("clip_normalize", C.c_int32)]
-
-
-class GlassConfigResnet(C.Structure):
-    """glass_config as the library defines it now: GlassConfig's fields, then the ResNet tower's, appended as clip_resize was (zero: a ViT).
-    GlassConfig itself stays the struct up to clip_normalize — what a library built before the ResNet towers reads of this one."""
-    _fields_ = GlassConfig._fields_ + [("clip_arch", C.c_int32), ("clip_rn_layers", C.c_int32 * 4)]
-
-
-class GlassConfigLpips(C.Structure):
-    """glass_config as the library defines it now: GlassConfigResnet's fields, then the perceptual objective's, appended as the ResNet
-    tower's were (zero: off).  The two shorter structs stay what libraries built before each addition read."""
-    _fields_ = GlassConfigResnet._fields_ + [("lpips_size", C.c_int32), ("lpips_lambda", C.c_float)]
-
-
-class GlassConfigPrompt(C.Structure):
-    """glass_config as the library defines it now: GlassConfigLpips's fields, then the prompt sets' column count, appended as the others
-    were (zero: one similarity column).  The shorter structs stay what libraries built before each addition read."""
-    _fields_ = GlassConfigLpips._fields_ + [("sim_columns", C.c_int32)]
-
-
-class GlassConfigEdit(C.Structure):
-    """glass_config as the library defines it now: GlassConfigPrompt's fields, then the latent anchor's (include/glass.h "Image editing"),
-    appended as the others were (zero: off).  The shorter structs stay what libraries built before each addition read."""
-    _fields_ = GlassConfigPrompt._fields_ + [("anchor", C.c_int32), ("anchor_lambda", C.c_float)]
+                ("clip_resize", C.c_int32), ("clip_normalize", C.c_int32),
+                ("clip_arch", C.c_int32), ("clip_rn_layers", C.c_int32 * 4),
+                ("lpips_size", C.c_int32), ("lpips_lambda", C.c_float),
+                ("sim_columns", C.c_int32),
+                ("anchor", C.c_int32), ("anchor_lambda", C.c_float)]
 
 
 PROMPT_MODES = {"sum": 0, "pareto": 1}      # include/glass.h "Prompt sets"
@@ -70,6 +55,96 @@ class ProfRow(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+# The C signature of every function of include/glass.h, argument by argument, in header order.  glass_engine* is an opaque handle (h);
+# load_library() applies the table once; tests/test_engine_signatures.py holds it, RESTYPES and the three structs against the header.
+i32, i64, u64, f32, f64, h, cp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_void_p, C.c_char_p
+fp, ip, lp, dp = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+SIGNATURES = {
+    "glass_last_error": [],
+    "glass_version": [],
+    "glass_clip_geometry_supported": [i32] * 6,
+    "glass_clip_resnet_supported": [ip, i32, i32, i32],
+    "glass_clip_preprocess_supported": [i32] * 4,
+    "glass_clip_views_supported": [i32] * 6,
+    "glass_host_clip_view_boxes": [u64, i32, i32, i32, i32, i32, i32, ip],
+    "glass_lpips_supported": [i32, i32],
+    "glass_prompt_set_supported": [i32, i32, i32],
+    "glass_engine_set_targets": [h, fp, fp, i32, i32, i32],
+    "glass_engine_last_set_details": [h, i32, fp],
+    "glass_engine_encode_generated": [h, fp, i32, fp],
+    "glass_edit_supported": [i32, i32, i32, i32, i32, i32, f32, i32],
+    "glass_engine_set_anchor": [h, fp],
+    "glass_engine_last_anchor": [h, i32, fp],
+    "glass_engine_set_direction_source": [h, fp],
+    "glass_engine_last_direction_source": [h, fp],
+    "glass_engine_create": [C.POINTER(GlassConfig), C.POINTER(h)],
+    "glass_engine_set_lpips_target": [h, fp, i32],
+    "glass_engine_lpips": [h, fp, fp, i32, fp],
+    "glass_engine_last_lpips": [h, i32, fp],
+    "glass_engine_set_clip_views": [h, i32, i32, i32, i32],
+    "glass_engine_destroy": [h],
+    "glass_host_layer_psi": [i32, f32, i32, fp],
+    "glass_engine_set_latent_space": [h, i32],
+    "glass_engine_set_truncation": [h, f32, i32],
+    "glass_engine_latent_row": [h, ip, ip],
+    "glass_engine_map_latents": [h, fp, i32, fp],
+    "glass_subspace_supported": [i32, i32, i32, i32, ip, cp, i32],
+    "glass_engine_set_subspace_shape": [h, i32, i32],
+    "glass_engine_set_subspace": [h, ip, fp, fp],
+    "glass_engine_expand_latents": [h, fp, i32, fp],
+    "glass_engine_load_tensor": [h, cp, fp, i32, lp],
+    "glass_engine_finalize": [h],
+    "glass_engine_set_target": [h, fp, i32],
+    "glass_engine_encode_text": [h, ip, i32, i32, fp],
+    "glass_engine_encode_image": [h, fp, i32, fp],
+    "glass_engine_gpt2_decode": [h, ip, i32, i32, i32, ip],
+    "glass_engine_gpt2_sample": [h, ip, i32, i32, i32, f32, i32, u64, i32, i32, i32, ip],
+    "glass_engine_evaluate": [h, fp, i32, i32, i32, C.POINTER(GlassNoise), fp],
+    "glass_engine_last_details": [h, i32, fp, fp, fp],
+    "glass_engine_last_view_details": [h, i32, fp, fp, ip],
+    "glass_engine_generate": [h, fp, i32, i32, i32, C.POINTER(GlassNoise), fp],
+    "glass_engine_last_gpu_ms": [h, fp],
+    "glass_engine_last_F_device": [h, i32, C.POINTER(C.c_void_p)],
+    "glass_engine_set_profiling": [h, i32],
+    "glass_engine_set_profile_filter": [h, cp],
+    "glass_engine_get_profile": [h, C.POINTER(ProfRow), i32, ip],
+    "glass_engine_set_overlap": [h, i32],
+    "glass_engine_set_biggan_tap": [h, i32],
+    "glass_engine_get_biggan_tap": [h, fp, i64, ip],
+    "glass_search_supported": [i32] * 4,
+    "glass_engine_set_search": [h, i32, i32, f64, f64, f64, f64, f64, u64],
+    "glass_engine_set_search_operators": [h, f64, f64, f64, f64, f64, u64],
+    "glass_search_mixed_supported": [i32] * 5,
+    "glass_engine_set_search_mixed": [h, i32, i32, i32, f64, f64, f64, f64, f64, f64, f64, u64],
+    "glass_engine_set_search_operators_mixed": [h, f64, f64, f64, f64, f64, f64, f64, u64],
+    "glass_engine_search_init": [h, fp],
+    "glass_engine_search_vary": [h, i32],
+    "glass_engine_search_evaluate": [h, i32, i32, i32],
+    "glass_engine_search_survive": [h, i32],
+    "glass_engine_search_step": [h, i32],
+    "glass_engine_search_read": [h, fp, fp, ip, dp, fp, fp, ip, ip],
+    "glass_engine_latent_uploads": [h, lp, lp],
+    "glass_search_islands_supported": [i32] * 7,
+    "glass_engine_set_search_islands": [h, i32, i32, i32],
+    "glass_engine_set_island_weights": [h, fp, i32, i32],
+    "glass_engine_search_migrate": [h, i32],
+    "glass_engine_search_read_islands": [h, ip],
+    "glass_engine_search_init_cma": [h, dp, dp, f64],
+    "glass_engine_search_read_cma": [h, dp, dp, dp, dp, dp, ip, fp, fp],
+    "glass_device_info": [i32, cp, i32, ip, lp],
+}
+RESTYPES = {"glass_last_error": cp, "glass_version": cp, "glass_engine_destroy": None}      # every other function returns int
+
+
+def bind(lib, signatures, restypes={}):
+    """Give every function of the table that `lib` exports its C signature.  A name the build lacks is skipped: an older build of
+    libglass.so loaded through GLASS_LIB (the A/B knob) predates the newer functions, and calling one of those fails by name."""
+    for name, argtypes in signatures.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restypes.get(name, C.c_int)
+
+
 _lib = None
 
 
@@ -83,100 +158,7 @@ def load_library(path=None):
         raise RuntimeError("libglass.so not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "or `make -C clip_glass_amd/csrc` — there is no CPU fallback" % path)
     lib = C.CDLL(path)
-    fp = C.POINTER(C.c_float)
-    lib.glass_last_error.restype = C.c_char_p
-    lib.glass_version.restype = C.c_char_p
-    lib.glass_engine_create.argtypes = [C.POINTER(GlassConfigEdit), C.POINTER(C.c_void_p)]
-    if hasattr(lib, "glass_clip_geometry_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_clip_geometry_supported.argtypes = [C.c_int32] * 6
-    if hasattr(lib, "glass_clip_preprocess_supported"):   # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_clip_preprocess_supported.argtypes = [C.c_int32] * 4
-    if hasattr(lib, "glass_clip_resnet_supported"):     # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_clip_resnet_supported.argtypes = [C.POINTER(C.c_int32)] + [C.c_int32] * 3
-    if hasattr(lib, "glass_clip_views_supported"):      # (absent from older A/B builds loaded through GLASS_LIB)
-        ip = C.POINTER(C.c_int32)
-        lib.glass_clip_views_supported.argtypes = [C.c_int32] * 6
-        lib.glass_host_clip_view_boxes.argtypes = [C.c_uint64] + [C.c_int32] * 6 + [ip]
-        lib.glass_engine_set_clip_views.argtypes = [C.c_void_p] + [C.c_int32] * 4
-        lib.glass_engine_last_view_details.argtypes = [C.c_void_p, C.c_int32, fp, fp, ip]
-    if hasattr(lib, "glass_engine_set_latent_space"):   # (absent from older A/B builds loaded through GLASS_LIB)
-        ip = C.POINTER(C.c_int32)
-        lib.glass_host_layer_psi.argtypes = [C.c_int32, C.c_float, C.c_int32, fp]
-        lib.glass_engine_set_latent_space.argtypes = [C.c_void_p, C.c_int32]
-        lib.glass_engine_set_truncation.argtypes = [C.c_void_p, C.c_float, C.c_int32]
-        lib.glass_engine_latent_row.argtypes = [C.c_void_p, ip, ip]
-        lib.glass_engine_map_latents.argtypes = [C.c_void_p, fp, C.c_int32, fp]
-    if hasattr(lib, "glass_subspace_supported"):        # (absent from older A/B builds loaded through GLASS_LIB)
-        ip = C.POINTER(C.c_int32)
-        lib.glass_subspace_supported.argtypes = [C.c_int32] * 4 + [ip, C.c_char_p, C.c_int32]
-        lib.glass_engine_set_subspace_shape.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.glass_engine_set_subspace.argtypes = [C.c_void_p, ip, fp, fp]
-        lib.glass_engine_expand_latents.argtypes = [C.c_void_p, fp, C.c_int32, fp]
-    if hasattr(lib, "glass_lpips_supported"):           # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_lpips_supported.argtypes = [C.c_int32] * 2
-        lib.glass_engine_set_lpips_target.argtypes = [C.c_void_p, fp, C.c_int32]
-        lib.glass_engine_lpips.argtypes = [C.c_void_p, fp, fp, C.c_int32, fp]
-        lib.glass_engine_last_lpips.argtypes = [C.c_void_p, C.c_int32, fp]
-    if hasattr(lib, "glass_prompt_set_supported"):      # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_prompt_set_supported.argtypes = [C.c_int32] * 3
-        lib.glass_engine_set_targets.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.c_int32]
-        lib.glass_engine_last_set_details.argtypes = [C.c_void_p, C.c_int32, fp]
-        lib.glass_engine_encode_generated.argtypes = [C.c_void_p, fp, C.c_int32, fp]
-    if hasattr(lib, "glass_edit_supported"):            # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_edit_supported.argtypes = [C.c_int32] * 6 + [C.c_float, C.c_int32]
-        lib.glass_engine_set_anchor.argtypes = [C.c_void_p, fp]
-        lib.glass_engine_last_anchor.argtypes = [C.c_void_p, C.c_int32, fp]
-        lib.glass_engine_set_direction_source.argtypes = [C.c_void_p, fp]
-        lib.glass_engine_last_direction_source.argtypes = [C.c_void_p, fp]
-    if hasattr(lib, "glass_search_supported"):          # (absent from older A/B builds loaded through GLASS_LIB)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        lib.glass_search_supported.argtypes = [C.c_int32] * 4
-        lib.glass_engine_set_search.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_double] * 5 + [C.c_uint64]
-        lib.glass_engine_set_search_operators.argtypes = [C.c_void_p] + [C.c_double] * 5 + [C.c_uint64]
-        lib.glass_engine_search_init.argtypes = [C.c_void_p, fp]
-        lib.glass_engine_search_vary.argtypes = [C.c_void_p, C.c_int32]
-        lib.glass_engine_search_evaluate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        lib.glass_engine_search_survive.argtypes = [C.c_void_p, C.c_int32]
-        lib.glass_engine_search_step.argtypes = [C.c_void_p, C.c_int32]
-        lib.glass_engine_search_read.argtypes = [C.c_void_p, fp, fp, ip, dp, fp, fp, ip, ip]
-        lib.glass_engine_latent_uploads.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    if hasattr(lib, "glass_search_mixed_supported"):    # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_search_mixed_supported.argtypes = [C.c_int32] * 5
-        lib.glass_engine_set_search_mixed.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_double] * 7 + [C.c_uint64]
-        lib.glass_engine_set_search_operators_mixed.argtypes = [C.c_void_p] + [C.c_double] * 7 + [C.c_uint64]
-    if hasattr(lib, "glass_engine_search_init_cma"):    # (absent from older A/B builds loaded through GLASS_LIB)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        lib.glass_engine_search_init_cma.argtypes = [C.c_void_p, dp, dp, C.c_double]
-        lib.glass_engine_search_read_cma.argtypes = [C.c_void_p, dp, dp, dp, dp, dp, ip, fp, fp]
-    if hasattr(lib, "glass_search_islands_supported"):  # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_search_islands_supported.argtypes = [C.c_int32] * 7
-        lib.glass_engine_set_search_islands.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        lib.glass_engine_set_island_weights.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32]
-        lib.glass_engine_search_migrate.argtypes = [C.c_void_p, C.c_int32]
-        lib.glass_engine_search_read_islands.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-    lib.glass_engine_destroy.argtypes = [C.c_void_p]
-    lib.glass_engine_destroy.restype = None
-    lib.glass_engine_load_tensor.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int32, C.POINTER(C.c_int64)]
-    lib.glass_engine_finalize.argtypes = [C.c_void_p]
-    lib.glass_engine_set_target.argtypes = [C.c_void_p, fp, C.c_int32]
-    lib.glass_engine_encode_text.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, fp]
-    lib.glass_engine_encode_image.argtypes = [C.c_void_p, fp, C.c_int32, fp]
-    lib.glass_engine_gpt2_decode.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    if hasattr(lib, "glass_engine_gpt2_sample"):        # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_engine_gpt2_sample.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
-                                                 C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    lib.glass_engine_evaluate.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GlassNoise), fp]
-    lib.glass_engine_generate.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GlassNoise), fp]
-    lib.glass_engine_last_details.argtypes = [C.c_void_p, C.c_int32, fp, fp, fp]
-    lib.glass_engine_last_gpu_ms.argtypes = [C.c_void_p, fp]
-    if hasattr(lib, "glass_engine_last_F_device"):      # (absent from older A/B builds loaded through GLASS_LIB)
-        lib.glass_engine_last_F_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
-    lib.glass_engine_set_profiling.argtypes = [C.c_void_p, C.c_int32]
-    lib.glass_engine_set_overlap.argtypes = [C.c_void_p, C.c_int32]
-    lib.glass_engine_set_biggan_tap.argtypes = [C.c_void_p, C.c_int32]
-    lib.glass_engine_set_profile_filter.argtypes = [C.c_void_p, C.c_char_p]
-    lib.glass_engine_get_profile.argtypes = [C.c_void_p, C.POINTER(ProfRow), C.c_int32, C.POINTER(C.c_int32)]
-    lib.glass_device_info.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    bind(lib, SIGNATURES, RESTYPES)
     _lib = lib
     return lib
 
@@ -194,40 +176,38 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _verdict(rule, *args):
+    """(True, "") or (False, glass_last_error()) from glass_<rule>_supported(*args): the library's own rules, host only."""
+    lib = load_library()
+    rc = getattr(lib, "glass_%s_supported" % rule)(*args)
+    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+
+
 def clip_geometry_supported(geometry):
     """(ok, message) for a CLIP image tower (width, layers, heads, patch, input_res, embed): the library's own rule, the one
     glass_engine_create applies.  Host only: needs the built library, not a GPU."""
-    lib = load_library()
-    rc = lib.glass_clip_geometry_supported(*[int(v) for v in geometry])
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("clip_geometry", *[int(v) for v in geometry])
 
 
 def clip_preprocess_supported(gen_res, clip_res, clip_resize, clip_normalize):
     """(ok, message) for the CLIP preprocessing fields (clip_resize, clip_normalize) from a gen_res px image to clip_res: the library's
     own rule, the one glass_engine_create applies.  Host only."""
-    lib = load_library()
-    rc = lib.glass_clip_preprocess_supported(int(gen_res), int(clip_res), int(clip_resize), int(clip_normalize))
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("clip_preprocess", int(gen_res), int(clip_res), int(clip_resize), int(clip_normalize))
 
 
 def clip_resnet_supported(geometry):
     """(ok, message) for a CLIP ResNet image tower (layers4, width, input_res, embed): the library's own rule, the one
     glass_engine_create applies.  Host only: needs the built library, not a GPU."""
-    lib = load_library()
     layers, width, res, embed = geometry
     if len(layers) != 4:
         return False, "unsupported CLIP ResNet geometry: layers must hold four stage depths, got %r" % (tuple(layers),)
-    arr = (C.c_int32 * 4)(*[int(v) for v in layers])
-    rc = lib.glass_clip_resnet_supported(arr, int(width), int(res), int(embed))
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("clip_resnet", (C.c_int32 * 4)(*[int(v) for v in layers]), int(width), int(res), int(embed))
 
 
 def lpips_supported(gen_res, lpips_size):
     """(ok, message) for the perceptual objective at VGG input side lpips_size on a gen_res px generator (0: the side alone): the
     library's own rule, the one glass_engine_create applies.  Host only."""
-    lib = load_library()
-    rc = lib.glass_lpips_supported(int(gen_res), int(lpips_size))
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("lpips", int(gen_res), int(lpips_size))
 
 
 def lpips_n_obj(use_discriminator, lpips_lambda):
@@ -247,9 +227,7 @@ def prompt_mode_id(mode):
 def prompt_set_supported(n_entries, mode="sum", sim_columns=0):
     """(ok, message) for a prompt set of n_entries in `mode` on an engine with `sim_columns`: the library's own rule, the one
     glass_engine_set_targets applies.  Host only."""
-    lib = load_library()
-    rc = lib.glass_prompt_set_supported(int(n_entries), prompt_mode_id(mode), int(sim_columns))
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("prompt_set", int(n_entries), prompt_mode_id(mode), int(sim_columns))
 
 
 def prompt_n_obj(sim_columns, use_discriminator, lpips_column=False):
@@ -268,12 +246,10 @@ def edit_supported(generator="stylegan2", n_blocks=9, sim_columns=0, use_discrim
                    n_obj=1):
     """(ok, message) for the latent anchor's fields on an engine of that kind ("stylegan2", "biggan", or None: no generator — n_blocks is
     then taken as 0): the library's own rule (glass_edit_supported), the one glass_engine_create applies.  Host only."""
-    lib = load_library()
     gen = GEN_BIGGAN_DEEP if generator == "biggan" else GEN_STYLEGAN2
     nb = int(n_blocks) if generator == "stylegan2" else 0
-    rc = lib.glass_edit_supported(gen, nb, int(sim_columns), int(bool(use_discriminator)), int(bool(lpips_column)), int(anchor), float(anchor_lambda),
-                                  int(n_obj))
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("edit", gen, nb, int(sim_columns), int(bool(use_discriminator)), int(bool(lpips_column)), int(anchor), float(anchor_lambda),
+                    int(n_obj))
 
 
 def clip_view_permille(fraction):
@@ -294,9 +270,7 @@ def clip_views_tower_rows(clip=None, clip_resnet=None):
 def clip_views_supported(max_pop, tokens, width, clip_resize, views, min_permille):
     """(ok, message) for crop views over a tower of `tokens` rows x `width` per image (clip_views_tower_rows): the library's own rule, the
     one glass_engine_set_clip_views applies.  Host only."""
-    lib = load_library()
-    rc = lib.glass_clip_views_supported(int(max_pop), int(tokens), int(width), int(clip_resize), int(views), int(min_permille))
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("clip_views", int(max_pop), int(tokens), int(width), int(clip_resize), int(views), int(min_permille))
 
 
 def host_clip_view_boxes(seed, generation, views, gen_res, min_permille, flip, fixed):
@@ -319,9 +293,7 @@ def search_supported(pop, n_var, n_obj, algorithm):
     (glass_search_supported), the one glass_engine_set_search and finalize apply.  Host only."""
     if algorithm not in SEARCH_ALGORITHMS:
         return False, "device search: unknown algorithm %r (expected one of %s)" % (algorithm, ", ".join(SEARCH_ALGORITHMS))
-    lib = load_library()
-    rc = lib.glass_search_supported(int(pop), int(n_var), int(n_obj), SEARCH_ALGORITHMS[algorithm])
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("search", int(pop), int(n_var), int(n_obj), SEARCH_ALGORITHMS[algorithm])
 
 
 SEARCH_MAX_ISLANDS = 64
@@ -333,10 +305,8 @@ def search_islands_supported(islands, pop, n_var, n_obj, algorithm, migrate_ever
     only."""
     if algorithm not in SEARCH_ALGORITHMS:
         return False, "device search: unknown algorithm %r (expected one of %s)" % (algorithm, ", ".join(SEARCH_ALGORITHMS))
-    lib = load_library()
-    rc = lib.glass_search_islands_supported(int(islands), int(pop), int(n_var), int(n_obj), SEARCH_ALGORITHMS[algorithm], int(migrate_every),
-                                            int(migrants))
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("search_islands", int(islands), int(pop), int(n_var), int(n_obj), SEARCH_ALGORITHMS[algorithm], int(migrate_every),
+                    int(migrants))
 
 
 SEARCH_MAX_BITS = 4096
@@ -347,9 +317,7 @@ def mixed_search_supported(pop, n_real, n_bits, n_obj, algorithm):
     (glass_search_mixed_supported), the one glass_engine_set_search_mixed and finalize apply.  Host only."""
     if algorithm not in SEARCH_ALGORITHMS:
         return False, "device search: unknown algorithm %r (expected one of %s)" % (algorithm, ", ".join(SEARCH_ALGORITHMS))
-    lib = load_library()
-    rc = lib.glass_search_mixed_supported(int(pop), int(n_real), int(n_bits), int(n_obj), SEARCH_ALGORITHMS[algorithm])
-    return (True, "") if rc == 0 else (False, lib.glass_last_error().decode())
+    return _verdict("search_mixed", int(pop), int(n_real), int(n_bits), int(n_obj), SEARCH_ALGORITHMS[algorithm])
 
 
 LATENT_SPACES = {"z": 0, "w": 1, "w+": 2, "sub": 3}     # GLASS_LATENT_Z / _W / _WPLUS / _SUB
@@ -434,7 +402,7 @@ class Engine:
         latent_space "sub" with subspace_shape = (G, K) (include/glass.h "Subspace latent space"): a row is G * K coefficients of K
         directions of W for each of G groups of style layers; set_subspace(layer_group, basis, base) after finalize() gives the directions."""
         self.lib = load_library()
-        cfg = GlassConfigEdit()
+        cfg = GlassConfig()
         cfg.anchor, cfg.anchor_lambda = int(bool(anchor)), float(anchor_lambda)
         cfg.sim_columns = int(sim_columns)
         cfg.lpips_size, cfg.lpips_lambda = int(lpips_size), float(lpips_lambda)
@@ -481,18 +449,12 @@ class Engine:
         self._h = C.c_void_p()
         _check(self.lib, self.lib.glass_engine_create(C.byref(cfg), C.byref(self._h)))
         self.clip_views = int(clip_views)
-        if self.clip_views:
-            rc = self.lib.glass_engine_set_clip_views(self._h, self.clip_views, clip_view_permille(clip_view_min), int(bool(clip_view_flip)),
-                                                      int(bool(clip_view_fixed)))
-            if rc != 0:
-                msg = self.lib.glass_last_error().decode()
-                self.close()
-                raise RuntimeError("libglass error %d: %s" % (rc, msg))
-
         self.latent_space = latent_space
         try:
+            if self.clip_views:
+                self._call("set_clip_views", self.clip_views, clip_view_permille(clip_view_min), int(bool(clip_view_flip)), int(bool(clip_view_fixed)))
             if latent_space != "z":
-                _check(self.lib, self.lib.glass_engine_set_latent_space(self._h, latent_space_id(latent_space)))
+                self._call("set_latent_space", latent_space_id(latent_space))
             if latent_space == "sub" and subspace_shape is None:
                 raise ValueError('latent_space "sub" needs subspace_shape=(groups, components)')
             if subspace_shape is not None:
@@ -504,6 +466,10 @@ class Engine:
         except Exception:
             self.close()
             raise
+
+    def _call(self, name, *args):
+        """glass_engine_<name>(handle, *args); a non-zero status raises RuntimeError with glass_last_error()."""
+        _check(self.lib, getattr(self.lib, "glass_engine_" + name)(self._h, *args))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -520,18 +486,18 @@ class Engine:
     def load_tensor(self, name, array):
         a = _f32(array)
         dims = (C.c_int64 * max(a.ndim, 1))(*a.shape)
-        _check(self.lib, self.lib.glass_engine_load_tensor(self._h, name.encode(), _fp(a), a.ndim, dims))
+        self._call("load_tensor", name.encode(), _fp(a), a.ndim, dims)
 
     def load_state(self, state):
         for k, v in state.items():
             self.load_tensor(k, np.asarray(v))
 
     def finalize(self):
-        _check(self.lib, self.lib.glass_engine_finalize(self._h))
+        self._call("finalize")
 
     def set_target(self, feat):
         f = _f32(feat).reshape(-1)
-        _check(self.lib, self.lib.glass_engine_set_target(self._h, _fp(f), f.size))
+        self._call("set_target", _fp(f), f.size)
         self.n_prompts = 0
 
     # --- prompt sets -----------------------------------------------------------
@@ -541,14 +507,14 @@ class Engine:
         f, w = _f32(features), _f32(weights).reshape(-1)
         if f.ndim != 2 or f.shape[0] != w.size:
             raise ValueError("set_targets: features must be [T, clip_embed] with one weight per row, got %r and %d weights" % (f.shape, w.size))
-        _check(self.lib, self.lib.glass_engine_set_targets(self._h, _fp(f), _fp(w), f.shape[0], f.shape[1], prompt_mode_id(mode)))
+        self._call("set_targets", _fp(f), _fp(w), f.shape[0], f.shape[1], prompt_mode_id(mode))
         self.n_prompts = int(f.shape[0])
 
     def set_details(self, P):
         """Per-entry similarities [P, T] of the last evaluate() with a prompt set (the means over the views where they are on)."""
         T = int(getattr(self, "n_prompts", 0))
         out = np.empty((P, max(T, 1)), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_last_set_details(self._h, P, _fp(out)))
+        self._call("last_set_details", P, _fp(out))
         return out
 
     def encode_generated(self, images):
@@ -558,7 +524,7 @@ class Engine:
         if a.ndim != 4 or a.shape[1:] != (3, self.res, self.res):
             raise ValueError("encode_generated: images must be [n, 3, %d, %d], got %r" % (self.res, self.res, a.shape))
         out = np.empty((a.shape[0], self.cfg.clip_embed), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_encode_generated(self._h, _fp(a), a.shape[0], _fp(out)))
+        self._call("encode_generated", _fp(a), a.shape[0], _fp(out))
         return out
 
     @staticmethod
@@ -569,29 +535,29 @@ class Engine:
     def set_anchor(self, row):
         """The latent anchor: one row of the current latent space, float32 [floats_per_row].  After finalize(), on Engine(anchor=True)."""
         r = self._rows(np.asarray(row, dtype=np.float32).reshape(1, -1))
-        _check(self.lib, self.lib.glass_engine_set_anchor(self._h, _fp(r)))
+        self._call("set_anchor", _fp(r))
 
     def last_anchor(self, P):
         """The anchor distances [P] of the last evaluate()."""
         d = np.empty((P,), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_last_anchor(self._h, P, _fp(d)))
+        self._call("last_anchor", P, _fp(d))
         return d
 
     def set_direction_source(self, image):
         """The source image of the directional similarity: float32 [3, R, R] in [-1, 1] (the generator's raw range), or None: off.  While
         one is set, the entries of set_targets() are directions.  After finalize()."""
         if image is None:
-            _check(self.lib, self.lib.glass_engine_set_direction_source(self._h, None))
+            self._call("set_direction_source", None)
             return
         a = _f32(image)
         if a.shape != (3, self.res, self.res):
             raise ValueError("set_direction_source: the image must be [3, %d, %d], got %r" % (self.res, self.res, a.shape))
-        _check(self.lib, self.lib.glass_engine_set_direction_source(self._h, _fp(a)))
+        self._call("set_direction_source", _fp(a))
 
     def last_direction_source(self):
         """The unit rows [max(clip_views, 1), clip_embed] the last pass subtracted from the candidates' unit features."""
         out = np.empty((max(self.clip_views, 1), self.cfg.clip_embed), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_last_direction_source(self._h, _fp(out)))
+        self._call("last_direction_source", _fp(out))
         return out
 
     # --- perceptual objective --------------------------------------------------
@@ -601,7 +567,7 @@ class Engine:
         S = int(self.cfg.lpips_size)
         if a.shape != (3, S, S):
             raise ValueError("set_lpips_target: the image must be [3, %d, %d], got %r" % (S, S, a.shape))
-        _check(self.lib, self.lib.glass_engine_set_lpips_target(self._h, _fp(a), S))
+        self._call("set_lpips_target", _fp(a), S)
 
     def lpips(self, x0, x1):
         """LPIPS_VGG16.forward(x0, x1) on caller images float32 [n, 3, S, S] in [-1, 1], through the kernels of the pass -> [n]."""
@@ -610,37 +576,34 @@ class Engine:
         if a.ndim != 4 or a.shape[1:] != (3, S, S) or b.shape != a.shape:
             raise ValueError("lpips: both image stacks must be [n, 3, %d, %d], got %r and %r" % (S, S, a.shape, b.shape))
         out = np.empty((a.shape[0],), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_lpips(self._h, _fp(a), _fp(b), a.shape[0], _fp(out)))
+        self._call("lpips", _fp(a), _fp(b), a.shape[0], _fp(out))
         return out
 
     def last_lpips(self, P):
         """The distances [P] of the last evaluate()."""
         d = np.empty((P,), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_last_lpips(self._h, P, _fp(d)))
+        self._call("last_lpips", P, _fp(d))
         return d
 
     def encode_text(self, tokens):
         """CLIP.encode_text (clip/model.py:307-320): tokens int [n, ctx] -> float32 [n, clip_embed]."""
         t = np.ascontiguousarray(tokens, dtype=np.int32)
         out = np.empty((t.shape[0], self.cfg.clip_embed), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_encode_text(self._h, t.ctypes.data_as(C.POINTER(C.c_int32)), t.shape[0],
-                                                            t.shape[1], _fp(out)))
+        self._call("encode_text", t.ctypes.data_as(ip), t.shape[0], t.shape[1], _fp(out))
         return out
 
     def encode_image(self, images):
         """CLIP.encode_image on preprocessed images [n,3,R,R] float32 -> [n, clip_embed] (generator.py:26-27)."""
         a = _f32(images)
         out = np.empty((a.shape[0], self.cfg.clip_embed), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_encode_image(self._h, _fp(a), a.shape[0], _fp(out)))
+        self._call("encode_image", _fp(a), a.shape[0], _fp(out))
         return out
 
     def gpt2_decode(self, context, length):
         """gpt2/sample.py:21-36 with sample=False: int tokens [P, n] -> [P, n + length] (greedy, fp32)."""
         c = np.ascontiguousarray(context, dtype=np.int32)
         out = np.empty((c.shape[0], c.shape[1] + length), dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
-        _check(self.lib, self.lib.glass_engine_gpt2_decode(self._h, c.ctypes.data_as(ip), c.shape[0], c.shape[1], length,
-                                                            out.ctypes.data_as(ip)))
+        self._call("gpt2_decode", c.ctypes.data_as(ip), c.shape[0], c.shape[1], length, out.ctypes.data_as(ip))
         return out
 
     def gpt2_sample(self, context, length, temperature=0.7, top_k=40, seed=0, generation=0, first_row=0, purpose=0):
@@ -649,10 +612,8 @@ class Engine:
         separates the fitness evaluation (GPT2_SAMPLE_EVALUATE) from the save callback (GPT2_SAMPLE_SAVE) of one generation."""
         c = np.ascontiguousarray(context, dtype=np.int32)
         out = np.empty((c.shape[0], c.shape[1] + length), dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
-        _check(self.lib, self.lib.glass_engine_gpt2_sample(self._h, c.ctypes.data_as(ip), c.shape[0], c.shape[1], length, float(temperature),
-                                                            int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation), int(first_row),
-                                                            int(purpose), out.ctypes.data_as(ip)))
+        self._call("gpt2_sample", c.ctypes.data_as(ip), c.shape[0], c.shape[1], length, float(temperature), int(top_k),
+                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation), int(first_row), int(purpose), out.ctypes.data_as(ip))
         return out
 
     # --- device search (include/glass.h "Device search") ------------------------
@@ -661,37 +622,35 @@ class Engine:
         objective; eta_c, eta_m and prob_m are ignored) with scalar bounds xl / xu."""
         if algorithm not in SEARCH_ALGORITHMS:
             raise ValueError("unknown search algorithm %r: expected one of %s" % (algorithm, ", ".join(SEARCH_ALGORITHMS)))
-        _check(self.lib, self.lib.glass_engine_set_search(self._h, SEARCH_ALGORITHMS[algorithm], int(pop), float(xl), float(xu), float(eta_c),
-                                                           float(eta_m), float(prob_m), int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self._call("set_search", SEARCH_ALGORITHMS[algorithm], int(pop), float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m),
+                   int(seed) & 0xFFFFFFFFFFFFFFFF)
         self.search_pop = int(pop)
         self.search_algorithm = algorithm
 
     def set_search_operators(self, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, seed=1):
         """Any time after set_search: the values that size nothing (the bounds of a w / w+ search are known only after finalize())."""
-        _check(self.lib, self.lib.glass_engine_set_search_operators(self._h, float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m),
-                                                                     int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self._call("set_search_operators", float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m), int(seed) & 0xFFFFFFFFFFFFFFFF)
 
     def set_search_mixed(self, algorithm, pop, n_real, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, prob_x=0.2, prob_flip=0.01, seed=1):
         """Between construction and finalize(), BigGAN engines: turn the device search on for `pop` mixed rows — n_real (= z_dim) real
         columns with scalar bounds xl / xu, then the class bits, varied by HUX (prob_x per mating) and bit-flip (prob_flip per bit)."""
         if algorithm not in SEARCH_ALGORITHMS:
             raise ValueError("unknown search algorithm %r: expected one of %s" % (algorithm, ", ".join(SEARCH_ALGORITHMS)))
-        _check(self.lib, self.lib.glass_engine_set_search_mixed(self._h, SEARCH_ALGORITHMS[algorithm], int(pop), int(n_real), float(xl), float(xu),
-                                                                 float(eta_c), float(eta_m), float(prob_m), float(prob_x), float(prob_flip),
-                                                                 int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self._call("set_search_mixed", SEARCH_ALGORITHMS[algorithm], int(pop), int(n_real), float(xl), float(xu), float(eta_c), float(eta_m),
+                   float(prob_m), float(prob_x), float(prob_flip), int(seed) & 0xFFFFFFFFFFFFFFFF)
         self.search_pop = int(pop)
         self.search_n_real = int(n_real)
 
     def set_search_operators_mixed(self, xl, xu, eta_c=3.0, eta_m=3.0, prob_m=0.5, prob_x=0.2, prob_flip=0.01, seed=1):
         """Any time after set_search_mixed: the values that size nothing."""
-        _check(self.lib, self.lib.glass_engine_set_search_operators_mixed(self._h, float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m),
-                                                                           float(prob_x), float(prob_flip), int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self._call("set_search_operators_mixed", float(xl), float(xu), float(eta_c), float(eta_m), float(prob_m), float(prob_x), float(prob_flip),
+                   int(seed) & 0xFFFFFFFFFFFFFFFF)
 
     def set_search_islands(self, islands, migrate_every=0, migrants=1):
         """After set_search / set_search_mixed and before finalize() (include/glass.h "Device search: islands"): `islands` populations of pop
         rows each, island i under seed + i, in one pass per generation; the `migrants` best rows of island i - 1 replace the worst of island i
         every `migrate_every` generations (0: never).  Every search_* buffer then holds islands * pop rows, island-major."""
-        _check(self.lib, self.lib.glass_engine_set_search_islands(self._h, int(islands), int(migrate_every), int(migrants)))
+        self._call("set_search_islands", int(islands), int(migrate_every), int(migrants))
         self.search_islands = int(islands)
 
     def set_island_weights(self, weights):
@@ -701,7 +660,7 @@ class Engine:
         w = _f32(weights)
         if w.ndim != 2:
             raise ValueError("set_island_weights: weights must be [islands, T], got shape %r" % (w.shape,))
-        _check(self.lib, self.lib.glass_engine_set_island_weights(self._h, _fp(w), w.shape[0], w.shape[1]))
+        self._call("set_island_weights", _fp(w), w.shape[0], w.shape[1])
 
     def search_rows(self):
         """Rows of the device search's buffers: pop, or islands * pop."""
@@ -714,7 +673,7 @@ class Engine:
         pop = self.search_rows() if hasattr(self, "search_pop") else None      # (None: set_search was never called — the library says so)
         if pop is not None and z.shape[0] != pop:
             raise ValueError("search_init: the initial population must have exactly pop = %d rows, got %d" % (pop, z.shape[0]))
-        _check(self.lib, self.lib.glass_engine_search_init(self._h, _fp(z)))
+        self._call("search_init", _fp(z))
 
     def search_init_cma(self, mean, diag=None, sigma=1.0):
         """A "cmaes" search: the distribution of generation 0 — mean [floats_per_row], diag (None: ones) and the step sigma, float64."""
@@ -723,9 +682,7 @@ class Engine:
         d = None if diag is None else np.ascontiguousarray(diag, dtype=np.float64).reshape(-1)
         if m.size != nv or (d is not None and d.size != nv):
             raise ValueError("search_init_cma: mean and diag must hold %d values (a row of latent space %r)" % (nv, self.latent_space))
-        dp = C.POINTER(C.c_double)
-        _check(self.lib, self.lib.glass_engine_search_init_cma(self._h, m.ctypes.data_as(dp), None if d is None else d.ctypes.data_as(dp),
-                                                                float(sigma)))
+        self._call("search_init_cma", m.ctypes.data_as(dp), None if d is None else d.ctypes.data_as(dp), float(sigma))
 
     def search_read_cma(self):
         """The state of a "cmaes" search: dict(mean, diag, p_sigma, p_c float64 [floats_per_row]; sigma, ps_norm; h, finite, updated, skipped,
@@ -734,36 +691,35 @@ class Engine:
         out = {k: np.empty((nv,), np.float64) for k in ("mean", "diag", "p_sigma", "p_c")}
         sd, si = np.empty((2,), np.float64), np.empty((5,), np.int32)
         best_X, best_F = np.empty((nv,), np.float32), np.empty((1,), np.float32)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        _check(self.lib, self.lib.glass_engine_search_read_cma(self._h, *[out[k].ctypes.data_as(dp) for k in ("mean", "diag", "p_sigma", "p_c")],
-                                                                sd.ctypes.data_as(dp), si.ctypes.data_as(ip), _fp(best_X), _fp(best_F)))
+        self._call("search_read_cma", *[out[k].ctypes.data_as(dp) for k in ("mean", "diag", "p_sigma", "p_c")], sd.ctypes.data_as(dp),
+                   si.ctypes.data_as(ip), _fp(best_X), _fp(best_F))
         out.update(sigma=float(sd[0]), ps_norm=float(sd[1]), best_X=best_X, best_F=float(best_F[0]))
         out.update(zip(("h", "finite", "updated", "skipped", "updates"), (int(v) for v in si)))
         return out
 
     def search_vary(self, generation):
-        _check(self.lib, self.lib.glass_engine_search_vary(self._h, int(generation)))
+        self._call("search_vary", int(generation))
 
     def search_evaluate(self, generation, first_row=0, rows=None):
         rows = self.search_rows() - int(first_row) if rows is None else int(rows)
-        _check(self.lib, self.lib.glass_engine_search_evaluate(self._h, int(generation), int(first_row), rows))
+        self._call("search_evaluate", int(generation), int(first_row), rows)
 
     def search_survive(self, generation):
-        _check(self.lib, self.lib.glass_engine_search_survive(self._h, int(generation)))
+        self._call("search_survive", int(generation))
 
     def search_migrate(self, generation):
         """The migration behind search_survive(generation), as a phase of its own (search_step runs it itself); nothing where none is due."""
-        _check(self.lib, self.lib.glass_engine_search_migrate(self._h, int(generation)))
+        self._call("search_migrate", int(generation))
 
     def search_read_islands(self):
         """int32 [islands, 3]: per island the flagged and the non-finite rows of its last survival and the migrants it accepted last."""
         out = np.empty((getattr(self, "search_islands", 1), 3), np.int32)
-        _check(self.lib, self.lib.glass_engine_search_read_islands(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._call("search_read_islands", out.ctypes.data_as(C.POINTER(C.c_int32)))
         return out
 
     def search_step(self, generation):
         """One generation on the device: variation, the scoring pass, survival (islands: then the migration, where due); one wait at the end."""
-        _check(self.lib, self.lib.glass_engine_search_step(self._h, int(generation)))
+        self._call("search_step", int(generation))
 
     def search_read(self, *fields, islands=False):
         """dict of the named device-search buffers: "X", "F", "rank", "cd" (the population), "off_X", "off_F", "flags" (the last offspring),
@@ -778,7 +734,7 @@ class Engine:
         out = {f: np.empty(*shapes[f]) for f in fields}
         ctype = {np.float32: C.c_float, np.int32: C.c_int32, np.float64: C.c_double}
         args = [out[f].ctypes.data_as(C.POINTER(ctype[shapes[f][1]])) if f in out else None for f in shapes]
-        _check(self.lib, self.lib.glass_engine_search_read(self._h, *args))
+        self._call("search_read", *args)
         if islands:
             K = getattr(self, "search_islands", 1)
             out = {f: a if f == "counts" else a.reshape((K, self.search_pop) + a.shape[1:]) for f, a in out.items()}
@@ -787,18 +743,18 @@ class Engine:
     def latent_uploads(self):
         """(calls, rows): host-to-device latent copies the pass has made on this engine so far."""
         calls, rows = C.c_int64(), C.c_int64()
-        _check(self.lib, self.lib.glass_engine_latent_uploads(self._h, C.byref(calls), C.byref(rows)))
+        self._call("latent_uploads", C.byref(calls), C.byref(rows))
         return calls.value, rows.value
 
     # --- latent spaces / truncation -------------------------------------------
     def set_latent_space(self, name):
         """Between construction and finalize(): "z", "w", "w+" or "sub" (include/glass.h; "sub" needs set_subspace_shape after it)."""
-        _check(self.lib, self.lib.glass_engine_set_latent_space(self._h, latent_space_id(name)))
+        self._call("set_latent_space", latent_space_id(name))
         self.latent_space = name
 
     def set_subspace_shape(self, groups, components):
         """Between set_latent_space("sub") and finalize(): a row is groups * components coefficients."""
-        _check(self.lib, self.lib.glass_engine_set_subspace_shape(self._h, int(groups), int(components)))
+        self._call("set_subspace_shape", int(groups), int(components))
         self.subspace_shape = (int(groups), int(components))
 
     def set_subspace(self, layer_group, basis, base):
@@ -813,7 +769,7 @@ class Engine:
         if lg.shape != (n_lat,) or B.shape != (K, L) or b.shape != (n_lat, L):
             raise ValueError("set_subspace: layer_group [%d], basis [%d, %d] and base [%d, %d] (or [%d]) expected, got %r, %r, %r"
                              % (n_lat, K, L, n_lat, L, L, lg.shape, B.shape, b.shape))
-        _check(self.lib, self.lib.glass_engine_set_subspace(self._h, lg.ctypes.data_as(C.POINTER(C.c_int32)), _fp(B), _fp(b)))
+        self._call("set_subspace", lg.ctypes.data_as(C.POINTER(C.c_int32)), _fp(B), _fp(b))
 
     def expand_latents(self, rows):
         """The dlatents the pass makes its styles from, after truncation: rows [P, floats_per_row] of the engine's space -> float32
@@ -821,7 +777,7 @@ class Engine:
         z = self._rows(rows)
         n_lat, L = self.latent_row()[1], int(self.cfg.latent_size)
         out = np.empty((z.shape[0], n_lat, L), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_expand_latents(self._h, _fp(z), z.shape[0], _fp(out)))
+        self._call("expand_latents", _fp(z), z.shape[0], _fp(out))
         return out
 
     @staticmethod
@@ -830,14 +786,14 @@ class Engine:
 
     def set_truncation(self, psi, cutoff=None):
         """The truncation trick: dlatents = lerp(dlatent_avg, dlatents, layer_psi); psi in [0, 1], cutoff None = every layer."""
-        _check(self.lib, self.lib.glass_engine_set_truncation(self._h, float(psi), truncation_cutoff_arg(cutoff)))
+        self._call("set_truncation", float(psi), truncation_cutoff_arg(cutoff))
 
     def latent_row(self):
         """(floats_per_row, n_lat): what evaluate / generate read per row, and the number of style layers (0: not a StyleGAN2 engine)."""
         if not hasattr(self.lib, "glass_engine_latent_row"):     # (an older A/B build loaded through GLASS_LIB: z rows only)
             return int(self.cfg.latent_size), 0
         w, n = C.c_int32(), C.c_int32()
-        _check(self.lib, self.lib.glass_engine_latent_row(self._h, C.byref(w), C.byref(n)))
+        self._call("latent_row", C.byref(w), C.byref(n))
         return w.value, n.value
 
     def map_latents(self, z):
@@ -846,7 +802,7 @@ class Engine:
         if z.ndim != 2 or z.shape[1] != self.cfg.latent_size:
             raise ValueError("map_latents: z must be [P, %d], got %r" % (self.cfg.latent_size, z.shape))
         out = np.empty_like(z)
-        _check(self.lib, self.lib.glass_engine_map_latents(self._h, _fp(z), z.shape[0], _fp(out)))
+        self._call("map_latents", _fp(z), z.shape[0], _fp(out))
         return out
 
     def _rows(self, x):
@@ -874,8 +830,7 @@ class Engine:
         P = z.shape[0]
         out = np.empty((P, self.cfg.n_obj), dtype=np.float32)
         gn, keep = self._noise_arg(noise)
-        _check(self.lib, self.lib.glass_engine_evaluate(self._h, _fp(z), P, generation, first_minibatch,
-                                                         C.byref(gn) if gn is not None else None, _fp(out)))
+        self._call("evaluate", _fp(z), P, generation, first_minibatch, C.byref(gn) if gn is not None else None, _fp(out))
         del keep
         return out
 
@@ -885,8 +840,7 @@ class Engine:
         P = z.shape[0]
         out = np.empty((P, 3, self.res, self.res), dtype=np.float32)
         gn, keep = self._noise_arg(noise)
-        _check(self.lib, self.lib.glass_engine_generate(self._h, _fp(z), P, generation, first_minibatch,
-                                                         C.byref(gn) if gn is not None else None, _fp(out)))
+        self._call("generate", _fp(z), P, generation, first_minibatch, C.byref(gn) if gn is not None else None, _fp(out))
         del keep
         return out
 
@@ -894,7 +848,7 @@ class Engine:
         feat = np.empty((P, self.cfg.clip_embed), dtype=np.float32)
         dis = np.empty((P,), dtype=np.float32)
         sim = np.empty((P,), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_last_details(self._h, P, _fp(feat), _fp(dis), _fp(sim)))
+        self._call("last_details", P, _fp(feat), _fp(dis), _fp(sim))
         return dict(features=feat, dis=dis, sim=sim)
 
     def view_details(self, P):
@@ -905,7 +859,7 @@ class Engine:
         feat = np.empty((P, V, self.cfg.clip_embed), dtype=np.float32)
         sims = np.empty((P, V), dtype=np.float32)
         boxes = np.empty((V, 4), dtype=np.int32)
-        _check(self.lib, self.lib.glass_engine_last_view_details(self._h, P, _fp(feat), _fp(sims), boxes.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._call("last_view_details", P, _fp(feat), _fp(sims), boxes.ctypes.data_as(C.POINTER(C.c_int32)))
         return dict(features=feat, sims=sims, boxes=boxes)
 
     def last_F_device(self, P):
@@ -913,7 +867,7 @@ class Engine:
         engine's next call) — what the RCCL all-gather of a generation sends (parallel.py)."""
         import torch
         ptr = C.c_void_p()
-        _check(self.lib, self.lib.glass_engine_last_F_device(self._h, P, C.byref(ptr)))
+        self._call("last_F_device", P, C.byref(ptr))
 
         class _View:      # CUDA array interface (v2): torch.as_tensor wraps device memory it does not own
             __cuda_array_interface__ = dict(shape=(P, int(self.cfg.n_obj)), typestr="<f4", data=(int(ptr.value), False), version=2)
@@ -921,34 +875,33 @@ class Engine:
 
     def last_gpu_ms(self):
         ms = C.c_float()
-        _check(self.lib, self.lib.glass_engine_last_gpu_ms(self._h, C.byref(ms)))
+        self._call("last_gpu_ms", C.byref(ms))
         return ms.value
 
     def set_profiling(self, on):
-        _check(self.lib, self.lib.glass_engine_set_profiling(self._h, int(on)))
+        self._call("set_profiling", int(on))
 
     def biggan_tap(self, block):
         """Record the activation after GenBlock `block` (-1: after self-attention) on the next pass; see biggan_tap_result."""
-        _check(self.lib, self.lib.glass_engine_set_biggan_tap(self._h, int(block)))
+        self._call("set_biggan_tap", int(block))
 
     def biggan_tap_result(self):
         dims = (C.c_int32 * 4)()
-        self.lib.glass_engine_get_biggan_tap.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int32)]
-        _check(self.lib, self.lib.glass_engine_get_biggan_tap(self._h, None, 0, dims))
+        self._call("get_biggan_tap", None, 0, dims)
         out = np.empty(tuple(int(d) for d in dims), dtype=np.float32)
-        _check(self.lib, self.lib.glass_engine_get_biggan_tap(self._h, _fp(out), out.size, dims))
+        self._call("get_biggan_tap", _fp(out), out.size, dims)
         return out
 
     def set_overlap(self, on):
-        _check(self.lib, self.lib.glass_engine_set_overlap(self._h, int(on)))
+        self._call("set_overlap", int(on))
 
     def set_profile_filter(self, kernel_substr):
-        _check(self.lib, self.lib.glass_engine_set_profile_filter(self._h, (kernel_substr or "").encode()))
+        self._call("set_profile_filter", (kernel_substr or "").encode())
 
     def profile(self):
         n = C.c_int32()
-        _check(self.lib, self.lib.glass_engine_get_profile(self._h, None, 0, C.byref(n)))
+        self._call("get_profile", None, 0, C.byref(n))
         rows = (ProfRow * max(n.value, 1))()
-        _check(self.lib, self.lib.glass_engine_get_profile(self._h, rows, n.value, C.byref(n)))
+        self._call("get_profile", rows, n.value, C.byref(n))
         return [dict(name=r.name.decode(), launches=r.launches, total_ms=r.total_ms, flops=r.flops, bytes=r.bytes)
                 for r in rows[:n.value]]

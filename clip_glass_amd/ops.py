@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .engine import _check, _f32, _fp, load_library
+from .engine import _check, _f32, _fp, bind, load_library
 
 
 class ConvDesc(C.Structure):
@@ -120,10 +120,7 @@ def _lib():
     global _signed
     lib = load_library()
     if lib is not _signed:
-        for name, argtypes in SIGNATURES.items():
-            if hasattr(lib, name):
-                fn = getattr(lib, name)
-                fn.argtypes, fn.restype = argtypes, C.c_int32
+        bind(lib, SIGNATURES)
         _signed = lib
     return lib
 

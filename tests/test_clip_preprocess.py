@@ -127,7 +127,8 @@ def test_engine_create_refuses_an_over_wide_ratio():
 
 def test_config_struct_ends_with_the_new_fields():
     names = [f[0] for f in engine.GlassConfig._fields_]
-    assert names[-2:] == ["clip_resize", "clip_normalize"]
+    assert names[29:31] == ["clip_resize", "clip_normalize"]                      # the end of the struct when they were appended; later fields follow
+    assert (engine.GlassConfig.clip_resize.offset, engine.GlassConfig.clip_normalize.offset) == (356, 360)
     assert engine.GlassConfig().clip_resize == 0 and engine.GlassConfig().clip_normalize == 0
 
 

@@ -107,13 +107,14 @@ def test_unsupported_geometries_say_why(geom, word):
 
 def test_config_mirror_appends_the_resnet_fields():
     import ctypes
-    old, new = engine.GlassConfig, engine.GlassConfigResnet
-    assert [f[0] for f in new._fields_] == [f[0] for f in old._fields_] + ["clip_arch", "clip_rn_layers"]
-    for name, _ in old._fields_:                                                 # appended: nothing before them moved
-        assert getattr(new, name).offset == getattr(old, name).offset
-    assert new.clip_arch.offset == old.clip_normalize.offset + 4 and new.clip_rn_layers.offset == new.clip_arch.offset + 4
-    assert ctypes.sizeof(new) == 384                                             # sizeof(glass_config): 364 + 4 + 16, 8-byte aligned
-    cfg = new()
+    G = engine.GlassConfig
+    names = [f[0] for f in G._fields_]
+    assert names[29:33] == ["clip_resize", "clip_normalize", "clip_arch", "clip_rn_layers"]
+    assert (G.clip_resize.offset, G.clip_normalize.offset) == (356, 360)         # appended: nothing before them moved
+    assert G.clip_arch.offset == 364 == G.clip_normalize.offset + 4 and G.clip_rn_layers.offset == 368 == G.clip_arch.offset + 4
+    assert G.clip_rn_layers.size == 16 and G.lpips_size.offset == 384            # the struct with them: 364 + 4 + 16 = 384, 8-byte aligned
+    assert ctypes.alignment(G) == 8 and ctypes.sizeof(G) == 408
+    cfg = G()
     assert cfg.clip_arch == 0 and list(cfg.clip_rn_layers) == [0, 0, 0, 0]       # zero: the ViT engine
 
 

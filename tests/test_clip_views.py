@@ -166,11 +166,15 @@ def test_tower_rows():
 
 
 def test_config_structs_are_unchanged():
-    names = [f[0] for f in engine.GlassConfig._fields_]
-    assert len(names) == 31 and names[-2:] == ["clip_resize", "clip_normalize"] and C.sizeof(engine.GlassConfig) == 368
-    rn = [f[0] for f in engine.GlassConfigResnet._fields_]
-    assert rn == names + ["clip_arch", "clip_rn_layers"] and C.sizeof(engine.GlassConfigResnet) == 384
-    assert not any("view" in n for n in rn)
+    G = engine.GlassConfig
+    every = [f[0] for f in G._fields_]
+    names = every[:31]                                              # the struct before the ResNet towers: 364 bytes, 368 at its 8-byte alignment
+    assert names[-2:] == ["clip_resize", "clip_normalize"] and (G.clip_resize.offset, G.clip_normalize.offset) == (356, 360)
+    assert C.alignment(G) == 8 and G.clip_normalize.size == 4
+    assert every[31:33] == ["clip_arch", "clip_rn_layers"] and (G.clip_arch.offset, G.clip_rn_layers.offset) == (364, 368)
+    assert G.clip_rn_layers.size == 16 and G.lpips_size.offset == 384        # with them: 384 bytes, and the next field starts there
+    assert C.sizeof(G) == 408
+    assert not any("view" in n for n in every)
 
 
 # ---- the plumbing ------------------------------------------------------------------------------------------------------------

@@ -19,10 +19,14 @@ def test_symbols_are_exported():
 
 
 def test_config_struct_appends_the_fields_last():
-    names = [f[0] for f in engine.GlassConfigEdit._fields_]
-    assert names[:-2] == [f[0] for f in engine.GlassConfigPrompt._fields_] and names[-2:] == ["anchor", "anchor_lambda"]
-    assert C.sizeof(engine.GlassConfigEdit) == C.sizeof(engine.GlassConfigPrompt) + 8      # (the struct ends on 4 bytes of padding: the two fields fill 8)
-    cfg = engine.GlassConfigEdit()
+    G = engine.GlassConfig
+    names = [f[0] for f in G._fields_]
+    assert len(names) == 38 and names[29:31] == ["clip_resize", "clip_normalize"]
+    assert names[31:] == ["clip_arch", "clip_rn_layers", "lpips_size", "lpips_lambda", "sim_columns", "anchor", "anchor_lambda"]
+    assert G.sim_columns.offset == 392                                            # nothing before them moved
+    assert (G.anchor.offset, G.anchor_lambda.offset) == (396, 400)
+    assert C.sizeof(G) == 408      # (400 at 8-byte alignment without the two fields: they fill 8, and the struct ends on 4 bytes of padding)
+    cfg = G()
     assert cfg.anchor == 0 and cfg.anchor_lambda == 0.0
 
 

@@ -31,10 +31,12 @@ def test_refused_with_the_reason(gen_res, S, word):
 
 
 def test_config_struct_appends_the_two_fields():
-    names = [f[0] for f in engine.GlassConfigLpips._fields_]
-    assert names[:-2] == [f[0] for f in engine.GlassConfigResnet._fields_] and names[-2:] == ["lpips_size", "lpips_lambda"]
-    assert C.sizeof(engine.GlassConfigLpips) == C.sizeof(engine.GlassConfigResnet) + 8
-    z = engine.GlassConfigLpips()
+    G = engine.GlassConfig
+    names = [f[0] for f in G._fields_]
+    assert names[31:35] == ["clip_arch", "clip_rn_layers", "lpips_size", "lpips_lambda"]
+    assert (G.clip_arch.offset, G.clip_rn_layers.offset) == (364, 368)            # nothing before them moved
+    assert (G.lpips_size.offset, G.lpips_lambda.offset) == (384, 388) and G.sim_columns.offset == 392      # 384 + 8: the two fields fill 8 bytes
+    z = G()
     assert z.lpips_size == 0 and z.lpips_lambda == 0.0
 
 

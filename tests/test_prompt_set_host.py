@@ -18,10 +18,12 @@ def test_symbols_are_exported():
 
 
 def test_config_struct_appends_the_field():
-    names = [f[0] for f in engine.GlassConfigPrompt._fields_]
-    assert names[:-1] == [f[0] for f in engine.GlassConfigLpips._fields_] and names[-1] == "sim_columns"
-    assert C.sizeof(engine.GlassConfigPrompt) >= C.sizeof(engine.GlassConfigLpips)
-    assert engine.GlassConfigPrompt().sim_columns == 0
+    G = engine.GlassConfig
+    names = [f[0] for f in G._fields_]
+    assert names[33:36] == ["lpips_size", "lpips_lambda", "sim_columns"]
+    assert (G.lpips_size.offset, G.lpips_lambda.offset) == (384, 388)             # nothing before it moved
+    assert G.sim_columns.offset == 392 and C.sizeof(G) == 408
+    assert G().sim_columns == 0
 
 
 # ---- the library's rule ------------------------------------------------------------------------------------------------------------
