@@ -144,7 +144,7 @@ struct Stage {
     }
 };
 
-// The symbol(s) of the last conv / dblock_down / dblock0 launch of the calling thread (glass_op_last_kernel): what ConvKernel::name,
+// The symbol(s) of the last conv / gemm / gemm_batched / bg_tail / dblock_down / dblock0 launch of the calling thread (glass_op_last_kernel): what ConvKernel::name,
 // launch_conv_gemm, launch_conv_down and launch_dblock0 return; two launches of one op are joined by " + ".  Empty: the op launched nothing.
 thread_local std::string g_last_kernel;
 const char* ran_kernel(const char* name) {
@@ -161,11 +161,12 @@ int accepted(R answer, const std::string& refusal) {
     return GLASS_OK;
 }
 
-// impl 1: gemm_direct; 2: gemm_tiled, a refusal is an error; else gemm_tiled, then gemm_direct where it refuses (run_gemm's order)
+// impl 1: gemm_direct; 2: gemm_tiled, a refusal is an error; else gemm_tiled, then gemm_direct where it refuses (run_gemm's order).
+// The symbol that ran goes to ran_kernel.
 int launch_gemm_impl(const GemmParams& g, int impl) {
-    if (impl == 1) launch_gemm_direct(g, 0);
-    else if (impl == 2) return accepted(launch_gemm_tiled(g, 0), "tiled gemm: unsupported shape");
-    else if (!launch_gemm_tiled(g, 0)) launch_gemm_direct(g, 0);
+    if (impl == 1) ran_kernel(launch_gemm_direct(g, 0));
+    else if (impl == 2) return accepted(ran_kernel(launch_gemm_tiled(g, 0)), "tiled gemm: unsupported shape");
+    else if (!ran_kernel(launch_gemm_tiled(g, 0))) ran_kernel(launch_gemm_direct(g, 0));
     return GLASS_OK;
 }
 }  // namespace
@@ -296,7 +297,8 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
     }
     Buf<float> ytanh;
     if (d->rgb_tanh) {
-        ytanh = st.poisoned<float>(nrgb);        // NaN: a pixel the conv does not write shows
+        const size_t gt = CONV_GUARD_ROWS * d->Wo;
+        ytanh = st.poisoned<float>(nrgb, gt, gt);      // NaN: a pixel the conv does not write shows
         p.rgb_tanh_out = ytanh;
     }
     Buf<float> part;
@@ -354,8 +356,16 @@ extern "C" int glass_op_conv(int32_t device, const glass_conv_desc* d) {
         return GLASS_OK;
     }));
     if (part) TRY(st.run([&] { launch_trgb_finish(part, ntn, d->B, d->Ho, p.trgb_b, part_yprev, yrgb, 0); }));
-    if (ytanh) {                                                 // (p.y is not written)
+    if (ytanh) {                                                 // (p.y is not written: every byte of it still holds the poison)
         TRY(st.fetch(d->rgb_tanh, ytanh));
+        TRY(st.intact_named(ytanh, "conv: rgb_tanh"));
+        std::vector<_Float16> hy(y.n);
+        TRY(st.fetch(hy.data(), y));
+        for (size_t i = 0; i < hy.size(); ++i) {
+            uint16_t bits;
+            memcpy(&bits, &hy[i], sizeof bits);
+            REQUIRE(bits == 0xFFFF, GLASS_ERR_STATE, "conv: y (rgb_tanh form, not an output) was written at element " + std::to_string(i));
+        }
         return st.intact_named(y, "conv: y (rgb_tanh form, not an output)");
     }
     if (yrgb) {
@@ -378,6 +388,7 @@ constexpr size_t GUARD_ROWS = 128;
 extern "C" int glass_op_gemm(int32_t device, int32_t M, int32_t N, int32_t K, const float* a, const float* w,
                              const float* bias, int32_t mode, int32_t impl, float* out) {
     OPREQ(a && w && out && K % 16 == 0, "bad argument");
+    g_last_kernel.clear();
     Stage st(device);
     GemmParams g;
     memset(&g, 0, sizeof g);
@@ -448,18 +459,20 @@ extern "C" int glass_op_gemm_batched(int32_t device, int32_t batch, int32_t M, i
     OPREQ(a && w && out && batch >= 1 && M > 0 && N > 0 && K > 0 && K % 16 == 0, "bad argument (K a multiple of 16)");
     OPREQ(mode == 0 || mode == 3, "batched gemm: mode 0 (fp16 out) or 3 (fp32 out), the self-attention products");
     OPREQ(impl >= 0 && impl <= 2, "impl must lie in [0, 2]");
+    g_last_kernel.clear();
     Stage st(device);
-    const size_t n = (size_t)batch * M * N;
+    const size_t n = (size_t)batch * M * N, guard = GUARD_ROWS * N;
     const auto da = st.in16(a, (size_t)batch * M * K), dw = st.in16(w, (size_t)batch * N * K);
     Buf<half_t> o16;
     Buf<float> o32;
-    if (mode == 0) o16 = st.poisoned<half_t>(n);
-    else o32 = st.poisoned<float>(n);
+    if (mode == 0) o16 = st.poisoned<half_t>(n, guard, guard);      // NaN: an element no tile stores shows
+    else o32 = st.poisoned<float>(n, guard, guard);
     GemmParams g = gemm_params(da, dw, M, N, K, nullptr, mode, o16, o32, 0);      // as bg_attention (biggan.cpp)
     g.cand_batch = cand_batch ? 1 : 0;
     g.batch = batch; g.a_bs = (long long)M * K; g.w_bs = (long long)N * K; g.o_bs = (long long)M * N;
     TRY(st.run([&] { return launch_gemm_impl(g, impl); }));
-    return o16 ? st.fetch(out, o16) : st.fetch(out, o32);
+    TRY(o16 ? st.fetch(out, o16) : st.fetch(out, o32));
+    return o16 ? st.intact_named(o16, "gemm_batched: out") : st.intact_named(o32, "gemm_batched: out");
 }
 
 extern "C" int glass_op_dense(int32_t device, int32_t P, int32_t K, int32_t N, const float* x, const float* wt,
@@ -881,7 +894,7 @@ extern "C" int glass_op_bg_bn_tables(int32_t device, int32_t P, int32_t cd, int3
     const size_t n = (size_t)P * 2 * C;
     const auto dc = st.in32(cond, (size_t)P * cd), dw = st.in32(wt, (size_t)cd * 2 * C), db = st.in32(bias, 2 * (size_t)C);
     const auto di = st.in32(inv_std, C), dm = st.in32(mean, C), dp = st.in32(prebias, C);
-    const auto dt = st.raw<float>(n);
+    const auto dt = st.poisoned<float>(n);          // NaN: a table entry launch_dense does not write shows in both tables
     const auto dt16 = st.poisoned<half_t>(n);
     TRY(st.run([&] {      // glass_biggan_prepare's three launches
         launch_dense(dc, cd, P, cd, dw, 2 * C, db, dt, 2 * C, 0, 0, nullptr, 0, 0);
@@ -939,6 +952,7 @@ extern "C" int glass_op_bg_tail(int32_t device, int32_t B, int32_t R, int32_t mi
     OPREQ(h && x0 && w3 && b3 && bn_a && bn_s && rgb_w && rgb_b && y && B > 0 && R > 0 && mid > 0, "bad argument");
     const int C = 128, cpad = 32;                           // the last block's width; BgState::rgb_cpad
     OPREQ(bg_tail_supported(R, mid, C, C, 1, cpad), "bg_tail: unsupported shape (R % 32 == 0, R >= 32, mid == 32, 128 -> 128 channels of an up block)");
+    g_last_kernel.clear();
     Stage st(device);
     const int R2 = R / 2;
     std::vector<_Float16> pk((size_t)9 * cpad * C, (_Float16)0.f);      // [tap][cpad][128], rows 0..2 used (biggan.cpp pack())
@@ -957,10 +971,16 @@ extern "C" int glass_op_bg_tail(int32_t device, int32_t B, int32_t R, int32_t mi
     tp.tab = st.in32(tab.data(), tab.size()); tp.bnf_off = 0; tp.ctot = C;
     tp.rgb_w = st.in16(pk); tp.cpad = cpad;
     tp.rgb_b = st.in32(rb.data(), rb.size());
-    const auto dy = st.poisoned<float>((size_t)B * 3 * R * R);      // NaN: a pixel no tile writes shows
+    const size_t gy = CONV_GUARD_ROWS * R;
+    const auto dy = st.poisoned<float>((size_t)B * 3 * R * R, gy, gy);      // NaN: a pixel no tile writes shows; 16 image rows of guard on both sides
     tp.y = dy; tp.B = B; tp.R = R;
-    TRY(st.run([&] { return accepted(launch_bg_tail(tp, 0), "bg_tail: the launcher refused the shape"); }));
-    return st.fetch(y, dy);
+    TRY(st.run([&]() -> int {
+        TRY(accepted(launch_bg_tail(tp, 0), "bg_tail: the launcher refused the shape"));
+        ran_kernel("bg_tail_kernel");       // (launch_bg_tail has one instance)
+        return GLASS_OK;
+    }));
+    TRY(st.fetch(y, dy));
+    return st.intact_named(dy, "bg_tail: y");
 }
 
 // ---- the small fp32 kernels around StyleGAN2 and the CLIP towers, each launched as the engine's host code launches it ------------------------

@@ -236,7 +236,7 @@ def conv(x, w, *, stride=1, pad=None, up=False, sn=None, dscale=None, noise=None
 def last_kernel():
     """The kernel symbol(s) the last conv / dblock_down / dblock0 of this thread launched ("a + b" for two launches; "" for none) — and of the
     last rn_avgpool, rn_stem_conv1 (the conv itself, not the patch operand's preparation), rn_conv_bn, rn_tokens, lpips_input, vgg_conv1 or
-    maxpool2."""
+    maxpool2, and of the last gemm, gemm_batched or bg_tail."""
     lib = _lib()
     buf = C.create_string_buffer(512)
     _check(lib, lib.glass_op_last_kernel(buf, len(buf)))

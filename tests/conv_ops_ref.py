@@ -47,6 +47,24 @@ hi + lo / 2048 (kernels_misc.hip trgb_table_value; conv_stream.hip:213-217), who
 partial-sum form (trgb_finish_kernel, kernels_misc.hip:507-508) adds TRGB_PARTIAL = 4 more: one fp32 addition per n tile (two tiles at Cout = 256)
 and the two roundings of each partial's own closing additions.
 
+THE BigGAN FIELDS of glass_conv_desc (csrc/biggan.cpp bg_conv; inputs with pre_shift / in_up / shift / act == 2 / res_cs / res_up / rgb_tanh):
+
+  pre_shift   the input affine a = relu(x A + S), zero at padding pixels, mirrored in the form its site takes:
+     family              operand a                                                          where
+     conv_tiled          relu(ra * sh + shf) in packed fp16 from the FP16 tables            conv_tiled.hip:165-170
+     conv_direct         (half_t)fmaxf((float)x * s + t, 0) from the FP32 tables            conv_direct.hip:85-86
+     conv_gemm (im2col)  the same form as conv_direct                                       conv_gemm.hip:37
+              The compiler may contract each a * b + c ("fma", one rounding) or not ("sep", two): `pre_form` says which, and a device result
+              passes when ONE form holds for the whole output.  Exact sums come from biggan_ops_ref.sum_odd (round to odd), so no float64
+              sum is assumed exact.
+  in_up       addressing only: (iy >> 1, ix >> 1), the padding tested at the upsampled size.
+  shift       bb = bias + shift: one more fp32 addition, inside the "+ 8".
+  act == 2    max(v k1, v 0): g = 1; ReLU is 1-Lipschitz, so an element with |v| <= tol may be 0 or v and the bound needs nothing more.
+              conv_stream: k1 = (half_t)out_scale, k2 = 0 — the same three fp16 roundings as with act == 1.
+  res_cs / res_up   addressing only: the first Cout of res_cs channels, row / column (oy >> 1, ox >> 1).
+  rgb_tanh    (conv_tiled.hip:412-418) tanhf of the fp32 v of channels 0..2: NO fp16 store term — the bound of v (tanh is 1-Lipschitz) plus
+              biggan_ops_ref.tanh_term, the project's rule for a float32 tanh (test_gpu_biggan_ops._f32_bar).  Returned as [B,3,Ho,Wo].
+
 No term is fitted to an observed error."""
 import math
 
@@ -54,6 +72,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from biggan_ops_ref import fma16, fma32, tanh_term
 from glue_ops_ref import U16, U32, h16, tol_torgb, torgb
 from util import style_tables
 
@@ -78,13 +97,36 @@ def _pack(w):
     return ops.host_pack_conv(np.asarray(w, np.float32))
 
 
-def operands(inp, form, table):
-    """The fp16 operands of the MFMAs as float32 arrays: a [B,H,W,Cin] and b [B or 1][T][Cout][Cin] — and whether dscale still applies."""
+def up2(a):
+    """Nearest x2 of an NHWC map: what in_up / res_up address."""
+    return np.repeat(np.repeat(a, 2, axis=1), 2, axis=2)
+
+
+def pre_affine(x, A, S, table, pre_form):
+    """relu(x A + S) as its site rounds it (module docstring): fp16 tables and a packed fp16 fma (conv_tiled) or fp32 tables, an fp32 fma and
+    one conversion to fp16 (conv_direct, conv_gemm).  x [B,H,W,Cin] fp16 values; A, S [B,Cin] fp32."""
+    x = np.asarray(x, np.float64)
+    A, S = (np.asarray(t, np.float32).astype(np.float64)[:, None, None, :] for t in (A, S))
+    if table == "sn16":
+        v = fma16(x, h16(A).astype(np.float64), h16(S).astype(np.float64), pre_form)
+    else:
+        v = h16(fma32(x, A, S, pre_form))
+    return np.maximum(v, 0.0).astype(np.float32)
+
+
+def operands(inp, form, table, pre_form="fma"):
+    """The fp16 operands of the MFMAs as float32 arrays: a [B,H,W,Cin] (the map the taps address: upsampled with in_up) and
+    b [B or 1][T][Cout][Cin] — and whether dscale still applies."""
     x, sn, B = inp["x"], inp.get("sn"), inp["B"]
     wp = _pack(inp["w"])
     a = np.broadcast_to(x, (B,) + x.shape[1:]) if x.shape[0] != B else x
     b = wp[None]
     demod = inp.get("dscale") is not None
+    if inp.get("pre_shift") is not None:
+        assert form == "x", "the input affine is staged on the activation operand only (conv_glds / conv_stream refuse it)"
+        a, sn = pre_affine(a, sn, inp["pre_shift"], table, pre_form), None
+    if inp.get("in_up"):
+        a = up2(a)
     if sn is None:
         return np.ascontiguousarray(a, np.float32), b, demod
     s = np.asarray(sn, np.float32)
@@ -125,10 +167,20 @@ def _planes(inp, Ho, Wo):
     return (float(np.float32(inp.get("noise_strength", 0.0))) * nz)[..., None]
 
 
-def conv_ref(inp, family):
-    """(ref, tol) of one launch under `family`'s operand form and epilogue roundings; ref and tol [B,Ho,Wo,Cout] float64."""
+def residual(inp):
+    """The residual as the epilogue addresses it: [B,Ho,Wo,Cout] from res [B,Ho >> res_up,Wo >> res_up,res_cs or Cout] (None without)."""
+    if inp.get("res") is None:
+        return None
+    r = np.asarray(inp["res"])
+    r = up2(r) if inp.get("res_up") else r
+    return r[..., :inp["w"].shape[0]]
+
+
+def conv_ref(inp, family, pre_form="fma"):
+    """(ref, tol) of one launch under `family`'s operand form and epilogue roundings; ref and tol [B,Ho,Wo,Cout] float64 ([B,3,Ho,Wo] with
+    rgb_tanh)."""
     form, table, epi = KERNELS[family]
-    a, b, demod = operands(inp, form, table)
+    a, b, demod = operands(inp, form, table, pre_form)
     KS, stride, pad = inp["w"].shape[2], inp.get("stride", 1), inp.get("pad", inp["w"].shape[2] // 2)
     acc = _conv(a, b, KS, stride, pad, torch.float64)
     B, Ho, Wo, Cout = acc.shape
@@ -138,15 +190,21 @@ def conv_ref(inp, family):
     d = np.asarray(inp["dscale"], np.float64)[:, None, None, :] if demod else 1.0
     nz = _planes(inp, Ho, Wo)
     bias = np.asarray(inp["bias"], np.float64) if inp.get("bias") is not None else np.zeros(Cout)
-    pre = acc * d + nz + bias
-    P = A * np.abs(d) + np.abs(nz) + np.abs(bias)
-    act = bool(inp.get("act"))
-    g = SQRT2 if act else 1.0
+    shift = np.asarray(inp["shift"], np.float64)[:, None, None, :] if inp.get("shift") is not None else 0.0
+    pre = acc * d + nz + bias + shift
+    P = A * np.abs(d) + np.abs(nz) + np.abs(bias) + np.abs(shift)
+    act = int(inp.get("act") or 0)
+    g = SQRT2 if act == 1 else 1.0
     os_ = float(np.float32(inp.get("out_scale", 1.0)))
-    res = np.asarray(inp["res"], np.float64) if inp.get("res") is not None else 0.0
-    post = np.where(pre > 0, pre, 0.2 * pre) * SQRT2 if act else pre
+    res = residual(inp)
+    res = 0.0 if res is None else res.astype(np.float64)
+    post = np.where(pre > 0, pre, 0.2 * pre) * SQRT2 if act == 1 else np.maximum(pre, 0.0) if act == 2 else pre
     out = (post + res) * os_
     tol = os_ * g * (2 * K + 8) * U32 * P + 4 * U32 * (np.abs(res) * os_ + np.abs(out)) + SUBNORMAL
+    if inp.get("rgb_tanh"):          # tanhf of the fp32 v: no store term
+        assert epi == "fp32" and family == "conv_tiled"
+        v = np.ascontiguousarray(out[..., :3].transpose(0, 3, 1, 2))
+        return np.tanh(v), np.ascontiguousarray(tol[..., :3].transpose(0, 3, 1, 2)) + tanh_term(v)
     if epi == "fp32":
         tol = tol + U16 * np.abs(out)
     else:                   # conv_stream: fp16(pre), fp16(k), fp16(v * k)
@@ -165,10 +223,11 @@ class Emulation:
     """float32 accumulators of the mirrored operands (torch float32 conv) and the epilogue in float32 — or, for conv_stream, in packed fp16 —
     ending in the fp16 store.  finish() takes the pieces a planted defect replaces."""
 
-    def __init__(self, inp, family):
+    def __init__(self, inp, family, pre_form="fma", table=None):
         self.inp, self.family = inp, family
         self.form, self.table, self.epi = KERNELS[family]
-        self.a, self.b, self.demod = operands(inp, self.form, self.table)
+        self.table = table or self.table                                              # (a planted defect: the other family's tables)
+        self.a, self.b, self.demod = operands(inp, self.form, self.table, pre_form)
         self.KS, self.stride = inp["w"].shape[2], inp.get("stride", 1)
         self.pad = inp.get("pad", self.KS // 2)
         self.acc = self.accumulate(self.a, self.b)
@@ -176,7 +235,8 @@ class Emulation:
     def accumulate(self, a, b):
         return _conv(a, b, self.KS, self.stride, self.pad, torch.float32)
 
-    def finish(self, acc=None, noise_planes=None, res_before_act=False):
+    def finish(self, acc=None, noise_planes=None, res_before_act=False, res=None, relu_before_shift=False, tanh_of_fp16=False):
+        """acc / noise_planes / res: replacements (a planted defect's); res_before_act, relu_before_shift, tanh_of_fp16: planted defects."""
         inp = self.inp
         f32 = np.float32
         v = (self.acc if acc is None else acc).astype(f32)
@@ -185,26 +245,39 @@ class Emulation:
             v = v * np.asarray(inp["dscale"], f32)[:, None, None, :]
         nz = (_planes(inp, Ho, Wo) if noise_planes is None else noise_planes).astype(f32)
         bias = np.asarray(inp["bias"], f32) if inp.get("bias") is not None else np.zeros(Cout, f32)
-        act, os_ = bool(inp.get("act")), f32(inp.get("out_scale", 1.0))
-        res = np.asarray(inp["res"], f32) if inp.get("res") is not None else None
+        shift = np.asarray(inp["shift"], f32)[:, None, None, :] if inp.get("shift") is not None else None
+        act, os_ = int(inp.get("act") or 0), f32(inp.get("out_scale", 1.0))
+        if res is None:
+            res = residual(inp)
+        res = None if res is None else np.asarray(res, f32)
         if self.epi == "stream":
-            t = h16(v + (nz + bias))                                                   # fp32 up to the activation input, then fp16
+            bb = bias if shift is None else bias + shift                                # Cb = bias + shift (conv_stream.hip:200)
+            t = h16(v + (nz + bb))                                                     # fp32 up to the activation input, then fp16
             if res is not None and res_before_act:
                 t = h16(t + res)
-            k1 = h16(f32(SQRT2 if act else 1.0) * os_)
-            k2 = h16(f32(0.2 * SQRT2 if act else 1.0) * os_)
+            k1 = h16(f32(SQRT2 if act == 1 else 1.0) * os_)
+            k2 = h16(f32(0.2 * SQRT2 if act == 1 else 0.0 if act == 2 else 1.0) * os_)
             out = np.maximum(h16(t * k1), h16(t * k2))
             if res is not None and not res_before_act:                                  # (conv_stream has no residual; the teeth tests give it one)
                 out = h16(out + res * os_)
             return out
         v = v + nz
         v = v + bias
+        if relu_before_shift:
+            v = np.maximum(v, f32(0))
+        if shift is not None:
+            v = v + shift
         if res is not None and res_before_act:
             v = v + res
-        if act:
+        if act == 1:
             v = np.where(v > 0, v, f32(0.2) * v) * f32(SQRT2)
+        elif act == 2 and not relu_before_shift:
+            v = np.maximum(v, f32(0))
         if res is not None and not res_before_act:
             v = v + res
+        if inp.get("rgb_tanh"):
+            v = np.ascontiguousarray((v * os_)[..., :3].transpose(0, 3, 1, 2))
+            return np.tanh(h16(v) if tanh_of_fp16 else v)
         return h16(v * os_)
 
 
@@ -307,3 +380,185 @@ CASES = {
     "gemm skip1x1": ("conv_gemm", 6, "gemm_tiled_kernel<64>", dict(B=6, H=8, W=8, Cin=128, Cout=256, KS=1, pad=0, bias=False, act=False)),
     "gemm const4": ("conv_gemm", 6, "conv_gemm(im2col+gemm_tiled+finish)", dict(B=16, H=4, W=4, Cin=128, Cout=128, broadcast_x=True, style=True, demod=True)),
 }
+
+
+# ---- the BigGAN path's conv forms (csrc/biggan.cpp bg_conv): inputs, cases, lattice builders ---------------------------------------------------
+FAMILY_OF_IMPL = {1: "conv_direct", 2: "conv_tiled", 4: "conv_stream", 5: "conv_glds", 6: "conv_gemm"}
+OLD_BAR = 5e-3                       # x max|ref|: the bar these cases were held to before the per-element bound
+PRE_FORMS = ("fma", "sep")
+
+
+def stream_shape(cus=256):
+    """The smallest map choose_conv_stream accepts: 64 nominal candidates x (W / 32) (H / 8) tiles >= 6 per slot, 3 slots per CU."""
+    need = -(-cus * 3 * 6 // 64)
+    return 64, 32 * -(-need // 8)
+
+
+def _bg_tables(rng, B, C):
+    """Per-(candidate, channel) scale and shift: O(1) apart between candidates and channels, both signs; the shift has a positive mean."""
+    A = (rng.standard_normal((B, C)) + 0.8 * rng.choice([-1.0, 1.0], (B, 1))).astype(np.float32)
+    S = (0.6 + 0.8 * rng.standard_normal((B, C))).astype(np.float32)
+    return A, S
+
+
+def _bg_xw(rng, B, H, W, Cin, Cout, ks):
+    return h16(rng.standard_normal((B, H, W, Cin))), rng.standard_normal((Cout, Cin, ks, ks)).astype(np.float32)
+
+
+def bg_inputs(form, impl, B, H, W, Cin, Cout, up=False, res_mult=1, res_up=False, seed=None):
+    """The inputs of one BigGAN conv form, drawn exactly as test_gpu_biggan_ops.py drew them under the 5e-3 max|ref| bar.  H, W: the STORED
+    input map (conv1 with up: the output is twice that)."""
+    inp = dict(B=B, stride=1, out_scale=1.0, batch_size=1, act=0, form=form, impl=impl)
+    if form == "conv0":
+        rng = np.random.default_rng(100 + impl + H if seed is None else seed)
+        inp["x"], inp["w"] = _bg_xw(rng, B, H, W, Cin, Cout, 1)
+        inp["sn"], inp["pre_shift"] = _bg_tables(rng, B, Cin)
+        inp["dscale"], inp["shift"] = _bg_tables(rng, B, Cout)
+        inp["act"] = 2
+    elif form in ("conv1", "conv2"):
+        rng = np.random.default_rng((200 + impl + Cin if form == "conv1" else 300 + Cin) if seed is None else seed)
+        inp["x"], inp["w"] = _bg_xw(rng, B, H, W, Cin, Cout, 3)
+        inp["dscale"], inp["shift"] = _bg_tables(rng, B, Cout)
+        inp["act"], inp["in_up"] = 2, bool(up)
+    elif form == "conv3":
+        rng = np.random.default_rng(400 + res_mult + res_up if seed is None else seed)
+        inp["x"], inp["w"] = _bg_xw(rng, B, H, W, Cin, Cout, 1)
+        inp["bias"] = rng.standard_normal(Cout).astype(np.float32)
+        rcs = res_mult * Cout
+        inp["res"] = h16(rng.standard_normal((B, H >> res_up, W >> res_up, rcs)) + np.arange(B)[:, None, None, None])     # O(1) apart per candidate
+        inp["res_cs"], inp["res_up"] = (rcs if res_mult > 1 else 0), bool(res_up)
+    elif form == "final":
+        rng = np.random.default_rng(500 + H if seed is None else seed)
+        inp["x"], inp["w"] = _bg_xw(rng, B, H, W, 128, 32, 3)
+        inp["sn"], inp["pre_shift"] = _bg_tables(rng, B, 128)
+        inp["bias"] = (0.2 * rng.standard_normal(32)).astype(np.float32)
+        inp["rgb_tanh"] = True
+    else:
+        raise ValueError(form)
+    inp["pad"] = inp["w"].shape[2] // 2
+    return inp
+
+
+def bg_op_kwargs(inp):
+    """The keyword arguments of ops.conv for a BigGAN form (without x, w)."""
+    kw = {k: inp[k] for k in ("sn", "pre_shift", "dscale", "shift", "bias", "res") if inp.get(k) is not None}
+    kw.update(impl=inp["impl"], act=inp["act"], in_up=bool(inp.get("in_up")), res_cs=inp.get("res_cs", 0), res_up=bool(inp.get("res_up")),
+              rgb_tanh=bool(inp.get("rgb_tanh")))
+    return kw
+
+
+def old_bar(inp, ref):
+    """What the case was held to before: 5e-3 max|ref| of the float64 reference WITHOUT the mirrored input affine."""
+    return OLD_BAR * float(np.abs(ref).max())
+
+
+# name -> (arguments of bg_inputs, the symbol ops.last_kernel() must report).  H = 0: stream_shape() of the device.
+BG_CASES = {
+    "conv0 tiled 8x32": (dict(form="conv0", impl=2, B=3, H=8, W=32, Cin=128, Cout=32), "conv_tiled_kernel<1,1,8,32>"),
+    "conv0 tiled 24x64": (dict(form="conv0", impl=2, B=2, H=24, W=64, Cin=128, Cout=32), "conv_tiled_kernel<1,1,8,32>"),
+    "conv0 gemm 4x4": (dict(form="conv0", impl=6, B=3, H=4, W=4, Cin=256, Cout=64), "conv_gemm(im2col+gemm_tiled+finish)"),
+    "conv0 direct 8x8": (dict(form="conv0", impl=1, B=3, H=8, W=8, Cin=128, Cout=32), "conv_direct_kernel<1>"),
+    "conv1 tiled up 32": (dict(form="conv1", impl=2, B=3, H=12, W=32, Cin=32, Cout=32, up=True), "conv_tiled_kernel<3,1,8,32>"),
+    "conv1 tiled up 64": (dict(form="conv1", impl=2, B=3, H=12, W=32, Cin=64, Cout=64, up=True), "conv_tiled_kernel<3,1,8,64>"),
+    "conv1 gemm up 64": (dict(form="conv1", impl=6, B=3, H=4, W=4, Cin=64, Cout=64, up=True), "conv_gemm(im2col+gemm_tiled+finish)"),
+    "conv1 direct up 64": (dict(form="conv1", impl=1, B=3, H=4, W=4, Cin=64, Cout=64, up=True), "conv_direct_kernel<2>"),
+    "conv1 gemm up 128": (dict(form="conv1", impl=6, B=3, H=4, W=4, Cin=128, Cout=128, up=True), "conv_gemm(im2col+gemm_tiled+finish)"),
+    "conv1 gemm 64": (dict(form="conv1", impl=6, B=3, H=4, W=4, Cin=64, Cout=64), "conv_gemm(gather+gemm_tiled+finish)"),
+    "conv1 gemm 256": (dict(form="conv1", impl=6, B=3, H=4, W=4, Cin=256, Cout=256), "conv_gemm(gather+gemm_tiled+finish)"),
+    "conv2 glds<16>": (dict(form="conv2", impl=5, B=3, H=16, W=16, Cin=128, Cout=128), "conv_glds_kernel<16>"),
+    "conv2 glds<32>": (dict(form="conv2", impl=5, B=3, H=16, W=32, Cin=128, Cout=128), "conv_glds_kernel<32>"),
+    "conv2 stream": (dict(form="conv2", impl=4, B=2, H=0, W=0, Cin=32, Cout=32), "conv_stream_kernel"),
+    "conv2 tiled": (dict(form="conv2", impl=2, B=2, H=0, W=0, Cin=32, Cout=32), "conv_tiled_kernel<3,1,8,32>"),
+    "conv2 gemm 8x8": (dict(form="conv2", impl=6, B=3, H=8, W=8, Cin=64, Cout=64), "conv_gemm(gather+gemm_tiled+finish)"),
+    "final tanh 8x32": (dict(form="final", impl=2, B=3, H=8, W=32, Cin=128, Cout=32), "conv_tiled_kernel<3,1,8,32>"),
+    "final tanh 24x64": (dict(form="final", impl=2, B=2, H=24, W=64, Cin=128, Cout=32), "conv_tiled_kernel<3,1,8,32>"),
+}
+_CONV3_KERNEL = {2: "conv_tiled_kernel<1,1,8,64>", 6: "conv_gemm(im2col+gemm_tiled+finish)", 1: "conv_direct_kernel<2>"}
+for _impl in (2, 6, 1):
+    for _rm, _ru in ((2, True), (1, False), (2, False)):
+        BG_CASES["conv3 %s res_cs %d up%d" % (FAMILY_OF_IMPL[_impl][5:], _rm * 64, _ru)] = (
+            dict(form="conv3", impl=_impl, B=3, H=8, W=32, Cin=64, Cout=64, res_mult=_rm, res_up=_ru), _CONV3_KERNEL[_impl])
+
+
+def bg_case_name(args):
+    """The name under which BG_CASES holds these bg_inputs arguments."""
+    given = {k: v for k, v in args.items() if v not in (False, None)}          # (up / res_up False are the defaults the table leaves out)
+    for name, (a, _) in BG_CASES.items():
+        if {k: v for k, v in a.items() if v not in (False, None)} == given:
+            return name
+    raise KeyError(args)
+
+
+def bg_case(name, cus=256, lattice=False):
+    """The inputs of BG_CASES[name] (lattice: on the lattice, with the exact result: (inp, want))."""
+    args = dict(BG_CASES[name][0])
+    if args["H"] == 0:
+        args["H"], args["W"] = stream_shape(cus)
+    return bg_lattice(**args) if lattice else bg_inputs(**args)
+
+
+def bg_lattice(form, impl, B, H, W, Cin, Cout, up=False, res_mult=1, res_up=False, seed=0):
+    """A BigGAN form on the lattice, and what a correct kernel MUST return bit for bit: (inp, want).
+    x in multiples of 1/4 up to 1; A signed powers of two in +-{1/2, 1, 2} and S in multiples of 1/8, both per candidate and channel, so that
+    relu(x A + S) is the same bits under both forms and both tables; packed weights in {0, +-1/4, +-1/2} (through host_pack_conv); dscale signed
+    powers of two; shift / bias / res dyadic.  Then the accumulator is exact in every order and v = acc d + bias + shift (+ res) is exact in
+    fp32, contracted or not: want = fp16(v), one rounding.  final: want = the exact fp32 v [B,3,H,W] — the output is tanhf of it — and the
+    weights are sparse enough that at least half of the values have |v| <= 2.  Every premise is asserted."""
+    from fir_ops_ref import assert_order_free, lattice_weights, pow2, quantum
+    rng = np.random.default_rng([seed, impl, B, H, W, Cin, Cout, len(form)])
+    KS = 1 if form in ("conv0", "conv3") else 3
+    f32, f64 = np.float32, np.float64
+    inp = dict(B=B, stride=1, pad=KS // 2, out_scale=1.0, batch_size=1, act=0, form=form, impl=impl)
+    inp["x"] = (rng.integers(-4, 5, (B, H, W, Cin)) / 4.0).astype(f32)
+    w = lattice_weights(rng, (Cout, Cin, KS, KS), [0, 0.25, -0.25, 0.5, -0.5], Cin * KS * KS)
+    if form == "final":                                                        # sparse: tanh must not saturate
+        w = w * (rng.random(w.shape) < 12.0 / (Cin * KS * KS))
+        assert np.array_equal(np.abs(_pack(w)) > 0, np.abs(w.transpose(2, 3, 0, 1).reshape(KS * KS, Cout, Cin)) > 0)
+    inp["w"] = w.astype(f32)
+    family = FAMILY_OF_IMPL[impl]
+    fam_form, table, _ = KERNELS[family]
+    if form in ("conv0", "final"):
+        inp["sn"] = pow2(rng, (B, Cin), [-1, 0, 1])
+        inp["pre_shift"] = (rng.integers(-8, 9, (B, Cin)) / 8.0).astype(f32)
+        want_a = np.maximum(inp["x"].astype(f64) * inp["sn"].astype(f64)[:, None, None, :] + inp["pre_shift"].astype(f64)[:, None, None, :], 0.0)
+        for tb in ("sn", "sn16"):
+            for pf in PRE_FORMS:
+                assert np.array_equal(pre_affine(inp["x"], inp["sn"], inp["pre_shift"], tb, pf), want_a), "lattice: relu(x A + S) depends on the form"
+    if form in ("conv0", "conv1", "conv2"):
+        inp["dscale"] = pow2(rng, (B, Cout), [-1, 0, 1])
+        inp["shift"] = (rng.integers(-32, 33, (B, Cout)) / 16.0).astype(f32)
+        inp["act"], inp["in_up"] = 2, bool(up)
+    if form == "conv3":
+        inp["bias"] = (rng.integers(-32, 33, Cout) / 16.0).astype(f32)
+        rcs = res_mult * Cout
+        inp["res"] = ((rng.integers(-8, 9, (B, H >> res_up, W >> res_up, rcs)) + 4 * np.arange(B)[:, None, None, None]) / 4.0).astype(f32)
+        inp["res_cs"], inp["res_up"] = (rcs if res_mult > 1 else 0), bool(res_up)
+    if form == "final":               # a bias of 14 fractional bits: v needs more than fp16's 11 bits, so tanhf(fp16(v)) shows
+        inp["bias"] = (rng.integers(-8192, 8193, Cout) / 16384.0).astype(f32)
+        inp["rgb_tanh"] = True
+    a, b, demod = operands(inp, fam_form, table)
+    name = "bg lattice %s impl %d" % (form, impl)
+    acc = assert_order_free(name, _conv, a, b, KS, 1, KS // 2)
+    A = _conv(np.abs(a), np.abs(b), KS, 1, KS // 2, torch.float64)
+    d = inp["dscale"].astype(f64)[:, None, None, :] if demod else np.ones((1, 1, 1, 1))
+    bb = (inp["bias"].astype(f64) if inp.get("bias") is not None else 0.0) + (inp["shift"].astype(f64)[:, None, None, :] if inp.get("shift") is not None else 0.0)
+    bb = np.broadcast_to(bb, acc.shape)
+    r = residual(inp)
+    r = np.zeros((1, 1, 1, 1)) if r is None else r.astype(f64)
+    q = min(quantum(acc) * float(np.abs(d).min()), quantum(bb), quantum(r))
+    P = A * np.abs(d) + np.abs(bb) + np.abs(r)
+    assert P.max() < 2.0 ** 24 * q, "%s: |acc d| + |bias + shift| + |res| reaches %.3g, v is exact below 2^24 q = %.3g" % (name, P.max(), 2.0 ** 24 * q)
+    v = acc * d + bb
+    v = (np.maximum(v, 0.0) if inp["act"] == 2 else v) + r
+    assert np.array_equal(v, v.astype(f32).astype(f64)) and np.abs(v).max() < 65504
+    if form == "final":
+        v = np.ascontiguousarray(v[..., :3].transpose(0, 3, 1, 2))
+        assert (v != h16(v)).mean() >= 0.25, "%s: v fits fp16 almost everywhere: a tanh of the rounded value would not show" % name
+        assert (np.abs(v) <= 2.0).mean() >= 0.5, "%s: tanh saturates on more than half of the pixels (%.2f within 2)" % (name, (np.abs(v) <= 2.0).mean())
+        return inp, v
+    return inp, h16(v)
+
+
+# the lattice runs of test_gpu_biggan_ops.py: one per conv form and family reached
+BG_LATTICE = ("conv0 tiled 8x32", "conv0 direct 8x8", "conv0 gemm 4x4", "conv1 tiled up 32", "conv1 gemm up 64", "conv2 glds<16>", "conv2 glds<32>",
+              "conv2 stream", "conv2 tiled", "conv3 tiled res_cs 128 up1", "conv3 gemm res_cs 128 up1", "conv3 direct res_cs 128 up1", "final tanh 8x32")
